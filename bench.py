@@ -19,6 +19,20 @@ N > 1: one process per GPU; the 1000 images shard contiguously over the ranks
 (strong scaling, as BASELINE.json configs[4] names it), each rank runs the full
 network on its shard and one RCCL all-gather collects the logits.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline
+(images/sec, ms_per_step).  --full adds everything else this script measures or
+checks: HIP events sampled in the timed region, the other step discipline, the
+per-kernel breakdown and roofline, the PCIe-inclusive rate, the FP32 path, the
+CPU oracle baseline and logit parity against it.
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
+
+--dump-outputs DIR writes what the last timed step returned (rank 0's gathered
+logits, float32, and the host top-1 classes) as DIR/logits.npy and
+DIR/top1_class.npy; weights and inputs are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -41,7 +55,7 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1000, help="global batch (images per step over all GPUs)")
     ap.add_argument("--network", default="alexnet")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline and parity")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the oracle baseline sample")
     ap.add_argument("--force-dist", action="store_true", help="take the torch.distributed path even with one rank")
     ap.add_argument("--weak", action="store_true",
@@ -52,7 +66,15 @@ def parse():
                          "shard is at most 256 images, where the eager forward is launch-bound")
     ap.add_argument("--sync-steps", action="store_true",
                     help="read every batch's logits before launching the next batch (no software pipeline)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (untimed passes, per-kernel "
+                         "breakdown, roofline, PCIe rate, FP32 path, CPU baseline, parity); off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's logits and top-1 classes to DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def main():
@@ -208,7 +230,8 @@ def main():
     run_steps(args.warmup, pipelined)
     barrier()
     torch.cuda.synchronize()
-    if rank == 0 and not os.environ.get("I8IE_BENCH_NO_EVENTS") and graphed is None:
+    sample_events = args.full and rank == 0 and not os.environ.get("I8IE_BENCH_NO_EVENTS") and graphed is None
+    if sample_events:
         # HIP events around contraction-kernel launches, on the stream the kernels run on.  Every event
         # packet costs a few microseconds of stream time (bracketing all 9 contraction launches of a step:
         # ~5 % of the step), so the timed region brackets every 5th contraction launch -- coprime with the
@@ -219,27 +242,30 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
-    prof = cx.profile_stop() if (rank == 0 and graphed is None and not os.environ.get("I8IE_BENCH_NO_EVENTS")) else {}
-    # untimed: the same batches with the other step discipline, for the record
-    barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    run_steps(args.steps, not pipelined)
-    torch.cuda.synchronize()
-    barrier()
-    other_ms = (time.perf_counter() - t1) / args.steps * 1e3
-    mode["eager"] = True  # the per-kernel breakdown needs individual launches: graph replays are not bracketed
-    if rank == 0:  # untimed pass with every launch bracketed: the per-kernel breakdown
-        cx.profile_start(mfma_only=False)
-        run_steps(args.steps, pipelined)
-        full = cx.profile_stop()
-    else:
-        run_steps(args.steps, pipelined)  # keep the collectives matched
-    mode["eager"] = False
+    prof = cx.profile_stop() if sample_events else {}
+    # the last timed step's logits (rank 0), kept apart from the untimed passes below
+    last_logits = None if state["logits"] is None else np.array(state["logits"], np.float32)
+    if args.full:
+        # untimed: the same batches with the other step discipline, for the record
+        barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        run_steps(args.steps, not pipelined)
+        torch.cuda.synchronize()
+        barrier()
+        other_ms = (time.perf_counter() - t1) / args.steps * 1e3
+        mode["eager"] = True  # the per-kernel breakdown needs individual launches: graph replays are not bracketed
+        if rank == 0:  # untimed pass with every launch bracketed: the per-kernel breakdown
+            cx.profile_start(mfma_only=False)
+            run_steps(args.steps, pipelined)
+            full = cx.profile_stop()
+        else:
+            run_steps(args.steps, pipelined)  # keep the collectives matched
+        mode["eager"] = False
     # ---- untimed: PCIe-inclusive rate.  The FP32 batch starts in pinned host memory, its upload runs on the
     # transfer stream beside the kernels of the batch before (two pinned buffers, two device blocks).
     pcie = None
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         pin = [i8ie.pinned_empty(x_loc.shape) for _ in range(2)]
         for b in pin:
             b[...] = x_loc
@@ -278,135 +304,142 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = n_total * args.steps / elapsed
 
-    # ---- roofline of the dominant kernel (by device time) --------------------------------------
-    def table(raw):
-        return {k: {"launches": int(v[0]), "ms": v[1], "ops": v[2], "bytes": v[3]} for k, v in raw.items()}
+    if args.dump_outputs:  # what a caller of the timed path receives from its last step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), last_logits)
+        np.save(os.path.join(args.dump_outputs, "top1_class.npy"),
+                sharding.centred_argmax(last_logits, centre).astype(np.float32))
 
-    def by_kernel(shapes):  # entries are "kernel|shape": group by kernel
-        out = {}
-        for k, v in shapes.items():
-            e = out.setdefault(k.split("|")[0], {"launches": 0, "ms": 0.0, "ops": 0.0, "bytes": 0.0})
-            for f in e:
-                e[f] += v[f]
-        return out
+    if args.full:
+        # ---- roofline of the dominant kernel (by device time) --------------------------------------
+        def table(raw):
+            return {k: {"launches": int(v[0]), "ms": v[1], "ops": v[2], "bytes": v[3]} for k, v in raw.items()}
 
-    per_shape = table(full)                 # untimed pass: every launch of every kernel bracketed
-    kernels = by_kernel(per_shape)
-    timed = by_kernel(table(prof)) if prof else kernels  # timed region: sampled contraction launches
-    mfma = {k: v for k, v in kernels.items() if v["ops"] > 0}
-    dom = max(mfma, key=lambda k: mfma[k]["ms"])
-    d = timed.get(dom, mfma[dom])
-    achieved = d["ops"] / (d["ms"] * 1e-3) / 1e12
-    # HBM bytes per launch of the dominant kernel: rocprofv3 PMC passes are collected offline (counter collection
-    # serialises every dispatch) and committed with the commit they were taken at; used only when they describe
-    # this kernel at this workload, otherwise null
-    traffic, traffic_meta = None, None
-    for cand in ("r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", cand)))
-            if tj.get("kernel") == dom and n_total == 1000 and world == 1 and name == "alexnet":
-                traffic = tj["hbm_bytes_per_launch"]
-                traffic_meta = {"file": "profiles/" + cand, "source": tj.get("source"), "collected_at_commit": tj.get("commit"),
-                                "algorithmic_bytes_per_launch": tj.get("algorithmic_bytes_per_launch")}
-                break
-        except (OSError, ValueError, KeyError):
-            pass
-    roofline = {
-        "bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": INT8_DENSE_PEAK_TOPS,
-        "unit": "TOP/s", "frac": round(achieved / INT8_DENSE_PEAK_TOPS, 4), "traffic": traffic,
-        "traffic_provenance": traffic_meta,
-        "ops_per_launch": d["ops"] / d["launches"], "avg_launch_ms": round(d["ms"] / d["launches"], 4),
-        "launches_per_step": mfma[dom]["launches"] / args.steps,
-        "launches_timed": d["launches"], "timed_in": "the timed region (every 5th contraction launch bracketed)" if prof else "untimed pass",
-        "avg_launch_ms_untimed_pass_all_launches": round(mfma[dom]["ms"] / mfma[dom]["launches"], 4),
-    }
-    # NOT measured by this run: constants from committed profiles, kept apart from the measured fields above
-    static_context = {
-        "note": "constants from earlier measurements on MI355X, for reading `roofline`; nothing here is measured by this run",
-        "register_only_int8_mfma_tops": {"random_operands": 3400.0, "constant_operands": 4860.0,
-                                         "source": "profiles/r01h_mfma_peak_and_power.txt (tools/mfma_peak.hip)"},
-        "in_kernel_clock_mhz_contraction_kernels_random_operands": {"range": [1880, 2174], "median": 2061, "nominal": 2400,
-                                                                    "source": "profiles/r02_inkernel_clock.txt (s_memtime / s_memrealtime stamps, csrc/i8ie_pp.hip diagnostic builds)"},
-    }
-    total_dev_ms = sum(v["ms"] for v in kernels.values())
-    breakdown = {k: round(v["ms"] / args.steps, 4) for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms"])}
-    per_layer = {k: {"ms": round(v["ms"] / args.steps, 4),
-                     "tops": round(v["ops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["ops"] else None,
-                     "gbps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)}
-                 for k, v in sorted(per_shape.items(), key=lambda kv: -kv[1]["ms"])}
-    macs = wl.macs_per_image(name)
-    whole = {"int8_tops_whole_step": round(value * macs * 2 / 1e12, 2),
-             "frac_of_int8_peak_whole_step": round(value * macs * 2 / 1e12 / INT8_DENSE_PEAK_TOPS, 4),
-             "device_ms_per_step": round(total_dev_ms / args.steps, 3)}
+        def by_kernel(shapes):  # entries are "kernel|shape": group by kernel
+            out = {}
+            for k, v in shapes.items():
+                e = out.setdefault(k.split("|")[0], {"launches": 0, "ms": 0.0, "ops": 0.0, "bytes": 0.0})
+                for f in e:
+                    e[f] += v[f]
+            return out
 
-    # ---- CPU baseline: the oracle (C restatement of the reference algorithm) on the host cores --
-    cpu = None
-    parity = None
-    if world == 1 and not args.no_cpu_baseline:
-        import orc
-        import pipeline
+        per_shape = table(full)                 # untimed pass: every launch of every kernel bracketed
+        kernels = by_kernel(per_shape)
+        timed = by_kernel(table(prof)) if prof else kernels  # timed region: sampled contraction launches
+        mfma = {k: v for k, v in kernels.items() if v["ops"] > 0}
+        dom = max(mfma, key=lambda k: mfma[k]["ms"])
+        d = timed.get(dom, mfma[dom])
+        achieved = d["ops"] / (d["ms"] * 1e-3) / 1e12
+        # HBM bytes per launch of the dominant kernel: rocprofv3 PMC passes are collected offline (counter collection
+        # serialises every dispatch) and committed with the commit they were taken at; used only when they describe
+        # this kernel at this workload, otherwise null
+        traffic, traffic_meta = None, None
+        for cand in ("r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):
+            try:
+                tj = json.load(open(os.path.join(ROOT, "profiles", cand)))
+                if tj.get("kernel") == dom and n_total == 1000 and world == 1 and name == "alexnet":
+                    traffic = tj["hbm_bytes_per_launch"]
+                    traffic_meta = {"file": "profiles/" + cand, "source": tj.get("source"), "collected_at_commit": tj.get("commit"),
+                                    "algorithmic_bytes_per_launch": tj.get("algorithmic_bytes_per_launch")}
+                    break
+            except (OSError, ValueError, KeyError):
+                pass
+        roofline = {
+            "bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": INT8_DENSE_PEAK_TOPS,
+            "unit": "TOP/s", "frac": round(achieved / INT8_DENSE_PEAK_TOPS, 4), "traffic": traffic,
+            "traffic_provenance": traffic_meta,
+            "ops_per_launch": d["ops"] / d["launches"], "avg_launch_ms": round(d["ms"] / d["launches"], 4),
+            "launches_per_step": mfma[dom]["launches"] / args.steps,
+            "launches_timed": d["launches"], "timed_in": "the timed region (every 5th contraction launch bracketed)" if prof else "untimed pass",
+            "avg_launch_ms_untimed_pass_all_launches": round(mfma[dom]["ms"] / mfma[dom]["launches"], 4),
+        }
+        # NOT measured by this run: constants from committed profiles, kept apart from the measured fields above
+        static_context = {
+            "note": "constants from earlier measurements on MI355X, for reading `roofline`; nothing here is measured by this run",
+            "register_only_int8_mfma_tops": {"random_operands": 3400.0, "constant_operands": 4860.0,
+                                             "source": "profiles/r01h_mfma_peak_and_power.txt (tools/mfma_peak.hip)"},
+            "in_kernel_clock_mhz_contraction_kernels_random_operands": {"range": [1880, 2174], "median": 2061, "nominal": 2400,
+                                                                        "source": "profiles/r02_inkernel_clock.txt (s_memtime / s_memrealtime stamps, csrc/i8ie_pp.hip diagnostic builds)"},
+        }
+        total_dev_ms = sum(v["ms"] for v in kernels.values())
+        breakdown = {k: round(v["ms"] / args.steps, 4) for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms"])}
+        per_layer = {k: {"ms": round(v["ms"] / args.steps, 4),
+                         "tops": round(v["ops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["ops"] else None,
+                         "gbps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)}
+                     for k, v in sorted(per_shape.items(), key=lambda kv: -kv[1]["ms"])}
+        macs = wl.macs_per_image(name)
+        whole = {"int8_tops_whole_step": round(value * macs * 2 / 1e12, 2),
+                 "frac_of_int8_peak_whole_step": round(value * macs * 2 / 1e12 / INT8_DENSE_PEAK_TOPS, 4),
+                 "device_ms_per_step": round(total_dev_ms / args.steps, 3)}
 
-        # a 1-GPU box gives this job a 16-CPU share; libgomp is already initialised (torch), so set it by call
-        orc.set_num_threads(int(os.environ.get("OMP_NUM_THREADS", min(len(os.sched_getaffinity(0)), 16))))
+        # ---- CPU baseline: the oracle (C restatement of the reference algorithm) on the host cores --
+        cpu = None
+        parity = None
+        if world == 1 and not args.no_cpu_baseline:
+            import orc
+            import pipeline
 
-        entry = wl.NETWORKS[name]
-        qlayers = pipeline.quantize_layers(entry, sd)
-        probe = min(8, n_total)
-        tp = time.perf_counter()
-        pipeline.forward(entry, x_all[:probe], qlayers, qparams)
-        rate = probe / (time.perf_counter() - tp)
-        sample = int(max(probe, min(n_total, rate * args.cpu_seconds)))
-        passes = 0
-        tp = time.perf_counter()
-        while True:  # whole passes over the sample until ~cpu_seconds of CPU work (at most 8 passes)
-            ref_logits = pipeline.forward(entry, x_all[:sample], qlayers, qparams)
-            passes += 1
-            cpu_s = time.perf_counter() - tp
-            if passes >= 8 or cpu_s * (passes + 1) / passes > args.cpu_seconds:
-                break
-        cpu = {"value": round(sample * passes / cpu_s, 2), "unit": "images/sec", "cores": orc.num_threads(), "kind": "port",
-               "sample": "%d pass(es) over %d of the %d images of the same batch, full network, %.1f s"
-                         % (passes, sample, n_total, cpu_s),
-               "host": open("/proc/cpuinfo").read().split("model name")[1].split("\n")[0].strip(": \t")}
-        # ---- the same baseline with the reference's own GEMM provider (Intel MKL cblas_gemm_s8u8s32) when its
-        # runtime is on this host and exact here; in a clean process, on a bounded sample (oracle/cpu_baseline_worker.py)
-        try:
-            import subprocess
-            import tempfile
+            # a 1-GPU box gives this job a 16-CPU share; libgomp is already initialised (torch), so set it by call
+            orc.set_num_threads(int(os.environ.get("OMP_NUM_THREADS", min(len(os.sched_getaffinity(0)), 16))))
 
-            k_mkl = int(min(sample, 400))
-            blob = {"entry_json": np.asarray(json.dumps([entry[0], entry[1], list(entry[2])])), "x": x_all[:k_mkl],
-                    "ref_logits": ref_logits[:k_mkl]}
-            for a, (qw_, qb_, sw_) in qlayers.items():
-                blob[a + "__qw"], blob[a + "__qb"], blob[a + "__sw"] = qw_, qb_, np.float32(sw_)
-                blob[a + "__qp"] = np.asarray([qparams[a][0], qparams[a][1]], np.float64)
-            with tempfile.TemporaryDirectory() as td:
-                np.savez(os.path.join(td, "in.npz"), **blob)
-                env = dict(os.environ, MKL_THREADING_LAYER="GNU", OMP_NUM_THREADS=str(orc.num_threads()))
-                subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "cpu_baseline_worker.py"),
-                                os.path.join(td, "in.npz"), os.path.join(td, "out.json"), str(orc.num_threads()),
-                                str(min(8.0, args.cpu_seconds * 0.5))], check=True, timeout=180, env=env,
-                               stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-                mk = json.load(open(os.path.join(td, "out.json")))
-        except Exception as e:  # the MKL leg is optional: never let it take the bench line down
-            mk = {"provider": None, "error": type(e).__name__}
-        cpu["gemm"] = "own AVX-512/AVX2 loop (oracle/i8ie_oracle.c)"
-        cpu["with_reference_gemm_provider"] = mk
-        if mk.get("provider") and mk.get("logits_bit_exact_vs_own_kernel") and mk["images_per_sec"] > cpu["value"]:
-            # the reference calls exactly this routine; where it is also the faster one (Intel hosts) it is the
-            # headline baseline.  (On the AMD hosts of the MI355X boxes MKL 2021.4 takes a generic path ~10x slower
-            # than the oracle's own VNNI loop, so the own loop stays the stronger, reported baseline there.)
-            cpu["value_own_gemm"] = cpu["value"]
-            cpu["value"] = mk["images_per_sec"]
-            cpu["gemm"] = "Intel MKL cblas_gemm_s8u8s32, the reference's provider (%s)" % mk["provider"][:70]
-            cpu["sample"] = "%d pass(es) over %d of the %d images of the same batch, full network, %.1f s" % (
-                mk["passes"], mk["images"], n_total, mk["seconds"])
-        got = state["logits"][:sample]
-        t_gpu = float((sharding.centred_argmax(got, centre) == lab_all[:sample]).mean())
-        t_cpu = float((sharding.centred_argmax(ref_logits, centre) == lab_all[:sample]).mean())
-        parity = {"logits_bit_exact_vs_oracle": bool(np.array_equal(got.view(np.uint32), ref_logits.view(np.uint32))),
-                  "top1_vs_fp32_teacher_gpu": round(t_gpu, 4), "top1_vs_fp32_teacher_cpu_oracle": round(t_cpu, 4),
-                  "top1_delta": round(abs(t_gpu - t_cpu), 6), "images_compared": sample}
+            entry = wl.NETWORKS[name]
+            qlayers = pipeline.quantize_layers(entry, sd)
+            probe = min(8, n_total)
+            tp = time.perf_counter()
+            pipeline.forward(entry, x_all[:probe], qlayers, qparams)
+            rate = probe / (time.perf_counter() - tp)
+            sample = int(max(probe, min(n_total, rate * args.cpu_seconds)))
+            passes = 0
+            tp = time.perf_counter()
+            while True:  # whole passes over the sample until ~cpu_seconds of CPU work (at most 8 passes)
+                ref_logits = pipeline.forward(entry, x_all[:sample], qlayers, qparams)
+                passes += 1
+                cpu_s = time.perf_counter() - tp
+                if passes >= 8 or cpu_s * (passes + 1) / passes > args.cpu_seconds:
+                    break
+            cpu = {"value": round(sample * passes / cpu_s, 2), "unit": "images/sec", "cores": orc.num_threads(), "kind": "port",
+                   "sample": "%d pass(es) over %d of the %d images of the same batch, full network, %.1f s"
+                             % (passes, sample, n_total, cpu_s),
+                   "host": open("/proc/cpuinfo").read().split("model name")[1].split("\n")[0].strip(": \t")}
+            # ---- the same baseline with the reference's own GEMM provider (Intel MKL cblas_gemm_s8u8s32) when its
+            # runtime is on this host and exact here; in a clean process, on a bounded sample (oracle/cpu_baseline_worker.py)
+            try:
+                import subprocess
+                import tempfile
+
+                k_mkl = int(min(sample, 400))
+                blob = {"entry_json": np.asarray(json.dumps([entry[0], entry[1], list(entry[2])])), "x": x_all[:k_mkl],
+                        "ref_logits": ref_logits[:k_mkl]}
+                for a, (qw_, qb_, sw_) in qlayers.items():
+                    blob[a + "__qw"], blob[a + "__qb"], blob[a + "__sw"] = qw_, qb_, np.float32(sw_)
+                    blob[a + "__qp"] = np.asarray([qparams[a][0], qparams[a][1]], np.float64)
+                with tempfile.TemporaryDirectory() as td:
+                    np.savez(os.path.join(td, "in.npz"), **blob)
+                    env = dict(os.environ, MKL_THREADING_LAYER="GNU", OMP_NUM_THREADS=str(orc.num_threads()))
+                    subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "cpu_baseline_worker.py"),
+                                    os.path.join(td, "in.npz"), os.path.join(td, "out.json"), str(orc.num_threads()),
+                                    str(min(8.0, args.cpu_seconds * 0.5))], check=True, timeout=180, env=env,
+                                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+                    mk = json.load(open(os.path.join(td, "out.json")))
+            except Exception as e:  # the MKL leg is optional: never let it take the bench line down
+                mk = {"provider": None, "error": type(e).__name__}
+            cpu["gemm"] = "own AVX-512/AVX2 loop (oracle/i8ie_oracle.c)"
+            cpu["with_reference_gemm_provider"] = mk
+            if mk.get("provider") and mk.get("logits_bit_exact_vs_own_kernel") and mk["images_per_sec"] > cpu["value"]:
+                # the reference calls exactly this routine; where it is also the faster one (Intel hosts) it is the
+                # headline baseline.  (On the AMD hosts of the MI355X boxes MKL 2021.4 takes a generic path ~10x slower
+                # than the oracle's own VNNI loop, so the own loop stays the stronger, reported baseline there.)
+                cpu["value_own_gemm"] = cpu["value"]
+                cpu["value"] = mk["images_per_sec"]
+                cpu["gemm"] = "Intel MKL cblas_gemm_s8u8s32, the reference's provider (%s)" % mk["provider"][:70]
+                cpu["sample"] = "%d pass(es) over %d of the %d images of the same batch, full network, %.1f s" % (
+                    mk["passes"], mk["images"], n_total, mk["seconds"])
+            got = state["logits"][:sample]
+            t_gpu = float((sharding.centred_argmax(got, centre) == lab_all[:sample]).mean())
+            t_cpu = float((sharding.centred_argmax(ref_logits, centre) == lab_all[:sample]).mean())
+            parity = {"logits_bit_exact_vs_oracle": bool(np.array_equal(got.view(np.uint32), ref_logits.view(np.uint32))),
+                      "top1_vs_fp32_teacher_gpu": round(t_gpu, 4), "top1_vs_fp32_teacher_cpu_oracle": round(t_cpu, 4),
+                      "top1_delta": round(abs(t_gpu - t_cpu), 6), "images_compared": sample}
 
     out = {
         "metric": "images/sec %s-INT8 %dx%d bs=%d" % (("AlexNet" if name == "alexnet" else name,) + wl.NETWORKS[name][2][1:] + (n_total,)),
@@ -416,8 +449,12 @@ def main():
         "config": {"workload": "%s INT8 forward + top-1, %dx%dx%d input, global batch %d sharded over %d GPU(s)"
                    % ((name,) + wl.NETWORKS[name][2] + (n_total, world)),
                    "global_batch": n_total, "per_gpu_batch": stop - start, "parallelism": "batch-shard x%d + logits all-gather" % world},
-        "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "whole_step": whole, "static_context": static_context,
-        "kernel_ms_per_step": breakdown, "per_launch_shape": per_layer, "top1_vs_fp32_teacher": round(state["correct"] / n_total, 4),
+    }
+    if args.full:
+        out.update({"roofline": roofline, "cpu_baseline": cpu, "parity": parity, "whole_step": whole, "static_context": static_context,
+                    "kernel_ms_per_step": breakdown, "per_launch_shape": per_layer})
+    out.update({
+        "top1_vs_fp32_teacher": round(state["correct"] / n_total, 4),
         "prewarm_steps_untimed": prewarm,
         **({"REHEARSAL": "all ranks on one GPU, gloo collectives on host copies: control flow only, not a measurement"}
            if rehearse else {}),
@@ -425,14 +462,17 @@ def main():
                         if graphed is not None else "eager launches"),
         "step_discipline": ("depth-2 software pipeline: batch i+1 is launched before batch i's logits are awaited"
                             if pipelined else "synchronous: logits of batch i read before batch i+1 is launched"),
-        ("ms_per_step_synchronous" if pipelined else "ms_per_step_pipelined"): round(other_ms, 4),
-        ("value_synchronous" if pipelined else "value_pipelined"): round(n_total / (other_ms * 1e-3), 1),
-        "h2d_ms_fp32_input_pageable_blocking": round(h2d_ms, 2),
-        "pcie_inclusive": pcie,
-        "fp32_engine_path": {"images_per_sec": round((stop - start) / (fp32_ms * 1e-3), 1), "ms": round(fp32_ms, 1),
-                             "how": "one forward of this rank's shard through the FP32 layers (pre-convert path: "
-                                    "Conv2d / Linear on v_mfma_f32_32x32x2_f32), input resident, logits read back"},
-    }
+    })
+    if args.full:
+        out.update({
+            ("ms_per_step_synchronous" if pipelined else "ms_per_step_pipelined"): round(other_ms, 4),
+            ("value_synchronous" if pipelined else "value_pipelined"): round(n_total / (other_ms * 1e-3), 1),
+            "h2d_ms_fp32_input_pageable_blocking": round(h2d_ms, 2),
+            "pcie_inclusive": pcie,
+            "fp32_engine_path": {"images_per_sec": round((stop - start) / (fp32_ms * 1e-3), 1), "ms": round(fp32_ms, 1),
+                                 "how": "one forward of this rank's shard through the FP32 layers (pre-convert path: "
+                                        "Conv2d / Linear on v_mfma_f32_32x32x2_f32), input resident, logits read back"},
+        })
     print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

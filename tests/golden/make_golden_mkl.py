@@ -11,12 +11,15 @@ with the reference's argument pattern
                        M, N, K, alpha = 1, A (u8, lda = K), ao = 0, B (s8, ldb = K), bo = 0,
                        beta = 0, C (s32, ldc = N), oc)
 
-on seeded operands and stores inputs + outputs as a small .npz fixture (data only).  Generated on an Intel
-VNNI host, where this MKL's integer arithmetic is exact; the fixture is what travels.
+on seeded operands and stores inputs + outputs as a small .npz fixture (data only), and MKL's outputs for the
+seeded operands of test_oracle_golden.py::test_contraction_against_live_mkl_when_present as a second one
+(mkl_gemm_seed9.npz).  Generated on an Intel VNNI host, where this MKL's integer arithmetic is exact; the
+fixtures are what travels.
 
 usage:  MKL_THREADING_LAYER=GNU python tests/golden/make_golden_mkl.py
 """
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -74,6 +77,35 @@ def main():
     flat["provider"] = np.asarray(buf.value.decode().strip())
     np.savez_compressed(os.path.join(HERE, "mkl_gemm_s8u8s32.npz"), **flat)
     print("mkl_gemm_s8u8s32.npz", len(cases), "cases from", buf.value.decode().strip())
+    live_seed9(flat["provider"])
+
+
+LIVE_SHAPES = ((17, 363, 20), (40, 4096, 10), (3, 800, 500))  # (M, K, N) of test_contraction_against_live_mkl_when_present
+
+
+def seed9_operands():
+    """The operands test_contraction_against_live_mkl_when_present draws, in its order."""
+    rng = np.random.default_rng(9)
+    for M, K, N in LIVE_SHAPES:
+        A = rng.integers(0, 256, (M, K), dtype=np.uint8)
+        B = rng.integers(-128, 128, (N, K), dtype=np.int8)
+        oc = rng.integers(-50000, 50000, N).astype(np.int32)
+        yield A, B, oc
+
+
+def operands_sha256(A, B, oc):
+    return hashlib.sha256(A.tobytes() + B.tobytes() + oc.tobytes()).hexdigest()
+
+
+def live_seed9(provider):
+    """MKL's results for the seeded operands of the live test, without the operands (they are redrawn from the seed;
+    their digest is stored so that a changed random stream is caught instead of compared)."""
+    flat = {"n_cases": np.asarray(len(LIVE_SHAPES)), "provider": provider}
+    for i, (A, B, oc) in enumerate(seed9_operands()):
+        flat["%d_C" % i] = gemm(A, B, oc)
+        flat["%d_operands_sha256" % i] = np.asarray(operands_sha256(A, B, oc))
+    np.savez_compressed(os.path.join(HERE, "mkl_gemm_seed9.npz"), **flat)
+    print("mkl_gemm_seed9.npz", len(LIVE_SHAPES), "cases")
 
 
 if __name__ == "__main__":

@@ -189,24 +189,34 @@ def test_contraction_against_the_reference_gemm_provider(orc):
 
 
 def test_contraction_against_live_mkl_when_present(orc):
-    """Same check against MKL itself where its runtime is installed (this image: /opt/conda/lib).  Skipped when
-    absent, and on non-Intel hosts, where MKL may take a vpmaddubsw path that saturates in int16."""
+    """Same check against MKL itself on seeded operands: MKL's results for them are stored in
+    tests/golden/mkl_gemm_seed9.npz (tests/golden/make_golden_mkl.py), and where MKL's runtime is installed on an
+    Intel host (I8IE_MKL_RT) it is also called live and must agree with them.  Not called live on non-Intel hosts,
+    where MKL may take a vpmaddubsw path that saturates in int16."""
     import ctypes as C
+    import hashlib
     import os
 
     path = os.environ.get("I8IE_MKL_RT", "/opt/conda/lib/libmkl_rt.so.1")
-    if not os.path.exists(path) or "GenuineIntel" not in open("/proc/cpuinfo").read():
-        pytest.skip("no MKL runtime / not an Intel host")
-    os.environ.setdefault("MKL_THREADING_LAYER", "GNU")
-    mkl = C.CDLL(path, mode=C.RTLD_GLOBAL)
+    mkl = None
+    if os.path.exists(path) and "GenuineIntel" in open("/proc/cpuinfo").read():
+        os.environ.setdefault("MKL_THREADING_LAYER", "GNU")
+        mkl = C.CDLL(path, mode=C.RTLD_GLOBAL)
+    stored = load_cases("mkl_gemm_seed9.npz")
     rng = np.random.default_rng(9)
-    for M, K, N in ((17, 363, 20), (40, 4096, 10), (3, 800, 500)):
+    shapes = ((17, 363, 20), (40, 4096, 10), (3, 800, 500))
+    assert len(stored) == len(shapes)
+    for (M, K, N), want in zip(shapes, stored):
         A = rng.integers(0, 256, (M, K), dtype=np.uint8)
         B = rng.integers(-128, 128, (N, K), dtype=np.int8)
         oc = rng.integers(-50000, 50000, N).astype(np.int32)
-        Cm = np.empty((M, N), np.int32)
-        mkl.cblas_gemm_s8u8s32(101, 111, 112, 171, C.c_int(M), C.c_int(N), C.c_int(K), C.c_float(1.0),
-                               A.ctypes.data_as(C.c_void_p), C.c_int(K), C.c_int8(0), B.ctypes.data_as(C.c_void_p),
-                               C.c_int(K), C.c_int8(0), C.c_float(0.0), Cm.ctypes.data_as(C.c_void_p), C.c_int(N),
-                               oc.ctypes.data_as(C.c_void_p))
-        assert np.array_equal(orc.gemm_u8s8s32(A, B, oc), Cm)
+        # the fixture holds MKL's results, not the operands: they must be the operands it was made from
+        assert hashlib.sha256(A.tobytes() + B.tobytes() + oc.tobytes()).hexdigest() == str(want["operands_sha256"])
+        if mkl is not None:
+            Cm = np.empty((M, N), np.int32)
+            mkl.cblas_gemm_s8u8s32(101, 111, 112, 171, C.c_int(M), C.c_int(N), C.c_int(K), C.c_float(1.0),
+                                   A.ctypes.data_as(C.c_void_p), C.c_int(K), C.c_int8(0), B.ctypes.data_as(C.c_void_p),
+                                   C.c_int(K), C.c_int8(0), C.c_float(0.0), Cm.ctypes.data_as(C.c_void_p), C.c_int(N),
+                                   oc.ctypes.data_as(C.c_void_p))
+            assert np.array_equal(Cm, want["C"])
+        assert np.array_equal(orc.gemm_u8s8s32(A, B, oc), want["C"])

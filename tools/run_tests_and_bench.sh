@@ -1,9 +1,11 @@
-mkdir -p gpurun_out/$1
-python -m pytest tests -m gpu -x -q > gpurun_out/$1/tests.log 2>&1; echo "tests rc $?" >> gpurun_out/$1/tests.log; tail -4 gpurun_out/$1/tests.log
-python bench.py --steps 20 --warmup 5 > gpurun_out/$1/bench.json 2> gpurun_out/$1/bench.err
+# the GPU suite, then the full bench line: usage run_tests_and_bench.sh <out-dir>
+O=${1:?usage: run_tests_and_bench.sh <out-dir>}
+mkdir -p $O
+python -m pytest tests -m gpu -x -q > $O/tests.log 2>&1; echo "tests rc $?" >> $O/tests.log; tail -4 $O/tests.log
+python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 python - <<PY
 import json
-d=json.loads(open("gpurun_out/$1/bench.json").read().strip().splitlines()[-1])
+d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])
 print(d["value"], d["ms_per_step"], d["roofline"]["kernel"], d["roofline"]["frac"]); print(d["kernel_ms_per_step"])
 PY
-tail -2 gpurun_out/$1/bench.err
+tail -2 $O/bench.err
