@@ -61,24 +61,28 @@ int i8ie_sync(i8ie_ctx* ctx);
 /* I8IE_OPT_KERNEL_VARIANT = 2 selects among compiled variants of the contraction kernel (all
  * produce identical bytes; a tuning / A-B timing aid, 0 = default). */
 #define I8IE_OPT_KERNEL_VARIANT 2
-/* The values the product library understands (anything else behaves like 0; the diagnostic build of tools/diag
- * adds timing experiments under further numbers, listed in tools/README.md).  A value changes the one thing it
- * names: 3 and 5 also keep the tiled conv at 128 x 128 tiles (0 picks 192 x 128 for large launches), the others
- * leave the tiled kernel's own defaults alone. */
+/* The values the product library understands.  Anything else behaves like 0; the diagnostic build of tools/diag
+ * adds timing experiments under further numbers, listed in tools/README.md.  A value changes the one thing it names
+ * and leaves every other choice automatic.  A convolution with a max-pool or a re-biased layout (below) folds them
+ * into the patch-stationary kernel only where that kernel is tried and takes the launch; otherwise the pool and the
+ * re-bias run as launches of their own. */
 #define I8IE_VARIANT_AUTO 0            /* automatic selection per launch */
-#define I8IE_VARIANT_IGEMM_REGSTAGE 3  /* tiled contraction kernel, one LDS stage filled through registers (Linear's default) */
-#define I8IE_VARIANT_IGEMM_DMA 5       /* tiled contraction kernel, one LDS stage filled by LDS-DMA (the tiled conv default) */
-#define I8IE_VARIANT_TILED 11          /* tiled contraction kernel everywhere: no patch-stationary conv, split-K Linear, dot4 head */
+#define I8IE_VARIANT_IGEMM_REGSTAGE 3  /* conv: the tiled contraction kernel only, 128 x 128 tiles, one LDS stage filled through registers;
+                                          Linear: the tiled kernel where the many-row kernel would run */
+#define I8IE_VARIANT_IGEMM_DMA 5       /* conv: the tiled contraction kernel only, 128 x 128 tiles, one LDS stage filled by LDS-DMA;
+                                          Linear: where the tiled kernel runs, DMA staging (its default: registers) */
+#define I8IE_VARIANT_TILED 11          /* tiled contraction kernel everywhere: no patch-stationary conv, no first-stage kernel,
+                                          split-K Linear, classifier head without its MFMA form */
 #define I8IE_VARIANT_STEM_WHOLE 12     /* first-stage kernel (csrc/i8ie_stem.hip): whole images per block at any batch size (no parts) */
-#define I8IE_VARIANT_STEM_SIMD_ROLES 13 /* the same with its two wave roles on separate SIMDs (A/B of the placement: 8 % slower, profiles/r04_stem_roles.txt) */
-#define I8IE_VARIANT_PCONV 50          /* patch-stationary conv kernel (csrc/i8ie_pconv.hip) at any batch size */
+#define I8IE_VARIANT_STEM_SIMD_ROLES 13 /* first-stage kernel with its two wave roles on separate SIMDs (A/B of the placement: 8 % slower, profiles/r04_stem_roles.txt) */
+#define I8IE_VARIANT_PCONV 50          /* conv: patch-stationary kernel (csrc/i8ie_pconv.hip) at any batch size, else the tiled kernel */
 #define I8IE_VARIANT_PCONV_2PASS 54    /* the same, N = 384 as two passes of 192 and no 128-wide pass split */
-#define I8IE_VARIANT_TCONV 70          /* two-team patch-stationary conv kernel (csrc/i8ie_tconv.hip) wherever its shape rules allow */
+#define I8IE_VARIANT_TCONV 70          /* conv: two-team patch-stationary kernel (csrc/i8ie_tconv.hip) wherever its shape rules allow, else the tiled kernel */
 #define I8IE_VARIANT_FLIN 80           /* few-row Linear kernel (csrc/i8ie_flin.hip) below its automatic feature threshold */
+#define I8IE_VARIANT_FLIN_128 81       /* the same in its 128-row x 16-feature form at up to 128 rows (default above 64 rows: 64 x 32) */
 #define I8IE_VARIANT_MLIN 83           /* many-row Linear kernel (csrc/i8ie_mlin.hip) from 257 rows on and below its automatic feature threshold */
-#define I8IE_VARIANT_MLIN_64 84        /* many-row Linear kernel with 64-row block tiles (automatic where 128-row tiles give at most half the CUs a block) */
-#define I8IE_VARIANT_MLIN_128 85       /* many-row Linear kernel with 128-row block tiles at any row count above 256 */
-#define I8IE_VARIANT_FLIN_128 81       /* few-row Linear kernel in its 128-row x 16-feature form at up to 128 rows (default above 64 rows: 64 x 32) */
+#define I8IE_VARIANT_MLIN_64 84        /* the same with 64-row block tiles (automatic where 128-row tiles give at most half the CUs a block) */
+#define I8IE_VARIANT_MLIN_128 85       /* the same with 128-row block tiles at any row count above 256 */
 /* I8IE_OPT_PROFILE_STRIDE = 3: while profiling, bracket only every value-th eligible launch
  * (default 1 = all).  Event packets cost a few microseconds each on the stream; a stride that is
  * coprime with the launches per batch samples every kernel over a few batches. */

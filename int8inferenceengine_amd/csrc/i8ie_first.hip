@@ -463,7 +463,7 @@ int i8ie_first_launch(i8ie_ctx* ctx, const I8ieFirstCall& c) {
   // again (x 1.35), and 204 VGPRs leave two blocks per CU instead of three.  Kept as a tested opt-in.
 #if defined(I8IE_DIAG)
   static const bool fused_opt = std::getenv("I8IE_FIRST_FUSED") != nullptr;
-  const bool fuse = c.x != nullptr && (fused_opt || ctx->variant == 60);  // (variant 60: per-ctx switch for tests / A-B runs)
+  const bool fuse = c.x != nullptr && (fused_opt || ctx->pick.first_fused);  // (variant 60: per-ctx switch for tests / A-B runs)
 #else
   const bool fuse = false;
 #endif
@@ -478,7 +478,7 @@ int i8ie_first_launch(i8ie_ctx* ctx, const I8ieFirstCall& c) {
     if (blocks > 256 * 16) blocks = 256 * 16;
     bool vec = (c.w & 1) == 0 && (c.pad & 1) == 0 && c.w >= 4 && (reinterpret_cast<uintptr_t>(c.x) & 7u) == 0;
 #if defined(I8IE_DIAG)
-    if (ctx->variant == 61) vec = false;  // (the scalar-load form, for comparison)
+    if (ctx->pick.first_scalar) vec = false;  // (the scalar-load form, for comparison)
 #endif
     const float rs = 1.0f / c.q_scale;
     const uint32_t zp8 = (uint32_t)(c.q_zp & 0xFF);

@@ -192,7 +192,7 @@ int i8ie_flin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   a.relu_lo = c.relu ? c.zp_out : 0;
   a.out = c.out; a.acc = c.acc;
   const double ops = 2.0 * c.M * c.N * c.Ktrue, bytes = (double)c.M * c.Ktrue + (double)c.N * c.Ktrue + (double)c.M * c.N;
-  if (c.M <= 64 || (ctx->variant == 81 && c.M <= 128)) {  // (81: the 128-row form at any row count up to 128, for A/B runs)
+  if (c.M <= 64 || (ctx->pick.linear == I8IE_LIN_FLIN128 && c.M <= 128)) {  // (81: the 128-row form at any row count up to 128, for A/B runs)
     I8ieProfScope prof(ctx, "flin_128x16", ops, bytes);
     return flin_launch_t<8, 1, 4>(ctx, a, c.M, c.N);
   }

@@ -1011,30 +1011,29 @@ int launch_tile_var(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, d
 // conv2-5): one stage (half the LDS) lets a third wave per SIMD in, +10 % over the two-stage form; DMA
 // staging +3-6 % over register staging (VAR 3); loads two tiles ahead and s_setprio around the MFMAs
 // within 2 % of the baseline; the 256-row two-stage DMA form (VAR 7) 10-20 % slower on these K depths
-// ("what bounds the contraction kernel").  ctx->variant selects the others.
+// ("what bounds the contraction kernel").  ctx->pick.conv_tile / linear_tile select the others.
 template <int AMODE, bool BIAS, bool ACC>
 int launch_tile(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, double bytes) {
+  const int tile = AMODE == 1 ? ctx->pick.conv_tile : ctx->pick.linear_tile;
   if (AMODE == 1 && !BIAS && !ACC) {
 #if defined(I8IE_DIAG)  // tile-shape experiments, compiled into the diagnostic build only
-    if (ctx->variant == 10) return launch_tile_var<1, false, false, 0>(ctx, a, kbytes, ops, bytes);
-    if (ctx->variant == 6 && a.N <= 96 && a.N > 64)  // 256 x 96 tile, 4 waves of 64 x 96
+    if (tile == 10) return launch_tile_var<1, false, false, 0>(ctx, a, kbytes, ops, bytes);
+    if (tile == 6 && a.N <= 96 && a.N > 64)  // 256 x 96 tile, 4 waves of 64 x 96
       return launch_cfg<1, 4, 1, 2, 3, false, false, 3>(ctx, a, "igemm_conv_256x96", kbytes, ops, bytes);
-    if (ctx->variant == 4 && a.N % 256 == 0)  // 256 x 256 tile, 8 waves, two stages
+    if (tile == 4 && a.N % 256 == 0)  // 256 x 256 tile, 8 waves, two stages
       return launch_cfg<1, 2, 4, 4, 2, false, false, 0>(ctx, a, "igemm_conv_256x256", kbytes, ops, bytes);
-    if (ctx->variant == 8 && a.N > 64)  // 256 x 128, 4 waves of 128 x 64, one DMA stage
+    if (tile == 8 && a.N > 64)  // 256 x 128, 4 waves of 128 x 64, one DMA stage
       return launch_cfg<1, 2, 2, 4, 2, false, false, 5>(ctx, a, "igemm_conv_256x128", kbytes, ops, bytes);
-    if (ctx->variant == 9 && a.N > 128)  // 128 x 256, 4 waves of 64 x 128
+    if (tile == 9 && a.N > 128)  // 128 x 256, 4 waves of 64 x 128
       return launch_cfg<1, 2, 2, 2, 4, false, false, 5>(ctx, a, "igemm_conv_128x256", kbytes, ops, bytes);
 #endif
     // 192 x 128, 4 waves of 96 x 64, one DMA stage: 6.4 KB staged per MOP (128 x 128: 7.6) at three blocks
-    // per CU; measured 2.5-4 % faster than 128 x 128 on AlexNet conv2-5.  Only the variants that name a staging form or tile
-    // shape of THIS kernel (3, 5 and the diagnostic 4-10) switch it to 128 x 128; variants that select other kernels (12, 50,
-    // 54, 70, 80, 81 ...) leave the tiled kernel's default alone, so an A/B run with them changes one thing
-    const bool tile_variant = ctx->variant == 3 || ctx->variant == 5 || (ctx->variant >= 4 && ctx->variant <= 10);
-    if (!tile_variant && a.N > 64 && a.M >= 192 * 256)
+    // per CU; measured 2.5-4 % faster than 128 x 128 on AlexNet conv2-5.  A variant that names a staging form or tile
+    // shape of THIS kernel switches it to 128 x 128; the others leave the tiled kernel's default alone
+    if (tile == I8IE_TILE_DEFAULT && a.N > 64 && a.M >= 192 * 256)
       return launch_cfg<1, 2, 2, 3, 2, false, false, 5>(ctx, a, "igemm_conv_192x128", kbytes, ops, bytes);
 #if defined(I8IE_DIAG)
-    if (ctx->variant == 7 && a.N > 128 && (long)((a.M + 255) / 256) >= 256) {
+    if (tile == 7 && a.N > 128 && (long)((a.M + 255) / 256) >= 256) {
       // 4 waves of 128 x 128 or 128 x 96: whichever pads N less
       const int pad4 = (a.N + 255) / 256 * 256, pad3 = (a.N + 191) / 192 * 192;
       if (pad4 <= pad3) return launch_cfg<1, 2, 2, 4, 4, false, false, 7>(ctx, a, "igemm_conv_256x256", kbytes, ops, bytes);
@@ -1043,15 +1042,15 @@ int launch_tile(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, doubl
 #endif
   }
 #if defined(I8IE_DIAG)
-  if (AMODE == 0 && ctx->variant == 13 && a.ksplit <= 1)  // Linear, 128 x 128 tiles, two 64 KiB DMA stages, one block per CU
+  if (AMODE == 0 && tile == 17 && a.ksplit <= 1)  // Linear, 128 x 128 tiles, two 64 KiB DMA stages, one block per CU
     return launch_cfg<AMODE, 2, 2, 2, 2, BIAS, ACC, 7>(ctx, a, "igemm_lin_128x128_dma2", kbytes, ops, bytes);
-  if (AMODE == 0 && ctx->variant == 14 && a.ksplit <= 1)  // Linear, 128 x 128 tiles, one DMA stage
+  if (AMODE == 0 && tile == 14 && a.ksplit <= 1)  // Linear, 128 x 128 tiles, one DMA stage
     return launch_cfg<AMODE, 2, 2, 2, 2, BIAS, ACC, 5>(ctx, a, "igemm_lin_128x128_dma1", kbytes, ops, bytes);
-  if (AMODE == 0 && ctx->variant == 15 && a.ksplit <= 1)  // Linear, 128 x 128 tiles, register staging
+  if (AMODE == 0 && tile == 15 && a.ksplit <= 1)  // Linear, 128 x 128 tiles, register staging
     return launch_cfg<AMODE, 2, 2, 2, 2, BIAS, ACC, 3>(ctx, a, "igemm_lin_128x128_reg", kbytes, ops, bytes);
 #endif
   // Linear (few, short split-K slices per block) measured 20 % slower with DMA staging: register staging there
-  if (ctx->variant == 3 || (AMODE == 0 && ctx->variant != 5))
+  if (AMODE == 1 ? tile == I8IE_TILE_REG : tile != I8IE_TILE_DMA)
     return launch_tile_var<AMODE, BIAS, ACC, 3>(ctx, a, kbytes, ops, bytes);
   return launch_tile_var<AMODE, BIAS, ACC, 5>(ctx, a, kbytes, ops, bytes);
 }
@@ -1117,26 +1116,28 @@ int i8ie_igemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   // The persistent ping-pong kernel (i8ie_pp.hip) is opt-in (variant 20; 21-49 are its diagnostic builds): measured
   // on MI355X it trails the tiled kernel by 3-8 % on AlexNet conv2 / conv5 as long as activations need the u8 -> s8
   // xor in its MFMA slots ("what bounds the ping-pong kernel"), and it pads N = 384 to 512.
-  if (c.amode == 1 && ctx->variant >= 20 && ctx->variant < 50) {
+  if (c.amode == 1 && i8ie_conv_tries(ctx, I8IE_CONV_PP)) {
     const int took = i8ie_pp_try_launch(ctx, c);
     if (took != 0) return took < 0 ? took : I8IE_OK;
   }
 #endif
   // The two-team form of the patch-stationary kernel (i8ie_tconv.hip) comes first: it declines unless forced
   // (variant 70) or the launch is of the kind it measured faster on (one feature pass, >= 8 bands per CU).
-  if (c.amode == 1 && (i8ie_conv_variant_auto(ctx->variant) || (ctx->variant >= 70 && ctx->variant < 80))) {
+  if (c.amode == 1 && i8ie_conv_tries(ctx, I8IE_CONV_TCONV)) {
     const int took = i8ie_tconv_try_launch(ctx, c);
     if (took != 0) return took < 0 ? took : I8IE_OK;
   }
   // The patch-stationary kernel (i8ie_pconv.hip) takes the large convolutions it is built for (it declines the rest):
   // 2000-2280 TOP/s on AlexNet conv2-5 at 1000 images against 1790-1900 of the tiled kernel below (variant 11 forces
   // the tiled kernel, 50 forces this one at any batch size).
-  if (c.amode == 1 && (i8ie_conv_variant_auto(ctx->variant) || (ctx->variant >= 50 && ctx->variant < 60))) {
+  if (c.amode == 1 && i8ie_conv_tries(ctx, I8IE_CONV_PCONV)) {
     const int took = i8ie_pconv_try_launch(ctx, c);
     if (took != 0) return took < 0 ? took : I8IE_OK;
   }
-  // (the kernels below know neither the folded max-pool nor the re-biased layouts: callers ask i8ie_pconv_takes first)
-  I8IE_REQUIRE(!(c.amode == 1 && (i8ie_is_pool(c.pool_k, c.pool_s) || c.a_s8 || c.out_s8)), "igemm: pool / re-biased layout without the patch-stationary kernel");
+  // (the kernels below know neither the folded max-pool nor the re-biased layouts: a caller folds them only where
+  // i8ie_conv_tries(ctx, I8IE_CONV_PCONV) and i8ie_pconv_takes said yes, so reaching this is a probe / dispatch mismatch)
+  I8IE_REQUIRE(!(c.amode == 1 && (i8ie_is_pool(c.pool_k, c.pool_s) || c.a_s8 || c.out_s8)),
+               "igemm: pool / re-biased layout the patch-stationary kernel declined (probe / dispatch mismatch)");
   IgemmArgs a{};
   a.A = c.A;
   a.a_bytes = (unsigned)c.a_bytes;
@@ -1286,7 +1287,7 @@ int i8ie_launch_linear_smalln(i8ie_ctx* ctx, const I8ieSmallNCall& c) {
   I8ieProfScope prof(ctx, "linear_smalln_dot4", 2.0 * c.M * c.N * c.K, (double)c.M * c.K + (double)c.N * c.K + 5.0 * c.M * c.N);
   // (activation rows are lda = K bytes apart and the weights are zero from K to Kpad: a step past K multiplies
   // the next row's bytes, or the zeros the descriptor returns past the buffer, by zero)
-  if (c.K >= 1024 && c.Kpad % 64 == 0 && (size_t)16 * c.lda + c.Kpad < ((size_t)1 << 31) && ctx->variant != 11)
+  if (c.K >= 1024 && c.Kpad % 64 == 0 && (size_t)16 * c.lda + c.Kpad < ((size_t)1 << 31) && !ctx->pick.no_dot4_head)
     linear_head_mfma_kernel<<<(c.M + 15) / 16, 512, 0, ctx->stream>>>(a);
   else if (c.K >= 2048)
     linear_smalln_kernel<4><<<c.M, 256, 0, ctx->stream>>>(a);

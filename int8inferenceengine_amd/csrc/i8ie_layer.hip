@@ -250,6 +250,7 @@ int i8ie_ctx_set_option(i8ie_ctx* ctx, int option, int value) {
   }
   if (option == I8IE_OPT_KERNEL_VARIANT) {
     ctx->variant = value;
+    ctx->pick = i8ie_decode_variant(value);
     return I8IE_OK;
   }
   if (value)
@@ -505,17 +506,17 @@ int i8ie_layer_forward_dequant(i8ie_layer* L, const uint8_t* in, int in_layout, 
 
 // the first-stage kernel (i8ie_stem.hip) takes this conv layer at this output size (+ this pool behind it)?
 static bool stem_takes(const i8ie_layer* L, const ConvGeom& cg, int pool_k, int pool_s) {
-  return L->conv && L->path == PATH_B && L->Bstem != nullptr && !force_fallback(L->ctx) && L->ctx->variant != 11 &&
+  return L->conv && L->path == PATH_B && L->Bstem != nullptr && !force_fallback(L->ctx) && !L->ctx->pick.no_stem &&
          i8ie_stem_supported(cg.c, cg.stride, L->n, cg.kh, cg.kw, cg.oh, cg.ow, pool_k, pool_s) != 0;
 }
 
 // would the patch-stationary kernel (i8ie_pconv.hip) take this conv launch, with this pool folded in and these
-// re-biased layouts?  (it answers from the geometry and the batch; nothing is launched)
+// re-biased layouts?  (it answers from the kernel choice, the geometry and the batch, as the dispatcher will; nothing is launched)
 // (`out_border`: the border of the output the real call will write; the size limits of the kernel depend on it.  The layout
 // negotiation queries below do not know it yet and ask with 0: layer_forward_impl asks again with the real one and runs the
 // pool / the re-bias as launches of their own when the kernel then declines)
 static bool pconv_probe(i8ie_layer* L, const ConvGeom& cg, int m, int in_border, int pool_k, int pool_s, bool a_s8, bool out_s8, int out_border = 0) {
-  if (!L->conv || L->path != PATH_A || force_fallback(L->ctx)) return false;
+  if (!L->conv || L->path != PATH_A || force_fallback(L->ctx) || !i8ie_conv_tries(L->ctx, I8IE_CONV_PCONV)) return false;
   const int b = in_border > cg.pad ? in_border : cg.pad;
   I8ieIgemmCall q{};
   q.amode = 1; q.M = m * cg.oh * cg.ow; q.B = L->Bpack2; q.Kpad = L->Kpad2; q.Npad = L->Npad;
@@ -590,7 +591,7 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
     // opt-in ($I8IE_SKINNY=1): once the tiled split-K kernel wrote its partial tiles as row segments it became
     // the faster one even at m = 125 (fc6 + fc7: 33 us against 42 us), see DESIGN.md
     static const bool use_skinny = std::getenv("I8IE_SKINNY") != nullptr;
-    if (!force_fallback(ctx) && !need_pad && use_skinny && ctx->variant == 0 &&
+    if (!force_fallback(ctx) && !need_pad && use_skinny && ctx->pick.linear == I8IE_LIN_AUTO &&
         i8ie_skinny_plan(m, L->n, L->Kpad, &sk_steps, &sk_slices)) {
       // few input rows: activations' K slice resident in LDS, weights streamed once in fragment order
       const bool perm = panel == L->Bperm && L->Bperm != nullptr;
@@ -616,21 +617,24 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
       return I8IE_OK;
     }
     I8ieIgemmCall c{};
-    // few rows: the one-launch kernel of i8ie_flin.hip (variant 11 keeps the tiled split-K kernel, for comparison)
-    const bool flin = !need_pad && ctx->variant != 11 && L->K % 16 == 0 && i8ie_flin_wants(m, L->n, L->Kpad, ctx->variant == 80 || ctx->variant == 81);
+    const int lin = ctx->pick.linear;
+    // few rows: the one-launch kernel of i8ie_flin.hip
+    const bool flin = !need_pad && lin != I8IE_LIN_TILED && L->K % 16 == 0 &&
+                      i8ie_flin_wants(m, L->n, L->Kpad, lin == I8IE_LIN_FLIN || lin == I8IE_LIN_FLIN128);
     // split K when the output has too few tiles to fill the chip (small batch, or few features)
     const long tiles_m = (m + 127) / 128, blocks_est = tiles_m * ((L->n + 63) / 64);
     const int nk = L->Kpad / 128;
     int ksplit = 1;
 #if defined(I8IE_DIAG)
-    const bool lgemm = !need_pad && ctx->variant == 82 && i8ie_lgemm_wants(m, L->n, L->K, L->Kpad) && aligned16(out) &&
+    const bool lgemm = !need_pad && lin == I8IE_LIN_LGEMM && i8ie_lgemm_wants(m, L->n, L->K, L->Kpad) && aligned16(out) &&
                        (size_t)m * L->K < i8ie_igemm_chunk_limit();
 #else
     const bool lgemm = false;
 #endif
-    // many rows: the one-launch kernel of i8ie_mlin.hip (variants 3 / 11 keep the tiled kernel, for comparison)
-    const bool mlin = !need_pad && !flin && !lgemm && ctx->variant != 11 && ctx->variant != 3 && L->K % 16 == 0 && aligned16(out) &&
-                      L->Npad % 128 == 0 && i8ie_mlin_wants(m, L->n, L->Kpad, ctx->variant == 83 || ctx->variant == 84 || ctx->variant == 85);
+    // many rows: the one-launch kernel of i8ie_mlin.hip
+    const bool mlin = !need_pad && !flin && !lgemm && lin != I8IE_LIN_TILED && lin != I8IE_LIN_TILED_MANY && L->K % 16 == 0 &&
+                      aligned16(out) && L->Npad % 128 == 0 &&
+                      i8ie_mlin_wants(m, L->n, L->Kpad, lin == I8IE_LIN_MLIN || lin == I8IE_LIN_MLIN64 || lin == I8IE_LIN_MLIN128);
     if (blocks_est < 256 && nk >= 4 && !flin && !lgemm && !mlin) {
       ksplit = (int)((512 + blocks_est - 1) / blocks_est);
       if (ksplit > 8) ksplit = 8;

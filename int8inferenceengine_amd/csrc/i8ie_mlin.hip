@@ -379,7 +379,7 @@ int i8ie_mlin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   }
   // 64-row tiles when 128-row tiles give at most half the CUs a block (variant 84 / 85 force 64 / 128 rows)
   const long blocks128 = (long)((c.M + 127) / 128) * a.n_tiles;
-  const bool rows64 = ctx->variant == 84 || (ctx->variant != 85 && blocks128 * 2 <= i8ie_cus(ctx, cus[dev]));
+  const bool rows64 = ctx->pick.linear == I8IE_LIN_MLIN64 || (ctx->pick.linear != I8IE_LIN_MLIN128 && blocks128 * 2 <= i8ie_cus(ctx, cus[dev]));
   if (rows64) return mlin_launch_t<64>(ctx, a, c, "mlin_64x128");
   return mlin_launch_t<128>(ctx, a, c, "mlin_128x128");
 }

@@ -539,7 +539,7 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   int npass = (c.N + bn - 1) / bn;
   int RT = pick_rows(npass, false);
   if (RT == 0) return 0;
-  if (c.N % 384 == 0 && ctx->variant != 54) {
+  if (c.N % 384 == 0 && !ctx->pick.pconv_2pass) {
     const int rt6 = pick_rows(c.N / 384, true);
     // (only when 384-wide bands fill at least 3/4 of a whole-chip round: one such round costs 1.0, two rounds of 192-wide
     // (band, pass) units 2 x 0.62 (250 images of 13 x 13: 0.105 -> 0.085 ms for conv3 + conv4); with fewer bands the two passes
@@ -553,7 +553,7 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   }
   // Few bands and a single 256-wide pass (conv5 of a 125-image shard: 125 bands on 256 CUs): two passes of 128 instead,
   // each (band, pass) a unit of its own, so that every CU has work (variant 54 keeps the wide pass)
-  if (npass == 1 && bn == 256 && c.N % 128 == 0 && ctx->variant != 54 && (RT * c.OW + 15) / 16 <= 12 &&
+  if (npass == 1 && bn == 256 && c.N % 128 == 0 && !ctx->pick.pconv_2pass && (RT * c.OW + 15) / 16 <= 12 &&
       (long)n_img * ((c.OH + RT - 1) / RT) * 4 < (long)grid * 3) {
     bn = 128;
     npass = c.N / 128;
@@ -617,12 +617,12 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   // at 125 images: conv3/conv4 0.028/0.038 ms tiled vs 0.035/0.048 ms here) unless the caller forces this kernel.
   const int n_tiles = n_img * bands;
   const int split = (n_tiles < grid && npass > 1) ? 1 : 0;
-  if (i8ie_conv_variant_auto(ctx->variant) && n_tiles * (split ? npass : 1) < grid * 3 / 4) return 0;
+  if (ctx->pick.conv == I8IE_CONV_AUTO && n_tiles * (split ? npass : 1) < grid * 3 / 4) return 0;
   const int seq = (pool && bands > 1) ? 1 : 0;  // the bands of an image back to back in one block
   // pooling wants whole images per block: bands of an image back to back (seq), or -- whole-image bands whose feature passes
   // are units of their own (conv5 of a 125-image shard) -- every unit pooling its own features
   if (pool && split && (bands > 1 || c.N % bn != 0)) return 0;
-  if (pool && !split && i8ie_conv_variant_auto(ctx->variant) && n_img < grid * 3 / 4) return 0;
+  if (pool && !split && ctx->pick.conv == I8IE_CONV_AUTO && n_img < grid * 3 / 4) return 0;
   if (dry) return 1;
 
   // The deferred-epilogue form (tools/diag/csrc/i8ie_dconv.hip, diagnostic build, variant 55: one wave per SIMD, the requantiser
@@ -631,7 +631,7 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   // the AlexNet step's activations) the chip sits at its power cap either way, its clock falls as the instruction stream gets
   // denser (1.6 GHz there, 1.9 here) and the step got SLOWER (conv2 + pool 0.469 against 0.405 ms).
 #if defined(I8IE_DIAG)
-  const bool dconv = ctx->variant == 55 && i8ie_dconv_eligible(split, nkt, npass, patch_gran, PT, bn, pool, c.N);
+  const bool dconv = ctx->pick.dconv && i8ie_dconv_eligible(split, nkt, npass, patch_gran, PT, bn, pool, c.N);
 #else
   const bool dconv = false;
 #endif
@@ -695,7 +695,7 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   a.rcpPW = 1.0f / (float)PWo; a.rcpC16 = 1.0f / (float)(split ? bn / 16 : (c.N / 16 > 0 ? c.N / 16 : 1)); a.rcpRB = 1.0f / (float)RB;
   a.flags = !split ? 1 : 0;
 #if defined(I8IE_DIAG)
-  if (ctx->variant == 53) a.flags = 0;  // (weights fetched at the start of every pass)
+  if (ctx->pick.pconv_refetch) a.flags = 0;  // (weights fetched at the start of every pass)
 #endif
   a.lds_patch = 0;
   a.lds_ocp = patch_gran * 16;
@@ -724,7 +724,7 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
 #if defined(I8IE_DIAG)
   static unsigned long long* dbg_dev[64] = {};  // per device
   unsigned long long*& dbg = dbg_dev[ctx->device & 63];
-  if (ctx->variant == 51) {
+  if (ctx->pick.pconv_stamps) {
     if (!dbg) I8IE_HIP_TRY(hipMalloc(&dbg, 4096 * 64 * sizeof(unsigned long long)));
     I8IE_HIP_TRY(hipMemsetAsync(dbg, 0, 4096 * 64 * sizeof(unsigned long long), ctx->stream));
     a.dbg = dbg;
@@ -738,7 +738,7 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   else if (TMW == 6 && bn == 128) rc = launch_pc<6, 2>(ctx, a, grid, lds);
   else rc = launch_pc<8, 3>(ctx, a, grid, lds);
 #if defined(I8IE_DIAG)
-  if (rc == I8IE_OK && ctx->variant == 51 && std::getenv("I8IE_PCONV_STAMPS") != nullptr) {
+  if (rc == I8IE_OK && ctx->pick.pconv_stamps && std::getenv("I8IE_PCONV_STAMPS") != nullptr) {
     std::vector<unsigned long long> h((size_t)grid * 64);
     I8IE_HIP_TRY(hipStreamSynchronize(ctx->stream));
     I8IE_HIP_TRY(hipMemcpy(h.data(), dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));

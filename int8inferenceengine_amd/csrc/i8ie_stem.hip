@@ -730,7 +730,7 @@ int i8ie_stem_launch(i8ie_ctx* ctx, const I8ieStemCall& c) {
   int parts = 1;
   const int ncu = i8ie_cus(ctx, cus[dev]);
   while (parts < 4 && (long)c.n * parts * 4 < (long)ncu * 3) parts *= 2;
-  if (ctx->variant == 12) parts = 1;  // (I8IE_VARIANT_STEM_WHOLE)
+  if (ctx->pick.stem_whole) parts = 1;
   while (parts > 1 && !stem_plan(c.c, c.stride, c.N, c.KH, c.KW, c.OH, c.OW, c.pool_k, c.pool_s, parts, &s)) parts /= 2;
   if (!stem_plan(c.c, c.stride, c.N, c.KH, c.KW, c.OH, c.OW, c.pool_k, c.pool_s, parts, &s)) {
     i8ie_set_error("i8ie_stem_launch: geometry not supported");
@@ -791,9 +791,9 @@ int i8ie_stem_launch(i8ie_ctx* ctx, const I8ieStemCall& c) {
   if (grid > c.n * s.parts) grid = c.n * s.parts;
   const double ops = 2.0 * c.n * c.OH * c.OW * (double)c.N * c.c * c.KH * c.KW;
   const double bytes = (double)c.n * img_pitch + (double)out_bytes;
-  a.role_split = ctx->variant == 13 ? 1 : 0;  // (I8IE_VARIANT_STEM_SIMD_ROLES: A/B of the role placement)
+  a.role_split = ctx->pick.stem_simd_roles ? 1 : 0;  // (A/B of the role placement)
 #if defined(I8IE_DIAG)
-  const bool fused = s.pk == 3 && ctx->variant == 16;  // (tools/diag/csrc/i8ie_stem_fused.hip: every wave in both roles)
+  const bool fused = s.pk == 3 && ctx->pick.stem_fused;  // (tools/diag/csrc/i8ie_stem_fused.hip: every wave in both roles)
 #endif
   I8ieProfScope prof(ctx, s.pk > 1 ? "stem_conv_pool" : "stem_conv", ops, bytes);
 #if defined(I8IE_DIAG)

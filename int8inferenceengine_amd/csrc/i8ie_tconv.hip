@@ -498,7 +498,7 @@ int i8ie_tconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   // Chosen automatically only where it measured faster than i8ie_pconv.hip: one feature pass, whole patches in the
   // ring, and enough bands per CU to amortise the idle first / last segment of the two teams (AlexNet conv2 at
   // 1000 images: 3000 bands, 2360 vs 2280 TOP/s); variant 70 forces it.
-  if (i8ie_conv_variant_auto(ctx->variant) && !(npass == 1 && S == 1 && (long)n_img * bands >= 8L * grid)) return 0;
+  if (ctx->pick.conv == I8IE_CONV_AUTO && !(npass == 1 && S == 1 && (long)n_img * bands >= 8L * grid)) return 0;
   if (S == 2) {
     kt_split = Ksp / 8;
   } else {
@@ -575,10 +575,7 @@ int i8ie_tconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   a.lds_ktab = a.lds_tab + 2 * kTabPix * 4;
   const int lds = a.lds_ktab + nkt * 32;
 #if defined(I8IE_DIAG)
-  if (ctx->variant == 72) a.flags = 1;
-  if (ctx->variant == 73) a.flags = 2;
-  if (ctx->variant == 74) a.flags = 3;
-  if (ctx->variant == 75) a.flags = 4;
+  a.flags = ctx->pick.tconv_flags;
 #endif
 
   const double ops = 2.0 * c.M * c.N * c.Ktrue;
@@ -591,7 +588,7 @@ int i8ie_tconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
 #if defined(I8IE_DIAG)
   static unsigned long long* dbg_dev[64] = {};  // per device
   unsigned long long*& dbg = dbg_dev[ctx->device & 63];
-  const bool stamps = ctx->variant >= 71 && ctx->variant <= 74;
+  const bool stamps = ctx->pick.tconv_stamps;
   if (stamps) {
     if (!dbg) I8IE_HIP_TRY(hipMalloc(&dbg, 4096 * 8 * sizeof(unsigned long long)));
     I8IE_HIP_TRY(hipMemsetAsync(dbg, 0, 4096 * 8 * sizeof(unsigned long long), ctx->stream));

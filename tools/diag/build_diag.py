@@ -9,7 +9,7 @@ tools/diag/libi8ie_hip_diag.so.  Nothing in the package, bench.py or tests/ load
     I8IE_LIB=tools/diag/libi8ie_hip_diag.so python -m pytest tools/diag/tests -m gpu -q
 
 What the flag adds: in-kernel phase stamps (variants 51, 71-74), the tile-shape / staging experiments of the tiled
-contraction kernel (variants 4, 6-10), the ping-pong kernel (20-49), timing experiments of the two-team kernel
+contraction kernel (conv: variants 4, 6-10; Linear: 14, 15, 17), the ping-pong kernel (20-49), timing experiments of the two-team kernel
 (72-75, $I8IE_TCONV_SPLIT), weights fetched per pass (53), $I8IE_SKINNY.  tools/README.md lists them."""
 import os
 import subprocess
