@@ -61,11 +61,10 @@ int i8ie_sync(i8ie_ctx* ctx);
 /* I8IE_OPT_KERNEL_VARIANT = 2 selects among compiled variants of the contraction kernel (all
  * produce identical bytes; a tuning / A-B timing aid, 0 = default). */
 #define I8IE_OPT_KERNEL_VARIANT 2
-/* The values the product library understands.  Anything else behaves like 0; the diagnostic build of tools/diag
- * adds timing experiments under further numbers, listed in tools/README.md.  A value changes the one thing it names
- * and leaves every other choice automatic.  A convolution with a max-pool or a re-biased layout (below) folds them
- * into the patch-stationary kernel only where that kernel is tried and takes the launch; otherwise the pool and the
- * re-bias run as launches of their own. */
+/* The values the library understands.  Anything else behaves like 0 (earlier numbers named timing experiments,
+ * retired at 9e2c9d6).  A value changes the one thing it names and leaves every other choice automatic.  A
+ * convolution with a max-pool or a re-biased layout (below) folds them into the patch-stationary kernel only where
+ * that kernel is tried and takes the launch; otherwise the pool and the re-bias run as launches of their own. */
 #define I8IE_VARIANT_AUTO 0            /* automatic selection per launch */
 #define I8IE_VARIANT_IGEMM_REGSTAGE 3  /* conv: the tiled contraction kernel only, 128 x 128 tiles, one LDS stage filled through registers;
                                           Linear: the tiled kernel where the many-row kernel would run */

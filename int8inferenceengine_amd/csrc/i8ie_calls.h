@@ -54,11 +54,6 @@ inline bool i8ie_is_pool(int pool_k, int pool_s) { return pool_k > 1 || (pool_k 
 int i8ie_igemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c);
 size_t i8ie_igemm_chunk_limit();  // activations at or beyond this many bytes run as several launches
 
-#if defined(I8IE_DIAG)
-// tools/diag/csrc/i8ie_pp.hip (diagnostic build only): the persistent ping-pong form of the amode-1 contraction.
-int i8ie_pp_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c);
-#endif
-
 // i8ie_pconv.hip: the patch-stationary form of the amode-1 contraction (input patch resident in LDS, weights
 // streamed in fragment order).  Returns 1 when it took the launch, 0 when the shape is not its (the caller then
 // runs the tiled kernel), < 0 on error.
@@ -78,11 +73,3 @@ int i8ie_flin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c);
 // operands through a four-stage LDS-DMA ring fed by dedicated loader waves.  Takes the amode-0 fields of the call.
 bool i8ie_mlin_wants(int m, int n, int Kpad, bool force);
 int i8ie_mlin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c);
-
-#if defined(I8IE_DIAG)
-// tools/diag/csrc/i8ie_lgemm.hip (diagnostic build, variant 82): Linear for many rows (m > 256): 64 x 128 block tiles, weights
-// straight from L2 in fragment order, activations register-staged through LDS.  Round 3: 57 + 30 us for fc6 + fc7 at 1000
-// rows on their own (tiled kernel: 65 + 34), 98.5 us inside the AlexNet step (tiled: 99.5): not worth 72 MB of packed weights.
-bool i8ie_lgemm_wants(int m, int n, int K, int Kpad);
-int i8ie_lgemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool perm_panel);
-#endif

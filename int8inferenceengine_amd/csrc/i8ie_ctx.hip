@@ -76,7 +76,7 @@ void i8ie_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-// I8IE_OPT_KERNEL_VARIANT -> the choices the dispatch reads (the values: include/i8ie_hip.h; the diagnostic ones: tools/README.md)
+// I8IE_OPT_KERNEL_VARIANT -> the choices the dispatch reads (the values: include/i8ie_hip.h)
 I8ieKernelChoice i8ie_decode_variant(int v) {
   I8ieKernelChoice k;
   switch (v) {
@@ -107,31 +107,7 @@ I8ieKernelChoice i8ie_decode_variant(int v) {
     case I8IE_VARIANT_MLIN: k.linear = I8IE_LIN_MLIN; break;
     case I8IE_VARIANT_MLIN_64: k.linear = I8IE_LIN_MLIN64; break;
     case I8IE_VARIANT_MLIN_128: k.linear = I8IE_LIN_MLIN128; break;
-#if defined(I8IE_DIAG)  // the timing experiments of the diagnostic build
-    case 4: case 6: case 7: case 8: case 9: case 10:  // tile shapes / staging forms of the tiled conv
-      k.conv = I8IE_CONV_TILED;
-      k.conv_tile = v;
-      break;
-    case 14: case 15: case 17: k.linear_tile = v; break;  // staging forms of the tiled Linear
-    case 16: k.stem_fused = true; break;
-    case 51: case 52: case 53: case 55: case 56: case 57: case 58: case 59:
-      k.conv = I8IE_CONV_PCONV;
-      k.pconv_stamps = v == 51;
-      k.pconv_refetch = v == 53;
-      k.dconv = v == 55;
-      break;
-    case 60: k.first_fused = true; break;
-    case 61: k.first_scalar = true; break;
-    case 71: case 72: case 73: case 74: case 75: case 76: case 77: case 78: case 79:
-      k.conv = I8IE_CONV_TCONV;
-      k.tconv_stamps = v <= 74;
-      k.tconv_flags = v >= 72 && v <= 75 ? v - 71 : 0;
-      break;
-    case 82: k.linear = I8IE_LIN_LGEMM; break;
-    default:
-      if (v >= 20 && v < 50) k.conv = I8IE_CONV_PP;  // the ping-pong kernel; 21-49 its timing builds (the raw number picks one)
-      break;
-#endif
+    default: break;  // a number this library does not know: all automatic
   }
   return k;
 }
@@ -169,8 +145,7 @@ static int ctx_make(int device, hipStream_t borrowed, bool borrow, i8ie_ctx** ou
   }
   c->device = device;
   if (const char* e = std::getenv("I8IE_KERNEL_VARIANT")) {  // A/B aid, see I8IE_OPT_KERNEL_VARIANT
-    c->variant = std::atoi(e);
-    c->pick = i8ie_decode_variant(c->variant);
+    c->pick = i8ie_decode_variant(std::atoi(e));
   }
   if (borrow) {
     c->stream = borrowed;

@@ -27,7 +27,6 @@
 //     (src/functional.cc:15-26); optional physically padded output.
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
 
 #include "i8ie_internal.h"
 #include "i8ie_calls.h"
@@ -79,35 +78,29 @@ struct IgemmArgs {
   int32_t* partial;
 };
 
-// VAR (tuning variants, identical results): 0 = two LDS stages, loads one K tile ahead;
-// 1 = loads two K tiles ahead (second register set); 2 = VAR 0 + s_setprio around the MFMAs;
-// 3 = one LDS stage, two barriers per K tile (half the LDS: more blocks per CU);
-// 5 = VAR 3 staged by LDS-DMA (buffer_load ... lds, 1 KiB per wave-instruction, no VGPR pass, no ds_write):
+// VAR (staging forms, identical results), both one LDS stage and two barriers per K tile (half the LDS of two
+// stages: more blocks per CU):
+// 3 = register staging into 144-byte LDS rows, the u8 -> s8 re-bias applied on the way into LDS;
+// 5 = staged by LDS-DMA (buffer_load ... lds, 1 KiB per wave-instruction, no VGPR pass, no ds_write):
 //     unpadded 128-B LDS rows, 16-B chunk c of row r stored at chunk c ^ (r & 7) (conflict-free
-//     ds_read_b128 fragments), the u8 -> s8 re-bias applied to the A fragments after the read;
-// 7 = the DMA form with two 64 KiB stages in dynamic LDS (one block per CU): the fill of K tile k+1 is in
-//     flight under the MFMAs of K tile k, one barrier per K tile.  Meant for 256 x 256 / 256 x 192 block
-//     tiles (4 waves of 128 x 128 / 128 x 96): twice the MFMA work per staged byte, which is what the
-//     fill latency x LDS capacity product allows to keep the matrix cores busy
-extern __shared__ __attribute__((aligned(16))) uint8_t i8ie_dyn_smem[];
-
+//     ds_read_b128 fragments), the u8 -> s8 re-bias applied to the A fragments after the read.
+// The measured and retired forms (two stages, loads two K tiles ahead, s_setprio around the MFMAs, two 64 KiB DMA
+// stages for 256-row tiles) are at 9e2c9d6.
 template <int AMODE, int WM, int WN, int TM, int TN, bool BIAS, bool ACC, int VAR>
 __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, int tiles_m, int tiles_n,
                                                                  int m_fastest) {
+  static_assert(VAR == 3 || VAR == 5, "staging form");
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
-  constexpr bool DMA2 = VAR == 7;
-  constexpr bool DMA = VAR == 5 || DMA2;
-  constexpr int NST = (VAR == 3 || VAR == 5) ? 1 : 2;
+  constexpr bool DMA = VAR == 5;
   constexpr int A_PER = BM * 8 / NT, B_PER = BN * 8 / NT;
   static_assert(BM * 8 % NT == 0 && BN * 8 % NT == 0, "staging map");
   static_assert(!DMA || NT % 64 == 0, "DMA rows per pass are a multiple of 8");
   constexpr int LR = DMA ? BK2 : LROW;  // LDS row pitch
-  constexpr int STAGE = DMA2 ? 65536 : (BM + BN) * LR;  // DMA2: power-of-two pitch, stages toggle by XOR
-  static_assert((BM + BN) * LR <= STAGE, "stage holds the A and B tiles");
+  constexpr int STAGE = (BM + BN) * LR;
   constexpr int SROW = BN + 4;  // epilogue tile row stride: odd dword count -> conflict-free ds_write_b32
-  static_assert(BM * SROW <= NST * STAGE, "epilogue tile fits");
-  __shared__ __attribute__((aligned(16))) uint8_t smem_static[DMA2 ? 16 : NST * STAGE];
-  uint8_t* const smem = DMA2 ? i8ie_dyn_smem : smem_static;
+  static_assert(BM * SROW <= STAGE, "epilogue tile fits");
+  __shared__ __attribute__((aligned(16))) uint8_t smem_static[STAGE];
+  uint8_t* const smem = smem_static;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -191,15 +184,14 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
   }
 
   v4i ra[A_PER], rb[B_PER];
-  v4i ra2[VAR == 1 ? A_PER : 1], rb2[VAR == 1 ? B_PER : 1];  // second register set (VAR 1)
   int kbase_l = 0;  // set below once the K slice of this block is known
-  auto load_into = [&](int k0, v4i* da, v4i* db) {
+  auto load_tile = [&](int k0) {
 #pragma unroll
     for (int i = 0; i < A_PER; ++i)
-      da[i] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(rsA, a_off[i] + koff, 0, 0));
+      ra[i] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(rsA, a_off[i] + koff, 0, 0));
 #pragma unroll
     for (int i = 0; i < B_PER; ++i)
-      db[i] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(rsB, b_off[i], k0 + kbase_l, 0));
+      rb[i] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(rsB, b_off[i], k0 + kbase_l, 0));
     koff += BK2;
     if (AMODE == 1) {
       f += 8;
@@ -209,25 +201,26 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
       }
     }
   };
-  auto load_tile = [&](int k0) { load_into(k0, ra, rb); };
   // LDS-DMA: wave-instruction i of wave w fills LDS granules [i * NT + 64 w, + 64) = 8 rows x 128 B
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  // quarter q of the fill of one K tile (the fill is spread over the four k-steps of the tile before)
-  auto dma_part = [&](int k0, int stage_off, int q) {
+  // quarter q of the fill of one K tile
+  auto dma_part = [&](int k0, int q) {
 #pragma unroll
     for (int i = 0; i < A_PER; ++i)
       if (i * 4 / A_PER == q || (A_PER < 4 && q == 0))
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsA, (__attribute__((address_space(3))) void*)(smem + stage_off + (i * NT + wave_u * 64) * 16), 16,
+            rsA, (__attribute__((address_space(3))) void*)(smem + (i * NT + wave_u * 64) * 16), 16,
             (int)(a_off[i] + koff), 0, 0, 0);
 #pragma unroll
     for (int i = 0; i < B_PER; ++i)
       if (i * 4 / B_PER == q || (B_PER < 4 && q == 0))
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsB, (__attribute__((address_space(3))) void*)(smem + stage_off + BM * LR + (i * NT + wave_u * 64) * 16),
+            rsB, (__attribute__((address_space(3))) void*)(smem + BM * LR + (i * NT + wave_u * 64) * 16),
             16, (int)b_off[i], k0 + kbase_l, 0, 0);
   };
-  auto dma_advance = [&]() {
+  auto dma_tile = [&](int k0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dma_part(k0, q);
     koff += BK2;
     if (AMODE == 1) {
       f += 8;
@@ -237,12 +230,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
       }
     }
   };
-  auto dma_tile = [&](int k0, int stage_off) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dma_part(k0, stage_off, q);
-    dma_advance();
-  };
-  // LDS addresses (bytes from smem); stage s adds s * STAGE as an immediate
+  // LDS addresses (bytes from smem)
   int a_wr[A_PER], b_wr[B_PER], a_rd[TM], b_rd[TN];
 #pragma unroll
   for (int i = 0; i < A_PER; ++i) a_wr[i] = ((tid >> 3) + (NT >> 3) * i) * LROW + cA * 16;
@@ -257,15 +245,12 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
   for (int ni = 0; ni < TN; ++ni)
     b_rd[ni] = BM * LROW + ((wn * TN + ni) * 32 + (lane & 31)) * LROW + (lane >> 5) * 16;
 
-  auto store_from = [&](auto sc, const v4i* sa, const v4i* sb) {
-    constexpr int S = decltype(sc)::value;
+  auto store_tile = [&]() {
 #pragma unroll
-    for (int i = 0; i < A_PER; ++i)
-      *reinterpret_cast<v4i*>(smem + S * STAGE + a_wr[i]) = sa[i] ^ (int)0x80808080;  // u8 -> s8
+    for (int i = 0; i < A_PER; ++i) *reinterpret_cast<v4i*>(smem + a_wr[i]) = ra[i] ^ (int)0x80808080;  // u8 -> s8
 #pragma unroll
-    for (int i = 0; i < B_PER; ++i) *reinterpret_cast<v4i*>(smem + S * STAGE + b_wr[i]) = sb[i];
+    for (int i = 0; i < B_PER; ++i) *reinterpret_cast<v4i*>(smem + b_wr[i]) = rb[i];
   };
-  auto store_tile = [&](auto sc) { store_from(sc, ra, rb); };
   // DMA image: fragment of k-step ks for row r sits at chunk (2 ks + (lane >> 5)) ^ (r & 7); r & 7 == lane & 7
   int a_rdk[DMA ? 4 : 1], b_rdk[DMA ? 4 : 1];
   if (DMA) {
@@ -276,7 +261,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
       b_rdk[ks] = BM * LR + (wn * TN * 32 + (lane & 31)) * LR + sw;
     }
   }
-  auto compute_dma = [&](bool fill_next, int k0, int stage_off) {
+  auto compute_dma = [&]() {
     v4i af[2][TM], bf[2][TN];
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi) af[0][mi] = *reinterpret_cast<const v4i*>(smem + a_rdk[0] + mi * 32 * LR);
@@ -299,38 +284,31 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
         for (int ni = 0; ni < TN; ++ni)
           acc[mi][ni] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bf[ks & 1][ni], as8, acc[mi][ni], 0, 0, 0);
       }
-      if (DMA2 && fill_next) dma_part(k0, stage_off, ks);  // a quarter of the next tile's fill per k-step
     }
-    if (DMA2 && fill_next) dma_advance();
   };
-  auto compute = [&](auto sc) {
-    constexpr int S = decltype(sc)::value;
+  auto compute = [&]() {
     v4i af[2][TM], bf[2][TN];  // fragments of k-step ks+1 are fetched under the MFMAs of k-step ks
 #pragma unroll
-    for (int mi = 0; mi < TM; ++mi) af[0][mi] = *reinterpret_cast<const v4i*>(smem + S * STAGE + a_rd[mi]);
+    for (int mi = 0; mi < TM; ++mi) af[0][mi] = *reinterpret_cast<const v4i*>(smem + a_rd[mi]);
 #pragma unroll
-    for (int ni = 0; ni < TN; ++ni) bf[0][ni] = *reinterpret_cast<const v4i*>(smem + S * STAGE + b_rd[ni]);
+    for (int ni = 0; ni < TN; ++ni) bf[0][ni] = *reinterpret_cast<const v4i*>(smem + b_rd[ni]);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       if (ks < 3) {
 #pragma unroll
         for (int mi = 0; mi < TM; ++mi)
-          af[(ks + 1) & 1][mi] = *reinterpret_cast<const v4i*>(smem + S * STAGE + (ks + 1) * 32 + a_rd[mi]);
+          af[(ks + 1) & 1][mi] = *reinterpret_cast<const v4i*>(smem + (ks + 1) * 32 + a_rd[mi]);
 #pragma unroll
         for (int ni = 0; ni < TN; ++ni)
-          bf[(ks + 1) & 1][ni] = *reinterpret_cast<const v4i*>(smem + S * STAGE + (ks + 1) * 32 + b_rd[ni]);
+          bf[(ks + 1) & 1][ni] = *reinterpret_cast<const v4i*>(smem + (ks + 1) * 32 + b_rd[ni]);
       }
-      if (VAR == 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
         for (int ni = 0; ni < TN; ++ni)
           acc[mi][ni] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bf[ks & 1][ni], af[ks & 1][mi], acc[mi][ni], 0, 0, 0);
-      if (VAR == 2) __builtin_amdgcn_s_setprio(0);
     }
   };
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
 
   int nk = p.Kpad / BK2;
   int kbase = 0;  // first K byte of this block's slice
@@ -342,78 +320,31 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
     koff += kbase;
     kbase_l = kbase;
   }
-  if constexpr (DMA2) {  // two stages: fill of tile k+1 in flight under the MFMAs of tile k, one barrier per tile
-    dma_tile(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int fill = STAGE;  // byte offset of the stage the next fill goes to
-    for (int kt = 0; kt < nk; ++kt) {
-      compute_dma(kt + 1 < nk, (kt + 1) * BK2, fill);
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {  // fragments of the next tile come from the other stage
-        a_rdk[ks] ^= STAGE;
-        b_rdk[ks] ^= STAGE;
-      }
-      fill ^= STAGE;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-  } else if constexpr (DMA) {  // one stage: DMA fill | wait + barrier | compute | barrier
-    dma_tile(0, 0);
+  if constexpr (DMA) {  // fill | wait + barrier | compute | barrier
+    dma_tile(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
-      compute_dma(false, 0, 0);
+      compute_dma();
       __syncthreads();
       if (kt + 1 < nk) {
-        dma_tile((kt + 1) * BK2, 0);
+        dma_tile((kt + 1) * BK2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
       }
     }
-  } else if constexpr (VAR == 3) {  // one stage: compute | barrier | refill | barrier
+  } else {  // compute | barrier | refill | barrier
     load_tile(0);
-    store_tile(S0{});
+    store_tile();
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
       if (kt + 1 < nk) load_tile((kt + 1) * BK2);
-      compute(S0{});
+      compute();
       __syncthreads();
       if (kt + 1 < nk) {
-        store_tile(S0{});
+        store_tile();
         __syncthreads();
       }
-    }
-  } else if constexpr (VAR == 1) {  // loads run two K tiles ahead of the MFMAs
-    load_into(0, ra, rb);
-    store_from(S0{}, ra, rb);
-    if (nk > 1) load_into(BK2, ra2, rb2);
-    __syncthreads();
-    for (int kt = 0; kt < nk; kt += 2) {
-      if (kt + 2 < nk) load_into((kt + 2) * BK2, ra, rb);
-      compute(S0{});
-      if (kt + 1 < nk) store_from(S1{}, ra2, rb2);
-      __syncthreads();
-      if (kt + 1 >= nk) break;
-      if (kt + 3 < nk) load_into((kt + 3) * BK2, ra2, rb2);
-      compute(S1{});
-      if (kt + 2 < nk) store_from(S0{}, ra, rb);
-      __syncthreads();
-    }
-  } else {
-    load_tile(0);
-    store_tile(S0{});
-    __syncthreads();
-    for (int kt = 0; kt < nk; kt += 2) {
-      if (kt + 1 < nk) load_tile((kt + 1) * BK2);  // global loads in flight under the MFMAs
-      compute(S0{});
-      if (kt + 1 < nk) store_tile(S1{});
-      __syncthreads();
-      if (kt + 1 >= nk) break;
-      if (kt + 2 < nk) load_tile((kt + 2) * BK2);
-      compute(S1{});
-      if (kt + 2 < nk) store_tile(S0{});
-      __syncthreads();
     }
   }
 
@@ -422,7 +353,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
     // BN * 4 bytes (one dword per lane and row was ~64 scattered line requests per wave-instruction).
     int32_t* slab = p.partial + (size_t)blockIdx.y * p.M * p.N;
     constexpr int CTP = BN + 4;  // ints per staged row: 16-byte aligned, conflict-free 16-byte column writes
-    constexpr int PR = (NST * STAGE) / (CTP * 4) / 32 * 32 < BM ? (NST * STAGE) / (CTP * 4) / 32 * 32 : BM;
+    constexpr int PR = STAGE / (CTP * 4) / 32 * 32 < BM ? STAGE / (CTP * 4) / 32 * 32 : BM;
     static_assert(PR >= 32, "at least one MFMA row tile per pass");
     int* ct = reinterpret_cast<int*>(smem);
     const int hh2 = lane >> 5;
@@ -956,7 +887,7 @@ inline int cap_grid(int64_t items, int threads, int max_blocks = 256 * 16) {
   return (int)(b > max_blocks ? max_blocks : b);
 }
 
-template <int AMODE, int WM, int WN, int TM, int TN, bool BIAS, bool ACC, int VAR = 0>
+template <int AMODE, int WM, int WN, int TM, int TN, bool BIAS, bool ACC, int VAR>
 int launch_cfg(i8ie_ctx* ctx, const IgemmArgs& a, const char* name, int kbytes, double ops, double bytes) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
@@ -964,19 +895,8 @@ int launch_cfg(i8ie_ctx* ctx, const IgemmArgs& a, const char* name, int kbytes, 
   char tag[64];
   snprintf(tag, sizeof(tag), "%s|M%d,N%d,K%d", name, a.M, a.N, kbytes);
   I8ieProfScope prof(ctx, ctx->prof ? tag : name, ops, bytes);
-  constexpr unsigned dyn_lds = VAR == 7 ? 2u * 65536u : 0u;
-  if (VAR == 7) {
-    static bool raised_on[64] = {};  // per instantiation and device: allow 128 KiB of dynamic LDS
-    bool& raised = raised_on[ctx->device & 63];
-    if (!raised) {
-      I8IE_HIP_TRY(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&igemm_u8s8_kernel<AMODE, WM, WN, TM, TN, BIAS, ACC, VAR>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
-      raised = true;
-    }
-  }
   igemm_u8s8_kernel<AMODE, WM, WN, TM, TN, BIAS, ACC, VAR>
-      <<<dim3(tiles_m * tiles_n, a.ksplit > 1 ? a.ksplit : 1), WM * WN * 64, dyn_lds, ctx->stream>>>(
+      <<<dim3(tiles_m * tiles_n, a.ksplit > 1 ? a.ksplit : 1), WM * WN * 64, 0, ctx->stream>>>(
           a, tiles_m, tiles_n, m_fastest);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
@@ -1010,45 +930,19 @@ int launch_tile_var(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, d
 // Default: one LDS stage filled by LDS-DMA (VAR 5).  Measured on MI355X (tools/bench_layer.py, AlexNet
 // conv2-5): one stage (half the LDS) lets a third wave per SIMD in, +10 % over the two-stage form; DMA
 // staging +3-6 % over register staging (VAR 3); loads two tiles ahead and s_setprio around the MFMAs
-// within 2 % of the baseline; the 256-row two-stage DMA form (VAR 7) 10-20 % slower on these K depths
-// ("what bounds the contraction kernel").  ctx->pick.conv_tile / linear_tile select the others.
+// within 2 % of the baseline; the 256-row two-stage DMA form 10-20 % slower on these K depths (DESIGN.md,
+// "what bounds the contraction kernel"; the retired forms are at 9e2c9d6).  ctx->pick.conv_tile / linear_tile
+// select the staging form.
 template <int AMODE, bool BIAS, bool ACC>
 int launch_tile(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, double bytes) {
   const int tile = AMODE == 1 ? ctx->pick.conv_tile : ctx->pick.linear_tile;
   if (AMODE == 1 && !BIAS && !ACC) {
-#if defined(I8IE_DIAG)  // tile-shape experiments, compiled into the diagnostic build only
-    if (tile == 10) return launch_tile_var<1, false, false, 0>(ctx, a, kbytes, ops, bytes);
-    if (tile == 6 && a.N <= 96 && a.N > 64)  // 256 x 96 tile, 4 waves of 64 x 96
-      return launch_cfg<1, 4, 1, 2, 3, false, false, 3>(ctx, a, "igemm_conv_256x96", kbytes, ops, bytes);
-    if (tile == 4 && a.N % 256 == 0)  // 256 x 256 tile, 8 waves, two stages
-      return launch_cfg<1, 2, 4, 4, 2, false, false, 0>(ctx, a, "igemm_conv_256x256", kbytes, ops, bytes);
-    if (tile == 8 && a.N > 64)  // 256 x 128, 4 waves of 128 x 64, one DMA stage
-      return launch_cfg<1, 2, 2, 4, 2, false, false, 5>(ctx, a, "igemm_conv_256x128", kbytes, ops, bytes);
-    if (tile == 9 && a.N > 128)  // 128 x 256, 4 waves of 64 x 128
-      return launch_cfg<1, 2, 2, 2, 4, false, false, 5>(ctx, a, "igemm_conv_128x256", kbytes, ops, bytes);
-#endif
     // 192 x 128, 4 waves of 96 x 64, one DMA stage: 6.4 KB staged per MOP (128 x 128: 7.6) at three blocks
     // per CU; measured 2.5-4 % faster than 128 x 128 on AlexNet conv2-5.  A variant that names a staging form or tile
     // shape of THIS kernel switches it to 128 x 128; the others leave the tiled kernel's default alone
     if (tile == I8IE_TILE_DEFAULT && a.N > 64 && a.M >= 192 * 256)
       return launch_cfg<1, 2, 2, 3, 2, false, false, 5>(ctx, a, "igemm_conv_192x128", kbytes, ops, bytes);
-#if defined(I8IE_DIAG)
-    if (tile == 7 && a.N > 128 && (long)((a.M + 255) / 256) >= 256) {
-      // 4 waves of 128 x 128 or 128 x 96: whichever pads N less
-      const int pad4 = (a.N + 255) / 256 * 256, pad3 = (a.N + 191) / 192 * 192;
-      if (pad4 <= pad3) return launch_cfg<1, 2, 2, 4, 4, false, false, 7>(ctx, a, "igemm_conv_256x256", kbytes, ops, bytes);
-      return launch_cfg<1, 2, 2, 4, 3, false, false, 7>(ctx, a, "igemm_conv_256x192", kbytes, ops, bytes);
-    }
-#endif
   }
-#if defined(I8IE_DIAG)
-  if (AMODE == 0 && tile == 17 && a.ksplit <= 1)  // Linear, 128 x 128 tiles, two 64 KiB DMA stages, one block per CU
-    return launch_cfg<AMODE, 2, 2, 2, 2, BIAS, ACC, 7>(ctx, a, "igemm_lin_128x128_dma2", kbytes, ops, bytes);
-  if (AMODE == 0 && tile == 14 && a.ksplit <= 1)  // Linear, 128 x 128 tiles, one DMA stage
-    return launch_cfg<AMODE, 2, 2, 2, 2, BIAS, ACC, 5>(ctx, a, "igemm_lin_128x128_dma1", kbytes, ops, bytes);
-  if (AMODE == 0 && tile == 15 && a.ksplit <= 1)  // Linear, 128 x 128 tiles, register staging
-    return launch_cfg<AMODE, 2, 2, 2, 2, BIAS, ACC, 3>(ctx, a, "igemm_lin_128x128_reg", kbytes, ops, bytes);
-#endif
   // Linear (few, short split-K slices per block) measured 20 % slower with DMA staging: register staging there
   if (AMODE == 1 ? tile == I8IE_TILE_REG : tile != I8IE_TILE_DMA)
     return launch_tile_var<AMODE, BIAS, ACC, 3>(ctx, a, kbytes, ops, bytes);
@@ -1112,15 +1006,6 @@ int i8ie_igemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
     }
     return I8IE_OK;
   }
-#if defined(I8IE_DIAG)
-  // The persistent ping-pong kernel (i8ie_pp.hip) is opt-in (variant 20; 21-49 are its diagnostic builds): measured
-  // on MI355X it trails the tiled kernel by 3-8 % on AlexNet conv2 / conv5 as long as activations need the u8 -> s8
-  // xor in its MFMA slots ("what bounds the ping-pong kernel"), and it pads N = 384 to 512.
-  if (c.amode == 1 && i8ie_conv_tries(ctx, I8IE_CONV_PP)) {
-    const int took = i8ie_pp_try_launch(ctx, c);
-    if (took != 0) return took < 0 ? took : I8IE_OK;
-  }
-#endif
   // The two-team form of the patch-stationary kernel (i8ie_tconv.hip) comes first: it declines unless forced
   // (variant 70) or the launch is of the kind it measured faster on (one feature pass, >= 8 bands per CU).
   if (c.amode == 1 && i8ie_conv_tries(ctx, I8IE_CONV_TCONV)) {
@@ -1193,18 +1078,6 @@ int i8ie_igemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
     return accd ? launch_tile<0, false, true>(ctx, a, kb, ops, bytes) : launch_tile<0, false, false>(ctx, a, kb, ops, bytes);
   }
   return accd ? launch_tile<1, false, true>(ctx, a, kb, ops, bytes) : launch_tile<1, false, false>(ctx, a, kb, ops, bytes);
-}
-
-// the Linear epilogue over [slices][M][N] INT32 partial slabs (slice 0 carries oc'), for i8ie_skinny.hip
-int i8ie_launch_splitk_reduce(i8ie_ctx* ctx, const int32_t* partial, int slices, int M, int N, const float* biasf,
-                              float s_in, float s_w, float s_out, int zp_out, int relu, uint8_t* out, int32_t* acc) {
-  const Requant rq = i8ie_make_requant(s_in, s_w, s_out, zp_out);
-  I8ieProfScope prof(ctx, "splitk_reduce", 0.0, 4.0 * slices * M * N + (double)M * N);
-  const int64_t quads = ((int64_t)M * N + 3) / 4;
-  splitk_reduce_kernel<<<cap_grid(quads, 256), 256, 0, ctx->stream>>>(partial, slices, M, N, biasf, rq,
-                                                                      relu ? zp_out : 0, out, acc);
-  I8IE_LAUNCH_CHECK();
-  return I8IE_OK;
 }
 
 int i8ie_launch_finish_offsets(i8ie_ctx* ctx, const int32_t* oc, const int32_t* wsum, const int8_t* qb, float s_in,

@@ -10,9 +10,9 @@
 
 // I8IE_OPT_KERNEL_VARIANT decoded once (i8ie_decode_variant, i8ie_ctx.hip) into the choices the dispatch sites read.  A value
 // changes the one thing it names; a value this build does not know decodes to all-automatic.
-enum { I8IE_CONV_AUTO, I8IE_CONV_TILED, I8IE_CONV_PCONV, I8IE_CONV_TCONV, I8IE_CONV_PP };
-// the tiled contraction kernel's form: default, one LDS stage filled through registers / by LDS-DMA (the VAR of
-// i8ie_igemm.hip), or a diagnostic tile form named by its variant number
+enum { I8IE_CONV_AUTO, I8IE_CONV_TILED, I8IE_CONV_PCONV, I8IE_CONV_TCONV };
+// the tiled contraction kernel's form: default, or one LDS stage filled through registers / by LDS-DMA (the VAR of
+// i8ie_igemm.hip)
 enum { I8IE_TILE_DEFAULT = 0, I8IE_TILE_REG = 3, I8IE_TILE_DMA = 5 };
 enum {
   I8IE_LIN_AUTO,
@@ -23,7 +23,6 @@ enum {
   I8IE_LIN_MLIN,          // many-row kernel below its feature threshold
   I8IE_LIN_MLIN64,        // the same, 64-row block tiles
   I8IE_LIN_MLIN128,       // the same, 128-row block tiles
-  I8IE_LIN_LGEMM,         // diagnostic build: tools/diag/csrc/i8ie_lgemm.hip
 };
 struct I8ieKernelChoice {
   int conv = I8IE_CONV_AUTO;  // which kernels a conv launch tries (i8ie_conv_tries)
@@ -35,15 +34,6 @@ struct I8ieKernelChoice {
   bool stem_simd_roles = false;  // first-stage kernel: its two wave roles on separate SIMDs
   bool no_stem = false;      // no first-stage kernel (conv_smallc + separate pools)
   bool no_dot4_head = false;  // the classifier head without its MFMA form
-  // diagnostic build only
-  bool stem_fused = false;     // first-stage kernel, every wave in both roles (tools/diag/csrc/i8ie_stem_fused.hip)
-  bool first_fused = false;    // quantize fused into conv_smallc's patch fill
-  bool first_scalar = false;   // scalar loads in quantize + repack
-  bool pconv_stamps = false;   // pconv phase stamps
-  bool pconv_refetch = false;  // pconv fetches the weights at the start of every pass
-  bool dconv = false;          // the deferred-epilogue conv (tools/diag/csrc/i8ie_dconv.hip) where it is eligible
-  bool tconv_stamps = false;   // tconv phase stamps
-  int tconv_flags = 0;         // tconv timing experiments
 };
 I8ieKernelChoice i8ie_decode_variant(int v);
 
@@ -57,8 +47,7 @@ struct i8ie_ctx {
   void* prof = nullptr;  // I8ieProf* (i8ie_ctx.hip): HIP-event timing of every launch, when enabled
   unsigned options = 0;  // bit 0: I8IE_OPT_FORCE_FALLBACK
   int cu_limit = 0;  // I8IE_OPT_CU_LIMIT: compute units of the stream's CU mask (0 = the whole device)
-  int variant = 0;  // I8IE_OPT_KERNEL_VARIANT as set (diagnostic printfs); the dispatch reads `pick`
-  I8ieKernelChoice pick;  // i8ie_decode_variant(variant)
+  I8ieKernelChoice pick;  // i8ie_decode_variant(I8IE_OPT_KERNEL_VARIANT)
   int prof_mfma_only = 0;  // time only the contraction kernels (fewer event packets in a timed region)
   int prof_stride = 1;     // I8IE_OPT_PROFILE_STRIDE: bracket every prof_stride-th eligible launch
   unsigned prof_seen = 0;  // eligible launches since i8ie_profile_start
@@ -90,7 +79,7 @@ void i8ie_set_error(const char* fmt, ...);
 
 // compute units a one-block-per-CU kernel may count on: the device's, or the ctx's CU-mask share
 inline int i8ie_cus(const i8ie_ctx* ctx, int device_cus) { return ctx->cu_limit > 0 && ctx->cu_limit < device_cus ? ctx->cu_limit : device_cus; }
-// does a conv launch try this kernel (I8IE_CONV_PCONV / _TCONV / _PP) before the tiled one?  Automatic selection tries the two
+// does a conv launch try this kernel (I8IE_CONV_PCONV / _TCONV) before the tiled one?  Automatic selection tries the two
 // patch-stationary kernels (each declines what it is not measured faster on); a forced choice tries only the kernel it names.
 // The layout / pool negotiation (pconv_probe, i8ie_layer.hip) asks the same question as the dispatcher (i8ie_igemm.hip).
 inline bool i8ie_conv_tries(const i8ie_ctx* ctx, int kernel) {

@@ -306,18 +306,6 @@ __global__ __launch_bounds__(512, 2) void pconv_kernel(PCArgs p) {
   };
 
   // =============================== tile loop ===========================================================
-#if defined(I8IE_DIAG)
-  unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tq = 0;
-  auto stamp = [&](int i) {
-    if (p.dbg) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      ph[i] += now - tq;
-      tq = now;
-    }
-  };
-#else
-  auto stamp = [](int) {};  // (phase stamps exist in the diagnostic build only: tools/diag)
-#endif
   const int lin_total = p.npass * p.nkt;
   const int patch = p.lds_patch;
   const bool xpre = (p.flags & 1) != 0;  // the last K tile of a pass already fetches the first weights of the next pass / band (+1 %)
@@ -334,9 +322,6 @@ __global__ __launch_bounds__(512, 2) void pconv_kernel(PCArgs p) {
     load_B(Bq[1], 0, 1);
   }
   __syncthreads();
-#if defined(I8IE_DIAG)
-  if (p.dbg) tq = __builtin_amdgcn_s_memtime();
-#endif
   while (unit < t_hi) {
     const bool more = has_next(unit, band);
     const int tile = tile_at(unit, band);
@@ -378,19 +363,12 @@ __global__ __launch_bounds__(512, 2) void pconv_kernel(PCArgs p) {
         mfma_half(Ahi, Bq[1], 1);
         load_B(Bq[1], linn, 1);
       }
-      stamp(0);  // K loop
-      if (pass + 1 < pass_hi) {
-        epilogue(tile, pass);
-        stamp(1);
-      }
+      if (pass + 1 < pass_hi) epilogue(tile, pass);
     }
     // ---- hand-over: everyone is done with the patch -> request the next one -> it lands under the epilogue
     __syncthreads();
-    stamp(2);  // waiting for the slowest wave's K loop
     if (more) patch_fill(next_tile(unit, band), patch);
-    stamp(3);  // issuing the patch DMA
     epilogue(tile, pass_hi - 1);
-    stamp(1);
     if constexpr (POOL) {
       // the band's requantised rows are in the LDS ring: pool what they complete, under the landing patch
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (not __syncthreads(): the patch DMA and the ACC stores stay in flight)
@@ -411,18 +389,13 @@ __global__ __launch_bounds__(512, 2) void pconv_kernel(PCArgs p) {
           case 3: pc_wait_vm<3>(); break;
           default: pc_wait_vm<4>(); break;
         }
-        stamp(4);
         patch_xor(patch);
-        stamp(5);
       }
     } else if (more) {
       pc_wait_vm<ST>();  // all but the epilogue's stores
-      stamp(4);          // patch DMA not yet landed after the epilogue
       patch_xor(patch);
-      stamp(5);          // re-bias pass
     }
     __syncthreads();
-    stamp(6);  // second barrier
     if (p.seq && band + 1 < p.bands) {
       ++band;
     } else {
@@ -431,10 +404,6 @@ __global__ __launch_bounds__(512, 2) void pconv_kernel(PCArgs p) {
     }
   }
   pc_wait_vm<0>();
-#if defined(I8IE_DIAG)
-  if (p.dbg && lane == 0)
-    for (int i = 0; i < 7; ++i) p.dbg[((size_t)blockIdx.x * 8 + wave) * 8 + i] = ph[i];
-#endif
 }
 
 // ---- weights in fragment order for this kernel's K walk: [pass][kt][ks][ntile][lane][16] --------------------
@@ -625,24 +594,19 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   if (pool && !split && ctx->pick.conv == I8IE_CONV_AUTO && n_img < grid * 3 / 4) return 0;
   if (dry) return 1;
 
-  // The deferred-epilogue form (tools/diag/csrc/i8ie_dconv.hip, diagnostic build, variant 55: one wave per SIMD, the requantiser
+  // The deferred-epilogue form (i8ie_dconv.hip, retired at 9e2c9d6: one wave per SIMD, the requantiser
   // of one accumulator set inside the other set's K loop).  Round 4 measured it (profiles/r04_dconv_power_limit.txt): 20 % fewer cycles per band
   // than this file's kernel and 3.0 against 2.6 POPS on constant operands -- but on data whose bits toggle (random bytes, and
   // the AlexNet step's activations) the chip sits at its power cap either way, its clock falls as the instruction stream gets
   // denser (1.6 GHz there, 1.9 here) and the step got SLOWER (conv2 + pool 0.469 against 0.405 ms).
-#if defined(I8IE_DIAG)
-  const bool dconv = ctx->pick.dconv && i8ie_dconv_eligible(split, nkt, npass, patch_gran, PT, bn, pool, c.N);
-#else
-  const bool dconv = false;
-#endif
 
   // ---- fragment-packed weights: once per layer and packing key, kept in the layer handle (I8ieWCache)
   // (a buffer holds [perm: nkt * 8 ints, padded to 256 B][weights]; the fragment order depends on the pass width)
   const size_t perm_bytes = i8ie_align_up((size_t)nkt * 8 * sizeof(int), 256);
   const size_t bf_bytes = (size_t)npass * nkt * kt_bytes;
   const unsigned long long wkey = (1ull << 32) | (unsigned long long)(row_par | (bn << 1));
-  void* wbuf = dconv ? nullptr : c.wcache->find(wkey);
-  if (wbuf == nullptr && !dconv) {
+  void* wbuf = c.wcache->find(wkey);
+  if (wbuf == nullptr) {
     I8IE_REQUIRE(ctx->capture == nullptr, "weight re-packing inside a graph capture: run the same calls once eagerly first");
     I8IE_TRY(i8ie_malloc(ctx, perm_bytes + bf_bytes, &wbuf));
     int rc = i8ie_memcpy_h2d(ctx, wbuf, perm.data(), perm.size() * sizeof(int));
@@ -674,11 +638,9 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   a.patch_gran = patch_gran;
   a.row_gran = row_gran;
   a.rcpRowGran = 1.0f / (float)row_gran;
-  if (!dconv) {
-    a.Bf = (const int8_t*)wbuf + perm_bytes;
-    a.perm = (const int*)wbuf;
-    a.bf_bytes = (unsigned)bf_bytes;
-  }
+  a.Bf = (const int8_t*)wbuf + perm_bytes;
+  a.perm = (const int*)wbuf;
+  a.bf_bytes = (unsigned)bf_bytes;
   a.nkt = nkt;
   a.N = c.N; a.npass = npass;
   a.ocp = c.ocp; a.Npad = c.Npad;
@@ -694,9 +656,6 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   a.pk = pool ? c.pool_k : 1; a.ps = pool ? c.pool_s : 1; a.PH = PHo; a.PW = PWo; a.RB = RB; a.opitch = opitch; a.seq = seq;
   a.rcpPW = 1.0f / (float)PWo; a.rcpC16 = 1.0f / (float)(split ? bn / 16 : (c.N / 16 > 0 ? c.N / 16 : 1)); a.rcpRB = 1.0f / (float)RB;
   a.flags = !split ? 1 : 0;
-#if defined(I8IE_DIAG)
-  if (ctx->pick.pconv_refetch) a.flags = 0;  // (weights fetched at the start of every pass)
-#endif
   a.lds_patch = 0;
   a.lds_ocp = patch_gran * 16;
   a.lds_tab = a.lds_ocp + npass * bn * 4;
@@ -712,24 +671,7 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   snprintf(tag, sizeof(tag), "pconv%s_%dx%d|M%d,N%d,K%d", pool ? "_pool" : "", TMW * 32, bn, c.M, c.N, c.Kchunks * 16);
   char nm[32];
   snprintf(nm, sizeof(nm), "pconv%s_%dx%d", pool ? "_pool" : "", TMW * 32, bn);
-#if defined(I8IE_DIAG)
-  if (dconv) {
-    tag[0] = 'd';  // "dconv..."
-    nm[0] = 'd';
-    const int rcd = i8ie_dconv_launch(ctx, c, a, perm.data(), PT, bn, grid, lds, ctx->prof ? tag : nm);
-    return rcd == I8IE_OK ? 1 : rcd;
-  }
-#endif
   I8ieProfScope prof(ctx, ctx->prof ? tag : nm, ops, bytes);
-#if defined(I8IE_DIAG)
-  static unsigned long long* dbg_dev[64] = {};  // per device
-  unsigned long long*& dbg = dbg_dev[ctx->device & 63];
-  if (ctx->pick.pconv_stamps) {
-    if (!dbg) I8IE_HIP_TRY(hipMalloc(&dbg, 4096 * 64 * sizeof(unsigned long long)));
-    I8IE_HIP_TRY(hipMemsetAsync(dbg, 0, 4096 * 64 * sizeof(unsigned long long), ctx->stream));
-    a.dbg = dbg;
-  }
-#endif
   int rc;
   if (TMW == 8 && bn == 256) rc = launch_pc<8, 4>(ctx, a, grid, lds);
   else if (TMW == 6 && bn == 256) rc = launch_pc<6, 4>(ctx, a, grid, lds);
@@ -737,22 +679,5 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   else if (TMW == 6 && bn == 384) rc = launch_pc<6, 6>(ctx, a, grid, lds);
   else if (TMW == 6 && bn == 128) rc = launch_pc<6, 2>(ctx, a, grid, lds);
   else rc = launch_pc<8, 3>(ctx, a, grid, lds);
-#if defined(I8IE_DIAG)
-  if (rc == I8IE_OK && ctx->pick.pconv_stamps && std::getenv("I8IE_PCONV_STAMPS") != nullptr) {
-    std::vector<unsigned long long> h((size_t)grid * 64);
-    I8IE_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    I8IE_HIP_TRY(hipMemcpy(h.data(), dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double sum[8][7] = {};
-    for (int b = 0; b < grid; ++b)
-      for (int w = 0; w < 8; ++w)
-        for (int i = 0; i < 7; ++i) sum[w][i] += (double)h[((size_t)b * 8 + w) * 8 + i];
-    const double tp = (double)a.n_tiles * npass;  // band passes in all
-    fprintf(stderr, "pconv_stamps v%d M %d N %d K %d (%d tiles x %d passes, %d K tiles, TMW %d bn %d): per tile pass, cycles (wave 0): K loop %.0f (%.0f per K tile) | epilogue %.0f | hand-over: barrier after the K loop %.0f, DMA issue %.0f, DMA wait after the epilogue %.0f, re-bias %.0f, barrier %.0f ; K loop / first barrier per wave:",
-            ctx->variant, c.M, c.N, c.Kchunks * 16, a.n_tiles, npass, nkt, TMW, bn, sum[0][0] / tp, sum[0][0] / tp / nkt, sum[0][1] / tp, sum[0][2] / tp,
-            sum[0][3] / tp, sum[0][4] / tp, sum[0][5] / tp, sum[0][6] / tp);
-    for (int w = 0; w < 8; ++w) fprintf(stderr, " %.0f/%.0f", sum[w][0] / tp, sum[w][2] / tp);
-    fprintf(stderr, "\n");
-  }
-#endif
   return rc == I8IE_OK ? 1 : rc;
 }

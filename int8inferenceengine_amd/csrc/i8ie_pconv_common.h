@@ -1,6 +1,5 @@
-// i8ie_pconv_common.h -- what the patch-stationary convolution kernels share (i8ie_pconv.hip: 8 waves, 16 x 16 x 64 MFMA tiles,
-// epilogue behind the K loop; tools/diag/csrc/i8ie_dconv.hip: 4 waves with two accumulator sets, 32 x 32 x 32 tiles, the requantiser of one set
-// inside the other set's K loop): the kernel argument block, the LDS plan it describes, and a few device helpers.
+// i8ie_pconv_common.h -- the patch-stationary convolution kernel of i8ie_pconv.hip (8 waves, 16 x 16 x 64 MFMA tiles, epilogue
+// behind the K loop): the kernel argument block, the LDS plan it describes, and a few device helpers.
 #pragma once
 #include <cstdint>
 
@@ -51,7 +50,7 @@ struct PCArgs {
   // band are still there
   int pk, ps, PH, PW, RB, opitch, lds_otile, seq;
   float rcpPW, rcpC16, rcpRB;
-  unsigned long long* dbg;  // diagnostic build, variant 51: per block, cycles spent per phase (wave 0); null otherwise
+  unsigned long long* dbg;  // always 0 in this library; removing it changes the kernel's code
 };
 
 namespace {
@@ -80,12 +79,4 @@ extern __shared__ __attribute__((aligned(16))) uint8_t pc_smem[];
 // MFMA row r of a 16-row tile <-> pixel offset inside the tile (see the header: even pixels for rows 0-3, 12-15)
 __device__ __forceinline__ int pc_row_to_pix(int r) { return (r < 4) ? 2 * r : (r >= 12 ? 2 * (r - 8) : 2 * (r - 4) + 1); }
 
-
 }  // namespace
-
-#if defined(I8IE_DIAG)
-// tools/diag/csrc/i8ie_dconv.hip (diagnostic build): launches the deferred-epilogue kernel for a call pconv_impl (i8ie_pconv.hip) planned; `a` as for pconv_kernel
-// except Bf / perm (packed for this kernel's fragment order here, cached in the layer handle).  Returns I8IE_OK or an error.
-bool i8ie_dconv_eligible(int split, int nkt, int npass, int patch_gran, int PT, int bn, bool pool, int N);
-int i8ie_dconv_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c, PCArgs a, const int* perm_host, int PT, int bn, int grid, int lds, const char* name);
-#endif

@@ -199,23 +199,6 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
     for (int q = wave & 3; q < pieces; q += 4)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + q * 1024), 16, (q * 64 + lane) * 16, 0, 0, 0);
   };
-#if defined(I8IE_DIAG)
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, tq = 0;
-  auto stamp = [&](int i) {
-    if (p.dbg) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      ph[i] += now - tq;
-      tq = now;
-    }
-  };
-  auto stamps_out = [&]() {
-    if (p.dbg && lane == 0)
-      for (int i = 0; i < 6; ++i) p.dbg[((size_t)blockIdx.x * 8 + wave) * 8 + i] = ph[i];  // (role-relative wave number)
-  };
-#else
-  auto stamp = [](int) {};
-  auto stamps_out = []() {};
-#endif
 
   if (wave < 4) {
 #if defined(STEM_MPRIO)
@@ -266,9 +249,6 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
     strip_fetch(imn, tn, fa, fb);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     STEM_BAR();  // (the first patch)
-#if defined(I8IE_DIAG)
-    if (p.dbg) tq = __builtin_amdgcn_s_memtime();
-#endif
     for (int g = 0; g < G; ++g) {
       StemStrip en{};
       if (g + 1 < G) {  // the patch of strip g + 1 -> the other buffer (strip g - 1 was its last reader)
@@ -326,17 +306,11 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
           if constexpr (NA > 0)
             static_for<0, 4 * NA>([&](auto ic) { ring_store(std::integral_constant<int, decltype(ic)::value / 4>{}, std::integral_constant<int, decltype(ic)::value % 4>{}); });
         }
-        stamp(0);  // addresses, fragment reads, MFMAs (+ the first NG - 1 groups' ring stores)
         static_for<0, 4>([&](auto qc) { ring_store(std::integral_constant<int, NG - 1>{}, qc); });
-#if defined(I8IE_DIAG)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        stamp(1);  // ring writes
-#endif
       }
       strip_fetch(imn, tn, fa, fb);
       if (!STEM_DMA_VEC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the patch requested at the top of the interval has landed
       STEM_BAR();
-      stamp(2);  // at the barrier
       if (++t == T) {
         t = 0;
         ib += adv_of(un);
@@ -347,7 +321,6 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
       e = en;
     }
     STEM_BAR();  // the vector waves' last interval
-    stamps_out();
     return;
   }
 
@@ -361,9 +334,6 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
 #define STEM_VPRIO 0
 #endif
   if (STEM_VPRIO) __builtin_amdgcn_s_setprio(STEM_VPRIO);
-#if defined(I8IE_DIAG)
-  if (p.dbg_flags & 1) __builtin_amdgcn_s_setprio(3);  // experiment: the vector waves raised
-#endif
   const I8ieRequant rq = p.rq;
   const int lo_relu = p.relu_lo;
   const float lof = (float)lo_relu;
@@ -441,11 +411,6 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
 #pragma unroll
             for (int dx = 0; dx < PK; ++dx) v[u][dy * PK + dx] = *reinterpret_cast<const v4i*>(a + dx * PITCH);
           }
-#if defined(I8IE_DIAG)
-        stamp(1);  // (pool pass: scalar part, addresses, read issue)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        stamp(4);  // (pool pass: window reads landing)
-#endif
         uint32_t d[UN];
         float worst[UN];
         int c4[UN][4];
@@ -474,7 +439,6 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
 #pragma unroll
         for (int u = 0; u < UN; ++u) __builtin_amdgcn_raw_buffer_store_b32(d[u] ^ p.xor_out, rsO, tk[u].st, orow, 0);
         nst += UN;
-        stamp(5);  // (pool pass: maxima, requantiser, stores)
       };
       round(tk0, oc0);
       for (int k0 = vwave + 4 * UN; k0 < ntask; k0 += 4 * UN) {  // (more than 12 tasks to a pooled row: none of AlexNet's)
@@ -543,9 +507,6 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
   v4i fa, fb;  // the entry of the strip pooled in the next interval: fetched in front of every barrier, decoded behind it
   strip_fetch(im1, t1, fa, fb);
   STEM_BAR();
-#if defined(I8IE_DIAG)
-  if (p.dbg) tq = __builtin_amdgcn_s_memtime();
-#endif
   for (int g = 0; g <= G; ++g) {
     // interval g: the multiplying waves work on strip g (none at g == G); here: the pooled rows completed by strip g - 1.
     // The output stores stay in flight across the barriers (STEM_BAR waits for LDS operations only).
@@ -557,7 +518,6 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
       }
       nst = 0;
     }
-    stamp(0);  // patch request
     if (g >= 1) {
       const StemStrip e = strip_decode(fa, fb);
       const int img = im1 >> p.lg_parts;
@@ -577,14 +537,10 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
       }
     }
     strip_fetch(im1, t1, fa, fb);
-    stamp(1);  // pool pass
     if constexpr (ACC) wait_vm_keep(0);
     else if (STEM_DMA_VEC) wait_vm_keep(nst);  // the patch has landed; the stores issued behind it may stay in flight
-    stamp(2);
     STEM_BAR();
-    stamp(3);  // at the barrier
   }
-  stamps_out();
 }
 
 template <int NG, int KS, bool ACC>
@@ -792,49 +748,8 @@ int i8ie_stem_launch(i8ie_ctx* ctx, const I8ieStemCall& c) {
   const double ops = 2.0 * c.n * c.OH * c.OW * (double)c.N * c.c * c.KH * c.KW;
   const double bytes = (double)c.n * img_pitch + (double)out_bytes;
   a.role_split = ctx->pick.stem_simd_roles ? 1 : 0;  // (A/B of the role placement)
-#if defined(I8IE_DIAG)
-  const bool fused = s.pk == 3 && ctx->pick.stem_fused;  // (tools/diag/csrc/i8ie_stem_fused.hip: every wave in both roles)
-#endif
   I8ieProfScope prof(ctx, s.pk > 1 ? "stem_conv_pool" : "stem_conv", ops, bytes);
-#if defined(I8IE_DIAG)
-  static unsigned long long* dbg_dev[64] = {};
-  const bool stamps = std::getenv("I8IE_STEM_STAMPS") != nullptr;
-  if (stamps) {
-    if (!dbg_dev[dev]) I8IE_HIP_TRY(hipMalloc(&dbg_dev[dev], 4096 * 64 * sizeof(unsigned long long)));
-    I8IE_HIP_TRY(hipMemsetAsync(dbg_dev[dev], 0, 4096 * 64 * sizeof(unsigned long long), ctx->stream));
-    a.dbg = dbg_dev[dev];
-  }
-  if (const char* e = std::getenv("I8IE_STEM_FLAGS")) a.dbg_flags = std::atoi(e);
-  struct Report {
-    i8ie_ctx* ctx; unsigned long long* d; int grid, strips; bool on, fused;
-    ~Report() {
-      if (!on) return;
-      std::vector<unsigned long long> h((size_t)grid * 64);
-      if (hipStreamSynchronize(ctx->stream) != hipSuccess) return;
-      if (hipMemcpy(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return;
-      double sm[8][6] = {};
-      for (int b = 0; b < grid; ++b)
-        for (int w = 0; w < 8; ++w)
-          for (int i = 0; i < 6; ++i) sm[w][i] += (double)h[((size_t)b * 8 + w) * 8 + i];
-      const double n = (double)strips;  // strips in all (sum over blocks)
-      if (fused) {
-        fprintf(stderr, "stem_stamps (every wave in both roles): %d strips; per strip, cycles [region | ring stores + rest of the pool pass | patch wait + barrier]:", strips);
-        for (int w = 0; w < 8; ++w) fprintf(stderr, " w%d %.0f|%.0f|%.0f", w, sm[w][0] / n, sm[w][1] / n, sm[w][2] / n);
-        fprintf(stderr, "\n");
-        return;
-      }
-      fprintf(stderr, "stem_stamps: %d strips; per strip, cycles: multiplying waves [mfma | ring write | barrier]:", strips);
-      for (int w = 0; w < 4; ++w) fprintf(stderr, " w%d %.0f|%.0f|%.0f", w, sm[w][0] / n, sm[w][1] / n, sm[w][2] / n);
-      fprintf(stderr, " ; vector waves [patch request | pool: issue, reads landing, compute | patch wait | barrier]:");
-      for (int w = 4; w < 8; ++w) fprintf(stderr, " w%d %.0f|%.0f,%.0f,%.0f|%.0f|%.0f", w, sm[w][0] / n, sm[w][1] / n, sm[w][4] / n, sm[w][5] / n, sm[w][2] / n, sm[w][3] / n);
-      fprintf(stderr, "\n");
-    }
-  } report{ctx, a.dbg, grid, c.n * s.T * s.parts, a.dbg != nullptr, fused};
-#endif
   const int NG = c.N / 32;
-#if defined(I8IE_DIAG)
-  if (fused) return i8ie_stem_fused_launch(ctx, a, NG, s.KS, grid, s.lds);
-#endif
 #define I8IE_STEM_KS(NGV)                                                   \
   if (s.KS <= 6) return launch_stem<NGV, 6>(ctx, a, grid, s.lds);           \
   if (s.KS <= 10) return launch_stem<NGV, 10>(ctx, a, grid, s.lds);         \

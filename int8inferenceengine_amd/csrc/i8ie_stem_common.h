@@ -1,5 +1,4 @@
-// i8ie_stem_common.h -- what the first-stage kernels share: argument block, strip table, LDS helpers.  Included by
-// csrc/i8ie_stem.hip (the product kernel) and tools/diag/csrc/i8ie_stem_fused.hip (the every-wave-in-both-roles experiment).
+// i8ie_stem_common.h -- the first-stage kernel's argument block, strip table and LDS helpers (csrc/i8ie_stem.hip).
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -7,7 +6,7 @@
 #include "i8ie_internal.h"
 #include "i8ie_requant.h"
 
-// (at global scope: the diagnostic build passes it between translation units)
+// (at global scope: the kernel's name carries it)
 struct StemArgs {
   const uint8_t* img;  // s2d image [n][HY][WX][48], bytes re-biased (^0x80)
   unsigned img_pitch;  // bytes per image
@@ -33,8 +32,8 @@ struct StemArgs {
   int lds_patch, lds_ring, lds_ocp, lds_tab, lds_adv, lds_dump, lds_bfrag;  // LDS offsets (lds_dump: 2 KiB that lanes past a strip's last pixel store into; lds_bfrag: the last feature group's weights)
   unsigned out_bytes;
   float rcpOW;
-  unsigned long long* dbg;   // diagnostic build ($I8IE_STEM_STAMPS): per block and wave, cycles per phase; null otherwise
-  int dbg_flags;             // diagnostic build ($I8IE_STEM_FLAGS): 1 = vector waves at raised priority
+  unsigned long long* dbg;   // always 0 in this library; removing it changes the kernel's code
+  int dbg_flags;             // always 0 in this library; removing it changes the kernel's code
   int role_split;            // 0: waves 0-3 multiply, 4-7 do the vector work (a multiplying and a vector wave on every SIMD);
                              // 1: waves 0, 1, 4, 5 multiply, 2, 3, 6, 7 do the vector work (waves w and w + 4 share a SIMD: two
                              //    SIMDs multiply, two do vector work -- no vector wave sits beside an MFMA stream)
@@ -105,8 +104,3 @@ __device__ __forceinline__ void stem_fill_tables(const StemArgs& p, uint8_t* sme
   }
 }
 }  // namespace
-
-#if defined(I8IE_DIAG)
-// tools/diag/csrc/i8ie_stem_fused.hip (variant 16): every wave multiplies and pools
-int i8ie_stem_fused_launch(i8ie_ctx* ctx, const StemArgs& a, int NG, int KS, int grid, int lds);
-#endif

@@ -68,9 +68,9 @@ struct TCArgs {
   unsigned out_bytes;
   int ob, OHp, OWp;
   int lds_ring, lds_ocp, lds_tab, lds_ktab;  // LDS offsets
-  int flags;                                 // timing experiments (diagnostic build): 1 = no priority changes, 2 = teams in phase
+  int flags;                                 // always 0 in this library; removing it changes the kernel's code
   int32_t* acc;  // ACC kernels: [M][N] pre-requant accumulators (the cblas_gemm_s8u8s32 result, src/conv2d.cc:131-133)
-  unsigned long long* dbg;
+  unsigned long long* dbg;  // always 0 in this library; removing it changes the kernel's code
 };
 
 #define TC_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")  // (LDS writes of the re-bias pass are out before the hand-over)
@@ -261,18 +261,6 @@ __global__ __launch_bounds__(512, 2) void tconv_kernel(TCArgs p) {
     }
   };
 
-#if defined(I8IE_DIAG)
-  unsigned long long ph[4] = {0, 0, 0, 0}, tq = 0;
-  auto stamp = [&](int i) {
-    if (p.dbg) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      ph[i] += now - tq;
-      tq = now;
-    }
-  };
-#else
-  auto stamp = [](int) {};  // (phase stamps exist in the diagnostic build only: tools/diag)
-#endif
 
   // =============================== segments =============================================================
   // Segment sg of a team = (tile index sg / (2 npass), pass (sg / 2) % npass, K half sg & 1).  In the interval
@@ -284,9 +272,6 @@ __global__ __launch_bounds__(512, 2) void tconv_kernel(TCArgs p) {
   tc_wait_vm0();
   slice_rebias(0);
   __syncthreads();
-#if defined(I8IE_DIAG)
-  if (p.dbg) tq = __builtin_amdgcn_s_memtime();
-#endif
   for (int I = 0; I <= segs; ++I) {
     // ---- duty of this interval: the slice with first use in interval I + 1
     int duty_n = -1;
@@ -336,30 +321,21 @@ __global__ __launch_bounds__(512, 2) void tconv_kernel(TCArgs p) {
         load_A(Ahi, 1, patch, k0);
         load_B(B1, pass, ktn, 1);
       }
-      stamp(0);  // K loop
       if (duty_n >= 0) {
         tc_wait_vm0();
         slice_rebias(duty_n);
       }
-      stamp(1);  // wait for the slice + re-bias
       if (part) {
         if (p.flags & 4) __builtin_amdgcn_s_setprio(0);  // experiment: the requantising wave yields to the other team's MFMAs
         epilogue(tile0 + j * per, pass);
-        stamp(2);  // epilogue
       }
     } else if (duty_n >= 0) {
       tc_wait_vm0();
       slice_rebias(duty_n);
     }
     TC_BAR();
-    stamp(3);  // barrier
   }
   tc_wait_vm0();
-#if defined(I8IE_DIAG)
-  if (p.dbg && lane == 0 && (wave == 0 || wave == 4)) {
-    for (int i = 0; i < 4; ++i) p.dbg[blockIdx.x * 8 + (wave >> 2) * 4 + i] = ph[i];
-  }
-#endif
 }
 
 // ---- weights in fragment order for this kernel's K walk: [pass][kt][ks][ntile][lane][16]; K is ordered
@@ -505,10 +481,6 @@ int i8ie_tconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
     // the first K half is the longer one: the wave that goes on to the epilogue leaves the MFMA pipe to the other
     // team's wave earlier (epilogue ~ 5 k cycles ~ 2-3 K tiles of the pair)
     kt_split = (nkt + 1) / 2 + 1;
-#if defined(I8IE_DIAG)
-    static const char* const split_env = std::getenv("I8IE_TCONV_SPLIT");  // tuning aid, read once
-    if (split_env) kt_split = std::atoi(split_env);
-#endif
     if (kt_split > nkt - 1) kt_split = nkt - 1;
     if (kt_split < 1) kt_split = 1;
   }
@@ -574,9 +546,6 @@ int i8ie_tconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   a.lds_tab = a.lds_ocp + npass * bn * 4;
   a.lds_ktab = a.lds_tab + 2 * kTabPix * 4;
   const int lds = a.lds_ktab + nkt * 32;
-#if defined(I8IE_DIAG)
-  a.flags = ctx->pick.tconv_flags;
-#endif
 
   const double ops = 2.0 * c.M * c.N * c.Ktrue;
   const double bytes = (double)c.M * c.Ktrue + (double)c.N * c.Ktrue + (double)c.M * c.N;
@@ -585,36 +554,10 @@ int i8ie_tconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   char nm[32];
   snprintf(nm, sizeof(nm), "tconv_%dx%d", TMW * 32, bn);
   I8ieProfScope prof(ctx, ctx->prof ? tag : nm, ops, bytes);
-#if defined(I8IE_DIAG)
-  static unsigned long long* dbg_dev[64] = {};  // per device
-  unsigned long long*& dbg = dbg_dev[ctx->device & 63];
-  const bool stamps = ctx->pick.tconv_stamps;
-  if (stamps) {
-    if (!dbg) I8IE_HIP_TRY(hipMalloc(&dbg, 4096 * 8 * sizeof(unsigned long long)));
-    I8IE_HIP_TRY(hipMemsetAsync(dbg, 0, 4096 * 8 * sizeof(unsigned long long), ctx->stream));
-    a.dbg = dbg;
-  }
-#endif
   int rc;
   if (TMW == 8 && bn == 256) rc = launch_tc<8, 4>(ctx, a, grid, lds);
   else if (TMW == 6 && bn == 256) rc = launch_tc<6, 4>(ctx, a, grid, lds);
   else if (TMW == 6 && bn == 192) rc = launch_tc<6, 3>(ctx, a, grid, lds);
   else rc = launch_tc<8, 3>(ctx, a, grid, lds);
-#if defined(I8IE_DIAG)
-  if (rc == I8IE_OK && stamps && std::getenv("I8IE_TCONV_STAMPS") != nullptr) {
-    std::vector<unsigned long long> h((size_t)grid * 8);
-    I8IE_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    I8IE_HIP_TRY(hipMemcpy(h.data(), dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double sum[2][4] = {};
-    for (int b = 0; b < grid; ++b)
-      for (int t = 0; t < 2; ++t)
-        for (int i = 0; i < 4; ++i) sum[t][i] += (double)h[(size_t)b * 8 + t * 4 + i];
-    const double tp = (double)a.n_tiles * npass;  // tile passes in all
-    for (int t = 0; t < 2; ++t)
-      fprintf(stderr, "tconv_stamps v%d team %d M %d N %d K %d (%d tiles x %d passes, %d K tiles split at %d, TMW %d bn %d S %d R %d): per tile pass, cycles: K loops %.0f (%.0f per K tile) | slice wait + re-bias %.0f | epilogue %.0f | at barriers %.0f\n",
-              ctx->variant, t, c.M, c.N, c.Kchunks * 16, a.n_tiles, npass, nkt, kt_split, TMW, bn, S, R, sum[t][0] / tp, sum[t][0] / tp / nkt,
-              sum[t][1] / tp, sum[t][2] / tp, sum[t][3] / tp);
-  }
-#endif
   return rc == I8IE_OK ? 1 : rc;
 }

@@ -8,7 +8,7 @@ import re
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# ($I8IE_LIB: another build of the same C-ABI, e.g. the diagnostic build of tools/diag)
+# ($I8IE_LIB: another build of the same C-ABI, e.g. an A/B build of tools/dbg/build_ab.sh)
 LIB_PATH = os.environ.get("I8IE_LIB") or os.path.join(ROOT, "int8inferenceengine_amd", "libi8ie_hip.so")
 HEADER = os.path.join(ROOT, "include", "i8ie_hip.h")
 

@@ -328,11 +328,11 @@ def test_conv_batch_invariance_fused_at_bench_size(gpu, orc):
     assert np.array_equal(out[:4], cs["out"]) and np.array_equal(out[-4:], cs["out"])
 
 
-# ---- large-tile contraction kernels (256 x 256 / 256 x 192 block tiles, LDS-DMA staging) --------------
-# Selected for M >= 65 281 rows and N > 128 features; every output byte and INT32 accumulator of the whole
-# batch against the oracle, for the compiled staging variants (0 = default, 5 = one-stage DMA; the two-stage 256-row
-# form lives in the diagnostic build, tools/diag): ragged N (masked feature tiles, scalar store path), K tails that end inside a
-# 128-byte K tile, stride 2, bordered outputs, fused relu.
+# ---- large convolutions (M >= 65 281 rows, N > 128 features) ------------------------------------------------
+# Written for the 256 x 256 / 256 x 192 block tiles, retired at 9e2c9d6 with the other tile experiments.  Every output
+# byte and INT32 accumulator of the whole batch against the oracle, for variant 0 (automatic) and 5 (the tiled kernel,
+# one-stage DMA): ragged N (masked feature tiles, scalar store path), K tails that end inside a 128-byte K tile,
+# stride 2, bordered outputs, fused relu.
 LARGE_GEOMS = [
     (400, 128, 13, 13, 256, 3, 1, 1),  # N = 256: one 256-wide feature tile
     (400, 64, 13, 13, 384, 3, 1, 1),   # N = 384: two 192-wide tiles; K = 576 = 4.5 K tiles

@@ -1,8 +1,8 @@
-"""Every kernel variant include/i8ie_hip.h names, two numbers only the diagnostic build knows (4, 53) and one nobody
-knows (99), set process-wide through $I8IE_KERNEL_VARIANT: AlexNet at 125 and 260 images (its pooled conv layers at
-batch sizes where the patch-stationary kernel folds the pool, and where a forced choice leaves the pool to a launch of
-its own) and two_conv at 16 images, through the i8ie surface, logits bit for bit against the oracle with the qparams
-the child calibrated.  Probe and dispatch decide from the same decode (i8ie_conv_tries), so no value may end in the
+"""Every kernel variant include/i8ie_hip.h names and three numbers the library does not know (4, 53, 99), set
+process-wide through $I8IE_KERNEL_VARIANT: AlexNet at 125 and 260 images (its pooled conv layers at batch sizes where
+the patch-stationary kernel folds the pool, and where a forced choice leaves the pool to a launch of its own) and
+two_conv at 16 images, through the i8ie surface, logits bit for bit against the oracle with the qparams the child
+calibrated.  Probe and dispatch decide from the same decode (i8ie_conv_tries), so no value may end in the
 dispatcher's pool / re-biased-layout invariant.  One child process per value (the variable is read when a ctx is
 created), one after another; the first child that dies by a signal ends the test."""
 import json
@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NAMED = [0, 3, 5, 11, 12, 13, 50, 54, 70, 80, 81, 83, 84, 85]  # the I8IE_VARIANT_* of include/i8ie_hip.h
-VALUES = NAMED + [4, 53, 99]  # (diagnostic-build numbers and an unknown one: all behave like 0 in the product library)
+VALUES = NAMED + [4, 53, 99]  # (numbers the library does not know: all behave like 0)
 CASES = [("alexnet", 125), ("alexnet", 260), ("two_conv", 16)]
 
 CHILD = r'''

@@ -1,5 +1,5 @@
 // dma_probe.hip -- what does one LDS-DMA piece (buffer_load_dwordx4 ... lds, 1 KiB per wave-instruction) cost the
-// wave that issues it, and what does a CU sustain?  Tuning aid for csrc/i8ie_pp.hip (not part of the product).
+// wave that issues it, and what does a CU sustain?  Tuning aid (not part of the product).
 //   mode 0: buffer_load ... lds       mode 1: global_load_lds       mode 2: buffer_load to VGPRs (no LDS)
 // Every wave issues `pieces` instructions per round back to back, then waits vmcnt(0); `rounds` rounds.
 // The source is a per-CU window of `window` bytes (64 KiB: L2 / L1 resident; 64 MiB: streams from HBM / MALL).
