@@ -214,6 +214,10 @@ int i8ie_calib_sample_f32(i8ie_ctx* ctx, const float* data_dev, int64_t n, int64
 /* down_scale  src/quantize_utils.cc:27-36 (standalone requantiser; the layers fuse it) */
 int i8ie_down_scale(i8ie_ctx* ctx, const int32_t* acc_dev, uint8_t* out_dev, int64_t n, float sa,
                     float sb, float sc, uint8_t zp_c);
+/* the same per column: acc [rows, cols] int32, column j requantised with its own weight scale sb_dev[j]
+ * (device, float [cols]):  deq = ((float)C[., j] * sa) * sb[j];  q = deq / sc + (float)zp_c;  clamp / truncate */
+int i8ie_down_scale_per_channel(i8ie_ctx* ctx, const int32_t* acc_dev, uint8_t* out_dev, int64_t rows, int cols,
+                                float sa, const float* sb_dev, float sc, uint8_t zp_c);
 
 /* ---- FP32 ops: the path taken before convert() and while calibrating -------
  * Conv2d/Linear::forward_prop(Tensor<float>&&)  src/conv2d.cc:63-98, src/fully_connected.cc:5-21
@@ -234,6 +238,14 @@ int i8ie_maxpool2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n
  * s_w = (max - min) / 127, q = (s8)(x / s_w) truncating, unclamped.  Host pointers. */
 int i8ie_quantize_weight(const float* w_host, int64_t nw, const float* b_host, int64_t nb,
                          int8_t* qw_host, int8_t* qb_host, float* scale_out);
+/* per-output-channel weights (opt-in; not the reference's rule).  Row j = w[j*row_len .. +row_len) (Conv2d:
+ * in*kh*kw values, Linear: in), with its bias b[j] (b_host may be NULL: zero bias).  IEEE fp32:
+ *   a_j = max(max_k |w[j,k]|, |b[j]|);  s_w[j] = a_j / 127  (a_j == 0: 1)
+ *   q_w[j,k] = (s8) clamp(rint(w[j,k] / s_w[j]), -127, 127),  q_b[j] likewise   (rint: round half to even)
+ * scales_host: float [rows].  The bias stays s8 at its row's scale, so the offset vector and Linear's float bias
+ * step are unchanged; only the requantiser reads s_w[j] ("Per-channel weight scales"). */
+int i8ie_quantize_weight_per_channel(const float* w_host, int rows, int64_t row_len, const float* b_host,
+                                     int8_t* qw_host, int8_t* qb_host, float* scales_host);
 
 /* ---- zero-point offset vectors (device) --------------------------------- */
 /* src/conv2d.cc:117-124:  t_j = sum_k zp_in*q_w[j,k] accumulated sequentially in fp32;
@@ -274,6 +286,17 @@ int i8ie_linear_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_ho
                        float s_w, i8ie_layer** out);
 int i8ie_conv2d_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c,
                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out);
+/* the same with one weight scale per output feature: s_w_host float [n] / [kc], each finite and >= 0
+ * (I8IE_ERR_ARG otherwise).  Every forward entry point below then requantises column j with s_w[j]:
+ *   deq = ((float)C[., j] * s_in) * s_w[j];  q = deq / s_out + (float)zp_out  (down_scale per column)
+ * and takes the same kernels, layouts and fused pools as the per-tensor layer of the same shape. */
+int i8ie_linear_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int n, int k,
+                                   const float* s_w_host, i8ie_layer** out);
+int i8ie_conv2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c,
+                                   int kh, int kw, int stride, int pad, const float* s_w_host, i8ie_layer** out);
+/* the weight scales: out float [n] (n = out features); a per-tensor layer gives n copies of its scale and
+ * *per_channel = 0, a per-channel layer its s_w[j] and *per_channel = 1 */
+int i8ie_layer_weight_scales(const i8ie_layer* layer, float* out, int n, int* per_channel);
 /* the layer's output (scale_, zero_point_): src/layer.cc:44, include/layer.h:46-47 (default 1, 0) */
 int i8ie_layer_set_output_qparams(i8ie_layer* layer, float s_out, uint8_t zp_out);
 int i8ie_layer_get_output_qparams(const i8ie_layer* layer, float* s_out, uint8_t* zp_out);

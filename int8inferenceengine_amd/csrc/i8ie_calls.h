@@ -47,6 +47,11 @@ struct I8ieIgemmCall {
   // amode 1, honoured by i8ie_pconv.hip only (ask i8ie_pconv_takes first; the tiled kernel ignores them):
   int pool_k, pool_s;  // max_pool2d behind the (relu'd) convolution: `out` is then the pooled tensor, ob its border
   int a_s8, out_s8;    // input bytes / output bytes stored re-biased (^0x80: I8IE_LAYOUT_NHWC_S8)
+  // per-channel layers: [Npad] multipliers fl(s_in * s_w[j] / s_out) and [Npad] weight scales s_w[j] (i8ie_requant.h);
+  // s_w is then 1 when every column allows the guarded estimate and 0 when the layer takes the exact sequence.
+  // nullptr: a per-tensor layer (the kernels' per-tensor instances)
+  const float* msv = nullptr;
+  const float* sbv = nullptr;
 };
 // ONE definition of "this call carries a max-pool" for every file: a 1 x 1 window with a stride > 1 subsamples, so it IS a
 // pool (src/functional.cc:36-64 makes no exception for it); kernels that fold pools take k > 1 only and must decline it

@@ -67,6 +67,19 @@ __global__ __launch_bounds__(kThreads) void down_scale_kernel(const int32_t* __r
   }
 }
 
+// the same with column j's own weight scale: acc is [rows][cols], sb[cols] (per-channel layers)
+__global__ __launch_bounds__(kThreads) void down_scale_pc_kernel(const int32_t* __restrict__ acc,
+                                                                 uint8_t* __restrict__ out, int64_t n, int cols,
+                                                                 float sa, const float* __restrict__ sb, float sc,
+                                                                 float zpf) {
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
+    float deq = ((float)acc[i] * sa) * sb[i % cols];
+    float q = deq / sc + zpf;
+    out[i] = (q >= 255.0f) ? (uint8_t)255 : ((q < 0.0f) ? (uint8_t)0 : (uint8_t)(int)q);
+  }
+}
+
 // ---- a7: src/functional.cc:15-26 -------------------------------------------
 __device__ __forceinline__ uint32_t max_u8x4(uint32_t a, uint32_t b) {
   uint32_t r = 0;
@@ -244,6 +257,19 @@ int i8ie_down_scale(i8ie_ctx* ctx, const int32_t* acc, uint8_t* out, int64_t n, 
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   I8ieProfScope prof(ctx, "down_scale", 0.0, 5.0 * n);
   down_scale_kernel<<<grid_for(n), kThreads, 0, ctx->stream>>>(acc, out, n, sa, sb, sc, (float)zp_c);
+  I8IE_LAUNCH_CHECK();
+  return I8IE_OK;
+}
+
+int i8ie_down_scale_per_channel(i8ie_ctx* ctx, const int32_t* acc, uint8_t* out, int64_t rows, int cols, float sa,
+                                const float* sb_dev, float sc, uint8_t zp_c) {
+  I8IE_REQUIRE(ctx && acc && out && sb_dev, "null argument");
+  I8IE_REQUIRE(rows >= 0 && cols > 0, "bad shape");
+  if (rows == 0) return I8IE_OK;
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  const int64_t n = rows * cols;
+  I8ieProfScope prof(ctx, "down_scale_per_channel", 0.0, 5.0 * n);
+  down_scale_pc_kernel<<<grid_for(n), kThreads, 0, ctx->stream>>>(acc, out, n, cols, sa, sb_dev, sc, (float)zp_c);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }

@@ -67,6 +67,8 @@ struct FirstArgs {
   int ob;
   int toff[2 * kMaxKS];  // LDS byte offset of K chunk q inside a pixel's window
   int32_t* acc;          // ACC kernels: [n * OH * OW][N] pre-requant accumulators (the cblas_gemm_s8u8s32 result, src/conv2d.cc:131-133)
+  const float* msv;      // PC kernels (per-channel layers): [Npad] multipliers and weight scales (i8ie_requant.h)
+  const float* sbv;
 };
 
 // ---- quantize + repack: FP32 NCHW -> grouped u8 [n][Hp][WG][16] -------------------------------
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(256) void quantize_repack_kernel(const float* __res
 
 // ACC: also dump the INT32 accumulators (acc_dbg of the C-ABI) -- a separate instantiation, the default one is untouched
 // FUSEQ: always false (the quantising patch fill was retired); it stays because it is part of the kernel's name
-template <int KS, bool FUSEQ, bool ACC>
+template <int KS, bool FUSEQ, bool ACC, bool PC>
 __global__ __launch_bounds__(512) void conv_smallc_kernel(FirstArgs p) {
   static_assert(!FUSEQ, "the quantising patch fill was retired");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -282,8 +284,14 @@ __global__ __launch_bounds__(512) void conv_smallc_kernel(FirstArgs p) {
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const uint32_t packed =
-              frequant_pack4(acc[g * 4 + 0], acc[g * 4 + 1], acc[g * 4 + 2], acc[g * 4 + 3], rq, lo, lof);
+          uint32_t packed;
+          if constexpr (PC) {  // features wave * 32 + 8 g + 4 hh .. + 3 (N % 32 == 0: all exist)
+            const int j0 = wave * 32 + 8 * g + 4 * hh;
+            const int c4[4] = {acc[g * 4 + 0], acc[g * 4 + 1], acc[g * 4 + 2], acc[g * 4 + 3]};
+            packed = i8ie_requant_pack4_pc(c4, rq, *reinterpret_cast<const float4*>(p.msv + j0), p.sbv + j0, lo, lof);
+          } else {
+            packed = frequant_pack4(acc[g * 4 + 0], acc[g * 4 + 1], acc[g * 4 + 2], acc[g * 4 + 3], rq, lo, lof);
+          }
           *reinterpret_cast<uint32_t*>(scratch + (lane & 31) * 36 + 8 * g + 4 * hh) = packed;
         }
         // wave-private transpose: lane l stores 16 bytes (features 16*(l&1) .. +15) of pixel l >> 1
@@ -308,17 +316,19 @@ __global__ __launch_bounds__(512) void conv_smallc_kernel(FirstArgs p) {
   }
 }
 
-template <int KS, bool FUSEQ, bool ACC>
+template <int KS, bool FUSEQ, bool ACC, bool PC>
 int launch_first_qa(i8ie_ctx* ctx, const FirstArgs& a, int blocks, int threads, size_t lds) {
-  I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_smallc_kernel<KS, FUSEQ, ACC>),
+  I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_smallc_kernel<KS, FUSEQ, ACC, PC>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  conv_smallc_kernel<KS, FUSEQ, ACC><<<blocks, threads, lds, ctx->stream>>>(a);
+  conv_smallc_kernel<KS, FUSEQ, ACC, PC><<<blocks, threads, lds, ctx->stream>>>(a);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }
 template <int KS>
 int launch_first(i8ie_ctx* ctx, const FirstArgs& a, int blocks, int threads, size_t lds) {
-  return a.acc != nullptr ? launch_first_qa<KS, false, true>(ctx, a, blocks, threads, lds) : launch_first_qa<KS, false, false>(ctx, a, blocks, threads, lds);
+  if (a.msv != nullptr)
+    return a.acc != nullptr ? launch_first_qa<KS, false, true, true>(ctx, a, blocks, threads, lds) : launch_first_qa<KS, false, false, true>(ctx, a, blocks, threads, lds);
+  return a.acc != nullptr ? launch_first_qa<KS, false, true, false>(ctx, a, blocks, threads, lds) : launch_first_qa<KS, false, false, false>(ctx, a, blocks, threads, lds);
 }
 
 }  // namespace
@@ -339,6 +349,8 @@ struct I8ieFirstCall {
   uint8_t* out;
   int ob;
   int32_t* acc;  // null, or [n * OH * OW][N]
+  const float* msv;  // per-channel layers: [Npad] multipliers and weight scales (i8ie_requant.h); null otherwise
+  const float* sbv;
 };
 
 int i8ie_first_supported(int c, int stride, int n_out, int K2, int KH, int KWG, int OW) {
@@ -403,7 +415,7 @@ int i8ie_first_launch(i8ie_ctx* ctx, const I8ieFirstCall& c) {
   a.B = c.B; a.Kpad = c.Kpad; a.N = c.N; a.ocp = c.ocp;
   a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
   a.relu_lo = c.relu ? c.zp_out : 0;
-  a.out = c.out; a.ob = c.ob; a.acc = c.acc;
+  a.out = c.out; a.ob = c.ob; a.acc = c.acc; a.msv = c.msv; a.sbv = c.sbv;
   const int ks_needed = (c.K2 + 31) / 32;
   const int nchunks = c.KH * c.KWG;
   for (int q = 0; q < 2 * kMaxKS; ++q) {

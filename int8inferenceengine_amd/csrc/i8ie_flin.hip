@@ -43,6 +43,8 @@ struct FlinArgs {
   int relu_lo;
   uint8_t* out;
   int32_t* acc;
+  const float* msv;  // PC kernels (per-channel layers): [Npad] multipliers and weight scales (i8ie_requant.h)
+  const float* sbv;
 };
 
 constexpr int kChunk = 256;  // K bytes per chunk
@@ -59,7 +61,7 @@ struct FlinShape {
   static constexpr int kLds = STAGES * kStage;
 };
 
-template <int RT, int FT, int STAGES>
+template <int RT, int FT, int STAGES, bool PC>
 __global__ __launch_bounds__(512) void flin_kernel(FlinArgs p) {
   using S = FlinShape<RT, FT, STAGES>;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -140,7 +142,9 @@ __global__ __launch_bounds__(512) void flin_kernel(FlinArgs p) {
         if (p.biasf != nullptr) cv[r] = (int)((float)cv[r] + p.biasf[n + r]);
       }
     }
-    const uint32_t packed = i8ie_requant_pack4(cv, p.rq, p.relu_lo, (float)p.relu_lo);
+    // (n < N <= Npad, n % 4 == 0: the quad lies inside the padded arrays)
+    const uint32_t packed = PC ? i8ie_requant_pack4_pc(cv, p.rq, *reinterpret_cast<const float4*>(p.msv + n), p.sbv + n, p.relu_lo, (float)p.relu_lo)
+                               : i8ie_requant_pack4(cv, p.rq, p.relu_lo, (float)p.relu_lo);
     uint8_t* o = p.out + (size_t)row * p.N + n;
     if (n + 3 < p.N && (p.N & 3) == 0) {
       *reinterpret_cast<uint32_t*>(o) = packed;
@@ -163,20 +167,23 @@ bool i8ie_flin_wants(int m, int n, int Kpad, bool force) {
   return m <= 256 && n >= (force ? 16 : 2048) && Kpad >= 1024 && Kpad % kChunk == 0;
 }
 
-template <int RT, int FT, int STAGES>
+template <int RT, int FT, int STAGES, bool PC>
 static int flin_launch_t(i8ie_ctx* ctx, const FlinArgs& a, int M, int N) {
   using S = FlinShape<RT, FT, STAGES>;
   static bool raised[64] = {};
   const int dev = ctx->device & 63;
   if (!raised[dev]) {
-    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&flin_kernel<RT, FT, STAGES>), hipFuncAttributeMaxDynamicSharedMemorySize, S::kLds));
+    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&flin_kernel<RT, FT, STAGES, PC>), hipFuncAttributeMaxDynamicSharedMemorySize, S::kLds));
     raised[dev] = true;
   }
   const dim3 grid((unsigned)((N + S::kFeats - 1) / S::kFeats), (unsigned)((M + S::kRows - 1) / S::kRows));
-  flin_kernel<RT, FT, STAGES><<<grid, 512, S::kLds, ctx->stream>>>(a);
+  flin_kernel<RT, FT, STAGES, PC><<<grid, 512, S::kLds, ctx->stream>>>(a);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }
+
+template <bool PC>
+static int flin_shape(i8ie_ctx* ctx, const FlinArgs& a, const I8ieIgemmCall& c);
 
 int i8ie_flin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   I8IE_REQUIRE(c.amode == 0 && c.M > 0 && c.M <= 256 && c.N > 0 && c.Kpad % kChunk == 0, "flin: shape");
@@ -190,13 +197,19 @@ int i8ie_flin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   a.ocp = c.ocp; a.biasf = c.biasf;
   a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
   a.relu_lo = c.relu ? c.zp_out : 0;
-  a.out = c.out; a.acc = c.acc;
+  a.out = c.out; a.acc = c.acc; a.msv = c.msv; a.sbv = c.sbv;
+  if (c.msv != nullptr) return flin_shape<true>(ctx, a, c);
+  return flin_shape<false>(ctx, a, c);
+}
+
+template <bool PC>
+static int flin_shape(i8ie_ctx* ctx, const FlinArgs& a, const I8ieIgemmCall& c) {
   const double ops = 2.0 * c.M * c.N * c.Ktrue, bytes = (double)c.M * c.Ktrue + (double)c.N * c.Ktrue + (double)c.M * c.N;
   if (c.M <= 64 || (ctx->pick.linear == I8IE_LIN_FLIN128 && c.M <= 128)) {  // (81: the 128-row form at any row count up to 128, for A/B runs)
     I8ieProfScope prof(ctx, "flin_128x16", ops, bytes);
-    return flin_launch_t<8, 1, 4>(ctx, a, c.M, c.N);
+    return flin_launch_t<8, 1, 4, PC>(ctx, a, c.M, c.N);
   }
   I8ieProfScope prof(ctx, "flin_64x32", ops, bytes);
-  if (c.M <= 128) return flin_launch_t<4, 2, 4>(ctx, a, c.M, c.N);
-  return flin_launch_t<4, 2, 3>(ctx, a, c.M, c.N);  // (72 KB of LDS: two blocks per CU)
+  if (c.M <= 128) return flin_launch_t<4, 2, 4, PC>(ctx, a, c.M, c.N);
+  return flin_launch_t<4, 2, 3, PC>(ctx, a, c.M, c.N);  // (72 KB of LDS: two blocks per CU)
 }

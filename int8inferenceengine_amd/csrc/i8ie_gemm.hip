@@ -36,7 +36,7 @@ __device__ __forceinline__ uint8_t requant_u8(int c, float sa, float sb, float s
   return (uint8_t)i8ie_requant_exact((float)c, q, 0);
 }
 
-template <int WM, int WN, int TM, int TN>
+template <int WM, int WN, int TM, int TN, bool PC>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_u8s8_kernel(I8ieGemmArgs p, int tiles_m,
                                                                 int tiles_n, int m_fastest) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
@@ -179,6 +179,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_u8s8_kernel(I8ieGemmArgs p, 
     const int gcol = n0 + lcol;
     float bias_f = 0.0f;
     if (p.qb != nullptr && gcol < p.N) bias_f = (float)p.qb[gcol] / sa;  // src/fully_connected.cc:44
+    const float sbj = PC ? (gcol < p.N ? p.sbv[gcol] : 1.0f) : sb;  // per-channel: column j's own s_w
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi) {
 #pragma unroll
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_u8s8_kernel(I8ieGemmArgs p, 
           const int grow = m0 + lrow0 + r;
           if (p.acc != nullptr && grow < p.M && gcol < p.N) p.acc[(size_t)grow * p.N + gcol] = c;
           if (p.qb != nullptr) c = (int)((float)c + bias_f);
-          const uint32_t u = requant_u8(c, sa, sb, sc, zpf);
+          const uint32_t u = requant_u8(c, sa, sbj, sc, zpf);
           packed |= u << (8 * r);
           if (!nchw) smem[(lrow0 + r) * SROW_R + lcol] = (uint8_t)u;
         }
@@ -338,7 +339,7 @@ inline int cap_grid(int64_t items, int threads) {
   return (int)(b > 256 * 16 ? 256 * 16 : b);
 }
 
-template <int WM, int WN, int TM, int TN>
+template <int WM, int WN, int TM, int TN, bool PC>
 int launch_cfg(i8ie_ctx* ctx, const I8ieGemmArgs& a) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
@@ -349,7 +350,7 @@ int launch_cfg(i8ie_ctx* ctx, const I8ieGemmArgs& a) {
                              : BN == 64 ? "gemm_u8s8_128x64" : "gemm_u8s8_128x32";
   const double kt = a.Ktrue > 0 ? a.Ktrue : a.Kpad;
   I8ieProfScope prof(ctx, kName, 2.0 * a.M * a.N * kt, (double)a.M * kt + (double)a.N * kt + (double)a.M * a.N);
-  gemm_u8s8_kernel<WM, WN, TM, TN>
+  gemm_u8s8_kernel<WM, WN, TM, TN, PC>
       <<<tiles_m * tiles_n, WM * WN * 64, 0, ctx->stream>>>(a, tiles_m, tiles_n, m_fastest);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
@@ -363,10 +364,16 @@ int i8ie_gemm_launch(i8ie_ctx* ctx, const I8ieGemmArgs& a) {
   I8IE_REQUIRE((reinterpret_cast<uintptr_t>(a.A) & 15u) == 0 && (reinterpret_cast<uintptr_t>(a.B) & 15u) == 0,
                "operands must be 16-byte aligned");
   I8IE_REQUIRE((long long)a.M * a.N < (1LL << 40), "output too large");
-  if (a.N <= 32) return launch_cfg<4, 1, 1, 1>(ctx, a);
-  if (a.N <= 64) return launch_cfg<2, 2, 2, 1>(ctx, a);
-  if (a.N <= 96) return launch_cfg<4, 1, 1, 3>(ctx, a);
-  return launch_cfg<2, 2, 2, 2>(ctx, a);
+  if (a.sbv != nullptr) {  // per-channel layer
+    if (a.N <= 32) return launch_cfg<4, 1, 1, 1, true>(ctx, a);
+    if (a.N <= 64) return launch_cfg<2, 2, 2, 1, true>(ctx, a);
+    if (a.N <= 96) return launch_cfg<4, 1, 1, 3, true>(ctx, a);
+    return launch_cfg<2, 2, 2, 2, true>(ctx, a);
+  }
+  if (a.N <= 32) return launch_cfg<4, 1, 1, 1, false>(ctx, a);
+  if (a.N <= 64) return launch_cfg<2, 2, 2, 1, false>(ctx, a);
+  if (a.N <= 96) return launch_cfg<4, 1, 1, 3, false>(ctx, a);
+  return launch_cfg<2, 2, 2, 2, false>(ctx, a);
 }
 
 // ---- helpers shared with i8ie_layer.hip ----------------------------------------

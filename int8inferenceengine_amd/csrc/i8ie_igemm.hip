@@ -76,6 +76,9 @@ struct IgemmArgs {
   // [slice][M][N] to `partial` and skip the epilogue; splitk_reduce_kernel finishes
   int ksplit, tiles_per_slice;
   int32_t* partial;
+  // per-channel layers (PC kernels): [Npad] multipliers and [Npad] weight scales (i8ie_requant.h); null otherwise
+  const float* msv;
+  const float* sbv;
 };
 
 // VAR (staging forms, identical results), both one LDS stage and two barriers per K tile (half the LDS of two
@@ -86,7 +89,7 @@ struct IgemmArgs {
 //     ds_read_b128 fragments), the u8 -> s8 re-bias applied to the A fragments after the read.
 // The measured and retired forms (two stages, loads two K tiles ahead, s_setprio around the MFMAs, two 64 KiB DMA
 // stages for 256-row tiles) are at 9e2c9d6.
-template <int AMODE, int WM, int WN, int TM, int TN, bool BIAS, bool ACC, int VAR>
+template <int AMODE, int WM, int WN, int TM, int TN, bool BIAS, bool ACC, int VAR, bool PC>
 __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, int tiles_m, int tiles_n,
                                                                  int m_fastest) {
   static_assert(VAR == 3 || VAR == 5, "staging form");
@@ -412,6 +415,9 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
       if (BIAS && gcol0 < p.N) bfv = *reinterpret_cast<const float4*>(p.biasf + gcol0);  // padded to Npad
       // (feature tiles wider than 128 may run past Npad: columns >= N are never stored)
       const int4 ocv = gcol0 < p.N ? *reinterpret_cast<const int4*>(p.ocp + gcol0) : make_int4(0, 0, 0, 0);
+      float4 msq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (PC && gcol0 < p.N) msq = *reinterpret_cast<const float4*>(p.msv + gcol0);  // padded to Npad, like ocp
+      const float* sbq = PC ? p.sbv + (gcol0 < p.N ? gcol0 : 0) : nullptr;
 #pragma unroll
       for (int mi = 0; mi < TM; ++mi) {
         const int lrow = (wm * TM + mi) * 32 + (lane & 31);
@@ -426,7 +432,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
           if (BIAS) c = (int)((float)c + (r == 0 ? bfv.x : r == 1 ? bfv.y : r == 2 ? bfv.z : bfv.w));  // src/fully_connected.cc:44
           cv[r] = c;
         }
-        const uint32_t packed = requant_pack4(cv, rq, lo, lof);
+        const uint32_t packed = PC ? i8ie_requant_pack4_pc(cv, rq, msq, sbq, lo, lof) : requant_pack4(cv, rq, lo, lof);
         *reinterpret_cast<uint32_t*>(smem + lrow * SROW + lcol0) = packed;
       }
     }
@@ -706,11 +712,12 @@ struct SmallNArgs {
   float* out_f32;    // [M][N] or nullptr: (q - zp_out) * s_out
   float dq_scale;
   int dq_zp;
+  const float* sbv;  // per-channel layers: [N] weight scales (the head always takes the exact sequence); else nullptr
 };
 
 // WPR = waves per row: 1 (four rows per block) for short K, 4 (one row per block, K split over 256 threads
 // and the four partial sums joined through LDS) when K is long enough to make one wave's walk a latency chain
-template <int WPR>
+template <int WPR, bool PC>
 __global__ __launch_bounds__(256) void linear_smalln_kernel(SmallNArgs p) {
   __shared__ int part[4][kSmallN];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -764,7 +771,7 @@ __global__ __launch_bounds__(256) void linear_smalln_kernel(SmallNArgs p) {
     const size_t o = (size_t)row * p.N + lane;
     if (p.acc) p.acc[o] = c;
     c = (int)((float)c + p.biasf[lane]);  // src/fully_connected.cc:44
-    const int q = requant_exact((float)c, p.rq, p.relu_lo);
+    const int q = PC ? i8ie_requant_exact_col((float)c, p.rq, p.sbv[lane], p.relu_lo) : requant_exact((float)c, p.rq, p.relu_lo);
     if (p.out) p.out[o] = (uint8_t)q;
     if (p.out_f32) p.out_f32[o] = (float)(q - p.dq_zp) * p.dq_scale;  // src/quantize_utils.cc:38-42
   }
@@ -776,6 +783,7 @@ __global__ __launch_bounds__(256) void linear_smalln_kernel(SmallNArgs p) {
 // of 60 cross-lane adds per row after its loads (11-13 us for fc8 whatever the batch); this one is one memory
 // round trip, 8 MFMAs and one LDS exchange.
 constexpr int kHeadSteps = 8;  // K steps in flight per wave and round
+template <bool PC>
 __global__ __launch_bounds__(512) void linear_head_mfma_kernel(SmallNArgs p) {
   __shared__ __attribute__((aligned(16))) int part[8 * 16 * 16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -817,7 +825,7 @@ __global__ __launch_bounds__(512) void linear_head_mfma_kernel(SmallNArgs p) {
       const size_t o = (size_t)row * p.N + j;
       if (p.acc) p.acc[o] = c;
       c = (int)((float)c + p.biasf[j]);  // src/fully_connected.cc:44
-      const int q = requant_exact((float)c, p.rq, p.relu_lo);
+      const int q = PC ? i8ie_requant_exact_col((float)c, p.rq, p.sbv[j], p.relu_lo) : requant_exact((float)c, p.rq, p.relu_lo);
       if (p.out) p.out[o] = (uint8_t)q;
       if (p.out_f32) p.out_f32[o] = (float)(q - p.dq_zp) * p.dq_scale;  // src/quantize_utils.cc:38-42
     }
@@ -854,10 +862,13 @@ __global__ __launch_bounds__(64) void finish_offsets_kernel(const int32_t* __res
 
 // split-K finish: C = sum of the slices' partials (slice 0 carries ocp), then the Linear epilogue of
 // src/fully_connected.cc:42-48 on 4 consecutive features per thread
+// (PC: per-channel layers, msv / sbv [N]; the 4 values of a thread may straddle a row end, so each finds its own column)
+template <bool PC>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const int32_t* __restrict__ partial, int ksplit, int M,
                                                             int N, const float* __restrict__ biasf, Requant rq,
                                                             int relu_lo, uint8_t* __restrict__ out,
-                                                            int32_t* __restrict__ acc) {
+                                                            int32_t* __restrict__ acc, const float* __restrict__ msv,
+                                                            const float* __restrict__ sbv) {
   const int64_t total = (int64_t)M * N;
   const int64_t gstride = (int64_t)gridDim.x * 256;
   const float lof = (float)relu_lo;
@@ -874,7 +885,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const int32_t* __res
       }
       cv[r] = c;
     }
-    const uint32_t packed = requant_pack4(cv, rq, relu_lo, lof);
+    uint32_t packed;
+    if constexpr (PC) {
+      float ms[4], sb[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = (int)((e + (r < nvalid ? r : 0)) % N);
+        ms[r] = msv[j];
+        sb[r] = sbv[j];
+      }
+      packed = i8ie_requant_pack4_pc(cv, rq, make_float4(ms[0], ms[1], ms[2], ms[3]), sb, relu_lo, lof);
+    } else {
+      packed = requant_pack4(cv, rq, relu_lo, lof);
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (r < nvalid) out[e + r] = (uint8_t)(packed >> (8 * r));
@@ -887,7 +910,7 @@ inline int cap_grid(int64_t items, int threads, int max_blocks = 256 * 16) {
   return (int)(b > max_blocks ? max_blocks : b);
 }
 
-template <int AMODE, int WM, int WN, int TM, int TN, bool BIAS, bool ACC, int VAR>
+template <int AMODE, int WM, int WN, int TM, int TN, bool BIAS, bool ACC, int VAR, bool PC>
 int launch_cfg(i8ie_ctx* ctx, const IgemmArgs& a, const char* name, int kbytes, double ops, double bytes) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
@@ -895,14 +918,14 @@ int launch_cfg(i8ie_ctx* ctx, const IgemmArgs& a, const char* name, int kbytes, 
   char tag[64];
   snprintf(tag, sizeof(tag), "%s|M%d,N%d,K%d", name, a.M, a.N, kbytes);
   I8ieProfScope prof(ctx, ctx->prof ? tag : name, ops, bytes);
-  igemm_u8s8_kernel<AMODE, WM, WN, TM, TN, BIAS, ACC, VAR>
+  igemm_u8s8_kernel<AMODE, WM, WN, TM, TN, BIAS, ACC, VAR, PC>
       <<<dim3(tiles_m * tiles_n, a.ksplit > 1 ? a.ksplit : 1), WM * WN * 64, 0, ctx->stream>>>(
           a, tiles_m, tiles_n, m_fastest);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }
 
-template <int AMODE, bool BIAS, bool ACC, int VAR>
+template <int AMODE, bool BIAS, bool ACC, int VAR, bool PC>
 int launch_tile_var(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, double bytes) {
   // widest N tile that still gives the chip enough blocks: small-M Linear layers (one or a few M tiles)
   // otherwise run on N/128 blocks only (M = 125, N = 4096: 32 blocks on 256 CUs)
@@ -915,15 +938,15 @@ int launch_tile_var(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, d
     if (tiles_m * ((a.N + 63) / 64) < 256 && a.ksplit <= 1) bn = 32;
   }
   if (bn == 32)
-    return launch_cfg<AMODE, 4, 1, 1, 1, BIAS, ACC, VAR>(ctx, a, AMODE ? "igemm_conv_128x32" : "igemm_lin_128x32", kbytes,
+    return launch_cfg<AMODE, 4, 1, 1, 1, BIAS, ACC, VAR, PC>(ctx, a, AMODE ? "igemm_conv_128x32" : "igemm_lin_128x32", kbytes,
                                                          ops, bytes);
   if (bn == 64)
-    return launch_cfg<AMODE, 2, 2, 2, 1, BIAS, ACC, VAR>(ctx, a, AMODE ? "igemm_conv_128x64" : "igemm_lin_128x64", kbytes,
+    return launch_cfg<AMODE, 2, 2, 2, 1, BIAS, ACC, VAR, PC>(ctx, a, AMODE ? "igemm_conv_128x64" : "igemm_lin_128x64", kbytes,
                                                          ops, bytes);
   if (bn == 96)
-    return launch_cfg<AMODE, 4, 1, 1, 3, BIAS, ACC, VAR>(ctx, a, AMODE ? "igemm_conv_128x96" : "igemm_lin_128x96", kbytes,
+    return launch_cfg<AMODE, 4, 1, 1, 3, BIAS, ACC, VAR, PC>(ctx, a, AMODE ? "igemm_conv_128x96" : "igemm_lin_128x96", kbytes,
                                                          ops, bytes);
-  return launch_cfg<AMODE, 2, 2, 2, 2, BIAS, ACC, VAR>(ctx, a, AMODE ? "igemm_conv_128x128" : "igemm_lin_128x128", kbytes,
+  return launch_cfg<AMODE, 2, 2, 2, 2, BIAS, ACC, VAR, PC>(ctx, a, AMODE ? "igemm_conv_128x128" : "igemm_lin_128x128", kbytes,
                                                        ops, bytes);
 }
 
@@ -933,7 +956,7 @@ int launch_tile_var(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, d
 // within 2 % of the baseline; the 256-row two-stage DMA form 10-20 % slower on these K depths (DESIGN.md,
 // "what bounds the contraction kernel"; the retired forms are at 9e2c9d6).  ctx->pick.conv_tile / linear_tile
 // select the staging form.
-template <int AMODE, bool BIAS, bool ACC>
+template <int AMODE, bool BIAS, bool ACC, bool PC = false>
 int launch_tile(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, double bytes) {
   const int tile = AMODE == 1 ? ctx->pick.conv_tile : ctx->pick.linear_tile;
   if (AMODE == 1 && !BIAS && !ACC) {
@@ -941,12 +964,12 @@ int launch_tile(i8ie_ctx* ctx, const IgemmArgs& a, int kbytes, double ops, doubl
     // per CU; measured 2.5-4 % faster than 128 x 128 on AlexNet conv2-5.  A variant that names a staging form or tile
     // shape of THIS kernel switches it to 128 x 128; the others leave the tiled kernel's default alone
     if (tile == I8IE_TILE_DEFAULT && a.N > 64 && a.M >= 192 * 256)
-      return launch_cfg<1, 2, 2, 3, 2, false, false, 5>(ctx, a, "igemm_conv_192x128", kbytes, ops, bytes);
+      return launch_cfg<1, 2, 2, 3, 2, false, false, 5, PC>(ctx, a, "igemm_conv_192x128", kbytes, ops, bytes);
   }
   // Linear (few, short split-K slices per block) measured 20 % slower with DMA staging: register staging there
   if (AMODE == 1 ? tile == I8IE_TILE_REG : tile != I8IE_TILE_DMA)
-    return launch_tile_var<AMODE, BIAS, ACC, 3>(ctx, a, kbytes, ops, bytes);
-  return launch_tile_var<AMODE, BIAS, ACC, 5>(ctx, a, kbytes, ops, bytes);
+    return launch_tile_var<AMODE, BIAS, ACC, 3, PC>(ctx, a, kbytes, ops, bytes);
+  return launch_tile_var<AMODE, BIAS, ACC, 5, PC>(ctx, a, kbytes, ops, bytes);
 }
 
 }  // namespace
@@ -1052,6 +1075,8 @@ int i8ie_igemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   a.vec_store = ((c.N & 15) == 0 && (reinterpret_cast<uintptr_t>(c.out) & 15u) == 0) ? 1 : 0;
   I8IE_REQUIRE(a.ob == 0 || a.vec_store, "bordered output needs N % 16 == 0");
   a.acc = c.acc;
+  a.msv = c.msv;
+  a.sbv = c.sbv;
   const double ops = 2.0 * c.M * c.N * c.Ktrue;
   const double bytes = (double)c.M * c.Ktrue + (double)c.N * c.Ktrue + (double)c.M * c.N;
   const int kb = c.Kchunks * 16;
@@ -1065,12 +1090,24 @@ int i8ie_igemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
       I8IE_TRY((launch_tile<0, false, false>(ctx, a, kb, ops, bytes)));
       I8ieProfScope prof(ctx, "splitk_reduce", 0.0, 4.0 * a.ksplit * c.M * c.N + (double)c.M * c.N);
       const int64_t quads = ((int64_t)c.M * c.N + 3) / 4;
-      splitk_reduce_kernel<<<cap_grid(quads, 256), 256, 0, ctx->stream>>>(c.partial, a.ksplit, c.M, c.N, c.biasf, a.rq,
-                                                                          a.relu_lo, c.out, c.acc);
+      if (c.msv != nullptr)
+        splitk_reduce_kernel<true><<<cap_grid(quads, 256), 256, 0, ctx->stream>>>(c.partial, a.ksplit, c.M, c.N, c.biasf, a.rq,
+                                                                                  a.relu_lo, c.out, c.acc, c.msv, c.sbv);
+      else
+        splitk_reduce_kernel<false><<<cap_grid(quads, 256), 256, 0, ctx->stream>>>(c.partial, a.ksplit, c.M, c.N, c.biasf, a.rq,
+                                                                                   a.relu_lo, c.out, c.acc, nullptr, nullptr);
       I8IE_LAUNCH_CHECK();
       return I8IE_OK;
     }
     a.ksplit = 0;
+  }
+  if (c.msv != nullptr) {  // per-channel layer: the same dispatch, the PC instances
+    if (c.amode == 0) {
+      if (bias)
+        return accd ? launch_tile<0, true, true, true>(ctx, a, kb, ops, bytes) : launch_tile<0, true, false, true>(ctx, a, kb, ops, bytes);
+      return accd ? launch_tile<0, false, true, true>(ctx, a, kb, ops, bytes) : launch_tile<0, false, false, true>(ctx, a, kb, ops, bytes);
+    }
+    return accd ? launch_tile<1, false, true, true>(ctx, a, kb, ops, bytes) : launch_tile<1, false, false, true>(ctx, a, kb, ops, bytes);
   }
   if (c.amode == 0) {
     if (bias)
@@ -1144,6 +1181,7 @@ struct I8ieSmallNCall {
   uint8_t* out;
   int32_t* acc;
   float* out_f32;
+  const float* sbv;  // per-channel layers: [N] weight scales; nullptr otherwise
 };
 int i8ie_smalln_max_features() { return kSmallN; }
 int i8ie_launch_linear_smalln(i8ie_ctx* ctx, const I8ieSmallNCall& c) {
@@ -1156,16 +1194,21 @@ int i8ie_launch_linear_smalln(i8ie_ctx* ctx, const I8ieSmallNCall& c) {
   a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
   a.rq.fast = I8IE_RQ_EXACT;
   a.relu_lo = c.relu ? c.zp_out : 0;
-  a.out = c.out; a.acc = c.acc; a.out_f32 = c.out_f32; a.dq_scale = c.s_out; a.dq_zp = c.zp_out;
+  a.out = c.out; a.acc = c.acc; a.out_f32 = c.out_f32; a.dq_scale = c.s_out; a.dq_zp = c.zp_out; a.sbv = c.sbv;
   I8ieProfScope prof(ctx, "linear_smalln_dot4", 2.0 * c.M * c.N * c.K, (double)c.M * c.K + (double)c.N * c.K + 5.0 * c.M * c.N);
   // (activation rows are lda = K bytes apart and the weights are zero from K to Kpad: a step past K multiplies
   // the next row's bytes, or the zeros the descriptor returns past the buffer, by zero)
-  if (c.K >= 1024 && c.Kpad % 64 == 0 && (size_t)16 * c.lda + c.Kpad < ((size_t)1 << 31) && !ctx->pick.no_dot4_head)
-    linear_head_mfma_kernel<<<(c.M + 15) / 16, 512, 0, ctx->stream>>>(a);
-  else if (c.K >= 2048)
-    linear_smalln_kernel<4><<<c.M, 256, 0, ctx->stream>>>(a);
-  else
-    linear_smalln_kernel<1><<<(c.M + 3) / 4, 256, 0, ctx->stream>>>(a);
+  const bool pc = c.sbv != nullptr;
+  if (c.K >= 1024 && c.Kpad % 64 == 0 && (size_t)16 * c.lda + c.Kpad < ((size_t)1 << 31) && !ctx->pick.no_dot4_head) {
+    if (pc) linear_head_mfma_kernel<true><<<(c.M + 15) / 16, 512, 0, ctx->stream>>>(a);
+    else linear_head_mfma_kernel<false><<<(c.M + 15) / 16, 512, 0, ctx->stream>>>(a);
+  } else if (c.K >= 2048) {
+    if (pc) linear_smalln_kernel<4, true><<<c.M, 256, 0, ctx->stream>>>(a);
+    else linear_smalln_kernel<4, false><<<c.M, 256, 0, ctx->stream>>>(a);
+  } else {
+    if (pc) linear_smalln_kernel<1, true><<<(c.M + 3) / 4, 256, 0, ctx->stream>>>(a);
+    else linear_smalln_kernel<1, false><<<(c.M + 3) / 4, 256, 0, ctx->stream>>>(a);
+  }
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }

@@ -137,5 +137,6 @@ struct I8ieGemmArgs {
   int P;
   int32_t* acc;  // nullptr or [M][N]
   int Ktrue;     // unpadded reduction length (profiling: algorithmic ops = 2*M*N*Ktrue)
+  const float* sbv;  // per-channel layers: [N] weight scales s_w[j] (s_w unused); nullptr otherwise
 };
 int i8ie_gemm_launch(i8ie_ctx* ctx, const I8ieGemmArgs& a);

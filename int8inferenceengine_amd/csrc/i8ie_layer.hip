@@ -12,6 +12,7 @@
 //   F  anything else: materialised im2col + v1 GEMM (i8ie_gemm.hip)
 // Activations cross the ABI as NCHW (the reference's layout) or, on request, as
 // NHWC so that consecutive layers skip the layout conversion.
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -19,6 +20,7 @@
 #include "i8ie_internal.h"
 #include "i8ie_calls.h"
 #include "i8ie_stem.h"
+#include "i8ie_requant.h"
 
 int i8ie_launch_pad_rows(i8ie_ctx* ctx, const void* src, int rows, int k, void* dst, int rows_pad, int k_pad,
                          int fill);
@@ -46,6 +48,7 @@ struct I8ieSmallNCall {
   uint8_t* out;
   int32_t* acc;
   float* out_f32;
+  const float* sbv;
 };
 int i8ie_smalln_max_features();
 int i8ie_launch_linear_smalln(i8ie_ctx* ctx, const I8ieSmallNCall& c);
@@ -73,6 +76,8 @@ struct I8ieFirstCall {
   uint8_t* out;
   int ob;
   int32_t* acc;
+  const float* msv;
+  const float* sbv;
 };
 int i8ie_first_supported(int c, int stride, int n_out, int K2, int KH, int KWG, int OW);
 int i8ie_first_launch(i8ie_ctx* ctx, const I8ieFirstCall& c);
@@ -114,7 +119,7 @@ inline int chunk_images(const ConvGeom& g, int n) {
 // ---- v1 (fallback) runners ------------------------------------------------------------------
 int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, const int8_t* Bpack, const int32_t* oc,
                 const int32_t* wsum, uint8_t zp_in, float s_in, float s_w, float s_out, uint8_t zp_out, uint8_t* out,
-                int32_t* acc, uint8_t* col, int imgs_per_chunk) {
+                int32_t* acc, uint8_t* col, int imgs_per_chunk, const float* sbv = nullptr) {
   const int P = cg.oh * cg.ow;
   for (int i0 = 0; i0 < n; i0 += imgs_per_chunk) {
     const int nb = (n - i0) < imgs_per_chunk ? (n - i0) : imgs_per_chunk;
@@ -140,6 +145,7 @@ int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, con
     g.P = P;
     g.acc = acc ? acc + (size_t)i0 * P * cg.kc : nullptr;
     g.Ktrue = cg.K;
+    g.sbv = sbv;
     I8IE_TRY(i8ie_gemm_launch(ctx, g));
   }
   return I8IE_OK;
@@ -147,7 +153,7 @@ int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, con
 
 int linear_run_v1(i8ie_ctx* ctx, const uint8_t* in, int m, int k, const int8_t* Bpack, int Kpad, const int8_t* qb,
                   int n, const int32_t* oc, const int32_t* wsum, float s_in, float s_w, float s_out, uint8_t zp_out,
-                  uint8_t* out, int32_t* acc, uint8_t* scratch) {
+                  uint8_t* out, int32_t* acc, uint8_t* scratch, const float* sbv = nullptr) {
   I8ieGemmArgs g{};
   if (k % 16 != 0 || !aligned16(in)) {
     I8IE_TRY(i8ie_launch_pad_rows(ctx, in, m, k, scratch, m, Kpad, 0));
@@ -161,7 +167,7 @@ int linear_run_v1(i8ie_ctx* ctx, const uint8_t* in, int m, int k, const int8_t* 
   }
   g.M = m; g.B = Bpack; g.Kpad = Kpad; g.N = n; g.oc = oc; g.wsum = wsum; g.qb = qb;
   g.s_in = s_in; g.s_w = s_w; g.s_out = s_out; g.zp_out = zp_out;
-  g.out = out; g.out_mode = I8IE_OUT_ROWMAJOR; g.P = 1; g.acc = acc; g.Ktrue = k;
+  g.out = out; g.out_mode = I8IE_OUT_ROWMAJOR; g.P = 1; g.acc = acc; g.Ktrue = k; g.sbv = sbv;
   return i8ie_gemm_launch(ctx, g);
 }
 
@@ -196,6 +202,15 @@ struct i8ie_layer {
   bool oc_valid = false;
   float oc_s_in = 0.0f;
   int oc_zp_in = -1;
+  // per-channel weight scales (i8ie_*_create_per_channel): s_w[j] per output feature, and the per-column multipliers of
+  // i8ie_requant.h cached like oc' per (s_in, s_out); every kernel then runs its PC instance (s_w above is unused)
+  bool pc = false;
+  std::vector<float> sw_host;  // [n]
+  float* swv = nullptr;        // [Npad] s_w[j] (padding 1)
+  float* msv = nullptr;        // [Npad] fl(s_in * s_w[j] / s_out) (padding 0), valid for (ms_s_in, ms_s_out)
+  bool ms_valid = false;
+  bool ms_fast = false;        // every column allows the guarded estimate (i8ie_requant_pc_fast)
+  float ms_s_in = 0.0f, ms_s_out = 0.0f;
 };
 
 namespace {
@@ -215,6 +230,26 @@ int ensure_offsets(i8ie_layer* L, float s_in, uint8_t zp_in) {
   L->oc_zp_in = zp_in;
   return I8IE_OK;
 }
+
+// per-channel layers: the multipliers for (s_in, s_out), computed on the host in double (as i8ie_make_requant does) and
+// copied over the same buffer -- built by the eager run before a graph capture, never reallocated
+int ensure_multipliers(i8ie_layer* L, float s_in) {
+  if (!L->pc) return I8IE_OK;
+  if (L->ms_valid && memcmp(&s_in, &L->ms_s_in, 4) == 0 && memcmp(&L->s_out, &L->ms_s_out, 4) == 0) return I8IE_OK;
+  std::vector<float> ms((size_t)L->Npad, 0.0f);
+  for (int j = 0; j < L->n; ++j) ms[j] = i8ie_requant_ms(s_in, L->sw_host[j], L->s_out);
+  I8IE_TRY(i8ie_memcpy_h2d(L->ctx, L->msv, ms.data(), ms.size() * 4));
+  L->ms_fast = i8ie_requant_pc_fast(s_in, L->sw_host.data(), L->n, L->s_out);
+  L->ms_valid = true;
+  L->ms_s_in = s_in;
+  L->ms_s_out = L->s_out;
+  return I8IE_OK;
+}
+// what the launchers get as s_w: the layer's scale, or for a per-channel layer the switch between the guarded estimate
+// (1) and the exact sequence (0) that i8ie_make_requant reads off it (I8ieIgemmCall::msv)
+inline float sw_arg(const i8ie_layer* L) { return L->pc ? (L->ms_fast ? 1.0f : 0.0f) : L->s_w; }
+inline const float* msv_arg(const i8ie_layer* L) { return L->pc ? L->msv : nullptr; }
+inline const float* sbv_arg(const i8ie_layer* L) { return L->pc ? L->swv : nullptr; }
 
 bool force_fallback(const i8ie_ctx* ctx) { return (ctx->options & 1) != 0; }
 
@@ -419,6 +454,70 @@ static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const i
   return I8IE_OK;
 }
 
+// per-channel layers: the per-tensor handle plus s_w[n] (host copy, device [Npad]) and the multiplier buffer
+static int layer_make_per_channel(i8ie_layer* L, const float* s_w_host) {
+  const int n = L->n;
+  L->pc = true;
+  L->sw_host.assign(s_w_host, s_w_host + n);
+  std::vector<float> sw((size_t)L->Npad, 1.0f);
+  for (int j = 0; j < n; ++j) sw[j] = s_w_host[j];
+  I8IE_TRY(i8ie_malloc(L->ctx, (size_t)L->Npad * 4, (void**)&L->swv));
+  I8IE_TRY(i8ie_malloc(L->ctx, (size_t)L->Npad * 4, (void**)&L->msv));
+  I8IE_TRY(i8ie_memcpy_h2d(L->ctx, L->swv, sw.data(), sw.size() * 4));
+  return i8ie_memset(L->ctx, L->msv, 0, (size_t)L->Npad * 4);
+}
+
+// scales from the caller: finite and >= 0 (pooling the INT32 accumulators before the requantiser needs a monotone
+// map per channel, DESIGN.md "Per-channel weight scales")
+static int check_scales(const float* s_w, int n) {
+  I8IE_REQUIRE(s_w != nullptr, "null argument");
+  for (int j = 0; j < n; ++j) {
+    if (!(s_w[j] >= 0.0f && s_w[j] <= 3.402823466e+38f)) {
+      i8ie_set_error("per-channel weight scale %d is negative or not finite", j);
+      return I8IE_ERR_ARG;
+    }
+  }
+  return I8IE_OK;
+}
+
+int i8ie_linear_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int n, int k,
+                                   const float* s_w_host, i8ie_layer** out) {
+  I8IE_REQUIRE(out != nullptr && n > 0, "bad argument");
+  I8IE_TRY(check_scales(s_w_host, n));
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_linear_create(ctx, qw_host, qb_host, n, k, 1.0f, &L));
+  const int rc = layer_make_per_channel(L, s_w_host);
+  if (rc != I8IE_OK) {
+    i8ie_layer_destroy(L);
+    return rc;
+  }
+  *out = L;
+  return I8IE_OK;
+}
+
+int i8ie_conv2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh,
+                                   int kw, int stride, int pad, const float* s_w_host, i8ie_layer** out) {
+  I8IE_REQUIRE(out != nullptr && kc > 0, "bad argument");
+  I8IE_TRY(check_scales(s_w_host, kc));
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_conv2d_create(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, 1.0f, &L));
+  const int rc = layer_make_per_channel(L, s_w_host);
+  if (rc != I8IE_OK) {
+    i8ie_layer_destroy(L);
+    return rc;
+  }
+  *out = L;
+  return I8IE_OK;
+}
+
+int i8ie_layer_weight_scales(const i8ie_layer* L, float* out, int n, int* per_channel) {
+  I8IE_REQUIRE(L && out && per_channel, "null argument");
+  I8IE_REQUIRE(n == L->n, "n must be the layer's out features");
+  for (int j = 0; j < n; ++j) out[j] = L->pc ? L->sw_host[j] : L->s_w;
+  *per_channel = L->pc ? 1 : 0;
+  return I8IE_OK;
+}
+
 int i8ie_linear_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int n, int k, float s_w,
                        i8ie_layer** out) {
   return layer_create(ctx, false, qw_host, qb_host, n, k, 0, 0, 0, 1, 0, s_w, out);
@@ -436,6 +535,7 @@ int i8ie_layer_set_output_qparams(i8ie_layer* L, float s_out, uint8_t zp_out) {
   I8IE_REQUIRE(L != nullptr, "null layer");
   L->s_out = s_out;
   L->zp_out = zp_out;
+  L->ms_valid = false;  // (per-channel multipliers depend on s_out)
   return I8IE_OK;
 }
 
@@ -532,6 +632,7 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
   i8ie_ctx* ctx = L->ctx;
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   I8IE_TRY(ensure_offsets(L, s_in, zp_in));
+  I8IE_TRY(ensure_multipliers(L, s_in));
 
   if (!L->conv) {  // ---- Linear: row-major in / out -------------------------------------------------
     I8IE_REQUIRE(in_border == 0 && out_border == 0, "Linear tensors carry no border");
@@ -564,8 +665,8 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
       // classifier head: one wave per row, dot4 + wavefront reduction, epilogue (and dequantize) fused
       I8ieSmallNCall sc{};
       sc.A = in; sc.lda = (size_t)L->K; sc.M = m; sc.K = L->K; sc.B = panel; sc.Kpad = L->Kpad; sc.N = L->n;
-      sc.ocp = L->ocp; sc.biasf = L->biasf; sc.s_in = s_in; sc.s_w = L->s_w; sc.s_out = L->s_out;
-      sc.zp_out = L->zp_out; sc.relu = relu; sc.out = out; sc.acc = acc; sc.out_f32 = out_f32;
+      sc.ocp = L->ocp; sc.biasf = L->biasf; sc.s_in = s_in; sc.s_w = sw_arg(L); sc.s_out = L->s_out;
+      sc.zp_out = L->zp_out; sc.relu = relu; sc.out = out; sc.acc = acc; sc.out_f32 = out_f32; sc.sbv = sbv_arg(L);
       return i8ie_launch_linear_smalln(ctx, sc);
     }
     I8IE_REQUIRE(out != nullptr, "i8ie_layer_forward_dequant: this layer needs the u8 output buffer as well");
@@ -576,7 +677,7 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
     if (force_fallback(ctx)) {
       if (need_pad) I8IE_TRY(i8ie_ws_reserve(ctx, (size_t)m * L->Kpad));
       I8IE_TRY(linear_run_v1(ctx, in, m, L->K, L->Bpack, L->Kpad, L->qb, L->n, L->oc, L->wsum, s_in, L->s_w, L->s_out,
-                             L->zp_out, out, acc, (uint8_t*)ctx->ws));
+                             L->zp_out, out, acc, (uint8_t*)ctx->ws, sbv_arg(L)));
       if (relu) I8IE_TRY(i8ie_relu_u8(ctx, out, out, (int64_t)m * L->n, L->zp_out));
       return I8IE_OK;
     }
@@ -616,8 +717,8 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
     c.a_bytes = (size_t)m * c.lda;
     c.amode = 0; c.M = m;
     c.B = panel; c.Kpad = L->Kpad; c.Npad = L->Npad; c.N = L->n; c.ocp = L->ocp; c.biasf = L->biasf;
-    c.s_in = s_in; c.s_w = L->s_w; c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = relu;
-    c.out = out; c.ob = 0; c.acc = acc; c.Ktrue = L->K;
+    c.s_in = s_in; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = relu;
+    c.out = out; c.ob = 0; c.acc = acc; c.Ktrue = L->K; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
     if (flin) return i8ie_flin_launch(ctx, c);
     if (mlin) return i8ie_mlin_launch(ctx, c);
     return i8ie_igemm_launch(ctx, c);
@@ -705,7 +806,7 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
     }
     uint8_t* dst = o_bytes ? ws + col_bytes + a_bytes : out;
     I8IE_TRY(conv_run_v1(ctx, src, m, cg, L->Bpack, L->oc, L->wsum, zp_in, s_in, L->s_w, L->s_out, L->zp_out, dst, acc,
-                         col, ipc));
+                         col, ipc, sbv_arg(L)));
     if (relu) I8IE_TRY(i8ie_relu_u8(ctx, dst, dst, (int64_t)out_bytes, L->zp_out));
     if (o_bytes) {
       I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, dst, out, m, cg.kc, cg.oh, cg.ow, out_border));
@@ -717,8 +818,8 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
   c.amode = 1; c.M = m * cg.oh * cg.ow;
   c.B = L->Bpack2; c.Kpad = L->Kpad2; c.Npad = L->Npad; c.Kchunks = L->K2 / 16; c.N = L->n; c.ocp = L->ocp;
   c.biasf = nullptr; c.wcache = &L->wc;
-  c.s_in = s_in; c.s_w = L->s_w; c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = relu;
-  c.acc = acc; c.Ktrue = cg.K; c.OH = cg.oh; c.OW = cg.ow;
+  c.s_in = s_in; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = relu;
+  c.acc = acc; c.Ktrue = cg.K; c.OH = cg.oh; c.OW = cg.ow; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
   if (pconv) {  // (the patch-stationary kernel said it takes this launch as it is)
     c.pool_k = pool ? pool_k : 0; c.pool_s = pool_s; c.a_s8 = in_s8 ? 1 : 0; c.out_s8 = out_s8 ? 1 : 0;
   }
@@ -770,9 +871,10 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
       f.n = m; f.c = cg.c; f.h = cg.h; f.w = cg.w; f.q_scale = s_in; f.q_zp = zp_in;
       f.KH = cg.kh; f.KW = cg.kw; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
       f.B = L->Bstem; f.Kpad = L->KpadStem; f.N = L->n; f.ocp = L->ocp;
-      f.s_in = s_in; f.s_w = L->s_w; f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = relu;
+      f.s_in = s_in; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = relu;
       f.pool_k = pool ? pool_k : 0; f.pool_s = pool_s;
       f.out = dst; f.ob = o_bytes ? 0 : out_border; f.out_s8 = out_s8 ? 1 : 0; f.acc = acc;
+      f.msv = msv_arg(L); f.sbv = sbv_arg(L);
       I8IE_TRY(i8ie_stem_launch(ctx, f));
       if (o_bytes) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, dst, out, m, cg.kc, ph, pw, 0));
       return I8IE_OK;
@@ -796,8 +898,8 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
       f.n = m; f.c = cg.c; f.h = cg.h; f.w = cg.w; f.q_scale = s_in; f.q_zp = zp_in;
       f.KH = cg.kh; f.KW = cg.kw; f.KWG = L->kwg; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
       f.B = L->Bpack2; f.Kpad = L->Kpad2; f.K2 = L->K2; f.N = L->n; f.ocp = L->ocp;
-      f.s_in = s_in; f.s_w = L->s_w; f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = relu;
-      f.out = dst; f.ob = ob; f.acc = acc;
+      f.s_in = s_in; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = relu;
+      f.out = dst; f.ob = ob; f.acc = acc; f.msv = msv_arg(L); f.sbv = sbv_arg(L);
       I8IE_TRY(i8ie_first_launch(ctx, f));
       if (o_bytes) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, dst, out, m, cg.kc, cg.oh, cg.ow, 0));
       return I8IE_OK;
@@ -866,6 +968,7 @@ int i8ie_layer_forward_f32_input_pool(i8ie_layer* L, const float* in, int m, int
   I8IE_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15u) == 0, "output must be 16-byte aligned");
   I8IE_REQUIRE(acc == nullptr || aligned16(acc), "accumulator buffer must be 16-byte aligned");
   I8IE_TRY(ensure_offsets(L, q_scale, q_zp));
+  I8IE_TRY(ensure_multipliers(L, q_scale));
   ConvGeom cg;
   I8IE_TRY(conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg));
   const bool pool = i8ie_is_pool(pool_k, pool_s);
@@ -879,9 +982,10 @@ int i8ie_layer_forward_f32_input_pool(i8ie_layer* L, const float* in, int m, int
     f.n = m; f.c = cg.c; f.h = h; f.w = w; f.q_scale = q_scale; f.q_zp = q_zp;
     f.KH = cg.kh; f.KW = cg.kw; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
     f.B = L->Bstem; f.Kpad = L->KpadStem; f.N = L->n; f.ocp = L->ocp;
-    f.s_in = q_scale; f.s_w = L->s_w; f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = relu;
+    f.s_in = q_scale; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = relu;
     f.pool_k = pool ? pool_k : 0; f.pool_s = pool_s;
     f.out = out; f.ob = out_border; f.out_s8 = out_layout == I8IE_LAYOUT_NHWC_S8 ? 1 : 0; f.acc = acc;
+    f.msv = msv_arg(L); f.sbv = sbv_arg(L);
     return i8ie_stem_launch(ctx, f);
   }
   if (pool || out_layout == I8IE_LAYOUT_NHWC_S8) {
@@ -913,8 +1017,8 @@ int i8ie_layer_forward_f32_input_pool(i8ie_layer* L, const float* in, int m, int
   c.n = m; c.c = cg.c; c.h = h; c.w = w; c.q_scale = q_scale; c.q_zp = q_zp;
   c.KH = cg.kh; c.KW = cg.kw; c.KWG = L->kwg; c.stride = cg.stride; c.pad = cg.pad; c.OH = cg.oh; c.OW = cg.ow;
   c.B = L->Bpack2; c.Kpad = L->Kpad2; c.K2 = L->K2; c.N = L->n; c.ocp = L->ocp;
-  c.s_in = q_scale; c.s_w = L->s_w; c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = relu;
-  c.out = out; c.ob = out_border; c.acc = acc;
+  c.s_in = q_scale; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = relu;
+  c.out = out; c.ob = out_border; c.acc = acc; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
   return i8ie_first_launch(ctx, c);
 }
 
@@ -942,6 +1046,8 @@ int i8ie_layer_destroy(i8ie_layer* L) {
   i8ie_free(ctx, L->ocp);
   if (L->Bperm) i8ie_free(ctx, L->Bperm);
   i8ie_free(ctx, L->biasf);
+  if (L->swv) i8ie_free(ctx, L->swv);
+  if (L->msv) i8ie_free(ctx, L->msv);
   delete L;
   return I8IE_OK;
 }
@@ -964,6 +1070,30 @@ int i8ie_quantize_weight(const float* w, int64_t nw, const float* b, int64_t nb,
   for (int64_t i = 0; i < nw; ++i) qw[i] = (int8_t)(int32_t)(w[i] / s);
   for (int64_t i = 0; i < nb; ++i) qb[i] = (int8_t)(int32_t)(b[i] / s);
   *scale_out = s;
+  return I8IE_OK;
+}
+
+// per-output-channel quantize (DESIGN.md "Per-channel weight scales"): row j = w[j * row_len ..], bias b[j] (may be null:
+// zero); symmetric max-abs over the row and its bias, round half to even, clamp to [-127, 127]
+int i8ie_quantize_weight_per_channel(const float* w, int rows, int64_t row_len, const float* b, int8_t* qw, int8_t* qb,
+                                     float* scales) {
+  I8IE_REQUIRE(w && qw && qb && scales, "null argument");
+  I8IE_REQUIRE(rows > 0 && row_len > 0, "empty tensor");
+  auto q8 = [](float x, float s) {
+    float r = std::nearbyint(x / s);  // (the default rounding mode: to nearest, ties to even)
+    r = r > 127.0f ? 127.0f : (r < -127.0f ? -127.0f : r);
+    return (int8_t)(int32_t)r;
+  };
+  for (int j = 0; j < rows; ++j) {
+    const float* row = w + (size_t)j * row_len;
+    const float bj = b ? b[j] : 0.0f;
+    float a = std::fabs(bj);
+    for (int64_t k = 0; k < row_len; ++k) a = std::fabs(row[k]) > a ? std::fabs(row[k]) : a;
+    const float s = a == 0.0f ? 1.0f : a / 127.0f;
+    for (int64_t k = 0; k < row_len; ++k) qw[(size_t)j * row_len + k] = q8(row[k], s);
+    qb[j] = q8(bj, s);
+    scales[j] = s;
+  }
   return I8IE_OK;
 }
 

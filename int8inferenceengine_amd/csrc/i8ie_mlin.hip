@@ -46,6 +46,8 @@ struct MlinArgs {
   int32_t* acc;
   int n_tiles, m_tiles;
   int ahead;  // a line is touched (-> L2) this many chunks before the chunk being multiplied
+  const float* msv;  // PC kernels (per-channel layers): [Npad] multipliers and weight scales (i8ie_requant.h)
+  const float* sbv;
 };
 
 constexpr int kMlChunk = 128;                 // K bytes per chunk
@@ -76,7 +78,7 @@ __device__ __forceinline__ void ml_wait_vm() {
 }
 #define ML_BAR() asm volatile("s_barrier" ::: "memory")
 
-template <int RB>
+template <int RB, bool PC>
 __global__ __launch_bounds__(512, 2) void mlin_kernel(MlinArgs p) {
   using S = MlShape<RB>;
   constexpr int kMlRows = S::kRows, kMlStage = S::kStage, kMlPPW = S::kPPW, IT = S::kIT;
@@ -273,11 +275,13 @@ __global__ __launch_bounds__(512, 2) void mlin_kernel(MlinArgs p) {
   typedef float v4f __attribute__((ext_vector_type(4)));
   v4i ocq[4];
   v4f bq[4];
+  float4 msq[4];  // PC: the quads' multipliers (padded arrays: a quad that starts below N lies inside them)
 #pragma unroll
   for (int n = 0; n < 4; ++n) {
     const int f = n0 + 64 * wf + 16 * n + 4 * lq;
     ocq[n] = v4i{0, 0, 0, 0};
     bq[n] = v4f{0.f, 0.f, 0.f, 0.f};
+    if constexpr (PC) msq[n] = f < p.N ? *reinterpret_cast<const float4*>(p.msv + f) : make_float4(0.f, 0.f, 0.f, 0.f);
     if (vec) {
       if (f < p.N) {
         ocq[n] = *reinterpret_cast<const v4i*>(p.ocp + f);
@@ -309,7 +313,7 @@ __global__ __launch_bounds__(512, 2) void mlin_kernel(MlinArgs p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) cv[r] = (int)((float)cv[r] + bq[n][r]);
         }
-        const uint32_t packed = i8ie_requant_pack4(cv, rq, lo, lof);
+        const uint32_t packed = PC ? i8ie_requant_pack4_pc(cv, rq, msq[n], p.sbv + f, lo, lof) : i8ie_requant_pack4(cv, rq, lo, lof);
         uint8_t* o = p.out + (size_t)row * p.N + f;
         if (vec) {
           *reinterpret_cast<uint32_t*>(o) = packed;
@@ -334,7 +338,7 @@ bool i8ie_mlin_wants(int m, int n, int Kpad, bool force) {
   return m > 256 && (force || n >= 2048) && Kpad % kMlChunk == 0 && Kpad >= 4 * kMlChunk;
 }
 
-template <int RB>
+template <int RB, bool PC>
 static int mlin_launch_t(i8ie_ctx* ctx, MlinArgs& a, const I8ieIgemmCall& c, const char* name) {
   using S = MlShape<RB>;
   I8IE_REQUIRE((size_t)RB * c.lda + c.Kpad < ((size_t)1 << 31), "mlin: offsets exceed 32 bits");
@@ -342,14 +346,14 @@ static int mlin_launch_t(i8ie_ctx* ctx, MlinArgs& a, const I8ieIgemmCall& c, con
   static bool raised[64] = {};
   const int dev = ctx->device & 63;
   if (!raised[dev]) {
-    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlin_kernel<RB>), hipFuncAttributeMaxDynamicSharedMemorySize, S::kLds));
+    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlin_kernel<RB, PC>), hipFuncAttributeMaxDynamicSharedMemorySize, S::kLds));
     raised[dev] = true;
   }
   const int per = (a.n_tiles + 7) / 8;
   const int grid = 8 * per * a.m_tiles;
   const double ops = 2.0 * c.M * c.N * c.Ktrue, bytes = (double)c.M * c.Ktrue + (double)c.N * c.Ktrue + (double)c.M * c.N;
   I8ieProfScope prof(ctx, name, ops, bytes);
-  mlin_kernel<RB><<<grid, 512, S::kLds, ctx->stream>>>(a);
+  mlin_kernel<RB, PC><<<grid, 512, S::kLds, ctx->stream>>>(a);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }
@@ -367,7 +371,7 @@ int i8ie_mlin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   a.ocp = c.ocp; a.biasf = c.biasf;
   a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
   a.relu_lo = c.relu ? c.zp_out : 0;
-  a.out = c.out; a.acc = c.acc;
+  a.out = c.out; a.acc = c.acc; a.msv = c.msv; a.sbv = c.sbv;
   a.n_tiles = (c.N + kMlFeats - 1) / kMlFeats;
   a.ahead = kMlAhead;
   static int cus[64] = {};
@@ -380,6 +384,10 @@ int i8ie_mlin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   // 64-row tiles when 128-row tiles give at most half the CUs a block (variant 84 / 85 force 64 / 128 rows)
   const long blocks128 = (long)((c.M + 127) / 128) * a.n_tiles;
   const bool rows64 = ctx->pick.linear == I8IE_LIN_MLIN64 || (ctx->pick.linear != I8IE_LIN_MLIN128 && blocks128 * 2 <= i8ie_cus(ctx, cus[dev]));
-  if (rows64) return mlin_launch_t<64>(ctx, a, c, "mlin_64x128");
-  return mlin_launch_t<128>(ctx, a, c, "mlin_128x128");
+  if (c.msv != nullptr) {
+    if (rows64) return mlin_launch_t<64, true>(ctx, a, c, "mlin_64x128");
+    return mlin_launch_t<128, true>(ctx, a, c, "mlin_128x128");
+  }
+  if (rows64) return mlin_launch_t<64, false>(ctx, a, c, "mlin_64x128");
+  return mlin_launch_t<128, false>(ctx, a, c, "mlin_128x128");
 }

@@ -47,7 +47,7 @@ namespace {
 // features, block = 64 NTW features per pass)
 // ACC: also dump the INT32 accumulators (acc_dbg of the C-ABI) -- a separate instantiation, the default one is untouched
 // POOL: max-pool folded in behind the requantiser (PCArgs::pk ...)
-template <int TMW, int NTW, bool ACC, bool POOL>
+template <int TMW, int NTW, bool ACC, bool POOL, bool PC>
 __global__ __launch_bounds__(512, 2) void pconv_kernel(PCArgs p) {
   uint8_t* const smem = pc_smem;
   constexpr int BN = NTW * 64;
@@ -195,8 +195,17 @@ __global__ __launch_bounds__(512, 2) void pconv_kernel(PCArgs p) {
 #pragma unroll
       for (int ni = 0; ni < NTW; ++ni) {
         const int c4[4] = {acc[mi][ni].x, acc[mi][ni].y, acc[mi][ni].z, acc[mi][ni].w};
-        if constexpr (POOL) d[ni] = i8ie_requant_pack4_norelu(c4, rq);  // (the ReLU follows the pool: pool_pass)
-        else d[ni] = i8ie_requant_pack4(c4, rq, lo, lof);
+        if constexpr (PC) {  // features n0 + 16 ni + 4 lq .. + 3 (columns past N: nothing is stored, s_w[0] for the replay)
+          const int col = n0 + ni * 16 + 4 * lq;
+          const float4 msq = col < p.N ? *reinterpret_cast<const float4*>(p.msv + col) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+          const float* sbq = p.sbv + (col < p.N ? col : 0);
+          if constexpr (POOL) d[ni] = i8ie_requant_pack4_norelu_pc(c4, rq, msq, sbq);
+          else d[ni] = i8ie_requant_pack4_pc(c4, rq, msq, sbq, lo, lof);
+        } else if constexpr (POOL) {
+          d[ni] = i8ie_requant_pack4_norelu(c4, rq);  // (the ReLU follows the pool: pool_pass)
+        } else {
+          d[ni] = i8ie_requant_pack4(c4, rq, lo, lof);
+        }
         if constexpr (ACC) {  // row = image-major pixel index (bands are whole rows), 4 consecutive features per lane
           const int col = n0 + ni * 16 + 4 * lq;
           if (pi < valid && col < p.N)
@@ -429,24 +438,28 @@ __global__ __launch_bounds__(256) void pconv_pack_kernel(const int8_t* __restric
   }
 }
 
-template <int TMW, int NTW, bool ACC, bool POOL>
+template <int TMW, int NTW, bool ACC, bool POOL, bool PC>
 int launch_pc_t(i8ie_ctx* ctx, const PCArgs& a, int grid, int lds) {
   static bool raised[64] = {};
   const int dev = ctx->device & 63;
   if (!raised[dev]) {
-    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pconv_kernel<TMW, NTW, ACC, POOL>),
+    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pconv_kernel<TMW, NTW, ACC, POOL, PC>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     raised[dev] = true;
   }
-  pconv_kernel<TMW, NTW, ACC, POOL><<<grid, 512, lds, ctx->stream>>>(a);
+  pconv_kernel<TMW, NTW, ACC, POOL, PC><<<grid, 512, lds, ctx->stream>>>(a);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }
+template <int TMW, int NTW, bool PC>
+int launch_pc_p(i8ie_ctx* ctx, const PCArgs& a, int grid, int lds) {
+  if (a.pk > 1)
+    return a.acc != nullptr ? launch_pc_t<TMW, NTW, true, true, PC>(ctx, a, grid, lds) : launch_pc_t<TMW, NTW, false, true, PC>(ctx, a, grid, lds);
+  return a.acc != nullptr ? launch_pc_t<TMW, NTW, true, false, PC>(ctx, a, grid, lds) : launch_pc_t<TMW, NTW, false, false, PC>(ctx, a, grid, lds);
+}
 template <int TMW, int NTW>
 int launch_pc(i8ie_ctx* ctx, const PCArgs& a, int grid, int lds) {
-  if (a.pk > 1)
-    return a.acc != nullptr ? launch_pc_t<TMW, NTW, true, true>(ctx, a, grid, lds) : launch_pc_t<TMW, NTW, false, true>(ctx, a, grid, lds);
-  return a.acc != nullptr ? launch_pc_t<TMW, NTW, true, false>(ctx, a, grid, lds) : launch_pc_t<TMW, NTW, false, false>(ctx, a, grid, lds);
+  return a.msv != nullptr ? launch_pc_p<TMW, NTW, true>(ctx, a, grid, lds) : launch_pc_p<TMW, NTW, false>(ctx, a, grid, lds);
 }
 
 }  // namespace
@@ -651,6 +664,7 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   a.ob = c.ob; a.OHp = c.OH + 2 * c.ob; a.OWp = c.OW + 2 * c.ob;
   a.split = split;
   a.acc = c.acc;
+  a.msv = c.msv; a.sbv = c.sbv;
   a.a_s8 = c.a_s8;
   a.xor_out = c.out_s8 ? 0x80808080u : 0u;
   a.pk = pool ? c.pool_k : 1; a.ps = pool ? c.pool_s : 1; a.PH = PHo; a.PW = PWo; a.RB = RB; a.opitch = opitch; a.seq = seq;

@@ -51,6 +51,8 @@ struct PCArgs {
   int pk, ps, PH, PW, RB, opitch, lds_otile, seq;
   float rcpPW, rcpC16, rcpRB;
   unsigned long long* dbg;  // always 0 in this library; removing it changes the kernel's code
+  const float* msv;         // PC kernels (per-channel layers): [Npad] multipliers and weight scales (i8ie_requant.h), read
+  const float* sbv;         // from memory in the epilogue: the LDS plan (and so which launches the kernel takes) is unchanged
 };
 
 namespace {

@@ -96,6 +96,50 @@ __device__ __forceinline__ uint32_t i8ie_requant_exact4(const int (&c)[4], const
   return packed;
 }
 
+// ---- per-output-channel weight scales (i8ie_linear_create_per_channel / i8ie_conv2d_create_per_channel) ---------------
+// Column j has its own multiplier ms[j] = fl(s_in * s_w[j] / s_out) (host, in double) and its own s_w[j] for the exact
+// replay.  The guard's bound is per value, so it holds column by column; q.fast is decided for the whole layer on the host
+// (every column's scales ordinary, or the layer takes the exact sequence).  A column with ms[j] == 0 has e = zp - 0.5,
+// fract(e) = 0.5: it always replays.  `ms` holds the multipliers of 4 consecutive columns, `sb` points at s_w of the first
+// of them; sb is read in the replay only.
+__device__ __forceinline__ int i8ie_requant_exact_col(float cf, const I8ieRequant& q, float sb, int lo) {
+  I8ieRequant qc = q;
+  qc.sb = sb;
+  return i8ie_requant_exact(cf, qc, lo);
+}
+__device__ __forceinline__ uint32_t i8ie_requant_exact4_pc(const int (&c)[4], const I8ieRequant& q, const float* sb, int lo) {
+  uint32_t packed = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) packed |= (uint32_t)i8ie_requant_exact_col((float)c[r], q, sb[r], lo) << (8 * r);
+  return packed;
+}
+__device__ __forceinline__ uint32_t i8ie_requant_est4_pc(const int (&c)[4], const I8ieRequant& q, const float4& ms, float lof,
+                                                         float& worst) {
+  const float m[4] = {ms.x, ms.y, ms.z, ms.w};
+  uint32_t packed = 0;
+  float w = q.fast ? 1.0f : 0.0f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float e = __builtin_fmaf((float)c[r], m[r], q.zpf - 0.5f);
+    packed = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaxf(e, lof), r, packed);
+    w = __builtin_fminf(w, __builtin_fabsf(__builtin_amdgcn_fractf(e) - 0.5f));
+  }
+  worst = w;
+  return packed;
+}
+__device__ __forceinline__ uint32_t i8ie_requant_pack4_pc(const int (&c)[4], const I8ieRequant& q, const float4& ms,
+                                                          const float* sb, int lo, float lof) {
+  float worst;
+  const uint32_t packed = i8ie_requant_est4_pc(c, q, ms, lof, worst);
+  if (i8ie_requant_est_ok(worst)) return packed;
+  return i8ie_requant_exact4_pc(c, q, sb, lo);
+}
+// (v_cvt_pk_u8_f32 saturates at 0: lof = -1 is no clamp at all, as in i8ie_requant_pack4_norelu)
+__device__ __forceinline__ uint32_t i8ie_requant_pack4_norelu_pc(const int (&c)[4], const I8ieRequant& q, const float4& ms,
+                                                                 const float* sb) {
+  return i8ie_requant_pack4_pc(c, q, ms, sb, 0, -1.0f);
+}
+
 #endif
 
 // ---- host side --------------------------------------------------------------------------------------------
@@ -108,4 +152,17 @@ inline I8ieRequant i8ie_make_requant(float s_in, float s_w, float s_out, int zp_
   r.fast = (s_in > 1e-30f && s_w > 1e-30f && s_out > 1e-30f && s_in < 1e30f && s_w < 1e30f && s_out < 1e30f &&
             ms > 1e-30 && ms < 1e30) ? I8IE_RQ_GUARDED : I8IE_RQ_EXACT;
   return r;
+}
+
+// Per-channel layers: the multiplier of column j (0 for s_w[j] == 0, see above), and whether the estimate may be used for
+// the whole layer -- every s_w[j] zero or ordinary, and every nonzero multiplier ordinary.
+inline float i8ie_requant_ms(float s_in, float s_w, float s_out) { return (float)((double)s_in * (double)s_w / (double)s_out); }
+inline bool i8ie_requant_pc_fast(float s_in, const float* s_w, int n, float s_out) {
+  if (!(s_in > 1e-30f && s_out > 1e-30f && s_in < 1e30f && s_out < 1e30f)) return false;
+  for (int j = 0; j < n; ++j) {
+    if (s_w[j] == 0.0f) continue;
+    const double ms = (double)s_in * (double)s_w[j] / (double)s_out;
+    if (!(s_w[j] > 1e-30f && s_w[j] < 1e30f && ms > 1e-30 && ms < 1e30)) return false;
+  }
+  return true;
 }

@@ -23,6 +23,8 @@ struct I8ieStemCall {
   int ob;
   int out_s8;    // 1: bytes stored re-biased (^0x80), the I8IE_LAYOUT_NHWC_S8 form
   int32_t* acc;  // null, or [n * OH * OW][N]: the convolution's pre-requant accumulators
+  const float* msv = nullptr;  // per-channel layers: [Npad] multipliers and weight scales (i8ie_requant.h); null otherwise
+  const float* sbv = nullptr;
 };
 int i8ie_stem_supported(int c, int stride, int N, int KH, int KW, int OH, int OW, int pool_k, int pool_s);
 int i8ie_stem_kpad(int KH, int KW);

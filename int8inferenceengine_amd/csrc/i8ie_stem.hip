@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void quantize_s2d_kernel(const void* __restric
 }
 
 // NG: 32-feature groups (N = 32 NG); KS: k-steps; ACC: also dump the INT32 accumulators (acc_dbg of the C-ABI)
-template <int NG, int KS, bool ACC>
+template <int NG, int KS, bool ACC, bool PC>
 __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
   uint8_t* const smem = stem_smem;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -402,6 +402,12 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
       const int orow = ((im * PHp + j + p.ob) * PWp + p.ob) * p.N;
       // one round: UN tasks side by side (tasks past the row's last are computed and stored nowhere)
       auto round = [&](const PoolTask (&tk)[UN], const v4i (&ocv)[UN]) {
+        // PC: the multipliers of the task's feature quad (its oc' quad sits at lds_ocp + 4 j0), from memory (L1 / L2)
+        float4 msq[UN];
+        if constexpr (PC) {
+#pragma unroll
+          for (int u = 0; u < UN; ++u) msq[u] = *reinterpret_cast<const float4*>(p.msv + ((tk[u].oc - p.lds_ocp) >> 2));
+        }
         v4i v[UN][PK * PK];
 #pragma unroll
         for (int u = 0; u < UN; ++u)
@@ -426,7 +432,8 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
           }
           c4[u][0] = m.x + ocv[u].x; c4[u][1] = m.y + ocv[u].y;  // max(C) + oc' = max(C + oc'): exact integer adds
           c4[u][2] = m.z + ocv[u].z; c4[u][3] = m.w + ocv[u].w;
-          d[u] = i8ie_requant_est4(c4[u], rq, lof, worst[u]);
+          if constexpr (PC) d[u] = i8ie_requant_est4_pc(c4[u], rq, msq[u], lof, worst[u]);
+          else d[u] = i8ie_requant_est4(c4[u], rq, lof, worst[u]);
         }
         float wmin = worst[0];
 #pragma unroll
@@ -434,7 +441,10 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
         if (!i8ie_requant_est_ok(wmin)) {  // a value within 2^-13 of a rounding boundary: the exact sequence for its pack
 #pragma unroll
           for (int u = 0; u < UN; ++u)
-            if (!i8ie_requant_est_ok(worst[u])) d[u] = i8ie_requant_exact4(c4[u], rq, lo_relu);
+            if (!i8ie_requant_est_ok(worst[u])) {
+              if constexpr (PC) d[u] = i8ie_requant_exact4_pc(c4[u], rq, p.sbv + ((tk[u].oc - p.lds_ocp) >> 2), lo_relu);
+              else d[u] = i8ie_requant_exact4(c4[u], rq, lo_relu);
+            }
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u) __builtin_amdgcn_raw_buffer_store_b32(d[u] ^ p.xor_out, rsO, tk[u].st, orow, 0);
@@ -543,21 +553,23 @@ __global__ __launch_bounds__(512, 2) void stem_conv_kernel(StemArgs p) {
   }
 }
 
-template <int NG, int KS, bool ACC>
+template <int NG, int KS, bool ACC, bool PC>
 int launch_stem_t(i8ie_ctx* ctx, const StemArgs& a, int grid, int lds) {
   static bool raised[64] = {};
   const int dev = ctx->device & 63;
   if (!raised[dev]) {
-    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_conv_kernel<NG, KS, ACC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_conv_kernel<NG, KS, ACC, PC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     raised[dev] = true;
   }
-  stem_conv_kernel<NG, KS, ACC><<<grid, 512, lds, ctx->stream>>>(a);
+  stem_conv_kernel<NG, KS, ACC, PC><<<grid, 512, lds, ctx->stream>>>(a);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }
 template <int NG, int KS>
 int launch_stem(i8ie_ctx* ctx, const StemArgs& a, int grid, int lds) {
-  return a.acc != nullptr ? launch_stem_t<NG, KS, true>(ctx, a, grid, lds) : launch_stem_t<NG, KS, false>(ctx, a, grid, lds);
+  if (a.msv != nullptr)
+    return a.acc != nullptr ? launch_stem_t<NG, KS, true, true>(ctx, a, grid, lds) : launch_stem_t<NG, KS, false, true>(ctx, a, grid, lds);
+  return a.acc != nullptr ? launch_stem_t<NG, KS, true, false>(ctx, a, grid, lds) : launch_stem_t<NG, KS, false, false>(ctx, a, grid, lds);
 }
 
 struct StemPlan {
@@ -728,6 +740,7 @@ int i8ie_stem_launch(i8ie_ctx* ctx, const I8ieStemCall& c) {
   a.relu_lo = c.relu ? c.zp_out : 0;
   a.out = c.out; a.ob = c.ob; a.xor_out = c.out_s8 ? 0x80808080u : 0u;
   a.acc = c.acc;
+  a.msv = c.msv; a.sbv = c.sbv;
   a.pitchP = s.pitchP; a.ringRowB = s.ringRowB; a.RING = s.RING;
   a.patchB = s.patchB;
   a.lds_patch = 0;

@@ -37,6 +37,8 @@ struct StemArgs {
   int role_split;            // 0: waves 0-3 multiply, 4-7 do the vector work (a multiplying and a vector wave on every SIMD);
                              // 1: waves 0, 1, 4, 5 multiply, 2, 3, 6, 7 do the vector work (waves w and w + 4 share a SIMD: two
                              //    SIMDs multiply, two do vector work -- no vector wave sits beside an MFMA stream)
+  const float* msv;          // PC kernels (per-channel layers): [Npad] multipliers and weight scales (i8ie_requant.h)
+  const float* sbv;
 };
 
 // Strip t of an image, tabulated once per block in LDS (8 ints): the scalar arithmetic of a strip is then two LDS reads

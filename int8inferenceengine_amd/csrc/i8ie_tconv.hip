@@ -71,6 +71,8 @@ struct TCArgs {
   int flags;                                 // always 0 in this library; removing it changes the kernel's code
   int32_t* acc;  // ACC kernels: [M][N] pre-requant accumulators (the cblas_gemm_s8u8s32 result, src/conv2d.cc:131-133)
   unsigned long long* dbg;  // always 0 in this library; removing it changes the kernel's code
+  const float* msv;  // PC kernels (per-channel layers): [Npad] multipliers and weight scales (i8ie_requant.h), read from
+  const float* sbv;  // memory in the epilogue: the LDS plan is unchanged
 };
 
 #define TC_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")  // (LDS writes of the re-bias pass are out before the hand-over)
@@ -98,7 +100,8 @@ __device__ __forceinline__ int tc_row_to_pix(int r) { return (r < 4) ? 2 * r : (
 // TMW: 16-pixel row tiles per wave (2 waves of a team along the pixels); NTW: 16-feature tiles per wave
 // (2 waves of a team x 2 teams along the features: a pass is 64 NTW features wide)
 // ACC: also dump the INT32 accumulators (acc_dbg of the C-ABI) -- a separate instantiation, the default one is untouched
-template <int TMW, int NTW, bool ACC>
+// PC: per-channel weight scales (multiplier quad per 4 features) -- likewise
+template <int TMW, int NTW, bool ACC, bool PC>
 __global__ __launch_bounds__(512, 2) void tconv_kernel(TCArgs p) {
   uint8_t* const smem = tc_smem;
   constexpr int BN = NTW * 64;
@@ -237,7 +240,13 @@ __global__ __launch_bounds__(512, 2) void tconv_kernel(TCArgs p) {
       for (int ni = 0; ni < NTW; ++ni) {
         const v4i c = acc[mi][ni];
         const int cv[4] = {c.x, c.y, c.z, c.w};
-        d[ni] = i8ie_requant_pack4(cv, rq, lo, lof);
+        if constexpr (PC) {  // features n0 + 16 ni + 4 lq .. + 3 (columns past N: nothing is stored, s_w[0] for the replay)
+          const int col = n0 + ni * 16 + 4 * lq;
+          const float4 msq = col < p.N ? *reinterpret_cast<const float4*>(p.msv + col) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+          d[ni] = i8ie_requant_pack4_pc(cv, rq, msq, p.sbv + (col < p.N ? col : 0), lo, lof);
+        } else {
+          d[ni] = i8ie_requant_pack4(cv, rq, lo, lof);
+        }
         if constexpr (ACC) {  // row = image-major pixel index (bands are whole rows), 4 consecutive features per lane
           const int col = n0 + ni * 16 + 4 * lq;
           if (pi < valid && col < p.N)
@@ -373,21 +382,23 @@ __global__ __launch_bounds__(256) void tconv_pack_kernel(const int8_t* __restric
   }
 }
 
-template <int TMW, int NTW, bool ACC>
+template <int TMW, int NTW, bool ACC, bool PC>
 int launch_tc_acc(i8ie_ctx* ctx, const TCArgs& a, int grid, int lds) {
   static bool raised[64] = {};
   const int dev = ctx->device & 63;
   if (!raised[dev]) {
-    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_kernel<TMW, NTW, ACC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    I8IE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_kernel<TMW, NTW, ACC, PC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     raised[dev] = true;
   }
-  tconv_kernel<TMW, NTW, ACC><<<grid, 512, lds, ctx->stream>>>(a);
+  tconv_kernel<TMW, NTW, ACC, PC><<<grid, 512, lds, ctx->stream>>>(a);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }
 template <int TMW, int NTW>
 int launch_tc(i8ie_ctx* ctx, const TCArgs& a, int grid, int lds) {
-  return a.acc != nullptr ? launch_tc_acc<TMW, NTW, true>(ctx, a, grid, lds) : launch_tc_acc<TMW, NTW, false>(ctx, a, grid, lds);
+  if (a.msv != nullptr)
+    return a.acc != nullptr ? launch_tc_acc<TMW, NTW, true, true>(ctx, a, grid, lds) : launch_tc_acc<TMW, NTW, false, true>(ctx, a, grid, lds);
+  return a.acc != nullptr ? launch_tc_acc<TMW, NTW, true, false>(ctx, a, grid, lds) : launch_tc_acc<TMW, NTW, false, false>(ctx, a, grid, lds);
 }
 
 }  // namespace
@@ -541,6 +552,7 @@ int i8ie_tconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   a.out_bytes = (unsigned)out_bytes;
   a.ob = c.ob; a.OHp = c.OH + 2 * c.ob; a.OWp = c.OW + 2 * c.ob;
   a.acc = c.acc;
+  a.msv = c.msv; a.sbv = c.sbv;
   a.lds_ring = 0;
   a.lds_ocp = R * slice_gran * 16;
   a.lds_tab = a.lds_ocp + npass * bn * 4;

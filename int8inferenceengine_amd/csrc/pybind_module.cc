@@ -838,7 +838,7 @@ class BaseLayer {
     cal_ = std::make_unique<Calibrator>();
     is_preparing_ = true;
   }
-  void convert() {  // src/layer.cc:36-54
+  void convert(bool per_channel = false) {  // src/layer.cc:36-54 (per_channel: the opt-in per-output-channel rule)
     if (is_quantized_) {
       std::cerr << "already quantized" << std::endl;
       return;
@@ -859,9 +859,18 @@ class BaseLayer {
     const ssize_t n = (ssize_t)b_.size();
     qw_.resize(w_.size());
     qb_.resize(b_.size());
-    check(i8ie_quantize_weight(w_.data(), (int64_t)w_.size(), b_.data(), (int64_t)b_.size(),
-                               reinterpret_cast<int8_t*>(qw_.data()), reinterpret_cast<int8_t*>(qb_.data()),
-                               &w_scale_));
+    per_channel_ = per_channel;
+    if (per_channel) {
+      w_scales_.assign((size_t)n, 0.0f);
+      check(i8ie_quantize_weight_per_channel(w_.data(), (int)n, (int64_t)(w_.size() / n), b_.data(),
+                                             reinterpret_cast<int8_t*>(qw_.data()), reinterpret_cast<int8_t*>(qb_.data()),
+                                             w_scales_.data()));
+      w_scale_ = 1;
+    } else {
+      check(i8ie_quantize_weight(w_.data(), (int64_t)w_.size(), b_.data(), (int64_t)b_.size(),
+                                 reinterpret_cast<int8_t*>(qw_.data()), reinterpret_cast<int8_t*>(qb_.data()),
+                                 &w_scale_));
+    }
     i8ie_layer* raw = make_handle(n);
     q_ = std::shared_ptr<i8ie_layer>(raw, [](i8ie_layer* l) { i8ie_layer_destroy(l); });
     check(i8ie_layer_set_output_qparams(q_.get(), scale_, zero_point_));
@@ -881,17 +890,29 @@ class BaseLayer {
   }
   std::tuple<float, int> output_qparams() const { return std::make_tuple(scale_, (int)zero_point_); }
   // additive: restore a converted layer from saved INT8 weights (what convert() would have produced)
+  // w_scale: a number (per-tensor layer) or an array of one scale per output feature (per-channel layer)
   void load_quantized(py::array_t<s8_t, py::array::c_style | py::array::forcecast> qw,
-                      py::array_t<s8_t, py::array::c_style | py::array::forcecast> qb, float w_scale, float s_out,
+                      py::array_t<s8_t, py::array::c_style | py::array::forcecast> qb, py::object w_scale, float s_out,
                       int zp_out) {
     if (zp_out < 0 || zp_out > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
     std::vector<ssize_t> shp(qw.shape(), qw.shape() + qw.ndim());
     if (shp.size() != wshape_.size()) throw std::runtime_error("i8ie: load_quantized: weight rank mismatch");
     wshape_ = shp;
     if (qb.size() != wshape_[0]) throw std::runtime_error("i8ie: load_quantized: bias size mismatch");
+    const bool pc = py::isinstance<py::array>(w_scale) ? py::array(w_scale).ndim() > 0
+                                                        : (py::isinstance<py::list>(w_scale) || py::isinstance<py::tuple>(w_scale));
+    std::vector<float> scales;
+    if (pc) {
+      auto a = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(w_scale);
+      if (!a || a.ndim() != 1 || a.size() != wshape_[0])
+        throw std::runtime_error("i8ie: load_quantized: weight_scale array must hold one scale per output feature");
+      scales.assign(a.data(), a.data() + a.size());
+    }
     qw_.assign(qw.data(), qw.data() + qw.size());
     qb_.assign(qb.data(), qb.data() + qb.size());
-    w_scale_ = w_scale;
+    per_channel_ = pc;
+    w_scales_ = scales;
+    w_scale_ = pc ? 1.0f : w_scale.cast<float>();
     scale_ = s_out;
     zero_point_ = (u8_t)zp_out;
     qparams_overridden_ = true;
@@ -920,8 +941,17 @@ class BaseLayer {
   }
   float weight_scale() const {
     need_quantized();
+    if (per_channel_) throw std::runtime_error("i8ie: weight_scale: per-channel layer (use weight_scales())");
     return w_scale_;
   }
+  py::array_t<float> weight_scales() const {  // float32 [out] in both modes (i8ie_layer_weight_scales)
+    need_quantized();
+    py::array_t<float> a((ssize_t)qb_.size());
+    int pc = 0;
+    check(i8ie_layer_weight_scales(q_.get(), a.mutable_data(), (int)qb_.size(), &pc));
+    return a;
+  }
+  bool is_per_channel() const { return is_quantized_ && per_channel_; }
   bool is_quantized() const { return is_quantized_; }
 
  protected:
@@ -1080,6 +1110,8 @@ class BaseLayer {
   float* b_dev_ = nullptr;
   std::vector<s8_t> qw_, qb_;
   float w_scale_ = 1;
+  bool per_channel_ = false;
+  std::vector<float> w_scales_;  // per-channel layers: s_w[j]
   std::unique_ptr<Calibrator> cal_;
   bool is_preparing_ = false;
   bool is_quantized_ = false;
@@ -1130,8 +1162,13 @@ class Linear : public BaseLayer {
   }
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
-    check(i8ie_linear_create(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
-                             reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1], w_scale_, &l));
+    if (per_channel_)
+      check(i8ie_linear_create_per_channel(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+                                           reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1],
+                                           w_scales_.data(), &l));
+    else
+      check(i8ie_linear_create(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+                               reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1], w_scale_, &l));
     return l;
   }
 };
@@ -1190,9 +1227,15 @@ class Conv2d : public BaseLayer {
   }
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
-    check(i8ie_conv2d_create(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
-                             reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1], (int)wshape_[2],
-                             (int)wshape_[3], (int)stride_, (int)padding_, w_scale_, &l));
+    if (per_channel_)
+      check(i8ie_conv2d_create_per_channel(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+                                           reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1],
+                                           (int)wshape_[2], (int)wshape_[3], (int)stride_, (int)padding_,
+                                           w_scales_.data(), &l));
+    else
+      check(i8ie_conv2d_create(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+                               reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1], (int)wshape_[2],
+                               (int)wshape_[3], (int)stride_, (int)padding_, w_scale_, &l));
     return l;
   }
 
@@ -1206,7 +1249,7 @@ void bind_layer_common(py::class_<L>& c) {
   c.def("load_weight", &L::load_weight)
       .def("load_bias", &L::load_bias)
       .def("prepare", &L::prepare)
-      .def("convert", &L::convert)
+      .def("convert", &L::convert, py::arg("per_channel") = false)
       .def("__call__", [](L& l, Tensor<float>& x) { return l.forward_f32(x); })
       .def("__call__", [](L& l, Tensor<u8_t>& x) { return std::get<0>(l.forward_u8(x, false)); })
       .def("forward_debug", [](L& l, Tensor<u8_t>& x) { return l.forward_u8(x, true); })
@@ -1217,6 +1260,8 @@ void bind_layer_common(py::class_<L>& c) {
       .def("q_weight", &L::q_weight)
       .def("q_bias", &L::q_bias)
       .def("weight_scale", &L::weight_scale)
+      .def("weight_scales", &L::weight_scales)
+      .def("is_per_channel", &L::is_per_channel)
       .def("is_quantized", &L::is_quantized);
 }
 

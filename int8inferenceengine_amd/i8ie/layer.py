@@ -23,9 +23,12 @@ class Layer:
         """Start collecting output samples for calibration (reference src/layer.cc:28-35)."""
         self.layer.prepare()
 
-    def convert(self):
-        """Quantise weights, fix the output (scale, zero_point) (reference src/layer.cc:36-54)."""
-        self.layer.convert()
+    def convert(self, per_channel=False):
+        """Quantise weights, fix the output (scale, zero_point) (reference src/layer.cc:36-54).
+
+        per_channel=True (additive, not the reference's rule): one symmetric max-abs weight scale per output
+        feature, rounded to nearest even (include/i8ie_hip.h, i8ie_quantize_weight_per_channel)."""
+        self.layer.convert(bool(per_channel))
 
     # ---- additive (the reference cannot inject or read these) ----------------
     def set_output_qparams(self, scale, zero_point):
@@ -34,6 +37,17 @@ class Layer:
 
     def output_qparams(self):
         return self.layer.output_qparams()
+
+    def weight_scale(self):
+        """The per-tensor weight scale (raises for a per-channel layer)."""
+        return self.layer.weight_scale()
+
+    def weight_scales(self):
+        """np.float32[out]: s_w[j] of every output feature (a per-tensor layer repeats its one scale)."""
+        return self.layer.weight_scales()
+
+    def is_per_channel(self):
+        return self.layer.is_per_channel()
 
     def forward_debug(self, x):
         """INT8 forward that also returns the INT32 pre-requant accumulators (numpy)."""

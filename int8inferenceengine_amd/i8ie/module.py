@@ -39,9 +39,10 @@ class Module:
         for _, layer in self._layers():
             layer.prepare()
 
-    def convert(self):
+    def convert(self, per_channel=False):
+        """per_channel=True: every layer with one weight scale per output feature (Layer.convert)."""
         for _, layer in self._layers():
-            layer.convert()
+            layer.convert(per_channel)
         self.is_quant = True
 
     # ---- additive: save / restore the converted (INT8) model ------------------
@@ -49,7 +50,8 @@ class Module:
     # quantised state when the process ends; these keep it as plain arrays.
     def quantized_state_dict(self):
         """{'<attr>.q_weight' int8, '<attr>.q_bias' int8, '<attr>.qparams' float64[3] =
-        (weight_scale, out_scale, out_zero_point)} for every converted layer."""
+        (weight_scale, out_scale, out_zero_point)} for every converted layer; a per-channel layer also has
+        '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused)."""
         import numpy as np
 
         out = {}
@@ -60,7 +62,11 @@ class Module:
             s_out, zp_out = L.output_qparams()
             out[name + ".q_weight"] = L.q_weight()
             out[name + ".q_bias"] = L.q_bias()
-            out[name + ".qparams"] = np.array([L.weight_scale(), s_out, zp_out], np.float64)
+            if L.is_per_channel():
+                out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
+                out[name + ".w_scales"] = np.asarray(L.weight_scales(), np.float32)
+            else:
+                out[name + ".qparams"] = np.array([L.weight_scale(), s_out, zp_out], np.float64)
         return out
 
     def load_quantized(self, state):
@@ -69,9 +75,13 @@ class Module:
 
         for name, layer in self._layers():
             w_scale, s_out, zp_out = (float(v) for v in state[name + ".qparams"])
+            if name + ".w_scales" in state:  # per-channel layer
+                w_scale = np.ascontiguousarray(state[name + ".w_scales"], np.float32)
+            else:
+                w_scale = float(np.float32(w_scale))
             layer.layer.load_quantized(np.asarray(state[name + ".q_weight"], np.int8),
                                        np.asarray(state[name + ".q_bias"], np.int8),
-                                       float(np.float32(w_scale)), float(np.float32(s_out)), int(zp_out))
+                                       w_scale, float(np.float32(s_out)), int(zp_out))
         self.is_quant = True
 
     def save_quantized(self, path):

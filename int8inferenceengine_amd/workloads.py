@@ -127,8 +127,9 @@ def build(name):
     return SpecNet()
 
 
-def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7):
-    """The reference workflow (notebook cells 'prepare -> one FP32 batch -> convert')."""
+def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, per_channel=False):
+    """The reference workflow (notebook cells 'prepare -> one FP32 batch -> convert'); per_channel=True converts
+    with one weight scale per output feature (Module.convert)."""
     import _CXX_i8ie as cx
     import i8ie
 
@@ -138,7 +139,7 @@ def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7):
     net.prepare()
     x = calib_batch if calib_batch is not None else synthetic_input(name, 100 if name != "alexnet" else 32, seed=99)
     net(i8ie.tensor(x))
-    net.convert()
+    net.convert(per_channel)
     return net
 
 
