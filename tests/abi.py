@@ -62,6 +62,38 @@ class Dev:
             self.ptr = C.c_void_p()
 
 
+class GuardedOut:
+    """A float32 output region with GUARD floats before and after it in one device allocation.  The guards are
+    pre-filled with GUARD_BITS and the region with FILL_BITS (a quiet NaN no arithmetic here produces), so a store
+    outside the region and an element never stored both show.  `ptr` is the region's address; read() returns
+    (region, guards untouched?)."""
+    GUARD = 4096
+    GUARD_BITS = 0xA5C3F00D
+    FILL_BITS = 0x7FC0DEAD
+
+    def __init__(self, ctx, shape):
+        self.shape = tuple(int(d) for d in shape)
+        self.size = int(np.prod(self.shape, dtype=np.int64))
+        host = np.full(self.size + 2 * self.GUARD, self.GUARD_BITS, np.uint32)
+        host[self.GUARD:self.GUARD + self.size] = self.FILL_BITS
+        self.buf = ctx.put(host)
+        self.ptr = C.c_void_p(self.buf.ptr.value + 4 * self.GUARD)
+
+    def read(self):
+        bits = self.buf.get()
+        g = self.GUARD
+        ok = bool((bits[:g] == self.GUARD_BITS).all() and (bits[g + self.size:] == self.GUARD_BITS).all())
+        return bits[g:g + self.size].view(np.float32).reshape(self.shape).copy(), ok
+
+    @classmethod
+    def unwritten(cls, out):
+        """number of elements of a read() result that still hold the fill pattern"""
+        return int((np.ascontiguousarray(out, np.float32).view(np.uint32) == cls.FILL_BITS).sum())
+
+    def free(self):
+        self.buf.free()
+
+
 class Ctx:
     def __init__(self, device=0):
         self.h = C.c_void_p()
@@ -221,6 +253,57 @@ class Ctx:
         for b in (di, out, acc):
             if b is not None:
                 b.free()
+        return r
+
+    # ---- FP32 ops (include/i8ie_hip.h, "FP32 ops") ------------------------------
+    def guarded(self, shape):
+        """A float32 output of `shape` inside a larger device buffer (GuardedOut)."""
+        return GuardedOut(self, shape)
+
+    def linear_f32(self, x, w, b):
+        """i8ie_linear_f32: x [m, k], w [n, k], b [n] -> (out [m, n], guards untouched?)."""
+        x, w, b = (np.ascontiguousarray(a, np.float32) for a in (x, w, b))
+        (m, k), n = x.shape, w.shape[0]
+        assert w.shape == (n, k) and b.shape == (n,)
+        di, dw, db, o = self.put(x), self.put(w), self.put(b), self.guarded((m, n))
+        try:
+            ck(lib().i8ie_linear_f32(self.h, di.ptr, m, k, dw.ptr, db.ptr, n, o.ptr))
+            return o.read()
+        finally:
+            for d in (di, dw, db, o):
+                d.free()
+
+    def conv2d_f32(self, x, w, b, stride, pad):
+        """i8ie_conv2d_f32: x [n, c, h, w], w [kc, c, kh, kw], b [kc] -> (out [n, kc, oh, ow], guards untouched?)."""
+        x, w, b = (np.ascontiguousarray(a, np.float32) for a in (x, w, b))
+        n, c, h, wd = x.shape
+        kc, c2, kh, kw = w.shape
+        assert c2 == c and b.shape == (kc,)
+        oh, ow = (h - kh + 2 * pad) // stride + 1, (wd - kw + 2 * pad) // stride + 1
+        di, dw, db, o = self.put(x), self.put(w), self.put(b), self.guarded((n, kc, oh, ow))
+        try:
+            ck(lib().i8ie_conv2d_f32(self.h, di.ptr, n, c, h, wd, dw.ptr, db.ptr, kc, kh, kw, stride, pad, o.ptr))
+            return o.read()
+        finally:
+            for d in (di, dw, db, o):
+                d.free()
+
+    def relu_f32(self, x):
+        x = np.ascontiguousarray(x, np.float32)
+        d, o = self.put(x), self.empty(x.shape, np.float32)
+        ck(lib().i8ie_relu_f32(self.h, d.ptr, o.ptr, C.c_int64(x.size)))
+        r = o.get()
+        d.free(); o.free()
+        return r
+
+    def maxpool2d_f32(self, x, k, s):
+        x = np.ascontiguousarray(x, np.float32)
+        n, c, h, w = x.shape
+        oh, ow = (h - k) // s + 1, (w - k) // s + 1
+        d, o = self.put(x), self.empty((n, c, oh, ow), np.float32)
+        ck(lib().i8ie_maxpool2d_f32(self.h, d.ptr, o.ptr, n, c, h, w, k, s))
+        r = o.get()
+        d.free(); o.free()
         return r
 
     # ---- v2 entry points ----------------------------------------------------
