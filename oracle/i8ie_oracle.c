@@ -20,16 +20,14 @@
  *   src/conv2d.cc:131-133 / src/fully_connected.cc:39-41; MKL 2021.4 shared objects are in this image and
  *   are called directly through ctypes by tests/golden/make_golden_mkl.py -- nothing of the reference is
  *   built for this): orc_gemm_u8s8s32                   (tests/golden/mkl_gemm_s8u8s32.npz)
- *   PARITY UNPINNED by a reference run (src/conv2d.cc, src/fully_connected.cc
- *   and src/layer.cc include mkl.h, which this image lacks, so those
- *   translation units are unbuildable here; the reference's own tests hold no
- *   golden vectors for them):
- *     orc_quantize_weight, orc_conv_offsets, orc_linear_offsets, orc_im2col_u8,
- *     and the composition of the pinned pieces in orc_conv2d_u8 / orc_linear_u8
- *   For these the integer contraction is exact by definition
- *   (C = sum A*B + oc) and is cross-checked in tests/ against an independent
- *   int64 numpy/torch formulation; the float epilogue they feed is the pinned
- *   orc_down_scale.
+ *   pinned against the reference's own compiled LAYER code (oracle/_ref/_i8ie_ref_layers, built from
+ *   src/layer.cc + src/conv2d.cc + src/fully_connected.cc where they lie, with oracle/mkl_stub/mkl.h standing in for
+ *   the header the image lacks and oracle/gemm_provider.c -- itself held to the MKL fixtures -- in MKL's place):
+ *     orc_quantize_weight, orc_conv_offsets, orc_linear_offsets, orc_im2col_u8 and the composition in
+ *     orc_conv2d_u8 / orc_linear_u8 (offset vector, accumulators and output of every case), oracle/pipeline.py
+ *     (tests/golden/ref_quantize_weight.npz, ref_conv2d_u8.npz, ref_linear_u8.npz, ref_networks.npz,
+ *     ref_alexnet_digests.json, ref_kernel_digests.json; tests/test_ref_layers_golden.py)
+ *   The cross-checks against an independent int64 numpy/torch formulation (tests/test_oracle_golden.py) stay.
  */
 #include <stdint.h>
 #include <stdlib.h>

@@ -14,11 +14,12 @@ _LIB = None
 
 
 def build(quiet=True):
-    """Compile liborc.so (and oracle/_ref when /root/reference is present)."""
+    """Compile liborc.so and libgemm_provider.so (and, when /root/reference is present, oracle/_ref: the
+    reference's elementwise units and its layer code, each behind a binding file of ours)."""
     out = subprocess.DEVNULL if quiet else None
     subprocess.check_call(["make", "-C", _HERE, "all"], stdout=out)
     if os.path.isdir("/root/reference/src"):
-        subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=out, stderr=out)
+        subprocess.check_call(["make", "-C", _HERE, "ref", "ref_layers"], stdout=out, stderr=out)
 
 
 def lib():

@@ -5,9 +5,10 @@
 //     /root/reference/src/calibrator.cc       (Calibrator::sample / get_range)
 // They are compiled WHERE THEY LIE by oracle/Makefile (target `ref`) into
 // oracle/_ref/ (git-ignored).  Nothing from the reference is copied into this
-// repository.  The rest of the reference (conv2d.cc, fully_connected.cc,
-// layer.cc, pybind11.cc) includes mkl.h, which the image lacks, so it is
-// unbuildable here and is NOT stood in for.
+// repository.  The reference's layer code (layer.cc, conv2d.cc,
+// fully_connected.cc) includes mkl.h, which the image lacks; it is built by
+// the target `ref_layers` behind ref_layers_bind.cc, with mkl_stub/mkl.h and
+// gemm_provider.c in MKL's place.
 //
 // TEST INFRASTRUCTURE ONLY: used by tests/golden/make_golden.py (in this
 // container) to produce golden vectors, and by tests/ to validate

@@ -11,7 +11,8 @@ itself never travels.
 Covers SURVEY.md section 8 rows a1 (quantize), a5 (down_scale), a6 (dequantize),
 a7 (relu u8), a8 (max_pool2d u8) and the calibrator's range computation
 (src/calibrator.cc, compiled the same way).  Rows a2/a3/a4/a10 live in translation
-units that include mkl.h (absent from the image) and cannot be built here.
+units that include mkl.h (absent from the image): make_golden_layers.py covers them,
+with a stand-in header and a plain-C GEMM provider in MKL's place.
 
 usage:  python tests/golden/make_golden.py
 """
