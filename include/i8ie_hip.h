@@ -229,6 +229,13 @@ int i8ie_linear_f32(i8ie_ctx* ctx, const float* in_dev, int m, int k, const floa
 int i8ie_conv2d_f32(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int w,
                     const float* w_dev, const float* b_dev, int kc, int kh, int kw, int stride,
                     int pad, float* out_dev);
+/* i8ie_conv2d_f32 with groups (src/conv2d.cc:63-98 per group; groups: not in the reference): w_dev is
+ * [kc, c/groups, kh, kw], output features [g*kc/groups, (g+1)*kc/groups) see input channels [g*c/groups, (g+1)*c/groups).
+ * groups must divide c and kc (I8IE_ERR_ARG otherwise); groups == 1 is i8ie_conv2d_f32.  One launch, the group index
+ * a grid dimension.  The path taken before convert() and while calibrating. */
+int i8ie_conv2d_f32_grouped(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int w,
+                            const float* w_dev, const float* b_dev, int kc, int kh, int kw, int stride,
+                            int pad, int groups, float* out_dev);
 int i8ie_relu_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int64_t n);
 int i8ie_maxpool2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h,
                        int w, int kernel_size, int stride);
@@ -277,6 +284,16 @@ int i8ie_conv2d_u8s8(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, 
                      uint8_t zp_in, const int32_t* oc_dev, float s_in, float s_w, float s_out,
                      uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
 
+/* Conv2d::forward_prop(Tensor<u8>&&)  src/conv2d.cc:100-142, one reference convolution per group; groups: not in the
+ * reference.  i8ie_conv2d_u8s8 with `groups` dividing c and kc (I8IE_ERR_ARG otherwise): qw [kc, (c/groups)*kh*kw],
+ * oc [kc] from i8ie_conv_offsets on that matrix (K = (c/groups)*kh*kw).  groups == 1 is i8ie_conv2d_u8s8 itself;
+ * groups > 1 reads the weights back and packs them for this one call (it waits for the stream): a layer handle
+ * (i8ie_conv2d_create_grouped) keeps them packed. */
+int i8ie_conv2d_u8s8_grouped(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w,
+                             const int8_t* qw_dev, int kc, int kh, int kw, int stride, int pad, int groups,
+                             uint8_t zp_in, const int32_t* oc_dev, float s_in, float s_w, float s_out,
+                             uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
+
 /* ---- layer handles: converted layers with device-resident packed weights -
  * What BaseLayer::convert() leaves behind (src/layer.cc:36-54: q_weight_,
  * q_bias_, scale_, zero_point_), kept on the device in MFMA operand order,
@@ -294,6 +311,26 @@ int i8ie_linear_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const i
                                    const float* s_w_host, i8ie_layer** out);
 int i8ie_conv2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c,
                                    int kh, int kw, int stride, int pad, const float* s_w_host, i8ie_layer** out);
+/* Grouped / depthwise Conv2d: src/conv2d.cc:100-142 applied per group; groups: not in the reference.
+ * `groups` divides c and kc; with Cg = c/groups, Ng = kc/groups, output features [g*Ng, (g+1)*Ng) are the reference
+ * convolution of input channels [g*Cg, (g+1)*Cg) with weight rows [g*Ng, (g+1)*Ng), all groups sharing the layer's
+ * (s_in, zp_in, s_w, s_out, zp_out).  qw_host is [kc][Cg*kh*kw], K ordered (c, kh, kw) inside the group; the offset
+ * vector is src/conv2d.cc:117-124 on that matrix as it stands.  groups < 1 or a non-divisor: I8IE_ERR_ARG (checked
+ * before any device call).  groups == 1 returns exactly what i8ie_conv2d_create(_per_channel) returns.
+ * Kernels (csrc/i8ie_gconv.hip): gconv_mfma when Cg*kh*kw >= 32 and I8IE_OPT_FORCE_FALLBACK is off, gconv_direct
+ * otherwise (depthwise, channel multipliers, tiny groups, and every grouped layer under the option).
+ * A grouped handle supports i8ie_layer_forward, i8ie_layer_forward_fused and i8ie_layer_forward_pool, in every
+ * layout (NCHW, NHWC with any border, NHWC_S8 by converting around the kernel).  It folds nothing:
+ * i8ie_layer_fuses_pool answers 0 (the pool runs as the max-pool kernel behind the convolution),
+ * i8ie_layer_rebiased_io answers 0 / 0, i8ie_layer_accepts_f32_input answers 0 (i8ie_layer_forward_f32_input*
+ * then return I8IE_ERR_STATE), and i8ie_layer_forward_dequant is for Linear layers only. */
+int i8ie_conv2d_create_grouped(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c,
+                               int kh, int kw, int stride, int pad, int groups, float s_w, i8ie_layer** out);
+int i8ie_conv2d_create_grouped_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc,
+                                           int c, int kh, int kw, int stride, int pad, int groups,
+                                           const float* s_w_host, i8ie_layer** out);
+/* *groups = the layer's groups: 1 for Linear and for a dense Conv2d */
+int i8ie_layer_groups(const i8ie_layer* layer, int* groups);
 /* the weight scales: out float [n] (n = out features); a per-tensor layer gives n copies of its scale and
  * *per_channel = 0, a per-channel layer its s_w[j] and *per_channel = 1 */
 int i8ie_layer_weight_scales(const i8ie_layer* layer, float* out, int n, int* per_channel);

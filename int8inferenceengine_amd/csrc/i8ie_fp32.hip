@@ -37,6 +37,8 @@ struct F32Args {
   const int2* ktab;  // [K]: {input offset of K position k relative to the window origin, (kernel row << 16) | kernel column}
   int M, N, K;
   int c, h, wd, oh, ow, stride, pad, P;  // P = oh * ow output pixels per image (1 for Linear)
+  // grouped Conv2d (blockIdx.z = group): N, K, c above are one group's; these the whole tensors' channel counts
+  int ctot, Ntot;
 };
 
 __global__ __launch_bounds__(256) void k_table_kernel(int2* tab, int K, int h, int w, int kh, int kw) {
@@ -51,6 +53,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(F32Args p) {
   __shared__ float Xs[FK][FP], Ws[FK][FP];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int bm0 = blockIdx.y * FB, bn0 = blockIdx.x * FB;
+  const int grp = blockIdx.z;  // (0 unless a grouped Conv2d)
+  const float* wg = p.w + (size_t)grp * p.N * p.K;
+  const float* bg = p.b + (size_t)grp * p.N;
 
   // ---- this thread's gather row (activations): row bm0 + tid % 128, K positions (tid / 128) + 2 e
   const int xr = bm0 + (tid & 127), xk0 = tid >> 7;
@@ -58,7 +63,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(F32Args p) {
   const int ximg = xr / p.P, xpix = xr - ximg * p.P;
   const int xoy = xpix / p.ow, xox = xpix - xoy * p.ow;
   const int y0 = xoy * p.stride - p.pad, x0 = xox * p.stride - p.pad;
-  const float* xbase = p.in + ((size_t)ximg * p.c * p.h + y0) * (size_t)p.wd + x0;  // (may point before the image: only used with valid taps)
+  const float* xbase = p.in + (((size_t)ximg * p.ctot + (size_t)grp * p.c) * p.h + y0) * (size_t)p.wd + x0;  // (may point before the image: only used with valid taps)
   // ---- this thread's weight elements: K position tid % 16, features tid / 16 + 16 e
   const int wk = tid & 15, wj0 = tid >> 4;
 
@@ -75,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(F32Args p) {
       }
       xv[e] = v;
       const int j = bn0 + wj0 + 16 * e, kw_ = k0 + wk;
-      wv[e] = (j < p.N && kw_ < p.K) ? p.w[(size_t)j * p.K + kw_] : 0.0f;
+      wv[e] = (j < p.N && kw_ < p.K) ? wg[(size_t)j * p.K + kw_] : 0.0f;
     }
   };
   auto stage = [&]() {
@@ -129,18 +134,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(F32Args p) {
       const int r = bm0 + col;  // output pixel (global row)
       if (r >= p.M) continue;
       const int img = r / p.P, pix = r - img * p.P;
-      float* obase = p.out + (size_t)img * p.N * p.P + pix;
+      float* obase = p.out + ((size_t)img * p.Ntot + (size_t)grp * p.N) * p.P + pix;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int f = bn0 + 64 * wa + 32 * i + 8 * (e >> 2) + 4 * hh + (e & 3);
-          if (f < p.N) obase[(size_t)f * p.P] = acc[i][j][e] + p.b[f];
+          if (f < p.N) obase[(size_t)f * p.P] = acc[i][j][e] + bg[f];
         }
     } else {
       const int f = bn0 + col;
       if (f >= p.N) continue;
-      const float bias = p.b[f];
+      const float bias = bg[f];
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -153,17 +158,17 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(F32Args p) {
 }
 
 template <bool CONV>
-int launch_gemm_f32(i8ie_ctx* ctx, F32Args a, int kh, int kw, const char* name) {
+int launch_gemm_f32(i8ie_ctx* ctx, F32Args a, int kh, int kw, const char* name, int groups = 1) {
   I8IE_REQUIRE((size_t)a.M * a.K < ((size_t)1 << 62) && a.K < (1 << 30), "f32 gemm: dimensions");
   I8IE_TRY(i8ie_ws_reserve(ctx, (size_t)a.K * sizeof(int2) + 256));
   int2* tab = reinterpret_cast<int2*>(ctx->ws);
   k_table_kernel<<<(a.K + 255) / 256 < 64 ? (a.K + 255) / 256 : 64, 256, 0, ctx->stream>>>(tab, a.K, a.h, a.wd, kh, kw);
   I8IE_LAUNCH_CHECK();
   a.ktab = tab;
-  const dim3 grid((unsigned)((a.N + FB - 1) / FB), (unsigned)((a.M + FB - 1) / FB));
+  const dim3 grid((unsigned)((a.N + FB - 1) / FB), (unsigned)((a.M + FB - 1) / FB), (unsigned)groups);
   // (blockIdx.y carries the row tiles: 65 535 x 128 = 8.4 M rows per launch; AlexNet's largest, 1000 x 55 x 55, is 3.0 M)
   I8IE_REQUIRE(grid.y <= 65535u, "f32 gemm: more than 8.4 M output rows in one call");
-  I8ieProfScope prof(ctx, name, 0.0, (double)a.M * a.K * 4 + (double)a.N * a.K * 4 + (double)a.M * a.N * 4);
+  I8ieProfScope prof(ctx, name, 0.0, ((double)a.M * a.K * 4 + (double)a.N * a.K * 4 + (double)a.M * a.N * 4) * groups);
   gemm_f32_kernel<CONV><<<grid, 256, 0, ctx->stream>>>(a);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
@@ -216,12 +221,21 @@ int i8ie_linear_f32(i8ie_ctx* ctx, const float* in, int m, int k, const float* w
   a.in = in; a.w = w; a.b = b; a.out = out;
   a.M = m; a.N = n; a.K = k;
   a.c = k; a.h = 1; a.wd = 1; a.oh = 1; a.ow = 1; a.stride = 1; a.pad = 0; a.P = 1;
+  a.ctot = k; a.Ntot = n;
   return launch_gemm_f32<false>(ctx, a, 1, 1, "linear_f32_mfma");
 }
 
 int i8ie_conv2d_f32(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, const float* wt,
                     const float* b, int kc, int kh, int kw, int stride, int pad, float* out) {
+  return i8ie_conv2d_f32_grouped(ctx, in, n, c, h, w, wt, b, kc, kh, kw, stride, pad, 1, out);
+}
+
+// src/conv2d.cc:63-98 per group; groups: not in the reference.  One launch: the group is the grid's z dimension.
+int i8ie_conv2d_f32_grouped(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, const float* wt,
+                            const float* b, int kc, int kh, int kw, int stride, int pad, int groups, float* out) {
   I8IE_REQUIRE(ctx && in && wt && b && out, "null argument");
+  I8IE_REQUIRE(groups >= 1 && groups <= 65535, "groups must be in [1, 65535]");
+  I8IE_REQUIRE(c > 0 && kc > 0 && c % groups == 0 && kc % groups == 0, "groups must divide the input and the output channels");
   I8IE_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && kc > 0 && kh > 0 && kw > 0, "non-positive dimension");
   I8IE_REQUIRE(stride > 0 && pad >= 0, "bad stride/padding");
   I8IE_REQUIRE(h - kh + 2 * pad >= 0 && w - kw + 2 * pad >= 0, "kernel larger than padded input");
@@ -230,9 +244,10 @@ int i8ie_conv2d_f32(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, 
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   F32Args a{};
   a.in = in; a.w = wt; a.b = b; a.out = out;
-  a.M = n * oh * ow; a.N = kc; a.K = c * kh * kw;
-  a.c = c; a.h = h; a.wd = w; a.oh = oh; a.ow = ow; a.stride = stride; a.pad = pad; a.P = oh * ow;
-  return launch_gemm_f32<true>(ctx, a, kh, kw, "conv2d_f32_mfma");
+  a.M = n * oh * ow; a.N = kc / groups; a.K = (c / groups) * kh * kw;
+  a.c = c / groups; a.h = h; a.wd = w; a.oh = oh; a.ow = ow; a.stride = stride; a.pad = pad; a.P = oh * ow;
+  a.ctot = c; a.Ntot = kc;
+  return launch_gemm_f32<true>(ctx, a, kh, kw, "conv2d_f32_mfma", groups);
 }
 
 int i8ie_relu_f32(i8ie_ctx* ctx, const float* in, float* out, int64_t n) {

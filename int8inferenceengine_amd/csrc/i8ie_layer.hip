@@ -10,6 +10,8 @@
 //   B  channels <= 4 and stride % 4 == 0 (AlexNet conv1): the NCHW input is repacked
 //      once into a physically padded, 4-pixel-grouped NHWC image; then path A's kernel
 //   F  anything else: materialised im2col + v1 GEMM (i8ie_gemm.hip)
+//   G  groups > 1 (i8ie_conv2d_create_grouped; not in the reference): one reference convolution per group, in the
+//      grouped kernels of i8ie_gconv.hip over NHWC activations
 // Activations cross the ABI as NCHW (the reference's layout) or, on request, as
 // NHWC so that consecutive layers skip the layout conversion.
 #include <cmath>
@@ -21,6 +23,7 @@
 #include "i8ie_calls.h"
 #include "i8ie_stem.h"
 #include "i8ie_requant.h"
+#include "i8ie_gconv.h"
 
 int i8ie_launch_pad_rows(i8ie_ctx* ctx, const void* src, int rows, int k, void* dst, int rows_pad, int k_pad,
                          int fill);
@@ -90,7 +93,7 @@ constexpr size_t kColBudget = (size_t)192 << 20;  // im2col scratch per chunk (f
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
 
-enum { PATH_F = 0, PATH_A = 1, PATH_B = 2 };
+enum { PATH_F = 0, PATH_A = 1, PATH_B = 2, PATH_G = 3 };  // PATH_G: grouped (i8ie_gconv.hip)
 
 struct ConvGeom {
   int c, h, w, kc, kh, kw, stride, pad, oh, ow, K, Kpad;
@@ -187,7 +190,11 @@ struct i8ie_layer {
   int8_t* Bpack = nullptr;  // [Npad][Kpad] zero padded, reference K order (Linear; conv path F)
   int8_t* Bperm = nullptr;  // Linear fed by an NHWC-flattened activation: Bpack with K reordered (h, w, c)
   int perm_c = 0, perm_hw = 0;
-  int path = PATH_F;        // conv: PATH_A / PATH_B / PATH_F
+  int path = PATH_F;        // conv: PATH_A / PATH_B / PATH_F / PATH_G
+  int groups = 1;           // conv, groups > 1 (PATH_G): K above is the reduction length INSIDE a group, (c / groups) * kh * kw,
+  int Ngp = 0, Kgp = 0;     // and the weights live in `wc` as [groups][Ngp][Kgp], K ordered (kh, kw, cg) (i8ie_gconv.h)
+  int8_t* Bg = nullptr;
+  int* gtab = nullptr;      // the MFMA kernel's gather table (i8ie_gconv_ktab), in `wc` as well
   int8_t* Bpack2 = nullptr; // conv paths A/B: [Npad][Kpad2], K ordered (kh, kw, c) / grouped
   int K2 = 0, Kpad2 = 0;    // valid / padded K of Bpack2 (bytes)
   I8ieWCache wc;            // Bpack2 in the fragment orders of i8ie_pconv.hip / i8ie_tconv.hip: one buffer per packing
@@ -342,6 +349,42 @@ int i8ie_conv2d_u8s8(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int 
   return conv_run_v1(ctx, in, n, cg, Bpack, oc, wsum, zp_in, s_in, s_w, s_out, zp_out, out, acc, col, ipc);
 }
 
+static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const int8_t* qb_host, int n, int K, int c,
+                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups = 1);
+
+// the stateless form with groups (groups: not in the reference).  groups > 1 packs the weights for this one call: the
+// device weights are read back, a temporary layer handle runs the call with the caller's oc[] and is destroyed.
+int i8ie_conv2d_u8s8_grouped(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int kh,
+                             int kw, int stride, int pad, int groups, uint8_t zp_in, const int32_t* oc, float s_in,
+                             float s_w, float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
+  I8IE_REQUIRE(groups >= 1, "groups must be >= 1");
+  I8IE_REQUIRE(c > 0 && kc > 0 && c % groups == 0 && kc % groups == 0, "groups must divide the input and the output channels");
+  if (groups == 1)
+    return i8ie_conv2d_u8s8(ctx, in, n, c, h, w, qw, kc, kh, kw, stride, pad, zp_in, oc, s_in, s_w, s_out, zp_out, out, acc);
+  I8IE_REQUIRE(ctx && in && qw && oc && out, "null argument");
+  I8IE_REQUIRE(n > 0, "non-positive batch");
+  ConvGeom cg;
+  I8IE_TRY(conv_geom(c, h, w, kc, kh, kw, stride, pad, &cg));
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  const int Kg = (c / groups) * kh * kw;
+  std::vector<int8_t> qw_host((size_t)kc * Kg), qb_host((size_t)kc, 0);
+  I8IE_TRY(i8ie_memcpy_d2h(ctx, qw_host.data(), qw, qw_host.size()));
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(layer_create(ctx, true, qw_host.data(), qb_host.data(), kc, Kg, c, kh, kw, stride, pad, s_w, &L, groups));
+  L->s_out = s_out;
+  L->zp_out = zp_out;
+  // the caller's offset vector (it carries the bias term) instead of the handle's own
+  int rc = i8ie_launch_finish_offsets(ctx, oc, L->wsum, L->qb, s_in, kc, L->ocp, nullptr);
+  if (rc == I8IE_OK) {
+    L->oc_valid = true;
+    L->oc_s_in = s_in;
+    L->oc_zp_in = zp_in;
+    rc = i8ie_layer_forward(L, in, n, h, w, s_in, zp_in, out, acc);
+  }
+  i8ie_layer_destroy(L);
+  return rc;
+}
+
 // ---- NHWC helpers exposed on the ABI -----------------------------------------------------------
 int i8ie_layout_convert_u8(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int c, int h, int w, int to_nhwc,
                            int border, uint8_t border_value) {
@@ -377,7 +420,7 @@ int i8ie_maxpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in, int in_border, uint
 
 // ---- layer handles ----------------------------------------------------------------------------
 static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const int8_t* qb_host, int n, int K, int c,
-                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out) {
+                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups) {
   I8IE_REQUIRE(ctx && qw_host && qb_host && out, "null argument");
   I8IE_REQUIRE(n > 0 && K > 0, "non-positive dimension");
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
@@ -388,8 +431,24 @@ static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const i
   L->Kpad = round_up(K, 128);
   L->Npad = round_up(n, 128);
   // MFMA-order weight panel for the implicit-GEMM conv paths, built on the host once
-  std::vector<int8_t> pack2;
-  if (conv && c % 16 == 0) {
+  std::vector<int8_t> pack2, packg;
+  std::vector<int> gtab;
+  if (conv && groups > 1) {
+    // grouped: qw_host is [n][Cg * kh * kw]; group g's Ng rows go to panel g in (kh, kw, cg) order
+    const int Cg = c / groups, Ng = n / groups;
+    L->path = PATH_G;
+    L->groups = groups;
+    L->Ngp = round_up(Ng, 16);
+    L->Kgp = round_up(K, 64);
+    packg.assign((size_t)groups * L->Ngp * L->Kgp, 0);
+    for (int j = 0; j < n; ++j)
+      for (int ch = 0; ch < Cg; ++ch)
+        for (int y = 0; y < kh; ++y)
+          for (int x = 0; x < kw; ++x)
+            packg[((size_t)(j / Ng) * L->Ngp + j % Ng) * L->Kgp + ((size_t)y * kw + x) * Cg + ch] =
+                qw_host[(((size_t)j * Cg + ch) * kh + y) * kw + x];
+    i8ie_gconv_ktab(Cg, kh, kw, L->Kgp, gtab);
+  } else if (conv && c % 16 == 0) {
     L->path = PATH_A;
     L->K2 = kh * kw * c;
     L->Kpad2 = round_up(L->K2, 128);
@@ -440,6 +499,14 @@ static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const i
     if (!pack2.empty()) {
       if ((rc = i8ie_malloc(ctx, pack2.size(), (void**)&L->Bpack2)) != I8IE_OK) break;
       if ((rc = i8ie_memcpy_h2d(ctx, L->Bpack2, pack2.data(), pack2.size())) != I8IE_OK) break;
+    }
+    if (!packg.empty()) {  // (kept per packing key like the re-packed panels: never overwritten, freed with the layer)
+      if ((rc = i8ie_malloc(ctx, packg.size(), (void**)&L->Bg)) != I8IE_OK) break;
+      L->wc.ents.push_back({0x6763000000000001ull, L->Bg});
+      if ((rc = i8ie_memcpy_h2d(ctx, L->Bg, packg.data(), packg.size())) != I8IE_OK) break;
+      if ((rc = i8ie_malloc(ctx, gtab.size() * 4, (void**)&L->gtab)) != I8IE_OK) break;
+      L->wc.ents.push_back({0x6763000000000002ull, L->gtab});
+      if ((rc = i8ie_memcpy_h2d(ctx, L->gtab, gtab.data(), gtab.size() * 4)) != I8IE_OK) break;
     }
     if (!packs.empty()) {
       if ((rc = i8ie_malloc(ctx, packs.size(), (void**)&L->Bstem)) != I8IE_OK) break;
@@ -529,6 +596,48 @@ int i8ie_conv2d_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_ho
   I8IE_REQUIRE(stride > 0, "stride must be positive");
   I8IE_REQUIRE(pad >= 0, "negative padding");
   return layer_create(ctx, true, qw_host, qb_host, kc, c * kh * kw, c, kh, kw, stride, pad, s_w, out);
+}
+
+// groups: not in the reference (src/conv2d.cc:100-142 per group).  Argument checks come before any device call.
+static int check_groups(int kc, int c, int kh, int kw, int stride, int pad, int groups) {
+  I8IE_REQUIRE(kc > 0 && c > 0 && kh > 0 && kw > 0, "non-positive dimension");
+  I8IE_REQUIRE(stride > 0, "stride must be positive");
+  I8IE_REQUIRE(pad >= 0, "negative padding");
+  I8IE_REQUIRE(groups >= 1, "groups must be >= 1");
+  I8IE_REQUIRE(c % groups == 0 && kc % groups == 0, "groups must divide the input and the output channels");
+  I8IE_REQUIRE(groups <= 65535, "at most 65535 groups");
+  return I8IE_OK;
+}
+
+int i8ie_conv2d_create_grouped(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh, int kw,
+                               int stride, int pad, int groups, float s_w, i8ie_layer** out) {
+  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
+  if (groups == 1) return i8ie_conv2d_create(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, s_w, out);
+  return layer_create(ctx, true, qw_host, qb_host, kc, (c / groups) * kh * kw, c, kh, kw, stride, pad, s_w, out, groups);
+}
+
+int i8ie_conv2d_create_grouped_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c,
+                                           int kh, int kw, int stride, int pad, int groups, const float* s_w_host,
+                                           i8ie_layer** out) {
+  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
+  if (groups == 1) return i8ie_conv2d_create_per_channel(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, s_w_host, out);
+  I8IE_REQUIRE(out != nullptr, "bad argument");
+  I8IE_TRY(check_scales(s_w_host, kc));
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_conv2d_create_grouped(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, groups, 1.0f, &L));
+  const int rc = layer_make_per_channel(L, s_w_host);
+  if (rc != I8IE_OK) {
+    i8ie_layer_destroy(L);
+    return rc;
+  }
+  *out = L;
+  return I8IE_OK;
+}
+
+int i8ie_layer_groups(const i8ie_layer* L, int* groups) {
+  I8IE_REQUIRE(L && groups, "null argument");
+  *groups = L->groups;
+  return I8IE_OK;
 }
 
 int i8ie_layer_set_output_qparams(i8ie_layer* L, float s_out, uint8_t zp_out) {
@@ -789,7 +898,28 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
   const int ph = pool ? (cg.oh - pool_k) / pool_s + 1 : cg.oh, pw = pool ? (cg.ow - pool_k) / pool_s + 1 : cg.ow;
   const size_t in_bytes = (size_t)m * cg.c * cg.h * cg.w;
   const size_t out_bytes = (size_t)m * cg.kc * ph * pw;
-  const int path = force_fallback(ctx) ? PATH_F : L->path;
+  const int path = L->path == PATH_G ? PATH_G : (force_fallback(ctx) ? PATH_F : L->path);
+
+  if (path == PATH_G) {
+    // grouped: NHWC in and out of the kernel (the input's own border serves, or bounds checks against zp_in); the layout
+    // conversions around it as on the other paths.  The force-fallback option picks gconv_direct inside the launcher.
+    const bool in_nchw = in_layout == I8IE_LAYOUT_NCHW, out_nchw = out_layout == I8IE_LAYOUT_NCHW;
+    const size_t a_bytes = in_nchw ? i8ie_align_up(in_bytes, 256) : 0;
+    const size_t o_bytes = out_nchw ? i8ie_align_up(out_bytes, 256) : 0;
+    if (a_bytes + o_bytes) I8IE_TRY(i8ie_ws_reserve(ctx, a_bytes + o_bytes + 256));
+    uint8_t* ws = (uint8_t*)ctx->ws;
+    if (in_nchw) I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, in, ws, m, cg.c, cg.h, cg.w, 0));
+    I8ieGconvCall g{};
+    g.A = in_nchw ? ws : in; g.m = m; g.H = cg.h; g.W = cg.w; g.C = cg.c; g.ib = in_nchw ? 0 : in_border;
+    g.OH = cg.oh; g.OW = cg.ow; g.stride = cg.stride; g.pad = cg.pad; g.KH = cg.kh; g.KW = cg.kw;
+    g.groups = L->groups; g.Cg = cg.c / L->groups; g.Ng = L->n / L->groups; g.Ngp = L->Ngp; g.Kgp = L->Kgp;
+    g.Bp = L->Bg; g.ktab = L->gtab; g.ocp = L->ocp; g.msv = msv_arg(L); g.sbv = sbv_arg(L);
+    g.s_in = s_in; g.s_w = sw_arg(L); g.s_out = L->s_out; g.zp_in = zp_in; g.zp_out = L->zp_out; g.relu = relu;
+    g.out = out_nchw ? ws + a_bytes : out; g.ob = out_nchw ? 0 : out_border; g.acc = acc;
+    I8IE_TRY(i8ie_gconv_launch(ctx, g));
+    if (out_nchw) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, g.out, out, m, cg.kc, cg.oh, cg.ow, 0));
+    return I8IE_OK;
+  }
 
   if (path == PATH_F) {
     const int ipc = chunk_images(cg, m);

@@ -821,6 +821,7 @@ class BaseLayer {
 
   void load_weight(py::array_t<float, py::array::c_style | py::array::forcecast> w) {  // include/layer.h:15-20
     if (!has_fp32_) throw std::runtime_error("i8ie: load_weight: layer is already converted");
+    check_weight_shape(std::vector<ssize_t>(w.shape(), w.shape() + w.ndim()), "load_weight");
     wshape_.assign(w.shape(), w.shape() + w.ndim());
     w_.assign(w.data(), w.data() + w.size());
     release_fp32_dev();
@@ -897,6 +898,7 @@ class BaseLayer {
     if (zp_out < 0 || zp_out > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
     std::vector<ssize_t> shp(qw.shape(), qw.shape() + qw.ndim());
     if (shp.size() != wshape_.size()) throw std::runtime_error("i8ie: load_quantized: weight rank mismatch");
+    check_weight_shape(shp, "load_quantized");
     wshape_ = shp;
     if (qb.size() != wshape_[0]) throw std::runtime_error("i8ie: load_quantized: bias size mismatch");
     const bool pc = py::isinstance<py::array>(w_scale) ? py::array(w_scale).ndim() > 0
@@ -956,6 +958,8 @@ class BaseLayer {
 
  protected:
   virtual void check_shapes() const = 0;
+  // a layer that was given its channel counts refuses a weight of another shape (Conv2d with groups: [out, in/groups, k, k])
+  virtual void check_weight_shape(const std::vector<ssize_t>&, const char*) const {}
   virtual i8ie_layer* make_handle(ssize_t n) = 0;
   // Deferred INT8 forward: returns a tensor whose launch happens when it is first needed.
   Tensor<u8_t> defer(Tensor<u8_t>& in, std::vector<ssize_t> oshape, int m, int h, int w, bool spatial) {
@@ -1175,9 +1179,10 @@ class Linear : public BaseLayer {
 
 class Conv2d : public BaseLayer {
  public:
-  Conv2d(ssize_t in_channel, ssize_t out_channel, ssize_t kernel_size, ssize_t stride, ssize_t padding)
-      : BaseLayer({out_channel, in_channel, kernel_size, kernel_size}, out_channel),
-        stride_(stride), padding_(padding) {
+  // groups: not in the reference (src/conv2d.cc:100-142 per group); the weight is [out, in / groups, k, k]
+  Conv2d(ssize_t in_channel, ssize_t out_channel, ssize_t kernel_size, ssize_t stride, ssize_t padding, ssize_t groups = 1)
+      : BaseLayer({out_channel, checked_cg(in_channel, out_channel, groups), kernel_size, kernel_size}, out_channel),
+        stride_(stride), padding_(padding), groups_(groups), in_channels_(in_channel) {
     if (stride == 0) throw std::runtime_error("i8ie: Conv2d: stride must not be 0");  // include/conv2d.h:12-14
     if (stride < 0 || padding < 0) throw std::runtime_error("i8ie: Conv2d: negative stride/padding");
   }
@@ -1189,7 +1194,7 @@ class Conv2d : public BaseLayer {
 
   std::vector<ssize_t> out_shape(const std::vector<ssize_t>& s) const {
     if (s.size() != 4) throw std::runtime_error("i8ie: Conv2d expects an NCHW tensor");
-    if (s[1] != wshape_[1]) throw std::runtime_error("i8ie: Conv2d: input channels do not match the weight");
+    if (s[1] != in_channels()) throw std::runtime_error("i8ie: Conv2d: input channels do not match the weight");
     const ssize_t kh = wshape_[2], kw = wshape_[3];
     if (s[2] - kh + 2 * padding_ < 0 || s[3] - kw + 2 * padding_ < 0)
       throw std::runtime_error("i8ie: Conv2d: kernel larger than the padded input");
@@ -1200,9 +1205,9 @@ class Conv2d : public BaseLayer {
     check_shapes();
     Tensor<float> out(out_shape(in.shape));
     upload_fp32();
-    check(i8ie_conv2d_f32(ctx(), in.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3],
-                          w_dev_, b_dev_, (int)wshape_[0], (int)wshape_[2], (int)wshape_[3], (int)stride_,
-                          (int)padding_, out.dptr()));
+    check(i8ie_conv2d_f32_grouped(ctx(), in.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3],
+                                  w_dev_, b_dev_, (int)wshape_[0], (int)wshape_[2], (int)wshape_[3], (int)stride_,
+                                  (int)padding_, (int)groups_, out.dptr()));
     maybe_sample(out);
     return out;
   }
@@ -1225,23 +1230,41 @@ class Conv2d : public BaseLayer {
     if (wshape_.size() != 4) throw std::runtime_error("i8ie: Conv2d weight must be [out, in, kh, kw]");
     if (has_fp32_ && (ssize_t)b_.size() != wshape_[0]) throw std::runtime_error("i8ie: Conv2d bias size mismatch");
   }
+  void check_weight_shape(const std::vector<ssize_t>& shp, const char* what) const override {
+    if (in_channels_ <= 0) return;  // (built from arrays: the weight defines the layer)
+    if (shp.size() != 4 || shp[0] != wshape_[0] || shp[1] != in_channels_ / groups_ || shp[2] != wshape_[2] || shp[3] != wshape_[3])
+      throw std::runtime_error(std::string("i8ie: Conv2d: ") + what + ": weight must be [out, in / groups, k, k]");
+  }
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
     if (per_channel_)
-      check(i8ie_conv2d_create_per_channel(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
-                                           reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1],
-                                           (int)wshape_[2], (int)wshape_[3], (int)stride_, (int)padding_,
-                                           w_scales_.data(), &l));
+      check(i8ie_conv2d_create_grouped_per_channel(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+                                                   reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)in_channels(),
+                                                   (int)wshape_[2], (int)wshape_[3], (int)stride_, (int)padding_,
+                                                   (int)groups_, w_scales_.data(), &l));
     else
-      check(i8ie_conv2d_create(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
-                               reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1], (int)wshape_[2],
-                               (int)wshape_[3], (int)stride_, (int)padding_, w_scale_, &l));
+      check(i8ie_conv2d_create_grouped(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+                                       reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)in_channels(),
+                                       (int)wshape_[2], (int)wshape_[3], (int)stride_, (int)padding_, (int)groups_,
+                                       w_scale_, &l));
     return l;
   }
 
+ public:
+  ssize_t groups() const { return groups_; }
+
  private:
+  static ssize_t checked_cg(ssize_t in_channel, ssize_t out_channel, ssize_t groups) {
+    if (groups < 1) throw std::runtime_error("i8ie: Conv2d: groups must be >= 1");
+    if (in_channel % groups != 0 || out_channel % groups != 0)
+      throw std::runtime_error("i8ie: Conv2d: groups must divide in_channels and out_channels");
+    return in_channel / groups;
+  }
+  ssize_t in_channels() const { return wshape_[1] * groups_; }
   ssize_t stride_ = 1;
   ssize_t padding_ = 0;
+  ssize_t groups_ = 1;
+  ssize_t in_channels_ = 0;  // as constructed from sizes (0: constructed from arrays)
 };
 
 template <typename L>
@@ -1312,8 +1335,10 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
     c.def(py::init<py::array_t<float, py::array::c_style | py::array::forcecast>,
                    py::array_t<float, py::array::c_style | py::array::forcecast>>())
         .def(py::init([](Tensor<float>& w, Tensor<float>& b) { return new Conv2d(w.numpy(), b.numpy()); }))
-        .def(py::init<ssize_t, ssize_t, ssize_t, ssize_t, ssize_t>(), py::arg("in_channels"),
-             py::arg("out_channels"), py::arg("kernel_size"), py::arg("stride") = 1, py::arg("padding") = 0);
+        .def(py::init<ssize_t, ssize_t, ssize_t, ssize_t, ssize_t, ssize_t>(), py::arg("in_channels"),
+             py::arg("out_channels"), py::arg("kernel_size"), py::arg("stride") = 1, py::arg("padding") = 0,
+             py::arg("groups") = 1)
+        .def("groups", &Conv2d::groups);
     bind_layer_common(c);
   }
 

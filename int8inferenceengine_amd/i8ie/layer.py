@@ -49,6 +49,10 @@ class Layer:
     def is_per_channel(self):
         return self.layer.is_per_channel()
 
+    def groups(self):
+        """Groups of a Conv2d (1 for a dense Conv2d and for Linear)."""
+        return self.layer.groups() if hasattr(self.layer, "groups") else 1
+
     def forward_debug(self, x):
         """INT8 forward that also returns the INT32 pre-requant accumulators (numpy)."""
         out, acc = self.layer.forward_debug(x.data)
@@ -61,5 +65,7 @@ class Linear(Layer):
 
 
 class Conv2d(Layer):
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0):
-        self.layer = _C.Conv2d(in_channels, out_channels, kernel_size, stride, padding)
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, groups=1):
+        """groups (additive, not in the reference): output features [g*out/groups, (g+1)*out/groups) see input channels
+        [g*in/groups, (g+1)*in/groups); the weight is [out, in/groups, k, k].  groups == in_channels is depthwise."""
+        self.layer = _C.Conv2d(in_channels, out_channels, kernel_size, stride, padding, groups)

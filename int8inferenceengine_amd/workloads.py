@@ -12,7 +12,7 @@ product path (SpecNet, through i8ie) and the CPU oracle in tests/bench.
 import numpy as np
 
 # name -> (layers, spec, input_shape CHW)
-#   layers: {attr: ("conv", in_c, out_c, k, stride, pad) | ("fc", in_f, out_f)}
+#   layers: {attr: ("conv", in_c, out_c, k, stride, pad[, groups]) | ("fc", in_f, out_f)}
 #   spec  : [("layer", attr) | ("relu",) | ("pool", k, s) | ("flatten", features)]
 NETWORKS = {
     # sample/notebooks/AlexNet_cifar10_resize224.ipynb:47-71
@@ -49,6 +49,21 @@ NETWORKS = {
     "mnist_fc": ({"fc": ("fc", 784, 10)}, [("flatten", 784), ("layer", "fc")], (1, 28, 28)),
 }
 
+# The AlexNet of the paper (Krizhevsky et al. 2012, figure 2): conv2, conv4 and conv5 have groups = 2.  Not in the reference
+# (its Conv2d has no groups); everything else is the "alexnet" entry.
+NETWORKS["alexnet_paper"] = (
+    dict(NETWORKS["alexnet"][0], conv2=("conv", 96, 256, 5, 1, 2, 2), conv4=("conv", 384, 384, 3, 1, 1, 2),
+         conv5=("conv", 384, 256, 3, 1, 1, 2)),
+    NETWORKS["alexnet"][1],
+    NETWORKS["alexnet"][2],
+)
+
+
+def conv_groups(L):
+    """groups of a ("conv", ...) layer tuple: its optional 7th element"""
+    return L[6] if len(L) > 6 else 1
+
+
 # MACs per image (SURVEY.md Appendix C): the algorithmic work of the INT8 contractions
 ALEXNET_MACS_PER_IMAGE = 1131201056
 
@@ -60,9 +75,9 @@ def macs_per_image(name):
         if op[0] == "layer":
             L = layers[op[1]]
             if L[0] == "conv":
-                _, ic, oc, k, s, p = L
+                _, ic, oc, k, s, p = L[:6]
                 h, w = (h - k + 2 * p) // s + 1, (w - k + 2 * p) // s + 1
-                total += h * w * oc * ic * k * k
+                total += h * w * oc * (ic // conv_groups(L)) * k * k
                 c = oc
             else:
                 total += L[1] * L[2]
@@ -77,7 +92,7 @@ def synthetic_state_dict(name, seed=42):
     layers = NETWORKS[name][0]
     sd = {}
     for attr, L in layers.items():
-        shape = (L[2], L[1], L[3], L[3]) if L[0] == "conv" else (L[2], L[1])
+        shape = (L[2], L[1] // conv_groups(L), L[3], L[3]) if L[0] == "conv" else (L[2], L[1])
         fan_in = int(np.prod(shape[1:]))
         sd[attr + ".weight"] = (rng.uniform(-1, 1, shape) * np.sqrt(6.0 / fan_in)).astype(np.float32)
         sd[attr + ".bias"] = (rng.uniform(-1, 1, shape[0]) / np.sqrt(fan_in)).astype(np.float32)
@@ -107,7 +122,10 @@ def build(name):
             super().__init__()
             for attr, L in layers.items():
                 if L[0] == "conv":
-                    setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5]))
+                    if conv_groups(L) == 1:
+                        setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5]))
+                    else:
+                        setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], groups=L[6]))
                 else:
                     setattr(self, attr, i8ie.Linear(L[1], L[2]))
 
@@ -137,7 +155,7 @@ def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, p
     net.load(state_dict if state_dict is not None else synthetic_state_dict(name, seed))
     cx.set_calibration_seed(calib_seed)  # the reference's calibrator is unseeded (std::random_device)
     net.prepare()
-    x = calib_batch if calib_batch is not None else synthetic_input(name, 100 if name != "alexnet" else 32, seed=99)
+    x = calib_batch if calib_batch is not None else synthetic_input(name, 100 if not name.startswith("alexnet") else 32, seed=99)
     net(i8ie.tensor(x))
     net.convert(per_channel)
     return net
