@@ -418,6 +418,33 @@ int i8ie_fill_border_u8(i8ie_ctx* ctx, uint8_t* buf_dev, int n, int c, int h, in
 int i8ie_maxpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, uint8_t* out_dev,
                            int out_border, int n, int c, int h, int w, int kernel_size, int stride);
 
+/* ---- quantized residual Add (no counterpart in the reference: it has no op that joins two tensors) ------------
+ * Defined as a composition of the reference's own expressions -- dequantize (src/quantize_utils.cc:38-42) of both
+ * operands, down_scale's clamp and truncation (src/quantize_utils.cc:27-36), relu<u8> (src/functional.cc:15-26) --
+ * in IEEE fp32, one rounding per operation, no contraction:
+ *     fa = (float)((int)a - (int)zp_a) * s_a;   fb = (float)((int)b - (int)zp_b) * s_b
+ *     t  = (fa + fb) / s_out + (float)zp_out
+ *     q  = t >= 255 ? 255 : (t < 0 ? 0 : (u8)t)          truncation toward zero
+ *     q  = relu ? max(q, zp_out) : q
+ * (s_a, zp_a), (s_b, zp_b): the operands' own quantisation parameters; (s_out, zp_out): the result's.  The bytes equal
+ * that sequence for every input pair, whichever way the kernel evaluates it (csrc/i8ie_add.hip).  Scales must be
+ * finite and s_out > 0 (I8IE_ERR_ARG otherwise).  Stateless and capturable in a graph.
+ * i8ie_add_u8: n bytes in one physical order (NCHW, [m, k] rows, border-free NHWC); 16-byte aligned buffers; out may
+ * alias a or b, and a may be b. */
+int i8ie_add_u8(i8ie_ctx* ctx, const uint8_t* a_dev, const uint8_t* b_dev, uint8_t* out_dev, int64_t n, float s_a,
+                uint8_t zp_a, float s_b, uint8_t zp_b, float s_out, uint8_t zp_out, int relu);
+/* The same arithmetic (no reference counterpart) on NHWC buffers [n, h+2b, w+2b, c], each with its own border b and
+ * each plain (x_s8 = 0) or re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80).  Only the interior of `out` is
+ * written: its border bytes are the caller's and must hold zp_out (zp_out ^ 0x80 when out_s8), as i8ie_fill_border_u8
+ * leaves them.  Any c; rows of w * c bytes are the contiguous unit (16 / 4 / 1 bytes per lane by c % 16, c % 4).  With
+ * all three borders 0 this is the flat form (and out may alias an operand). */
+int i8ie_add_u8_nhwc(i8ie_ctx* ctx, const uint8_t* a_dev, int a_border, int a_s8, const uint8_t* b_dev, int b_border,
+                     int b_s8, uint8_t* out_dev, int out_border, int out_s8, int n, int c, int h, int w, float s_a,
+                     uint8_t zp_a, float s_b, uint8_t zp_b, float s_out, uint8_t zp_out, int relu);
+/* out = a + b in fp32, one rounding (no reference counterpart): the Add before convert() and while calibrating.
+ * 16-byte aligned buffers; out may alias a or b. */
+int i8ie_add_f32(i8ie_ctx* ctx, const float* a_dev, const float* b_dev, float* out_dev, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -316,11 +316,31 @@ struct PendNode {
     made.push_back(Made{relu, border, st});
     return st;
   }
+  // a result already produced for this relu, whatever border / re-bias it was asked with: for a consumer that reads its
+  // operand as it lies (add), so that a producer launched for another consumer is not launched a second time
+  std::shared_ptr<Storage> find_any(bool relu) const {
+    for (const Made& m : made)
+      if (m.relu == relu && m.st) return m.st;
+    return nullptr;
+  }
+  // the pending producers this node reads (none once they have launched): lets a two-operand consumer launch the operand
+  // that is downstream of the other one first
+  std::vector<std::weak_ptr<PendNode>> inputs;
+  bool reads(const PendNode* target) const {
+    for (const auto& w : inputs)
+      if (auto n = w.lock()) {
+        if (n.get() == target) return true;
+        if (n->made.empty() && n->reads(target)) return true;
+      }
+    return false;
+  }
 };
 template <typename F>
-std::shared_ptr<PendNode> make_pend(F&& f) {
+std::shared_ptr<PendNode> make_pend(F&& f, std::initializer_list<std::shared_ptr<PendNode>> inputs = {}) {
   auto n = std::make_shared<PendNode>();
   n->fn = std::forward<F>(f);
+  for (const auto& i : inputs)
+    if (i) n->inputs.push_back(i);
   return n;
 }
 
@@ -707,7 +727,96 @@ Tensor<u8_t> max_pool2d_u8(Tensor<u8_t>& in, ssize_t k, ssize_t s) {  // src/fun
         }
         if (relu) check(i8ie_relu_u8(ctx(), (const uint8_t*)st->dev, (uint8_t*)st->dev, (int64_t)st->bytes, zp));
         return st;
-      });
+      }, {in.pend});
+  return out;
+}
+
+// ---- add (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_add_u8) ----------------------------
+Tensor<float> add_f32(Tensor<float>& a, Tensor<float>& b) {
+  if (a.shape != b.shape) throw std::runtime_error("i8ie: add: shapes differ (there is no broadcasting)");
+  Tensor<float> out(a.shape);
+  check(i8ie_add_f32(ctx(), a.dptr(), b.dptr(), out.dptr(), a.size));
+  return out;
+}
+// The storage an operand of add is read from, as it lies (any layout, border, re-bias).  A producer that has launched for
+// another consumer -- the skip tensor, made bordered / re-biased for the first conv of the block -- is taken from its
+// node's results; one that has not launches plain.
+std::shared_ptr<Storage> add_operand(Tensor<u8_t>& t) {
+  if (t.pend) {
+    if (auto st = t.pend->find_any(t.pend_relu)) {
+      t.st = st;
+      t.pend.reset();
+      t.pend_f32.reset();
+      t.qsrc.reset();
+    } else {
+      t.realize();
+    }
+  }
+  if (!t.st) throw std::runtime_error("i8ie: empty tensor");
+  t.st->device_ptr();  // (uploads a host-made tensor, waits for an asynchronous upload)
+  return t.st;
+}
+Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
+  if (a.shape != b.shape) throw std::runtime_error("i8ie: add: shapes differ (there is no broadcasting)");
+  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error("i8ie: add: the output scale must be positive and finite");
+  Tensor<u8_t> out;
+  out.shape = a.shape;
+  out.size = a.size;
+  out.scale = scale;
+  out.zero_point = (u8_t)zp;
+  Tensor<u8_t> ta = a, tb = b;  // share the operands' storage / pending launches
+  const float s_a = a.scale, s_b = b.scale;
+  const u8_t zp_a = a.zero_point, zp_b = b.zero_point, zp_o = (u8_t)zp;
+  const std::vector<ssize_t> shp = a.shape;
+  const ssize_t n = a.size;
+  // deferred like max_pool2d's result: relu(add(..)) is one launch, and a consuming conv gets its zero-point border and,
+  // where it reads them, re-biased bytes straight from the add kernel
+  out.pend = make_pend(
+      [ta, tb, s_a, s_b, zp_a, zp_b, scale, zp_o, shp, n](bool relu, int border, bool s8) mutable {
+        // b = f(a) still pending: launching b first launches a for f (bordered as f wants it), and a is then read as it lies
+        const bool b_first = ta.pend && tb.pend && ta.pend != tb.pend && tb.pend->made.empty() && tb.pend->reads(ta.pend.get());
+        std::shared_ptr<Storage> sa, sb;
+        if (b_first) {
+          sb = add_operand(tb);
+          sa = add_operand(ta);
+        } else {
+          sa = add_operand(ta);
+          sb = add_operand(tb);
+        }
+        const bool four = shp.size() == 4;
+        auto same_nhwc = [](const Storage& x, const Storage& y) {
+          return x.dn == y.dn && x.dc == y.dc && x.dh == y.dh && x.dw == y.dw;
+        };
+        std::shared_ptr<Storage> tmp;  // an NCHW operand converted for this launch
+        if (sa->layout != sb->layout || (sa->layout == I8IE_LAYOUT_NHWC && !same_nhwc(*sa, *sb))) {
+          if (four) {  // the engine keeps NHWC between layers (and a consumer that asked for a border reads NHWC)
+            std::shared_ptr<Storage>& nchw = sa->layout == I8IE_LAYOUT_NCHW ? sa : sb;
+            tmp = device_storage((size_t)n);
+            tmp->set_nhwc(shp, 0);
+            check(i8ie_layout_convert_u8(ctx(), (const uint8_t*)nchw->device_ptr(), (uint8_t*)tmp->dev, (int)shp[0], (int)shp[1],
+                                         (int)shp[2], (int)shp[3], 1, 0, 0));
+            nchw = tmp;
+          } else {  // a flattened NHWC activation against plain rows: back to the reference's order
+            sa->to_nchw();
+            sb->to_nchw();
+          }
+        }
+        std::shared_ptr<Storage> st;
+        if (sa->layout == I8IE_LAYOUT_NHWC) {
+          const std::vector<ssize_t> lshp = {sa->dn, sa->dc, sa->dh, sa->dw};
+          st = nhwc_storage(lshp, four ? border : 0, zp_o, s8);
+          check(i8ie_add_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
+                                 sb->border, sb->s8 ? 1 : 0, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, sa->dn, sa->dc, sa->dh,
+                                 sa->dw, s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
+        } else {
+          st = device_storage((size_t)n);
+          check(i8ie_add_u8(ctx(), (const uint8_t*)sa->device_ptr(), (const uint8_t*)sb->device_ptr(), (uint8_t*)st->dev, (int64_t)n,
+                            s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
+        }
+        // (the operands are released with the closure's copies, as a layer's input is)
+        return st;
+      }, {a.pend, b.pend});
   return out;
 }
 // the s8 instantiations of the generic templates (src/functional.cc:5-13, 36-64, registered at :78-82)
@@ -798,6 +907,16 @@ struct Calibrator {
     return std::make_tuple(scale, zp);
   }
 };
+
+// what a preparing layer (or Add) does with its FP32 result: src/conv2d.cc:94-96, src/fully_connected.cc:17-19
+void calib_sample(Calibrator& cal, Tensor<float>& out) {
+  if (Calibrator::on_device()) {  // no copy of the layer output to the host
+    cal.sample_device(out.dptr(), out.size);
+    return;
+  }
+  py::array_t<float> a = out.numpy();
+  cal.sample(a.data(), out.size);
+}
 
 // ------------------------------------------------------------------ layers ----
 class BaseLayer {
@@ -1040,7 +1159,8 @@ class BaseLayer {
       // launch in `x = relu(layer(x))`, later if the un-fused result is observed as well)
       return st;
     };
-    out.pend = make_pend([run, src, h, w](bool relu, int border, bool s8) mutable { return run(src, h, w, relu, border, s8, 0, 0); });
+    out.pend = make_pend([run, src, h, w](bool relu, int border, bool s8) mutable { return run(src, h, w, relu, border, s8, 0, 0); },
+                         {in.pend});
     if (spatial) {
       // max_pool2d right behind this (relu'd) conv: one call of the library, which folds the pool into the convolution's
       // epilogue where a kernel of its can and runs the max-pool kernel behind it otherwise
@@ -1098,13 +1218,7 @@ class BaseLayer {
     w_dev_ = b_dev_ = nullptr;
   }
   void maybe_sample(Tensor<float>& out) {  // src/conv2d.cc:94-96, src/fully_connected.cc:17-19
-    if (!is_preparing_) return;
-    if (Calibrator::on_device()) {  // no copy of the layer output to the host
-      cal_->sample_device(out.dptr(), out.size);
-      return;
-    }
-    py::array_t<float> a = out.numpy();
-    cal_->sample(a.data(), out.size);
+    if (is_preparing_) calib_sample(*cal_, out);
   }
 
   std::vector<ssize_t> wshape_;
@@ -1267,6 +1381,74 @@ class Conv2d : public BaseLayer {
   ssize_t in_channels_ = 0;  // as constructed from sizes (0: constructed from arrays)
 };
 
+// The residual Add as a layer without weights: the layers' prepare / convert state machine (src/layer.cc:28-54) around
+// its output (scale, zero_point); FP32 tensors add in FP32 (and are sampled while preparing), u8 tensors after convert().
+class Add {
+ public:
+  Add() = default;
+  Add(const Add&) = delete;
+  Add& operator=(const Add&) = delete;
+  void prepare() {
+    if (is_quantized_) {
+      std::cerr << "already quantized" << std::endl;
+      return;
+    }
+    cal_ = std::make_unique<Calibrator>();
+    is_preparing_ = true;
+  }
+  void convert(bool /*per_channel: an Add has no weights*/ = false) {
+    if (is_quantized_) {
+      std::cerr << "already quantized" << std::endl;
+      return;
+    }
+    if (!is_preparing_) {
+      if (!qparams_overridden_) std::cerr << "No prepared, use default config" << std::endl;
+    } else {
+      float s;
+      u8_t z;
+      std::tie(s, z) = cal_->get_range(1);
+      if (!qparams_overridden_) {
+        scale_ = s;
+        zero_point_ = z;
+      }
+      cal_.reset();
+    }
+    is_preparing_ = false;
+    is_quantized_ = true;
+  }
+  void set_output_qparams(float s, int zp) {
+    if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+    scale_ = s;
+    zero_point_ = (u8_t)zp;
+    qparams_overridden_ = true;
+  }
+  std::tuple<float, int> output_qparams() const { return std::make_tuple(scale_, (int)zero_point_); }
+  void load_quantized(float s_out, int zp_out) {  // what convert() would have left behind
+    set_output_qparams(s_out, zp_out);
+    cal_.reset();
+    is_preparing_ = false;
+    is_quantized_ = true;
+  }
+  bool is_quantized() const { return is_quantized_; }
+  Tensor<float> forward_f32(Tensor<float>& a, Tensor<float>& b) {
+    Tensor<float> out = add_f32(a, b);
+    if (is_preparing_) calib_sample(*cal_, out);
+    return out;
+  }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& a, Tensor<u8_t>& b) {
+    if (!is_quantized_) throw std::runtime_error("i8ie: Add is not converted (call convert() first)");
+    return add_u8(a, b, scale_, zero_point_);
+  }
+
+ private:
+  std::unique_ptr<Calibrator> cal_;
+  bool is_preparing_ = false;
+  bool is_quantized_ = false;
+  bool qparams_overridden_ = false;
+  float scale_ = 1;
+  u8_t zero_point_ = 0;
+};
+
 template <typename L>
 void bind_layer_common(py::class_<L>& c) {
   c.def("load_weight", &L::load_weight)
@@ -1321,6 +1503,9 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
   m.def("max_pool2d", &max_pool2d_u8);
   m.def("relu", &relu_s8);               // src/functional.cc:81
   m.def("max_pool2d", &max_pool2d_s8);
+  // additive (the reference joins no two tensors): a + b in FP32; the quantized Add of include/i8ie_hip.h on u8 tensors
+  m.def("add", &add_f32, py::arg("a"), py::arg("b"));
+  m.def("add", &add_u8, py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("zero_point"));
 
   {
     py::class_<Linear> c(m, "Linear");  // src/fully_connected.cc:54-72
@@ -1341,6 +1526,17 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
         .def("groups", &Conv2d::groups);
     bind_layer_common(c);
   }
+
+  py::class_<Add>(m, "Add")
+      .def(py::init<>())
+      .def("prepare", &Add::prepare)
+      .def("convert", &Add::convert, py::arg("per_channel") = false)
+      .def("__call__", &Add::forward_f32)
+      .def("__call__", &Add::forward_u8)
+      .def("set_output_qparams", &Add::set_output_qparams, py::arg("scale"), py::arg("zero_point"))
+      .def("output_qparams", &Add::output_qparams)
+      .def("load_quantized", &Add::load_quantized, py::arg("out_scale"), py::arg("out_zero_point"))
+      .def("is_quantized", &Add::is_quantized);
 
   // ---- additive runtime controls -------------------------------------------------
   m.def("abi_version", []() { return i8ie_version(); });

@@ -7,7 +7,7 @@ device-resident and `.numpy()` copies back to the host.
 """
 import _CXX_i8ie as _C
 
-from .layer import Conv2d, Layer, Linear
+from .layer import Add, Conv2d, Layer, Linear
 from .module import Module
 from .tensor import Tensor
 
@@ -15,7 +15,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
-    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module",
+    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -47,6 +47,20 @@ def dequantize(x):
 
 
 # ---- additive helpers (not in the reference) ---------------------------------
+def add(a, b, scale=None, zero_point=None):
+    """a + b of two tensors of equal shape (no broadcasting).  FP32 tensors: plain fp32 sum, `scale` / `zero_point` must
+    not be given.  uint8 tensors: the quantized add of include/i8ie_hip.h (i8ie_add_u8); the result's `scale` and
+    `zero_point` are required.  `i8ie.Add` is the calibrated form for use inside a Module."""
+    quantized = type(a.data).__name__ == "6TensorIhE"
+    if quantized:
+        if scale is None or zero_point is None:
+            raise TypeError("add of uint8 tensors needs the result's scale and zero_point")
+        return Tensor(_C.add(a.data, b.data, float(scale), int(zero_point)))
+    if scale is not None or zero_point is not None:
+        raise TypeError("add of FP32 tensors takes no scale / zero_point")
+    return Tensor(_C.add(a.data, b.data))
+
+
 def synchronize():
     """Wait for all queued device work (ops are asynchronous on one HIP stream)."""
     _C.synchronize()

@@ -69,3 +69,31 @@ class Conv2d(Layer):
         """groups (additive, not in the reference): output features [g*out/groups, (g+1)*out/groups) see input channels
         [g*in/groups, (g+1)*in/groups); the weight is [out, in/groups, k, k].  groups == in_channels is depthwise."""
         self.layer = _C.Conv2d(in_channels, out_channels, kernel_size, stride, padding, groups)
+
+
+class Add(Layer):
+    """Quantized residual add `y = self.add1(a, b)` (additive, not in the reference): a layer without weights.
+
+    FP32 tensors add in FP32 (sampled by the calibrator while preparing, as a layer's FP32 output is); uint8 tensors,
+    after convert(), by the arithmetic of include/i8ie_hip.h (i8ie_add_u8) with this Add's output (scale, zero_point).
+    Shapes must be equal (no broadcasting).  Takes part in Module.prepare() / convert() / quantized_state_dict();
+    Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values); load_weight, load_bias,
+    weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
+
+    def __init__(self):
+        self.layer = _C.Add()
+
+    def __call__(self, a, b):
+        return Tensor(self.layer(a.data, b.data))
+
+    def convert(self, per_channel=False):
+        """per_channel is accepted and ignored."""
+        self.layer.convert()
+
+    def is_per_channel(self):
+        return False
+
+    def _no_weights(self, *args, **kwargs):
+        raise RuntimeError("i8ie: an Add has no weights")
+
+    load_weight = load_bias = weight_scale = weight_scales = forward_debug = _no_weights

@@ -13,7 +13,10 @@ import numpy as np
 
 # name -> (layers, spec, input_shape CHW)
 #   layers: {attr: ("conv", in_c, out_c, k, stride, pad[, groups]) | ("fc", in_f, out_f)}
-#   spec  : [("layer", attr) | ("relu",) | ("pool", k, s) | ("flatten", features)]
+#   spec  : [("layer", attr) | ("relu",) | ("pool", k, s) | ("flatten", features)
+#            | ("save", tag)              remember the current tensor under `tag`
+#            | ("add", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Add (not in `layers`)
+#            | ("branch", tag, [ops...])  run ops on saved[tag] and store the result back under `tag` (projection shortcut)]
 NETWORKS = {
     # sample/notebooks/AlexNet_cifar10_resize224.ipynb:47-71
     "alexnet": (
@@ -57,6 +60,35 @@ NETWORKS["alexnet_paper"] = (
     NETWORKS["alexnet"][1],
     NETWORKS["alexnet"][2],
 )
+
+
+# A small residual network (He et al. 2015 basic blocks, one with a projection shortcut, one with a grouped conv as in
+# ResNeXt): what the Add exists for.  Not in the reference (it joins no two tensors).
+NETWORKS["resnet_tiny"] = (
+    {
+        "stem": ("conv", 3, 16, 3, 1, 1),
+        "b1c1": ("conv", 16, 16, 3, 1, 1), "b1c2": ("conv", 16, 16, 3, 1, 1),
+        "b2c1": ("conv", 16, 32, 3, 2, 1), "b2c2": ("conv", 32, 32, 3, 1, 1), "b2proj": ("conv", 16, 32, 1, 2, 0),
+        "b3c1": ("conv", 32, 32, 3, 1, 1, 4), "b3c2": ("conv", 32, 32, 1, 1, 0),
+        "fc": ("fc", 32 * 8 * 8, 10),
+    },
+    [("layer", "stem"), ("relu",),
+     ("save", "x1"), ("layer", "b1c1"), ("relu",), ("layer", "b1c2"), ("add", "add1", "x1"), ("relu",),
+     ("save", "x2"), ("layer", "b2c1"), ("relu",), ("layer", "b2c2"), ("branch", "x2", [("layer", "b2proj")]),
+     ("add", "add2", "x2"), ("relu",),
+     ("save", "x3"), ("layer", "b3c1"), ("relu",), ("layer", "b3c2"), ("add", "add3", "x3"), ("relu",),
+     ("pool", 2, 2), ("flatten", 2048), ("layer", "fc")],
+    (3, 32, 32),
+)
+
+
+def _walk(spec):
+    """every op of a spec in order, the ops inside ("branch", tag, [ops]) included"""
+    for op in spec:
+        if op[0] == "branch":
+            yield from _walk(op[2])
+        else:
+            yield op
 
 
 def conv_groups(L):
@@ -120,6 +152,9 @@ def build(name):
     class SpecNet(i8ie.Module):
         def __init__(self):
             super().__init__()
+            for op in _walk(spec):
+                if op[0] == "add":
+                    setattr(self, op[1], i8ie.Add())
             for attr, L in layers.items():
                 if L[0] == "conv":
                     if conv_groups(L) == 1:
@@ -129,17 +164,26 @@ def build(name):
                 else:
                     setattr(self, attr, i8ie.Linear(L[1], L[2]))
 
-        def forward(self, x):
-            for op in spec:
+        def run(self, ops, x, saved):
+            for op in ops:
                 if op[0] == "layer":
                     x = getattr(self, op[1])(x)
                 elif op[0] == "relu":
                     x = i8ie.relu(x)
                 elif op[0] == "pool":
                     x = i8ie.max_pool2d(x, op[1], op[2])
+                elif op[0] == "save":
+                    saved[op[1]] = x
+                elif op[0] == "branch":
+                    saved[op[1]] = self.run(op[2], saved[op[1]], saved)
+                elif op[0] == "add":
+                    x = getattr(self, op[1])(x, saved[op[2]])
                 else:
                     x = x.reshape(-1, op[1])
             return x
+
+        def forward(self, x):
+            return self.run(spec, x, {})
 
     SpecNet.__name__ = "SpecNet_" + name
     return SpecNet()
@@ -162,4 +206,10 @@ def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, p
 
 
 def layer_names(name):
-    return [op[1] for op in NETWORKS[name][1] if op[0] == "layer"]
+    """the weighted layers (Conv2d / Linear) in the order the spec names them, those of a branch included"""
+    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "layer"]
+
+
+def add_names(name):
+    """the Adds of a residual network, in spec order"""
+    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "add"]

@@ -1,0 +1,372 @@
+"""The quantized residual Add on the GPU (csrc/i8ie_add.hip).  Every comparison is byte-exact against
+the numpy restatement of the definition (tests/add_ref.py), never against the code under test: all 65 536 byte pairs through
+the flat entry for a range of quantisation parameters, ragged lengths and aliasing, the bordered / re-biased NHWC entry with
+guard bytes, the FP32 entry as bit patterns, the Python surface, launch counts of a basic block, calibration, and the
+residual network end to end."""
+import ctypes as C
+import itertools
+
+import numpy as np
+import pytest
+
+import abi
+import add_ref as ar
+import grouped_ref as gr
+import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = abi.Ctx()
+    ar.bind(abi.lib())
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def pairs(ctx):
+    """all 65 536 (a, b) byte pairs as flat tensors, resident on the device, and one output buffer"""
+    v = np.arange(256, dtype=np.uint8)
+    a, b = np.repeat(v, 256), np.tile(v, 256)
+    da, db, do = ctx.put(a), ctx.put(b), ctx.empty(a.shape, np.uint8)
+    yield a, b, da, db, do
+    for d in (da, db, do):
+        d.free()
+
+
+def _qparam_sets():
+    s = f32(0.05)
+    sets = [("equal", (s, 128, s, 128, s, 128)), ("equal_zp_mixed", (s, 3, s, 250, s, 17))]
+    s = f32(0.02)
+    sets.append(("thirds", (s, 120, s, 131, f32(3) * s, 64)))
+    so = f32(0.04)
+    sets.append(("half_double", (f32(0.5) * so, 100, f32(2) * so, 128, so, 60)))
+    so = f32(0.064)
+    sets.append(("ratio_1_64_and_64", (so / f32(64), 7, so * f32(64), 128, so, 128)))
+    sets.append(("ratio_64_and_1_64", (so * f32(64), 130, so / f32(64), 200, so, 9)))
+    for zps in itertools.product((0, 255, 128), repeat=3):
+        sets.append(("zp_%d_%d_%d" % zps, (f32(0.031), zps[0], f32(0.047), zps[1], f32(0.052), zps[2])))
+    rng = np.random.default_rng(20251017)
+    for i in range(3):  # calibrated-looking: a range / 255 and a zero point from it
+        sa, sb, so = (f32(v) for v in rng.uniform(0.004, 0.2, 3))
+        za, zb, zo = (int(v) for v in rng.integers(0, 256, 3))
+        sets.append(("calibrated_%d" % i, (sa, za, sb, zb, so, zo)))
+    sets.append(("denormal_s_a", (f32(1e-40), 128, f32(0.03), 128, f32(0.03), 100)))
+    return sets
+
+
+QP = _qparam_sets()
+
+
+def _add_flat(ctx, pa, pb, po, n, qp, relu):
+    s_a, zp_a, s_b, zp_b, s_out, zp_out = qp
+    abi.ck(abi.lib().i8ie_add_u8(ctx.h, pa, pb, po, n, float(s_a), int(zp_a), float(s_b), int(zp_b), float(s_out), int(zp_out),
+                                 1 if relu else 0))
+
+
+@pytest.mark.parametrize("relu", [False, True], ids=["plain", "relu"])
+@pytest.mark.parametrize("name,qp", QP, ids=[q[0] for q in QP])
+def test_exhaustive_byte_pairs(ctx, pairs, name, qp, relu):
+    a, b, da, db, do = pairs
+    _add_flat(ctx, da.ptr, db.ptr, do.ptr, a.size, qp, relu)
+    got = do.get()
+    s_a, zp_a, s_b, zp_b, s_out, zp_out = qp
+    want = ar.add_u8(a, zp_a, s_a, b, zp_b, s_b, s_out, zp_out, relu)
+    bad = np.flatnonzero(got != want)  # every one of the 65 536 elements is compared
+    assert got.shape == want.shape == (65536,) and bad.size == 0, (name, bad[:8], got[bad[:8]], want[bad[:8]])
+
+
+@pytest.mark.parametrize("n", [1, 15, 16, 17, 4097])
+def test_ragged_lengths_and_aliasing(ctx, n):
+    rng = np.random.default_rng(n)
+    a, b = rng.integers(0, 256, n, dtype=np.uint8), rng.integers(0, 256, n, dtype=np.uint8)
+    qp = (f32(0.043), 119, f32(0.027), 131, f32(0.061), 97)
+    pad = np.full(64, 0xA5, np.uint8)  # guard bytes behind the n elements
+    for relu in (False, True):
+        want = ar.add_u8(a, qp[1], qp[0], b, qp[3], qp[2], qp[4], qp[5], relu)
+        # separate output
+        da, db, do = ctx.put(np.concatenate([a, pad])), ctx.put(np.concatenate([b, pad])), ctx.put(np.concatenate([a ^ 0xFF, pad]))
+        _add_flat(ctx, da.ptr, db.ptr, do.ptr, n, qp, relu)
+        got = do.get()
+        assert np.array_equal(got[:n], want) and np.array_equal(got[n:], pad)
+        assert np.array_equal(da.get()[:n], a) and np.array_equal(db.get()[:n], b)
+        # out aliases a
+        _add_flat(ctx, da.ptr, db.ptr, da.ptr, n, qp, relu)
+        got = da.get()
+        assert np.array_equal(got[:n], want) and np.array_equal(got[n:], pad)
+        # a is b
+        _add_flat(ctx, db.ptr, db.ptr, do.ptr, n, qp, relu)
+        got = do.get()
+        assert np.array_equal(got[:n], ar.add_u8(b, qp[1], qp[0], b, qp[3], qp[2], qp[4], qp[5], relu)) and np.array_equal(got[n:], pad)
+        for d in (da, db, do):
+            d.free()
+
+
+GUARD = 64
+
+
+def _phys(x_nhwc, border, fill, s8):
+    """[n, h, w, c] u8 -> guarded flat buffer holding [n, h+2b, w+2b, c] with `fill` in the border (re-biased if s8)"""
+    n, h, w, c = x_nhwc.shape
+    p = np.full((n, h + 2 * border, w + 2 * border, c), fill, np.uint8)
+    p[:, border:border + h, border:border + w, :] = x_nhwc
+    if s8:
+        p = p ^ np.uint8(0x80)
+    return np.concatenate([np.full(GUARD, 0x5A, np.uint8), p.ravel(), np.full(GUARD, 0x5A, np.uint8)]), p.shape
+
+
+@pytest.mark.parametrize("borders", [(0, 0, 0), (1, 0, 1), (0, 2, 1), (2, 1, 0)], ids=lambda b: "b%d%d%d" % b)
+@pytest.mark.parametrize("c", [16, 20, 3])
+def test_bordered_nhwc(ctx, c, borders):
+    n, h, w = 2, 3, 5
+    rng = np.random.default_rng(c * 10 + sum(borders))
+    a = rng.integers(0, 256, (n, h, w, c), dtype=np.uint8)
+    b = rng.integers(0, 256, (n, h, w, c), dtype=np.uint8)
+    qp = (f32(0.043), 119, f32(0.027), 131, f32(0.061), 97)
+    s_a, zp_a, s_b, zp_b, s_out, zp_out = qp
+    ba, bb, bo = borders
+    lib = abi.lib()
+    for i, (a_s8, b_s8, o_s8) in enumerate(itertools.product((0, 1), repeat=3)):
+        relu = (i + c) % 2
+        want = ar.add_u8(a, zp_a, s_a, b, zp_b, s_b, s_out, zp_out, bool(relu))
+        fa, _ = _phys(a, ba, zp_a, a_s8)
+        fb, _ = _phys(b, bb, zp_b, b_s8)
+        fo, oshape = _phys(np.zeros_like(a) + np.uint8(0xEE), bo, zp_out, o_s8)  # the border as i8ie_fill_border_u8 leaves it
+        da, db, do = ctx.put(fa), ctx.put(fb), ctx.put(fo)
+        pa, pb, po = (C.c_void_p(d.ptr.value + GUARD) for d in (da, db, do))
+        abi.ck(lib.i8ie_add_u8_nhwc(ctx.h, pa, ba, a_s8, pb, bb, b_s8, po, bo, o_s8, n, c, h, w, float(s_a), zp_a, float(s_b), zp_b,
+                                    float(s_out), zp_out, relu))
+        ga, gb, go = da.get(), db.get(), do.get()
+        for d in (da, db, do):
+            d.free()
+        assert np.array_equal(ga, fa) and np.array_equal(gb, fb), "operands (and their guards) must be untouched"
+        assert (go[:GUARD] == 0x5A).all() and (go[-GUARD:] == 0x5A).all(), "guard bytes around the result"
+        out = go[GUARD:-GUARD].reshape(oshape)
+        if o_s8:
+            out = out ^ np.uint8(0x80)
+        ring = out.copy()
+        ring[:, bo:bo + h, bo:bo + w, :] = zp_out
+        assert (ring == zp_out).all(), "every border byte of the result holds zp_out"
+        assert np.array_equal(out[:, bo:bo + h, bo:bo + w, :], want), (a_s8, b_s8, o_s8, relu)
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1025])
+def test_fp32_bit_patterns(ctx, n):
+    """a + b as numpy float32 computes it, as bit patterns.  (inf + -inf is left out: IEEE 754 leaves the sign of a generated
+    NaN open, x86 SSE makes it negative and the GPU positive.  A NaN operand is propagated by both.)"""
+    rng = np.random.default_rng(n)
+    a = rng.standard_normal(n).astype(f32) * f32(100)
+    b = rng.standard_normal(n).astype(f32)
+    inf, nan = f32(np.inf), f32(np.nan)
+    special = [(-0.0, -0.0), (inf, 1.0), (nan, 1.0), (-inf, -inf), (-0.0, 0.0), (3e38, 3e38), (1.0, -inf), (1e-40, 2e-41),
+               (16777216.0, 1.0), (1.0, nan)]
+    for i, (x, y) in enumerate(special[:n]):  # (n = 1: -0.0; n = 3: + inf and the NaN; n = 1025: the tail element is ordinary)
+        a[i], b[i] = f32(x), f32(y)
+    with np.errstate(all="ignore"):
+        want = (a + b).astype(f32)
+    da, db, do = ctx.put(a), ctx.put(b), ctx.guarded((n,))
+    try:
+        abi.ck(abi.lib().i8ie_add_f32(ctx.h, da.ptr, db.ptr, do.ptr, n))
+        got, guards_ok = do.read()
+    finally:
+        for d in (da, db, do):
+            d.free()
+    assert guards_ok
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (got, want)
+
+
+# ---- the Python surface ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def i8ie():
+    import i8ie as mod
+
+    return mod
+
+
+def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
+    rng = np.random.default_rng(seed)
+    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
+    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
+    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
+    L.set_output_qparams(*qp)
+    L.convert()
+    return L
+
+
+def test_surface_mixed_layouts_and_errors(i8ie):
+    rng = np.random.default_rng(11)
+    x = rng.uniform(-2, 2, (2, 16, 8, 8)).astype(f32)
+    conv = _conv(i8ie, 16, 16, 3, 1, 5, (0.05, 120))
+    q = i8ie.quantize(i8ie.tensor(x), 0.025, 127)          # NCHW bytes
+    qv = q.numpy()
+    yv = conv(q).numpy()                                   # (observed on a tensor of its own: the operand below stays as it lies)
+    print("conv output layout:", conv(q).data.layout())
+    for relu in (False, True):
+        for swap in (False, True):
+            y = conv(q)                                    # a conv result in the engine's layout, still pending
+            r = i8ie.add(q, y, 0.07, 99) if swap else i8ie.add(y, q, scale=0.07, zero_point=99)
+            if relu:
+                r = i8ie.relu(r)
+            assert r.shape == (2, 16, 8, 8) and r.scale == pytest.approx(0.07) and r.zero_point == 99
+            ops = (qv, 127, f32(0.025), yv, 120, f32(0.05)) if swap else (yv, 120, f32(0.05), qv, 127, f32(0.025))
+            assert np.array_equal(r.numpy(), ar.add_u8(*ops, f32(0.07), 99, relu)), (relu, swap)
+    # 2-D rows (Linear outputs): the flat form
+    a2, b2 = q.reshape(2, -1), i8ie.quantize(i8ie.tensor(x[::-1].copy()), 0.03, 100).reshape(2, -1)
+    r = i8ie.add(a2, b2, 0.04, 128)
+    assert np.array_equal(r.numpy(), ar.add_u8(a2.numpy(), 127, f32(0.025), b2.numpy(), 100, f32(0.03), f32(0.04), 128))
+    # a is b
+    r = i8ie.add(q, q, 0.05, 127)
+    assert np.array_equal(r.numpy(), ar.add_u8(qv, 127, f32(0.025), qv, 127, f32(0.025), f32(0.05), 127))
+    # FP32
+    t = i8ie.tensor(x)
+    s = i8ie.add(t, t)
+    assert np.array_equal(s.numpy().view(np.uint32), (x + x).view(np.uint32))
+    with pytest.raises(RuntimeError):
+        i8ie.add(q, q.reshape(2, -1), 0.05, 127)           # shapes must be equal, there is no broadcasting
+    with pytest.raises(RuntimeError):
+        i8ie.add(t, i8ie.tensor(x[:1]))
+    with pytest.raises(TypeError):
+        i8ie.add(q, q)                                     # u8 needs the result's qparams
+    with pytest.raises(TypeError):
+        i8ie.add(t, t, 0.05, 127)                          # ... and FP32 takes none
+    with pytest.raises(RuntimeError):
+        i8ie.add(q, q, 0.05, 256)
+    with pytest.raises(RuntimeError):
+        i8ie.add(q, q, 0.0, 1)
+    with pytest.raises(RuntimeError):
+        i8ie.Add()(q, q)                                   # not converted
+
+
+def _block(i8ie):
+    conv0 = _conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110))
+    conv_a = _conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
+    conv_b = _conv(i8ie, 16, 16, 3, 1, 3, (0.06, 130))
+    add = i8ie.Add()
+    add.set_output_qparams(0.07, 100)
+    add.convert()
+    return conv0, conv_a, conv_b, add
+
+
+@pytest.mark.parametrize("skip_first", [False, True], ids=["add_fx_x", "add_x_fx"])
+def test_basic_block_launch_counts(i8ie, skip_first):
+    """relu(add(conv_b(relu(conv_a(x))), x)) with x = relu(conv0(..)): three conv launches and ONE add launch -- x, made
+    bordered for conv_a, is read by the add as it lies; the relu folds into the add; nothing converts, re-biases or fills."""
+    import _CXX_i8ie as cx
+
+    conv0, conv_a, conv_b, add = _block(i8ie)
+    xin = np.random.default_rng(4).uniform(-2, 2, (2, 3, 8, 8)).astype(f32)
+    # the block's input as it is inside a network: an activation in the engine's layout (a 3-channel first conv takes the
+    # any-geometry path and leaves NCHW; the 16-channel conv behind it leaves NHWC).  It stays recorded: the warm-up forward
+    # launches it once, with the border conv0 asks its producer for, and the counted forward finds that result.
+    q = i8ie.relu(_conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(_conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
+        i8ie.quantize(i8ie.tensor(xin), 0.025, 127)))))
+    qv = q.shape
+
+    def forward():
+        x = i8ie.relu(conv0(q))
+        fx = conv_b(i8ie.relu(conv_a(x)))
+        return i8ie.relu(add(x, fx) if skip_first else add(fx, x))
+
+    first = forward().numpy()  # (packs weights, fills the bordered buffers' borders once: they are cached per geometry)
+    cx.synchronize()
+    cx.profile_start()
+    try:
+        y = forward()
+        y.data.layout()  # launches what is pending; the bytes are observed (and put in NCHW order) outside the counted region
+    finally:
+        prof = cx.profile_stop()
+    got = y.numpy()
+    print(prof)
+    assert q.data.layout() == 1  # NHWC
+    # the expected bytes, from the observed conv outputs of the same layers and the restatement of the add
+    xv = i8ie.relu(conv0(q)).numpy()
+    fv = conv_b(i8ie.relu(conv_a(i8ie.relu(conv0(q))))).numpy()
+    ops = (xv, 110, f32(0.04), fv, 130, f32(0.06)) if skip_first else (fv, 130, f32(0.06), xv, 110, f32(0.04))
+    want = ar.add_u8(*ops, f32(0.07), 100, True)
+    assert np.array_equal(got, want) and np.array_equal(first, want) and qv == (2, 16, 8, 8)
+    launches = {k.split("|")[0]: v[0] for k, v in prof.items()}
+    adds = sum(v for k, v in launches.items() if k.startswith("add_u8"))
+    assert adds == 1, launches
+    for k in launches:
+        assert not k.startswith(("relu_u8", "rebias", "fill_border", "reborder", "layout_")), launches
+    others = sum(v for k, v in launches.items() if not k.startswith("add_u8"))
+    assert others == 3, launches  # conv0, conv_a, conv_b: one launch each (same shape, so one kernel name holds all three)
+
+
+@pytest.mark.parametrize("mode", ["host", "device"])
+def test_add_is_calibrated_like_a_layer(i8ie, mode):
+    import _CXX_i8ie as cx
+
+    rng = np.random.default_rng(8)
+    a = rng.normal(0.2, 1.5, (5, 8, 10, 10)).astype(f32)
+    b = rng.normal(-0.1, 0.7, (5, 8, 10, 10)).astype(f32)
+    total = (a + b).astype(f32)
+    cx.set_calibration_mode(mode)
+    cx.set_calibration_seed(7)
+    try:
+        add = i8ie.Add()
+        add.prepare()
+        got = add(i8ie.tensor(a), i8ie.tensor(b)).numpy()
+        add.convert()
+        if mode == "host":
+            want = tuple(cx.calibrator_range([total.ravel()], 1.0))
+        else:
+            want = tuple(cx.calibrator_device_samples([total.ravel()], 7)[2:])
+    finally:
+        cx.set_calibration_mode("auto")
+        cx.set_calibration_seed(-1)
+    assert np.array_equal(got.view(np.uint32), total.view(np.uint32))
+    assert add.layer.is_quantized() and add.output_qparams() == want and want[0] != 1.0
+
+
+# ---- the residual network ----------------------------------------------------------------------------------------------
+_NETS = {}
+
+
+def _resnet(per_channel):
+    from int8inferenceengine_amd import workloads as wl
+
+    if per_channel not in _NETS:
+        name = "resnet_tiny"
+        sd = wl.synthetic_state_dict(name)
+        net = wl.calibrated(name, sd, per_channel=per_channel)
+        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
+        aqp = {a: getattr(net, a).output_qparams() for a in wl.add_names(name)}
+        _NETS[per_channel] = (net, gr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, aqp)
+    return _NETS[per_channel]
+
+
+@pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
+@pytest.mark.parametrize("batch", [2, 66])
+def test_resnet_tiny_bit_exact(i8ie, batch, per_channel, tmp_path):
+    import _CXX_i8ie as cx
+    from int8inferenceengine_amd import workloads as wl
+    from int8inferenceengine_amd.graph import GraphedForward
+
+    name = "resnet_tiny"
+    net, qlayers, qp, aqp = _resnet(per_channel)
+    assert all(s > 0 and s != 1.0 for s, _ in aqp.values()), aqp  # the Adds were calibrated
+    x = wl.synthetic_input(name, batch, seed=5)
+    want = ar.forward(wl.NETWORKS[name], x, qlayers, qp, aqp, per_channel)
+    got = net(i8ie.tensor(x)).numpy()
+    assert got.shape == want.shape == (batch, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    cx.force_fallback(True)
+    try:
+        fb = net(i8ie.tensor(x)).numpy()
+    finally:
+        cx.force_fallback(False)
+    assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
+    if batch != 2:
+        return
+    g = GraphedForward(net, i8ie.tensor(x).prefetch())
+    for _ in range(2):
+        assert np.array_equal(g().numpy().view(np.uint32), want.view(np.uint32))
+    path = str(tmp_path / "resnet_tiny.npz")
+    net.save_quantized(path)
+    fresh = wl.build(name)
+    fresh.load_quantized_file(path)
+    assert {a: getattr(fresh, a).output_qparams() for a in wl.add_names(name)} == aqp
+    assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), want.view(np.uint32))
