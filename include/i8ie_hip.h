@@ -445,6 +445,31 @@ int i8ie_add_u8_nhwc(i8ie_ctx* ctx, const uint8_t* a_dev, int a_border, int a_s8
  * 16-byte aligned buffers; out may alias a or b. */
 int i8ie_add_f32(i8ie_ctx* ctx, const float* a_dev, const float* b_dev, float* out_dev, int64_t n);
 
+/* ---- quantized average pooling (no counterpart in the reference) -----------------------------------------------
+ * Everything but the reduction follows max_pool2d<u8_t> (src/functional.cc:36-64): NCHW logical shape, window
+ * kernel_h x kernel_w, one stride, floor output size (h - kernel_h) / stride + 1 by (w - kernel_w) / stride + 1, no
+ * padding; the result carries the input's (scale, zero_point).  With n = kernel_h * kernel_w and S the exact integer
+ * sum of the window's bytes:
+ *     q = (S + n / 2) / n        integer floor division: round to nearest, ties up
+ * (the value never leaves the integers, so no fp32 step of the reference applies; truncation would bias every pooled
+ * tensor by -1/2 LSB).  The global pool is kernel_h = h, kernel_w = w, stride = 1.  n <= 65536.  Null pointers,
+ * non-positive sizes, a window larger than the input, n > 65536 and a negative border are I8IE_ERR_ARG, raised before
+ * any device call.  Stateless and capturable in a graph (csrc/i8ie_avgpool.hip).
+ * i8ie_avgpool2d_u8: NCHW in and out, any shape. */
+int i8ie_avgpool2d_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int n, int c, int h, int w, int kernel_h,
+                      int kernel_w, int stride);
+/* The same on NHWC buffers [n, h+2b, w+2b, c] / [n, oh+2b', ow+2b', c], each with its own border and each plain
+ * (x_s8 = 0) or re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80).  relu != 0: q = max(q, zero_point)
+ * (relu<u8>, src/functional.cc:15-26, on the result).  Only the interior of `out` is written: its border bytes are
+ * the caller's (i8ie_fill_border_u8).  Any c: 16 / 4 / 1 channels per lane by c % 16, c % 4.  h, w: logical input dims. */
+int i8ie_avgpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev,
+                           int out_border, int out_s8, int n, int c, int h, int w, int kernel_h, int kernel_w,
+                           int stride, int relu, uint8_t zero_point);
+/* FP32 (before convert(), and while calibrating), NCHW: sum / n, the sum taken in fp32 in window order (rows outer,
+ * columns inner), then one division.  NaN and inf propagate as IEEE gives them. */
+int i8ie_avgpool2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int kernel_h,
+                       int kernel_w, int stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -819,6 +819,67 @@ Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
       }, {a.pend, b.pend});
   return out;
 }
+// ---- avg_pool2d / global_avg_pool2d (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_avgpool2d_u8) ---
+// kh x kw window; the global pool is the whole image at stride 1
+template <typename T>
+std::vector<ssize_t> avg_pool_shape(const Tensor<T>& in, ssize_t kh, ssize_t kw, ssize_t s, bool global) {
+  const std::string what = global ? "i8ie: global_avg_pool2d" : "i8ie: avg_pool2d";
+  if (in.shape.size() != 4) throw std::runtime_error(what + " expects an NCHW tensor");
+  if (global) {
+    kh = in.shape[2];
+    kw = in.shape[3];
+  }
+  if (kh <= 0 || kw <= 0 || s <= 0) throw std::runtime_error(what + ": kernel_size and stride must be positive");
+  if (kh > in.shape[2] || kw > in.shape[3]) throw std::runtime_error(what + ": window larger than input");
+  if (kh * kw > 65536) throw std::runtime_error(what + ": window of more than 65536 elements");
+  return {in.shape[0], in.shape[1], (in.shape[2] - kh) / s + 1, (in.shape[3] - kw) / s + 1};
+}
+Tensor<float> avg_pool_f32(Tensor<float>& in, ssize_t k, ssize_t s, bool global) {
+  Tensor<float> out(avg_pool_shape(in, k, k, s, global));
+  const ssize_t kh = global ? in.shape[2] : k, kw = global ? in.shape[3] : k;
+  check(i8ie_avgpool2d_f32(ctx(), in.dptr(), out.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3],
+                           (int)kh, (int)kw, (int)s));
+  return out;
+}
+std::shared_ptr<Storage> add_operand(Tensor<u8_t>& t);
+Tensor<u8_t> avg_pool_u8(Tensor<u8_t>& in, ssize_t k, ssize_t s, bool global) {
+  Tensor<u8_t> out;
+  out.shape = avg_pool_shape(in, k, k, s, global);
+  out.size = 1;
+  for (ssize_t d : out.shape) out.size *= d;
+  out.scale = in.scale;  // as max_pool2d: the input's quantisation parameters, unchanged
+  out.zero_point = in.zero_point;
+  Tensor<u8_t> src = in;
+  const std::vector<ssize_t> ishp = in.shape, oshp = out.shape;
+  const u8_t zp = in.zero_point;
+  const int kh = (int)(global ? in.shape[2] : k), kw = (int)(global ? in.shape[3] : k), ss = (int)s;
+  // deferred like max_pool2d's and add's results: relu(avg_pool2d(..)) is one launch, and a consuming conv gets its
+  // zero-point border and, where it reads them, re-biased bytes straight from the pool kernel
+  out.pend = make_pend(
+      [src, ishp, oshp, zp, kh, kw, ss](bool relu, int border, bool s8) mutable {
+        // the input as it lies (any border, plain or re-biased): a pending producer launches plain, one that has launched
+        // for another consumer is not launched again
+        std::shared_ptr<Storage> si = add_operand(src);
+        const size_t logical = (size_t)oshp[0] * oshp[1] * oshp[2] * oshp[3];
+        std::shared_ptr<Storage> st;
+        if (si->layout == I8IE_LAYOUT_NHWC) {
+          // a plain border-free [n, c, 1, 1] result is the same bytes in both orders: it is labelled NCHW, so that its
+          // reshape to [n, c] reaches a Linear layer (or the host) without a layout conversion
+          const bool both_orders = oshp[2] == 1 && oshp[3] == 1 && border == 0 && !s8;
+          st = both_orders ? device_storage(logical) : nhwc_storage(oshp, border, zp, s8);
+          check(i8ie_avgpool2d_u8_nhwc(ctx(), (const uint8_t*)si->device_ptr(), si->border, si->s8 ? 1 : 0, (uint8_t*)st->dev,
+                                       st->border, st->s8 ? 1 : 0, (int)ishp[0], (int)ishp[1], (int)ishp[2], (int)ishp[3], kh, kw, ss,
+                                       relu ? 1 : 0, zp));
+        } else {  // an NCHW operand (a user-made tensor)
+          st = device_storage(logical);
+          check(i8ie_avgpool2d_u8(ctx(), (const uint8_t*)si->device_ptr(), (uint8_t*)st->dev, (int)ishp[0], (int)ishp[1], (int)ishp[2],
+                                  (int)ishp[3], kh, kw, ss));
+          if (relu) check(i8ie_relu_u8(ctx(), (const uint8_t*)st->dev, (uint8_t*)st->dev, (int64_t)st->bytes, zp));
+        }
+        return st;
+      }, {in.pend});
+  return out;
+}
 // the s8 instantiations of the generic templates (src/functional.cc:5-13, 36-64, registered at :78-82)
 Tensor<s8_t> relu_s8(Tensor<s8_t>& in) {
   if (!in.st) return Tensor<s8_t>();  // default-constructed: nothing to do
@@ -1506,6 +1567,13 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
   // additive (the reference joins no two tensors): a + b in FP32; the quantized Add of include/i8ie_hip.h on u8 tensors
   m.def("add", &add_f32, py::arg("a"), py::arg("b"));
   m.def("add", &add_u8, py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("zero_point"));
+  // additive (the reference has no average pool): round-to-nearest integer mean on u8 tensors, fp32 sum / n on FP32 ones
+  m.def("avg_pool2d", [](Tensor<float>& x, ssize_t k, ssize_t s) { return avg_pool_f32(x, k, s, false); }, py::arg("x"),
+        py::arg("kernel_size"), py::arg("stride"));
+  m.def("avg_pool2d", [](Tensor<u8_t>& x, ssize_t k, ssize_t s) { return avg_pool_u8(x, k, s, false); }, py::arg("x"),
+        py::arg("kernel_size"), py::arg("stride"));
+  m.def("global_avg_pool2d", [](Tensor<float>& x) { return avg_pool_f32(x, 0, 1, true); }, py::arg("x"));
+  m.def("global_avg_pool2d", [](Tensor<u8_t>& x) { return avg_pool_u8(x, 0, 1, true); }, py::arg("x"));
 
   {
     py::class_<Linear> c(m, "Linear");  // src/fully_connected.cc:54-72

@@ -15,7 +15,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
-    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add",
+    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add", "avg_pool2d", "global_avg_pool2d",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -59,6 +59,19 @@ def add(a, b, scale=None, zero_point=None):
     if scale is not None or zero_point is not None:
         raise TypeError("add of FP32 tensors takes no scale / zero_point")
     return Tensor(_C.add(a.data, b.data))
+
+
+def avg_pool2d(x, kernel_size, stride=None):
+    """Average pooling over kernel_size x kernel_size windows (NCHW, floor output size, no padding, as max_pool2d);
+    `stride` defaults to `kernel_size`.  uint8 tensors: the integer mean rounded to nearest, ties up,
+    (sum + n // 2) // n (include/i8ie_hip.h, i8ie_avgpool2d_u8); the result carries the input's scale and zero point.
+    FP32 tensors: the fp32 sum of the window divided by n."""
+    return Tensor(_C.avg_pool2d(x.data, int(kernel_size), int(kernel_size if stride is None else stride)))
+
+
+def global_avg_pool2d(x):
+    """avg_pool2d over the whole image: [n, c, h, w] -> [n, c, 1, 1].  `.reshape(-1, c)` of the result feeds a Linear layer."""
+    return Tensor(_C.global_avg_pool2d(x.data))
 
 
 def synchronize():

@@ -16,7 +16,9 @@ import numpy as np
 #   spec  : [("layer", attr) | ("relu",) | ("pool", k, s) | ("flatten", features)
 #            | ("save", tag)              remember the current tensor under `tag`
 #            | ("add", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Add (not in `layers`)
-#            | ("branch", tag, [ops...])  run ops on saved[tag] and store the result back under `tag` (projection shortcut)]
+#            | ("branch", tag, [ops...])  run ops on saved[tag] and store the result back under `tag` (projection shortcut)
+#            | ("avgpool", k, s)          i8ie.avg_pool2d(x, k, s)
+#            | ("gap",)                   i8ie.global_avg_pool2d(x)]
 NETWORKS = {
     # sample/notebooks/AlexNet_cifar10_resize224.ipynb:47-71
     "alexnet": (
@@ -82,6 +84,40 @@ NETWORKS["resnet_tiny"] = (
 )
 
 
+# resnet_tiny with the head every residual network has: average pooling down to [n, c, 1, 1] instead of a wide flatten
+NETWORKS["resnet_tiny_gap"] = (
+    dict({k: v for k, v in NETWORKS["resnet_tiny"][0].items() if k != "fc"}, fc=("fc", 32, 10)),
+    NETWORKS["resnet_tiny"][1][:-3] + [("avgpool", 2, 2), ("gap",), ("flatten", 32), ("layer", "fc")],
+    (3, 32, 32),
+)
+
+
+def _resnet18_cifar():
+    """ResNet-18 for CIFAR-10 (He et al. 2015, section 4.2 style stem: 3x3, no stem max-pool): four stages of two basic
+    blocks at 64 / 128 / 256 / 512 channels, stride 2 and a 1x1 projection shortcut at the start of stages 2-4."""
+    layers = {"stem": ("conv", 3, 64, 3, 1, 1)}
+    spec = [("layer", "stem"), ("relu",)]
+    in_c = 64
+    for stage, out_c in enumerate((64, 128, 256, 512), start=1):
+        for block in (1, 2):
+            p = "s%db%d" % (stage, block)
+            stride = 2 if (stage > 1 and block == 1) else 1
+            layers[p + "c1"] = ("conv", in_c, out_c, 3, stride, 1)
+            layers[p + "c2"] = ("conv", out_c, out_c, 3, 1, 1)
+            spec += [("save", p), ("layer", p + "c1"), ("relu",), ("layer", p + "c2")]
+            if stride != 1 or in_c != out_c:
+                layers[p + "proj"] = ("conv", in_c, out_c, 1, stride, 0)
+                spec.append(("branch", p, [("layer", p + "proj")]))
+            spec += [("add", p + "add", p), ("relu",)]
+            in_c = out_c
+    layers["fc"] = ("fc", 512, 10)
+    spec += [("gap",), ("flatten", 512), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+NETWORKS["resnet18_cifar"] = _resnet18_cifar()
+
+
 def _walk(spec):
     """every op of a spec in order, the ops inside ("branch", tag, [ops]) included"""
     for op in spec:
@@ -113,8 +149,10 @@ def macs_per_image(name):
                 c = oc
             else:
                 total += L[1] * L[2]
-        elif op[0] == "pool":
+        elif op[0] in ("pool", "avgpool"):
             h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
+        elif op[0] == "gap":
+            h, w = 1, 1
     return total
 
 
@@ -172,6 +210,10 @@ def build(name):
                     x = i8ie.relu(x)
                 elif op[0] == "pool":
                     x = i8ie.max_pool2d(x, op[1], op[2])
+                elif op[0] == "avgpool":
+                    x = i8ie.avg_pool2d(x, op[1], op[2])
+                elif op[0] == "gap":
+                    x = i8ie.global_avg_pool2d(x)
                 elif op[0] == "save":
                     saved[op[1]] = x
                 elif op[0] == "branch":
