@@ -94,6 +94,36 @@ class GuardedOut:
         self.buf.free()
 
 
+class GuardedU8:
+    """The byte counterpart of GuardedOut: a region of `shape` elements of `dtype` with GUARD bytes before and after it
+    in one device allocation, the guards pre-filled with GUARD_BYTE and the region with `fill`.  GUARD is a multiple of
+    256, so `ptr` is aligned like an allocation of its own.  get() returns the region, guards_ok() whether no byte of
+    either guard changed."""
+    GUARD = 4096
+    GUARD_BYTE = 0x5A
+
+    def __init__(self, ctx, shape, dtype=np.uint8, fill=0xC3):
+        self.shape, self.dtype = tuple(int(d) for d in shape), np.dtype(dtype)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+        host = np.full(self.nbytes + 2 * self.GUARD, self.GUARD_BYTE, np.uint8)
+        host[self.GUARD:self.GUARD + self.nbytes] = fill
+        self.buf = ctx.put(host)
+        self.ptr = C.c_void_p(self.buf.ptr.value + self.GUARD)
+        self._raw = None
+
+    def get(self):
+        self._raw = self.buf.get()
+        return self._raw[self.GUARD:self.GUARD + self.nbytes].view(self.dtype).reshape(self.shape).copy()
+
+    def guards_ok(self):
+        raw = self._raw if self._raw is not None else self.buf.get()
+        g = self.GUARD
+        return bool((raw[:g] == self.GUARD_BYTE).all() and (raw[g + self.nbytes:] == self.GUARD_BYTE).all())
+
+    def free(self):
+        self.buf.free()
+
+
 class Ctx:
     def __init__(self, device=0):
         self.h = C.c_void_p()
@@ -406,10 +436,13 @@ class Ctx:
 
     def layer_forward_pool(self, q_in_nchw, qw, qb, s_in, zp_in, s_w, s_out, zp_out, stride=1, pad=0, in_nhwc=False,
                            out_nhwc=False, relu=False, in_border=0, out_border=0, pool=None, variant=0, in_s8=False,
-                           out_s8=False, names=None):
+                           out_s8=False, names=None, guard=None):
         """i8ie_layer_forward_pool (pool=(k, s)) or i8ie_layer_forward_fused (pool=None) of a conv layer.
         in_s8 / out_s8: the NHWC input / output in the re-biased form (I8IE_LAYOUT_NHWC_S8: every byte ^ 0x80, borders
-        included).  names: list that receives the kernels that ran.  Returns (out NCHW, acc [n, oh*ow, kc])."""
+        included).  names: list that receives the kernels that ran.  guard: a dict; when given, the output and the
+        accumulators live in GuardedU8 regions and it receives "phys" (the whole physical output as the call left it,
+        the re-bias undone) and "ok" (no guard byte of either region changed).
+        Returns (out NCHW, acc [n, oh*ow, kc])."""
         q_in = np.ascontiguousarray(q_in_nchw, np.uint8)
         qw = np.ascontiguousarray(qw, np.int8)
         qb = np.ascontiguousarray(qb, np.int8)
@@ -427,8 +460,12 @@ class Ctx:
             phys_in = phys_in ^ np.uint8(0x80)
         di = self.put(phys_in)
         oshape = (m, ph + 2 * out_border, pw + 2 * out_border, kc) if out_nhwc else (m, kc, ph, pw)
-        out = self.empty(oshape, np.uint8)
-        acc = self.empty((m, oh * ow, kc), np.int32)
+        if guard is None:
+            out = self.empty(oshape, np.uint8)
+            acc = self.empty((m, oh * ow, kc), np.int32)
+        else:
+            out = GuardedU8(self, oshape)
+            acc = GuardedU8(self, (m, oh * ow, kc), np.int32)
         ozp = zp_out ^ (0x80 if out_s8 else 0)
         if out_nhwc and out_border:
             ck(lib().i8ie_fill_border_u8(self.h, out.ptr, m, kc, ph, pw, out_border, C.c_uint8(ozp)))
@@ -470,6 +507,8 @@ class Ctx:
                 o = phys[:, b:-b, b:-b, :]
             o = np.ascontiguousarray(o.transpose(0, 3, 1, 2))
         r = (o, acc.get())
+        if guard is not None:
+            guard["phys"], guard["ok"] = phys, out.guards_ok() and acc.guards_ok()
         lib().i8ie_layer_destroy(L)
         for bb in (di, out, acc):
             bb.free()
