@@ -78,3 +78,41 @@ int i8ie_flin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c);
 // operands through a four-stage LDS-DMA ring fed by dedicated loader waves.  Takes the amode-0 fields of the call.
 bool i8ie_mlin_wants(int m, int n, int Kpad, bool force);
 int i8ie_mlin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c);
+
+// ---- launch helpers of i8ie_gemm.hip (the first three) and i8ie_igemm.hip, called by i8ie_layer.hip --------------------
+int i8ie_launch_pad_rows(i8ie_ctx* ctx, const void* src, int rows, int k, void* dst, int rows_pad, int k_pad, int fill);
+int i8ie_launch_offsets(i8ie_ctx* ctx, bool conv, const int8_t* qw, const int8_t* qb, int n, int K, float s_in, int zp_in,
+                        int32_t* oc, int32_t* wsum);
+int i8ie_launch_im2col(i8ie_ctx* ctx, const uint8_t* in, uint8_t* col, int n, int c, int h, int w, int kh, int kw, int oh,
+                       int ow, int stride, int pad, int K, int Kpad, int zp);
+int i8ie_launch_finish_offsets(i8ie_ctx* ctx, const int32_t* oc, const int32_t* wsum, const int8_t* qb, float s_in, int n,
+                               int32_t* ocp, float* biasf);
+int i8ie_launch_nchw_to_nhwc(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int c, int h, int w, int b);
+int i8ie_launch_nhwc_to_nchw(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int c, int h, int w, int b);
+int i8ie_launch_reborder(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int c, int h, int w, int ib, int ob, int zp);
+int i8ie_launch_fill_border(i8ie_ctx* ctx, uint8_t* out, int n, int c, int h, int w, int b, int zp);
+int i8ie_launch_permute_k(i8ie_ctx* ctx, const int8_t* B, int8_t* Bp, int rows, int Kpad, int K, int c, int hw);
+int i8ie_launch_repack_smallc(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int c, int h, int w, int Hp, int Wg,
+                              int ph, int pw, int zp, int rebias);
+int i8ie_launch_maxpool_nhwc(i8ie_ctx* ctx, const uint8_t* in, int ib, uint8_t* out, int ob, int n, int c, int h, int w, int k,
+                             int s, int relu_zp);
+
+// i8ie_igemm.hip: the classifier head, Linear with at most i8ie_smalln_max_features() outputs in one launch (one wave per
+// row, epilogue and, with out_f32, the dequantize fused)
+struct I8ieSmallNCall {
+  const uint8_t* A;
+  size_t lda;
+  int M, K;
+  const int8_t* B;
+  int Kpad, N;
+  const int32_t* ocp;
+  const float* biasf;
+  float s_in, s_w, s_out;
+  int zp_out, relu;
+  uint8_t* out;
+  int32_t* acc;
+  float* out_f32;
+  const float* sbv;  // per-channel layers: [N] weight scales; nullptr otherwise
+};
+int i8ie_smalln_max_features();
+int i8ie_launch_linear_smalln(i8ie_ctx* ctx, const I8ieSmallNCall& c);

@@ -17,6 +17,7 @@
 // are issued before the current tile's MFMAs) into a 16-B-chunk XOR-swizzled
 // LDS image that makes the ds_read_b128 fragment reads conflict-free.
 #include "i8ie_internal.h"
+#include "i8ie_calls.h"
 #include "i8ie_requant.h"
 
 namespace {

@@ -1168,21 +1168,6 @@ int i8ie_launch_fill_border(i8ie_ctx* ctx, uint8_t* out, int n, int c, int h, in
   return I8IE_OK;
 }
 
-struct I8ieSmallNCall {
-  const uint8_t* A;
-  size_t lda;
-  int M, K;
-  const int8_t* B;
-  int Kpad, N;
-  const int32_t* ocp;
-  const float* biasf;
-  float s_in, s_w, s_out;
-  int zp_out, relu;
-  uint8_t* out;
-  int32_t* acc;
-  float* out_f32;
-  const float* sbv;  // per-channel layers: [N] weight scales; nullptr otherwise
-};
 int i8ie_smalln_max_features() { return kSmallN; }
 int i8ie_launch_linear_smalln(i8ie_ctx* ctx, const I8ieSmallNCall& c) {
   I8IE_REQUIRE(c.M > 0 && c.N > 0 && c.N <= kSmallN && c.K > 0 && c.K % 16 == 0 && c.lda % 16 == 0, "small-N linear shape");

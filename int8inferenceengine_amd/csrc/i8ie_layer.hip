@@ -5,7 +5,7 @@
 //   reference: src/fully_connected.cc:22-52, src/conv2d.cc:100-142,
 //              src/layer.cc:6-26,36-54
 //
-// Conv2d has three execution paths, all producing the reference's bytes:
+// Conv2d has four execution paths, all producing the reference's bytes:
 //   A  channels % 16 == 0: implicit GEMM over NHWC activations (i8ie_igemm.hip)
 //   B  channels <= 4 and stride % 4 == 0 (AlexNet conv1): the NCHW input is repacked
 //      once into a physically padded, 4-pixel-grouped NHWC image; then path A's kernel
@@ -21,70 +21,10 @@
 
 #include "i8ie_internal.h"
 #include "i8ie_calls.h"
+#include "i8ie_first.h"
 #include "i8ie_stem.h"
 #include "i8ie_requant.h"
 #include "i8ie_gconv.h"
-
-int i8ie_launch_pad_rows(i8ie_ctx* ctx, const void* src, int rows, int k, void* dst, int rows_pad, int k_pad,
-                         int fill);
-int i8ie_launch_offsets(i8ie_ctx* ctx, bool conv, const int8_t* qw, const int8_t* qb, int n, int K, float s_in,
-                        int zp_in, int32_t* oc, int32_t* wsum);
-int i8ie_launch_im2col(i8ie_ctx* ctx, const uint8_t* in, uint8_t* col, int n, int c, int h, int w, int kh, int kw,
-                       int oh, int ow, int stride, int pad, int K, int Kpad, int zp);
-int i8ie_launch_finish_offsets(i8ie_ctx* ctx, const int32_t* oc, const int32_t* wsum, const int8_t* qb, float s_in,
-                               int n, int32_t* ocp, float* biasf);
-int i8ie_launch_nchw_to_nhwc(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int c, int h, int w, int b);
-int i8ie_launch_nhwc_to_nchw(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int c, int h, int w, int b);
-int i8ie_launch_reborder(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int c, int h, int w, int ib, int ob,
-                         int zp);
-int i8ie_launch_permute_k(i8ie_ctx* ctx, const int8_t* B, int8_t* Bp, int rows, int Kpad, int K, int c, int hw);
-struct I8ieSmallNCall {
-  const uint8_t* A;
-  size_t lda;
-  int M, K;
-  const int8_t* B;
-  int Kpad, N;
-  const int32_t* ocp;
-  const float* biasf;
-  float s_in, s_w, s_out;
-  int zp_out, relu;
-  uint8_t* out;
-  int32_t* acc;
-  float* out_f32;
-  const float* sbv;
-};
-int i8ie_smalln_max_features();
-int i8ie_launch_linear_smalln(i8ie_ctx* ctx, const I8ieSmallNCall& c);
-int i8ie_launch_repack_smallc(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int n, int c, int h, int w, int Hp,
-                              int Wg, int ph, int pw, int zp, int rebias);
-int i8ie_launch_fill_border(i8ie_ctx* ctx, uint8_t* out, int n, int c, int h, int w, int b, int zp);
-int i8ie_launch_maxpool_nhwc(i8ie_ctx* ctx, const uint8_t* in, int ib, uint8_t* out, int ob, int n, int c, int h,
-                             int w, int k, int s, int relu_zp);
-
-
-
-struct I8ieFirstCall {
-  const float* x;
-  const uint8_t* grouped;
-  uint8_t* scratch;
-  int n, c, h, w;
-  float q_scale;
-  int q_zp;
-  int KH, KW, KWG, stride, pad, OH, OW;
-  const int8_t* B;
-  int Kpad, K2, N;
-  const int32_t* ocp;
-  float s_in, s_w, s_out;
-  int zp_out, relu;
-  uint8_t* out;
-  int ob;
-  int32_t* acc;
-  const float* msv;
-  const float* sbv;
-};
-int i8ie_first_supported(int c, int stride, int n_out, int K2, int KH, int KWG, int OW);
-int i8ie_first_launch(i8ie_ctx* ctx, const I8ieFirstCall& c);
-size_t i8ie_first_scratch_bytes(int n, int KH, int KWG, int stride, int OH, int OW);
 
 namespace {
 
