@@ -470,6 +470,37 @@ int i8ie_avgpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, 
 int i8ie_avgpool2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int kernel_h,
                        int kernel_w, int stride);
 
+/* ---- quantized channel concatenation (no counterpart in the reference: it has no op that joins two tensors) ----
+ * cat(x_0 .. x_{k-1}) along axis 1, 1 <= k <= I8IE_CONCAT_MAX_INPUTS; the same buffer may appear more than once.  The
+ * result carries its own (s_out, zp_out).  A byte a of input i, with that tensor's (s_i, zp_i), becomes
+ *     if (bits(s_i) == bits(s_out) && zp_i == zp_out)  q = a                       the copy rule
+ *     else  f = (float)((int)a - (int)zp_i) * s_i                                  dequantize, src/quantize_utils.cc:38-42
+ *           t = f / s_out + (float)zp_out                                          IEEE fp32, one rounding per operation
+ *           q = t >= 255 ? 255 : (t < 0 ? 0 : (u8)t)                               down_scale's clamp + truncation, :27-36
+ *     q = relu ? max(q, zp_out) : q                                                relu<u8>, src/functional.cc:15-26
+ * The copy rule is part of the definition (the literal sequence is not the identity at equal parameters): a tensor that
+ * is already in the result's quantisation is not moved.  The bytes equal that sequence for every input byte, whichever
+ * way the kernel evaluates it (csrc/i8ie_concat.hip).  Scales must be finite and s_out > 0; null
+ * pointers, k outside [1, 8], non-positive sizes and negative borders are I8IE_ERR_ARG too, all raised before any device
+ * call.  `in_dev`, `len`, `s_in`, ... are host arrays of k entries.  One launch for all k inputs; stateless and capturable
+ * in a graph.  `out` must not overlap an input.
+ * i8ie_concat_u8, the run form: `outer` x (for each input a contiguous run of len[i] bytes), written at
+ * outer_index * sum(len) + (len[0] + .. + len[i-1]).  NCHW: outer = n, len[i] = c_i * h * w; [m, f_i] rows: outer = m;
+ * border-free plain NHWC: outer = n * h * w, len[i] = c_i.  Any alignment (16 / 4 / 1 bytes per lane, chosen per input). */
+#define I8IE_CONCAT_MAX_INPUTS 8
+int i8ie_concat_u8(i8ie_ctx* ctx, int k, const uint8_t* const* in_dev, const int64_t* len, const float* s_in,
+                   const uint8_t* zp_in, uint8_t* out_dev, int64_t outer, float s_out, uint8_t zp_out, int relu);
+/* The same arithmetic on NHWC buffers: out [n, h+2b, w+2b, sum(c_in)], input i [n, h+2b_i, w+2b_i, c_in[i]], every
+ * buffer with its own border and plain (x_s8 = 0) or re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80).  Only the
+ * interior of `out` is written: its border bytes are the caller's and must hold zp_out (zp_out ^ 0x80 when out_s8), as
+ * i8ie_fill_border_u8 leaves them.  With every border 0 and nothing re-biased this is the run form. */
+int i8ie_concat_u8_nhwc(i8ie_ctx* ctx, int k, const uint8_t* const* in_dev, const int* c_in, const int* border_in,
+                        const int* s8_in, const float* s_in, const uint8_t* zp_in, uint8_t* out_dev, int out_border,
+                        int out_s8, int n, int h, int w, float s_out, uint8_t zp_out, int relu);
+/* The run form on fp32 elements (len[i] counts floats), a copy bit for bit: the Concat before convert() and while
+ * calibrating.  4-byte aligned buffers. */
+int i8ie_concat_f32(i8ie_ctx* ctx, int k, const float* const* in_dev, const int64_t* len, float* out_dev, int64_t outer);
+
 #ifdef __cplusplus
 }
 #endif

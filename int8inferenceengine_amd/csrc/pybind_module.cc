@@ -819,6 +819,140 @@ Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
       }, {a.pend, b.pend});
   return out;
 }
+// ---- cat (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_concat_u8) --------------------------
+// axis 1 of k rank-4 [n, c_i, h, w] or k rank-2 [m, f_i] tensors: the result's shape, or a RuntimeError (before any device call)
+template <typename T>
+std::vector<ssize_t> cat_shape(const std::vector<Tensor<T>>& ts) {
+  if (ts.empty() || ts.size() > I8IE_CONCAT_MAX_INPUTS) throw std::runtime_error("i8ie: cat: between 1 and 8 tensors");
+  std::vector<ssize_t> shp = ts[0].shape;
+  if (shp.size() != 2 && shp.size() != 4) throw std::runtime_error("i8ie: cat: tensors must be [n, c, h, w] or [m, f] (joined along axis 1)");
+  for (size_t i = 1; i < ts.size(); ++i) {
+    const std::vector<ssize_t>& s = ts[i].shape;
+    if (s.size() != shp.size()) throw std::runtime_error("i8ie: cat: ranks differ");
+    for (size_t d = 0; d < s.size(); ++d)
+      if (d != 1 && s[d] != ts[0].shape[d]) throw std::runtime_error("i8ie: cat: shapes differ outside axis 1");
+    shp[1] += s[1];
+  }
+  for (const auto& t : ts)
+    for (ssize_t d : t.shape)
+      if (d <= 0) throw std::runtime_error("i8ie: cat: empty tensor");
+  return shp;
+}
+// a Python list of tensors of one dtype; anything else (a mix included) is a RuntimeError
+template <typename T>
+std::vector<Tensor<T>> cat_list(const py::list& l) {
+  std::vector<Tensor<T>> ts;
+  for (const py::handle& h : l) {
+    if (!py::isinstance<Tensor<T>>(h)) throw std::runtime_error("i8ie: cat: every tensor must have the same dtype (float32, or uint8 with scale and zero_point)");
+    ts.push_back(h.cast<Tensor<T>&>());
+  }
+  return ts;
+}
+template <typename T>
+ssize_t cat_run_len(const Tensor<T>& t) { return t.shape.size() == 4 ? t.shape[1] * t.shape[2] * t.shape[3] : t.shape[1]; }
+Tensor<float> cat_f32(std::vector<Tensor<float>> ts) {
+  Tensor<float> out(cat_shape(ts));
+  const float* in[I8IE_CONCAT_MAX_INPUTS];
+  int64_t len[I8IE_CONCAT_MAX_INPUTS];
+  for (size_t i = 0; i < ts.size(); ++i) {
+    in[i] = ts[i].dptr();
+    len[i] = (int64_t)cat_run_len(ts[i]);
+  }
+  check(i8ie_concat_f32(ctx(), (int)ts.size(), in, len, out.dptr(), (int64_t)out.shape[0]));
+  return out;
+}
+Tensor<u8_t> cat_u8(std::vector<Tensor<u8_t>> ts, float scale, int zp) {
+  const std::vector<ssize_t> shp = cat_shape(ts);
+  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error("i8ie: cat: the output scale must be positive and finite");
+  for (const auto& t : ts)
+    if (!std::isfinite(t.scale)) throw std::runtime_error("i8ie: cat: an input's scale is not finite");
+  Tensor<u8_t> out;
+  out.shape = shp;
+  out.size = 1;
+  for (ssize_t d : shp) out.size *= d;
+  out.scale = scale;
+  out.zero_point = (u8_t)zp;
+  const u8_t zp_o = (u8_t)zp;
+  const ssize_t total = out.size;
+  // deferred like add's result: relu(cat(..)) is one launch, and a consuming conv gets its zero-point border and, where it
+  // reads them, re-biased bytes straight from the concat kernel.  (the closure's copies share the inputs' storage / launches)
+  auto node = make_pend([ts, scale, zp_o, shp, total](bool relu, int border, bool s8) mutable {
+    const int k = (int)ts.size();
+    // The inputs as they lie (add_operand).  A pending input that reads another one launches first: that launches the other
+    // for it (bordered as it wants it), and the other is then found among its node's results.
+    std::vector<std::shared_ptr<Storage>> ss((size_t)k);
+    for (int round = 0; round < k; ++round) {
+      int pick = -1;
+      for (int i = 0; i < k && pick < 0; ++i) {
+        if (ss[i]) continue;
+        bool is_read = false;
+        for (int j = 0; j < k && !is_read; ++j)
+          is_read = j != i && !ss[j] && ts[i].pend && ts[j].pend && ts[j].pend != ts[i].pend && ts[j].pend->made.empty() &&
+                    ts[j].pend->reads(ts[i].pend.get());
+        if (!is_read) pick = i;
+      }
+      if (pick < 0) pick = (int)(std::find(ss.begin(), ss.end(), nullptr) - ss.begin());  // (a cycle cannot be recorded)
+      ss[pick] = add_operand(ts[pick]);
+    }
+    const bool four = shp.size() == 4;
+    bool any_nhwc = false;
+    for (int i = 0; i < k; ++i) any_nhwc = any_nhwc || ss[i]->layout == I8IE_LAYOUT_NHWC;
+    const uint8_t* in[I8IE_CONCAT_MAX_INPUTS];
+    float s_in[I8IE_CONCAT_MAX_INPUTS];
+    uint8_t zp_in[I8IE_CONCAT_MAX_INPUTS];
+    for (int i = 0; i < k; ++i) {
+      s_in[i] = ts[i].scale;
+      zp_in[i] = ts[i].zero_point;
+    }
+    std::shared_ptr<Storage> st;
+    if (four && any_nhwc) {  // the engine keeps NHWC between layers (and a consumer that asked for a border reads NHWC)
+      int c_in[I8IE_CONCAT_MAX_INPUTS], b_in[I8IE_CONCAT_MAX_INPUTS], x_in[I8IE_CONCAT_MAX_INPUTS];
+      std::vector<std::shared_ptr<Storage>> tmps;  // NCHW inputs converted for this launch
+      for (int i = 0; i < k; ++i) {
+        const std::vector<ssize_t>& is = ts[i].shape;
+        // (a view whose storage is NHWC under other logical dims goes back to the reference's order, which the view is defined on)
+        if (ss[i]->layout == I8IE_LAYOUT_NHWC && (ss[i]->dn != is[0] || ss[i]->dc != is[1] || ss[i]->dh != is[2] || ss[i]->dw != is[3]))
+          ss[i]->to_nchw();
+        if (ss[i]->layout == I8IE_LAYOUT_NCHW) {
+          std::shared_ptr<Storage> src = ss[i];
+          for (int j = 0; j < i; ++j)
+            if (ts[j].st == src) ss[i] = ss[j];  // the same tensor again: its conversion too
+          if (ss[i] == src) {
+            auto tmp = device_storage((size_t)ts[i].size);
+            tmp->set_nhwc(is, 0);
+            check(i8ie_layout_convert_u8(ctx(), (const uint8_t*)src->device_ptr(), (uint8_t*)tmp->dev, (int)is[0], (int)is[1], (int)is[2],
+                                         (int)is[3], 1, 0, 0));
+            tmps.push_back(tmp);
+            ss[i] = tmp;
+          }
+        }
+        in[i] = (const uint8_t*)ss[i]->device_ptr();
+        c_in[i] = (int)is[1];
+        b_in[i] = ss[i]->border;
+        x_in[i] = ss[i]->s8 ? 1 : 0;
+      }
+      st = nhwc_storage(shp, border, zp_o, s8);
+      check(i8ie_concat_u8_nhwc(ctx(), k, in, c_in, b_in, x_in, s_in, zp_in, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, (int)shp[0],
+                                (int)shp[2], (int)shp[3], scale, zp_o, relu ? 1 : 0));
+    } else {  // NCHW tensors and [m, f_i] rows (a flattened NHWC activation goes back to the reference's order): the run form
+      int64_t len[I8IE_CONCAT_MAX_INPUTS];
+      for (int i = 0; i < k; ++i) {
+        ss[i]->to_nchw();
+        in[i] = (const uint8_t*)ss[i]->device_ptr();
+        len[i] = (int64_t)cat_run_len(ts[i]);
+      }
+      st = device_storage((size_t)total);
+      check(i8ie_concat_u8(ctx(), k, in, len, s_in, zp_in, (uint8_t*)st->dev, (int64_t)shp[0], scale, zp_o, relu ? 1 : 0));
+    }
+    // (the inputs are released with the closure's copies, as a layer's input is)
+    return st;
+  });
+  for (const auto& t : ts)
+    if (t.pend) node->inputs.push_back(t.pend);
+  out.pend = node;
+  return out;
+}
 // ---- avg_pool2d / global_avg_pool2d (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_avgpool2d_u8) ---
 // kh x kw window; the global pool is the whole image at stride 1
 template <typename T>
@@ -1442,13 +1576,14 @@ class Conv2d : public BaseLayer {
   ssize_t in_channels_ = 0;  // as constructed from sizes (0: constructed from arrays)
 };
 
-// The residual Add as a layer without weights: the layers' prepare / convert state machine (src/layer.cc:28-54) around
-// its output (scale, zero_point); FP32 tensors add in FP32 (and are sampled while preparing), u8 tensors after convert().
-class Add {
+// A layer without weights (the residual Add, the channel Concat): the layers' prepare / convert state machine
+// (src/layer.cc:28-54) around its output (scale, zero_point); FP32 tensors join in FP32 (and are sampled while preparing),
+// u8 tensors after convert().
+class Weightless {
  public:
-  Add() = default;
-  Add(const Add&) = delete;
-  Add& operator=(const Add&) = delete;
+  Weightless() = default;
+  Weightless(const Weightless&) = delete;
+  Weightless& operator=(const Weightless&) = delete;
   void prepare() {
     if (is_quantized_) {
       std::cerr << "already quantized" << std::endl;
@@ -1457,7 +1592,7 @@ class Add {
     cal_ = std::make_unique<Calibrator>();
     is_preparing_ = true;
   }
-  void convert(bool /*per_channel: an Add has no weights*/ = false) {
+  void convert(bool /*per_channel: there are no weights*/ = false) {
     if (is_quantized_) {
       std::cerr << "already quantized" << std::endl;
       return;
@@ -1491,17 +1626,15 @@ class Add {
     is_quantized_ = true;
   }
   bool is_quantized() const { return is_quantized_; }
-  Tensor<float> forward_f32(Tensor<float>& a, Tensor<float>& b) {
-    Tensor<float> out = add_f32(a, b);
+
+ protected:
+  Tensor<float> sampled(Tensor<float> out) {  // what a preparing layer does with its FP32 result
     if (is_preparing_) calib_sample(*cal_, out);
     return out;
   }
-  Tensor<u8_t> forward_u8(Tensor<u8_t>& a, Tensor<u8_t>& b) {
-    if (!is_quantized_) throw std::runtime_error("i8ie: Add is not converted (call convert() first)");
-    return add_u8(a, b, scale_, zero_point_);
+  void need_quantized(const char* what) const {
+    if (!is_quantized_) throw std::runtime_error(std::string("i8ie: ") + what + " is not converted (call convert() first)");
   }
-
- private:
   std::unique_ptr<Calibrator> cal_;
   bool is_preparing_ = false;
   bool is_quantized_ = false;
@@ -1509,6 +1642,37 @@ class Add {
   float scale_ = 1;
   u8_t zero_point_ = 0;
 };
+class Add : public Weightless {
+ public:
+  Tensor<float> forward_f32(Tensor<float>& a, Tensor<float>& b) { return sampled(add_f32(a, b)); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& a, Tensor<u8_t>& b) {
+    need_quantized("Add");
+    return add_u8(a, b, scale_, zero_point_);
+  }
+};
+// cat along axis 1: a list of FP32 tensors before convert(), of u8 tensors after it
+class Concat : public Weightless {
+ public:
+  py::object forward(const py::list& tensors) {
+    if (!tensors.empty() && py::isinstance<Tensor<u8_t>>(tensors[0])) {
+      std::vector<Tensor<u8_t>> ts = cat_list<u8_t>(tensors);
+      cat_shape(ts);
+      need_quantized("Concat");
+      return py::cast(cat_u8(std::move(ts), scale_, zero_point_));
+    }
+    return py::cast(sampled(cat_f32(cat_list<float>(tensors))));
+  }
+};
+template <typename L>
+void bind_weightless_common(py::class_<L>& c) {
+  c.def(py::init<>())
+      .def("prepare", &L::prepare)
+      .def("convert", &L::convert, py::arg("per_channel") = false)
+      .def("set_output_qparams", &L::set_output_qparams, py::arg("scale"), py::arg("zero_point"))
+      .def("output_qparams", &L::output_qparams)
+      .def("load_quantized", &L::load_quantized, py::arg("out_scale"), py::arg("out_zero_point"))
+      .def("is_quantized", &L::is_quantized);
+}
 
 template <typename L>
 void bind_layer_common(py::class_<L>& c) {
@@ -1567,6 +1731,10 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
   // additive (the reference joins no two tensors): a + b in FP32; the quantized Add of include/i8ie_hip.h on u8 tensors
   m.def("add", &add_f32, py::arg("a"), py::arg("b"));
   m.def("add", &add_u8, py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("zero_point"));
+  // additive: cat along axis 1 of up to 8 tensors, a copy in FP32; the quantized concat of include/i8ie_hip.h on u8 tensors
+  m.def("cat", [](const py::list& tensors) { return cat_f32(cat_list<float>(tensors)); }, py::arg("tensors"));
+  m.def("cat", [](const py::list& tensors, float scale, int zp) { return cat_u8(cat_list<u8_t>(tensors), scale, zp); },
+        py::arg("tensors"), py::arg("scale"), py::arg("zero_point"));
   // additive (the reference has no average pool): round-to-nearest integer mean on u8 tensors, fp32 sum / n on FP32 ones
   m.def("avg_pool2d", [](Tensor<float>& x, ssize_t k, ssize_t s) { return avg_pool_f32(x, k, s, false); }, py::arg("x"),
         py::arg("kernel_size"), py::arg("stride"));
@@ -1595,16 +1763,16 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
     bind_layer_common(c);
   }
 
-  py::class_<Add>(m, "Add")
-      .def(py::init<>())
-      .def("prepare", &Add::prepare)
-      .def("convert", &Add::convert, py::arg("per_channel") = false)
-      .def("__call__", &Add::forward_f32)
-      .def("__call__", &Add::forward_u8)
-      .def("set_output_qparams", &Add::set_output_qparams, py::arg("scale"), py::arg("zero_point"))
-      .def("output_qparams", &Add::output_qparams)
-      .def("load_quantized", &Add::load_quantized, py::arg("out_scale"), py::arg("out_zero_point"))
-      .def("is_quantized", &Add::is_quantized);
+  {
+    py::class_<Add> c(m, "Add");
+    bind_weightless_common(c);
+    c.def("__call__", &Add::forward_f32).def("__call__", &Add::forward_u8);
+  }
+  {
+    py::class_<Concat> c(m, "Concat");
+    bind_weightless_common(c);
+    c.def("__call__", &Concat::forward, py::arg("tensors"));
+  }
 
   // ---- additive runtime controls -------------------------------------------------
   m.def("abi_version", []() { return i8ie_version(); });

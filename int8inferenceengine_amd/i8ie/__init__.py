@@ -7,7 +7,7 @@ device-resident and `.numpy()` copies back to the host.
 """
 import _CXX_i8ie as _C
 
-from .layer import Add, Conv2d, Layer, Linear
+from .layer import Add, Concat, Conv2d, Layer, Linear
 from .module import Module
 from .tensor import Tensor
 
@@ -15,7 +15,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
-    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add", "avg_pool2d", "global_avg_pool2d",
+    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add", "Concat", "cat", "avg_pool2d", "global_avg_pool2d",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -59,6 +59,22 @@ def add(a, b, scale=None, zero_point=None):
     if scale is not None or zero_point is not None:
         raise TypeError("add of FP32 tensors takes no scale / zero_point")
     return Tensor(_C.add(a.data, b.data))
+
+
+def cat(tensors, scale=None, zero_point=None):
+    """Join 1 to 8 tensors [n, c_i, h, w] (or [m, f_i]) along axis 1.  FP32 tensors: a copy, `scale` / `zero_point` must not
+    be given.  uint8 tensors: the quantized concat of include/i8ie_hip.h (i8ie_concat_u8); the result's `scale` and
+    `zero_point` are required, an input that already has them is copied byte for byte and any other is requantised.
+    `i8ie.Concat` is the calibrated form for use inside a Module."""
+    tensors = list(tensors)
+    quantized = bool(tensors) and type(tensors[0].data).__name__ == "6TensorIhE"
+    if quantized:
+        if scale is None or zero_point is None:
+            raise TypeError("cat of uint8 tensors needs the result's scale and zero_point")
+        return Tensor(_C.cat([t.data for t in tensors], float(scale), int(zero_point)))
+    if scale is not None or zero_point is not None:
+        raise TypeError("cat of FP32 tensors takes no scale / zero_point")
+    return Tensor(_C.cat([t.data for t in tensors]))
 
 
 def avg_pool2d(x, kernel_size, stride=None):

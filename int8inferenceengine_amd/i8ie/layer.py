@@ -71,20 +71,11 @@ class Conv2d(Layer):
         self.layer = _C.Conv2d(in_channels, out_channels, kernel_size, stride, padding, groups)
 
 
-class Add(Layer):
-    """Quantized residual add `y = self.add1(a, b)` (additive, not in the reference): a layer without weights.
-
-    FP32 tensors add in FP32 (sampled by the calibrator while preparing, as a layer's FP32 output is); uint8 tensors,
-    after convert(), by the arithmetic of include/i8ie_hip.h (i8ie_add_u8) with this Add's output (scale, zero_point).
-    Shapes must be equal (no broadcasting).  Takes part in Module.prepare() / convert() / quantized_state_dict();
-    Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values); load_weight, load_bias,
-    weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
-
-    def __init__(self):
-        self.layer = _C.Add()
-
-    def __call__(self, a, b):
-        return Tensor(self.layer(a.data, b.data))
+class Weightless(Layer):
+    """Common behaviour of the layers without weights (Add, Concat): `self.layer` has only the prepare / convert state
+    machine around an output (scale, zero_point).  Takes part in Module.prepare() / convert() / quantized_state_dict()
+    (`<attr>.qparams` only); Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values);
+    load_weight, load_bias, weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
 
     def convert(self, per_channel=False):
         """per_channel is accepted and ignored."""
@@ -94,6 +85,35 @@ class Add(Layer):
         return False
 
     def _no_weights(self, *args, **kwargs):
-        raise RuntimeError("i8ie: an Add has no weights")
+        raise RuntimeError("i8ie: %s has no weights" % type(self).__name__)
 
     load_weight = load_bias = weight_scale = weight_scales = forward_debug = _no_weights
+
+
+class Add(Weightless):
+    """Quantized residual add `y = self.add1(a, b)` (additive, not in the reference): a layer without weights.
+
+    FP32 tensors add in FP32 (sampled by the calibrator while preparing, as a layer's FP32 output is); uint8 tensors,
+    after convert(), by the arithmetic of include/i8ie_hip.h (i8ie_add_u8) with this Add's output (scale, zero_point).
+    Shapes must be equal (no broadcasting)."""
+
+    def __init__(self):
+        self.layer = _C.Add()
+
+    def __call__(self, a, b):
+        return Tensor(self.layer(a.data, b.data))
+
+
+class Concat(Weightless):
+    """Quantized channel concatenation `y = self.cat1([a, b, ...])` (additive, not in the reference): a layer without weights.
+
+    Joins 1 to 8 tensors [n, c_i, h, w] (or [m, f_i]) along axis 1.  FP32 tensors are copied (the result is sampled by
+    the calibrator while preparing); uint8 tensors, after convert(), are brought to this Concat's output (scale,
+    zero_point) by the arithmetic of include/i8ie_hip.h (i8ie_concat_u8): an input already in that quantisation is
+    copied byte for byte, any other is requantised."""
+
+    def __init__(self):
+        self.layer = _C.Concat()
+
+    def __call__(self, tensors):
+        return Tensor(self.layer([t.data for t in tensors]))

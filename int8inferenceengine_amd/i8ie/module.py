@@ -1,7 +1,7 @@
 """Module base class (reference i8ie/module.py:6-35)."""
 import _CXX_i8ie as _C
 
-from .layer import Add, Layer
+from .layer import Layer, Weightless
 from .tensor import Tensor
 
 # Hard-coded input quantisation of the reference (i8ie/module.py:20).
@@ -51,7 +51,7 @@ class Module:
     def quantized_state_dict(self):
         """{'<attr>.q_weight' int8, '<attr>.q_bias' int8, '<attr>.qparams' float64[3] =
         (weight_scale, out_scale, out_zero_point)} for every converted layer; a per-channel layer also has
-        '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused).  An Add contributes only
+        '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused).  An Add or a Concat contributes only
         '<attr>.qparams' = (0, out_scale, out_zero_point)."""
         import numpy as np
 
@@ -61,7 +61,7 @@ class Module:
             if not L.is_quantized():
                 raise RuntimeError("layer %r is not converted" % name)
             s_out, zp_out = L.output_qparams()
-            if isinstance(layer, Add):
+            if isinstance(layer, Weightless):
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
                 continue
             out[name + ".q_weight"] = L.q_weight()
@@ -79,7 +79,7 @@ class Module:
 
         for name, layer in self._layers():
             w_scale, s_out, zp_out = (float(v) for v in state[name + ".qparams"])
-            if isinstance(layer, Add):
+            if isinstance(layer, Weightless):
                 layer.layer.load_quantized(float(np.float32(s_out)), int(zp_out))
                 continue
             if name + ".w_scales" in state:  # per-channel layer

@@ -18,7 +18,8 @@ import numpy as np
 #            | ("add", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Add (not in `layers`)
 #            | ("branch", tag, [ops...])  run ops on saved[tag] and store the result back under `tag` (projection shortcut)
 #            | ("avgpool", k, s)          i8ie.avg_pool2d(x, k, s)
-#            | ("gap",)                   i8ie.global_avg_pool2d(x)]
+#            | ("gap",)                   i8ie.global_avg_pool2d(x)
+#            | ("concat", attr, [tags])   x = getattr(net, attr)([x] + [saved[t] for t in tags]); attr names an i8ie.Concat]
 NETWORKS = {
     # sample/notebooks/AlexNet_cifar10_resize224.ipynb:47-71
     "alexnet": (
@@ -118,6 +119,53 @@ def _resnet18_cifar():
 NETWORKS["resnet18_cifar"] = _resnet18_cifar()
 
 
+def _fire(layers, spec, p, in_c, squeeze, e1, e3, relu_after=False):
+    """A fire module (Iandola et al. 2016): 1x1 squeeze, then a 1x1 and a 3x3 expand side by side, joined along the channels.
+    relu_after: one ReLU behind the concat instead of one on each expand branch (the same function; it folds into the concat)."""
+    layers[p + "s"] = ("conv", in_c, squeeze, 1, 1, 0)
+    layers[p + "e1"] = ("conv", squeeze, e1, 1, 1, 0)
+    layers[p + "e3"] = ("conv", squeeze, e3, 3, 1, 1)
+    r = [] if relu_after else [("relu",)]
+    spec += [("layer", p + "s"), ("relu",), ("save", p), ("layer", p + "e1")] + r
+    spec += [("branch", p, [("layer", p + "e3")] + r), ("concat", p + "cat", [p])] + ([("relu",)] if relu_after else [])
+    return e1 + e3
+
+
+def _fire_tiny():
+    """Two fire modules (the second with channel counts that are no multiple of 16 and its ReLU behind the concat), then an
+    Inception-style reduction: a max-pool, a 4-group 3x3 conv and a 1x1 conv side by side.  What the Concat exists for."""
+    layers = {"stem": ("conv", 3, 16, 3, 1, 1)}
+    spec = [("layer", "stem"), ("relu",)]
+    c = _fire(layers, spec, "fa", 16, 8, 16, 16)
+    c = _fire(layers, spec, "fb", c, 12, 20, 12, relu_after=True)
+    layers["rg"] = ("conv", c, 16, 3, 2, 1, 4)
+    layers["r1"] = ("conv", c, 16, 1, 2, 0)
+    spec += [("save", "rg"), ("save", "r1"), ("pool", 2, 2), ("branch", "rg", [("layer", "rg"), ("relu",)]),
+             ("branch", "r1", [("layer", "r1"), ("relu",)]), ("concat", "rcat", ["rg", "r1"])]
+    layers["fc"] = ("fc", c + 32, 10)
+    spec += [("gap",), ("flatten", c + 32), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+def _squeezenet_cifar():
+    """SqueezeNet 1.1 (Iandola et al. 2016; the 1.1 revision's pool placement) for CIFAR-10: a 3x3 stem at stride 1, eight fire
+    modules at the original widths, 3x3 stride-2 floor-mode max-pools, a 1x1 classifier conv to 10, global average pool."""
+    layers = {"stem": ("conv", 3, 64, 3, 1, 1)}
+    spec = [("layer", "stem"), ("relu",), ("pool", 3, 2)]
+    c = 64
+    for i, (sq, ex) in enumerate(((16, 64), (16, 64), (32, 128), (32, 128), (48, 192), (48, 192), (64, 256), (64, 256)), start=2):
+        c = _fire(layers, spec, "fire%d" % i, c, sq, ex, ex)
+        if i in (3, 5):
+            spec.append(("pool", 3, 2))
+    layers["classifier"] = ("conv", c, 10, 1, 1, 0)
+    spec += [("layer", "classifier"), ("relu",), ("gap",), ("flatten", 10)]
+    return layers, spec, (3, 32, 32)
+
+
+NETWORKS["fire_tiny"] = _fire_tiny()
+NETWORKS["squeezenet_cifar"] = _squeezenet_cifar()
+
+
 def _walk(spec):
     """every op of a spec in order, the ops inside ("branch", tag, [ops]) included"""
     for op in spec:
@@ -193,6 +241,8 @@ def build(name):
             for op in _walk(spec):
                 if op[0] == "add":
                     setattr(self, op[1], i8ie.Add())
+                elif op[0] == "concat":
+                    setattr(self, op[1], i8ie.Concat())
             for attr, L in layers.items():
                 if L[0] == "conv":
                     if conv_groups(L) == 1:
@@ -220,6 +270,8 @@ def build(name):
                     saved[op[1]] = self.run(op[2], saved[op[1]], saved)
                 elif op[0] == "add":
                     x = getattr(self, op[1])(x, saved[op[2]])
+                elif op[0] == "concat":
+                    x = getattr(self, op[1])([x] + [saved[t] for t in op[2]])
                 else:
                     x = x.reshape(-1, op[1])
             return x
@@ -255,3 +307,8 @@ def layer_names(name):
 def add_names(name):
     """the Adds of a residual network, in spec order"""
     return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "add"]
+
+
+def concat_names(name):
+    """the Concats of a network, in spec order"""
+    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "concat"]
