@@ -501,6 +501,49 @@ int i8ie_concat_u8_nhwc(i8ie_ctx* ctx, int k, const uint8_t* const* in_dev, cons
  * calibrating.  4-byte aligned buffers. */
 int i8ie_concat_f32(i8ie_ctx* ctx, int k, const float* const* in_dev, const int64_t* len, float* out_dev, int64_t outer);
 
+/* ---- table-driven quantized activations (no counterpart in the reference: its one non-linearity is relu) ----
+ * In the quantized domain an activation is a function from one byte to one byte: a 256-entry table applied to a u8
+ * tensor.  f(x) on a float x, IEEE fp32, one rounding per operation, no contraction:
+ *     I8IE_ACT_RELU6        v = x > 0 ? x : 0;  y = v < 6 ? v : 6                   min(max(x, 0), 6)
+ *     I8IE_ACT_LEAKY_RELU   y = x >= 0 ? x : x * param                              param: the slope (finite)
+ *     I8IE_ACT_HARDSIGMOID  v = x + 3;  v = v > 0 ? v : 0;  h = v < 6 ? v : 6;  y = h / 6
+ *     I8IE_ACT_HARDSWISH    h as above;  y = (x * h) / 6
+ *     I8IE_ACT_SIGMOID      y = (float)(1.0 / (1.0 + exp(-(double)x)))              double precision, one rounding to float
+ *     I8IE_ACT_TANH         y = (float)tanh((double)x)
+ * `param` is read by I8IE_ACT_LEAKY_RELU only.  The table of an activation from (s_in, zp_in) to (s_out, zp_out), for
+ * every byte a:
+ *     x = (float)((int)a - (int)zp_in) * s_in                                       dequantize, src/quantize_utils.cc:38-42
+ *     t = f(x) / s_out + (float)zp_out
+ *     table[a] = t >= 255 ? 255 : (t < 0 ? 0 : (u8)t)                               down_scale's clamp + truncation, :27-36
+ * The scales must be finite, s_out > 0 and 255 * s_in finite in fp32 (no NaN can then arise in any kind); an unknown
+ * kind, a non-finite slope and a null table are I8IE_ERR_ARG too.
+ * i8ie_activation_table: host only (no ctx, like i8ie_quantize_weight); for sigmoid and tanh it calls the host's
+ * double-precision libm.  A following relu folds into a table as max(table[a], zp_out). */
+#define I8IE_ACT_RELU6 0
+#define I8IE_ACT_LEAKY_RELU 1
+#define I8IE_ACT_HARDSIGMOID 2
+#define I8IE_ACT_HARDSWISH 3
+#define I8IE_ACT_SIGMOID 4
+#define I8IE_ACT_TANH 5
+int i8ie_activation_table(int kind, float param, float s_in, uint8_t zp_in, float s_out, uint8_t zp_out,
+                          uint8_t table_host[256]);
+/* out[i] = table[in[i]] over n bytes in one physical order, any n and any alignment (16 / 4 / 1 bytes per lane by the
+ * alignment of both pointers); `out` may be `in` itself (no other overlap).  The 256 table bytes are read from the
+ * host at the call and travel by value in the kernel arguments: one launch, no device allocation, no copy, no
+ * synchronisation; stateless and capturable in a graph.  Every argument error is raised before any device call. */
+int i8ie_lut_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int64_t n, const uint8_t* table_host);
+/* The same on NHWC buffers [n, h+2b, w+2b, c], each with its own border and plain (x_s8 = 0) or re-biased (x_s8 != 0:
+ * I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80); `table_host` maps plain bytes to plain bytes, the re-bias of either side is
+ * folded into the table on the host (t'[a ^ 0x80*in_s8] = table[a] ^ 0x80*out_s8).  Only the interior of `out` is
+ * written: its border bytes are the caller's.  Any c (16 / 4 / 1 bytes per lane by c % 16, c % 4 and the pointers'
+ * alignment).  With both borders 0 this is the flat form. */
+int i8ie_lut_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev, int out_border,
+                     int out_s8, int n, int c, int h, int w, const uint8_t* table_host);
+/* out[i] = f(in[i]) on n floats (4-byte aligned; in place allowed): the activation before convert() and while
+ * calibrating.  relu6, leaky_relu, hardsigmoid and hardswish are the fp32 sequences above bit for bit; sigmoid and
+ * tanh go through the device's double-precision exp / tanh (DESIGN.md section 8f states the error bound). */
+int i8ie_activation_f32(i8ie_ctx* ctx, int kind, float param, const float* in_dev, float* out_dev, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1014,6 +1014,72 @@ Tensor<u8_t> avg_pool_u8(Tensor<u8_t>& in, ssize_t k, ssize_t s, bool global) {
       }, {in.pend});
   return out;
 }
+// ---- activation / lut (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_activation_table) -------
+using LutBytes = std::array<u8_t, 256>;
+Tensor<float> activation_f32(Tensor<float>& in, int kind, float param) {
+  Tensor<float> out(in.shape);
+  check(i8ie_activation_f32(ctx(), kind, param, in.dptr(), out.dptr(), in.size));
+  return out;
+}
+// out = table[in] with the result's (scale, zp): table maps plain bytes to plain bytes
+Tensor<u8_t> lut_u8(Tensor<u8_t>& in, const LutBytes& table, float scale, int zp) {
+  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error("i8ie: lut: the output scale must be positive and finite");
+  if (!in.st && !in.pend) throw std::runtime_error("i8ie: empty tensor");
+  Tensor<u8_t> out;
+  out.shape = in.shape;
+  out.size = in.size;
+  out.scale = scale;
+  out.zero_point = (u8_t)zp;
+  Tensor<u8_t> src = in;
+  const std::vector<ssize_t> shp = in.shape;
+  const ssize_t total = in.size;
+  const u8_t zp_o = (u8_t)zp;
+  // deferred like add's and cat's results: relu(act(..)) is one launch (the relu is max(table[a], zp) on the host), and a
+  // consuming conv gets its zero-point border and, where it reads them, re-biased bytes straight from the lookup kernel
+  out.pend = make_pend(
+      [src, table, zp_o, shp, total](bool relu, int border, bool s8) mutable {
+        // the input as it lies (any border, plain or re-biased): a pending producer launches plain, one that has launched
+        // for another consumer is not launched again
+        std::shared_ptr<Storage> si = add_operand(src);
+        LutBytes t = table;
+        if (relu)
+          for (u8_t& b : t) b = std::max(b, zp_o);
+        std::shared_ptr<Storage> st;
+        if (shp.size() == 4) {  // the engine keeps NHWC between layers (and a consumer that asked for a border reads NHWC)
+          // (a view whose storage is NHWC under other logical dims goes back to the reference's order, which the view is defined on)
+          if (si->layout == I8IE_LAYOUT_NHWC && (si->dn != shp[0] || si->dc != shp[1] || si->dh != shp[2] || si->dw != shp[3])) si->to_nchw();
+          if (si->layout == I8IE_LAYOUT_NCHW) {  // a user-made tensor: one layout conversion
+            auto tmp = device_storage((size_t)total);
+            tmp->set_nhwc(shp, 0);
+            check(i8ie_layout_convert_u8(ctx(), (const uint8_t*)si->device_ptr(), (uint8_t*)tmp->dev, (int)shp[0], (int)shp[1], (int)shp[2],
+                                         (int)shp[3], 1, 0, 0));
+            si = tmp;
+          }
+          st = nhwc_storage(shp, border, zp_o, s8);
+          check(i8ie_lut_u8_nhwc(ctx(), (const uint8_t*)si->device_ptr(), si->border, si->s8 ? 1 : 0, (uint8_t*)st->dev, st->border,
+                                 st->s8 ? 1 : 0, (int)shp[0], (int)shp[1], (int)shp[2], (int)shp[3], t.data()));
+        } else {  // rows and other ranks (a flattened NHWC activation goes back to the reference's order): the flat form
+          si->to_nchw();
+          st = device_storage((size_t)total);
+          check(i8ie_lut_u8(ctx(), (const uint8_t*)si->device_ptr(), (uint8_t*)st->dev, (int64_t)total, t.data()));
+        }
+        return st;
+      }, {in.pend});
+  return out;
+}
+Tensor<u8_t> activation_u8(Tensor<u8_t>& in, int kind, float param, float scale, int zp) {
+  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+  LutBytes table;
+  check(i8ie_activation_table(kind, param, in.scale, in.zero_point, scale, (uint8_t)zp, table.data()));
+  return lut_u8(in, table, scale, zp);
+}
+LutBytes lut_from_array(const py::array_t<uint8_t, py::array::c_style>& a) {
+  if (a.size() != 256) throw std::runtime_error("i8ie: lut: the table must hold 256 uint8 entries");
+  LutBytes t;
+  std::memcpy(t.data(), a.data(), 256);
+  return t;
+}
 // the s8 instantiations of the generic templates (src/functional.cc:5-13, 36-64, registered at :78-82)
 Tensor<s8_t> relu_s8(Tensor<s8_t>& in) {
   if (!in.st) return Tensor<s8_t>();  // default-constructed: nothing to do
@@ -1663,15 +1729,39 @@ class Concat : public Weightless {
     return py::cast(sampled(cat_f32(cat_list<float>(tensors))));
   }
 };
+// a table-driven activation (I8IE_ACT_*): f in FP32 before convert(), one table lookup from the input tensor's
+// (scale, zero_point) to this layer's own output qparams after it
+class Activation : public Weightless {
+ public:
+  Activation(int kind, float param) : kind_(kind), param_(param) {
+    LutBytes probe;  // (an unknown kind or a slope that is not finite is refused here)
+    check(i8ie_activation_table(kind, param, 1.0f, 0, 1.0f, 0, probe.data()));
+  }
+  Tensor<float> forward_f32(Tensor<float>& x) { return sampled(activation_f32(x, kind_, param_)); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& x) {
+    need_quantized("Activation");
+    return activation_u8(x, kind_, param_, scale_, zero_point_);
+  }
+  int kind() const { return kind_; }
+  float param() const { return param_; }
+
+ private:
+  int kind_;
+  float param_;
+};
 template <typename L>
-void bind_weightless_common(py::class_<L>& c) {
-  c.def(py::init<>())
-      .def("prepare", &L::prepare)
+void bind_weightless_state(py::class_<L>& c) {
+  c.def("prepare", &L::prepare)
       .def("convert", &L::convert, py::arg("per_channel") = false)
       .def("set_output_qparams", &L::set_output_qparams, py::arg("scale"), py::arg("zero_point"))
       .def("output_qparams", &L::output_qparams)
       .def("load_quantized", &L::load_quantized, py::arg("out_scale"), py::arg("out_zero_point"))
       .def("is_quantized", &L::is_quantized);
+}
+template <typename L>
+void bind_weightless_common(py::class_<L>& c) {
+  c.def(py::init<>());
+  bind_weightless_state(c);
 }
 
 template <typename L>
@@ -1735,6 +1825,19 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
   m.def("cat", [](const py::list& tensors) { return cat_f32(cat_list<float>(tensors)); }, py::arg("tensors"));
   m.def("cat", [](const py::list& tensors, float scale, int zp) { return cat_u8(cat_list<u8_t>(tensors), scale, zp); },
         py::arg("tensors"), py::arg("scale"), py::arg("zero_point"));
+  // additive: the table-driven activations of include/i8ie_hip.h (kind: I8IE_ACT_*), f in FP32, one table lookup on u8
+  // tensors; lut applies a caller's own 256-entry table
+  m.def("activation", &activation_f32, py::arg("x"), py::arg("kind"), py::arg("param"));
+  m.def("activation", &activation_u8, py::arg("x"), py::arg("kind"), py::arg("param"), py::arg("scale"), py::arg("zero_point"));
+  m.def("lut", [](Tensor<u8_t>& x, const py::array_t<uint8_t, py::array::c_style>& table, float scale, int zp) {
+    return lut_u8(x, lut_from_array(table), scale, zp);
+  }, py::arg("x"), py::arg("table"), py::arg("scale"), py::arg("zero_point"));
+  m.def("activation_table", [](int kind, float param, float s_in, int zp_in, float s_out, int zp_out) {
+    if (zp_in < 0 || zp_in > 255 || zp_out < 0 || zp_out > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+    py::array_t<uint8_t> out(256);
+    check(i8ie_activation_table(kind, param, s_in, (uint8_t)zp_in, s_out, (uint8_t)zp_out, out.mutable_data()));
+    return out;
+  }, py::arg("kind"), py::arg("param"), py::arg("s_in"), py::arg("zp_in"), py::arg("s_out"), py::arg("zp_out"));
   // additive (the reference has no average pool): round-to-nearest integer mean on u8 tensors, fp32 sum / n on FP32 ones
   m.def("avg_pool2d", [](Tensor<float>& x, ssize_t k, ssize_t s) { return avg_pool_f32(x, k, s, false); }, py::arg("x"),
         py::arg("kernel_size"), py::arg("stride"));
@@ -1772,6 +1875,12 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
     py::class_<Concat> c(m, "Concat");
     bind_weightless_common(c);
     c.def("__call__", &Concat::forward, py::arg("tensors"));
+  }
+  {
+    py::class_<Activation> c(m, "Activation");
+    c.def(py::init<int, float>(), py::arg("kind"), py::arg("param") = 0.0f);
+    bind_weightless_state(c);
+    c.def("__call__", &Activation::forward_f32).def("__call__", &Activation::forward_u8).def("kind", &Activation::kind).def("param", &Activation::param);
   }
 
   // ---- additive runtime controls -------------------------------------------------

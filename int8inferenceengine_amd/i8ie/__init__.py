@@ -7,7 +7,7 @@ device-resident and `.numpy()` copies back to the host.
 """
 import _CXX_i8ie as _C
 
-from .layer import Add, Concat, Conv2d, Layer, Linear
+from .layer import Activation, Add, Concat, Conv2d, Layer, Linear, activation_kind
 from .module import Module
 from .tensor import Tensor
 
@@ -15,7 +15,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
-    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add", "Concat", "cat", "avg_pool2d", "global_avg_pool2d",
+    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -75,6 +75,35 @@ def cat(tensors, scale=None, zero_point=None):
     if scale is not None or zero_point is not None:
         raise TypeError("cat of FP32 tensors takes no scale / zero_point")
     return Tensor(_C.cat([t.data for t in tensors]))
+
+
+def activation(x, kind, scale=None, zero_point=None, param=None):
+    """f(x) for kind "relu6", "leaky_relu" (param: the slope, default 0.01), "hardsigmoid", "hardswish", "sigmoid" or "tanh".
+    FP32 tensors: f in FP32, `scale` / `zero_point` must not be given.  uint8 tensors: one 256-entry table from x's
+    (scale, zero_point) to the result's `scale` and `zero_point`, which are required (include/i8ie_hip.h,
+    i8ie_activation_table).  `i8ie.Activation` is the calibrated form for use inside a Module."""
+    code, p = activation_kind(kind, param)
+    quantized = type(x.data).__name__ == "6TensorIhE"
+    if quantized:
+        if scale is None or zero_point is None:
+            raise TypeError("activation of a uint8 tensor needs the result's scale and zero_point")
+        return Tensor(_C.activation(x.data, code, p, float(scale), int(zero_point)))
+    if scale is not None or zero_point is not None:
+        raise TypeError("activation of an FP32 tensor takes no scale / zero_point")
+    return Tensor(_C.activation(x.data, code, p))
+
+
+def lut(x, table, scale, zero_point):
+    """y = table[x] on a uint8 tensor: `table` is 256 uint8 entries from x's bytes to the result's, which carries `scale`
+    and `zero_point` (include/i8ie_hip.h, i8ie_lut_u8)."""
+    import numpy as np
+
+    t = np.asarray(table)
+    if t.dtype != np.uint8 or t.shape != (256,):
+        raise TypeError("lut needs a uint8 table of 256 entries")
+    if type(x.data).__name__ != "6TensorIhE":
+        raise TypeError("lut needs a uint8 tensor")
+    return Tensor(_C.lut(x.data, np.ascontiguousarray(t), float(scale), int(zero_point)))
 
 
 def avg_pool2d(x, kernel_size, stride=None):

@@ -72,7 +72,7 @@ class Conv2d(Layer):
 
 
 class Weightless(Layer):
-    """Common behaviour of the layers without weights (Add, Concat): `self.layer` has only the prepare / convert state
+    """Common behaviour of the layers without weights (Add, Concat, Activation): `self.layer` has only the prepare / convert state
     machine around an output (scale, zero_point).  Takes part in Module.prepare() / convert() / quantized_state_dict()
     (`<attr>.qparams` only); Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values);
     load_weight, load_bias, weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
@@ -117,3 +117,37 @@ class Concat(Weightless):
 
     def __call__(self, tensors):
         return Tensor(self.layer([t.data for t in tensors]))
+
+
+# the kinds of a table-driven activation (include/i8ie_hip.h, I8IE_ACT_*)
+ACTIVATION_KINDS = {"relu6": 0, "leaky_relu": 1, "hardsigmoid": 2, "hardswish": 3, "sigmoid": 4, "tanh": 5}
+LEAKY_RELU_DEFAULT_SLOPE = 0.01
+
+
+def activation_kind(kind, param):
+    """(I8IE_ACT_* code, param) of a kind given by name.  `param` is leaky_relu's slope (default 0.01) and must be None for
+    every other kind."""
+    if kind not in ACTIVATION_KINDS:
+        raise ValueError("unknown activation %r (one of %s)" % (kind, ", ".join(sorted(ACTIVATION_KINDS))))
+    if kind == "leaky_relu":
+        return ACTIVATION_KINDS[kind], float(LEAKY_RELU_DEFAULT_SLOPE if param is None else param)
+    if param is not None:
+        raise TypeError("activation %r takes no param" % kind)
+    return ACTIVATION_KINDS[kind], 0.0
+
+
+class Activation(Weightless):
+    """Quantized activation `y = self.act1(x)` (additive, not in the reference): a layer without weights.
+
+    kind: "relu6", "leaky_relu" (param: the slope, default 0.01), "hardsigmoid", "hardswish", "sigmoid" or "tanh".  FP32
+    tensors go through f in FP32 (sampled by the calibrator while preparing, as a layer's FP32 output is); uint8 tensors,
+    after convert(), through one 256-entry table from the input tensor's (scale, zero_point) to this layer's own output
+    (scale, zero_point), by the arithmetic of include/i8ie_hip.h (i8ie_activation_table)."""
+
+    def __init__(self, kind, param=None):
+        self.kind = kind
+        code, self.param = activation_kind(kind, param)
+        self.layer = _C.Activation(code, self.param)
+
+    def __call__(self, x):
+        return Tensor(self.layer(x.data))

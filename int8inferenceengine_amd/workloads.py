@@ -19,7 +19,8 @@ import numpy as np
 #            | ("branch", tag, [ops...])  run ops on saved[tag] and store the result back under `tag` (projection shortcut)
 #            | ("avgpool", k, s)          i8ie.avg_pool2d(x, k, s)
 #            | ("gap",)                   i8ie.global_avg_pool2d(x)
-#            | ("concat", attr, [tags])   x = getattr(net, attr)([x] + [saved[t] for t in tags]); attr names an i8ie.Concat]
+#            | ("concat", attr, [tags])   x = getattr(net, attr)([x] + [saved[t] for t in tags]); attr names an i8ie.Concat
+#            | ("act", attr, kind[, param])  x = getattr(net, attr)(x); attr names an i8ie.Activation(kind, param)]
 NETWORKS = {
     # sample/notebooks/AlexNet_cifar10_resize224.ipynb:47-71
     "alexnet": (
@@ -166,6 +167,69 @@ NETWORKS["fire_tiny"] = _fire_tiny()
 NETWORKS["squeezenet_cifar"] = _squeezenet_cifar()
 
 
+def _inverted_residual(layers, spec, p, in_c, out_c, t, stride):
+    """An inverted residual block (Sandler et al. 2018, figure 3b): 1x1 expansion by t + relu6 (left out at t = 1), depthwise
+    3x3 + relu6, linear 1x1 projection; a residual Add around it where the stride is 1 and the channel counts agree."""
+    mid = in_c * t
+    skip = stride == 1 and in_c == out_c
+    if skip:
+        spec.append(("save", p))
+    if t != 1:
+        layers[p + "e"] = ("conv", in_c, mid, 1, 1, 0)
+        spec += [("layer", p + "e"), ("act", p + "ea", "relu6")]
+    layers[p + "d"] = ("conv", mid, mid, 3, stride, 1, mid)
+    layers[p + "p"] = ("conv", mid, out_c, 1, 1, 0)
+    spec += [("layer", p + "d"), ("act", p + "da", "relu6"), ("layer", p + "p")]
+    if skip:
+        spec.append(("add", p + "add", p))
+    return out_c
+
+
+def _mobilenetv2_tiny():
+    """A MobileNetV2 in small: a 3x3 stem, three inverted residual blocks (two with their Add, one at stride 2), a 1x1 head,
+    global average pool, fc.  What the Activation exists for: every non-linearity is a relu6."""
+    layers = {"stem": ("conv", 3, 16, 3, 1, 1)}
+    spec = [("layer", "stem"), ("act", "stema", "relu6")]
+    c = _inverted_residual(layers, spec, "b1", 16, 16, 2, 1)
+    c = _inverted_residual(layers, spec, "b2", c, 24, 2, 2)
+    c = _inverted_residual(layers, spec, "b3", c, 24, 4, 1)
+    layers["head"] = ("conv", c, 64, 1, 1, 0)
+    layers["fc"] = ("fc", 64, 10)
+    spec += [("layer", "head"), ("act", "heada", "relu6"), ("gap",), ("flatten", 64), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+def _act_tiny():
+    """Every other kind of Activation, and every lane width of its kernel (16, 20 and 35 channels), in one network."""
+    layers = {"c1": ("conv", 3, 16, 3, 1, 1), "c2": ("conv", 16, 20, 3, 2, 1), "c3": ("conv", 20, 35, 1, 1, 0),
+              "c4": ("conv", 35, 16, 1, 1, 0), "c5": ("conv", 16, 16, 3, 1, 1), "fc": ("fc", 16, 10)}
+    spec = [("layer", "c1"), ("act", "a1", "hardswish"), ("layer", "c2"), ("act", "a2", "leaky_relu", 0.1),
+            ("layer", "c3"), ("act", "a3", "hardsigmoid"), ("layer", "c4"), ("act", "a4", "sigmoid"),
+            ("layer", "c5"), ("act", "a5", "tanh"), ("gap",), ("flatten", 16), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+def _mobilenetv2_cifar():
+    """MobileNetV2 at width 1.0 (Sandler et al. 2018, table 2) for CIFAR-10: the stem and the second stage at stride 1 for
+    32x32 input, head 1x1 320 -> 1280, global average pool, fc 1280 -> 10."""
+    layers = {"stem": ("conv", 3, 32, 3, 1, 1)}
+    spec = [("layer", "stem"), ("act", "stema", "relu6")]
+    c = 32
+    for stage, (t, out_c, n, s) in enumerate(((1, 16, 1, 1), (6, 24, 2, 1), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1),
+                                              (6, 160, 3, 2), (6, 320, 1, 1)), start=1):
+        for block in range(1, n + 1):
+            c = _inverted_residual(layers, spec, "s%db%d" % (stage, block), c, out_c, t, s if block == 1 else 1)
+    layers["head"] = ("conv", c, 1280, 1, 1, 0)
+    layers["fc"] = ("fc", 1280, 10)
+    spec += [("layer", "head"), ("act", "heada", "relu6"), ("gap",), ("flatten", 1280), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+NETWORKS["mobilenetv2_tiny"] = _mobilenetv2_tiny()
+NETWORKS["act_tiny"] = _act_tiny()
+NETWORKS["mobilenetv2_cifar"] = _mobilenetv2_cifar()
+
+
 def _walk(spec):
     """every op of a spec in order, the ops inside ("branch", tag, [ops]) included"""
     for op in spec:
@@ -201,6 +265,7 @@ def macs_per_image(name):
             h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
         elif op[0] == "gap":
             h, w = 1, 1
+        # ("act", ...), like relu, add and concat, has no MACs and keeps the shape
     return total
 
 
@@ -243,6 +308,8 @@ def build(name):
                     setattr(self, op[1], i8ie.Add())
                 elif op[0] == "concat":
                     setattr(self, op[1], i8ie.Concat())
+                elif op[0] == "act":
+                    setattr(self, op[1], i8ie.Activation(op[2], op[3] if len(op) > 3 else None))
             for attr, L in layers.items():
                 if L[0] == "conv":
                     if conv_groups(L) == 1:
@@ -272,6 +339,8 @@ def build(name):
                     x = getattr(self, op[1])(x, saved[op[2]])
                 elif op[0] == "concat":
                     x = getattr(self, op[1])([x] + [saved[t] for t in op[2]])
+                elif op[0] == "act":
+                    x = getattr(self, op[1])(x)
                 else:
                     x = x.reshape(-1, op[1])
             return x
@@ -312,3 +381,8 @@ def add_names(name):
 def concat_names(name):
     """the Concats of a network, in spec order"""
     return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "concat"]
+
+
+def activation_names(name):
+    """the Activations of a network, in spec order"""
+    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "act"]
