@@ -445,6 +445,40 @@ int i8ie_add_u8_nhwc(i8ie_ctx* ctx, const uint8_t* a_dev, int a_border, int a_s8
  * 16-byte aligned buffers; out may alias a or b. */
 int i8ie_add_f32(i8ie_ctx* ctx, const float* a_dev, const float* b_dev, float* out_dev, int64_t n);
 
+/* ---- quantized broadcast Mul (no counterpart in the reference: it has no op that joins two tensors) ----------
+ * Defined as the Add is, as a composition of the reference's own expressions -- dequantize (src/quantize_utils.cc:38-42)
+ * of both operands, down_scale's clamp and truncation (src/quantize_utils.cc:27-36), relu<u8> (src/functional.cc:15-26)
+ * -- in IEEE fp32, one rounding per operation, no contraction:
+ *     fa = (float)((int)a - (int)zp_a) * s_a;   fb = (float)((int)b - (int)zp_b) * s_b
+ *     t  = (fa * fb) / s_out + (float)zp_out
+ *     q  = t >= 255 ? 255 : (t < 0 ? 0 : (u8)t)          truncation toward zero
+ *     q  = relu ? max(q, zp_out) : q
+ * b has a's shape, or is a gate: for a of shape [n, c, h, w] one byte per image and channel ([n, c, 1, 1] or [n, c]),
+ * multiplied into every pixel of that image (the excitation of a squeeze-and-excitation block).  Only the second operand
+ * broadcasts; the result has a's shape and its own (s_out, zp_out).  The bytes equal that sequence for every input
+ * pair, whichever way the kernel evaluates it (csrc/i8ie_mul.hip).  Scales must be finite and
+ * s_out > 0 (I8IE_ERR_ARG otherwise, like every other argument error before any device call).  Stateless and
+ * capturable in a graph.
+ * i8ie_mul_u8: n bytes of each operand in one physical order (NCHW, [m, k] rows, border-free NHWC); 16-byte aligned
+ * buffers; out may alias a or b, and a may be b. */
+int i8ie_mul_u8(i8ie_ctx* ctx, const uint8_t* a_dev, const uint8_t* b_dev, uint8_t* out_dev, int64_t n, float s_a,
+                uint8_t zp_a, float s_b, uint8_t zp_b, float s_out, uint8_t zp_out, int relu);
+/* The same arithmetic on NHWC buffers: a and out [n, h+2b, w+2b, c], each with its own border b and each plain
+ * (x_s8 = 0) or re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80).  b_gate = 0: b is a third such buffer.
+ * b_gate != 0: b is the gate, c bytes per image, read as its producer left it: [n, 1+2b, 1+2b, c] with its own border
+ * and re-bias flag (plain [n, c] rows are b_border = 0, b_s8 = 0).  Only the interior of `out` is written: its border
+ * bytes are the caller's and must hold zp_out (zp_out ^ 0x80 when out_s8), as i8ie_fill_border_u8 leaves them.  Any c
+ * (16 / 4 / 1 bytes per lane by c % 16, c % 4 and the pointers' alignment).  With equal shapes and all three borders 0
+ * this is the flat form (and out may alias an operand); otherwise out must not overlap a or b. */
+int i8ie_mul_u8_nhwc(i8ie_ctx* ctx, const uint8_t* a_dev, int a_border, int a_s8, const uint8_t* b_dev, int b_border,
+                     int b_s8, int b_gate, uint8_t* out_dev, int out_border, int out_s8, int n, int c, int h, int w,
+                     float s_a, uint8_t zp_a, float s_b, uint8_t zp_b, float s_out, uint8_t zp_out, int relu);
+/* out = a * b in fp32, one rounding (no reference counterpart): the Mul before convert() and while calibrating.  n
+ * elements of a and out.  gate_run = 0: b has n elements too; 16-byte aligned buffers; out may alias a or b.
+ * gate_run > 0 (it must divide n): b has n / gate_run elements and out[i] = a[i] * b[i / gate_run] -- NCHW tensors with
+ * gate_run = h * w; b 4-byte aligned; out may alias a. */
+int i8ie_mul_f32(i8ie_ctx* ctx, const float* a_dev, const float* b_dev, float* out_dev, int64_t n, int64_t gate_run);
+
 /* ---- quantized average pooling (no counterpart in the reference) -----------------------------------------------
  * Everything but the reduction follows max_pool2d<u8_t> (src/functional.cc:36-64): NCHW logical shape, window
  * kernel_h x kernel_w, one stride, floor output size (h - kernel_h) / stride + 1 by (w - kernel_w) / stride + 1, no

@@ -819,6 +819,114 @@ Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
       }, {a.pend, b.pend});
   return out;
 }
+// ---- mul (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_mul_u8) ----------------------------
+// b has a's shape (false), or is a gate [n, c, 1, 1] / [n, c] of a rank-4 a (true); anything else is a RuntimeError
+// (before any device call).  Only the second operand broadcasts.
+template <typename T>
+bool mul_is_gate(const Tensor<T>& a, const Tensor<T>& b) {
+  if (a.shape.size() != 2 && a.shape.size() != 4) throw std::runtime_error("i8ie: mul: the first operand must be [n, c, h, w] or [m, f]");
+  for (ssize_t d : a.shape)
+    if (d <= 0) throw std::runtime_error("i8ie: mul: empty tensor");
+  if (a.shape == b.shape) return false;
+  const bool gate = a.shape.size() == 4 && b.shape.size() >= 2 && b.shape[0] == a.shape[0] && b.shape[1] == a.shape[1] &&
+                    (b.shape.size() == 2 || (b.shape.size() == 4 && b.shape[2] == 1 && b.shape[3] == 1));
+  if (!gate)
+    throw std::runtime_error("i8ie: mul: the second operand must have the first one's shape or be its gate [n, c, 1, 1] / [n, c] "
+                             "(no other broadcasting)");
+  return true;
+}
+Tensor<float> mul_f32(Tensor<float>& a, Tensor<float>& b) {
+  const bool gate = mul_is_gate(a, b);
+  Tensor<float> out(a.shape);
+  check(i8ie_mul_f32(ctx(), a.dptr(), b.dptr(), out.dptr(), a.size, gate ? (int64_t)(a.shape[2] * a.shape[3]) : 0));
+  return out;
+}
+Tensor<u8_t> mul_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
+  const bool gate = mul_is_gate(a, b);
+  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error("i8ie: mul: the output scale must be positive and finite");
+  if (!std::isfinite(a.scale) || !std::isfinite(b.scale)) throw std::runtime_error("i8ie: mul: an operand's scale is not finite");
+  if ((!a.st && !a.pend) || (!b.st && !b.pend)) throw std::runtime_error("i8ie: empty tensor");
+  Tensor<u8_t> out;
+  out.shape = a.shape;
+  out.size = a.size;
+  out.scale = scale;
+  out.zero_point = (u8_t)zp;
+  Tensor<u8_t> ta = a, tb = b;  // share the operands' storage / pending launches
+  const float s_a = a.scale, s_b = b.scale;
+  const u8_t zp_a = a.zero_point, zp_b = b.zero_point, zp_o = (u8_t)zp;
+  const std::vector<ssize_t> shp = a.shape;
+  const ssize_t n = a.size;
+  // deferred like add's result: relu(mul(..)) is one launch, and a consuming conv gets its zero-point border and, where it
+  // reads them, re-biased bytes straight from the mul kernel
+  out.pend = make_pend(
+      [ta, tb, gate, s_a, s_b, zp_a, zp_b, scale, zp_o, shp, n](bool relu, int border, bool s8) mutable {
+        // b = f(a) still pending (the gate of a squeeze-and-excitation block is): launching b first launches a for f, and a
+        // is then read as it lies.  And the other way round.
+        const bool b_first = ta.pend && tb.pend && ta.pend != tb.pend && tb.pend->made.empty() && tb.pend->reads(ta.pend.get());
+        std::shared_ptr<Storage> sa, sb;
+        if (b_first) {
+          sb = add_operand(tb);
+          sa = add_operand(ta);
+        } else {
+          sa = add_operand(ta);
+          sb = add_operand(tb);
+        }
+        const bool four = shp.size() == 4;
+        auto is_nhwc_of = [](const Storage& x, ssize_t dn, ssize_t dc, ssize_t dh, ssize_t dw) {
+          return x.layout == I8IE_LAYOUT_NHWC && x.dn == dn && x.dc == dc && x.dh == dh && x.dw == dw;
+        };
+        std::shared_ptr<Storage> tmp;  // an NCHW operand converted for this launch
+        auto to_nhwc = [&](std::shared_ptr<Storage>& s) {
+          tmp = device_storage((size_t)n);
+          tmp->set_nhwc(shp, 0);
+          check(i8ie_layout_convert_u8(ctx(), (const uint8_t*)s->device_ptr(), (uint8_t*)tmp->dev, (int)shp[0], (int)shp[1], (int)shp[2],
+                                       (int)shp[3], 1, 0, 0));
+          s = tmp;
+        };
+        std::shared_ptr<Storage> st;
+        if (gate) {
+          // a in the engine's layout (a view whose storage is NHWC under other logical dims goes back to the reference's
+          // order first; a user-made NCHW tensor takes one layout conversion)
+          if (sa->layout == I8IE_LAYOUT_NHWC && !is_nhwc_of(*sa, shp[0], shp[1], shp[2], shp[3])) sa->to_nchw();
+          if (sa->layout == I8IE_LAYOUT_NCHW) to_nhwc(sa);
+          // the gate as its producer left it: an [n, c, 1, 1] NHWC buffer with its border and re-bias, or plain rows (an
+          // NCHW [n, c, 1, 1] tensor is the same bytes)
+          if (!is_nhwc_of(*sb, shp[0], shp[1], 1, 1)) sb->to_nchw();
+          const bool g_nhwc = sb->layout == I8IE_LAYOUT_NHWC;
+          st = nhwc_storage(shp, border, zp_o, s8);
+          check(i8ie_mul_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
+                                 g_nhwc ? sb->border : 0, g_nhwc && sb->s8 ? 1 : 0, 1, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0,
+                                 (int)shp[0], (int)shp[1], (int)shp[2], (int)shp[3], s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
+          return st;
+        }
+        auto same_nhwc = [](const Storage& x, const Storage& y) {
+          return x.dn == y.dn && x.dc == y.dc && x.dh == y.dh && x.dw == y.dw;
+        };
+        if (sa->layout != sb->layout || (sa->layout == I8IE_LAYOUT_NHWC && !same_nhwc(*sa, *sb))) {
+          if (four) {  // the engine keeps NHWC between layers (and a consumer that asked for a border reads NHWC)
+            to_nhwc(sa->layout == I8IE_LAYOUT_NCHW ? sa : sb);
+          } else {  // a flattened NHWC activation against plain rows: back to the reference's order
+            sa->to_nchw();
+            sb->to_nchw();
+          }
+        }
+        if (sa->layout == I8IE_LAYOUT_NHWC) {
+          const std::vector<ssize_t> lshp = {sa->dn, sa->dc, sa->dh, sa->dw};
+          st = nhwc_storage(lshp, four ? border : 0, zp_o, s8);
+          check(i8ie_mul_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
+                                 sb->border, sb->s8 ? 1 : 0, 0, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, sa->dn, sa->dc, sa->dh,
+                                 sa->dw, s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
+        } else {
+          st = device_storage((size_t)n);
+          check(i8ie_mul_u8(ctx(), (const uint8_t*)sa->device_ptr(), (const uint8_t*)sb->device_ptr(), (uint8_t*)st->dev, (int64_t)n,
+                            s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
+        }
+        // (the operands are released with the closure's copies, as a layer's input is)
+        return st;
+      }, {a.pend, b.pend});
+  return out;
+}
 // ---- cat (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_concat_u8) --------------------------
 // axis 1 of k rank-4 [n, c_i, h, w] or k rank-2 [m, f_i] tensors: the result's shape, or a RuntimeError (before any device call)
 template <typename T>
@@ -1716,6 +1824,16 @@ class Add : public Weightless {
     return add_u8(a, b, scale_, zero_point_);
   }
 };
+// a * b; b has a's shape or is a's gate [n, c, 1, 1] / [n, c]
+class Mul : public Weightless {
+ public:
+  Tensor<float> forward_f32(Tensor<float>& a, Tensor<float>& b) { return sampled(mul_f32(a, b)); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& a, Tensor<u8_t>& b) {
+    mul_is_gate(a, b);
+    need_quantized("Mul");
+    return mul_u8(a, b, scale_, zero_point_);
+  }
+};
 // cat along axis 1: a list of FP32 tensors before convert(), of u8 tensors after it
 class Concat : public Weightless {
  public:
@@ -1821,6 +1939,9 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
   // additive (the reference joins no two tensors): a + b in FP32; the quantized Add of include/i8ie_hip.h on u8 tensors
   m.def("add", &add_f32, py::arg("a"), py::arg("b"));
   m.def("add", &add_u8, py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("zero_point"));
+  // additive: a * b in FP32; the quantized Mul of include/i8ie_hip.h on u8 tensors.  b has a's shape or is a's gate
+  m.def("mul", &mul_f32, py::arg("a"), py::arg("b"));
+  m.def("mul", &mul_u8, py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("zero_point"));
   // additive: cat along axis 1 of up to 8 tensors, a copy in FP32; the quantized concat of include/i8ie_hip.h on u8 tensors
   m.def("cat", [](const py::list& tensors) { return cat_f32(cat_list<float>(tensors)); }, py::arg("tensors"));
   m.def("cat", [](const py::list& tensors, float scale, int zp) { return cat_u8(cat_list<u8_t>(tensors), scale, zp); },
@@ -1870,6 +1991,11 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
     py::class_<Add> c(m, "Add");
     bind_weightless_common(c);
     c.def("__call__", &Add::forward_f32).def("__call__", &Add::forward_u8);
+  }
+  {
+    py::class_<Mul> c(m, "Mul");
+    bind_weightless_common(c);
+    c.def("__call__", &Mul::forward_f32).def("__call__", &Mul::forward_u8);
   }
   {
     py::class_<Concat> c(m, "Concat");

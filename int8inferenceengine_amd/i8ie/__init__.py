@@ -7,7 +7,7 @@ device-resident and `.numpy()` copies back to the host.
 """
 import _CXX_i8ie as _C
 
-from .layer import Activation, Add, Concat, Conv2d, Layer, Linear, activation_kind
+from .layer import Activation, Add, Concat, Conv2d, Layer, Linear, Mul, activation_kind
 from .module import Module
 from .tensor import Tensor
 
@@ -15,7 +15,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
-    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d",
+    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -59,6 +59,21 @@ def add(a, b, scale=None, zero_point=None):
     if scale is not None or zero_point is not None:
         raise TypeError("add of FP32 tensors takes no scale / zero_point")
     return Tensor(_C.add(a.data, b.data))
+
+
+def mul(a, b, scale=None, zero_point=None):
+    """a * b.  `b` has `a`'s shape, or is a gate of an [n, c, h, w] `a`: [n, c, 1, 1] or [n, c], one value per image and
+    channel (only the second operand broadcasts; anything else raises RuntimeError).  FP32 tensors: plain fp32 product,
+    `scale` / `zero_point` must not be given.  uint8 tensors: the quantized multiply of include/i8ie_hip.h (i8ie_mul_u8);
+    the result's `scale` and `zero_point` are required.  `i8ie.Mul` is the calibrated form for use inside a Module."""
+    quantized = type(a.data).__name__ == "6TensorIhE"
+    if quantized:
+        if scale is None or zero_point is None:
+            raise TypeError("mul of uint8 tensors needs the result's scale and zero_point")
+        return Tensor(_C.mul(a.data, b.data, float(scale), int(zero_point)))
+    if scale is not None or zero_point is not None:
+        raise TypeError("mul of FP32 tensors takes no scale / zero_point")
+    return Tensor(_C.mul(a.data, b.data))
 
 
 def cat(tensors, scale=None, zero_point=None):

@@ -72,7 +72,7 @@ class Conv2d(Layer):
 
 
 class Weightless(Layer):
-    """Common behaviour of the layers without weights (Add, Concat, Activation): `self.layer` has only the prepare / convert state
+    """Common behaviour of the layers without weights (Add, Mul, Concat, Activation): `self.layer` has only the prepare / convert state
     machine around an output (scale, zero_point).  Takes part in Module.prepare() / convert() / quantized_state_dict()
     (`<attr>.qparams` only); Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values);
     load_weight, load_bias, weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
@@ -99,6 +99,21 @@ class Add(Weightless):
 
     def __init__(self):
         self.layer = _C.Add()
+
+    def __call__(self, a, b):
+        return Tensor(self.layer(a.data, b.data))
+
+
+class Mul(Weightless):
+    """Quantized broadcast multiply `y = self.mul1(x, g)` (additive, not in the reference): a layer without weights.
+
+    `g` has `x`'s shape, or is a gate of an [n, c, h, w] `x`: one value per image and channel, [n, c, 1, 1] or [n, c], as a
+    squeeze-and-excitation block makes it.  Only the second operand broadcasts.  FP32 tensors multiply in FP32 (sampled by
+    the calibrator while preparing, as a layer's FP32 output is); uint8 tensors, after convert(), by the arithmetic of
+    include/i8ie_hip.h (i8ie_mul_u8) with this Mul's output (scale, zero_point)."""
+
+    def __init__(self):
+        self.layer = _C.Mul()
 
     def __call__(self, a, b):
         return Tensor(self.layer(a.data, b.data))

@@ -51,7 +51,7 @@ class Module:
     def quantized_state_dict(self):
         """{'<attr>.q_weight' int8, '<attr>.q_bias' int8, '<attr>.qparams' float64[3] =
         (weight_scale, out_scale, out_zero_point)} for every converted layer; a per-channel layer also has
-        '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused).  An Add, a Concat or an Activation contributes only
+        '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused).  An Add, a Mul, a Concat or an Activation contributes only
         '<attr>.qparams' = (0, out_scale, out_zero_point)."""
         import numpy as np
 

@@ -20,7 +20,9 @@ import numpy as np
 #            | ("avgpool", k, s)          i8ie.avg_pool2d(x, k, s)
 #            | ("gap",)                   i8ie.global_avg_pool2d(x)
 #            | ("concat", attr, [tags])   x = getattr(net, attr)([x] + [saved[t] for t in tags]); attr names an i8ie.Concat
-#            | ("act", attr, kind[, param])  x = getattr(net, attr)(x); attr names an i8ie.Activation(kind, param)]
+#            | ("act", attr, kind[, param])  x = getattr(net, attr)(x); attr names an i8ie.Activation(kind, param)
+#            | ("mul", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Mul; saved[tag] has x's
+#                                         shape or is its gate [n, c] (the branch of a squeeze-and-excitation block)]
 NETWORKS = {
     # sample/notebooks/AlexNet_cifar10_resize224.ipynb:47-71
     "alexnet": (
@@ -225,9 +227,82 @@ def _mobilenetv2_cifar():
     return layers, spec, (3, 32, 32)
 
 
+def make_divisible(v, divisor=8):
+    """the channel rounding of the MobileNet family: to the nearest multiple of `divisor`, at least `divisor`, never more
+    than 10 % below v"""
+    new_v = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    return new_v + divisor if new_v < 0.9 * v else new_v
+
+
+def _squeeze_excite(layers, spec, p, c, squeeze):
+    """A squeeze-and-excitation block (Hu et al. 2018, with MobileNetV3's hardsigmoid): the current [n, c, h, w] tensor times
+    a gate of one value per image and channel, made from its global average by two Linears.  What the Mul exists for."""
+    layers[p + "fc1"] = ("fc", c, squeeze)
+    layers[p + "fc2"] = ("fc", squeeze, c)
+    spec += [("save", p), ("branch", p, [("gap",), ("flatten", c), ("layer", p + "fc1"), ("relu",), ("layer", p + "fc2"),
+                                         ("act", p + "hs", "hardsigmoid")]), ("mul", p + "mul", p)]
+
+
+def _se_tiny():
+    """Every form of the Mul in one network: squeeze-and-excitation at 16, 20 and 35 channels (16-, 4- and 1-byte items of
+    its kernel), the first feeding a 3x3 pad-1 conv, and the product of two conv outputs of one shape, followed by a relu and
+    a 3x3 pad-1 conv."""
+    layers = {"c1": ("conv", 3, 16, 3, 1, 1), "c2": ("conv", 16, 20, 3, 2, 1), "c3": ("conv", 20, 35, 1, 1, 0),
+              "c4a": ("conv", 35, 16, 1, 1, 0), "c4b": ("conv", 35, 16, 3, 1, 1), "c5": ("conv", 16, 16, 3, 1, 1), "fc": ("fc", 16, 10)}
+    spec = [("layer", "c1"), ("act", "a1", "hardswish")]
+    _squeeze_excite(layers, spec, "s1", 16, 8)
+    spec += [("layer", "c2"), ("act", "a2", "hardswish")]
+    _squeeze_excite(layers, spec, "s2", 20, 8)
+    spec += [("layer", "c3"), ("relu",)]
+    _squeeze_excite(layers, spec, "s3", 35, 12)
+    spec += [("save", "m"), ("layer", "c4a"), ("branch", "m", [("layer", "c4b")]), ("mul", "mab", "m"),
+             ("relu",), ("layer", "c5"), ("relu",), ("gap",), ("flatten", 16), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+def _mobilenetv3_small_cifar():
+    """MobileNetV3-small (Howard et al. 2019, table 2) for CIFAR-10, with torchvision's squeeze-and-excitation: behind the
+    depthwise activation, squeeze width make_divisible(exp / 4, 8), none on the last 1x1 conv.  The stem and the first block
+    run at stride 1 for 32x32 input (the first block then has a residual Add); head 1x1 -> 576 with hardswish, global
+    average pool, fc 576 -> 1024 with hardswish, fc 1024 -> 10."""
+    layers = {"stem": ("conv", 3, 16, 3, 1, 1)}
+    spec = [("layer", "stem"), ("act", "stema", "hardswish")]
+    c = 16
+    #        k  exp  out  SE     HS     stride
+    table = [(3, 16, 16, True, False, 1), (3, 72, 24, False, False, 2), (3, 88, 24, False, False, 1), (5, 96, 40, True, True, 2),
+             (5, 240, 40, True, True, 1), (5, 240, 40, True, True, 1), (5, 120, 48, True, True, 1), (5, 144, 48, True, True, 1),
+             (5, 288, 96, True, True, 2), (5, 576, 96, True, True, 1), (5, 576, 96, True, True, 1)]
+    for i, (k, exp, out_c, se, hs, stride) in enumerate(table, start=1):
+        p = "b%d" % i
+        act = (lambda a: ("act", a, "hardswish")) if hs else (lambda a: ("relu",))
+        skip = stride == 1 and c == out_c
+        if skip:
+            spec.append(("save", p))
+        if exp != c:
+            layers[p + "e"] = ("conv", c, exp, 1, 1, 0)
+            spec += [("layer", p + "e"), act(p + "ea")]
+        layers[p + "d"] = ("conv", exp, exp, k, stride, k // 2, exp)
+        spec += [("layer", p + "d"), act(p + "da")]
+        if se:
+            _squeeze_excite(layers, spec, p + "se", exp, make_divisible(exp / 4, 8))
+        layers[p + "p"] = ("conv", exp, out_c, 1, 1, 0)
+        spec.append(("layer", p + "p"))
+        if skip:
+            spec.append(("add", p + "add", p))
+        c = out_c
+    layers["head"] = ("conv", c, 576, 1, 1, 0)
+    layers["fc1"] = ("fc", 576, 1024)
+    layers["fc2"] = ("fc", 1024, 10)
+    spec += [("layer", "head"), ("act", "heada", "hardswish"), ("gap",), ("flatten", 576), ("layer", "fc1"),
+             ("act", "fc1a", "hardswish"), ("layer", "fc2")]
+    return layers, spec, (3, 32, 32)
+
+
 NETWORKS["mobilenetv2_tiny"] = _mobilenetv2_tiny()
 NETWORKS["act_tiny"] = _act_tiny()
 NETWORKS["mobilenetv2_cifar"] = _mobilenetv2_cifar()
+NETWORKS["se_tiny"] = _se_tiny()
+NETWORKS["mobilenetv3_small_cifar"] = _mobilenetv3_small_cifar()
 
 
 def _walk(spec):
@@ -265,7 +340,11 @@ def macs_per_image(name):
             h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
         elif op[0] == "gap":
             h, w = 1, 1
-        # ("act", ...), like relu, add and concat, has no MACs and keeps the shape
+        elif op[0] == "branch":
+            # the Linears of a squeeze-and-excitation branch.  (the convs of a branch -- projection shortcuts, fire expands --
+            # have never been counted, and the figures of those networks are pinned: they stay as they are)
+            total += sum(layers[b[1]][1] * layers[b[1]][2] for b in _walk(op[2]) if b[0] == "layer" and layers[b[1]][0] == "fc")
+        # ("act", ...), like relu, add, mul and concat, has no MACs and keeps the shape
     return total
 
 
@@ -306,6 +385,8 @@ def build(name):
             for op in _walk(spec):
                 if op[0] == "add":
                     setattr(self, op[1], i8ie.Add())
+                elif op[0] == "mul":
+                    setattr(self, op[1], i8ie.Mul())
                 elif op[0] == "concat":
                     setattr(self, op[1], i8ie.Concat())
                 elif op[0] == "act":
@@ -335,7 +416,7 @@ def build(name):
                     saved[op[1]] = x
                 elif op[0] == "branch":
                     saved[op[1]] = self.run(op[2], saved[op[1]], saved)
-                elif op[0] == "add":
+                elif op[0] in ("add", "mul"):
                     x = getattr(self, op[1])(x, saved[op[2]])
                 elif op[0] == "concat":
                     x = getattr(self, op[1])([x] + [saved[t] for t in op[2]])
@@ -376,6 +457,11 @@ def layer_names(name):
 def add_names(name):
     """the Adds of a residual network, in spec order"""
     return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "add"]
+
+
+def mul_names(name):
+    """the Muls of a network, in spec order"""
+    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "mul"]
 
 
 def concat_names(name):
