@@ -236,6 +236,16 @@ int i8ie_conv2d_f32(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int
 int i8ie_conv2d_f32_grouped(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int w,
                             const float* w_dev, const float* b_dev, int kc, int kh, int kw, int stride,
                             int pad, int groups, float* out_dev);
+/* ConvTranspose2d in FP32 (not in the reference; the definition of torch.nn.ConvTranspose2d with groups = 1,
+ * dilation = 1, a square kernel): out[n, oc, iy*s - p + ky, ix*s - p + kx] += in[n, ic, iy, ix] * w[ic, oc, ky, kx], + b[oc].
+ * w_dev is [c, kc, k, k], out_dev [n, kc, oh, ow] with oh = (h - 1)*stride - 2*pad + k + output_pad.  stride >= 1,
+ * 0 <= pad <= k - 1, 0 <= output_pad < stride (I8IE_ERR_ARG otherwise, before any device call).  Equivalently
+ * src/conv2d.cc:63-98 (stride 1, padding 0) of the zero-inserted, padded input with the flipped, transposed kernel; the
+ * kernel sums only the taps that meet a real pixel, in (ic, ky, kx) order.  The path taken before convert() and while
+ * calibrating. */
+int i8ie_conv_transpose2d_f32(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int w,
+                              const float* w_dev, const float* b_dev, int kc, int k, int stride, int pad,
+                              int output_pad, float* out_dev);
 int i8ie_relu_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int64_t n);
 int i8ie_maxpool2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h,
                        int w, int kernel_size, int stride);
@@ -294,6 +304,16 @@ int i8ie_conv2d_u8s8_grouped(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c,
                              uint8_t zp_in, const int32_t* oc_dev, float s_in, float s_w, float s_out,
                              uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
 
+/* ConvTranspose2d in INT8: Conv2d::forward_prop(Tensor<u8>&&), src/conv2d.cc:100-142, of the equivalent problem (see
+ * i8ie_conv_transpose2d_create below); the layer itself: not in the reference.  qw_dev is the equivalent matrix
+ * [kc, c*k*k], oc_dev [kc] from i8ie_conv_offsets on that matrix (K = c*k*k, src/conv2d.cc:117-124).  out_dev is NCHW
+ * [n, kc, oh, ow], acc_dbg_dev NULL or int32 [n, oh*ow, kc]: the full-K sums including the inserted positions.  Reads the
+ * weights back and packs them for this one call (it waits for the stream): a layer handle keeps them packed. */
+int i8ie_conv_transpose2d_u8s8(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w,
+                               const int8_t* qw_dev, int kc, int k, int stride, int pad, int output_pad,
+                               uint8_t zp_in, const int32_t* oc_dev, float s_in, float s_w, float s_out,
+                               uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
+
 /* ---- layer handles: converted layers with device-resident packed weights -
  * What BaseLayer::convert() leaves behind (src/layer.cc:36-54: q_weight_,
  * q_bias_, scale_, zero_point_), kept on the device in MFMA operand order,
@@ -329,6 +349,27 @@ int i8ie_conv2d_create_grouped(i8ie_ctx* ctx, const int8_t* qw_host, const int8_
 int i8ie_conv2d_create_grouped_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc,
                                            int c, int kh, int kw, int stride, int pad, int groups,
                                            const float* s_w_host, i8ie_layer** out);
+/* ConvTranspose2d (torch.nn.ConvTranspose2d with a square kernel, groups = 1, dilation = 1; not in the reference).
+ * Nothing new is defined arithmetically: the layer IS src/conv2d.cc:100-142 (stride 1, padding 0) applied to
+ *   x~  the input with stride - 1 positions inserted between neighbouring pixels, padded by k - 1 - pad on top / left and
+ *       k - 1 - pad + output_pad on bottom / right, every inserted or padded position holding zp_in;
+ *   W~  [kc][c][k][k], W~[oc][ic][ky][kx] = W[ic][oc][k-1-ky][k-1-kx] for torch's weight W [c][kc][k][k].
+ * qw_host is W~ as the matrix [kc][c*k*k] (K ordered (ic, ky, kx)), qb_host [kc].  The offset vector is
+ * src/conv2d.cc:117-124 (i8ie_conv_offsets) on that matrix as it stands, the accumulators (acc_dbg) are the full-K sums
+ * including the positions that hold zp_in, the epilogue is down_scale (src/quantize_utils.cc:27-36).
+ * oh = (h - 1)*stride - 2*pad + k + output_pad.  stride >= 1, 0 <= pad <= k - 1, 0 <= output_pad < stride
+ * (I8IE_ERR_ARG otherwise, checked before any device call).
+ * Kernels (csrc/i8ie_deconv.hip; x~ is never built, an NHWC forward is one launch): deconv_mfma when
+ * c * ceil(k/stride)^2 >= 32 and I8IE_OPT_FORCE_FALLBACK is off, deconv_direct otherwise.
+ * A transposed handle supports i8ie_layer_forward, i8ie_layer_forward_fused and i8ie_layer_forward_pool, in every
+ * layout (NCHW, NHWC with any border, NHWC_S8 by converting around the kernel).  It folds nothing and answers as a
+ * grouped handle does: i8ie_layer_fuses_pool 0, i8ie_layer_rebiased_io 0 / 0, i8ie_layer_accepts_f32_input 0,
+ * i8ie_layer_padding 0 (it reads no border), and i8ie_layer_forward_dequant is for Linear layers only. */
+int i8ie_conv_transpose2d_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int k,
+                                 int stride, int pad, int output_pad, float s_w, i8ie_layer** out);
+int i8ie_conv_transpose2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc,
+                                             int c, int k, int stride, int pad, int output_pad,
+                                             const float* s_w_host, i8ie_layer** out);
 /* *groups = the layer's groups: 1 for Linear and for a dense Conv2d */
 int i8ie_layer_groups(const i8ie_layer* layer, int* groups);
 /* the weight scales: out float [n] (n = out features); a per-tensor layer gives n copies of its scale and

@@ -7,6 +7,7 @@
 // atol 0.1 against torch (unittest/test_layers.py:10-11), so summation order
 // is free here.
 #include "i8ie_internal.h"
+#include "i8ie_deconv.h"
 
 
 namespace {
@@ -248,6 +249,18 @@ int i8ie_conv2d_f32_grouped(i8ie_ctx* ctx, const float* in, int n, int c, int h,
   a.c = c / groups; a.h = h; a.wd = w; a.oh = oh; a.ow = ow; a.stride = stride; a.pad = pad; a.P = oh * ow;
   a.ctot = c; a.Ntot = kc;
   return launch_gemm_f32<true>(ctx, a, kh, kw, "conv2d_f32_mfma", groups);
+}
+
+// ConvTranspose2d in FP32 (not in the reference; torch.nn.functional.conv_transpose2d's definition): wt is [c][kc][k][k]
+int i8ie_conv_transpose2d_f32(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, const float* wt, const float* b,
+                              int kc, int k, int stride, int pad, int output_pad, float* out) {
+  I8IE_TRY(i8ie_deconv_check_args(kc, c, k, stride, pad, output_pad));
+  I8IE_REQUIRE(ctx && in && wt && b && out, "null argument");
+  I8IE_REQUIRE(n > 0 && h > 0 && w > 0, "non-positive dimension");
+  const int64_t oh = (int64_t)(h - 1) * stride - 2 * pad + k + output_pad, ow = (int64_t)(w - 1) * stride - 2 * pad + k + output_pad;
+  I8IE_REQUIRE(oh > 0 && ow > 0 && oh < (1 << 30) && ow < (1 << 30), "transposed conv: empty or oversized output");
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  return i8ie_deconv_f32_launch(ctx, in, n, c, h, w, wt, b, kc, k, stride, pad, (int)oh, (int)ow, out);
 }
 
 int i8ie_relu_f32(i8ie_ctx* ctx, const float* in, float* out, int64_t n) {

@@ -12,6 +12,8 @@
 //   F  anything else: materialised im2col + v1 GEMM (i8ie_gemm.hip)
 //   G  groups > 1 (i8ie_conv2d_create_grouped; not in the reference): one reference convolution per group, in the
 //      grouped kernels of i8ie_gconv.hip over NHWC activations
+//   T  ConvTranspose2d (i8ie_conv_transpose2d_create; not in the reference): the reference convolution of the equivalent
+//      zero-inserted problem, computed phase by phase in the kernels of i8ie_deconv.hip over NHWC activations
 // Activations cross the ABI as NCHW (the reference's layout) or, on request, as
 // NHWC so that consecutive layers skip the layout conversion.
 #include <cmath>
@@ -25,6 +27,7 @@
 #include "i8ie_stem.h"
 #include "i8ie_requant.h"
 #include "i8ie_gconv.h"
+#include "i8ie_deconv.h"
 
 namespace {
 
@@ -33,7 +36,7 @@ constexpr size_t kColBudget = (size_t)192 << 20;  // im2col scratch per chunk (f
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
 
-enum { PATH_F = 0, PATH_A = 1, PATH_B = 2, PATH_G = 3 };  // PATH_G: grouped (i8ie_gconv.hip)
+enum { PATH_F = 0, PATH_A = 1, PATH_B = 2, PATH_G = 3, PATH_T = 4 };  // PATH_G: grouped (i8ie_gconv.hip), PATH_T: transposed (i8ie_deconv.hip)
 
 struct ConvGeom {
   int c, h, w, kc, kh, kw, stride, pad, oh, ow, K, Kpad;
@@ -48,6 +51,19 @@ int conv_geom(int c, int h, int w, int kc, int kh, int kw, int stride, int pad, 
   g->oh = (h - kh + 2 * pad) / stride + 1;  // src/conv2d.cc:108-109
   g->ow = (w - kw + 2 * pad) / stride + 1;
   g->K = c * kh * kw;
+  g->Kpad = round_up(g->K, 128);
+  return I8IE_OK;
+}
+
+// ConvTranspose2d: kh = kw = k, OH = (H - 1) s - 2 p + k + output_padding (torch.nn.ConvTranspose2d)
+int deconv_geom(int c, int h, int w, int kc, int k, int stride, int pad, int opad, ConvGeom* g) {
+  I8IE_REQUIRE(c > 0 && h > 0 && w > 0 && kc > 0 && k > 0, "non-positive dimension");
+  g->c = c; g->h = h; g->w = w; g->kc = kc; g->kh = k; g->kw = k; g->stride = stride; g->pad = pad;
+  const long long oh = (long long)(h - 1) * stride - 2 * pad + k + opad, ow = (long long)(w - 1) * stride - 2 * pad + k + opad;
+  I8IE_REQUIRE(oh > 0 && ow > 0 && oh < (1 << 30) && ow < (1 << 30), "transposed conv: empty or oversized output");
+  g->oh = (int)oh;
+  g->ow = (int)ow;
+  g->K = c * k * k;
   g->Kpad = round_up(g->K, 128);
   return I8IE_OK;
 }
@@ -130,11 +146,16 @@ struct i8ie_layer {
   int8_t* Bpack = nullptr;  // [Npad][Kpad] zero padded, reference K order (Linear; conv path F)
   int8_t* Bperm = nullptr;  // Linear fed by an NHWC-flattened activation: Bpack with K reordered (h, w, c)
   int perm_c = 0, perm_hw = 0;
-  int path = PATH_F;        // conv: PATH_A / PATH_B / PATH_F / PATH_G
+  int path = PATH_F;        // conv: PATH_A / PATH_B / PATH_F / PATH_G / PATH_T
   int groups = 1;           // conv, groups > 1 (PATH_G): K above is the reduction length INSIDE a group, (c / groups) * kh * kw,
   int Ngp = 0, Kgp = 0;     // and the weights live in `wc` as [groups][Ngp][Kgp], K ordered (kh, kw, cg) (i8ie_gconv.h)
   int8_t* Bg = nullptr;
   int* gtab = nullptr;      // the MFMA kernel's gather table (i8ie_gconv_ktab), in `wc` as well
+  int opad = 0;             // ConvTranspose2d (PATH_T): output_padding; qw / K above are the EQUIVALENT matrix [n][c * k * k];
+  int Kpp = 0;              // the phase panels [stride^2][Ngp][Kpp], their gather table and the per-(phase, feature) sums of
+  int8_t* Bt = nullptr;     // the taps a phase does not see (i8ie_deconv.h), all three in `wc`
+  int* ttab = nullptr;
+  int32_t* tph = nullptr;
   int8_t* Bpack2 = nullptr; // conv paths A/B: [Npad][Kpad2], K ordered (kh, kw, c) / grouped
   int K2 = 0, Kpad2 = 0;    // valid / padded K of Bpack2 (bytes)
   I8ieWCache wc;            // Bpack2 in the fragment orders of i8ie_pconv.hip / i8ie_tconv.hip: one buffer per packing
@@ -290,7 +311,7 @@ int i8ie_conv2d_u8s8(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int 
 }
 
 static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const int8_t* qb_host, int n, int K, int c,
-                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups = 1);
+                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups = 1, int opad = -1);
 
 // the stateless form with groups (groups: not in the reference).  groups > 1 packs the weights for this one call: the
 // device weights are read back, a temporary layer handle runs the call with the caller's oc[] and is destroyed.
@@ -360,7 +381,7 @@ int i8ie_maxpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in, int in_border, uint
 
 // ---- layer handles ----------------------------------------------------------------------------
 static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const int8_t* qb_host, int n, int K, int c,
-                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups) {
+                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups, int opad) {
   I8IE_REQUIRE(ctx && qw_host && qb_host && out, "null argument");
   I8IE_REQUIRE(n > 0 && K > 0, "non-positive dimension");
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
@@ -372,8 +393,18 @@ static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const i
   L->Npad = round_up(n, 128);
   // MFMA-order weight panel for the implicit-GEMM conv paths, built on the host once
   std::vector<int8_t> pack2, packg;
-  std::vector<int> gtab;
-  if (conv && groups > 1) {
+  std::vector<int> gtab, ttab;
+  std::vector<int8_t> packt;
+  std::vector<int32_t> tph;
+  if (conv && opad >= 0) {
+    // transposed (opad: output_padding): qw_host is the equivalent matrix [n][c * k * k]
+    L->path = PATH_T;
+    L->opad = opad;
+    L->Ngp = round_up(n, 16);
+    L->Kpp = i8ie_deconv_kpitch(c, kh, stride);
+    i8ie_deconv_pack(qw_host, n, c, kh, stride, packt, tph);
+    i8ie_deconv_ktab(c, kh, stride, ttab);
+  } else if (conv && groups > 1) {
     // grouped: qw_host is [n][Cg * kh * kw]; group g's Ng rows go to panel g in (kh, kw, cg) order
     const int Cg = c / groups, Ng = n / groups;
     L->path = PATH_G;
@@ -447,6 +478,17 @@ static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const i
       if ((rc = i8ie_malloc(ctx, gtab.size() * 4, (void**)&L->gtab)) != I8IE_OK) break;
       L->wc.ents.push_back({0x6763000000000002ull, L->gtab});
       if ((rc = i8ie_memcpy_h2d(ctx, L->gtab, gtab.data(), gtab.size() * 4)) != I8IE_OK) break;
+    }
+    if (!packt.empty()) {  // (per packing key as well)
+      if ((rc = i8ie_malloc(ctx, packt.size(), (void**)&L->Bt)) != I8IE_OK) break;
+      L->wc.ents.push_back({0x6463000000000001ull, L->Bt});
+      if ((rc = i8ie_memcpy_h2d(ctx, L->Bt, packt.data(), packt.size())) != I8IE_OK) break;
+      if ((rc = i8ie_malloc(ctx, ttab.size() * 4, (void**)&L->ttab)) != I8IE_OK) break;
+      L->wc.ents.push_back({0x6463000000000002ull, L->ttab});
+      if ((rc = i8ie_memcpy_h2d(ctx, L->ttab, ttab.data(), ttab.size() * 4)) != I8IE_OK) break;
+      if ((rc = i8ie_malloc(ctx, tph.size() * 4, (void**)&L->tph)) != I8IE_OK) break;
+      L->wc.ents.push_back({0x6463000000000003ull, L->tph});
+      if ((rc = i8ie_memcpy_h2d(ctx, L->tph, tph.data(), tph.size() * 4)) != I8IE_OK) break;
     }
     if (!packs.empty()) {
       if ((rc = i8ie_malloc(ctx, packs.size(), (void**)&L->Bstem)) != I8IE_OK) break;
@@ -580,6 +622,58 @@ int i8ie_layer_groups(const i8ie_layer* L, int* groups) {
   return I8IE_OK;
 }
 
+// ConvTranspose2d: not in the reference (src/conv2d.cc:100-142 on the equivalent problem, include/i8ie_hip.h).  Argument
+// checks (i8ie_deconv_check_args) come before any device call.
+int i8ie_conv_transpose2d_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int k, int stride,
+                                 int pad, int output_pad, float s_w, i8ie_layer** out) {
+  I8IE_TRY(i8ie_deconv_check_args(kc, c, k, stride, pad, output_pad));
+  return layer_create(ctx, true, qw_host, qb_host, kc, c * k * k, c, k, k, stride, pad, s_w, out, 1, output_pad);
+}
+
+int i8ie_conv_transpose2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int k,
+                                             int stride, int pad, int output_pad, const float* s_w_host, i8ie_layer** out) {
+  I8IE_TRY(i8ie_deconv_check_args(kc, c, k, stride, pad, output_pad));
+  I8IE_REQUIRE(out != nullptr, "bad argument");
+  I8IE_TRY(check_scales(s_w_host, kc));
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_conv_transpose2d_create(ctx, qw_host, qb_host, kc, c, k, stride, pad, output_pad, 1.0f, &L));
+  const int rc = layer_make_per_channel(L, s_w_host);
+  if (rc != I8IE_OK) {
+    i8ie_layer_destroy(L);
+    return rc;
+  }
+  *out = L;
+  return I8IE_OK;
+}
+
+// the stateless form: qw is the equivalent matrix on the device; it is read back and packed for this one call (a temporary
+// layer handle runs the call with the caller's oc[] and is destroyed), as i8ie_conv2d_u8s8_grouped does
+int i8ie_conv_transpose2d_u8s8(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int k,
+                               int stride, int pad, int output_pad, uint8_t zp_in, const int32_t* oc, float s_in, float s_w,
+                               float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
+  I8IE_TRY(i8ie_deconv_check_args(kc, c, k, stride, pad, output_pad));
+  I8IE_REQUIRE(ctx && in && qw && oc && out, "null argument");
+  I8IE_REQUIRE(n > 0, "non-positive batch");
+  ConvGeom cg;
+  I8IE_TRY(deconv_geom(c, h, w, kc, k, stride, pad, output_pad, &cg));
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  std::vector<int8_t> qw_host((size_t)kc * cg.K), qb_host((size_t)kc, 0);
+  I8IE_TRY(i8ie_memcpy_d2h(ctx, qw_host.data(), qw, qw_host.size()));
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_conv_transpose2d_create(ctx, qw_host.data(), qb_host.data(), kc, c, k, stride, pad, output_pad, s_w, &L));
+  L->s_out = s_out;
+  L->zp_out = zp_out;
+  int rc = i8ie_launch_finish_offsets(ctx, oc, L->wsum, L->qb, s_in, kc, L->ocp, nullptr);
+  if (rc == I8IE_OK) {
+    L->oc_valid = true;
+    L->oc_s_in = s_in;
+    L->oc_zp_in = zp_in;
+    rc = i8ie_layer_forward(L, in, n, h, w, s_in, zp_in, out, acc);
+  }
+  i8ie_layer_destroy(L);
+  return rc;
+}
+
 int i8ie_layer_set_output_qparams(i8ie_layer* L, float s_out, uint8_t zp_out) {
   I8IE_REQUIRE(L != nullptr, "null layer");
   L->s_out = s_out;
@@ -604,7 +698,7 @@ int i8ie_layer_preferred_layout(const i8ie_layer* L, int* layout) {
 
 int i8ie_layer_padding(const i8ie_layer* L, int* pad) {
   I8IE_REQUIRE(L && pad, "null argument");
-  *pad = L->conv ? L->pad : 0;
+  *pad = (L->conv && L->path != PATH_T) ? L->pad : 0;  // (a transposed layer reads no border)
   return I8IE_OK;
 }
 
@@ -662,6 +756,30 @@ static bool pconv_probe(i8ie_layer* L, const ConvGeom& cg, int m, int in_border,
   q.a_bytes = (size_t)m * q.Hp * q.Wp * cg.c;
   q.pool_k = pool_k; q.pool_s = pool_s; q.a_s8 = a_s8 ? 1 : 0; q.out_s8 = out_s8 ? 1 : 0; q.ob = out_border;
   return q.a_bytes < i8ie_igemm_chunk_limit() && i8ie_pconv_takes(L->ctx, q) == 1;
+}
+
+// route T: NHWC in and out of the kernel, one launch (no zero-insert, scatter or fill pass); the layout conversions around
+// it as on the other routes.  The force-fallback option picks deconv_direct inside the launcher.  (NHWC_S8 and the pool have
+// been taken off by the caller: plain bytes, no pool.)
+static int forward_transposed(i8ie_layer* L, const ConvGeom& cg, const uint8_t* in, int in_layout, int in_border, int m,
+                              float s_in, uint8_t zp_in, int relu, uint8_t* out, int out_layout, int out_border, int32_t* acc) {
+  i8ie_ctx* ctx = L->ctx;
+  const bool in_nchw = in_layout == I8IE_LAYOUT_NCHW, out_nchw = out_layout == I8IE_LAYOUT_NCHW;
+  const size_t a_bytes = in_nchw ? i8ie_align_up((size_t)m * cg.c * cg.h * cg.w, 256) : 0;
+  const size_t o_bytes = out_nchw ? i8ie_align_up((size_t)m * cg.kc * cg.oh * cg.ow, 256) : 0;
+  if (a_bytes + o_bytes) I8IE_TRY(i8ie_ws_reserve(ctx, a_bytes + o_bytes + 256));
+  uint8_t* ws = (uint8_t*)ctx->ws;
+  if (in_nchw) I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, in, ws, m, cg.c, cg.h, cg.w, 0));
+  I8ieDeconvCall d{};
+  d.A = in_nchw ? ws : in; d.m = m; d.H = cg.h; d.W = cg.w; d.C = cg.c; d.ib = in_nchw ? 0 : in_border;
+  d.OH = cg.oh; d.OW = cg.ow; d.k = cg.kh; d.s = cg.stride; d.p = cg.pad;
+  d.N = L->n; d.Ngp = L->Ngp; d.Kpp = L->Kpp; d.Bp = L->Bt; d.ktab = L->ttab; d.ocp = L->ocp; d.tph = L->tph;
+  d.msv = msv_arg(L); d.sbv = sbv_arg(L);
+  d.s_in = s_in; d.s_w = sw_arg(L); d.s_out = L->s_out; d.zp_in = zp_in; d.zp_out = L->zp_out; d.relu = relu;
+  d.out = out_nchw ? ws + a_bytes : out; d.ob = out_nchw ? 0 : out_border; d.acc = acc;
+  I8IE_TRY(i8ie_deconv_launch(ctx, d));
+  if (out_nchw) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, d.out, out, m, cg.kc, cg.oh, cg.ow, 0));
+  return I8IE_OK;
 }
 
 static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, int in_border, int m, int h, int w,
@@ -775,7 +893,10 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
 
   // ---- Conv2d --------------------------------------------------------------------------------
   ConvGeom cg;
-  I8IE_TRY(conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg));
+  if (L->path == PATH_T)
+    I8IE_TRY(deconv_geom(L->c, h, w, L->n, L->kh, L->stride, L->pad, L->opad, &cg));
+  else
+    I8IE_TRY(conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg));
   const bool pool = i8ie_is_pool(pool_k, pool_s);
   if (pool) I8IE_REQUIRE(pool_k <= cg.oh && pool_k <= cg.ow, "max-pool window larger than the convolution's output");
   const bool in_s8 = in_layout == I8IE_LAYOUT_NHWC_S8, out_s8 = out_layout == I8IE_LAYOUT_NHWC_S8;
@@ -838,7 +959,9 @@ static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, i
   const int ph = pool ? (cg.oh - pool_k) / pool_s + 1 : cg.oh, pw = pool ? (cg.ow - pool_k) / pool_s + 1 : cg.ow;
   const size_t in_bytes = (size_t)m * cg.c * cg.h * cg.w;
   const size_t out_bytes = (size_t)m * cg.kc * ph * pw;
-  const int path = L->path == PATH_G ? PATH_G : (force_fallback(ctx) ? PATH_F : L->path);
+  const int path = (L->path == PATH_G || L->path == PATH_T) ? L->path : (force_fallback(ctx) ? PATH_F : L->path);
+
+  if (path == PATH_T) return forward_transposed(L, cg, in, in_layout, in_border, m, s_in, zp_in, relu, out, out_layout, out_border, acc);
 
   if (path == PATH_G) {
     // grouped: NHWC in and out of the kernel (the input's own border serves, or bounds checks against zp_in); the layout
@@ -999,7 +1122,7 @@ int i8ie_layer_accepts_f32_input(const i8ie_layer* L, int h, int w, int* yes) {
 int i8ie_layer_fuses_pool(const i8ie_layer* L, int m, int h, int w, int pool_k, int pool_s, int* yes) {
   I8IE_REQUIRE(L && yes, "null argument");
   *yes = 0;
-  if (!L->conv || pool_k < 1 || pool_s < 1 || m < 1) return I8IE_OK;
+  if (!L->conv || L->path == PATH_T || pool_k < 1 || pool_s < 1 || m < 1) return I8IE_OK;
   ConvGeom cg;
   if (conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg) != I8IE_OK) return I8IE_OK;
   if (pool_k > cg.oh || pool_k > cg.ow) return I8IE_OK;
@@ -1010,7 +1133,7 @@ int i8ie_layer_fuses_pool(const i8ie_layer* L, int m, int h, int w, int pool_k, 
 int i8ie_layer_rebiased_io(const i8ie_layer* L, int m, int h, int w, int pool_k, int pool_s, int* reads, int* stores) {
   I8IE_REQUIRE(L && reads && stores, "null argument");
   *reads = *stores = 0;
-  if (!L->conv || m < 1) return I8IE_OK;
+  if (!L->conv || L->path == PATH_T || m < 1) return I8IE_OK;
   ConvGeom cg;
   if (conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg) != I8IE_OK) return I8IE_OK;
   const bool pool = i8ie_is_pool(pool_k, pool_s);

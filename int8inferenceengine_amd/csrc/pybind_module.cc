@@ -1750,6 +1750,131 @@ class Conv2d : public BaseLayer {
   ssize_t in_channels_ = 0;  // as constructed from sizes (0: constructed from arrays)
 };
 
+// ConvTranspose2d (additive, not in the reference): torch.nn.ConvTranspose2d with a square kernel, groups = 1, dilation = 1.
+// The layer is the reference convolution of the equivalent zero-inserted problem (include/i8ie_hip.h,
+// i8ie_conv_transpose2d_create), so the weights are held as the equivalent kernel W~ [out, in, k, k],
+// W~[oc][ic][ky][kx] = W[ic][oc][k-1-ky][k-1-kx]: convert() quantises W~ by the layers' own rules (per tensor over weight and
+// bias; per row of W~ with row_len = in*k*k).  load_weight / load_quantized take and q_weight gives torch's [in, out, k, k].
+class ConvTranspose2d : public BaseLayer {
+ public:
+  ConvTranspose2d(ssize_t in_channel, ssize_t out_channel, ssize_t kernel_size, ssize_t stride, ssize_t padding, ssize_t output_padding)
+      : BaseLayer({checked(out_channel, in_channel, kernel_size, stride, padding, output_padding), in_channel, kernel_size, kernel_size},
+                  out_channel),
+        stride_(stride), padding_(padding), opad_(output_padding) {}
+
+  // torch's [in, out, k, k] <-> the equivalent [out, in, k, k] (the same map both ways round, with the outer sizes swapped)
+  template <typename T>
+  static std::vector<T> swap_flip(const T* src, ssize_t a, ssize_t b, ssize_t k) {  // src [a][b][k][k] -> [b][a][k][k], flipped
+    std::vector<T> dst((size_t)(a * b * k * k));
+    for (ssize_t i = 0; i < a; ++i)
+      for (ssize_t j = 0; j < b; ++j)
+        for (ssize_t y = 0; y < k; ++y)
+          for (ssize_t x = 0; x < k; ++x)
+            dst[(size_t)(((j * a + i) * k + (k - 1 - y)) * k + (k - 1 - x))] = src[(size_t)(((i * b + j) * k + y) * k + x)];
+    return dst;
+  }
+  void check_torch_shape(const std::vector<ssize_t>& shp, const char* what) const {
+    if (shp.size() != 4 || shp[0] != wshape_[1] || shp[1] != wshape_[0] || shp[2] != wshape_[2] || shp[3] != wshape_[3])
+      throw std::runtime_error(std::string("i8ie: ConvTranspose2d: ") + what + ": weight must be [in, out, k, k]");
+  }
+  void load_weight(py::array_t<float, py::array::c_style | py::array::forcecast> w) {
+    if (!has_fp32_) throw std::runtime_error("i8ie: load_weight: layer is already converted");
+    check_torch_shape(std::vector<ssize_t>(w.shape(), w.shape() + w.ndim()), "load_weight");
+    w_ = swap_flip<float>(w.data(), wshape_[1], wshape_[0], wshape_[2]);
+    wt_.assign(w.data(), w.data() + w.size());
+    release_fp32_dev();
+  }
+  void load_quantized(py::array_t<s8_t, py::array::c_style | py::array::forcecast> qw,
+                      py::array_t<s8_t, py::array::c_style | py::array::forcecast> qb, py::object w_scale, float s_out, int zp_out) {
+    check_torch_shape(std::vector<ssize_t>(qw.shape(), qw.shape() + qw.ndim()), "load_quantized");
+    std::vector<s8_t> eq = swap_flip<s8_t>(qw.data(), wshape_[1], wshape_[0], wshape_[2]);
+    py::array_t<s8_t> a(wshape_);
+    std::memcpy(a.mutable_data(), eq.data(), eq.size());
+    BaseLayer::load_quantized(a, qb, w_scale, s_out, zp_out);
+    std::vector<float>().swap(wt_);
+  }
+  void convert(bool per_channel = false) {
+    BaseLayer::convert(per_channel);
+    if (is_quantized_) std::vector<float>().swap(wt_);
+  }
+  py::array_t<s8_t> q_weight() const {
+    need_quantized();
+    std::vector<s8_t> t = swap_flip<s8_t>(qw_.data(), wshape_[0], wshape_[1], wshape_[2]);
+    py::array_t<s8_t> a(std::vector<ssize_t>{wshape_[1], wshape_[0], wshape_[2], wshape_[3]});
+    std::memcpy(a.mutable_data(), t.data(), t.size());
+    return a;
+  }
+
+  std::vector<ssize_t> out_shape(const std::vector<ssize_t>& s) const {
+    if (s.size() != 4) throw std::runtime_error("i8ie: ConvTranspose2d expects an NCHW tensor");
+    if (s[1] != wshape_[1]) throw std::runtime_error("i8ie: ConvTranspose2d: input channels do not match the weight");
+    const ssize_t k = wshape_[2];
+    const ssize_t oh = (s[2] - 1) * stride_ - 2 * padding_ + k + opad_, ow = (s[3] - 1) * stride_ - 2 * padding_ + k + opad_;
+    if (s[2] < 1 || s[3] < 1 || oh < 1 || ow < 1) throw std::runtime_error("i8ie: ConvTranspose2d: empty output");
+    return {s[0], wshape_[0], oh, ow};
+  }
+  Tensor<float> forward_f32(Tensor<float>& in) {
+    need_fp32();
+    Tensor<float> out(out_shape(in.shape));
+    if (!w_dev_) {  // (the FP32 kernel reads torch's layout)
+      if (wt_.empty()) wt_ = swap_flip<float>(w_.data(), wshape_[0], wshape_[1], wshape_[2]);
+      check(i8ie_malloc(ctx(), wt_.size() * 4, (void**)&w_dev_));
+      check(i8ie_malloc(ctx(), b_.size() * 4, (void**)&b_dev_));
+      check(i8ie_memcpy_h2d(ctx(), w_dev_, wt_.data(), wt_.size() * 4));
+      check(i8ie_memcpy_h2d(ctx(), b_dev_, b_.data(), b_.size() * 4));
+    }
+    check(i8ie_conv_transpose2d_f32(ctx(), in.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3],
+                                    w_dev_, b_dev_, (int)wshape_[0], (int)wshape_[2], (int)stride_, (int)padding_, (int)opad_,
+                                    out.dptr()));
+    maybe_sample(out);
+    return out;
+  }
+  std::tuple<Tensor<u8_t>, py::object> forward_u8(Tensor<u8_t>& in, bool want_acc) {
+    need_quantized();
+    std::vector<ssize_t> oshape = out_shape(in.shape);
+    const int n = (int)in.shape[0], h = (int)in.shape[2], w = (int)in.shape[3];
+    if (!want_acc) return std::make_tuple(defer(in, oshape, n, h, w, true), py::object(py::none()));
+    Tensor<u8_t> out(oshape);
+    out.scale = scale_;
+    out.zero_point = zero_point_;
+    Tensor<int32_t> acc({out.shape[0], out.shape[2] * out.shape[3], out.shape[1]});
+    check(i8ie_layer_forward(q_.get(), in.dptr(), n, h, w, in.scale, in.zero_point, out.dptr(), acc.dptr()));
+    py::object acc_np = acc.numpy();
+    return std::make_tuple(std::move(out), acc_np);
+  }
+
+ protected:
+  void check_shapes() const override {
+    if (wshape_.size() != 4) throw std::runtime_error("i8ie: ConvTranspose2d weight must be [in, out, k, k]");
+    if (has_fp32_ && (ssize_t)b_.size() != wshape_[0]) throw std::runtime_error("i8ie: ConvTranspose2d bias size mismatch");
+  }
+  i8ie_layer* make_handle(ssize_t n) override {
+    i8ie_layer* l = nullptr;
+    if (per_channel_)
+      check(i8ie_conv_transpose2d_create_per_channel(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+                                                     reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1],
+                                                     (int)wshape_[2], (int)stride_, (int)padding_, (int)opad_,
+                                                     w_scales_.data(), &l));
+    else
+      check(i8ie_conv_transpose2d_create(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+                                         reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)wshape_[1], (int)wshape_[2],
+                                         (int)stride_, (int)padding_, (int)opad_, w_scale_, &l));
+    return l;
+  }
+
+ private:
+  // the rules of the C entries (I8IE_ERR_ARG there), raised where Conv2d raises for bad groups
+  static ssize_t checked(ssize_t out_channel, ssize_t in_channel, ssize_t k, ssize_t stride, ssize_t padding, ssize_t opad) {
+    if (in_channel < 1 || out_channel < 1 || k < 1) throw std::runtime_error("i8ie: ConvTranspose2d: non-positive size");
+    if (stride < 1) throw std::runtime_error("i8ie: ConvTranspose2d: stride must be >= 1");
+    if (padding < 0 || padding > k - 1) throw std::runtime_error("i8ie: ConvTranspose2d: padding must be in [0, kernel_size - 1]");
+    if (opad < 0 || opad >= stride) throw std::runtime_error("i8ie: ConvTranspose2d: output_padding must be in [0, stride)");
+    return out_channel;
+  }
+  ssize_t stride_ = 1, padding_ = 0, opad_ = 0;
+  std::vector<float> wt_;  // the FP32 weight as loaded (torch's layout), for the FP32 kernel
+};
+
 // A layer without weights (the residual Add, the channel Concat): the layers' prepare / convert state machine
 // (src/layer.cc:28-54) around its output (scale, zero_point); FP32 tensors join in FP32 (and are sampled while preparing),
 // u8 tensors after convert().
@@ -1984,6 +2109,13 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
              py::arg("out_channels"), py::arg("kernel_size"), py::arg("stride") = 1, py::arg("padding") = 0,
              py::arg("groups") = 1)
         .def("groups", &Conv2d::groups);
+    bind_layer_common(c);
+  }
+
+  {
+    py::class_<ConvTranspose2d> c(m, "ConvTranspose2d");
+    c.def(py::init<ssize_t, ssize_t, ssize_t, ssize_t, ssize_t, ssize_t>(), py::arg("in_channels"), py::arg("out_channels"),
+          py::arg("kernel_size"), py::arg("stride") = 1, py::arg("padding") = 0, py::arg("output_padding") = 0);
     bind_layer_common(c);
   }
 

@@ -7,7 +7,7 @@ device-resident and `.numpy()` copies back to the host.
 """
 import _CXX_i8ie as _C
 
-from .layer import Activation, Add, Concat, Conv2d, Layer, Linear, Mul, activation_kind
+from .layer import Activation, Add, Concat, Conv2d, ConvTranspose2d, Layer, Linear, Mul, activation_kind
 from .module import Module
 from .tensor import Tensor
 
@@ -15,7 +15,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
-    "Linear", "FullyConnected", "Conv2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d",
+    "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 

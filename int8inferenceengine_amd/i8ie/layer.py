@@ -71,6 +71,16 @@ class Conv2d(Layer):
         self.layer = _C.Conv2d(in_channels, out_channels, kernel_size, stride, padding, groups)
 
 
+class ConvTranspose2d(Layer):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, output_padding=0):
+        """Learned upsampling (additive, not in the reference): torch.nn.ConvTranspose2d with a square kernel, groups = 1 and
+        dilation = 1.  The weight is torch's [in, out, k, k], the bias [out]; the output is (h - 1) * stride - 2 * padding +
+        k + output_padding high.  stride >= 1, 0 <= padding <= k - 1, 0 <= output_padding < stride (RuntimeError otherwise).
+        In INT8 it is the reference convolution of the zero-inserted input with the flipped kernel (include/i8ie_hip.h,
+        i8ie_conv_transpose2d_create): convert(per_channel=True) gives one weight scale per OUTPUT feature."""
+        self.layer = _C.ConvTranspose2d(in_channels, out_channels, kernel_size, stride, padding, output_padding)
+
+
 class Weightless(Layer):
     """Common behaviour of the layers without weights (Add, Mul, Concat, Activation): `self.layer` has only the prepare / convert state
     machine around an output (scale, zero_point).  Takes part in Module.prepare() / convert() / quantized_state_dict()

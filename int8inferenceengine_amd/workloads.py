@@ -12,7 +12,8 @@ product path (SpecNet, through i8ie) and the CPU oracle in tests/bench.
 import numpy as np
 
 # name -> (layers, spec, input_shape CHW)
-#   layers: {attr: ("conv", in_c, out_c, k, stride, pad[, groups]) | ("fc", in_f, out_f)}
+#   layers: {attr: ("conv", in_c, out_c, k, stride, pad[, groups]) | ("fc", in_f, out_f)
+#                  | ("deconv", in_c, out_c, k, stride, pad, output_pad)   i8ie.ConvTranspose2d, weight [in_c, out_c, k, k]}
 #   spec  : [("layer", attr) | ("relu",) | ("pool", k, s) | ("flatten", features)
 #            | ("save", tag)              remember the current tensor under `tag`
 #            | ("add", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Add (not in `layers`)
@@ -305,6 +306,54 @@ NETWORKS["se_tiny"] = _se_tiny()
 NETWORKS["mobilenetv3_small_cifar"] = _mobilenetv3_small_cifar()
 
 
+def _unet_tiny():
+    """A U-Net in small (two levels down by max-pool): what the ConvTranspose2d exists for.  Three up-convs, 2x2 stride 2 and
+    4x4 stride 2 pad 1 side by side out of the bottleneck and 3x3 stride 2 pad 1 output_pad 1 above them; the skips joined by
+    Concat at 47 (= 20 + 7 + 20) and 24 channels; a 3x3 pad-1 conv behind each join; a 1x1 head to 10 maps of 32 x 32."""
+    layers = {"enc1": ("conv", 3, 12, 3, 1, 1), "enc2": ("conv", 12, 20, 3, 1, 1), "bott": ("conv", 20, 32, 3, 1, 1),
+              "up2a": ("deconv", 32, 20, 2, 2, 0, 0), "up2b": ("deconv", 32, 7, 4, 2, 1, 0), "dec2": ("conv", 47, 20, 3, 1, 1),
+              "up1": ("deconv", 20, 12, 3, 2, 1, 1), "dec1": ("conv", 24, 12, 3, 1, 1), "head": ("conv", 12, 10, 1, 1, 0)}
+    spec = [("layer", "enc1"), ("relu",), ("save", "e1"), ("pool", 2, 2),
+            ("layer", "enc2"), ("relu",), ("save", "e2"), ("pool", 2, 2),
+            ("layer", "bott"), ("relu",), ("save", "b"),
+            ("layer", "up2a"), ("branch", "b", [("layer", "up2b")]), ("concat", "cat2", ["b", "e2"]), ("layer", "dec2"), ("relu",),
+            ("layer", "up1"), ("relu",), ("concat", "cat1", ["e1"]), ("layer", "dec1"), ("relu",), ("layer", "head")]
+    return layers, spec, (3, 32, 32)
+
+
+def _unet_cifar():
+    """U-Net (Ronneberger et al. 2015) at widths 64 / 128 / 256 / 512 for 32 x 32 input: two padded 3x3 convs per level, 2x2
+    max-pools down, 2x2 stride-2 up-convs, the skips joined by Concat, a 1x1 head to 10 maps."""
+    layers, spec = {}, []
+
+    def double(p, in_c, out_c):
+        layers[p + "a"] = ("conv", in_c, out_c, 3, 1, 1)
+        layers[p + "b"] = ("conv", out_c, out_c, 3, 1, 1)
+        spec.extend([("layer", p + "a"), ("relu",), ("layer", p + "b"), ("relu",)])
+
+    widths = (64, 128, 256, 512)
+    c = 3
+    for i, wd in enumerate(widths[:-1], start=1):
+        double("d%d" % i, c, wd)
+        spec.extend([("save", "s%d" % i), ("pool", 2, 2)])
+        c = wd
+    double("mid", c, widths[-1])
+    c = widths[-1]
+    for i in (3, 2, 1):
+        wd = widths[i - 1]
+        layers["up%d" % i] = ("deconv", c, wd, 2, 2, 0, 0)
+        spec.extend([("layer", "up%d" % i), ("concat", "cat%d" % i, ["s%d" % i])])
+        double("u%d" % i, 2 * wd, wd)
+        c = wd
+    layers["head"] = ("conv", c, 10, 1, 1, 0)
+    spec.append(("layer", "head"))
+    return layers, spec, (3, 32, 32)
+
+
+NETWORKS["unet_tiny"] = _unet_tiny()
+NETWORKS["unet_cifar"] = _unet_cifar()
+
+
 def _walk(spec):
     """every op of a spec in order, the ops inside ("branch", tag, [ops]) included"""
     for op in spec:
@@ -334,6 +383,11 @@ def macs_per_image(name):
                 h, w = (h - k + 2 * p) // s + 1, (w - k + 2 * p) // s + 1
                 total += h * w * oc * (ic // conv_groups(L)) * k * k
                 c = oc
+            elif L[0] == "deconv":  # the real MACs: every input pixel meets every tap once
+                _, ic, oc, k, s, p, op_ = L
+                total += h * w * ic * oc * k * k
+                h, w = (h - 1) * s - 2 * p + k + op_, (w - 1) * s - 2 * p + k + op_
+                c = oc
             else:
                 total += L[1] * L[2]
         elif op[0] in ("pool", "avgpool"):
@@ -354,10 +408,14 @@ def synthetic_state_dict(name, seed=42):
     layers = NETWORKS[name][0]
     sd = {}
     for attr, L in layers.items():
-        shape = (L[2], L[1] // conv_groups(L), L[3], L[3]) if L[0] == "conv" else (L[2], L[1])
-        fan_in = int(np.prod(shape[1:]))
+        if L[0] == "deconv":  # [in, out, k, k]; an output pixel sums in * ceil(k / stride)^2 products
+            shape, n_out = (L[1], L[2], L[3], L[3]), L[2]
+            fan_in = L[1] * (-(-L[3] // L[4])) ** 2
+        else:
+            shape = (L[2], L[1] // conv_groups(L), L[3], L[3]) if L[0] == "conv" else (L[2], L[1])
+            fan_in, n_out = int(np.prod(shape[1:])), shape[0]
         sd[attr + ".weight"] = (rng.uniform(-1, 1, shape) * np.sqrt(6.0 / fan_in)).astype(np.float32)
-        sd[attr + ".bias"] = (rng.uniform(-1, 1, shape[0]) / np.sqrt(fan_in)).astype(np.float32)
+        sd[attr + ".bias"] = (rng.uniform(-1, 1, n_out) / np.sqrt(fan_in)).astype(np.float32)
     return sd
 
 
@@ -392,7 +450,9 @@ def build(name):
                 elif op[0] == "act":
                     setattr(self, op[1], i8ie.Activation(op[2], op[3] if len(op) > 3 else None))
             for attr, L in layers.items():
-                if L[0] == "conv":
+                if L[0] == "deconv":
+                    setattr(self, attr, i8ie.ConvTranspose2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], output_padding=L[6]))
+                elif L[0] == "conv":
                     if conv_groups(L) == 1:
                         setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5]))
                     else:
