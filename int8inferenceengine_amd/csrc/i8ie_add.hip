@@ -19,18 +19,9 @@
 #include <cmath>
 
 #include "i8ie_internal.h"
+#include "i8ie_pointwise.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 256 * 8;
-
-inline int grid_for(int64_t work_items) {
-  int64_t b = (work_items + kThreads - 1) / kThreads;
-  if (b < 1) b = 1;
-  return (int)(b > kMaxBlocks ? kMaxBlocks : b);
-}
-inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 struct AddParams {
   float sa, zpa, sb, zpb, sc, zpc;
@@ -98,14 +89,9 @@ __global__ __launch_bounds__(kThreads) void add_u8_flat_kernel(const uint8_t* a,
 // ---- bordered NHWC form: [n][h + 2b][w + 2b][c] per buffer, each with its own b.  The w * c interior bytes of an image row
 // are the contiguous unit; an item is VEC bytes of one row (VEC = 16 / 4 / 1 by c's divisibility: every row start is then
 // VEC-aligned in all three buffers).  Only the interior of `out` is written.
-struct AddBuf {
-  int64_t img;  // bytes per image: (h + 2b) * (w + 2b) * c
-  int64_t row;  // bytes per physical row: (w + 2b) * c
-  int64_t org;  // offset of interior pixel (0, 0): b * row + b * c
-};
 template <int VEC, typename Idx>
-__global__ __launch_bounds__(kThreads) void add_u8_nhwc_kernel(const uint8_t* __restrict__ a, AddBuf ga, const uint8_t* __restrict__ b,
-                                                               AddBuf gb, uint8_t* __restrict__ out, AddBuf go, Idx items, Idx per_row,
+__global__ __launch_bounds__(kThreads) void add_u8_nhwc_kernel(const uint8_t* __restrict__ a, NhwcGeom ga, const uint8_t* __restrict__ b,
+                                                               NhwcGeom gb, uint8_t* __restrict__ out, NhwcGeom go, Idx items, Idx per_row,
                                                                Idx h, AddParams p) {
   const Idx stride = (Idx)gridDim.x * kThreads;
   for (Idx v = (Idx)blockIdx.x * kThreads + threadIdx.x; v < items; v += stride) {
@@ -138,8 +124,6 @@ __global__ __launch_bounds__(kThreads) void add_f32_kernel(const float* a, const
   if (blockIdx.x == 0 && threadIdx.x < (n - t0)) out[t0 + threadIdx.x] = a[t0 + threadIdx.x] + b[t0 + threadIdx.x];
 }
 
-inline bool ordinary(float s) { return s > 1e-30f && s < 1e30f; }
-
 AddParams make_params(float s_a, int zp_a, float s_b, int zp_b, float s_out, int zp_out, int relu, int a_s8, int b_s8, int out_s8) {
   AddParams p;
   p.sa = s_a; p.zpa = (float)zp_a; p.sb = s_b; p.zpb = (float)zp_b; p.sc = s_out; p.zpc = (float)zp_out;
@@ -156,19 +140,9 @@ AddParams make_params(float s_a, int zp_a, float s_b, int zp_b, float s_out, int
   return p;
 }
 
-bool scales_ok(float s_a, float s_b, float s_out) { return std::isfinite(s_a) && std::isfinite(s_b) && std::isfinite(s_out) && s_out > 0.0f; }
-
-AddBuf buf_geom(int c, int h, int w, int border) {
-  AddBuf g;
-  g.row = (int64_t)(w + 2 * border) * c;
-  g.img = (int64_t)(h + 2 * border) * g.row;
-  g.org = (int64_t)border * g.row + (int64_t)border * c;
-  return g;
-}
-
 template <int VEC>
-void launch_nhwc(i8ie_ctx* ctx, const uint8_t* a, const AddBuf& ga, const uint8_t* b, const AddBuf& gb, uint8_t* out,
-                 const AddBuf& go, int n, int c, int h, int w, const AddParams& p) {
+void launch_nhwc(i8ie_ctx* ctx, const uint8_t* a, const NhwcGeom& ga, const uint8_t* b, const NhwcGeom& gb, uint8_t* out,
+                 const NhwcGeom& go, int n, int c, int h, int w, const AddParams& p) {
   const int64_t per_row = (int64_t)w * c / VEC, items = (int64_t)n * h * per_row;
   if (items <= 0x7FFFFFFF)
     add_u8_nhwc_kernel<VEC, uint32_t><<<grid_for(items), kThreads, 0, ctx->stream>>>(a, ga, b, gb, out, go, (uint32_t)items,
@@ -212,7 +186,7 @@ int i8ie_add_u8_nhwc(i8ie_ctx* ctx, const uint8_t* a, int a_border, int a_s8, co
   if (a_border == 0 && b_border == 0 && out_border == 0 && al16) {  // one physical order, no border: the flat form
     add_u8_flat_kernel<<<grid_for((total >> 4) + 1), kThreads, 0, ctx->stream>>>(a, b, out, total, p);
   } else {
-    const AddBuf ga = buf_geom(c, h, w, a_border), gb = buf_geom(c, h, w, b_border), go = buf_geom(c, h, w, out_border);
+    const NhwcGeom ga = buf_geom(c, h, w, a_border), gb = buf_geom(c, h, w, b_border), go = buf_geom(c, h, w, out_border);
     if (c % 16 == 0 && al16) launch_nhwc<16>(ctx, a, ga, b, gb, out, go, n, c, h, w, p);
     else if (c % 4 == 0 && al4) launch_nhwc<4>(ctx, a, ga, b, gb, out, go, n, c, h, w, p);
     else launch_nhwc<1>(ctx, a, ga, b, gb, out, go, n, c, h, w, p);

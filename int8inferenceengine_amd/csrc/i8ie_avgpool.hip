@@ -45,22 +45,14 @@
 #include <cmath>
 
 #include "i8ie_internal.h"
+#include "i8ie_pointwise.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 256 * 8;
 constexpr int kMaxWindow = 65536;
 constexpr int kPackedMax = 257;            // 255 * n < 65536
 constexpr int kReduceMinWindow = 16;       // the regime rule (header)
 constexpr int64_t kReduceMaxItems = 65536;
-
-inline int grid_for(int64_t work_items) {
-  int64_t b = (work_items + kThreads - 1) / kThreads;
-  if (b < 1) b = 1;
-  return (int)(b > kMaxBlocks ? kMaxBlocks : b);
-}
-inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 struct DivParams {
   uint32_t n, rnd;   // window size, n / 2

@@ -31,17 +31,9 @@
 #include <cstring>
 
 #include "i8ie_internal.h"
+#include "i8ie_pointwise.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 256 * 8;
-
-inline int grid_for(int64_t work_items) {
-  int64_t b = (work_items + kThreads - 1) / kThreads;
-  if (b < 1) b = 1;
-  return (int)(b > kMaxBlocks ? kMaxBlocks : b);
-}
 
 enum { kCopy = 0, kGuarded = 1, kExact = 2 };
 
@@ -176,13 +168,11 @@ __global__ __launch_bounds__(kThreads) void concat_kernel(const CatArgs a) {
   else cat_items<1, NHWC, Idx>(d, a.out);
 }
 
-inline bool ordinary(float s) { return s > 1e-30f && s < 1e30f; }
 inline uint32_t bits_of(float f) {
   uint32_t u;
   std::memcpy(&u, &f, 4);
   return u;
 }
-inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 void set_out(CatOut& o, uint8_t* out, float s_out, int zp_out, int relu, int out_s8) {
   o.p = out;

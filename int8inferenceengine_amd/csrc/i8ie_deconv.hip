@@ -26,6 +26,7 @@
 // the optional ReLU clamp; a lane's 4 consecutive features of a pixel go out as one dword.
 #include "i8ie_internal.h"
 #include "i8ie_deconv.h"
+#include "i8ie_pointwise.h"
 
 namespace {
 
@@ -293,7 +294,6 @@ __global__ __launch_bounds__(256) void deconv_f32_kernel(const float* __restrict
   }
 }
 
-inline bool aligned_to(const void* ptr, unsigned a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
 inline int granularity(int C) { return C % 16 == 0 ? 16 : (C % 4 == 0 ? 4 : 1); }
 
 }  // namespace

@@ -5,17 +5,9 @@
 // fp32 arithmetic follows SURVEY.md Appendix A exactly (IEEE divide, no FMA
 // contraction: the library is built with -ffp-contract=off).
 #include "i8ie_internal.h"
+#include "i8ie_pointwise.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 256 * 8;
-
-inline int grid_for(int64_t work_items) {
-  int64_t b = (work_items + kThreads - 1) / kThreads;
-  if (b < 1) b = 1;
-  return (int)(b > kMaxBlocks ? kMaxBlocks : b);
-}
 
 // ---- a1: src/quantize_utils.cc:44-52 ---------------------------------------
 __device__ __forceinline__ uint32_t quant1(float x, float scale, float zpf) {
@@ -174,9 +166,6 @@ __global__ __launch_bounds__(kThreads) void maxpool_s8_nchw_kernel(const int8_t*
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-
 // ---- Calibrator::sample on the device (src/calibrator.cc:6-23; include/i8ie_hip.h) ---------------------------
 constexpr int kCalibSlots = 1000;
 __device__ __forceinline__ uint32_t calib_draw(uint64_t seed, uint64_t g) {  // uniform in [0, 2000], splitmix64 of (seed, g)
@@ -228,7 +217,7 @@ int i8ie_quantize_f32_u8(i8ie_ctx* ctx, const float* in, uint8_t* out, int64_t n
                          uint8_t zp) {
   I8IE_REQUIRE(ctx && in && out, "null argument");
   I8IE_REQUIRE(n >= 0, "negative size");
-  I8IE_REQUIRE(aligned16(in) && aligned16(out), "buffers must be 16-byte aligned");
+  I8IE_REQUIRE(aligned_to(in, 16) && aligned_to(out, 16), "buffers must be 16-byte aligned");
   if (n == 0) return I8IE_OK;
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   I8ieProfScope prof(ctx, "quantize_f32_u8", 0.0, 5.0 * n);
@@ -277,7 +266,7 @@ int i8ie_down_scale_per_channel(i8ie_ctx* ctx, const int32_t* acc, uint8_t* out,
 int i8ie_relu_u8(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int64_t n, uint8_t zp) {
   I8IE_REQUIRE(ctx && in && out, "null argument");
   I8IE_REQUIRE(n >= 0, "negative size");
-  I8IE_REQUIRE(aligned16(in) && aligned16(out), "buffers must be 16-byte aligned");
+  I8IE_REQUIRE(aligned_to(in, 16) && aligned_to(out, 16), "buffers must be 16-byte aligned");
   if (n == 0) return I8IE_OK;
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   uint32_t z = zp;
@@ -291,7 +280,7 @@ int i8ie_relu_u8(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int64_t n, uint
 int i8ie_rebias_u8(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int64_t n) {
   I8IE_REQUIRE(ctx && in && out, "null argument");
   I8IE_REQUIRE(n >= 0, "negative size");
-  I8IE_REQUIRE(aligned16(in) && aligned16(out), "buffers must be 16-byte aligned");
+  I8IE_REQUIRE(aligned_to(in, 16) && aligned_to(out, 16), "buffers must be 16-byte aligned");
   if (n == 0) return I8IE_OK;
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   I8ieProfScope prof(ctx, "rebias_u8", 0.0, 2.0 * n);

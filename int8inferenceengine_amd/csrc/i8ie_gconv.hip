@@ -15,6 +15,7 @@
 // is the requantiser of i8ie_requant.h (per-tensor and per-channel instances) with the optional ReLU clamp.
 #include "i8ie_internal.h"
 #include "i8ie_gconv.h"
+#include "i8ie_pointwise.h"
 
 namespace {
 
@@ -231,8 +232,6 @@ __global__ __launch_bounds__(256) void gconv_direct_kernel(GconvArgs p, int grou
     finish4<PC>(p, c, pxi, q.out_pix, g, f);
   }
 }
-
-inline bool aligned_to(const void* ptr, unsigned a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
 
 }  // namespace
 

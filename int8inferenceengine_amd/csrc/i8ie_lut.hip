@@ -18,19 +18,11 @@
 #include <cstring>
 
 #include "i8ie_internal.h"
+#include "i8ie_pointwise.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 256 * 8;
 constexpr int kKinds = 6;
-
-inline int grid_for(int64_t work_items) {
-  int64_t b = (work_items + kThreads - 1) / kThreads;
-  if (b < 1) b = 1;
-  return (int)(b > kMaxBlocks ? kMaxBlocks : b);
-}
-inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 struct LutTable {
   uint32_t w[64];  // table[4k .. 4k+3] in dword k, as the bytes lie in memory
@@ -80,13 +72,8 @@ __global__ __launch_bounds__(kThreads) void lut_u8_flat_kernel(const uint8_t* in
 
 // ---- bordered NHWC form: [n][h + 2b][w + 2b][c] per buffer, each with its own b.  The w * c interior bytes of an image row
 // are the contiguous unit; an item is VEC bytes of one row (every row start is VEC-aligned in both buffers: c % VEC == 0).
-struct LutBuf {
-  int64_t img;  // bytes per image: (h + 2b) * (w + 2b) * c
-  int64_t row;  // bytes per physical row: (w + 2b) * c
-  int64_t org;  // offset of interior pixel (0, 0): b * row + b * c
-};
 template <int VEC, typename Idx>
-__global__ __launch_bounds__(kThreads) void lut_u8_nhwc_kernel(const uint8_t* __restrict__ in, LutBuf gi, uint8_t* __restrict__ out, LutBuf go,
+__global__ __launch_bounds__(kThreads) void lut_u8_nhwc_kernel(const uint8_t* __restrict__ in, NhwcGeom gi, uint8_t* __restrict__ out, NhwcGeom go,
                                                                Idx items, Idx per_row, Idx h, const LutTable t) {
   __shared__ uint32_t lds[64 * 32];
   lut_fill(lds, t);
@@ -152,15 +139,8 @@ void launch_flat(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int64_t n, cons
     lut_u8_flat_kernel<1><<<grid_for(n), kThreads, 0, ctx->stream>>>(in, out, n, t);
 }
 
-LutBuf buf_geom(int c, int h, int w, int border) {
-  LutBuf g;
-  g.row = (int64_t)(w + 2 * border) * c;
-  g.img = (int64_t)(h + 2 * border) * g.row;
-  g.org = (int64_t)border * g.row + (int64_t)border * c;
-  return g;
-}
 template <int VEC>
-void launch_nhwc(i8ie_ctx* ctx, const uint8_t* in, const LutBuf& gi, uint8_t* out, const LutBuf& go, int n, int c, int h, int w,
+void launch_nhwc(i8ie_ctx* ctx, const uint8_t* in, const NhwcGeom& gi, uint8_t* out, const NhwcGeom& go, int n, int c, int h, int w,
                  const LutTable& t) {
   const int64_t per_row = (int64_t)w * c / VEC, items = (int64_t)n * h * per_row;
   if (items <= 0x7FFFFFFF)
@@ -211,7 +191,7 @@ int i8ie_lut_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in, int in_border, int in_s8,
   if (in_border == 0 && out_border == 0) {  // one physical order, no border: the flat form
     launch_flat(ctx, in, out, total, t);
   } else {
-    const LutBuf gi = buf_geom(c, h, w, in_border), go = buf_geom(c, h, w, out_border);
+    const NhwcGeom gi = buf_geom(c, h, w, in_border), go = buf_geom(c, h, w, out_border);
     if (c % 16 == 0 && aligned_to(in, 16) && aligned_to(out, 16)) launch_nhwc<16>(ctx, in, gi, out, go, n, c, h, w, t);
     else if (c % 4 == 0 && aligned_to(in, 4) && aligned_to(out, 4)) launch_nhwc<4>(ctx, in, gi, out, go, n, c, h, w, t);
     else launch_nhwc<1>(ctx, in, gi, out, go, n, c, h, w, t);

@@ -38,19 +38,11 @@
 #include <cmath>
 
 #include "i8ie_internal.h"
+#include "i8ie_pointwise.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 256 * 8;
 constexpr int kWalk = 8;  // pixels a lane of the gate kernel walks with one gate item in registers
-
-inline int grid_for(int64_t work_items) {
-  int64_t b = (work_items + kThreads - 1) / kThreads;
-  if (b < 1) b = 1;
-  return (int)(b > kMaxBlocks ? kMaxBlocks : b);
-}
-inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 struct MulParams {
   float sa, zpa, sb, zpb, sc, zpc;
@@ -120,14 +112,9 @@ __global__ __launch_bounds__(kThreads) void mul_u8_flat_kernel(const uint8_t* a,
 
 // ---- bordered NHWC form, equal shapes: [n][h + 2b][w + 2b][c] per buffer, each with its own b.  The w * c interior bytes of
 // an image row are the contiguous unit; an item is VEC bytes of one row.  Only the interior of `out` is written.
-struct MulBuf {
-  int64_t img;  // bytes per image: (h + 2b) * (w + 2b) * c
-  int64_t row;  // bytes per physical row: (w + 2b) * c
-  int64_t org;  // offset of interior pixel (0, 0): b * row + b * c
-};
 template <int VEC, typename Idx>
-__global__ __launch_bounds__(kThreads) void mul_u8_nhwc_kernel(const uint8_t* __restrict__ a, MulBuf ga, const uint8_t* __restrict__ b,
-                                                               MulBuf gb, uint8_t* __restrict__ out, MulBuf go, Idx items, Idx per_row,
+__global__ __launch_bounds__(kThreads) void mul_u8_nhwc_kernel(const uint8_t* __restrict__ a, NhwcGeom ga, const uint8_t* __restrict__ b,
+                                                               NhwcGeom gb, uint8_t* __restrict__ out, NhwcGeom go, Idx items, Idx per_row,
                                                                Idx h, MulParams p) {
   const Idx stride = (Idx)gridDim.x * kThreads;
   for (Idx v = (Idx)blockIdx.x * kThreads + threadIdx.x; v < items; v += stride) {
@@ -182,8 +169,8 @@ __device__ __forceinline__ uint32_t gate4(uint32_t a4, const float* h4, uint32_t
 }
 
 template <int VEC>
-__global__ __launch_bounds__(kThreads) void mul_u8_gate_kernel(const uint8_t* __restrict__ a, MulBuf ga, const uint8_t* __restrict__ g,
-                                                               uint8_t* __restrict__ out, MulBuf go, MulGate t, MulParams p) {
+__global__ __launch_bounds__(kThreads) void mul_u8_gate_kernel(const uint8_t* __restrict__ a, NhwcGeom ga, const uint8_t* __restrict__ g,
+                                                               uint8_t* __restrict__ out, NhwcGeom go, MulGate t, MulParams p) {
   constexpr int W = VEC >= 4 ? VEC / 4 : 1;  // dwords per item
   const int pc = (int)threadIdx.x / t.lanes_c, ci = (int)threadIdx.x - pc * t.lanes_c;
   if (pc >= t.rows) return;  // (the lanes behind the block's last whole pixel)
@@ -261,7 +248,8 @@ __global__ __launch_bounds__(kThreads) void mul_f32_gate_kernel(const float* a, 
   for (int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x; v < n; v += stride) out[v] = a[v] * g[v / run];
 }
 
-inline bool ordinary(double s) { return s > 1e-30 && s < 1e30; }
+// (in double, unlike the pointwise units' shared ordinary(float): the bound above is stated on the double products and quotients)
+inline bool ordinary_d(double s) { return s > 1e-30 && s < 1e30; }
 
 MulParams make_params(float s_a, int zp_a, float s_b, int zp_b, float s_out, int zp_out, int relu, int a_s8, int b_s8, int out_s8) {
   MulParams p;
@@ -273,27 +261,17 @@ MulParams make_params(float s_a, int zp_a, float s_b, int zp_b, float s_out, int
   // the estimate only where nothing can overflow or go denormal on the way: ordinary scales, an ordinary s_a * s_b (the
   // smallest nonzero |P|), an ordinary s_b / s_out (the smallest nonzero |H|) and an ordinary largest |P / s_out|
   const double top = 255.0 * 255.0 * (double)s_a * (double)s_b / (double)s_out;
-  p.fast = (ordinary(s_a) && ordinary(s_b) && ordinary(s_out) && ordinary((double)s_a * (double)s_b) &&
-            ordinary((double)s_b / (double)s_out) && top < 1e30) ? 1 : 0;
+  p.fast = (ordinary_d(s_a) && ordinary_d(s_b) && ordinary_d(s_out) && ordinary_d((double)s_a * (double)s_b) &&
+            ordinary_d((double)s_b / (double)s_out) && top < 1e30) ? 1 : 0;
   p.xa = a_s8 ? 0x80808080u : 0u;
   p.xb = b_s8 ? 0x80808080u : 0u;
   p.xo = out_s8 ? 0x80808080u : 0u;
   return p;
 }
 
-bool scales_ok(float s_a, float s_b, float s_out) { return std::isfinite(s_a) && std::isfinite(s_b) && std::isfinite(s_out) && s_out > 0.0f; }
-
-MulBuf buf_geom(int c, int h, int w, int border) {
-  MulBuf g;
-  g.row = (int64_t)(w + 2 * border) * c;
-  g.img = (int64_t)(h + 2 * border) * g.row;
-  g.org = (int64_t)border * g.row + (int64_t)border * c;
-  return g;
-}
-
 template <int VEC>
-void launch_nhwc(i8ie_ctx* ctx, const uint8_t* a, const MulBuf& ga, const uint8_t* b, const MulBuf& gb, uint8_t* out,
-                 const MulBuf& go, int n, int c, int h, int w, const MulParams& p) {
+void launch_nhwc(i8ie_ctx* ctx, const uint8_t* a, const NhwcGeom& ga, const uint8_t* b, const NhwcGeom& gb, uint8_t* out,
+                 const NhwcGeom& go, int n, int c, int h, int w, const MulParams& p) {
   const int64_t per_row = (int64_t)w * c / VEC, items = (int64_t)n * h * per_row;
   if (items <= 0x7FFFFFFF)
     mul_u8_nhwc_kernel<VEC, uint32_t><<<grid_for(items), kThreads, 0, ctx->stream>>>(a, ga, b, gb, out, go, (uint32_t)items,
@@ -304,10 +282,10 @@ void launch_nhwc(i8ie_ctx* ctx, const uint8_t* a, const MulBuf& ga, const uint8_
 }
 
 template <int VEC>
-void launch_gate(i8ie_ctx* ctx, const uint8_t* a, const MulBuf& ga, const uint8_t* g, int g_border, uint8_t* out, const MulBuf& go,
+void launch_gate(i8ie_ctx* ctx, const uint8_t* a, const NhwcGeom& ga, const uint8_t* g, int g_border, uint8_t* out, const NhwcGeom& go,
                  int n, int c, int h, int w, const MulParams& p) {
   MulGate t;
-  const MulBuf gg = buf_geom(c, 1, 1, g_border);
+  const NhwcGeom gg = buf_geom(c, 1, 1, g_border);
   t.g_img = gg.img;
   t.g_org = gg.org;
   t.cpv = c / VEC;
@@ -360,7 +338,7 @@ int i8ie_mul_u8_nhwc(i8ie_ctx* ctx, const uint8_t* a, int a_border, int a_s8, co
   const int64_t total = (int64_t)n * c * h * w;
   const bool al16 = aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(out, 16);
   const bool al4 = aligned_to(a, 4) && aligned_to(b, 4) && aligned_to(out, 4);
-  const MulBuf ga = buf_geom(c, h, w, a_border), go = buf_geom(c, h, w, out_border);
+  const NhwcGeom ga = buf_geom(c, h, w, a_border), go = buf_geom(c, h, w, out_border);
   if (b_gate) {
     I8ieProfScope prof(ctx, "mul_u8_gate", 0.0, 2.0 * total + (double)n * c);
     if (c % 16 == 0 && al16) launch_gate<16>(ctx, a, ga, b, b_border, out, go, n, c, h, w, p);
@@ -373,7 +351,7 @@ int i8ie_mul_u8_nhwc(i8ie_ctx* ctx, const uint8_t* a, int a_border, int a_s8, co
   if (a_border == 0 && b_border == 0 && out_border == 0 && al16) {  // one physical order, no border: the flat form
     mul_u8_flat_kernel<<<grid_for((total >> 4) + 1), kThreads, 0, ctx->stream>>>(a, b, out, total, p);
   } else {
-    const MulBuf gb = buf_geom(c, h, w, b_border);
+    const NhwcGeom gb = buf_geom(c, h, w, b_border);
     if (c % 16 == 0 && al16) launch_nhwc<16>(ctx, a, ga, b, gb, out, go, n, c, h, w, p);
     else if (c % 4 == 0 && al4) launch_nhwc<4>(ctx, a, ga, b, gb, out, go, n, c, h, w, p);
     else launch_nhwc<1>(ctx, a, ga, b, gb, out, go, n, c, h, w, p);

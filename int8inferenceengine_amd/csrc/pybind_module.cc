@@ -364,12 +364,14 @@ struct Tensor {
   float qscale = 0;
   u8_t qzp = 0;
 
-  void realize(int border = 0, bool s8 = false) {
-    if (!pend) return;
-    st = pend->get(pend_relu, border, s8);
+  void adopt(std::shared_ptr<Storage> s) {  // takes a launched result: nothing is pending on this tensor any more
+    st = std::move(s);
     pend.reset();
     pend_f32.reset();
     qsrc.reset();
+  }
+  void realize(int border = 0, bool s8 = false) {
+    if (pend) adopt(pend->get(pend_relu, border, s8));
   }
 
   Tensor() = default;
@@ -619,13 +621,29 @@ void bind_tensor(py::module_& m, const char* name) {
       .def("nbytes", [](const Tensor<T>& t) { return (size_t)t.size * sizeof(T); });
 }
 
+// A u8 result that is still to be produced (recorded, or written by the caller): shape, element count and quantisation
+// parameters, no storage yet.
+Tensor<u8_t> pending_u8(std::vector<ssize_t> shape, float scale, u8_t zp) {
+  Tensor<u8_t> t;
+  t.shape = std::move(shape);
+  t.size = 1;
+  for (ssize_t d : t.shape) t.size *= d;
+  t.scale = scale;
+  t.zero_point = zp;
+  return t;
+}
+void check_zero_point(int zp) {
+  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+}
+// the result's quantisation parameters as a caller of add / mul / cat / lut gave them
+void check_out_qparams(const char* op, float scale, int zp) {
+  check_zero_point(zp);
+  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error(std::string("i8ie: ") + op + ": the output scale must be positive and finite");
+}
+
 // ------------------------------------------------------------ elementwise ----
 Tensor<u8_t> quantize(Tensor<float>& in, float scale, u8_t zp) {  // src/quantize_utils.cc:44-52
-  Tensor<u8_t> out;
-  out.shape = in.shape;
-  out.size = in.size;
-  out.scale = scale;
-  out.zero_point = zp;
+  Tensor<u8_t> out = pending_u8(in.shape, scale, zp);
   (void)in.dptr();  // make sure the FP32 source is on the device
   std::shared_ptr<Storage> src = in.st;
   const ssize_t n = in.size;
@@ -658,11 +676,7 @@ Tensor<u8_t> relu_u8(Tensor<u8_t>& in) {  // src/functional.cc:15-26
   if (in.pend && !in.pend_relu) {
     // `in` is a layer output that has not been launched: record layer+relu as one launch.
     // `in` itself stays pending (if it is ever observed it launches without the relu).
-    Tensor<u8_t> out;
-    out.shape = in.shape;
-    out.size = in.size;
-    out.scale = in.scale;
-    out.zero_point = in.zero_point;
+    Tensor<u8_t> out = pending_u8(in.shape, in.scale, in.zero_point);
     out.pend = in.pend;
     out.pend_f32 = in.pend_f32;
     out.pend_relu = true;  // (qsrc is not carried over: relu(quantize(x)) is not a plain quantize)
@@ -692,12 +706,7 @@ std::vector<ssize_t> pool_shape(const Tensor<T>& in, ssize_t k, ssize_t s) {
   return {in.shape[0], in.shape[1], (in.shape[2] - k) / s + 1, (in.shape[3] - k) / s + 1};
 }
 Tensor<u8_t> max_pool2d_u8(Tensor<u8_t>& in, ssize_t k, ssize_t s) {  // src/functional.cc:36-64
-  Tensor<u8_t> out;
-  out.shape = pool_shape(in, k, s);
-  out.size = 1;
-  for (ssize_t d : out.shape) out.size *= d;
-  out.scale = in.scale;
-  out.zero_point = in.zero_point;
+  Tensor<u8_t> out = pending_u8(pool_shape(in, k, s), in.scale, in.zero_point);
   Tensor<u8_t> src = in;
   const std::vector<ssize_t> ishp = in.shape, oshp = out.shape;
   const u8_t zp = in.zero_point;
@@ -738,34 +747,79 @@ Tensor<float> add_f32(Tensor<float>& a, Tensor<float>& b) {
   check(i8ie_add_f32(ctx(), a.dptr(), b.dptr(), out.dptr(), a.size));
   return out;
 }
-// The storage an operand of add is read from, as it lies (any layout, border, re-bias).  A producer that has launched for
-// another consumer -- the skip tensor, made bordered / re-biased for the first conv of the block -- is taken from its
-// node's results; one that has not launches plain.
-std::shared_ptr<Storage> add_operand(Tensor<u8_t>& t) {
+// ---- the operand rules of the deferred joining ops (add, mul, cat, lut, avg_pool2d) ----------------
+// The storage an operand is read from, as it lies (any layout, border, re-bias).  A producer that has launched for another
+// consumer -- the skip tensor, made bordered / re-biased for the first conv of the block -- is taken from its node's results;
+// one that has not launches plain.
+std::shared_ptr<Storage> operand_as_it_lies(Tensor<u8_t>& t) {
   if (t.pend) {
-    if (auto st = t.pend->find_any(t.pend_relu)) {
-      t.st = st;
-      t.pend.reset();
-      t.pend_f32.reset();
-      t.qsrc.reset();
-    } else {
-      t.realize();
-    }
+    if (auto st = t.pend->find_any(t.pend_relu)) t.adopt(st);
+    else t.realize();
   }
   if (!t.st) throw std::runtime_error("i8ie: empty tensor");
   t.st->device_ptr();  // (uploads a host-made tensor, waits for an asynchronous upload)
   return t.st;
 }
+// `t` must not launch before `reader`: both are pending and reader = f(t) has not launched.  Launching the reader launches t
+// for f (bordered as f wants it), and t is then found among its node's results instead of launching a second time, plain.
+bool waits_for(const Tensor<u8_t>& t, const Tensor<u8_t>& reader) {
+  return t.pend && reader.pend && reader.pend != t.pend && reader.pend->made.empty() && reader.pend->reads(t.pend.get());
+}
+// The storages of k operands, as they lie: each round launches the first unresolved operand that waits for no other unresolved
+// one.  Two operands: b goes first exactly when waits_for(a, b) -- a then finds waits_for(b, a) false, which a cycle alone could
+// make true, and a cycle cannot be recorded -- and a goes first otherwise.
+std::vector<std::shared_ptr<Storage>> resolve_operands(Tensor<u8_t>* ts, size_t k) {
+  std::vector<std::shared_ptr<Storage>> ss(k);
+  for (size_t round = 0; round < k; ++round) {
+    size_t pick = k;
+    for (size_t i = 0; i < k && pick == k; ++i) {
+      if (ss[i]) continue;
+      bool is_read = false;
+      for (size_t j = 0; j < k && !is_read; ++j) is_read = j != i && !ss[j] && waits_for(ts[i], ts[j]);
+      if (!is_read) pick = i;
+    }
+    if (pick == k) pick = (size_t)(std::find(ss.begin(), ss.end(), nullptr) - ss.begin());  // (a cycle cannot be recorded)
+    ss[pick] = operand_as_it_lies(ts[pick]);
+  }
+  return ss;
+}
+// NCHW operands converted for one launch: (source, its NHWC copy).  Lives as long as the launch is being queued.
+using NhwcCopies = std::vector<std::pair<std::shared_ptr<Storage>, std::shared_ptr<Storage>>>;
+// A rank-4 operand in the engine's layout under the logical dims `shp`.  A view whose storage is NHWC under other logical dims
+// goes back to the reference's order first (the view is defined on it); an NCHW tensor (user-made) takes one conversion into a
+// temporary that `copies` keeps alive, and the same storage coming again gets the same copy.
+std::shared_ptr<Storage> as_engine_nhwc(const std::shared_ptr<Storage>& s, const std::vector<ssize_t>& shp, NhwcCopies& copies) {
+  if (s->layout == I8IE_LAYOUT_NHWC && (s->dn != shp[0] || s->dc != shp[1] || s->dh != shp[2] || s->dw != shp[3])) s->to_nchw();
+  if (s->layout == I8IE_LAYOUT_NHWC) return s;
+  for (const auto& c : copies)
+    if (c.first == s) return c.second;
+  auto tmp = device_storage((size_t)(shp[0] * shp[1] * shp[2] * shp[3]));
+  tmp->set_nhwc(shp, 0);
+  check(i8ie_layout_convert_u8(ctx(), (const uint8_t*)s->device_ptr(), (uint8_t*)tmp->dev, (int)shp[0], (int)shp[1], (int)shp[2],
+                               (int)shp[3], 1, 0, 0));
+  copies.emplace_back(s, tmp);
+  return tmp;
+}
+// Two operands of one shape brought to one layout (add, the equal-shape mul).  Operands that agree stay as they lie: two NCHW
+// tensors take the flat form.  Rank 4 otherwise: the engine keeps NHWC between layers (and a consumer that asked for a border
+// reads NHWC).  Other ranks -- a flattened NHWC activation against plain rows -- both back to the reference's order.
+void reconcile_pair(std::shared_ptr<Storage>& sa, std::shared_ptr<Storage>& sb, const std::vector<ssize_t>& shp, NhwcCopies& copies) {
+  const bool same_dims = sa->dn == sb->dn && sa->dc == sb->dc && sa->dh == sb->dh && sa->dw == sb->dw;
+  if (sa->layout == sb->layout && (sa->layout == I8IE_LAYOUT_NCHW || same_dims)) return;
+  if (shp.size() == 4) {
+    sa = as_engine_nhwc(sa, shp, copies);
+    sb = as_engine_nhwc(sb, shp, copies);
+  } else {
+    sa->to_nchw();
+    sb->to_nchw();
+  }
+}
+
 Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
   if (a.shape != b.shape) throw std::runtime_error("i8ie: add: shapes differ (there is no broadcasting)");
-  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
-  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error("i8ie: add: the output scale must be positive and finite");
-  Tensor<u8_t> out;
-  out.shape = a.shape;
-  out.size = a.size;
-  out.scale = scale;
-  out.zero_point = (u8_t)zp;
-  Tensor<u8_t> ta = a, tb = b;  // share the operands' storage / pending launches
+  check_out_qparams("add", scale, zp);  // (add alone checks neither the operands' scales nor for an empty tensor)
+  Tensor<u8_t> out = pending_u8(a.shape, scale, (u8_t)zp);
+  std::array<Tensor<u8_t>, 2> ops{a, b};  // share the operands' storage / pending launches
   const float s_a = a.scale, s_b = b.scale;
   const u8_t zp_a = a.zero_point, zp_b = b.zero_point, zp_o = (u8_t)zp;
   const std::vector<ssize_t> shp = a.shape;
@@ -773,39 +827,14 @@ Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
   // deferred like max_pool2d's result: relu(add(..)) is one launch, and a consuming conv gets its zero-point border and,
   // where it reads them, re-biased bytes straight from the add kernel
   out.pend = make_pend(
-      [ta, tb, s_a, s_b, zp_a, zp_b, scale, zp_o, shp, n](bool relu, int border, bool s8) mutable {
-        // b = f(a) still pending: launching b first launches a for f (bordered as f wants it), and a is then read as it lies
-        const bool b_first = ta.pend && tb.pend && ta.pend != tb.pend && tb.pend->made.empty() && tb.pend->reads(ta.pend.get());
-        std::shared_ptr<Storage> sa, sb;
-        if (b_first) {
-          sb = add_operand(tb);
-          sa = add_operand(ta);
-        } else {
-          sa = add_operand(ta);
-          sb = add_operand(tb);
-        }
-        const bool four = shp.size() == 4;
-        auto same_nhwc = [](const Storage& x, const Storage& y) {
-          return x.dn == y.dn && x.dc == y.dc && x.dh == y.dh && x.dw == y.dw;
-        };
-        std::shared_ptr<Storage> tmp;  // an NCHW operand converted for this launch
-        if (sa->layout != sb->layout || (sa->layout == I8IE_LAYOUT_NHWC && !same_nhwc(*sa, *sb))) {
-          if (four) {  // the engine keeps NHWC between layers (and a consumer that asked for a border reads NHWC)
-            std::shared_ptr<Storage>& nchw = sa->layout == I8IE_LAYOUT_NCHW ? sa : sb;
-            tmp = device_storage((size_t)n);
-            tmp->set_nhwc(shp, 0);
-            check(i8ie_layout_convert_u8(ctx(), (const uint8_t*)nchw->device_ptr(), (uint8_t*)tmp->dev, (int)shp[0], (int)shp[1],
-                                         (int)shp[2], (int)shp[3], 1, 0, 0));
-            nchw = tmp;
-          } else {  // a flattened NHWC activation against plain rows: back to the reference's order
-            sa->to_nchw();
-            sb->to_nchw();
-          }
-        }
+      [ops, s_a, s_b, zp_a, zp_b, scale, zp_o, shp, n](bool relu, int border, bool s8) mutable {
+        auto ss = resolve_operands(ops.data(), 2);
+        NhwcCopies copies;
+        reconcile_pair(ss[0], ss[1], shp, copies);
+        Storage *sa = ss[0].get(), *sb = ss[1].get();
         std::shared_ptr<Storage> st;
         if (sa->layout == I8IE_LAYOUT_NHWC) {
-          const std::vector<ssize_t> lshp = {sa->dn, sa->dc, sa->dh, sa->dw};
-          st = nhwc_storage(lshp, four ? border : 0, zp_o, s8);
+          st = nhwc_storage({sa->dn, sa->dc, sa->dh, sa->dw}, shp.size() == 4 ? border : 0, zp_o, s8);
           check(i8ie_add_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
                                  sb->border, sb->s8 ? 1 : 0, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, sa->dn, sa->dc, sa->dh,
                                  sa->dw, s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
@@ -843,16 +872,11 @@ Tensor<float> mul_f32(Tensor<float>& a, Tensor<float>& b) {
 }
 Tensor<u8_t> mul_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
   const bool gate = mul_is_gate(a, b);
-  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
-  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error("i8ie: mul: the output scale must be positive and finite");
+  check_out_qparams("mul", scale, zp);
   if (!std::isfinite(a.scale) || !std::isfinite(b.scale)) throw std::runtime_error("i8ie: mul: an operand's scale is not finite");
   if ((!a.st && !a.pend) || (!b.st && !b.pend)) throw std::runtime_error("i8ie: empty tensor");
-  Tensor<u8_t> out;
-  out.shape = a.shape;
-  out.size = a.size;
-  out.scale = scale;
-  out.zero_point = (u8_t)zp;
-  Tensor<u8_t> ta = a, tb = b;  // share the operands' storage / pending launches
+  Tensor<u8_t> out = pending_u8(a.shape, scale, (u8_t)zp);
+  std::array<Tensor<u8_t>, 2> ops{a, b};  // share the operands' storage / pending launches
   const float s_a = a.scale, s_b = b.scale;
   const u8_t zp_a = a.zero_point, zp_b = b.zero_point, zp_o = (u8_t)zp;
   const std::vector<ssize_t> shp = a.shape;
@@ -860,60 +884,28 @@ Tensor<u8_t> mul_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
   // deferred like add's result: relu(mul(..)) is one launch, and a consuming conv gets its zero-point border and, where it
   // reads them, re-biased bytes straight from the mul kernel
   out.pend = make_pend(
-      [ta, tb, gate, s_a, s_b, zp_a, zp_b, scale, zp_o, shp, n](bool relu, int border, bool s8) mutable {
-        // b = f(a) still pending (the gate of a squeeze-and-excitation block is): launching b first launches a for f, and a
-        // is then read as it lies.  And the other way round.
-        const bool b_first = ta.pend && tb.pend && ta.pend != tb.pend && tb.pend->made.empty() && tb.pend->reads(ta.pend.get());
-        std::shared_ptr<Storage> sa, sb;
-        if (b_first) {
-          sb = add_operand(tb);
-          sa = add_operand(ta);
-        } else {
-          sa = add_operand(ta);
-          sb = add_operand(tb);
-        }
-        const bool four = shp.size() == 4;
-        auto is_nhwc_of = [](const Storage& x, ssize_t dn, ssize_t dc, ssize_t dh, ssize_t dw) {
-          return x.layout == I8IE_LAYOUT_NHWC && x.dn == dn && x.dc == dc && x.dh == dh && x.dw == dw;
-        };
-        std::shared_ptr<Storage> tmp;  // an NCHW operand converted for this launch
-        auto to_nhwc = [&](std::shared_ptr<Storage>& s) {
-          tmp = device_storage((size_t)n);
-          tmp->set_nhwc(shp, 0);
-          check(i8ie_layout_convert_u8(ctx(), (const uint8_t*)s->device_ptr(), (uint8_t*)tmp->dev, (int)shp[0], (int)shp[1], (int)shp[2],
-                                       (int)shp[3], 1, 0, 0));
-          s = tmp;
-        };
+      [ops, gate, s_a, s_b, zp_a, zp_b, scale, zp_o, shp, n](bool relu, int border, bool s8) mutable {
+        // (the gate of a squeeze-and-excitation block is f(a), still pending: it launches first, and a is read as it lies)
+        auto ss = resolve_operands(ops.data(), 2);
+        NhwcCopies copies;
+        std::shared_ptr<Storage>& sa = ss[0];
+        std::shared_ptr<Storage>& sb = ss[1];
         std::shared_ptr<Storage> st;
         if (gate) {
-          // a in the engine's layout (a view whose storage is NHWC under other logical dims goes back to the reference's
-          // order first; a user-made NCHW tensor takes one layout conversion)
-          if (sa->layout == I8IE_LAYOUT_NHWC && !is_nhwc_of(*sa, shp[0], shp[1], shp[2], shp[3])) sa->to_nchw();
-          if (sa->layout == I8IE_LAYOUT_NCHW) to_nhwc(sa);
+          sa = as_engine_nhwc(sa, shp, copies);
           // the gate as its producer left it: an [n, c, 1, 1] NHWC buffer with its border and re-bias, or plain rows (an
           // NCHW [n, c, 1, 1] tensor is the same bytes)
-          if (!is_nhwc_of(*sb, shp[0], shp[1], 1, 1)) sb->to_nchw();
-          const bool g_nhwc = sb->layout == I8IE_LAYOUT_NHWC;
+          const bool g_nhwc = sb->layout == I8IE_LAYOUT_NHWC && sb->dn == shp[0] && sb->dc == shp[1] && sb->dh == 1 && sb->dw == 1;
+          if (!g_nhwc) sb->to_nchw();
           st = nhwc_storage(shp, border, zp_o, s8);
           check(i8ie_mul_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
                                  g_nhwc ? sb->border : 0, g_nhwc && sb->s8 ? 1 : 0, 1, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0,
                                  (int)shp[0], (int)shp[1], (int)shp[2], (int)shp[3], s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
           return st;
         }
-        auto same_nhwc = [](const Storage& x, const Storage& y) {
-          return x.dn == y.dn && x.dc == y.dc && x.dh == y.dh && x.dw == y.dw;
-        };
-        if (sa->layout != sb->layout || (sa->layout == I8IE_LAYOUT_NHWC && !same_nhwc(*sa, *sb))) {
-          if (four) {  // the engine keeps NHWC between layers (and a consumer that asked for a border reads NHWC)
-            to_nhwc(sa->layout == I8IE_LAYOUT_NCHW ? sa : sb);
-          } else {  // a flattened NHWC activation against plain rows: back to the reference's order
-            sa->to_nchw();
-            sb->to_nchw();
-          }
-        }
+        reconcile_pair(sa, sb, shp, copies);
         if (sa->layout == I8IE_LAYOUT_NHWC) {
-          const std::vector<ssize_t> lshp = {sa->dn, sa->dc, sa->dh, sa->dw};
-          st = nhwc_storage(lshp, four ? border : 0, zp_o, s8);
+          st = nhwc_storage({sa->dn, sa->dc, sa->dh, sa->dw}, shp.size() == 4 ? border : 0, zp_o, s8);
           check(i8ie_mul_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
                                  sb->border, sb->s8 ? 1 : 0, 0, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, sa->dn, sa->dc, sa->dh,
                                  sa->dw, s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
@@ -971,39 +963,17 @@ Tensor<float> cat_f32(std::vector<Tensor<float>> ts) {
 }
 Tensor<u8_t> cat_u8(std::vector<Tensor<u8_t>> ts, float scale, int zp) {
   const std::vector<ssize_t> shp = cat_shape(ts);
-  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
-  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error("i8ie: cat: the output scale must be positive and finite");
+  check_out_qparams("cat", scale, zp);
   for (const auto& t : ts)
     if (!std::isfinite(t.scale)) throw std::runtime_error("i8ie: cat: an input's scale is not finite");
-  Tensor<u8_t> out;
-  out.shape = shp;
-  out.size = 1;
-  for (ssize_t d : shp) out.size *= d;
-  out.scale = scale;
-  out.zero_point = (u8_t)zp;
+  Tensor<u8_t> out = pending_u8(shp, scale, (u8_t)zp);
   const u8_t zp_o = (u8_t)zp;
   const ssize_t total = out.size;
   // deferred like add's result: relu(cat(..)) is one launch, and a consuming conv gets its zero-point border and, where it
   // reads them, re-biased bytes straight from the concat kernel.  (the closure's copies share the inputs' storage / launches)
   auto node = make_pend([ts, scale, zp_o, shp, total](bool relu, int border, bool s8) mutable {
     const int k = (int)ts.size();
-    // The inputs as they lie (add_operand).  A pending input that reads another one launches first: that launches the other
-    // for it (bordered as it wants it), and the other is then found among its node's results.
-    std::vector<std::shared_ptr<Storage>> ss((size_t)k);
-    for (int round = 0; round < k; ++round) {
-      int pick = -1;
-      for (int i = 0; i < k && pick < 0; ++i) {
-        if (ss[i]) continue;
-        bool is_read = false;
-        for (int j = 0; j < k && !is_read; ++j)
-          is_read = j != i && !ss[j] && ts[i].pend && ts[j].pend && ts[j].pend != ts[i].pend && ts[j].pend->made.empty() &&
-                    ts[j].pend->reads(ts[i].pend.get());
-        if (!is_read) pick = i;
-      }
-      if (pick < 0) pick = (int)(std::find(ss.begin(), ss.end(), nullptr) - ss.begin());  // (a cycle cannot be recorded)
-      ss[pick] = add_operand(ts[pick]);
-    }
-    const bool four = shp.size() == 4;
+    auto ss = resolve_operands(ts.data(), ts.size());
     bool any_nhwc = false;
     for (int i = 0; i < k; ++i) any_nhwc = any_nhwc || ss[i]->layout == I8IE_LAYOUT_NHWC;
     const uint8_t* in[I8IE_CONCAT_MAX_INPUTS];
@@ -1014,29 +984,13 @@ Tensor<u8_t> cat_u8(std::vector<Tensor<u8_t>> ts, float scale, int zp) {
       zp_in[i] = ts[i].zero_point;
     }
     std::shared_ptr<Storage> st;
-    if (four && any_nhwc) {  // the engine keeps NHWC between layers (and a consumer that asked for a border reads NHWC)
+    if (shp.size() == 4 && any_nhwc) {  // the engine keeps NHWC between layers (and a consumer that asked for a border reads NHWC)
       int c_in[I8IE_CONCAT_MAX_INPUTS], b_in[I8IE_CONCAT_MAX_INPUTS], x_in[I8IE_CONCAT_MAX_INPUTS];
-      std::vector<std::shared_ptr<Storage>> tmps;  // NCHW inputs converted for this launch
+      NhwcCopies copies;  // (the same tensor again takes its conversion too)
       for (int i = 0; i < k; ++i) {
-        const std::vector<ssize_t>& is = ts[i].shape;
-        // (a view whose storage is NHWC under other logical dims goes back to the reference's order, which the view is defined on)
-        if (ss[i]->layout == I8IE_LAYOUT_NHWC && (ss[i]->dn != is[0] || ss[i]->dc != is[1] || ss[i]->dh != is[2] || ss[i]->dw != is[3]))
-          ss[i]->to_nchw();
-        if (ss[i]->layout == I8IE_LAYOUT_NCHW) {
-          std::shared_ptr<Storage> src = ss[i];
-          for (int j = 0; j < i; ++j)
-            if (ts[j].st == src) ss[i] = ss[j];  // the same tensor again: its conversion too
-          if (ss[i] == src) {
-            auto tmp = device_storage((size_t)ts[i].size);
-            tmp->set_nhwc(is, 0);
-            check(i8ie_layout_convert_u8(ctx(), (const uint8_t*)src->device_ptr(), (uint8_t*)tmp->dev, (int)is[0], (int)is[1], (int)is[2],
-                                         (int)is[3], 1, 0, 0));
-            tmps.push_back(tmp);
-            ss[i] = tmp;
-          }
-        }
+        ss[i] = as_engine_nhwc(ss[i], ts[i].shape, copies);
         in[i] = (const uint8_t*)ss[i]->device_ptr();
-        c_in[i] = (int)is[1];
+        c_in[i] = (int)ts[i].shape[1];
         b_in[i] = ss[i]->border;
         x_in[i] = ss[i]->s8 ? 1 : 0;
       }
@@ -1083,14 +1037,8 @@ Tensor<float> avg_pool_f32(Tensor<float>& in, ssize_t k, ssize_t s, bool global)
                            (int)kh, (int)kw, (int)s));
   return out;
 }
-std::shared_ptr<Storage> add_operand(Tensor<u8_t>& t);
 Tensor<u8_t> avg_pool_u8(Tensor<u8_t>& in, ssize_t k, ssize_t s, bool global) {
-  Tensor<u8_t> out;
-  out.shape = avg_pool_shape(in, k, k, s, global);
-  out.size = 1;
-  for (ssize_t d : out.shape) out.size *= d;
-  out.scale = in.scale;  // as max_pool2d: the input's quantisation parameters, unchanged
-  out.zero_point = in.zero_point;
+  Tensor<u8_t> out = pending_u8(avg_pool_shape(in, k, k, s, global), in.scale, in.zero_point);  // (as max_pool2d: the input's qparams)
   Tensor<u8_t> src = in;
   const std::vector<ssize_t> ishp = in.shape, oshp = out.shape;
   const u8_t zp = in.zero_point;
@@ -1099,9 +1047,7 @@ Tensor<u8_t> avg_pool_u8(Tensor<u8_t>& in, ssize_t k, ssize_t s, bool global) {
   // zero-point border and, where it reads them, re-biased bytes straight from the pool kernel
   out.pend = make_pend(
       [src, ishp, oshp, zp, kh, kw, ss](bool relu, int border, bool s8) mutable {
-        // the input as it lies (any border, plain or re-biased): a pending producer launches plain, one that has launched
-        // for another consumer is not launched again
-        std::shared_ptr<Storage> si = add_operand(src);
+        std::shared_ptr<Storage> si = operand_as_it_lies(src);
         const size_t logical = (size_t)oshp[0] * oshp[1] * oshp[2] * oshp[3];
         std::shared_ptr<Storage> st;
         if (si->layout == I8IE_LAYOUT_NHWC) {
@@ -1131,14 +1077,9 @@ Tensor<float> activation_f32(Tensor<float>& in, int kind, float param) {
 }
 // out = table[in] with the result's (scale, zp): table maps plain bytes to plain bytes
 Tensor<u8_t> lut_u8(Tensor<u8_t>& in, const LutBytes& table, float scale, int zp) {
-  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
-  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error("i8ie: lut: the output scale must be positive and finite");
+  check_out_qparams("lut", scale, zp);
   if (!in.st && !in.pend) throw std::runtime_error("i8ie: empty tensor");
-  Tensor<u8_t> out;
-  out.shape = in.shape;
-  out.size = in.size;
-  out.scale = scale;
-  out.zero_point = (u8_t)zp;
+  Tensor<u8_t> out = pending_u8(in.shape, scale, (u8_t)zp);
   Tensor<u8_t> src = in;
   const std::vector<ssize_t> shp = in.shape;
   const ssize_t total = in.size;
@@ -1147,23 +1088,14 @@ Tensor<u8_t> lut_u8(Tensor<u8_t>& in, const LutBytes& table, float scale, int zp
   // consuming conv gets its zero-point border and, where it reads them, re-biased bytes straight from the lookup kernel
   out.pend = make_pend(
       [src, table, zp_o, shp, total](bool relu, int border, bool s8) mutable {
-        // the input as it lies (any border, plain or re-biased): a pending producer launches plain, one that has launched
-        // for another consumer is not launched again
-        std::shared_ptr<Storage> si = add_operand(src);
+        std::shared_ptr<Storage> si = operand_as_it_lies(src);
         LutBytes t = table;
         if (relu)
           for (u8_t& b : t) b = std::max(b, zp_o);
         std::shared_ptr<Storage> st;
         if (shp.size() == 4) {  // the engine keeps NHWC between layers (and a consumer that asked for a border reads NHWC)
-          // (a view whose storage is NHWC under other logical dims goes back to the reference's order, which the view is defined on)
-          if (si->layout == I8IE_LAYOUT_NHWC && (si->dn != shp[0] || si->dc != shp[1] || si->dh != shp[2] || si->dw != shp[3])) si->to_nchw();
-          if (si->layout == I8IE_LAYOUT_NCHW) {  // a user-made tensor: one layout conversion
-            auto tmp = device_storage((size_t)total);
-            tmp->set_nhwc(shp, 0);
-            check(i8ie_layout_convert_u8(ctx(), (const uint8_t*)si->device_ptr(), (uint8_t*)tmp->dev, (int)shp[0], (int)shp[1], (int)shp[2],
-                                         (int)shp[3], 1, 0, 0));
-            si = tmp;
-          }
+          NhwcCopies copies;
+          si = as_engine_nhwc(si, shp, copies);
           st = nhwc_storage(shp, border, zp_o, s8);
           check(i8ie_lut_u8_nhwc(ctx(), (const uint8_t*)si->device_ptr(), si->border, si->s8 ? 1 : 0, (uint8_t*)st->dev, st->border,
                                  st->s8 ? 1 : 0, (int)shp[0], (int)shp[1], (int)shp[2], (int)shp[3], t.data()));
@@ -1177,7 +1109,7 @@ Tensor<u8_t> lut_u8(Tensor<u8_t>& in, const LutBytes& table, float scale, int zp
   return out;
 }
 Tensor<u8_t> activation_u8(Tensor<u8_t>& in, int kind, float param, float scale, int zp) {
-  if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+  check_zero_point(zp);
   LutBytes table;
   check(i8ie_activation_table(kind, param, in.scale, in.zero_point, scale, (uint8_t)zp, table.data()));
   return lut_u8(in, table, scale, zp);
@@ -1288,7 +1220,81 @@ void calib_sample(Calibrator& cal, Tensor<float>& out) {
 }
 
 // ------------------------------------------------------------------ layers ----
-class BaseLayer {
+// The prepare / convert state machine of src/layer.cc:28-54 around a layer's output (scale, zero_point): what the layers with
+// weights and those without share.
+class QuantState {
+ public:
+  QuantState() = default;
+  QuantState(const QuantState&) = delete;
+  QuantState& operator=(const QuantState&) = delete;
+  void prepare() {  // src/layer.cc:28-35
+    if (is_quantized_) {
+      std::cerr << "already quantized" << std::endl;
+      return;
+    }
+    cal_ = std::make_unique<Calibrator>();
+    is_preparing_ = true;
+  }
+  void set_output_qparams(float s, int zp) {  // additive: inject what calibration would produce
+    check_zero_point(zp);
+    scale_ = s;
+    zero_point_ = (u8_t)zp;
+    qparams_overridden_ = true;
+    output_qparams_changed();
+  }
+  std::tuple<float, int> output_qparams() const { return std::make_tuple(scale_, (int)zero_point_); }
+  bool is_quantized() const { return is_quantized_; }
+
+ protected:
+  ~QuantState() = default;
+  virtual void output_qparams_changed() {}  // (a layer with a live handle pushes them into it)
+  // the calibration half of convert() (src/layer.cc:36-47): false when the layer is quantized already
+  bool convert_qparams() {
+    if (is_quantized_) {
+      std::cerr << "already quantized" << std::endl;
+      return false;
+    }
+    if (!is_preparing_) {
+      if (!qparams_overridden_) std::cerr << "No prepared, use default config" << std::endl;
+    } else {
+      float s;
+      u8_t z;
+      std::tie(s, z) = cal_->get_range(1);
+      if (!qparams_overridden_) {
+        scale_ = s;
+        zero_point_ = z;
+      }
+      cal_.reset();
+    }
+    return true;
+  }
+  void set_quantized() {
+    cal_.reset();
+    is_preparing_ = false;
+    is_quantized_ = true;
+  }
+  void maybe_sample(Tensor<float>& out) {  // src/conv2d.cc:94-96, src/fully_connected.cc:17-19
+    if (is_preparing_) calib_sample(*cal_, out);
+  }
+
+  std::unique_ptr<Calibrator> cal_;
+  bool is_preparing_ = false;
+  bool is_quantized_ = false;
+  bool qparams_overridden_ = false;
+  float scale_ = 1;       // include/layer.h:46
+  u8_t zero_point_ = 0;   // include/layer.h:47
+};
+
+// x.reshape(n, -1) of a border-free NHWC activation of m images that still lies as its conv left it: its storage (a Linear
+// layer then walks K in (h, w, c) order instead of asking for the reference's order), or null
+const Storage* flattened_nhwc(const Tensor<u8_t>& t, int m) {
+  const Storage* s = t.st.get();
+  const bool yes = s && s->layout == I8IE_LAYOUT_NHWC && s->border == 0 && s->dn == m && s->dh * s->dw > 1 &&
+                   (ssize_t)s->dn * s->dc * s->dh * s->dw == t.size;
+  return yes ? s : nullptr;
+}
+
+class BaseLayer : public QuantState {
  public:
   BaseLayer(std::vector<ssize_t> wshape, ssize_t out_channel) : wshape_(std::move(wshape)) {
     ssize_t n = 1;
@@ -1304,8 +1310,6 @@ class BaseLayer {
     load_bias(b);
   }
   virtual ~BaseLayer() { release_fp32_dev(); }
-  BaseLayer(const BaseLayer&) = delete;
-  BaseLayer& operator=(const BaseLayer&) = delete;
 
   void load_weight(py::array_t<float, py::array::c_style | py::array::forcecast> w) {  // include/layer.h:15-20
     if (!has_fp32_) throw std::runtime_error("i8ie: load_weight: layer is already converted");
@@ -1319,31 +1323,8 @@ class BaseLayer {
     b_.assign(b.data(), b.data() + b.size());
     release_fp32_dev();
   }
-  void prepare() {  // src/layer.cc:28-35
-    if (is_quantized_) {
-      std::cerr << "already quantized" << std::endl;
-      return;
-    }
-    cal_ = std::make_unique<Calibrator>();
-    is_preparing_ = true;
-  }
   void convert(bool per_channel = false) {  // src/layer.cc:36-54 (per_channel: the opt-in per-output-channel rule)
-    if (is_quantized_) {
-      std::cerr << "already quantized" << std::endl;
-      return;
-    }
-    if (!is_preparing_) {
-      if (!qparams_overridden_) std::cerr << "No prepared, use default config" << std::endl;
-    } else {
-      float s;
-      u8_t z;
-      std::tie(s, z) = cal_->get_range(1);
-      if (!qparams_overridden_) {
-        scale_ = s;
-        zero_point_ = z;
-      }
-      cal_.reset();
-    }
+    if (!convert_qparams()) return;
     check_shapes();
     const ssize_t n = (ssize_t)b_.size();
     qw_.resize(w_.size());
@@ -1360,30 +1341,14 @@ class BaseLayer {
                                  reinterpret_cast<int8_t*>(qw_.data()), reinterpret_cast<int8_t*>(qb_.data()),
                                  &w_scale_));
     }
-    i8ie_layer* raw = make_handle(n);
-    q_ = std::shared_ptr<i8ie_layer>(raw, [](i8ie_layer* l) { i8ie_layer_destroy(l); });
-    check(i8ie_layer_set_output_qparams(q_.get(), scale_, zero_point_));
-    is_preparing_ = false;
-    is_quantized_ = true;
-    std::vector<float>().swap(w_);  // src/layer.cc:52-53: FP32 weights are released
-    std::vector<float>().swap(b_);
-    has_fp32_ = false;
-    release_fp32_dev();
+    install_handle();
   }
-  void set_output_qparams(float s, int zp) {  // additive: inject what calibration would produce
-    if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
-    scale_ = s;
-    zero_point_ = (u8_t)zp;
-    qparams_overridden_ = true;
-    if (q_) check(i8ie_layer_set_output_qparams(q_.get(), scale_, zero_point_));
-  }
-  std::tuple<float, int> output_qparams() const { return std::make_tuple(scale_, (int)zero_point_); }
   // additive: restore a converted layer from saved INT8 weights (what convert() would have produced)
   // w_scale: a number (per-tensor layer) or an array of one scale per output feature (per-channel layer)
   void load_quantized(py::array_t<s8_t, py::array::c_style | py::array::forcecast> qw,
                       py::array_t<s8_t, py::array::c_style | py::array::forcecast> qb, py::object w_scale, float s_out,
                       int zp_out) {
-    if (zp_out < 0 || zp_out > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+    check_zero_point(zp_out);
     std::vector<ssize_t> shp(qw.shape(), qw.shape() + qw.ndim());
     if (shp.size() != wshape_.size()) throw std::runtime_error("i8ie: load_quantized: weight rank mismatch");
     check_weight_shape(shp, "load_quantized");
@@ -1406,16 +1371,7 @@ class BaseLayer {
     scale_ = s_out;
     zero_point_ = (u8_t)zp_out;
     qparams_overridden_ = true;
-    i8ie_layer* raw = make_handle((ssize_t)qb_.size());
-    q_ = std::shared_ptr<i8ie_layer>(raw, [](i8ie_layer* l) { i8ie_layer_destroy(l); });
-    check(i8ie_layer_set_output_qparams(q_.get(), scale_, zero_point_));
-    cal_.reset();
-    is_preparing_ = false;
-    is_quantized_ = true;
-    std::vector<float>().swap(w_);
-    std::vector<float>().swap(b_);
-    has_fp32_ = false;
-    release_fp32_dev();
+    install_handle();
   }
   py::array_t<s8_t> q_weight() const {
     need_quantized();
@@ -1442,21 +1398,30 @@ class BaseLayer {
     return a;
   }
   bool is_per_channel() const { return is_quantized_ && per_channel_; }
-  bool is_quantized() const { return is_quantized_; }
 
  protected:
+  void output_qparams_changed() override {
+    if (q_) check(i8ie_layer_set_output_qparams(q_.get(), scale_, zero_point_));
+  }
+  // the tail convert() and load_quantized() share: the library's layer from the INT8 weights, the output qparams into it,
+  // the FP32 weights released (src/layer.cc:52-53), the state flipped
+  void install_handle() {
+    i8ie_layer* raw = make_handle((ssize_t)qb_.size());
+    q_ = std::shared_ptr<i8ie_layer>(raw, [](i8ie_layer* l) { i8ie_layer_destroy(l); });
+    check(i8ie_layer_set_output_qparams(q_.get(), scale_, zero_point_));
+    set_quantized();
+    std::vector<float>().swap(w_);
+    std::vector<float>().swap(b_);
+    has_fp32_ = false;
+    release_fp32_dev();
+  }
   virtual void check_shapes() const = 0;
   // a layer that was given its channel counts refuses a weight of another shape (Conv2d with groups: [out, in/groups, k, k])
   virtual void check_weight_shape(const std::vector<ssize_t>&, const char*) const {}
   virtual i8ie_layer* make_handle(ssize_t n) = 0;
   // Deferred INT8 forward: returns a tensor whose launch happens when it is first needed.
   Tensor<u8_t> defer(Tensor<u8_t>& in, std::vector<ssize_t> oshape, int m, int h, int w, bool spatial) {
-    Tensor<u8_t> out;
-    out.shape = std::move(oshape);
-    out.size = 1;
-    for (ssize_t d : out.shape) out.size *= d;
-    out.scale = scale_;
-    out.zero_point = zero_point_;
+    Tensor<u8_t> out = pending_u8(std::move(oshape), scale_, zero_point_);
     std::shared_ptr<i8ie_layer> handle = q_;
     Tensor<u8_t> src = in;  // shares the input's storage / pending launch
     const float s_in = in.scale;
@@ -1503,10 +1468,7 @@ class BaseLayer {
         ip = (src.st && src.st->s8 && reads) ? src.dptr_raw() : src.dptr_any();
       } else {
         src.realize(0);
-        Storage* s = src.st.get();
-        // x.reshape(n, -1) of an NHWC activation: the Linear layer walks K in (h, w, c) order instead
-        if (s && s->layout == I8IE_LAYOUT_NHWC && s->border == 0 && s->dn == m && s->dh * s->dw > 1 &&
-            (ssize_t)s->dn * s->dc * s->dh * s->dw == src.size) {
+        if (const Storage* s = flattened_nhwc(src, m)) {
           ip = src.dptr_any();
           h = s->dh;
           w = s->dw;
@@ -1544,11 +1506,9 @@ class BaseLayer {
       out.pend_f32 = std::make_shared<std::function<std::shared_ptr<Storage>(bool)>>(
           [handle, src2, s_in, zp_in, m, obytes](bool relu) mutable {
             src2.realize(0);
-            Storage* s = src2.st.get();
             const uint8_t* ip;
             int lay = I8IE_LAYOUT_NCHW, hh = 0, ww = 0;
-            if (s && s->layout == I8IE_LAYOUT_NHWC && s->border == 0 && s->dn == m && s->dh * s->dw > 1 &&
-                (ssize_t)s->dn * s->dc * s->dh * s->dw == src2.size) {
+            if (const Storage* s = flattened_nhwc(src2, m)) {
               ip = src2.dptr_any();
               lay = I8IE_LAYOUT_NHWC;
               hh = s->dh;
@@ -1564,6 +1524,22 @@ class BaseLayer {
           });
     }
     return out;
+  }
+  // forward_debug: the eager forward in the reference's order, with the int32 accumulators (shape `ashape`) beside the result
+  std::tuple<Tensor<u8_t>, py::object> forward_acc(Tensor<u8_t>& in, std::vector<ssize_t> oshape, std::vector<ssize_t> ashape, int m, int h,
+                                                   int w) {
+    Tensor<u8_t> out = pending_u8(std::move(oshape), scale_, zero_point_);
+    out.st = device_storage((size_t)out.size);
+    Tensor<int32_t> acc(std::move(ashape));
+    check(i8ie_layer_forward(q_.get(), in.dptr(), m, h, w, in.scale, in.zero_point, out.dptr(), acc.dptr()));
+    py::object acc_np = acc.numpy();
+    return std::make_tuple(std::move(out), acc_np);
+  }
+  // Conv2d / ConvTranspose2d on a u8 tensor: recorded, or the debug forward
+  std::tuple<Tensor<u8_t>, py::object> forward_spatial_u8(Tensor<u8_t>& in, std::vector<ssize_t> oshape, bool want_acc) {
+    const int n = (int)in.shape[0], h = (int)in.shape[2], w = (int)in.shape[3];
+    if (!want_acc) return std::make_tuple(defer(in, oshape, n, h, w, true), py::object(py::none()));
+    return forward_acc(in, oshape, {oshape[0], oshape[2] * oshape[3], oshape[1]}, n, h, w);
   }
   void need_quantized() const {
     if (!is_quantized_) throw std::runtime_error("i8ie: layer is not converted (call convert() first)");
@@ -1586,9 +1562,6 @@ class BaseLayer {
     }
     w_dev_ = b_dev_ = nullptr;
   }
-  void maybe_sample(Tensor<float>& out) {  // src/conv2d.cc:94-96, src/fully_connected.cc:17-19
-    if (is_preparing_) calib_sample(*cal_, out);
-  }
 
   std::vector<ssize_t> wshape_;
   std::vector<float> w_, b_;
@@ -1599,12 +1572,6 @@ class BaseLayer {
   float w_scale_ = 1;
   bool per_channel_ = false;
   std::vector<float> w_scales_;  // per-channel layers: s_w[j]
-  std::unique_ptr<Calibrator> cal_;
-  bool is_preparing_ = false;
-  bool is_quantized_ = false;
-  bool qparams_overridden_ = false;
-  float scale_ = 1;       // include/layer.h:46
-  u8_t zero_point_ = 0;   // include/layer.h:47
   std::shared_ptr<i8ie_layer> q_;
 };
 
@@ -1633,13 +1600,7 @@ class Linear : public BaseLayer {
       throw std::runtime_error("i8ie: Linear: input's last dimension must equal in_features");
     const ssize_t m = in.size / k;
     if (!want_acc) return std::make_tuple(defer(in, {m, n}, (int)m, 0, 0, false), py::object(py::none()));
-    Tensor<u8_t> out({m, n});
-    out.scale = scale_;
-    out.zero_point = zero_point_;
-    Tensor<int32_t> acc({m, n});
-    check(i8ie_layer_forward(q_.get(), in.dptr(), (int)m, 0, 0, in.scale, in.zero_point, out.dptr(), acc.dptr()));
-    py::object acc_np = acc.numpy();
-    return std::make_tuple(std::move(out), acc_np);
+    return forward_acc(in, {m, n}, {m, n}, (int)m, 0, 0);
   }
 
  protected:
@@ -1696,16 +1657,7 @@ class Conv2d : public BaseLayer {
   }
   std::tuple<Tensor<u8_t>, py::object> forward_u8(Tensor<u8_t>& in, bool want_acc) {  // src/conv2d.cc:100-142
     need_quantized();
-    std::vector<ssize_t> oshape = out_shape(in.shape);
-    const int n = (int)in.shape[0], h = (int)in.shape[2], w = (int)in.shape[3];
-    if (!want_acc) return std::make_tuple(defer(in, oshape, n, h, w, true), py::object(py::none()));
-    Tensor<u8_t> out(oshape);
-    out.scale = scale_;
-    out.zero_point = zero_point_;
-    Tensor<int32_t> acc({out.shape[0], out.shape[2] * out.shape[3], out.shape[1]});
-    check(i8ie_layer_forward(q_.get(), in.dptr(), n, h, w, in.scale, in.zero_point, out.dptr(), acc.dptr()));
-    py::object acc_np = acc.numpy();
-    return std::make_tuple(std::move(out), acc_np);
+    return forward_spatial_u8(in, out_shape(in.shape), want_acc);
   }
 
  protected:
@@ -1831,16 +1783,7 @@ class ConvTranspose2d : public BaseLayer {
   }
   std::tuple<Tensor<u8_t>, py::object> forward_u8(Tensor<u8_t>& in, bool want_acc) {
     need_quantized();
-    std::vector<ssize_t> oshape = out_shape(in.shape);
-    const int n = (int)in.shape[0], h = (int)in.shape[2], w = (int)in.shape[3];
-    if (!want_acc) return std::make_tuple(defer(in, oshape, n, h, w, true), py::object(py::none()));
-    Tensor<u8_t> out(oshape);
-    out.scale = scale_;
-    out.zero_point = zero_point_;
-    Tensor<int32_t> acc({out.shape[0], out.shape[2] * out.shape[3], out.shape[1]});
-    check(i8ie_layer_forward(q_.get(), in.dptr(), n, h, w, in.scale, in.zero_point, out.dptr(), acc.dptr()));
-    py::object acc_np = acc.numpy();
-    return std::make_tuple(std::move(out), acc_np);
+    return forward_spatial_u8(in, out_shape(in.shape), want_acc);
   }
 
  protected:
@@ -1878,68 +1821,24 @@ class ConvTranspose2d : public BaseLayer {
 // A layer without weights (the residual Add, the channel Concat): the layers' prepare / convert state machine
 // (src/layer.cc:28-54) around its output (scale, zero_point); FP32 tensors join in FP32 (and are sampled while preparing),
 // u8 tensors after convert().
-class Weightless {
+class Weightless : public QuantState {
  public:
-  Weightless() = default;
-  Weightless(const Weightless&) = delete;
-  Weightless& operator=(const Weightless&) = delete;
-  void prepare() {
-    if (is_quantized_) {
-      std::cerr << "already quantized" << std::endl;
-      return;
-    }
-    cal_ = std::make_unique<Calibrator>();
-    is_preparing_ = true;
-  }
   void convert(bool /*per_channel: there are no weights*/ = false) {
-    if (is_quantized_) {
-      std::cerr << "already quantized" << std::endl;
-      return;
-    }
-    if (!is_preparing_) {
-      if (!qparams_overridden_) std::cerr << "No prepared, use default config" << std::endl;
-    } else {
-      float s;
-      u8_t z;
-      std::tie(s, z) = cal_->get_range(1);
-      if (!qparams_overridden_) {
-        scale_ = s;
-        zero_point_ = z;
-      }
-      cal_.reset();
-    }
-    is_preparing_ = false;
-    is_quantized_ = true;
+    if (convert_qparams()) set_quantized();
   }
-  void set_output_qparams(float s, int zp) {
-    if (zp < 0 || zp > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
-    scale_ = s;
-    zero_point_ = (u8_t)zp;
-    qparams_overridden_ = true;
-  }
-  std::tuple<float, int> output_qparams() const { return std::make_tuple(scale_, (int)zero_point_); }
   void load_quantized(float s_out, int zp_out) {  // what convert() would have left behind
     set_output_qparams(s_out, zp_out);
-    cal_.reset();
-    is_preparing_ = false;
-    is_quantized_ = true;
+    set_quantized();
   }
-  bool is_quantized() const { return is_quantized_; }
 
  protected:
   Tensor<float> sampled(Tensor<float> out) {  // what a preparing layer does with its FP32 result
-    if (is_preparing_) calib_sample(*cal_, out);
+    maybe_sample(out);
     return out;
   }
   void need_quantized(const char* what) const {
     if (!is_quantized_) throw std::runtime_error(std::string("i8ie: ") + what + " is not converted (call convert() first)");
   }
-  std::unique_ptr<Calibrator> cal_;
-  bool is_preparing_ = false;
-  bool is_quantized_ = false;
-  bool qparams_overridden_ = false;
-  float scale_ = 1;
-  u8_t zero_point_ = 0;
 };
 class Add : public Weightless {
  public:
@@ -2079,7 +1978,8 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
     return lut_u8(x, lut_from_array(table), scale, zp);
   }, py::arg("x"), py::arg("table"), py::arg("scale"), py::arg("zero_point"));
   m.def("activation_table", [](int kind, float param, float s_in, int zp_in, float s_out, int zp_out) {
-    if (zp_in < 0 || zp_in > 255 || zp_out < 0 || zp_out > 255) throw std::runtime_error("i8ie: zero point must be in [0, 255]");
+    check_zero_point(zp_in);
+    check_zero_point(zp_out);
     py::array_t<uint8_t> out(256);
     check(i8ie_activation_table(kind, param, s_in, (uint8_t)zp_in, s_out, (uint8_t)zp_out, out.mutable_data()));
     return out;
