@@ -5,7 +5,7 @@
 //   reference: src/fully_connected.cc:22-52, src/conv2d.cc:100-142,
 //              src/layer.cc:6-26,36-54
 //
-// Conv2d has four execution paths, all producing the reference's bytes:
+// Conv2d has five execution paths, all producing the reference's bytes (how a forward reaches them: DESIGN.md section 4a):
 //   A  channels % 16 == 0: implicit GEMM over NHWC activations (i8ie_igemm.hip)
 //   B  channels <= 4 and stride % 4 == 0 (AlexNet conv1): the NCHW input is repacked
 //      once into a physically padded, 4-pixel-grouped NHWC image; then path A's kernel
@@ -313,6 +313,21 @@ int i8ie_conv2d_u8s8(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int 
 static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const int8_t* qb_host, int n, int K, int c,
                         int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups = 1, int opad = -1);
 
+// the stateless grouped / transposed calls: the temporary handle `L` runs one NCHW forward with the caller's offset vector (it
+// carries the bias term) instead of the handle's own, and is destroyed
+static int run_once(i8ie_layer* L, const uint8_t* in, int n, int h, int w, uint8_t zp_in, const int32_t* oc, float s_in,
+                    float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
+  L->s_out = s_out;
+  L->zp_out = zp_out;
+  int rc = i8ie_launch_finish_offsets(L->ctx, oc, L->wsum, L->qb, s_in, L->n, L->ocp, nullptr);
+  L->oc_valid = rc == I8IE_OK;
+  L->oc_s_in = s_in;
+  L->oc_zp_in = zp_in;
+  if (rc == I8IE_OK) rc = i8ie_layer_forward(L, in, n, h, w, s_in, zp_in, out, acc);
+  i8ie_layer_destroy(L);
+  return rc;
+}
+
 // the stateless form with groups (groups: not in the reference).  groups > 1 packs the weights for this one call: the
 // device weights are read back, a temporary layer handle runs the call with the caller's oc[] and is destroyed.
 int i8ie_conv2d_u8s8_grouped(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int kh,
@@ -332,18 +347,7 @@ int i8ie_conv2d_u8s8_grouped(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int
   I8IE_TRY(i8ie_memcpy_d2h(ctx, qw_host.data(), qw, qw_host.size()));
   i8ie_layer* L = nullptr;
   I8IE_TRY(layer_create(ctx, true, qw_host.data(), qb_host.data(), kc, Kg, c, kh, kw, stride, pad, s_w, &L, groups));
-  L->s_out = s_out;
-  L->zp_out = zp_out;
-  // the caller's offset vector (it carries the bias term) instead of the handle's own
-  int rc = i8ie_launch_finish_offsets(ctx, oc, L->wsum, L->qb, s_in, kc, L->ocp, nullptr);
-  if (rc == I8IE_OK) {
-    L->oc_valid = true;
-    L->oc_s_in = s_in;
-    L->oc_zp_in = zp_in;
-    rc = i8ie_layer_forward(L, in, n, h, w, s_in, zp_in, out, acc);
-  }
-  i8ie_layer_destroy(L);
-  return rc;
+  return run_once(L, in, n, h, w, zp_in, oc, s_in, s_out, zp_out, out, acc);
 }
 
 // ---- NHWC helpers exposed on the ABI -----------------------------------------------------------
@@ -503,17 +507,21 @@ static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const i
   return I8IE_OK;
 }
 
-// per-channel layers: the per-tensor handle plus s_w[n] (host copy, device [Npad]) and the multiplier buffer
-static int layer_make_per_channel(i8ie_layer* L, const float* s_w_host) {
+// per-channel layers: the per-tensor handle `L` (created with s_w = 1) plus s_w[n] (host copy, device [Npad]) and the
+// multiplier buffer.  Hands the handle over in *out, or destroys it.
+static int layer_make_per_channel(i8ie_layer* L, const float* s_w_host, i8ie_layer** out) {
   const int n = L->n;
   L->pc = true;
   L->sw_host.assign(s_w_host, s_w_host + n);
   std::vector<float> sw((size_t)L->Npad, 1.0f);
   for (int j = 0; j < n; ++j) sw[j] = s_w_host[j];
-  I8IE_TRY(i8ie_malloc(L->ctx, (size_t)L->Npad * 4, (void**)&L->swv));
-  I8IE_TRY(i8ie_malloc(L->ctx, (size_t)L->Npad * 4, (void**)&L->msv));
-  I8IE_TRY(i8ie_memcpy_h2d(L->ctx, L->swv, sw.data(), sw.size() * 4));
-  return i8ie_memset(L->ctx, L->msv, 0, (size_t)L->Npad * 4);
+  int rc = i8ie_malloc(L->ctx, (size_t)L->Npad * 4, (void**)&L->swv);
+  if (rc == I8IE_OK) rc = i8ie_malloc(L->ctx, (size_t)L->Npad * 4, (void**)&L->msv);
+  if (rc == I8IE_OK) rc = i8ie_memcpy_h2d(L->ctx, L->swv, sw.data(), sw.size() * 4);
+  if (rc == I8IE_OK) rc = i8ie_memset(L->ctx, L->msv, 0, (size_t)L->Npad * 4);
+  if (rc == I8IE_OK) *out = L;
+  else i8ie_layer_destroy(L);
+  return rc;
 }
 
 // scales from the caller: finite and >= 0 (pooling the INT32 accumulators before the requantiser needs a monotone
@@ -535,13 +543,7 @@ int i8ie_linear_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const i
   I8IE_TRY(check_scales(s_w_host, n));
   i8ie_layer* L = nullptr;
   I8IE_TRY(i8ie_linear_create(ctx, qw_host, qb_host, n, k, 1.0f, &L));
-  const int rc = layer_make_per_channel(L, s_w_host);
-  if (rc != I8IE_OK) {
-    i8ie_layer_destroy(L);
-    return rc;
-  }
-  *out = L;
-  return I8IE_OK;
+  return layer_make_per_channel(L, s_w_host, out);
 }
 
 int i8ie_conv2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh,
@@ -550,13 +552,7 @@ int i8ie_conv2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const i
   I8IE_TRY(check_scales(s_w_host, kc));
   i8ie_layer* L = nullptr;
   I8IE_TRY(i8ie_conv2d_create(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, 1.0f, &L));
-  const int rc = layer_make_per_channel(L, s_w_host);
-  if (rc != I8IE_OK) {
-    i8ie_layer_destroy(L);
-    return rc;
-  }
-  *out = L;
-  return I8IE_OK;
+  return layer_make_per_channel(L, s_w_host, out);
 }
 
 int i8ie_layer_weight_scales(const i8ie_layer* L, float* out, int n, int* per_channel) {
@@ -607,13 +603,7 @@ int i8ie_conv2d_create_grouped_per_channel(i8ie_ctx* ctx, const int8_t* qw_host,
   I8IE_TRY(check_scales(s_w_host, kc));
   i8ie_layer* L = nullptr;
   I8IE_TRY(i8ie_conv2d_create_grouped(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, groups, 1.0f, &L));
-  const int rc = layer_make_per_channel(L, s_w_host);
-  if (rc != I8IE_OK) {
-    i8ie_layer_destroy(L);
-    return rc;
-  }
-  *out = L;
-  return I8IE_OK;
+  return layer_make_per_channel(L, s_w_host, out);
 }
 
 int i8ie_layer_groups(const i8ie_layer* L, int* groups) {
@@ -637,13 +627,7 @@ int i8ie_conv_transpose2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_hos
   I8IE_TRY(check_scales(s_w_host, kc));
   i8ie_layer* L = nullptr;
   I8IE_TRY(i8ie_conv_transpose2d_create(ctx, qw_host, qb_host, kc, c, k, stride, pad, output_pad, 1.0f, &L));
-  const int rc = layer_make_per_channel(L, s_w_host);
-  if (rc != I8IE_OK) {
-    i8ie_layer_destroy(L);
-    return rc;
-  }
-  *out = L;
-  return I8IE_OK;
+  return layer_make_per_channel(L, s_w_host, out);
 }
 
 // the stateless form: qw is the equivalent matrix on the device; it is read back and packed for this one call (a temporary
@@ -661,17 +645,7 @@ int i8ie_conv_transpose2d_u8s8(i8ie_ctx* ctx, const uint8_t* in, int n, int c, i
   I8IE_TRY(i8ie_memcpy_d2h(ctx, qw_host.data(), qw, qw_host.size()));
   i8ie_layer* L = nullptr;
   I8IE_TRY(i8ie_conv_transpose2d_create(ctx, qw_host.data(), qb_host.data(), kc, c, k, stride, pad, output_pad, s_w, &L));
-  L->s_out = s_out;
-  L->zp_out = zp_out;
-  int rc = i8ie_launch_finish_offsets(ctx, oc, L->wsum, L->qb, s_in, kc, L->ocp, nullptr);
-  if (rc == I8IE_OK) {
-    L->oc_valid = true;
-    L->oc_s_in = s_in;
-    L->oc_zp_in = zp_in;
-    rc = i8ie_layer_forward(L, in, n, h, w, s_in, zp_in, out, acc);
-  }
-  i8ie_layer_destroy(L);
-  return rc;
+  return run_once(L, in, n, h, w, zp_in, oc, s_in, s_out, zp_out, out, acc);
 }
 
 int i8ie_layer_set_output_qparams(i8ie_layer* L, float s_out, uint8_t zp_out) {
@@ -702,16 +676,444 @@ int i8ie_layer_padding(const i8ie_layer* L, int* pad) {
   return I8IE_OK;
 }
 
-static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, int in_border, int m, int h, int w,
-                              float s_in, uint8_t zp_in, int relu, int pool_k, int pool_s, uint8_t* out, int out_layout,
-                              int out_border, int32_t* acc, float* out_f32);
+// ---- the layer forward: validate -> geometry -> plan -> peel -> route -----------------------------------
+// One forward as an exported entry point hands it over.  `x`: the FP32 NCHW input of the f32-input entry (path B layers; `in` is
+// then unused and in_layout NCHW).  `out_f32`: i8ie_layer_forward_dequant (Linear).
+struct ConvRequest {
+  const uint8_t* in = nullptr;
+  const float* x = nullptr;
+  int in_layout = I8IE_LAYOUT_NCHW, in_border = 0, m = 0, h = 0, w = 0;
+  float s_in = 0.0f;
+  uint8_t zp_in = 0;
+  int relu = 0, pool_k = 0, pool_s = 0;  // (the pool as the caller gave it)
+  uint8_t* out = nullptr;
+  int out_layout = I8IE_LAYOUT_NCHW, out_border = 0;
+  int32_t* acc = nullptr;
+  float* out_f32 = nullptr;
+  bool pool() const { return i8ie_is_pool(pool_k, pool_s); }
+  int fold_k() const { return pool() ? pool_k : 0; }  // the window as a kernel that folds the pool gets it
+  int pooled(int o) const { return pool() ? (o - pool_k) / pool_s + 1 : o; }
+  bool in_s8() const { return in_layout == I8IE_LAYOUT_NHWC_S8; }
+  bool out_s8() const { return out_layout == I8IE_LAYOUT_NHWC_S8; }
+  bool in_nchw() const { return in_layout == I8IE_LAYOUT_NCHW; }
+  bool out_nchw() const { return out_layout == I8IE_LAYOUT_NCHW; }
+};
+
+static ConvRequest make_request(const uint8_t* in, int in_layout, int in_border, int m, int h, int w, float s_in, uint8_t zp_in,
+                                int relu, uint8_t* out, int out_layout, int out_border, int32_t* acc) {
+  ConvRequest q;
+  q.in = in; q.in_layout = in_layout; q.in_border = in_border; q.m = m; q.h = h; q.w = w; q.s_in = s_in; q.zp_in = zp_in; q.relu = relu;
+  q.out = out; q.out_layout = out_layout; q.out_border = out_border; q.acc = acc;
+  return q;
+}
+// route A's launch over an NHWC image with `border` pixels around it, as far as the geometry goes: what conv_plan asks the
+// patch-stationary kernel about and what forward_implicit launches
+static I8ieIgemmCall implicit_call(i8ie_layer* L, const ConvGeom& cg, int m, int border) {
+  I8ieIgemmCall c{};
+  c.amode = 1; c.M = m * cg.oh * cg.ow; c.B = L->Bpack2; c.Kpad = L->Kpad2; c.Npad = L->Npad;
+  c.Kchunks = L->K2 / 16; c.N = L->n; c.wcache = &L->wc; c.OH = cg.oh; c.OW = cg.ow;
+  c.Hp = cg.h + 2 * border; c.Wp = cg.w + 2 * border; c.C = cg.c; c.KH = cg.kh; c.KW = cg.kw; c.sh = c.sw = cg.stride;
+  c.a_bytes = (size_t)m * c.Hp * c.Wp * cg.c;
+  return c;
+}
+// ... and the rest of a launch of the contraction kernel (routes A and B)
+static void implicit_epilogue(I8ieIgemmCall& c, const i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  c.ocp = L->ocp; c.biasf = nullptr; c.s_in = q.s_in; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out;
+  c.relu = q.relu; c.acc = q.acc; c.Ktrue = cg.K; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
+}
+
+// Which kernel takes this conv launch whole, with what the request asks folded in: the first-stage kernel (i8ie_stem.hip, path
+// B) pools and can store re-biased; the patch-stationary kernel (i8ie_pconv.hip, path A) pools, reads and stores re-biased --
+// when it takes the launch at all (kernel choice, geometry, batch, LDS; nothing is launched).  Neither: the plain call, the pool /
+// the re-bias as launches of their own around it (the peel passes).  The ONLY place that asks the two kernels: the dispatcher and
+// the layout queries read the same plan (the queries ask with output border 0; the kernel's size limits depend on the real one).
+struct ConvPlan { bool stem = false, pconv = false; };
+static ConvPlan conv_plan(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  ConvPlan p;
+  i8ie_ctx* ctx = L->ctx;
+  if (!L->conv || force_fallback(ctx) || !(q.acc == nullptr || aligned16(q.acc))) return p;
+  if (L->path == PATH_B)
+    p.stem = L->Bstem != nullptr && !ctx->pick.no_stem &&
+             i8ie_stem_supported(cg.c, cg.stride, L->n, cg.kh, cg.kw, cg.oh, cg.ow, q.fold_k(), q.pool_s) != 0;
+  if (L->path != PATH_A || !i8ie_conv_tries(ctx, I8IE_CONV_PCONV)) return p;
+  if (!(q.pool_k > 0 || q.in_s8() || q.out_s8()) || q.out_nchw() || !aligned16(q.in) || !aligned16(q.out)) return p;
+  I8ieIgemmCall c = implicit_call(L, cg, q.m, q.in_border > cg.pad ? q.in_border : cg.pad);
+  c.pool_k = q.fold_k(); c.pool_s = q.pool_s; c.a_s8 = q.in_s8() ? 1 : 0; c.out_s8 = q.out_s8() ? 1 : 0; c.ob = q.out_border;
+  p.pconv = c.a_bytes < i8ie_igemm_chunk_limit() && i8ie_pconv_takes(ctx, c) == 1;
+  return p;
+}
+
+// The kernels of routes A, B, G and T write NHWC.  Their workspace: [front: what the route puts before the kernel][the NHWC
+// result, when the caller wants NCHW]; unstage() converts that result back.
+struct Staged {
+  uint8_t *front, *out;  // the workspace; where the kernel writes, with border `ob`
+  const uint8_t* in;     // stage_io: where the kernel reads, with border `ib`
+  int ob, ib;
+};
+static int stage_out(i8ie_ctx* ctx, const ConvRequest& q, size_t front_bytes, size_t out_bytes, Staged* s) {
+  const size_t o_bytes = q.out_nchw() ? i8ie_align_up(out_bytes, 256) : 0;
+  I8IE_TRY(i8ie_ws_reserve(ctx, front_bytes + o_bytes + 256));
+  s->front = (uint8_t*)ctx->ws;
+  s->out = o_bytes ? s->front + front_bytes : q.out;
+  s->ob = o_bytes ? 0 : q.out_border;
+  return I8IE_OK;
+}
+// routes G and T read NHWC with any border (or none: bounds checks against zp_in): an NCHW input is converted into the front
+static int stage_io(i8ie_ctx* ctx, const ConvGeom& cg, const ConvRequest& q, Staged* s) {
+  const size_t a_bytes = q.in_nchw() ? i8ie_align_up((size_t)q.m * cg.c * cg.h * cg.w, 256) : 0;
+  I8IE_TRY(stage_out(ctx, q, a_bytes, (size_t)q.m * cg.kc * cg.oh * cg.ow, s));
+  s->in = q.in_nchw() ? s->front : q.in;
+  s->ib = q.in_nchw() ? 0 : q.in_border;
+  if (q.in_nchw()) I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, q.in, s->front, q.m, cg.c, cg.h, cg.w, 0));
+  return I8IE_OK;
+}
+static int unstage(i8ie_ctx* ctx, const Staged& s, const ConvRequest& q, int kc, int oh, int ow) {
+  if (s.out != q.out) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, s.out, q.out, q.m, kc, oh, ow, 0));
+  return I8IE_OK;
+}
+// ---- routes: the request as the plan and the peel passes left it (plain bytes and no pool unless the plan's kernel folds them) ----
+// route T: one launch (no zero-insert, scatter or fill pass).  The force-fallback option picks deconv_direct inside the launcher.
+static int forward_transposed(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  Staged s;
+  I8IE_TRY(stage_io(L->ctx, cg, q, &s));
+  I8ieDeconvCall d{};
+  d.A = s.in; d.m = q.m; d.H = cg.h; d.W = cg.w; d.C = cg.c; d.ib = s.ib;
+  d.OH = cg.oh; d.OW = cg.ow; d.k = cg.kh; d.s = cg.stride; d.p = cg.pad;
+  d.N = L->n; d.Ngp = L->Ngp; d.Kpp = L->Kpp; d.Bp = L->Bt; d.ktab = L->ttab; d.ocp = L->ocp; d.tph = L->tph;
+  d.msv = msv_arg(L); d.sbv = sbv_arg(L);
+  d.s_in = q.s_in; d.s_w = sw_arg(L); d.s_out = L->s_out; d.zp_in = q.zp_in; d.zp_out = L->zp_out; d.relu = q.relu;
+  d.out = s.out; d.ob = s.ob; d.acc = q.acc;
+  I8IE_TRY(i8ie_deconv_launch(L->ctx, d));
+  return unstage(L->ctx, s, q, cg.kc, cg.oh, cg.ow);
+}
+// route G: the grouped kernels; the force-fallback option picks gconv_direct inside the launcher
+static int forward_grouped(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  Staged s;
+  I8IE_TRY(stage_io(L->ctx, cg, q, &s));
+  I8ieGconvCall g{};
+  g.A = s.in; g.m = q.m; g.H = cg.h; g.W = cg.w; g.C = cg.c; g.ib = s.ib;
+  g.OH = cg.oh; g.OW = cg.ow; g.stride = cg.stride; g.pad = cg.pad; g.KH = cg.kh; g.KW = cg.kw;
+  g.groups = L->groups; g.Cg = cg.c / L->groups; g.Ng = L->n / L->groups; g.Ngp = L->Ngp; g.Kgp = L->Kgp;
+  g.Bp = L->Bg; g.ktab = L->gtab; g.ocp = L->ocp; g.msv = msv_arg(L); g.sbv = sbv_arg(L);
+  g.s_in = q.s_in; g.s_w = sw_arg(L); g.s_out = L->s_out; g.zp_in = q.zp_in; g.zp_out = L->zp_out; g.relu = q.relu;
+  g.out = s.out; g.ob = s.ob; g.acc = q.acc;
+  I8IE_TRY(i8ie_gconv_launch(L->ctx, g));
+  return unstage(L->ctx, s, q, cg.kc, cg.oh, cg.ow);
+}
+
+// route F: materialised im2col + the v1 GEMM, NCHW in and out of the kernels, relu as its own launch
+static int forward_fallback(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  const size_t in_bytes = (size_t)q.m * cg.c * cg.h * cg.w, out_bytes = (size_t)q.m * cg.kc * cg.oh * cg.ow;
+  const int ipc = chunk_images(cg, q.m);
+  const size_t col_bytes = i8ie_align_up((size_t)ipc * cg.oh * cg.ow * cg.Kpad, 256);
+  const size_t a_bytes = q.in_layout == I8IE_LAYOUT_NHWC ? i8ie_align_up(in_bytes, 256) : 0;
+  const size_t o_bytes = q.out_layout == I8IE_LAYOUT_NHWC ? i8ie_align_up(out_bytes, 256) : 0;
+  I8IE_TRY(i8ie_ws_reserve(ctx, col_bytes + a_bytes + o_bytes));
+  uint8_t* ws = (uint8_t*)ctx->ws;
+  const uint8_t* src = q.in;
+  if (a_bytes) {
+    I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, q.in, ws + col_bytes, q.m, cg.c, cg.h, cg.w, q.in_border));
+    src = ws + col_bytes;
+  }
+  uint8_t* dst = o_bytes ? ws + col_bytes + a_bytes : q.out;
+  I8IE_TRY(conv_run_v1(ctx, src, q.m, cg, L->Bpack, L->oc, L->wsum, q.zp_in, q.s_in, L->s_w, L->s_out, L->zp_out, dst, q.acc,
+                       ws, ipc, sbv_arg(L)));
+  if (q.relu) I8IE_TRY(i8ie_relu_u8(ctx, dst, dst, (int64_t)out_bytes, L->zp_out));
+  if (o_bytes) I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, dst, q.out, q.m, cg.kc, cg.oh, cg.ow, q.out_border));
+  return I8IE_OK;
+}
+
+// route A: implicit GEMM over the NHWC image with the layer's padding as a physical border.  `pconv`: the patch-stationary
+// kernel said it takes this launch as it is (conv_plan), pool and re-biased layouts included.
+static int forward_implicit(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q, bool pconv) {
+  i8ie_ctx* ctx = L->ctx;
+  const int oh = q.pooled(cg.oh), ow = q.pooled(cg.ow);  // (a pool is still on the request only when `pconv` folds it)
+  const bool direct = !q.in_nchw() && q.in_border >= cg.pad && aligned16(q.in);  // the input's own border serves
+  I8ieIgemmCall c = implicit_call(L, cg, q.m, direct ? q.in_border : cg.pad);
+  Staged s;
+  I8IE_TRY(stage_out(ctx, q, direct ? 0 : i8ie_align_up(c.a_bytes, 256), (size_t)q.m * cg.kc * oh * ow, &s));
+  if (direct) {
+    const int d = q.in_border - cg.pad;
+    const size_t shift = ((size_t)d * c.Wp + d) * cg.c;
+    c.A = q.in + shift;
+    c.a_bytes -= shift;
+  } else {
+    if (!q.in_nchw()) {  // (re-biased bytes are copied as they are; their border value is zp ^ 0x80)
+      I8IE_TRY(i8ie_launch_reborder(ctx, q.in, s.front, q.m, cg.c, cg.h, cg.w, q.in_border, cg.pad, q.in_s8() ? (q.zp_in ^ 0x80) : q.zp_in));
+    } else {
+      if (cg.pad > 0) I8IE_HIP_TRY(hipMemsetAsync(s.front, q.zp_in, c.a_bytes, ctx->stream));
+      I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, q.in, s.front, q.m, cg.c, cg.h, cg.w, cg.pad));
+    }
+    c.A = s.front;
+  }
+  implicit_epilogue(c, L, cg, q);
+  if (pconv) {
+    c.pool_k = q.fold_k(); c.pool_s = q.pool_s; c.a_s8 = q.in_s8() ? 1 : 0; c.out_s8 = q.out_s8() ? 1 : 0;
+  }
+  c.out = s.out; c.ob = s.ob;
+  I8IE_TRY(i8ie_igemm_launch(ctx, c));
+  return unstage(ctx, s, q, cg.kc, oh, ow);
+}
+// the calls of the two small-C kernels, all but the source and the destination (shared by the u8 and the f32-input forward)
+static I8ieStemCall fill_stem_call(const i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  I8ieStemCall f{};
+  f.n = q.m; f.c = cg.c; f.h = cg.h; f.w = cg.w; f.q_scale = q.s_in; f.q_zp = q.zp_in;
+  f.KH = cg.kh; f.KW = cg.kw; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
+  f.B = L->Bstem; f.Kpad = L->KpadStem; f.N = L->n; f.ocp = L->ocp;
+  f.s_in = q.s_in; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = q.relu;
+  f.pool_k = q.fold_k(); f.pool_s = q.pool_s; f.out_s8 = q.out_s8() ? 1 : 0; f.acc = q.acc;
+  f.msv = msv_arg(L); f.sbv = sbv_arg(L);
+  return f;
+}
+static I8ieFirstCall fill_first_call(const i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  I8ieFirstCall f{};
+  f.n = q.m; f.c = cg.c; f.h = cg.h; f.w = cg.w; f.q_scale = q.s_in; f.q_zp = q.zp_in;
+  f.KH = cg.kh; f.KW = cg.kw; f.KWG = L->kwg; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
+  f.B = L->Bpack2; f.Kpad = L->Kpad2; f.K2 = L->K2; f.N = L->n; f.ocp = L->ocp;
+  f.s_in = q.s_in; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = q.relu;
+  f.acc = q.acc; f.msv = msv_arg(L); f.sbv = sbv_arg(L);
+  return f;
+}
+
+// route B (small-C, stride % 4 == 0): the kernels read NCHW (u8, or FP32 that they quantize on the way: q.x) through an image
+// they repack into the workspace.  `stem`: the first-stage kernel (i8ie_stem.hip) takes the launch, conv (+ relu) (+ max-pool) in
+// one contraction; else the weights-stationary kernel (i8ie_first.hip) where it supports the layer (an f32-input forward always:
+// i8ie_layer_accepts_f32_input), else the 4-pixel-grouped image through the tiled kernel of route A.
+static int forward_small_c(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q, bool stem) {
+  i8ie_ctx* ctx = L->ctx;
+  const int oh = q.pooled(cg.oh), ow = q.pooled(cg.ow);  // (a pool is still on the request only when `stem` folds it)
+  const int Hp = (cg.oh - 1) * cg.stride + cg.kh, Wg = (cg.ow - 1) * (cg.stride / 4) + L->kwg;  // the grouped image
+  const bool wstat = !stem && (q.acc == nullptr || (L->n % 4 == 0 && aligned16(q.acc))) &&
+                     i8ie_first_supported(cg.c, cg.stride, L->n, L->K2, cg.kh, L->kwg, cg.ow);
+  const size_t t_bytes = q.x == nullptr && !q.in_nchw() ? i8ie_align_up((size_t)q.m * cg.c * cg.h * cg.w, 256) : 0;
+  const size_t r_bytes = i8ie_align_up(stem ? i8ie_stem_scratch_bytes(q.m, cg.kh, cg.kw, cg.stride, cg.oh, cg.ow)
+                                            : i8ie_first_scratch_bytes(q.m, cg.kh, L->kwg, cg.stride, cg.oh, cg.ow), 256);
+  Staged s;
+  I8IE_TRY(stage_out(ctx, q, t_bytes + r_bytes, (size_t)q.m * cg.kc * oh * ow, &s));
+  const uint8_t* src = q.in;
+  if (t_bytes) {
+    I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, q.in, s.front, q.m, cg.c, cg.h, cg.w, q.in_border));
+    src = s.front;
+  }
+  uint8_t* rep = s.front + t_bytes;
+  if (stem) {
+    I8ieStemCall f = fill_stem_call(L, cg, q);
+    f.x = q.x; f.xu8 = q.x ? nullptr : src; f.scratch = rep; f.out = s.out; f.ob = s.ob;
+    I8IE_TRY(i8ie_stem_launch(ctx, f));
+    return unstage(ctx, s, q, cg.kc, oh, ow);
+  }
+  if (q.x == nullptr) I8IE_TRY(i8ie_launch_repack_smallc(ctx, src, rep, q.m, cg.c, cg.h, cg.w, Hp, Wg, cg.pad, cg.pad, q.zp_in, wstat));
+  if (wstat) {
+    I8ieFirstCall f = fill_first_call(L, cg, q);
+    f.x = q.x; f.grouped = q.x ? nullptr : rep; f.scratch = q.x ? rep : nullptr; f.out = s.out; f.ob = s.ob;
+    I8IE_TRY(i8ie_first_launch(ctx, f));
+    return unstage(ctx, s, q, cg.kc, oh, ow);
+  }
+  I8ieIgemmCall c = implicit_call(L, cg, q.m, 0);
+  c.A = rep; c.a_bytes = (size_t)q.m * Hp * Wg * 16;
+  c.Hp = Hp; c.Wp = Wg; c.C = 16; c.KW = L->kwg; c.sw = cg.stride / 4;
+  implicit_epilogue(c, L, cg, q);
+  c.out = s.out; c.ob = s.ob;
+  I8IE_TRY(i8ie_igemm_launch(ctx, c));
+  return unstage(ctx, s, q, cg.kc, oh, ow);
+}
+
+// ---- plan -> peel -> route.  Each peel pass takes one thing off the request that no kernel folds, runs forward_conv on the
+// changed request -- which plans AGAIN: the inner layout, border and pool differ, so a peeled re-biased output can still fold
+// its pool and a plain-copied input can still get a folded pool or store -- and does that thing as launches of its own.
+static int forward_conv(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q);
+// re-biased input nobody reads as it is: plain copy first
+static int peel_rebiased_input(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  const size_t bytes = (size_t)q.m * (cg.h + 2 * q.in_border) * (cg.w + 2 * q.in_border) * cg.c;
+  uint8_t* tmp = nullptr;
+  I8IE_TRY(i8ie_malloc(ctx, bytes, (void**)&tmp));
+  ConvRequest r = q;
+  r.in = tmp; r.in_layout = I8IE_LAYOUT_NHWC;
+  int rc = i8ie_rebias_u8(ctx, q.in, tmp, (int64_t)bytes);
+  if (rc == I8IE_OK) rc = forward_conv(L, cg, r);
+  i8ie_free(ctx, tmp);
+  return rc;
+}
+
+// re-biased output nobody stores: the plain result into a temporary, re-biased, then laid into `out` with its border
+static int peel_rebiased_output(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  const int oph = q.pooled(cg.oh), opw = q.pooled(cg.ow);
+  const size_t bytes = (size_t)q.m * L->n * oph * opw;
+  I8IE_REQUIRE(L->n % 16 == 0, "re-biased NHWC output needs out features % 16 == 0");
+  uint8_t* tmp = nullptr;
+  I8IE_TRY(i8ie_malloc(ctx, bytes, (void**)&tmp));
+  ConvRequest r = q;
+  r.out = tmp; r.out_layout = I8IE_LAYOUT_NHWC; r.out_border = 0;
+  int rc = forward_conv(L, cg, r);
+  if (rc == I8IE_OK) rc = i8ie_rebias_u8(ctx, tmp, tmp, (int64_t)bytes);
+  if (rc == I8IE_OK) rc = i8ie_launch_reborder(ctx, tmp, q.out, q.m, L->n, oph, opw, 0, q.out_border, L->zp_out ^ 0x80);
+  i8ie_free(ctx, tmp);
+  return rc;
+}
+
+// a pool no kernel folds: max_pool2d<u8> (src/functional.cc:36-64) as its own launch behind the convolution
+static int peel_pool(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  const int oph = q.pooled(cg.oh), opw = q.pooled(cg.ow);
+  const bool nhwc = q.out_layout == I8IE_LAYOUT_NHWC && L->n % 16 == 0;
+  uint8_t* tmp = nullptr;
+  I8IE_TRY(i8ie_malloc(ctx, (size_t)q.m * L->n * cg.oh * cg.ow, (void**)&tmp));
+  ConvRequest r = q;
+  r.pool_k = r.pool_s = 0;
+  r.out = tmp; r.out_layout = nhwc ? I8IE_LAYOUT_NHWC : I8IE_LAYOUT_NCHW; r.out_border = 0;
+  int rc = forward_conv(L, cg, r);
+  if (rc == I8IE_OK) {
+    if (nhwc) {
+      rc = i8ie_launch_maxpool_nhwc(ctx, tmp, 0, q.out, q.out_border, q.m, L->n, cg.oh, cg.ow, q.pool_k, q.pool_s, 0);
+    } else if (q.out_nchw()) {
+      rc = i8ie_maxpool2d_u8(ctx, tmp, q.out, q.m, L->n, cg.oh, cg.ow, q.pool_k, q.pool_s);
+    } else {  // NHWC result with channels % 16 != 0: pool in NCHW, then lay out
+      uint8_t* tmp2 = nullptr;
+      rc = i8ie_malloc(ctx, (size_t)q.m * L->n * oph * opw, (void**)&tmp2);
+      if (rc == I8IE_OK) rc = i8ie_maxpool2d_u8(ctx, tmp, tmp2, q.m, L->n, cg.oh, cg.ow, q.pool_k, q.pool_s);
+      if (rc == I8IE_OK) rc = i8ie_launch_nchw_to_nhwc(ctx, tmp2, q.out, q.m, L->n, oph, opw, q.out_border);
+      i8ie_free(ctx, tmp2);
+    }
+  }
+  i8ie_free(ctx, tmp);
+  return rc;
+}
+
+static int forward_conv(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  const ConvPlan plan = conv_plan(L, cg, q);
+  if (q.in_s8() && !plan.pconv) return peel_rebiased_input(L, cg, q);
+  if (q.out_s8() && !plan.pconv && !plan.stem) return peel_rebiased_output(L, cg, q);
+  if (q.pool() && !plan.pconv && !plan.stem) return peel_pool(L, cg, q);
+  if (L->path == PATH_T) return forward_transposed(L, cg, q);
+  if (L->path == PATH_G) return forward_grouped(L, cg, q);
+  if (L->path == PATH_F || force_fallback(L->ctx)) return forward_fallback(L, cg, q);
+  return L->path == PATH_A ? forward_implicit(L, cg, q, plan.pconv) : forward_small_c(L, cg, q, plan.stem);
+}
+
+// ---- Linear: row-major in / out ------------------------------------------------------------------------------------------------
+static int forward_linear(i8ie_layer* L, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  const int m = q.m;
+  I8IE_REQUIRE(q.in_border == 0 && q.out_border == 0, "Linear tensors carry no border");
+  // Rows that are a flattened NHWC activation [m][h][w][c] (the engine's layout between layers) instead of
+  // the reference's flattened NCHW: same contraction with K walked in (h, w, c) order, so the weight panel
+  // is permuted once per (c, h*w) and the input is used as it lies -- no transpose back to NCHW.  oc[] and
+  // wsum[] are sums over all of K and keep the reference's accumulation order (they come from qw).
+  const int hw = (q.in_layout == I8IE_LAYOUT_NHWC && q.h > 0 && q.w > 0) ? q.h * q.w : 1;
+  const int8_t* panel = L->Bpack;
+  if (hw > 1) {
+    I8IE_REQUIRE(L->K % hw == 0, "Linear: in_features is not c * h * w for the given h, w");
+    if (force_fallback(ctx) || L->K % 16 != 0 || !aligned16(q.in)) {
+      // the any-geometry route wants reference order: transpose the input instead of the weights, into the workspace BEYOND
+      // what the inner forward reserves and uses (its padded rows and split-K partials)
+      I8IE_TRY(i8ie_ws_reserve(ctx, (size_t)m * L->K + (size_t)m * L->Kpad + (size_t)8 * m * L->n * 4 + 4096));
+      uint8_t* t = (uint8_t*)ctx->ws + i8ie_align_up((size_t)m * L->Kpad + (size_t)8 * m * L->n * 4, 256) + 512;
+      I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, q.in, t, m, L->K / hw, q.h, q.w, 0));
+      ConvRequest r = q;
+      r.in = t; r.in_layout = I8IE_LAYOUT_NCHW; r.h = r.w = 0;
+      return forward_linear(L, r);
+    }
+    if (L->Bperm == nullptr || L->perm_c != L->K / hw || L->perm_hw != hw) {
+      if (L->Bperm == nullptr) I8IE_TRY(i8ie_malloc(ctx, (size_t)L->Npad * L->Kpad, (void**)&L->Bperm));
+      I8IE_TRY(i8ie_launch_permute_k(ctx, L->Bpack, L->Bperm, L->Npad, L->Kpad, L->K, L->K / hw, hw));
+      L->perm_c = L->K / hw;
+      L->perm_hw = hw;
+    }
+    panel = L->Bperm;
+  }
+  const bool need_pad = (L->K % 16 != 0) || !aligned16(q.in);
+  if (!force_fallback(ctx) && !need_pad && L->n <= i8ie_smalln_max_features()) {
+    // classifier head: one wave per row, dot4 + wavefront reduction, epilogue (and dequantize) fused
+    I8ieSmallNCall sc{};
+    sc.A = q.in; sc.lda = (size_t)L->K; sc.M = m; sc.K = L->K; sc.B = panel; sc.Kpad = L->Kpad; sc.N = L->n;
+    sc.ocp = L->ocp; sc.biasf = L->biasf; sc.s_in = q.s_in; sc.s_w = sw_arg(L); sc.s_out = L->s_out;
+    sc.zp_out = L->zp_out; sc.relu = q.relu; sc.out = q.out; sc.acc = q.acc; sc.out_f32 = q.out_f32; sc.sbv = sbv_arg(L);
+    return i8ie_launch_linear_smalln(ctx, sc);
+  }
+  I8IE_REQUIRE(q.out != nullptr, "i8ie_layer_forward_dequant: this layer needs the u8 output buffer as well");
+  if (q.out_f32 != nullptr) {  // general shape: the ordinary forward, then the dequantize kernel
+    ConvRequest r = q;
+    r.out_f32 = nullptr; r.out_layout = I8IE_LAYOUT_NCHW;
+    I8IE_TRY(forward_linear(L, r));
+    return i8ie_dequantize_u8_f32(ctx, q.out, q.out_f32, (int64_t)m * L->n, L->s_out, L->zp_out);
+  }
+  if (force_fallback(ctx)) {
+    if (need_pad) I8IE_TRY(i8ie_ws_reserve(ctx, (size_t)m * L->Kpad));
+    I8IE_TRY(linear_run_v1(ctx, q.in, m, L->K, L->Bpack, L->Kpad, L->qb, L->n, L->oc, L->wsum, q.s_in, L->s_w, L->s_out,
+                           L->zp_out, q.out, q.acc, (uint8_t*)ctx->ws, sbv_arg(L)));
+    if (q.relu) I8IE_TRY(i8ie_relu_u8(ctx, q.out, q.out, (int64_t)m * L->n, L->zp_out));
+    return I8IE_OK;
+  }
+  I8ieIgemmCall c{};
+  const int lin = ctx->pick.linear;
+  // few rows: the one-launch kernel of i8ie_flin.hip
+  const bool flin = !need_pad && lin != I8IE_LIN_TILED && L->K % 16 == 0 &&
+                    i8ie_flin_wants(m, L->n, L->Kpad, lin == I8IE_LIN_FLIN || lin == I8IE_LIN_FLIN128);
+  // split K when the output has too few tiles to fill the chip (small batch, or few features)
+  const long tiles_m = (m + 127) / 128, blocks_est = tiles_m * ((L->n + 63) / 64);
+  const int nk = L->Kpad / 128;
+  int ksplit = 1;
+  // many rows: the one-launch kernel of i8ie_mlin.hip
+  const bool mlin = !need_pad && !flin && lin != I8IE_LIN_TILED && lin != I8IE_LIN_TILED_MANY && L->K % 16 == 0 &&
+                    aligned16(q.out) && L->Npad % 128 == 0 &&
+                    i8ie_mlin_wants(m, L->n, L->Kpad, lin == I8IE_LIN_MLIN || lin == I8IE_LIN_MLIN64 || lin == I8IE_LIN_MLIN128);
+  if (blocks_est < 256 && nk >= 4 && !flin && !mlin) {
+    ksplit = (int)((512 + blocks_est - 1) / blocks_est);
+    if (ksplit > 8) ksplit = 8;
+    if (ksplit > nk / 2) ksplit = nk / 2;
+  }
+  const size_t pad_bytes = need_pad ? i8ie_align_up((size_t)m * L->Kpad, 256) : 0;
+  const size_t part_bytes = ksplit > 1 ? (size_t)ksplit * m * L->n * 4 : 0;
+  if (pad_bytes + part_bytes) I8IE_TRY(i8ie_ws_reserve(ctx, pad_bytes + part_bytes));
+  c.ksplit = ksplit;
+  c.partial = ksplit > 1 ? (int32_t*)((uint8_t*)ctx->ws + pad_bytes) : nullptr;
+  if (need_pad) I8IE_TRY(i8ie_launch_pad_rows(ctx, q.in, m, L->K, ctx->ws, m, L->Kpad, 0));
+  c.A = need_pad ? (const uint8_t*)ctx->ws : q.in;
+  c.lda = need_pad ? L->Kpad : L->K;
+  c.Kchunks = (int)c.lda / 16;
+  c.a_bytes = (size_t)m * c.lda;
+  c.amode = 0; c.M = m;
+  c.B = panel; c.Kpad = L->Kpad; c.Npad = L->Npad; c.N = L->n; c.ocp = L->ocp; c.biasf = L->biasf;
+  c.s_in = q.s_in; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = q.relu;
+  c.out = q.out; c.ob = 0; c.acc = q.acc; c.Ktrue = L->K; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
+  if (flin) return i8ie_flin_launch(ctx, c);
+  if (mlin) return i8ie_mlin_launch(ctx, c);
+  return i8ie_igemm_launch(ctx, c);
+}
+
+// ---- validate -> geometry, then forward_linear or forward_conv -----------------------------------------------------------------
+static int layer_forward(i8ie_layer* L, const ConvRequest& q) {
+  I8IE_REQUIRE(L && q.in, "null argument");
+  I8IE_REQUIRE(q.out != nullptr || (q.out_f32 != nullptr && !L->conv), "null output");
+  I8IE_REQUIRE(q.m > 0, "non-positive batch");
+  I8IE_REQUIRE(q.in_layout >= I8IE_LAYOUT_NCHW && q.in_layout <= I8IE_LAYOUT_NHWC_S8 && q.out_layout >= I8IE_LAYOUT_NCHW &&
+                   q.out_layout <= I8IE_LAYOUT_NHWC_S8,
+               "bad layout tag");
+  I8IE_REQUIRE(L->conv || (!q.in_s8() && !q.out_s8()), "the re-biased layout applies to conv layers only");
+  I8IE_REQUIRE(q.in_border >= 0 && q.out_border >= 0, "negative border");
+  I8IE_REQUIRE(!q.in_nchw() || q.in_border == 0, "only NHWC tensors carry a border");
+  I8IE_REQUIRE(!q.out_nchw() || q.out_border == 0, "only NHWC tensors carry a border");
+  I8IE_HIP_TRY(hipSetDevice(L->ctx->device));
+  I8IE_TRY(ensure_offsets(L, q.s_in, q.zp_in));
+  I8IE_TRY(ensure_multipliers(L, q.s_in));
+  if (!L->conv) return forward_linear(L, q);
+  ConvGeom cg;
+  if (L->path == PATH_T)
+    I8IE_TRY(deconv_geom(L->c, q.h, q.w, L->n, L->kh, L->stride, L->pad, L->opad, &cg));
+  else
+    I8IE_TRY(conv_geom(L->c, q.h, q.w, L->n, L->kh, L->kw, L->stride, L->pad, &cg));
+  if (q.pool()) I8IE_REQUIRE(q.pool_k <= cg.oh && q.pool_k <= cg.ow, "max-pool window larger than the convolution's output");
+  return forward_conv(L, cg, q);
+}
 
 int i8ie_layer_forward_fused(i8ie_layer* L, const uint8_t* in, int in_layout, int in_border, int m, int h, int w,
                              float s_in, uint8_t zp_in, int relu, uint8_t* out, int out_layout, int out_border,
                              int32_t* acc) {
   I8IE_REQUIRE(out != nullptr, "null argument");
-  return layer_forward_impl(L, in, in_layout, in_border, m, h, w, s_in, zp_in, relu, 0, 0, out, out_layout, out_border,
-                            acc, nullptr);
+  return layer_forward(L, make_request(in, in_layout, in_border, m, h, w, s_in, zp_in, relu, out, out_layout, out_border, acc));
 }
 
 int i8ie_layer_forward_pool(i8ie_layer* L, const uint8_t* in, int in_layout, int in_border, int m, int h, int w,
@@ -720,8 +1122,9 @@ int i8ie_layer_forward_pool(i8ie_layer* L, const uint8_t* in, int in_layout, int
   I8IE_REQUIRE(L != nullptr && out != nullptr, "null argument");
   I8IE_REQUIRE(L->conv, "i8ie_layer_forward_pool: Conv2d layers only");
   I8IE_REQUIRE(pool_k > 0 && pool_s > 0, "kernel_size and stride must be positive");
-  return layer_forward_impl(L, in, in_layout, in_border, m, h, w, s_in, zp_in, relu, pool_k, pool_s, out, out_layout,
-                            out_border, acc, nullptr);
+  ConvRequest q = make_request(in, in_layout, in_border, m, h, w, s_in, zp_in, relu, out, out_layout, out_border, acc);
+  q.pool_k = pool_k; q.pool_s = pool_s;
+  return layer_forward(L, q);
 }
 
 // dequantize(layer(x)) for a Linear layer: src/quantize_utils.cc:54-58 applied to the result of
@@ -731,416 +1134,55 @@ int i8ie_layer_forward_dequant(i8ie_layer* L, const uint8_t* in, int in_layout, 
                                uint8_t zp_in, int relu, uint8_t* out_u8, float* out_f32) {
   I8IE_REQUIRE(L && out_f32, "null argument");
   I8IE_REQUIRE(!L->conv, "i8ie_layer_forward_dequant: Linear layers only");
-  return layer_forward_impl(L, in, in_layout, 0, m, h, w, s_in, zp_in, relu, 0, 0, out_u8, I8IE_LAYOUT_NCHW, 0, nullptr,
-                            out_f32);
+  ConvRequest q = make_request(in, in_layout, 0, m, h, w, s_in, zp_in, relu, out_u8, I8IE_LAYOUT_NCHW, 0, nullptr);
+  q.out_f32 = out_f32;
+  return layer_forward(L, q);
 }
 
-// the first-stage kernel (i8ie_stem.hip) takes this conv layer at this output size (+ this pool behind it)?
-static bool stem_takes(const i8ie_layer* L, const ConvGeom& cg, int pool_k, int pool_s) {
-  return L->conv && L->path == PATH_B && L->Bstem != nullptr && !force_fallback(L->ctx) && !L->ctx->pick.no_stem &&
-         i8ie_stem_supported(cg.c, cg.stride, L->n, cg.kh, cg.kw, cg.oh, cg.ow, pool_k, pool_s) != 0;
-}
-
-// would the patch-stationary kernel (i8ie_pconv.hip) take this conv launch, with this pool folded in and these
-// re-biased layouts?  (it answers from the kernel choice, the geometry and the batch, as the dispatcher will; nothing is launched)
-// (`out_border`: the border of the output the real call will write; the size limits of the kernel depend on it.  The layout
-// negotiation queries below do not know it yet and ask with 0: layer_forward_impl asks again with the real one and runs the
-// pool / the re-bias as launches of their own when the kernel then declines)
-static bool pconv_probe(i8ie_layer* L, const ConvGeom& cg, int m, int in_border, int pool_k, int pool_s, bool a_s8, bool out_s8, int out_border = 0) {
-  if (!L->conv || L->path != PATH_A || force_fallback(L->ctx) || !i8ie_conv_tries(L->ctx, I8IE_CONV_PCONV)) return false;
-  const int b = in_border > cg.pad ? in_border : cg.pad;
-  I8ieIgemmCall q{};
-  q.amode = 1; q.M = m * cg.oh * cg.ow; q.B = L->Bpack2; q.Kpad = L->Kpad2; q.Npad = L->Npad;
-  q.Kchunks = L->K2 / 16; q.N = L->n; q.wcache = &L->wc; q.OH = cg.oh; q.OW = cg.ow;
-  q.Hp = cg.h + 2 * b; q.Wp = cg.w + 2 * b; q.C = cg.c; q.KH = cg.kh; q.KW = cg.kw; q.sh = q.sw = cg.stride;
-  q.a_bytes = (size_t)m * q.Hp * q.Wp * cg.c;
-  q.pool_k = pool_k; q.pool_s = pool_s; q.a_s8 = a_s8 ? 1 : 0; q.out_s8 = out_s8 ? 1 : 0; q.ob = out_border;
-  return q.a_bytes < i8ie_igemm_chunk_limit() && i8ie_pconv_takes(L->ctx, q) == 1;
-}
-
-// route T: NHWC in and out of the kernel, one launch (no zero-insert, scatter or fill pass); the layout conversions around
-// it as on the other routes.  The force-fallback option picks deconv_direct inside the launcher.  (NHWC_S8 and the pool have
-// been taken off by the caller: plain bytes, no pool.)
-static int forward_transposed(i8ie_layer* L, const ConvGeom& cg, const uint8_t* in, int in_layout, int in_border, int m,
-                              float s_in, uint8_t zp_in, int relu, uint8_t* out, int out_layout, int out_border, int32_t* acc) {
-  i8ie_ctx* ctx = L->ctx;
-  const bool in_nchw = in_layout == I8IE_LAYOUT_NCHW, out_nchw = out_layout == I8IE_LAYOUT_NCHW;
-  const size_t a_bytes = in_nchw ? i8ie_align_up((size_t)m * cg.c * cg.h * cg.w, 256) : 0;
-  const size_t o_bytes = out_nchw ? i8ie_align_up((size_t)m * cg.kc * cg.oh * cg.ow, 256) : 0;
-  if (a_bytes + o_bytes) I8IE_TRY(i8ie_ws_reserve(ctx, a_bytes + o_bytes + 256));
-  uint8_t* ws = (uint8_t*)ctx->ws;
-  if (in_nchw) I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, in, ws, m, cg.c, cg.h, cg.w, 0));
-  I8ieDeconvCall d{};
-  d.A = in_nchw ? ws : in; d.m = m; d.H = cg.h; d.W = cg.w; d.C = cg.c; d.ib = in_nchw ? 0 : in_border;
-  d.OH = cg.oh; d.OW = cg.ow; d.k = cg.kh; d.s = cg.stride; d.p = cg.pad;
-  d.N = L->n; d.Ngp = L->Ngp; d.Kpp = L->Kpp; d.Bp = L->Bt; d.ktab = L->ttab; d.ocp = L->ocp; d.tph = L->tph;
-  d.msv = msv_arg(L); d.sbv = sbv_arg(L);
-  d.s_in = s_in; d.s_w = sw_arg(L); d.s_out = L->s_out; d.zp_in = zp_in; d.zp_out = L->zp_out; d.relu = relu;
-  d.out = out_nchw ? ws + a_bytes : out; d.ob = out_nchw ? 0 : out_border; d.acc = acc;
-  I8IE_TRY(i8ie_deconv_launch(ctx, d));
-  if (out_nchw) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, d.out, out, m, cg.kc, cg.oh, cg.ow, 0));
-  return I8IE_OK;
-}
-
-static int layer_forward_impl(i8ie_layer* L, const uint8_t* in, int in_layout, int in_border, int m, int h, int w,
-                              float s_in, uint8_t zp_in, int relu, int pool_k, int pool_s, uint8_t* out, int out_layout,
-                              int out_border, int32_t* acc, float* out_f32) {
-  I8IE_REQUIRE(L && in, "null argument");
-  I8IE_REQUIRE(out != nullptr || (out_f32 != nullptr && !L->conv), "null output");
-  I8IE_REQUIRE(m > 0, "non-positive batch");
-  I8IE_REQUIRE(in_layout >= I8IE_LAYOUT_NCHW && in_layout <= I8IE_LAYOUT_NHWC_S8 && out_layout >= I8IE_LAYOUT_NCHW &&
-                   out_layout <= I8IE_LAYOUT_NHWC_S8,
-               "bad layout tag");
-  I8IE_REQUIRE(L->conv || (in_layout != I8IE_LAYOUT_NHWC_S8 && out_layout != I8IE_LAYOUT_NHWC_S8),
-               "the re-biased layout applies to conv layers only");
-  I8IE_REQUIRE(in_border >= 0 && out_border >= 0, "negative border");
-  I8IE_REQUIRE(in_layout != I8IE_LAYOUT_NCHW || in_border == 0, "only NHWC tensors carry a border");
-  I8IE_REQUIRE(out_layout != I8IE_LAYOUT_NCHW || out_border == 0, "only NHWC tensors carry a border");
-  i8ie_ctx* ctx = L->ctx;
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  I8IE_TRY(ensure_offsets(L, s_in, zp_in));
-  I8IE_TRY(ensure_multipliers(L, s_in));
-
-  if (!L->conv) {  // ---- Linear: row-major in / out -------------------------------------------------
-    I8IE_REQUIRE(in_border == 0 && out_border == 0, "Linear tensors carry no border");
-    // Rows that are a flattened NHWC activation [m][h][w][c] (the engine's layout between layers) instead of
-    // the reference's flattened NCHW: same contraction with K walked in (h, w, c) order, so the weight panel
-    // is permuted once per (c, h*w) and the input is used as it lies -- no transpose back to NCHW.  oc[] and
-    // wsum[] are sums over all of K and keep the reference's accumulation order (they come from qw).
-    const int hw = (in_layout == I8IE_LAYOUT_NHWC && h > 0 && w > 0) ? h * w : 1;
-    const int8_t* panel = L->Bpack;
-    if (hw > 1) {
-      I8IE_REQUIRE(L->K % hw == 0, "Linear: in_features is not c * h * w for the given h, w");
-      if (force_fallback(ctx) || L->K % 16 != 0 || !aligned16(in)) {
-        // the any-geometry route wants reference order: transpose the input instead of the weights
-        I8IE_TRY(i8ie_ws_reserve(ctx, (size_t)m * L->K + (size_t)m * L->Kpad + (size_t)8 * m * L->n * 4 + 4096));
-        uint8_t* t = (uint8_t*)ctx->ws + i8ie_align_up((size_t)m * L->Kpad + (size_t)8 * m * L->n * 4, 256) + 512;
-        I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, in, t, m, L->K / hw, h, w, 0));
-        return layer_forward_impl(L, t, I8IE_LAYOUT_NCHW, 0, m, 0, 0, s_in, zp_in, relu, 0, 0, out, out_layout, out_border,
-                                  acc, out_f32);
-      }
-      if (L->Bperm == nullptr || L->perm_c != L->K / hw || L->perm_hw != hw) {
-        if (L->Bperm == nullptr) I8IE_TRY(i8ie_malloc(ctx, (size_t)L->Npad * L->Kpad, (void**)&L->Bperm));
-        I8IE_TRY(i8ie_launch_permute_k(ctx, L->Bpack, L->Bperm, L->Npad, L->Kpad, L->K, L->K / hw, hw));
-        L->perm_c = L->K / hw;
-        L->perm_hw = hw;
-      }
-      panel = L->Bperm;
-    }
-    const bool need_pad = (L->K % 16 != 0) || !aligned16(in);
-    if (!force_fallback(ctx) && !need_pad && L->n <= i8ie_smalln_max_features()) {
-      // classifier head: one wave per row, dot4 + wavefront reduction, epilogue (and dequantize) fused
-      I8ieSmallNCall sc{};
-      sc.A = in; sc.lda = (size_t)L->K; sc.M = m; sc.K = L->K; sc.B = panel; sc.Kpad = L->Kpad; sc.N = L->n;
-      sc.ocp = L->ocp; sc.biasf = L->biasf; sc.s_in = s_in; sc.s_w = sw_arg(L); sc.s_out = L->s_out;
-      sc.zp_out = L->zp_out; sc.relu = relu; sc.out = out; sc.acc = acc; sc.out_f32 = out_f32; sc.sbv = sbv_arg(L);
-      return i8ie_launch_linear_smalln(ctx, sc);
-    }
-    I8IE_REQUIRE(out != nullptr, "i8ie_layer_forward_dequant: this layer needs the u8 output buffer as well");
-    if (out_f32 != nullptr) {  // general shape: the ordinary forward, then the dequantize kernel
-      I8IE_TRY(layer_forward_impl(L, in, in_layout, 0, m, h, w, s_in, zp_in, relu, 0, 0, out, I8IE_LAYOUT_NCHW, 0, acc, nullptr));
-      return i8ie_dequantize_u8_f32(ctx, out, out_f32, (int64_t)m * L->n, L->s_out, L->zp_out);
-    }
-    if (force_fallback(ctx)) {
-      if (need_pad) I8IE_TRY(i8ie_ws_reserve(ctx, (size_t)m * L->Kpad));
-      I8IE_TRY(linear_run_v1(ctx, in, m, L->K, L->Bpack, L->Kpad, L->qb, L->n, L->oc, L->wsum, s_in, L->s_w, L->s_out,
-                             L->zp_out, out, acc, (uint8_t*)ctx->ws, sbv_arg(L)));
-      if (relu) I8IE_TRY(i8ie_relu_u8(ctx, out, out, (int64_t)m * L->n, L->zp_out));
-      return I8IE_OK;
-    }
-    I8ieIgemmCall c{};
-    const int lin = ctx->pick.linear;
-    // few rows: the one-launch kernel of i8ie_flin.hip
-    const bool flin = !need_pad && lin != I8IE_LIN_TILED && L->K % 16 == 0 &&
-                      i8ie_flin_wants(m, L->n, L->Kpad, lin == I8IE_LIN_FLIN || lin == I8IE_LIN_FLIN128);
-    // split K when the output has too few tiles to fill the chip (small batch, or few features)
-    const long tiles_m = (m + 127) / 128, blocks_est = tiles_m * ((L->n + 63) / 64);
-    const int nk = L->Kpad / 128;
-    int ksplit = 1;
-    // many rows: the one-launch kernel of i8ie_mlin.hip
-    const bool mlin = !need_pad && !flin && lin != I8IE_LIN_TILED && lin != I8IE_LIN_TILED_MANY && L->K % 16 == 0 &&
-                      aligned16(out) && L->Npad % 128 == 0 &&
-                      i8ie_mlin_wants(m, L->n, L->Kpad, lin == I8IE_LIN_MLIN || lin == I8IE_LIN_MLIN64 || lin == I8IE_LIN_MLIN128);
-    if (blocks_est < 256 && nk >= 4 && !flin && !mlin) {
-      ksplit = (int)((512 + blocks_est - 1) / blocks_est);
-      if (ksplit > 8) ksplit = 8;
-      if (ksplit > nk / 2) ksplit = nk / 2;
-    }
-    const size_t pad_bytes = need_pad ? i8ie_align_up((size_t)m * L->Kpad, 256) : 0;
-    const size_t part_bytes = ksplit > 1 ? (size_t)ksplit * m * L->n * 4 : 0;
-    if (pad_bytes + part_bytes) I8IE_TRY(i8ie_ws_reserve(ctx, pad_bytes + part_bytes));
-    c.ksplit = ksplit;
-    c.partial = ksplit > 1 ? (int32_t*)((uint8_t*)ctx->ws + pad_bytes) : nullptr;
-    if (need_pad) {
-      I8IE_TRY(i8ie_launch_pad_rows(ctx, in, m, L->K, ctx->ws, m, L->Kpad, 0));
-      c.A = (const uint8_t*)ctx->ws;
-      c.lda = L->Kpad;
-      c.Kchunks = L->Kpad / 16;
-    } else {
-      c.A = in;
-      c.lda = L->K;
-      c.Kchunks = L->K / 16;
-    }
-    c.a_bytes = (size_t)m * c.lda;
-    c.amode = 0; c.M = m;
-    c.B = panel; c.Kpad = L->Kpad; c.Npad = L->Npad; c.N = L->n; c.ocp = L->ocp; c.biasf = L->biasf;
-    c.s_in = s_in; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = relu;
-    c.out = out; c.ob = 0; c.acc = acc; c.Ktrue = L->K; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
-    if (flin) return i8ie_flin_launch(ctx, c);
-    if (mlin) return i8ie_mlin_launch(ctx, c);
-    return i8ie_igemm_launch(ctx, c);
-  }
-
-  // ---- Conv2d --------------------------------------------------------------------------------
-  ConvGeom cg;
-  if (L->path == PATH_T)
-    I8IE_TRY(deconv_geom(L->c, h, w, L->n, L->kh, L->stride, L->pad, L->opad, &cg));
-  else
-    I8IE_TRY(conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg));
-  const bool pool = i8ie_is_pool(pool_k, pool_s);
-  if (pool) I8IE_REQUIRE(pool_k <= cg.oh && pool_k <= cg.ow, "max-pool window larger than the convolution's output");
-  const bool in_s8 = in_layout == I8IE_LAYOUT_NHWC_S8, out_s8 = out_layout == I8IE_LAYOUT_NHWC_S8;
-  // Which kernel folds what: the first-stage kernel (path B) pools and can store re-biased; the patch-stationary kernel
-  // (path A) pools, reads and stores re-biased -- when it takes the launch at all (batch, geometry, LDS: asked below).
-  // Everything else: the plain call, with the pool / the re-bias as launches of their own around it.
-  const bool stem = stem_takes(L, cg, pool ? pool_k : 0, pool_s) && (acc == nullptr || aligned16(acc));
-  bool pconv = false;
-  if (!stem && (pool || in_s8 || out_s8) && out_layout != I8IE_LAYOUT_NCHW && aligned16(in) && aligned16(out) &&
-      (acc == nullptr || aligned16(acc)))
-    pconv = pconv_probe(L, cg, m, in_border, pool ? pool_k : 0, pool_s, in_s8, out_s8, out_border);
-  if (in_s8 && !pconv) {  // nobody reads the re-biased bytes as they are: plain copy first
-    const size_t bytes = (size_t)m * (cg.h + 2 * in_border) * (cg.w + 2 * in_border) * cg.c;
-    uint8_t* tmp = nullptr;
-    I8IE_TRY(i8ie_malloc(ctx, bytes, (void**)&tmp));
-    int rc = i8ie_rebias_u8(ctx, in, tmp, (int64_t)bytes);
-    if (rc == I8IE_OK)
-      rc = layer_forward_impl(L, tmp, I8IE_LAYOUT_NHWC, in_border, m, h, w, s_in, zp_in, relu, pool_k, pool_s, out, out_layout,
-                              out_border, acc, nullptr);
-    i8ie_free(ctx, tmp);
-    return rc;
-  }
-  if (out_s8 && !pconv && !stem) {  // plain result into a temporary, re-biased, then laid into `out` with its border
-    const int oph = pool ? (cg.oh - pool_k) / pool_s + 1 : cg.oh, opw = pool ? (cg.ow - pool_k) / pool_s + 1 : cg.ow;
-    const size_t bytes = (size_t)m * L->n * oph * opw;
-    I8IE_REQUIRE(L->n % 16 == 0, "re-biased NHWC output needs out features % 16 == 0");
-    uint8_t* tmp = nullptr;
-    I8IE_TRY(i8ie_malloc(ctx, bytes, (void**)&tmp));
-    int rc = layer_forward_impl(L, in, in_layout, in_border, m, h, w, s_in, zp_in, relu, pool_k, pool_s, tmp, I8IE_LAYOUT_NHWC, 0,
-                                acc, nullptr);
-    if (rc == I8IE_OK) rc = i8ie_rebias_u8(ctx, tmp, tmp, (int64_t)bytes);
-    if (rc == I8IE_OK) rc = i8ie_launch_reborder(ctx, tmp, out, m, L->n, oph, opw, 0, out_border, L->zp_out ^ 0x80);
-    i8ie_free(ctx, tmp);
-    return rc;
-  }
-  if (pool && !stem && !pconv) {
-    // no kernel fuses this pool: max_pool2d<u8> (src/functional.cc:36-64) as its own launch behind the convolution
-    const int oph = (cg.oh - pool_k) / pool_s + 1, opw = (cg.ow - pool_k) / pool_s + 1;
-    const bool nhwc = out_layout == I8IE_LAYOUT_NHWC && L->n % 16 == 0;
-    uint8_t* tmp = nullptr;
-    I8IE_TRY(i8ie_malloc(ctx, (size_t)m * L->n * cg.oh * cg.ow, (void**)&tmp));
-    int rc = layer_forward_impl(L, in, in_layout, in_border, m, h, w, s_in, zp_in, relu, 0, 0, tmp,
-                                nhwc ? I8IE_LAYOUT_NHWC : I8IE_LAYOUT_NCHW, 0, acc, nullptr);
-    if (rc == I8IE_OK) {
-      if (nhwc) {
-        rc = i8ie_launch_maxpool_nhwc(ctx, tmp, 0, out, out_border, m, L->n, cg.oh, cg.ow, pool_k, pool_s, 0);
-      } else if (out_layout == I8IE_LAYOUT_NCHW) {
-        rc = i8ie_maxpool2d_u8(ctx, tmp, out, m, L->n, cg.oh, cg.ow, pool_k, pool_s);
-      } else {  // NHWC result with channels % 16 != 0: pool in NCHW, then lay out
-        uint8_t* tmp2 = nullptr;
-        rc = i8ie_malloc(ctx, (size_t)m * L->n * oph * opw, (void**)&tmp2);
-        if (rc == I8IE_OK) rc = i8ie_maxpool2d_u8(ctx, tmp, tmp2, m, L->n, cg.oh, cg.ow, pool_k, pool_s);
-        if (rc == I8IE_OK) rc = i8ie_launch_nchw_to_nhwc(ctx, tmp2, out, m, L->n, oph, opw, out_border);
-        i8ie_free(ctx, tmp2);
-      }
-    }
-    i8ie_free(ctx, tmp);
-    return rc;
-  }
-  const int ph = pool ? (cg.oh - pool_k) / pool_s + 1 : cg.oh, pw = pool ? (cg.ow - pool_k) / pool_s + 1 : cg.ow;
-  const size_t in_bytes = (size_t)m * cg.c * cg.h * cg.w;
-  const size_t out_bytes = (size_t)m * cg.kc * ph * pw;
-  const int path = (L->path == PATH_G || L->path == PATH_T) ? L->path : (force_fallback(ctx) ? PATH_F : L->path);
-
-  if (path == PATH_T) return forward_transposed(L, cg, in, in_layout, in_border, m, s_in, zp_in, relu, out, out_layout, out_border, acc);
-
-  if (path == PATH_G) {
-    // grouped: NHWC in and out of the kernel (the input's own border serves, or bounds checks against zp_in); the layout
-    // conversions around it as on the other paths.  The force-fallback option picks gconv_direct inside the launcher.
-    const bool in_nchw = in_layout == I8IE_LAYOUT_NCHW, out_nchw = out_layout == I8IE_LAYOUT_NCHW;
-    const size_t a_bytes = in_nchw ? i8ie_align_up(in_bytes, 256) : 0;
-    const size_t o_bytes = out_nchw ? i8ie_align_up(out_bytes, 256) : 0;
-    if (a_bytes + o_bytes) I8IE_TRY(i8ie_ws_reserve(ctx, a_bytes + o_bytes + 256));
-    uint8_t* ws = (uint8_t*)ctx->ws;
-    if (in_nchw) I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, in, ws, m, cg.c, cg.h, cg.w, 0));
-    I8ieGconvCall g{};
-    g.A = in_nchw ? ws : in; g.m = m; g.H = cg.h; g.W = cg.w; g.C = cg.c; g.ib = in_nchw ? 0 : in_border;
-    g.OH = cg.oh; g.OW = cg.ow; g.stride = cg.stride; g.pad = cg.pad; g.KH = cg.kh; g.KW = cg.kw;
-    g.groups = L->groups; g.Cg = cg.c / L->groups; g.Ng = L->n / L->groups; g.Ngp = L->Ngp; g.Kgp = L->Kgp;
-    g.Bp = L->Bg; g.ktab = L->gtab; g.ocp = L->ocp; g.msv = msv_arg(L); g.sbv = sbv_arg(L);
-    g.s_in = s_in; g.s_w = sw_arg(L); g.s_out = L->s_out; g.zp_in = zp_in; g.zp_out = L->zp_out; g.relu = relu;
-    g.out = out_nchw ? ws + a_bytes : out; g.ob = out_nchw ? 0 : out_border; g.acc = acc;
-    I8IE_TRY(i8ie_gconv_launch(ctx, g));
-    if (out_nchw) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, g.out, out, m, cg.kc, cg.oh, cg.ow, 0));
-    return I8IE_OK;
-  }
-
-  if (path == PATH_F) {
-    const int ipc = chunk_images(cg, m);
-    const size_t col_bytes = i8ie_align_up((size_t)ipc * cg.oh * cg.ow * cg.Kpad, 256);
-    const size_t a_bytes = in_layout == I8IE_LAYOUT_NHWC ? i8ie_align_up(in_bytes, 256) : 0;
-    const size_t o_bytes = out_layout == I8IE_LAYOUT_NHWC ? i8ie_align_up(out_bytes, 256) : 0;
-    I8IE_TRY(i8ie_ws_reserve(ctx, col_bytes + a_bytes + o_bytes));
-    uint8_t* ws = (uint8_t*)ctx->ws;
-    uint8_t* col = ws;
-    const uint8_t* src = in;
-    if (a_bytes) {
-      I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, in, ws + col_bytes, m, cg.c, cg.h, cg.w, in_border));
-      src = ws + col_bytes;
-    }
-    uint8_t* dst = o_bytes ? ws + col_bytes + a_bytes : out;
-    I8IE_TRY(conv_run_v1(ctx, src, m, cg, L->Bpack, L->oc, L->wsum, zp_in, s_in, L->s_w, L->s_out, L->zp_out, dst, acc,
-                         col, ipc, sbv_arg(L)));
-    if (relu) I8IE_TRY(i8ie_relu_u8(ctx, dst, dst, (int64_t)out_bytes, L->zp_out));
-    if (o_bytes) {
-      I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, dst, out, m, cg.kc, cg.oh, cg.ow, out_border));
-    }
-    return I8IE_OK;
-  }
-
-  I8ieIgemmCall c{};
-  c.amode = 1; c.M = m * cg.oh * cg.ow;
-  c.B = L->Bpack2; c.Kpad = L->Kpad2; c.Npad = L->Npad; c.Kchunks = L->K2 / 16; c.N = L->n; c.ocp = L->ocp;
-  c.biasf = nullptr; c.wcache = &L->wc;
-  c.s_in = s_in; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = relu;
-  c.acc = acc; c.Ktrue = cg.K; c.OH = cg.oh; c.OW = cg.ow; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
-  if (pconv) {  // (the patch-stationary kernel said it takes this launch as it is)
-    c.pool_k = pool ? pool_k : 0; c.pool_s = pool_s; c.a_s8 = in_s8 ? 1 : 0; c.out_s8 = out_s8 ? 1 : 0;
-  }
-  const size_t o_bytes = out_layout == I8IE_LAYOUT_NCHW ? i8ie_align_up(out_bytes, 256) : 0;
-
-  if (path == PATH_A) {
-    const int Hp = cg.h + 2 * cg.pad, Wp = cg.w + 2 * cg.pad;
-    const bool direct = in_layout != I8IE_LAYOUT_NCHW && in_border >= cg.pad && aligned16(in);
-    const size_t a_bytes = direct ? 0 : i8ie_align_up((size_t)m * Hp * Wp * cg.c, 256);
-    I8IE_TRY(i8ie_ws_reserve(ctx, a_bytes + o_bytes + 256));
-    uint8_t* ws = (uint8_t*)ctx->ws;
-    if (direct) {
-      const int iHp = cg.h + 2 * in_border, iWp = cg.w + 2 * in_border, d = in_border - cg.pad;
-      const size_t shift = ((size_t)d * iWp + d) * cg.c;
-      c.A = in + shift;
-      c.a_bytes = (size_t)m * iHp * iWp * cg.c - shift;
-      c.Hp = iHp; c.Wp = iWp;
-    } else {
-      if (in_layout != I8IE_LAYOUT_NCHW) {  // (re-biased bytes are copied as they are; their border value is zp ^ 0x80)
-        I8IE_TRY(i8ie_launch_reborder(ctx, in, ws, m, cg.c, cg.h, cg.w, in_border, cg.pad, in_s8 ? (zp_in ^ 0x80) : zp_in));
-      } else {
-        if (cg.pad > 0) I8IE_HIP_TRY(hipMemsetAsync(ws, zp_in, (size_t)m * Hp * Wp * cg.c, ctx->stream));
-        I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, in, ws, m, cg.c, cg.h, cg.w, cg.pad));
-      }
-      c.A = ws;
-      c.a_bytes = (size_t)m * Hp * Wp * cg.c;
-      c.Hp = Hp; c.Wp = Wp;
-    }
-    c.C = cg.c; c.KH = cg.kh; c.KW = cg.kw; c.sh = c.sw = cg.stride;
-    c.out = o_bytes ? ws + a_bytes : out;
-  } else {  // PATH_B: small-C, stride % 4 == 0
-    const int Hp = (cg.oh - 1) * cg.stride + cg.kh;
-    const int Wg = (cg.ow - 1) * (cg.stride / 4) + L->kwg;
-    const size_t t_bytes = in_layout != I8IE_LAYOUT_NCHW ? i8ie_align_up(in_bytes, 256) : 0;
-    const size_t r_bytes = i8ie_align_up((size_t)m * Hp * Wg * 16, 256);
-    if (stem && (acc == nullptr || aligned16(acc))) {
-      // first-stage kernel (i8ie_stem.hip): space-to-depth image, conv (+ relu) (+ max-pool) in one contraction launch
-      const size_t s_bytes = i8ie_align_up(i8ie_stem_scratch_bytes(m, cg.kh, cg.kw, cg.stride, cg.oh, cg.ow), 256);
-      I8IE_TRY(i8ie_ws_reserve(ctx, t_bytes + s_bytes + o_bytes + 256));
-      uint8_t* ws = (uint8_t*)ctx->ws;
-      const uint8_t* src = in;
-      if (t_bytes) {
-        I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, in, ws, m, cg.c, cg.h, cg.w, in_border));
-        src = ws;
-      }
-      uint8_t* dst = o_bytes ? ws + t_bytes + s_bytes : out;
-      I8ieStemCall f{};
-      f.x = nullptr; f.xu8 = src; f.scratch = ws + t_bytes;
-      f.n = m; f.c = cg.c; f.h = cg.h; f.w = cg.w; f.q_scale = s_in; f.q_zp = zp_in;
-      f.KH = cg.kh; f.KW = cg.kw; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
-      f.B = L->Bstem; f.Kpad = L->KpadStem; f.N = L->n; f.ocp = L->ocp;
-      f.s_in = s_in; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = relu;
-      f.pool_k = pool ? pool_k : 0; f.pool_s = pool_s;
-      f.out = dst; f.ob = o_bytes ? 0 : out_border; f.out_s8 = out_s8 ? 1 : 0; f.acc = acc;
-      f.msv = msv_arg(L); f.sbv = sbv_arg(L);
-      I8IE_TRY(i8ie_stem_launch(ctx, f));
-      if (o_bytes) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, dst, out, m, cg.kc, ph, pw, 0));
-      return I8IE_OK;
-    }
-    I8IE_TRY(i8ie_ws_reserve(ctx, t_bytes + r_bytes + o_bytes + 256));
-    uint8_t* ws = (uint8_t*)ctx->ws;
-    const uint8_t* src = in;
-    if (t_bytes) {
-      I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, in, ws, m, cg.c, cg.h, cg.w, in_border));
-      src = ws;
-    }
-    uint8_t* rep = ws + t_bytes;
-    const bool wstat = (acc == nullptr || (L->n % 4 == 0 && aligned16(acc))) && i8ie_first_supported(cg.c, cg.stride, L->n, L->K2, cg.kh, L->kwg, cg.ow);
-    I8IE_TRY(i8ie_launch_repack_smallc(ctx, src, rep, m, cg.c, cg.h, cg.w, Hp, Wg, cg.pad, cg.pad, zp_in, wstat));
-    if (wstat) {
-      // weights-stationary small-C kernel (i8ie_first.hip) on the grouped image
-      uint8_t* dst = o_bytes ? ws + t_bytes + r_bytes : out;
-      const int ob = o_bytes ? 0 : out_border;
-      I8ieFirstCall f{};
-      f.x = nullptr; f.grouped = rep; f.scratch = nullptr;
-      f.n = m; f.c = cg.c; f.h = cg.h; f.w = cg.w; f.q_scale = s_in; f.q_zp = zp_in;
-      f.KH = cg.kh; f.KW = cg.kw; f.KWG = L->kwg; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
-      f.B = L->Bpack2; f.Kpad = L->Kpad2; f.K2 = L->K2; f.N = L->n; f.ocp = L->ocp;
-      f.s_in = s_in; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = relu;
-      f.out = dst; f.ob = ob; f.acc = acc; f.msv = msv_arg(L); f.sbv = sbv_arg(L);
-      I8IE_TRY(i8ie_first_launch(ctx, f));
-      if (o_bytes) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, dst, out, m, cg.kc, cg.oh, cg.ow, 0));
-      return I8IE_OK;
-    }
-    c.A = rep;
-    c.a_bytes = (size_t)m * Hp * Wg * 16;
-    c.Hp = Hp; c.Wp = Wg; c.C = 16; c.KH = cg.kh; c.KW = L->kwg;
-    c.sh = cg.stride; c.sw = cg.stride / 4;
-    c.out = o_bytes ? ws + t_bytes + r_bytes : out;
-  }
-  c.ob = o_bytes ? 0 : out_border;
-  I8IE_TRY(i8ie_igemm_launch(ctx, c));
-  if (o_bytes) I8IE_TRY(i8ie_launch_nhwc_to_nchw(ctx, c.out, out, m, cg.kc, cg.oh, cg.ow, 0));
-  return I8IE_OK;
+// ---- the layout / pool negotiation: each query builds the request it means and reads the plan -----------------------------
+// (NHWC in with the layer's padding as its border, NHWC out without one, no buffers yet: null pointers count as aligned)
+static bool query_plan(const i8ie_layer* L, int m, int h, int w, int pool_k, int pool_s, int in_layout, int out_layout, ConvPlan* p,
+                       ConvGeom* cg) {
+  if (conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, cg) != I8IE_OK) return false;
+  ConvRequest q = make_request(nullptr, in_layout, cg->pad, m, h, w, 0.0f, 0, 0, nullptr, out_layout, 0, nullptr);
+  q.pool_k = pool_k; q.pool_s = pool_s;
+  if (q.pool() && (pool_s < 1 || pool_k > cg->oh || pool_k > cg->ow)) return false;
+  *p = conv_plan(const_cast<i8ie_layer*>(L), *cg, q);
+  return true;
 }
 
 int i8ie_layer_accepts_f32_input(const i8ie_layer* L, int h, int w, int* yes) {
   I8IE_REQUIRE(L && yes, "null argument");
   *yes = 0;
-  if (!L->conv || L->path != PATH_B || force_fallback(L->ctx)) return I8IE_OK;
+  ConvPlan p;
   ConvGeom cg;
-  if (conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg) != I8IE_OK) return I8IE_OK;
-  *yes = (stem_takes(L, cg, 0, 0) || i8ie_first_supported(L->c, L->stride, L->n, L->K2, L->kh, L->kwg, cg.ow)) ? 1 : 0;
+  if (!L->conv || L->path != PATH_B || force_fallback(L->ctx)) return I8IE_OK;
+  if (!query_plan(L, 1, h, w, 0, 0, I8IE_LAYOUT_NCHW, I8IE_LAYOUT_NHWC, &p, &cg)) return I8IE_OK;
+  *yes = (p.stem || i8ie_first_supported(L->c, L->stride, L->n, L->K2, L->kh, L->kwg, cg.ow)) ? 1 : 0;
   return I8IE_OK;
 }
 
 int i8ie_layer_fuses_pool(const i8ie_layer* L, int m, int h, int w, int pool_k, int pool_s, int* yes) {
   I8IE_REQUIRE(L && yes, "null argument");
   *yes = 0;
-  if (!L->conv || L->path == PATH_T || pool_k < 1 || pool_s < 1 || m < 1) return I8IE_OK;
+  ConvPlan p;
   ConvGeom cg;
-  if (conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg) != I8IE_OK) return I8IE_OK;
-  if (pool_k > cg.oh || pool_k > cg.ow) return I8IE_OK;
-  *yes = (stem_takes(L, cg, pool_k, pool_s) || pconv_probe(const_cast<i8ie_layer*>(L), cg, m, cg.pad, pool_k, pool_s, false, false)) ? 1 : 0;
+  if (!L->conv || L->path == PATH_T || pool_k < 1 || pool_s < 1 || m < 1) return I8IE_OK;
+  if (query_plan(L, m, h, w, pool_k, pool_s, I8IE_LAYOUT_NHWC, I8IE_LAYOUT_NHWC, &p, &cg)) *yes = (p.stem || p.pconv) ? 1 : 0;
   return I8IE_OK;
 }
 
 int i8ie_layer_rebiased_io(const i8ie_layer* L, int m, int h, int w, int pool_k, int pool_s, int* reads, int* stores) {
   I8IE_REQUIRE(L && reads && stores, "null argument");
   *reads = *stores = 0;
-  if (!L->conv || L->path == PATH_T || m < 1) return I8IE_OK;
+  ConvPlan in, out;
   ConvGeom cg;
-  if (conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg) != I8IE_OK) return I8IE_OK;
-  const bool pool = i8ie_is_pool(pool_k, pool_s);
-  if (pool && (pool_s < 1 || pool_k > cg.oh || pool_k > cg.ow)) return I8IE_OK;
-  i8ie_layer* Lm = const_cast<i8ie_layer*>(L);
-  *reads = pconv_probe(Lm, cg, m, cg.pad, pool ? pool_k : 0, pool_s, true, false) ? 1 : 0;
-  *stores = (stem_takes(L, cg, pool ? pool_k : 0, pool_s) || pconv_probe(Lm, cg, m, cg.pad, pool ? pool_k : 0, pool_s, false, true)) ? 1 : 0;
+  if (!L->conv || L->path == PATH_T || m < 1) return I8IE_OK;
+  if (!query_plan(L, m, h, w, pool_k, pool_s, I8IE_LAYOUT_NHWC_S8, I8IE_LAYOUT_NHWC, &in, &cg) ||
+      !query_plan(L, m, h, w, pool_k, pool_s, I8IE_LAYOUT_NHWC, I8IE_LAYOUT_NHWC_S8, &out, &cg))
+    return I8IE_OK;
+  *reads = in.pconv ? 1 : 0;
+  *stores = (out.stem || out.pconv) ? 1 : 0;
   return I8IE_OK;
 }
 
@@ -1156,69 +1198,26 @@ int i8ie_layer_forward_f32_input_pool(i8ie_layer* L, const float* in, int m, int
     i8ie_set_error("i8ie_layer_forward_f32_input: layer/geometry not supported by the fused first-layer kernels");
     return I8IE_ERR_STATE;
   }
-  i8ie_ctx* ctx = L->ctx;
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  I8IE_HIP_TRY(hipSetDevice(L->ctx->device));
   I8IE_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15u) == 0, "output must be 16-byte aligned");
   I8IE_REQUIRE(acc == nullptr || aligned16(acc), "accumulator buffer must be 16-byte aligned");
   I8IE_TRY(ensure_offsets(L, q_scale, q_zp));
   I8IE_TRY(ensure_multipliers(L, q_scale));
   ConvGeom cg;
   I8IE_TRY(conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg));
-  const bool pool = i8ie_is_pool(pool_k, pool_s);
-  if (pool) {
-    I8IE_REQUIRE(pool_s > 0 && pool_k <= cg.oh && pool_k <= cg.ow, "max-pool window larger than the convolution's output");
-  }
-  if (stem_takes(L, cg, pool ? pool_k : 0, pool_s)) {
-    I8IE_TRY(i8ie_ws_reserve(ctx, i8ie_stem_scratch_bytes(m, cg.kh, cg.kw, cg.stride, cg.oh, cg.ow) + 256));
-    I8ieStemCall f{};
-    f.x = in; f.xu8 = nullptr; f.scratch = (uint8_t*)ctx->ws;
-    f.n = m; f.c = cg.c; f.h = h; f.w = w; f.q_scale = q_scale; f.q_zp = q_zp;
-    f.KH = cg.kh; f.KW = cg.kw; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
-    f.B = L->Bstem; f.Kpad = L->KpadStem; f.N = L->n; f.ocp = L->ocp;
-    f.s_in = q_scale; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = relu;
-    f.pool_k = pool ? pool_k : 0; f.pool_s = pool_s;
-    f.out = out; f.ob = out_border; f.out_s8 = out_layout == I8IE_LAYOUT_NHWC_S8 ? 1 : 0; f.acc = acc;
-    f.msv = msv_arg(L); f.sbv = sbv_arg(L);
-    return i8ie_stem_launch(ctx, f);
-  }
-  if (pool || out_layout == I8IE_LAYOUT_NHWC_S8) {
-    // the older first-layer kernel neither pools nor stores re-biased: conv (+ relu) into a temporary, then the rest
-    I8IE_REQUIRE(L->n % 16 == 0, "i8ie_layer_forward_f32_input_pool: out features % 16 != 0");
-    const int oph = pool ? (cg.oh - pool_k) / pool_s + 1 : cg.oh, opw = pool ? (cg.ow - pool_k) / pool_s + 1 : cg.ow;
-    uint8_t *tmp = nullptr, *tmp2 = nullptr;
-    I8IE_TRY(i8ie_malloc(ctx, (size_t)m * L->n * cg.oh * cg.ow, (void**)&tmp));
-    int rc = i8ie_layer_forward_f32_input_pool(L, in, m, h, w, q_scale, q_zp, relu, 0, 0, tmp, I8IE_LAYOUT_NHWC, 0, acc);
-    if (rc == I8IE_OK && out_layout == I8IE_LAYOUT_NHWC) {
-      rc = i8ie_launch_maxpool_nhwc(ctx, tmp, 0, out, out_border, m, L->n, cg.oh, cg.ow, pool_k, pool_s, 0);
-    } else if (rc == I8IE_OK) {
-      uint8_t* plain = tmp;
-      if (pool) {
-        rc = i8ie_malloc(ctx, (size_t)m * L->n * oph * opw, (void**)&tmp2);
-        if (rc == I8IE_OK) rc = i8ie_launch_maxpool_nhwc(ctx, tmp, 0, tmp2, 0, m, L->n, cg.oh, cg.ow, pool_k, pool_s, 0);
-        plain = tmp2;
-      }
-      if (rc == I8IE_OK) rc = i8ie_rebias_u8(ctx, plain, plain, (int64_t)m * L->n * oph * opw);
-      if (rc == I8IE_OK) rc = i8ie_launch_reborder(ctx, plain, out, m, L->n, oph, opw, 0, out_border, L->zp_out ^ 0x80);
-    }
-    i8ie_free(ctx, tmp);
-    if (tmp2) i8ie_free(ctx, tmp2);
-    return rc;
-  }
-  I8IE_TRY(i8ie_ws_reserve(ctx, i8ie_first_scratch_bytes(m, cg.kh, L->kwg, cg.stride, cg.oh, cg.ow) + 256));
-  I8ieFirstCall c{};
-  c.x = in; c.grouped = nullptr; c.scratch = (uint8_t*)ctx->ws;
-  c.n = m; c.c = cg.c; c.h = h; c.w = w; c.q_scale = q_scale; c.q_zp = q_zp;
-  c.KH = cg.kh; c.KW = cg.kw; c.KWG = L->kwg; c.stride = cg.stride; c.pad = cg.pad; c.OH = cg.oh; c.OW = cg.ow;
-  c.B = L->Bpack2; c.Kpad = L->Kpad2; c.K2 = L->K2; c.N = L->n; c.ocp = L->ocp;
-  c.s_in = q_scale; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = relu;
-  c.out = out; c.ob = out_border; c.acc = acc; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
-  return i8ie_first_launch(ctx, c);
+  ConvRequest q = make_request(nullptr, I8IE_LAYOUT_NCHW, 0, m, h, w, q_scale, q_zp, relu, out, out_layout, out_border, acc);
+  q.x = in; q.pool_k = pool_k; q.pool_s = pool_s;
+  if (q.pool()) I8IE_REQUIRE(pool_s > 0 && pool_k <= cg.oh && pool_k <= cg.ow, "max-pool window larger than the convolution's output");
+  // plan, peel and route as for a u8 forward: what the kernel that takes the launch does not fold (the older first-layer kernel
+  // neither pools nor stores re-biased) runs as launches of its own behind the plain result
+  return forward_conv(L, cg, q);
 }
 
 int i8ie_layer_forward_f32_input(i8ie_layer* L, const float* in, int m, int h, int w, float q_scale, uint8_t q_zp,
                                  int relu, uint8_t* out, int out_border, int32_t* acc) {
   return i8ie_layer_forward_f32_input_pool(L, in, m, h, w, q_scale, q_zp, relu, 0, 0, out, I8IE_LAYOUT_NHWC, out_border, acc);
 }
+
 
 int i8ie_layer_forward(i8ie_layer* L, const uint8_t* in, int m, int h, int w, float s_in, uint8_t zp_in, uint8_t* out,
                        int32_t* acc) {

@@ -1,6 +1,7 @@
 """ctypes binding of libi8ie_hip.so used by the tests (and a model of the stub an
 FFI user would write).  numpy in, numpy out; every call goes
 through the C-ABI declared in include/i8ie_hip.h."""
+import contextlib
 import ctypes as C
 import os
 import re
@@ -122,6 +123,12 @@ class GuardedU8:
 
     def free(self):
         self.buf.free()
+
+
+class ProfEntry(C.Structure):
+    """i8ie_profile_entry of include/i8ie_hip.h"""
+    _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double),
+                ("total_ops", C.c_double), ("total_bytes", C.c_double)]
 
 
 class Ctx:
@@ -367,6 +374,34 @@ class Ctx:
         r = o.get()
         d.free(); o.free()
         return r
+
+    def set_variant(self, value):
+        ck(lib().i8ie_ctx_set_option(self.h, 2, int(value)))
+
+    @contextlib.contextmanager
+    def launch_map(self):
+        """Inside: every launch on this ctx is profiled.  Yields a dict that holds, once the block has ended, kernel name
+        (cut at '|') -> launches."""
+        got = {}
+        ck(lib().i8ie_profile_start(self.h, 0))
+        try:
+            yield got
+        finally:
+            ents, cnt = (ProfEntry * 128)(), C.c_int(0)
+            ck(lib().i8ie_profile_stop(self.h, ents, 128, C.byref(cnt)))
+            for e in ents[:cnt.value]:
+                name = e.name.decode().split("|")[0]
+                got[name] = got.get(name, 0) + int(e.launches)
+
+    def layer_queries(self, L, m, h, w, pool_k, pool_s):
+        """The layout / pool negotiation answers of a layer handle at batch m, input h x w, with this pool behind it."""
+        fuses, reads, stores, f32, pref = (C.c_int(-1) for _ in range(5))
+        ck(lib().i8ie_layer_fuses_pool(L, m, h, w, pool_k, pool_s, C.byref(fuses)))
+        ck(lib().i8ie_layer_rebiased_io(L, m, h, w, pool_k, pool_s, C.byref(reads), C.byref(stores)))
+        ck(lib().i8ie_layer_accepts_f32_input(L, h, w, C.byref(f32)))
+        ck(lib().i8ie_layer_preferred_layout(L, C.byref(pref)))
+        return dict(fuses_pool=fuses.value, reads_s8=reads.value, stores_s8=stores.value, accepts_f32=f32.value,
+                    preferred_layout=pref.value)
 
     @staticmethod
     def to_phys(q_nchw, border, fill):

@@ -49,7 +49,7 @@ def dispatch(case):
 
 
 def header_rejects(case):
-    """the argument checks of layer_forward_impl / conv_geom that a drawn shape can miss (message, or None)"""
+    """the argument checks of layer_forward / conv_geom that a drawn shape can miss (message, or None)"""
     if case.h - case.kh + 2 * case.pad < 0 or case.w - case.kw + 2 * case.pad < 0:
         return "kernel larger than padded input"
     if (not case.in_nhwc and case.ib) or (not case.out_nhwc and case.ob):
