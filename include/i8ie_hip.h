@@ -468,7 +468,7 @@ int i8ie_maxpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, 
  *     q  = t >= 255 ? 255 : (t < 0 ? 0 : (u8)t)          truncation toward zero
  *     q  = relu ? max(q, zp_out) : q
  * (s_a, zp_a), (s_b, zp_b): the operands' own quantisation parameters; (s_out, zp_out): the result's.  The bytes equal
- * that sequence for every input pair, whichever way the kernel evaluates it (csrc/i8ie_add.hip).  Scales must be
+ * that sequence for every input pair, whichever way the kernel evaluates it (csrc/i8ie_binary.hip).  Scales must be
  * finite and s_out > 0 (I8IE_ERR_ARG otherwise).  Stateless and capturable in a graph.
  * i8ie_add_u8: n bytes in one physical order (NCHW, [m, k] rows, border-free NHWC); 16-byte aligned buffers; out may
  * alias a or b, and a may be b. */
@@ -497,7 +497,7 @@ int i8ie_add_f32(i8ie_ctx* ctx, const float* a_dev, const float* b_dev, float* o
  * b has a's shape, or is a gate: for a of shape [n, c, h, w] one byte per image and channel ([n, c, 1, 1] or [n, c]),
  * multiplied into every pixel of that image (the excitation of a squeeze-and-excitation block).  Only the second operand
  * broadcasts; the result has a's shape and its own (s_out, zp_out).  The bytes equal that sequence for every input
- * pair, whichever way the kernel evaluates it (csrc/i8ie_mul.hip).  Scales must be finite and
+ * pair, whichever way the kernel evaluates it (csrc/i8ie_binary.hip).  Scales must be finite and
  * s_out > 0 (I8IE_ERR_ARG otherwise, like every other argument error before any device call).  Stateless and
  * capturable in a graph.
  * i8ie_mul_u8: n bytes of each operand in one physical order (NCHW, [m, k] rows, border-free NHWC); 16-byte aligned

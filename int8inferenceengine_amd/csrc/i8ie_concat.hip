@@ -20,7 +20,7 @@
 //   exact    the sequence itself ((float)a - (float)zp_i is the exact integer difference).
 //   guarded  f as above (the same one product), then e = fma(f, r, zp_out - 0.5) with r = fl(1 / s_out) from the host, packed
 //            with v_cvt_pk_u8_f32 (round to nearest even, saturate).  A dword holding a value closer than 2^-13 to a rounding
-//            boundary replays the exact sequence: the rule of i8ie_requant.h.
+//            boundary replays the exact sequence: the guarded pack of i8ie_requant.h.
 //            Bound: while |f / s_out| < 257 (which covers every t in (-1, 256), zp_out being in [0, 255]) every value involved
 //            is below 512, where half an ulp is 2^-16.  The reference rounds twice (the quotient, the sum: each <= 2^-16); the
 //            estimate has the relative error 2^-24 of r on a product below 257 (<= 257 * 2^-24 < 2^-15.99) and the one rounding
@@ -32,6 +32,7 @@
 
 #include "i8ie_internal.h"
 #include "i8ie_pointwise.h"
+#include "i8ie_requant.h"
 
 namespace {
 
@@ -94,11 +95,9 @@ __device__ __forceinline__ uint32_t cat4(uint32_t a4, const CatIn& d, const CatO
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float f = ((float)((a4 >> (8 * r)) & 0xFFu) - d.zp) * d.s;
-      const float e = __builtin_fmaf(f, o.rc, o.zph);
-      packed = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaxf(e, o.lof), r, packed);
-      worst = __builtin_fminf(worst, __builtin_fabsf(__builtin_amdgcn_fractf(e) - 0.5f));
+      packed = i8ie_requant_est_step(__builtin_fmaf(f, o.rc, o.zph), o.lof, r, packed, worst);
     }
-    if (worst >= 1.220703125e-4f) return packed ^ o.x;  // 2^-13 > 6.2e-5, the proven bound
+    if (i8ie_requant_est_ok(worst)) return packed ^ o.x;
   }
   uint32_t packed = 0;
 #pragma unroll
@@ -194,9 +193,7 @@ int mode_of(float s_i, int zp_i, float s_out, int zp_out) {
 // items of 16 / 4 / 1 bytes: the widest that divides the input's unit, its offset in the output unit, the output unit, and
 // both base addresses
 uint32_t vec_of(int64_t c, int64_t off, int64_t total, const void* in, const void* out) {
-  for (uint32_t v = 16; v > 1; v >>= 2)
-    if (c % v == 0 && off % v == 0 && total % v == 0 && aligned_to(in, v) && aligned_to(out, v)) return v;
-  return 1;
+  return (uint32_t)item_width({c, off, total}, {in, out});
 }
 // items of input i and the grid stride in its own (image, row, pixel, item) digits
 void set_walk(CatIn& d, int64_t units, uint32_t h, uint32_t w, int64_t stride) {

@@ -70,8 +70,7 @@ __global__ __launch_bounds__(kThreads) void lut_u8_flat_kernel(const uint8_t* in
   if (VEC > 1 && blockIdx.x == 0 && threadIdx.x < (n - t0)) out[t0 + threadIdx.x] = (uint8_t)lut1(mine, in[t0 + threadIdx.x]);
 }
 
-// ---- bordered NHWC form: [n][h + 2b][w + 2b][c] per buffer, each with its own b.  The w * c interior bytes of an image row
-// are the contiguous unit; an item is VEC bytes of one row (every row start is VEC-aligned in both buffers: c % VEC == 0).
+// ---- bordered NHWC form: [n][h + 2b][w + 2b][c] per buffer, each with its own b, walked by row items (i8ie_pointwise.h)
 template <int VEC, typename Idx>
 __global__ __launch_bounds__(kThreads) void lut_u8_nhwc_kernel(const uint8_t* __restrict__ in, NhwcGeom gi, uint8_t* __restrict__ out, NhwcGeom go,
                                                                Idx items, Idx per_row, Idx h, const LutTable t) {
@@ -80,11 +79,8 @@ __global__ __launch_bounds__(kThreads) void lut_u8_nhwc_kernel(const uint8_t* __
   const uint8_t* mine = reinterpret_cast<const uint8_t*>(lds) + (threadIdx.x & 31u) * 4;
   const Idx stride = (Idx)gridDim.x * kThreads;
   for (Idx v = (Idx)blockIdx.x * kThreads + threadIdx.x; v < items; v += stride) {
-    const Idx r = v / per_row;
-    const int64_t col = (int64_t)(v - r * per_row) * VEC;
-    const Idx img = r / h;
-    const int64_t y = (int64_t)(r - img * h);
-    lut_item<VEC>(mine, in + (int64_t)img * gi.img + gi.org + y * gi.row + col, out + (int64_t)img * go.img + go.org + y * go.row + col);
+    const RowItem<Idx> it = row_item<VEC>(v, per_row, h);
+    lut_item<VEC>(mine, in + nhwc_at(gi, it), out + nhwc_at(go, it));
   }
 }
 
@@ -131,12 +127,10 @@ LutTable pack_table(const uint8_t* table, int in_s8, int out_s8) {
 }
 
 void launch_flat(i8ie_ctx* ctx, const uint8_t* in, uint8_t* out, int64_t n, const LutTable& t) {
-  if (aligned_to(in, 16) && aligned_to(out, 16))
-    lut_u8_flat_kernel<16><<<grid_for((n >> 4) + 1), kThreads, 0, ctx->stream>>>(in, out, n, t);
-  else if (aligned_to(in, 4) && aligned_to(out, 4))
-    lut_u8_flat_kernel<4><<<grid_for((n >> 2) + 1), kThreads, 0, ctx->stream>>>(in, out, n, t);
-  else
-    lut_u8_flat_kernel<1><<<grid_for(n), kThreads, 0, ctx->stream>>>(in, out, n, t);
+  const int vec = item_width({}, {in, out});  // (a ragged end goes byte by byte: n need not be a multiple)
+  if (vec == 16) lut_u8_flat_kernel<16><<<grid_for((n >> 4) + 1), kThreads, 0, ctx->stream>>>(in, out, n, t);
+  else if (vec == 4) lut_u8_flat_kernel<4><<<grid_for((n >> 2) + 1), kThreads, 0, ctx->stream>>>(in, out, n, t);
+  else lut_u8_flat_kernel<1><<<grid_for(n), kThreads, 0, ctx->stream>>>(in, out, n, t);
 }
 
 template <int VEC>
@@ -192,8 +186,9 @@ int i8ie_lut_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in, int in_border, int in_s8,
     launch_flat(ctx, in, out, total, t);
   } else {
     const NhwcGeom gi = buf_geom(c, h, w, in_border), go = buf_geom(c, h, w, out_border);
-    if (c % 16 == 0 && aligned_to(in, 16) && aligned_to(out, 16)) launch_nhwc<16>(ctx, in, gi, out, go, n, c, h, w, t);
-    else if (c % 4 == 0 && aligned_to(in, 4) && aligned_to(out, 4)) launch_nhwc<4>(ctx, in, gi, out, go, n, c, h, w, t);
+    const int vec = item_width({c}, {in, out});
+    if (vec == 16) launch_nhwc<16>(ctx, in, gi, out, go, n, c, h, w, t);
+    else if (vec == 4) launch_nhwc<4>(ctx, in, gi, out, go, n, c, h, w, t);
     else launch_nhwc<1>(ctx, in, gi, out, go, n, c, h, w, t);
   }
   I8IE_LAUNCH_CHECK();

@@ -1,12 +1,13 @@
-// i8ie_pointwise.h -- host helpers the pointwise units share (i8ie_elementwise, i8ie_add, i8ie_mul, i8ie_concat, i8ie_lut,
-// i8ie_avgpool): the launch constants and grid rule, the alignment test, i8ie_requant.h's "ordinary scale" rule, the
-// three-scale argument check of the two-operand ops and the geometry of a bordered NHWC buffer.  Everything here has internal
-// linkage (an unnamed namespace per including unit): no call crosses a translation unit through this header.
-// i8ie_gconv.hip and i8ie_deconv.hip include it for aligned_to alone.
+// i8ie_pointwise.h -- helpers the pointwise units share (i8ie_elementwise, i8ie_binary, i8ie_concat, i8ie_lut, i8ie_avgpool).
+// Host: the launch constants and grid rule, the alignment test and the item width it allows, i8ie_requant.h's "ordinary scale"
+// rule, the three-scale argument check of the two-operand ops and the geometry of a bordered NHWC buffer.  Device: the walk of
+// a bordered NHWC buffer by row items.  Everything here has internal linkage (an unnamed namespace per including unit): no
+// call crosses a translation unit through this header.  i8ie_gconv.hip and i8ie_deconv.hip include it for aligned_to alone.
 #pragma once
 
 #include <cmath>
 #include <cstdint>
+#include <initializer_list>
 
 namespace {
 
@@ -20,6 +21,17 @@ inline int grid_for(int64_t work_items) {
   return (int)(b > kMaxBlocks ? kMaxBlocks : b);
 }
 inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// items of 16 / 4 / 1 bytes: the widest that divides every one of `sizes` (the run of bytes an item must not straddle, and
+// whatever else must stay item-aligned) and to which every one of `bufs` is aligned
+inline int item_width(std::initializer_list<int64_t> sizes, std::initializer_list<const void*> bufs) {
+  for (int v = 16; v > 1; v >>= 2) {
+    bool ok = true;
+    for (int64_t s : sizes) ok = ok && s % v == 0;
+    for (const void* p : bufs) ok = ok && aligned_to(p, (unsigned)v);
+    if (ok) return v;
+  }
+  return 1;
+}
 
 // a scale the guarded estimate may be used with (i8ie_requant.h's rule): not zero, denormal or huge
 inline bool ordinary(float s) { return s > 1e-30f && s < 1e30f; }
@@ -42,5 +54,28 @@ inline NhwcGeom buf_geom(int c, int h, int w, int border) {
   g.org = (int64_t)border * g.row + (int64_t)border * c;
   return g;
 }
+
+#if defined(__HIPCC__)
+// The interior of a bordered NHWC buffer walked by row items.  The w * c interior bytes of an image row are the contiguous
+// unit; an item is VEC bytes of one row (c % VEC == 0 and VEC-aligned buffers: every row start is then VEC-aligned in every
+// buffer, whatever its border).  A launch covers items = n * h * per_row of them, per_row = w * c / VEC; Idx is uint32_t while
+// items fits, int64_t beyond.
+template <typename Idx>
+struct RowItem {
+  Idx img;
+  int64_t y, col;  // interior row, byte column in it
+};
+template <int VEC, typename Idx>
+__device__ __forceinline__ RowItem<Idx> row_item(Idx v, Idx per_row, Idx h) {
+  const Idx r = v / per_row;
+  const int64_t col = (int64_t)(v - r * per_row) * VEC;
+  const Idx img = r / h;
+  return {img, (int64_t)(r - img * h), col};
+}
+template <typename Idx>
+__device__ __forceinline__ int64_t nhwc_at(const NhwcGeom& g, const RowItem<Idx>& it) {
+  return (int64_t)it.img * g.img + g.org + it.y * g.row + it.col;
+}
+#endif
 
 }  // namespace

@@ -39,16 +39,30 @@ __host__ __device__ __forceinline__ int i8ie_requant_exact(float cf, const I8ieR
 // inside the unit interval [k, k+1) with k = rne(e), and the reference's trunc + clamp equals sat_u8(rne(e)),
 // which is what v_cvt_pk_u8_f32 computes.  Outside (-1, 256) both sides clamp, with the same margin.  relu
 // (max with zp_out) commutes with the monotone rounding: rne(max(e, lo)) for the integer lo.
+//
+// The guard exists once.  A pack is four steps, one per estimate e of (value) - 0.5, whatever e was computed from: byte r of
+// `packed` becomes sat_u8(rne(max(e, lof))) (v_cvt_pk_u8_f32; lof = -1 is no clamp at all, the pack saturates at 0, and
+// CLAMP = false leaves the max out), and `worst` keeps the smallest distance of any e to a rounding boundary.  It starts at 1,
+// or at 0 for a pack that must not stand (scales that do not allow the estimate).  The dword stands where
+// i8ie_requant_est_ok(worst): the threshold 2^-13 lies above every bound proven for an estimate in this library (9.2e-5 here
+// and for the gate multiply, 6.2e-5 for add, multiply and concat: i8ie_binary.hip, i8ie_concat.hip).  Otherwise the caller
+// replays its exact sequence.
+template <bool CLAMP = true>
+__device__ __forceinline__ uint32_t i8ie_requant_est_step(float e, float lof, int r, uint32_t packed, float& worst) {
+  packed = __builtin_amdgcn_cvt_pk_u8_f32(CLAMP ? __builtin_fmaxf(e, lof) : e, r, packed);
+  worst = __builtin_fminf(worst, __builtin_fabsf(__builtin_amdgcn_fractf(e) - 0.5f));
+  return packed;
+}
+__device__ __forceinline__ bool i8ie_requant_est_ok(float worst) { return worst >= 1.220703125e-4f; }
+
 __device__ __forceinline__ uint32_t i8ie_requant_pack4(const int (&c)[4], const I8ieRequant& q, int lo, float lof) {
   uint32_t packed = 0;
   float worst = q.fast ? 1.0f : 0.0f;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float e = __builtin_fmaf((float)c[r], q.ms, q.zpf - 0.5f);
-    packed = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaxf(e, lof), r, packed);
-    worst = __builtin_fminf(worst, __builtin_fabsf(__builtin_amdgcn_fractf(e) - 0.5f));
+    packed = i8ie_requant_est_step(__builtin_fmaf((float)c[r], q.ms, q.zpf - 0.5f), lof, r, packed, worst);
   }
-  if (worst >= 1.220703125e-4f) return packed;  // 2^-13 > 9.2e-5, the proven bound
+  if (i8ie_requant_est_ok(worst)) return packed;
   packed = 0;
 #pragma unroll
   for (int r = 0; r < 4; ++r) packed |= (uint32_t)i8ie_requant_exact((float)c[r], q, lo) << (8 * r);
@@ -62,11 +76,9 @@ __device__ __forceinline__ uint32_t i8ie_requant_pack4_norelu(const int (&c)[4],
   float worst = q.fast ? 1.0f : 0.0f;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float e = __builtin_fmaf((float)c[r], q.ms, q.zpf - 0.5f);
-    packed = __builtin_amdgcn_cvt_pk_u8_f32(e, r, packed);
-    worst = __builtin_fminf(worst, __builtin_fabsf(__builtin_amdgcn_fractf(e) - 0.5f));
+    packed = i8ie_requant_est_step<false>(__builtin_fmaf((float)c[r], q.ms, q.zpf - 0.5f), 0.0f, r, packed, worst);
   }
-  if (worst >= 1.220703125e-4f) return packed;
+  if (i8ie_requant_est_ok(worst)) return packed;
   packed = 0;
 #pragma unroll
   for (int r = 0; r < 4; ++r) packed |= (uint32_t)i8ie_requant_exact((float)c[r], q, 0) << (8 * r);
@@ -81,14 +93,11 @@ __device__ __forceinline__ uint32_t i8ie_requant_est4(const int (&c)[4], const I
   float w = q.fast ? 1.0f : 0.0f;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float e = __builtin_fmaf((float)c[r], q.ms, q.zpf - 0.5f);
-    packed = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaxf(e, lof), r, packed);
-    w = __builtin_fminf(w, __builtin_fabsf(__builtin_amdgcn_fractf(e) - 0.5f));
+    packed = i8ie_requant_est_step(__builtin_fmaf((float)c[r], q.ms, q.zpf - 0.5f), lof, r, packed, w);
   }
   worst = w;
   return packed;
 }
-__device__ __forceinline__ bool i8ie_requant_est_ok(float worst) { return worst >= 1.220703125e-4f; }
 __device__ __forceinline__ uint32_t i8ie_requant_exact4(const int (&c)[4], const I8ieRequant& q, int lo) {
   uint32_t packed = 0;
 #pragma unroll
@@ -120,9 +129,7 @@ __device__ __forceinline__ uint32_t i8ie_requant_est4_pc(const int (&c)[4], cons
   float w = q.fast ? 1.0f : 0.0f;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float e = __builtin_fmaf((float)c[r], m[r], q.zpf - 0.5f);
-    packed = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaxf(e, lof), r, packed);
-    w = __builtin_fminf(w, __builtin_fabsf(__builtin_amdgcn_fractf(e) - 0.5f));
+    packed = i8ie_requant_est_step(__builtin_fmaf((float)c[r], m[r], q.zpf - 0.5f), lof, r, packed, w);
   }
   worst = w;
   return packed;

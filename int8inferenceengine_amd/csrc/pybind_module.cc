@@ -815,19 +815,20 @@ void reconcile_pair(std::shared_ptr<Storage>& sa, std::shared_ptr<Storage>& sb, 
   }
 }
 
-Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
-  if (a.shape != b.shape) throw std::runtime_error("i8ie: add: shapes differ (there is no broadcasting)");
-  check_out_qparams("add", scale, zp);  // (add alone checks neither the operands' scales nor for an empty tensor)
+// The deferred result of a two-operand op on operands of one shape (add, the equal-shape mul), through the op's flat and NHWC
+// C entries.  Deferred like max_pool2d's result: relu(op(..)) is one launch, and a consuming conv gets its zero-point border
+// and, where it reads them, re-biased bytes straight from the op's kernel.  The caller has checked its arguments.
+using PairFlatFn = decltype(&i8ie_add_u8);
+using PairNhwcFn = decltype(&i8ie_add_u8_nhwc);
+Tensor<u8_t> equal_shape_u8(PairFlatFn flat, PairNhwcFn nhwc, Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
   Tensor<u8_t> out = pending_u8(a.shape, scale, (u8_t)zp);
   std::array<Tensor<u8_t>, 2> ops{a, b};  // share the operands' storage / pending launches
   const float s_a = a.scale, s_b = b.scale;
   const u8_t zp_a = a.zero_point, zp_b = b.zero_point, zp_o = (u8_t)zp;
   const std::vector<ssize_t> shp = a.shape;
   const ssize_t n = a.size;
-  // deferred like max_pool2d's result: relu(add(..)) is one launch, and a consuming conv gets its zero-point border and,
-  // where it reads them, re-biased bytes straight from the add kernel
   out.pend = make_pend(
-      [ops, s_a, s_b, zp_a, zp_b, scale, zp_o, shp, n](bool relu, int border, bool s8) mutable {
+      [flat, nhwc, ops, s_a, s_b, zp_a, zp_b, scale, zp_o, shp, n](bool relu, int border, bool s8) mutable {
         auto ss = resolve_operands(ops.data(), 2);
         NhwcCopies copies;
         reconcile_pair(ss[0], ss[1], shp, copies);
@@ -835,18 +836,23 @@ Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
         std::shared_ptr<Storage> st;
         if (sa->layout == I8IE_LAYOUT_NHWC) {
           st = nhwc_storage({sa->dn, sa->dc, sa->dh, sa->dw}, shp.size() == 4 ? border : 0, zp_o, s8);
-          check(i8ie_add_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
-                                 sb->border, sb->s8 ? 1 : 0, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, sa->dn, sa->dc, sa->dh,
-                                 sa->dw, s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
+          check(nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(), sb->border,
+                     sb->s8 ? 1 : 0, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, sa->dn, sa->dc, sa->dh, sa->dw, s_a, zp_a, s_b, zp_b,
+                     scale, zp_o, relu ? 1 : 0));
         } else {
           st = device_storage((size_t)n);
-          check(i8ie_add_u8(ctx(), (const uint8_t*)sa->device_ptr(), (const uint8_t*)sb->device_ptr(), (uint8_t*)st->dev, (int64_t)n,
-                            s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
+          check(flat(ctx(), (const uint8_t*)sa->device_ptr(), (const uint8_t*)sb->device_ptr(), (uint8_t*)st->dev, (int64_t)n, s_a, zp_a,
+                     s_b, zp_b, scale, zp_o, relu ? 1 : 0));
         }
         // (the operands are released with the closure's copies, as a layer's input is)
         return st;
       }, {a.pend, b.pend});
   return out;
+}
+Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
+  if (a.shape != b.shape) throw std::runtime_error("i8ie: add: shapes differ (there is no broadcasting)");
+  check_out_qparams("add", scale, zp);  // (add alone checks neither the operands' scales nor for an empty tensor)
+  return equal_shape_u8(i8ie_add_u8, i8ie_add_u8_nhwc, a, b, scale, zp);
 }
 // ---- mul (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_mul_u8) ----------------------------
 // b has a's shape (false), or is a gate [n, c, 1, 1] / [n, c] of a rank-4 a (true); anything else is a RuntimeError
@@ -870,51 +876,40 @@ Tensor<float> mul_f32(Tensor<float>& a, Tensor<float>& b) {
   check(i8ie_mul_f32(ctx(), a.dptr(), b.dptr(), out.dptr(), a.size, gate ? (int64_t)(a.shape[2] * a.shape[3]) : 0));
   return out;
 }
+// i8ie_mul_u8_nhwc on operands of one shape, with the add's argument list
+int mul_u8_nhwc_equal(i8ie_ctx* c, const uint8_t* a, int a_border, int a_s8, const uint8_t* b, int b_border, int b_s8, uint8_t* out,
+                      int out_border, int out_s8, int n, int ch, int h, int w, float s_a, uint8_t zp_a, float s_b, uint8_t zp_b,
+                      float s_out, uint8_t zp_out, int relu) {
+  return i8ie_mul_u8_nhwc(c, a, a_border, a_s8, b, b_border, b_s8, 0, out, out_border, out_s8, n, ch, h, w, s_a, zp_a, s_b, zp_b, s_out,
+                          zp_out, relu);
+}
 Tensor<u8_t> mul_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
   const bool gate = mul_is_gate(a, b);
   check_out_qparams("mul", scale, zp);
   if (!std::isfinite(a.scale) || !std::isfinite(b.scale)) throw std::runtime_error("i8ie: mul: an operand's scale is not finite");
   if ((!a.st && !a.pend) || (!b.st && !b.pend)) throw std::runtime_error("i8ie: empty tensor");
+  if (!gate) return equal_shape_u8(i8ie_mul_u8, mul_u8_nhwc_equal, a, b, scale, zp);
   Tensor<u8_t> out = pending_u8(a.shape, scale, (u8_t)zp);
   std::array<Tensor<u8_t>, 2> ops{a, b};  // share the operands' storage / pending launches
   const float s_a = a.scale, s_b = b.scale;
   const u8_t zp_a = a.zero_point, zp_b = b.zero_point, zp_o = (u8_t)zp;
   const std::vector<ssize_t> shp = a.shape;
-  const ssize_t n = a.size;
-  // deferred like add's result: relu(mul(..)) is one launch, and a consuming conv gets its zero-point border and, where it
-  // reads them, re-biased bytes straight from the mul kernel
+  // deferred like the equal-shape result
   out.pend = make_pend(
-      [ops, gate, s_a, s_b, zp_a, zp_b, scale, zp_o, shp, n](bool relu, int border, bool s8) mutable {
+      [ops, s_a, s_b, zp_a, zp_b, scale, zp_o, shp](bool relu, int border, bool s8) mutable {
         // (the gate of a squeeze-and-excitation block is f(a), still pending: it launches first, and a is read as it lies)
         auto ss = resolve_operands(ops.data(), 2);
         NhwcCopies copies;
-        std::shared_ptr<Storage>& sa = ss[0];
+        std::shared_ptr<Storage> sa = as_engine_nhwc(ss[0], shp, copies);
         std::shared_ptr<Storage>& sb = ss[1];
-        std::shared_ptr<Storage> st;
-        if (gate) {
-          sa = as_engine_nhwc(sa, shp, copies);
-          // the gate as its producer left it: an [n, c, 1, 1] NHWC buffer with its border and re-bias, or plain rows (an
-          // NCHW [n, c, 1, 1] tensor is the same bytes)
-          const bool g_nhwc = sb->layout == I8IE_LAYOUT_NHWC && sb->dn == shp[0] && sb->dc == shp[1] && sb->dh == 1 && sb->dw == 1;
-          if (!g_nhwc) sb->to_nchw();
-          st = nhwc_storage(shp, border, zp_o, s8);
-          check(i8ie_mul_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
-                                 g_nhwc ? sb->border : 0, g_nhwc && sb->s8 ? 1 : 0, 1, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0,
-                                 (int)shp[0], (int)shp[1], (int)shp[2], (int)shp[3], s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
-          return st;
-        }
-        reconcile_pair(sa, sb, shp, copies);
-        if (sa->layout == I8IE_LAYOUT_NHWC) {
-          st = nhwc_storage({sa->dn, sa->dc, sa->dh, sa->dw}, shp.size() == 4 ? border : 0, zp_o, s8);
-          check(i8ie_mul_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
-                                 sb->border, sb->s8 ? 1 : 0, 0, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, sa->dn, sa->dc, sa->dh,
-                                 sa->dw, s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
-        } else {
-          st = device_storage((size_t)n);
-          check(i8ie_mul_u8(ctx(), (const uint8_t*)sa->device_ptr(), (const uint8_t*)sb->device_ptr(), (uint8_t*)st->dev, (int64_t)n,
-                            s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
-        }
-        // (the operands are released with the closure's copies, as a layer's input is)
+        // the gate as its producer left it: an [n, c, 1, 1] NHWC buffer with its border and re-bias, or plain rows (an
+        // NCHW [n, c, 1, 1] tensor is the same bytes)
+        const bool g_nhwc = sb->layout == I8IE_LAYOUT_NHWC && sb->dn == shp[0] && sb->dc == shp[1] && sb->dh == 1 && sb->dw == 1;
+        if (!g_nhwc) sb->to_nchw();
+        std::shared_ptr<Storage> st = nhwc_storage(shp, border, zp_o, s8);
+        check(i8ie_mul_u8_nhwc(ctx(), (const uint8_t*)sa->device_ptr(), sa->border, sa->s8 ? 1 : 0, (const uint8_t*)sb->device_ptr(),
+                               g_nhwc ? sb->border : 0, g_nhwc && sb->s8 ? 1 : 0, 1, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0,
+                               (int)shp[0], (int)shp[1], (int)shp[2], (int)shp[3], s_a, zp_a, s_b, zp_b, scale, zp_o, relu ? 1 : 0));
         return st;
       }, {a.pend, b.pend});
   return out;

@@ -20,7 +20,7 @@ import pipeline
 
 f32 = np.float32
 
-# the launch constants of csrc/i8ie_mul.hip: threads per block, the grid cap, pixels a lane of the gate kernel walks
+# the launch constants of csrc/i8ie_binary.hip: threads per block, the grid cap, pixels a lane of the gate kernel walks
 THREADS, MAX_BLOCKS, WALK = 256, 256 * 8, 8
 
 

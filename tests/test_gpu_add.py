@@ -1,4 +1,4 @@
-"""The quantized residual Add on the GPU (csrc/i8ie_add.hip).  Every comparison is byte-exact against
+"""The quantized residual Add on the GPU (csrc/i8ie_binary.hip).  Every comparison is byte-exact against
 the numpy restatement of the definition (tests/add_ref.py), never against the code under test: all 65 536 byte pairs through
 the flat entry for a range of quantisation parameters, ragged lengths and aliasing, the bordered / re-biased NHWC entry with
 guard bytes, the FP32 entry as bit patterns, the Python surface, launch counts of a basic block, calibration, and the
@@ -13,6 +13,7 @@ import abi
 import add_ref as ar
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import pointwise_util as pu
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -105,19 +106,6 @@ def test_ragged_lengths_and_aliasing(ctx, n):
             d.free()
 
 
-GUARD = 64
-
-
-def _phys(x_nhwc, border, fill, s8):
-    """[n, h, w, c] u8 -> guarded flat buffer holding [n, h+2b, w+2b, c] with `fill` in the border (re-biased if s8)"""
-    n, h, w, c = x_nhwc.shape
-    p = np.full((n, h + 2 * border, w + 2 * border, c), fill, np.uint8)
-    p[:, border:border + h, border:border + w, :] = x_nhwc
-    if s8:
-        p = p ^ np.uint8(0x80)
-    return np.concatenate([np.full(GUARD, 0x5A, np.uint8), p.ravel(), np.full(GUARD, 0x5A, np.uint8)]), p.shape
-
-
 @pytest.mark.parametrize("borders", [(0, 0, 0), (1, 0, 1), (0, 2, 1), (2, 1, 0)], ids=lambda b: "b%d%d%d" % b)
 @pytest.mark.parametrize("c", [16, 20, 3])
 def test_bordered_nhwc(ctx, c, borders):
@@ -132,25 +120,18 @@ def test_bordered_nhwc(ctx, c, borders):
     for i, (a_s8, b_s8, o_s8) in enumerate(itertools.product((0, 1), repeat=3)):
         relu = (i + c) % 2
         want = ar.add_u8(a, zp_a, s_a, b, zp_b, s_b, s_out, zp_out, bool(relu))
-        fa, _ = _phys(a, ba, zp_a, a_s8)
-        fb, _ = _phys(b, bb, zp_b, b_s8)
-        fo, oshape = _phys(np.zeros_like(a) + np.uint8(0xEE), bo, zp_out, o_s8)  # the border as i8ie_fill_border_u8 leaves it
+        fa, _ = pu.phys(a, ba, zp_a, a_s8)
+        fb, _ = pu.phys(b, bb, zp_b, b_s8)
+        fo, oshape = pu.phys(np.zeros_like(a) + np.uint8(0xEE), bo, zp_out, o_s8)  # the border as i8ie_fill_border_u8 leaves it
         da, db, do = ctx.put(fa), ctx.put(fb), ctx.put(fo)
-        pa, pb, po = (C.c_void_p(d.ptr.value + GUARD) for d in (da, db, do))
+        pa, pb, po = (C.c_void_p(d.ptr.value + pu.GUARD) for d in (da, db, do))
         abi.ck(lib.i8ie_add_u8_nhwc(ctx.h, pa, ba, a_s8, pb, bb, b_s8, po, bo, o_s8, n, c, h, w, float(s_a), zp_a, float(s_b), zp_b,
                                     float(s_out), zp_out, relu))
         ga, gb, go = da.get(), db.get(), do.get()
         for d in (da, db, do):
             d.free()
         assert np.array_equal(ga, fa) and np.array_equal(gb, fb), "operands (and their guards) must be untouched"
-        assert (go[:GUARD] == 0x5A).all() and (go[-GUARD:] == 0x5A).all(), "guard bytes around the result"
-        out = go[GUARD:-GUARD].reshape(oshape)
-        if o_s8:
-            out = out ^ np.uint8(0x80)
-        ring = out.copy()
-        ring[:, bo:bo + h, bo:bo + w, :] = zp_out
-        assert (ring == zp_out).all(), "every border byte of the result holds zp_out"
-        assert np.array_equal(out[:, bo:bo + h, bo:bo + w, :], want), (a_s8, b_s8, o_s8, relu)
+        assert np.array_equal(pu.interior(go, oshape, bo, zp_out, o_s8), want), (a_s8, b_s8, o_s8, relu)  # (guards and ring checked)
 
 
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 1025])

@@ -1,4 +1,4 @@
-"""The quantized broadcast Mul on the GPU (csrc/i8ie_mul.hip).  Every comparison is byte-exact against
+"""The quantized broadcast Mul on the GPU (csrc/i8ie_binary.hip).  Every comparison is byte-exact against
 the numpy restatement of the definition (tests/mul_ref.py), never against the code under test: all 65 536 byte pairs through
 the flat entry and through the gate kernel at each item width for a range of quantisation parameters, the bordered /
 re-biased NHWC entry in both forms with guard bytes, ragged lengths and aliasing, the edges of the gate kernel's tiling, the
@@ -14,6 +14,7 @@ import abi
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import mul_ref as mr
+import pointwise_util as pu
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -61,19 +62,6 @@ def test_exhaustive_byte_pairs(ctx, pairs, name, qp, relu):
     assert got.shape == want.shape == (65536,) and bad.size == 0, (name, bad[:8], a[bad[:8]], b[bad[:8]], got[bad[:8]], want[bad[:8]])
 
 
-GUARD = 64
-
-
-def _phys(x_nhwc, border, fill, s8):
-    """[n, h, w, c] u8 -> guarded flat buffer holding [n, h+2b, w+2b, c] with `fill` in the border (re-biased if s8)"""
-    n, h, w, c = x_nhwc.shape
-    p = np.full((n, h + 2 * border, w + 2 * border, c), fill, np.uint8)
-    p[:, border:border + h, border:border + w, :] = x_nhwc
-    if s8:
-        p = p ^ np.uint8(0x80)
-    return np.concatenate([np.full(GUARD, 0x5A, np.uint8), p.ravel(), np.full(GUARD, 0x5A, np.uint8)]), p.shape
-
-
 def _run_nhwc(ctx, a, b, gate, borders, flags, qp, relu, keep=None):
     """a: [n, h, w, c]; b: the same shape, or with gate [n, c].  Runs i8ie_mul_u8_nhwc on guarded, bordered buffers, checks
     that the operands, every guard and the result's border are untouched, and returns the result's interior [n, h, w, c].
@@ -86,14 +74,14 @@ def _run_nhwc(ctx, a, b, gate, borders, flags, qp, relu, keep=None):
     if keep is not None and key in keep:
         fa, fb, da, db = keep[key]
     else:
-        fa, _ = _phys(a, ba, zp_a, a_s8)
-        fb, _ = _phys(b.reshape(n, 1, 1, c) if gate else b, bb, zp_b, b_s8)
+        fa, _ = pu.phys(a, ba, zp_a, a_s8)
+        fb, _ = pu.phys(b.reshape(n, 1, 1, c) if gate else b, bb, zp_b, b_s8)
         da, db = ctx.put(fa), ctx.put(fb)
         if keep is not None:
             keep[key] = (fa, fb, da, db)
-    fo, oshape = _phys(np.zeros_like(a) + np.uint8(0xEE), bo, zp_out, o_s8)  # the border as i8ie_fill_border_u8 leaves it
+    fo, oshape = pu.phys(np.zeros_like(a) + np.uint8(0xEE), bo, zp_out, o_s8)  # the border as i8ie_fill_border_u8 leaves it
     do = ctx.put(fo)
-    pa, pb, po = (C.c_void_p(d.ptr.value + GUARD) for d in (da, db, do))
+    pa, pb, po = (C.c_void_p(d.ptr.value + pu.GUARD) for d in (da, db, do))
     abi.ck(abi.lib().i8ie_mul_u8_nhwc(ctx.h, pa, ba, a_s8, pb, bb, b_s8, 1 if gate else 0, po, bo, o_s8, n, c, h, w, float(s_a), int(zp_a),
                                       float(s_b), int(zp_b), float(s_out), int(zp_out), 1 if relu else 0))
     go = do.get()
@@ -103,14 +91,7 @@ def _run_nhwc(ctx, a, b, gate, borders, flags, qp, relu, keep=None):
         da.free()
         db.free()
         assert np.array_equal(ga, fa) and np.array_equal(gb, fb), "operands (and their guards) must be untouched"
-    assert (go[:GUARD] == 0x5A).all() and (go[-GUARD:] == 0x5A).all(), "guard bytes around the result"
-    out = go[GUARD:-GUARD].reshape(oshape)
-    if o_s8:
-        out = out ^ np.uint8(0x80)
-    ring = out.copy()
-    ring[:, bo:bo + h, bo:bo + w, :] = zp_out
-    assert (ring == zp_out).all(), "every border byte of the result holds zp_out"
-    return out[:, bo:bo + h, bo:bo + w, :]
+    return pu.interior(go, oshape, bo, int(zp_out), o_s8)  # (checks the guard bytes and the border ring)
 
 
 def _free(keep):
