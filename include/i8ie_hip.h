@@ -545,6 +545,45 @@ int i8ie_avgpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, 
 int i8ie_avgpool2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int kernel_h,
                        int kernel_w, int stride);
 
+/* ---- quantized upsampling by integer factors (no counterpart in the reference: it has no resize op) --------------
+ * NCHW logical shape [n, c, h, w]; integer factors fh, fw, each in 1..8; the result is [n, c, h*fh, w*fw] and carries
+ * the input's (scale, zero_point), as the pools' results do.
+ * I8IE_UPSAMPLE_NEAREST:   out[y, x] = in[y / fh, x / fw] (integer division): a byte copy.
+ * I8IE_UPSAMPLE_BILINEAR:  torch's align_corners=False.  Along one axis of length L with factor f, write the output
+ * index as o = f*i + r and let t = 2*r + 1 - f:
+ *     t >= 0:  i0 = i,      w1 = t
+ *     t <  0:  i0 = i - 1,  w1 = 2*f + t
+ *     i0 <  0: i0 = 0,      w1 = 0
+ *     i1 = min(i0 + 1, L - 1),  w0 = 2*f - w1
+ * With (y0, y1, wy0, wy1) and (x0, x1, wx0, wx1) from that rule and D = 4*fh*fw:
+ *     S = wx0 * (wy0 * q[y0,x0] + wy1 * q[y1,x0]) + wx1 * (wy0 * q[y0,x1] + wy1 * q[y1,x1])
+ *     out = (S + D / 2) / D       integer floor division: round to nearest, ties up (the rule of i8ie_avgpool2d_u8)
+ * The value never leaves the integers, so no fp32 step of the reference applies: S / D is the interpolated value
+ * exactly, and the only rounding is the one above.  S + D / 2 <= 65408 < 2^16 at fh = fw = 8: the blends fit packed
+ * 16-bit lanes, which is the reason for the bound of 8 (compose two calls beyond it).
+ *     out = relu ? max(out, zero_point) : out                relu<u8>, src/functional.cc:15-26, on the result
+ * FP32 (before convert(), and while calibrating): nearest copies bits; bilinear takes l = (float)w1 / (float)(2*f) per
+ * axis, the two row blends a * (1 - lx) + b * lx first, then the column blend of their results with ly; every step in
+ * fp32, one rounding per operation, no contraction.
+ * Null pointers, non-positive sizes, factors outside 1..8, an unknown mode and negative borders are I8IE_ERR_ARG,
+ * raised before any device call.  Stateless and capturable in a graph (csrc/i8ie_upsample.hip).
+ * i8ie_upsample2d_u8: NCHW in and out, any shape. */
+#define I8IE_UPSAMPLE_NEAREST 0
+#define I8IE_UPSAMPLE_BILINEAR 1
+int i8ie_upsample2d_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int n, int c, int h, int w, int fh, int fw,
+                       int mode);
+/* The same on NHWC buffers [n, h+2b, w+2b, c] -> [n, h*fh+2b', w*fw+2b', c], each with its own border and each plain
+ * (x_s8 = 0) or re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80).  Edge pixels are replicated by clamping
+ * indices: the input's border bytes are never read.  Only the interior of `out` is written: its border bytes are the
+ * caller's (i8ie_fill_border_u8).  Any c: 16 / 4 / 1 channels per lane by c % 16, c % 4 and the pointers' alignment.
+ * `out` must not overlap `in`.  h, w: logical input dims. */
+int i8ie_upsample2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev,
+                            int out_border, int out_s8, int n, int c, int h, int w, int fh, int fw, int mode, int relu,
+                            uint8_t zero_point);
+/* FP32, NCHW (the definition above).  NaN and inf propagate as IEEE gives them. */
+int i8ie_upsample2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int fh, int fw,
+                        int mode);
+
 /* ---- quantized channel concatenation (no counterpart in the reference: it has no op that joins two tensors) ----
  * cat(x_0 .. x_{k-1}) along axis 1, 1 <= k <= I8IE_CONCAT_MAX_INPUTS; the same buffer may appear more than once.  The
  * result carries its own (s_out, zp_out).  A byte a of input i, with that tensor's (s_i, zp_i), becomes

@@ -1063,6 +1063,52 @@ Tensor<u8_t> avg_pool_u8(Tensor<u8_t>& in, ssize_t k, ssize_t s, bool global) {
       }, {in.pend});
   return out;
 }
+// ---- upsample (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_upsample2d_u8) -----------------------
+template <typename T>
+std::vector<ssize_t> upsample_shape(const Tensor<T>& in, ssize_t fh, ssize_t fw, int mode) {
+  if (in.shape.size() != 4) throw std::runtime_error("i8ie: upsample expects an NCHW tensor");
+  for (ssize_t d : in.shape)
+    if (d <= 0) throw std::runtime_error("i8ie: upsample: empty tensor");
+  if (fh < 1 || fh > 8 || fw < 1 || fw > 8) throw std::runtime_error("i8ie: upsample: scale factors must be integers in 1..8");
+  if (mode != I8IE_UPSAMPLE_NEAREST && mode != I8IE_UPSAMPLE_BILINEAR) throw std::runtime_error("i8ie: upsample: unknown mode");
+  return {in.shape[0], in.shape[1], in.shape[2] * fh, in.shape[3] * fw};
+}
+Tensor<float> upsample_f32(Tensor<float>& in, ssize_t fh, ssize_t fw, int mode) {
+  Tensor<float> out(upsample_shape(in, fh, fw, mode));
+  check(i8ie_upsample2d_f32(ctx(), in.dptr(), out.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3],
+                            (int)fh, (int)fw, mode));
+  return out;
+}
+Tensor<u8_t> upsample_u8(Tensor<u8_t>& in, ssize_t fh, ssize_t fw, int mode) {
+  Tensor<u8_t> out = pending_u8(upsample_shape(in, fh, fw, mode), in.scale, in.zero_point);  // (as the pools: the input's qparams)
+  if (!in.st && !in.pend) throw std::runtime_error("i8ie: empty tensor");
+  Tensor<u8_t> src = in;
+  const std::vector<ssize_t> ishp = in.shape, oshp = out.shape;
+  const u8_t zp = in.zero_point;
+  const int f_h = (int)fh, f_w = (int)fw;
+  // deferred like avg_pool2d's result: relu(upsample(..)) is one launch, and a consuming conv gets its zero-point border
+  // and, where it reads them, re-biased bytes straight from the upsample kernel
+  out.pend = make_pend(
+      [src, ishp, oshp, zp, f_h, f_w, mode](bool relu, int border, bool s8) mutable {
+        std::shared_ptr<Storage> si = operand_as_it_lies(src);
+        // (a view whose storage is NHWC under other logical dims goes back to the reference's order: the view is defined on it)
+        if (si->layout == I8IE_LAYOUT_NHWC && (si->dn != ishp[0] || si->dc != ishp[1] || si->dh != ishp[2] || si->dw != ishp[3])) si->to_nchw();
+        std::shared_ptr<Storage> st;
+        if (si->layout == I8IE_LAYOUT_NHWC) {
+          st = nhwc_storage(oshp, border, zp, s8);
+          check(i8ie_upsample2d_u8_nhwc(ctx(), (const uint8_t*)si->device_ptr(), si->border, si->s8 ? 1 : 0, (uint8_t*)st->dev, st->border,
+                                        st->s8 ? 1 : 0, (int)ishp[0], (int)ishp[1], (int)ishp[2], (int)ishp[3], f_h, f_w, mode,
+                                        relu ? 1 : 0, zp));
+        } else {  // an NCHW operand (a user-made tensor)
+          st = device_storage((size_t)oshp[0] * oshp[1] * oshp[2] * oshp[3]);
+          check(i8ie_upsample2d_u8(ctx(), (const uint8_t*)si->device_ptr(), (uint8_t*)st->dev, (int)ishp[0], (int)ishp[1], (int)ishp[2],
+                                   (int)ishp[3], f_h, f_w, mode));
+          if (relu) check(i8ie_relu_u8(ctx(), (const uint8_t*)st->dev, (uint8_t*)st->dev, (int64_t)st->bytes, zp));
+        }
+        return st;
+      }, {in.pend});
+  return out;
+}
 // ---- activation / lut (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_activation_table) -------
 using LutBytes = std::array<u8_t, 256>;
 Tensor<float> activation_f32(Tensor<float>& in, int kind, float param) {
@@ -1986,6 +2032,10 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
         py::arg("kernel_size"), py::arg("stride"));
   m.def("global_avg_pool2d", [](Tensor<float>& x) { return avg_pool_f32(x, 0, 1, true); }, py::arg("x"));
   m.def("global_avg_pool2d", [](Tensor<u8_t>& x) { return avg_pool_u8(x, 0, 1, true); }, py::arg("x"));
+  // additive (the reference has no resize op): nearest / bilinear upsampling by integer factors (mode: I8IE_UPSAMPLE_*), exact
+  // integers on u8 tensors, the fp32 sequence of include/i8ie_hip.h on FP32 ones
+  m.def("upsample", &upsample_f32, py::arg("x"), py::arg("factor_h"), py::arg("factor_w"), py::arg("mode"));
+  m.def("upsample", &upsample_u8, py::arg("x"), py::arg("factor_h"), py::arg("factor_w"), py::arg("mode"));
 
   {
     py::class_<Linear> c(m, "Linear");  // src/fully_connected.cc:54-72

@@ -5,17 +5,20 @@ Mirrors reference i8ie/__init__.py:1-32: `tensor`, `argmax`, `relu`,
 Every op forwards to the rebuilt extension `_CXX_i8ie`; tensors are
 device-resident and `.numpy()` copies back to the host.
 """
+import numbers
+
 import _CXX_i8ie as _C
 
 from .layer import Activation, Add, Concat, Conv2d, ConvTranspose2d, Layer, Linear, Mul, activation_kind
 from .module import Module
 from .tensor import Tensor
 
+_UPSAMPLE_MODES = {"nearest": 0, "bilinear": 1}  # I8IE_UPSAMPLE_* of include/i8ie_hip.h
 FullyConnected = Linear  # BASELINE.json's name for the same class (no such symbol in the reference)
 
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
-    "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d",
+    "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -132,6 +135,25 @@ def avg_pool2d(x, kernel_size, stride=None):
 def global_avg_pool2d(x):
     """avg_pool2d over the whole image: [n, c, h, w] -> [n, c, 1, 1].  `.reshape(-1, c)` of the result feeds a Linear layer."""
     return Tensor(_C.global_avg_pool2d(x.data))
+
+
+def upsample(x, scale_factor, mode="nearest"):
+    """Upsampling of an [n, c, h, w] tensor by integer factors: `scale_factor` is an int or (fh, fw), each in 1..8; `mode` is
+    "nearest" or "bilinear" (torch's align_corners=False).  uint8 tensors: exact integers, the blend rounded to nearest, ties
+    up (include/i8ie_hip.h, i8ie_upsample2d_u8); the result carries the input's scale and zero point.  FP32 tensors: a copy
+    (nearest) or the fp32 blend, rows first."""
+    if isinstance(scale_factor, (tuple, list)):
+        if len(scale_factor) != 2:
+            raise TypeError("upsample: scale_factor is an int or a pair (fh, fw)")
+        fh, fw = scale_factor
+    else:
+        fh = fw = scale_factor
+    for f in (fh, fw):
+        if isinstance(f, bool) or not isinstance(f, numbers.Integral):
+            raise TypeError("upsample: scale factors must be integers (there is no fractional resizing)")
+    if mode not in _UPSAMPLE_MODES:
+        raise RuntimeError("upsample: mode must be 'nearest' or 'bilinear'")
+    return Tensor(_C.upsample(x.data, int(fh), int(fw), _UPSAMPLE_MODES[mode]))
 
 
 def synchronize():

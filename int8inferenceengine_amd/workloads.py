@@ -23,7 +23,8 @@ import numpy as np
 #            | ("concat", attr, [tags])   x = getattr(net, attr)([x] + [saved[t] for t in tags]); attr names an i8ie.Concat
 #            | ("act", attr, kind[, param])  x = getattr(net, attr)(x); attr names an i8ie.Activation(kind, param)
 #            | ("mul", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Mul; saved[tag] has x's
-#                                         shape or is its gate [n, c] (the branch of a squeeze-and-excitation block)]
+#                                         shape or is its gate [n, c] (the branch of a squeeze-and-excitation block)
+#            | ("upsample", factor, mode) x = i8ie.upsample(x, factor, mode); factor an int or (fh, fw), mode "nearest" / "bilinear"]
 NETWORKS = {
     # sample/notebooks/AlexNet_cifar10_resize224.ipynb:47-71
     "alexnet": (
@@ -321,9 +322,10 @@ def _unet_tiny():
     return layers, spec, (3, 32, 32)
 
 
-def _unet_cifar():
+def _unet_cifar(bilinear=False):
     """U-Net (Ronneberger et al. 2015) at widths 64 / 128 / 256 / 512 for 32 x 32 input: two padded 3x3 convs per level, 2x2
-    max-pools down, 2x2 stride-2 up-convs, the skips joined by Concat, a 1x1 head to 10 maps."""
+    max-pools down, 2x2 stride-2 up-convs, the skips joined by Concat, a 1x1 head to 10 maps.  bilinear: the usual replacement
+    for the up-convs, a bilinear x2 upsample and a 1x1 conv to the skip's width."""
     layers, spec = {}, []
 
     def double(p, in_c, out_c):
@@ -341,7 +343,11 @@ def _unet_cifar():
     c = widths[-1]
     for i in (3, 2, 1):
         wd = widths[i - 1]
-        layers["up%d" % i] = ("deconv", c, wd, 2, 2, 0, 0)
+        if bilinear:
+            layers["up%d" % i] = ("conv", c, wd, 1, 1, 0)
+            spec.append(("upsample", 2, "bilinear"))
+        else:
+            layers["up%d" % i] = ("deconv", c, wd, 2, 2, 0, 0)
         spec.extend([("layer", "up%d" % i), ("concat", "cat%d" % i, ["s%d" % i])])
         double("u%d" % i, 2 * wd, wd)
         c = wd
@@ -352,6 +358,33 @@ def _unet_cifar():
 
 NETWORKS["unet_tiny"] = _unet_tiny()
 NETWORKS["unet_cifar"] = _unet_cifar()
+
+
+def _upsample_tiny():
+    """Every form of the upsample in one network.  A feature pyramid (Lin et al. 2017): a bottom-up path to 35 channels of
+    4 x 4, then three top-down steps at 35, 20 and 16 channels (1-, 4- and 16-byte items of the kernel), each a nearest x2
+    upsample, a lateral 1x1 conv of the bottom-up map, their Add and a 3x3 pad-1 conv.  Behind it a bilinear x2 of a conv
+    output with its relu directly behind, joined by Concat with a skip; a bilinear (2, 3) upsample in front of a 3x3 pad-1
+    conv; a 1x1 head to 10 maps of 32 x 48."""
+    layers = {"c1": ("conv", 3, 16, 3, 1, 1), "c2": ("conv", 16, 20, 3, 2, 1), "c3": ("conv", 20, 35, 3, 2, 1),
+              "c4": ("conv", 35, 35, 3, 2, 1)}
+    spec = [("layer", "c1"), ("relu",), ("save", "f1"), ("layer", "c2"), ("relu",), ("save", "f2"),
+            ("layer", "c3"), ("relu",), ("save", "f3"), ("layer", "c4"), ("relu",)]
+    for i, c, out_c in ((3, 35, 20), (2, 20, 16), (1, 16, 16)):
+        layers["l%d" % i] = ("conv", c, c, 1, 1, 0)
+        layers["p%d" % i] = ("conv", c, out_c, 3, 1, 1)
+        spec += [("upsample", 2, "nearest"), ("branch", "f%d" % i, [("layer", "l%d" % i)]), ("add", "a%d" % i, "f%d" % i),
+                 ("layer", "p%d" % i), ("relu",)]
+    layers.update({"d1": ("conv", 16, 20, 3, 1, 1), "dec": ("conv", 36, 16, 3, 1, 1), "e1": ("conv", 16, 16, 3, 1, 1),
+                   "head": ("conv", 16, 10, 1, 1, 0)})
+    spec += [("save", "t"), ("pool", 2, 2), ("layer", "d1"), ("upsample", 2, "bilinear"), ("relu",), ("concat", "cat1", ["t"]),
+             ("layer", "dec"), ("relu",), ("pool", 2, 2), ("upsample", (2, 3), "bilinear"), ("layer", "e1"), ("relu",),
+             ("layer", "head")]
+    return layers, spec, (3, 32, 32)
+
+
+NETWORKS["upsample_tiny"] = _upsample_tiny()
+NETWORKS["unet_bilinear_cifar"] = _unet_cifar(bilinear=True)
 
 
 def _walk(spec):
@@ -366,6 +399,11 @@ def _walk(spec):
 def conv_groups(L):
     """groups of a ("conv", ...) layer tuple: its optional 7th element"""
     return L[6] if len(L) > 6 else 1
+
+
+def upsample_factors(factor):
+    """(fh, fw) of an ("upsample", factor, mode) op: factor is an int or a pair"""
+    return tuple(factor) if isinstance(factor, (tuple, list)) else (factor, factor)
 
 
 # MACs per image (SURVEY.md Appendix C): the algorithmic work of the INT8 contractions
@@ -394,6 +432,9 @@ def macs_per_image(name):
             h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
         elif op[0] == "gap":
             h, w = 1, 1
+        elif op[0] == "upsample":
+            fh, fw = upsample_factors(op[1])
+            h, w = h * fh, w * fw
         elif op[0] == "branch":
             # the Linears of a squeeze-and-excitation branch.  (the convs of a branch -- projection shortcuts, fire expands --
             # have never been counted, and the figures of those networks are pinned: they stay as they are)
@@ -482,6 +523,8 @@ def build(name):
                     x = getattr(self, op[1])([x] + [saved[t] for t in op[2]])
                 elif op[0] == "act":
                     x = getattr(self, op[1])(x)
+                elif op[0] == "upsample":
+                    x = i8ie.upsample(x, op[1], op[2])
                 else:
                     x = x.reshape(-1, op[1])
             return x
