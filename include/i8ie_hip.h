@@ -236,6 +236,15 @@ int i8ie_conv2d_f32(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int
 int i8ie_conv2d_f32_grouped(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int w,
                             const float* w_dev, const float* b_dev, int kc, int kh, int kw, int stride,
                             int pad, int groups, float* out_dev);
+/* i8ie_conv2d_f32_grouped with a dilation (not in the reference; torch.nn.Conv2d's dilation=): tap (ky, kx) of the window
+ * of output pixel (oy, ox) reads input pixel (oy*stride - pad + ky*dilation, ox*stride - pad + kx*dilation), i.e.
+ * src/conv2d.cc:63-98 per group with the kernel inflated by zeros to dilation*(k-1)+1 (see i8ie_conv2d_create_dilated).
+ * oh = (h + 2*pad - dilation*(kh-1) - 1)/stride + 1.  dilation >= 1 and the inflated kernel no larger than the padded
+ * input (I8IE_ERR_ARG otherwise, before any device call).  dilation == 1 is i8ie_conv2d_f32_grouped bit for bit: the same
+ * kernel, the dilation only in its gather table.  The path taken before convert() and while calibrating. */
+int i8ie_conv2d_f32_dilated(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int w,
+                            const float* w_dev, const float* b_dev, int kc, int kh, int kw, int stride,
+                            int pad, int groups, int dilation, float* out_dev);
 /* ConvTranspose2d in FP32 (not in the reference; the definition of torch.nn.ConvTranspose2d with groups = 1,
  * dilation = 1, a square kernel): out[n, oc, iy*s - p + ky, ix*s - p + kx] += in[n, ic, iy, ix] * w[ic, oc, ky, kx], + b[oc].
  * w_dev is [c, kc, k, k], out_dev [n, kc, oh, ow] with oh = (h - 1)*stride - 2*pad + k + output_pad.  stride >= 1,
@@ -304,6 +313,16 @@ int i8ie_conv2d_u8s8_grouped(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c,
                              uint8_t zp_in, const int32_t* oc_dev, float s_in, float s_w, float s_out,
                              uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
 
+/* i8ie_conv2d_u8s8_grouped with a dilation (see i8ie_conv2d_create_dilated; not in the reference): qw [kc, (c/groups)*kh*kw]
+ * and oc [kc] are those of the undilated layer (inflating the kernel by zeros changes neither).  out NCHW [n, kc, oh, ow],
+ * oh = (h + 2*pad - dilation*(kh-1) - 1)/stride + 1; acc_dbg_dev NULL or int32 [n, oh*ow, kc].  dilation < 1, or an inflated
+ * kernel larger than the padded input: I8IE_ERR_ARG before any device call.  kh == kw == 1 or dilation == 1 is
+ * i8ie_conv2d_u8s8_grouped itself; otherwise it reads the weights back and packs them for this one call. */
+int i8ie_conv2d_u8s8_dilated(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w,
+                             const int8_t* qw_dev, int kc, int kh, int kw, int stride, int pad, int groups, int dilation,
+                             uint8_t zp_in, const int32_t* oc_dev, float s_in, float s_w, float s_out,
+                             uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
+
 /* ConvTranspose2d in INT8: Conv2d::forward_prop(Tensor<u8>&&), src/conv2d.cc:100-142, of the equivalent problem (see
  * i8ie_conv_transpose2d_create below); the layer itself: not in the reference.  qw_dev is the equivalent matrix
  * [kc, c*k*k], oc_dev [kc] from i8ie_conv_offsets on that matrix (K = c*k*k, src/conv2d.cc:117-124).  out_dev is NCHW
@@ -349,6 +368,31 @@ int i8ie_conv2d_create_grouped(i8ie_ctx* ctx, const int8_t* qw_host, const int8_
 int i8ie_conv2d_create_grouped_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc,
                                            int c, int kh, int kw, int stride, int pad, int groups,
                                            const float* s_w_host, i8ie_layer** out);
+/* Dilated (atrous) Conv2d: torch.nn.Conv2d's dilation=; not in the reference.  Nothing new is defined arithmetically: the
+ * layer IS src/conv2d.cc:100-142 (per group, as above) with the kernel
+ *   W~  of side k~ = dilation*(k-1)+1, W~[.., ky*dilation, kx*dilation] = W[.., ky, kx] and zero elsewhere.
+ * qw_host [kc][(c/groups)*kh*kw] and qb_host are W's own: zeros add nothing to the max-abs, to the weight sums or to the
+ * offset vector, so quantising W and inflating commute.  oh = (h + 2*pad - dilation*(kh-1) - 1)/stride + 1.
+ * dilation is one integer >= 1 (I8IE_ERR_ARG otherwise, checked before any device call); a forward whose inflated kernel is
+ * larger than the padded input returns I8IE_ERR_ARG.  A layer with kh == kw == 1 or dilation == 1 is exactly what
+ * i8ie_conv2d_create_grouped(_per_channel) returns (same route, same kernels, same bytes); it only remembers the number
+ * for i8ie_layer_dilation.  Kernels (W~ is never built, an NHWC forward is one launch): dconv_mfma (csrc/i8ie_dconv.hip,
+ * phase-subsampled input patches resident in LDS) for groups == 1, stride == 1, kh == kw >= 2, c % 16 == 0, 16-byte
+ * aligned buffers, an LDS plan of 8*(k+3)^2*min(c, 64) bytes inside 64 KiB and I8IE_OPT_FORCE_FALLBACK off; every other
+ * layer in the grouped kernels of csrc/i8ie_gconv.hip with the dilation in the tap offsets (gconv_mfma when
+ * (c/groups)*kh*kw >= 32 and the option is off, gconv_direct otherwise).
+ * Such a handle answers the layout queries as follows: i8ie_layer_padding 0 (it needs no border and accepts any: taps are
+ * bounds-checked against zp_in), i8ie_layer_fuses_pool 0, i8ie_layer_accepts_f32_input 0, i8ie_layer_rebiased_io 0 / 0
+ * (pool and re-biased layouts run as passes around the kernel), i8ie_layer_preferred_layout as a grouped handle (NHWC when
+ * kc % 16 == 0 and the option is off). */
+int i8ie_conv2d_create_dilated(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c,
+                               int kh, int kw, int stride, int pad, int groups, int dilation, float s_w,
+                               i8ie_layer** out);
+int i8ie_conv2d_create_dilated_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc,
+                                           int c, int kh, int kw, int stride, int pad, int groups, int dilation,
+                                           const float* s_w_host, i8ie_layer** out);
+/* *dilation = the number the layer was created with: 1 for Linear, for ConvTranspose2d and for every other create entry */
+int i8ie_layer_dilation(const i8ie_layer* layer, int* dilation);
 /* ConvTranspose2d (torch.nn.ConvTranspose2d with a square kernel, groups = 1, dilation = 1; not in the reference).
  * Nothing new is defined arithmetically: the layer IS src/conv2d.cc:100-142 (stride 1, padding 0) applied to
  *   x~  the input with stride - 1 positions inserted between neighbouring pixels, padded by k - 1 - pad on top / left and

@@ -42,9 +42,10 @@ struct F32Args {
   int ctot, Ntot;
 };
 
-__global__ __launch_bounds__(256) void k_table_kernel(int2* tab, int K, int h, int w, int kh, int kw) {
+// dil: the dilation of a Conv2d (1 otherwise): kernel row l / column m read the window's pixel (l * dil, m * dil)
+__global__ __launch_bounds__(256) void k_table_kernel(int2* tab, int K, int h, int w, int kh, int kw, int dil) {
   for (int k = blockIdx.x * 256 + threadIdx.x; k < K; k += gridDim.x * 256) {
-    const int ch = k / (kh * kw), rem = k - ch * (kh * kw), l = rem / kw, m = rem - l * kw;
+    const int ch = k / (kh * kw), rem = k - ch * (kh * kw), l = rem / kw * dil, m = (rem % kw) * dil;
     tab[k] = make_int2((ch * h + l) * w + m, (l << 16) | m);
   }
 }
@@ -159,11 +160,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(F32Args p) {
 }
 
 template <bool CONV>
-int launch_gemm_f32(i8ie_ctx* ctx, F32Args a, int kh, int kw, const char* name, int groups = 1) {
+int launch_gemm_f32(i8ie_ctx* ctx, F32Args a, int kh, int kw, const char* name, int groups = 1, int dil = 1) {
   I8IE_REQUIRE((size_t)a.M * a.K < ((size_t)1 << 62) && a.K < (1 << 30), "f32 gemm: dimensions");
   I8IE_TRY(i8ie_ws_reserve(ctx, (size_t)a.K * sizeof(int2) + 256));
   int2* tab = reinterpret_cast<int2*>(ctx->ws);
-  k_table_kernel<<<(a.K + 255) / 256 < 64 ? (a.K + 255) / 256 : 64, 256, 0, ctx->stream>>>(tab, a.K, a.h, a.wd, kh, kw);
+  k_table_kernel<<<(a.K + 255) / 256 < 64 ? (a.K + 255) / 256 : 64, 256, 0, ctx->stream>>>(tab, a.K, a.h, a.wd, kh, kw, dil);
   I8IE_LAUNCH_CHECK();
   a.ktab = tab;
   const dim3 grid((unsigned)((a.N + FB - 1) / FB), (unsigned)((a.M + FB - 1) / FB), (unsigned)groups);
@@ -234,21 +235,30 @@ int i8ie_conv2d_f32(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, 
 // src/conv2d.cc:63-98 per group; groups: not in the reference.  One launch: the group is the grid's z dimension.
 int i8ie_conv2d_f32_grouped(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, const float* wt,
                             const float* b, int kc, int kh, int kw, int stride, int pad, int groups, float* out) {
-  I8IE_REQUIRE(ctx && in && wt && b && out, "null argument");
+  return i8ie_conv2d_f32_dilated(ctx, in, n, c, h, w, wt, b, kc, kh, kw, stride, pad, groups, 1, out);
+}
+
+// ... and with a dilation (not in the reference): the gather table carries it, the kernel is the same
+int i8ie_conv2d_f32_dilated(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, const float* wt, const float* b, int kc,
+                            int kh, int kw, int stride, int pad, int groups, int dilation, float* out) {
+  I8IE_REQUIRE(dilation >= 1, "dilation must be >= 1");
   I8IE_REQUIRE(groups >= 1 && groups <= 65535, "groups must be in [1, 65535]");
   I8IE_REQUIRE(c > 0 && kc > 0 && c % groups == 0 && kc % groups == 0, "groups must divide the input and the output channels");
   I8IE_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && kc > 0 && kh > 0 && kw > 0, "non-positive dimension");
   I8IE_REQUIRE(stride > 0 && pad >= 0, "bad stride/padding");
-  I8IE_REQUIRE(h - kh + 2 * pad >= 0 && w - kw + 2 * pad >= 0, "kernel larger than padded input");
-  const int oh = (h - kh + 2 * pad) / stride + 1, ow = (w - kw + 2 * pad) / stride + 1;
-  I8IE_REQUIRE((int64_t)n * oh * ow < ((int64_t)1 << 31) && kh < 65536 && kw < 65536, "conv2d_f32: too many output pixels");
+  const int64_t eh = (int64_t)dilation * (kh - 1) + 1, ew = (int64_t)dilation * (kw - 1) + 1;  // the kernel's extent
+  I8IE_REQUIRE(h - eh + 2 * pad >= 0 && w - ew + 2 * pad >= 0,
+               dilation > 1 ? "dilated kernel larger than padded input" : "kernel larger than padded input");
+  const int oh = (int)((h - eh + 2 * pad) / stride) + 1, ow = (int)((w - ew + 2 * pad) / stride) + 1;
+  I8IE_REQUIRE((int64_t)n * oh * ow < ((int64_t)1 << 31) && eh < 65536 && ew < 65536, "conv2d_f32: too many output pixels");
+  I8IE_REQUIRE(ctx && in && wt && b && out, "null argument");  // (behind the argument rules: they need no device)
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   F32Args a{};
   a.in = in; a.w = wt; a.b = b; a.out = out;
   a.M = n * oh * ow; a.N = kc / groups; a.K = (c / groups) * kh * kw;
   a.c = c / groups; a.h = h; a.wd = w; a.oh = oh; a.ow = ow; a.stride = stride; a.pad = pad; a.P = oh * ow;
   a.ctot = c; a.Ntot = kc;
-  return launch_gemm_f32<true>(ctx, a, kh, kw, "conv2d_f32_mfma", groups);
+  return launch_gemm_f32<true>(ctx, a, kh, kw, "conv2d_f32_mfma", groups, dilation);
 }
 
 // ConvTranspose2d in FP32 (not in the reference; torch.nn.functional.conv_transpose2d's definition): wt is [c][kc][k][k]

@@ -8,6 +8,8 @@
 //   gconv_mfma    a block owns (group, 128 output pixels, up to 64 features of the group); each wave multiplies 32 pixels by
 //                 the block's features on v_mfma_i32_16x16x64_i8, both operands read as fragments straight from global
 //                 memory (the weights of a group are a few hundred KiB at most: they stay in L2 / the vector cache)
+//   (both)        a dilation `dil` (Conv2d dilation=) multiplies a tap's pixel offset and nothing else: the
+//                 weights, the tap table and the K order are those of the undilated layer
 //   gconv_direct  no matrix instruction: a lane owns up to 4 features of one (pixel, group) and walks the taps
 //                 (v_dot4_i32_i8 where Cg % 4 == 0); depthwise, channel multipliers, tiny groups, and every grouped layer
 //                 while I8IE_OPT_FORCE_FALLBACK is on
@@ -24,7 +26,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 struct GconvArgs {
   const uint8_t* A;  // [m][H + 2 ib][W + 2 ib][C]
   int H, W, C, ib;
-  int OH, OW, stride, pad, KH, KW;
+  int OH, OW, stride, pad, KH, KW, dil;  // dil: tap (kh, kw) reads the pixel (kh * dil, kw * dil) of the window
   int Cg, Ng, Ngp, Kg, Kgp, kc;
   long long M;          // m * OH * OW output pixels
   const int8_t* Bp;     // [groups][Ngp][Kgp]
@@ -58,6 +60,7 @@ __device__ __forceinline__ Pixel locate(const GconvArgs& p, long long px, int g)
   return q;
 }
 
+// (dy, dx): the tap's offset in pixels from the window origin, the dilation already in it
 __device__ __forceinline__ bool tap_inside(const GconvArgs& p, const Pixel& q, int dy, int dx) {
   const int y = q.y0 + dy + p.ib, x = q.x0 + dx + p.ib;
   return (unsigned)y < (unsigned)(p.H + 2 * p.ib) && (unsigned)x < (unsigned)(p.W + 2 * p.ib);
@@ -111,7 +114,7 @@ __device__ __forceinline__ v4i gather16(const GconvArgs& p, const Pixel& q, int 
   uint32_t d[4];
   if constexpr (G == 16) {
     const int2 t = p.ktab[kpos >> 4];
-    const int dy = t.x >> 16, dx = t.x & 0xffff;
+    const int dy = (t.x >> 16) * p.dil, dx = (t.x & 0xffff) * p.dil;
     v4i v = {(int)zp4, (int)zp4, (int)zp4, (int)zp4};
     if (tap_inside(p, q, dy, dx)) v = *reinterpret_cast<const v4i*>(p.A + q.in_base + (long long)(dy * Wp + dx) * p.C + t.y);
     return v;
@@ -119,7 +122,7 @@ __device__ __forceinline__ v4i gather16(const GconvArgs& p, const Pixel& q, int 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int2 t = p.ktab[(kpos >> 2) + i];
-      const int dy = t.x >> 16, dx = t.x & 0xffff;
+      const int dy = (t.x >> 16) * p.dil, dx = (t.x & 0xffff) * p.dil;
       d[i] = zp4;
       if (tap_inside(p, q, dy, dx)) d[i] = *reinterpret_cast<const uint32_t*>(p.A + q.in_base + (long long)(dy * Wp + dx) * p.C + t.y);
     }
@@ -130,7 +133,7 @@ __device__ __forceinline__ v4i gather16(const GconvArgs& p, const Pixel& q, int 
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
         const int2 t = p.ktab[kpos + 4 * i + b];
-        const int dy = t.x >> 16, dx = t.x & 0xffff;
+        const int dy = (t.x >> 16) * p.dil, dx = (t.x & 0xffff) * p.dil;
         uint32_t v = (uint32_t)p.zp_in;
         if (tap_inside(p, q, dy, dx)) v = p.A[q.in_base + (long long)(dy * Wp + dx) * p.C + t.y];
         d[i] |= v << (8 * b);
@@ -208,8 +211,8 @@ __global__ __launch_bounds__(256) void gconv_direct_kernel(GconvArgs p, int grou
     int c[4] = {0, 0, 0, 0};
     for (int dy = 0; dy < p.KH; ++dy)
       for (int dx = 0; dx < p.KW; ++dx) {
-        const bool in = tap_inside(p, q, dy, dx);
-        const uint8_t* a = p.A + q.in_base + (long long)(dy * Wp + dx) * p.C;
+        const bool in = tap_inside(p, q, dy * p.dil, dx * p.dil);
+        const uint8_t* a = p.A + q.in_base + (long long)(dy * Wp + dx) * p.dil * p.C;
         const int8_t* wt = w + (dy * p.KW + dx) * p.Cg;
         if constexpr (DOT4) {
           for (int cg = 0; cg < p.Cg; cg += 4) {
@@ -258,9 +261,10 @@ bool i8ie_gconv_mfma_takes(const i8ie_ctx* ctx, const I8ieGconvCall& c) {
 int i8ie_gconv_launch(i8ie_ctx* ctx, const I8ieGconvCall& c) {
   I8IE_REQUIRE(c.groups >= 1 && c.groups <= 65535, "grouped conv: at most 65535 groups");
   I8IE_REQUIRE(c.KH < 65536 && c.KW < 65536, "grouped conv: kernel size");
+  I8IE_REQUIRE(c.dil >= 1 && (long long)c.dil * (c.KH > c.KW ? c.KH : c.KW) < 65536, "grouped conv: dilation");
   GconvArgs a{};
   a.A = c.A; a.H = c.H; a.W = c.W; a.C = c.C; a.ib = c.ib;
-  a.OH = c.OH; a.OW = c.OW; a.stride = c.stride; a.pad = c.pad; a.KH = c.KH; a.KW = c.KW;
+  a.OH = c.OH; a.OW = c.OW; a.stride = c.stride; a.pad = c.pad; a.KH = c.KH; a.KW = c.KW; a.dil = c.dil;
   a.Cg = c.Cg; a.Ng = c.Ng; a.Ngp = c.Ngp; a.Kg = c.Cg * c.KH * c.KW; a.Kgp = c.Kgp; a.kc = c.groups * c.Ng;
   a.M = (long long)c.m * c.OH * c.OW;
   a.Bp = c.Bp; a.ktab = reinterpret_cast<const int2*>(c.ktab); a.ocp = c.ocp; a.msv = c.msv; a.sbv = c.sbv;

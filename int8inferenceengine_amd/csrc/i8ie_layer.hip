@@ -11,7 +11,10 @@
 //      once into a physically padded, 4-pixel-grouped NHWC image; then path A's kernel
 //   F  anything else: materialised im2col + v1 GEMM (i8ie_gemm.hip)
 //   G  groups > 1 (i8ie_conv2d_create_grouped; not in the reference): one reference convolution per group, in the
-//      grouped kernels of i8ie_gconv.hip over NHWC activations
+//      grouped kernels of i8ie_gconv.hip over NHWC activations; and every layer with a dilation > 1
+//      (i8ie_conv2d_create_dilated; not in the reference), dense ones as groups = 1
+//   D  inside G: a dense dilated layer at stride 1 with channels % 16 == 0 runs in dconv_mfma (i8ie_dconv.hip), its input
+//      patches phase-subsampled into LDS; what that kernel declines stays in the grouped kernels
 //   T  ConvTranspose2d (i8ie_conv_transpose2d_create; not in the reference): the reference convolution of the equivalent
 //      zero-inserted problem, computed phase by phase in the kernels of i8ie_deconv.hip over NHWC activations
 // Activations cross the ABI as NCHW (the reference's layout) or, on request, as
@@ -28,6 +31,7 @@
 #include "i8ie_requant.h"
 #include "i8ie_gconv.h"
 #include "i8ie_deconv.h"
+#include "i8ie_dconv.h"
 
 namespace {
 
@@ -42,14 +46,18 @@ struct ConvGeom {
   int c, h, w, kc, kh, kw, stride, pad, oh, ow, K, Kpad;
 };
 
-int conv_geom(int c, int h, int w, int kc, int kh, int kw, int stride, int pad, ConvGeom* g) {
+// dil: the dilation: the kernel spans dil (k - 1) + 1 pixels; 1 = the reference's geometry
+int conv_geom(int c, int h, int w, int kc, int kh, int kw, int stride, int pad, ConvGeom* g, int dil = 1) {
   I8IE_REQUIRE(c > 0 && h > 0 && w > 0 && kc > 0 && kh > 0 && kw > 0, "non-positive dimension");
   I8IE_REQUIRE(stride > 0, "stride must be positive");  // include/conv2d.h:12-14
   I8IE_REQUIRE(pad >= 0, "negative padding");
-  I8IE_REQUIRE(h - kh + 2 * pad >= 0 && w - kw + 2 * pad >= 0, "kernel larger than padded input");
+  I8IE_REQUIRE(dil >= 1, "dilation must be >= 1");
+  const long long eh = (long long)dil * (kh - 1) + 1, ew = (long long)dil * (kw - 1) + 1;  // the kernel's extent
+  I8IE_REQUIRE(h - eh + 2 * pad >= 0 && w - ew + 2 * pad >= 0,
+               dil > 1 ? "dilated kernel larger than padded input" : "kernel larger than padded input");
   g->c = c; g->h = h; g->w = w; g->kc = kc; g->kh = kh; g->kw = kw; g->stride = stride; g->pad = pad;
-  g->oh = (h - kh + 2 * pad) / stride + 1;  // src/conv2d.cc:108-109
-  g->ow = (w - kw + 2 * pad) / stride + 1;
+  g->oh = (int)((h - eh + 2 * pad) / stride) + 1;  // src/conv2d.cc:108-109
+  g->ow = (int)((w - ew + 2 * pad) / stride) + 1;
   g->K = c * kh * kw;
   g->Kpad = round_up(g->K, 128);
   return I8IE_OK;
@@ -147,6 +155,8 @@ struct i8ie_layer {
   int8_t* Bperm = nullptr;  // Linear fed by an NHWC-flattened activation: Bpack with K reordered (h, w, c)
   int perm_c = 0, perm_hw = 0;
   int path = PATH_F;        // conv: PATH_A / PATH_B / PATH_F / PATH_G / PATH_T
+  int dil = 1, dil_arg = 1; // conv: the effective dilation (1 when the kernel is 1 x 1) and the number the layer was created with;
+                            // dil > 1 (i8ie_conv2d_create_dilated) is PATH_G as well, with groups >= 1
   int groups = 1;           // conv, groups > 1 (PATH_G): K above is the reduction length INSIDE a group, (c / groups) * kh * kw,
   int Ngp = 0, Kgp = 0;     // and the weights live in `wc` as [groups][Ngp][Kgp], K ordered (kh, kw, cg) (i8ie_gconv.h)
   int8_t* Bg = nullptr;
@@ -311,7 +321,8 @@ int i8ie_conv2d_u8s8(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int 
 }
 
 static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const int8_t* qb_host, int n, int K, int c,
-                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups = 1, int opad = -1);
+                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups = 1, int opad = -1,
+                        int dil = 1);
 
 // the stateless grouped / transposed calls: the temporary handle `L` runs one NCHW forward with the caller's offset vector (it
 // carries the bias term) instead of the handle's own, and is destroyed
@@ -385,14 +396,14 @@ int i8ie_maxpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in, int in_border, uint
 
 // ---- layer handles ----------------------------------------------------------------------------
 static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const int8_t* qb_host, int n, int K, int c,
-                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups, int opad) {
+                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups, int opad, int dil) {
   I8IE_REQUIRE(ctx && qw_host && qb_host && out, "null argument");
   I8IE_REQUIRE(n > 0 && K > 0, "non-positive dimension");
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   i8ie_layer* L = new (std::nothrow) i8ie_layer();
   if (!L) return I8IE_ERR_OOM;
   L->ctx = ctx; L->conv = conv; L->n = n; L->K = K; L->c = c; L->kh = kh; L->kw = kw;
-  L->stride = stride; L->pad = pad; L->s_w = s_w;
+  L->stride = stride; L->pad = pad; L->s_w = s_w; L->dil = L->dil_arg = dil;
   L->Kpad = round_up(K, 128);
   L->Npad = round_up(n, 128);
   // MFMA-order weight panel for the implicit-GEMM conv paths, built on the host once
@@ -408,8 +419,9 @@ static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const i
     L->Kpp = i8ie_deconv_kpitch(c, kh, stride);
     i8ie_deconv_pack(qw_host, n, c, kh, stride, packt, tph);
     i8ie_deconv_ktab(c, kh, stride, ttab);
-  } else if (conv && groups > 1) {
-    // grouped: qw_host is [n][Cg * kh * kw]; group g's Ng rows go to panel g in (kh, kw, cg) order
+  } else if (conv && (groups > 1 || dil > 1)) {
+    // grouped: qw_host is [n][Cg * kh * kw]; group g's Ng rows go to panel g in (kh, kw, cg) order.  A dilated layer
+    // (dil > 1) takes this route with any groups >= 1: its weights are packed as they are, the dilation is in the gather
     const int Cg = c / groups, Ng = n / groups;
     L->path = PATH_G;
     L->groups = groups;
@@ -612,6 +624,68 @@ int i8ie_layer_groups(const i8ie_layer* L, int* groups) {
   return I8IE_OK;
 }
 
+// dilation: not in the reference (src/conv2d.cc:100-142 per group with the kernel inflated by zeros).
+// Argument checks come before any device call.  A 1 x 1 kernel or dilation 1 is exactly the undilated layer (same route, same
+// kernels): it only remembers the number.  Anything else is route G with the dilation in the gather, for every groups >= 1.
+static int check_dilation(int dilation) {
+  I8IE_REQUIRE(dilation >= 1, "dilation must be >= 1");
+  return I8IE_OK;
+}
+static inline bool dilation_is_identity(int kh, int kw, int dilation) { return dilation == 1 || (kh == 1 && kw == 1); }
+
+int i8ie_conv2d_create_dilated(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh, int kw,
+                               int stride, int pad, int groups, int dilation, float s_w, i8ie_layer** out) {
+  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
+  I8IE_TRY(check_dilation(dilation));
+  if (dilation_is_identity(kh, kw, dilation)) {
+    I8IE_TRY(i8ie_conv2d_create_grouped(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, groups, s_w, out));
+    (*out)->dil_arg = dilation;
+    return I8IE_OK;
+  }
+  return layer_create(ctx, true, qw_host, qb_host, kc, (c / groups) * kh * kw, c, kh, kw, stride, pad, s_w, out, groups, -1, dilation);
+}
+
+int i8ie_conv2d_create_dilated_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh,
+                                           int kw, int stride, int pad, int groups, int dilation, const float* s_w_host,
+                                           i8ie_layer** out) {
+  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
+  I8IE_TRY(check_dilation(dilation));
+  I8IE_REQUIRE(out != nullptr, "bad argument");
+  I8IE_TRY(check_scales(s_w_host, kc));
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_conv2d_create_dilated(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, groups, dilation, 1.0f, &L));
+  return layer_make_per_channel(L, s_w_host, out);
+}
+
+int i8ie_layer_dilation(const i8ie_layer* L, int* dilation) {
+  I8IE_REQUIRE(L && dilation, "null argument");
+  *dilation = L->dil_arg;
+  return I8IE_OK;
+}
+
+// the stateless form, as i8ie_conv2d_u8s8_grouped: a layer that is not an identity case reads the weights back and packs them
+// for this one call
+int i8ie_conv2d_u8s8_dilated(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int kh,
+                             int kw, int stride, int pad, int groups, int dilation, uint8_t zp_in, const int32_t* oc, float s_in,
+                             float s_w, float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
+  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
+  I8IE_TRY(check_dilation(dilation));
+  if (dilation_is_identity(kh, kw, dilation))
+    return i8ie_conv2d_u8s8_grouped(ctx, in, n, c, h, w, qw, kc, kh, kw, stride, pad, groups, zp_in, oc, s_in, s_w, s_out, zp_out,
+                                    out, acc);
+  ConvGeom cg;
+  I8IE_TRY(conv_geom(c, h, w, kc, kh, kw, stride, pad, &cg, dilation));
+  I8IE_REQUIRE(ctx && in && qw && oc && out, "null argument");
+  I8IE_REQUIRE(n > 0, "non-positive batch");
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  const int Kg = (c / groups) * kh * kw;
+  std::vector<int8_t> qw_host((size_t)kc * Kg), qb_host((size_t)kc, 0);
+  I8IE_TRY(i8ie_memcpy_d2h(ctx, qw_host.data(), qw, qw_host.size()));
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(layer_create(ctx, true, qw_host.data(), qb_host.data(), kc, Kg, c, kh, kw, stride, pad, s_w, &L, groups, -1, dilation));
+  return run_once(L, in, n, h, w, zp_in, oc, s_in, s_out, zp_out, out, acc);
+}
+
 // ConvTranspose2d: not in the reference (src/conv2d.cc:100-142 on the equivalent problem, include/i8ie_hip.h).  Argument
 // checks (i8ie_deconv_check_args) come before any device call.
 int i8ie_conv_transpose2d_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int k, int stride,
@@ -672,7 +746,9 @@ int i8ie_layer_preferred_layout(const i8ie_layer* L, int* layout) {
 
 int i8ie_layer_padding(const i8ie_layer* L, int* pad) {
   I8IE_REQUIRE(L && pad, "null argument");
-  *pad = (L->conv && L->path != PATH_T) ? L->pad : 0;  // (a transposed layer reads no border)
+  // (a transposed layer reads no border; a dilated one needs none and accepts any: its taps are bounds-checked, and a
+  // border of `pad` pixels around a small map would multiply its bytes)
+  *pad = (L->conv && L->path != PATH_T && L->dil == 1) ? L->pad : 0;
   return I8IE_OK;
 }
 
@@ -792,11 +868,26 @@ static int forward_grouped(i8ie_layer* L, const ConvGeom& cg, const ConvRequest&
   I8IE_TRY(stage_io(L->ctx, cg, q, &s));
   I8ieGconvCall g{};
   g.A = s.in; g.m = q.m; g.H = cg.h; g.W = cg.w; g.C = cg.c; g.ib = s.ib;
-  g.OH = cg.oh; g.OW = cg.ow; g.stride = cg.stride; g.pad = cg.pad; g.KH = cg.kh; g.KW = cg.kw;
+  g.OH = cg.oh; g.OW = cg.ow; g.stride = cg.stride; g.pad = cg.pad; g.KH = cg.kh; g.KW = cg.kw; g.dil = L->dil;
   g.groups = L->groups; g.Cg = cg.c / L->groups; g.Ng = L->n / L->groups; g.Ngp = L->Ngp; g.Kgp = L->Kgp;
   g.Bp = L->Bg; g.ktab = L->gtab; g.ocp = L->ocp; g.msv = msv_arg(L); g.sbv = sbv_arg(L);
   g.s_in = q.s_in; g.s_w = sw_arg(L); g.s_out = L->s_out; g.zp_in = q.zp_in; g.zp_out = L->zp_out; g.relu = q.relu;
   g.out = s.out; g.ob = s.ob; g.acc = q.acc;
+  // route D: a dense dilated layer at stride 1 goes to the kernel of i8ie_dconv.hip (input patches resident in LDS) when that
+  // takes it -- C % 16 == 0, K >= 32, aligned buffers, an LDS plan that fits, the force-fallback option off; it reads route G's
+  // panel (groups = 1: [Ngp][Kgp], K ordered (kh, kw, c)) as it is.  Everything it declines stays in the grouped kernels.
+  if (L->dil > 1 && L->groups == 1 && cg.stride == 1 && cg.kh == cg.kw) {
+    I8ieDconvCall d{};
+    d.A = s.in; d.m = q.m; d.H = cg.h; d.W = cg.w; d.C = cg.c; d.ib = s.ib;
+    d.OH = cg.oh; d.OW = cg.ow; d.pad = cg.pad; d.k = cg.kh; d.dil = L->dil;
+    d.N = L->n; d.Ngp = L->Ngp; d.Kgp = L->Kgp; d.Bp = L->Bg; d.ocp = L->ocp; d.msv = msv_arg(L); d.sbv = sbv_arg(L);
+    d.s_in = q.s_in; d.s_w = sw_arg(L); d.s_out = L->s_out; d.zp_in = q.zp_in; d.zp_out = L->zp_out; d.relu = q.relu;
+    d.out = s.out; d.ob = s.ob; d.acc = q.acc;
+    if (i8ie_dconv_takes(L->ctx, d)) {
+      I8IE_TRY(i8ie_dconv_launch(L->ctx, d));
+      return unstage(L->ctx, s, q, cg.kc, cg.oh, cg.ow);
+    }
+  }
   I8IE_TRY(i8ie_gconv_launch(L->ctx, g));
   return unstage(L->ctx, s, q, cg.kc, cg.oh, cg.ow);
 }
@@ -1104,7 +1195,7 @@ static int layer_forward(i8ie_layer* L, const ConvRequest& q) {
   if (L->path == PATH_T)
     I8IE_TRY(deconv_geom(L->c, q.h, q.w, L->n, L->kh, L->stride, L->pad, L->opad, &cg));
   else
-    I8IE_TRY(conv_geom(L->c, q.h, q.w, L->n, L->kh, L->kw, L->stride, L->pad, &cg));
+    I8IE_TRY(conv_geom(L->c, q.h, q.w, L->n, L->kh, L->kw, L->stride, L->pad, &cg, L->dil));
   if (q.pool()) I8IE_REQUIRE(q.pool_k <= cg.oh && q.pool_k <= cg.ow, "max-pool window larger than the convolution's output");
   return forward_conv(L, cg, q);
 }
@@ -1143,7 +1234,7 @@ int i8ie_layer_forward_dequant(i8ie_layer* L, const uint8_t* in, int in_layout, 
 // (NHWC in with the layer's padding as its border, NHWC out without one, no buffers yet: null pointers count as aligned)
 static bool query_plan(const i8ie_layer* L, int m, int h, int w, int pool_k, int pool_s, int in_layout, int out_layout, ConvPlan* p,
                        ConvGeom* cg) {
-  if (conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, cg) != I8IE_OK) return false;
+  if (conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, cg, L->dil) != I8IE_OK) return false;
   ConvRequest q = make_request(nullptr, in_layout, cg->pad, m, h, w, 0.0f, 0, 0, nullptr, out_layout, 0, nullptr);
   q.pool_k = pool_k; q.pool_s = pool_s;
   if (q.pool() && (pool_s < 1 || pool_k > cg->oh || pool_k > cg->ow)) return false;
@@ -1204,7 +1295,7 @@ int i8ie_layer_forward_f32_input_pool(i8ie_layer* L, const float* in, int m, int
   I8IE_TRY(ensure_offsets(L, q_scale, q_zp));
   I8IE_TRY(ensure_multipliers(L, q_scale));
   ConvGeom cg;
-  I8IE_TRY(conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg));
+  I8IE_TRY(conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg, L->dil));
   ConvRequest q = make_request(nullptr, I8IE_LAYOUT_NCHW, 0, m, h, w, q_scale, q_zp, relu, out, out_layout, out_border, acc);
   q.x = in; q.pool_k = pool_k; q.pool_s = pool_s;
   if (q.pool()) I8IE_REQUIRE(pool_s > 0 && pool_k <= cg.oh && pool_k <= cg.ow, "max-pool window larger than the convolution's output");

@@ -1665,9 +1665,12 @@ class Linear : public BaseLayer {
 class Conv2d : public BaseLayer {
  public:
   // groups: not in the reference (src/conv2d.cc:100-142 per group); the weight is [out, in / groups, k, k]
-  Conv2d(ssize_t in_channel, ssize_t out_channel, ssize_t kernel_size, ssize_t stride, ssize_t padding, ssize_t groups = 1)
+  // dilation: not in the reference either (torch.nn.Conv2d's dilation=, one integer)
+  Conv2d(ssize_t in_channel, ssize_t out_channel, ssize_t kernel_size, ssize_t stride, ssize_t padding, ssize_t groups = 1,
+         ssize_t dilation = 1)
       : BaseLayer({out_channel, checked_cg(in_channel, out_channel, groups), kernel_size, kernel_size}, out_channel),
-        stride_(stride), padding_(padding), groups_(groups), in_channels_(in_channel) {
+        stride_(stride), padding_(padding), groups_(groups), dilation_(dilation), in_channels_(in_channel) {
+    if (dilation < 1) throw std::runtime_error("i8ie: Conv2d: dilation must be >= 1");
     if (stride == 0) throw std::runtime_error("i8ie: Conv2d: stride must not be 0");  // include/conv2d.h:12-14
     if (stride < 0 || padding < 0) throw std::runtime_error("i8ie: Conv2d: negative stride/padding");
   }
@@ -1680,9 +1683,10 @@ class Conv2d : public BaseLayer {
   std::vector<ssize_t> out_shape(const std::vector<ssize_t>& s) const {
     if (s.size() != 4) throw std::runtime_error("i8ie: Conv2d expects an NCHW tensor");
     if (s[1] != in_channels()) throw std::runtime_error("i8ie: Conv2d: input channels do not match the weight");
-    const ssize_t kh = wshape_[2], kw = wshape_[3];
+    const ssize_t kh = dilation_ * (wshape_[2] - 1) + 1, kw = dilation_ * (wshape_[3] - 1) + 1;  // the kernel's extent
     if (s[2] - kh + 2 * padding_ < 0 || s[3] - kw + 2 * padding_ < 0)
-      throw std::runtime_error("i8ie: Conv2d: kernel larger than the padded input");
+      throw std::runtime_error(dilation_ > 1 ? "i8ie: Conv2d: dilated kernel larger than the padded input"
+                                             : "i8ie: Conv2d: kernel larger than the padded input");
     return {s[0], wshape_[0], (s[2] - kh + 2 * padding_) / stride_ + 1, (s[3] - kw + 2 * padding_) / stride_ + 1};
   }
   Tensor<float> forward_f32(Tensor<float>& in) {  // src/conv2d.cc:63-98
@@ -1690,9 +1694,9 @@ class Conv2d : public BaseLayer {
     check_shapes();
     Tensor<float> out(out_shape(in.shape));
     upload_fp32();
-    check(i8ie_conv2d_f32_grouped(ctx(), in.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3],
+    check(i8ie_conv2d_f32_dilated(ctx(), in.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3],
                                   w_dev_, b_dev_, (int)wshape_[0], (int)wshape_[2], (int)wshape_[3], (int)stride_,
-                                  (int)padding_, (int)groups_, out.dptr()));
+                                  (int)padding_, (int)groups_, (int)dilation_, out.dptr()));
     maybe_sample(out);
     return out;
   }
@@ -1714,20 +1718,21 @@ class Conv2d : public BaseLayer {
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
     if (per_channel_)
-      check(i8ie_conv2d_create_grouped_per_channel(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+      check(i8ie_conv2d_create_dilated_per_channel(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
                                                    reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)in_channels(),
                                                    (int)wshape_[2], (int)wshape_[3], (int)stride_, (int)padding_,
-                                                   (int)groups_, w_scales_.data(), &l));
+                                                   (int)groups_, (int)dilation_, w_scales_.data(), &l));
     else
-      check(i8ie_conv2d_create_grouped(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+      check(i8ie_conv2d_create_dilated(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
                                        reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)in_channels(),
                                        (int)wshape_[2], (int)wshape_[3], (int)stride_, (int)padding_, (int)groups_,
-                                       w_scale_, &l));
+                                       (int)dilation_, w_scale_, &l));
     return l;
   }
 
  public:
   ssize_t groups() const { return groups_; }
+  ssize_t dilation() const { return dilation_; }
 
  private:
   static ssize_t checked_cg(ssize_t in_channel, ssize_t out_channel, ssize_t groups) {
@@ -1740,6 +1745,7 @@ class Conv2d : public BaseLayer {
   ssize_t stride_ = 1;
   ssize_t padding_ = 0;
   ssize_t groups_ = 1;
+  ssize_t dilation_ = 1;
   ssize_t in_channels_ = 0;  // as constructed from sizes (0: constructed from arrays)
 };
 
@@ -2050,10 +2056,11 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
     c.def(py::init<py::array_t<float, py::array::c_style | py::array::forcecast>,
                    py::array_t<float, py::array::c_style | py::array::forcecast>>())
         .def(py::init([](Tensor<float>& w, Tensor<float>& b) { return new Conv2d(w.numpy(), b.numpy()); }))
-        .def(py::init<ssize_t, ssize_t, ssize_t, ssize_t, ssize_t, ssize_t>(), py::arg("in_channels"),
+        .def(py::init<ssize_t, ssize_t, ssize_t, ssize_t, ssize_t, ssize_t, ssize_t>(), py::arg("in_channels"),
              py::arg("out_channels"), py::arg("kernel_size"), py::arg("stride") = 1, py::arg("padding") = 0,
-             py::arg("groups") = 1)
-        .def("groups", &Conv2d::groups);
+             py::arg("groups") = 1, py::arg("dilation") = 1)
+        .def("groups", &Conv2d::groups)
+        .def("dilation", &Conv2d::dilation);
     bind_layer_common(c);
   }
 

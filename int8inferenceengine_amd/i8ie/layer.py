@@ -53,6 +53,10 @@ class Layer:
         """Groups of a Conv2d (1 for a dense Conv2d and for Linear)."""
         return self.layer.groups() if hasattr(self.layer, "groups") else 1
 
+    def dilation(self):
+        """Dilation of a Conv2d as it was constructed (1 for every other layer)."""
+        return self.layer.dilation() if hasattr(self.layer, "dilation") else 1
+
     def forward_debug(self, x):
         """INT8 forward that also returns the INT32 pre-requant accumulators (numpy)."""
         out, acc = self.layer.forward_debug(x.data)
@@ -65,10 +69,13 @@ class Linear(Layer):
 
 
 class Conv2d(Layer):
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, groups=1):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, groups=1, dilation=1):
         """groups (additive, not in the reference): output features [g*out/groups, (g+1)*out/groups) see input channels
-        [g*in/groups, (g+1)*in/groups); the weight is [out, in/groups, k, k].  groups == in_channels is depthwise."""
-        self.layer = _C.Conv2d(in_channels, out_channels, kernel_size, stride, padding, groups)
+        [g*in/groups, (g+1)*in/groups); the weight is [out, in/groups, k, k].  groups == in_channels is depthwise.
+        dilation (additive as well; one integer >= 1, torch.nn.Conv2d's): tap (ky, kx) reads the input dilation * ky rows and
+        dilation * kx columns from the window's origin, so the output is (h + 2 * padding - dilation * (k - 1) - 1) // stride
+        + 1 high.  The weight keeps its shape; save / load are unchanged (dilation is a constructor argument like stride)."""
+        self.layer = _C.Conv2d(in_channels, out_channels, kernel_size, stride, padding, groups, dilation)
 
 
 class ConvTranspose2d(Layer):

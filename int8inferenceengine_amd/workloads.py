@@ -12,7 +12,7 @@ product path (SpecNet, through i8ie) and the CPU oracle in tests/bench.
 import numpy as np
 
 # name -> (layers, spec, input_shape CHW)
-#   layers: {attr: ("conv", in_c, out_c, k, stride, pad[, groups]) | ("fc", in_f, out_f)
+#   layers: {attr: ("conv", in_c, out_c, k, stride, pad[, groups[, dilation]]) | ("fc", in_f, out_f)
 #                  | ("deconv", in_c, out_c, k, stride, pad, output_pad)   i8ie.ConvTranspose2d, weight [in_c, out_c, k, k]}
 #   spec  : [("layer", attr) | ("relu",) | ("pool", k, s) | ("flatten", features)
 #            | ("save", tag)              remember the current tensor under `tag`
@@ -387,6 +387,80 @@ NETWORKS["upsample_tiny"] = _upsample_tiny()
 NETWORKS["unet_bilinear_cifar"] = _unet_cifar(bilinear=True)
 
 
+# Networks added after tests began to pin set(NETWORKS): a second registry with the same entries.  network(name) looks in both;
+# everything below goes through it.
+EXTRA_NETWORKS = {}
+
+
+def _aspp_tiny():
+    """An atrous spatial pyramid (Chen et al. 2017) in small: what Conv2d's dilation exists for.  Two stride-2 3x3 convs down
+    to 32 channels of 8 x 8, a dilated 3x3 conv (rate 2), then five branches over that map -- 1x1; 3x3 at rate 2; 3x3 at rate
+    3 to 20 channels; a depthwise 3x3 at rate 2 with its 1x1; the image pool (gap, 1x1, relu, nearest x8) -- joined by Concat
+    at 84 channels, a 1x1 projection, the residual Add with the pyramid's input, a 1x1 head to 10 and a bilinear x4 to 32 x 32."""
+    layers = {"stem": ("conv", 3, 16, 3, 2, 1), "down": ("conv", 16, 32, 3, 2, 1), "atr": ("conv", 32, 32, 3, 1, 2, 1, 2),
+              "a1": ("conv", 32, 16, 1, 1, 0), "a2": ("conv", 32, 16, 3, 1, 2, 1, 2), "a3": ("conv", 32, 20, 3, 1, 3, 1, 3),
+              "a4d": ("conv", 32, 32, 3, 1, 2, 32, 2), "a4p": ("conv", 32, 16, 1, 1, 0), "a5": ("conv", 32, 16, 1, 1, 0),
+              "proj": ("conv", 84, 32, 1, 1, 0), "head": ("conv", 32, 10, 1, 1, 0)}
+    spec = [("layer", "stem"), ("relu",), ("layer", "down"), ("relu",), ("layer", "atr"), ("relu",),
+            ("save", "x"), ("save", "b2"), ("save", "b3"), ("save", "b4"), ("save", "b5"), ("layer", "a1"),
+            ("branch", "b2", [("layer", "a2")]), ("branch", "b3", [("layer", "a3")]),
+            ("branch", "b4", [("layer", "a4d"), ("layer", "a4p")]),
+            ("branch", "b5", [("gap",), ("layer", "a5"), ("relu",), ("upsample", 8, "nearest")]),
+            ("concat", "cat", ["b2", "b3", "b4", "b5"]), ("layer", "proj"), ("add", "res", "x"), ("layer", "head"),
+            ("upsample", 4, "bilinear")]
+    return layers, spec, (3, 32, 32)
+
+
+def _deeplabv3_cifar():
+    """DeepLabV3 (Chen et al. 2017) for 32 x 32 input: resnet18_cifar's stem and stages 1-3 (256 channels of 8 x 8), stage 4
+    kept at stride 1 with its 3x3 convs at rate 2 (512 channels, output stride 4), the pyramid -- a 1x1 branch, three 3x3
+    branches at rates 2 / 4 / 6 (padding = rate) and the image-pool branch, 128 channels each -- joined by Concat at 640, a 1x1
+    to 128, a 1x1 head to 10 and a bilinear x4."""
+    rl, rs, shape = _resnet18_cifar()
+    layers = {a: L for a, L in rl.items() if not a.startswith("s4") and a != "fc"}
+    cut = rs.index(("save", "s4b1"))
+    spec = list(rs[:cut])
+    in_c = 256
+    for block in (1, 2):
+        p = "s4b%d" % block
+        layers[p + "c1"] = ("conv", in_c, 512, 3, 1, 2, 1, 2)
+        layers[p + "c2"] = ("conv", 512, 512, 3, 1, 2, 1, 2)
+        spec += [("save", p), ("layer", p + "c1"), ("relu",), ("layer", p + "c2")]
+        if in_c != 512:
+            layers[p + "proj"] = ("conv", in_c, 512, 1, 1, 0)
+            spec.append(("branch", p, [("layer", p + "proj")]))
+        spec += [("add", p + "add", p), ("relu",)]
+        in_c = 512
+    layers["aspp1"] = ("conv", 512, 128, 1, 1, 0)
+    tags = []
+    for rate in (2, 4, 6):
+        layers["aspp_r%d" % rate] = ("conv", 512, 128, 3, 1, rate, 1, rate)
+        tags.append("r%d" % rate)
+        spec.append(("save", tags[-1]))
+    layers["aspp_pool"] = ("conv", 512, 128, 1, 1, 0)
+    spec += [("save", "ip"), ("layer", "aspp1"), ("relu",)]
+    spec += [("branch", "r%d" % rate, [("layer", "aspp_r%d" % rate), ("relu",)]) for rate in (2, 4, 6)]
+    spec += [("branch", "ip", [("gap",), ("layer", "aspp_pool"), ("relu",), ("upsample", 8, "nearest")]),
+             ("concat", "aspp_cat", tags + ["ip"])]
+    layers["aspp_proj"] = ("conv", 640, 128, 1, 1, 0)
+    layers["head"] = ("conv", 128, 10, 1, 1, 0)
+    spec += [("layer", "aspp_proj"), ("relu",), ("layer", "head"), ("upsample", 4, "bilinear")]
+    return layers, spec, shape
+
+
+EXTRA_NETWORKS["aspp_tiny"] = _aspp_tiny()
+EXTRA_NETWORKS["deeplabv3_cifar"] = _deeplabv3_cifar()
+
+
+def network(name):
+    """the (layers, spec, input shape) entry of a network of either registry"""
+    if name in NETWORKS:
+        return NETWORKS[name]
+    if name in EXTRA_NETWORKS:
+        return EXTRA_NETWORKS[name]
+    raise KeyError("unknown network %r" % (name,))
+
+
 def _walk(spec):
     """every op of a spec in order, the ops inside ("branch", tag, [ops]) included"""
     for op in spec:
@@ -401,6 +475,11 @@ def conv_groups(L):
     return L[6] if len(L) > 6 else 1
 
 
+def conv_dilation(L):
+    """dilation of a ("conv", ...) layer tuple: its optional 8th element"""
+    return L[7] if len(L) > 7 else 1
+
+
 def upsample_factors(factor):
     """(fh, fw) of an ("upsample", factor, mode) op: factor is an int or a pair"""
     return tuple(factor) if isinstance(factor, (tuple, list)) else (factor, factor)
@@ -410,15 +489,55 @@ def upsample_factors(factor):
 ALEXNET_MACS_PER_IMAGE = 1131201056
 
 
+def _macs_all(layers, ops, hw, saved):
+    """MACs of every weighted layer of `ops`, those inside branches included, with true taps (a dilated kernel's zeros are no
+    work); returns (macs, (h, w) behind the ops)"""
+    total = 0
+    h, w = hw
+    for op in ops:
+        if op[0] == "layer":
+            L = layers[op[1]]
+            if L[0] == "conv":
+                _, ic, oc, k, s, p = L[:6]
+                e = conv_dilation(L) * (k - 1) + 1
+                h, w = (h - e + 2 * p) // s + 1, (w - e + 2 * p) // s + 1
+                total += h * w * oc * (ic // conv_groups(L)) * k * k
+            elif L[0] == "deconv":
+                _, ic, oc, k, s, p, op_ = L
+                total += h * w * ic * oc * k * k
+                h, w = (h - 1) * s - 2 * p + k + op_, (w - 1) * s - 2 * p + k + op_
+            else:
+                total += L[1] * L[2]
+        elif op[0] in ("pool", "avgpool"):
+            h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
+        elif op[0] == "gap":
+            h, w = 1, 1
+        elif op[0] == "upsample":
+            fh, fw = upsample_factors(op[1])
+            h, w = h * fh, w * fw
+        elif op[0] == "save":
+            saved[op[1]] = (h, w)
+        elif op[0] == "branch":
+            t, saved[op[1]] = _macs_all(layers, op[2], saved[op[1]], saved)
+            total += t
+    return total, (h, w)
+
+
 def macs_per_image(name):
-    layers, spec, (c, h, w) = NETWORKS[name]
+    """MACs of one image through network(name), true taps.  Two countings, by registry: an entry of EXTRA_NETWORKS counts every
+    weighted layer, those inside branches included (_macs_all); an entry of NETWORKS keeps the older counting below, which
+    skips the convs of a branch -- its figures are pinned by tests and quoted in the documents."""
+    layers, spec, (c, h, w) = network(name)
+    if name in EXTRA_NETWORKS:  # (every conv counts, the branches' too; the older entries keep their pinned figures below)
+        return _macs_all(layers, spec, (h, w), {})[0]
     total = 0
     for op in spec:
         if op[0] == "layer":
             L = layers[op[1]]
             if L[0] == "conv":
                 _, ic, oc, k, s, p = L[:6]
-                h, w = (h - k + 2 * p) // s + 1, (w - k + 2 * p) // s + 1
+                e = conv_dilation(L) * (k - 1) + 1
+                h, w = (h - e + 2 * p) // s + 1, (w - e + 2 * p) // s + 1
                 total += h * w * oc * (ic // conv_groups(L)) * k * k
                 c = oc
             elif L[0] == "deconv":  # the real MACs: every input pixel meets every tap once
@@ -446,7 +565,7 @@ def macs_per_image(name):
 def synthetic_state_dict(name, seed=42):
     """He-uniform weights, U(-1/sqrt(fan_in), 1/sqrt(fan_in)) biases; keys '<attr>.weight'/'<attr>.bias'."""
     rng = np.random.default_rng(seed)
-    layers = NETWORKS[name][0]
+    layers = network(name)[0]
     sd = {}
     for attr, L in layers.items():
         if L[0] == "deconv":  # [in, out, k, k]; an output pixel sums in * ceil(k / stride)^2 products
@@ -462,7 +581,7 @@ def synthetic_state_dict(name, seed=42):
 
 def synthetic_input(name, batch, seed=1234):
     """Normalised-image-like input, inside quantize()'s no-wrap window for scale 0.025 / zp 127."""
-    c, h, w = NETWORKS[name][2]
+    c, h, w = network(name)[2]
     rng = np.random.default_rng(seed)
     if name in ("mnist_fc", "two_conv"):
         return rng.uniform(0, 1, (batch, c, h, w)).astype(np.float32)  # ToTensor() only
@@ -472,11 +591,11 @@ def synthetic_input(name, batch, seed=1234):
 
 
 def build(name):
-    """An i8ie.Module running NETWORKS[name] on the GPU."""
+    """An i8ie.Module running network(name) on the GPU."""
     import int8inferenceengine_amd  # noqa: F401  (puts i8ie / _CXX_i8ie on sys.path)
     import i8ie
 
-    layers, spec, _ = NETWORKS[name]
+    layers, spec, _ = network(name)
 
     class SpecNet(i8ie.Module):
         def __init__(self):
@@ -494,7 +613,10 @@ def build(name):
                 if L[0] == "deconv":
                     setattr(self, attr, i8ie.ConvTranspose2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], output_padding=L[6]))
                 elif L[0] == "conv":
-                    if conv_groups(L) == 1:
+                    if conv_dilation(L) != 1:
+                        setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], groups=conv_groups(L),
+                                                        dilation=L[7]))
+                    elif conv_groups(L) == 1:
                         setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5]))
                     else:
                         setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], groups=L[6]))
@@ -554,24 +676,24 @@ def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, p
 
 def layer_names(name):
     """the weighted layers (Conv2d / Linear) in the order the spec names them, those of a branch included"""
-    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "layer"]
+    return [op[1] for op in _walk(network(name)[1]) if op[0] == "layer"]
 
 
 def add_names(name):
     """the Adds of a residual network, in spec order"""
-    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "add"]
+    return [op[1] for op in _walk(network(name)[1]) if op[0] == "add"]
 
 
 def mul_names(name):
     """the Muls of a network, in spec order"""
-    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "mul"]
+    return [op[1] for op in _walk(network(name)[1]) if op[0] == "mul"]
 
 
 def concat_names(name):
     """the Concats of a network, in spec order"""
-    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "concat"]
+    return [op[1] for op in _walk(network(name)[1]) if op[0] == "concat"]
 
 
 def activation_names(name):
     """the Activations of a network, in spec order"""
-    return [op[1] for op in _walk(NETWORKS[name][1]) if op[0] == "act"]
+    return [op[1] for op in _walk(network(name)[1]) if op[0] == "act"]
