@@ -79,7 +79,8 @@ int i8ie_flin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c);
 bool i8ie_mlin_wants(int m, int n, int Kpad, bool force);
 int i8ie_mlin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c);
 
-// ---- launch helpers of i8ie_gemm.hip (the first three) and i8ie_igemm.hip, called by i8ie_layer.hip --------------------
+// ---- launch helpers of i8ie_gemm.hip (the first three) and i8ie_igemm.hip, called by i8ie_layer.hip and, where a handle is
+// made or a stateless call runs (pad_rows, offsets, finish_offsets), by i8ie_layer_create.hip ---------------------------
 int i8ie_launch_pad_rows(i8ie_ctx* ctx, const void* src, int rows, int k, void* dst, int rows_pad, int k_pad, int fill);
 int i8ie_launch_offsets(i8ie_ctx* ctx, bool conv, const int8_t* qw, const int8_t* qb, int n, int K, float s_in, int zp_in,
                         int32_t* oc, int32_t* wsum);

@@ -1,31 +1,25 @@
-// i8ie_layer.hip -- Linear / Conv2d INT8 forward entry points of the C-ABI:
-// the stateless calls on raw device pointers and the layer handles that keep
-// the converted weights resident (packed for the MFMA kernels) and cache the
-// zero-point offset vector per (s_in, zp_in).
-//   reference: src/fully_connected.cc:22-52, src/conv2d.cc:100-142,
-//              src/layer.cc:6-26,36-54
+// i8ie_layer.hip -- the forward of a layer handle (Linear / Conv2d / ConvTranspose2d, INT8): validate -> geometry -> plan -> peel ->
+// route, the layout / pool queries that read the same plan, and the v1 runners.  How a handle is made,
+// which route it takes and the stateless calls: i8ie_layer_create.hip (section 4b).
+//   reference: src/fully_connected.cc:22-52, src/conv2d.cc:100-142
 //
-// Conv2d has five execution paths, all producing the reference's bytes (how a forward reaches them: DESIGN.md section 4a):
+// Conv2d has five execution paths, all producing the reference's bytes:
 //   A  channels % 16 == 0: implicit GEMM over NHWC activations (i8ie_igemm.hip)
 //   B  channels <= 4 and stride % 4 == 0 (AlexNet conv1): the NCHW input is repacked
 //      once into a physically padded, 4-pixel-grouped NHWC image; then path A's kernel
 //   F  anything else: materialised im2col + v1 GEMM (i8ie_gemm.hip)
-//   G  groups > 1 (i8ie_conv2d_create_grouped; not in the reference): one reference convolution per group, in the
-//      grouped kernels of i8ie_gconv.hip over NHWC activations; and every layer with a dilation > 1
-//      (i8ie_conv2d_create_dilated; not in the reference), dense ones as groups = 1
+//   G  groups > 1 (not in the reference): one reference convolution per group, in the grouped kernels of i8ie_gconv.hip over
+//      NHWC activations; and every layer with a dilation > 1 (not in the reference), dense ones as groups = 1
 //   D  inside G: a dense dilated layer at stride 1 with channels % 16 == 0 runs in dconv_mfma (i8ie_dconv.hip), its input
 //      patches phase-subsampled into LDS; what that kernel declines stays in the grouped kernels
-//   T  ConvTranspose2d (i8ie_conv_transpose2d_create; not in the reference): the reference convolution of the equivalent
-//      zero-inserted problem, computed phase by phase in the kernels of i8ie_deconv.hip over NHWC activations
+//   T  ConvTranspose2d (not in the reference): the reference convolution of the equivalent zero-inserted problem, computed
+//      phase by phase in the kernels of i8ie_deconv.hip over NHWC activations
 // Activations cross the ABI as NCHW (the reference's layout) or, on request, as
 // NHWC so that consecutive layers skip the layout conversion.
-#include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
-#include "i8ie_internal.h"
-#include "i8ie_calls.h"
+#include "i8ie_layer.h"
 #include "i8ie_first.h"
 #include "i8ie_stem.h"
 #include "i8ie_requant.h"
@@ -33,60 +27,10 @@
 #include "i8ie_deconv.h"
 #include "i8ie_dconv.h"
 
-namespace {
-
-constexpr size_t kColBudget = (size_t)192 << 20;  // im2col scratch per chunk (fallback path F)
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
-
-enum { PATH_F = 0, PATH_A = 1, PATH_B = 2, PATH_G = 3, PATH_T = 4 };  // PATH_G: grouped (i8ie_gconv.hip), PATH_T: transposed (i8ie_deconv.hip)
-
-struct ConvGeom {
-  int c, h, w, kc, kh, kw, stride, pad, oh, ow, K, Kpad;
-};
-
-// dil: the dilation: the kernel spans dil (k - 1) + 1 pixels; 1 = the reference's geometry
-int conv_geom(int c, int h, int w, int kc, int kh, int kw, int stride, int pad, ConvGeom* g, int dil = 1) {
-  I8IE_REQUIRE(c > 0 && h > 0 && w > 0 && kc > 0 && kh > 0 && kw > 0, "non-positive dimension");
-  I8IE_REQUIRE(stride > 0, "stride must be positive");  // include/conv2d.h:12-14
-  I8IE_REQUIRE(pad >= 0, "negative padding");
-  I8IE_REQUIRE(dil >= 1, "dilation must be >= 1");
-  const long long eh = (long long)dil * (kh - 1) + 1, ew = (long long)dil * (kw - 1) + 1;  // the kernel's extent
-  I8IE_REQUIRE(h - eh + 2 * pad >= 0 && w - ew + 2 * pad >= 0,
-               dil > 1 ? "dilated kernel larger than padded input" : "kernel larger than padded input");
-  g->c = c; g->h = h; g->w = w; g->kc = kc; g->kh = kh; g->kw = kw; g->stride = stride; g->pad = pad;
-  g->oh = (int)((h - eh + 2 * pad) / stride) + 1;  // src/conv2d.cc:108-109
-  g->ow = (int)((w - ew + 2 * pad) / stride) + 1;
-  g->K = c * kh * kw;
-  g->Kpad = round_up(g->K, 128);
-  return I8IE_OK;
-}
-
-// ConvTranspose2d: kh = kw = k, OH = (H - 1) s - 2 p + k + output_padding (torch.nn.ConvTranspose2d)
-int deconv_geom(int c, int h, int w, int kc, int k, int stride, int pad, int opad, ConvGeom* g) {
-  I8IE_REQUIRE(c > 0 && h > 0 && w > 0 && kc > 0 && k > 0, "non-positive dimension");
-  g->c = c; g->h = h; g->w = w; g->kc = kc; g->kh = k; g->kw = k; g->stride = stride; g->pad = pad;
-  const long long oh = (long long)(h - 1) * stride - 2 * pad + k + opad, ow = (long long)(w - 1) * stride - 2 * pad + k + opad;
-  I8IE_REQUIRE(oh > 0 && ow > 0 && oh < (1 << 30) && ow < (1 << 30), "transposed conv: empty or oversized output");
-  g->oh = (int)oh;
-  g->ow = (int)ow;
-  g->K = c * k * k;
-  g->Kpad = round_up(g->K, 128);
-  return I8IE_OK;
-}
-
-inline int chunk_images(const ConvGeom& g, int n) {
-  const size_t per_img = (size_t)g.oh * g.ow * g.Kpad;
-  size_t imgs = kColBudget / per_img;
-  if (imgs < 1) imgs = 1;
-  return imgs > (size_t)n ? n : (int)imgs;
-}
-
 // ---- v1 (fallback) runners ------------------------------------------------------------------
 int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, const int8_t* Bpack, const int32_t* oc,
                 const int32_t* wsum, uint8_t zp_in, float s_in, float s_w, float s_out, uint8_t zp_out, uint8_t* out,
-                int32_t* acc, uint8_t* col, int imgs_per_chunk, const float* sbv = nullptr) {
+                int32_t* acc, uint8_t* col, int imgs_per_chunk, const float* sbv) {
   const int P = cg.oh * cg.ow;
   for (int i0 = 0; i0 < n; i0 += imgs_per_chunk) {
     const int nb = (n - i0) < imgs_per_chunk ? (n - i0) : imgs_per_chunk;
@@ -120,7 +64,7 @@ int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, con
 
 int linear_run_v1(i8ie_ctx* ctx, const uint8_t* in, int m, int k, const int8_t* Bpack, int Kpad, const int8_t* qb,
                   int n, const int32_t* oc, const int32_t* wsum, float s_in, float s_w, float s_out, uint8_t zp_out,
-                  uint8_t* out, int32_t* acc, uint8_t* scratch, const float* sbv = nullptr) {
+                  uint8_t* out, int32_t* acc, uint8_t* scratch, const float* sbv) {
   I8ieGemmArgs g{};
   if (k % 16 != 0 || !aligned16(in)) {
     I8IE_TRY(i8ie_launch_pad_rows(ctx, in, m, k, scratch, m, Kpad, 0));
@@ -137,59 +81,6 @@ int linear_run_v1(i8ie_ctx* ctx, const uint8_t* in, int m, int k, const int8_t* 
   g.out = out; g.out_mode = I8IE_OUT_ROWMAJOR; g.P = 1; g.acc = acc; g.Ktrue = k; g.sbv = sbv;
   return i8ie_gemm_launch(ctx, g);
 }
-
-}  // namespace
-
-struct i8ie_layer {
-  i8ie_ctx* ctx = nullptr;
-  bool conv = false;
-  int n = 0, K = 0;  // out features, reduction length (reference K order)
-  int c = 0, kh = 0, kw = 0, stride = 1, pad = 0;
-  int Kpad = 0, Npad = 0;
-  float s_w = 1.0f;
-  float s_out = 1.0f;   // include/layer.h:46
-  uint8_t zp_out = 0;   // include/layer.h:47
-  int8_t* qw = nullptr;     // [n][K] as converted, K ordered (c, kh, kw)
-  int8_t* qb = nullptr;     // [n]
-  int8_t* Bpack = nullptr;  // [Npad][Kpad] zero padded, reference K order (Linear; conv path F)
-  int8_t* Bperm = nullptr;  // Linear fed by an NHWC-flattened activation: Bpack with K reordered (h, w, c)
-  int perm_c = 0, perm_hw = 0;
-  int path = PATH_F;        // conv: PATH_A / PATH_B / PATH_F / PATH_G / PATH_T
-  int dil = 1, dil_arg = 1; // conv: the effective dilation (1 when the kernel is 1 x 1) and the number the layer was created with;
-                            // dil > 1 (i8ie_conv2d_create_dilated) is PATH_G as well, with groups >= 1
-  int groups = 1;           // conv, groups > 1 (PATH_G): K above is the reduction length INSIDE a group, (c / groups) * kh * kw,
-  int Ngp = 0, Kgp = 0;     // and the weights live in `wc` as [groups][Ngp][Kgp], K ordered (kh, kw, cg) (i8ie_gconv.h)
-  int8_t* Bg = nullptr;
-  int* gtab = nullptr;      // the MFMA kernel's gather table (i8ie_gconv_ktab), in `wc` as well
-  int opad = 0;             // ConvTranspose2d (PATH_T): output_padding; qw / K above are the EQUIVALENT matrix [n][c * k * k];
-  int Kpp = 0;              // the phase panels [stride^2][Ngp][Kpp], their gather table and the per-(phase, feature) sums of
-  int8_t* Bt = nullptr;     // the taps a phase does not see (i8ie_deconv.h), all three in `wc`
-  int* ttab = nullptr;
-  int32_t* tph = nullptr;
-  int8_t* Bpack2 = nullptr; // conv paths A/B: [Npad][Kpad2], K ordered (kh, kw, c) / grouped
-  int K2 = 0, Kpad2 = 0;    // valid / padded K of Bpack2 (bytes)
-  I8ieWCache wc;            // Bpack2 in the fragment orders of i8ie_pconv.hip / i8ie_tconv.hip: one buffer per packing
-                            // key, made on first use, never overwritten (captured graphs replay their addresses)
-  int kwg = 0;              // path B: taps per row in 4-pixel groups
-  int8_t* Bstem = nullptr;  // path B, when the first-stage kernel (i8ie_stem.hip) takes the layer: [n][KpadStem], K in its
-  int KpadStem = 0;         // space-to-depth order (i8ie_stem_kindex), zero padded
-  int32_t* wsum = nullptr;  // [n]
-  int32_t* oc = nullptr;    // [n], valid for (oc_s_in, oc_zp_in)
-  int32_t* ocp = nullptr;   // [n] oc + 128 * wsum
-  float* biasf = nullptr;   // [n] (float)qb / s_in (Linear)
-  bool oc_valid = false;
-  float oc_s_in = 0.0f;
-  int oc_zp_in = -1;
-  // per-channel weight scales (i8ie_*_create_per_channel): s_w[j] per output feature, and the per-column multipliers of
-  // i8ie_requant.h cached like oc' per (s_in, s_out); every kernel then runs its PC instance (s_w above is unused)
-  bool pc = false;
-  std::vector<float> sw_host;  // [n]
-  float* swv = nullptr;        // [Npad] s_w[j] (padding 1)
-  float* msv = nullptr;        // [Npad] fl(s_in * s_w[j] / s_out) (padding 0), valid for (ms_s_in, ms_s_out)
-  bool ms_valid = false;
-  bool ms_fast = false;        // every column allows the guarded estimate (i8ie_requant_pc_fast)
-  float ms_s_in = 0.0f, ms_s_out = 0.0f;
-};
 
 namespace {
 
@@ -223,13 +114,6 @@ int ensure_multipliers(i8ie_layer* L, float s_in) {
   L->ms_s_out = L->s_out;
   return I8IE_OK;
 }
-// what the launchers get as s_w: the layer's scale, or for a per-channel layer the switch between the guarded estimate
-// (1) and the exact sequence (0) that i8ie_make_requant reads off it (I8ieIgemmCall::msv)
-inline float sw_arg(const i8ie_layer* L) { return L->pc ? (L->ms_fast ? 1.0f : 0.0f) : L->s_w; }
-inline const float* msv_arg(const i8ie_layer* L) { return L->pc ? L->msv : nullptr; }
-inline const float* sbv_arg(const i8ie_layer* L) { return L->pc ? L->swv : nullptr; }
-
-bool force_fallback(const i8ie_ctx* ctx) { return (ctx->options & 1) != 0; }
 
 }  // namespace
 
@@ -259,106 +143,6 @@ int i8ie_ctx_set_option(i8ie_ctx* ctx, int option, int value) {
   else
     ctx->options &= ~1;
   return I8IE_OK;
-}
-
-int i8ie_conv_offsets(i8ie_ctx* ctx, const int8_t* qw, const int8_t* qb, int kc, int K, float s_in, uint8_t zp_in,
-                      int32_t* oc) {
-  I8IE_REQUIRE(ctx && qw && qb && oc, "null argument");
-  I8IE_REQUIRE(kc > 0 && K > 0, "non-positive dimension");
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  return i8ie_launch_offsets(ctx, true, qw, qb, kc, K, s_in, zp_in, oc, nullptr);
-}
-
-int i8ie_linear_offsets(i8ie_ctx* ctx, const int8_t* qw, int n, int k, uint8_t zp_in, int32_t* oc) {
-  I8IE_REQUIRE(ctx && qw && oc, "null argument");
-  I8IE_REQUIRE(n > 0 && k > 0, "non-positive dimension");
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  return i8ie_launch_offsets(ctx, false, qw, nullptr, n, k, 0.0f, zp_in, oc, nullptr);
-}
-
-// ---- stateless entry points: any geometry, v1 kernels, caller supplies oc --------------------
-int i8ie_linear_u8s8(i8ie_ctx* ctx, const uint8_t* in, int m, int k, const int8_t* qw, const int8_t* qb, int n,
-                     const int32_t* oc, float s_in, float s_w, float s_out, uint8_t zp_out, uint8_t* out,
-                     int32_t* acc) {
-  I8IE_REQUIRE(ctx && in && qw && qb && oc && out, "null argument");
-  I8IE_REQUIRE(m > 0 && k > 0 && n > 0, "non-positive dimension");
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  const int Kpad = round_up(k, 128), Npad = round_up(n, 128);
-  const size_t b_bytes = i8ie_align_up((size_t)Npad * Kpad, 256);
-  const size_t s_bytes = i8ie_align_up((size_t)n * 4, 256);
-  const size_t a_bytes = (size_t)m * Kpad;
-  I8IE_TRY(i8ie_ws_reserve(ctx, b_bytes + s_bytes + a_bytes));
-  uint8_t* ws = (uint8_t*)ctx->ws;
-  int8_t* Bpack = (int8_t*)ws;
-  int32_t* wsum = (int32_t*)(ws + b_bytes);
-  uint8_t* scratch = ws + b_bytes + s_bytes;
-  I8IE_TRY(i8ie_launch_pad_rows(ctx, qw, n, k, Bpack, Npad, Kpad, 0));
-  I8IE_TRY(i8ie_launch_offsets(ctx, false, qw, nullptr, n, k, 0.0f, 0, nullptr, wsum));
-  return linear_run_v1(ctx, in, m, k, Bpack, Kpad, qb, n, oc, wsum, s_in, s_w, s_out, zp_out, out, acc, scratch);
-}
-
-int i8ie_conv2d_u8s8(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int kh,
-                     int kw, int stride, int pad, uint8_t zp_in, const int32_t* oc, float s_in, float s_w,
-                     float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
-  I8IE_REQUIRE(ctx && in && qw && oc && out, "null argument");
-  I8IE_REQUIRE(n > 0, "non-positive batch");
-  ConvGeom cg;
-  I8IE_TRY(conv_geom(c, h, w, kc, kh, kw, stride, pad, &cg));
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  const int Npad = round_up(kc, 128);
-  const int ipc = chunk_images(cg, n);
-  const size_t b_bytes = i8ie_align_up((size_t)Npad * cg.Kpad, 256);
-  const size_t s_bytes = i8ie_align_up((size_t)kc * 4, 256);
-  const size_t col_bytes = (size_t)ipc * cg.oh * cg.ow * cg.Kpad;
-  I8IE_TRY(i8ie_ws_reserve(ctx, b_bytes + s_bytes + col_bytes));
-  uint8_t* ws = (uint8_t*)ctx->ws;
-  int8_t* Bpack = (int8_t*)ws;
-  int32_t* wsum = (int32_t*)(ws + b_bytes);
-  uint8_t* col = ws + b_bytes + s_bytes;
-  I8IE_TRY(i8ie_launch_pad_rows(ctx, qw, kc, cg.K, Bpack, Npad, cg.Kpad, 0));
-  I8IE_TRY(i8ie_launch_offsets(ctx, true, qw, nullptr, kc, cg.K, 1.0f, 0, nullptr, wsum));
-  return conv_run_v1(ctx, in, n, cg, Bpack, oc, wsum, zp_in, s_in, s_w, s_out, zp_out, out, acc, col, ipc);
-}
-
-static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const int8_t* qb_host, int n, int K, int c,
-                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups = 1, int opad = -1,
-                        int dil = 1);
-
-// the stateless grouped / transposed calls: the temporary handle `L` runs one NCHW forward with the caller's offset vector (it
-// carries the bias term) instead of the handle's own, and is destroyed
-static int run_once(i8ie_layer* L, const uint8_t* in, int n, int h, int w, uint8_t zp_in, const int32_t* oc, float s_in,
-                    float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
-  L->s_out = s_out;
-  L->zp_out = zp_out;
-  int rc = i8ie_launch_finish_offsets(L->ctx, oc, L->wsum, L->qb, s_in, L->n, L->ocp, nullptr);
-  L->oc_valid = rc == I8IE_OK;
-  L->oc_s_in = s_in;
-  L->oc_zp_in = zp_in;
-  if (rc == I8IE_OK) rc = i8ie_layer_forward(L, in, n, h, w, s_in, zp_in, out, acc);
-  i8ie_layer_destroy(L);
-  return rc;
-}
-
-// the stateless form with groups (groups: not in the reference).  groups > 1 packs the weights for this one call: the
-// device weights are read back, a temporary layer handle runs the call with the caller's oc[] and is destroyed.
-int i8ie_conv2d_u8s8_grouped(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int kh,
-                             int kw, int stride, int pad, int groups, uint8_t zp_in, const int32_t* oc, float s_in,
-                             float s_w, float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
-  I8IE_REQUIRE(groups >= 1, "groups must be >= 1");
-  I8IE_REQUIRE(c > 0 && kc > 0 && c % groups == 0 && kc % groups == 0, "groups must divide the input and the output channels");
-  if (groups == 1)
-    return i8ie_conv2d_u8s8(ctx, in, n, c, h, w, qw, kc, kh, kw, stride, pad, zp_in, oc, s_in, s_w, s_out, zp_out, out, acc);
-  I8IE_REQUIRE(ctx && in && qw && oc && out, "null argument");
-  I8IE_REQUIRE(n > 0, "non-positive batch");
-  ConvGeom cg;
-  I8IE_TRY(conv_geom(c, h, w, kc, kh, kw, stride, pad, &cg));
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  const int Kg = (c / groups) * kh * kw;
-  std::vector<int8_t> qw_host((size_t)kc * Kg), qb_host((size_t)kc, 0);
-  I8IE_TRY(i8ie_memcpy_d2h(ctx, qw_host.data(), qw, qw_host.size()));
-  i8ie_layer* L = nullptr;
-  I8IE_TRY(layer_create(ctx, true, qw_host.data(), qb_host.data(), kc, Kg, c, kh, kw, stride, pad, s_w, &L, groups));
-  return run_once(L, in, n, h, w, zp_in, oc, s_in, s_out, zp_out, out, acc);
 }
 
 // ---- NHWC helpers exposed on the ABI -----------------------------------------------------------
@@ -392,364 +176,6 @@ int i8ie_maxpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in, int in_border, uint
   I8IE_REQUIRE(aligned16(in) && aligned16(out), "buffers must be 16-byte aligned");
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   return i8ie_launch_maxpool_nhwc(ctx, in, in_border, out, out_border, n, c, h, w, k, s, 0);
-}
-
-// ---- layer handles ----------------------------------------------------------------------------
-static int layer_create(i8ie_ctx* ctx, bool conv, const int8_t* qw_host, const int8_t* qb_host, int n, int K, int c,
-                        int kh, int kw, int stride, int pad, float s_w, i8ie_layer** out, int groups, int opad, int dil) {
-  I8IE_REQUIRE(ctx && qw_host && qb_host && out, "null argument");
-  I8IE_REQUIRE(n > 0 && K > 0, "non-positive dimension");
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  i8ie_layer* L = new (std::nothrow) i8ie_layer();
-  if (!L) return I8IE_ERR_OOM;
-  L->ctx = ctx; L->conv = conv; L->n = n; L->K = K; L->c = c; L->kh = kh; L->kw = kw;
-  L->stride = stride; L->pad = pad; L->s_w = s_w; L->dil = L->dil_arg = dil;
-  L->Kpad = round_up(K, 128);
-  L->Npad = round_up(n, 128);
-  // MFMA-order weight panel for the implicit-GEMM conv paths, built on the host once
-  std::vector<int8_t> pack2, packg;
-  std::vector<int> gtab, ttab;
-  std::vector<int8_t> packt;
-  std::vector<int32_t> tph;
-  if (conv && opad >= 0) {
-    // transposed (opad: output_padding): qw_host is the equivalent matrix [n][c * k * k]
-    L->path = PATH_T;
-    L->opad = opad;
-    L->Ngp = round_up(n, 16);
-    L->Kpp = i8ie_deconv_kpitch(c, kh, stride);
-    i8ie_deconv_pack(qw_host, n, c, kh, stride, packt, tph);
-    i8ie_deconv_ktab(c, kh, stride, ttab);
-  } else if (conv && (groups > 1 || dil > 1)) {
-    // grouped: qw_host is [n][Cg * kh * kw]; group g's Ng rows go to panel g in (kh, kw, cg) order.  A dilated layer
-    // (dil > 1) takes this route with any groups >= 1: its weights are packed as they are, the dilation is in the gather
-    const int Cg = c / groups, Ng = n / groups;
-    L->path = PATH_G;
-    L->groups = groups;
-    L->Ngp = round_up(Ng, 16);
-    L->Kgp = round_up(K, 64);
-    packg.assign((size_t)groups * L->Ngp * L->Kgp, 0);
-    for (int j = 0; j < n; ++j)
-      for (int ch = 0; ch < Cg; ++ch)
-        for (int y = 0; y < kh; ++y)
-          for (int x = 0; x < kw; ++x)
-            packg[((size_t)(j / Ng) * L->Ngp + j % Ng) * L->Kgp + ((size_t)y * kw + x) * Cg + ch] =
-                qw_host[(((size_t)j * Cg + ch) * kh + y) * kw + x];
-    i8ie_gconv_ktab(Cg, kh, kw, L->Kgp, gtab);
-  } else if (conv && c % 16 == 0) {
-    L->path = PATH_A;
-    L->K2 = kh * kw * c;
-    L->Kpad2 = round_up(L->K2, 128);
-    pack2.assign((size_t)L->Npad * L->Kpad2, 0);
-    for (int j = 0; j < n; ++j)
-      for (int ch = 0; ch < c; ++ch)
-        for (int y = 0; y < kh; ++y)
-          for (int x = 0; x < kw; ++x)
-            pack2[(size_t)j * L->Kpad2 + ((size_t)y * kw + x) * c + ch] = qw_host[(((size_t)j * c + ch) * kh + y) * kw + x];
-  } else if (conv && c <= 4 && stride % 4 == 0) {
-    L->path = PATH_B;
-    L->kwg = (kw + 3) / 4;
-    L->K2 = kh * L->kwg * 16;
-    L->Kpad2 = round_up(L->K2, 128);
-    pack2.assign((size_t)L->Npad * L->Kpad2, 0);
-    for (int j = 0; j < n; ++j)
-      for (int ch = 0; ch < c; ++ch)
-        for (int y = 0; y < kh; ++y)
-          for (int x = 0; x < kw; ++x)
-            pack2[(size_t)j * L->Kpad2 + ((size_t)y * L->kwg + x / 4) * 16 + (x % 4) * 4 + ch] =
-                qw_host[(((size_t)j * c + ch) * kh + y) * kw + x];
-  }
-  std::vector<int8_t> packs;  // the same weights in the K order of the first-stage kernel (i8ie_stem.hip)
-  if (L->path == PATH_B && c <= 3 && n % 32 == 0 && n <= 96 && (kh + 3) / 4 * ((kw + 3) / 4) * 48 <= 14 * 32) {
-    L->KpadStem = i8ie_stem_kpad(kh, kw);
-    packs.assign((size_t)n * L->KpadStem, 0);
-    for (int j = 0; j < n; ++j)
-      for (int ch = 0; ch < c; ++ch)
-        for (int y = 0; y < kh; ++y)
-          for (int x = 0; x < kw; ++x)
-            packs[(size_t)j * L->KpadStem + i8ie_stem_kindex(kw, ch, y, x)] = qw_host[(((size_t)j * c + ch) * kh + y) * kw + x];
-  }
-  int rc = I8IE_OK;
-  do {
-    if ((rc = i8ie_malloc(ctx, (size_t)n * K, (void**)&L->qw)) != I8IE_OK) break;
-    if ((rc = i8ie_malloc(ctx, (size_t)n, (void**)&L->qb)) != I8IE_OK) break;
-    if ((rc = i8ie_malloc(ctx, (size_t)L->Npad * L->Kpad, (void**)&L->Bpack)) != I8IE_OK) break;
-    if ((rc = i8ie_malloc(ctx, (size_t)n * 4, (void**)&L->wsum)) != I8IE_OK) break;
-    if ((rc = i8ie_malloc(ctx, (size_t)n * 4, (void**)&L->oc)) != I8IE_OK) break;
-    if ((rc = i8ie_malloc(ctx, (size_t)L->Npad * 4, (void**)&L->ocp)) != I8IE_OK) break;  // padded: vector loads
-    if ((rc = i8ie_malloc(ctx, (size_t)L->Npad * 4, (void**)&L->biasf)) != I8IE_OK) break;
-    if ((rc = i8ie_memset(ctx, L->ocp, 0, (size_t)L->Npad * 4)) != I8IE_OK) break;
-    if ((rc = i8ie_memset(ctx, L->biasf, 0, (size_t)L->Npad * 4)) != I8IE_OK) break;
-    if ((rc = i8ie_memcpy_h2d(ctx, L->qw, qw_host, (size_t)n * K)) != I8IE_OK) break;
-    if ((rc = i8ie_memcpy_h2d(ctx, L->qb, qb_host, (size_t)n)) != I8IE_OK) break;
-    if ((rc = i8ie_launch_pad_rows(ctx, L->qw, n, K, L->Bpack, L->Npad, L->Kpad, 0)) != I8IE_OK) break;
-    if ((rc = i8ie_launch_offsets(ctx, conv, L->qw, nullptr, n, K, 1.0f, 0, nullptr, L->wsum)) != I8IE_OK) break;
-    if (!pack2.empty()) {
-      if ((rc = i8ie_malloc(ctx, pack2.size(), (void**)&L->Bpack2)) != I8IE_OK) break;
-      if ((rc = i8ie_memcpy_h2d(ctx, L->Bpack2, pack2.data(), pack2.size())) != I8IE_OK) break;
-    }
-    if (!packg.empty()) {  // (kept per packing key like the re-packed panels: never overwritten, freed with the layer)
-      if ((rc = i8ie_malloc(ctx, packg.size(), (void**)&L->Bg)) != I8IE_OK) break;
-      L->wc.ents.push_back({0x6763000000000001ull, L->Bg});
-      if ((rc = i8ie_memcpy_h2d(ctx, L->Bg, packg.data(), packg.size())) != I8IE_OK) break;
-      if ((rc = i8ie_malloc(ctx, gtab.size() * 4, (void**)&L->gtab)) != I8IE_OK) break;
-      L->wc.ents.push_back({0x6763000000000002ull, L->gtab});
-      if ((rc = i8ie_memcpy_h2d(ctx, L->gtab, gtab.data(), gtab.size() * 4)) != I8IE_OK) break;
-    }
-    if (!packt.empty()) {  // (per packing key as well)
-      if ((rc = i8ie_malloc(ctx, packt.size(), (void**)&L->Bt)) != I8IE_OK) break;
-      L->wc.ents.push_back({0x6463000000000001ull, L->Bt});
-      if ((rc = i8ie_memcpy_h2d(ctx, L->Bt, packt.data(), packt.size())) != I8IE_OK) break;
-      if ((rc = i8ie_malloc(ctx, ttab.size() * 4, (void**)&L->ttab)) != I8IE_OK) break;
-      L->wc.ents.push_back({0x6463000000000002ull, L->ttab});
-      if ((rc = i8ie_memcpy_h2d(ctx, L->ttab, ttab.data(), ttab.size() * 4)) != I8IE_OK) break;
-      if ((rc = i8ie_malloc(ctx, tph.size() * 4, (void**)&L->tph)) != I8IE_OK) break;
-      L->wc.ents.push_back({0x6463000000000003ull, L->tph});
-      if ((rc = i8ie_memcpy_h2d(ctx, L->tph, tph.data(), tph.size() * 4)) != I8IE_OK) break;
-    }
-    if (!packs.empty()) {
-      if ((rc = i8ie_malloc(ctx, packs.size(), (void**)&L->Bstem)) != I8IE_OK) break;
-      if ((rc = i8ie_memcpy_h2d(ctx, L->Bstem, packs.data(), packs.size())) != I8IE_OK) break;
-    }
-  } while (0);
-  if (rc != I8IE_OK) {
-    i8ie_layer_destroy(L);
-    return rc;
-  }
-  *out = L;
-  return I8IE_OK;
-}
-
-// per-channel layers: the per-tensor handle `L` (created with s_w = 1) plus s_w[n] (host copy, device [Npad]) and the
-// multiplier buffer.  Hands the handle over in *out, or destroys it.
-static int layer_make_per_channel(i8ie_layer* L, const float* s_w_host, i8ie_layer** out) {
-  const int n = L->n;
-  L->pc = true;
-  L->sw_host.assign(s_w_host, s_w_host + n);
-  std::vector<float> sw((size_t)L->Npad, 1.0f);
-  for (int j = 0; j < n; ++j) sw[j] = s_w_host[j];
-  int rc = i8ie_malloc(L->ctx, (size_t)L->Npad * 4, (void**)&L->swv);
-  if (rc == I8IE_OK) rc = i8ie_malloc(L->ctx, (size_t)L->Npad * 4, (void**)&L->msv);
-  if (rc == I8IE_OK) rc = i8ie_memcpy_h2d(L->ctx, L->swv, sw.data(), sw.size() * 4);
-  if (rc == I8IE_OK) rc = i8ie_memset(L->ctx, L->msv, 0, (size_t)L->Npad * 4);
-  if (rc == I8IE_OK) *out = L;
-  else i8ie_layer_destroy(L);
-  return rc;
-}
-
-// scales from the caller: finite and >= 0 (pooling the INT32 accumulators before the requantiser needs a monotone
-// map per channel, DESIGN.md "Per-channel weight scales")
-static int check_scales(const float* s_w, int n) {
-  I8IE_REQUIRE(s_w != nullptr, "null argument");
-  for (int j = 0; j < n; ++j) {
-    if (!(s_w[j] >= 0.0f && s_w[j] <= 3.402823466e+38f)) {
-      i8ie_set_error("per-channel weight scale %d is negative or not finite", j);
-      return I8IE_ERR_ARG;
-    }
-  }
-  return I8IE_OK;
-}
-
-int i8ie_linear_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int n, int k,
-                                   const float* s_w_host, i8ie_layer** out) {
-  I8IE_REQUIRE(out != nullptr && n > 0, "bad argument");
-  I8IE_TRY(check_scales(s_w_host, n));
-  i8ie_layer* L = nullptr;
-  I8IE_TRY(i8ie_linear_create(ctx, qw_host, qb_host, n, k, 1.0f, &L));
-  return layer_make_per_channel(L, s_w_host, out);
-}
-
-int i8ie_conv2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh,
-                                   int kw, int stride, int pad, const float* s_w_host, i8ie_layer** out) {
-  I8IE_REQUIRE(out != nullptr && kc > 0, "bad argument");
-  I8IE_TRY(check_scales(s_w_host, kc));
-  i8ie_layer* L = nullptr;
-  I8IE_TRY(i8ie_conv2d_create(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, 1.0f, &L));
-  return layer_make_per_channel(L, s_w_host, out);
-}
-
-int i8ie_layer_weight_scales(const i8ie_layer* L, float* out, int n, int* per_channel) {
-  I8IE_REQUIRE(L && out && per_channel, "null argument");
-  I8IE_REQUIRE(n == L->n, "n must be the layer's out features");
-  for (int j = 0; j < n; ++j) out[j] = L->pc ? L->sw_host[j] : L->s_w;
-  *per_channel = L->pc ? 1 : 0;
-  return I8IE_OK;
-}
-
-int i8ie_linear_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int n, int k, float s_w,
-                       i8ie_layer** out) {
-  return layer_create(ctx, false, qw_host, qb_host, n, k, 0, 0, 0, 1, 0, s_w, out);
-}
-
-int i8ie_conv2d_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh, int kw,
-                       int stride, int pad, float s_w, i8ie_layer** out) {
-  I8IE_REQUIRE(c > 0 && kh > 0 && kw > 0, "non-positive dimension");
-  I8IE_REQUIRE(stride > 0, "stride must be positive");
-  I8IE_REQUIRE(pad >= 0, "negative padding");
-  return layer_create(ctx, true, qw_host, qb_host, kc, c * kh * kw, c, kh, kw, stride, pad, s_w, out);
-}
-
-// groups: not in the reference (src/conv2d.cc:100-142 per group).  Argument checks come before any device call.
-static int check_groups(int kc, int c, int kh, int kw, int stride, int pad, int groups) {
-  I8IE_REQUIRE(kc > 0 && c > 0 && kh > 0 && kw > 0, "non-positive dimension");
-  I8IE_REQUIRE(stride > 0, "stride must be positive");
-  I8IE_REQUIRE(pad >= 0, "negative padding");
-  I8IE_REQUIRE(groups >= 1, "groups must be >= 1");
-  I8IE_REQUIRE(c % groups == 0 && kc % groups == 0, "groups must divide the input and the output channels");
-  I8IE_REQUIRE(groups <= 65535, "at most 65535 groups");
-  return I8IE_OK;
-}
-
-int i8ie_conv2d_create_grouped(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh, int kw,
-                               int stride, int pad, int groups, float s_w, i8ie_layer** out) {
-  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
-  if (groups == 1) return i8ie_conv2d_create(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, s_w, out);
-  return layer_create(ctx, true, qw_host, qb_host, kc, (c / groups) * kh * kw, c, kh, kw, stride, pad, s_w, out, groups);
-}
-
-int i8ie_conv2d_create_grouped_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c,
-                                           int kh, int kw, int stride, int pad, int groups, const float* s_w_host,
-                                           i8ie_layer** out) {
-  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
-  if (groups == 1) return i8ie_conv2d_create_per_channel(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, s_w_host, out);
-  I8IE_REQUIRE(out != nullptr, "bad argument");
-  I8IE_TRY(check_scales(s_w_host, kc));
-  i8ie_layer* L = nullptr;
-  I8IE_TRY(i8ie_conv2d_create_grouped(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, groups, 1.0f, &L));
-  return layer_make_per_channel(L, s_w_host, out);
-}
-
-int i8ie_layer_groups(const i8ie_layer* L, int* groups) {
-  I8IE_REQUIRE(L && groups, "null argument");
-  *groups = L->groups;
-  return I8IE_OK;
-}
-
-// dilation: not in the reference (src/conv2d.cc:100-142 per group with the kernel inflated by zeros).
-// Argument checks come before any device call.  A 1 x 1 kernel or dilation 1 is exactly the undilated layer (same route, same
-// kernels): it only remembers the number.  Anything else is route G with the dilation in the gather, for every groups >= 1.
-static int check_dilation(int dilation) {
-  I8IE_REQUIRE(dilation >= 1, "dilation must be >= 1");
-  return I8IE_OK;
-}
-static inline bool dilation_is_identity(int kh, int kw, int dilation) { return dilation == 1 || (kh == 1 && kw == 1); }
-
-int i8ie_conv2d_create_dilated(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh, int kw,
-                               int stride, int pad, int groups, int dilation, float s_w, i8ie_layer** out) {
-  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
-  I8IE_TRY(check_dilation(dilation));
-  if (dilation_is_identity(kh, kw, dilation)) {
-    I8IE_TRY(i8ie_conv2d_create_grouped(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, groups, s_w, out));
-    (*out)->dil_arg = dilation;
-    return I8IE_OK;
-  }
-  return layer_create(ctx, true, qw_host, qb_host, kc, (c / groups) * kh * kw, c, kh, kw, stride, pad, s_w, out, groups, -1, dilation);
-}
-
-int i8ie_conv2d_create_dilated_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh,
-                                           int kw, int stride, int pad, int groups, int dilation, const float* s_w_host,
-                                           i8ie_layer** out) {
-  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
-  I8IE_TRY(check_dilation(dilation));
-  I8IE_REQUIRE(out != nullptr, "bad argument");
-  I8IE_TRY(check_scales(s_w_host, kc));
-  i8ie_layer* L = nullptr;
-  I8IE_TRY(i8ie_conv2d_create_dilated(ctx, qw_host, qb_host, kc, c, kh, kw, stride, pad, groups, dilation, 1.0f, &L));
-  return layer_make_per_channel(L, s_w_host, out);
-}
-
-int i8ie_layer_dilation(const i8ie_layer* L, int* dilation) {
-  I8IE_REQUIRE(L && dilation, "null argument");
-  *dilation = L->dil_arg;
-  return I8IE_OK;
-}
-
-// the stateless form, as i8ie_conv2d_u8s8_grouped: a layer that is not an identity case reads the weights back and packs them
-// for this one call
-int i8ie_conv2d_u8s8_dilated(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int kh,
-                             int kw, int stride, int pad, int groups, int dilation, uint8_t zp_in, const int32_t* oc, float s_in,
-                             float s_w, float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
-  I8IE_TRY(check_groups(kc, c, kh, kw, stride, pad, groups));
-  I8IE_TRY(check_dilation(dilation));
-  if (dilation_is_identity(kh, kw, dilation))
-    return i8ie_conv2d_u8s8_grouped(ctx, in, n, c, h, w, qw, kc, kh, kw, stride, pad, groups, zp_in, oc, s_in, s_w, s_out, zp_out,
-                                    out, acc);
-  ConvGeom cg;
-  I8IE_TRY(conv_geom(c, h, w, kc, kh, kw, stride, pad, &cg, dilation));
-  I8IE_REQUIRE(ctx && in && qw && oc && out, "null argument");
-  I8IE_REQUIRE(n > 0, "non-positive batch");
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  const int Kg = (c / groups) * kh * kw;
-  std::vector<int8_t> qw_host((size_t)kc * Kg), qb_host((size_t)kc, 0);
-  I8IE_TRY(i8ie_memcpy_d2h(ctx, qw_host.data(), qw, qw_host.size()));
-  i8ie_layer* L = nullptr;
-  I8IE_TRY(layer_create(ctx, true, qw_host.data(), qb_host.data(), kc, Kg, c, kh, kw, stride, pad, s_w, &L, groups, -1, dilation));
-  return run_once(L, in, n, h, w, zp_in, oc, s_in, s_out, zp_out, out, acc);
-}
-
-// ConvTranspose2d: not in the reference (src/conv2d.cc:100-142 on the equivalent problem, include/i8ie_hip.h).  Argument
-// checks (i8ie_deconv_check_args) come before any device call.
-int i8ie_conv_transpose2d_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int k, int stride,
-                                 int pad, int output_pad, float s_w, i8ie_layer** out) {
-  I8IE_TRY(i8ie_deconv_check_args(kc, c, k, stride, pad, output_pad));
-  return layer_create(ctx, true, qw_host, qb_host, kc, c * k * k, c, k, k, stride, pad, s_w, out, 1, output_pad);
-}
-
-int i8ie_conv_transpose2d_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int k,
-                                             int stride, int pad, int output_pad, const float* s_w_host, i8ie_layer** out) {
-  I8IE_TRY(i8ie_deconv_check_args(kc, c, k, stride, pad, output_pad));
-  I8IE_REQUIRE(out != nullptr, "bad argument");
-  I8IE_TRY(check_scales(s_w_host, kc));
-  i8ie_layer* L = nullptr;
-  I8IE_TRY(i8ie_conv_transpose2d_create(ctx, qw_host, qb_host, kc, c, k, stride, pad, output_pad, 1.0f, &L));
-  return layer_make_per_channel(L, s_w_host, out);
-}
-
-// the stateless form: qw is the equivalent matrix on the device; it is read back and packed for this one call (a temporary
-// layer handle runs the call with the caller's oc[] and is destroyed), as i8ie_conv2d_u8s8_grouped does
-int i8ie_conv_transpose2d_u8s8(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int k,
-                               int stride, int pad, int output_pad, uint8_t zp_in, const int32_t* oc, float s_in, float s_w,
-                               float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
-  I8IE_TRY(i8ie_deconv_check_args(kc, c, k, stride, pad, output_pad));
-  I8IE_REQUIRE(ctx && in && qw && oc && out, "null argument");
-  I8IE_REQUIRE(n > 0, "non-positive batch");
-  ConvGeom cg;
-  I8IE_TRY(deconv_geom(c, h, w, kc, k, stride, pad, output_pad, &cg));
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<int8_t> qw_host((size_t)kc * cg.K), qb_host((size_t)kc, 0);
-  I8IE_TRY(i8ie_memcpy_d2h(ctx, qw_host.data(), qw, qw_host.size()));
-  i8ie_layer* L = nullptr;
-  I8IE_TRY(i8ie_conv_transpose2d_create(ctx, qw_host.data(), qb_host.data(), kc, c, k, stride, pad, output_pad, s_w, &L));
-  return run_once(L, in, n, h, w, zp_in, oc, s_in, s_out, zp_out, out, acc);
-}
-
-int i8ie_layer_set_output_qparams(i8ie_layer* L, float s_out, uint8_t zp_out) {
-  I8IE_REQUIRE(L != nullptr, "null layer");
-  L->s_out = s_out;
-  L->zp_out = zp_out;
-  L->ms_valid = false;  // (per-channel multipliers depend on s_out)
-  return I8IE_OK;
-}
-
-int i8ie_layer_get_output_qparams(const i8ie_layer* L, float* s_out, uint8_t* zp_out) {
-  I8IE_REQUIRE(L && s_out && zp_out, "null argument");
-  *s_out = L->s_out;
-  *zp_out = L->zp_out;
-  return I8IE_OK;
-}
-
-int i8ie_layer_preferred_layout(const i8ie_layer* L, int* layout) {
-  I8IE_REQUIRE(L && layout, "null argument");
-  const bool fast = L->conv && L->path != PATH_F && !force_fallback(L->ctx) && (L->n % 16 == 0);
-  *layout = fast ? I8IE_LAYOUT_NHWC : I8IE_LAYOUT_NCHW;
-  return I8IE_OK;
-}
-
-int i8ie_layer_padding(const i8ie_layer* L, int* pad) {
-  I8IE_REQUIRE(L && pad, "null argument");
-  // (a transposed layer reads no border; a dilated one needs none and accepts any: its taps are bounds-checked, and a
-  // border of `pad` pixels around a small map would multiply its bytes)
-  *pad = (L->conv && L->path != PATH_T && L->dil == 1) ? L->pad : 0;
-  return I8IE_OK;
 }
 
 // ---- the layer forward: validate -> geometry -> plan -> peel -> route -----------------------------------
@@ -1108,7 +534,7 @@ static int forward_linear(i8ie_layer* L, const ConvRequest& q) {
       return forward_linear(L, r);
     }
     if (L->Bperm == nullptr || L->perm_c != L->K / hw || L->perm_hw != hw) {
-      if (L->Bperm == nullptr) I8IE_TRY(i8ie_malloc(ctx, (size_t)L->Npad * L->Kpad, (void**)&L->Bperm));
+      if (L->Bperm == nullptr) I8IE_TRY(i8ie_layer_buffer(L, (void**)&L->Bperm, (size_t)L->Npad * L->Kpad));
       I8IE_TRY(i8ie_launch_permute_k(ctx, L->Bpack, L->Bperm, L->Npad, L->Kpad, L->K, L->K / hw, hw));
       L->perm_c = L->K / hw;
       L->perm_hw = hw;
@@ -1313,71 +739,6 @@ int i8ie_layer_forward_f32_input(i8ie_layer* L, const float* in, int m, int h, i
 int i8ie_layer_forward(i8ie_layer* L, const uint8_t* in, int m, int h, int w, float s_in, uint8_t zp_in, uint8_t* out,
                        int32_t* acc) {
   return i8ie_layer_forward_fused(L, in, I8IE_LAYOUT_NCHW, 0, m, h, w, s_in, zp_in, 0, out, I8IE_LAYOUT_NCHW, 0, acc);
-}
-
-int i8ie_layer_destroy(i8ie_layer* L) {
-  if (!L) return I8IE_OK;
-  i8ie_ctx* ctx = L->ctx;
-  i8ie_free(ctx, L->qw);
-  i8ie_free(ctx, L->qb);
-  i8ie_free(ctx, L->Bpack);
-  i8ie_free(ctx, L->Bpack2);
-  if (L->Bstem) i8ie_free(ctx, L->Bstem);
-  for (const I8ieWCache::Ent& e : L->wc.ents) i8ie_free(ctx, e.buf);
-  i8ie_free(ctx, L->wsum);
-  i8ie_free(ctx, L->oc);
-  i8ie_free(ctx, L->ocp);
-  if (L->Bperm) i8ie_free(ctx, L->Bperm);
-  i8ie_free(ctx, L->biasf);
-  if (L->swv) i8ie_free(ctx, L->swv);
-  if (L->msv) i8ie_free(ctx, L->msv);
-  delete L;
-  return I8IE_OK;
-}
-
-// quantize_weight, src/layer.cc:6-26 (host side, one-shot at convert())
-int i8ie_quantize_weight(const float* w, int64_t nw, const float* b, int64_t nb, int8_t* qw, int8_t* qb,
-                         float* scale_out) {
-  I8IE_REQUIRE(w && b && qw && qb && scale_out, "null argument");
-  I8IE_REQUIRE(nw > 0 && nb > 0, "empty tensor");
-  float mx = -3.402823466e+38f, mn = 3.402823466e+38f;
-  for (int64_t i = 0; i < nw; ++i) {
-    mn = w[i] < mn ? w[i] : mn;
-    mx = w[i] > mx ? w[i] : mx;
-  }
-  for (int64_t i = 0; i < nb; ++i) {
-    mn = b[i] < mn ? b[i] : mn;
-    mx = b[i] > mx ? b[i] : mx;
-  }
-  const float s = (mx - mn) / 127;
-  for (int64_t i = 0; i < nw; ++i) qw[i] = (int8_t)(int32_t)(w[i] / s);
-  for (int64_t i = 0; i < nb; ++i) qb[i] = (int8_t)(int32_t)(b[i] / s);
-  *scale_out = s;
-  return I8IE_OK;
-}
-
-// per-output-channel quantize (DESIGN.md "Per-channel weight scales"): row j = w[j * row_len ..], bias b[j] (may be null:
-// zero); symmetric max-abs over the row and its bias, round half to even, clamp to [-127, 127]
-int i8ie_quantize_weight_per_channel(const float* w, int rows, int64_t row_len, const float* b, int8_t* qw, int8_t* qb,
-                                     float* scales) {
-  I8IE_REQUIRE(w && qw && qb && scales, "null argument");
-  I8IE_REQUIRE(rows > 0 && row_len > 0, "empty tensor");
-  auto q8 = [](float x, float s) {
-    float r = std::nearbyint(x / s);  // (the default rounding mode: to nearest, ties to even)
-    r = r > 127.0f ? 127.0f : (r < -127.0f ? -127.0f : r);
-    return (int8_t)(int32_t)r;
-  };
-  for (int j = 0; j < rows; ++j) {
-    const float* row = w + (size_t)j * row_len;
-    const float bj = b ? b[j] : 0.0f;
-    float a = std::fabs(bj);
-    for (int64_t k = 0; k < row_len; ++k) a = std::fabs(row[k]) > a ? std::fabs(row[k]) : a;
-    const float s = a == 0.0f ? 1.0f : a / 127.0f;
-    for (int64_t k = 0; k < row_len; ++k) qw[(size_t)j * row_len + k] = q8(row[k], s);
-    qb[j] = q8(bj, s);
-    scales[j] = s;
-  }
-  return I8IE_OK;
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// i8ie_stem.h -- the first-stage kernel of i8ie_stem.hip as seen by i8ie_layer.hip
+// i8ie_stem.h -- the first-stage kernel of i8ie_stem.hip as seen by the layer handle: i8ie_layer.hip plans and launches it,
+// i8ie_layer_create.hip packs its weights (i8ie_stem_kpad / i8ie_stem_kindex)
 #pragma once
 #include <cstddef>
 #include <cstdint>
