@@ -4,19 +4,12 @@ The reference's one non-linearity is relu; every other activation is defined in 
 from the reference's own dequantize (src/quantize_utils.cc:38-42) and down_scale's clamp / truncation (:27-36) around f, IEEE
 fp32 with one rounding per operation.  act_f32 and table spell that in numpy with an explicit float32 cast between the steps
 (sigmoid and tanh through Python's math.exp / math.tanh in float64, the libm the host code calls, then one rounding to
-float32), forward() walks a spec with the act op over the oracle, fp32_qparams() stands in for calibration with a numpy FP32
-forward, and the four new C symbols get their ctypes signatures here (tests/abi.py binds the rest)."""
+float32), nontrivial() holds the limits the network tests put on the Activations' expected bytes, and the four new C symbols
+get their ctypes signatures here (tests/abi.py binds the rest)."""
 import ctypes as C
 import math
 
 import numpy as np
-
-import concat_ref as cr
-import f64_ref
-import grouped_ref as gr
-import orc
-import pc_pipeline as pcp
-import pipeline
 
 f32 = np.float32
 KINDS = {"relu6": 0, "leaky_relu": 1, "hardsigmoid": 2, "hardswish": 3, "sigmoid": 4, "tanh": 5}
@@ -56,7 +49,7 @@ def _exp(v):
 
 
 def act_f64(kind, x, param=0.0):
-    """the real-valued function in float64 (the yardstick of the FP32 entry's sigmoid / tanh, and the FP32 stand-in forward)"""
+    """the real-valued function in float64 (the yardstick of the FP32 entry's sigmoid / tanh, and of spec_ref.fp32_qparams)"""
     x = np.asarray(x, np.float64)
     with np.errstate(all="ignore"):
         if kind == "relu6":
@@ -99,113 +92,13 @@ def act_of(op):
     return op[2], f32(op[3] if len(op) > 3 else (0.01 if op[2] == "leaky_relu" else 0.0))
 
 
-def forward(networks_entry, x, qlayers, out_qparams, join_qparams, per_channel=False, trace=None):
-    """concat_ref.forward with ("act", attr, kind[, param]).  join_qparams: {attr: (scale, zp)} of the Adds, Concats and
-    Activations.  trace: a dict that receives {attr: u8 output} of every Activation.  Returns float32 logits."""
-    layers, spec, _ = networks_entry
-
-    def run(ops, cur, saved):
-        q, s, zp = cur
-        for op in ops:
-            if op[0] == "layer":
-                L = layers[op[1]]
-                qw, qb, s_w = qlayers[op[1]]
-                s_out, zp_out = out_qparams[op[1]]
-                s_out = f32(s_out)
-                if L[0] == "conv":
-                    f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
-                    q, _ = f(q, qw, qb, gr.layer_groups(L), L[4], L[5], s, zp, s_w, s_out, zp_out)
-                elif per_channel:
-                    q, _, _ = pcp.linear_pc(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-                else:
-                    q, _, _ = orc.linear(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-                s, zp = s_out, int(zp_out)
-            elif op[0] == "relu":
-                q = orc.relu(q, zp)
-            elif op[0] == "pool":
-                q = orc.max_pool2d(q, op[1], op[2])
-            elif op[0] == "avgpool":
-                q = cr.apr.avg_pool2d_u8(q, op[1], op[1], op[2])
-            elif op[0] == "gap":
-                q = cr.apr.global_avg_pool2d_u8(q)
-            elif op[0] == "save":
-                saved[op[1]] = (q, s, zp)
-            elif op[0] == "branch":
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            elif op[0] == "add":
-                q2, s2, zp2 = saved[op[2]]
-                s_out, zp_out = join_qparams[op[1]]
-                q = cr.ar.add_u8(q, zp, s, q2, zp2, s2, f32(s_out), int(zp_out), relu=False)
-                s, zp = f32(s_out), int(zp_out)
-            elif op[0] == "concat":
-                s_out, zp_out = join_qparams[op[1]]
-                q = cr.cat_u8([(q, s, zp)] + [saved[t] for t in op[2]], f32(s_out), int(zp_out))
-                s, zp = f32(s_out), int(zp_out)
-            elif op[0] == "act":
-                kind, param = act_of(op)
-                s_out, zp_out = join_qparams[op[1]]
-                q = act_u8(q, kind, param, s, zp, f32(s_out), int(zp_out))
-                s, zp = f32(s_out), int(zp_out)
-                if trace is not None:
-                    trace[op[1]] = q
-            else:
-                q = q.reshape(-1, op[1])
-        return q, s, zp
-
-    q0 = orc.quantize(x, pipeline.INPUT_SCALE, pipeline.INPUT_ZP)
-    q, s, zp = run(spec, (q0, pipeline.INPUT_SCALE, pipeline.INPUT_ZP), {})
-    return orc.dequantize(q, s, zp)
-
-
-def range_qparams(lo, hi):
-    """the calibrator's rule (src/calibrator.cc:24-37 at quantile 1) on a real-valued range"""
-    lo, hi = min(float(lo), 0.0), max(float(hi), 0.0)
-    if hi - lo < 1e-12:
-        return f32(1.0), 0
-    zp = int(255 * (0 - lo) / (hi - lo))
-    scale = (hi - lo) / 255 if zp == 0 else (0 - lo) / zp
-    return f32(scale), zp
-
-
-def fp32_qparams(networks_entry, state_dict, x):
-    """Stand-in for calibration without a GPU: a numpy forward in float64 over the FP32 weights; the output range of every
-    layer, Add and Activation gives its (scale, zero_point) by the calibrator's rule.  Returns (layer qparams, join qparams)."""
-    layers, spec, _ = networks_entry
-    qp, jqp = {}, {}
-    saved = {}
-    v = np.asarray(x, np.float64)
-    for op in spec:
-        if op[0] == "layer":
-            L = layers[op[1]]
-            w, b = state_dict[op[1] + ".weight"].astype(np.float64), state_dict[op[1] + ".bias"].astype(np.float64)
-            v = gr.conv2d_f64(v, w, b, gr.layer_groups(L), L[4], L[5]) if L[0] == "conv" else f64_ref.linear(v.reshape(v.shape[0], -1), w, b)
-            qp[op[1]] = range_qparams(v.min(), v.max())
-        elif op[0] == "act":
-            kind, param = act_of(op)
-            v = act_f64(kind, v, param)
-            jqp[op[1]] = range_qparams(v.min(), v.max())
-        elif op[0] == "save":
-            saved[op[1]] = v
-        elif op[0] == "add":
-            v = v + saved[op[2]]
-            jqp[op[1]] = range_qparams(v.min(), v.max())
-        elif op[0] == "gap":
-            v = v.mean(axis=(2, 3), keepdims=True)
-        elif op[0] == "flatten":
-            v = v.reshape(-1, op[1])
-        else:
-            raise ValueError("fp32_qparams: op %r" % (op,))
-    return qp, jqp
-
-
-# synthetic weights, inputs and calibration stand-in of the three networks, fixed here: with them every Activation's oracle
-# output takes at least MIN_DISTINCT byte values and no value holds more than MAX_SHARE of its bytes (tests/test_act_host.py)
-WEIGHT_SEED, CALIB_SEED, CALIB_IMAGES, INPUT_SEED = 42, 99, 4, 5
+# with the seeds of tests/spec_ref.py every Activation's oracle output takes at least MIN_DISTINCT byte values and no value
+# holds more than MAX_SHARE of its bytes (tests/test_act_host.py)
 MIN_DISTINCT, MAX_SHARE = 16, 0.9
 
 
 def nontrivial(trace):
-    """{attr: (distinct byte values, largest share of one value)} of a forward()'s trace, asserted against the two limits"""
+    """{attr: (distinct byte values, largest share of one value)} of the Activations' traced bytes, asserted against the two limits"""
     out = {}
     for attr, q in trace.items():
         counts = np.bincount(np.asarray(q, np.uint8).ravel(), minlength=256)

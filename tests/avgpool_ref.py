@@ -4,17 +4,10 @@ The reference has no average pool.  Everything but the reduction follows its max
 NCHW, window kh x kw, one stride, floor output size, no padding, the input's (scale, zero_point) carried through.
 avg_pool2d_u8 is the integer definition q = (S + n // 2) // n in int64, avg_pool2d_f32 the FP32 one (fp32 sum in window
 order, rows outer and columns inner, then one fp32 division), avg_pool2d_f64 the float64 mean the FP32 kernel is bounded
-against.  forward() walks a residual spec with the two new ops over the oracle, and the three new C symbols get their
-ctypes signatures here (tests/abi.py binds the rest)."""
+against.  The three new C symbols get their ctypes signatures here (tests/abi.py binds the rest)."""
 import ctypes as C
 
 import numpy as np
-
-import add_ref as ar
-import grouped_ref as gr
-import orc
-import pc_pipeline as pcp
-import pipeline
 
 f32 = np.float32
 
@@ -68,52 +61,6 @@ def avg_pool2d_f64(x, kh, kw, s):
         tot = sum(_windows(x, kh, kw, s))
         mag = sum(_windows(np.abs(x), kh, kw, s))
     return tot / (kh * kw), mag / (kh * kw)
-
-
-def forward(networks_entry, x, qlayers, out_qparams, add_qparams, per_channel=False):
-    """add_ref.forward with ("avgpool", k, s) and ("gap",).  Returns float32 logits."""
-    layers, spec, _ = networks_entry
-
-    def run(ops, cur, saved):
-        q, s, zp = cur
-        for op in ops:
-            if op[0] == "layer":
-                L = layers[op[1]]
-                qw, qb, s_w = qlayers[op[1]]
-                s_out, zp_out = out_qparams[op[1]]
-                s_out = f32(s_out)
-                if L[0] == "conv":
-                    f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
-                    q, _ = f(q, qw, qb, gr.layer_groups(L), L[4], L[5], s, zp, s_w, s_out, zp_out)
-                elif per_channel:
-                    q, _, _ = pcp.linear_pc(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-                else:
-                    q, _, _ = orc.linear(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-                s, zp = s_out, int(zp_out)
-            elif op[0] == "relu":
-                q = orc.relu(q, zp)
-            elif op[0] == "pool":
-                q = orc.max_pool2d(q, op[1], op[2])
-            elif op[0] == "avgpool":
-                q = avg_pool2d_u8(q, op[1], op[1], op[2])
-            elif op[0] == "gap":
-                q = global_avg_pool2d_u8(q)
-            elif op[0] == "save":
-                saved[op[1]] = (q, s, zp)
-            elif op[0] == "branch":
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            elif op[0] == "add":
-                q2, s2, zp2 = saved[op[2]]
-                s_out, zp_out = add_qparams[op[1]]
-                q = ar.add_u8(q, zp, s, q2, zp2, s2, f32(s_out), int(zp_out), relu=False)
-                s, zp = f32(s_out), int(zp_out)
-            else:
-                q = q.reshape(-1, op[1])
-        return q, s, zp
-
-    q0 = orc.quantize(x, pipeline.INPUT_SCALE, pipeline.INPUT_ZP)
-    q, s, zp = run(spec, (q0, pipeline.INPUT_SCALE, pipeline.INPUT_ZP), {})
-    return orc.dequantize(q, s, zp)
 
 
 # ---- ctypes signatures of the average-pool entry points ------------------------------------------------------------

@@ -3,18 +3,10 @@
 The reference has no concat; the definition is a composition of its own dequantize (src/quantize_utils.cc:38-42) and
 down_scale's clamp / truncation (src/quantize_utils.cc:27-36) in IEEE fp32, one rounding per operation, plus the copy rule:
 an input whose (scale bits, zero point) equal the result's is not touched.  cat_u8 spells it in numpy with an explicit float32
-cast between the steps, forward() walks a spec with the concat op over the oracle, and the three new C symbols get their
-ctypes signatures here (tests/abi.py binds the rest)."""
+cast between the steps, and the three new C symbols get their ctypes signatures here (tests/abi.py binds the rest)."""
 import ctypes as C
 
 import numpy as np
-
-import add_ref as ar
-import avgpool_ref as apr
-import grouped_ref as gr
-import orc
-import pc_pipeline as pcp
-import pipeline
 
 f32 = np.float32
 MAX_INPUTS = 8
@@ -48,59 +40,6 @@ def cat_u8(inputs, s_out, zp_out, relu=False):
     if relu:
         out = np.maximum(out, np.uint8(zp_out))
     return out
-
-
-def forward(networks_entry, x, qlayers, out_qparams, join_qparams, per_channel=False, trace=None):
-    """avgpool_ref.forward with ("concat", attr, [tags]).  join_qparams: {attr: (scale, zp)} of the Adds and Concats.
-    trace: a dict that receives {attr: u8 output} of every Concat.  Returns float32 logits."""
-    layers, spec, _ = networks_entry
-
-    def run(ops, cur, saved):
-        q, s, zp = cur
-        for op in ops:
-            if op[0] == "layer":
-                L = layers[op[1]]
-                qw, qb, s_w = qlayers[op[1]]
-                s_out, zp_out = out_qparams[op[1]]
-                s_out = f32(s_out)
-                if L[0] == "conv":
-                    f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
-                    q, _ = f(q, qw, qb, gr.layer_groups(L), L[4], L[5], s, zp, s_w, s_out, zp_out)
-                elif per_channel:
-                    q, _, _ = pcp.linear_pc(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-                else:
-                    q, _, _ = orc.linear(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-                s, zp = s_out, int(zp_out)
-            elif op[0] == "relu":
-                q = orc.relu(q, zp)
-            elif op[0] == "pool":
-                q = orc.max_pool2d(q, op[1], op[2])
-            elif op[0] == "avgpool":
-                q = apr.avg_pool2d_u8(q, op[1], op[1], op[2])
-            elif op[0] == "gap":
-                q = apr.global_avg_pool2d_u8(q)
-            elif op[0] == "save":
-                saved[op[1]] = (q, s, zp)
-            elif op[0] == "branch":
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            elif op[0] == "add":
-                q2, s2, zp2 = saved[op[2]]
-                s_out, zp_out = join_qparams[op[1]]
-                q = ar.add_u8(q, zp, s, q2, zp2, s2, f32(s_out), int(zp_out), relu=False)
-                s, zp = f32(s_out), int(zp_out)
-            elif op[0] == "concat":
-                s_out, zp_out = join_qparams[op[1]]
-                q = cat_u8([(q, s, zp)] + [saved[t] for t in op[2]], f32(s_out), int(zp_out))
-                s, zp = f32(s_out), int(zp_out)
-                if trace is not None:
-                    trace[op[1]] = q
-            else:
-                q = q.reshape(-1, op[1])
-        return q, s, zp
-
-    q0 = orc.quantize(x, pipeline.INPUT_SCALE, pipeline.INPUT_ZP)
-    q, s, zp = run(spec, (q0, pipeline.INPUT_SCALE, pipeline.INPUT_ZP), {})
-    return orc.dequantize(q, s, zp)
 
 
 # ---- ctypes signatures of the concat entry points ------------------------------------------------------------------

@@ -5,21 +5,16 @@ positions inserted between neighbouring pixels and k - 1 - p (+ output_padding a
 position holding zp_in (0.0 in FP32), with the kernel flipped and its channel axes swapped.  equivalent_input /
 equivalent_weight build that problem in numpy and deconv_u8 / deconv_u8_pc hand it to orc.conv2d / pc_pipeline.conv2d_pc.
 scatter() is the independent definition (every input pixel adds its k x k patch into the output) in float64 or exact
-integers.  Also here: the ctypes signatures of the new symbols, the oracle composition of a spec network with "deconv"
-layers, the case list of the GPU tests with the launcher's dispatch restated, and the runner of a case through a handle."""
+integers.  Also here: the ctypes signatures of the new symbols, tracer() for the up-convs' bytes in a spec_ref.forward, the
+case list of the GPU tests with the launcher's dispatch restated, and the runner of a case through a handle."""
 import collections
 import ctypes as C
 
 import numpy as np
 
-import act_ref as acr
-import concat_ref as cr
 import f64_ref
-import grouped_ref as gr
-import mul_ref as mr
 import orc
 import pc_pipeline as pcp
-import pipeline
 
 f32 = np.float32
 
@@ -82,141 +77,13 @@ def equivalent_f64(x, w, b, s, p, op):
 
 
 # ---- spec networks -----------------------------------------------------------------------------------------------------
-def quantize_layers(networks_entry, state_dict, per_channel=False):
-    """convert()'s rules: a "deconv" layer is quantised as its equivalent kernel W~ [out, in, k, k] (per tensor over weight and
-    bias; per channel per row of W~); every other layer as grouped_ref.quantize_layers does"""
-    layers = networks_entry[0]
-    sd = dict(state_dict)
-    for attr, L in layers.items():
-        if L[0] == "deconv":
-            sd[attr + ".weight"] = equivalent_weight(state_dict[attr + ".weight"])
-    return gr.quantize_layers(networks_entry, sd, per_channel)
+def tracer(layers, into):
+    """a trace callback for spec_ref.forward: into[attr] = the output bytes of every "deconv" layer"""
+    def trace(op, out, operands):
+        if op[0] == "layer" and layers[op[1]][0] == "deconv":
+            into[op[1]] = out[0]
 
-
-def forward(networks_entry, x, qlayers, out_qparams, join_qparams, per_channel=False, trace=None):
-    """mul_ref.forward with ("deconv", in, out, k, stride, pad, output_pad) layers: each is what it is by definition, the
-    reference convolution (stride 1, padding 0) of the equivalent input with the equivalent kernel.  trace: a dict that
-    receives {attr: output bytes} of every deconv layer."""
-    layers, spec, shape = networks_entry
-
-    def run(ops, cur, saved):
-        seg = []
-
-        def flush(cur):
-            if seg:
-                cur = _run_segment((layers, list(seg), shape), cur, saved, qlayers, out_qparams, join_qparams, per_channel)
-                del seg[:]
-            return cur
-
-        for op in ops:
-            if op[0] == "layer" and layers[op[1]][0] == "deconv":
-                q, s, zp = flush(cur)
-                L = layers[op[1]]
-                qw, qb, s_w = qlayers[op[1]]
-                s_out, zp_out = out_qparams[op[1]]
-                f = deconv_u8_pc if per_channel else deconv_u8
-                q, _ = f(q, qw, qb, L[4], L[5], L[6], s, zp, s_w, f32(s_out), int(zp_out))
-                if trace is not None:
-                    trace[op[1]] = q
-                cur = (q, f32(s_out), int(zp_out))
-            elif op[0] == "branch":
-                cur = flush(cur)
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            else:
-                seg.append(op)
-        return flush(cur)
-
-    q0 = orc.quantize(x, pipeline.INPUT_SCALE, pipeline.INPUT_ZP)
-    q, s, zp = run(spec, (q0, pipeline.INPUT_SCALE, pipeline.INPUT_ZP), {})
-    return orc.dequantize(q, s, zp)
-
-
-def _run_segment(entry, cur, saved, qlayers, out_qparams, join_qparams, per_channel):
-    """a run of ops without deconv layers and branches: mul_ref.forward's own loop, restated on a tensor that is already
-    quantised (the wrapped function quantises its input and dequantises its result)"""
-    layers, ops, _ = entry
-    q, s, zp = cur
-    for op in ops:
-        if op[0] == "layer":
-            L = layers[op[1]]
-            qw, qb, s_w = qlayers[op[1]]
-            s_out, zp_out = out_qparams[op[1]]
-            s_out = f32(s_out)
-            if L[0] == "conv":
-                f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
-                q, _ = f(q, qw, qb, gr.layer_groups(L), L[4], L[5], s, zp, s_w, s_out, zp_out)
-            elif per_channel:
-                q, _, _ = pcp.linear_pc(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-            else:
-                q, _, _ = orc.linear(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-            s, zp = s_out, int(zp_out)
-        elif op[0] == "relu":
-            q = orc.relu(q, zp)
-        elif op[0] == "pool":
-            q = orc.max_pool2d(q, op[1], op[2])
-        elif op[0] == "avgpool":
-            q = cr.apr.avg_pool2d_u8(q, op[1], op[1], op[2])
-        elif op[0] == "gap":
-            q = cr.apr.global_avg_pool2d_u8(q)
-        elif op[0] == "save":
-            saved[op[1]] = (q, s, zp)
-        elif op[0] == "add":
-            q2, s2, zp2 = saved[op[2]]
-            s_out, zp_out = join_qparams[op[1]]
-            q = cr.ar.add_u8(q, zp, s, q2, zp2, s2, f32(s_out), int(zp_out), relu=False)
-            s, zp = f32(s_out), int(zp_out)
-        elif op[0] == "mul":
-            q2, s2, zp2 = saved[op[2]]
-            s_out, zp_out = join_qparams[op[1]]
-            q = mr.mul_u8(q, zp, s, q2, zp2, s2, f32(s_out), int(zp_out), relu=False)
-            s, zp = f32(s_out), int(zp_out)
-        elif op[0] == "concat":
-            s_out, zp_out = join_qparams[op[1]]
-            q = cr.cat_u8([(q, s, zp)] + [saved[t] for t in op[2]], f32(s_out), int(zp_out))
-            s, zp = f32(s_out), int(zp_out)
-        elif op[0] == "act":
-            kind, param = acr.act_of(op)
-            s_out, zp_out = join_qparams[op[1]]
-            q = acr.act_u8(q, kind, param, s, zp, f32(s_out), int(zp_out))
-            s, zp = f32(s_out), int(zp_out)
-        else:
-            q = q.reshape(-1, op[1])
-    return q, s, zp
-
-
-def fp32_qparams(networks_entry, state_dict, x):
-    """stand-in for calibration without a GPU: a float64 forward over the FP32 weights; every layer's and Concat's output
-    range gives its (scale, zero_point) by the calibrator's rule.  Returns (layer qparams, join qparams)."""
-    layers, spec, _ = networks_entry
-    qp, jqp = {}, {}
-
-    def run(ops, v, saved):
-        for op in ops:
-            if op[0] == "layer":
-                L = layers[op[1]]
-                w, b = state_dict[op[1] + ".weight"].astype(np.float64), state_dict[op[1] + ".bias"].astype(np.float64)
-                v = scatter(v, w, b, L[4], L[5], L[6]) if L[0] == "deconv" else gr.conv2d_f64(v, w, b, gr.layer_groups(L), L[4], L[5])
-                qp[op[1]] = acr.range_qparams(v.min(), v.max())
-            elif op[0] == "relu":
-                v = np.maximum(v, 0.0)
-            elif op[0] == "pool":
-                v = f64_ref.max_pool2d(v, op[1], op[2])
-            elif op[0] == "save":
-                saved[op[1]] = v
-            elif op[0] == "branch":
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            elif op[0] == "concat":
-                v = np.concatenate([v] + [saved[t] for t in op[2]], axis=1)
-                jqp[op[1]] = acr.range_qparams(v.min(), v.max())
-            else:
-                raise ValueError("fp32_qparams: op %r" % (op,))
-        return v
-
-    run(spec, np.asarray(x, np.float64), {})
-    return qp, jqp
-
-
-WEIGHT_SEED, CALIB_SEED, CALIB_IMAGES, INPUT_SEED = 42, 99, 4, 5
+    return trace
 
 
 # ---- ctypes signatures of the new entry points -----------------------------------------------------------------------------

@@ -11,8 +11,7 @@ K = (c / groups) k k in the bound.
   dilated_handles(...)   inside, the helpers of tests/abi.py drive dilated handles: they are handed the INFLATED weights (so
                          that the geometry they work out is the layer's) and the patched create makes the dilated layer from
                          the compact ones
-  forward(...)           a network with dilated layers over the existing reference forward (upsample_ref.forward): the
-                         dilated layers' quantised weights inflated, their tuples rewritten to dense-kernel convs
+  layer_dilation(L)      the optional 8th element of a conv tuple; spec_ref.forward inflates such a layer's quantised weights
   CASES / dispatch / reference   the GPU case lists of tests/test_gpu_dilated.py, checked by tests/test_dilated_host.py"""
 import collections
 import contextlib
@@ -21,7 +20,6 @@ import ctypes as C
 import numpy as np
 
 import grouped_ref as gr
-import upsample_ref as ur
 
 
 def inflate(w, d):
@@ -86,30 +84,6 @@ def dilated_handles(lib, qw, groups, dilation, scales=None):
 # ---- spec networks --------------------------------------------------------------------------------------------------------
 def layer_dilation(L):
     return L[7] if len(L) > 7 else 1
-
-
-def dense_entry(networks_entry):
-    """the entry with every dilated conv tuple rewritten to the conv of its inflated kernel (dilation 1)"""
-    layers, spec, shape = networks_entry
-    out = {}
-    for a, L in layers.items():
-        if L[0] == "conv" and layer_dilation(L) > 1:
-            d = L[7]
-            L = ("conv", L[1], L[2], d * (L[3] - 1) + 1, L[4], L[5], gr.layer_groups(L))
-        out[a] = L
-    return out, spec, shape
-
-
-def forward(networks_entry, x, qlayers, out_qparams, join_qparams, per_channel=False, trace=None):
-    """upsample_ref.forward of the dense entry, the quantised weights of the dilated layers inflated: the expected output is
-    the existing oracle composition.  qlayers: the COMPACT weights as convert() quantises them."""
-    layers = networks_entry[0]
-    ql = {}
-    for a, (qw, qb, s_w) in qlayers.items():
-        L = layers[a]
-        d = layer_dilation(L) if L[0] == "conv" else 1
-        ql[a] = (inflate(qw, d) if d > 1 else qw, qb, s_w)
-    return ur.forward(dense_entry(networks_entry), x, ql, out_qparams, join_qparams, per_channel, trace)
 
 
 # ---- the GPU cases --------------------------------------------------------------------------------------------------------

@@ -12,7 +12,6 @@ import numpy as np
 import f64_ref
 import orc
 import pc_pipeline as pcp
-import pipeline
 
 
 def _split(q_in, qw, groups):
@@ -73,43 +72,6 @@ def conv2d_f64_mag(x, w, b, groups, stride, pad):
 
 def layer_groups(L):
     return L[6] if len(L) > 6 else 1
-
-
-def forward(networks_entry, x, qlayers, out_qparams, per_channel=False):
-    """oracle/pipeline.forward with the optional 7th element `groups` of a conv tuple honoured (alexnet_paper).
-    qlayers: {attr: (qw, qb, s_w)}, s_w a scalar or, per_channel, float32 [out]."""
-    layers, spec, _ = networks_entry
-    q = orc.quantize(x, pipeline.INPUT_SCALE, pipeline.INPUT_ZP)
-    s, zp = pipeline.INPUT_SCALE, pipeline.INPUT_ZP
-    for op in spec:
-        if op[0] == "layer":
-            L = layers[op[1]]
-            qw, qb, s_w = qlayers[op[1]]
-            s_out, zp_out = out_qparams[op[1]]
-            s_out = np.float32(s_out)
-            if L[0] == "conv":
-                f = conv2d_grouped_pc if per_channel else conv2d_grouped
-                q, _ = f(q, qw, qb, layer_groups(L), L[4], L[5], s, zp, s_w, s_out, zp_out)
-            elif per_channel:
-                q, _, _ = pcp.linear_pc(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-            else:
-                q, _, _ = orc.linear(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-            s, zp = s_out, int(zp_out)
-        elif op[0] == "relu":
-            q = orc.relu(q, zp)
-        elif op[0] == "pool":
-            q = orc.max_pool2d(q, op[1], op[2])
-        else:
-            q = q.reshape(-1, op[1])
-    return orc.dequantize(q, s, zp)
-
-
-def quantize_layers(networks_entry, state_dict, per_channel=False):
-    """convert()'s rules on the (grouped) weight tensors as they stand: per-tensor joint min/max over the whole weight and
-    the bias; per-channel per row of the [kc, Cg*kh*kw] matrix"""
-    if per_channel:
-        return pcp.quantize_layers_pc(networks_entry, state_dict)
-    return pipeline.quantize_layers(networks_entry, state_dict)
 
 
 # ---- ctypes signatures of the grouped entry points --------------------------------------------------------------

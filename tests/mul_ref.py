@@ -3,20 +3,14 @@
 The reference has no multiply; the definition is a composition of its own dequantize (src/quantize_utils.cc:38-42) and
 down_scale's clamp / truncation (src/quantize_utils.cc:27-36) in IEEE fp32, one rounding per operation.  mul_u8 spells it in
 numpy with an explicit float32 cast between the steps (a gate broadcasts as numpy broadcasts [n, c, 1, 1]), QP is the list of
-quantisation parameter sets the exhaustive tests run over, forward() walks a spec with the mul op (and every op the older
-*_ref helpers know, through their own primitives) over the oracle, fp32_qparams() stands in for calibration with a numpy
-forward, and the three new C symbols get their ctypes signatures here (tests/abi.py binds the rest)."""
+quantisation parameter sets the exhaustive tests run over, tracer() and nontrivial() are what the network tests look at in
+a spec_ref.forward (gate bytes, the floor of a relu behind a Mul), and the three new C symbols get their ctypes signatures
+here (tests/abi.py binds the rest)."""
 import ctypes as C
 
 import numpy as np
 
-import act_ref as acr
-import concat_ref as cr
-import f64_ref
-import grouped_ref as gr
 import orc
-import pc_pipeline as pcp
-import pipeline
 
 f32 = np.float32
 
@@ -109,124 +103,28 @@ def relu_follows(spec):
     return out
 
 
-def forward(networks_entry, x, qlayers, out_qparams, join_qparams, per_channel=False, trace=None):
-    """act_ref.forward with ("mul", attr, tag).  join_qparams: {attr: (scale, zp)} of the Adds, Muls, Concats and Activations.
-    trace: a dict that receives {attr: (gate bytes or None, output bytes with a directly following relu applied, the relu's
-    floor or None)} of every Mul.  Returns float32 logits."""
-    layers, spec, _ = networks_entry
+def tracer(spec, into):
+    """a trace callback for spec_ref.forward: into[attr] = (gate bytes or None, output bytes with a directly following relu
+    applied, the relu's floor or None) of every Mul of the spec"""
     floors = relu_follows(spec)
 
-    def run(ops, cur, saved):
-        q, s, zp = cur
-        for op in ops:
-            if op[0] == "layer":
-                L = layers[op[1]]
-                qw, qb, s_w = qlayers[op[1]]
-                s_out, zp_out = out_qparams[op[1]]
-                s_out = f32(s_out)
-                if L[0] == "conv":
-                    f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
-                    q, _ = f(q, qw, qb, gr.layer_groups(L), L[4], L[5], s, zp, s_w, s_out, zp_out)
-                elif per_channel:
-                    q, _, _ = pcp.linear_pc(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-                else:
-                    q, _, _ = orc.linear(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)
-                s, zp = s_out, int(zp_out)
-            elif op[0] == "relu":
-                q = orc.relu(q, zp)
-            elif op[0] == "pool":
-                q = orc.max_pool2d(q, op[1], op[2])
-            elif op[0] == "avgpool":
-                q = cr.apr.avg_pool2d_u8(q, op[1], op[1], op[2])
-            elif op[0] == "gap":
-                q = cr.apr.global_avg_pool2d_u8(q)
-            elif op[0] == "save":
-                saved[op[1]] = (q, s, zp)
-            elif op[0] == "branch":
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            elif op[0] == "add":
-                q2, s2, zp2 = saved[op[2]]
-                s_out, zp_out = join_qparams[op[1]]
-                q = cr.ar.add_u8(q, zp, s, q2, zp2, s2, f32(s_out), int(zp_out), relu=False)
-                s, zp = f32(s_out), int(zp_out)
-            elif op[0] == "mul":
-                q2, s2, zp2 = saved[op[2]]
-                s_out, zp_out = join_qparams[op[1]]
-                gate = q2 if q2.shape != q.shape else None
-                q = mul_u8(q, zp, s, q2, zp2, s2, f32(s_out), int(zp_out), relu=False)
-                s, zp = f32(s_out), int(zp_out)
-                if trace is not None:
-                    floor = zp if op[1] in floors else None
-                    trace[op[1]] = (gate, q if floor is None else orc.relu(q, zp), floor)
-            elif op[0] == "concat":
-                s_out, zp_out = join_qparams[op[1]]
-                q = cr.cat_u8([(q, s, zp)] + [saved[t] for t in op[2]], f32(s_out), int(zp_out))
-                s, zp = f32(s_out), int(zp_out)
-            elif op[0] == "act":
-                kind, param = acr.act_of(op)
-                s_out, zp_out = join_qparams[op[1]]
-                q = acr.act_u8(q, kind, param, s, zp, f32(s_out), int(zp_out))
-                s, zp = f32(s_out), int(zp_out)
-            else:
-                q = q.reshape(-1, op[1])
-        return q, s, zp
+    def trace(op, out, operands):
+        if op[0] == "mul":
+            q, _, zp = out
+            q2 = operands[1][0]
+            floor = zp if op[1] in floors else None
+            into[op[1]] = (q2 if q2.shape != q.shape else None, q if floor is None else orc.relu(q, zp), floor)
 
-    q0 = orc.quantize(x, pipeline.INPUT_SCALE, pipeline.INPUT_ZP)
-    q, s, zp = run(spec, (q0, pipeline.INPUT_SCALE, pipeline.INPUT_ZP), {})
-    return orc.dequantize(q, s, zp)
+    return trace
 
 
-def fp32_qparams(networks_entry, state_dict, x):
-    """Stand-in for calibration without a GPU (act_ref.fp32_qparams with relu, branch and mul): a numpy forward in float64
-    over the FP32 weights; the output range of every layer, Add, Mul and Activation gives its (scale, zero_point) by the
-    calibrator's rule.  Returns (layer qparams, join qparams)."""
-    layers, spec, _ = networks_entry
-    qp, jqp = {}, {}
-
-    def run(ops, v, saved):
-        for op in ops:
-            if op[0] == "layer":
-                L = layers[op[1]]
-                w, b = state_dict[op[1] + ".weight"].astype(np.float64), state_dict[op[1] + ".bias"].astype(np.float64)
-                v = gr.conv2d_f64(v, w, b, gr.layer_groups(L), L[4], L[5]) if L[0] == "conv" else f64_ref.linear(v.reshape(v.shape[0], -1), w, b)
-                qp[op[1]] = acr.range_qparams(v.min(), v.max())
-            elif op[0] == "act":
-                kind, param = acr.act_of(op)
-                v = acr.act_f64(kind, v, param)
-                jqp[op[1]] = acr.range_qparams(v.min(), v.max())
-            elif op[0] == "relu":
-                v = np.maximum(v, 0.0)
-            elif op[0] == "save":
-                saved[op[1]] = v
-            elif op[0] == "branch":
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            elif op[0] == "add":
-                v = v + saved[op[2]]
-                jqp[op[1]] = acr.range_qparams(v.min(), v.max())
-            elif op[0] == "mul":
-                v = v * as_gate(v, saved[op[2]])
-                jqp[op[1]] = acr.range_qparams(v.min(), v.max())
-            elif op[0] == "gap":
-                v = v.mean(axis=(2, 3), keepdims=True)
-            elif op[0] == "flatten":
-                v = v.reshape(-1, op[1])
-            else:
-                raise ValueError("fp32_qparams: op %r" % (op,))
-        return v
-
-    run(spec, np.asarray(x, np.float64), {})
-    return qp, jqp
-
-
-# synthetic weights, inputs and calibration stand-in of the network tests, fixed here: with them every gate of the oracle's
-# se_tiny forward takes at least MIN_GATE_VALUES byte values and no Mul output has more than MAX_EDGE_SHARE of its bytes on
-# 0, 255 or the floor of a relu behind it (tests/test_mul_host.py)
-WEIGHT_SEED, CALIB_SEED, CALIB_IMAGES, INPUT_SEED = 42, 99, 4, 5
+# with the seeds of tests/spec_ref.py every gate of the oracle's se_tiny forward takes at least MIN_GATE_VALUES byte values and
+# no Mul output has more than MAX_EDGE_SHARE of its bytes on 0, 255 or the floor of a relu behind it (tests/test_mul_host.py)
 MIN_GATE_VALUES, MAX_EDGE_SHARE = 8, 0.6
 
 
 def nontrivial(trace):
-    """{attr: (distinct gate byte values or None, share of output bytes on 0 / 255 / the relu floor)} of a forward()'s trace,
+    """{attr: (distinct gate byte values or None, share of output bytes on 0 / 255 / the relu floor)} of a tracer()'s dict,
     asserted against the two limits"""
     out = {}
     for attr, (gate, q, floor) in trace.items():

@@ -1,0 +1,190 @@
+"""The numpy interpreter of a `workloads` spec over the oracle: the expected bytes of every network test (DESIGN.md section
+2).  A helper module, not a conftest.
+
+Nothing is defined arithmetically here.  Every op is the function of its own module -- the reference's ops in oracle/orc.py,
+per-channel requantisation in pc_pipeline, and grouped_ref, add_ref, avgpool_ref, concat_ref, act_ref, mul_ref, deconv_ref,
+upsample_ref, dilated_ref for what the reference does not have -- and this module only walks the spec with (bytes, scale,
+zero_point) in hand.  A new op adds one branch to forward(), one to fp32_qparams() if it is calibrated, its name to OPS, and
+its arithmetic in a module of its own.
+
+  OPS                                the op names a spec may hold; anything else raises ValueError
+  forward(...)                       float32 logits of a network
+  fp32_qparams(...)                  stand-in for calibration without a GPU: a float64 forward over the FP32 weights
+  quantize_layers(...)               convert()'s weight rules
+  outputs_of(name, into)             a trace callback that keeps the output bytes of the ops called `name`"""
+import numpy as np
+
+import act_ref as acr
+import add_ref as ar
+import avgpool_ref as apr
+import concat_ref as cr
+import deconv_ref as dr
+import dilated_ref as dl
+import f64_ref
+import grouped_ref as gr
+import mul_ref as mr
+import orc
+import pc_pipeline as pcp
+import pipeline
+import upsample_ref as ur
+
+f32 = np.float32
+OPS = frozenset(["layer", "relu", "pool", "avgpool", "gap", "save", "branch", "add", "mul", "concat", "act", "upsample", "flatten"])
+
+# synthetic weights, calibration batch and input of the network tests, GPU and host: with them the traced tensors keep the
+# limits of act_ref.nontrivial and mul_ref.nontrivial.  (CALIB_IMAGES is the batch of fp32_qparams in the host tests; the GPU
+# tests calibrate the product on batches of their own size.)
+WEIGHT_SEED, CALIB_SEED, CALIB_IMAGES, INPUT_SEED = 42, 99, 4, 5
+
+
+def _layer(L, cur, qlayer, s_out, zp_out, per_channel):
+    """the output bytes of a weighted layer.  Conv: the reference convolution per group, a dilated kernel inflated by zeros
+    (the kernel extent is the weight's); deconv: the reference convolution of the equivalent problem; fc: the reference linear"""
+    (q, s, zp), (qw, qb, s_w) = cur, qlayer
+    if L[0] == "conv":
+        d = dl.layer_dilation(L)
+        f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
+        return f(q, dl.inflate(qw, d) if d > 1 else qw, qb, gr.layer_groups(L), L[4], L[5], s, zp, s_w, s_out, zp_out)[0]
+    if L[0] == "deconv":
+        f = dr.deconv_u8_pc if per_channel else dr.deconv_u8
+        return f(q, qw, qb, L[4], L[5], L[6], s, zp, s_w, s_out, zp_out)[0]
+    if L[0] == "fc":
+        f = pcp.linear_pc if per_channel else orc.linear
+        return f(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)[0]
+    raise ValueError("spec_ref.forward: layer %r" % (L,))
+
+
+def forward(networks_entry, x, qlayers, out_qparams, join_qparams=None, per_channel=False, trace=None):
+    """x: float32 NCHW.  qlayers: {attr: (qw, qb, s_w)} as quantize_layers gives them (s_w a scalar or, per_channel, float32
+    [out]).  out_qparams: {attr: (scale, zp)} of the layers, join_qparams: the same of the Adds, Muls, Concats and Activations.
+    trace: called as trace(op, (bytes, scale, zp), operands) behind every op that produces bytes, operands the list of
+    (bytes, scale, zp) it read, the current tensor first.  Returns float32 logits."""
+    layers, spec, _ = networks_entry
+
+    def run(ops, cur, saved):
+        for op in ops:
+            (q, s, zp), name = cur, op[0]
+            if name == "save":
+                saved[op[1]] = cur
+                continue
+            if name == "branch":
+                saved[op[1]] = run(op[2], saved[op[1]], saved)
+                continue
+            operands = [cur]
+            if name in ("layer", "add", "mul", "concat", "act"):  # the ops with output parameters of their own
+                s_out, zp_out = (out_qparams if name == "layer" else join_qparams or {})[op[1]]
+                s_out, zp_out = f32(s_out), int(zp_out)
+            if name == "layer":
+                cur = (_layer(layers[op[1]], cur, qlayers[op[1]], s_out, zp_out, per_channel), s_out, zp_out)
+            elif name == "relu":
+                cur = (orc.relu(q, zp), s, zp)
+            elif name == "pool":
+                cur = (orc.max_pool2d(q, op[1], op[2]), s, zp)
+            elif name == "avgpool":
+                cur = (apr.avg_pool2d_u8(q, op[1], op[1], op[2]), s, zp)
+            elif name == "gap":
+                cur = (apr.global_avg_pool2d_u8(q), s, zp)
+            elif name == "upsample":
+                cur = (ur.upsample_u8(q, *ur.factors(op[1]), op[2]), s, zp)
+            elif name in ("add", "mul"):
+                q2, s2, zp2 = saved[op[2]]
+                operands.append(saved[op[2]])
+                cur = ((ar.add_u8 if name == "add" else mr.mul_u8)(q, zp, s, q2, zp2, s2, s_out, zp_out, relu=False), s_out, zp_out)
+            elif name == "concat":
+                operands += [saved[t] for t in op[2]]
+                cur = (cr.cat_u8(operands, s_out, zp_out), s_out, zp_out)
+            elif name == "act":
+                kind, param = acr.act_of(op)
+                cur = (acr.act_u8(q, kind, param, s, zp, s_out, zp_out), s_out, zp_out)
+            elif name == "flatten":
+                cur = (q.reshape(-1, op[1]), s, zp)
+            else:
+                raise ValueError("spec_ref.forward: op %r" % (op,))
+            if trace is not None:
+                trace(op, cur, operands)
+        return cur
+
+    q0 = orc.quantize(x, pipeline.INPUT_SCALE, pipeline.INPUT_ZP)
+    return orc.dequantize(*run(spec, (q0, pipeline.INPUT_SCALE, pipeline.INPUT_ZP), {}))
+
+
+def outputs_of(name, into):
+    """a trace callback for forward(): into[attr] = the output bytes of every ("add" | "mul" | "concat" | "act", attr, ...)
+    op called `name`.  (mul_ref.tracer, deconv_ref.tracer and upsample_ref.tracer keep what their tests look at.)"""
+    def trace(op, out, operands):
+        if op[0] == name:
+            into[op[1]] = out[0]
+
+    return trace
+
+
+def range_qparams(lo, hi):
+    """the calibrator's rule (src/calibrator.cc:24-37 at quantile 1) on a real-valued range"""
+    lo, hi = min(float(lo), 0.0), max(float(hi), 0.0)
+    if hi - lo < 1e-12:
+        return f32(1.0), 0
+    zp = int(255 * (0 - lo) / (hi - lo))
+    scale = (hi - lo) / 255 if zp == 0 else (0 - lo) / zp
+    return f32(scale), zp
+
+
+def fp32_qparams(networks_entry, state_dict, x):
+    """Stand-in for calibration without a GPU: a numpy forward in float64 over the FP32 weights; the output range of every
+    layer, Add, Mul, Concat and Activation gives its (scale, zero_point) by the calibrator's rule.  No registry network needs
+    avgpool or upsample here; they raise like any other op.  Returns (layer qparams, join qparams)."""
+    layers, spec, _ = networks_entry
+    qp, jqp = {}, {}
+
+    def run(ops, v, saved):
+        for op in ops:
+            name = op[0]
+            if name == "layer":
+                L = layers[op[1]]
+                w, b = state_dict[op[1] + ".weight"].astype(np.float64), state_dict[op[1] + ".bias"].astype(np.float64)
+                if L[0] == "conv":
+                    v = gr.conv2d_f64(v, dl.inflate(w, dl.layer_dilation(L)), b, gr.layer_groups(L), L[4], L[5])
+                elif L[0] == "deconv":
+                    v = dr.scatter(v, w, b, L[4], L[5], L[6])
+                else:
+                    v = f64_ref.linear(v.reshape(v.shape[0], -1), w, b)
+            elif name == "act":
+                kind, param = acr.act_of(op)
+                v = acr.act_f64(kind, v, param)
+            elif name == "relu":
+                v = np.maximum(v, 0.0)
+            elif name == "pool":
+                v = f64_ref.max_pool2d(v, op[1], op[2])
+            elif name == "save":
+                saved[op[1]] = v
+            elif name == "branch":
+                saved[op[1]] = run(op[2], saved[op[1]], saved)
+            elif name == "add":
+                v = v + saved[op[2]]
+            elif name == "mul":
+                v = v * mr.as_gate(v, saved[op[2]])
+            elif name == "concat":
+                v = np.concatenate([v] + [saved[t] for t in op[2]], axis=1)
+            elif name == "gap":
+                v = v.mean(axis=(2, 3), keepdims=True)
+            elif name == "flatten":
+                v = v.reshape(-1, op[1])
+            else:
+                raise ValueError("spec_ref.fp32_qparams: op %r" % (op,))
+            if name in ("layer", "act", "add", "mul", "concat"):
+                (qp if name == "layer" else jqp)[op[1]] = range_qparams(v.min(), v.max())
+        return v
+
+    run(spec, np.asarray(x, np.float64), {})
+    return qp, jqp
+
+
+def quantize_layers(networks_entry, state_dict, per_channel=False):
+    """{attr: (qw, qb, s_w)} by convert()'s rules on the weight tensors as they stand ([kc, c / groups, kh, kw] of a grouped
+    conv, the compact kernel of a dilated one), a "deconv" layer as its equivalent kernel W~ [out, in, k, k]: per tensor the
+    oracle's joint min / max over the whole weight and the bias, per channel the same per row of the [kc, K] matrix"""
+    rule = pcp.quantize_weight_pc if per_channel else orc.quantize_weight
+    out = {}
+    for attr, L in networks_entry[0].items():
+        w = state_dict[attr + ".weight"]
+        out[attr] = tuple(rule(dr.equivalent_weight(w) if L[0] == "deconv" else w, state_dict[attr + ".bias"]))
+    return out

@@ -9,6 +9,7 @@ import pytest
 
 import abi
 import act_ref as ar
+import spec_ref as sr
 
 f32 = np.float32
 KINDS = sorted(ar.KINDS, key=ar.KINDS.get)
@@ -342,12 +343,12 @@ def test_existing_networks_have_no_activations_and_keep_their_macs():
 def test_every_activation_of_the_oracle_forward_discriminates(name, batch):
     from int8inferenceengine_amd import workloads as wl
 
-    sd = wl.synthetic_state_dict(name, ar.WEIGHT_SEED)
-    qp, jqp = ar.fp32_qparams(wl.NETWORKS[name], sd, wl.synthetic_input(name, ar.CALIB_IMAGES, seed=ar.CALIB_SEED))
+    sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
+    qp, jqp = sr.fp32_qparams(wl.NETWORKS[name], sd, wl.synthetic_input(name, sr.CALIB_IMAGES, seed=sr.CALIB_SEED))
     assert sorted(jqp) == sorted(wl.activation_names(name) + wl.add_names(name)) and sorted(qp) == sorted(wl.layer_names(name))
     trace = {}
-    x = wl.synthetic_input(name, batch, seed=ar.INPUT_SEED)
-    y = ar.forward(wl.NETWORKS[name], x, ar.gr.quantize_layers(wl.NETWORKS[name], sd), qp, jqp, False, trace)
+    x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
+    y = sr.forward(wl.NETWORKS[name], x, sr.quantize_layers(wl.NETWORKS[name], sd), qp, jqp, False, sr.outputs_of("act", trace))
     assert y.shape == (batch, 10) and list(trace) == wl.activation_names(name)
     stats = ar.nontrivial(trace)
     print({a: (d, round(s, 3)) for a, (d, s) in stats.items()})

@@ -8,6 +8,7 @@ import pytest
 
 import abi
 import deconv_ref as dr
+import spec_ref as sr
 
 f32 = np.float32
 
@@ -306,12 +307,12 @@ def test_network_deconv_outputs_are_not_clamped(name):
     """the oracle alone, with the float64 stand-in for calibration: at most 20 % of every up-conv's expected bytes on a clamp"""
     from int8inferenceengine_amd import workloads as wl
 
-    sd = wl.synthetic_state_dict(name, dr.WEIGHT_SEED)
-    qp, jqp = dr.fp32_qparams(wl.NETWORKS[name], sd, wl.synthetic_input(name, dr.CALIB_IMAGES, seed=dr.CALIB_SEED))
+    sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
+    qp, jqp = sr.fp32_qparams(wl.NETWORKS[name], sd, wl.synthetic_input(name, sr.CALIB_IMAGES, seed=sr.CALIB_SEED))
     assert sorted(qp) == sorted(wl.layer_names(name)) and sorted(jqp) == sorted(wl.concat_names(name))
     trace = {}
-    x = wl.synthetic_input(name, 1, seed=dr.INPUT_SEED)
-    y = dr.forward(wl.NETWORKS[name], x, dr.quantize_layers(wl.NETWORKS[name], sd), qp, jqp, False, trace)
+    x = wl.synthetic_input(name, 1, seed=sr.INPUT_SEED)
+    y = sr.forward(wl.NETWORKS[name], x, sr.quantize_layers(wl.NETWORKS[name], sd), qp, jqp, False, dr.tracer(wl.NETWORKS[name][0], trace))
     assert y.shape == (1, 10, 32, 32) and len(trace) == 3
     for a, q in trace.items():
         share = float(((q == 0) | (q == 255)).mean())

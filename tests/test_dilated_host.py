@@ -177,15 +177,6 @@ def test_networks_registry_and_macs():
     net.load(sd)
 
 
-def test_dense_entry_rewrites_only_dilated_layers():
-    from int8inferenceengine_amd import workloads as wl
-
-    layers, spec, shape = dl.dense_entry(wl.network("aspp_tiny"))
-    assert layers["atr"] == ("conv", 32, 32, 5, 1, 2, 1) and layers["a3"] == ("conv", 32, 20, 7, 1, 3, 1)
-    assert layers["a4d"] == ("conv", 32, 32, 5, 1, 2, 32) and layers["a1"] == ("conv", 32, 16, 1, 1, 0)
-    assert spec is wl.network("aspp_tiny")[1]
-
-
 # ---- the GPU case lists --------------------------------------------------------------------------------------------------
 def _plain(pred):
     return [c for c in dl.CASES if not c.force and not c.extreme and c.zp_in == dl.ZP_IN and pred(c)]

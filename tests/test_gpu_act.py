@@ -13,6 +13,7 @@ import abi
 import act_ref as ar
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -394,11 +395,11 @@ def _net(name, per_channel):
     from int8inferenceengine_amd import workloads as wl
 
     if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name, ar.WEIGHT_SEED)
+        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
         net = wl.calibrated(name, sd, per_channel=per_channel)
         qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
         jqp = {a: getattr(net, a).output_qparams() for a in wl.activation_names(name) + wl.add_names(name)}
-        _NETS[(name, per_channel)] = (net, gr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
+        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
     return _NETS[(name, per_channel)]
 
 
@@ -412,9 +413,9 @@ def test_tiny_networks_bit_exact(i8ie, name, batch, per_channel, tmp_path):
 
     net, qlayers, qp, jqp = _net(name, per_channel)
     assert all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
-    x = wl.synthetic_input(name, batch, seed=ar.INPUT_SEED)
+    x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
     trace = {}
-    want = ar.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, trace)
+    want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, sr.outputs_of("act", trace))
     stats = ar.nontrivial(trace)  # the expected bytes discriminate
     print({a: (d, round(s, 3)) for a, (d, s) in stats.items()})
     assert list(trace) == wl.activation_names(name)
@@ -446,9 +447,9 @@ def test_mobilenetv2_cifar_bit_exact(i8ie):
     name = "mobilenetv2_cifar"
     net, qlayers, qp, jqp = _net(name, False)
     assert len(jqp) == 35 + 10 and all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
-    x = wl.synthetic_input(name, 2, seed=ar.INPUT_SEED)
+    x = wl.synthetic_input(name, 2, seed=sr.INPUT_SEED)
     trace = {}
-    want = ar.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, False, trace)
+    want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, False, sr.outputs_of("act", trace))
     stats = ar.nontrivial(trace)
     print({a: (d, round(s, 3)) for a, (d, s) in stats.items()})
     got = net(i8ie.tensor(x)).numpy()

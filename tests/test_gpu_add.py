@@ -11,9 +11,9 @@ import pytest
 
 import abi
 import add_ref as ar
-import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import pointwise_util as pu
+import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -316,7 +316,7 @@ def _resnet(per_channel):
         net = wl.calibrated(name, sd, per_channel=per_channel)
         qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
         aqp = {a: getattr(net, a).output_qparams() for a in wl.add_names(name)}
-        _NETS[per_channel] = (net, gr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, aqp)
+        _NETS[per_channel] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, aqp)
     return _NETS[per_channel]
 
 
@@ -331,7 +331,7 @@ def test_resnet_tiny_bit_exact(i8ie, batch, per_channel, tmp_path):
     net, qlayers, qp, aqp = _resnet(per_channel)
     assert all(s > 0 and s != 1.0 for s, _ in aqp.values()), aqp  # the Adds were calibrated
     x = wl.synthetic_input(name, batch, seed=5)
-    want = ar.forward(wl.NETWORKS[name], x, qlayers, qp, aqp, per_channel)
+    want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, aqp, per_channel)
     got = net(i8ie.tensor(x)).numpy()
     assert got.shape == want.shape == (batch, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
     cx.force_fallback(True)

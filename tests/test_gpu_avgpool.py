@@ -21,6 +21,7 @@ import avgpool_ref as apr
 import f64_ref
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -410,7 +411,7 @@ def _net(name, per_channel):
         net = wl.calibrated(name, sd, calib_batch=wl.synthetic_input(name, 16, seed=99), per_channel=per_channel)
         qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
         aqp = {a: getattr(net, a).output_qparams() for a in wl.add_names(name)}
-        _NETS[(name, per_channel)] = (net, gr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, aqp)
+        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, aqp)
     return _NETS[(name, per_channel)]
 
 
@@ -424,7 +425,7 @@ def test_networks_bit_exact(i8ie, name, batch, per_channel, tmp_path):
     net, qlayers, qp, aqp = _net(name, per_channel)
     assert all(s > 0 and s != 1.0 for s, _ in aqp.values()), aqp  # the Adds were calibrated
     x = wl.synthetic_input(name, batch, seed=5)
-    want = apr.forward(wl.NETWORKS[name], x, qlayers, qp, aqp, per_channel)
+    want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, aqp, per_channel)
     got = net(i8ie.tensor(x)).numpy()
     assert got.shape == want.shape == (batch, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
     cx.force_fallback(True)

@@ -11,8 +11,8 @@ import pytest
 
 import abi
 import concat_ref as cr
-import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -460,7 +460,7 @@ def _net(name, per_channel):
         net = wl.calibrated(name, sd, per_channel=per_channel)
         qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
         jqp = {a: getattr(net, a).output_qparams() for a in wl.concat_names(name) + wl.add_names(name)}
-        _NETS[(name, per_channel)] = (net, gr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
+        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
     return _NETS[(name, per_channel)]
 
 
@@ -490,7 +490,7 @@ def test_fire_tiny_bit_exact(i8ie, batch, per_channel, tmp_path):
     assert sorted(jqp) == ["facat", "fbcat", "rcat"] and all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
     x = wl.synthetic_input(name, batch, seed=5)
     trace = {}
-    want = cr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, trace)
+    want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, sr.outputs_of("concat", trace))
     sat, literal = _saturated(trace, jqp)
     print("concat bytes on a clamp: %.4f, bytes 0 / 255: %.4f" % (sat, literal), jqp)
     assert sorted(trace) == sorted(jqp) and sat < 0.2 and literal < 0.6, (sat, literal)  # the expected bytes discriminate
@@ -523,7 +523,7 @@ def test_squeezenet_cifar_bit_exact(i8ie):
     assert len(jqp) == 8 and all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
     x = wl.synthetic_input(name, 2, seed=5)
     trace = {}
-    want = cr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, False, trace)
+    want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, False, sr.outputs_of("concat", trace))
     sat, literal = _saturated(trace, jqp)
     print("concat bytes on a clamp: %.4f, bytes 0 / 255: %.4f" % (sat, literal))
     assert sat < 0.2 and literal < 0.6, (sat, literal)

@@ -15,6 +15,7 @@ import f64_ref
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import orc
+import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -321,11 +322,11 @@ def _net(name, per_channel):
     from int8inferenceengine_amd import workloads as wl
 
     if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name, dr.WEIGHT_SEED)
-        net = wl.calibrated(name, sd, calib_batch=wl.synthetic_input(name, 8, seed=dr.CALIB_SEED), per_channel=per_channel)
+        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
+        net = wl.calibrated(name, sd, calib_batch=wl.synthetic_input(name, 8, seed=sr.CALIB_SEED), per_channel=per_channel)
         qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
         jqp = {a: getattr(net, a).output_qparams() for a in wl.concat_names(name)}
-        _NETS[(name, per_channel)] = (net, dr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
+        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
     return _NETS[(name, per_channel)]
 
 
@@ -337,9 +338,9 @@ def _want(name, batch, per_channel):
 
     if (name, batch, per_channel) not in _WANT:
         net, qlayers, qp, jqp = _net(name, per_channel)
-        x = wl.synthetic_input(name, batch, seed=dr.INPUT_SEED)
+        x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
         trace = {}
-        want = dr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, trace)
+        want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, dr.tracer(wl.NETWORKS[name][0], trace))
         _WANT[(name, batch, per_channel)] = (x, want, trace)
     return _WANT[(name, batch, per_channel)]
 

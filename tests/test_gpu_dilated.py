@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 
 import abi
-import deconv_ref as dr
 import dilated_ref as dl
 import f64_ref
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import orc
+import spec_ref as sr
 import upsample_ref as ur
 
 pytestmark = pytest.mark.gpu
@@ -290,7 +290,7 @@ def test_prepare_convert_save_load(i8ie, tmp_path):
     from int8inferenceengine_amd import workloads as wl
 
     net = _net("aspp_tiny", False)[0]  # (prepare() -> an FP32 batch through the dilated FP32 conv -> convert())
-    x = wl.synthetic_input("aspp_tiny", 3, seed=ur.INPUT_SEED)
+    x = wl.synthetic_input("aspp_tiny", 3, seed=sr.INPUT_SEED)
     want = net(i8ie.tensor(x)).numpy()
     path = str(tmp_path / "aspp.npz")
     net.save_quantized(path)
@@ -308,11 +308,11 @@ def _net(name, per_channel):
     from int8inferenceengine_amd import workloads as wl
 
     if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name, ur.WEIGHT_SEED)
-        net = wl.calibrated(name, sd, calib_batch=wl.synthetic_input(name, 8, seed=ur.CALIB_SEED), per_channel=per_channel)
+        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
+        net = wl.calibrated(name, sd, calib_batch=wl.synthetic_input(name, 8, seed=sr.CALIB_SEED), per_channel=per_channel)
         qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
         jqp = {a: getattr(net, a).output_qparams() for a in wl.add_names(name) + wl.concat_names(name)}
-        _NETS[(name, per_channel)] = (net, dr.quantize_layers(wl.network(name), sd, per_channel), qp, jqp)
+        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.network(name), sd, per_channel), qp, jqp)
     return _NETS[(name, per_channel)]
 
 
@@ -324,9 +324,9 @@ def test_networks_bit_exact(i8ie, name, per_channel):
 
     batch = 2 if name == "deeplabv3_cifar" else 5
     net, qlayers, qp, jqp = _net(name, per_channel)
-    x = wl.synthetic_input(name, batch, seed=ur.INPUT_SEED)
+    x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
     trace = []
-    want = dl.forward(wl.network(name), x, qlayers, qp, jqp, per_channel, trace)
+    want = sr.forward(wl.network(name), x, qlayers, qp, jqp, per_channel, ur.tracer(trace))
     assert len(trace) == 2 and all(len(np.unique(q)) > 30 for _, q in trace[1:])  # (the head's maps are not saturated)
     got = net(i8ie.tensor(x)).numpy()
     assert got.shape == want.shape == (batch, 10, 32, 32)

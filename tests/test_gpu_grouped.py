@@ -12,6 +12,7 @@ import f64_ref
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import orc
+import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
 
@@ -251,7 +252,7 @@ def test_alexnet_paper_bit_exact(batch, per_channel, tmp_path):
     x = wl.synthetic_input(name, batch, seed=5)
     got = net(i8ie.tensor(x)).numpy()
     qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-    want = gr.forward(wl.NETWORKS[name], x, gr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, per_channel)
+    want = sr.forward(wl.NETWORKS[name], x, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, per_channel=per_channel)
     assert got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
     if batch != 2:
         return

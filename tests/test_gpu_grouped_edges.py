@@ -15,6 +15,7 @@ import grouped_cases as gc
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import orc
+import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
 
@@ -252,5 +253,5 @@ def test_module_with_a_g1_layer(per_channel, monkeypatch):
     print("module per_channel=%d: %s" % (per_channel, sorted(GCONV & launched)))
     assert GCONV & launched == {"gconv_mfma"}, launched
     qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-    want = gr.forward(TINY, x, gr.quantize_layers(TINY, sd, per_channel), qp, per_channel)
+    want = sr.forward(TINY, x, sr.quantize_layers(TINY, sd, per_channel), qp, per_channel=per_channel)
     assert got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))

@@ -15,6 +15,7 @@ import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import mul_ref as mr
 import pointwise_util as pu
+import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -449,11 +450,11 @@ def _net(name, per_channel):
     from int8inferenceengine_amd import workloads as wl
 
     if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name, mr.WEIGHT_SEED)
+        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
         net = wl.calibrated(name, sd, per_channel=per_channel)
         qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
         jqp = {a: getattr(net, a).output_qparams() for a in wl.activation_names(name) + wl.add_names(name) + wl.mul_names(name)}
-        _NETS[(name, per_channel)] = (net, gr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
+        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
     return _NETS[(name, per_channel)]
 
 
@@ -467,9 +468,9 @@ def test_se_tiny_bit_exact(i8ie, batch, per_channel, tmp_path):
     name = "se_tiny"
     net, qlayers, qp, jqp = _net(name, per_channel)
     assert all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp  # the Muls and Activations were calibrated
-    x = wl.synthetic_input(name, batch, seed=mr.INPUT_SEED)
+    x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
     trace = {}
-    want = mr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, trace)
+    want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, mr.tracer(wl.NETWORKS[name][1], trace))
     stats = mr.nontrivial(trace)  # the expected bytes discriminate
     print({a: (d, round(s, 3)) for a, (d, s) in stats.items()})
     assert list(trace) == wl.mul_names(name)
@@ -500,9 +501,9 @@ def test_mobilenetv3_small_cifar_bit_exact(i8ie, tmp_path):
     name = "mobilenetv3_small_cifar"
     net, qlayers, qp, jqp = _net(name, False)
     assert len(wl.mul_names(name)) == 9 and all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
-    x = wl.synthetic_input(name, 2, seed=mr.INPUT_SEED)
+    x = wl.synthetic_input(name, 2, seed=sr.INPUT_SEED)
     trace = {}
-    want = mr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, False, trace)
+    want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, False, mr.tracer(wl.NETWORKS[name][1], trace))
     print({a: (len(np.unique(g)), round(float(((q == 0) | (q == 255)).mean()), 3)) for a, (g, q, _) in trace.items()})
     got = net(i8ie.tensor(x)).numpy()
     assert got.shape == want.shape == (2, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))

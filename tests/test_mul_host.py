@@ -9,6 +9,7 @@ import pytest
 
 import abi
 import mul_ref as mr
+import spec_ref as sr
 
 f32 = np.float32
 
@@ -401,12 +402,12 @@ def test_se_tiny_oracle_forward_has_live_gates_and_unclamped_products():
     from int8inferenceengine_amd import workloads as wl
 
     name = "se_tiny"
-    sd = wl.synthetic_state_dict(name, mr.WEIGHT_SEED)
-    qp, jqp = mr.fp32_qparams(wl.NETWORKS[name], sd, wl.synthetic_input(name, mr.CALIB_IMAGES, seed=mr.CALIB_SEED))
+    sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
+    qp, jqp = sr.fp32_qparams(wl.NETWORKS[name], sd, wl.synthetic_input(name, sr.CALIB_IMAGES, seed=sr.CALIB_SEED))
     assert sorted(jqp) == sorted(wl.activation_names(name) + wl.mul_names(name)) and sorted(qp) == sorted(wl.layer_names(name))
     trace = {}
-    x = wl.synthetic_input(name, 2, seed=mr.INPUT_SEED)
-    y = mr.forward(wl.NETWORKS[name], x, mr.gr.quantize_layers(wl.NETWORKS[name], sd), qp, jqp, False, trace)
+    x = wl.synthetic_input(name, 2, seed=sr.INPUT_SEED)
+    y = sr.forward(wl.NETWORKS[name], x, sr.quantize_layers(wl.NETWORKS[name], sd), qp, jqp, False, mr.tracer(wl.NETWORKS[name][1], trace))
     assert y.shape == (2, 10) and list(trace) == wl.mul_names(name)
     stats = mr.nontrivial(trace)
     print({a: (d, round(s, 3)) for a, (d, s) in stats.items()})

@@ -6,15 +6,11 @@ align_corners=False written in integers -- per axis the taps (i0, i1) and weight
 of the four taps, D = 4 fh fw, out = (S + D // 2) // D.  taps() is that rule as arrays over the output index, bilinear_sd the
 exact (S, D) in int64, upsample_u8 the bytes, bilinear_f64 the float64 value S / D of any real input (with the largest
 magnitude among each output's four taps), upsample_f32 the FP32 sequence in order (row blends first, one float32 rounding
-per operation).  forward() walks a spec with ("upsample", factor, mode) over the oracle, and the three new C symbols get
-their ctypes signatures here (tests/abi.py binds the rest)."""
+per operation).  tracer() keeps the upsamples' bytes of a spec_ref.forward, and the three new C symbols get their ctypes
+signatures here (tests/abi.py binds the rest)."""
 import ctypes as C
 
 import numpy as np
-
-import deconv_ref as dr
-import orc
-import pipeline
 
 f32 = np.float32
 NEAREST, BILINEAR = 0, 1
@@ -103,50 +99,13 @@ def upsample_f32(x, fh, fw, mode):
 
 
 # ---- spec networks -----------------------------------------------------------------------------------------------------
-def forward(networks_entry, x, qlayers, out_qparams, join_qparams, per_channel=False, trace=None):
-    """deconv_ref.forward with ("upsample", factor, mode): the op is upsample_u8 on the bytes, the (scale, zero_point) carried
-    through; everything between two such ops is deconv_ref's own segment walk.  trace: a list that receives (op, output bytes)
-    of every upsample."""
-    layers, spec, shape = networks_entry
+def tracer(into):
+    """a trace callback for spec_ref.forward: (op, output bytes) of every upsample, appended to the list `into`"""
+    def trace(op, out, operands):
+        if op[0] == "upsample":
+            into.append((op, out[0]))
 
-    def run(ops, cur, saved):
-        seg = []
-
-        def flush(cur):
-            if seg:
-                cur = dr._run_segment((layers, list(seg), shape), cur, saved, qlayers, out_qparams, join_qparams, per_channel)
-                del seg[:]
-            return cur
-
-        for op in ops:
-            if op[0] == "upsample":
-                q, s, zp = flush(cur)
-                fh, fw = factors(op[1])
-                q = upsample_u8(q, fh, fw, op[2])
-                if trace is not None:
-                    trace.append((op, q))
-                cur = (q, s, zp)
-            elif op[0] == "layer" and layers[op[1]][0] == "deconv":
-                q, s, zp = flush(cur)
-                L = layers[op[1]]
-                qw, qb, s_w = qlayers[op[1]]
-                s_out, zp_out = out_qparams[op[1]]
-                f = dr.deconv_u8_pc if per_channel else dr.deconv_u8
-                q, _ = f(q, qw, qb, L[4], L[5], L[6], s, zp, s_w, f32(s_out), int(zp_out))
-                cur = (q, f32(s_out), int(zp_out))
-            elif op[0] == "branch":
-                cur = flush(cur)
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            else:
-                seg.append(op)
-        return flush(cur)
-
-    q0 = orc.quantize(x, pipeline.INPUT_SCALE, pipeline.INPUT_ZP)
-    q, s, zp = run(spec, (q0, pipeline.INPUT_SCALE, pipeline.INPUT_ZP), {})
-    return orc.dequantize(q, s, zp)
-
-
-WEIGHT_SEED, CALIB_SEED, INPUT_SEED = 42, 99, 5
+    return trace
 
 
 # ---- ctypes signatures of the upsample entry points -----------------------------------------------------------------------
