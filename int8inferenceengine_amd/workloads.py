@@ -387,11 +387,6 @@ NETWORKS["upsample_tiny"] = _upsample_tiny()
 NETWORKS["unet_bilinear_cifar"] = _unet_cifar(bilinear=True)
 
 
-# Networks added after tests began to pin set(NETWORKS): a second registry with the same entries.  network(name) looks in both;
-# everything below goes through it.
-EXTRA_NETWORKS = {}
-
-
 def _aspp_tiny():
     """An atrous spatial pyramid (Chen et al. 2017) in small: what Conv2d's dilation exists for.  Two stride-2 3x3 convs down
     to 32 channels of 8 x 8, a dilated 3x3 conv (rate 2), then five branches over that map -- 1x1; 3x3 at rate 2; 3x3 at rate
@@ -448,17 +443,15 @@ def _deeplabv3_cifar():
     return layers, spec, shape
 
 
-EXTRA_NETWORKS["aspp_tiny"] = _aspp_tiny()
-EXTRA_NETWORKS["deeplabv3_cifar"] = _deeplabv3_cifar()
+NETWORKS["aspp_tiny"] = _aspp_tiny()
+NETWORKS["deeplabv3_cifar"] = _deeplabv3_cifar()
 
 
 def network(name):
-    """the (layers, spec, input shape) entry of a network of either registry"""
-    if name in NETWORKS:
-        return NETWORKS[name]
-    if name in EXTRA_NETWORKS:
-        return EXTRA_NETWORKS[name]
-    raise KeyError("unknown network %r" % (name,))
+    """the (layers, spec, input shape) entry of a network"""
+    if name not in NETWORKS:
+        raise KeyError("unknown network %r" % (name,))
+    return NETWORKS[name]
 
 
 def _walk(spec):
@@ -468,6 +461,10 @@ def _walk(spec):
             yield from _walk(op[2])
         else:
             yield op
+
+
+# the op names a spec may hold: build() refuses any other
+OPS = frozenset(("layer", "relu", "pool", "avgpool", "gap", "save", "branch", "add", "mul", "concat", "act", "upsample", "flatten"))
 
 
 def conv_groups(L):
@@ -489,10 +486,21 @@ def upsample_factors(factor):
 ALEXNET_MACS_PER_IMAGE = 1131201056
 
 
-def _macs_all(layers, ops, hw, saved):
-    """MACs of every weighted layer of `ops`, those inside branches included, with true taps (a dilated kernel's zeros are no
-    work); returns (macs, (h, w) behind the ops)"""
+# The networks whose figures were pinned while macs_per_image skipped the convs of a branch (projection shortcuts, fire
+# expands, the second up-conv of unet_tiny) and counted only the Linears found inside one.  Their figures are quoted in the
+# documents and pinned by tests, so they keep that counting.  This set is closed: a new network counts every weighted layer.
+MAIN_PATH_MACS = frozenset((
+    "alexnet", "simple_conv", "two_conv", "mnist_fc", "alexnet_paper", "resnet_tiny", "resnet_tiny_gap", "resnet18_cifar",
+    "fire_tiny", "squeezenet_cifar", "mobilenetv2_tiny", "act_tiny", "mobilenetv2_cifar", "se_tiny", "mobilenetv3_small_cifar",
+    "unet_tiny", "unet_cifar", "upsample_tiny", "unet_bilinear_cifar"))
+
+
+def _macs(layers, ops, hw, saved, branch_convs, in_branch=False):
+    """MACs of the weighted layers of `ops` from an (h, w) map on, those of its branches included, with true taps (a dilated
+    kernel's zeros are no work); without branch_convs a branch counts its Linears only.  Returns (macs, (h, w) behind the
+    ops)."""
     total = 0
+    convs = branch_convs or not in_branch
     h, w = hw
     for op in ops:
         if op[0] == "layer":
@@ -501,10 +509,10 @@ def _macs_all(layers, ops, hw, saved):
                 _, ic, oc, k, s, p = L[:6]
                 e = conv_dilation(L) * (k - 1) + 1
                 h, w = (h - e + 2 * p) // s + 1, (w - e + 2 * p) // s + 1
-                total += h * w * oc * (ic // conv_groups(L)) * k * k
-            elif L[0] == "deconv":
+                total += convs * h * w * oc * (ic // conv_groups(L)) * k * k
+            elif L[0] == "deconv":  # the real MACs: every input pixel meets every tap once
                 _, ic, oc, k, s, p, op_ = L
-                total += h * w * ic * oc * k * k
+                total += convs * h * w * ic * oc * k * k
                 h, w = (h - 1) * s - 2 * p + k + op_, (w - 1) * s - 2 * p + k + op_
             else:
                 total += L[1] * L[2]
@@ -518,48 +526,17 @@ def _macs_all(layers, ops, hw, saved):
         elif op[0] == "save":
             saved[op[1]] = (h, w)
         elif op[0] == "branch":
-            t, saved[op[1]] = _macs_all(layers, op[2], saved[op[1]], saved)
+            t, saved[op[1]] = _macs(layers, op[2], saved[op[1]], saved, branch_convs, True)
             total += t
+        # ("act", ...), like relu, flatten, add, mul and concat, has no MACs and keeps the shape
     return total, (h, w)
 
 
 def macs_per_image(name):
-    """MACs of one image through network(name), true taps.  Two countings, by registry: an entry of EXTRA_NETWORKS counts every
-    weighted layer, those inside branches included (_macs_all); an entry of NETWORKS keeps the older counting below, which
-    skips the convs of a branch -- its figures are pinned by tests and quoted in the documents."""
+    """MACs of one image through network(name): every weighted layer, true taps.  The networks of MAIN_PATH_MACS leave out
+    the convs of their branches."""
     layers, spec, (c, h, w) = network(name)
-    if name in EXTRA_NETWORKS:  # (every conv counts, the branches' too; the older entries keep their pinned figures below)
-        return _macs_all(layers, spec, (h, w), {})[0]
-    total = 0
-    for op in spec:
-        if op[0] == "layer":
-            L = layers[op[1]]
-            if L[0] == "conv":
-                _, ic, oc, k, s, p = L[:6]
-                e = conv_dilation(L) * (k - 1) + 1
-                h, w = (h - e + 2 * p) // s + 1, (w - e + 2 * p) // s + 1
-                total += h * w * oc * (ic // conv_groups(L)) * k * k
-                c = oc
-            elif L[0] == "deconv":  # the real MACs: every input pixel meets every tap once
-                _, ic, oc, k, s, p, op_ = L
-                total += h * w * ic * oc * k * k
-                h, w = (h - 1) * s - 2 * p + k + op_, (w - 1) * s - 2 * p + k + op_
-                c = oc
-            else:
-                total += L[1] * L[2]
-        elif op[0] in ("pool", "avgpool"):
-            h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
-        elif op[0] == "gap":
-            h, w = 1, 1
-        elif op[0] == "upsample":
-            fh, fw = upsample_factors(op[1])
-            h, w = h * fh, w * fw
-        elif op[0] == "branch":
-            # the Linears of a squeeze-and-excitation branch.  (the convs of a branch -- projection shortcuts, fire expands --
-            # have never been counted, and the figures of those networks are pinned: they stay as they are)
-            total += sum(layers[b[1]][1] * layers[b[1]][2] for b in _walk(op[2]) if b[0] == "layer" and layers[b[1]][0] == "fc")
-        # ("act", ...), like relu, add, mul and concat, has no MACs and keeps the shape
-    return total
+    return _macs(layers, spec, (h, w), {}, name not in MAIN_PATH_MACS)[0]
 
 
 def synthetic_state_dict(name, seed=42):
@@ -596,6 +573,9 @@ def build(name):
     import i8ie
 
     layers, spec, _ = network(name)
+    for op in _walk(spec):
+        if op[0] not in OPS:
+            raise ValueError("network %r: unknown spec op %r" % (name, op[0]))
 
     class SpecNet(i8ie.Module):
         def __init__(self):
@@ -613,13 +593,8 @@ def build(name):
                 if L[0] == "deconv":
                     setattr(self, attr, i8ie.ConvTranspose2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], output_padding=L[6]))
                 elif L[0] == "conv":
-                    if conv_dilation(L) != 1:
-                        setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], groups=conv_groups(L),
-                                                        dilation=L[7]))
-                    elif conv_groups(L) == 1:
-                        setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5]))
-                    else:
-                        setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], groups=L[6]))
+                    setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], groups=conv_groups(L),
+                                                    dilation=conv_dilation(L)))
                 else:
                     setattr(self, attr, i8ie.Linear(L[1], L[2]))
 
@@ -647,7 +622,7 @@ def build(name):
                     x = getattr(self, op[1])(x)
                 elif op[0] == "upsample":
                     x = i8ie.upsample(x, op[1], op[2])
-                else:
+                elif op[0] == "flatten":
                     x = x.reshape(-1, op[1])
             return x
 
@@ -674,26 +649,32 @@ def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, p
     return net
 
 
+def op_names(name, *kinds):
+    """the attribute names of the ops of the given kinds, in the order the spec names them, those of a branch included"""
+    return [op[1] for op in _walk(network(name)[1]) if op[0] in kinds]
+
+
 def layer_names(name):
-    """the weighted layers (Conv2d / Linear) in the order the spec names them, those of a branch included"""
-    return [op[1] for op in _walk(network(name)[1]) if op[0] == "layer"]
+    """the weighted layers (Conv2d / ConvTranspose2d / Linear)"""
+    return op_names(name, "layer")
 
 
 def add_names(name):
-    """the Adds of a residual network, in spec order"""
-    return [op[1] for op in _walk(network(name)[1]) if op[0] == "add"]
+    return op_names(name, "add")
 
 
 def mul_names(name):
-    """the Muls of a network, in spec order"""
-    return [op[1] for op in _walk(network(name)[1]) if op[0] == "mul"]
+    return op_names(name, "mul")
 
 
 def concat_names(name):
-    """the Concats of a network, in spec order"""
-    return [op[1] for op in _walk(network(name)[1]) if op[0] == "concat"]
+    return op_names(name, "concat")
 
 
 def activation_names(name):
-    """the Activations of a network, in spec order"""
-    return [op[1] for op in _walk(network(name)[1]) if op[0] == "act"]
+    return op_names(name, "act")
+
+
+def join_names(name):
+    """every op that is a module without weights (Add, Mul, Concat, Activation): those with output_qparams() beside the layers"""
+    return op_names(name, "add", "mul", "concat", "act")

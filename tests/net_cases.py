@@ -1,0 +1,61 @@
+"""What every bit-exact network test on the GPU shares (tests/test_gpu_add.py ... test_gpu_dilated.py): the calibrated network
+with what tests/spec_ref.py needs to restate it, and the comparison of the product's output with the expected bytes -- eager,
+under the force-fallback option, replayed as a HIP graph, and after a save / load round trip.  A test keeps what is its own:
+its input, its traced tensors and their limits, its shapes and counts."""
+import numpy as np
+
+import spec_ref as sr
+
+_CALIBRATED = {}
+
+
+def calibrated(name, per_channel, calib_images=None):
+    """(net, qlayers, qp, jqp) of network `name` with the synthetic weights of sr.WEIGHT_SEED, calibrated once per argument
+    triple.  calib_images: None for workloads.calibrated's own batch, or the number of images of sr.CALIB_SEED.  qp holds the
+    output_qparams() of wl.layer_names(name), jqp those of wl.join_names(name)."""
+    from int8inferenceengine_amd import workloads as wl
+
+    key = (name, per_channel, calib_images)
+    if key not in _CALIBRATED:
+        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
+        batch = None if calib_images is None else wl.synthetic_input(name, calib_images, seed=sr.CALIB_SEED)
+        net = wl.calibrated(name, sd, calib_batch=batch, per_channel=per_channel)
+        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
+        jqp = {a: getattr(net, a).output_qparams() for a in wl.join_names(name)}
+        _CALIBRATED[key] = (net, sr.quantize_layers(wl.network(name), sd, per_channel), qp, jqp)
+    return _CALIBRATED[key]
+
+
+def _same(got, want):
+    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def check_bit_exact(i8ie, net, name, x, want, *, fallback=False, graph=False, reload_dir=None, expect_jqp=None):
+    """net(x) is `want` bit for bit; returns the eager output.  fallback: also under cx.force_fallback(True).  graph: also two
+    replays of the forward captured as one HIP graph.  reload_dir: also a fresh wl.build(name) that loaded what
+    net.save_quantized() wrote there, which then answers expect_jqp (name -> output_qparams()) as well."""
+    import _CXX_i8ie as cx
+    from int8inferenceengine_amd import workloads as wl
+    from int8inferenceengine_amd.graph import GraphedForward
+
+    got = net(i8ie.tensor(x)).numpy()
+    assert _same(got, want), "eager"
+    if fallback:
+        cx.force_fallback(True)
+        try:
+            fb = net(i8ie.tensor(x)).numpy()
+        finally:
+            cx.force_fallback(False)
+        assert _same(fb, want), "force_fallback"
+    if graph:
+        g = GraphedForward(net, i8ie.tensor(x).prefetch())
+        for _ in range(2):
+            assert _same(g().numpy(), want), "graph replay"
+    if reload_dir is not None:
+        path = str(reload_dir / (name + ".npz"))
+        net.save_quantized(path)
+        fresh = wl.build(name)
+        fresh.load_quantized_file(path)
+        assert {a: getattr(fresh, a).output_qparams() for a in expect_jqp or {}} == (expect_jqp or {})
+        assert _same(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
+    return got

@@ -74,7 +74,7 @@ def case(name, per_channel, run=run, fp32_qparams=None, quantize_layers=None):
         out["qparams"] = {a: [int(np.float32(s).view(np.uint32)), int(zp)] for a, (s, zp) in sorted(dict(qp, **jqp).items())}
     else:
         qp = synthetic_qparams(wl.layer_names(name))
-        jqp = synthetic_qparams(wl.add_names(name) + wl.mul_names(name) + wl.concat_names(name) + wl.activation_names(name))
+        jqp = synthetic_qparams(wl.join_names(name))
     qlayers = (quantize_layers or sr.quantize_layers)(entry, sd, per_channel)
     logits, trace = run(family, entry, wl.synthetic_input(name, BATCH, seed=sr.INPUT_SEED), qlayers, qp, jqp, per_channel)
     assert logits.dtype == np.float32 and logits.shape[0] == BATCH

@@ -8,6 +8,7 @@ import pytest
 
 import abi
 import deconv_ref as dr
+import pinned_networks as pn
 import spec_ref as sr
 
 f32 = np.float32
@@ -252,10 +253,8 @@ def test_unet_cifar_workload():
 def test_existing_networks_keep_their_macs():
     from int8inferenceengine_amd import workloads as wl
 
-    before = {"alexnet": 1131201056, "simple_conv": 25252800, "resnet_tiny": 9572352, "resnet18_cifar": 549131264,
-              "fire_tiny": 1344128, "squeezenet_cifar": 5224448, "mobilenetv2_tiny": 4375168, "act_tiny": 2092192,
-              "mobilenetv2_cifar": 87976448, "alexnet_paper": 720351776, "resnet_tiny_gap": 9552192}
-    assert {n: wl.macs_per_image(n) for n in before} == before
+    before = pn.NAMES[:pn.NAMES.index("unet_tiny")]
+    assert len(before) == 15 and {n: wl.macs_per_image(n) for n in before} == {n: pn.MACS[n] for n in before}
     sd = wl.synthetic_state_dict("two_conv")  # (the draw order of the existing networks is unchanged)
     assert sd["conv1.weight"].shape == (20, 1, 5, 5)
 

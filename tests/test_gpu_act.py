@@ -13,6 +13,7 @@ import abi
 import act_ref as ar
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import net_cases as nc
 import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -388,69 +389,37 @@ def test_activation_is_calibrated_like_a_layer(i8ie, mode):
 
 
 # ---- the networks ------------------------------------------------------------------------------------------------------
-_NETS = {}
-
-
-def _net(name, per_channel):
-    from int8inferenceengine_amd import workloads as wl
-
-    if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
-        net = wl.calibrated(name, sd, per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-        jqp = {a: getattr(net, a).output_qparams() for a in wl.activation_names(name) + wl.add_names(name)}
-        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
-    return _NETS[(name, per_channel)]
-
-
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [1, 5])
 @pytest.mark.parametrize("name", ["mobilenetv2_tiny", "act_tiny"])
 def test_tiny_networks_bit_exact(i8ie, name, batch, per_channel, tmp_path):
-    import _CXX_i8ie as cx
     from int8inferenceengine_amd import workloads as wl
-    from int8inferenceengine_amd.graph import GraphedForward
 
-    net, qlayers, qp, jqp = _net(name, per_channel)
+    net, qlayers, qp, jqp = nc.calibrated(name, per_channel)
+    assert sorted(jqp) == sorted(wl.activation_names(name) + wl.add_names(name))
     assert all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
     x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
     trace = {}
     want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, sr.outputs_of("act", trace))
     stats = ar.nontrivial(trace)  # the expected bytes discriminate
     print({a: (d, round(s, 3)) for a, (d, s) in stats.items()})
-    assert list(trace) == wl.activation_names(name)
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (batch, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
-    if batch != 5 or per_channel:
-        return
-    if name == "mobilenetv2_tiny":  # replayed as one HIP graph: the table travels in the kernel arguments
-        g = GraphedForward(net, i8ie.tensor(x).prefetch())
-        for _ in range(2):
-            assert np.array_equal(g().numpy().view(np.uint32), want.view(np.uint32))
-    path = str(tmp_path / (name + ".npz"))
-    net.save_quantized(path)
-    fresh = wl.build(name)
-    fresh.load_quantized_file(path)
-    assert {a: getattr(fresh, a).output_qparams() for a in jqp} == jqp
-    assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), want.view(np.uint32))
+    assert list(trace) == wl.activation_names(name) and want.shape == (batch, 10)
+    more = batch == 5 and not per_channel
+    # (mobilenetv2_tiny replayed as one HIP graph: the table travels in the kernel arguments)
+    nc.check_bit_exact(i8ie, net, name, x, want, fallback=True, graph=more and name == "mobilenetv2_tiny",
+                       reload_dir=tmp_path if more else None, expect_jqp=jqp)
 
 
 def test_mobilenetv2_cifar_bit_exact(i8ie):
     from int8inferenceengine_amd import workloads as wl
 
     name = "mobilenetv2_cifar"
-    net, qlayers, qp, jqp = _net(name, False)
+    net, qlayers, qp, jqp = nc.calibrated(name, False)
     assert len(jqp) == 35 + 10 and all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
     x = wl.synthetic_input(name, 2, seed=sr.INPUT_SEED)
     trace = {}
     want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, False, sr.outputs_of("act", trace))
     stats = ar.nontrivial(trace)
     print({a: (d, round(s, 3)) for a, (d, s) in stats.items()})
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (2, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert want.shape == (2, 10)
+    nc.check_bit_exact(i8ie, net, name, x, want)

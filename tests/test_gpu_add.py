@@ -12,6 +12,7 @@ import pytest
 import abi
 import add_ref as ar
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import net_cases as nc
 import pointwise_util as pu
 import spec_ref as sr
 
@@ -304,50 +305,16 @@ def test_add_is_calibrated_like_a_layer(i8ie, mode):
 
 
 # ---- the residual network ----------------------------------------------------------------------------------------------
-_NETS = {}
-
-
-def _resnet(per_channel):
-    from int8inferenceengine_amd import workloads as wl
-
-    if per_channel not in _NETS:
-        name = "resnet_tiny"
-        sd = wl.synthetic_state_dict(name)
-        net = wl.calibrated(name, sd, per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-        aqp = {a: getattr(net, a).output_qparams() for a in wl.add_names(name)}
-        _NETS[per_channel] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, aqp)
-    return _NETS[per_channel]
-
-
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [2, 66])
 def test_resnet_tiny_bit_exact(i8ie, batch, per_channel, tmp_path):
-    import _CXX_i8ie as cx
     from int8inferenceengine_amd import workloads as wl
-    from int8inferenceengine_amd.graph import GraphedForward
 
     name = "resnet_tiny"
-    net, qlayers, qp, aqp = _resnet(per_channel)
-    assert all(s > 0 and s != 1.0 for s, _ in aqp.values()), aqp  # the Adds were calibrated
+    net, qlayers, qp, aqp = nc.calibrated(name, per_channel)
+    assert sorted(aqp) == sorted(wl.add_names(name)) and all(s > 0 and s != 1.0 for s, _ in aqp.values()), aqp  # the Adds were calibrated
     x = wl.synthetic_input(name, batch, seed=5)
     want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, aqp, per_channel)
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (batch, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
-    if batch != 2:
-        return
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert np.array_equal(g().numpy().view(np.uint32), want.view(np.uint32))
-    path = str(tmp_path / "resnet_tiny.npz")
-    net.save_quantized(path)
-    fresh = wl.build(name)
-    fresh.load_quantized_file(path)
-    assert {a: getattr(fresh, a).output_qparams() for a in wl.add_names(name)} == aqp
-    assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), want.view(np.uint32))
+    assert want.shape == (batch, 10)
+    nc.check_bit_exact(i8ie, net, name, x, want, fallback=True, graph=batch == 2, reload_dir=tmp_path if batch == 2 else None,
+                       expect_jqp=aqp)

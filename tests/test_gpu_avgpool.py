@@ -21,6 +21,7 @@ import avgpool_ref as apr
 import f64_ref
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import net_cases as nc
 import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -400,51 +401,18 @@ def test_surface_user_tensor_qparams_and_errors(i8ie):
 
 
 # ---- 5. the networks ---------------------------------------------------------------------------------------------------
-_NETS = {}
-
-
-def _net(name, per_channel):
-    from int8inferenceengine_amd import workloads as wl
-
-    if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name)
-        net = wl.calibrated(name, sd, calib_batch=wl.synthetic_input(name, 16, seed=99), per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-        aqp = {a: getattr(net, a).output_qparams() for a in wl.add_names(name)}
-        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, aqp)
-    return _NETS[(name, per_channel)]
-
-
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("name,batch", [("resnet_tiny_gap", 2), ("resnet_tiny_gap", 66), ("resnet18_cifar", 2), ("resnet18_cifar", 9)])
 def test_networks_bit_exact(i8ie, name, batch, per_channel, tmp_path):
-    import _CXX_i8ie as cx
     from int8inferenceengine_amd import workloads as wl
-    from int8inferenceengine_amd.graph import GraphedForward
 
-    net, qlayers, qp, aqp = _net(name, per_channel)
-    assert all(s > 0 and s != 1.0 for s, _ in aqp.values()), aqp  # the Adds were calibrated
+    net, qlayers, qp, aqp = nc.calibrated(name, per_channel, calib_images=16)
+    assert sorted(aqp) == sorted(wl.add_names(name)) and all(s > 0 and s != 1.0 for s, _ in aqp.values()), aqp  # the Adds were calibrated
     x = wl.synthetic_input(name, batch, seed=5)
     want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, aqp, per_channel)
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (batch, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
-    if (name, batch) != ("resnet_tiny_gap", 2):
-        return
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert np.array_equal(g().numpy().view(np.uint32), want.view(np.uint32))
-    path = str(tmp_path / "net.npz")
-    net.save_quantized(path)
-    fresh = wl.build(name)
-    fresh.load_quantized_file(path)
-    assert {a: getattr(fresh, a).output_qparams() for a in wl.add_names(name)} == aqp
-    assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), want.view(np.uint32))
+    assert want.shape == (batch, 10)
+    both = (name, batch) == ("resnet_tiny_gap", 2)
+    nc.check_bit_exact(i8ie, net, name, x, want, fallback=True, graph=both, reload_dir=tmp_path if both else None, expect_jqp=aqp)
 
 
 # ---- 6. FP32 resnet_tiny_gap before convert() --------------------------------------------------------------------------

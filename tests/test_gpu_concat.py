@@ -12,6 +12,7 @@ import pytest
 import abi
 import concat_ref as cr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import net_cases as nc
 import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -449,21 +450,6 @@ def test_concat_is_calibrated_like_a_layer(i8ie, mode, tmp_path):
 
 
 # ---- the fire networks -------------------------------------------------------------------------------------------------
-_NETS = {}
-
-
-def _net(name, per_channel):
-    from int8inferenceengine_amd import workloads as wl
-
-    if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name)
-        net = wl.calibrated(name, sd, per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-        jqp = {a: getattr(net, a).output_qparams() for a in wl.concat_names(name) + wl.add_names(name)}
-        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
-    return _NETS[(name, per_channel)]
-
-
 def _saturated(trace, jqp):
     """(clamped, literal): two shares of the Concats' expected bytes.
     clamped  bytes that sit on a clamp: 255, or 0 where 0 is not the zero point itself.  Behind a ReLU the calibrated zero
@@ -481,12 +467,10 @@ def _saturated(trace, jqp):
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [2, 66])
 def test_fire_tiny_bit_exact(i8ie, batch, per_channel, tmp_path):
-    import _CXX_i8ie as cx
     from int8inferenceengine_amd import workloads as wl
-    from int8inferenceengine_amd.graph import GraphedForward
 
     name = "fire_tiny"
-    net, qlayers, qp, jqp = _net(name, per_channel)
+    net, qlayers, qp, jqp = nc.calibrated(name, per_channel)
     assert sorted(jqp) == ["facat", "fbcat", "rcat"] and all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
     x = wl.synthetic_input(name, batch, seed=5)
     trace = {}
@@ -494,38 +478,22 @@ def test_fire_tiny_bit_exact(i8ie, batch, per_channel, tmp_path):
     sat, literal = _saturated(trace, jqp)
     print("concat bytes on a clamp: %.4f, bytes 0 / 255: %.4f" % (sat, literal), jqp)
     assert sorted(trace) == sorted(jqp) and sat < 0.2 and literal < 0.6, (sat, literal)  # the expected bytes discriminate
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (batch, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
-    if batch != 2:
-        return
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert np.array_equal(g().numpy().view(np.uint32), want.view(np.uint32))
-    path = str(tmp_path / "fire_tiny.npz")
-    net.save_quantized(path)
-    fresh = wl.build(name)
-    fresh.load_quantized_file(path)
-    assert {a: getattr(fresh, a).output_qparams() for a in jqp} == jqp
-    assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), want.view(np.uint32))
+    assert want.shape == (batch, 10)
+    nc.check_bit_exact(i8ie, net, name, x, want, fallback=True, graph=batch == 2, reload_dir=tmp_path if batch == 2 else None,
+                       expect_jqp=jqp)
 
 
 def test_squeezenet_cifar_bit_exact(i8ie):
     from int8inferenceengine_amd import workloads as wl
 
     name = "squeezenet_cifar"
-    net, qlayers, qp, jqp = _net(name, False)
-    assert len(jqp) == 8 and all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
+    net, qlayers, qp, jqp = nc.calibrated(name, False)
+    assert sorted(jqp) == sorted(wl.concat_names(name)) and len(jqp) == 8 and all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
     x = wl.synthetic_input(name, 2, seed=5)
     trace = {}
     want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, False, sr.outputs_of("concat", trace))
     sat, literal = _saturated(trace, jqp)
     print("concat bytes on a clamp: %.4f, bytes 0 / 255: %.4f" % (sat, literal))
     assert sat < 0.2 and literal < 0.6, (sat, literal)
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (2, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert want.shape == (2, 10)
+    nc.check_bit_exact(i8ie, net, name, x, want)

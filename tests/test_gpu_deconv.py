@@ -14,6 +14,7 @@ import deconv_ref as dr
 import f64_ref
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import net_cases as nc
 import orc
 import spec_ref as sr
 
@@ -315,21 +316,6 @@ def test_save_load_round_trip_of_one_layer(i8ie, per_channel, tmp_path):
 
 
 # ---- the networks ------------------------------------------------------------------------------------------------------
-_NETS = {}
-
-
-def _net(name, per_channel):
-    from int8inferenceengine_amd import workloads as wl
-
-    if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
-        net = wl.calibrated(name, sd, calib_batch=wl.synthetic_input(name, 8, seed=sr.CALIB_SEED), per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-        jqp = {a: getattr(net, a).output_qparams() for a in wl.concat_names(name)}
-        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
-    return _NETS[(name, per_channel)]
-
-
 _WANT = {}
 
 
@@ -337,7 +323,7 @@ def _want(name, batch, per_channel):
     from int8inferenceengine_amd import workloads as wl
 
     if (name, batch, per_channel) not in _WANT:
-        net, qlayers, qp, jqp = _net(name, per_channel)
+        net, qlayers, qp, jqp = nc.calibrated(name, per_channel, calib_images=8)
         x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
         trace = {}
         want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, dr.tracer(wl.NETWORKS[name][0], trace))
@@ -349,34 +335,15 @@ def _want(name, batch, per_channel):
 @pytest.mark.parametrize("batch", [2, 66])
 @pytest.mark.parametrize("name", ["unet_tiny", "unet_cifar"])
 def test_unet_bit_exact(i8ie, name, batch, per_channel, tmp_path):
-    import _CXX_i8ie as cx
     from int8inferenceengine_amd import workloads as wl
-    from int8inferenceengine_amd.graph import GraphedForward
 
-    net, qlayers, qp, jqp = _net(name, per_channel)
+    net, qlayers, qp, jqp = nc.calibrated(name, per_channel, calib_images=8)
     x, want, trace = _want(name, batch, per_channel)
     ups = [a for a, L in wl.NETWORKS[name][0].items() if L[0] == "deconv"]
-    assert sorted(trace) == sorted(ups) and len(ups) == 3
+    assert sorted(trace) == sorted(ups) and len(ups) == 3 and sorted(jqp) == sorted(wl.concat_names(name))
     print({a: round(float(((q == 0) | (q == 255)).mean()), 3) for a, q in trace.items()})
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (batch, 10, 32, 32) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    if name != "unet_tiny":
-        return
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
-    if batch == 2:
-        path = str(tmp_path / (name + ".npz"))
-        net.save_quantized(path)
-        fresh = wl.build(name)
-        fresh.load_quantized_file(path)
-        assert {a: getattr(fresh, a).output_qparams() for a in jqp} == jqp
-        assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), want.view(np.uint32))
-    # replayed as one HIP graph (the packed phase panels keep their addresses): the same bytes as the eager run, at both
-    # batch sizes on the one network
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert np.array_equal(g().numpy().view(np.uint32), got.view(np.uint32))
+    assert want.shape == (batch, 10, 32, 32)
+    # unet_tiny also replayed as one HIP graph (the packed phase panels keep their addresses), at both batch sizes
+    tiny = name == "unet_tiny"
+    nc.check_bit_exact(i8ie, net, name, x, want, fallback=tiny, graph=tiny, reload_dir=tmp_path if tiny and batch == 2 else None,
+                       expect_jqp=jqp)

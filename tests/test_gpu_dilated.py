@@ -13,6 +13,7 @@ import dilated_ref as dl
 import f64_ref
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import net_cases as nc
 import orc
 import spec_ref as sr
 import upsample_ref as ur
@@ -289,7 +290,7 @@ def test_nhwc_dilated_conv_relu_is_one_launch(i8ie):
 def test_prepare_convert_save_load(i8ie, tmp_path):
     from int8inferenceengine_amd import workloads as wl
 
-    net = _net("aspp_tiny", False)[0]  # (prepare() -> an FP32 batch through the dilated FP32 conv -> convert())
+    net = nc.calibrated("aspp_tiny", False, calib_images=8)[0]  # (prepare() -> an FP32 batch through the dilated FP32 conv -> convert())
     x = wl.synthetic_input("aspp_tiny", 3, seed=sr.INPUT_SEED)
     want = net(i8ie.tensor(x)).numpy()
     path = str(tmp_path / "aspp.npz")
@@ -301,41 +302,19 @@ def test_prepare_convert_save_load(i8ie, tmp_path):
 
 
 # ---- the networks ---------------------------------------------------------------------------------------------------------
-_NETS = {}
-
-
-def _net(name, per_channel):
-    from int8inferenceengine_amd import workloads as wl
-
-    if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
-        net = wl.calibrated(name, sd, calib_batch=wl.synthetic_input(name, 8, seed=sr.CALIB_SEED), per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-        jqp = {a: getattr(net, a).output_qparams() for a in wl.add_names(name) + wl.concat_names(name)}
-        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.network(name), sd, per_channel), qp, jqp)
-    return _NETS[(name, per_channel)]
-
-
 @pytest.mark.parametrize("name,per_channel", [("aspp_tiny", False), ("aspp_tiny", True), ("deeplabv3_cifar", False)],
                          ids=["aspp_tiny-per_tensor", "aspp_tiny-per_channel", "deeplabv3_cifar-per_tensor"])
 def test_networks_bit_exact(i8ie, name, per_channel):
     from int8inferenceengine_amd import workloads as wl
-    from int8inferenceengine_amd.graph import GraphedForward
 
     batch = 2 if name == "deeplabv3_cifar" else 5
-    net, qlayers, qp, jqp = _net(name, per_channel)
+    net, qlayers, qp, jqp = nc.calibrated(name, per_channel, calib_images=8)
     x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
     trace = []
     want = sr.forward(wl.network(name), x, qlayers, qp, jqp, per_channel, ur.tracer(trace))
     assert len(trace) == 2 and all(len(np.unique(q)) > 30 for _, q in trace[1:])  # (the head's maps are not saturated)
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (batch, 10, 32, 32)
-    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    if name != "aspp_tiny":
-        return
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert np.array_equal(g().numpy().view(np.uint32), want.view(np.uint32))
+    assert want.shape == (batch, 10, 32, 32)
+    nc.check_bit_exact(i8ie, net, name, x, want, graph=name == "aspp_tiny")
 
 
 def test_fp32_deeplabv3_convs_layer_by_layer(i8ie):

@@ -14,6 +14,7 @@ import abi
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import mul_ref as mr
+import net_cases as nc
 import pointwise_util as pu
 import spec_ref as sr
 
@@ -443,72 +444,34 @@ def test_mul_is_calibrated_like_a_layer(i8ie, mode):
 
 
 # ---- the networks ------------------------------------------------------------------------------------------------------
-_NETS = {}
-
-
-def _net(name, per_channel):
-    from int8inferenceengine_amd import workloads as wl
-
-    if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
-        net = wl.calibrated(name, sd, per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-        jqp = {a: getattr(net, a).output_qparams() for a in wl.activation_names(name) + wl.add_names(name) + wl.mul_names(name)}
-        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
-    return _NETS[(name, per_channel)]
-
-
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [2, 66])
 def test_se_tiny_bit_exact(i8ie, batch, per_channel, tmp_path):
-    import _CXX_i8ie as cx
     from int8inferenceengine_amd import workloads as wl
-    from int8inferenceengine_amd.graph import GraphedForward
 
     name = "se_tiny"
-    net, qlayers, qp, jqp = _net(name, per_channel)
+    net, qlayers, qp, jqp = nc.calibrated(name, per_channel)
+    assert sorted(jqp) == sorted(wl.activation_names(name) + wl.mul_names(name))
     assert all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp  # the Muls and Activations were calibrated
     x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
     trace = {}
     want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, mr.tracer(wl.NETWORKS[name][1], trace))
     stats = mr.nontrivial(trace)  # the expected bytes discriminate
     print({a: (d, round(s, 3)) for a, (d, s) in stats.items()})
-    assert list(trace) == wl.mul_names(name)
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (batch, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
-    if batch != 2:
-        return
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())  # replayed as one HIP graph: the same bytes as the eager run
-    for _ in range(2):
-        assert np.array_equal(g().numpy().view(np.uint32), got.view(np.uint32))
-    path = str(tmp_path / "se_tiny.npz")
-    net.save_quantized(path)
-    fresh = wl.build(name)
-    fresh.load_quantized_file(path)
-    assert {a: getattr(fresh, a).output_qparams() for a in jqp} == jqp
-    assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), want.view(np.uint32))
+    assert list(trace) == wl.mul_names(name) and want.shape == (batch, 10)
+    nc.check_bit_exact(i8ie, net, name, x, want, fallback=True, graph=batch == 2, reload_dir=tmp_path if batch == 2 else None,
+                       expect_jqp=jqp)
 
 
 def test_mobilenetv3_small_cifar_bit_exact(i8ie, tmp_path):
     from int8inferenceengine_amd import workloads as wl
 
     name = "mobilenetv3_small_cifar"
-    net, qlayers, qp, jqp = _net(name, False)
+    net, qlayers, qp, jqp = nc.calibrated(name, False)
     assert len(wl.mul_names(name)) == 9 and all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp
     x = wl.synthetic_input(name, 2, seed=sr.INPUT_SEED)
     trace = {}
     want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, False, mr.tracer(wl.NETWORKS[name][1], trace))
     print({a: (len(np.unique(g)), round(float(((q == 0) | (q == 255)).mean()), 3)) for a, (g, q, _) in trace.items()})
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == (2, 10) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    path = str(tmp_path / (name + ".npz"))
-    net.save_quantized(path)
-    fresh = wl.build(name)
-    fresh.load_quantized_file(path)
-    assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), want.view(np.uint32))
+    assert want.shape == (2, 10)
+    nc.check_bit_exact(i8ie, net, name, x, want, reload_dir=tmp_path)

@@ -13,6 +13,7 @@ import abi
 import f64_ref
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import net_cases as nc
 import pointwise_util as pu
 import spec_ref as sr
 import upsample_ref as ur
@@ -338,26 +339,14 @@ def test_surface_user_tensor_qparams_and_errors(i8ie):
 
 
 # ---- 8. the networks ---------------------------------------------------------------------------------------------------
-_NETS, _WANT = {}, {}
-
-
-def _net(name, per_channel):
-    from int8inferenceengine_amd import workloads as wl
-
-    if (name, per_channel) not in _NETS:
-        sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
-        net = wl.calibrated(name, sd, calib_batch=wl.synthetic_input(name, 8, seed=sr.CALIB_SEED), per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in wl.layer_names(name)}
-        jqp = {a: getattr(net, a).output_qparams() for a in wl.add_names(name) + wl.concat_names(name)}
-        _NETS[(name, per_channel)] = (net, sr.quantize_layers(wl.NETWORKS[name], sd, per_channel), qp, jqp)
-    return _NETS[(name, per_channel)]
+_WANT = {}
 
 
 def _want(name, batch, per_channel):
     from int8inferenceengine_amd import workloads as wl
 
     if (name, batch, per_channel) not in _WANT:
-        net, qlayers, qp, jqp = _net(name, per_channel)
+        net, qlayers, qp, jqp = nc.calibrated(name, per_channel, calib_images=8)
         x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
         trace = []
         want = sr.forward(wl.NETWORKS[name], x, qlayers, qp, jqp, per_channel, ur.tracer(trace))
@@ -369,23 +358,14 @@ def _want(name, batch, per_channel):
 @pytest.mark.parametrize("batch", [2, 9])
 @pytest.mark.parametrize("name", ["upsample_tiny", "unet_bilinear_cifar"])
 def test_networks_bit_exact(i8ie, name, batch, per_channel):
-    from int8inferenceengine_amd import workloads as wl
-    from int8inferenceengine_amd.graph import GraphedForward
-
-    net, qlayers, qp, jqp = _net(name, per_channel)
+    net = nc.calibrated(name, per_channel, calib_images=8)[0]
     x, want, trace = _want(name, batch, per_channel)
     assert len(trace) == (5 if name == "upsample_tiny" else 3)
     print([(op[1:], len(np.unique(q))) for op, q in trace])
     assert all(len(np.unique(q)) > 30 for _, q in trace)  # (the upsampled tensors are not saturated)
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape == ((batch, 10, 32, 48) if name == "upsample_tiny" else (batch, 10, 32, 32))
-    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    if name != "upsample_tiny":
-        return
-    # captured and replayed as one HIP graph: the same bytes as the eager run
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert np.array_equal(g().numpy().view(np.uint32), want.view(np.uint32))
+    assert want.shape == ((batch, 10, 32, 48) if name == "upsample_tiny" else (batch, 10, 32, 32))
+    # (upsample_tiny also captured and replayed as one HIP graph)
+    nc.check_bit_exact(i8ie, net, name, x, want, graph=name == "upsample_tiny")
 
 
 def _bits_equal(a, b):

@@ -1,7 +1,7 @@
 """tests/spec_ref.py against the interpreters it replaced, on the CPU alone.  tests/golden/
 spec_ref_digests.json holds what those gave for every case of tests/spec_ref_cases.py: every registry network, per tensor
 and per channel, its traced tensors and the parameters of the float64 calibration stand-in.  The replay must give the same
-digests; an op name outside spec_ref.OPS must raise; and OPS must hold every op name of both registries."""
+digests; an op name outside spec_ref.OPS must raise; and OPS must hold every op name of the registry."""
 import json
 import os
 
@@ -28,11 +28,11 @@ def _op_names(spec):
 def test_the_table_covers_both_registries_and_every_op():
     from int8inferenceengine_amd import workloads as wl
 
-    names = list(wl.NETWORKS) + list(wl.EXTRA_NETWORKS)
+    names = list(wl.NETWORKS)
     assert sorted(sc.FAMILY) == sorted(names)
     assert sorted(DIGESTS) == sorted("%s-%s" % (n, t) for n in names for t in ("pt", "pc"))
     seen = set().union(*[_op_names(wl.network(n)[1]) for n in names])
-    assert seen == sr.OPS  # every op of the registries is known, and the replay below runs every known op
+    assert seen == sr.OPS == wl.OPS  # every op of the registry is known to both interpreters, and the replay below runs every known op
     assert seen - {"branch"} == {op[0] for n in names for op in wl._walk(wl.network(n)[1])}
     kinds = {wl.network(n)[0][a][0] for n in names for a in wl.layer_names(n)}
     assert kinds == {"conv", "deconv", "fc"}

@@ -91,21 +91,10 @@ def test_fp32_restatement_close_to_float64():
 
 
 # ---- workloads.py ------------------------------------------------------------------------------------------------------------
-# macs_per_image of every network that existed before the ("upsample", ...) spec op
-PINNED_MACS = {
-    "alexnet": 1131201056, "simple_conv": 25252800, "two_conv": 2293000, "mnist_fc": 7840, "alexnet_paper": 720351776,
-    "resnet_tiny": 9572352, "resnet_tiny_gap": 9552192, "resnet18_cifar": 549131264, "fire_tiny": 1344128,
-    "squeezenet_cifar": 5224448, "mobilenetv2_tiny": 4375168, "act_tiny": 2092192, "mobilenetv2_cifar": 87976448,
-    "se_tiny": 2093608, "mobilenetv3_small_cifar": 17507328, "unet_tiny": 6913024, "unet_cifar": 574947328,
-}
-
-
 def test_macs_of_existing_networks_unchanged():
+    """(the figures of the networks before the ("upsample", ...) spec op: tests/test_workloads_host.py)"""
     from int8inferenceengine_amd import workloads as wl
 
-    assert set(wl.NETWORKS) == set(PINNED_MACS) | {"upsample_tiny", "unet_bilinear_cifar"}
-    for name, macs in PINNED_MACS.items():
-        assert wl.macs_per_image(name) == macs, name
     # a bilinear x2 and a 1x1 conv at four times the pixels cost what the 2x2 stride-2 up-conv costs
     assert wl.macs_per_image("unet_bilinear_cifar") == wl.macs_per_image("unet_cifar")
     # upsample_tiny by hand: (pixels, out_c, in_c * k * k) of every conv outside a branch
