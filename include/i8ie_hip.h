@@ -702,6 +702,83 @@ int i8ie_lut_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in
  * tanh go through the device's double-precision exp / tanh (DESIGN.md section 8f states the error bound). */
 int i8ie_activation_f32(i8ie_ctx* ctx, int kind, float param, const float* in_dev, float* out_dev, int64_t n);
 
+/* ---- quantized batched MatMul of two activation tensors (no counterpart in the reference: every op of it multiplies
+ * by static weights) ------------------------------------------------------------------------------------------------
+ * Logical form A [b, m, k] . B [b, k, n] -> [b, m, n]; both operands are u8 tensors with their own (scale, zero_point),
+ * the same b on both sides (no broadcast).  The exact int32 sum is
+ *     C[b,i,j] = sum_k ((int)a[b,i,k] - zp_a) * ((int)b[b,k,j] - zp_b)
+ * k <= 32768 keeps |C| <= 255 * 255 * 32768 < 2^31; a larger k is I8IE_ERR_ARG.  Then
+ *     out = down_scale(C, s_a, s_b, s_out, zp_out)        src/quantize_utils.cc:27-36 (csrc/i8ie_requant.h):
+ *           deq = ((float)C * s_a) * s_b;  t = deq / s_out + (float)zp_out;  q = t >= 255 ? 255 : (t < 0 ? 0 : (u8)t)
+ *     out = relu ? max(q, zp_out) : q                     relu<u8>, src/functional.cc:15-26
+ * There is no bias and no alpha: a 1/sqrt(d) factor folds into the weights of the projection that makes the operand.
+ * Scales must be finite and s_out > 0.
+ * Each operand and the result is described physically (i8ie_bmm_mat): element (batch, row, col) of the logical matrix
+ * lies at ptr[batch * batch_stride + row * row_stride + col * col_stride], and one of row_stride, col_stride must be 1.
+ * A is [m, k] (rows i, columns k), B is [k, n] (rows k, columns j), the result [m, n]: an operand given transposed
+ * ([b, k, m] / [b, n, k]) is the same matrix with its two strides exchanged, so a K-contiguous and a K-strided operand
+ * are accepted on either side.  s8 != 0: the bytes are stored re-biased (^0x80, I8IE_LAYOUT_NHWC_S8).
+ * The result may instead be the interior of a bordered NHWC feature map [b, h+2B, w+2B, c]: out_pix_axis = 1 (the m
+ * rows are the h*w pixels, m == out_h * out_w) or 2 (the n columns are), out_border = B > 0.  `out.ptr` is then the
+ * buffer's first byte, out.batch_stride = (h+2B)*(w+2B)*c, the pixel axis' stride is c and the other stride 1; pixel p
+ * lies at physical pixel (p / w + B) * (w + 2B) + p % w + B.  Only the interior is written: border bytes are the
+ * caller's, as for i8ie_add_u8_nhwc.  out_pix_axis = 0 is the plain strided form.  `out` must not overlap an operand (a
+ * and b may be the same buffer).  As in the other stateless entries, extents are the caller's responsibility: neither the
+ * overlap nor whether the strides describe disjoint elements inside the caller's allocations is checked.
+ * acc_dbg_dev is NULL or int32 [b, m, n] and receives C.  Stateless and capturable in a graph: one launch, no device
+ * allocation.  Every argument error (null pointers, non-positive sizes, k > 32768, both strides != 1, negative strides,
+ * bad scales, a pixel axis that does not match) is I8IE_ERR_ARG before any device call.
+ * Two kernels with identical bytes (csrc/i8ie_matmul.hip): bmm_mfma, and bmm_direct for k < 16,
+ * for a, b or out not 16-byte aligned, for strides beyond 2^31 and for everything under I8IE_OPT_FORCE_FALLBACK. */
+typedef struct i8ie_bmm_mat {
+  void* ptr;              /* device pointer (read-only for an operand) */
+  int64_t batch_stride;   /* elements between two batch items */
+  int64_t row_stride;     /* ... between two rows of the logical matrix */
+  int64_t col_stride;     /* ... between two columns; one of row_stride, col_stride is 1 */
+  int s8;                 /* != 0: bytes stored re-biased (^0x80) */
+} i8ie_bmm_mat;
+typedef struct i8ie_bmm_args {
+  int b, m, n, k;
+  i8ie_bmm_mat a;         /* [m, k] */
+  i8ie_bmm_mat bm;        /* [k, n] */
+  i8ie_bmm_mat out;       /* [m, n] */
+  int out_pix_axis;       /* 0: plain; 1: rows are the pixels of a bordered NHWC map; 2: columns are */
+  int out_h, out_w, out_border;
+  float s_a, s_b, s_out;
+  uint8_t zp_a, zp_b, zp_out;
+  int relu;
+  int32_t* acc_dbg_dev;   /* NULL or [b, m, n] */
+} i8ie_bmm_args;
+int i8ie_bmm_u8(i8ie_ctx* ctx, const i8ie_bmm_args* args);
+/* FP32 (before convert(), and while calibrating): the same descriptor with float elements (s8, the pixel axis, the
+ * scales, relu and acc_dbg_dev are ignored and must be 0 / NULL); out[i,j] = sum over k in ascending order of
+ * a[i,k] * b[k,j], fp32 products added in fp32 to a sum that starts at 0, one rounding per operation, no contraction. */
+int i8ie_bmm_f32(i8ie_ctx* ctx, const i8ie_bmm_args* args);
+
+/* ---- quantized Softmax over the last axis (no counterpart in the reference) ------------------------------------------
+ * Input: `rows` rows of L u8 values with (s_in, zero point), 1 <= L <= 65535, in reference order.  The result always
+ * carries scale = 1/256, zero_point = 0.  Everything is integer.  Per row:
+ *     mx   = max_j x_j
+ *     d_j  = mx - x_j                                   0..255; the zero point cancels
+ *     E[d] = (uint32) floor(65536 * exp(-(double)s_in * d) + 0.5),  d = 0..255      the host-built table
+ *     S    = sum_j E[d_j]                               65536 <= S < 2^32
+ *     q_j  = min(255, (E[d_j] * 256 + S / 2) / S)       unsigned 32-bit, floor division
+ * E[d] <= 65536, so E * 256 + S / 2 < 2^24 + 2^31 never wraps.  With p the real softmax, the unclamped quotient is within
+ * 0.5 + 256 (L + 1) / 131072 of 256 p; the byte clamps at 255, so the bound that holds for q is
+ *     |q - min(256 p, 255)| <= 0.5 + 256 (L + 1) / 131072
+ * (L = 1 gives q = 255 where 256 p = 256).
+ * i8ie_softmax_table: host only (no ctx, like i8ie_activation_table); exp is the host's double-precision libm.  s_in
+ * must be finite and >= 0; a null table is I8IE_ERR_ARG too.
+ * i8ie_softmax_u8: out may alias in (no other overlap); any alignment.  The table is built at the call and travels by
+ * value in the kernel arguments: one launch, no device allocation, no copy; stateless and capturable in a graph.  One
+ * wave per row up to L = 1024 (the row stays in registers between the passes), one block per row beyond
+ * (csrc/i8ie_softmax.hip). */
+int i8ie_softmax_table(float s_in, uint32_t table_host[256]);
+int i8ie_softmax_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int64_t rows, int L, float s_in);
+/* FP32: per row mx = max_j x_j; e_j = expf(x_j - mx); S = the fp32 sum of e_j in ascending j; out_j = e_j / S (one
+ * division per element).  out may alias in. */
+int i8ie_softmax_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int64_t rows, int L);
+
 #ifdef __cplusplus
 }
 #endif

@@ -914,6 +914,132 @@ Tensor<u8_t> mul_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp) {
       }, {a.pend, b.pend});
   return out;
 }
+// ---- matmul / softmax (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_bmm_u8, i8ie_softmax_u8) ----
+// Operands are rank 3 [b, r, c], or rank 4 [n, c, h, w] counted as [n, c, h * w] (the last two dimensions merged in reference
+// order).  a is [b, m, k] ([b, k, m] when transpose_a), b is [b, k, n] ([b, n, k] when transpose_b); the same b on both sides.
+// The result is [b, m, n] -- or [b, m, h, w] when a was given as rank 4 [b, m, h, w], untransposed, and n == h * w.  Anything
+// else is a RuntimeError (before any device call).
+struct MatmulShape {
+  ssize_t b = 0, m = 0, n = 0, k = 0;
+  std::vector<ssize_t> out;
+};
+template <typename T>
+MatmulShape matmul_shape(const Tensor<T>& a, const Tensor<T>& b, bool ta, bool tb) {
+  auto rc = [](const Tensor<T>& t, const char* which) {
+    if (t.shape.size() != 3 && t.shape.size() != 4)
+      throw std::runtime_error(std::string("i8ie: matmul: the ") + which + " operand must be [b, r, c] or [n, c, h, w]");
+    for (ssize_t d : t.shape)
+      if (d <= 0) throw std::runtime_error("i8ie: matmul: empty tensor");
+    return std::array<ssize_t, 3>{t.shape[0], t.shape[1], t.shape.size() == 4 ? t.shape[2] * t.shape[3] : t.shape[2]};
+  };
+  const auto A = rc(a, "first"), B = rc(b, "second");
+  MatmulShape s;
+  s.b = A[0];
+  s.m = ta ? A[2] : A[1];
+  s.k = ta ? A[1] : A[2];
+  s.n = tb ? B[1] : B[2];
+  if (B[0] != s.b) throw std::runtime_error("i8ie: matmul: the operands' batch sizes differ (there is no broadcasting)");
+  if ((tb ? B[2] : B[1]) != s.k) throw std::runtime_error("i8ie: matmul: the operands' inner dimensions differ");
+  if (s.k > 32768) throw std::runtime_error("i8ie: matmul: inner dimension above 32768");
+  if (a.shape.size() == 4 && !ta && s.n == a.shape[2] * a.shape[3]) s.out = {s.b, s.m, a.shape[2], a.shape[3]};
+  else s.out = {s.b, s.m, s.n};
+  return s;
+}
+// the [rows, cols] matrix per batch item of a tensor in reference order; `transposed`: the tensor holds [cols, rows]
+i8ie_bmm_mat mat_reference_order(void* ptr, ssize_t rows, ssize_t cols, bool transposed) {
+  i8ie_bmm_mat m;
+  m.ptr = ptr;
+  m.batch_stride = (int64_t)rows * cols;
+  m.row_stride = transposed ? 1 : (int64_t)cols;
+  m.col_stride = transposed ? (int64_t)rows : 1;
+  m.s8 = 0;
+  return m;
+}
+Tensor<float> matmul_f32(Tensor<float>& a, Tensor<float>& b, bool ta, bool tb) {
+  const MatmulShape s = matmul_shape(a, b, ta, tb);
+  Tensor<float> out(s.out);
+  i8ie_bmm_args g{};
+  g.b = (int)s.b; g.m = (int)s.m; g.n = (int)s.n; g.k = (int)s.k;
+  g.a = mat_reference_order(a.dptr(), s.m, s.k, ta);
+  g.bm = mat_reference_order(b.dptr(), s.k, s.n, tb);
+  g.out = mat_reference_order(out.dptr(), s.m, s.n, false);
+  check(i8ie_bmm_f32(ctx(), &g));
+  return out;
+}
+// A u8 operand as it lies.  A rank-4 tensor stored NHWC without a border is physically [n, t, c]: its [c, t] matrix has the
+// channel stride 1 and is read through the strides, re-biased or not.  One that exists with a border, and a view under other
+// logical dims, goes back to the reference's order first (one layout conversion).
+i8ie_bmm_mat mat_of_storage(const std::shared_ptr<Storage>& s, const std::vector<ssize_t>& shp, ssize_t rows, ssize_t cols, bool transposed) {
+  const bool nhwc = s->layout == I8IE_LAYOUT_NHWC && s->border == 0 && shp.size() == 4 && s->dn == shp[0] && s->dc == shp[1] &&
+                    s->dh == shp[2] && s->dw == shp[3];
+  if (!nhwc) {
+    s->to_nchw();
+    return mat_reference_order(s->device_ptr(), rows, cols, transposed);
+  }
+  i8ie_bmm_mat m = mat_reference_order(s->device_ptr(), rows, cols, !transposed);  // [t, c] in memory: the transpose of [c, t]
+  m.s8 = s->s8 ? 1 : 0;
+  return m;
+}
+Tensor<u8_t> matmul_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp, bool ta, bool tb) {
+  const MatmulShape s = matmul_shape(a, b, ta, tb);
+  check_out_qparams("matmul", scale, zp);
+  if (!std::isfinite(a.scale) || !std::isfinite(b.scale)) throw std::runtime_error("i8ie: matmul: an operand's scale is not finite");
+  if ((!a.st && !a.pend) || (!b.st && !b.pend)) throw std::runtime_error("i8ie: empty tensor");
+  Tensor<u8_t> out = pending_u8(s.out, scale, (u8_t)zp);
+  std::array<Tensor<u8_t>, 2> ops{a, b};  // share the operands' storage / pending launches
+  const float s_a = a.scale, s_b = b.scale;
+  const u8_t zp_a = a.zero_point, zp_b = b.zero_point, zp_o = (u8_t)zp;
+  const std::vector<ssize_t> sha = a.shape, shb = b.shape;
+  // deferred like add's result: relu(matmul(..)) is one launch, and a rank-4 result gets the border and re-bias the next conv
+  // asks for straight from the kernel.  The operands' producers are asked for border 0 (operand_as_it_lies).
+  out.pend = make_pend(
+      [ops, s, s_a, s_b, zp_a, zp_b, scale, zp_o, sha, shb, ta, tb](bool relu, int border, bool s8) mutable {
+        auto ss = resolve_operands(ops.data(), 2);
+        i8ie_bmm_args g{};
+        g.b = (int)s.b; g.m = (int)s.m; g.n = (int)s.n; g.k = (int)s.k;
+        g.a = mat_of_storage(ss[0], sha, s.m, s.k, ta);
+        g.bm = mat_of_storage(ss[1], shb, s.k, s.n, tb);
+        std::shared_ptr<Storage> st;
+        if (s.out.size() == 4) {  // NHWC [b, h + 2B, w + 2B, m]: the n columns are the pixels
+          st = nhwc_storage(s.out, border, zp_o, s8);
+          g.out.ptr = st->dev;
+          g.out.batch_stride = (int64_t)s.m * (s.out[2] + 2 * st->border) * (s.out[3] + 2 * st->border);
+          g.out.row_stride = 1;
+          g.out.col_stride = (int64_t)s.m;
+          g.out.s8 = st->s8 ? 1 : 0;
+          g.out_pix_axis = 2;
+          g.out_h = (int)s.out[2]; g.out_w = (int)s.out[3]; g.out_border = st->border;
+        } else {
+          st = device_storage((size_t)(s.b * s.m * s.n));
+          g.out = mat_reference_order(st->dev, s.m, s.n, false);
+        }
+        g.s_a = s_a; g.s_b = s_b; g.s_out = scale;
+        g.zp_a = zp_a; g.zp_b = zp_b; g.zp_out = zp_o;
+        g.relu = relu ? 1 : 0;
+        check(i8ie_bmm_u8(ctx(), &g));
+        return st;
+      }, {a.pend, b.pend});
+  return out;
+}
+// softmax over the last axis; the u8 result always carries scale 1/256, zero point 0.  A plain flat tensor: an input that is
+// not in reference order is converted first.
+Tensor<float> softmax_f32(Tensor<float>& x) {
+  if (x.shape.empty() || x.size <= 0) throw std::runtime_error("i8ie: softmax: empty tensor");
+  Tensor<float> out(x.shape);
+  check(i8ie_softmax_f32(ctx(), x.dptr(), out.dptr(), (int64_t)(x.size / x.shape.back()), (int)x.shape.back()));
+  return out;
+}
+Tensor<u8_t> softmax_u8(Tensor<u8_t>& x) {
+  if (x.shape.empty() || x.size <= 0) throw std::runtime_error("i8ie: softmax: empty tensor");
+  if (x.shape.back() > 65535) throw std::runtime_error("i8ie: softmax: rows of more than 65535 values");
+  if (!std::isfinite(x.scale) || x.scale < 0) throw std::runtime_error("i8ie: softmax: the input scale must be finite and not negative");
+  const uint8_t* src = x.dptr();
+  Tensor<u8_t> out(x.shape);
+  out.scale = 1.0f / 256.0f;
+  out.zero_point = 0;
+  check(i8ie_softmax_u8(ctx(), src, out.dptr(), (int64_t)(x.size / x.shape.back()), (int)x.shape.back(), x.scale));
+  return out;
+}
 // ---- cat (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_concat_u8) --------------------------
 // axis 1 of k rank-4 [n, c_i, h, w] or k rank-2 [m, f_i] tensors: the result's shape, or a RuntimeError (before any device call)
 template <typename T>
@@ -1905,6 +2031,22 @@ class Mul : public Weightless {
     return mul_u8(a, b, scale_, zero_point_);
   }
 };
+// a . b of two activation tensors (matmul_shape's rules), each optionally given transposed
+class MatMul : public Weightless {
+ public:
+  MatMul(bool transpose_a, bool transpose_b) : ta_(transpose_a), tb_(transpose_b) {}
+  Tensor<float> forward_f32(Tensor<float>& a, Tensor<float>& b) { return sampled(matmul_f32(a, b, ta_, tb_)); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& a, Tensor<u8_t>& b) {
+    matmul_shape(a, b, ta_, tb_);
+    need_quantized("MatMul");
+    return matmul_u8(a, b, scale_, zero_point_, ta_, tb_);
+  }
+  bool transpose_a() const { return ta_; }
+  bool transpose_b() const { return tb_; }
+
+ private:
+  bool ta_, tb_;
+};
 // cat along axis 1: a list of FP32 tensors before convert(), of u8 tensors after it
 class Concat : public Weightless {
  public:
@@ -2013,6 +2155,13 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
   // additive: a * b in FP32; the quantized Mul of include/i8ie_hip.h on u8 tensors.  b has a's shape or is a's gate
   m.def("mul", &mul_f32, py::arg("a"), py::arg("b"));
   m.def("mul", &mul_u8, py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("zero_point"));
+  // additive: the batched matmul of two activation tensors and the softmax over the last axis (include/i8ie_hip.h,
+  // i8ie_bmm_u8 / i8ie_softmax_u8); a u8 softmax result always carries scale 1/256, zero point 0
+  m.def("matmul", &matmul_f32, py::arg("a"), py::arg("b"), py::arg("transpose_a") = false, py::arg("transpose_b") = false);
+  m.def("matmul", &matmul_u8, py::arg("a"), py::arg("b"), py::arg("scale"), py::arg("zero_point"), py::arg("transpose_a") = false,
+        py::arg("transpose_b") = false);
+  m.def("softmax", &softmax_f32, py::arg("x"));
+  m.def("softmax", &softmax_u8, py::arg("x"));
   // additive: cat along axis 1 of up to 8 tensors, a copy in FP32; the quantized concat of include/i8ie_hip.h on u8 tensors
   m.def("cat", [](const py::list& tensors) { return cat_f32(cat_list<float>(tensors)); }, py::arg("tensors"));
   m.def("cat", [](const py::list& tensors, float scale, int zp) { return cat_u8(cat_list<u8_t>(tensors), scale, zp); },
@@ -2080,6 +2229,13 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
     py::class_<Mul> c(m, "Mul");
     bind_weightless_common(c);
     c.def("__call__", &Mul::forward_f32).def("__call__", &Mul::forward_u8);
+  }
+  {
+    py::class_<MatMul> c(m, "MatMul");
+    c.def(py::init<bool, bool>(), py::arg("transpose_a") = false, py::arg("transpose_b") = false);
+    bind_weightless_state(c);
+    c.def("__call__", &MatMul::forward_f32).def("__call__", &MatMul::forward_u8)
+        .def("transpose_a", &MatMul::transpose_a).def("transpose_b", &MatMul::transpose_b);
   }
   {
     py::class_<Concat> c(m, "Concat");

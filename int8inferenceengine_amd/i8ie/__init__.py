@@ -9,7 +9,7 @@ import numbers
 
 import _CXX_i8ie as _C
 
-from .layer import Activation, Add, Concat, Conv2d, ConvTranspose2d, Layer, Linear, Mul, activation_kind
+from .layer import Activation, Add, Concat, Conv2d, ConvTranspose2d, Layer, Linear, MatMul, Mul, activation_kind
 from .module import Module
 from .tensor import Tensor
 
@@ -19,6 +19,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
+    "MatMul", "matmul", "softmax",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -77,6 +78,32 @@ def mul(a, b, scale=None, zero_point=None):
     if scale is not None or zero_point is not None:
         raise TypeError("mul of FP32 tensors takes no scale / zero_point")
     return Tensor(_C.mul(a.data, b.data))
+
+
+def matmul(a, b, scale=None, zero_point=None, transpose_a=False, transpose_b=False):
+    """Batched matmul of two activation tensors.  Operands are rank 3 [b, r, c], or rank 4 [n, c, h, w] counted as
+    [n, c, h * w]; `a` is [b, m, k] ([b, k, m] with transpose_a), `b` is [b, k, n] ([b, n, k] with transpose_b), the same b on
+    both sides (no broadcasting; anything else raises RuntimeError).  The result is [b, m, n], or [b, m, h, w] when `a` was
+    given as rank 4 [b, m, h, w], untransposed, and n == h * w.  FP32 tensors: fp32 products added in ascending k, `scale` /
+    `zero_point` must not be given.  uint8 tensors: the quantized matmul of include/i8ie_hip.h (i8ie_bmm_u8); the result's
+    `scale` and `zero_point` are required.  `i8ie.MatMul` is the calibrated form for use inside a Module."""
+    quantized = type(a.data).__name__ == "6TensorIhE"
+    if quantized:
+        if scale is None or zero_point is None:
+            raise TypeError("matmul of uint8 tensors needs the result's scale and zero_point")
+        return Tensor(_C.matmul(a.data, b.data, float(scale), int(zero_point), bool(transpose_a), bool(transpose_b)))
+    if scale is not None or zero_point is not None:
+        raise TypeError("matmul of FP32 tensors takes no scale / zero_point")
+    return Tensor(_C.matmul(a.data, b.data, bool(transpose_a), bool(transpose_b)))
+
+
+def softmax(x):
+    """Softmax over the last axis.  FP32 tensors: max-subtracted expf, fp32 sum, one division per element.  uint8 tensors:
+    the integer softmax of include/i8ie_hip.h (i8ie_softmax_u8), defined from one 256-entry table of the input's scale; the
+    result always carries scale 1/256 and zero point 0, so there are no parameters and no layer.  The result is a plain
+    tensor in reference order; an input that is not in reference order (an NHWC activation between layers) is converted
+    first."""
+    return Tensor(_C.softmax(x.data))
 
 
 def cat(tensors, scale=None, zero_point=None):

@@ -136,6 +136,25 @@ class Mul(Weightless):
         return Tensor(self.layer(a.data, b.data))
 
 
+class MatMul(Weightless):
+    """Quantized batched matmul of two activation tensors `y = self.mm1(a, b)` (additive, not in the reference): a layer
+    without weights.
+
+    Operands are rank 3 [b, r, c], or rank 4 [n, c, h, w] counted as [n, c, h * w].  `a` is [b, m, k] ([b, k, m] with
+    transpose_a), `b` is [b, k, n] ([b, n, k] with transpose_b), the same b on both sides (no broadcasting), k <= 32768.  The
+    result is [b, m, n], or [b, m, h, w] when `a` was given as rank 4 [b, m, h, w], untransposed, and n == h * w.  Anything else
+    raises RuntimeError.  FP32 tensors multiply in FP32 (sampled by the calibrator while preparing, as a layer's FP32 output
+    is); uint8 tensors, after convert(), by the arithmetic of include/i8ie_hip.h (i8ie_bmm_u8) with this MatMul's output
+    (scale, zero_point).  There is no bias and no alpha: fold a 1/sqrt(d) factor into the projection that makes an operand."""
+
+    def __init__(self, transpose_a=False, transpose_b=False):
+        self.transpose_a, self.transpose_b = bool(transpose_a), bool(transpose_b)
+        self.layer = _C.MatMul(self.transpose_a, self.transpose_b)
+
+    def __call__(self, a, b):
+        return Tensor(self.layer(a.data, b.data))
+
+
 class Concat(Weightless):
     """Quantized channel concatenation `y = self.cat1([a, b, ...])` (additive, not in the reference): a layer without weights.
 

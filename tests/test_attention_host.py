@@ -1,0 +1,196 @@
+"""CPU-side checks of the quantized matmul / softmax definitions (tests/attention_ref.py against independent restatements),
+of the host-only table entry i8ie_softmax_table, and of the Python surface.  No GPU."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import abi
+import attention_ref as ar
+
+SCALES = [1.0 / 256, 0.01, 0.05, 0.3, 1.0, 0.0]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return ar.bind(abi.lib())
+
+
+@pytest.mark.parametrize("s", SCALES)
+def test_softmax_table_entry_equals_ref(lib, s):
+    t = np.zeros(256, np.uint32)
+    assert lib.i8ie_softmax_table(C.c_float(s), t.ctypes.data_as(C.c_void_p)) == 0
+    want = ar.softmax_table(s)
+    assert np.array_equal(t, want)
+    assert t[0] == 65536 and (np.diff(t.astype(np.int64)) <= 0).all()
+
+
+def test_softmax_table_argument_errors(lib):
+    t = np.zeros(256, np.uint32)
+    assert lib.i8ie_softmax_table(C.c_float(0.1), None) == -1
+    for bad in (float("nan"), float("inf"), -0.5):
+        assert lib.i8ie_softmax_table(C.c_float(bad), t.ctypes.data_as(C.c_void_p)) == -1
+
+
+@pytest.mark.parametrize("L", [1, 2, 17, 64, 257, 1027])
+def test_softmax_u8_within_derived_bound_of_float64(L):
+    rng = np.random.default_rng(100 + L)
+    for s in SCALES[:5]:
+        x = rng.integers(0, 256, (6, L), dtype=np.uint8)
+        x[1] = 77                      # an all-equal row
+        x[2] = 0
+        x[2, L // 2] = 255             # one dominant entry
+        q = ar.softmax_u8(x, s)
+        # (255 is the largest byte: 256 softmax above it is compared at 255, attention_ref.softmax_u8_bound)
+        want = np.minimum(256.0 * ar.softmax(np.float64(np.float32(s)) * x.astype(np.float64)), 255.0)
+        err = np.abs(q.astype(np.float64) - want).max()
+        assert err <= ar.softmax_u8_bound(L), (L, s, err)
+    assert (ar.softmax_u8(np.full((1, 1), 9, np.uint8), 0.3) == 255).all()   # L = 1: 256 clamps to 255
+
+
+def _triple_loop(a, zp_a, b, zp_b):
+    bb, m, k = a.shape
+    n = b.shape[2]
+    out = np.zeros((bb, m, n), np.int64)
+    for t in range(bb):
+        for i in range(m):
+            for j in range(n):
+                for kk in range(k):
+                    out[t, i, j] += (int(a[t, i, kk]) - zp_a) * (int(b[t, kk, j]) - zp_b)
+    return out
+
+
+@pytest.mark.parametrize("ta", [False, True])
+@pytest.mark.parametrize("tb", [False, True])
+def test_matmul_u8_all_transpose_forms_against_triple_loop(orc, ta, tb):
+    rng = np.random.default_rng(7)
+    bb, m, n, k = 2, 3, 4, 5
+    A = rng.integers(0, 256, (bb, m, k), dtype=np.uint8)
+    B = rng.integers(0, 256, (bb, k, n), dtype=np.uint8)
+    a = np.ascontiguousarray(A.transpose(0, 2, 1)) if ta else A
+    b = np.ascontiguousarray(B.transpose(0, 2, 1)) if tb else B
+    zp_a, zp_b = 13, 200
+    acc = ar.matmul_acc(a, zp_a, b, zp_b, ta, tb)
+    want = _triple_loop(A, zp_a, B, zp_b)
+    assert np.array_equal(acc.astype(np.int64), want)
+    for relu in (False, True):
+        q = ar.matmul_u8(a, zp_a, 0.02, b, zp_b, 0.03, 0.9, 40, relu, ta, tb)
+        w = orc.down_scale(want.astype(np.int32), 0.02, 0.03, 0.9, 40)
+        assert np.array_equal(q, np.maximum(w, 40) if relu else w)
+    assert ar.result_shape((2, 3, 2, 2), (2, 4, 4), False, False) == (2, 3, 2, 2)
+    assert ar.result_shape((2, 3, 2, 2), (2, 4, 5), False, False) == (2, 3, 5)
+
+
+def test_matmul_acc_extremes_fit_int32():
+    a = np.full((1, 16, ar.MAX_K), 255, np.uint8)
+    assert ar.matmul_acc(a, 0, a.transpose(0, 2, 1), 0).max() == 255 * 255 * ar.MAX_K < 2 ** 31
+    z = np.zeros_like(a)
+    assert ar.matmul_acc(z, 255, z.transpose(0, 2, 1), 255).max() == 255 * 255 * ar.MAX_K
+
+
+def test_bmm_argument_errors_need_no_gpu(lib):
+    """every argument error is I8IE_ERR_ARG before any device call (the ctx is never dereferenced)"""
+    g = ar.BmmArgs(b=1, m=2, n=2, k=2, a=ar.mat(4096, 2, 2), bm=ar.mat(8192, 2, 2), out=ar.mat(12288, 2, 2),
+                   s_a=1.0, s_b=1.0, s_out=1.0)
+    assert lib.i8ie_bmm_u8(None, C.byref(g)) == -1
+    fake_ctx = C.create_string_buffer(512)  # (never read: each call below fails its argument check first)
+    for field, value in (("k", ar.MAX_K + 1), ("k", 0), ("s_out", 0.0), ("s_out", -1.0), ("s_a", float("inf")),
+                         ("out_pix_axis", 3)):
+        h = ar.BmmArgs.from_buffer_copy(g)
+        setattr(h, field, value)
+        assert lib.i8ie_bmm_u8(fake_ctx, C.byref(h)) == -1, field
+    h = ar.BmmArgs.from_buffer_copy(g)
+    h.a.row_stride, h.a.col_stride = 2, 2   # neither stride is 1
+    assert lib.i8ie_bmm_u8(fake_ctx, C.byref(h)) == -1
+    h = ar.BmmArgs.from_buffer_copy(g)
+    h.out_pix_axis, h.out_h, h.out_w, h.out_border = 2, 3, 1, 1   # n != out_h * out_w
+    assert lib.i8ie_bmm_u8(fake_ctx, C.byref(h)) == -1
+    assert lib.i8ie_softmax_u8(fake_ctx, 4096, 4096, C.c_int64(1), 65536, C.c_float(0.1)) == -1
+    assert lib.i8ie_softmax_u8(fake_ctx, 4096, 4096, C.c_int64(1), 0, C.c_float(0.1)) == -1
+    assert lib.i8ie_softmax_u8(fake_ctx, 4096, 4096, C.c_int64(1), 8, C.c_float(float("nan"))) == -1
+
+
+@pytest.fixture(scope="module")
+def i8ie():
+    import int8inferenceengine_amd  # noqa: F401
+    import i8ie as mod
+
+    return mod
+
+
+def test_surface_names(i8ie):
+    import _CXX_i8ie as cx
+
+    for n in ("MatMul", "matmul", "softmax"):
+        assert n in i8ie.__all__ and hasattr(i8ie, n) and hasattr(cx, n)
+    mm = i8ie.MatMul(transpose_b=True)
+    assert isinstance(mm, i8ie.layer.Weightless) and (mm.transpose_a, mm.transpose_b) == (False, True)
+    assert mm.output_qparams() == (1.0, 0) and not mm.layer.is_quantized()
+    mm.layer.load_quantized(0.5, 3)
+    assert mm.output_qparams() == (0.5, 3) and mm.layer.is_quantized()
+    with pytest.raises(RuntimeError):
+        mm.load_weight(np.zeros(1, np.float32))
+
+
+def test_python_level_type_errors(i8ie):
+    a = i8ie.tensor(np.zeros((1, 2, 3), np.float32))
+    b = i8ie.tensor(np.zeros((1, 3, 2), np.float32))
+    for kw in ({"scale": 1.0}, {"zero_point": 0}, {"scale": 1.0, "zero_point": 0}):
+        with pytest.raises(TypeError):
+            i8ie.matmul(a, b, **kw)
+
+
+def test_module_saves_a_matmul_as_qparams_only(i8ie):
+    class Net(i8ie.Module):
+        def __init__(self):
+            super().__init__()
+            self.mm1 = i8ie.MatMul(transpose_a=True)
+
+    net = Net()
+    net.mm1.layer.load_quantized(0.25, 7)
+    sd = net.quantized_state_dict()
+    assert list(sd) == ["mm1.qparams"] and sd["mm1.qparams"].tolist() == [0.0, 0.25, 7.0]
+    other = Net()
+    other.load_quantized(sd)
+    assert other.mm1.output_qparams() == (0.25, 7) and other.is_quant
+
+
+# ---- the "tiny" non-local network: the reference composition alone, with the seeds the GPU test uses ------------------------
+@pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
+@pytest.mark.parametrize("batch", [1, 5])
+def test_nonlocal_tiny_reference_discriminates(orc, batch, per_channel):
+    from int8inferenceengine_amd import nonlocal_net as nl
+
+    entry = nl.CONFIGS["tiny"]
+    sd = nl.synthetic_state_dict("tiny", ar.WEIGHT_SEED)
+    qp, jqp = ar.nonlocal_fp32_qparams(entry, sd, nl.synthetic_input("tiny", 8, seed=ar.CALIB_SEED))
+    assert sorted(qp) == sorted(nl.layer_names("tiny")) and sorted(jqp) == sorted(nl.join_names("tiny"))
+    trace = {}
+    x = nl.synthetic_input("tiny", batch, seed=ar.INPUT_SEED)
+    logits = ar.nonlocal_forward(entry, x, ar.nonlocal_quantize_layers(entry, sd, per_channel), qp, jqp, per_channel, trace)
+    assert logits.shape == (batch, 10) and len(np.unique(logits)) > 1
+    assert sorted(trace) == sorted(p + t for p in nl.blocks("tiny") for t in ("scores", "softmax", "block"))
+    assert trace["a_scores"].shape == (batch, 64, 64) and trace["b_scores"].shape == (batch, 16, 16)
+    assert trace["a_block"].shape == (batch, 16, 8, 8) and trace["b_block"].shape == (batch, 20, 4, 4)
+    for p in nl.blocks("tiny"):
+        assert len(np.unique(trace[p + "softmax"])) >= 16, p
+        assert ((trace[p + "scores"] == 0) | (trace[p + "scores"] == 255)).mean() < 0.05, p
+
+
+def test_nonlocal_configs_and_state_dict():
+    from int8inferenceengine_amd import nonlocal_net as nl
+    from int8inferenceengine_amd import workloads as wl
+
+    assert sorted(nl.CONFIGS) == ["cifar", "tiny"] and "nonlocal" not in wl.OPS and len(wl.NETWORKS) == 21
+    L = nl.CONFIGS["tiny"][0]
+    assert L["b_theta"] == ("conv", 20, 12, 1, 1, 0) and L["down"] == ("conv", 16, 20, 3, 2, 1) and L["fc"] == ("fc", 20, 10)
+    C = nl.CONFIGS["cifar"][0]
+    assert C["nl_theta"] == ("conv", 256, 128, 1, 1, 0) and C["nl_out"] == ("conv", 128, 256, 1, 1, 0)
+    assert set(C) - set(wl.network("resnet18_cifar")[0]) == {"nl_theta", "nl_phi", "nl_g", "nl_out"}
+    spec = nl.CONFIGS["cifar"][1]
+    assert spec.index(("nonlocal", "nl_")) == spec.index(("save", "s4b1")) - 2
+    a, b = nl.synthetic_state_dict("tiny", 3), nl.synthetic_state_dict("tiny", 3)
+    assert sorted(a) == sorted(k + s for k in L for s in (".weight", ".bias"))
+    assert all(np.array_equal(a[k], b[k]) for k in a) and a["a_theta.weight"].shape == (16, 16, 1, 1)
+    net = nl.build("tiny")
+    assert isinstance(net, nl.NonLocalNet) and [k for k, _ in net._layers()] == nl.layer_names("tiny") + nl.join_names("tiny")
