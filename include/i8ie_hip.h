@@ -779,6 +779,64 @@ int i8ie_softmax_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int6
  * division per element).  out may alias in. */
 int i8ie_softmax_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int64_t rows, int L);
 
+/* ---- quantized LayerNorm over the last axis (no counterpart in the reference: every op of it is a contraction, a pointwise
+ * map or a window reduction; none takes a statistic of a row at run time) ----------------------------------------------------
+ * A row is C bytes a[0..C) with (s_in, zp_in), 1 <= C <= 16384; eps is finite and > 0; the result carries (s_out, zp_out);
+ * gamma[C], beta[C] are fp32.  LayerNorm does not depend on the input zero point and the input scale enters only through
+ * eps, so the statistics stay in the integers:
+ *     S1 = sum a[c]           S2 = sum a[c]^2        exact; S2 <= 16384 * 65025 < 2^31 (the reason for the bound on C)
+ *     V  = C * S2 - S1 * S1   exact in int64, 0 <= V < 2^53          (= C^2 * the variance in byte units)
+ *     E  = (double)C * C * (double)eps / ((double)s_in * (double)s_in)                  host, double
+ *     r  = (float)(1.0 / sqrt((double)V + E))    IEEE double add, sqrt, divide; one rounding to float
+ *     d[c] = C * a[c] - S1                       integer, |d| <= 255 * C < 2^22: exact in fp32
+ *     g[c] = gamma[c] / s_out                    fp32 divide                    }  i8ie_layernorm_affine, once per layer
+ *     b[c] = (beta[c] / s_out) + (float)zp_out   fp32, two roundings            }
+ *     t = (float)d[c] * r;  u = t * g[c];  v = u + b[c]        fp32, three roundings, no contraction
+ *     q = v >= 255 ? 255 : (v < 0 ? 0 : (u8)v)   down_scale's clamp + truncation, src/quantize_utils.cc:27-36
+ *     q = relu ? max(q, zp_out) : q              relu<u8>, src/functional.cc:15-26
+ * A constant row has V = 0, every d = 0, t = 0 and q = clamp(trunc(b[c])).  E must be positive and 1 / sqrt(E) finite in
+ * fp32 (so r is finite whatever V is); every g[c] and b[c] must be finite.  No NaN can then arise: t is finite, u may
+ * overflow to an infinity, which clamps.
+ * The bound against the real numbers.  Let y* = T G + Bt be the real-number LayerNorm of the dequantised row in output
+ * units, T = d / sqrt(V + C^2 eps / s_in^2) (= (x - mean) / sqrt(var + eps) exactly: sum d^2 = C V, so |T| <= sqrt(C)),
+ * G = gamma / s_out, Bt = beta / s_out + zp_out, all as real numbers of the fp32 inputs.  With u = 2^-24:
+ *     r = (1 + e_r) / sqrt(V + E*),  |e_r| <= u + 4 * 2^-53 (three double roundings of E, one each of the add, sqrt, divide)
+ *     t u-product: u_fp = T G (1 + th), |th| <= 4.01 u (r, t, g, u: four fp32 roundings)
+ *     b = Bt + e_b, |e_b| <= u |beta / s_out| + u (|beta / s_out| (1 + u) + 255)
+ *     v = (u_fp + b)(1 + e_3)
+ *     |v - y*| <= B(y*) = 1.01 * 2^-24 * (5 |T G| + 2 |beta / s_out| + 255 + |y*|)
+ * (5 instead of 4.01 and the factor 1.01 absorb every second-order term; a product below 2^-126 adds at most 2^-149.)
+ * Where y* is further than B from an integer, q = clamp(trunc(y*)).
+ * i8ie_layernorm_affine: host only (no ctx, like i8ie_activation_table): g_host[c], b_host[c] from gamma, beta.  s_out must
+ * be finite and > 0, C in 1..16384, every gamma, beta, g and b finite; null pointers are I8IE_ERR_ARG too. */
+int i8ie_layernorm_affine(const float* gamma, const float* beta, int C, float s_out, uint8_t zp_out, float* g_host,
+                          float* b_host);
+/* `rows` flat rows of C contiguous bytes, any alignment of in and out; out may alias in (no other overlap).  g_dev, b_dev:
+ * fp32 [C] on the device (4-byte aligned), as i8ie_layernorm_affine made them.  zp_in is not an argument: it drops out.
+ * Stateless: one launch, no device allocation, no host synchronisation, capturable in a graph.  C outside 1..16384, eps
+ * or s_in not finite and positive (or an E as excluded above), rows <= 0 or > 2^31 - 1 and null pointers are I8IE_ERR_ARG
+ * with a message, before any device call.  Three kernels with identical bytes (csrc/i8ie_layernorm.hip, DESIGN.md section
+ * 8l): layernorm_u8_group (a power-of-two group of lanes per row, C <= 4096), layernorm_u8_block (one block per row) and
+ * layernorm_u8_direct (one lane per row, the definition verbatim) for in, out, g or b not 16-byte aligned and for
+ * everything under I8IE_OPT_FORCE_FALLBACK. */
+int i8ie_layernorm_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int64_t rows, int C, const float* g_dev,
+                      const float* b_dev, float s_in, float eps, int relu, uint8_t zp_out);
+/* The same on NHWC buffers [n, h+2b, w+2b, C] -> [n, h+2b', w+2b', C], each with its own border and plain (x_s8 = 0) or
+ * re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80): a pixel is a row.  The input's border bytes are never read.
+ * Only the interior of `out` is written: its border bytes are the caller's (i8ie_fill_border_u8), as for i8ie_add_u8_nhwc
+ * and i8ie_lut_u8_nhwc.  out may be in itself when both geometries agree.  Negative borders and non-positive sizes are
+ * I8IE_ERR_ARG too. */
+int i8ie_layernorm_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev, int out_border,
+                           int out_s8, int n, int C, int h, int w, const float* g_dev, const float* b_dev, float s_in,
+                           float eps, int relu, uint8_t zp_out);
+/* FP32 (before convert(), and while calibrating): per row of C floats, every step fp32 with one rounding per operation, no
+ * contraction: mean = (sum of x[c] in ascending c) / C; var = (sum of (x[c] - mean)^2 in ascending c) / C;
+ * out[c] = (x[c] - mean) / sqrtf(var + eps) * gamma[c] + beta[c].  out may alias in.  1 <= C <= 16384, eps finite and > 0.
+ * Element c of row r lies at ((r / inner) * C + c) * inner + r % inner: inner = 1 is flat rows of C floats; an NCHW tensor
+ * normalised over c per pixel is rows = n * h * w, inner = h * w (one launch, no transposition).  inner must divide rows. */
+int i8ie_layernorm_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int64_t rows, int C, const float* gamma_dev,
+                       const float* beta_dev, float eps, int64_t inner);
+
 #ifdef __cplusplus
 }
 #endif

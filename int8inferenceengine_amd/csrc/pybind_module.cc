@@ -1040,6 +1040,91 @@ Tensor<u8_t> softmax_u8(Tensor<u8_t>& x) {
   check(i8ie_softmax_u8(ctx(), src, out.dptr(), (int64_t)(x.size / x.shape.back()), (int)x.shape.back(), x.scale));
   return out;
 }
+// ---- layer_norm (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_layernorm_u8) ---------------------
+// [n, c, h, w] is normalised over c per pixel, [m, f] and [b, t, f] over the last axis: (rows, inner) of the FP32 entry, or
+// a RuntimeError (before any device call)
+template <typename T>
+std::pair<int64_t, int64_t> layer_norm_rows(const Tensor<T>& x, ssize_t channels) {
+  const size_t r = x.shape.size();
+  if (x.size <= 0 || (r != 2 && r != 3 && r != 4)) throw std::runtime_error("i8ie: layer_norm expects [n, c, h, w], [m, f] or [b, t, f]");
+  if ((r == 4 ? x.shape[1] : x.shape.back()) != channels)
+    throw std::runtime_error("i8ie: layer_norm: the normalised axis has " + std::to_string(r == 4 ? x.shape[1] : x.shape.back()) +
+                             " values, the layer " + std::to_string(channels));
+  if (channels > 16384) throw std::runtime_error("i8ie: layer_norm: rows of more than 16384 values");
+  return {(int64_t)(x.size / channels), r == 4 ? (int64_t)(x.shape[2] * x.shape[3]) : 1};
+}
+std::shared_ptr<Storage> upload_f32(const std::vector<float>& v) {
+  auto s = device_storage(v.size() * sizeof(float));
+  check(i8ie_memcpy_h2d(ctx(), s->dev, v.data(), v.size() * sizeof(float)));
+  return s;
+}
+Tensor<float> layer_norm_f32(Tensor<float>& x, const std::shared_ptr<Storage>& gamma, const std::shared_ptr<Storage>& beta, ssize_t channels,
+                             float eps) {
+  const auto ri = layer_norm_rows(x, channels);
+  if (!(eps > 0) || !std::isfinite(eps)) throw std::runtime_error("i8ie: layer_norm: eps must be positive and finite");
+  Tensor<float> out(x.shape);
+  check(i8ie_layernorm_f32(ctx(), x.dptr(), out.dptr(), ri.first, (int)channels, (const float*)gamma->dev, (const float*)beta->dev, eps,
+                           ri.second));
+  return out;
+}
+// g, b: the device arrays of i8ie_layernorm_affine for (scale, zp), kept alive by the recorded launch
+Tensor<u8_t> layer_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, const std::shared_ptr<Storage>& b, ssize_t channels, float eps,
+                           float scale, int zp) {
+  check_out_qparams("layer_norm", scale, zp);
+  if (!in.st && !in.pend) throw std::runtime_error("i8ie: empty tensor");
+  const int64_t rows = layer_norm_rows(in, channels).first;
+  if (!(eps > 0) || !std::isfinite(eps)) throw std::runtime_error("i8ie: layer_norm: eps must be positive and finite");
+  if (!(in.scale > 0) || !std::isfinite(in.scale)) throw std::runtime_error("i8ie: layer_norm: the input scale must be positive and finite");
+  Tensor<u8_t> out = pending_u8(in.shape, scale, (u8_t)zp);
+  Tensor<u8_t> src = in;
+  const std::vector<ssize_t> shp = in.shape;
+  const float s_in = in.scale;
+  const u8_t zp_o = (u8_t)zp;
+  const int C = (int)channels;
+  // deferred like add's and the activations' results: relu(ln(..)) is one launch, a consuming conv gets its zero-point border
+  // and, where it reads them, re-biased bytes straight from the kernel, and several consumers share one launch (PendNode)
+  out.pend = make_pend(
+      [src, g, b, shp, rows, s_in, eps, zp_o, C](bool relu, int border, bool s8) mutable {
+        std::shared_ptr<Storage> si = operand_as_it_lies(src);
+        std::shared_ptr<Storage> st;
+        if (shp.size() == 4) {
+          NhwcCopies copies;
+          si = as_engine_nhwc(si, shp, copies);
+          st = nhwc_storage(shp, border, zp_o, s8);
+          check(i8ie_layernorm_u8_nhwc(ctx(), (const uint8_t*)si->device_ptr(), si->border, si->s8 ? 1 : 0, (uint8_t*)st->dev, st->border,
+                                       st->s8 ? 1 : 0, (int)shp[0], C, (int)shp[2], (int)shp[3], (const float*)g->dev, (const float*)b->dev,
+                                       s_in, eps, relu ? 1 : 0, zp_o));
+        } else {  // rows (a flattened NHWC activation goes back to the reference's order; one pixel per image is in it already)
+          if (si->layout == I8IE_LAYOUT_NHWC && si->dh * si->dw == 1 && si->border == 0) si->unbias();
+          else si->to_nchw();
+          st = device_storage((size_t)rows * C);
+          check(i8ie_layernorm_u8(ctx(), (const uint8_t*)si->device_ptr(), (uint8_t*)st->dev, rows, C, (const float*)g->dev,
+                                  (const float*)b->dev, s_in, eps, relu ? 1 : 0, zp_o));
+        }
+        return st;
+      }, {in.pend});
+  return out;
+}
+using F32Array = py::array_t<float, py::array::c_style | py::array::forcecast>;
+std::vector<float> layer_norm_param(const py::object& a, ssize_t channels, float fill, const char* what) {
+  if (a.is_none()) return std::vector<float>((size_t)channels, fill);
+  F32Array v = F32Array::ensure(a);
+  if (!v || v.ndim() != 1 || v.shape(0) != channels)
+    throw std::runtime_error(std::string("i8ie: layer_norm: ") + what + " must hold one float per normalised value");
+  return std::vector<float>(v.data(), v.data() + v.size());
+}
+// (g, b) of i8ie_layernorm_affine on the device
+std::pair<std::shared_ptr<Storage>, std::shared_ptr<Storage>> layer_norm_affine(const std::vector<float>& gamma, const std::vector<float>& beta,
+                                                                                 float scale, int zp) {
+  std::vector<float> g(gamma.size()), b(gamma.size());
+  check(i8ie_layernorm_affine(gamma.data(), beta.data(), (int)gamma.size(), scale, (uint8_t)zp, g.data(), b.data()));
+  return {upload_f32(g), upload_f32(b)};
+}
+template <typename T>
+ssize_t layer_norm_axis(const Tensor<T>& x) {
+  if (x.shape.size() < 2) throw std::runtime_error("i8ie: layer_norm expects [n, c, h, w], [m, f] or [b, t, f]");
+  return x.shape.size() == 4 ? x.shape[1] : x.shape.back();
+}
 // ---- cat (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_concat_u8) --------------------------
 // axis 1 of k rank-4 [n, c_i, h, w] or k rank-2 [m, f_i] tensors: the result's shape, or a RuntimeError (before any device call)
 template <typename T>
@@ -2080,6 +2165,74 @@ class Activation : public Weightless {
   int kind_;
   float param_;
 };
+// LayerNorm over the channel axis of [n, c, h, w] or the last axis of [m, f] / [b, t, f]: a layer with fp32 weight (gamma) and
+// bias (beta) and the layers' prepare / convert state machine around its output (scale, zero_point).  There are no INT8
+// weights: convert() computes g = gamma / s_out and b = beta / s_out + zp_out (i8ie_layernorm_affine) and uploads them once.
+class LayerNorm : public QuantState {
+ public:
+  LayerNorm(ssize_t channels, float eps) : channels_(channels), eps_(eps) {
+    if (channels < 1 || channels > 16384) throw std::runtime_error("i8ie: LayerNorm: channels must be in 1..16384");
+    if (!(eps > 0) || !std::isfinite(eps)) throw std::runtime_error("i8ie: LayerNorm: eps must be positive and finite");
+    gamma_.assign((size_t)channels, 1.0f);
+    beta_.assign((size_t)channels, 0.0f);
+  }
+  void load_weight(const py::object& w) { gamma_ = layer_norm_param(w, channels_, 1.0f, "weight"); params_changed(); }
+  void load_bias(const py::object& b) { beta_ = layer_norm_param(b, channels_, 0.0f, "bias"); params_changed(); }
+  void convert(bool /*per_channel: there are no INT8 weights*/ = false) {
+    if (!convert_qparams()) return;
+    install();
+  }
+  void load_quantized(const py::object& w, const py::object& b, float s_out, int zp_out) {  // what convert() would have left behind
+    check_zero_point(zp_out);
+    gamma_ = layer_norm_param(w, channels_, 1.0f, "weight");
+    beta_ = layer_norm_param(b, channels_, 0.0f, "bias");
+    scale_ = s_out;
+    zero_point_ = (u8_t)zp_out;
+    qparams_overridden_ = true;
+    install();
+  }
+  Tensor<float> forward_f32(Tensor<float>& x) {
+    layer_norm_rows(x, channels_);
+    if (!gamma_dev_) {
+      gamma_dev_ = upload_f32(gamma_);
+      beta_dev_ = upload_f32(beta_);
+    }
+    Tensor<float> out = layer_norm_f32(x, gamma_dev_, beta_dev_, channels_, eps_);
+    maybe_sample(out);
+    return out;
+  }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& x) {
+    layer_norm_rows(x, channels_);
+    if (!is_quantized_) throw std::runtime_error("i8ie: LayerNorm is not converted (call convert() first)");
+    return layer_norm_u8(x, g_dev_, b_dev_, channels_, eps_, scale_, zero_point_);
+  }
+  py::array_t<float> weight() const { return py::array_t<float>((ssize_t)gamma_.size(), gamma_.data()); }
+  py::array_t<float> bias() const { return py::array_t<float>((ssize_t)beta_.size(), beta_.data()); }
+  ssize_t channels() const { return channels_; }
+  float eps() const { return eps_; }
+
+ protected:
+  void output_qparams_changed() override {
+    if (is_quantized_) install();
+  }
+
+ private:
+  void params_changed() {
+    gamma_dev_.reset();
+    beta_dev_.reset();
+    if (is_quantized_) install();
+  }
+  void install() {
+    if (!(scale_ > 0) || !std::isfinite(scale_)) throw std::runtime_error("i8ie: LayerNorm: the output scale must be positive and finite");
+    std::tie(g_dev_, b_dev_) = layer_norm_affine(gamma_, beta_, scale_, zero_point_);
+    set_quantized();
+  }
+  ssize_t channels_;
+  float eps_;
+  std::vector<float> gamma_, beta_;
+  std::shared_ptr<Storage> gamma_dev_, beta_dev_;  // FP32 path
+  std::shared_ptr<Storage> g_dev_, b_dev_;         // after convert()
+};
 template <typename L>
 void bind_weightless_state(py::class_<L>& c) {
   c.def("prepare", &L::prepare)
@@ -2162,6 +2315,19 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
         py::arg("transpose_b") = false);
   m.def("softmax", &softmax_f32, py::arg("x"));
   m.def("softmax", &softmax_u8, py::arg("x"));
+  // additive: LayerNorm over the channel axis of [n, c, h, w] or the last axis of [m, f] / [b, t, f] (include/i8ie_hip.h,
+  // i8ie_layernorm_u8); weight / bias: float32 [channels] or None (ones / zeros); uploaded per call
+  m.def("layer_norm", [](Tensor<float>& x, const py::object& w, const py::object& b, float eps) {
+    const ssize_t c = layer_norm_axis(x);
+    return layer_norm_f32(x, upload_f32(layer_norm_param(w, c, 1.0f, "weight")), upload_f32(layer_norm_param(b, c, 0.0f, "bias")), c, eps);
+  }, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("eps"));
+  m.def("layer_norm", [](Tensor<u8_t>& x, const py::object& w, const py::object& b, float eps, float scale, int zp) {
+    check_out_qparams("layer_norm", scale, zp);
+    const ssize_t c = layer_norm_axis(x);
+    if (c > 16384) throw std::runtime_error("i8ie: layer_norm: rows of more than 16384 values");
+    auto gb = layer_norm_affine(layer_norm_param(w, c, 1.0f, "weight"), layer_norm_param(b, c, 0.0f, "bias"), scale, zp);
+    return layer_norm_u8(x, gb.first, gb.second, c, eps, scale, zp);
+  }, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("scale"), py::arg("zero_point"));
   // additive: cat along axis 1 of up to 8 tensors, a copy in FP32; the quantized concat of include/i8ie_hip.h on u8 tensors
   m.def("cat", [](const py::list& tensors) { return cat_f32(cat_list<float>(tensors)); }, py::arg("tensors"));
   m.def("cat", [](const py::list& tensors, float scale, int zp) { return cat_u8(cat_list<u8_t>(tensors), scale, zp); },
@@ -2247,6 +2413,26 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
     c.def(py::init<int, float>(), py::arg("kind"), py::arg("param") = 0.0f);
     bind_weightless_state(c);
     c.def("__call__", &Activation::forward_f32).def("__call__", &Activation::forward_u8).def("kind", &Activation::kind).def("param", &Activation::param);
+  }
+
+  {
+    py::class_<LayerNorm> c(m, "LayerNorm");
+    c.def(py::init<ssize_t, float>(), py::arg("channels"), py::arg("eps") = 1e-5f)
+        .def("load_weight", &LayerNorm::load_weight)
+        .def("load_bias", &LayerNorm::load_bias)
+        .def("prepare", &LayerNorm::prepare)
+        .def("convert", &LayerNorm::convert, py::arg("per_channel") = false)
+        .def("__call__", &LayerNorm::forward_f32)
+        .def("__call__", &LayerNorm::forward_u8)
+        .def("set_output_qparams", &LayerNorm::set_output_qparams, py::arg("scale"), py::arg("zero_point"))
+        .def("output_qparams", &LayerNorm::output_qparams)
+        .def("load_quantized", &LayerNorm::load_quantized, py::arg("weight"), py::arg("bias"), py::arg("out_scale"),
+             py::arg("out_zero_point"))
+        .def("weight", &LayerNorm::weight)
+        .def("bias", &LayerNorm::bias)
+        .def("channels", &LayerNorm::channels)
+        .def("eps", &LayerNorm::eps)
+        .def("is_quantized", &LayerNorm::is_quantized);
   }
 
   // ---- additive runtime controls -------------------------------------------------

@@ -9,7 +9,7 @@ import numbers
 
 import _CXX_i8ie as _C
 
-from .layer import Activation, Add, Concat, Conv2d, ConvTranspose2d, Layer, Linear, MatMul, Mul, activation_kind
+from .layer import Activation, Add, Concat, Conv2d, ConvTranspose2d, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind
 from .module import Module
 from .tensor import Tensor
 
@@ -19,7 +19,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
-    "MatMul", "matmul", "softmax",
+    "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -104,6 +104,23 @@ def softmax(x):
     tensor in reference order; an input that is not in reference order (an NHWC activation between layers) is converted
     first."""
     return Tensor(_C.softmax(x.data))
+
+
+def layer_norm(x, weight=None, bias=None, eps=1e-5, scale=None, zero_point=None):
+    """LayerNorm of [n, c, h, w] over c per pixel, of [m, f] and [b, t, f] over the last axis (anything else raises
+    RuntimeError).  `weight` / `bias`: float32 arrays of one value per normalised entry, or None for ones / zeros.  FP32
+    tensors: the fp32 sequence of include/i8ie_hip.h (i8ie_layernorm_f32), `scale` / `zero_point` must not be given.  uint8
+    tensors: the quantized LayerNorm (i8ie_layernorm_u8); the result's `scale` and `zero_point` are required, and gamma /
+    scale, beta / scale + zero_point are computed and uploaded at every call.  `i8ie.LayerNorm` is the calibrated form for
+    use inside a Module (it uploads them once, at convert())."""
+    quantized = type(x.data).__name__ == "6TensorIhE"
+    if quantized:
+        if scale is None or zero_point is None:
+            raise TypeError("layer_norm of a uint8 tensor needs the result's scale and zero_point")
+        return Tensor(_C.layer_norm(x.data, weight, bias, float(eps), float(scale), int(zero_point)))
+    if scale is not None or zero_point is not None:
+        raise TypeError("layer_norm of an FP32 tensor takes no scale / zero_point")
+    return Tensor(_C.layer_norm(x.data, weight, bias, float(eps)))
 
 
 def cat(tensors, scale=None, zero_point=None):

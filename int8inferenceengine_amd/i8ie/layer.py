@@ -88,6 +88,34 @@ class ConvTranspose2d(Layer):
         self.layer = _C.ConvTranspose2d(in_channels, out_channels, kernel_size, stride, padding, output_padding)
 
 
+class LayerNorm(Layer):
+    """Quantized LayerNorm `y = self.norm1(x)` (additive, not in the reference): a layer with fp32 `weight` (gamma, default
+    ones) and `bias` (beta, default zeros) of `channels` values each, and no INT8 weights.
+
+    [n, c, h, w] is normalised over c per pixel (torch's channels-first "LayerNorm2d" of a ConvNeXt), c == channels; [m, f]
+    and [b, t, f] over the last axis, f == channels; any other shape raises RuntimeError.  1 <= channels <= 16384.  FP32
+    tensors go through the fp32 sequence of include/i8ie_hip.h (i8ie_layernorm_f32; sampled by the calibrator while
+    preparing, as a layer's FP32 output is); uint8 tensors, after convert(), through i8ie_layernorm_u8 with this layer's
+    output (scale, zero_point).  Module.load() takes `<attr>.weight` / `<attr>.bias`; quantized_state_dict() keeps both as
+    float32 beside `<attr>.qparams`.  weight_scale, weight_scales, q_weight, q_bias and forward_debug raise RuntimeError."""
+
+    def __init__(self, channels, eps=1e-5):
+        self.channels, self.eps = int(channels), float(eps)
+        self.layer = _C.LayerNorm(self.channels, self.eps)
+
+    def convert(self, per_channel=False):
+        """per_channel is accepted and ignored: there are no INT8 weights."""
+        self.layer.convert()
+
+    def is_per_channel(self):
+        return False
+
+    def _no_int8_weights(self, *args, **kwargs):
+        raise RuntimeError("i8ie: LayerNorm has no INT8 weights (weight and bias stay float32)")
+
+    weight_scale = weight_scales = q_weight = q_bias = forward_debug = _no_int8_weights
+
+
 class Weightless(Layer):
     """Common behaviour of the layers without weights (Add, Mul, Concat, Activation): `self.layer` has only the prepare / convert state
     machine around an output (scale, zero_point).  Takes part in Module.prepare() / convert() / quantized_state_dict()

@@ -1,7 +1,7 @@
 """Module base class (reference i8ie/module.py:6-35)."""
 import _CXX_i8ie as _C
 
-from .layer import Layer, Weightless
+from .layer import Layer, LayerNorm, Weightless
 from .tensor import Tensor
 
 # Hard-coded input quantisation of the reference (i8ie/module.py:20).
@@ -52,7 +52,7 @@ class Module:
         """{'<attr>.q_weight' int8, '<attr>.q_bias' int8, '<attr>.qparams' float64[3] =
         (weight_scale, out_scale, out_zero_point)} for every converted layer; a per-channel layer also has
         '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused).  An Add, a Mul, a Concat or an Activation contributes only
-        '<attr>.qparams' = (0, out_scale, out_zero_point)."""
+        '<attr>.qparams' = (0, out_scale, out_zero_point); a LayerNorm that and '<attr>.weight', '<attr>.bias' as float32."""
         import numpy as np
 
         out = {}
@@ -62,6 +62,11 @@ class Module:
                 raise RuntimeError("layer %r is not converted" % name)
             s_out, zp_out = L.output_qparams()
             if isinstance(layer, Weightless):
+                out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
+                continue
+            if isinstance(layer, LayerNorm):
+                out[name + ".weight"] = np.asarray(L.weight(), np.float32)
+                out[name + ".bias"] = np.asarray(L.bias(), np.float32)
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
                 continue
             out[name + ".q_weight"] = L.q_weight()
@@ -81,6 +86,10 @@ class Module:
             w_scale, s_out, zp_out = (float(v) for v in state[name + ".qparams"])
             if isinstance(layer, Weightless):
                 layer.layer.load_quantized(float(np.float32(s_out)), int(zp_out))
+                continue
+            if isinstance(layer, LayerNorm):
+                layer.layer.load_quantized(np.asarray(state[name + ".weight"], np.float32), np.asarray(state[name + ".bias"], np.float32),
+                                           float(np.float32(s_out)), int(zp_out))
                 continue
             if name + ".w_scales" in state:  # per-channel layer
                 w_scale = np.ascontiguousarray(state[name + ".w_scales"], np.float32)
