@@ -13,7 +13,8 @@ import numpy as np
 
 # name -> (layers, spec, input_shape CHW)
 #   layers: {attr: ("conv", in_c, out_c, k, stride, pad[, groups[, dilation]]) | ("fc", in_f, out_f)
-#                  | ("deconv", in_c, out_c, k, stride, pad, output_pad)   i8ie.ConvTranspose2d, weight [in_c, out_c, k, k]}
+#                  | ("deconv", in_c, out_c, k, stride, pad, output_pad)   i8ie.ConvTranspose2d, weight [in_c, out_c, k, k]
+#                  | ("ln", channels)     i8ie.LayerNorm: float32 gamma / beta, no INT8 weights, no MACs}
 #   spec  : [("layer", attr) | ("relu",) | ("pool", k, s) | ("flatten", features)
 #            | ("save", tag)              remember the current tensor under `tag`
 #            | ("add", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Add (not in `layers`)
@@ -24,7 +25,11 @@ import numpy as np
 #            | ("act", attr, kind[, param])  x = getattr(net, attr)(x); attr names an i8ie.Activation(kind, param)
 #            | ("mul", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Mul; saved[tag] has x's
 #                                         shape or is its gate [n, c] (the branch of a squeeze-and-excitation block)
-#            | ("upsample", factor, mode) x = i8ie.upsample(x, factor, mode); factor an int or (fh, fw), mode "nearest" / "bilinear"]
+#            | ("upsample", factor, mode) x = i8ie.upsample(x, factor, mode); factor an int or (fh, fw), mode "nearest" / "bilinear"
+#            | ("matmul", attr, tag, transpose_a, transpose_b)   x = getattr(net, attr)(x, saved[tag]); attr names an
+#                                         i8ie.MatMul(transpose_a, transpose_b)
+#            | ("softmax",)               x = i8ie.softmax(x): scale 1/256, zero point 0, nothing to calibrate
+#            | ("load", tag)              x = saved[tag] (what a branch computed becomes the current tensor)]
 NETWORKS = {
     # sample/notebooks/AlexNet_cifar10_resize224.ipynb:47-71
     "alexnet": (
@@ -447,6 +452,124 @@ NETWORKS["aspp_tiny"] = _aspp_tiny()
 NETWORKS["deeplabv3_cifar"] = _deeplabv3_cifar()
 
 
+# {network: {attr: factor}}: what synthetic_state_dict folds into a layer's weight and bias (1.0 where nothing is named)
+FOLDS = {}
+LAYER_SCALE = 0.5  # the layer-scale factor of a ConvNeXt block, folded into its second 1x1 conv
+
+
+def _attention(layers, spec, folds, p, c, d):
+    """Single-head self-attention over the t = h * w pixels of the current [n, c, h, w] tensor y, into saved[p + "g"]:
+    theta, phi, g = 1x1 convs c -> d of y; s = mm1(theta, phi), transpose_a: [n, t, t], s[i, j] = sum_c theta[c, i] phi[c, j];
+    pr = softmax(s) over j; z = mm2(g, pr), transpose_b: [n, d, h, w], z[c, i] = sum_j g[c, j] pr[i, j]; out(z), a 1x1 conv
+    d -> c.  The 1/sqrt(d) of the scores is folded into theta.  What the MatMul and the softmax exist for."""
+    for r in ("theta", "phi", "g"):
+        layers[p + r] = ("conv", c, d, 1, 1, 0)
+    layers[p + "out"] = ("conv", d, c, 1, 1, 0)
+    folds[p + "theta"] = 1.0 / np.sqrt(d)
+    spec += [("save", p + "phi"), ("save", p + "g"), ("layer", p + "theta"), ("branch", p + "phi", [("layer", p + "phi")]),
+             ("matmul", p + "mm1", p + "phi", True, False), ("softmax",), ("save", p + "pr"),
+             ("branch", p + "g", [("layer", p + "g"), ("matmul", p + "mm2", p + "pr", False, True), ("layer", p + "out")])]
+
+
+def _nonlocal(layers, spec, folds, p, c, d):
+    """A non-local block (Wang et al. 2018): x = add(attention(x), x)"""
+    spec.append(("save", p + "x"))
+    _attention(layers, spec, folds, p, c, d)
+    spec += [("load", p + "g"), ("add", p + "add", p + "x")]
+
+
+def _attn(layers, spec, folds, p, c, d):
+    """A pre-LN attention block: x = add(attention(ln(x)), x); one LayerNorm feeds the three projections"""
+    layers[p + "ln"] = ("ln", c)
+    spec += [("save", p + "x"), ("layer", p + "ln")]
+    _attention(layers, spec, folds, p, c, d)
+    spec += [("load", p + "g"), ("add", p + "add", p + "x")]
+
+
+def _cnblock(layers, spec, folds, p, c):
+    """A ConvNeXt block (Liu et al. 2022): depthwise 7x7, LayerNorm(c), 1x1 c -> 4c, hardswish, 1x1 4c -> c (LAYER_SCALE
+    folded in), the residual Add.  What the LayerNorm exists for."""
+    layers[p + "dw"] = ("conv", c, c, 7, 1, 3, c)
+    layers[p + "ln"] = ("ln", c)
+    layers[p + "pw1"] = ("conv", c, 4 * c, 1, 1, 0)
+    layers[p + "pw2"] = ("conv", 4 * c, c, 1, 1, 0)
+    folds[p + "pw2"] = LAYER_SCALE
+    spec += [("save", p + "x"), ("layer", p + "dw"), ("layer", p + "ln"), ("layer", p + "pw1"), ("act", p + "act", "hardswish"),
+             ("layer", p + "pw2"), ("add", p + "add", p + "x")]
+
+
+def _nonlocal_tiny(folds):
+    """3x32x32: conv 3->16 3x3 s2 p1, relu, max-pool 2/2 (8x8, t = 64), block A (c = 16, d = 16), relu, conv 16->20 3x3 s2 p1
+    (a bordered consumer), relu (4x4, t = 16), block B (c = 20, d = 12: k = 12 takes bmm_direct), relu, global average
+    pool, fc 20->10"""
+    layers = {"stem": ("conv", 3, 16, 3, 2, 1)}
+    spec = [("layer", "stem"), ("relu",), ("pool", 2, 2)]
+    _nonlocal(layers, spec, folds, "a_", 16, 16)
+    layers["down"] = ("conv", 16, 20, 3, 2, 1)
+    spec += [("relu",), ("layer", "down"), ("relu",)]
+    _nonlocal(layers, spec, folds, "b_", 20, 12)
+    layers["fc"] = ("fc", 20, 10)
+    spec += [("relu",), ("gap",), ("flatten", 20), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+def _nonlocal_resnet_cifar(folds):
+    """resnet18_cifar with one non-local block (c = 256, d = 128) and a relu after stage 3 (8x8)"""
+    base_layers, base_spec, shape = _resnet18_cifar()
+    block_layers, block = {}, []
+    _nonlocal(block_layers, block, folds, "nl_", 256, 128)
+    cut = base_spec.index(("save", "s4b1"))
+    layers = {}
+    for attr, L in base_layers.items():  # (the block's layers where stage 4 begins)
+        if attr == "s4b1c1":
+            layers.update(block_layers)
+        layers[attr] = L
+    return layers, base_spec[:cut] + block + [("relu",)] + base_spec[cut:], shape
+
+
+def _convnext_tiny(folds):
+    """3x32x32: stem conv 3->16 4x4 s4 (8x8), LayerNorm(16), a block at c = 16, a downsample LayerNorm(16) -> conv 16->20 3x3
+    s2 p1 (an LN result that carries a border; 4x4), a block at c = 20 (rows that are no multiple of 16), an attention block
+    at c = 20, d = 12, global average pool, LayerNorm(20) on [n, 20], fc 20->10"""
+    layers = {"stem": ("conv", 3, 16, 4, 4, 0), "stem_ln": ("ln", 16)}
+    spec = [("layer", "stem"), ("layer", "stem_ln")]
+    _cnblock(layers, spec, folds, "a_", 16)
+    layers["down_ln"] = ("ln", 16)
+    layers["down"] = ("conv", 16, 20, 3, 2, 1)
+    spec += [("layer", "down_ln"), ("layer", "down")]
+    _cnblock(layers, spec, folds, "b_", 20)
+    _attn(layers, spec, folds, "t_", 20, 12)
+    layers["head_ln"] = ("ln", 20)
+    layers["fc"] = ("fc", 20, 10)
+    spec += [("gap",), ("flatten", 20), ("layer", "head_ln"), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+def _convnext_cifar(folds):
+    """ConvNeXt (Liu et al. 2022) for 32x32 input: patchify stem 3->64 2x2 s2 + LN (16x16), stages of (2, 2, 2, 2) blocks at
+    64 / 128 / 256 / 512 with LN + 2x2 s2 conv between them, global average pool, LN, fc 512->10"""
+    layers = {"stem": ("conv", 3, 64, 2, 2, 0), "stem_ln": ("ln", 64)}
+    spec = [("layer", "stem"), ("layer", "stem_ln")]
+    c = 64
+    for s in range(4):
+        if s:
+            layers["d%d_ln" % s] = ("ln", c)
+            layers["d%d" % s] = ("conv", c, 2 * c, 2, 2, 0)
+            spec += [("layer", "d%d_ln" % s), ("layer", "d%d" % s)]
+            c *= 2
+        for b in range(2):
+            _cnblock(layers, spec, folds, "s%db%d_" % (s, b), c)
+    layers["head_ln"] = ("ln", c)
+    layers["fc"] = ("fc", c, 10)
+    spec += [("gap",), ("flatten", c), ("layer", "head_ln"), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+for _name, _make in (("nonlocal_tiny", _nonlocal_tiny), ("nonlocal_resnet_cifar", _nonlocal_resnet_cifar),
+                     ("convnext_tiny", _convnext_tiny), ("convnext_cifar", _convnext_cifar)):
+    NETWORKS[_name] = _make(FOLDS.setdefault(_name, {}))
+
+
 def network(name):
     """the (layers, spec, input shape) entry of a network"""
     if name not in NETWORKS:
@@ -464,7 +587,8 @@ def _walk(spec):
 
 
 # the op names a spec may hold: build() refuses any other
-OPS = frozenset(("layer", "relu", "pool", "avgpool", "gap", "save", "branch", "add", "mul", "concat", "act", "upsample", "flatten"))
+OPS = frozenset(("layer", "relu", "pool", "avgpool", "gap", "save", "branch", "add", "mul", "concat", "act", "upsample", "flatten",
+                 "matmul", "softmax", "load"))
 
 
 def conv_groups(L):
@@ -497,8 +621,9 @@ MAIN_PATH_MACS = frozenset((
 
 def _macs(layers, ops, hw, saved, branch_convs, in_branch=False):
     """MACs of the weighted layers of `ops` from an (h, w) map on, those of its branches included, with true taps (a dilated
-    kernel's zeros are no work); without branch_convs a branch counts its Linears only.  Returns (macs, (h, w) behind the
-    ops)."""
+    kernel's zeros are no work); without branch_convs a branch counts its Linears only.  Weighted layers only: a LayerNorm
+    has none, and the products of a ("matmul", ...) of two activations are not counted (no channel count is tracked here).
+    Returns (macs, (h, w) behind the ops)."""
     total = 0
     convs = branch_convs or not in_branch
     h, w = hw
@@ -514,8 +639,9 @@ def _macs(layers, ops, hw, saved, branch_convs, in_branch=False):
                 _, ic, oc, k, s, p, op_ = L
                 total += convs * h * w * ic * oc * k * k
                 h, w = (h - 1) * s - 2 * p + k + op_, (w - 1) * s - 2 * p + k + op_
-            else:
+            elif L[0] == "fc":
                 total += L[1] * L[2]
+            # ("ln", c): no MACs, the same map
         elif op[0] in ("pool", "avgpool"):
             h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
         elif op[0] == "gap":
@@ -525,10 +651,13 @@ def _macs(layers, ops, hw, saved, branch_convs, in_branch=False):
             h, w = h * fh, w * fw
         elif op[0] == "save":
             saved[op[1]] = (h, w)
+        elif op[0] == "load":
+            h, w = saved[op[1]]
         elif op[0] == "branch":
             t, saved[op[1]] = _macs(layers, op[2], saved[op[1]], saved, branch_convs, True)
             total += t
-        # ("act", ...), like relu, flatten, add, mul and concat, has no MACs and keeps the shape
+        # ("act", ...), like relu, flatten, add, mul and concat, has no MACs and keeps the shape; matmul and softmax leave
+        # (h, w) alone too: the map behind them is read only by 1x1 convs or replaced by a load
     return total, (h, w)
 
 
@@ -540,19 +669,26 @@ def macs_per_image(name):
 
 
 def synthetic_state_dict(name, seed=42):
-    """He-uniform weights, U(-1/sqrt(fan_in), 1/sqrt(fan_in)) biases; keys '<attr>.weight'/'<attr>.bias'."""
+    """He-uniform weights, U(-1/sqrt(fan_in), 1/sqrt(fan_in)) biases, both times the layer's factor in FOLDS; a LayerNorm gets
+    gamma from U(0.5, 1.5) and beta from U(-0.3, 0.3); keys '<attr>.weight'/'<attr>.bias'."""
     rng = np.random.default_rng(seed)
     layers = network(name)[0]
+    folds = FOLDS.get(name, {})
     sd = {}
     for attr, L in layers.items():
+        if L[0] == "ln":
+            sd[attr + ".weight"] = rng.uniform(0.5, 1.5, L[1]).astype(np.float32)
+            sd[attr + ".bias"] = rng.uniform(-0.3, 0.3, L[1]).astype(np.float32)
+            continue
+        fold = folds.get(attr, 1.0)
         if L[0] == "deconv":  # [in, out, k, k]; an output pixel sums in * ceil(k / stride)^2 products
             shape, n_out = (L[1], L[2], L[3], L[3]), L[2]
             fan_in = L[1] * (-(-L[3] // L[4])) ** 2
         else:
             shape = (L[2], L[1] // conv_groups(L), L[3], L[3]) if L[0] == "conv" else (L[2], L[1])
             fan_in, n_out = int(np.prod(shape[1:])), shape[0]
-        sd[attr + ".weight"] = (rng.uniform(-1, 1, shape) * np.sqrt(6.0 / fan_in)).astype(np.float32)
-        sd[attr + ".bias"] = (rng.uniform(-1, 1, n_out) / np.sqrt(fan_in)).astype(np.float32)
+        sd[attr + ".weight"] = (rng.uniform(-1, 1, shape) * np.sqrt(6.0 / fan_in) * fold).astype(np.float32)
+        sd[attr + ".bias"] = (rng.uniform(-1, 1, n_out) / np.sqrt(fan_in) * fold).astype(np.float32)
     return sd
 
 
@@ -589,12 +725,16 @@ def build(name):
                     setattr(self, op[1], i8ie.Concat())
                 elif op[0] == "act":
                     setattr(self, op[1], i8ie.Activation(op[2], op[3] if len(op) > 3 else None))
+                elif op[0] == "matmul":
+                    setattr(self, op[1], i8ie.MatMul(transpose_a=op[3], transpose_b=op[4]))
             for attr, L in layers.items():
                 if L[0] == "deconv":
                     setattr(self, attr, i8ie.ConvTranspose2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], output_padding=L[6]))
                 elif L[0] == "conv":
                     setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], groups=conv_groups(L),
                                                     dilation=conv_dilation(L)))
+                elif L[0] == "ln":
+                    setattr(self, attr, i8ie.LayerNorm(L[1]))
                 else:
                     setattr(self, attr, i8ie.Linear(L[1], L[2]))
 
@@ -614,8 +754,12 @@ def build(name):
                     saved[op[1]] = x
                 elif op[0] == "branch":
                     saved[op[1]] = self.run(op[2], saved[op[1]], saved)
-                elif op[0] in ("add", "mul"):
+                elif op[0] == "load":
+                    x = saved[op[1]]
+                elif op[0] in ("add", "mul", "matmul"):
                     x = getattr(self, op[1])(x, saved[op[2]])
+                elif op[0] == "softmax":
+                    x = i8ie.softmax(x)
                 elif op[0] == "concat":
                     x = getattr(self, op[1])([x] + [saved[t] for t in op[2]])
                 elif op[0] == "act":
@@ -655,7 +799,7 @@ def op_names(name, *kinds):
 
 
 def layer_names(name):
-    """the weighted layers (Conv2d / ConvTranspose2d / Linear)"""
+    """the layers of the `layers` dict (Conv2d / ConvTranspose2d / Linear / LayerNorm)"""
     return op_names(name, "layer")
 
 
@@ -676,5 +820,6 @@ def activation_names(name):
 
 
 def join_names(name):
-    """every op that is a module without weights (Add, Mul, Concat, Activation): those with output_qparams() beside the layers"""
-    return op_names(name, "add", "mul", "concat", "act")
+    """every op that is a module without weights (Add, Mul, Concat, Activation, MatMul): those with output_qparams() beside
+    the layers"""
+    return op_names(name, "add", "mul", "concat", "act", "matmul")

@@ -1,5 +1,6 @@
 """numpy restatement of the quantized batched matmul and softmax (include/i8ie_hip.h, i8ie_bmm_u8 / i8ie_softmax_u8), the
-float64 references of their FP32 forms, and the ctypes side of the two descriptors.  A helper, not a conftest."""
+float64 references of their FP32 forms, the ctypes side of the two descriptors, and the trace adapter of the attention
+networks (tests/spec_ref.py composes them).  A helper, not a conftest."""
 import ctypes as C
 
 import numpy as np
@@ -116,142 +117,18 @@ def mat(ptr, rows, cols, transposed=False, s8=False, offset=0):
     return BmmMat(ptr + offset, rows * cols, 1 if transposed else cols, rows if transposed else 1, 1 if s8 else 0)
 
 
-# ---- the numpy composition of NonLocalNet (int8inferenceengine_amd/nonlocal_net.py) ----------------------------------------
-INPUT_SCALE, INPUT_ZP = np.float32(0.025), 127
-# weights, calibration batch and input of the "tiny" tests, GPU and host: tests/test_attention_host.py checks that with
-# them the expected bytes discriminate (more than one logit, spread softmax bytes, few saturated scores)
-WEIGHT_SEED, CALIB_SEED, INPUT_SEED = 42, 99, 5
+def tracer(into):
+    """a trace callback for spec_ref.forward: of every attention block of prefix p, into[p + "scores"] (the bytes of its first
+    MatMul, p + "mm1"), into[p + "softmax"] (of the softmax behind it) and into[p + "block"] (of its Add, p + "add")"""
+    at = {"p": None}
 
+    def trace(op, out, operands):
+        if op[0] == "matmul" and op[1].endswith("mm1"):
+            at["p"] = op[1][:-3]
+            into[at["p"] + "scores"] = out[0]
+        elif op[0] == "softmax":
+            into[at["p"] + "softmax"] = out[0]
+        elif op[0] == "add" and at["p"] is not None and op[1] == at["p"] + "add":
+            into[at["p"] + "block"] = out[0]
 
-def _layer(L, cur, qlayer, s_out, zp_out, per_channel):
-    import grouped_ref as gr
-    import pc_pipeline as pcp
-
-    (q, s, zp), (qw, qb, s_w) = cur, qlayer
-    if L[0] == "conv":
-        f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
-        return f(q, qw, qb, 1, L[4], L[5], s, zp, s_w, s_out, zp_out)[0]
-    f = pcp.linear_pc if per_channel else orc.linear
-    return f(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)[0]
-
-
-def nonlocal_forward(entry, x, qlayers, qp, jqp, per_channel=False, trace=None):
-    """float32 logits of a NonLocalNet plan.  entry: nonlocal_net.CONFIGS[config]; qlayers: {attr: (qw, qb, s_w)}; qp / jqp:
-    {attr: (scale, zp)} of the layers / of the MatMuls and Adds.  trace: a dict that receives, per block prefix p,
-    p + "scores", p + "softmax" and p + "block" (the Add's result) as bytes."""
-    import add_ref
-    import avgpool_ref as apr
-
-    layers, spec, _ = entry
-
-    def out_of(table, attr):
-        s, zp = table[attr]
-        return np.float32(s), int(zp)
-
-    def layer(attr, cur):
-        s_out, zp_out = out_of(qp, attr)
-        return (_layer(layers[attr], cur, qlayers[attr], s_out, zp_out, per_channel), s_out, zp_out)
-
-    def block(p, cur):
-        th, ph, g = layer(p + "theta", cur), layer(p + "phi", cur), layer(p + "g", cur)
-        s1, z1 = out_of(jqp, p + "mm1")
-        scores = matmul_u8(th[0], th[2], th[1], ph[0], ph[2], ph[1], s1, z1, transpose_a=True)
-        prob = softmax_u8(scores, s1)
-        s2, z2 = out_of(jqp, p + "mm2")
-        y = matmul_u8(g[0], g[2], g[1], prob, 0, np.float32(1.0 / 256), s2, z2, transpose_b=True)
-        y = y.reshape(result_shape(g[0].shape, prob.shape, False, True))
-        z = layer(p + "out", (y, s2, z2))
-        s3, z3 = out_of(jqp, p + "add")
-        out = add_ref.add_u8(z[0], z[2], z[1], cur[0], cur[2], cur[1], s3, z3, relu=False)
-        if trace is not None:
-            trace[p + "scores"], trace[p + "softmax"], trace[p + "block"] = scores, prob, out
-        return (out, s3, z3)
-
-    def run(ops, cur, saved):
-        for op in ops:
-            q, s, zp = cur
-            if op[0] == "layer":
-                cur = layer(op[1], cur)
-            elif op[0] == "relu":
-                cur = (orc.relu(q, zp), s, zp)
-            elif op[0] == "pool":
-                cur = (orc.max_pool2d(q, op[1], op[2]), s, zp)
-            elif op[0] == "gap":
-                cur = (apr.global_avg_pool2d_u8(q), s, zp)
-            elif op[0] == "save":
-                saved[op[1]] = cur
-            elif op[0] == "branch":
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            elif op[0] == "add":
-                q2, s2, zp2 = saved[op[2]]
-                s_o, z_o = out_of(jqp, op[1])
-                cur = (add_ref.add_u8(q, zp, s, q2, zp2, s2, s_o, z_o, relu=False), s_o, z_o)
-            elif op[0] == "flatten":
-                cur = (q.reshape(-1, op[1]), s, zp)
-            elif op[0] == "nonlocal":
-                cur = block(op[1], cur)
-            else:
-                raise ValueError("attention_ref.nonlocal_forward: op %r" % (op,))
-        return cur
-
-    q0 = orc.quantize(x, INPUT_SCALE, INPUT_ZP)
-    return orc.dequantize(*run(spec, (q0, INPUT_SCALE, INPUT_ZP), {}))
-
-
-def nonlocal_quantize_layers(entry, state_dict, per_channel=False):
-    """convert()'s weight rules, as spec_ref.quantize_layers applies them"""
-    import pc_pipeline as pcp
-
-    rule = pcp.quantize_weight_pc if per_channel else orc.quantize_weight
-    return {a: tuple(rule(state_dict[a + ".weight"], state_dict[a + ".bias"])) for a in entry[0]}
-
-
-def nonlocal_fp32_qparams(entry, state_dict, x):
-    """Stand-in for calibration without a GPU (spec_ref.fp32_qparams' method): a float64 forward over the FP32 weights; the
-    output range of every layer, MatMul and Add gives its (scale, zero_point) by the calibrator's rule.  Returns (qp, jqp)."""
-    import f64_ref
-    import grouped_ref as gr
-    import spec_ref as sr
-
-    layers, spec, _ = entry
-    qp, jqp = {}, {}
-
-    def layer(attr, v):
-        L = layers[attr]
-        w, b = state_dict[attr + ".weight"].astype(np.float64), state_dict[attr + ".bias"].astype(np.float64)
-        v = gr.conv2d_f64(v, w, b, 1, L[4], L[5]) if L[0] == "conv" else f64_ref.linear(v.reshape(v.shape[0], -1), w, b)
-        qp[attr] = sr.range_qparams(v.min(), v.max())
-        return v
-
-    def joined(attr, v):
-        jqp[attr] = sr.range_qparams(v.min(), v.max())
-        return v
-
-    def run(ops, v, saved):
-        for op in ops:
-            if op[0] == "layer":
-                v = layer(op[1], v)
-            elif op[0] == "relu":
-                v = np.maximum(v, 0.0)
-            elif op[0] == "pool":
-                v = f64_ref.max_pool2d(v, op[1], op[2])
-            elif op[0] == "gap":
-                v = v.mean(axis=(2, 3), keepdims=True)
-            elif op[0] == "save":
-                saved[op[1]] = v
-            elif op[0] == "branch":
-                saved[op[1]] = run(op[2], saved[op[1]], saved)
-            elif op[0] == "add":
-                v = joined(op[1], v + saved[op[2]])
-            elif op[0] == "flatten":
-                v = v.reshape(-1, op[1])
-            elif op[0] == "nonlocal":
-                p = op[1]
-                th, ph, g = layer(p + "theta", v), layer(p + "phi", v), layer(p + "g", v)
-                s = joined(p + "mm1", matmul(th, ph, transpose_a=True)[0])
-                y = joined(p + "mm2", matmul(g, softmax(s), transpose_b=True)[0]).reshape(g.shape)
-                v = joined(p + "add", layer(p + "out", y) + v)
-        return v
-
-    run(spec, np.asarray(x, np.float64), {})
-    return qp, jqp
+    return trace

@@ -7,7 +7,9 @@ tests called: pipeline.forward / pc_pipeline.forward_pc (alexnet, simple_conv, t
 (alexnet_paper), add_ref.forward (resnet_tiny), avgpool_ref.forward (resnet_tiny_gap, resnet18_cifar), concat_ref.forward (the
 fire networks), act_ref.forward and fp32_qparams (the MobileNetV2s, act_tiny), mul_ref.forward and fp32_qparams (se_tiny,
 mobilenetv3_small_cifar), deconv_ref.forward and fp32_qparams (the U-Nets), upsample_ref.forward (upsample_tiny,
-unet_bilinear_cifar) and dilated_ref.forward (aspp_tiny, deeplabv3_cifar).  Those are gone, so this script now records what
+unet_bilinear_cifar) and dilated_ref.forward (aspp_tiny, deeplabv3_cifar); later, the same way, attention_ref.nonlocal_forward
+and nonlocal_fp32_qparams (the non-local networks) and the ConvNeXt walk of tests/test_gpu_layernorm.py with a float64 stand-in
+written beside it (the ConvNeXts).  Those are gone, so this script now records what
 spec_ref gives.  Run it on a tree whose expected bytes are the ones to keep, never to make a failing replay pass:
 
     python tests/golden/make_spec_ref_digests.py

@@ -1,6 +1,6 @@
 """numpy restatement of the quantized LayerNorm (include/i8ie_hip.h, i8ie_layernorm_u8), the real-number value it is bounded
-against and that bound, the float64 reference of the FP32 form with its bound, and the ctypes side of the four entries.  A
-helper, not a conftest."""
+against and that bound, the float64 reference of the FP32 form with its bound, the ctypes side of the four entries, and the trace adapter of the
+ConvNeXt networks.  A helper, not a conftest."""
 import ctypes as C
 
 import numpy as np
@@ -159,3 +159,12 @@ def extreme_rows():
     out.append(("half_C16384", half))                                 # the largest V
     out.append(("all255_C16384", np.full((1, MAX_C), 255, np.uint8)))  # the largest S2 and S1^2
     return out
+
+
+def tracer(layers, into):
+    """a trace callback for spec_ref.forward: into[attr] = the output bytes of every ("ln", channels) layer"""
+    def trace(op, out, operands):
+        if op[0] == "layer" and layers[op[1]][0] == "ln":
+            into[op[1]] = out[0]
+
+    return trace

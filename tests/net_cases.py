@@ -59,3 +59,16 @@ def check_bit_exact(i8ie, net, name, x, want, *, fallback=False, graph=False, re
         assert {a: getattr(fresh, a).output_qparams() for a in expect_jqp or {}} == (expect_jqp or {})
         assert _same(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
     return got
+
+
+def traced(i8ie, net, name, x, trace):
+    """The product's own tensors where spec_ref.forward traces its main path: the top-level spec of network `name` walked op by
+    op through net.run, and `trace` -- a spec_ref trace callback that looks at the op and the output bytes only -- called
+    behind every op that produces a tensor, as trace(op, (bytes, scale, zero_point), None)."""
+    from int8inferenceengine_amd import workloads as wl
+
+    cur, saved = i8ie.quantize(i8ie.tensor(x), float(sr.pipeline.INPUT_SCALE), sr.pipeline.INPUT_ZP), {}
+    for op in wl.network(name)[1]:
+        cur = net.run([op], cur, saved)
+        if op[0] not in ("save", "branch", "load"):
+            trace(op, (cur.numpy(), cur.scale, cur.zero_point), None)

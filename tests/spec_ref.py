@@ -3,25 +3,28 @@
 
 Nothing is defined arithmetically here.  Every op is the function of its own module -- the reference's ops in oracle/orc.py,
 per-channel requantisation in pc_pipeline, and grouped_ref, add_ref, avgpool_ref, concat_ref, act_ref, mul_ref, deconv_ref,
-upsample_ref, dilated_ref for what the reference does not have -- and this module only walks the spec with (bytes, scale,
-zero_point) in hand.  A new op adds one branch to forward(), one to fp32_qparams() if it is calibrated, its name to OPS, and
+upsample_ref, dilated_ref, attention_ref, layernorm_ref for what the reference does not have -- and this module only walks
+the spec with (bytes, scale, zero_point) in hand.  A new op adds one branch to forward(), one to fp32_qparams() if it is calibrated, its name to OPS, and
 its arithmetic in a module of its own.
 
   OPS                                the op names a spec may hold; anything else raises ValueError
   forward(...)                       float32 logits of a network
   fp32_qparams(...)                  stand-in for calibration without a GPU: a float64 forward over the FP32 weights
   quantize_layers(...)               convert()'s weight rules
-  outputs_of(name, into)             a trace callback that keeps the output bytes of the ops called `name`"""
+  outputs_of(name, into)             a trace callback that keeps the output bytes of the ops called `name`
+  traces(*callbacks)                 several trace callbacks as one"""
 import numpy as np
 
 import act_ref as acr
 import add_ref as ar
+import attention_ref as atr
 import avgpool_ref as apr
 import concat_ref as cr
 import deconv_ref as dr
 import dilated_ref as dl
 import f64_ref
 import grouped_ref as gr
+import layernorm_ref as lnr
 import mul_ref as mr
 import orc
 import pc_pipeline as pcp
@@ -29,7 +32,8 @@ import pipeline
 import upsample_ref as ur
 
 f32 = np.float32
-OPS = frozenset(["layer", "relu", "pool", "avgpool", "gap", "save", "branch", "add", "mul", "concat", "act", "upsample", "flatten"])
+OPS = frozenset(["layer", "relu", "pool", "avgpool", "gap", "save", "branch", "add", "mul", "concat", "act", "upsample", "flatten",
+                 "matmul", "softmax", "load"])
 
 # synthetic weights, calibration batch and input of the network tests, GPU and host: with them the traced tensors keep the
 # limits of act_ref.nontrivial and mul_ref.nontrivial.  (CALIB_IMAGES is the batch of fp32_qparams in the host tests; the GPU
@@ -39,8 +43,12 @@ WEIGHT_SEED, CALIB_SEED, CALIB_IMAGES, INPUT_SEED = 42, 99, 4, 5
 
 def _layer(L, cur, qlayer, s_out, zp_out, per_channel):
     """the output bytes of a weighted layer.  Conv: the reference convolution per group, a dilated kernel inflated by zeros
-    (the kernel extent is the weight's); deconv: the reference convolution of the equivalent problem; fc: the reference linear"""
-    (q, s, zp), (qw, qb, s_w) = cur, qlayer
+    (the kernel extent is the weight's); deconv: the reference convolution of the equivalent problem; fc: the reference linear;
+    ln: layernorm_ref's LayerNorm at eps 1e-5, qlayer its float32 (gamma, beta)"""
+    q, s, zp = cur
+    if L[0] == "ln":
+        return lnr.layer_norm_any(q, s, f32(1e-5), qlayer[0], qlayer[1], s_out, zp_out)
+    qw, qb, s_w = qlayer
     if L[0] == "conv":
         d = dl.layer_dilation(L)
         f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
@@ -56,7 +64,8 @@ def _layer(L, cur, qlayer, s_out, zp_out, per_channel):
 
 def forward(networks_entry, x, qlayers, out_qparams, join_qparams=None, per_channel=False, trace=None):
     """x: float32 NCHW.  qlayers: {attr: (qw, qb, s_w)} as quantize_layers gives them (s_w a scalar or, per_channel, float32
-    [out]).  out_qparams: {attr: (scale, zp)} of the layers, join_qparams: the same of the Adds, Muls, Concats and Activations.
+    [out]).  out_qparams: {attr: (scale, zp)} of the layers, join_qparams: the same of the Adds, Muls, Concats, Activations
+    and MatMuls.
     trace: called as trace(op, (bytes, scale, zp), operands) behind every op that produces bytes, operands the list of
     (bytes, scale, zp) it read, the current tensor first.  Returns float32 logits."""
     layers, spec, _ = networks_entry
@@ -70,8 +79,11 @@ def forward(networks_entry, x, qlayers, out_qparams, join_qparams=None, per_chan
             if name == "branch":
                 saved[op[1]] = run(op[2], saved[op[1]], saved)
                 continue
+            if name == "load":
+                cur = saved[op[1]]
+                continue
             operands = [cur]
-            if name in ("layer", "add", "mul", "concat", "act"):  # the ops with output parameters of their own
+            if name in ("layer", "add", "mul", "concat", "act", "matmul"):  # the ops with output parameters of their own
                 s_out, zp_out = (out_qparams if name == "layer" else join_qparams or {})[op[1]]
                 s_out, zp_out = f32(s_out), int(zp_out)
             if name == "layer":
@@ -90,6 +102,13 @@ def forward(networks_entry, x, qlayers, out_qparams, join_qparams=None, per_chan
                 q2, s2, zp2 = saved[op[2]]
                 operands.append(saved[op[2]])
                 cur = ((ar.add_u8 if name == "add" else mr.mul_u8)(q, zp, s, q2, zp2, s2, s_out, zp_out, relu=False), s_out, zp_out)
+            elif name == "matmul":
+                q2, s2, zp2 = saved[op[2]]
+                operands.append(saved[op[2]])
+                out = atr.matmul_u8(q, zp, s, q2, zp2, s2, s_out, zp_out, transpose_a=op[3], transpose_b=op[4])
+                cur = (out.reshape(atr.result_shape(q.shape, q2.shape, op[3], op[4])), s_out, zp_out)
+            elif name == "softmax":
+                cur = (atr.softmax_u8(q, s), f32(1.0 / 256), 0)
             elif name == "concat":
                 operands += [saved[t] for t in op[2]]
                 cur = (cr.cat_u8(operands, s_out, zp_out), s_out, zp_out)
@@ -118,6 +137,15 @@ def outputs_of(name, into):
     return trace
 
 
+def traces(*callbacks):
+    """one trace callback that calls every one of `callbacks`"""
+    def trace(op, out, operands):
+        for t in callbacks:
+            t(op, out, operands)
+
+    return trace
+
+
 def range_qparams(lo, hi):
     """the calibrator's rule (src/calibrator.cc:24-37 at quantile 1) on a real-valued range"""
     lo, hi = min(float(lo), 0.0), max(float(hi), 0.0)
@@ -130,7 +158,7 @@ def range_qparams(lo, hi):
 
 def fp32_qparams(networks_entry, state_dict, x):
     """Stand-in for calibration without a GPU: a numpy forward in float64 over the FP32 weights; the output range of every
-    layer, Add, Mul, Concat and Activation gives its (scale, zero_point) by the calibrator's rule.  No registry network needs
+    layer, Add, Mul, Concat, Activation and MatMul gives its (scale, zero_point) by the calibrator's rule.  No registry network needs
     avgpool or upsample here; they raise like any other op.  Returns (layer qparams, join qparams)."""
     layers, spec, _ = networks_entry
     qp, jqp = {}, {}
@@ -141,7 +169,10 @@ def fp32_qparams(networks_entry, state_dict, x):
             if name == "layer":
                 L = layers[op[1]]
                 w, b = state_dict[op[1] + ".weight"].astype(np.float64), state_dict[op[1] + ".bias"].astype(np.float64)
-                if L[0] == "conv":
+                if L[0] == "ln":  # over the channel axis: axis 1 of [n, c, h, w], the last of [n, f]
+                    rows = np.ascontiguousarray(np.moveaxis(v, 1, -1))
+                    v = np.ascontiguousarray(np.moveaxis(lnr.layer_norm_f64(rows, w, b, 1e-5), -1, 1))
+                elif L[0] == "conv":
                     v = gr.conv2d_f64(v, dl.inflate(w, dl.layer_dilation(L)), b, gr.layer_groups(L), L[4], L[5])
                 elif L[0] == "deconv":
                     v = dr.scatter(v, w, b, L[4], L[5], L[6])
@@ -162,6 +193,13 @@ def fp32_qparams(networks_entry, state_dict, x):
                 v = v + saved[op[2]]
             elif name == "mul":
                 v = v * mr.as_gate(v, saved[op[2]])
+            elif name == "load":
+                v = saved[op[1]]
+            elif name == "matmul":
+                v2 = saved[op[2]]
+                v = atr.matmul(v, v2, op[3], op[4])[0].reshape(atr.result_shape(v.shape, v2.shape, op[3], op[4]))
+            elif name == "softmax":
+                v = atr.softmax(v)
             elif name == "concat":
                 v = np.concatenate([v] + [saved[t] for t in op[2]], axis=1)
             elif name == "gap":
@@ -170,7 +208,7 @@ def fp32_qparams(networks_entry, state_dict, x):
                 v = v.reshape(-1, op[1])
             else:
                 raise ValueError("spec_ref.fp32_qparams: op %r" % (op,))
-            if name in ("layer", "act", "add", "mul", "concat"):
+            if name in ("layer", "act", "add", "mul", "concat", "matmul"):
                 (qp if name == "layer" else jqp)[op[1]] = range_qparams(v.min(), v.max())
         return v
 
@@ -181,10 +219,11 @@ def fp32_qparams(networks_entry, state_dict, x):
 def quantize_layers(networks_entry, state_dict, per_channel=False):
     """{attr: (qw, qb, s_w)} by convert()'s rules on the weight tensors as they stand ([kc, c / groups, kh, kw] of a grouped
     conv, the compact kernel of a dilated one), a "deconv" layer as its equivalent kernel W~ [out, in, k, k]: per tensor the
-    oracle's joint min / max over the whole weight and the bias, per channel the same per row of the [kc, K] matrix"""
+    oracle's joint min / max over the whole weight and the bias, per channel the same per row of the [kc, K] matrix.  An "ln"
+    layer has no INT8 weights: its float32 (weight, bias) as they stand."""
     rule = pcp.quantize_weight_pc if per_channel else orc.quantize_weight
     out = {}
     for attr, L in networks_entry[0].items():
-        w = state_dict[attr + ".weight"]
-        out[attr] = tuple(rule(dr.equivalent_weight(w) if L[0] == "deconv" else w, state_dict[attr + ".bias"]))
+        w, b = state_dict[attr + ".weight"], state_dict[attr + ".bias"]
+        out[attr] = (w, b) if L[0] == "ln" else tuple(rule(dr.equivalent_weight(w) if L[0] == "deconv" else w, b))
     return out

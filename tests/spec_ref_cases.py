@@ -10,7 +10,9 @@ import zlib
 
 import numpy as np
 
+import attention_ref as atr
 import deconv_ref as dr
+import layernorm_ref as lnr
 import mul_ref as mr
 import spec_ref as sr
 import upsample_ref as ur
@@ -24,8 +26,11 @@ FAMILY = {
     "se_tiny": "mul", "mobilenetv3_small_cifar": "mul",
     "unet_tiny": "deconv", "unet_cifar": "deconv",
     "upsample_tiny": "upsample", "unet_bilinear_cifar": "upsample", "aspp_tiny": "upsample", "deeplabv3_cifar": "upsample",
+    "nonlocal_tiny": "attention", "nonlocal_resnet_cifar": "attention",
+    "convnext_tiny": "layernorm", "convnext_cifar": "layernorm",
 }
-CALIBRATED = ("act", "mul", "deconv")  # the families whose host tests take their parameters from fp32_qparams
+# the families whose host tests take their parameters from fp32_qparams
+CALIBRATED = ("act", "mul", "deconv", "attention", "layernorm")
 
 
 def synthetic_qparams(attrs):
@@ -53,7 +58,8 @@ def run(family, entry, x, qlayers, qp, jqp, per_channel):
     layers, spec, _ = entry
     trace = [] if family == "upsample" else {}
     tracer = {"plain": None, "concat": sr.outputs_of("concat", trace), "act": sr.outputs_of("act", trace),
-              "mul": mr.tracer(spec, trace), "deconv": dr.tracer(layers, trace), "upsample": ur.tracer(trace)}[family]
+              "mul": mr.tracer(spec, trace), "deconv": dr.tracer(layers, trace), "upsample": ur.tracer(trace),
+              "attention": atr.tracer(trace), "layernorm": sr.traces(lnr.tracer(layers, trace), atr.tracer(trace))}[family]
     return sr.forward(entry, x, qlayers, qp, jqp, per_channel, tracer), trace
 
 

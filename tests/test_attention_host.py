@@ -156,41 +156,61 @@ def test_module_saves_a_matmul_as_qparams_only(i8ie):
 
 
 # ---- the "tiny" non-local network: the reference composition alone, with the seeds the GPU test uses ------------------------
+BLOCKS = ("a_", "b_")   # the prefixes of nonlocal_tiny's two blocks, in spec order
+
+
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [1, 5])
 def test_nonlocal_tiny_reference_discriminates(orc, batch, per_channel):
-    from int8inferenceengine_amd import nonlocal_net as nl
+    import spec_ref as sr
+    from int8inferenceengine_amd import workloads as wl
 
-    entry = nl.CONFIGS["tiny"]
-    sd = nl.synthetic_state_dict("tiny", ar.WEIGHT_SEED)
-    qp, jqp = ar.nonlocal_fp32_qparams(entry, sd, nl.synthetic_input("tiny", 8, seed=ar.CALIB_SEED))
-    assert sorted(qp) == sorted(nl.layer_names("tiny")) and sorted(jqp) == sorted(nl.join_names("tiny"))
+    name, entry = "nonlocal_tiny", wl.network("nonlocal_tiny")
+    sd = wl.synthetic_state_dict(name, sr.WEIGHT_SEED)
+    qp, jqp = sr.fp32_qparams(entry, sd, wl.synthetic_input(name, 8, seed=sr.CALIB_SEED))
+    assert sorted(qp) == sorted(wl.layer_names(name)) and sorted(jqp) == sorted(wl.join_names(name))
     trace = {}
-    x = nl.synthetic_input("tiny", batch, seed=ar.INPUT_SEED)
-    logits = ar.nonlocal_forward(entry, x, ar.nonlocal_quantize_layers(entry, sd, per_channel), qp, jqp, per_channel, trace)
+    x = wl.synthetic_input(name, batch, seed=sr.INPUT_SEED)
+    logits = sr.forward(entry, x, sr.quantize_layers(entry, sd, per_channel), qp, jqp, per_channel, ar.tracer(trace))
     assert logits.shape == (batch, 10) and len(np.unique(logits)) > 1
-    assert sorted(trace) == sorted(p + t for p in nl.blocks("tiny") for t in ("scores", "softmax", "block"))
+    assert sorted(trace) == sorted(p + t for p in BLOCKS for t in ("scores", "softmax", "block"))
     assert trace["a_scores"].shape == (batch, 64, 64) and trace["b_scores"].shape == (batch, 16, 16)
     assert trace["a_block"].shape == (batch, 16, 8, 8) and trace["b_block"].shape == (batch, 20, 4, 4)
-    for p in nl.blocks("tiny"):
+    for p in BLOCKS:
         assert len(np.unique(trace[p + "softmax"])) >= 16, p
         assert ((trace[p + "scores"] == 0) | (trace[p + "scores"] == 255)).mean() < 0.05, p
 
 
 def test_nonlocal_configs_and_state_dict():
-    from int8inferenceengine_amd import nonlocal_net as nl
     from int8inferenceengine_amd import workloads as wl
 
-    assert sorted(nl.CONFIGS) == ["cifar", "tiny"] and "nonlocal" not in wl.OPS and len(wl.NETWORKS) == 21
-    L = nl.CONFIGS["tiny"][0]
+    assert {"matmul", "softmax", "load"} <= wl.OPS and "nonlocal" not in wl.OPS
+    L, spec, shape = wl.network("nonlocal_tiny")
+    assert shape == (3, 32, 32) and list(L) == ["stem", "a_theta", "a_phi", "a_g", "a_out", "down", "b_theta", "b_phi", "b_g", "b_out", "fc"]
     assert L["b_theta"] == ("conv", 20, 12, 1, 1, 0) and L["down"] == ("conv", 16, 20, 3, 2, 1) and L["fc"] == ("fc", 20, 10)
-    C = nl.CONFIGS["cifar"][0]
+    assert wl.op_names("nonlocal_tiny", "matmul") == ["a_mm1", "a_mm2", "b_mm1", "b_mm2"] and wl.add_names("nonlocal_tiny") == ["a_add", "b_add"]
+    # by hand: stem 16x16 x 16 x 27; block A at 8x8: four 1x1 convs 16 <-> 16; down 4x4 x 20 x 144; block B at 4x4: four 1x1
+    # convs 20 <-> 12; fc 200.  The products of the MatMuls are not counted.
+    assert wl.macs_per_image("nonlocal_tiny") == 256 * 16 * 27 + 4 * 64 * 16 * 16 + 16 * 20 * 144 + 4 * 16 * 20 * 12 + 200 == 237768
+    C, cspec, _ = wl.network("nonlocal_resnet_cifar")
+    R, rspec, _ = wl.network("resnet18_cifar")
     assert C["nl_theta"] == ("conv", 256, 128, 1, 1, 0) and C["nl_out"] == ("conv", 128, 256, 1, 1, 0)
-    assert set(C) - set(wl.network("resnet18_cifar")[0]) == {"nl_theta", "nl_phi", "nl_g", "nl_out"}
-    spec = nl.CONFIGS["cifar"][1]
-    assert spec.index(("nonlocal", "nl_")) == spec.index(("save", "s4b1")) - 2
-    a, b = nl.synthetic_state_dict("tiny", 3), nl.synthetic_state_dict("tiny", 3)
+    assert set(C) - set(R) == {"nl_theta", "nl_phi", "nl_g", "nl_out"} and {a: C[a] for a in R} == R
+    assert list(C)[list(C).index("s4b1c1") - 4:list(C).index("s4b1c1")] == ["nl_theta", "nl_phi", "nl_g", "nl_out"]
+    # the block and its relu sit where stage 3 has ended, and nothing else of resnet18_cifar's spec moved
+    cut, block = rspec.index(("save", "s4b1")), wl.network("nonlocal_tiny")[1][3:14]
+    assert cspec.index(("add", "nl_add", "nl_x")) == cspec.index(("save", "s4b1")) - 2 and cspec[cspec.index(("save", "s4b1")) - 1] == ("relu",)
+    assert cspec[:cut] == rspec[:cut] and cspec[cut + len(block) + 1:] == rspec[cut:] and cspec[cut] == ("save", "nl_x")
+    assert [op[0] for op in cspec[cut:cut + len(block)]] == [op[0] for op in block]
+    # by hand: every weighted layer of resnet18_cifar (its pinned figure leaves the three 1x1 projections out: 3 x 2097152)
+    # and the block's four 1x1 convs 256 <-> 128 at 8x8
+    assert wl.macs_per_image("nonlocal_resnet_cifar") == 549131264 + 3 * 2097152 + 4 * 64 * 256 * 128 == 563811328
+    a, b = wl.synthetic_state_dict("nonlocal_tiny", 3), wl.synthetic_state_dict("nonlocal_tiny", 3)
     assert sorted(a) == sorted(k + s for k in L for s in (".weight", ".bias"))
     assert all(np.array_equal(a[k], b[k]) for k in a) and a["a_theta.weight"].shape == (16, 16, 1, 1)
-    net = nl.build("tiny")
-    assert isinstance(net, nl.NonLocalNet) and [k for k, _ in net._layers()] == nl.layer_names("tiny") + nl.join_names("tiny")
+    assert wl.FOLDS["nonlocal_tiny"] == {"a_theta": 1 / np.sqrt(16), "b_theta": 1 / np.sqrt(12)} and wl.FOLDS["nonlocal_resnet_cifar"] == {"nl_theta": 1 / np.sqrt(128)}
+    net = wl.build("nonlocal_tiny")
+    assert type(net).__name__ == "SpecNet_nonlocal_tiny"
+    assert [k for k, _ in net._layers()] == wl.join_names("nonlocal_tiny") + wl.layer_names("nonlocal_tiny")
+    assert wl.join_names("nonlocal_tiny") == ["a_mm1", "a_mm2", "a_add", "b_mm1", "b_mm2", "b_add"] and wl.layer_names("nonlocal_tiny") == list(L)
+    assert (net.a_mm1.transpose_a, net.a_mm1.transpose_b, net.b_mm2.transpose_a, net.b_mm2.transpose_b) == (True, False, False, True)

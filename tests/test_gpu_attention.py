@@ -458,78 +458,47 @@ def test_matmul_is_calibrated_like_a_layer_and_round_trips(i8ie):
     assert np.array_equal(r1, ar.matmul_u8(qa.numpy(), 120, f32(0.05), qb.numpy(), 128, f32(0.04), f32(s_o), zp_o, transpose_b=True))
 
 
-# ---- the "tiny" non-local network --------------------------------------------------------------------------------------
-_TINY = {}
+# ---- nonlocal_tiny ----------------------------------------------------------------------------------------------------------
+NAME = "nonlocal_tiny"
 
 
-def _tiny(per_channel):
-    """(net, qlayers, qp, jqp): NonLocalNet("tiny") with attention_ref's seeds, calibrated once per weight mode"""
-    from int8inferenceengine_amd import nonlocal_net as nl
+def _case(per_channel, batch):
+    """(net, jqp, x, expected logits, the reference's traced tensors) with spec_ref's seeds"""
+    import net_cases as nc
+    import spec_ref as sr
+    from int8inferenceengine_amd import workloads as wl
 
-    if per_channel not in _TINY:
-        sd = nl.synthetic_state_dict("tiny", ar.WEIGHT_SEED)
-        net = nl.calibrated("tiny", sd, calib_batch=nl.synthetic_input("tiny", 8, seed=ar.CALIB_SEED), per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in nl.layer_names("tiny")}
-        jqp = {a: getattr(net, a).output_qparams() for a in nl.join_names("tiny")}
-        _TINY[per_channel] = (net, ar.nonlocal_quantize_layers(nl.CONFIGS["tiny"], sd, per_channel), qp, jqp)
-    return _TINY[per_channel]
-
-
-def _traced(i8ie, net, x):
-    """the product's own tensors where attention_ref.nonlocal_forward traces: the plan walked op by op through the net's
-    layers, each block's scores, softmax and result observed"""
-    from int8inferenceengine_amd import nonlocal_net as nl
-
-    cur, saved, out = i8ie.quantize(i8ie.tensor(x), 0.025, 127), {}, {}
-    for op in nl.CONFIGS["tiny"][1]:
-        if op[0] != "nonlocal":
-            cur = net.run([op], cur, saved)
-            continue
-        p = op[1]
-        s = getattr(net, p + "mm1")(getattr(net, p + "theta")(cur), getattr(net, p + "phi")(cur))
-        pr = i8ie.softmax(s)
-        y = getattr(net, p + "mm2")(getattr(net, p + "g")(cur), pr)
-        cur = getattr(net, p + "add")(getattr(net, p + "out")(y), cur)
-        out[p + "scores"], out[p + "softmax"], out[p + "block"] = s.numpy(), pr.numpy(), cur.numpy()
-    return out
+    net, qlayers, qp, jqp = nc.calibrated(NAME, per_channel, calib_images=8)
+    x = wl.synthetic_input(NAME, batch, seed=sr.INPUT_SEED)
+    trace = {}
+    want = sr.forward(wl.network(NAME), x, qlayers, qp, jqp, per_channel, ar.tracer(trace))
+    return net, jqp, x, want, trace
 
 
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [1, 5])
 def test_nonlocal_tiny_bit_exact(i8ie, batch, per_channel):
-    import _CXX_i8ie as cx
-    from int8inferenceengine_amd import nonlocal_net as nl
+    import net_cases as nc
 
-    net, qlayers, qp, jqp = _tiny(per_channel)
+    net, jqp, x, want, trace = _case(per_channel, batch)
     assert all(s > 0 and s != 1.0 for s, _ in jqp.values()), jqp   # the MatMuls and Adds were calibrated
-    x = nl.synthetic_input("tiny", batch, seed=ar.INPUT_SEED)
-    trace = {}
-    want = ar.nonlocal_forward(nl.CONFIGS["tiny"], x, qlayers, qp, jqp, per_channel, trace)
     assert want.shape == (batch, 10) and len(np.unique(want)) > 1
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    mine = _traced(i8ie, net, x)
-    assert sorted(mine) == sorted(trace)
+    nc.check_bit_exact(i8ie, net, NAME, x, want, fallback=True)
+    mine = {}
+    nc.traced(i8ie, net, NAME, x, ar.tracer(mine))
+    assert sorted(mine) == sorted(trace) and len(trace) == 6
     for k in trace:
         assert mine[k].shape == trace[k].shape and np.array_equal(mine[k], trace[k]), k
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
 
 
-def test_nonlocal_tiny_kernels_graph_replay_and_reload(i8ie):
+def test_nonlocal_tiny_kernels_graph_replay_and_reload(i8ie, tmp_path):
     """block A's products run in bmm_mfma, block B's first one (k = 12) in bmm_direct; the forward replayed as one HIP graph
-    and a fresh net loaded from the quantized state dict give the eager bytes"""
+    and a fresh net loaded from the saved quantized state give the expected bytes"""
     import _CXX_i8ie as cx
-    from int8inferenceengine_amd import nonlocal_net as nl
-    from int8inferenceengine_amd.graph import GraphedForward
+    import net_cases as nc
 
-    net, _, _, jqp = _tiny(False)
-    x = nl.synthetic_input("tiny", 5, seed=ar.INPUT_SEED)
-    eager = net(i8ie.tensor(x)).numpy()
+    net, jqp, x, want, _ = _case(False, 5)
+    nc.check_bit_exact(i8ie, net, NAME, x, want, graph=True, reload_dir=tmp_path, expect_jqp=jqp)
     cx.synchronize()
     cx.profile_start()
     try:
@@ -541,10 +510,3 @@ def test_nonlocal_tiny_kernels_graph_replay_and_reload(i8ie):
         launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
     print(launches)
     assert launches.get("bmm_mfma") == 3 and launches.get("bmm_direct") == 1 and launches.get("softmax_u8_wave") == 2, launches
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert np.array_equal(g().numpy().view(np.uint32), eager.view(np.uint32))
-    fresh = nl.build("tiny")
-    fresh.load_quantized(net.quantized_state_dict())
-    assert {a: getattr(fresh, a).output_qparams() for a in jqp} == jqp
-    assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), eager.view(np.uint32))

@@ -2,7 +2,7 @@
 restatement of the definition (tests/layernorm_ref.py), never against the code under test: the flat entry over every width at
 which the kernel changes its lane-group size or its form, through all three kernels, aligned, offset by a byte and in place;
 the statistics extremes; the bordered / re-biased NHWC entry with guard bytes; the FP32 entry against float64; the Python
-surface (shapes, launch counts, calibration, save / load, graph replay) and ConvNeXt("tiny")."""
+surface (shapes, launch counts, calibration, save / load, graph replay) and convnext_tiny."""
 import ctypes as C
 import itertools
 
@@ -10,16 +10,12 @@ import numpy as np
 import pytest
 
 import abi
-import add_ref
 import attention_ref as ar
-import avgpool_ref as apr
-import act_ref as acr
 import f64_ref
 import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import layernorm_ref as lr
 import orc
-import pc_pipeline as pcp
 import spec_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -381,161 +377,48 @@ def test_calibrated_like_a_layer_round_trips_and_replays(i8ie, tmp_path):
         assert np.array_equal(g().numpy().view(np.uint32), ref.view(np.uint32))
 
 
-# ---- ConvNeXt("tiny") ----------------------------------------------------------------------------------------------------
-WEIGHT_SEED, CALIB_SEED, INPUT_SEED = 42, 99, 5
-_TINY = {}
+# ---- convnext_tiny ----------------------------------------------------------------------------------------------------------
+NAME = "convnext_tiny"
 
 
-def _weighted(L, cur, qlayer, s_out, zp_out, per_channel):
-    (q, s, zp), (qw, qb, s_w) = cur, qlayer
-    if L[0] == "conv":
-        f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
-        return f(q, qw, qb, L[6] if len(L) > 6 else 1, L[4], L[5], s, zp, s_w, s_out, zp_out)[0]
-    f = pcp.linear_pc if per_channel else orc.linear
-    return f(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_out, zp_out)[0]
-
-
-def _convnext_forward(entry, sd, x, qlayers, qp, per_channel, trace):
-    """float32 logits of a ConvNeXt plan by the numpy restatements: spec_ref's layer functions, attention_ref's matmul and
-    softmax, layernorm_ref's LayerNorm.  qp: {attr: (scale, zp)} of every layer of the module.  trace[attr] receives the bytes
-    of every LayerNorm, every block and the attention's scores and softmax."""
-    layers, spec, _ = entry
-
-    def out_of(attr):
-        return f32(qp[attr][0]), int(qp[attr][1])
-
-    def layer(attr, cur):
-        s_o, z_o = out_of(attr)
-        return (_weighted(layers[attr], cur, qlayers[attr], s_o, z_o, per_channel), s_o, z_o)
-
-    def ln(attr, cur):
-        s_o, z_o = out_of(attr)
-        out = lr.layer_norm_any(cur[0], cur[1], f32(1e-5), sd[attr + ".weight"], sd[attr + ".bias"], s_o, z_o)
-        trace[attr] = out
-        return (out, s_o, z_o)
-
-    def add(attr, a, b):
-        s_o, z_o = out_of(attr)
-        return (add_ref.add_u8(a[0], a[2], a[1], b[0], b[2], b[1], s_o, z_o, relu=False), s_o, z_o)
-
-    cur = (orc.quantize(x, ar.INPUT_SCALE, ar.INPUT_ZP), ar.INPUT_SCALE, ar.INPUT_ZP)
-    for op in spec:
-        if op[0] == "layer":
-            cur = layer(op[1], cur)
-        elif op[0] == "ln":
-            cur = ln(op[1], cur)
-        elif op[0] == "cnblock":
-            p = op[1]
-            y = layer(p + "pw1", ln(p + "ln", layer(p + "dw", cur)))
-            s_o, z_o = out_of(p + "act")
-            y = (acr.act_u8(y[0], *acr.act_of(("act", p + "act", "hardswish")), y[1], y[2], s_o, z_o), s_o, z_o)
-            cur = add(p + "add", layer(p + "pw2", y), cur)
-            trace[p + "block"] = cur[0]
-        elif op[0] == "attn":
-            p = op[1]
-            y = ln(p + "ln", cur)
-            th, ph, g = layer(p + "theta", y), layer(p + "phi", y), layer(p + "g", y)
-            s1, z1 = out_of(p + "mm1")
-            scores = ar.matmul_u8(th[0], th[2], th[1], ph[0], ph[2], ph[1], s1, z1, transpose_a=True)
-            prob = ar.softmax_u8(scores, s1)
-            s2, z2 = out_of(p + "mm2")
-            z = ar.matmul_u8(g[0], g[2], g[1], prob, 0, f32(1.0 / 256), s2, z2, transpose_b=True).reshape(g[0].shape)
-            cur = add(p + "add", layer(p + "out", (z, s2, z2)), cur)
-            trace[p + "scores"], trace[p + "softmax"], trace[p + "block"] = scores, prob, cur[0]
-        elif op[0] == "gap":
-            cur = (apr.global_avg_pool2d_u8(cur[0]), cur[1], cur[2])
-        elif op[0] == "flatten":
-            cur = (cur[0].reshape(-1, op[1]), cur[1], cur[2])
-        else:
-            raise ValueError(op)
-    return orc.dequantize(*cur)
-
-
-def _tiny(per_channel):
-    from int8inferenceengine_amd import convnext_net as cn
-
-    if per_channel not in _TINY:
-        sd = cn.synthetic_state_dict("tiny", WEIGHT_SEED)
-        net = cn.calibrated("tiny", sd, calib_batch=cn.synthetic_input("tiny", 8, seed=CALIB_SEED), per_channel=per_channel)
-        qp = {a: getattr(net, a).output_qparams() for a in cn.layer_names("tiny") + cn.join_names("tiny")}
-        rule = pcp.quantize_weight_pc if per_channel else orc.quantize_weight
-        qlayers = {a: tuple(rule(sd[a + ".weight"], sd[a + ".bias"])) for a, L in cn.CONFIGS["tiny"][0].items() if L[0] != "ln"}
-        _TINY[per_channel] = (net, sd, qlayers, qp)
-    return _TINY[per_channel]
-
-
-def _traced(i8ie, net, x):
-    """the product's own tensors where _convnext_forward traces"""
-    from int8inferenceengine_amd import convnext_net as cn
-
-    cur, out = i8ie.quantize(i8ie.tensor(x), 0.025, 127), {}
-    L = lambda a: getattr(net, a)  # noqa: E731
-    for op in cn.CONFIGS["tiny"][1]:
-        p = op[1] if len(op) > 1 else None
-        if op[0] == "ln":
-            cur = L(p)(cur)
-            out[p] = cur.numpy()
-        elif op[0] == "cnblock":
-            y = L(p + "ln")(L(p + "dw")(cur))
-            out[p + "ln"] = y.numpy()
-            cur = L(p + "add")(L(p + "pw2")(L(p + "act")(L(p + "pw1")(y))), cur)
-            out[p + "block"] = cur.numpy()
-        elif op[0] == "attn":
-            y = L(p + "ln")(cur)
-            s = L(p + "mm1")(L(p + "theta")(y), L(p + "phi")(y))
-            pr = i8ie.softmax(s)
-            cur = L(p + "add")(L(p + "out")(L(p + "mm2")(L(p + "g")(y), pr)), cur)
-            out[p + "ln"], out[p + "scores"], out[p + "softmax"], out[p + "block"] = y.numpy(), s.numpy(), pr.numpy(), cur.numpy()
-        else:
-            cur = net.run([op], cur)
-    return out
+def _tracer(layers, into):
+    """every LayerNorm's bytes, the attention block's scores, softmax and result, and every block's Add"""
+    return sr.traces(lr.tracer(layers, into), ar.tracer(into), sr.outputs_of("add", into))
 
 
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [1, 5])
 def test_convnext_tiny_bit_exact(i8ie, batch, per_channel, tmp_path):
-    import _CXX_i8ie as cx
-    from int8inferenceengine_amd import convnext_net as cn
-    from int8inferenceengine_amd.graph import GraphedForward
+    import net_cases as nc
+    from int8inferenceengine_amd import workloads as wl
 
-    net, sd, qlayers, qp = _tiny(per_channel)
-    assert all(s > 0 and s != 1.0 for s, _ in qp.values()), qp   # every layer, LayerNorm and join was calibrated
-    x = cn.synthetic_input("tiny", batch, seed=INPUT_SEED)
+    net, qlayers, qp, jqp = nc.calibrated(NAME, per_channel, calib_images=8)
+    both = dict(qp, **jqp)
+    assert all(s > 0 and s != 1.0 for s, _ in both.values()), both   # every layer, LayerNorm and join was calibrated
+    entry = wl.network(NAME)
+    x = wl.synthetic_input(NAME, batch, seed=sr.INPUT_SEED)
     trace = {}
-    want = _convnext_forward(cn.CONFIGS["tiny"], sd, x, qlayers, qp, per_channel, trace)
+    want = sr.forward(entry, x, qlayers, qp, jqp, per_channel, _tracer(entry[0], trace))
     assert want.shape == (batch, 10) and len(np.unique(want)) > 1
     for k in ("stem_ln", "a_ln", "down_ln", "b_ln", "t_ln"):
         assert len(np.unique(trace[k])) >= 32 and ((trace[k] == 0) | (trace[k] == 255)).mean() < 0.05, k
-    got = net(i8ie.tensor(x)).numpy()
-    assert got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-    mine = _traced(i8ie, net, x)
-    assert sorted(mine) == sorted(trace)
+    nc.check_bit_exact(i8ie, net, NAME, x, want, fallback=True, graph=True, reload_dir=tmp_path, expect_jqp=both)
+    mine = {}
+    nc.traced(i8ie, net, NAME, x, _tracer(entry[0], mine))
+    assert sorted(mine) == sorted(trace) == sorted(["stem_ln", "a_ln", "down_ln", "b_ln", "t_ln", "head_ln", "a_add", "b_add", "t_add",
+                                                    "t_scores", "t_softmax", "t_block"])
     for k in trace:
         assert mine[k].shape == trace[k].shape and np.array_equal(mine[k], trace[k]), k
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert np.array_equal(fb.view(np.uint32), want.view(np.uint32))
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert np.array_equal(g().numpy().view(np.uint32), want.view(np.uint32))
-    path = str(tmp_path / "tiny.npz")
-    net.save_quantized(path)
-    fresh = cn.build("tiny")
-    fresh.load_quantized_file(path)
-    assert {a: getattr(fresh, a).output_qparams() for a in qp} == qp
-    assert np.array_equal(fresh(i8ie.tensor(x)).numpy().view(np.uint32), want.view(np.uint32))
 
 
 def test_convnext_tiny_launches(i8ie):
     """six LayerNorms, one launch each: five on NHWC activations, one on [n, 20] rows"""
     import _CXX_i8ie as cx
-    from int8inferenceengine_amd import convnext_net as cn
+    import net_cases as nc
+    from int8inferenceengine_amd import workloads as wl
 
-    net = _tiny(False)[0]
-    x = cn.synthetic_input("tiny", 5, seed=INPUT_SEED)
+    net = nc.calibrated(NAME, False, calib_images=8)[0]
+    x = wl.synthetic_input(NAME, 5, seed=sr.INPUT_SEED)
     net(i8ie.tensor(x)).numpy()
     cx.synchronize()
     cx.profile_start()

@@ -35,7 +35,7 @@ def test_the_table_covers_both_registries_and_every_op():
     assert seen == sr.OPS == wl.OPS  # every op of the registry is known to both interpreters, and the replay below runs every known op
     assert seen - {"branch"} == {op[0] for n in names for op in wl._walk(wl.network(n)[1])}
     kinds = {wl.network(n)[0][a][0] for n in names for a in wl.layer_names(n)}
-    assert kinds == {"conv", "deconv", "fc"}
+    assert kinds == {"conv", "deconv", "fc", "ln"} and {"matmul", "softmax", "load"} <= seen and len(seen) == 16
     assert any(wl.conv_dilation(L) > 1 for L in wl.network("aspp_tiny")[0].values())
 
 
@@ -53,7 +53,7 @@ def test_replay_gives_the_recorded_digests(name, per_channel):
 TINY = ({"c": ("conv", 3, 4, 3, 1, 1)}, [("layer", "c"), ("relu",)], (3, 4, 4))
 
 
-@pytest.mark.parametrize("bad", [("shuffle", 2), ("softmax",), ("reshape", 64), ("Flatten", 64)])
+@pytest.mark.parametrize("bad", [("shuffle", 2), ("sigmoid",), ("reshape", 64), ("Flatten", 64)])
 @pytest.mark.parametrize("where", ["top", "branch"])
 def test_an_unknown_op_raises(bad, where):
     layers, spec, shape = TINY

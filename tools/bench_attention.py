@@ -10,7 +10,7 @@ a lower bound.  Softmax: i8ie_softmax_u8 over the scores against i8ie_relu_u8 ov
 library's own per-launch HIP-event bracket (i8ie_profile_start / _stop): `warmup` calls unprofiled, then `rounds` rounds of
 `iters` profiled calls; a round's figure is its mean per call and the reported one the median over rounds.  The aim is parity
 (ratio <= 1); every row records the ratio and MET or MISSED.  The first images of every result are checked against the
-definition (numpy) before the timing.  Then NonLocalNet("cifar")'s step through the Python surface with the share its three
+definition (numpy) before the timing.  Then nonlocal_resnet_cifar's step through the Python surface with the share its three
 attention launches take of the kernel time."""
 import argparse
 import ctypes as C
@@ -175,12 +175,13 @@ def network(args):
     import int8inferenceengine_amd  # noqa: F401
     import _CXX_i8ie as cx
     import i8ie
-    from int8inferenceengine_amd import nonlocal_net as nl
+    from int8inferenceengine_amd import workloads as wl
 
-    net = nl.calibrated("cifar", calib_batch=nl.synthetic_input("cifar", 16, seed=99))
+    name = "nonlocal_resnet_cifar"
+    net = wl.calibrated(name, calib_batch=wl.synthetic_input(name, 16, seed=99))
     rows = []
     for m in BATCHES:
-        x = i8ie.tensor(nl.synthetic_input("cifar", m)).prefetch()
+        x = i8ie.tensor(wl.synthetic_input(name, m)).prefetch()
         for _ in range(args.warmup):
             net(x).numpy()
         walls = []

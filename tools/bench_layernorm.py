@@ -14,7 +14,7 @@ round's figure is its mean per launch, the reported one the median over rounds. 
 same run; a ratio below 0.97 is written MISSED.  The bytes of the first images are asserted against the definition
 (tests/layernorm_ref.py).  This part goes through the C-ABI by ctypes only.
 
-Then the step time of ConvNeXt("cifar") at the same two batch sizes through the Python surface, with the share of the
+Then the step time of convnext_cifar at the same two batch sizes through the Python surface, with the share of the
 profiled kernel time its LayerNorm launches take (`--net-steps 0` skips it)."""
 import argparse
 import ctypes as C
@@ -140,13 +140,13 @@ def network(args):
     import int8inferenceengine_amd  # noqa: F401
     import _CXX_i8ie as cx
     import i8ie
-    from int8inferenceengine_amd import convnext_net as cn
+    from int8inferenceengine_amd import workloads as wl
 
-    name = "cifar"
-    net = cn.calibrated(name)
+    name = "convnext_cifar"
+    net = wl.calibrated(name)
     rows = []
     for m in BATCHES:
-        x = i8ie.tensor(cn.synthetic_input(name, m)).prefetch()
+        x = i8ie.tensor(wl.synthetic_input(name, m)).prefetch()
         for _ in range(args.warmup):
             net(x).numpy()
         cx.synchronize()
@@ -165,7 +165,7 @@ def network(args):
             return sum(v[1] for k, v in prof.items() if k.startswith(prefix))
 
         lut = share("layernorm_u8")
-        rows.append({"network": "ConvNeXt(%s)" % name, "images": m, "step_ms_wall": wall, "kernel_ms_per_step": total / args.net_steps,
+        rows.append({"network": "ConvNeXt(cifar)", "images": m, "step_ms_wall": wall, "kernel_ms_per_step": total / args.net_steps,
                      "layernorm_ms_per_step": lut / args.net_steps, "layernorm_share_of_kernel_time": lut / total,
                      "layernorm_launches_per_step": sum(v[0] for k, v in prof.items() if k.startswith("layernorm_u8")) / args.net_steps,
                      "grouped_conv_share_of_kernel_time": share("gconv") / total,
