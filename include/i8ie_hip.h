@@ -779,6 +779,63 @@ int i8ie_softmax_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int6
  * division per element).  out may alias in. */
 int i8ie_softmax_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int64_t rows, int L);
 
+/* ---- fused multi-head attention (no counterpart in the reference) -----------------------------------------------------
+ * Scaled-dot-product attention over `heads` heads as one op.  q is [b, tq, c], k and v are [b, tk, c], c = heads * d; each
+ * is a u8 tensor with its own (scale, zero_point); head h is columns h*d .. h*d + d - 1.  Nothing new is defined
+ * arithmetically: for every (batch item, head) the result is exactly the composition of the three entries above,
+ *     S   = bmm_u8(Q_h [tq x d], K_h^T [d x tk]; s_q, zp_q, s_k, zp_k -> s_s, zp_s)    no relu; the u8 scores
+ *     P   = softmax_u8(S, s_s) over tk                                                 scale 1/256, zero point 0
+ *     O_h = bmm_u8(P [tq x tk], V_h [tk x d]; 1/256, 0, s_v, zp_v -> s_o, zp_o)        then the optional relu
+ * byte for byte: down_scale's fp32 steps (the second product's requantiser takes (float)(1.0 / 256) as s_a and s_v as s_b,
+ * in this order: its products do not commute), the table E[d] of s_s and min(255, (E * 256 + S / 2) / S).  There is no
+ * alpha, no mask, no bias and no dropout: the 1/sqrt(d) factor folds into the weights of the projection that makes q.
+ * Conditions: b, heads, d, tq >= 1; 1 <= tk <= 32768 (the second product's k); scales finite, s_s > 0 and s_o > 0.
+ * Each operand is described physically (i8ie_attn_mat): element (batch, token, column) lies at
+ * ptr[batch * batch_stride + token * token_stride + column], token_stride >= heads * d, columns contiguous; s8 != 0: the
+ * bytes are stored re-biased (^0x80).  The strides make a packed QKV operand free: one projection c -> 3c gives
+ * [b, t, 3c], and q, k, v are that buffer at byte offsets 0, c, 2c with token stride 3c.  Any two operands may be the
+ * same buffer; `out` must not overlap an operand.  The result is plain [b, tq, c] through out.batch_stride and
+ * out.token_stride (out_h == 0; out_w and out_border must then be 0 too), or the interior of a bordered NHWC map
+ * [b, out_h + 2B, out_w + 2B, .] with B = out_border >= 0 and tq == out_h * out_w: `out.ptr` is then the buffer's first
+ * byte, out.token_stride the stride of one physical pixel (>= c), out.batch_stride that of one image, and token p lies at
+ * physical pixel (p / out_w + B) * (out_w + 2B) + p % out_w + B (i8ie_bmm_args' pixel rule).  Only the c result bytes of a
+ * token are written: border bytes and the gap of a token stride above c are the caller's.  out.s8 != 0 stores re-biased.
+ * Debug outputs, each NULL or: scores_dbg_dev u8 [b, heads, tq, tk] (S), probs_dbg_dev u8 [b, heads, tq, tk] (P),
+ * acc_dbg_dev int32 [b, tq, c] (the second product's accumulators).  scores_out_dev belongs to the FP32 entry and must be
+ * NULL here.  Stateless and capturable in a graph: one launch, no device allocation; the softmax table travels by value in
+ * the kernel arguments.  Every argument error is I8IE_ERR_ARG before any device call.  As in the other stateless entries,
+ * extents and overlap are the caller's responsibility.
+ * Two kernels with identical bytes (csrc/i8ie_attention.hip): attn_mfma (d % 16 == 0, operand
+ * pointers and strides 16-byte aligned, tk <= 1024: scores and probabilities stay in LDS) and attn_direct for everything
+ * else and for everything under I8IE_OPT_FORCE_FALLBACK. */
+typedef struct i8ie_attn_mat {
+  void* ptr;              /* device pointer (read-only for an operand) */
+  int64_t batch_stride;   /* elements between two batch items */
+  int64_t token_stride;   /* ... between two tokens (>= heads * d) */
+  int s8;                 /* != 0: bytes stored re-biased (^0x80) */
+} i8ie_attn_mat;
+typedef struct i8ie_attention_args {
+  int b, heads, d, tq, tk;
+  i8ie_attn_mat q;        /* [b, tq, heads * d] */
+  i8ie_attn_mat k, v;     /* [b, tk, heads * d] */
+  i8ie_attn_mat out;      /* [b, tq, heads * d], plain or the interior of a bordered NHWC map */
+  int out_h, out_w, out_border;   /* out_h == 0: plain */
+  float s_q, s_k, s_v, s_s, s_o;
+  uint8_t zp_q, zp_k, zp_v, zp_s, zp_o;
+  int relu;
+  uint8_t* scores_dbg_dev;   /* NULL or [b, heads, tq, tk] */
+  uint8_t* probs_dbg_dev;    /* NULL or [b, heads, tq, tk] */
+  int32_t* acc_dbg_dev;      /* NULL or [b, tq, heads * d] */
+  float* scores_out_dev;     /* i8ie_attention_f32 only: NULL or float [b, heads, tq, tk] */
+} i8ie_attention_args;
+int i8ie_attention_u8(i8ie_ctx* ctx, const i8ie_attention_args* args);
+/* FP32 (before convert(), and while calibrating): the same descriptor with float elements, strides in floats, a plain
+ * result (every s8, out_h, out_w, out_border, the u8 debug pointers and relu must be 0 / NULL; scales and zero points are
+ * ignored).  Per head it is i8ie_bmm_f32 (Q_h K_h^T), i8ie_softmax_f32, i8ie_bmm_f32 (P V_h), launched through strides
+ * with the scores in the ctx workspace, so it is bit-identical to that composition; scores_out_dev, when given, receives
+ * the scores before the softmax (what the calibrator samples).  The calibration path: 3 * heads launches, not tuned. */
+int i8ie_attention_f32(i8ie_ctx* ctx, const i8ie_attention_args* args);
+
 /* ---- quantized LayerNorm over the last axis (no counterpart in the reference: every op of it is a contraction, a pointwise
  * map or a window reduction; none takes a statistic of a row at run time) ----------------------------------------------------
  * A row is C bytes a[0..C) with (s_in, zp_in), 1 <= C <= 16384; eps is finite and > 0; the result carries (s_out, zp_out);

@@ -29,25 +29,15 @@
 //   bmm_f32     one output per lane, products added in ascending k (off the timed path).
 #include <cmath>
 
+#include "i8ie_bmm_tile.h"
 #include "i8ie_internal.h"
 #include "i8ie_pointwise.h"
 #include "i8ie_requant.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 constexpr int kMaxK = 32768;
-constexpr int TM = 64, TN = 64, TK = 64;  // block tile
-constexpr int LROW = TK + 16;             // LDS bytes per staged row
-
-struct BmmOp {          // an operand as rows x k
-  const uint8_t* p;
-  int64_t batch, rs, ks;  // strides in bytes; rs == 1 or ks == 1
-  uint32_t x;           // 0x80808080 for plain bytes (re-biased while staging), 0 for bytes stored re-biased
-  int vec;              // bytes per load the strides allow along the contiguous axis: 16, 4 or 1
-  int zp;               // plain zero point
-};
+// (the block tile TM, TN, TK, LROW, the operand BmmOp and stage_tile live in i8ie_bmm_tile.h: attn_mfma stages with them too)
 struct BmmParams {
   BmmOp A, B;           // rows of A are the result's rows, rows of B its columns
   int M, N, K, tiles_m, tiles_n;
@@ -63,57 +53,6 @@ struct BmmParams {
 
 __device__ __forceinline__ int64_t out_row_index(const BmmParams& p, int i) {
   return p.pix_pad ? (int64_t)i + (int64_t)(i / p.pix_w) * p.pix_pad : (int64_t)i;
-}
-
-// one 64 x 64 tile of `op` (rows row0.., k k0..) into lds[64][LROW], re-biased, zero-filled outside the operand
-__device__ __forceinline__ void stage_tile(const BmmOp& op, const uint8_t* base, int rows, int K, int row0, int k0, uint8_t* lds) {
-  const int t = threadIdx.x;
-  const uint32_t x8 = op.x & 0xFFu;
-  if (op.ks == 1) {  // K-contiguous: a lane moves 16 consecutive k of one row
-    const int r = t >> 2, kc = (t & 3) * 16;
-    const int gr = row0 + r, gk = k0 + kc;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    if (gr < rows && gk < K) {
-      const uint8_t* src = base + (int64_t)gr * op.rs + gk;
-      if (gk + 16 <= K && op.vec == 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(src);
-        w[0] = v.x ^ op.x; w[1] = v.y ^ op.x; w[2] = v.z ^ op.x; w[3] = v.w ^ op.x;
-      } else if (gk + 16 <= K && op.vec == 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = *reinterpret_cast<const uint32_t*>(src + 4 * i) ^ op.x;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          if (gk + i < K) w[i >> 2] |= ((uint32_t)src[i] ^ x8) << (8 * (i & 3));
-      }
-    }
-    *reinterpret_cast<uint4*>(lds + r * LROW + kc) = make_uint4(w[0], w[1], w[2], w[3]);
-  } else {  // K-strided (rows contiguous): a lane moves 4 rows x 4 k and transposes them in registers
-    const int rb = (t & 15) * 4, kb = (t >> 4) * 4;
-    const int gr = row0 + rb;
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int gk = k0 + kb + i;
-      w[i] = 0u;
-      if (gk < K && gr < rows) {
-        const uint8_t* src = base + (int64_t)gk * op.ks + gr;
-        if (gr + 4 <= rows && op.vec >= 4) {
-          w[i] = *reinterpret_cast<const uint32_t*>(src) ^ op.x;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (gr + j < rows) w[i] |= ((uint32_t)src[j] ^ x8) << (8 * j);
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t o = ((w[0] >> (8 * j)) & 0xFFu) | (((w[1] >> (8 * j)) & 0xFFu) << 8) | (((w[2] >> (8 * j)) & 0xFFu) << 16) |
-                         (((w[3] >> (8 * j)) & 0xFFu) << 24);
-      *reinterpret_cast<uint32_t*>(lds + (rb + j) * LROW + kb) = o;
-    }
-  }
 }
 
 __global__ __launch_bounds__(256) void bmm_mfma_kernel(BmmParams p) {

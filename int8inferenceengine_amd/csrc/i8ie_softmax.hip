@@ -22,37 +22,14 @@
 
 #include "i8ie_internal.h"
 #include "i8ie_pointwise.h"
+#include "i8ie_softmax_dev.h"
 
 namespace {
 
 constexpr int kWaveMaxL = 1024;  // 64 lanes x 16 values
 constexpr int kMaxL = 65535;
 
-struct SoftmaxTable {
-  uint32_t e[256];
-};
-
-__device__ __forceinline__ uint32_t div_by(uint32_t x, uint32_t S, float rinv) {
-  uint32_t q = (uint32_t)((float)x * rinv);
-  const int64_t r = (int64_t)x - (int64_t)((uint64_t)q * (uint64_t)S);
-  q += (r >= (int64_t)S) ? 1u : 0u;
-  q -= (r < 0) ? 1u : 0u;
-  return q > 255u ? 255u : q;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = (uint32_t)__shfl_xor((int)v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-  return v;
-}
+// (SoftmaxTable, div_by, wave_max and wave_sum live in i8ie_softmax_dev.h: the fused attention kernel uses them too)
 
 // VEC = 4: item i of lane l is bytes 4 (l + 64 i) .. + 3 of the row, i < 4 (rows start 4-byte aligned: L % 4 == 0 and aligned
 // buffers).  VEC = 1: item i is byte l + 64 i, i < 16.

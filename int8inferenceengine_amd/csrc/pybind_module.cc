@@ -1040,6 +1040,174 @@ Tensor<u8_t> softmax_u8(Tensor<u8_t>& x) {
   check(i8ie_softmax_u8(ctx(), src, out.dptr(), (int64_t)(x.size / x.shape.back()), (int)x.shape.back(), x.scale));
   return out;
 }
+// ---- attention (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_attention_u8) -----------------------
+// Operands are rank 3 [b, t, c], or rank 4 [n, c, h, w] counted as [n, h * w, c] (the engine's NHWC storage as it lies).  q is
+// [b, tq, c], k and v are [b, tk, c], c = heads * d; or one packed tensor with 3 * heads * d channels (k == v == nullptr): q, k, v
+// are then its channels [0, c), [c, 2c), [2c, 3c).  The result has q's rank: [b, tq, c] or [n, c, h, w].  Anything else is a
+// RuntimeError (before any device call).
+struct AttnShape {
+  ssize_t b = 0, heads = 0, d = 0, c = 0, tq = 0, tk = 0;
+  bool packed = false;
+  std::vector<ssize_t> out;
+};
+template <typename T>
+AttnShape attention_shape(const Tensor<T>& q, const Tensor<T>* k, const Tensor<T>* v, ssize_t heads) {
+  auto btc = [](const Tensor<T>& t, const char* which) {
+    if (t.shape.size() != 3 && t.shape.size() != 4)
+      throw std::runtime_error(std::string("i8ie: attention: ") + which + " must be [b, t, c] or [n, c, h, w]");
+    for (ssize_t d : t.shape)
+      if (d <= 0) throw std::runtime_error("i8ie: attention: empty tensor");
+    if (t.shape.size() == 4) return std::array<ssize_t, 3>{t.shape[0], t.shape[2] * t.shape[3], t.shape[1]};
+    return std::array<ssize_t, 3>{t.shape[0], t.shape[1], t.shape[2]};
+  };
+  if ((k == nullptr) != (v == nullptr)) throw std::runtime_error("i8ie: attention takes q, k and v, or one packed qkv tensor");
+  if (heads < 1) throw std::runtime_error("i8ie: attention: heads must be >= 1");
+  AttnShape s;
+  s.heads = heads;
+  s.packed = k == nullptr;
+  const auto Q = btc(q, s.packed ? "qkv" : "q");
+  s.b = Q[0];
+  s.tq = s.tk = Q[1];
+  if (s.packed) {
+    if (Q[2] % (3 * heads) != 0) throw std::runtime_error("i8ie: attention: a packed qkv tensor needs 3 * heads * d channels");
+    s.c = Q[2] / 3;
+  } else {
+    const auto K = btc(*k, "k"), V = btc(*v, "v");
+    if (K[0] != s.b || V[0] != s.b) throw std::runtime_error("i8ie: attention: the operands' batch sizes differ (there is no broadcasting)");
+    if (K[2] != Q[2] || V[2] != Q[2]) throw std::runtime_error("i8ie: attention: q, k and v must have the same channel count");
+    if (K[1] != V[1]) throw std::runtime_error("i8ie: attention: k and v must have the same token count");
+    if (Q[2] % heads != 0) throw std::runtime_error("i8ie: attention: the channel count is not heads * d");
+    s.c = Q[2];
+    s.tk = K[1];
+  }
+  s.d = s.c / heads;
+  if (s.tk > 32768) throw std::runtime_error("i8ie: attention: more than 32768 key tokens");
+  if (q.shape.size() == 4) s.out = {s.b, s.c, q.shape[2], q.shape[3]};
+  else s.out = {s.b, s.tq, s.c};
+  return s;
+}
+// FP32: the composition i8ie_bmm_f32, i8ie_softmax_f32, i8ie_bmm_f32 per head.  Rank-3 operands go through
+// i8ie_attention_f32; an FP32 rank-4 tensor is NCHW, its token matrix has the token stride 1, so the same three entries are
+// driven through strides here (the bits are the same: i8ie_bmm_f32 adds in ascending k whatever the strides are).  `scores`:
+// null, or a [b, heads, tq, tk] tensor that receives the scores before the softmax (what the calibrator samples).
+Tensor<float> attention_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads, Tensor<float>* scores) {
+  const AttnShape s = attention_shape(q, k, v, heads);
+  Tensor<float> out(s.out);
+  Tensor<float>* ts[3] = {&q, s.packed ? &q : k, s.packed ? &q : v};
+  const ssize_t C = s.packed ? 3 * s.c : s.c;
+  const bool flat = q.shape.size() == 3 && ts[1]->shape.size() == 3 && ts[2]->shape.size() == 3;
+  if (flat) {
+    i8ie_attention_args g{};
+    g.b = (int)s.b; g.heads = (int)s.heads; g.d = (int)s.d; g.tq = (int)s.tq; g.tk = (int)s.tk;
+    i8ie_attn_mat* ms[3] = {&g.q, &g.k, &g.v};
+    for (int i = 0; i < 3; ++i) {
+      const ssize_t t = i == 0 ? s.tq : s.tk;
+      *ms[i] = i8ie_attn_mat{ts[i]->dptr() + (s.packed ? i * s.c : 0), (int64_t)t * C, (int64_t)C, 0};
+    }
+    g.out = i8ie_attn_mat{out.dptr(), (int64_t)s.tq * s.c, (int64_t)s.c, 0};
+    g.scores_out_dev = scores ? scores->dptr() : nullptr;
+    check(i8ie_attention_f32(ctx(), &g));
+    return out;
+  }
+  // element (batch, token, column) of a tensor with `ch` channels, channel offset `off`: [b, t, ch] or NCHW [b, ch, t]
+  auto mat = [](Tensor<float>& t, ssize_t tokens, ssize_t ch, ssize_t off, bool tokens_are_rows) {
+    const bool nchw = t.shape.size() == 4;
+    i8ie_bmm_mat m;
+    m.ptr = t.dptr() + (nchw ? off * tokens : off);
+    m.batch_stride = (int64_t)tokens * ch;
+    const int64_t tok = nchw ? 1 : (int64_t)ch, col = nchw ? (int64_t)tokens : 1;
+    m.row_stride = tokens_are_rows ? tok : col;
+    m.col_stride = tokens_are_rows ? col : tok;
+    m.s8 = 0;
+    return m;
+  };
+  const ssize_t per_head = s.tq * s.tk;
+  Tensor<float> ws({s.b, s.tq, s.tk});
+  for (ssize_t h = 0; h < s.heads; ++h) {
+    i8ie_bmm_args a{};
+    a.b = (int)s.b; a.m = (int)s.tq; a.n = (int)s.tk; a.k = (int)s.d;
+    a.a = mat(*ts[0], s.tq, C, h * s.d, true);
+    a.bm = mat(*ts[1], s.tk, C, (s.packed ? s.c : 0) + h * s.d, false);
+    a.out = i8ie_bmm_mat{ws.dptr(), (int64_t)per_head, (int64_t)s.tk, 1, 0};
+    check(i8ie_bmm_f32(ctx(), &a));
+    if (scores) {
+      a.out = i8ie_bmm_mat{scores->dptr() + h * per_head, (int64_t)(s.heads * per_head), (int64_t)s.tk, 1, 0};
+      check(i8ie_bmm_f32(ctx(), &a));
+    }
+    check(i8ie_softmax_f32(ctx(), ws.dptr(), ws.dptr(), (int64_t)(s.b * s.tq), (int)s.tk));
+    i8ie_bmm_args o{};
+    o.b = (int)s.b; o.m = (int)s.tq; o.n = (int)s.d; o.k = (int)s.tk;
+    o.a = i8ie_bmm_mat{ws.dptr(), (int64_t)per_head, (int64_t)s.tk, 1, 0};
+    o.bm = mat(*ts[2], s.tk, C, (s.packed ? 2 * s.c : 0) + h * s.d, true);
+    o.out = mat(out, s.tq, s.c, h * s.d, true);
+    check(i8ie_bmm_f32(ctx(), &o));
+  }
+  return out;
+}
+// A u8 operand as it lies.  A rank-4 tensor stored NHWC without a border is physically [n, t, ch]: read in place, re-biased or
+// not.  One that exists with a border, a view under other logical dims and an NCHW tensor take a layout conversion into a
+// border-free NHWC buffer (`copies` keeps a temporary alive); a rank-3 tensor is read in the reference's order.
+i8ie_attn_mat attn_operand(std::shared_ptr<Storage> s, const std::vector<ssize_t>& shp, ssize_t tokens, ssize_t ch, ssize_t off,
+                           NhwcCopies& copies) {
+  i8ie_attn_mat m{};
+  if (shp.size() == 4) {
+    if (s->layout == I8IE_LAYOUT_NHWC && s->border != 0) s->to_nchw();
+    s = as_engine_nhwc(s, shp, copies);
+    m.s8 = s->s8 ? 1 : 0;
+  } else {
+    s->to_nchw();
+  }
+  m.ptr = (uint8_t*)s->device_ptr() + off;
+  m.batch_stride = (int64_t)tokens * ch;
+  m.token_stride = (int64_t)ch;
+  return m;
+}
+Tensor<u8_t> attention_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, float s_s, int zp_s, float scale, int zp) {
+  const AttnShape s = attention_shape(q, k, v, heads);
+  check_out_qparams("attention", scale, zp);
+  check_out_qparams("attention (scores)", s_s, zp_s);
+  std::vector<Tensor<u8_t>> ops{q};  // share the operands' storage / pending launches
+  if (!s.packed) {
+    ops.push_back(*k);
+    ops.push_back(*v);
+  }
+  for (const auto& t : ops) {
+    if (!std::isfinite(t.scale)) throw std::runtime_error("i8ie: attention: an operand's scale is not finite");
+    if (!t.st && !t.pend) throw std::runtime_error("i8ie: empty tensor");
+  }
+  Tensor<u8_t> out = pending_u8(s.out, scale, (u8_t)zp);
+  const u8_t zp_o = (u8_t)zp, zs = (u8_t)zp_s;
+  // deferred like matmul's result: relu(attention(..)) is one launch, and a rank-4 result gets the border and re-bias the next
+  // conv asks for straight from the kernel.  The operands' producers are asked for border 0 (operand_as_it_lies).
+  auto run = [ops, s, s_s, zs, scale, zp_o](bool relu, int border, bool s8) mutable {
+    auto ss = resolve_operands(ops.data(), ops.size());
+    NhwcCopies copies;
+    i8ie_attention_args g{};
+    g.b = (int)s.b; g.heads = (int)s.heads; g.d = (int)s.d; g.tq = (int)s.tq; g.tk = (int)s.tk;
+    const ssize_t C = s.packed ? 3 * s.c : s.c;
+    const Tensor<u8_t>&tq = ops[0], &tk = ops[s.packed ? 0 : 1], &tv = ops[s.packed ? 0 : 2];
+    g.q = attn_operand(ss[0], tq.shape, s.tq, C, 0, copies);
+    g.k = attn_operand(ss[s.packed ? 0 : 1], tk.shape, s.tk, C, s.packed ? s.c : 0, copies);
+    g.v = attn_operand(ss[s.packed ? 0 : 2], tv.shape, s.tk, C, s.packed ? 2 * s.c : 0, copies);
+    g.s_q = tq.scale; g.s_k = tk.scale; g.s_v = tv.scale; g.s_s = s_s; g.s_o = scale;
+    g.zp_q = tq.zero_point; g.zp_k = tk.zero_point; g.zp_v = tv.zero_point; g.zp_s = zs; g.zp_o = zp_o;
+    g.relu = relu ? 1 : 0;
+    std::shared_ptr<Storage> st;
+    if (s.out.size() == 4) {  // NHWC [b, h + 2B, w + 2B, c]: the tq tokens are the pixels
+      st = nhwc_storage(s.out, border, zp_o, s8);
+      g.out = i8ie_attn_mat{st->dev, (int64_t)s.c * (s.out[2] + 2 * st->border) * (s.out[3] + 2 * st->border), (int64_t)s.c, st->s8 ? 1 : 0};
+      g.out_h = (int)s.out[2]; g.out_w = (int)s.out[3]; g.out_border = st->border;
+    } else {
+      st = device_storage((size_t)(s.b * s.tq * s.c));
+      g.out = i8ie_attn_mat{st->dev, (int64_t)s.tq * s.c, (int64_t)s.c, 0};
+    }
+    check(i8ie_attention_u8(ctx(), &g));
+    return st;
+  };
+  if (s.packed) out.pend = make_pend(run, {q.pend});
+  else out.pend = make_pend(run, {q.pend, k->pend, v->pend});
+  return out;
+}
 // ---- layer_norm (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_layernorm_u8) ---------------------
 // [n, c, h, w] is normalised over c per pixel, [m, f] and [b, t, f] over the last axis: (rows, inner) of the FP32 entry, or
 // a RuntimeError (before any device call)
@@ -2132,6 +2300,67 @@ class MatMul : public Weightless {
  private:
   bool ta_, tb_;
 };
+// multi-head attention of q, k, v (or one packed qkv tensor; attention_shape's rules): two calibrated parameter sets, the
+// scores' (scale, zero_point) beside the output's.  While preparing, the FP32 scores are sampled by a calibrator of their own.
+class Attention : public Weightless {
+ public:
+  explicit Attention(ssize_t heads) : heads_(heads) {
+    if (heads < 1) throw std::runtime_error("i8ie: Attention: heads must be >= 1");
+  }
+  void prepare() {
+    if (!is_quantized_) score_cal_ = std::make_unique<Calibrator>();
+    QuantState::prepare();
+  }
+  void convert(bool /*per_channel: there are no weights*/ = false) {
+    if (!is_quantized_ && is_preparing_ && score_cal_ && score_cal_->cnt > 0) {
+      float s;
+      u8_t z;
+      std::tie(s, z) = score_cal_->get_range(1);
+      if (!score_overridden_) {
+        score_scale_ = s;
+        score_zp_ = z;
+      }
+    }
+    score_cal_.reset();
+    Weightless::convert();
+  }
+  void set_score_qparams(float s, int zp) {  // inject what calibration would produce
+    check_zero_point(zp);
+    score_scale_ = s;
+    score_zp_ = (u8_t)zp;
+    score_overridden_ = true;
+  }
+  std::tuple<float, int> score_qparams() const { return std::make_tuple(score_scale_, (int)score_zp_); }
+  void load_quantized(float s_out, int zp_out, float s_score, int zp_score) {  // what convert() would have left behind
+    set_score_qparams(s_score, zp_score);
+    Weightless::load_quantized(s_out, zp_out);
+  }
+  Tensor<float> forward_f32(Tensor<float>& q, Tensor<float>& k, Tensor<float>& v) { return run_f32(q, &k, &v); }
+  Tensor<float> forward_f32_packed(Tensor<float>& qkv) { return run_f32(qkv, nullptr, nullptr); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& q, Tensor<u8_t>& k, Tensor<u8_t>& v) { return run_u8(q, &k, &v); }
+  Tensor<u8_t> forward_u8_packed(Tensor<u8_t>& qkv) { return run_u8(qkv, nullptr, nullptr); }
+  ssize_t heads() const { return heads_; }
+
+ private:
+  Tensor<float> run_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v) {
+    if (!is_preparing_ || !score_cal_) return attention_f32(q, k, v, heads_, nullptr);
+    const AttnShape s = attention_shape(q, k, v, heads_);
+    Tensor<float> scores(std::vector<ssize_t>{s.b, s.heads, s.tq, s.tk});
+    Tensor<float> out = attention_f32(q, k, v, heads_, &scores);
+    calib_sample(*score_cal_, scores);
+    return sampled(out);
+  }
+  Tensor<u8_t> run_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v) {
+    attention_shape(q, k, v, heads_);
+    need_quantized("Attention");
+    return attention_u8(q, k, v, heads_, score_scale_, score_zp_, scale_, zero_point_);
+  }
+  ssize_t heads_;
+  std::unique_ptr<Calibrator> score_cal_;
+  float score_scale_ = 1;
+  u8_t score_zp_ = 0;
+  bool score_overridden_ = false;
+};
 // cat along axis 1: a list of FP32 tensors before convert(), of u8 tensors after it
 class Concat : public Weightless {
  public:
@@ -2315,6 +2544,11 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
         py::arg("transpose_b") = false);
   m.def("softmax", &softmax_f32, py::arg("x"));
   m.def("softmax", &softmax_u8, py::arg("x"));
+  // additive: fused multi-head attention (include/i8ie_hip.h, i8ie_attention_u8); k and v None: q is a packed qkv tensor
+  m.def("attention", [](Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads) { return attention_f32(q, k, v, heads, nullptr); },
+        py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"));
+  m.def("attention", &attention_u8, py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"),
+        py::arg("score_scale"), py::arg("score_zero_point"), py::arg("scale"), py::arg("zero_point"));
   // additive: LayerNorm over the channel axis of [n, c, h, w] or the last axis of [m, f] / [b, t, f] (include/i8ie_hip.h,
   // i8ie_layernorm_u8); weight / bias: float32 [channels] or None (ones / zeros); uploaded per call
   m.def("layer_norm", [](Tensor<float>& x, const py::object& w, const py::object& b, float eps) {
@@ -2402,6 +2636,22 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
     bind_weightless_state(c);
     c.def("__call__", &MatMul::forward_f32).def("__call__", &MatMul::forward_u8)
         .def("transpose_a", &MatMul::transpose_a).def("transpose_b", &MatMul::transpose_b);
+  }
+  {
+    py::class_<Attention> c(m, "Attention");
+    c.def(py::init<ssize_t>(), py::arg("heads"))
+        .def("prepare", &Attention::prepare)
+        .def("convert", &Attention::convert, py::arg("per_channel") = false)
+        .def("set_output_qparams", &Attention::set_output_qparams, py::arg("scale"), py::arg("zero_point"))
+        .def("output_qparams", &Attention::output_qparams)
+        .def("set_score_qparams", &Attention::set_score_qparams, py::arg("scale"), py::arg("zero_point"))
+        .def("score_qparams", &Attention::score_qparams)
+        .def("load_quantized", &Attention::load_quantized, py::arg("out_scale"), py::arg("out_zero_point"), py::arg("score_scale"),
+             py::arg("score_zero_point"))
+        .def("is_quantized", &Attention::is_quantized)
+        .def("heads", &Attention::heads)
+        .def("__call__", &Attention::forward_f32).def("__call__", &Attention::forward_f32_packed)
+        .def("__call__", &Attention::forward_u8).def("__call__", &Attention::forward_u8_packed);
   }
   {
     py::class_<Concat> c(m, "Concat");

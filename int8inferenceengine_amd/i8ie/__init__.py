@@ -9,7 +9,7 @@ import numbers
 
 import _CXX_i8ie as _C
 
-from .layer import Activation, Add, Concat, Conv2d, ConvTranspose2d, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind
+from .layer import Activation, Add, Attention, Concat, Conv2d, ConvTranspose2d, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind
 from .module import Module
 from .tensor import Tensor
 
@@ -19,7 +19,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
-    "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm",
+    "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "Attention", "attention",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -104,6 +104,29 @@ def softmax(x):
     tensor in reference order; an input that is not in reference order (an NHWC activation between layers) is converted
     first."""
     return Tensor(_C.softmax(x.data))
+
+
+def attention(q, k=None, v=None, heads=1, score_scale=None, score_zero_point=None, scale=None, zero_point=None):
+    """Multi-head scaled-dot-product attention as one op.  Operands are rank 3 [b, t, c], or rank 4 [n, c, h, w] counted as
+    [n, h * w, c] (the engine's NHWC storage as it lies); `q` is [b, tq, c], `k` and `v` are [b, tk, c] (tq != tk is allowed),
+    c = heads * d, head h is channels h * d .. h * d + d - 1.  `k = v = None`: `q` is a packed qkv tensor with 3 * heads * d
+    channels (q, k, v are its thirds, in this order).  The result has q's rank: [b, tq, c], or [n, heads * d, h, w].  Anything
+    else raises RuntimeError.  There is no alpha, mask, bias or dropout: fold the 1/sqrt(d) factor into the weights of the
+    projection that makes q.  FP32 tensors: matmul, softmax, matmul per head in FP32; no quantisation parameter may be given.
+    uint8 tensors: per head exactly matmul (-> `score_scale`, `score_zero_point`), softmax, matmul (-> `scale`, `zero_point`)
+    of include/i8ie_hip.h, in one launch (i8ie_attention_u8); all four parameters are required.  `i8ie.Attention` is the
+    calibrated form for use inside a Module."""
+    if (k is None) != (v is None):
+        raise TypeError("attention takes q, k and v, or one packed qkv tensor")
+    kd, vd = (None, None) if k is None else (k.data, v.data)
+    params = (score_scale, score_zero_point, scale, zero_point)
+    if type(q.data).__name__ == "6TensorIhE":
+        if any(p is None for p in params):
+            raise TypeError("attention of uint8 tensors needs score_scale, score_zero_point, scale and zero_point")
+        return Tensor(_C.attention(q.data, kd, vd, int(heads), float(score_scale), int(score_zero_point), float(scale), int(zero_point)))
+    if any(p is not None for p in params):
+        raise TypeError("attention of FP32 tensors takes no quantisation parameters")
+    return Tensor(_C.attention(q.data, kd, vd, int(heads)))
 
 
 def layer_norm(x, weight=None, bias=None, eps=1e-5, scale=None, zero_point=None):

@@ -183,6 +183,37 @@ class MatMul(Weightless):
         return Tensor(self.layer(a.data, b.data))
 
 
+class Attention(Weightless):
+    """Quantized multi-head attention `y = self.attn(q, k, v)` or, packed, `y = self.attn(qkv)` (additive, not in the
+    reference): a layer without weights and with two calibrated parameter sets, the scores' and the output's.
+
+    Operands are rank 3 [b, t, c], or rank 4 [n, c, h, w] counted as [n, h * w, c]; q is [b, tq, c], k and v are [b, tk, c],
+    c = heads * d.  In the packed form the tensor has 3 * heads * d channels (q, k, v are its thirds, as one 1x1 conv or Linear
+    c -> 3c makes them) and all three operands share its scale and zero point.  The result has q's rank.  Anything else raises
+    RuntimeError.  There is no alpha, mask, bias or dropout: the 1/sqrt(d) factor folds into the weights of the projection
+    that makes q.  FP32 tensors go through matmul, softmax, matmul per head in FP32; while preparing, the calibrator samples
+    the FP32 scores and the FP32 result, and convert() fixes score_qparams() and output_qparams().  uint8 tensors, after
+    convert(), take one launch (include/i8ie_hip.h, i8ie_attention_u8): per head exactly i8ie_bmm_u8, i8ie_softmax_u8,
+    i8ie_bmm_u8.  quantized_state_dict() writes `<attr>.qparams` and `<attr>.score_qparams` = (scale, zero_point)."""
+
+    def __init__(self, heads):
+        self.heads = int(heads)
+        self.layer = _C.Attention(self.heads)
+
+    def __call__(self, q, k=None, v=None):
+        if (k is None) != (v is None):
+            raise TypeError("Attention takes q, k and v, or one packed qkv tensor")
+        if k is None:
+            return Tensor(self.layer(q.data))
+        return Tensor(self.layer(q.data, k.data, v.data))
+
+    def score_qparams(self):
+        return self.layer.score_qparams()
+
+    def set_score_qparams(self, scale, zero_point):
+        self.layer.set_score_qparams(float(scale), int(zero_point))
+
+
 class Concat(Weightless):
     """Quantized channel concatenation `y = self.cat1([a, b, ...])` (additive, not in the reference): a layer without weights.
 

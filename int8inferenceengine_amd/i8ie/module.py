@@ -1,7 +1,7 @@
 """Module base class (reference i8ie/module.py:6-35)."""
 import _CXX_i8ie as _C
 
-from .layer import Layer, LayerNorm, Weightless
+from .layer import Attention, Layer, LayerNorm, Weightless
 from .tensor import Tensor
 
 # Hard-coded input quantisation of the reference (i8ie/module.py:20).
@@ -52,7 +52,8 @@ class Module:
         """{'<attr>.q_weight' int8, '<attr>.q_bias' int8, '<attr>.qparams' float64[3] =
         (weight_scale, out_scale, out_zero_point)} for every converted layer; a per-channel layer also has
         '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused).  An Add, a Mul, a Concat or an Activation contributes only
-        '<attr>.qparams' = (0, out_scale, out_zero_point); a LayerNorm that and '<attr>.weight', '<attr>.bias' as float32."""
+        '<attr>.qparams' = (0, out_scale, out_zero_point), an Attention that and '<attr>.score_qparams' float64[2] = (scale, zero_point);
+        a LayerNorm '<attr>.qparams' and '<attr>.weight', '<attr>.bias' as float32."""
         import numpy as np
 
         out = {}
@@ -61,6 +62,10 @@ class Module:
             if not L.is_quantized():
                 raise RuntimeError("layer %r is not converted" % name)
             s_out, zp_out = L.output_qparams()
+            if isinstance(layer, Attention):
+                out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
+                out[name + ".score_qparams"] = np.array(L.score_qparams(), np.float64)
+                continue
             if isinstance(layer, Weightless):
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
                 continue
@@ -84,6 +89,10 @@ class Module:
 
         for name, layer in self._layers():
             w_scale, s_out, zp_out = (float(v) for v in state[name + ".qparams"])
+            if isinstance(layer, Attention):
+                s_s, zp_s = (float(v) for v in state[name + ".score_qparams"])
+                layer.layer.load_quantized(float(np.float32(s_out)), int(zp_out), float(np.float32(s_s)), int(zp_s))
+                continue
             if isinstance(layer, Weightless):
                 layer.layer.load_quantized(float(np.float32(s_out)), int(zp_out))
                 continue

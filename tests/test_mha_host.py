@@ -1,0 +1,209 @@
+"""CPU-side checks of the fused multi-head attention: the header and the library carry the entries, the Python surface its
+names; every argument error is I8IE_ERR_ARG before any device call; tests/mha_ref.py is the composition of
+tests/attention_ref.py; a Module saves and restores an Attention's two parameter sets.  No GPU."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import abi
+import attention_ref as ar
+import mha_ref as mr
+
+f32 = np.float32
+QP = dict(s_q=f32(0.05), zp_q=120, s_k=f32(0.04), zp_k=131, s_v=f32(0.03), zp_v=7, s_s=f32(0.35), zp_s=140, s_o=f32(0.02), zp_o=9)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return mr.bind(abi.lib())
+
+
+def test_header_declares_and_library_exports_the_entries(lib):
+    names = abi.declared_symbols()
+    for n in ("i8ie_attention_u8", "i8ie_attention_f32"):
+        assert n in names and hasattr(lib, n)
+    src = open(abi.HEADER).read()
+    assert "typedef struct i8ie_attention_args" in src and "typedef struct i8ie_attn_mat" in src
+
+
+def _good():
+    # b = 2, H = 2, d = 4, tq = 6, tk = 5; the pointers are never dereferenced
+    return mr.AttnArgs(b=2, heads=2, d=4, tq=6, tk=5, q=mr.mat(4096, 6, 8), k=mr.mat(8192, 5, 8), v=mr.mat(12288, 5, 8),
+                       out=mr.mat(16384, 6, 8), s_q=1.0, s_k=1.0, s_v=1.0, s_s=1.0, s_o=1.0)
+
+
+def test_argument_errors_need_no_gpu(lib):
+    """every argument error is I8IE_ERR_ARG before any device call (the ctx is never dereferenced)"""
+    g = _good()
+    assert lib.i8ie_attention_u8(None, C.byref(g)) == -1 and lib.i8ie_attention_f32(None, C.byref(g)) == -1
+    fake_ctx = C.create_string_buffer(512)  # (never read: each call below fails its argument check first)
+    assert lib.i8ie_attention_u8(fake_ctx, None) == -1
+    bad = [("tk", mr.MAX_TK + 1), ("tk", 0), ("tq", 0), ("d", 0), ("heads", 0), ("b", 0), ("s_s", 0.0), ("s_s", -1.0), ("s_o", 0.0),
+           ("s_o", float("nan")), ("s_q", float("inf")), ("s_k", float("nan")), ("s_v", float("inf")), ("scores_out_dev", 4096),
+           ("out_w", 3), ("out_border", 1)]
+    for field, value in bad:
+        h = mr.AttnArgs.from_buffer_copy(g)
+        setattr(h, field, value)
+        assert lib.i8ie_attention_u8(fake_ctx, C.byref(h)) == -1, field
+        assert b"i8ie_attention_u8" in abi.lib().i8ie_last_error() or b"check_sizes" in abi.lib().i8ie_last_error()
+    for which in ("q", "k", "v", "out"):
+        h = mr.AttnArgs.from_buffer_copy(g)
+        getattr(h, which).token_stride = 7           # below heads * d = 8
+        assert lib.i8ie_attention_u8(fake_ctx, C.byref(h)) == -1, which
+        assert lib.i8ie_attention_f32(fake_ctx, C.byref(h)) == -1, which
+        h = mr.AttnArgs.from_buffer_copy(g)
+        getattr(h, which).ptr = None
+        assert lib.i8ie_attention_u8(fake_ctx, C.byref(h)) == -1, which
+        h = mr.AttnArgs.from_buffer_copy(g)
+        getattr(h, which).batch_stride = -1
+        assert lib.i8ie_attention_u8(fake_ctx, C.byref(h)) == -1, which
+    h = mr.AttnArgs.from_buffer_copy(g)
+    h.out_h, h.out_w, h.out_border = 2, 2, 1         # tq = 6 != 2 * 2: the pixel mismatch
+    assert lib.i8ie_attention_u8(fake_ctx, C.byref(h)) == -1
+    h.out_h, h.out_w, h.out_border = 2, 3, -1
+    assert lib.i8ie_attention_u8(fake_ctx, C.byref(h)) == -1
+    # the FP32 entry refuses every INT8-only field
+    for field, value in (("relu", 1), ("out_h", 2), ("scores_dbg_dev", 4096), ("probs_dbg_dev", 4096), ("acc_dbg_dev", 4096),
+                         ("tk", mr.MAX_TK + 1)):
+        h = mr.AttnArgs.from_buffer_copy(g)
+        setattr(h, field, value)
+        assert lib.i8ie_attention_f32(fake_ctx, C.byref(h)) == -1, field
+    h = mr.AttnArgs.from_buffer_copy(g)
+    h.k.s8 = 1
+    assert lib.i8ie_attention_f32(fake_ctx, C.byref(h)) == -1
+
+
+@pytest.fixture(scope="module")
+def i8ie():
+    import int8inferenceengine_amd  # noqa: F401
+    import i8ie as mod
+
+    return mod
+
+
+def test_surface_names(i8ie):
+    import _CXX_i8ie as cx
+
+    for n in ("Attention", "attention"):
+        assert n in i8ie.__all__ and hasattr(i8ie, n) and hasattr(cx, n)
+    at = i8ie.Attention(4)
+    assert isinstance(at, i8ie.layer.Weightless) and at.heads == 4 and at.layer.heads() == 4
+    assert at.output_qparams() == (1.0, 0) and at.score_qparams() == (1.0, 0) and not at.layer.is_quantized()
+    at.set_score_qparams(0.25, 130)
+    at.set_output_qparams(0.5, 3)
+    assert at.score_qparams() == (0.25, 130) and at.output_qparams() == (0.5, 3)
+    for bad in (256, -1):
+        with pytest.raises(RuntimeError):
+            at.set_score_qparams(0.1, bad)
+    with pytest.raises(RuntimeError):
+        i8ie.Attention(0)
+    with pytest.raises(RuntimeError):
+        at.load_weight(np.zeros(1, f32))
+    assert "1/sqrt(d)" in i8ie.Attention.__doc__ and "1/sqrt(d)" in i8ie.attention.__doc__
+
+
+def test_shape_and_type_errors_come_before_any_device_call(i8ie):
+    """RuntimeError from the shape rules, TypeError from the Python-level argument rules; FP32 tensors made on the host never
+    reach a device here"""
+    t = lambda *shape: i8ie.tensor(np.zeros(shape, f32))
+    at = i8ie.Attention(2)
+    cases = [lambda: at(t(1, 4, 7)),                          # packed: 7 channels are not 3 * 2 * d
+             lambda: at(t(1, 4, 9)),                          # ... nor are 9
+             lambda: at(t(1, 4, 6), t(1, 4, 6), t(1, 5, 6)),  # k and v differ in tokens
+             lambda: at(t(1, 4, 6), t(2, 4, 6), t(2, 4, 6)),  # batch
+             lambda: at(t(1, 4, 6), t(1, 4, 8), t(1, 4, 8)),  # channels differ
+             lambda: at(t(1, 4, 5), t(1, 4, 5), t(1, 4, 5)),  # c != heads * d
+             lambda: at(t(4, 6), t(4, 6), t(4, 6)),           # rank 2
+             lambda: i8ie.attention(t(1, 4, 6), t(1, 4, 6), t(1, 4, 6), heads=0),
+             lambda: i8ie.attention(t(1, 1, 4), t(1, mr.MAX_TK + 1, 4), t(1, mr.MAX_TK + 1, 4), heads=1)]
+    for bad in cases:
+        with pytest.raises(RuntimeError):
+            bad()
+    for bad in (lambda: at(t(1, 4, 6), t(1, 4, 6)), lambda: i8ie.attention(t(1, 4, 6), v=t(1, 4, 6), heads=2),
+                lambda: i8ie.attention(t(1, 4, 6), heads=1, scale=1.0), lambda: i8ie.attention(t(1, 4, 6), heads=1, score_zero_point=3)):
+        with pytest.raises(TypeError):
+            bad()
+
+
+def _operands(rng, b, tq, tk, c):
+    return (rng.integers(0, 256, (b, tq, c), dtype=np.uint8), rng.integers(0, 256, (b, tk, c), dtype=np.uint8),
+            rng.integers(0, 256, (b, tk, c), dtype=np.uint8))
+
+
+def test_ref_with_one_head_is_the_three_attention_ref_calls(orc):
+    rng = np.random.default_rng(11)
+    q, k, v = _operands(rng, 2, 7, 9, 12)
+    for relu in (False, True):
+        S, P, acc, O = mr.attention_u8(q, k, v, 1, relu=relu, **QP)
+        s = ar.matmul_u8(q, QP["zp_q"], QP["s_q"], k, QP["zp_k"], QP["s_k"], QP["s_s"], QP["zp_s"], transpose_b=True)
+        p = ar.softmax_u8(s, QP["s_s"])
+        a = ar.matmul_acc(p, 0, v, QP["zp_v"])
+        o = ar.matmul_u8(p, 0, f32(1.0 / 256), v, QP["zp_v"], QP["s_v"], QP["s_o"], QP["zp_o"], relu)
+        assert np.array_equal(S[:, 0], s) and np.array_equal(P[:, 0], p) and np.array_equal(acc, a) and np.array_equal(O, o)
+        assert len(np.unique(S)) > 50 and len(np.unique(O)) > 20   # the expected bytes discriminate
+
+
+def test_ref_heads_are_column_slices_and_packed_equals_unpacked():
+    rng = np.random.default_rng(12)
+    q, k, v = _operands(rng, 2, 5, 5, 12)
+    S, P, acc, O = mr.attention_u8(q, k, v, 3, **QP)
+    for h in range(3):
+        cs = slice(4 * h, 4 * h + 4)
+        s1, p1, a1, o1 = mr.attention_u8(q[:, :, cs], k[:, :, cs], v[:, :, cs], 1, **QP)
+        assert np.array_equal(S[:, h], s1[:, 0]) and np.array_equal(P[:, h], p1[:, 0])
+        assert np.array_equal(acc[:, :, cs], a1) and np.array_equal(O[:, :, cs], o1)
+    packed = np.concatenate([q, k, v], axis=2)
+    qp = dict(QP, s_k=QP["s_q"], s_v=QP["s_q"], zp_k=QP["zp_q"], zp_v=QP["zp_q"])
+    for a, b in zip(mr.attention_u8(packed, None, None, 3, **qp), mr.attention_u8(q, k, v, 3, **qp)):
+        assert np.array_equal(a, b)
+    sf, of = mr.attention(q, k, v, 3)
+    sp, op = mr.attention(packed, None, None, 3)
+    assert np.array_equal(sf, sp) and np.array_equal(of, op) and sf.shape == (2, 3, 5, 5) and of.shape == (2, 5, 12)
+    x = rng.integers(0, 256, (2, 6, 3, 4), dtype=np.uint8)
+    assert mr.tokens(x).shape == (2, 12, 6) and np.array_equal(mr.pixels(mr.tokens(x), 3, 4), x)
+
+
+def test_module_saves_and_restores_both_parameter_sets(i8ie):
+    class Net(i8ie.Module):
+        def __init__(self):
+            super().__init__()
+            self.attn = i8ie.Attention(2)
+            self.add1 = i8ie.Add()
+
+    net = Net()
+    with pytest.raises(RuntimeError):
+        net.quantized_state_dict()          # not converted
+    net.attn.layer.load_quantized(0.25, 7, 0.5, 131)
+    net.add1.layer.load_quantized(0.125, 3)
+    sd = net.quantized_state_dict()
+    assert sorted(sd) == ["add1.qparams", "attn.qparams", "attn.score_qparams"]
+    assert sd["attn.qparams"].tolist() == [0.0, 0.25, 7.0] and sd["attn.score_qparams"].tolist() == [0.5, 131.0]
+    assert sd["attn.score_qparams"].dtype == np.float64 and sd["attn.score_qparams"].shape == (2,)
+    other = Net()                           # unconverted, then load_quantized
+    assert not other.attn.layer.is_quantized()
+    other.load_quantized(sd)
+    assert other.attn.output_qparams() == (0.25, 7) and other.attn.score_qparams() == (0.5, 131)
+    assert other.attn.layer.is_quantized() and other.is_quant
+    assert sorted(other.quantized_state_dict()) == sorted(sd)
+
+
+def test_network_walk_discriminates_and_agrees_with_float64():
+    """the numpy walk of the test network of tests/test_gpu_mha.py, on quantisation parameters from a float64 forward: every
+    traced tensor is spread (few saturated scores, many distinct probabilities), the logits follow the float64 ones, and the
+    per-channel walk differs from the per-tensor one (the expected bytes tell the two modes apart)"""
+    sd = mr.net_state_dict()
+    qp, sq = mr.net_fp32_qparams(sd, mr.net_input(4, mr.CALIB_SEED))
+    assert sorted(qp) == sorted(list(mr.NET_LAYERS) + list(mr.NET_JOINS)) and sorted(sq) == sorted(mr.NET_ATTENTIONS)
+    x = mr.net_input(4, mr.CALIB_SEED)
+    outs = {}
+    for pc in (False, True):
+        trace = {}
+        outs[pc] = mr.net_forward(x, mr.net_quantize_layers(sd, pc), qp, sq, pc, trace)
+        assert outs[pc].shape == (4, 10) and sorted(trace) == sorted(list(mr.NET_TRACED) + [a + s for a in mr.NET_ATTENTIONS for s in (".S", ".P")])
+        for a in mr.NET_ATTENTIONS:
+            S, P = trace[a + ".S"], trace[a + ".P"]
+            assert len(np.unique(S)) > 30 and ((S == 0) | (S == 255)).mean() < 0.05 and len(np.unique(P)) >= 16 and len(np.unique(trace[a])) >= 16
+        assert trace["attn1"].shape == (4, 16, 8, 8) and trace["attn2"].shape == (4, 32, 4, 4)
+    assert not np.array_equal(outs[False], outs[True])
+    assert (outs[False].argmax(1) == outs[True].argmax(1)).all()
