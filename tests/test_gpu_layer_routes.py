@@ -38,12 +38,12 @@ _P = C.c_void_p
 # below 192 bands only when forced), i8ie_stem_supported (c <= 3, stride % 4 == 0, n in 32 / 64 / 96), i8ie_first_supported
 # (n % 32 == 0), gconv_mfma (Cg * kh * kw >= 32), deconv_mfma (c * ceil(k / s)^2 >= 32).
 DEFAULTS = dict(kind="conv", m=2, groups=1, op=0, il=NCHW, ib=0, ol=NCHW, ob=0, relu=0, pool=None, variant=0, force=False,
-                pc=False, flat=None, offset=0, dequant=None, f32=False)
+                pc=False, flat=None, offset=0, dequant=None, f32=False, dil=1)
 CASES = {}
 
 
 def case(cid, pc_twin=False, **kw):
-    bad = set(kw) - set(DEFAULTS) - {"c", "h", "w", "n", "k", "s", "p", "K"}
+    bad = set(kw) - set(DEFAULTS) - {"c", "h", "w", "n", "k", "s", "p", "K"}  # (dil: only tests/test_gpu_requant_replay.py's cases)
     assert not bad and cid not in CASES, (cid, bad)
     CASES[cid] = dict(DEFAULTS, id=cid, **kw)
     if pc_twin:
@@ -149,7 +149,7 @@ def out_hw(cs):
     if cs["kind"] == "deconv":
         oh, ow = ((d - 1) * cs["s"] - 2 * cs["p"] + cs["k"] + cs["op"] for d in (cs["h"], cs["w"]))
     else:
-        oh, ow = ((d - cs["k"] + 2 * cs["p"]) // cs["s"] + 1 for d in (cs["h"], cs["w"]))
+        oh, ow = ((d - cs["dil"] * (cs["k"] - 1) - 1 + 2 * cs["p"]) // cs["s"] + 1 for d in (cs["h"], cs["w"]))
     if cs["pool"]:
         pk, ps = cs["pool"]
         return oh, ow, (oh - pk) // ps + 1, (ow - pk) // ps + 1
@@ -194,9 +194,10 @@ def operands(cs):
 
 
 def create(gpu, cs, d):
+    """the case's layer handle over the operands d, output qparams set (d["zp_out"] when the operands name one)"""
     import deconv_ref
-    import grouped_ref
-    lib = deconv_ref.bind(grouped_ref.bind(abi.lib()))
+    import dilated_ref
+    lib = deconv_ref.bind(dilated_ref.bind(abi.lib()))
     L = C.c_void_p()
     qw, qb, sw = d["qw"].ctypes.data_as(_P), d["qb"].ctypes.data_as(_P), d["s_wv"].ctypes.data_as(_P)
     s_w, n, pc = C.c_float(d["s_w"]), cs["n"], cs["pc"]
@@ -207,11 +208,15 @@ def create(gpu, cs, d):
         a = (gpu.h, qw, qb, n, cs["c"], cs["k"], cs["s"], cs["p"], cs["op"])
         abi.ck(lib.i8ie_conv_transpose2d_create_per_channel(*a, sw, C.byref(L)) if pc else
                lib.i8ie_conv_transpose2d_create(*a, s_w, C.byref(L)))
+    elif cs["dil"] > 1:
+        a = (gpu.h, qw, qb, n, cs["c"], cs["k"], cs["k"], cs["s"], cs["p"], cs["groups"], cs["dil"])
+        abi.ck(lib.i8ie_conv2d_create_dilated_per_channel(*a, sw, C.byref(L)) if pc else
+               lib.i8ie_conv2d_create_dilated(*a, s_w, C.byref(L)))
     else:
         a = (gpu.h, qw, qb, n, cs["c"], cs["k"], cs["k"], cs["s"], cs["p"], cs["groups"])
         abi.ck(lib.i8ie_conv2d_create_grouped_per_channel(*a, sw, C.byref(L)) if pc else
                lib.i8ie_conv2d_create_grouped(*a, s_w, C.byref(L)))
-    abi.ck(lib.i8ie_layer_set_output_qparams(L, C.c_float(d["s_out"]), C.c_uint8(ZP_OUT)))
+    abi.ck(lib.i8ie_layer_set_output_qparams(L, C.c_float(d["s_out"]), C.c_uint8(d.get("zp_out", ZP_OUT))))
     return L
 
 
@@ -268,11 +273,14 @@ def core_message(text):
 
 
 # ---- one case through the entry point it names ------------------------------------------------------------------------------
-def run(gpu, cs):
+def run(gpu, cs, d=None, want_acc=False):
     """dict(first, warm: launch maps; queries; error: [rc, message] or None; violations; phys: the output region as the call
-    left it (None after an error); f32: the dequantized output of a dequant case; guards_ok)"""
+    left it (None after an error); f32: the dequantized output of a dequant case; guards_ok).  d: the operands, operands(cs)
+    when not supplied.  want_acc: the INT32 accumulators land in a guarded region of their own and come back as "acc"
+    ([m, n], or [m, oh * ow, n] of the unpooled convolution); the entries of a dequant case take none."""
     lib = abi.lib()
-    d = operands(cs)
+    d = operands(cs) if d is None else d
+    zp_out = d.get("zp_out", ZP_OUT)
     lin = cs["kind"] == "lin"
     m, n, il, ol, ib, ob = cs["m"], cs["n"], cs["il"], cs["ol"], cs["ib"], cs["ob"]
     pk, ps = cs["pool"] or (0, 0)
@@ -306,7 +314,14 @@ def run(gpu, cs):
     if cs["dequant"]:
         out_f32 = abi.GuardedU8(gpu, oshape, np.float32)
         bufs.append(out_f32)
-    ozp = ZP_OUT ^ (0x80 if ol == S8 else 0)
+    acc, acc_ptr = None, None
+    if want_acc:
+        assert not cs["dequant"]
+        uh, uw, _, _ = (1, 1, 1, 1) if lin else out_hw(cs)
+        acc = abi.GuardedU8(gpu, (m, n) if lin else (m, uh * uw, n), np.int32)
+        acc_ptr = acc.ptr
+        bufs.append(acc)
+    ozp = zp_out ^ (0x80 if ol == S8 else 0)
     if ob:
         abi.ck(lib.i8ie_fill_border_u8(gpu.h, out.ptr, m, n, ph, pw, ob, C.c_uint8(ozp)))
     L = create(gpu, cs, d)
@@ -317,10 +332,10 @@ def run(gpu, cs):
             return lib.i8ie_layer_forward_dequant(L, in_ptr, il, m, h, w, s_in, zp_in, relu,
                                                   None if cs["dequant"] == "null" else out.ptr, out_f32.ptr)
         if cs["f32"]:
-            return lib.i8ie_layer_forward_f32_input_pool(L, in_ptr, m, h, w, s_in, zp_in, relu, pk, ps, out.ptr, ol, ob, None)
+            return lib.i8ie_layer_forward_f32_input_pool(L, in_ptr, m, h, w, s_in, zp_in, relu, pk, ps, out.ptr, ol, ob, acc_ptr)
         if cs["pool"]:
-            return lib.i8ie_layer_forward_pool(L, in_ptr, il, ib, m, h, w, s_in, zp_in, relu, pk, ps, out.ptr, ol, ob, None)
-        return lib.i8ie_layer_forward_fused(L, in_ptr, il, ib, m, h, w, s_in, zp_in, relu, out.ptr, ol, ob, None)
+            return lib.i8ie_layer_forward_pool(L, in_ptr, il, ib, m, h, w, s_in, zp_in, relu, pk, ps, out.ptr, ol, ob, acc_ptr)
+        return lib.i8ie_layer_forward_fused(L, in_ptr, il, ib, m, h, w, s_in, zp_in, relu, out.ptr, ol, ob, acc_ptr)
 
     res = dict(error=None, phys=None, f32=None)
     gpu.set_variant(cs["variant"])
@@ -341,7 +356,9 @@ def run(gpu, cs):
         res["phys"] = out.get()
         if out_f32 is not None:
             res["f32"] = out_f32.get()
-    res["guards_ok"] = out.guards_ok() and (out_f32 is None or out_f32.guards_ok())
+        if acc is not None:
+            res["acc"] = acc.get()
+    res["guards_ok"] = out.guards_ok() and (out_f32 is None or out_f32.guards_ok()) and (acc is None or acc.guards_ok())
     # a query that says "folded" and a launch of its own behind it anyway
     qa, warm, bad = res["queries"], res["warm"], []
     if cs["pool"] and qa["fuses_pool"] and any(k.startswith("maxpool_") for k in warm):
@@ -360,10 +377,10 @@ def run(gpu, cs):
     return res
 
 
-def expected_phys(cs, ref):
+def expected_phys(cs, ref, zp_out=ZP_OUT):
     if cs["kind"] == "lin" or cs["ol"] == NCHW:
         return ref
-    phys = abi.Ctx.to_phys(ref, cs["ob"], ZP_OUT)
+    phys = abi.Ctx.to_phys(ref, cs["ob"], zp_out)
     return phys ^ np.uint8(0x80) if cs["ol"] == S8 else phys
 
 

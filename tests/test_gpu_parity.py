@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import abi
+import requant_ref
 import synth
 from conftest import load_cases
 
@@ -282,12 +283,8 @@ def test_requant_fast_path_boundaries(gpu, orc):
     qw[:16] = 0
     qw[np.arange(16), np.arange(16)] = 1  # first 16 features: accumulator = one input byte (+offsets)
     qb = rng.integers(-20, 20, n).astype(np.int8)
-    combos = [(1.0, 1.0, 1.0, 0), (1.0, 1.0, 1.0, 100), (0.5, 1.0, 0.25, 128), (1.0, 0.5, 4.0, 7),
-              (0.025, 0.0031, 0.11, 0), (0.1, 0.1, 0.01, 255), (3.0, 7.0, 0.001, 3), (1e-3, 1e-3, 10.0, 200),
-              (0.3333333, 0.1428571, 0.0476190, 64), (1.0, 1.0, 3.0, 1), (2.0, 1.0, 1.0, 254), (1.0, 1.0, 256.0, 0)]
-    combos += [(float(a), float(b), float(c), int(z)) for a, b, c, z in
-               zip(rng.uniform(0.001, 0.2, 12), rng.uniform(0.0005, 0.01, 12), rng.uniform(0.005, 0.5, 12),
-                   rng.integers(0, 256, 12))]
+    combos = requant_ref.BOUNDARY_COMBOS + requant_ref.random_combos(rng)  # (shared with the requantiser's dense sweeps)
+    assert len(combos) == 24
     for s_in, s_w, s_out, zp_out in combos:
         for zp_in in (0, 131):
             want, pre, _ = orc.linear(q_in, qw, qb, np.float32(s_in), zp_in, np.float32(s_w), np.float32(s_out),

@@ -15,6 +15,7 @@ import abi
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import orc
 import pc_pipeline as pcp
+from requant_ref import row_scales, s_out_for  # (shared with the requantiser's dense sweeps)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,16 +26,6 @@ def ctx():
     c = abi.Ctx()
     yield c
     c.close()
-
-
-def row_scales(n, rng, lo=1.0 / 30):
-    """per-feature scales spread log-uniformly over [lo, 1] x 2e-3"""
-    return (np.exp(rng.uniform(np.log(lo), 0.0, n)) * 2e-3).astype(np.float32)
-
-
-def s_out_for(s_in, s_w, K):
-    # an output scale that spreads the requantised values over the u8 range
-    return np.float32(s_in * float(np.median(s_w)) * np.sqrt(K) * 40.0 / 64.0)
 
 
 CONVS = [  # (name, m, c, h, kc, k, stride, pad)
