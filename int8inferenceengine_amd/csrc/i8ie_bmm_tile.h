@@ -6,9 +6,10 @@
 
 #include <cstdint>
 
+#include "i8ie_internal.h"
+
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int TM = 64, TN = 64, TK = 64;  // block tile
 constexpr int LROW = TK + 16;             // LDS bytes per staged row

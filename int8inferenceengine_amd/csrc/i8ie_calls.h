@@ -23,6 +23,21 @@ struct I8ieWCache {
   }
 };
 
+// What every contraction launch hands its epilogue (oc', Linear's float bias, the requantiser of i8ie_requant.h, the optional
+// ReLU, the accumulators' copy): one member `ep` of every call block, filled once per launch by i8ie_layer.hip.
+struct I8ieEpilogue {
+  const int32_t* ocp;  // oc[j] + 128 * wsum[j]
+  const float* biasf;  // Linear: (float)q_b[j] / s_in (src/fully_connected.cc:44); nullptr for a convolution
+  // per-channel layers: [Npad] multipliers fl(s_in * s_w[j] / s_out) and [Npad] weight scales s_w[j] (i8ie_requant.h);
+  // s_w is then 1 when every column allows the guarded estimate and 0 when the layer takes the exact sequence.
+  // nullptr: a per-tensor layer (the kernels' per-tensor instances).  The classifier head reads sbv alone.
+  const float* msv;
+  const float* sbv;
+  float s_in, s_w, s_out;
+  int zp_out, relu;
+  int32_t* acc;  // nullptr, or where the INT32 sums (with oc', before the float bias) go
+};
+
 // one contraction launch: Linear (amode 0) or implicit-GEMM Conv2d over bordered NHWC (amode 1)
 struct I8ieIgemmCall {
   const uint8_t* A;   // amode 0: [M][lda]; amode 1: window origin of pixel (0,0) in a bordered NHWC input
@@ -33,13 +48,9 @@ struct I8ieIgemmCall {
   int Hp, Wp, C, KH, KW, sh, sw, OH, OW;  // amode 1: physical input dims, kernel, strides, output dims
   const int8_t* B;
   int Kpad, Npad, N;
-  const int32_t* ocp;
-  const float* biasf;
-  float s_in, s_w, s_out;
-  int zp_out, relu;
+  I8ieEpilogue ep;
   uint8_t* out;
   int ob;  // physical border of the NHWC output (amode 1 only)
-  int32_t* acc;
   double Ktrue;
   int ksplit;        // amode 0 only: > 1 = split K over that many slices (partial must hold ksplit*M*N int32)
   int32_t* partial;
@@ -47,11 +58,6 @@ struct I8ieIgemmCall {
   // amode 1, honoured by i8ie_pconv.hip only (ask i8ie_pconv_takes first; the tiled kernel ignores them):
   int pool_k, pool_s;  // max_pool2d behind the (relu'd) convolution: `out` is then the pooled tensor, ob its border
   int a_s8, out_s8;    // input bytes / output bytes stored re-biased (^0x80: I8IE_LAYOUT_NHWC_S8)
-  // per-channel layers: [Npad] multipliers fl(s_in * s_w[j] / s_out) and [Npad] weight scales s_w[j] (i8ie_requant.h);
-  // s_w is then 1 when every column allows the guarded estimate and 0 when the layer takes the exact sequence.
-  // nullptr: a per-tensor layer (the kernels' per-tensor instances)
-  const float* msv = nullptr;
-  const float* sbv = nullptr;
 };
 // ONE definition of "this call carries a max-pool" for every file: a 1 x 1 window with a stride > 1 subsamples, so it IS a
 // pool (src/functional.cc:36-64 makes no exception for it); kernels that fold pools take k > 1 only and must decline it
@@ -106,14 +112,9 @@ struct I8ieSmallNCall {
   int M, K;
   const int8_t* B;
   int Kpad, N;
-  const int32_t* ocp;
-  const float* biasf;
-  float s_in, s_w, s_out;
-  int zp_out, relu;
+  I8ieEpilogue ep;  // (msv unused: the head takes the exact sequence)
   uint8_t* out;
-  int32_t* acc;
   float* out_f32;
-  const float* sbv;  // per-channel layers: [N] weight scales; nullptr otherwise
 };
 int i8ie_smalln_max_features();
 int i8ie_launch_linear_smalln(i8ie_ctx* ctx, const I8ieSmallNCall& c);

@@ -16,12 +16,12 @@
 // Accumulation is exact INT32, the epilogue the requantiser of i8ie_requant.h (per-tensor and per-channel instances) with the
 // optional ReLU clamp, the border the consumer asks for and the INT32 sums on request.
 #include "i8ie_internal.h"
+#include "i8ie_epilogue.h"
 #include "i8ie_dconv.h"
 #include "i8ie_pointwise.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int SLOTS = 8, TS = 4;  // slots per block; a slot is a TS x TS tile
 
 struct DconvArgs {
@@ -31,14 +31,10 @@ struct DconvArgs {
   int tyN, txN, spi;      // tiles per plane (of the largest phase) and slots per image = dil^2 tyN txN
   long long S;            // m * spi slots
   const int8_t* Bp;
-  const int32_t* ocp;
-  const float* msv;
-  const float* sbv;
-  I8ieRequant rq;
-  int relu_lo, zp_in;
+  I8ieEpiArgs ep;
+  int zp_in;
   uint8_t* out;
   int ob, vec_out;
-  int32_t* acc;
 };
 
 struct Slot {
@@ -107,48 +103,20 @@ __global__ __launch_bounds__(256) void dconv_mfma_kernel(DconvArgs p) {
   }
   if (!active) return;
 
-  // ---- oc', the accumulators' copy, requantise, store: features f .. f + 3 of the pixel of row lr in each slot
+  // ---- the quad epilogue (i8ie_epilogue.h): features f .. f + 3 of the pixel of row lr in each slot
   const int f = f0 + 4 * lq;
   if (f >= p.N) return;
   const int nf = p.N - f < 4 ? p.N - f : 4;
-  int oc4[4];
-  float ms[4], sb[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int j = f + (r < nf ? r : nf - 1);
-    oc4[r] = p.ocp[j];
-    if (PC) {
-      ms[r] = p.msv[j];
-      sb[r] = p.sbv[j];
-    }
-  }
-  const float lof = (float)p.relu_lo;
+  const I8ieQuadCols<PC> cols = i8ie_epi_cols<PC>(p.ep, f, nf);
 #pragma unroll
   for (int mi = 0; mi < SLOTS; ++mi) {
     const Slot q = decode(p, s0 + mi);
     const int oy = q.py + p.dil * (TS * q.ty + ti), ox = q.px + p.dil * (TS * q.tx + tj);
     if (!q.ok || oy >= p.OH || ox >= p.OW) continue;
-    int c[4] = {acc[mi].x + oc4[0], acc[mi].y + oc4[1], acc[mi].z + oc4[2], acc[mi].w + oc4[3]};
+    int c[4] = {acc[mi].x, acc[mi].y, acc[mi].z, acc[mi].w};
     const long long px = (q.img * p.OH + oy) * p.OW + ox;
     const long long opix = (q.img * (p.OH + 2 * p.ob) + oy + p.ob) * (p.OW + 2 * p.ob) + ox + p.ob;
-    if (p.acc != nullptr) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (r < nf) p.acc[px * p.N + f + r] = c[r];
-    }
-    uint32_t packed;
-    if constexpr (PC)
-      packed = i8ie_requant_pack4_pc(c, p.rq, make_float4(ms[0], ms[1], ms[2], ms[3]), sb, p.relu_lo, lof);
-    else
-      packed = i8ie_requant_pack4(c, p.rq, p.relu_lo, lof);
-    uint8_t* o = p.out + opix * p.N + f;
-    if (p.vec_out && nf == 4) {
-      *reinterpret_cast<uint32_t*>(o) = packed;
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (r < nf) o[r] = (uint8_t)(packed >> (8 * r));
-    }
+    i8ie_epi_finish<PC>(p.ep, c, cols, nf, px * p.N + f, p.out + opix * p.N + f, p.vec_out && nf == 4);
   }
 }
 
@@ -175,10 +143,8 @@ int i8ie_dconv_launch(i8ie_ctx* ctx, const I8ieDconvCall& c) {
   I8IE_REQUIRE(spi < ((long long)1 << 30), "dilated conv: too many tiles per image");
   a.spi = (int)spi;
   a.S = (long long)c.m * spi;
-  a.Bp = c.Bp; a.ocp = c.ocp; a.msv = c.msv; a.sbv = c.sbv;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0; a.zp_in = c.zp_in;
-  a.out = c.out; a.ob = c.ob; a.acc = c.acc;
+  a.Bp = c.Bp; a.ep = i8ie_epi_args(c.ep); a.zp_in = c.zp_in;
+  a.out = c.out; a.ob = c.ob;
   a.vec_out = (c.N % 4 == 0 && aligned_to(c.out, 4)) ? 1 : 0;
   const long long blocks = (a.S + SLOTS - 1) / SLOTS;
   I8IE_REQUIRE(blocks < ((long long)1 << 31), "dilated conv: too many output pixels in one call");
@@ -188,7 +154,7 @@ int i8ie_dconv_launch(i8ie_ctx* ctx, const I8ieDconvCall& c) {
   I8ieProfScope prof(ctx, "dconv_mfma", 2.0 * M * c.N * c.C * c.k * c.k,
                      (double)c.m * c.H * c.W * c.C + M * c.N + (double)c.Ngp * c.Kgp);
   const size_t lds = lds_bytes(c);
-  if (c.msv != nullptr) dconv_mfma_kernel<true><<<grid, 256, lds, ctx->stream>>>(a);
+  if (c.ep.msv != nullptr) dconv_mfma_kernel<true><<<grid, 256, lds, ctx->stream>>>(a);
   else dconv_mfma_kernel<false><<<grid, 256, lds, ctx->stream>>>(a);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;

@@ -10,6 +10,7 @@
 
 #include <vector>
 
+#include "i8ie_calls.h"
 #include "i8ie_requant.h"
 
 struct i8ie_ctx;
@@ -21,15 +22,11 @@ struct I8ieDeconvCall {
   int N, Ngp, Kpp;      // out features, N rounded up to 16, the phase panels' K pitch (i8ie_deconv_kpitch)
   const int8_t* Bp;     // [s * s][Ngp][Kpp]: phase (ry, rx)'s taps, K ordered (ty, tx, c), zero padded (i8ie_deconv_pack)
   const int* ktab;      // device, from i8ie_deconv_ktab
-  const int32_t* ocp;   // [N] oc + 128 * wsum, over the whole equivalent matrix
   const int32_t* tph;   // [s * s][Ngp]: the sum of feature j's weights at the taps phase ph does NOT see
-  const float* msv;     // per-channel layers (else nullptr): multipliers / weight scales, as in I8ieIgemmCall
-  const float* sbv;
-  float s_in, s_w, s_out;
-  int zp_in, zp_out, relu;
+  I8ieEpilogue ep;      // ocp [N], over the whole equivalent matrix; acc nullptr or [m * OH * OW][N]
+  int zp_in;
   uint8_t* out;         // NHWC [m][OH + 2 ob][OW + 2 ob][N], interior written
   int ob;
-  int32_t* acc;         // nullptr or [m * OH * OW][N]
 };
 bool i8ie_deconv_mfma_takes(const i8ie_ctx* ctx, const I8ieDeconvCall& c);
 int i8ie_deconv_launch(i8ie_ctx* ctx, const I8ieDeconvCall& c);

@@ -30,8 +30,6 @@
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 struct DeconvArgs {
   const uint8_t* A;  // [m][H + 2 ib][W + 2 ib][C]
   int H, W, C, ib;
@@ -51,6 +49,7 @@ struct DeconvArgs {
   int32_t* acc;  // nullptr or [m * OH * OW][N]
 };
 
+// (Not on the quad epilogue of i8ie_epilogue.h: with it the one-phase-at-a-time instances measured 1 to 2 % slower.)
 // oc', the accumulators' copy, requantise, store: 4 consecutive features f .. f + 3 of output pixel (img, oy, ox), phase ph
 template <bool PC>
 __device__ __forceinline__ void finish4(const DeconvArgs& p, int (&c)[4], long long img, int oy, int ox, int ph, int f) {
@@ -369,12 +368,12 @@ int i8ie_deconv_launch(i8ie_ctx* ctx, const I8ieDeconvCall& c) {
   a.QH = (c.OH - 1 + c.p) / c.s + 1; a.QW = (c.OW - 1 + c.p) / c.s + 1;
   a.N = c.N; a.Ngp = c.Ngp; a.Kpp = c.Kpp; a.ktab_pitch = c.Kpp / granularity(c.C);
   a.Mq = (long long)c.m * a.QH * a.QW;
-  a.Bp = c.Bp; a.ktab = reinterpret_cast<const int2*>(c.ktab); a.ocp = c.ocp; a.tph = c.tph; a.msv = c.msv; a.sbv = c.sbv;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0; a.zp_in = c.zp_in;
-  a.out = c.out; a.ob = c.ob; a.acc = c.acc;
+  a.Bp = c.Bp; a.ktab = reinterpret_cast<const int2*>(c.ktab); a.ocp = c.ep.ocp; a.tph = c.tph; a.msv = c.ep.msv; a.sbv = c.ep.sbv;
+  a.rq = i8ie_make_requant(c.ep.s_in, c.ep.s_w, c.ep.s_out, c.ep.zp_out);
+  a.relu_lo = c.ep.relu ? c.ep.zp_out : 0; a.zp_in = c.zp_in;
+  a.out = c.out; a.ob = c.ob; a.acc = c.ep.acc;
   a.vec_out = (c.N % 4 == 0 && aligned_to(c.out, 4)) ? 1 : 0;
-  const bool pc = c.msv != nullptr;
+  const bool pc = c.ep.msv != nullptr;
   const double M = (double)c.m * c.OH * c.OW;
   const double ops = 2.0 * (double)c.m * c.H * c.W * c.C * c.N * c.k * c.k;  // the real MACs
   const double bytes = (double)c.m * c.H * c.W * c.C + M * c.N + (double)c.s * c.s * c.Ngp * c.Kpp;

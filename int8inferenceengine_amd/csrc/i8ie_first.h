@@ -3,6 +3,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "i8ie_calls.h"
+
 struct i8ie_ctx;
 
 struct I8ieFirstCall {
@@ -15,14 +17,9 @@ struct I8ieFirstCall {
   int KH, KW, KWG, stride, pad, OH, OW;
   const int8_t* B;
   int Kpad, K2, N;
-  const int32_t* ocp;
-  float s_in, s_w, s_out;
-  int zp_out, relu;
+  I8ieEpilogue ep;  // acc null, or [n * OH * OW][N]
   uint8_t* out;
   int ob;
-  int32_t* acc;  // null, or [n * OH * OW][N]
-  const float* msv;  // per-channel layers: [Npad] multipliers and weight scales (i8ie_requant.h); null otherwise
-  const float* sbv;
 };
 int i8ie_first_supported(int c, int stride, int n_out, int K2, int KH, int KWG, int OW);
 size_t i8ie_first_scratch_bytes(int n, int KH, int KWG, int stride, int OH, int OW);

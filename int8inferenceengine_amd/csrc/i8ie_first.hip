@@ -25,15 +25,7 @@
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-
-using FRequant = I8ieRequant;  // i8ie_requant.h
-__device__ __forceinline__ uint32_t frequant_pack4(int c0, int c1, int c2, int c3, const FRequant& q, int lo,
-                                                   float lof) {
-  const int c[4] = {c0, c1, c2, c3};
-  return i8ie_requant_pack4(c, q, lo, lof);
-}
 
 constexpr int kMaxKS = 24;
 
@@ -62,7 +54,7 @@ struct FirstArgs {
   const int8_t* B;  // [Npad][Kpad] K ordered (kh, group, px, ch), zero padded
   int Kpad, N;
   const int32_t* ocp;
-  FRequant rq;
+  I8ieRequant rq;
   int relu_lo;
   uint8_t* out;  // NHWC [n][OH + 2ob][OW + 2ob][N]
   int ob;
@@ -191,7 +183,7 @@ __global__ __launch_bounds__(512) void conv_smallc_kernel(FirstArgs p) {
   const int pieces = (groups + 63) >> 6;                    // 1 KiB DMA wave-instructions per patch
   // iterations in which every wave issues one DMA piece
   const int fill_iters = (pieces + nwaves - 1) / nwaves;
-  const FRequant rq = p.rq;
+  const I8ieRequant rq = p.rq;
   const int lo = p.relu_lo;
   const float lof = (float)lo;
   const int OHp = p.OH + 2 * p.ob, OWp = p.OW + 2 * p.ob;
@@ -286,12 +278,12 @@ __global__ __launch_bounds__(512) void conv_smallc_kernel(FirstArgs p) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           uint32_t packed;
+          const int c4[4] = {acc[g * 4 + 0], acc[g * 4 + 1], acc[g * 4 + 2], acc[g * 4 + 3]};
           if constexpr (PC) {  // features wave * 32 + 8 g + 4 hh .. + 3 (N % 32 == 0: all exist)
             const int j0 = wave * 32 + 8 * g + 4 * hh;
-            const int c4[4] = {acc[g * 4 + 0], acc[g * 4 + 1], acc[g * 4 + 2], acc[g * 4 + 3]};
             packed = i8ie_requant_pack4_pc(c4, rq, *reinterpret_cast<const float4*>(p.msv + j0), p.sbv + j0, lo, lof);
           } else {
-            packed = frequant_pack4(acc[g * 4 + 0], acc[g * 4 + 1], acc[g * 4 + 2], acc[g * 4 + 3], rq, lo, lof);
+            packed = i8ie_requant_pack4(c4, rq, lo, lof);
           }
           *reinterpret_cast<uint32_t*>(scratch + (lane & 31) * 36 + 8 * g + 4 * hh) = packed;
         }
@@ -393,10 +385,10 @@ int i8ie_first_launch(i8ie_ctx* ctx, const I8ieFirstCall& c) {
   a.PR = (RB - 1) * a.sh + c.KH;
   a.bands_per_img = (c.OH + RB - 1) / RB;
   a.total_bands = a.bands_per_img * c.n;
-  a.B = c.B; a.Kpad = c.Kpad; a.N = c.N; a.ocp = c.ocp;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0;
-  a.out = c.out; a.ob = c.ob; a.acc = c.acc; a.msv = c.msv; a.sbv = c.sbv;
+  a.B = c.B; a.Kpad = c.Kpad; a.N = c.N; a.ocp = c.ep.ocp;
+  a.rq = i8ie_make_requant(c.ep.s_in, c.ep.s_w, c.ep.s_out, c.ep.zp_out);
+  a.relu_lo = c.ep.relu ? c.ep.zp_out : 0;
+  a.out = c.out; a.ob = c.ob; a.acc = c.ep.acc; a.msv = c.ep.msv; a.sbv = c.ep.sbv;
   const int ks_needed = (c.K2 + 31) / 32;
   const int nchunks = c.KH * c.KWG;
   for (int q = 0; q < 2 * kMaxKS; ++q) {

@@ -22,12 +22,10 @@
 // 4-GPU shard) stay one launch without partial sums (four row groups, three stages so that two blocks share a CU).  (A first form of this kernel read both operands as fragments
 // straight from global memory, 16-byte accesses 32 bytes apart: 39 us for fc6)
 #include "i8ie_calls.h"
+#include "i8ie_epilogue.h"
 #include "i8ie_internal.h"
-#include "i8ie_requant.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 struct FlinArgs {
   const uint8_t* A;  // [M][lda] u8
@@ -37,14 +35,8 @@ struct FlinArgs {
   const int8_t* B;  // [Npad][Kpad] s8, K contiguous, zero beyond K
   unsigned b_bytes;
   int Kpad, N;
-  const int32_t* ocp;  // oc + 128 * wsum (the activations enter re-biased by -128)
-  const float* biasf;
-  I8ieRequant rq;
-  int relu_lo;
+  I8ieEpiArgs ep;  // ocp = oc + 128 * wsum (the activations enter re-biased by -128); ocp, msv, sbv: [Npad]
   uint8_t* out;
-  int32_t* acc;
-  const float* msv;  // PC kernels (per-channel layers): [Npad] multipliers and weight scales (i8ie_requant.h)
-  const float* sbv;
 };
 
 constexpr int kChunk = 256;  // K bytes per chunk
@@ -134,25 +126,15 @@ __global__ __launch_bounds__(512) void flin_kernel(FlinArgs p) {
   const int row = row0 + wr * 16 + lr, n = n0 + wf * 16 + 4 * lq;
   if (row < p.M && n < p.N) {
     int cv[4] = {acc.x, acc.y, acc.z, acc.w};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (n + r < p.N) {
-        cv[r] += p.ocp[n + r];
-        if (p.acc != nullptr) p.acc[(size_t)row * p.N + n + r] = cv[r];
-        if (p.biasf != nullptr) cv[r] = (int)((float)cv[r] + p.biasf[n + r]);
-      }
-    }
+    const int nf = p.N - n < 4 ? p.N - n : 4;
     // (n < N <= Npad, n % 4 == 0: the quad lies inside the padded arrays)
-    const uint32_t packed = PC ? i8ie_requant_pack4_pc(cv, p.rq, *reinterpret_cast<const float4*>(p.msv + n), p.sbv + n, p.relu_lo, (float)p.relu_lo)
-                               : i8ie_requant_pack4(cv, p.rq, p.relu_lo, (float)p.relu_lo);
-    uint8_t* o = p.out + (size_t)row * p.N + n;
-    if (n + 3 < p.N && (p.N & 3) == 0) {
-      *reinterpret_cast<uint32_t*>(o) = packed;
-    } else {
+    i8ie_epi_finish<PC>(p.ep, cv, i8ie_epi_cols_vec<PC>(p.ep, n), nf, (long long)row * p.N + n, p.out + (size_t)row * p.N + n,
+                        nf == 4 && (p.N & 3) == 0, [&](int (&c)[4]) {
+                          if (p.ep.biasf == nullptr) return;
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (n + r < p.N) o[r] = (uint8_t)(packed >> (8 * r));
-    }
+                          for (int r = 0; r < 4; ++r)
+                            if (r < nf) c[r] = (int)((float)c[r] + p.ep.biasf[n + r]);
+                        });
   }
 }
 
@@ -194,11 +176,9 @@ int i8ie_flin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   FlinArgs a{};
   a.A = c.A; a.a_bytes = c.a_bytes; a.lda = (unsigned)c.lda; a.M = c.M;
   a.B = c.B; a.b_bytes = (unsigned)((size_t)c.Npad * c.Kpad); a.Kpad = c.Kpad; a.N = c.N;
-  a.ocp = c.ocp; a.biasf = c.biasf;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0;
-  a.out = c.out; a.acc = c.acc; a.msv = c.msv; a.sbv = c.sbv;
-  if (c.msv != nullptr) return flin_shape<true>(ctx, a, c);
+  a.ep = i8ie_epi_args(c.ep);
+  a.out = c.out;
+  if (c.ep.msv != nullptr) return flin_shape<true>(ctx, a, c);
   return flin_shape<false>(ctx, a, c);
 }
 

@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "i8ie_calls.h"
 #include "i8ie_requant.h"
 
 struct i8ie_ctx;
@@ -18,14 +19,10 @@ struct I8ieGconvCall {
   int groups, Cg, Ng, Ngp, Kgp;  // Ngp = Ng rounded up to 16, Kgp = Cg * KH * KW rounded up to 64
   const int8_t* Bp;   // [groups][Ngp][Kgp], K ordered (kh, kw, cg), zero padded
   const int* ktab;    // device, from i8ie_gconv_ktab
-  const int32_t* ocp;
-  const float* msv;   // per-channel layers (else nullptr): multipliers / weight scales, as in I8ieIgemmCall
-  const float* sbv;
-  float s_in, s_w, s_out;
-  int zp_in, zp_out, relu;
+  I8ieEpilogue ep;    // ocp [groups * Ng]; acc nullptr or [m * OH * OW][groups * Ng]
+  int zp_in;
   uint8_t* out;       // NHWC [m][OH + 2 ob][OW + 2 ob][groups * Ng], interior written
   int ob;
-  int32_t* acc;       // nullptr or [m * OH * OW][groups * Ng]
 };
 // gconv_mfma when Cg * KH * KW >= 32, the force-fallback option is off and the buffers are aligned for its gather;
 // gconv_direct otherwise

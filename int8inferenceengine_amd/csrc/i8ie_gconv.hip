@@ -16,12 +16,11 @@
 // Activations are re-biased ^0x80 on the way in (the term 128 * wsum[j] is in ocp), accumulation is exact INT32, the epilogue
 // is the requantiser of i8ie_requant.h (per-tensor and per-channel instances) with the optional ReLU clamp.
 #include "i8ie_internal.h"
+#include "i8ie_epilogue.h"
 #include "i8ie_gconv.h"
 #include "i8ie_pointwise.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 struct GconvArgs {
   const uint8_t* A;  // [m][H + 2 ib][W + 2 ib][C]
@@ -31,14 +30,10 @@ struct GconvArgs {
   long long M;          // m * OH * OW output pixels
   const int8_t* Bp;     // [groups][Ngp][Kgp]
   const int2* ktab;     // K position (in units of the gather granularity) -> {(kh << 16) | kw, cg}
-  const int32_t* ocp;   // [kc] oc + 128 * wsum
-  const float* msv;     // per-channel layers: [kc] multipliers, [kc] weight scales
-  const float* sbv;
-  I8ieRequant rq;
-  int relu_lo, zp_in;
+  I8ieEpiArgs ep;       // ocp, msv, sbv: [kc]; acc: nullptr or [M][kc]
+  int zp_in;
   uint8_t* out;         // [m][OH + 2 ob][OW + 2 ob][kc], interior written
   int ob, vec_out;      // vec_out: 4 features of a lane go out as one dword
-  int32_t* acc;         // nullptr or [M][kc]
 };
 
 struct Pixel {
@@ -66,39 +61,12 @@ __device__ __forceinline__ bool tap_inside(const GconvArgs& p, const Pixel& q, i
   return (unsigned)y < (unsigned)(p.H + 2 * p.ib) && (unsigned)x < (unsigned)(p.W + 2 * p.ib);
 }
 
-// oc', the accumulators' copy, requantise, store: 4 consecutive features f .. f + 3 of group g at one pixel
+// the quad epilogue (i8ie_epilogue.h) on 4 consecutive features f .. f + 3 of group g at one pixel
 template <bool PC>
-__device__ __forceinline__ void finish4(const GconvArgs& p, int (&c)[4], long long px, long long out_pix, int g, int f) {
+__device__ __forceinline__ void finish_quad(const GconvArgs& p, int (&c)[4], long long px, long long out_pix, int g, int f) {
   const int j0 = g * p.Ng + f, nf = p.Ng - f < 4 ? p.Ng - f : 4;
-  float ms[4], sb[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int j = j0 + (r < nf ? r : nf - 1);
-    c[r] += p.ocp[j];
-    if (PC) {
-      ms[r] = p.msv[j];
-      sb[r] = p.sbv[j];
-    }
-  }
-  if (p.acc != nullptr) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (r < nf) p.acc[px * p.kc + j0 + r] = c[r];
-  }
-  const float lof = (float)p.relu_lo;
-  uint32_t packed;
-  if constexpr (PC)
-    packed = i8ie_requant_pack4_pc(c, p.rq, make_float4(ms[0], ms[1], ms[2], ms[3]), sb, p.relu_lo, lof);
-  else
-    packed = i8ie_requant_pack4(c, p.rq, p.relu_lo, lof);
-  uint8_t* o = p.out + out_pix * p.kc + j0;
-  if (p.vec_out && nf == 4) {
-    *reinterpret_cast<uint32_t*>(o) = packed;
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (r < nf) o[r] = (uint8_t)(packed >> (8 * r));
-  }
+  i8ie_epi_finish<PC>(p.ep, c, i8ie_epi_cols<PC>(p.ep, j0, nf), nf, px * p.kc + j0, p.out + out_pix * p.kc + j0,
+                      p.vec_out && nf == 4);
 }
 
 // ---- gconv_mfma ------------------------------------------------------------------------------------------------------
@@ -188,7 +156,7 @@ __global__ __launch_bounds__(256) void gconv_mfma_kernel(GconvArgs p) {
       const int f = f0 + 16 * ni + 4 * lq;
       if (ni >= nt || f >= p.Ng) continue;
       int c[4] = {acc[mi][ni].x, acc[mi][ni].y, acc[mi][ni].z, acc[mi][ni].w};
-      finish4<PC>(p, c, q, px[mi].out_pix, g, f);
+      finish_quad<PC>(p, c, q, px[mi].out_pix, g, f);
     }
   }
 }
@@ -232,7 +200,7 @@ __global__ __launch_bounds__(256) void gconv_direct_kernel(GconvArgs p, int grou
           }
         }
       }
-    finish4<PC>(p, c, pxi, q.out_pix, g, f);
+    finish_quad<PC>(p, c, pxi, q.out_pix, g, f);
   }
 }
 
@@ -267,12 +235,11 @@ int i8ie_gconv_launch(i8ie_ctx* ctx, const I8ieGconvCall& c) {
   a.OH = c.OH; a.OW = c.OW; a.stride = c.stride; a.pad = c.pad; a.KH = c.KH; a.KW = c.KW; a.dil = c.dil;
   a.Cg = c.Cg; a.Ng = c.Ng; a.Ngp = c.Ngp; a.Kg = c.Cg * c.KH * c.KW; a.Kgp = c.Kgp; a.kc = c.groups * c.Ng;
   a.M = (long long)c.m * c.OH * c.OW;
-  a.Bp = c.Bp; a.ktab = reinterpret_cast<const int2*>(c.ktab); a.ocp = c.ocp; a.msv = c.msv; a.sbv = c.sbv;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0; a.zp_in = c.zp_in;
-  a.out = c.out; a.ob = c.ob; a.acc = c.acc;
+  a.Bp = c.Bp; a.ktab = reinterpret_cast<const int2*>(c.ktab);
+  a.ep = i8ie_epi_args(c.ep); a.zp_in = c.zp_in;
+  a.out = c.out; a.ob = c.ob;
   a.vec_out = (a.kc % 4 == 0 && c.Ng % 4 == 0 && aligned_to(c.out, 4)) ? 1 : 0;
-  const bool pc = c.msv != nullptr;
+  const bool pc = c.ep.msv != nullptr;
   const double ops = 2.0 * (double)a.M * a.kc * a.Kg;
   const double bytes = (double)c.m * c.H * c.W * c.C + (double)a.M * a.kc + (double)c.groups * c.Ngp * c.Kgp;
   if (i8ie_gconv_mfma_takes(ctx, c)) {

@@ -22,7 +22,6 @@
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 64;  // bytes of K per LDS tile = 4 chunks of 16 B = 2 MFMA k-steps

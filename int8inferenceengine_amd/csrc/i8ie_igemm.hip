@@ -34,17 +34,10 @@
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int BK2 = 128;   // bytes of K per stage: 8 chunks of 16 B = 4 MFMA k-steps
 constexpr int LROW = 144;  // LDS row stride
-
-using Requant = I8ieRequant;  // i8ie_requant.h: the exact sequence, the guarded estimate and its proof
-__device__ __forceinline__ int requant_exact(float cf, const Requant& q, int lo) { return i8ie_requant_exact(cf, q, lo); }
-__device__ __forceinline__ uint32_t requant_pack4(const int (&c)[4], const Requant& q, int lo, float lof) {
-  return i8ie_requant_pack4(c, q, lo, lof);
-}
 
 struct IgemmArgs {
   const uint8_t* A;
@@ -66,7 +59,7 @@ struct IgemmArgs {
   int N;
   const int32_t* ocp;  // [N] oc[j] + 128 * wsum[j]
   const float* biasf;  // [N] (float)q_b[j] / s_in (Linear, src/fully_connected.cc:44)
-  Requant rq;
+  I8ieRequant rq;
   int relu_lo;  // zp_out when relu is fused, else 0
   int vec_store;
   uint8_t* out;  // [M][N], or bordered NHWC when ob > 0
@@ -402,7 +395,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
   }
 
   // ---- epilogue: (bias) -> requant -> (relu) -> LDS tile [BM][BN] -> 16-B row stores ----
-  const Requant rq = p.rq;
+  const I8ieRequant rq = p.rq;
   const int lo = p.relu_lo;
   const float lof = (float)lo;
 #pragma unroll
@@ -432,7 +425,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_u8s8_kernel(IgemmArgs p, in
           if (BIAS) c = (int)((float)c + (r == 0 ? bfv.x : r == 1 ? bfv.y : r == 2 ? bfv.z : bfv.w));  // src/fully_connected.cc:44
           cv[r] = c;
         }
-        const uint32_t packed = PC ? i8ie_requant_pack4_pc(cv, rq, msq, sbq, lo, lof) : requant_pack4(cv, rq, lo, lof);
+        const uint32_t packed = PC ? i8ie_requant_pack4_pc(cv, rq, msq, sbq, lo, lof) : i8ie_requant_pack4(cv, rq, lo, lof);
         *reinterpret_cast<uint32_t*>(smem + lrow * SROW + lcol0) = packed;
       }
     }
@@ -705,7 +698,7 @@ struct SmallNArgs {
   int Kpad, N;
   const int32_t* ocp;  // oc + 128 * wsum
   const float* biasf;
-  Requant rq;
+  I8ieRequant rq;
   int relu_lo;
   uint8_t* out;      // [M][N] or nullptr
   int32_t* acc;      // [M][N] or nullptr (pre-bias INT32 accumulators)
@@ -771,7 +764,7 @@ __global__ __launch_bounds__(256) void linear_smalln_kernel(SmallNArgs p) {
     const size_t o = (size_t)row * p.N + lane;
     if (p.acc) p.acc[o] = c;
     c = (int)((float)c + p.biasf[lane]);  // src/fully_connected.cc:44
-    const int q = PC ? i8ie_requant_exact_col((float)c, p.rq, p.sbv[lane], p.relu_lo) : requant_exact((float)c, p.rq, p.relu_lo);
+    const int q = PC ? i8ie_requant_exact_col((float)c, p.rq, p.sbv[lane], p.relu_lo) : i8ie_requant_exact((float)c, p.rq, p.relu_lo);
     if (p.out) p.out[o] = (uint8_t)q;
     if (p.out_f32) p.out_f32[o] = (float)(q - p.dq_zp) * p.dq_scale;  // src/quantize_utils.cc:38-42
   }
@@ -825,7 +818,7 @@ __global__ __launch_bounds__(512) void linear_head_mfma_kernel(SmallNArgs p) {
       const size_t o = (size_t)row * p.N + j;
       if (p.acc) p.acc[o] = c;
       c = (int)((float)c + p.biasf[j]);  // src/fully_connected.cc:44
-      const int q = PC ? i8ie_requant_exact_col((float)c, p.rq, p.sbv[j], p.relu_lo) : requant_exact((float)c, p.rq, p.relu_lo);
+      const int q = PC ? i8ie_requant_exact_col((float)c, p.rq, p.sbv[j], p.relu_lo) : i8ie_requant_exact((float)c, p.rq, p.relu_lo);
       if (p.out) p.out[o] = (uint8_t)q;
       if (p.out_f32) p.out_f32[o] = (float)(q - p.dq_zp) * p.dq_scale;  // src/quantize_utils.cc:38-42
     }
@@ -860,12 +853,13 @@ __global__ __launch_bounds__(64) void finish_offsets_kernel(const int32_t* __res
   if (biasf != nullptr) biasf[j] = (float)qb[j] / s_in;
 }
 
+// (Not on the quad epilogue of i8ie_epilogue.h: that form measured 1.4 us slower per launch at 3 and 64 rows of fc7.)
 // split-K finish: C = sum of the slices' partials (slice 0 carries ocp), then the Linear epilogue of
 // src/fully_connected.cc:42-48 on 4 consecutive features per thread
 // (PC: per-channel layers, msv / sbv [N]; the 4 values of a thread may straddle a row end, so each finds its own column)
 template <bool PC>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const int32_t* __restrict__ partial, int ksplit, int M,
-                                                            int N, const float* __restrict__ biasf, Requant rq,
+                                                            int N, const float* __restrict__ biasf, I8ieRequant rq,
                                                             int relu_lo, uint8_t* __restrict__ out,
                                                             int32_t* __restrict__ acc, const float* __restrict__ msv,
                                                             const float* __restrict__ sbv) {
@@ -896,7 +890,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const int32_t* __res
       }
       packed = i8ie_requant_pack4_pc(cv, rq, make_float4(ms[0], ms[1], ms[2], ms[3]), sb, relu_lo, lof);
     } else {
-      packed = requant_pack4(cv, rq, relu_lo, lof);
+      packed = i8ie_requant_pack4(cv, rq, relu_lo, lof);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -1023,7 +1017,7 @@ int i8ie_igemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
       sub.a_bytes = left < (size_t)nb * unit_in ? left : (size_t)nb * unit_in;
       sub.M = nb * P;
       sub.out = c.out + (size_t)u0 * unit_out;
-      if (c.acc) sub.acc = c.acc + (size_t)u0 * P * c.N;
+      if (c.ep.acc) sub.ep.acc = c.ep.acc + (size_t)u0 * P * c.N;
       I8IE_REQUIRE(sub.a_bytes < limit, "igemm: chunking failed to fit the offset range");
       I8IE_TRY(i8ie_igemm_launch(ctx, sub));
     }
@@ -1064,23 +1058,23 @@ int i8ie_igemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   a.b_bytes = (unsigned)((size_t)c.Npad * c.Kpad);
   a.Kpad = c.Kpad;
   a.N = c.N;
-  a.ocp = c.ocp;
-  a.biasf = c.biasf;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0;
+  a.ocp = c.ep.ocp;
+  a.biasf = c.ep.biasf;
+  a.rq = i8ie_make_requant(c.ep.s_in, c.ep.s_w, c.ep.s_out, c.ep.zp_out);
+  a.relu_lo = c.ep.relu ? c.ep.zp_out : 0;
   a.out = c.out;
   a.ob = c.amode == 1 ? c.ob : 0;
   a.OHp = c.OH + 2 * a.ob;
   a.OWp = c.OW + 2 * a.ob;
   a.vec_store = ((c.N & 15) == 0 && (reinterpret_cast<uintptr_t>(c.out) & 15u) == 0) ? 1 : 0;
   I8IE_REQUIRE(a.ob == 0 || a.vec_store, "bordered output needs N % 16 == 0");
-  a.acc = c.acc;
-  a.msv = c.msv;
-  a.sbv = c.sbv;
+  a.acc = c.ep.acc;
+  a.msv = c.ep.msv;
+  a.sbv = c.ep.sbv;
   const double ops = 2.0 * c.M * c.N * c.Ktrue;
   const double bytes = (double)c.M * c.Ktrue + (double)c.N * c.Ktrue + (double)c.M * c.N;
   const int kb = c.Kchunks * 16;
-  const bool bias = c.biasf != nullptr, accd = c.acc != nullptr;
+  const bool bias = c.ep.biasf != nullptr, accd = c.ep.acc != nullptr;
   if (c.amode == 0 && c.ksplit > 1 && c.partial != nullptr) {
     const int nk = c.Kpad / BK2;
     a.tiles_per_slice = (nk + c.ksplit - 1) / c.ksplit;
@@ -1090,18 +1084,18 @@ int i8ie_igemm_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
       I8IE_TRY((launch_tile<0, false, false>(ctx, a, kb, ops, bytes)));
       I8ieProfScope prof(ctx, "splitk_reduce", 0.0, 4.0 * a.ksplit * c.M * c.N + (double)c.M * c.N);
       const int64_t quads = ((int64_t)c.M * c.N + 3) / 4;
-      if (c.msv != nullptr)
-        splitk_reduce_kernel<true><<<cap_grid(quads, 256), 256, 0, ctx->stream>>>(c.partial, a.ksplit, c.M, c.N, c.biasf, a.rq,
-                                                                                  a.relu_lo, c.out, c.acc, c.msv, c.sbv);
+      if (c.ep.msv != nullptr)
+        splitk_reduce_kernel<true><<<cap_grid(quads, 256), 256, 0, ctx->stream>>>(c.partial, a.ksplit, c.M, c.N, a.biasf, a.rq, a.relu_lo,
+                                                                                  c.out, a.acc, a.msv, a.sbv);
       else
-        splitk_reduce_kernel<false><<<cap_grid(quads, 256), 256, 0, ctx->stream>>>(c.partial, a.ksplit, c.M, c.N, c.biasf, a.rq,
-                                                                                   a.relu_lo, c.out, c.acc, nullptr, nullptr);
+        splitk_reduce_kernel<false><<<cap_grid(quads, 256), 256, 0, ctx->stream>>>(c.partial, a.ksplit, c.M, c.N, a.biasf, a.rq, a.relu_lo,
+                                                                                   c.out, a.acc, nullptr, nullptr);
       I8IE_LAUNCH_CHECK();
       return I8IE_OK;
     }
     a.ksplit = 0;
   }
-  if (c.msv != nullptr) {  // per-channel layer: the same dispatch, the PC instances
+  if (c.ep.msv != nullptr) {  // per-channel layer: the same dispatch, the PC instances
     if (c.amode == 0) {
       if (bias)
         return accd ? launch_tile<0, true, true, true>(ctx, a, kb, ops, bytes) : launch_tile<0, true, false, true>(ctx, a, kb, ops, bytes);
@@ -1175,15 +1169,15 @@ int i8ie_launch_linear_smalln(i8ie_ctx* ctx, const I8ieSmallNCall& c) {
                "operands must be 16-byte aligned");
   SmallNArgs a{};
   a.A = c.A; a.lda = c.lda; a.M = c.M; a.K = c.K; a.B = c.B; a.Kpad = c.Kpad; a.N = c.N;
-  a.ocp = c.ocp; a.biasf = c.biasf;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
+  a.ocp = c.ep.ocp; a.biasf = c.ep.biasf;
+  a.rq = i8ie_make_requant(c.ep.s_in, c.ep.s_w, c.ep.s_out, c.ep.zp_out);
   a.rq.fast = I8IE_RQ_EXACT;
-  a.relu_lo = c.relu ? c.zp_out : 0;
-  a.out = c.out; a.acc = c.acc; a.out_f32 = c.out_f32; a.dq_scale = c.s_out; a.dq_zp = c.zp_out; a.sbv = c.sbv;
+  a.relu_lo = c.ep.relu ? c.ep.zp_out : 0;
+  a.out = c.out; a.acc = c.ep.acc; a.out_f32 = c.out_f32; a.dq_scale = c.ep.s_out; a.dq_zp = c.ep.zp_out; a.sbv = c.ep.sbv;
   I8ieProfScope prof(ctx, "linear_smalln_dot4", 2.0 * c.M * c.N * c.K, (double)c.M * c.K + (double)c.N * c.K + 5.0 * c.M * c.N);
   // (activation rows are lda = K bytes apart and the weights are zero from K to Kpad: a step past K multiplies
   // the next row's bytes, or the zeros the descriptor returns past the buffer, by zero)
-  const bool pc = c.sbv != nullptr;
+  const bool pc = c.ep.sbv != nullptr;
   if (c.K >= 1024 && c.Kpad % 64 == 0 && (size_t)16 * c.lda + c.Kpad < ((size_t)1 << 31) && !ctx->pick.no_dot4_head) {
     if (pc) linear_head_mfma_kernel<true><<<(c.M + 15) / 16, 512, 0, ctx->stream>>>(a);
     else linear_head_mfma_kernel<false><<<(c.M + 15) / 16, 512, 0, ctx->stream>>>(a);

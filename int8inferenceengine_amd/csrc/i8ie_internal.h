@@ -8,6 +8,8 @@
 
 #include "i8ie_hip.h"
 
+typedef int v4i __attribute__((ext_vector_type(4)));  // an MFMA operand / accumulator fragment, a 16-byte access
+
 // I8IE_OPT_KERNEL_VARIANT decoded once (i8ie_decode_variant, i8ie_ctx.hip) into the choices the dispatch sites read.  A value
 // changes the one thing it names; a value this build does not know decodes to all-automatic.
 enum { I8IE_CONV_AUTO, I8IE_CONV_TILED, I8IE_CONV_PCONV, I8IE_CONV_TCONV };

@@ -208,6 +208,13 @@ static ConvRequest make_request(const uint8_t* in, int in_layout, int in_border,
   q.out = out; q.out_layout = out_layout; q.out_border = out_border; q.acc = acc;
   return q;
 }
+// the epilogue block of a contraction launch of this layer (`biasf`: the Linear routes)
+static I8ieEpilogue layer_epilogue(const i8ie_layer* L, const ConvRequest& q, const float* biasf = nullptr) {
+  I8ieEpilogue e{};
+  e.ocp = L->ocp; e.biasf = biasf; e.msv = msv_arg(L); e.sbv = sbv_arg(L);
+  e.s_in = q.s_in; e.s_w = sw_arg(L); e.s_out = L->s_out; e.zp_out = L->zp_out; e.relu = q.relu; e.acc = q.acc;
+  return e;
+}
 // route A's launch over an NHWC image with `border` pixels around it, as far as the geometry goes: what conv_plan asks the
 // patch-stationary kernel about and what forward_implicit launches
 static I8ieIgemmCall implicit_call(i8ie_layer* L, const ConvGeom& cg, int m, int border) {
@@ -220,8 +227,7 @@ static I8ieIgemmCall implicit_call(i8ie_layer* L, const ConvGeom& cg, int m, int
 }
 // ... and the rest of a launch of the contraction kernel (routes A and B)
 static void implicit_epilogue(I8ieIgemmCall& c, const i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
-  c.ocp = L->ocp; c.biasf = nullptr; c.s_in = q.s_in; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out;
-  c.relu = q.relu; c.acc = q.acc; c.Ktrue = cg.K; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
+  c.ep = layer_epilogue(L, q); c.Ktrue = cg.K;
 }
 
 // Which kernel takes this conv launch whole, with what the request asks folded in: the first-stage kernel (i8ie_stem.hip, path
@@ -281,10 +287,9 @@ static int forward_transposed(i8ie_layer* L, const ConvGeom& cg, const ConvReque
   I8ieDeconvCall d{};
   d.A = s.in; d.m = q.m; d.H = cg.h; d.W = cg.w; d.C = cg.c; d.ib = s.ib;
   d.OH = cg.oh; d.OW = cg.ow; d.k = cg.kh; d.s = cg.stride; d.p = cg.pad;
-  d.N = L->n; d.Ngp = L->Ngp; d.Kpp = L->Kpp; d.Bp = L->Bt; d.ktab = L->ttab; d.ocp = L->ocp; d.tph = L->tph;
-  d.msv = msv_arg(L); d.sbv = sbv_arg(L);
-  d.s_in = q.s_in; d.s_w = sw_arg(L); d.s_out = L->s_out; d.zp_in = q.zp_in; d.zp_out = L->zp_out; d.relu = q.relu;
-  d.out = s.out; d.ob = s.ob; d.acc = q.acc;
+  d.N = L->n; d.Ngp = L->Ngp; d.Kpp = L->Kpp; d.Bp = L->Bt; d.ktab = L->ttab; d.tph = L->tph;
+  d.ep = layer_epilogue(L, q); d.zp_in = q.zp_in;
+  d.out = s.out; d.ob = s.ob;
   I8IE_TRY(i8ie_deconv_launch(L->ctx, d));
   return unstage(L->ctx, s, q, cg.kc, cg.oh, cg.ow);
 }
@@ -296,9 +301,8 @@ static int forward_grouped(i8ie_layer* L, const ConvGeom& cg, const ConvRequest&
   g.A = s.in; g.m = q.m; g.H = cg.h; g.W = cg.w; g.C = cg.c; g.ib = s.ib;
   g.OH = cg.oh; g.OW = cg.ow; g.stride = cg.stride; g.pad = cg.pad; g.KH = cg.kh; g.KW = cg.kw; g.dil = L->dil;
   g.groups = L->groups; g.Cg = cg.c / L->groups; g.Ng = L->n / L->groups; g.Ngp = L->Ngp; g.Kgp = L->Kgp;
-  g.Bp = L->Bg; g.ktab = L->gtab; g.ocp = L->ocp; g.msv = msv_arg(L); g.sbv = sbv_arg(L);
-  g.s_in = q.s_in; g.s_w = sw_arg(L); g.s_out = L->s_out; g.zp_in = q.zp_in; g.zp_out = L->zp_out; g.relu = q.relu;
-  g.out = s.out; g.ob = s.ob; g.acc = q.acc;
+  g.Bp = L->Bg; g.ktab = L->gtab; g.ep = layer_epilogue(L, q); g.zp_in = q.zp_in;
+  g.out = s.out; g.ob = s.ob;
   // route D: a dense dilated layer at stride 1 goes to the kernel of i8ie_dconv.hip (input patches resident in LDS) when that
   // takes it -- C % 16 == 0, K >= 32, aligned buffers, an LDS plan that fits, the force-fallback option off; it reads route G's
   // panel (groups = 1: [Ngp][Kgp], K ordered (kh, kw, c)) as it is.  Everything it declines stays in the grouped kernels.
@@ -306,9 +310,8 @@ static int forward_grouped(i8ie_layer* L, const ConvGeom& cg, const ConvRequest&
     I8ieDconvCall d{};
     d.A = s.in; d.m = q.m; d.H = cg.h; d.W = cg.w; d.C = cg.c; d.ib = s.ib;
     d.OH = cg.oh; d.OW = cg.ow; d.pad = cg.pad; d.k = cg.kh; d.dil = L->dil;
-    d.N = L->n; d.Ngp = L->Ngp; d.Kgp = L->Kgp; d.Bp = L->Bg; d.ocp = L->ocp; d.msv = msv_arg(L); d.sbv = sbv_arg(L);
-    d.s_in = q.s_in; d.s_w = sw_arg(L); d.s_out = L->s_out; d.zp_in = q.zp_in; d.zp_out = L->zp_out; d.relu = q.relu;
-    d.out = s.out; d.ob = s.ob; d.acc = q.acc;
+    d.N = L->n; d.Ngp = L->Ngp; d.Kgp = L->Kgp; d.Bp = L->Bg; d.ep = g.ep; d.zp_in = q.zp_in;
+    d.out = s.out; d.ob = s.ob;
     if (i8ie_dconv_takes(L->ctx, d)) {
       I8IE_TRY(i8ie_dconv_launch(L->ctx, d));
       return unstage(L->ctx, s, q, cg.kc, cg.oh, cg.ow);
@@ -377,19 +380,15 @@ static I8ieStemCall fill_stem_call(const i8ie_layer* L, const ConvGeom& cg, cons
   I8ieStemCall f{};
   f.n = q.m; f.c = cg.c; f.h = cg.h; f.w = cg.w; f.q_scale = q.s_in; f.q_zp = q.zp_in;
   f.KH = cg.kh; f.KW = cg.kw; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
-  f.B = L->Bstem; f.Kpad = L->KpadStem; f.N = L->n; f.ocp = L->ocp;
-  f.s_in = q.s_in; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = q.relu;
-  f.pool_k = q.fold_k(); f.pool_s = q.pool_s; f.out_s8 = q.out_s8() ? 1 : 0; f.acc = q.acc;
-  f.msv = msv_arg(L); f.sbv = sbv_arg(L);
+  f.B = L->Bstem; f.Kpad = L->KpadStem; f.N = L->n; f.ep = layer_epilogue(L, q);
+  f.pool_k = q.fold_k(); f.pool_s = q.pool_s; f.out_s8 = q.out_s8() ? 1 : 0;
   return f;
 }
 static I8ieFirstCall fill_first_call(const i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
   I8ieFirstCall f{};
   f.n = q.m; f.c = cg.c; f.h = cg.h; f.w = cg.w; f.q_scale = q.s_in; f.q_zp = q.zp_in;
   f.KH = cg.kh; f.KW = cg.kw; f.KWG = L->kwg; f.stride = cg.stride; f.pad = cg.pad; f.OH = cg.oh; f.OW = cg.ow;
-  f.B = L->Bpack2; f.Kpad = L->Kpad2; f.K2 = L->K2; f.N = L->n; f.ocp = L->ocp;
-  f.s_in = q.s_in; f.s_w = sw_arg(L); f.s_out = L->s_out; f.zp_out = L->zp_out; f.relu = q.relu;
-  f.acc = q.acc; f.msv = msv_arg(L); f.sbv = sbv_arg(L);
+  f.B = L->Bpack2; f.Kpad = L->Kpad2; f.K2 = L->K2; f.N = L->n; f.ep = layer_epilogue(L, q);
   return f;
 }
 
@@ -546,8 +545,7 @@ static int forward_linear(i8ie_layer* L, const ConvRequest& q) {
     // classifier head: one wave per row, dot4 + wavefront reduction, epilogue (and dequantize) fused
     I8ieSmallNCall sc{};
     sc.A = q.in; sc.lda = (size_t)L->K; sc.M = m; sc.K = L->K; sc.B = panel; sc.Kpad = L->Kpad; sc.N = L->n;
-    sc.ocp = L->ocp; sc.biasf = L->biasf; sc.s_in = q.s_in; sc.s_w = sw_arg(L); sc.s_out = L->s_out;
-    sc.zp_out = L->zp_out; sc.relu = q.relu; sc.out = q.out; sc.acc = q.acc; sc.out_f32 = q.out_f32; sc.sbv = sbv_arg(L);
+    sc.ep = layer_epilogue(L, q, L->biasf); sc.out = q.out; sc.out_f32 = q.out_f32;
     return i8ie_launch_linear_smalln(ctx, sc);
   }
   I8IE_REQUIRE(q.out != nullptr, "i8ie_layer_forward_dequant: this layer needs the u8 output buffer as well");
@@ -593,9 +591,8 @@ static int forward_linear(i8ie_layer* L, const ConvRequest& q) {
   c.Kchunks = (int)c.lda / 16;
   c.a_bytes = (size_t)m * c.lda;
   c.amode = 0; c.M = m;
-  c.B = panel; c.Kpad = L->Kpad; c.Npad = L->Npad; c.N = L->n; c.ocp = L->ocp; c.biasf = L->biasf;
-  c.s_in = q.s_in; c.s_w = sw_arg(L); c.s_out = L->s_out; c.zp_out = L->zp_out; c.relu = q.relu;
-  c.out = q.out; c.ob = 0; c.acc = q.acc; c.Ktrue = L->K; c.msv = msv_arg(L); c.sbv = sbv_arg(L);
+  c.B = panel; c.Kpad = L->Kpad; c.Npad = L->Npad; c.N = L->n; c.ep = layer_epilogue(L, q, L->biasf);
+  c.out = q.out; c.ob = 0; c.Ktrue = L->K;
   if (flin) return i8ie_flin_launch(ctx, c);
   if (mlin) return i8ie_mlin_launch(ctx, c);
   return i8ie_igemm_launch(ctx, c);

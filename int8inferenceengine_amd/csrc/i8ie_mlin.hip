@@ -26,7 +26,6 @@
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
@@ -368,10 +367,10 @@ int i8ie_mlin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   MlinArgs a{};
   a.A = c.A; a.a_bytes = c.a_bytes; a.lda = (unsigned)c.lda; a.M = c.M;
   a.B = c.B; a.b_bytes = (unsigned)((size_t)c.Npad * c.Kpad); a.Kpad = c.Kpad; a.N = c.N;
-  a.ocp = c.ocp; a.biasf = c.biasf;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0;
-  a.out = c.out; a.acc = c.acc; a.msv = c.msv; a.sbv = c.sbv;
+  a.ocp = c.ep.ocp; a.biasf = c.ep.biasf;
+  a.rq = i8ie_make_requant(c.ep.s_in, c.ep.s_w, c.ep.s_out, c.ep.zp_out);
+  a.relu_lo = c.ep.relu ? c.ep.zp_out : 0;
+  a.out = c.out; a.acc = c.ep.acc; a.msv = c.ep.msv; a.sbv = c.ep.sbv;
   a.n_tiles = (c.N + kMlFeats - 1) / kMlFeats;
   a.ahead = kMlAhead;
   static int cus[64] = {};
@@ -384,7 +383,7 @@ int i8ie_mlin_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   // 64-row tiles when 128-row tiles give at most half the CUs a block (variant 84 / 85 force 64 / 128 rows)
   const long blocks128 = (long)((c.M + 127) / 128) * a.n_tiles;
   const bool rows64 = ctx->pick.linear == I8IE_LIN_MLIN64 || (ctx->pick.linear != I8IE_LIN_MLIN128 && blocks128 * 2 <= i8ie_cus(ctx, cus[dev]));
-  if (c.msv != nullptr) {
+  if (c.ep.msv != nullptr) {
     if (rows64) return mlin_launch_t<64, true>(ctx, a, c, "mlin_64x128");
     return mlin_launch_t<128, true>(ctx, a, c, "mlin_128x128");
   }

@@ -470,11 +470,11 @@ int i8ie_pconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) { return pconv_
 int i8ie_pconv_takes(i8ie_ctx* ctx, const I8ieIgemmCall& c) { return pconv_impl(ctx, c, true); }
 
 static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
-  if (c.amode != 1 || c.biasf != nullptr || c.wcache == nullptr) return 0;
+  if (c.amode != 1 || c.ep.biasf != nullptr || c.wcache == nullptr) return 0;
   if (c.pool_k == 1 && c.pool_s > 1) return 0;  // (a subsampling 1 x 1 pool is a pool, i8ie_is_pool, and this kernel does not fold it)
   const bool pool = c.pool_k > 1;
   if (pool && (c.pool_k > 3 || c.pool_s < 1 || c.pool_s > c.pool_k || c.pool_k > c.OH || c.pool_k > c.OW || c.N % 16 != 0)) return 0;
-  if (c.acc != nullptr && ((reinterpret_cast<uintptr_t>(c.acc) & 15u) != 0 || c.N % 4 != 0)) return 0;  // (16-byte accumulator stores)
+  if (c.ep.acc != nullptr && ((reinterpret_cast<uintptr_t>(c.ep.acc) & 15u) != 0 || c.N % 4 != 0)) return 0;  // (16-byte accumulator stores)
   if (c.N % 16 != 0 || c.N < 192 || c.Npad > 1024 || c.C < 32 || c.C % 32 != 0 || c.sh != c.sw) return 0;
   if ((reinterpret_cast<uintptr_t>(c.out) & 15u) != 0) return 0;
   const int P = c.OH * c.OW;
@@ -656,15 +656,15 @@ static int pconv_impl(i8ie_ctx* ctx, const I8ieIgemmCall& c, bool dry) {
   a.bf_bytes = (unsigned)bf_bytes;
   a.nkt = nkt;
   a.N = c.N; a.npass = npass;
-  a.ocp = c.ocp; a.Npad = c.Npad;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0;
+  a.ocp = c.ep.ocp; a.Npad = c.Npad;
+  a.rq = i8ie_make_requant(c.ep.s_in, c.ep.s_w, c.ep.s_out, c.ep.zp_out);
+  a.relu_lo = c.ep.relu ? c.ep.zp_out : 0;
   a.out = c.out;
   a.out_bytes = (unsigned)out_bytes;
   a.ob = c.ob; a.OHp = c.OH + 2 * c.ob; a.OWp = c.OW + 2 * c.ob;
   a.split = split;
-  a.acc = c.acc;
-  a.msv = c.msv; a.sbv = c.sbv;
+  a.acc = c.ep.acc;
+  a.msv = c.ep.msv; a.sbv = c.ep.sbv;
   a.a_s8 = c.a_s8;
   a.xor_out = c.out_s8 ? 0x80808080u : 0u;
   a.pk = pool ? c.pool_k : 1; a.ps = pool ? c.pool_s : 1; a.PH = PHo; a.PW = PWo; a.RB = RB; a.opitch = opitch; a.seq = seq;

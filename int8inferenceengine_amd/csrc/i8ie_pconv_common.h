@@ -7,7 +7,6 @@
 #include "i8ie_internal.h"
 #include "i8ie_requant.h"
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 

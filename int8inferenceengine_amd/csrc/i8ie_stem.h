@@ -4,6 +4,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "i8ie_calls.h"
+
 struct i8ie_ctx;
 
 struct I8ieStemCall {
@@ -16,16 +18,11 @@ struct I8ieStemCall {
   int KH, KW, stride, pad, OH, OW;
   const int8_t* B;  // [N][Kpad], K index i8ie_stem_kindex(), Kpad = i8ie_stem_kpad(), zero padded
   int Kpad, N;
-  const int32_t* ocp;
-  float s_in, s_w, s_out;
-  int zp_out, relu;
+  I8ieEpilogue ep;     // acc null, or [n * OH * OW][N]: the convolution's pre-requant accumulators
   int pool_k, pool_s;  // max_pool2d folded in behind the (relu'd) convolution: window / stride; pool_k <= 1: none
   uint8_t* out;        // NHWC u8 [n][PH + 2 ob][PW + 2 ob][N] (PH, PW: after the pool), interior only
   int ob;
   int out_s8;    // 1: bytes stored re-biased (^0x80), the I8IE_LAYOUT_NHWC_S8 form
-  int32_t* acc;  // null, or [n * OH * OW][N]: the convolution's pre-requant accumulators
-  const float* msv = nullptr;  // per-channel layers: [Npad] multipliers and weight scales (i8ie_requant.h); null otherwise
-  const float* sbv = nullptr;
 };
 int i8ie_stem_supported(int c, int stride, int N, int KH, int KW, int OH, int OW, int pool_k, int pool_s);
 int i8ie_stem_kpad(int KH, int KW);

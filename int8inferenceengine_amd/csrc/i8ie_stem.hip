@@ -735,12 +735,12 @@ int i8ie_stem_launch(i8ie_ctx* ctx, const I8ieStemCall& c) {
   a.OH = c.OH; a.OW = c.OW; a.sq = c.stride / 4; a.KC4 = s.KC4;
   a.NR = s.NR; a.first = s.first; a.T = s.T;
   a.pk = s.pk; a.ps = s.ps; a.PH = s.PH; a.PW = s.PW;
-  a.B = c.B; a.Kpad = c.Kpad; a.N = c.N; a.ocp = c.ocp;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0;
+  a.B = c.B; a.Kpad = c.Kpad; a.N = c.N; a.ocp = c.ep.ocp;
+  a.rq = i8ie_make_requant(c.ep.s_in, c.ep.s_w, c.ep.s_out, c.ep.zp_out);
+  a.relu_lo = c.ep.relu ? c.ep.zp_out : 0;
   a.out = c.out; a.ob = c.ob; a.xor_out = c.out_s8 ? 0x80808080u : 0u;
-  a.acc = c.acc;
-  a.msv = c.msv; a.sbv = c.sbv;
+  a.acc = c.ep.acc;
+  a.msv = c.ep.msv; a.sbv = c.ep.sbv;
   a.pitchP = s.pitchP; a.ringRowB = s.ringRowB; a.RING = s.RING;
   a.patchB = s.patchB;
   a.lds_patch = 0;

@@ -50,7 +50,6 @@ struct StemStrip {
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 template <int B, int E, typename F>

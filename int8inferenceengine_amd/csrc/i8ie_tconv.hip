@@ -33,7 +33,6 @@
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 
 constexpr unsigned kRowInvalid = 0xC0000000u;  // beyond any output buffer this kernel accepts (< 2^31 bytes)
@@ -404,9 +403,9 @@ int launch_tc(i8ie_ctx* ctx, const TCArgs& a, int grid, int lds) {
 }  // namespace
 
 int i8ie_tconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
-  if (c.amode != 1 || c.biasf != nullptr || c.wcache == nullptr) return 0;
+  if (c.amode != 1 || c.ep.biasf != nullptr || c.wcache == nullptr) return 0;
   if (i8ie_is_pool(c.pool_k, c.pool_s) || c.a_s8 || c.out_s8) return 0;  // (max-pool folding and re-biased layouts: i8ie_pconv.hip)
-  if (c.acc != nullptr && ((reinterpret_cast<uintptr_t>(c.acc) & 15u) != 0 || c.N % 4 != 0)) return 0;  // (16-byte accumulator stores)
+  if (c.ep.acc != nullptr && ((reinterpret_cast<uintptr_t>(c.ep.acc) & 15u) != 0 || c.N % 4 != 0)) return 0;  // (16-byte accumulator stores)
   if (c.N % 16 != 0 || c.N < 192 || c.Npad > 1024 || c.C < 32 || c.C % 32 != 0 || c.sh != c.sw) return 0;
   if ((reinterpret_cast<uintptr_t>(c.out) & 15u) != 0) return 0;
   const int P = c.OH * c.OW;
@@ -545,14 +544,14 @@ int i8ie_tconv_try_launch(i8ie_ctx* ctx, const I8ieIgemmCall& c) {
   a.bf_bytes = (unsigned)bf_bytes;
   a.nkt = nkt; a.kt_split = kt_split;
   a.N = c.N; a.npass = npass;
-  a.ocp = c.ocp; a.Npad = c.Npad;
-  a.rq = i8ie_make_requant(c.s_in, c.s_w, c.s_out, c.zp_out);
-  a.relu_lo = c.relu ? c.zp_out : 0;
+  a.ocp = c.ep.ocp; a.Npad = c.Npad;
+  a.rq = i8ie_make_requant(c.ep.s_in, c.ep.s_w, c.ep.s_out, c.ep.zp_out);
+  a.relu_lo = c.ep.relu ? c.ep.zp_out : 0;
   a.out = c.out;
   a.out_bytes = (unsigned)out_bytes;
   a.ob = c.ob; a.OHp = c.OH + 2 * c.ob; a.OWp = c.OW + 2 * c.ob;
-  a.acc = c.acc;
-  a.msv = c.msv; a.sbv = c.sbv;
+  a.acc = c.ep.acc;
+  a.msv = c.ep.msv; a.sbv = c.ep.sbv;
   a.lds_ring = 0;
   a.lds_ocp = R * slice_gran * 16;
   a.lds_tab = a.lds_ocp + npass * bn * 4;

@@ -55,7 +55,10 @@ site("igemm_conv_ragged", ["igemm_conv_128x32"], dict(lr.A, n=24, ol=NHWC), [dic
 site("igemm_conv_128", ["igemm_conv_128x128"], dict(lr.AP, variant=lr.V_TILED, **HH), [dict(pool=(2, 2)), dict(ol=S8, relu=1)])
 site("igemm_lin", ["igemm_lin_128x32"], dict(LIN, K=32, n=32), [dict()])
 site("splitk", ["splitk_reduce"], dict(LIN, K=512, n=32, variant=lr.V_TILED), [dict()])
+# (n = 18, no multiple of 4: the last quad of a row has two live values, and 3 x 18 values end inside a quad)
+site("splitk_ragged", ["splitk_reduce"], dict(LIN, K=512, n=18, variant=lr.V_TILED), [dict()])
 site("flin", ["flin_128x16"], dict(LIN, K=1024, n=2048), [dict()])
+site("flin_ragged", ["flin_128x16"], dict(LIN, K=1024, n=18, variant=V_FLIN), [dict()])
 # (above 64 rows the block is 64 rows x 32 features, two wave columns: four LDS stages up to 128 rows, three above; n = 272 is no
 # multiple of 32 and below the automatic feature threshold, hence the forced variant)
 site("flin_64", ["flin_64x32"], dict(LIN, m=65, K=1024, n=2048), [dict()])
@@ -99,7 +102,7 @@ def check_case_list():
         cases = [CASES[c] for tag in group for c in SITES[tag]["cases"]]
         assert any(c["relu"] and c["ol"] == S8 for c in cases), group
         assert any(c["zero"] for c in cases), group
-    for tag in ("igemm_lin", "splitk", "flin", "flin_64", "flin_64_3st", "mlin", "mlin_128"):
+    for tag in ("igemm_lin", "splitk", "splitk_ragged", "flin", "flin_ragged", "flin_64", "flin_64_3st", "mlin", "mlin_128"):
         assert any(CASES[c]["zero"] for c in SITES[tag]["cases"]), tag
 
 
