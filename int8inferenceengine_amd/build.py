@@ -25,6 +25,12 @@ HIP_SOURCES = ["i8ie_ctx.hip", "i8ie_elementwise.hip", "i8ie_binary.hip", "i8ie_
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
              "-Wall", "-Wno-unused-function", "-I" + INC, "-I" + CSRC]
 
+# the pybind11 module, one translation unit per concern ("The binding's layout"); it includes include/i8ie_hip.h and
+# its own headers only, and lives in a subdirectory so that _headers() does not make the kernels depend on it
+BINDING = os.path.join(CSRC, "binding")
+EXT_SOURCES = ["pybind_module.cc", "runtime.cc", "tensor.cc", "operands.cc", "ops.cc", "ops_join.cc", "ops_attention.cc", "calibrator.cc",
+               "layers.cc", "layers_weightless.cc"]
+
 LIB = os.path.join(PKG, "libi8ie_hip.so")
 EXT = os.path.join(PKG, "_CXX_i8ie" + sysconfig.get_config_var("EXT_SUFFIX"))
 
@@ -60,26 +66,36 @@ def build_hip(force=False):
         if force or _stale(o, [s] + hdrs):
             jobs.append([hipcc] + HIP_FLAGS + ["-c", s, "-o", o])
         objs.append(o)
-    if jobs:  # translation units are independent: compile them side by side (bounded: the build box has 8 CPUs)
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=int(os.environ.get("I8IE_BUILD_JOBS", "6"))) as ex:
-            list(ex.map(_run, jobs))
+    _compile(jobs)
     if force or _stale(LIB, objs):
         _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs)
     return LIB
 
 
+def _compile(jobs):
+    if jobs:  # translation units are independent: compile them side by side (bounded: the build box has 8 CPUs)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=int(os.environ.get("I8IE_BUILD_JOBS", "6"))) as ex:
+            list(ex.map(_run, jobs))
+
+
 def build_ext(force=False):
     import pybind11
 
-    src = os.path.join(CSRC, "pybind_module.cc")
-    if not os.path.exists(src):
-        return None
-    if force or _stale(EXT, [src, LIB] + _headers()):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-ffp-contract=off",
-               "-I" + INC, "-I" + CSRC, "-I" + pybind11.get_include(), "-I" + sysconfig.get_paths()["include"],
-               src, "-o", EXT, "-L" + PKG, "-li8ie_hip", "-Wl,-rpath,$ORIGIN"]
-        _run(cmd)
+    os.makedirs(OBJ, exist_ok=True)
+    cxx = ["g++", "-O2", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off", "-I" + INC, "-I" + CSRC, "-I" + BINDING,
+           "-I" + pybind11.get_include(), "-I" + sysconfig.get_paths()["include"]]
+    hdrs = [os.path.join(INC, "i8ie_hip.h")] + [os.path.join(BINDING, f) for f in os.listdir(BINDING) if f.endswith(".h")]
+    objs, jobs = [], []
+    for src in EXT_SOURCES:
+        s = os.path.join(BINDING, src)
+        o = os.path.join(OBJ, "binding_" + src.replace(".cc", ".o"))
+        if force or _stale(o, [s] + hdrs):
+            jobs.append(cxx + ["-c", s, "-o", o])
+        objs.append(o)
+    _compile(jobs)
+    if force or _stale(EXT, objs + [LIB]):
+        _run(["g++", "-shared", "-fPIC", "-o", EXT] + objs + ["-L" + PKG, "-li8ie_hip", "-Wl,-rpath,$ORIGIN"])
     return EXT
 
 

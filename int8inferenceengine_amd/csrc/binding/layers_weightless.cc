@@ -1,0 +1,294 @@
+// layers_weightless.cc -- the layers without INT8 weights (Add ... Activation, LayerNorm) and their bindings.
+#include "layers.h"
+
+namespace i8ie_py {
+
+// A layer without weights (the residual Add, the channel Concat): the layers' prepare / convert state machine
+// (src/layer.cc:28-54) around its output (scale, zero_point); FP32 tensors join in FP32 (and are sampled while preparing),
+// u8 tensors after convert().
+class Weightless : public QuantState {
+ public:
+  void convert(bool /*per_channel: there are no weights*/ = false) {
+    if (convert_qparams()) set_quantized();
+  }
+  void load_quantized(float s_out, int zp_out) {  // what convert() would have left behind
+    set_output_qparams(s_out, zp_out);
+    set_quantized();
+  }
+
+ protected:
+  Tensor<float> sampled(Tensor<float> out) {  // what a preparing layer does with its FP32 result
+    maybe_sample(out);
+    return out;
+  }
+  void need_quantized(const char* what) const {
+    if (!is_quantized_) throw std::runtime_error(std::string("i8ie: ") + what + " is not converted (call convert() first)");
+  }
+};
+class Add : public Weightless {
+ public:
+  Tensor<float> forward_f32(Tensor<float>& a, Tensor<float>& b) { return sampled(add_f32(a, b)); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& a, Tensor<u8_t>& b) {
+    need_quantized("Add");
+    return add_u8(a, b, scale_, zero_point_);
+  }
+};
+// a * b; b has a's shape or is a's gate [n, c, 1, 1] / [n, c]
+class Mul : public Weightless {
+ public:
+  Tensor<float> forward_f32(Tensor<float>& a, Tensor<float>& b) { return sampled(mul_f32(a, b)); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& a, Tensor<u8_t>& b) {
+    mul_is_gate(a, b);
+    need_quantized("Mul");
+    return mul_u8(a, b, scale_, zero_point_);
+  }
+};
+// a . b of two activation tensors (matmul_shape's rules), each optionally given transposed
+class MatMul : public Weightless {
+ public:
+  MatMul(bool transpose_a, bool transpose_b) : ta_(transpose_a), tb_(transpose_b) {}
+  Tensor<float> forward_f32(Tensor<float>& a, Tensor<float>& b) { return sampled(matmul_f32(a, b, ta_, tb_)); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& a, Tensor<u8_t>& b) {
+    matmul_shape(a, b, ta_, tb_);
+    need_quantized("MatMul");
+    return matmul_u8(a, b, scale_, zero_point_, ta_, tb_);
+  }
+  bool transpose_a() const { return ta_; }
+  bool transpose_b() const { return tb_; }
+
+ private:
+  bool ta_, tb_;
+};
+// multi-head attention of q, k, v (or one packed qkv tensor; attention_shape's rules): two calibrated parameter sets, the
+// scores' (scale, zero_point) beside the output's.  While preparing, the FP32 scores are sampled by a calibrator of their own.
+class Attention : public Weightless {
+ public:
+  explicit Attention(ssize_t heads) : heads_(heads) {
+    if (heads < 1) throw std::runtime_error("i8ie: Attention: heads must be >= 1");
+  }
+  void prepare() {
+    if (!is_quantized_) score_cal_ = std::make_unique<Calibrator>();
+    QuantState::prepare();
+  }
+  void convert(bool /*per_channel: there are no weights*/ = false) {
+    if (!is_quantized_ && is_preparing_ && score_cal_ && score_cal_->cnt > 0) {
+      float s;
+      u8_t z;
+      std::tie(s, z) = score_cal_->get_range(1);
+      if (!score_overridden_) {
+        score_scale_ = s;
+        score_zp_ = z;
+      }
+    }
+    score_cal_.reset();
+    Weightless::convert();
+  }
+  void set_score_qparams(float s, int zp) {  // inject what calibration would produce
+    check_zero_point(zp);
+    score_scale_ = s;
+    score_zp_ = (u8_t)zp;
+    score_overridden_ = true;
+  }
+  std::tuple<float, int> score_qparams() const { return std::make_tuple(score_scale_, (int)score_zp_); }
+  void load_quantized(float s_out, int zp_out, float s_score, int zp_score) {  // what convert() would have left behind
+    set_score_qparams(s_score, zp_score);
+    Weightless::load_quantized(s_out, zp_out);
+  }
+  Tensor<float> forward_f32(Tensor<float>& q, Tensor<float>& k, Tensor<float>& v) { return run_f32(q, &k, &v); }
+  Tensor<float> forward_f32_packed(Tensor<float>& qkv) { return run_f32(qkv, nullptr, nullptr); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& q, Tensor<u8_t>& k, Tensor<u8_t>& v) { return run_u8(q, &k, &v); }
+  Tensor<u8_t> forward_u8_packed(Tensor<u8_t>& qkv) { return run_u8(qkv, nullptr, nullptr); }
+  ssize_t heads() const { return heads_; }
+
+ private:
+  Tensor<float> run_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v) {
+    if (!is_preparing_ || !score_cal_) return attention_f32(q, k, v, heads_, nullptr);
+    const AttnShape s = attention_shape(q, k, v, heads_);
+    Tensor<float> scores(std::vector<ssize_t>{s.b, s.heads, s.tq, s.tk});
+    Tensor<float> out = attention_f32(q, k, v, heads_, &scores);
+    calib_sample(*score_cal_, scores);
+    return sampled(out);
+  }
+  Tensor<u8_t> run_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v) {
+    attention_shape(q, k, v, heads_);
+    need_quantized("Attention");
+    return attention_u8(q, k, v, heads_, score_scale_, score_zp_, scale_, zero_point_);
+  }
+  ssize_t heads_;
+  std::unique_ptr<Calibrator> score_cal_;
+  float score_scale_ = 1;
+  u8_t score_zp_ = 0;
+  bool score_overridden_ = false;
+};
+// cat along axis 1: a list of FP32 tensors before convert(), of u8 tensors after it
+class Concat : public Weightless {
+ public:
+  py::object forward(const py::list& tensors) {
+    if (!tensors.empty() && py::isinstance<Tensor<u8_t>>(tensors[0])) {
+      std::vector<Tensor<u8_t>> ts = cat_list<u8_t>(tensors);
+      cat_shape(ts);
+      need_quantized("Concat");
+      return py::cast(cat_u8(std::move(ts), scale_, zero_point_));
+    }
+    return py::cast(sampled(cat_f32(cat_list<float>(tensors))));
+  }
+};
+// a table-driven activation (I8IE_ACT_*): f in FP32 before convert(), one table lookup from the input tensor's
+// (scale, zero_point) to this layer's own output qparams after it
+class Activation : public Weightless {
+ public:
+  Activation(int kind, float param) : kind_(kind), param_(param) {
+    LutBytes probe;  // (an unknown kind or a slope that is not finite is refused here)
+    check(i8ie_activation_table(kind, param, 1.0f, 0, 1.0f, 0, probe.data()));
+  }
+  Tensor<float> forward_f32(Tensor<float>& x) { return sampled(activation_f32(x, kind_, param_)); }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& x) {
+    need_quantized("Activation");
+    return activation_u8(x, kind_, param_, scale_, zero_point_);
+  }
+  int kind() const { return kind_; }
+  float param() const { return param_; }
+
+ private:
+  int kind_;
+  float param_;
+};
+// LayerNorm over the channel axis of [n, c, h, w] or the last axis of [m, f] / [b, t, f]: a layer with fp32 weight (gamma) and
+// bias (beta) and the layers' prepare / convert state machine around its output (scale, zero_point).  There are no INT8
+// weights: convert() computes g = gamma / s_out and b = beta / s_out + zp_out (i8ie_layernorm_affine) and uploads them once.
+class LayerNorm : public QuantState {
+ public:
+  LayerNorm(ssize_t channels, float eps) : channels_(channels), eps_(eps) {
+    if (channels < 1 || channels > 16384) throw std::runtime_error("i8ie: LayerNorm: channels must be in 1..16384");
+    if (!(eps > 0) || !std::isfinite(eps)) throw std::runtime_error("i8ie: LayerNorm: eps must be positive and finite");
+    gamma_.assign((size_t)channels, 1.0f);
+    beta_.assign((size_t)channels, 0.0f);
+  }
+  void load_weight(const py::object& w) { gamma_ = layer_norm_param(w, channels_, 1.0f, "weight"); params_changed(); }
+  void load_bias(const py::object& b) { beta_ = layer_norm_param(b, channels_, 0.0f, "bias"); params_changed(); }
+  void convert(bool /*per_channel: there are no INT8 weights*/ = false) {
+    if (!convert_qparams()) return;
+    install();
+  }
+  void load_quantized(const py::object& w, const py::object& b, float s_out, int zp_out) {  // what convert() would have left behind
+    check_zero_point(zp_out);
+    gamma_ = layer_norm_param(w, channels_, 1.0f, "weight");
+    beta_ = layer_norm_param(b, channels_, 0.0f, "bias");
+    scale_ = s_out;
+    zero_point_ = (u8_t)zp_out;
+    qparams_overridden_ = true;
+    install();
+  }
+  Tensor<float> forward_f32(Tensor<float>& x) {
+    layer_norm_rows(x, channels_);
+    if (!gamma_dev_) {
+      gamma_dev_ = upload_f32(gamma_);
+      beta_dev_ = upload_f32(beta_);
+    }
+    Tensor<float> out = layer_norm_f32(x, gamma_dev_, beta_dev_, channels_, eps_);
+    maybe_sample(out);
+    return out;
+  }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& x) {
+    layer_norm_rows(x, channels_);
+    if (!is_quantized_) throw std::runtime_error("i8ie: LayerNorm is not converted (call convert() first)");
+    return layer_norm_u8(x, g_dev_, b_dev_, channels_, eps_, scale_, zero_point_);
+  }
+  py::array_t<float> weight() const { return py::array_t<float>((ssize_t)gamma_.size(), gamma_.data()); }
+  py::array_t<float> bias() const { return py::array_t<float>((ssize_t)beta_.size(), beta_.data()); }
+  ssize_t channels() const { return channels_; }
+  float eps() const { return eps_; }
+
+ protected:
+  void output_qparams_changed() override {
+    if (is_quantized_) install();
+  }
+
+ private:
+  void params_changed() {
+    gamma_dev_.reset();
+    beta_dev_.reset();
+    if (is_quantized_) install();
+  }
+  void install() {
+    if (!(scale_ > 0) || !std::isfinite(scale_)) throw std::runtime_error("i8ie: LayerNorm: the output scale must be positive and finite");
+    std::tie(g_dev_, b_dev_) = layer_norm_affine(gamma_, beta_, scale_, zero_point_);
+    set_quantized();
+  }
+  ssize_t channels_;
+  float eps_;
+  std::vector<float> gamma_, beta_;
+  std::shared_ptr<Storage> gamma_dev_, beta_dev_;  // FP32 path
+  std::shared_ptr<Storage> g_dev_, b_dev_;         // after convert()
+};
+template <typename L>
+void bind_weightless_state(py::class_<L>& c) {
+  bind_quant_state(c);
+  c.def("load_quantized", &L::load_quantized, py::arg("out_scale"), py::arg("out_zero_point"));
+}
+template <typename L>
+void bind_weightless_common(py::class_<L>& c) {
+  c.def(py::init<>());
+  bind_weightless_state(c);
+}
+
+void bind_weightless_layers(py::module_& m) {
+  {
+    py::class_<Add> c(m, "Add");
+    bind_weightless_common(c);
+    c.def("__call__", &Add::forward_f32).def("__call__", &Add::forward_u8);
+  }
+  {
+    py::class_<Mul> c(m, "Mul");
+    bind_weightless_common(c);
+    c.def("__call__", &Mul::forward_f32).def("__call__", &Mul::forward_u8);
+  }
+  {
+    py::class_<MatMul> c(m, "MatMul");
+    c.def(py::init<bool, bool>(), py::arg("transpose_a") = false, py::arg("transpose_b") = false);
+    bind_weightless_state(c);
+    c.def("__call__", &MatMul::forward_f32).def("__call__", &MatMul::forward_u8)
+        .def("transpose_a", &MatMul::transpose_a).def("transpose_b", &MatMul::transpose_b);
+  }
+  {
+    py::class_<Attention> c(m, "Attention");
+    bind_quant_state(c);
+    c.def(py::init<ssize_t>(), py::arg("heads"))
+        .def("set_score_qparams", &Attention::set_score_qparams, py::arg("scale"), py::arg("zero_point"))
+        .def("score_qparams", &Attention::score_qparams)
+        .def("load_quantized", &Attention::load_quantized, py::arg("out_scale"), py::arg("out_zero_point"), py::arg("score_scale"),
+             py::arg("score_zero_point"))
+        .def("heads", &Attention::heads)
+        .def("__call__", &Attention::forward_f32).def("__call__", &Attention::forward_f32_packed)
+        .def("__call__", &Attention::forward_u8).def("__call__", &Attention::forward_u8_packed);
+  }
+  {
+    py::class_<Concat> c(m, "Concat");
+    bind_weightless_common(c);
+    c.def("__call__", &Concat::forward, py::arg("tensors"));
+  }
+  {
+    py::class_<Activation> c(m, "Activation");
+    c.def(py::init<int, float>(), py::arg("kind"), py::arg("param") = 0.0f);
+    bind_weightless_state(c);
+    c.def("__call__", &Activation::forward_f32).def("__call__", &Activation::forward_u8).def("kind", &Activation::kind).def("param", &Activation::param);
+  }
+
+  {
+    py::class_<LayerNorm> c(m, "LayerNorm");
+    bind_quant_state(c);
+    c.def(py::init<ssize_t, float>(), py::arg("channels"), py::arg("eps") = 1e-5f)
+        .def("load_weight", &LayerNorm::load_weight)
+        .def("load_bias", &LayerNorm::load_bias)
+        .def("__call__", &LayerNorm::forward_f32)
+        .def("__call__", &LayerNorm::forward_u8)
+        .def("load_quantized", &LayerNorm::load_quantized, py::arg("weight"), py::arg("bias"), py::arg("out_scale"),
+             py::arg("out_zero_point"))
+        .def("weight", &LayerNorm::weight)
+        .def("bias", &LayerNorm::bias)
+        .def("channels", &LayerNorm::channels)
+        .def("eps", &LayerNorm::eps);
+  }
+}
+
+}  // namespace i8ie_py

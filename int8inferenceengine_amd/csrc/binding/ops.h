@@ -1,0 +1,167 @@
+// ops.h -- the functional ops: the shape rules the layer classes share with them (templates) and the ops the layers call.
+#pragma once
+#include "operands.h"
+
+namespace i8ie_py {
+
+// ---- mul (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_mul_u8) ----------------------------
+// b has a's shape (false), or is a gate [n, c, 1, 1] / [n, c] of a rank-4 a (true); anything else is a RuntimeError
+// (before any device call).  Only the second operand broadcasts.
+template <typename T>
+bool mul_is_gate(const Tensor<T>& a, const Tensor<T>& b) {
+  if (a.shape.size() != 2 && a.shape.size() != 4) throw std::runtime_error("i8ie: mul: the first operand must be [n, c, h, w] or [m, f]");
+  for (ssize_t d : a.shape)
+    if (d <= 0) throw std::runtime_error("i8ie: mul: empty tensor");
+  if (a.shape == b.shape) return false;
+  const bool gate = a.shape.size() == 4 && b.shape.size() >= 2 && b.shape[0] == a.shape[0] && b.shape[1] == a.shape[1] &&
+                    (b.shape.size() == 2 || (b.shape.size() == 4 && b.shape[2] == 1 && b.shape[3] == 1));
+  if (!gate)
+    throw std::runtime_error("i8ie: mul: the second operand must have the first one's shape or be its gate [n, c, 1, 1] / [n, c] "
+                             "(no other broadcasting)");
+  return true;
+}
+// ---- matmul / softmax (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_bmm_u8, i8ie_softmax_u8) ----
+// Operands are rank 3 [b, r, c], or rank 4 [n, c, h, w] counted as [n, c, h * w] (the last two dimensions merged in reference
+// order).  a is [b, m, k] ([b, k, m] when transpose_a), b is [b, k, n] ([b, n, k] when transpose_b); the same b on both sides.
+// The result is [b, m, n] -- or [b, m, h, w] when a was given as rank 4 [b, m, h, w], untransposed, and n == h * w.  Anything
+// else is a RuntimeError (before any device call).
+struct MatmulShape {
+  ssize_t b = 0, m = 0, n = 0, k = 0;
+  std::vector<ssize_t> out;
+};
+template <typename T>
+MatmulShape matmul_shape(const Tensor<T>& a, const Tensor<T>& b, bool ta, bool tb) {
+  auto rc = [](const Tensor<T>& t, const char* which) {
+    if (t.shape.size() != 3 && t.shape.size() != 4)
+      throw std::runtime_error(std::string("i8ie: matmul: the ") + which + " operand must be [b, r, c] or [n, c, h, w]");
+    for (ssize_t d : t.shape)
+      if (d <= 0) throw std::runtime_error("i8ie: matmul: empty tensor");
+    return std::array<ssize_t, 3>{t.shape[0], t.shape[1], t.shape.size() == 4 ? t.shape[2] * t.shape[3] : t.shape[2]};
+  };
+  const auto A = rc(a, "first"), B = rc(b, "second");
+  MatmulShape s;
+  s.b = A[0];
+  s.m = ta ? A[2] : A[1];
+  s.k = ta ? A[1] : A[2];
+  s.n = tb ? B[1] : B[2];
+  if (B[0] != s.b) throw std::runtime_error("i8ie: matmul: the operands' batch sizes differ (there is no broadcasting)");
+  if ((tb ? B[2] : B[1]) != s.k) throw std::runtime_error("i8ie: matmul: the operands' inner dimensions differ");
+  if (s.k > 32768) throw std::runtime_error("i8ie: matmul: inner dimension above 32768");
+  if (a.shape.size() == 4 && !ta && s.n == a.shape[2] * a.shape[3]) s.out = {s.b, s.m, a.shape[2], a.shape[3]};
+  else s.out = {s.b, s.m, s.n};
+  return s;
+}
+// ---- attention (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_attention_u8) -----------------------
+// Operands are rank 3 [b, t, c], or rank 4 [n, c, h, w] counted as [n, h * w, c] (the engine's NHWC storage as it lies).  q is
+// [b, tq, c], k and v are [b, tk, c], c = heads * d; or one packed tensor with 3 * heads * d channels (k == v == nullptr): q, k, v
+// are then its channels [0, c), [c, 2c), [2c, 3c).  The result has q's rank: [b, tq, c] or [n, c, h, w].  Anything else is a
+// RuntimeError (before any device call).
+struct AttnShape {
+  ssize_t b = 0, heads = 0, d = 0, c = 0, tq = 0, tk = 0;
+  bool packed = false;
+  std::vector<ssize_t> out;
+};
+template <typename T>
+AttnShape attention_shape(const Tensor<T>& q, const Tensor<T>* k, const Tensor<T>* v, ssize_t heads) {
+  auto btc = [](const Tensor<T>& t, const char* which) {
+    if (t.shape.size() != 3 && t.shape.size() != 4)
+      throw std::runtime_error(std::string("i8ie: attention: ") + which + " must be [b, t, c] or [n, c, h, w]");
+    for (ssize_t d : t.shape)
+      if (d <= 0) throw std::runtime_error("i8ie: attention: empty tensor");
+    if (t.shape.size() == 4) return std::array<ssize_t, 3>{t.shape[0], t.shape[2] * t.shape[3], t.shape[1]};
+    return std::array<ssize_t, 3>{t.shape[0], t.shape[1], t.shape[2]};
+  };
+  if ((k == nullptr) != (v == nullptr)) throw std::runtime_error("i8ie: attention takes q, k and v, or one packed qkv tensor");
+  if (heads < 1) throw std::runtime_error("i8ie: attention: heads must be >= 1");
+  AttnShape s;
+  s.heads = heads;
+  s.packed = k == nullptr;
+  const auto Q = btc(q, s.packed ? "qkv" : "q");
+  s.b = Q[0];
+  s.tq = s.tk = Q[1];
+  if (s.packed) {
+    if (Q[2] % (3 * heads) != 0) throw std::runtime_error("i8ie: attention: a packed qkv tensor needs 3 * heads * d channels");
+    s.c = Q[2] / 3;
+  } else {
+    const auto K = btc(*k, "k"), V = btc(*v, "v");
+    if (K[0] != s.b || V[0] != s.b) throw std::runtime_error("i8ie: attention: the operands' batch sizes differ (there is no broadcasting)");
+    if (K[2] != Q[2] || V[2] != Q[2]) throw std::runtime_error("i8ie: attention: q, k and v must have the same channel count");
+    if (K[1] != V[1]) throw std::runtime_error("i8ie: attention: k and v must have the same token count");
+    if (Q[2] % heads != 0) throw std::runtime_error("i8ie: attention: the channel count is not heads * d");
+    s.c = Q[2];
+    s.tk = K[1];
+  }
+  s.d = s.c / heads;
+  if (s.tk > 32768) throw std::runtime_error("i8ie: attention: more than 32768 key tokens");
+  if (q.shape.size() == 4) s.out = {s.b, s.c, q.shape[2], q.shape[3]};
+  else s.out = {s.b, s.tq, s.c};
+  return s;
+}
+// ---- layer_norm (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_layernorm_u8) ---------------------
+// [n, c, h, w] is normalised over c per pixel, [m, f] and [b, t, f] over the last axis: (rows, inner) of the FP32 entry, or
+// a RuntimeError (before any device call)
+template <typename T>
+std::pair<int64_t, int64_t> layer_norm_rows(const Tensor<T>& x, ssize_t channels) {
+  const size_t r = x.shape.size();
+  if (x.size <= 0 || (r != 2 && r != 3 && r != 4)) throw std::runtime_error("i8ie: layer_norm expects [n, c, h, w], [m, f] or [b, t, f]");
+  if ((r == 4 ? x.shape[1] : x.shape.back()) != channels)
+    throw std::runtime_error("i8ie: layer_norm: the normalised axis has " + std::to_string(r == 4 ? x.shape[1] : x.shape.back()) +
+                             " values, the layer " + std::to_string(channels));
+  if (channels > 16384) throw std::runtime_error("i8ie: layer_norm: rows of more than 16384 values");
+  return {(int64_t)(x.size / channels), r == 4 ? (int64_t)(x.shape[2] * x.shape[3]) : 1};
+}
+// ---- cat (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_concat_u8) --------------------------
+// axis 1 of k rank-4 [n, c_i, h, w] or k rank-2 [m, f_i] tensors: the result's shape, or a RuntimeError (before any device call)
+template <typename T>
+std::vector<ssize_t> cat_shape(const std::vector<Tensor<T>>& ts) {
+  if (ts.empty() || ts.size() > I8IE_CONCAT_MAX_INPUTS) throw std::runtime_error("i8ie: cat: between 1 and 8 tensors");
+  std::vector<ssize_t> shp = ts[0].shape;
+  if (shp.size() != 2 && shp.size() != 4) throw std::runtime_error("i8ie: cat: tensors must be [n, c, h, w] or [m, f] (joined along axis 1)");
+  for (size_t i = 1; i < ts.size(); ++i) {
+    const std::vector<ssize_t>& s = ts[i].shape;
+    if (s.size() != shp.size()) throw std::runtime_error("i8ie: cat: ranks differ");
+    for (size_t d = 0; d < s.size(); ++d)
+      if (d != 1 && s[d] != ts[0].shape[d]) throw std::runtime_error("i8ie: cat: shapes differ outside axis 1");
+    shp[1] += s[1];
+  }
+  for (const auto& t : ts)
+    for (ssize_t d : t.shape)
+      if (d <= 0) throw std::runtime_error("i8ie: cat: empty tensor");
+  return shp;
+}
+// a Python list of tensors of one dtype; anything else (a mix included) is a RuntimeError
+template <typename T>
+std::vector<Tensor<T>> cat_list(const py::list& l) {
+  std::vector<Tensor<T>> ts;
+  for (const py::handle& h : l) {
+    if (!py::isinstance<Tensor<T>>(h)) throw std::runtime_error("i8ie: cat: every tensor must have the same dtype (float32, or uint8 with scale and zero_point)");
+    ts.push_back(h.cast<Tensor<T>&>());
+  }
+  return ts;
+}
+using LutBytes = std::array<u8_t, 256>;
+
+// the ops a layer class calls (ops_join.cc, ops_attention.cc, ops.cc); every other op is reached through bind_ops alone
+Tensor<float> add_f32(Tensor<float>& a, Tensor<float>& b);
+Tensor<u8_t> add_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp);
+Tensor<float> mul_f32(Tensor<float>& a, Tensor<float>& b);
+Tensor<u8_t> mul_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp);
+Tensor<float> cat_f32(std::vector<Tensor<float>> ts);
+Tensor<u8_t> cat_u8(std::vector<Tensor<u8_t>> ts, float scale, int zp);
+Tensor<float> matmul_f32(Tensor<float>& a, Tensor<float>& b, bool ta, bool tb);
+Tensor<u8_t> matmul_u8(Tensor<u8_t>& a, Tensor<u8_t>& b, float scale, int zp, bool ta, bool tb);
+Tensor<float> softmax_f32(Tensor<float>& x);
+Tensor<u8_t> softmax_u8(Tensor<u8_t>& x);
+Tensor<float> attention_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads, Tensor<float>* scores);
+Tensor<u8_t> attention_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, float s_s, int zp_s, float scale, int zp);
+Tensor<float> layer_norm_f32(Tensor<float>& x, const std::shared_ptr<Storage>& gamma, const std::shared_ptr<Storage>& beta, ssize_t channels, float eps);
+Tensor<u8_t> layer_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, const std::shared_ptr<Storage>& b, ssize_t channels, float eps,
+                           float scale, int zp);
+std::vector<float> layer_norm_param(const py::object& a, ssize_t channels, float fill, const char* what);
+std::pair<std::shared_ptr<Storage>, std::shared_ptr<Storage>> layer_norm_affine(const std::vector<float>& gamma, const std::vector<float>& beta,
+                                                                                 float scale, int zp);
+Tensor<float> activation_f32(Tensor<float>& in, int kind, float param);
+Tensor<u8_t> activation_u8(Tensor<u8_t>& in, int kind, float param, float scale, int zp);
+void bind_ops(py::module_& m);
+
+}  // namespace i8ie_py
