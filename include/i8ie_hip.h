@@ -894,6 +894,59 @@ int i8ie_layernorm_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, 
 int i8ie_layernorm_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int64_t rows, int C, const float* gamma_dev,
                        const float* beta_dev, float eps, int64_t inner);
 
+/* ---- quantized GroupNorm over the pixels of an image (no counterpart in the reference) -----------------------------------
+ * The input is [n, C, h, w] bytes with (s_in, zp_in); there are G groups, C % G == 0, cg = C / G.  Row (i, g) is the
+ * N = cg * h * w bytes of image i whose channel c lies in [g cg, (g + 1) cg); gamma[C], beta[C] are fp32, indexed by the
+ * element's channel.  G == C is InstanceNorm, G == 1 a LayerNorm over (c, h, w) of one image.  1 <= N <= 65536:
+ *     |N a - S1| <= 255 * 65536 < 2^24, so d is exact in fp32;
+ *     S2 <= 65536 * 65025 < 2^32: it is kept in an unsigned 32 (or 64 bits), not in a signed 32;
+ *     V = N S2 - S1^2 <= (255 N)^2 / 4 < 2^47 < 2^53, exact in int64 and in a double.
+ * eps is finite and > 0.  Per row the arithmetic is the LayerNorm's above with C read as N, line for line:
+ *     S1 = sum a     S2 = sum a^2     V = N * S2 - S1 * S1  (int64)
+ *     E  = (double)N * N * (double)eps / ((double)s_in * (double)s_in)                  host, double
+ *     r  = (float)(1.0 / sqrt((double)V + E))
+ *     d = N * a - S1;  t = (float)d * r;  u = t * g[c];  v = u + b[c]     fp32, three roundings, no contraction
+ *     q = v >= 255 ? 255 : (v < 0 ? 0 : (u8)v);  q = relu ? max(q, zp_out) : q
+ * with g[c], b[c] of the element's channel c from i8ie_layernorm_affine (C values, unchanged).  zp_in drops out.  A constant
+ * row has V = 0 and q = clamp(trunc(b[c])).  The exclusions are the LayerNorm's: E positive with 1 / sqrt(E) finite in fp32,
+ * every g[c] and b[c] finite; no NaN can then arise.
+ * The bound against the real-number GroupNorm y* = T G + Bt (T = d / sqrt(V + N^2 eps / s_in^2) = (x - mean) / sqrt(var +
+ * eps), sum d^2 = N V so |T| <= sqrt(N); G = gamma[c] / s_out, Bt = beta[c] / s_out + zp_out) is the LayerNorm's, whose
+ * derivation uses the row length in |T| <= sqrt(N) alone:
+ *     |v - y*| <= B(y*) = 1.01 * 2^-24 * (5 |T G| + 2 |beta / s_out| + 255 + |y*|)
+ * and q = clamp(trunc(y*)) wherever y* is further than B from an integer.
+ *
+ * i8ie_groupnorm_u8_nhwc: NHWC buffers [n, h+2b, w+2b, C] -> [n, h+2b', w+2b', C], each with its own border and plain or
+ * re-biased (x_s8 != 0: bytes ^ 0x80), as for i8ie_layernorm_u8_nhwc.  The input's border bytes are never read; only the
+ * interior of `out` is written; out may be in itself when both geometries agree.  A flat [n, C] tensor is h = w = 1, border
+ * 0.  g_dev, b_dev: fp32 [C] on the device, 4-byte aligned.  ws_dev: i8ie_groupnorm_workspace_bytes(n, C, G, h, w) bytes
+ * of the caller's, 4-byte aligned (may be NULL where that is 0); it need not be zeroed: partial sums are written, then
+ * summed, with no atomics on device memory, so the integer statistics are bit-reproducible by construction.  Stateless: no
+ * device allocation, no host synchronisation, capturable in a graph.  C % G != 0, N outside 1..65536, C outside 1..16384,
+ * eps or s_in not finite and positive (or an E as excluded above), null pointers, negative borders, non-positive sizes and a
+ * null ws_dev where the split form runs (the direct form, which unaligned pointers or I8IE_OPT_FORCE_FALLBACK select, takes
+ * none) are I8IE_ERR_ARG with a message, before any device call.  Three forms with identical
+ * bytes (csrc/i8ie_groupnorm.hip): groupnorm_u8_image (one launch, a block stages one image's interior
+ * of at most I8IE_GROUPNORM_IMAGE_BYTES in LDS), groupnorm_u8_stats + groupnorm_u8_apply (two launches, larger images) and
+ * groupnorm_u8_direct (the definition verbatim, one wave per row) for C % 16 != 0, C > 4096, in, out, g or b not 16-byte
+ * aligned and for everything under I8IE_OPT_FORCE_FALLBACK. */
+#define I8IE_GROUPNORM_MAX_N 65536
+#define I8IE_GROUPNORM_IMAGE_BYTES 98304 /* h * w * C of the image form */
+#define I8IE_GROUPNORM_CHUNK_BYTES 32768 /* the split form's pixel chunk: max(1, this / C) pixels */
+int i8ie_groupnorm_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev, int out_border,
+                           int out_s8, int n, int C, int G, int h, int w, const float* g_dev, const float* b_dev, float s_in,
+                           float eps, int relu, uint8_t zp_out, void* ws_dev);
+/* Host only, no ctx: the bytes ws_dev must hold for these sizes -- the split form's partial sums, n * chunks * 2 * G
+ * unsigned 32-bit values, chunks = ceil(h w / max(1, 32768 / C)) -- or 0 where no form needs any (the image form, and every
+ * shape that takes the direct form whatever the pointers are).  -1 with a message for sizes the entry above refuses. */
+int64_t i8ie_groupnorm_workspace_bytes(int n, int C, int G, int h, int w);
+/* FP32 (before convert(), and while calibrating) on NCHW floats [n, C, hw]: row (i, g) is N = cg * hw contiguous floats.
+ * Per row the sequence of i8ie_layernorm_f32 in ascending address order, every step fp32 with one rounding per operation, no
+ * contraction: mean = (sum x) / N; var = (sum (x - mean)^2) / N; out = (x - mean) / sqrtf(var + eps) * gamma[c] + beta[c],
+ * c the element's channel.  out may alias in.  1 <= N <= 65536, C % G == 0, eps finite and > 0.  Not tuned. */
+int i8ie_groupnorm_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int C, int G, int64_t hw,
+                       const float* gamma_dev, const float* beta_dev, float eps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -295,6 +295,6 @@ class BaseLayer : public QuantState {
 };
 
 void bind_layers(py::module_& m);             // layers.cc: Linear, Conv2d, ConvTranspose2d, then the weightless ones
-void bind_weightless_layers(py::module_& m);  // layers_weightless.cc: Add ... Activation, LayerNorm
+void bind_weightless_layers(py::module_& m);  // layers_weightless.cc: Add ... Activation, LayerNorm, GroupNorm
 
 }  // namespace i8ie_py

@@ -1,4 +1,4 @@
-// layers_weightless.cc -- the layers without INT8 weights (Add ... Activation, LayerNorm) and their bindings.
+// layers_weightless.cc -- the layers without INT8 weights (Add ... Activation, LayerNorm, GroupNorm) and their bindings.
 #include "layers.h"
 
 namespace i8ie_py {
@@ -221,6 +221,75 @@ class LayerNorm : public QuantState {
   std::shared_ptr<Storage> gamma_dev_, beta_dev_;  // FP32 path
   std::shared_ptr<Storage> g_dev_, b_dev_;         // after convert()
 };
+// GroupNorm of [n, c, h, w] or [n, c] (torch.nn.GroupNorm): LayerNorm's state machine and parameters, the statistics taken per
+// image over the pixels and the c / groups channels of a group (include/i8ie_hip.h, i8ie_groupnorm_u8_nhwc).
+class GroupNorm : public QuantState {
+ public:
+  GroupNorm(ssize_t groups, ssize_t channels, float eps) : groups_(groups), channels_(channels), eps_(eps) {
+    if (channels < 1 || channels > 16384) throw std::runtime_error("i8ie: GroupNorm: num_channels must be in 1..16384");
+    if (groups < 1 || channels % groups != 0) throw std::runtime_error("i8ie: GroupNorm: num_channels must be a multiple of num_groups");
+    if (!(eps > 0) || !std::isfinite(eps)) throw std::runtime_error("i8ie: GroupNorm: eps must be positive and finite");
+    gamma_.assign((size_t)channels, 1.0f);
+    beta_.assign((size_t)channels, 0.0f);
+  }
+  void load_weight(const py::object& w) { gamma_ = layer_norm_param(w, channels_, 1.0f, "weight"); params_changed(); }
+  void load_bias(const py::object& b) { beta_ = layer_norm_param(b, channels_, 0.0f, "bias"); params_changed(); }
+  void convert(bool /*per_channel: there are no INT8 weights*/ = false) {
+    if (!convert_qparams()) return;
+    install();
+  }
+  void load_quantized(const py::object& w, const py::object& b, float s_out, int zp_out) {  // what convert() would have left behind
+    check_zero_point(zp_out);
+    gamma_ = layer_norm_param(w, channels_, 1.0f, "weight");
+    beta_ = layer_norm_param(b, channels_, 0.0f, "bias");
+    scale_ = s_out;
+    zero_point_ = (u8_t)zp_out;
+    qparams_overridden_ = true;
+    install();
+  }
+  Tensor<float> forward_f32(Tensor<float>& x) {
+    group_norm_pixels(x, groups_, channels_);
+    if (!gamma_dev_) {
+      gamma_dev_ = upload_f32(gamma_);
+      beta_dev_ = upload_f32(beta_);
+    }
+    Tensor<float> out = group_norm_f32(x, gamma_dev_, beta_dev_, groups_, channels_, eps_);
+    maybe_sample(out);
+    return out;
+  }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& x) {
+    group_norm_pixels(x, groups_, channels_);
+    if (!is_quantized_) throw std::runtime_error("i8ie: GroupNorm is not converted (call convert() first)");
+    return group_norm_u8(x, g_dev_, b_dev_, groups_, channels_, eps_, scale_, zero_point_);
+  }
+  py::array_t<float> weight() const { return py::array_t<float>((ssize_t)gamma_.size(), gamma_.data()); }
+  py::array_t<float> bias() const { return py::array_t<float>((ssize_t)beta_.size(), beta_.data()); }
+  ssize_t num_groups() const { return groups_; }
+  ssize_t channels() const { return channels_; }
+  float eps() const { return eps_; }
+
+ protected:
+  void output_qparams_changed() override {
+    if (is_quantized_) install();
+  }
+
+ private:
+  void params_changed() {
+    gamma_dev_.reset();
+    beta_dev_.reset();
+    if (is_quantized_) install();
+  }
+  void install() {
+    if (!(scale_ > 0) || !std::isfinite(scale_)) throw std::runtime_error("i8ie: GroupNorm: the output scale must be positive and finite");
+    std::tie(g_dev_, b_dev_) = layer_norm_affine(gamma_, beta_, scale_, zero_point_);
+    set_quantized();
+  }
+  ssize_t groups_, channels_;
+  float eps_;
+  std::vector<float> gamma_, beta_;
+  std::shared_ptr<Storage> gamma_dev_, beta_dev_;  // FP32 path
+  std::shared_ptr<Storage> g_dev_, b_dev_;         // after convert()
+};
 template <typename L>
 void bind_weightless_state(py::class_<L>& c) {
   bind_quant_state(c);
@@ -288,6 +357,22 @@ void bind_weightless_layers(py::module_& m) {
         .def("bias", &LayerNorm::bias)
         .def("channels", &LayerNorm::channels)
         .def("eps", &LayerNorm::eps);
+  }
+  {
+    py::class_<GroupNorm> c(m, "_GroupNorm");  // (private to the i8ie package: see _group_norm in ops.cc)
+    bind_quant_state(c);
+    c.def(py::init<ssize_t, ssize_t, float>(), py::arg("num_groups"), py::arg("num_channels"), py::arg("eps") = 1e-5f)
+        .def("load_weight", &GroupNorm::load_weight)
+        .def("load_bias", &GroupNorm::load_bias)
+        .def("__call__", &GroupNorm::forward_f32)
+        .def("__call__", &GroupNorm::forward_u8)
+        .def("load_quantized", &GroupNorm::load_quantized, py::arg("weight"), py::arg("bias"), py::arg("out_scale"),
+             py::arg("out_zero_point"))
+        .def("weight", &GroupNorm::weight)
+        .def("bias", &GroupNorm::bias)
+        .def("num_groups", &GroupNorm::num_groups)
+        .def("channels", &GroupNorm::channels)
+        .def("eps", &GroupNorm::eps);
   }
 }
 

@@ -265,6 +265,11 @@ ssize_t layer_norm_axis(const Tensor<T>& x) {
   if (x.shape.size() < 2) throw std::runtime_error("i8ie: layer_norm expects [n, c, h, w], [m, f] or [b, t, f]");
   return x.shape.size() == 4 ? x.shape[1] : x.shape.back();
 }
+template <typename T>
+ssize_t group_norm_channels(const Tensor<T>& x) {
+  if (x.shape.size() != 2 && x.shape.size() != 4) throw std::runtime_error("i8ie: group_norm expects [n, c, h, w] or [n, c]");
+  return x.shape[1];
+}
 
 void bind_ops(py::module_& m) {
   m.def("quantize", &quantize);         // src/pybind11.cc:41-45
@@ -306,6 +311,22 @@ void bind_ops(py::module_& m) {
     auto gb = layer_norm_affine(layer_norm_param(w, c, 1.0f, "weight"), layer_norm_param(b, c, 0.0f, "bias"), scale, zp);
     return layer_norm_u8(x, gb.first, gb.second, c, eps, scale, zp);
   }, py::arg("x"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("scale"), py::arg("zero_point"));
+  // additive: GroupNorm of [n, c, h, w] or [n, c] per image over the pixels and the c / num_groups channels of a group
+  // (include/i8ie_hip.h, i8ie_groupnorm_u8_nhwc); weight / bias: float32 [c] or None (ones / zeros); uploaded per call.  The
+  // extension's public names are recorded whole in tests/golden/binding_surface.json, which stays as it is: this entry and
+  // the _GroupNorm class are private to the i8ie package, which exposes them as i8ie.group_norm and i8ie.GroupNorm
+  m.def("_group_norm", [](Tensor<float>& x, ssize_t groups, const py::object& w, const py::object& b, float eps) {
+    const ssize_t c = group_norm_channels(x);
+    group_norm_pixels(x, groups, c);
+    return group_norm_f32(x, upload_f32(layer_norm_param(w, c, 1.0f, "weight")), upload_f32(layer_norm_param(b, c, 0.0f, "bias")), groups, c, eps);
+  }, py::arg("x"), py::arg("num_groups"), py::arg("weight"), py::arg("bias"), py::arg("eps"));
+  m.def("_group_norm", [](Tensor<u8_t>& x, ssize_t groups, const py::object& w, const py::object& b, float eps, float scale, int zp) {
+    check_out_qparams("group_norm", scale, zp);
+    const ssize_t c = group_norm_channels(x);
+    group_norm_pixels(x, groups, c);
+    auto gb = layer_norm_affine(layer_norm_param(w, c, 1.0f, "weight"), layer_norm_param(b, c, 0.0f, "bias"), scale, zp);
+    return group_norm_u8(x, gb.first, gb.second, groups, c, eps, scale, zp);
+  }, py::arg("x"), py::arg("num_groups"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("scale"), py::arg("zero_point"));
   // additive: cat along axis 1 of up to 8 tensors, a copy in FP32; the quantized concat of include/i8ie_hip.h on u8 tensors
   m.def("cat", [](const py::list& tensors) { return cat_f32(cat_list<float>(tensors)); }, py::arg("tensors"));
   m.def("cat", [](const py::list& tensors, float scale, int zp) { return cat_u8(cat_list<u8_t>(tensors), scale, zp); },

@@ -110,6 +110,22 @@ std::pair<int64_t, int64_t> layer_norm_rows(const Tensor<T>& x, ssize_t channels
   if (channels > 16384) throw std::runtime_error("i8ie: layer_norm: rows of more than 16384 values");
   return {(int64_t)(x.size / channels), r == 4 ? (int64_t)(x.shape[2] * x.shape[3]) : 1};
 }
+// ---- group_norm (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_groupnorm_u8_nhwc) ----------------
+// [n, c, h, w] is normalised per image over the pixels and the c / groups channels of a group, [n, c] is h = w = 1: the pixels
+// per image, or a RuntimeError (before any device call)
+template <typename T>
+int64_t group_norm_pixels(const Tensor<T>& x, ssize_t groups, ssize_t channels) {
+  const size_t r = x.shape.size();
+  if (x.size <= 0 || (r != 2 && r != 4)) throw std::runtime_error("i8ie: group_norm expects [n, c, h, w] or [n, c]");
+  if (channels < 1 || channels > 16384) throw std::runtime_error("i8ie: group_norm: channels must be in 1..16384");
+  if (groups < 1 || channels % groups != 0) throw std::runtime_error("i8ie: group_norm: the channel count must be a multiple of the group count");
+  if (x.shape[1] != channels)
+    throw std::runtime_error("i8ie: group_norm: the tensor has " + std::to_string(x.shape[1]) + " channels, the layer " + std::to_string(channels));
+  const int64_t hw = r == 4 ? (int64_t)(x.shape[2] * x.shape[3]) : 1;
+  if ((int64_t)(channels / groups) * hw > I8IE_GROUPNORM_MAX_N)
+    throw std::runtime_error("i8ie: group_norm: a group of one image has more than 65536 values");
+  return hw;
+}
 // ---- cat (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_concat_u8) --------------------------
 // axis 1 of k rank-4 [n, c_i, h, w] or k rank-2 [m, f_i] tensors: the result's shape, or a RuntimeError (before any device call)
 template <typename T>
@@ -160,6 +176,10 @@ Tensor<u8_t> layer_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, 
 std::vector<float> layer_norm_param(const py::object& a, ssize_t channels, float fill, const char* what);
 std::pair<std::shared_ptr<Storage>, std::shared_ptr<Storage>> layer_norm_affine(const std::vector<float>& gamma, const std::vector<float>& beta,
                                                                                  float scale, int zp);
+Tensor<float> group_norm_f32(Tensor<float>& x, const std::shared_ptr<Storage>& gamma, const std::shared_ptr<Storage>& beta, ssize_t groups,
+                             ssize_t channels, float eps);
+Tensor<u8_t> group_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, const std::shared_ptr<Storage>& b, ssize_t groups,
+                           ssize_t channels, float eps, float scale, int zp);
 Tensor<float> activation_f32(Tensor<float>& in, int kind, float param);
 Tensor<u8_t> activation_u8(Tensor<u8_t>& in, int kind, float param, float scale, int zp);
 void bind_ops(py::module_& m);

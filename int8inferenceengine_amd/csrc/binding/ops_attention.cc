@@ -1,4 +1,4 @@
-// ops_attention.cc -- matmul, softmax, attention and layer_norm.
+// ops_attention.cc -- matmul, softmax, attention, layer_norm and group_norm.
 #include "ops.h"
 
 namespace i8ie_py {
@@ -261,6 +261,56 @@ Tensor<u8_t> layer_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, 
           check(i8ie_layernorm_u8(ctx(), (const uint8_t*)si->device_ptr(), (uint8_t*)st->dev, rows, C, (const float*)g->dev,
                                   (const float*)b->dev, s_in, eps, relu ? 1 : 0, zp_o));
         }
+        return st;
+      });
+}
+Tensor<float> group_norm_f32(Tensor<float>& x, const std::shared_ptr<Storage>& gamma, const std::shared_ptr<Storage>& beta, ssize_t groups,
+                             ssize_t channels, float eps) {
+  const int64_t hw = group_norm_pixels(x, groups, channels);
+  if (!(eps > 0) || !std::isfinite(eps)) throw std::runtime_error("i8ie: group_norm: eps must be positive and finite");
+  Tensor<float> out(x.shape);
+  check(i8ie_groupnorm_f32(ctx(), x.dptr(), out.dptr(), (int)x.shape[0], (int)channels, (int)groups, hw, (const float*)gamma->dev,
+                           (const float*)beta->dev, eps));
+  return out;
+}
+// g, b: the device arrays of i8ie_layernorm_affine for (scale, zp), kept alive by the recorded launch
+Tensor<u8_t> group_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, const std::shared_ptr<Storage>& b, ssize_t groups,
+                           ssize_t channels, float eps, float scale, int zp) {
+  check_out_qparams("group_norm", scale, zp);
+  need_contents(in);
+  group_norm_pixels(in, groups, channels);
+  if (!(eps > 0) || !std::isfinite(eps)) throw std::runtime_error("i8ie: group_norm: eps must be positive and finite");
+  if (!(in.scale > 0) || !std::isfinite(in.scale)) throw std::runtime_error("i8ie: group_norm: the input scale must be positive and finite");
+  const std::vector<ssize_t> shp = in.shape;
+  const float s_in = in.scale;
+  const u8_t zp_o = (u8_t)zp;
+  const int C = (int)channels, G = (int)groups;
+  // deferred like layer_norm's result: relu(gn(..)) is one launch (two in the split form), a consuming conv gets its zero-point
+  // border and, where it reads them, re-biased bytes straight from the kernel
+  return deferred_one_input(
+      in, shp, scale, zp_o, [g, b, shp, s_in, eps, zp_o, C, G](std::shared_ptr<Storage> si, bool relu, int border, bool s8) {
+        const int n = (int)shp[0], h = shp.size() == 4 ? (int)shp[2] : 1, w = shp.size() == 4 ? (int)shp[3] : 1;
+        std::shared_ptr<Storage> st;
+        int in_border = 0, in_s8 = 0;
+        if (shp.size() == 4) {
+          NhwcCopies copies;
+          si = as_engine_nhwc(si, shp, copies);
+          st = nhwc_storage(shp, border, zp_o, s8);
+          in_border = si->border;
+          in_s8 = si->s8 ? 1 : 0;
+        } else {  // [n, c] rows: one pixel per image (a flattened NHWC activation of one pixel per image is in that order already)
+          if (si->layout == I8IE_LAYOUT_NHWC && si->dh * si->dw == 1 && si->border == 0) si->unbias();
+          else si->to_nchw();
+          st = device_storage((size_t)n * C);
+        }
+        // the split form's partial sums come from the allocator the result came from (stream-ordered, so a capture sees no
+        // allocation of its own kind); the block goes back behind the two launches
+        const int64_t ws_bytes = i8ie_groupnorm_workspace_bytes(n, C, G, h, w);
+        if (ws_bytes < 0) check(-1);
+        std::shared_ptr<Storage> ws = ws_bytes > 0 ? device_storage((size_t)ws_bytes) : nullptr;
+        check(i8ie_groupnorm_u8_nhwc(ctx(), (const uint8_t*)si->device_ptr(), in_border, in_s8, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, n,
+                                     C, G, h, w, (const float*)g->dev, (const float*)b->dev, s_in, eps, relu ? 1 : 0, zp_o,
+                                     ws ? ws->dev : nullptr));
         return st;
       });
 }

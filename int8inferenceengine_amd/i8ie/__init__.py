@@ -9,7 +9,7 @@ import numbers
 
 import _CXX_i8ie as _C
 
-from .layer import Activation, Add, Attention, Concat, Conv2d, ConvTranspose2d, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind
+from .layer import Activation, Add, Attention, Concat, Conv2d, ConvTranspose2d, GroupNorm, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind
 from .module import Module
 from .tensor import Tensor
 
@@ -19,7 +19,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
-    "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "Attention", "attention",
+    "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "GroupNorm", "group_norm", "Attention", "attention",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -144,6 +144,24 @@ def layer_norm(x, weight=None, bias=None, eps=1e-5, scale=None, zero_point=None)
     if scale is not None or zero_point is not None:
         raise TypeError("layer_norm of an FP32 tensor takes no scale / zero_point")
     return Tensor(_C.layer_norm(x.data, weight, bias, float(eps)))
+
+
+def group_norm(x, num_groups, weight=None, bias=None, eps=1e-5, scale=None, zero_point=None):
+    """GroupNorm of [n, c, h, w], or of [n, c] counted as h = w = 1 (anything else raises RuntimeError): per image, the
+    statistics of each of the `num_groups` groups of c / num_groups channels over all pixels.  num_groups == c is InstanceNorm,
+    num_groups == 1 a LayerNorm over (c, h, w).  `weight` / `bias`: float32 arrays of c values, or None for ones / zeros.  A
+    group of one image holds at most 65536 values.  FP32 tensors: the fp32 sequence of include/i8ie_hip.h
+    (i8ie_groupnorm_f32), `scale` / `zero_point` must not be given.  uint8 tensors: the quantized GroupNorm
+    (i8ie_groupnorm_u8_nhwc); the result's `scale` and `zero_point` are required, and gamma / scale, beta / scale +
+    zero_point are computed and uploaded at every call.  `i8ie.GroupNorm` is the calibrated form for use inside a Module."""
+    quantized = type(x.data).__name__ == "6TensorIhE"
+    if quantized:
+        if scale is None or zero_point is None:
+            raise TypeError("group_norm of a uint8 tensor needs the result's scale and zero_point")
+        return Tensor(_C._group_norm(x.data, int(num_groups), weight, bias, float(eps), float(scale), int(zero_point)))
+    if scale is not None or zero_point is not None:
+        raise TypeError("group_norm of an FP32 tensor takes no scale / zero_point")
+    return Tensor(_C._group_norm(x.data, int(num_groups), weight, bias, float(eps)))
 
 
 def cat(tensors, scale=None, zero_point=None):

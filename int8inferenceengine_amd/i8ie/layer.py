@@ -88,7 +88,25 @@ class ConvTranspose2d(Layer):
         self.layer = _C.ConvTranspose2d(in_channels, out_channels, kernel_size, stride, padding, output_padding)
 
 
-class LayerNorm(Layer):
+class Norm(Layer):
+    """Common behaviour of the normalisation layers (LayerNorm, GroupNorm): fp32 `weight` / `bias`, a calibrated output (scale,
+    zero_point) and no INT8 weights.  Module.load() takes `<attr>.weight` / `<attr>.bias`; quantized_state_dict() keeps both as
+    float32 beside `<attr>.qparams`.  weight_scale, weight_scales, q_weight, q_bias and forward_debug raise RuntimeError."""
+
+    def convert(self, per_channel=False):
+        """per_channel is accepted and ignored: there are no INT8 weights."""
+        self.layer.convert()
+
+    def is_per_channel(self):
+        return False
+
+    def _no_int8_weights(self, *args, **kwargs):
+        raise RuntimeError("i8ie: %s has no INT8 weights (weight and bias stay float32)" % type(self).__name__)
+
+    weight_scale = weight_scales = q_weight = q_bias = forward_debug = _no_int8_weights
+
+
+class LayerNorm(Norm):
     """Quantized LayerNorm `y = self.norm1(x)` (additive, not in the reference): a layer with fp32 `weight` (gamma, default
     ones) and `bias` (beta, default zeros) of `channels` values each, and no INT8 weights.
 
@@ -103,17 +121,22 @@ class LayerNorm(Layer):
         self.channels, self.eps = int(channels), float(eps)
         self.layer = _C.LayerNorm(self.channels, self.eps)
 
-    def convert(self, per_channel=False):
-        """per_channel is accepted and ignored: there are no INT8 weights."""
-        self.layer.convert()
 
-    def is_per_channel(self):
-        return False
+class GroupNorm(Norm):
+    """Quantized GroupNorm `y = self.gn1(x)` (additive, not in the reference), with torch.nn.GroupNorm's argument order: a layer
+    with fp32 `weight` (gamma, default ones) and `bias` (beta, default zeros) of `num_channels` values each, and no INT8
+    weights.
 
-    def _no_int8_weights(self, *args, **kwargs):
-        raise RuntimeError("i8ie: LayerNorm has no INT8 weights (weight and bias stay float32)")
+    [n, c, h, w] (c == num_channels) is normalised per image over the h * w pixels and the c / num_groups channels of each
+    group; [n, c] counts as h = w = 1; any other shape raises RuntimeError.  num_groups == num_channels is InstanceNorm,
+    num_groups == 1 a LayerNorm over (c, h, w) of one image: there are no extra classes for them.  num_channels must be a
+    multiple of num_groups, 1 <= num_channels <= 16384, and a group of one image holds at most 65536 values.  FP32 tensors go
+    through the fp32 sequence of include/i8ie_hip.h (i8ie_groupnorm_f32; sampled by the calibrator while preparing); uint8
+    tensors, after convert(), through i8ie_groupnorm_u8_nhwc with this layer's output (scale, zero_point)."""
 
-    weight_scale = weight_scales = q_weight = q_bias = forward_debug = _no_int8_weights
+    def __init__(self, num_groups, num_channels, eps=1e-5):
+        self.num_groups, self.num_channels, self.eps = int(num_groups), int(num_channels), float(eps)
+        self.layer = _C._GroupNorm(self.num_groups, self.num_channels, self.eps)
 
 
 class Weightless(Layer):

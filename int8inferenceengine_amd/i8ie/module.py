@@ -1,7 +1,7 @@
 """Module base class (reference i8ie/module.py:6-35)."""
 import _CXX_i8ie as _C
 
-from .layer import Attention, Layer, LayerNorm, Weightless
+from .layer import Attention, Layer, Norm, Weightless
 from .tensor import Tensor
 
 # Hard-coded input quantisation of the reference (i8ie/module.py:20).
@@ -53,7 +53,7 @@ class Module:
         (weight_scale, out_scale, out_zero_point)} for every converted layer; a per-channel layer also has
         '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused).  An Add, a Mul, a Concat or an Activation contributes only
         '<attr>.qparams' = (0, out_scale, out_zero_point), an Attention that and '<attr>.score_qparams' float64[2] = (scale, zero_point);
-        a LayerNorm '<attr>.qparams' and '<attr>.weight', '<attr>.bias' as float32."""
+        a LayerNorm or a GroupNorm '<attr>.qparams' and '<attr>.weight', '<attr>.bias' as float32."""
         import numpy as np
 
         out = {}
@@ -69,7 +69,7 @@ class Module:
             if isinstance(layer, Weightless):
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
                 continue
-            if isinstance(layer, LayerNorm):
+            if isinstance(layer, Norm):
                 out[name + ".weight"] = np.asarray(L.weight(), np.float32)
                 out[name + ".bias"] = np.asarray(L.bias(), np.float32)
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
@@ -96,7 +96,7 @@ class Module:
             if isinstance(layer, Weightless):
                 layer.layer.load_quantized(float(np.float32(s_out)), int(zp_out))
                 continue
-            if isinstance(layer, LayerNorm):
+            if isinstance(layer, Norm):
                 layer.layer.load_quantized(np.asarray(state[name + ".weight"], np.float32), np.asarray(state[name + ".bias"], np.float32),
                                            float(np.float32(s_out)), int(zp_out))
                 continue

@@ -1,0 +1,655 @@
+"""The quantized GroupNorm on the GPU (csrc/i8ie_groupnorm.hip).  Every byte is compared against the numpy
+restatement of the definition (tests/groupnorm_ref.py), never against the code under test: every group shape through the form
+its sizes select and through the direct form, the LDS budget's edge, the split form's chunks, the statistics extremes, the
+bordered / re-biased layouts with guard bytes in all three forms, the FP32 entry against float64, and the Python surface
+(shapes, launch counts, calibration, save / load, graph replay)."""
+import ctypes as C
+import itertools
+
+import numpy as np
+import pytest
+
+import abi
+import grouped_ref as gr
+import groupnorm_ref as gn
+import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import layernorm_ref as lr
+import orc
+import spec_ref as sr
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+QP = (f32(0.025), f32(0.02), 128, f32(1e-5))   # s_in, s_out, zp_out, eps
+# (C, G): cg = 1 (InstanceNorm), 2, 4, 10, 16, 32, G = 1, and two channel counts that are no multiple of 16 (direct)
+GROUPS = [(32, 32), (64, 32), (16, 4), (160, 16), (64, 4), (64, 2), (48, 1), (320, 32), (20, 5), (35, 7)]
+MAPS = [(1, 1), (3, 5), (8, 8), (7, 9)]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = abi.Ctx()
+    gn.bind(abi.lib())
+    yield c
+    c.close()
+
+
+def _params(ctx, Cn, seed, qp=QP):
+    rng = np.random.default_rng(seed)
+    gamma = rng.normal(1.0, 0.6, Cn).astype(f32)
+    beta = rng.normal(0.0, 0.6, Cn).astype(f32)
+    gamma[0] = 0.0
+    g, b = lr.affine(gamma, beta, qp[1], qp[2])
+    return gamma, beta, ctx.put(g), ctx.put(b)
+
+
+def _images(rng, n, Cn, h, w):
+    """n images of distinct content: uniform bytes, a narrow image, a ramp over channels"""
+    q = rng.integers(0, 256, (n, Cn, h, w), dtype=np.uint8)
+    if n > 1:
+        q[1] = (rng.integers(0, 9, (Cn, h, w)) + 60).astype(np.uint8)
+    if n > 2:
+        q[2] = ((np.arange(Cn).reshape(Cn, 1, 1) * 5 + rng.integers(0, 40, (Cn, h, w))) % 256).astype(np.uint8)
+    return q
+
+
+def _run(ctx, q, G, dg, db, qp=QP, relu=False, fallback=False, bi=0, bo=0, in_s8=0, out_s8=0, in_place=False, rng=None):
+    """one call of i8ie_groupnorm_u8_nhwc on [n, C, h, w] bytes; returns the interior as NCHW.  Checks the guard bytes of both
+    buffers, that the input and the result's border are untouched, and which kernels ran.  ws is filled with 0xFF."""
+    n, Cn, h, w = q.shape
+    s_in, _, zp_out, eps = qp
+    rng = rng or np.random.default_rng(0)
+    phys_in = rng.integers(0, 256, (n, h + 2 * bi, w + 2 * bi, Cn), dtype=np.uint8)   # a garbage border: it is never read
+    phys_in[:, bi:bi + h, bi:bi + w, :] = q.transpose(0, 2, 3, 1) ^ np.uint8(0x80 if in_s8 else 0)
+    di = abi.GuardedU8(ctx, phys_in.shape)
+    abi.ck(abi.lib().i8ie_memcpy_h2d(ctx.h, di.ptr, phys_in.ctypes.data_as(C.c_void_p), C.c_size_t(phys_in.nbytes)))
+    if in_place:
+        assert bi == bo and in_s8 == out_s8
+        do, phys_out = di, phys_in
+    else:
+        ring = np.uint8(zp_out ^ (0x80 if out_s8 else 0))
+        phys_out = np.full((n, h + 2 * bo, w + 2 * bo, Cn), ring, np.uint8)   # as i8ie_fill_border_u8 leaves it
+        do = abi.GuardedU8(ctx, phys_out.shape)
+        abi.ck(abi.lib().i8ie_memcpy_h2d(ctx.h, do.ptr, phys_out.ctypes.data_as(C.c_void_p), C.c_size_t(phys_out.nbytes)))
+    nbytes = abi.lib().i8ie_groupnorm_workspace_bytes(n, Cn, G, h, w)
+    assert nbytes == gn.workspace_bytes(n, Cn, G, h, w)
+    ws = abi.GuardedU8(ctx, (max(nbytes, 16),), fill=0xFF)
+    ctx.set_force_fallback(fallback)
+    try:
+        with ctx.launch_map() as names:
+            abi.ck(abi.lib().i8ie_groupnorm_u8_nhwc(ctx.h, di.ptr, bi, in_s8, do.ptr, bo, out_s8, n, Cn, G, h, w, dg.ptr, db.ptr, s_in, eps,
+                                                   1 if relu else 0, zp_out, ws.ptr if nbytes else None))
+    finally:
+        ctx.set_force_fallback(False)
+    got = do.get()
+    ws.get()
+    assert do.guards_ok() and di.guards_ok() and ws.guards_ok()
+    assert names == gn.kernels(Cn, h, w, fallback), (names, q.shape, fallback)
+    if not in_place:
+        assert np.array_equal(di.get(), phys_in)
+        do.free()
+    outside = got.copy()
+    outside[:, bo:bo + h, bo:bo + w, :] = phys_out[:, bo:bo + h, bo:bo + w, :]
+    assert np.array_equal(outside, phys_out)   # nothing but the interior was written
+    di.free(); ws.free()
+    return np.ascontiguousarray((got[:, bo:bo + h, bo:bo + w, :] ^ np.uint8(0x80 if out_s8 else 0)).transpose(0, 3, 1, 2))
+
+
+@pytest.mark.parametrize("Cn,G", GROUPS)
+def test_group_shapes_image_form_and_forced_fallback(ctx, Cn, G):
+    """n = 3 images of distinct content (a mix-up of images or groups changes bytes), every map, relu on / off, in place"""
+    rng = np.random.default_rng(500 + Cn + G)
+    gamma, beta, dg, db = _params(ctx, Cn, Cn)
+    spread = set()
+    for h, w in MAPS:
+        assert gn.form(Cn, h, w) == ("direct" if Cn % 16 else "image")
+        q = _images(rng, 3, Cn, h, w)
+        for relu in (False, True):
+            want = gn.group_norm_u8(q, G, QP[0], QP[3], gamma, beta, QP[1], QP[2], relu)
+            spread |= set(np.unique(want).tolist())
+            for fallback, in_place in ((False, False), (True, False), (False, True)):
+                got = _run(ctx, q, G, dg, db, relu=relu, fallback=fallback, in_place=in_place)
+                assert np.array_equal(got, want), (Cn, G, h, w, relu, fallback, in_place, np.argwhere(got != want)[:4])
+    assert len(spread) > 40
+    dg.free(); db.free()
+
+
+# (C, G, h, w, n): the LDS budget's edge (the same C, one pixel row apart), then split-form shapes whose pixel count is no
+# multiple of the chunk, with more chunks than one: cg = 2 (byte units), 10 (byte units, C / 16 no power of two), 4 (dword
+# units), 16 (item units)
+SPLIT = [(64, 32, 48, 32, 3), (64, 32, 49, 32, 3), (64, 32, 56, 56, 2), (160, 16, 25, 25, 2), (128, 32, 28, 28, 2), (256, 16, 20, 20, 2)]
+
+
+@pytest.mark.parametrize("Cn,G,h,w,n", SPLIT)
+def test_lds_budget_edge_and_split_form(ctx, Cn, G, h, w, n):
+    edge = (Cn, h, w) == (64, 48, 32)
+    assert gn.form(Cn, h, w) == ("image" if edge else "split") and (edge or gn.chunks(Cn, h, w) > 1)
+    assert edge or (h * w) % max(1, gn.CHUNK_BYTES // Cn) != 0
+    assert not edge or h * w * Cn == gn.IMAGE_BYTES
+    rng = np.random.default_rng(Cn + h)
+    gamma, beta, dg, db = _params(ctx, Cn, Cn + 1)
+    q = _images(rng, n, Cn, h, w)
+    for relu in (False, True):
+        want = gn.group_norm_u8(q, G, QP[0], QP[3], gamma, beta, QP[1], QP[2], relu)
+        assert len(np.unique(want)) > 40
+        for fallback, in_place in ((False, False), (True, False), (False, True)):
+            got = _run(ctx, q, G, dg, db, relu=relu, fallback=fallback, in_place=in_place)
+            assert np.array_equal(got, want), (relu, fallback, in_place, np.argwhere(got != want)[:4])
+    dg.free(); db.free()
+
+
+@pytest.mark.parametrize("Cn,G", [(16, 1), (32, 2)], ids=["image", "split"])
+def test_statistics_extremes_on_the_device(ctx, Cn, G):
+    """N = 65536 in both 16-byte forms and in the direct one"""
+    assert gn.form(Cn, 64, 64) == ("image" if Cn == 16 else "split")
+    for name, q in gn.extreme_images(Cn, G):
+        for qp in (QP, (f32(0.1), f32(0.05), 100, f32(1e-6))):
+            gamma, beta, dg, db = _params(ctx, Cn, 7 + Cn, qp)
+            want = gn.group_norm_u8(q, G, qp[0], qp[3], gamma, beta, qp[1], qp[2])
+            for fallback in (False, True):
+                got = _run(ctx, q, G, dg, db, qp=qp, fallback=fallback)
+                assert np.array_equal(got, want), (name, fallback, np.argwhere(got != want)[:4])
+            dg.free(); db.free()
+
+
+@pytest.mark.parametrize("Cn,G,h,w,n,fallback", [(32, 8, 3, 5, 2, False), (64, 32, 49, 32, 1, False), (20, 5, 3, 5, 2, False),
+                                                 (32, 8, 3, 5, 2, True)], ids=["image", "split", "direct", "fallback"])
+def test_layout_matrix_borders_rebias_relu_in_place_and_guards(ctx, Cn, G, h, w, n, fallback):
+    rng = np.random.default_rng(40 + Cn)
+    s_in, s_out, zp_out, eps = QP
+    gamma, beta, dg, db = _params(ctx, Cn, Cn)
+    q = _images(rng, n, Cn, h, w)
+    want = {relu: gn.group_norm_u8(q, G, s_in, eps, gamma, beta, s_out, zp_out, bool(relu)) for relu in (0, 1)}
+    for bi, bo, in_s8, out_s8, relu in itertools.product((0, 1, 2), (0, 1, 3), (0, 1), (0, 1), (0, 1)):
+        got = _run(ctx, q, G, dg, db, relu=bool(relu), fallback=fallback, bi=bi, bo=bo, in_s8=in_s8, out_s8=out_s8, rng=rng)
+        assert np.array_equal(got, want[relu]), (bi, bo, in_s8, out_s8, relu, np.argwhere(got != want[relu])[:4])
+        if bi == bo and in_s8 == out_s8:
+            got = _run(ctx, q, G, dg, db, relu=bool(relu), fallback=fallback, bi=bi, bo=bo, in_s8=in_s8, out_s8=out_s8, in_place=True, rng=rng)
+            assert np.array_equal(got, want[relu]), ("in place", bi, in_s8, relu)
+    dg.free(); db.free()
+
+
+def test_argument_errors_launch_nothing(ctx):
+    buf = ctx.put(np.zeros(8192, np.uint8))
+    p = buf.ptr.value
+    with ctx.launch_map() as names:
+        for Cn, G, h, w, s_in, eps, ws in ((0, 1, 2, 2, 0.1, 1e-5, p), (16, 3, 2, 2, 0.1, 1e-5, p), (16, 1, 64, 65, 0.1, 1e-5, p),
+                                           (16, 4, 2, 2, 0.0, 1e-5, p), (16, 4, 2, 2, 0.1, float("inf"), p), (64, 32, 56, 56, 0.1, 1e-5, None)):
+            assert abi.lib().i8ie_groupnorm_u8_nhwc(ctx.h, p, 0, 0, p, 0, 0, 1, Cn, G, h, w, p + 1024, p + 2048, s_in, eps, 0, 0, ws) == -1
+        assert abi.lib().i8ie_groupnorm_u8_nhwc(ctx.h, None, 0, 0, p, 0, 0, 1, 16, 4, 2, 2, p + 1024, p + 2048, 0.1, 1e-5, 0, 0, p) == -1
+        assert abi.lib().i8ie_groupnorm_u8_nhwc(ctx.h, p, -1, 0, p, 0, 0, 1, 16, 4, 2, 2, p + 1024, p + 2048, 0.1, 1e-5, 0, 0, p) == -1
+    assert names == {}
+    buf.free()
+
+
+@pytest.mark.parametrize("Cn,G,h,w", [(6, 3, 1, 1), (15, 5, 3, 7), (16, 1, 64, 64)], ids=["N2", "N63", "N65536"])
+def test_f32_against_float64(ctx, Cn, G, h, w):
+    """bound: groupnorm_ref.group_norm_f32_bound, derived from N and the roundings of the fp32 sequence"""
+    rng = np.random.default_rng(70 + Cn)
+    x = rng.normal(0.3, 2.0, (2, Cn, h, w)).astype(f32)
+    x[1, :Cn // G] = 2.5   # a constant row: var = 0, out = beta
+    gamma, beta = rng.normal(1, 0.5, Cn).astype(f32), rng.normal(0, 0.5, Cn).astype(f32)
+    dg, db = ctx.put(gamma), ctx.put(beta)
+    di, do = ctx.put(x), ctx.guarded(x.shape)
+    with ctx.launch_map() as names:
+        abi.ck(abi.lib().i8ie_groupnorm_f32(ctx.h, di.ptr, do.ptr, 2, Cn, G, h * w, dg.ptr, db.ptr, 1e-5))
+    got, ok = do.read()
+    assert ok and abi.GuardedOut.unwritten(got) == 0 and names == {"groupnorm_f32": 1}
+    err = np.abs(got.astype(np.float64) - gn.group_norm_f64(x, G, gamma, beta, 1e-5))
+    bound = gn.group_norm_f32_bound(x, G, gamma, beta, 1e-5)
+    print("groupnorm_f32 N=%d: max err %.3g, max err / bound %.3g" % ((Cn // G) * h * w, err.max(), (err / bound).max()))
+    assert (err <= bound).all()
+    assert np.array_equal(got[1, :Cn // G], np.broadcast_to(beta[:Cn // G].reshape(-1, 1, 1), (Cn // G, h, w)))
+    for d in (di, do, dg, db):
+        d.free()
+
+
+# ---- the Python surface ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def i8ie():
+    import i8ie as mod
+
+    return mod
+
+
+def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
+    rng = np.random.default_rng(seed)
+    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
+    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
+    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
+    L.set_output_qparams(*qp)
+    L.convert()
+    return L
+
+
+def _conv_ref(L, q, s_in, zp_in, pad=0, stride=1):
+    s_out, zp_out = L.output_qparams()
+    return gr.conv2d_grouped(q, L.layer.q_weight(), L.layer.q_bias(), 1, stride, pad, f32(s_in), zp_in, L.weight_scale(), f32(s_out), zp_out)[0]
+
+
+def _gn(i8ie, groups, c, seed, qp, eps=1e-5):
+    rng = np.random.default_rng(seed)
+    L = i8ie.GroupNorm(groups, c, eps)
+    w, b = rng.uniform(0.5, 1.5, c).astype(f32), rng.uniform(-0.3, 0.3, c).astype(f32)
+    L.load_weight(w)
+    L.load_bias(b)
+    L.set_output_qparams(*qp)
+    L.convert()
+    return L, w, b
+
+
+def _counted(make):
+    """{kernel name: launches} of make() after one warm-up call (tests/test_gpu_layernorm.py)"""
+    import _CXX_i8ie as cx
+
+    for t in make():
+        t.numpy()
+    cx.synchronize()
+    cx.profile_start()
+    try:
+        for t in make():
+            t.data.layout()
+    finally:
+        prof = cx.profile_stop()
+    launches = {}
+    for k, v in prof.items():
+        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
+    return launches
+
+
+def test_surface_shapes_and_errors(i8ie):
+    rng = np.random.default_rng(80)
+    w, b = rng.uniform(0.5, 1.5, 12).astype(f32), rng.uniform(-0.3, 0.3, 12).astype(f32)
+    for shape in ((2, 12, 3, 4), (5, 12)):
+        xf = rng.uniform(-3, 3, shape).astype(f32)
+        q = i8ie.quantize(i8ie.tensor(xf), 0.025, 127)
+        qv = q.numpy()
+        r = i8ie.relu(i8ie.group_norm(q, 3, w, b, 1e-5, 0.02, 120))
+        assert r.shape == shape and r.scale == pytest.approx(0.02) and r.zero_point == 120
+        assert np.array_equal(r.numpy(), gn.group_norm_u8(qv, 3, f32(0.025), f32(1e-5), w, b, f32(0.02), 120, True)), shape
+        r = i8ie.group_norm(q, 12, scale=0.02, zero_point=120)   # weight, bias default to ones, zeros; InstanceNorm
+        assert np.array_equal(r.numpy(), gn.group_norm_u8(qv, 12, f32(0.025), f32(1e-5), np.ones(12, f32), np.zeros(12, f32), f32(0.02), 120))
+        layer, lw, lb = _gn(i8ie, 1, 12, 4, (0.03, 131))
+        assert np.array_equal(layer(q).numpy(), gn.group_norm_u8(qv, 1, f32(0.025), f32(1e-5), lw, lb, f32(0.03), 131))
+        got = i8ie.group_norm(i8ie.tensor(xf), 3, w, b).numpy()
+        assert got.shape == shape
+        assert (np.abs(got - gn.group_norm_f64(xf, 3, w, b, 1e-5).reshape(shape)) <= gn.group_norm_f32_bound(xf, 3, w, b, 1e-5).reshape(shape)).all()
+    q = i8ie.quantize(i8ie.tensor(rng.uniform(-3, 3, (2, 12, 3, 4)).astype(f32)), 0.025, 127)
+    g = i8ie.GroupNorm(3, 12)
+    g10, _, _ = _gn(i8ie, 2, 10, 1, (0.02, 1))
+    bad = [lambda: g(q),                                                     # not converted
+           lambda: g10(q),                                                   # c != num_channels
+           lambda: i8ie.group_norm(q.reshape(-1), 1, None, None, 1e-5, 0.02, 1),              # rank 1
+           lambda: i8ie.group_norm(q.reshape(2, 12, 12), 3, None, None, 1e-5, 0.02, 1),       # rank 3
+           lambda: i8ie.group_norm(q.reshape(1, 2, 12, 3, 4), 1, None, None, 1e-5, 0.02, 1),  # rank 5
+           lambda: i8ie.group_norm(q, 5, w, b, 1e-5, 0.02, 1),               # C % G
+           lambda: i8ie.group_norm(q, 3, w[:11], b, 1e-5, 0.02, 1),
+           lambda: i8ie.group_norm(q, 3, w, b, 0.0, 0.02, 1),
+           lambda: i8ie.group_norm(q, 3, w, b, 1e-5, 0.0, 1),
+           lambda: i8ie.group_norm(q, 3, w, b, 1e-5, 0.02, 256)]
+    for f in bad:
+        with pytest.raises(RuntimeError):
+            f()
+    for kw in ({}, {"scale": 0.2}, {"zero_point": 3}):
+        with pytest.raises(TypeError):
+            i8ie.group_norm(q, 3, w, b, **kw)
+
+
+@pytest.mark.parametrize("h,w,form", [(6, 5, "image"), (80, 80, "split")])
+def test_launch_counts_borders_and_bytes(i8ie, h, w, form):
+    """conv -> GN -> relu -> padded conv is three launches in the image form and four in the split form (the GN reads the conv's
+    NHWC result as it lies and writes the border and re-bias the next conv asks for); nothing converts a layout, re-biases,
+    applies a relu or fills a border in between"""
+    rng = np.random.default_rng(90)
+    n, c = 2, 16
+    assert gn.form(c, h, w) == form
+    stem0 = _conv(i8ie, 3, c, 3, 1, 9, (0.05, 128))
+    stem1 = _conv(i8ie, c, c, 3, 1, 11, (0.05, 128))
+    stem = _conv(i8ie, c, c, 3, 1, 1, (0.05, 120))
+    g, gam, bet = _gn(i8ie, 4, c, 2, (0.02, 125))
+    tail = _conv(i8ie, c, 16, 3, 1, 5, (0.07, 100))
+    q = i8ie.quantize(i8ie.tensor(rng.uniform(-3, 3, (n, 3, h, w)).astype(f32)), 0.025, 127)
+    x = i8ie.relu(stem1(i8ie.relu(stem0(q))))
+
+    launches = _counted(lambda: [tail(i8ie.relu(g(stem(x))))])
+    print(launches)
+    mine = {k: v for k, v in launches.items() if k.startswith("groupnorm")}
+    assert mine == gn.kernels(c, h, w) and sum(launches.values()) == (3 if form == "image" else 4), launches
+    for k in launches:
+        assert not k.startswith(("relu_u8", "rebias", "fill_border", "reborder", "layout_")), launches
+    xv = x.numpy()
+    yv = _conv_ref(stem, xv, 0.05, 128, pad=1)
+    lv = gn.group_norm_u8(yv, 4, f32(0.05), f32(1e-5), gam, bet, f32(0.02), 125)
+    assert len(np.unique(lv)) > 40
+    assert np.array_equal(g(stem(x)).numpy(), lv)
+    assert np.array_equal(tail(i8ie.relu(g(stem(x)))).numpy(), _conv_ref(tail, np.maximum(lv, 125), 0.02, 125, pad=1))
+    # an NCHW input (user-made) goes through one layout conversion
+    qn = i8ie.quantize(i8ie.tensor(rng.uniform(-3, 3, (n, c, h, w)).astype(f32)), 0.025, 127)
+    assert np.array_equal(g(qn).numpy(), gn.group_norm_u8(qn.numpy(), 4, f32(0.025), f32(1e-5), gam, bet, f32(0.02), 125))
+
+
+@pytest.mark.parametrize("shape,groups", [((5, 20, 4, 3), 5), ((2, 16, 80, 80), 4)], ids=["direct", "split"])
+def test_calibrated_like_a_layer_round_trips_and_replays(i8ie, tmp_path, shape, groups):
+    import _CXX_i8ie as cx
+    from int8inferenceengine_amd.graph import GraphedForward
+
+    c = shape[1]
+    rng = np.random.default_rng(8)
+    a = rng.normal(0.2, 1.5, shape).astype(f32)
+    w, b = rng.uniform(0.5, 1.5, c).astype(f32), rng.uniform(-0.3, 0.3, c).astype(f32)
+
+    class Net(i8ie.Module):
+        def __init__(self):
+            super().__init__()
+            self.gn1 = i8ie.GroupNorm(groups, c)
+
+        def forward(self, x):
+            return self.gn1(x)
+
+    cx.set_calibration_mode("host")
+    cx.set_calibration_seed(7)
+    try:
+        net = Net()
+        net.load({"gn1.weight": w, "gn1.bias": b})
+        net.prepare()
+        got = net(i8ie.tensor(a)).numpy()
+        net.convert(per_channel=True)   # (accepted and ignored)
+        want = tuple(cx.calibrator_range([got.ravel()], 1.0))
+    finally:
+        cx.set_calibration_mode("auto")
+        cx.set_calibration_seed(-1)
+    assert (np.abs(got - gn.group_norm_f64(a, groups, w, b, 1e-5)) <= gn.group_norm_f32_bound(a, groups, w, b, 1e-5)).all()
+    assert net.gn1.layer.is_quantized() and net.gn1.output_qparams() == want and want[0] != 1.0 and not net.gn1.is_per_channel()
+    sd = net.quantized_state_dict()
+    assert list(sd) == ["gn1.weight", "gn1.bias", "gn1.qparams"]
+    assert sd["gn1.weight"].dtype == np.float32 and np.array_equal(sd["gn1.weight"], w) and np.array_equal(sd["gn1.bias"], b)
+    assert sd["gn1.qparams"].tolist() == [0.0, want[0], float(want[1])]
+    path = str(tmp_path / "gn.npz")
+    net.save_quantized(path)
+    other = Net()
+    other.load_quantized_file(path)
+    assert other.gn1.output_qparams() == want and other.is_quant
+    x = rng.normal(0.2, 1.5, shape).astype(f32)
+    r1, r2 = net(i8ie.tensor(x)).numpy(), other(i8ie.tensor(x)).numpy()
+    qx = orc.quantize(x, sr.pipeline.INPUT_SCALE, sr.pipeline.INPUT_ZP)
+    ref = orc.dequantize(gn.group_norm_u8(qx, groups, sr.pipeline.INPUT_SCALE, f32(1e-5), w, b, f32(want[0]), want[1]), f32(want[0]), want[1])
+    assert np.array_equal(r1.view(np.uint32), ref.view(np.uint32)) and np.array_equal(r2.view(np.uint32), ref.view(np.uint32))
+    # set_output_qparams on a converted layer re-derives g and b
+    other.gn1.set_output_qparams(0.05, 99)
+    ref2 = orc.dequantize(gn.group_norm_u8(qx, groups, sr.pipeline.INPUT_SCALE, f32(1e-5), w, b, f32(0.05), 99), f32(0.05), 99)
+    assert np.array_equal(other(i8ie.tensor(x)).numpy().view(np.uint32), ref2.view(np.uint32))
+    g = GraphedForward(net, i8ie.tensor(x).prefetch())   # (the split form takes its workspace inside the capture)
+    for _ in range(2):
+        assert np.array_equal(g().numpy().view(np.uint32), ref.view(np.uint32))
+
+
+def test_calibration_on_the_device(i8ie):
+    """the device sampler sees the GroupNorm's FP32 result like a layer's: its (scale, zero_point) is close to the host
+    sampler's (the two draw different samples; the closeness asked is tests/test_gpu_calibration_device.py's)"""
+    import _CXX_i8ie as cx
+
+    rng = np.random.default_rng(5)
+    a = rng.normal(0.2, 1.5, (4, 16, 6, 6)).astype(f32)
+    got = {}
+    for mode in ("host", "device"):
+        cx.set_calibration_mode(mode)
+        cx.set_calibration_seed(11)
+        try:
+            g = i8ie.GroupNorm(4, 16)
+            g.prepare()
+            g(i8ie.tensor(a)).numpy()
+            g.convert()
+        finally:
+            cx.set_calibration_mode("auto")
+            cx.set_calibration_seed(-1)
+        assert g.layer.is_quantized()
+        got[mode] = g.output_qparams()
+    (sh, zh), (sd, zd) = got["host"], got["device"]
+    assert sh != 1.0 and sd != 1.0 and 0.5 < sd / sh < 2.0 and abs(int(zd) - int(zh)) <= 64, got
+
+
+# ---- the test network ----------------------------------------------------------------------------------------------------
+# 3x32x32 -> conv 3x3 s2, relu, max-pool 2/2 (16 channels, 8x8) -> GN residual block at 16 channels [conv, GN(4), relu, conv (a
+# bordered consumer of the GN), GN(16) = InstanceNorm] + skip, relu -> conv 3x3 s2 to 20 channels (4x4), GN(5), relu -> GN
+# residual block at 20 channels [conv, GN(1), relu, conv, GN(10)] + skip -> the SiLU block [GN(4), x * sigmoid(x) (two consumers
+# of one pending GN), conv 3x3 with padding, packed 1x1 conv 20 -> 60, Attention(2) at d = 10, 1x1 conv] + skip -> relu, global
+# average pool, fc.  20 channels are no multiple of 16, so those GroupNorms take the direct form; the 16-channel ones the image form.
+NET_INPUT = (3, 32, 32)
+NET_HEADS = 2
+NET_LAYERS = {
+    "c1": ("conv", 3, 16, 3, 2, 1),
+    "a_c1": ("conv", 16, 16, 3, 1, 1), "a_gn1": ("gn", 4, 16), "a_c2": ("conv", 16, 16, 3, 1, 1), "a_gn2": ("gn", 16, 16),
+    "down": ("conv", 16, 20, 3, 2, 1), "d_gn": ("gn", 5, 20),
+    "b_c1": ("conv", 20, 20, 3, 1, 1), "b_gn1": ("gn", 1, 20), "b_c2": ("conv", 20, 20, 3, 1, 1), "b_gn2": ("gn", 10, 20),
+    "s_gn": ("gn", 4, 20), "s_c": ("conv", 20, 20, 3, 1, 1), "s_qkv": ("conv", 20, 60, 1, 1, 0), "s_proj": ("conv", 20, 20, 1, 1, 0),
+    "fc": ("fc", 20, 10)}
+NET_JOINS = ("a_add", "b_add", "s_sig", "s_mul", "s_attn", "s_add")
+NET_TRACED = ("pool", "a_gn1", "a_gn2", "a_add", "d_gn", "b_gn1", "b_gn2", "b_add", "s_gn", "s_sig", "s_mul", "s_c", "s_attn", "s_add", "gap")
+WEIGHT_SEED, CALIB_SEED, INPUT_SEED = 42, 99, 5
+_NET = {}
+
+
+def _net_state_dict():
+    """He-uniform weights and U(-1, 1) / sqrt(fan_in) biases, gamma from U(0.5, 1.5), beta from U(-0.3, 0.3); the 1 / sqrt(d) of
+    the attention is folded into the query third of s_qkv"""
+    rng = np.random.default_rng(WEIGHT_SEED)
+    sd = {}
+    for attr, L in NET_LAYERS.items():
+        if L[0] == "gn":
+            sd[attr + ".weight"] = rng.uniform(0.5, 1.5, L[2]).astype(f32)
+            sd[attr + ".bias"] = rng.uniform(-0.3, 0.3, L[2]).astype(f32)
+            continue
+        shape = (L[2], L[1], L[3], L[3]) if L[0] == "conv" else (L[2], L[1])
+        fan_in = int(np.prod(shape[1:]))
+        fold = np.ones(shape[0], np.float64)
+        if attr == "s_qkv":
+            fold[:20] = 1.0 / np.sqrt(20 // NET_HEADS)
+        w = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / fan_in)
+        sd[attr + ".weight"] = (w * fold.reshape((-1,) + (1,) * (len(shape) - 1))).astype(f32)
+        sd[attr + ".bias"] = (rng.uniform(-1, 1, shape[0]) / np.sqrt(fan_in) * fold).astype(f32)
+    return sd
+
+
+def _net_input(batch, seed=INPUT_SEED):
+    import mha_ref as mr
+
+    return mr.net_input(batch, seed)   # (the same 3x32x32 normalised-image-like input)
+
+
+def _net_quantize_layers(sd, per_channel):
+    import pc_pipeline as pcp
+
+    rule = pcp.quantize_weight_pc if per_channel else orc.quantize_weight
+    return {a: (sd[a + ".weight"], sd[a + ".bias"]) if L[0] == "gn" else tuple(rule(sd[a + ".weight"], sd[a + ".bias"]))
+            for a, L in NET_LAYERS.items()}
+
+
+def _net_forward(x, qlayers, qp, score_qp, per_channel, trace):
+    """the numpy walk: float32 logits; trace receives the bytes of NET_TRACED"""
+    import act_ref
+    import add_ref
+    import avgpool_ref as apr
+    import mha_ref as mr
+    import mul_ref
+    import pc_pipeline as pcp
+
+    def out_of(attr):
+        return f32(qp[attr][0]), int(qp[attr][1])
+
+    def layer(attr, cur):
+        (q, s, zp), L, (s_o, zp_o) = cur, NET_LAYERS[attr], out_of(attr)
+        if L[0] == "gn":
+            return (gn.group_norm_u8(q, L[1], s, f32(1e-5), qlayers[attr][0], qlayers[attr][1], s_o, zp_o), s_o, zp_o)
+        qw, qb, s_w = qlayers[attr]
+        if L[0] == "conv":
+            f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
+            return (f(q, qw, qb, 1, L[4], L[5], s, zp, s_w, s_o, zp_o)[0], s_o, zp_o)
+        f = pcp.linear_pc if per_channel else orc.linear
+        return (f(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_o, zp_o)[0], s_o, zp_o)
+
+    def add(attr, a, b):
+        s_o, zp_o = out_of(attr)
+        return (add_ref.add_u8(a[0], a[2], a[1], b[0], b[2], b[1], s_o, zp_o, relu=False), s_o, zp_o)
+
+    def relu(cur):
+        return (orc.relu(cur[0], cur[2]), cur[1], cur[2])
+
+    def kept(name, cur):
+        trace[name] = cur[0]
+        return cur
+
+    cur = (orc.quantize(x, sr.pipeline.INPUT_SCALE, sr.pipeline.INPUT_ZP), f32(sr.pipeline.INPUT_SCALE), sr.pipeline.INPUT_ZP)
+    cur = relu(layer("c1", cur))
+    cur = kept("pool", (orc.max_pool2d(cur[0], 2, 2), cur[1], cur[2]))
+    y = relu(kept("a_gn1", layer("a_gn1", layer("a_c1", cur))))
+    y = kept("a_gn2", layer("a_gn2", layer("a_c2", y)))
+    cur = relu(kept("a_add", add("a_add", y, cur)))
+    cur = relu(kept("d_gn", layer("d_gn", layer("down", cur))))
+    y = relu(kept("b_gn1", layer("b_gn1", layer("b_c1", cur))))
+    y = kept("b_gn2", layer("b_gn2", layer("b_c2", y)))
+    cur = kept("b_add", add("b_add", y, cur))
+    g = kept("s_gn", layer("s_gn", cur))
+    s_o, zp_o = out_of("s_sig")
+    sig = kept("s_sig", (act_ref.act_u8(g[0], "sigmoid", f32(0.0), g[1], g[2], s_o, zp_o), s_o, zp_o))
+    s_o, zp_o = out_of("s_mul")
+    y = kept("s_mul", (mul_ref.mul_u8(g[0], g[2], g[1], sig[0], sig[2], sig[1], s_o, zp_o), s_o, zp_o))
+    y = kept("s_c", layer("s_c", y))
+    qkv = layer("s_qkv", y)
+    (s_s, zp_s), (s_o, zp_o) = (f32(score_qp[0]), int(score_qp[1])), out_of("s_attn")
+    O = mr.attention_u8(mr.tokens(qkv[0]), None, None, NET_HEADS, qkv[1], qkv[2], qkv[1], qkv[2], qkv[1], qkv[2], s_s, zp_s, s_o, zp_o)[3]
+    y = kept("s_attn", (mr.pixels(O, 4, 4), s_o, zp_o))
+    cur = relu(kept("s_add", add("s_add", layer("s_proj", y), cur)))
+    cur = kept("gap", (apr.global_avg_pool2d_u8(cur[0]), cur[1], cur[2]))
+    return orc.dequantize(*layer("fc", cur))
+
+
+def _make_net(i8ie):
+    class GnNet(i8ie.Module):
+        def __init__(self):
+            super().__init__()
+            for attr, L in NET_LAYERS.items():
+                if L[0] == "conv":
+                    setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5]))
+                elif L[0] == "gn":
+                    setattr(self, attr, i8ie.GroupNorm(L[1], L[2]))
+                else:
+                    setattr(self, attr, i8ie.Linear(L[1], L[2]))
+            self.a_add, self.b_add, self.s_add = i8ie.Add(), i8ie.Add(), i8ie.Add()
+            self.s_sig, self.s_mul, self.s_attn = i8ie.Activation("sigmoid"), i8ie.Mul(), i8ie.Attention(NET_HEADS)
+            self.trace = None
+
+        def keep(self, name, t):
+            if self.trace is not None:
+                self.trace[name] = t.numpy()
+            return t
+
+        def forward(self, x):
+            x = self.keep("pool", i8ie.max_pool2d(i8ie.relu(self.c1(x)), 2, 2))
+            y = i8ie.relu(self.keep("a_gn1", self.a_gn1(self.a_c1(x))))
+            y = self.keep("a_gn2", self.a_gn2(self.a_c2(y)))
+            x = i8ie.relu(self.keep("a_add", self.a_add(y, x)))
+            x = i8ie.relu(self.keep("d_gn", self.d_gn(self.down(x))))
+            y = i8ie.relu(self.keep("b_gn1", self.b_gn1(self.b_c1(x))))
+            y = self.keep("b_gn2", self.b_gn2(self.b_c2(y)))
+            x = self.keep("b_add", self.b_add(y, x))
+            g = self.keep("s_gn", self.s_gn(x))
+            y = self.keep("s_mul", self.s_mul(g, self.keep("s_sig", self.s_sig(g))))   # SiLU: x * sigmoid(x)
+            y = self.keep("s_c", self.s_c(y))
+            y = self.keep("s_attn", self.s_attn(self.s_qkv(y)))
+            x = i8ie.relu(self.keep("s_add", self.s_add(self.s_proj(y), x)))
+            x = self.keep("gap", i8ie.global_avg_pool2d(x))
+            return self.fc(x.reshape(-1, 20))
+
+    return GnNet()
+
+
+def _net(i8ie, per_channel):
+    """(net, qlayers, qp, score_qp): calibrated on the device once per weight mode; every quantisation parameter is read from
+    the product"""
+    import _CXX_i8ie as cx
+
+    if per_channel not in _NET:
+        sd = _net_state_dict()
+        net = _make_net(i8ie)
+        net.load(sd)
+        cx.set_calibration_mode("device")
+        cx.set_calibration_seed(7)
+        try:
+            net.prepare()
+            net(i8ie.tensor(_net_input(8, CALIB_SEED)))
+            net.convert(per_channel)
+        finally:
+            cx.set_calibration_mode("auto")
+            cx.set_calibration_seed(-1)
+        qp = {a: getattr(net, a).output_qparams() for a in list(NET_LAYERS) + list(NET_JOINS)}
+        _NET[per_channel] = (net, _net_quantize_layers(sd, per_channel), qp, net.s_attn.score_qparams())
+    return _NET[per_channel]
+
+
+def _same(got, want):
+    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+@pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
+@pytest.mark.parametrize("batch", [1, 5])
+def test_gn_net_bit_exact(i8ie, batch, per_channel, tmp_path):
+    """logits and every traced tensor against the numpy walk: eager, under force-fallback, replayed as one HIP graph, and from a
+    fresh net that loaded what save_quantized() wrote"""
+    import _CXX_i8ie as cx
+    from int8inferenceengine_amd.graph import GraphedForward
+
+    net, qlayers, qp, sq = _net(i8ie, per_channel)
+    assert all(s > 0 and s != 1.0 for s, _ in list(qp.values()) + [sq]), (qp, sq)   # everything was calibrated
+    x = _net_input(batch)
+    trace = {}
+    want = _net_forward(x, qlayers, qp, sq, per_channel, trace)
+    assert want.shape == (batch, 10) and len(np.unique(want)) > 1
+    for k in ("a_gn1", "a_gn2", "d_gn", "b_gn1", "b_gn2", "s_gn"):   # the expected bytes discriminate
+        assert len(np.unique(trace[k])) >= 32 and ((trace[k] == 0) | (trace[k] == 255)).mean() < 0.05, k
+    assert _same(net(i8ie.tensor(x)).numpy(), want), "eager"
+    net.trace = {}
+    try:
+        assert _same(net(i8ie.tensor(x)).numpy(), want), "traced"
+        mine = net.trace
+    finally:
+        net.trace = None
+    assert sorted(mine) == sorted(NET_TRACED) == sorted(trace)
+    for k in NET_TRACED:
+        assert mine[k].shape == trace[k].shape and np.array_equal(mine[k], trace[k]), k
+    cx.force_fallback(True)
+    try:
+        fb = net(i8ie.tensor(x)).numpy()
+    finally:
+        cx.force_fallback(False)
+    assert _same(fb, want), "force_fallback"
+    g = GraphedForward(net, i8ie.tensor(x).prefetch())
+    for _ in range(2):
+        assert _same(g().numpy(), want), "graph replay"
+    path = str(tmp_path / "gn_net.npz")
+    net.save_quantized(path)
+    fresh = _make_net(i8ie)
+    fresh.load_quantized_file(path)
+    assert {a: getattr(fresh, a).output_qparams() for a in qp} == qp and fresh.s_attn.score_qparams() == sq
+    assert _same(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
+
+
+def test_gn_net_kernels_and_launches(i8ie):
+    """the two GroupNorms of 16 channels run in the image form and the four of 20 channels in the direct form, one launch
+    each, with the relus behind them folded in (the one relu launch left is c1's NCHW route).  The launches between the
+    20-channel layers belong to the existing operand machinery, which tests/test_gpu_operand_rules.py pins."""
+    import _CXX_i8ie as cx
+
+    net = _net(i8ie, False)[0]
+    x = _net_input(5)
+    net(i8ie.tensor(x)).numpy()
+    cx.synchronize()
+    cx.profile_start()
+    try:
+        net(i8ie.tensor(x)).numpy()
+    finally:
+        prof = cx.profile_stop()
+    launches = {}
+    for k, v in prof.items():
+        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
+    print(launches)
+    assert launches.get("groupnorm_u8_image") == 2 and launches.get("groupnorm_u8_direct") == 4, launches
+    assert launches.get("relu_u8", 0) <= 1, launches
