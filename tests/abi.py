@@ -393,6 +393,16 @@ class Ctx:
                 name = e.name.decode().split("|")[0]
                 got[name] = got.get(name, 0) + int(e.launches)
 
+    def kernels_run(self, fn):
+        """(fn(), the names -- cut at '|' -- of the kernels that ran on this ctx inside it, one per (kernel, problem size))"""
+        ck(lib().i8ie_profile_start(self.h, 0))
+        try:
+            res = fn()
+        finally:
+            ents, cnt = (ProfEntry * 64)(), C.c_int(0)
+            ck(lib().i8ie_profile_stop(self.h, ents, 64, C.byref(cnt)))
+        return res, [e.name.decode().split("|")[0] for e in ents[:cnt.value]]
+
     def layer_queries(self, L, m, h, w, pool_k, pool_s):
         """The layout / pool negotiation answers of a layer handle at batch m, input h x w, with this pool behind it."""
         fuses, reads, stores, f32, pref = (C.c_int(-1) for _ in range(5))
@@ -507,9 +517,6 @@ class Ctx:
         il = (2 if in_s8 else 1) if in_nhwc else 0
         ol = (2 if out_s8 else 1) if out_nhwc else 0
 
-        class _Entry(C.Structure):
-            _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double),
-                        ("total_ops", C.c_double), ("total_bytes", C.c_double)]
         ck(lib().i8ie_ctx_set_option(self.h, 2, variant))
         if names is not None:
             ck(lib().i8ie_profile_start(self.h, 0))
@@ -525,7 +532,7 @@ class Ctx:
         finally:
             ck(lib().i8ie_ctx_set_option(self.h, 2, 0))
             if names is not None:
-                ents = (_Entry * 64)()
+                ents = (ProfEntry * 64)()
                 cnt = C.c_int(0)
                 ck(lib().i8ie_profile_stop(self.h, ents, 64, C.byref(cnt)))
                 names.extend(ents[i].name.decode().split("|")[0] for i in range(cnt.value))

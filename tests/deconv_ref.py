@@ -254,11 +254,6 @@ def create(lib, ctx, d, case):
     return L
 
 
-class _Entry(C.Structure):
-    _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double), ("total_ops", C.c_double),
-                ("total_bytes", C.c_double)]
-
-
 def run_handle(ctx, case, relu, pool=None, in_s8=False, out_s8=False, **over):
     """the case through i8ie_layer_forward_fused (or _pool) on a transposed handle, output and accumulators in guarded
     regions.  Returns dict(out NCHW, acc, phys (the whole physical output, a re-bias undone), ok (no guard byte changed),
@@ -291,7 +286,7 @@ def run_handle(ctx, case, relu, pool=None, in_s8=False, out_s8=False, **over):
             abi.ck(lib.i8ie_layer_forward_pool(L, di.ptr, il, c.ib, c.m, c.h, c.w, C.c_float(S_IN), C.c_uint8(c.zp_in), 1 if relu else 0,
                                                pool[0], pool[1], out.ptr, ol, c.ob, acc.ptr))
     finally:
-        ents, cnt = (_Entry * 64)(), C.c_int(0)
+        ents, cnt = (abi.ProfEntry * 64)(), C.c_int(0)
         abi.ck(lib.i8ie_profile_stop(ctx.h, ents, 64, C.byref(cnt)))
         names.extend(ents[i].name.decode().split("|")[0] for i in range(cnt.value))
         ctx.set_force_fallback(False)

@@ -10,19 +10,14 @@ import hashlib
 
 import numpy as np
 
+from synth import he_weights
+
 
 def sha(*arrays):
     h = hashlib.sha256()
     for a in arrays:
         h.update(np.ascontiguousarray(a).tobytes())
     return h.hexdigest()
-
-
-def he_weights(rng, shape):
-    fan_in = int(np.prod(shape[1:]))
-    w = rng.uniform(-1, 1, shape).astype(np.float32) * np.float32(np.sqrt(6.0 / fan_in))
-    b = rng.uniform(-1, 1, shape[0]).astype(np.float32) * np.float32(1.0 / np.sqrt(fan_in))
-    return w, b
 
 
 def redraw(seed, in_shape, w_shape):

@@ -2,9 +2,8 @@
 with what tests/spec_ref.py needs to restate it, and the comparison of the product's output with the expected bytes -- eager,
 under the force-fallback option, replayed as a HIP graph, and after a save / load round trip.  A test keeps what is its own:
 its input, its traced tensors and their limits, its shapes and counts."""
-import numpy as np
-
 import spec_ref as sr
+from support import same_bits
 
 _CALIBRATED = {}
 
@@ -26,10 +25,6 @@ def calibrated(name, per_channel, calib_images=None):
     return _CALIBRATED[key]
 
 
-def _same(got, want):
-    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-
-
 def check_bit_exact(i8ie, net, name, x, want, *, fallback=False, graph=False, reload_dir=None, expect_jqp=None):
     """net(x) is `want` bit for bit; returns the eager output.  fallback: also under cx.force_fallback(True).  graph: also two
     replays of the forward captured as one HIP graph.  reload_dir: also a fresh wl.build(name) that loaded what
@@ -39,25 +34,25 @@ def check_bit_exact(i8ie, net, name, x, want, *, fallback=False, graph=False, re
     from int8inferenceengine_amd.graph import GraphedForward
 
     got = net(i8ie.tensor(x)).numpy()
-    assert _same(got, want), "eager"
+    assert same_bits(got, want), "eager"
     if fallback:
         cx.force_fallback(True)
         try:
             fb = net(i8ie.tensor(x)).numpy()
         finally:
             cx.force_fallback(False)
-        assert _same(fb, want), "force_fallback"
+        assert same_bits(fb, want), "force_fallback"
     if graph:
         g = GraphedForward(net, i8ie.tensor(x).prefetch())
         for _ in range(2):
-            assert _same(g().numpy(), want), "graph replay"
+            assert same_bits(g().numpy(), want), "graph replay"
     if reload_dir is not None:
         path = str(reload_dir / (name + ".npz"))
         net.save_quantized(path)
         fresh = wl.build(name)
         fresh.load_quantized_file(path)
         assert {a: getattr(fresh, a).output_qparams() for a in expect_jqp or {}} == (expect_jqp or {})
-        assert _same(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
+        assert same_bits(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
     return got
 
 

@@ -30,6 +30,7 @@ import orc
 import pc_pipeline as pcp
 import pipeline
 import upsample_ref as ur
+from layer_cases import range_qparams  # (the calibrator's rule on a real-valued range)
 
 f32 = np.float32
 OPS = frozenset(["layer", "relu", "pool", "avgpool", "gap", "save", "branch", "add", "mul", "concat", "act", "upsample", "flatten",
@@ -144,16 +145,6 @@ def traces(*callbacks):
             t(op, out, operands)
 
     return trace
-
-
-def range_qparams(lo, hi):
-    """the calibrator's rule (src/calibrator.cc:24-37 at quantile 1) on a real-valued range"""
-    lo, hi = min(float(lo), 0.0), max(float(hi), 0.0)
-    if hi - lo < 1e-12:
-        return f32(1.0), 0
-    zp = int(255 * (0 - lo) / (hi - lo))
-    scale = (hi - lo) / 255 if zp == 0 else (0 - lo) / zp
-    return f32(scale), zp
 
 
 def fp32_qparams(networks_entry, state_dict, x):

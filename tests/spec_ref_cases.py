@@ -5,7 +5,6 @@ not a conftest.  tests/golden/make_spec_ref_digests.py records the table, tests/
   FAMILY          which op family's tests own a network (it decides what is traced, and whether the float64 stand-in for
                   calibration or synthetic parameters give the output (scale, zero_point)s)
   case(...)       the digests of one (network, per_channel): logits, every traced tensor, and the stand-in's parameters"""
-import hashlib
 import zlib
 
 import numpy as np
@@ -16,6 +15,7 @@ import layernorm_ref as lnr
 import mul_ref as mr
 import spec_ref as sr
 import upsample_ref as ur
+from support import sha
 
 BATCH = 2
 FAMILY = {
@@ -40,10 +40,6 @@ def synthetic_qparams(attrs):
         h = zlib.crc32(a.encode())
         out[a] = (float(np.float32(0.02 + (h % 1000) * 4e-5)), 64 + (h >> 10) % 128)
     return out
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def trace_digests(trace):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import abi
+from support import i8ie  # noqa: F401
 
 
 def test_library_exports_every_declared_symbol():
@@ -43,14 +44,6 @@ def test_quantize_weight_host_entry_matches_oracle(orc):
 
 
 # ---- the Python surface (reference i8ie/*.py, unittest/test_refcount.py, test_tensor_ops.py) ----
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
-
-
 def test_surface_names(i8ie):
     for name in ["tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize", "Linear", "Conv2d", "Tensor",
                  "Module"]:

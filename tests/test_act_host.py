@@ -11,6 +11,8 @@ import abi
 import act_ref as ar
 import pinned_networks as pn
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 
 f32 = np.float32
 KINDS = sorted(ar.KINDS, key=ar.KINDS.get)
@@ -38,9 +40,7 @@ PARAM_SETS = _param_sets()
 SLOPES = [0.0, 0.01, 1.0, -0.5]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return ar.bind(abi.lib())
+lib = support.lib_fixture(ar)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -133,14 +133,6 @@ def test_device_entries_check_arguments_before_any_device_call(lib):
     assert f(ctx, 0, 0.0, C.c_void_p(18), one, 4) == -1 and b"aligned" in lib.i8ie_last_error()
     assert f(ctx, 0, 0.0, one, one, 0) == 0
     del keep
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def test_surface_names_and_argument_rules(i8ie):

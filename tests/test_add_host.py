@@ -7,11 +7,8 @@ import pytest
 
 import abi
 import add_ref as ar
-
-
-def _pairs():
-    v = np.arange(256, dtype=np.uint8)
-    return np.repeat(v, 256), np.tile(v, 256)
+import support
+from support import i8ie  # noqa: F401
 
 
 @pytest.mark.parametrize("scale", [0.5, 0.0234375, 3.0])  # powers of two and 3: every product and quotient below is exact
@@ -20,7 +17,7 @@ def _pairs():
 def test_restatement_equals_integer_add_for_equal_scales(scale, zps, relu):
     """s_a = s_b = s_out = s: fa, fb and their sum are (small integer) * s, exact in fp32 for these s, and the quotient by
     s is that integer again; so q = clamp(a - zp_a + b - zp_b + zp_out, 0, 255) in integers."""
-    a, b = _pairs()
+    a, b = support.byte_pairs()
     zp_a, zp_b, zp_out = zps
     want = np.clip(a.astype(np.int64) - zp_a + b.astype(np.int64) - zp_b + zp_out, 0, 255)
     if relu:
@@ -42,14 +39,6 @@ def test_saturation_and_relu_floor():
     assert ar.add_u8(np.array([1, 5], np.uint8), 0, 1.0, np.zeros(2, np.uint8), 0, 1.0, 3.0, 0).tolist() == [0, 1]
     # a negative t inside (-1, 0) is 0 by the clamp, not by the cast
     assert ar.add_u8(np.array([0], np.uint8), 1, 1.0, np.array([0], np.uint8), 0, 1.0, 3.0, 0).tolist() == [0]
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def test_surface_names(i8ie):

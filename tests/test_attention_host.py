@@ -5,15 +5,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import abi
 import attention_ref as ar
+import support
+from support import i8ie  # noqa: F401
 
 SCALES = [1.0 / 256, 0.01, 0.05, 0.3, 1.0, 0.0]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return ar.bind(abi.lib())
+lib = support.lib_fixture(ar)
 
 
 @pytest.mark.parametrize("s", SCALES)
@@ -108,14 +107,6 @@ def test_bmm_argument_errors_need_no_gpu(lib):
     assert lib.i8ie_softmax_u8(fake_ctx, 4096, 4096, C.c_int64(1), 65536, C.c_float(0.1)) == -1
     assert lib.i8ie_softmax_u8(fake_ctx, 4096, 4096, C.c_int64(1), 0, C.c_float(0.1)) == -1
     assert lib.i8ie_softmax_u8(fake_ctx, 4096, 4096, C.c_int64(1), 8, C.c_float(float("nan"))) == -1
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def test_surface_names(i8ie):

@@ -10,6 +10,7 @@ import pytest
 
 import abi
 import avgpool_ref as apr
+from support import i8ie  # noqa: F401
 
 f32 = np.float32
 
@@ -62,14 +63,6 @@ def test_f32_restatement_against_fractions():
     w = np.array([[[[16777216.0, 1.0], [1.0, 1.0]]]], f32)
     assert apr.avg_pool2d_f32(w, 2, 2, 1).ravel().tolist() == [4194304.0]
     assert apr.avg_pool2d_f32(w[:, :, ::-1, ::-1].copy(), 2, 2, 1).ravel().tolist() == [4194305.0]  # (3 + 2^24 is exact in the sum)
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def test_surface_names(i8ie):

@@ -8,6 +8,7 @@ import pytest
 import abi
 import concat_ref as cr
 import pinned_networks as pn
+from support import i8ie  # noqa: F401
 
 f32 = np.float32
 BYTES = np.arange(256, dtype=np.uint8).reshape(1, 1, 16, 16)
@@ -87,14 +88,6 @@ def test_restatement_joins_along_axis_one_and_saturates():
     x = np.arange(2 * 3 * 2 * 2, dtype=np.uint8).reshape(2, 3, 2, 2)
     got = cr.cat_u8([(x, 0.5, 3), (x[:, :1], 0.5, 3), (x, 0.5, 3)], 0.5, 3)
     assert got.shape == (2, 7, 2, 2) and np.array_equal(got, np.concatenate([x, x[:, :1], x], axis=1))
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def test_surface_names(i8ie):

@@ -10,6 +10,7 @@ import abi
 import deconv_ref as dr
 import pinned_networks as pn
 import spec_ref as sr
+from support import i8ie  # noqa: F401
 
 f32 = np.float32
 
@@ -104,14 +105,6 @@ def test_argument_rules_before_any_device_call():
         assert b"null" not in lib.i8ie_last_error()
         assert lib.i8ie_conv_transpose2d_create(None, P(qw), P(qb), kc, c, k, 1, 0, 0, C.c_float(1.0), C.byref(L)) == -1
         assert b"null" not in lib.i8ie_last_error()
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def test_surface_and_state_machine(i8ie):

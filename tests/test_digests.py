@@ -4,7 +4,6 @@ qparams.  The CPU test replays the oracle alone, so an edit that changes the ora
 if the kernels are changed the same way in the same round; the GPU tests hold the product
 to the same digests at the batch sizes BASELINE.json names (100 and 1000) and check that the seeded calibration
 still produces the fixture's qparams."""
-import hashlib
 import json
 import os
 import struct
@@ -12,6 +11,7 @@ import struct
 import numpy as np
 import pytest
 
+import support
 from conftest import GOLDEN
 
 FIX = json.load(open(os.path.join(GOLDEN, "alexnet_digests.json")))
@@ -20,10 +20,6 @@ FIX = json.load(open(os.path.join(GOLDEN, "alexnet_digests.json")))
 def _qparams():
     return {a: (np.float32(struct.unpack("<f", bytes.fromhex(v["scale_f32_hex"]))[0]), int(v["zero_point"]))
             for a, v in FIX["qparams"].items()}
-
-
-def _sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 @pytest.mark.parametrize("case", [c for c in FIX["cases"] if c["batch"] <= 100], ids=lambda c: "batch%d" % c["batch"])
@@ -37,8 +33,8 @@ def test_oracle_reproduces_committed_digests(orc, case):
     x = wl.synthetic_input("alexnet", case["batch"], seed=case["input_seed"])
     cap = {}
     logits = pipeline.forward(entry, x, qlayers, _qparams(), capture=cap)
-    got = {k: _sha(v) for k, v in cap.items() if isinstance(v, np.ndarray)}
-    got["_logits_f32"] = _sha(logits)
+    got = {k: support.sha(v) for k, v in cap.items() if isinstance(v, np.ndarray)}
+    got["_logits_f32"] = support.sha(logits)
     assert got == case["sha256"]
 
 
@@ -71,7 +67,7 @@ def test_gpu_alexnet_matches_committed_digests(calibrated_alexnet, case):
 
     x = wl.synthetic_input("alexnet", case["batch"], seed=case["input_seed"])
     got = calibrated_alexnet(i8ie.tensor(x)).numpy()
-    assert _sha(got) == case["sha256"]["_logits_f32"]
+    assert support.sha(got) == case["sha256"]["_logits_f32"]
     entry = wl.NETWORKS["alexnet"]
     qlayers = pipeline.quantize_layers(entry, wl.synthetic_state_dict("alexnet", seed=FIX["weights_seed"]))
     want = pipeline.forward(entry, x, qlayers, _qparams())

@@ -10,6 +10,7 @@ import pytest
 
 import abi
 import dilated_ref as dl
+from support import i8ie  # noqa: F401
 
 
 def _torch_cases():
@@ -112,14 +113,6 @@ def test_argument_rules_before_any_device_call():
     assert lib.i8ie_conv2d_f32_dilated(None, None, 1, 4, 7, 7, None, None, 4, 3, 3, 1, 1, 1, 4, None) == -1
     assert b"null" in lib.i8ie_last_error()
     assert lib.i8ie_layer_dilation(None, None) == -1 and b"null" in lib.i8ie_last_error()
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def test_conv2d_dilation_surface(i8ie):

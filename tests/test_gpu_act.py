@@ -15,26 +15,15 @@ import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import net_cases as nc
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 KINDS = sorted(ar.KINDS, key=ar.KINDS.get)
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    ar.bind(abi.lib())
-    yield c
-    c.close()
-
-
-def _phys(x_nchw, border, fill, s8):
-    """[n, c, h, w] u8 -> the physical buffer [n, h+2b, w+2b, c] with `fill` in the border (all of it re-biased if s8)"""
-    n, c, h, w = x_nchw.shape
-    p = np.full((n, h + 2 * border, w + 2 * border, c), fill, np.uint8)
-    p[:, border:border + h, border:border + w, :] = x_nchw.transpose(0, 2, 3, 1)
-    return p ^ np.uint8(0x80) if s8 else p
+ctx = support.ctx_fixture(ar)
 
 
 SENTINEL = 0x3C  # what the result's border holds before the call (no table below is the constant 0x3C everywhere)
@@ -44,9 +33,9 @@ def _run_nhwc(ctx, q, tab, in_border, in_s8, out_border, out_s8):
     """Returns (every byte of the physical result, the bytes expected there, guards untouched?).  The result's buffer starts
     with SENTINEL in the border and 0xC3 in the interior, as they lie (so a re-biased result holds them un-flipped)."""
     n, c, h, w = q.shape
-    src = _phys(q, in_border, 0x11, in_s8)
+    src = support.phys_nhwc(q, in_border, 0x11, in_s8)
     dev = ctx.put(src)
-    start = _phys(np.full((n, c, h, w), 0xC3, np.uint8), out_border, SENTINEL, False)
+    start = support.phys_nhwc(np.full((n, c, h, w), 0xC3, np.uint8), out_border, SENTINEL, False)
     out = abi.GuardedU8(ctx, start.shape, fill=start.ravel())
     ptr, keep = ar.host_table(tab)
     try:
@@ -89,11 +78,6 @@ def _run_flat(ctx, q, tab, in_off=0, out_off=0, in_place=False):
 
 
 # ---- exhaustive arithmetic ---------------------------------------------------------------------------------------------
-def _byte_image(c):
-    """[1, c, 16, 16]: pixel p holds byte p in every channel"""
-    return np.broadcast_to(np.arange(256, dtype=np.uint8).reshape(1, 1, 16, 16), (1, c, 16, 16)).copy()
-
-
 def _tables():
     a = np.arange(256, dtype=np.uint8)
     tabs = [("identity", a), ("reverse", (255 - a).astype(np.uint8)), ("permutation", np.random.default_rng(20261018).permutation(256).astype(np.uint8)),
@@ -113,7 +97,7 @@ TABLES = _tables()
 def test_exhaustive_bytes(ctx, case, entry):
     i, (name, tab) = case
     c = (16, 4, 3)[i % 3]
-    q = _byte_image(c)
+    q = support.byte_image(c)
     want = tab[q]
     if entry == "flat":
         got, ok = _run_flat(ctx, q, tab)
@@ -214,27 +198,10 @@ def test_fp32_entry_sigmoid_and_tanh_within_the_documented_bound(ctx, kind):
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
 def test_surface(i8ie, tmp_path):
     rng = np.random.default_rng(11)
     x = rng.uniform(-2, 2, (2, 16, 8, 8)).astype(f32)
-    conv = _conv(i8ie, 16, 20, 3, 1, 5, (0.05, 120))
+    conv = support.conv(i8ie, 16, 20, 3, 1, 5, (0.05, 120))
     q = i8ie.quantize(i8ie.tensor(x), 0.025, 127)          # NCHW bytes
     qv = q.numpy()
     yv = conv(q).numpy()
@@ -300,46 +267,28 @@ def test_surface(i8ie, tmp_path):
         assert np.array_equal(m(t).numpy().view(np.uint32), want.view(np.uint32))
 
 
-def _launches(prof):
-    launches = {}
-    for k, v in prof.items():  # (a kernel name may come with several shapes behind the bar)
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
-    for k in launches:
-        assert not k.startswith(("relu_u8", "rebias", "fill_border", "reborder", "layout_")), launches
-    luts = sum(v for k, v in launches.items() if k.startswith("lut_u8"))
-    return luts, sum(v for k, v in launches.items() if not k.startswith("lut_u8")), launches
-
-
-def _counted(forward):
-    import _CXX_i8ie as cx
-
-    first = forward().numpy()
-    cx.synchronize()
-    cx.profile_start()
-    try:
-        y = forward()
-        y.data.layout()  # launches what is pending; the bytes are observed outside the counted region
-    finally:
-        prof = cx.profile_stop()
-    assert np.array_equal(y.numpy(), first)
-    return first, _launches(prof)
+def _counted_luts(forward):
+    """(the output, (lookup launches, all other launches, {name: launches})) of the second of two equal forwards"""
+    first, again, launches = support.counted_forward(forward)
+    assert np.array_equal(again, first)
+    return first, support.split_launches(launches, "lut_u8")
 
 
 def test_launch_counts(i8ie):
     """conv_c(act(conv_a(x))): two conv launches and ONE lookup launch -- the padded conv_c gets its border (and re-biased
     bytes, where it reads them) from the lookup kernel; relu(act(x)) is one launch: the relu is folded into the table."""
-    conv_a = _conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
-    conv_c = _conv(i8ie, 16, 16, 3, 1, 6, (0.08, 90))
+    conv_a = support.conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
+    conv_c = support.conv(i8ie, 16, 16, 3, 1, 6, (0.08, 90))
     act = i8ie.Activation("hardswish")
     act.set_output_qparams(0.04, 25)
     act.convert()
     xin = np.random.default_rng(4).uniform(-2, 2, (2, 3, 8, 8)).astype(f32)
     # an activation in the engine's layout that stays recorded (as in tests/test_gpu_add.py): the warm-up forward launches it
     # once, with the border its consumer asks for, and the counted forward finds that result
-    q = i8ie.relu(_conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(_conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
+    q = i8ie.relu(support.conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(support.conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
         i8ie.quantize(i8ie.tensor(xin), 0.025, 127)))))
 
-    got, (luts, others, launches) = _counted(lambda: conv_c(act(conv_a(q))))
+    got, (luts, others, launches) = _counted_luts(lambda: conv_c(act(conv_a(q))))
     print(launches)
     assert luts == 1 and others == 2, launches
     av = conv_a(q).numpy()
@@ -351,7 +300,7 @@ def test_launch_counts(i8ie):
 
     a = conv_a(q)
     a.data.layout()
-    got, (luts, others, launches) = _counted(lambda: i8ie.relu(act(a)))
+    got, (luts, others, launches) = _counted_luts(lambda: i8ie.relu(act(a)))
     print(launches)
     assert luts == 1 and others == 0, launches
     assert np.array_equal(got, np.maximum(mid, 25))

@@ -15,28 +15,14 @@ import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path
 import net_cases as nc
 import pointwise_util as pu
 import spec_ref as sr
+import support
+from support import i8ie, pairs  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    ar.bind(abi.lib())
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def pairs(ctx):
-    """all 65 536 (a, b) byte pairs as flat tensors, resident on the device, and one output buffer"""
-    v = np.arange(256, dtype=np.uint8)
-    a, b = np.repeat(v, 256), np.tile(v, 256)
-    da, db, do = ctx.put(a), ctx.put(b), ctx.empty(a.shape, np.uint8)
-    yield a, b, da, db, do
-    for d in (da, db, do):
-        d.free()
+ctx = support.ctx_fixture(ar)
 
 
 def _qparam_sets():
@@ -161,27 +147,10 @@ def test_fp32_bit_patterns(ctx, n):
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
 def test_surface_mixed_layouts_and_errors(i8ie):
     rng = np.random.default_rng(11)
     x = rng.uniform(-2, 2, (2, 16, 8, 8)).astype(f32)
-    conv = _conv(i8ie, 16, 16, 3, 1, 5, (0.05, 120))
+    conv = support.conv(i8ie, 16, 16, 3, 1, 5, (0.05, 120))
     q = i8ie.quantize(i8ie.tensor(x), 0.025, 127)          # NCHW bytes
     qv = q.numpy()
     yv = conv(q).numpy()                                   # (observed on a tensor of its own: the operand below stays as it lies)
@@ -223,9 +192,9 @@ def test_surface_mixed_layouts_and_errors(i8ie):
 
 
 def _block(i8ie):
-    conv0 = _conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110))
-    conv_a = _conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
-    conv_b = _conv(i8ie, 16, 16, 3, 1, 3, (0.06, 130))
+    conv0 = support.conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110))
+    conv_a = support.conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
+    conv_b = support.conv(i8ie, 16, 16, 3, 1, 3, (0.06, 130))
     add = i8ie.Add()
     add.set_output_qparams(0.07, 100)
     add.convert()
@@ -243,7 +212,7 @@ def test_basic_block_launch_counts(i8ie, skip_first):
     # the block's input as it is inside a network: an activation in the engine's layout (a 3-channel first conv takes the
     # any-geometry path and leaves NCHW; the 16-channel conv behind it leaves NHWC).  It stays recorded: the warm-up forward
     # launches it once, with the border conv0 asks its producer for, and the counted forward finds that result.
-    q = i8ie.relu(_conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(_conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
+    q = i8ie.relu(support.conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(support.conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
         i8ie.quantize(i8ie.tensor(xin), 0.025, 127)))))
     qv = q.shape
 

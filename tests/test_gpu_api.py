@@ -5,15 +5,9 @@ the oracle pipeline (bit-exact logits)."""
 import numpy as np
 import pytest
 
+from support import i8ie  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def _u(shape, lo=-1, hi=1, seed=0):

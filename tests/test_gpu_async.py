@@ -9,25 +9,13 @@ import numpy as np
 import pytest
 
 import abi
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    import int8inferenceengine_amd  # noqa: F401  (torch's HIP runtime first)
-
-    c = abi.Ctx(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
+ctx = support.ctx_fixture()
 
 
 def _pinned(ctx, nbytes):

@@ -12,8 +12,9 @@ import pytest
 import abi
 import attention_ref as ar
 import f64_ref
-import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -21,12 +22,7 @@ FORMS = [(False, False), (True, False), (False, True), (True, True)]
 QP = (f32(0.02), f32(0.03), f32(0.21), 117)   # s_a, s_b, s_out, zp_out: spreads random accumulators over the byte range
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    ar.bind(abi.lib())
-    yield c
-    c.close()
+ctx = support.ctx_fixture(ar)
 
 
 def _bmm(ctx, A, zp_a, B, zp_b, ta=False, tb=False, relu=False, a_s8=False, b_s8=False, o_s8=False, qp=QP, fallback=False,
@@ -289,49 +285,6 @@ def test_softmax_f32_against_float64(ctx, L):
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
-def _conv_ref(L, q, s_in, zp_in, pad=0, stride=1):
-    s_out, zp_out = L.output_qparams()
-    out, _ = gr.conv2d_grouped(q, L.layer.q_weight(), L.layer.q_bias(), 1, stride, pad, f32(s_in), zp_in, L.weight_scale(),
-                               f32(s_out), zp_out)
-    return out
-
-
-def _counted(make):
-    """{kernel name: launches} of make() after one warm-up call (tests/test_gpu_mul.py)"""
-    import _CXX_i8ie as cx
-
-    for t in make():
-        t.numpy()
-    cx.synchronize()
-    cx.profile_start()
-    try:
-        for t in make():
-            t.data.layout()
-    finally:
-        prof = cx.profile_stop()
-    launches = {}
-    for k, v in prof.items():
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
-    return launches
-
-
 def test_surface_shapes_and_errors(i8ie):
     rng = np.random.default_rng(80)
     a3 = i8ie.quantize(i8ie.tensor(rng.uniform(-3, 3, (2, 5, 12)).astype(f32)), 0.025, 127)
@@ -380,9 +333,9 @@ def test_nonlocal_block_bytes_layouts_and_launch_counts(i8ie):
     rng = np.random.default_rng(90)
     n, c, d, h, w = 3, 16, 16, 6, 5
     # (two convs: the second one's result is an activation in the engine's layout, as in tests/test_gpu_mul.py)
-    stem0, stem = _conv(i8ie, 3, c, 3, 1, 9, (0.05, 128)), _conv(i8ie, c, c, 3, 1, 1, (0.05, 120))
-    theta, phi, gp = (_conv(i8ie, c, d, 1, 0, sd, (0.06, 125 + sd)) for sd in (2, 3, 4))
-    tail = _conv(i8ie, d, 16, 3, 1, 5, (0.07, 100))
+    stem0, stem = support.conv(i8ie, 3, c, 3, 1, 9, (0.05, 128)), support.conv(i8ie, c, c, 3, 1, 1, (0.05, 120))
+    theta, phi, gp = (support.conv(i8ie, c, d, 1, 0, sd, (0.06, 125 + sd)) for sd in (2, 3, 4))
+    tail = support.conv(i8ie, d, 16, 3, 1, 5, (0.07, 100))
     mm1, mm2 = i8ie.MatMul(transpose_a=True), i8ie.MatMul(transpose_b=True)
     mm1.set_output_qparams(0.6, 150)
     mm1.convert()
@@ -396,7 +349,7 @@ def test_nonlocal_block_bytes_layouts_and_launch_counts(i8ie):
         p = i8ie.softmax(s)
         return [tail(i8ie.relu(mm2(gp(x), p)))]
 
-    launches = _counted(block)
+    launches = support.counted(block)
     print(launches)
     assert launches.get("bmm_mfma", 0) + launches.get("bmm_direct", 0) == 2 and launches.get("softmax_u8_wave", 0) == 1
     assert sum(launches.values()) == 3 + 4, launches   # + theta, phi, g and the tail conv, one launch each
@@ -404,14 +357,14 @@ def test_nonlocal_block_bytes_layouts_and_launch_counts(i8ie):
         assert not k.startswith(("relu_u8", "rebias", "fill_border", "reborder", "layout_")), launches
     # the bytes, from the numpy composition
     xv = x.numpy()
-    tv, pv, gv = (_conv_ref(L, xv, 0.05, 120) for L in (theta, phi, gp))
+    tv, pv, gv = (support.conv_ref(L, xv, 0.05, 120) for L in (theta, phi, gp))
     sv = ar.matmul_u8(tv, 127, f32(0.06), pv, 128, f32(0.06), f32(0.6), 150, transpose_a=True)
     assert sv.shape == (n, h * w, h * w) and ((sv == 0) | (sv == 255)).mean() < 0.05
     smv = ar.softmax_u8(sv, f32(0.6))
     assert len(np.unique(smv)) >= 16
     yv = ar.matmul_u8(gv, 129, f32(0.06), smv, 0, f32(1 / 256), f32(0.06), 128, True, transpose_b=True).reshape(n, d, h, w)
     assert len(np.unique(yv)) >= 16
-    want = _conv_ref(tail, yv, 0.06, 128, pad=1)
+    want = support.conv_ref(tail, yv, 0.06, 128, pad=1)
     s = mm1(theta(x), phi(x))
     assert s.shape == (n, h * w, h * w) and np.array_equal(s.numpy(), sv)
     y = mm2(gp(x), i8ie.softmax(s))

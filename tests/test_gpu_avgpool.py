@@ -23,6 +23,8 @@ import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import net_cases as nc
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -32,28 +34,7 @@ f32 = np.float32
 REDUCE_MIN_WINDOW, REDUCE_MAX_ITEMS, PACKED_MAX = 16, 65536, 257
 
 
-class _Entry(C.Structure):
-    _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double),
-                ("total_ops", C.c_double), ("total_bytes", C.c_double)]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    apr.bind(abi.lib())
-    yield c
-    c.close()
-
-
-def _kernels_run(ctx, fn):
-    lib = abi.lib()
-    abi.ck(lib.i8ie_profile_start(ctx.h, 0))
-    try:
-        fn()
-    finally:
-        ents, n = (_Entry * 64)(), C.c_int(0)
-        abi.ck(lib.i8ie_profile_stop(ctx.h, ents, 64, C.byref(n)))
-    return sorted(ents[i].name.decode().split("|")[0] for i in range(n.value))
+ctx = support.ctx_fixture(apr)
 
 
 # ---- 1. every sum ------------------------------------------------------------------------------------------------------
@@ -119,7 +100,7 @@ def _check_every_sum(ctx, x, want, kh, kw, s, regime, nchw):
     dx, do = ctx.put(x), ctx.put(np.full(want.shape, 0xEE, np.uint8))
     try:
         for relu, zp in RELUS:
-            names = _kernels_run(ctx, lambda: _run_nhwc(ctx, dx.ptr, do.ptr, x.shape, kh, kw, s, relu, zp))
+            names = sorted(ctx.kernels_run(lambda: _run_nhwc(ctx, dx.ptr, do.ptr, x.shape, kh, kw, s, relu, zp))[1])
             assert names == [regime], (names, regime)
             got = do.get()
             exp = np.maximum(want, zp) if relu else want
@@ -166,7 +147,7 @@ GUARD = 64
 SENTINEL = 0xC7
 
 
-def _phys(x_nhwc, border, s8):
+def _guarded_phys(x_nhwc, border, s8):
     """[n, h, w, c] u8 -> guarded flat buffer holding [n, h+2b, w+2b, c] with SENTINEL in the border (interior re-biased if s8)"""
     n, h, w, c = x_nhwc.shape
     p = np.full((n, h + 2 * border, w + 2 * border, c), SENTINEL, np.uint8)
@@ -190,8 +171,8 @@ def test_layout_matrix(ctx, c):
                 relu, zp = bool(i % 2), 100 + (i % 7) * 10
                 want = apr.avg_pool2d_u8(x, kh, kw, s, relu, zp).transpose(0, 2, 3, 1)
                 oh, ow = want.shape[1:3]
-                fi, _ = _phys(x_nhwc, ib, in_s8)
-                fo, oshape = _phys(np.full(want.shape, 0xEE, np.uint8), ob, 0)
+                fi, _ = _guarded_phys(x_nhwc, ib, in_s8)
+                fo, oshape = _guarded_phys(np.full(want.shape, 0xEE, np.uint8), ob, 0)
                 di, do = ctx.put(fi), ctx.put(fo)
                 try:
                     _run_nhwc(ctx, C.c_void_p(di.ptr.value + GUARD), C.c_void_p(do.ptr.value + GUARD), (n, h, w, c), kh, kw, s, relu, zp,
@@ -276,50 +257,11 @@ def test_fp32_special_values_by_class(ctx):
 
 
 # ---- 4. the Python surface ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
-def _activation(i8ie):
-    """an activation as it is inside a network: in the engine's layout, still recorded (test_gpu_add.py's construction)"""
-    xin = np.random.default_rng(4).uniform(-2, 2, (2, 3, 8, 8)).astype(f32)
-    return i8ie.relu(_conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(_conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
-        i8ie.quantize(i8ie.tensor(xin), 0.025, 127)))))
-
-
-def _counted(forward):
-    import _CXX_i8ie as cx
-
-    first = forward().numpy()  # (packs weights, fills cached borders)
-    cx.synchronize()
-    cx.profile_start()
-    try:
-        y = forward()
-        y.data.layout()  # launches what is pending; the bytes are observed outside the counted region
-    finally:
-        prof = cx.profile_stop()
-    print(prof)
-    return first, y.numpy(), {k.split("|")[0]: v[0] for k, v in prof.items()}
-
-
 def test_relu_avg_pool_conv_launch_counts(i8ie):
     """relu(avg_pool2d(conv(x))): one conv launch and ONE pool launch with the relu folded in; nothing converts."""
-    q = _activation(i8ie)
-    conv = _conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110))
-    first, got, launches = _counted(lambda: i8ie.relu(i8ie.avg_pool2d(conv(q), 2)))
+    q = support.activation(i8ie)
+    conv = support.conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110))
+    first, got, launches = support.counted_forward(lambda: i8ie.relu(i8ie.avg_pool2d(conv(q), 2)))
     want = apr.avg_pool2d_u8(conv(q).numpy(), 2, 2, 2, True, 110)
     assert got.shape == (2, 16, 4, 4) and np.array_equal(got, want) and np.array_equal(first, want)
     pools = sum(v for k, v in launches.items() if k.startswith("avgpool_u8_nhwc"))
@@ -327,8 +269,8 @@ def test_relu_avg_pool_conv_launch_counts(i8ie):
     for k in launches:
         assert not k.startswith(("relu_u8", "rebias", "fill_border", "reborder", "layout_", "avgpool_u8_nchw")), launches
     # a conv behind the pool gets its zero-point border (and what it reads) from the pool kernel
-    conv2 = _conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
-    first, got, launches = _counted(lambda: conv2(i8ie.relu(i8ie.avg_pool2d(conv(q), 3, 1))))
+    conv2 = support.conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
+    first, got, launches = support.counted_forward(lambda: conv2(i8ie.relu(i8ie.avg_pool2d(conv(q), 3, 1))))
     pooled = i8ie.relu(i8ie.avg_pool2d(conv(q), 3, 1))
     assert np.array_equal(pooled.numpy(), apr.avg_pool2d_u8(conv(q).numpy(), 3, 3, 1, True, 110))
     assert np.array_equal(got, conv2(pooled).numpy()) and np.array_equal(first, got)  # (pooled: observed, NCHW, border-free)
@@ -342,8 +284,8 @@ def test_relu_avg_pool_conv_launch_counts(i8ie):
 def test_head_launch_counts(i8ie):
     """fc(global_avg_pool2d(relu(add(a, b))).reshape(-1, c)): two convs, one add (relu folded), one pool, one Linear -- and
     no layout conversion in front of the Linear: [n, c, 1, 1] is the same bytes in both orders."""
-    q = _activation(i8ie)
-    conv_a, conv_b = _conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120)), _conv(i8ie, 16, 16, 3, 1, 3, (0.06, 130))
+    q = support.activation(i8ie)
+    conv_a, conv_b = support.conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120)), support.conv(i8ie, 16, 16, 3, 1, 3, (0.06, 130))
     add = i8ie.Add()
     add.set_output_qparams(0.07, 100)
     add.convert()
@@ -357,7 +299,7 @@ def test_head_launch_counts(i8ie):
     def head():
         return fc(i8ie.global_avg_pool2d(i8ie.relu(add(conv_a(q), conv_b(q)))).reshape(-1, 16))
 
-    first, got, launches = _counted(head)
+    first, got, launches = support.counted_forward(head)
     summed = ar.add_u8(conv_a(q).numpy(), 120, f32(0.05), conv_b(q).numpy(), 130, f32(0.06), f32(0.07), 100, True)
     pooled = i8ie.global_avg_pool2d(i8ie.relu(add(conv_a(q), conv_b(q))))
     assert pooled.shape == (2, 16, 1, 1) and pooled.scale == pytest.approx(0.07) and pooled.zero_point == 100
@@ -416,11 +358,6 @@ def test_networks_bit_exact(i8ie, name, batch, per_channel, tmp_path):
 
 
 # ---- 6. FP32 resnet_tiny_gap before convert() --------------------------------------------------------------------------
-def _bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def test_fp32_resnet_tiny_gap_layer_by_layer(i8ie):
     """Walk the spec by hand with the FP32 ops, every op fed the product's own previous output: conv / fc inside
     f64_ref.dot_bound of the float64 result (the bounds of test_gpu_fp32.py; a grouped conv against grouped_ref's float64
@@ -452,7 +389,7 @@ def test_fp32_resnet_tiny_gap_layer_by_layer(i8ie):
                 assert got.dtype == f32 and got.shape == want.shape and np.all(err <= bound), (op, float(np.nanmax(err / bound)))
             elif op[0] == "relu":
                 t = i8ie.relu(t)
-                assert _bits_equal(t.numpy(), f64_ref.relu(prev)), op
+                assert support.bits_equal(t.numpy(), f64_ref.relu(prev)), op
             elif op[0] in ("avgpool", "gap"):
                 kh, kw, s = (op[1], op[1], op[2]) if op[0] == "avgpool" else (prev.shape[2], prev.shape[3], 1)
                 t = i8ie.avg_pool2d(t, op[1], op[2]) if op[0] == "avgpool" else i8ie.global_avg_pool2d(t)
@@ -466,12 +403,12 @@ def test_fp32_resnet_tiny_gap_layer_by_layer(i8ie):
             elif op[0] == "add":
                 other = saved[op[2]].numpy()
                 t = getattr(net, op[1])(t, saved[op[2]])
-                assert _bits_equal(t.numpy(), (prev + other).astype(f32)), op
+                assert support.bits_equal(t.numpy(), (prev + other).astype(f32)), op
             else:
                 t = t.reshape(-1, op[1])
-                assert _bits_equal(t.numpy(), prev.reshape(-1, op[1])), op
+                assert support.bits_equal(t.numpy(), prev.reshape(-1, op[1])), op
         return t
 
     walked = walk(spec, i8ie.tensor(x), {}).numpy()
     assert walked.shape == (3, 10)
-    assert _bits_equal(net(i8ie.tensor(x)).numpy(), walked)
+    assert support.bits_equal(net(i8ie.tensor(x)).numpy(), walked)

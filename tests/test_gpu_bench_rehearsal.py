@@ -4,20 +4,15 @@ I8IE_BENCH_REHEARSE=1 maps every rank to device 0 and runs the collectives over 
 gathered logits must score exactly like a single-process run of the same global batch."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
+import support
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _last_json(text):
@@ -30,7 +25,7 @@ def test_two_ranks_equal_one_rank():
     one = subprocess.run([sys.executable] + common, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                          "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + common + ["--gpus", "2"],
+                          "--master-addr", "127.0.0.1", "--master-port", str(support.free_port())] + common + ["--gpus", "2"],
                          cwd=ROOT, env=dict(env, I8IE_BENCH_REHEARSE="1"), capture_output=True, text=True, timeout=600)
     assert two.returncode == 0, two.stderr[-2000:]
     a, b = _last_json(one.stdout), _last_json(two.stdout)

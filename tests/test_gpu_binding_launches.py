@@ -16,6 +16,8 @@ import os
 
 import pytest
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -45,10 +47,7 @@ def launches(name):
     return {k: int(v[0]) for k, v in sorted(prof.items())}
 
 
-@pytest.fixture(scope="module")
-def golden():
-    with open(GOLDEN) as f:
-        return json.load(f)
+golden = support.json_fixture(GOLDEN)
 
 
 @pytest.mark.parametrize("name", NETS)

@@ -14,25 +14,14 @@ import concat_ref as cr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import net_cases as nc
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    cr.bind(abi.lib())
-    yield c
-    c.close()
-
-
-def _phys(x_nchw, border, fill, s8):
-    """[n, c, h, w] u8 -> the physical buffer [n, h+2b, w+2b, c] with `fill` in the border (all of it re-biased if s8)"""
-    n, c, h, w = x_nchw.shape
-    p = np.full((n, h + 2 * border, w + 2 * border, c), fill, np.uint8)
-    p[:, border:border + h, border:border + w, :] = x_nchw.transpose(0, 2, 3, 1)
-    return p ^ np.uint8(0x80) if s8 else p
+ctx = support.ctx_fixture(cr)
 
 
 def _run_nhwc(ctx, inputs, borders, s8s, s_out, zp_out, relu, out_border, out_s8, same=None):
@@ -42,8 +31,8 @@ def _run_nhwc(ctx, inputs, borders, s8s, s_out, zp_out, relu, out_border, out_s8
     ctot = sum(q.shape[1] for q, _, _ in inputs)
     devs = []
     for i, ((q, _, zp), b, x) in enumerate(zip(inputs, borders, s8s)):
-        devs.append(devs[same[i]] if same and same[i] is not None else ctx.put(_phys(q, b, zp, x)))
-    start = _phys(np.full((n, ctot, h, w), 0xC3, np.uint8), out_border, zp_out, False)
+        devs.append(devs[same[i]] if same and same[i] is not None else ctx.put(support.phys_nhwc(q, b, zp, x)))
+    start = support.phys_nhwc(np.full((n, ctot, h, w), 0xC3, np.uint8), out_border, zp_out, False)
     start = start ^ np.uint8(0x80) if out_s8 else start
     out = abi.GuardedU8(ctx, start.shape, fill=start.ravel())
     try:
@@ -53,12 +42,12 @@ def _run_nhwc(ctx, inputs, borders, s8s, s_out, zp_out, relu, out_border, out_s8
         got = out.get()
         ok = out.guards_ok()
         for (q, _, zp), b, x, d in zip(inputs, borders, s8s, devs):
-            assert np.array_equal(d.get(), _phys(q, b, zp, x)), "an input was written"
+            assert np.array_equal(d.get(), support.phys_nhwc(q, b, zp, x)), "an input was written"
     finally:
         out.free()
         for d in {id(d): d for d in devs}.values():
             d.free()
-    want = _phys(cr.cat_u8(inputs, s_out, zp_out, relu), out_border, zp_out, out_s8)
+    want = support.phys_nhwc(cr.cat_u8(inputs, s_out, zp_out, relu), out_border, zp_out, out_s8)
     return got, want, ok
 
 
@@ -81,11 +70,6 @@ def _run_rows(ctx, inputs, s_out, zp_out, relu):
 
 
 # ---- exhaustive arithmetic ---------------------------------------------------------------------------------------------
-def _byte_image(c):
-    """[1, c, 16, 16]: pixel p holds byte p in every channel"""
-    return np.broadcast_to(np.arange(256, dtype=np.uint8).reshape(1, 1, 16, 16), (1, c, 16, 16)).copy()
-
-
 def _arith_cases():
     so = f32(0.05)
     rng = np.random.default_rng(20261018)
@@ -118,7 +102,7 @@ ARITH = _arith_cases()
 @pytest.mark.parametrize("case", ARITH, ids=[c[0] for c in ARITH])
 def test_exhaustive_bytes(ctx, case, relu, entry):
     name, s_out, zp_out, qps, cs = case
-    inputs = [(_byte_image(c), s, zp) for (s, zp), c in zip(qps, cs)]
+    inputs = [(support.byte_image(c), s, zp) for (s, zp), c in zip(qps, cs)]
     assert any(cr.same_qparams(s, zp, s_out, zp_out) for s, zp in qps) or name == "denormal_everywhere"
     want = cr.cat_u8(inputs, s_out, zp_out, relu)
     if entry == "run":
@@ -251,27 +235,10 @@ def test_error_paths_reach_no_kernel(ctx):
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
 def test_surface_mixed_layouts(i8ie):
     rng = np.random.default_rng(11)
     x = rng.uniform(-2, 2, (2, 16, 8, 8)).astype(f32)
-    conv = _conv(i8ie, 16, 16, 3, 1, 5, (0.05, 120))
+    conv = support.conv(i8ie, 16, 16, 3, 1, 5, (0.05, 120))
     q = i8ie.quantize(i8ie.tensor(x), 0.025, 127)          # NCHW bytes
     qv = q.numpy()
     yv = conv(q).numpy()                                   # (observed on a tensor of its own: the input below stays as it lies)
@@ -306,36 +273,18 @@ def test_surface_mixed_layouts(i8ie):
         i8ie.Concat()([q, q])                              # not converted
 
 
-def _launches(prof):
-    launches = {}
-    for k, v in prof.items():  # (a kernel name may come with several shapes behind the bar)
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
-    for k in launches:
-        assert not k.startswith(("relu_u8", "rebias", "fill_border", "reborder", "layout_")), launches
-    cats = sum(v for k, v in launches.items() if k.startswith("concat_u8"))
-    return cats, sum(v for k, v in launches.items() if not k.startswith("concat_u8")), launches
-
-
-def _activation(i8ie):
-    """an activation in the engine's layout that stays recorded (as in tests/test_gpu_add.py): the warm-up forward launches it
-    once, with the border its consumers ask for, and the counted forward finds that result"""
-    xin = np.random.default_rng(4).uniform(-2, 2, (2, 3, 8, 8)).astype(f32)
-    return i8ie.relu(_conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(_conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
-        i8ie.quantize(i8ie.tensor(xin), 0.025, 127)))))
-
-
 def test_fire_launch_counts(i8ie):
     """conv_c(relu(cat(conv_a(x), conv_b(x)))): three conv launches and ONE concat launch -- the relu folds into the concat,
     and the padded conv_c gets its border (and re-biased bytes, where it reads them) from the concat kernel."""
     import _CXX_i8ie as cx
 
-    conv_a = _conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
-    conv_b = _conv(i8ie, 16, 16, 3, 1, 3, (0.06, 130))
-    conv_c = _conv(i8ie, 32, 16, 3, 1, 6, (0.08, 90))
+    conv_a = support.conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
+    conv_b = support.conv(i8ie, 16, 16, 3, 1, 3, (0.06, 130))
+    conv_c = support.conv(i8ie, 32, 16, 3, 1, 6, (0.08, 90))
     cat = i8ie.Concat()
     cat.set_output_qparams(0.06, 130)  # conv_b's: a copy; conv_a's result is requantised
     cat.convert()
-    q = _activation(i8ie)
+    q = support.activation(i8ie)
 
     def forward():
         return conv_c(i8ie.relu(cat([conv_a(q), conv_b(q)])))
@@ -353,7 +302,7 @@ def test_fire_launch_counts(i8ie):
     want_cat = cr.cat_u8([(av, f32(0.05), 120), (bv, f32(0.06), 130)], f32(0.06), 130, True)
     assert np.array_equal(i8ie.relu(cat([conv_a(q), conv_b(q)])).numpy(), want_cat)
     assert np.array_equal(got, first)
-    cats, others, launches = _launches(prof)
+    cats, others, launches = support.split_launches(support.launch_counts(prof), "concat_u8")
     print(launches)
     assert cats == 1 and others == 3, launches
 
@@ -364,12 +313,12 @@ def test_input_launched_for_another_consumer_is_read_as_it_lies(i8ie, skip_first
     either order: two conv launches and one concat launch"""
     import _CXX_i8ie as cx
 
-    conv0 = _conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110))
-    conv_a = _conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
+    conv0 = support.conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110))
+    conv_a = support.conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
     cat = i8ie.Concat()
     cat.set_output_qparams(0.04, 110)
     cat.convert()
-    q = _activation(i8ie)
+    q = support.activation(i8ie)
 
     def forward():
         x = i8ie.relu(conv0(q))
@@ -390,7 +339,7 @@ def test_input_launched_for_another_consumer_is_read_as_it_lies(i8ie, skip_first
     ops = [(xv, f32(0.04), 110), (fv, f32(0.05), 120)]
     want = cr.cat_u8(ops if skip_first else ops[::-1], f32(0.04), 110)
     assert np.array_equal(got, want) and np.array_equal(first, want)
-    cats, others, launches = _launches(prof)
+    cats, others, launches = support.split_launches(support.launch_counts(prof), "concat_u8")
     print(launches)
     assert cats == 1 and others == 2, launches
 

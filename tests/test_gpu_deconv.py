@@ -17,6 +17,8 @@ import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path
 import net_cases as nc
 import orc
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -24,19 +26,7 @@ DECONV = {"deconv_mfma", "deconv_direct"}
 BY_NAME = {c.name: c for c in dr.CASES}
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    dr.bind(abi.lib())
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
+ctx = support.ctx_fixture(dr)
 
 
 def _launched(r):
@@ -171,7 +161,7 @@ def test_fp32(ctx, geo, cls):
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------
-def _conv(i8ie, cin, cout, k, pad, seed, qp):
+def _conv(i8ie, cin, cout, k, pad, seed, qp):  # (not support.conv: the bias is uniform(-1, 1) * 0.1, which rounds differently)
     rng = np.random.default_rng(seed)
     L = i8ie.Conv2d(cin, cout, k, stride=1, padding=pad)
     L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
@@ -192,24 +182,6 @@ def _deconv(i8ie, cin, cout, geo, seed, qp, per_channel=False):
     return L
 
 
-def _counted(make):
-    import _CXX_i8ie as cx
-
-    for t in make():
-        t.numpy()
-    cx.synchronize()
-    cx.profile_start()
-    try:
-        for t in make():
-            t.data.layout()
-    finally:
-        prof = cx.profile_stop()
-    launches = {}
-    for k, v in prof.items():
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
-    return launches
-
-
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 def test_conv_deconv_relu_conv_launches_and_bytes(i8ie, per_channel):
     """conv -> ConvTranspose2d -> relu -> conv(pad 1): the launches of the producers on their own plus ONE deconv launch; the
@@ -223,9 +195,9 @@ def test_conv_deconv_relu_conv_launches_and_bytes(i8ie, per_channel):
     q = i8ie.relu(_conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(i8ie.quantize(i8ie.tensor(xin), 0.025, 127)))
     mid_in = i8ie.relu(up(i8ie.relu(conv0(q))))
 
-    made = _counted(lambda: [i8ie.relu(conv0(q))])
-    behind = _counted(lambda: [conv_c(mid_in)])
-    whole = _counted(lambda: [conv_c(i8ie.relu(up(i8ie.relu(conv0(q)))))])
+    made = support.counted(lambda: [i8ie.relu(conv0(q))])
+    behind = support.counted(lambda: [conv_c(mid_in)])
+    whole = support.counted(lambda: [conv_c(i8ie.relu(up(i8ie.relu(conv0(q)))))])
     print(made, behind, whole)
     want_launches = dict(made)
     for k, v in behind.items():

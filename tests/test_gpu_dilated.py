@@ -16,6 +16,8 @@ import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path
 import net_cases as nc
 import orc
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 import upsample_ref as ur
 
 pytestmark = pytest.mark.gpu
@@ -24,19 +26,7 @@ GCONV = dl.KERNELS  # the three kernels a dilated layer can reach
 CONV_KERNELS = GCONV | {"igemm", "pconv", "tconv", "gemm_v1", "im2col"}
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    dl.bind(abi.lib())
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
+ctx = support.ctx_fixture(dl)
 
 
 def run(ctx, case, relu, names=None, guard=None, **kw):
@@ -240,7 +230,7 @@ def test_conv2d_f32_dilation_1_is_the_grouped_entry(ctx, g):
 
 
 # ---- the Python surface ---------------------------------------------------------------------------------------------------
-def _conv(i8ie, cin, cout, k, pad, seed, qp, **kw):
+def _conv(i8ie, cin, cout, k, pad, seed, qp, **kw):  # (not support.conv: groups / dilation in kw, and w and b are returned too)
     rng = np.random.default_rng(seed)
     L = i8ie.Conv2d(cin, cout, k, padding=pad, **kw)
     wshape = (cout, cin // kw.get("groups", 1), k, k)

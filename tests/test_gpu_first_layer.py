@@ -8,21 +8,13 @@ import numpy as np
 import pytest
 
 import abi
+import support
 import synth
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    c = abi.Ctx(0)
-    yield c
-    c.close()
-
-
-class _Entry(C.Structure):
-    _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double),
-                ("total_ops", C.c_double), ("total_bytes", C.c_double)]
+gpu = support.ctx_fixture()
 
 
 def run_first(gpu, x, qw, qb, stride, pad, q_scale, q_zp, s_w, s_out, zp_out, relu, ob, pool=None, names=None):
@@ -53,7 +45,7 @@ def run_first(gpu, x, qw, qb, stride, pad, q_scale, q_zp, s_w, s_out, zp_out, re
             abi.ck(lib.i8ie_layer_forward_f32_input_pool(L, dx.ptr, n, h, w, C.c_float(q_scale), C.c_uint8(q_zp),
                                                          1 if relu else 0, pool[0], pool[1], out.ptr, 1, ob, acc.ptr))
     finally:
-        ents = (_Entry * 64)()
+        ents = (abi.ProfEntry * 64)()
         cnt = C.c_int(0)
         abi.ck(lib.i8ie_profile_stop(gpu.h, ents, 64, C.byref(cnt)))
         if names is not None:

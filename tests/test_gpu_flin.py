@@ -4,39 +4,17 @@ u8 outputs, every element.  Shapes: AlexNet fc6 / fc7 at the 8-GPU shard size (1
 count, N not a multiple of 16 / of 4, with and without the fused ReLU; both block shapes (128 rows x 16 features up to 64
 rows, 64 x 32 up to 256 rows incl. the 250-row fc6 of a 4-GPU shard); the tiled split-K kernel (variant 11) must
 give the same bytes.  The profile hooks confirm which kernel ran."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import abi
+import support
 import synth
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    c = abi.Ctx(0)
-    yield c
-    c.close()
-
-
-class _Entry(C.Structure):
-    _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double),
-                ("total_ops", C.c_double), ("total_bytes", C.c_double)]
-
-
-def _kernels_run(gpu, fn):
-    lib = abi.lib()
-    abi.ck(lib.i8ie_profile_start(gpu.h, 0))
-    try:
-        res = fn()
-    finally:
-        ents = (_Entry * 64)()
-        n = C.c_int(0)
-        abi.ck(lib.i8ie_profile_stop(gpu.h, ents, 64, C.byref(n)))
-    return res, [ents[i].name.decode().split("|")[0] for i in range(n.value)]
+gpu = support.ctx_fixture()
 
 
 SHAPES = [(125, 9216, 4096), (125, 4096, 4096), (128, 4096, 4096), (1, 1024, 256), (100, 1280, 272), (17, 2304, 260),
@@ -64,15 +42,15 @@ def test_flin_bit_exact(gpu, orc, mkn, relu):
         finally:
             abi.ck(lib.i8ie_ctx_set_option(gpu.h, 2, 0))
 
-    (out, acc, _), names = _kernels_run(gpu, lambda: run(0 if n >= 2048 else 80))  # (80: below the automatic feature threshold)
+    (out, acc, _), names = gpu.kernels_run(lambda: run(0 if n >= 2048 else 80))  # (80: below the automatic feature threshold)
     assert _kernel_of(m) in names, names
     want = orc.relu(c["out"], c["zp_out"]) if relu else c["out"]
     assert np.array_equal(acc, c["acc"]) and np.array_equal(out, want)
-    (out2, acc2, _), names2 = _kernels_run(gpu, lambda: run(11))
+    (out2, acc2, _), names2 = gpu.kernels_run(lambda: run(11))
     assert not any(nm.startswith("flin") for nm in names2), names2
     assert np.array_equal(out2, out) and np.array_equal(acc2, acc)
     if 64 < m <= 128:  # the 128-row form is still there for these row counts (variant 81)
-        (out3, acc3, _), names3 = _kernels_run(gpu, lambda: run(81))
+        (out3, acc3, _), names3 = gpu.kernels_run(lambda: run(81))
         assert "flin_128x16" in names3, names3
         assert np.array_equal(out3, out) and np.array_equal(acc3, acc)
 
@@ -95,7 +73,7 @@ def test_flin_extreme_values(gpu, orc):
             finally:
                 abi.ck(lib.i8ie_ctx_set_option(gpu.h, 2, 0))
 
-        (out, acc, _), names = _kernels_run(gpu, run)
+        (out, acc, _), names = gpu.kernels_run(run)
         assert "flin_128x16" in names, names
         want, pre, _ = orc.linear(q_in, qw, qb, 0.02, zp_in, 0.001, 0.7, 128, want_acc=True)
         assert np.array_equal(acc, pre) and np.array_equal(out, want)

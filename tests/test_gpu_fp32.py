@@ -33,16 +33,13 @@ import pytest
 
 import abi
 import f64_ref
+import support
 import synth
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    c = abi.Ctx(0)
-    yield c
-    c.close()
+gpu = support.ctx_fixture()
 
 
 # ---- the shapes: (reason, n, c, h, w, kc, kh, kw, stride, pad);  M = n*oh*ow rows, N = kc, K = c*kh*kw -------------
@@ -238,7 +235,7 @@ def test_case_lists_cover_the_edges():
 
 
 # ---- max-pool and ReLU: bit for bit ------------------------------------------------------------------------------
-def _bits_equal(got, want):
+def _bits_equal_f32(got, want):
     return got.shape == want.shape and got.dtype == want.dtype == np.float32 and np.array_equal(
         got.view(np.uint32), want.view(np.uint32))
 
@@ -261,7 +258,7 @@ def test_maxpool2d_f32(gpu, cs):
     _, shape, kss = cs
     x = np.random.default_rng(sum(shape)).uniform(-100, 100, shape).astype(np.float32)
     for k, s in kss:
-        assert _bits_equal(gpu.maxpool2d_f32(x, k, s), f64_ref.max_pool2d(x, k, s)), (k, s)
+        assert _bits_equal_f32(gpu.maxpool2d_f32(x, k, s), f64_ref.max_pool2d(x, k, s)), (k, s)
 
 
 RELU_SIZES = [1, 255, 256, 257, 256 * 32 * 256 + 3]  # the last is past cap_grid's 8192 blocks: the grid-stride loop wraps
@@ -272,7 +269,7 @@ def test_relu_f32(gpu, n):
     x = np.random.default_rng(n).uniform(-100, 100, n).astype(np.float32)
     x[-1] = 7.25  # the very last element is stored, with its own value
     got = gpu.relu_f32(x)
-    assert _bits_equal(got, f64_ref.relu(x)) and got[-1] == np.float32(7.25)
+    assert _bits_equal_f32(got, f64_ref.relu(x)) and got[-1] == np.float32(7.25)
 
 
 def _specials():
@@ -288,7 +285,7 @@ def test_relu_f32_special_values(gpu):
         x[(i * 83) % 1000] = v
     x[0], x[-1] = np.float32(-0.0), -np.float32(np.nan)
     got, want = gpu.relu_f32(x), f64_ref.relu(x)
-    assert _bits_equal(got, want)
+    assert _bits_equal_f32(got, want)
     assert not np.isnan(got).any() and not np.signbit(got).any()  # NaN and -0.0 give +0.0
 
 
@@ -309,7 +306,7 @@ def test_maxpool2d_f32_special_values(gpu):
     x[1, 1, 8:10, 8:10] = ((-0.0, 0.0), (0.0, -0.0))  # a >= b keeps the first of equal values
     for k, s in POOL_KS + [(12, 1), (4, 4)]:
         got, want = gpu.maxpool2d_f32(x, k, s), f64_ref.max_pool2d(x, k, s)
-        assert _bits_equal(got, want), (k, s, np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:4])
+        assert _bits_equal_f32(got, want), (k, s, np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:4])
     w = f64_ref.max_pool2d(x, 2, 2)
     assert w[0, 1, 2, 2] == -f64_ref.FLT_MAX and np.isnan(w[0, 0, 0, 0]) and np.isnan(w[0, 0, 5, 5])
 
@@ -372,7 +369,7 @@ def test_workspace_shared_with_int8_path(orc):
         ctx.sync()
         (ga, ok_a), (gb, ok_b), (gd, ok_d) = oa.read(), ob.read(), od.read()
         assert ok_a and ok_b and ok_d
-        assert _bits_equal(ga, wa_out) and _bits_equal(gb, wb_out) and _bits_equal(gd, wd_out)
+        assert _bits_equal_f32(ga, wa_out) and _bits_equal_f32(gb, wb_out) and _bits_equal_f32(gd, wd_out)
         assert np.array_equal(oc_out.get(), wc_out) and np.array_equal(oc_acc.get(), wc_acc)
     finally:
         if layer:
@@ -434,7 +431,7 @@ def test_networks_layer_by_layer(name, batch):
     net.load(sd)
     x = wl.synthetic_input(name, batch, seed=5)
     t = i8ie.tensor(x)
-    assert _bits_equal(t.numpy(), x)
+    assert _bits_equal_f32(t.numpy(), x)
     for op in spec:
         prev = t.numpy()
         if op[0] == "layer":
@@ -451,13 +448,13 @@ def test_networks_layer_by_layer(name, batch):
             assert np.all(err <= bound), "%s %s: worst err / bound = %.3g" % (name, op[1], float(np.nanmax(err / bound)))
         elif op[0] == "relu":
             t = i8ie.relu(t)
-            assert _bits_equal(t.numpy(), f64_ref.relu(prev)), (name, op)
+            assert _bits_equal_f32(t.numpy(), f64_ref.relu(prev)), (name, op)
         elif op[0] == "pool":
             t = i8ie.max_pool2d(t, op[1], op[2])
-            assert _bits_equal(t.numpy(), f64_ref.max_pool2d(prev, op[1], op[2])), (name, op)
+            assert _bits_equal_f32(t.numpy(), f64_ref.max_pool2d(prev, op[1], op[2])), (name, op)
         else:
             t = t.reshape(-1, op[1])
-            assert _bits_equal(t.numpy(), prev.reshape(-1, op[1])), (name, op)
+            assert _bits_equal_f32(t.numpy(), prev.reshape(-1, op[1])), (name, op)
     walked = t.numpy()
     assert walked.shape == (batch, 10)
-    assert _bits_equal(net(i8ie.tensor(x)).numpy(), walked)
+    assert _bits_equal_f32(net(i8ie.tensor(x)).numpy(), walked)

@@ -8,19 +8,14 @@ import numpy as np
 import pytest
 
 import abi
+import support
 import synth
 
 pytestmark = pytest.mark.gpu
 N_CASES = int(os.environ.get("I8IE_FUZZ_CASES", "48"))
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    import int8inferenceengine_amd  # noqa: F401
-
-    g = abi.Ctx(0)
-    yield g
-    g.close()
+gpu = support.ctx_fixture()
 
 
 @pytest.fixture(scope="module")

@@ -14,16 +14,12 @@ import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path
 import net_cases as nc
 import orc
 import spec_ref as sr
+import support
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    gr.bind(abi.lib())
-    yield c
-    c.close()
+ctx = support.ctx_fixture(gr)
 
 
 # (name, m, c, kc, groups, k, stride, pad, h, w)

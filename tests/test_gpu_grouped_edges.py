@@ -16,6 +16,7 @@ import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import orc
 import spec_ref as sr
+import support
 
 pytestmark = pytest.mark.gpu
 
@@ -25,12 +26,7 @@ BY_NAME = {c.name: c for c in EDGE}
 GCONV = {"gconv_mfma", "gconv_direct"}
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    gr.bind(abi.lib())
-    yield c
-    c.close()
+ctx = support.ctx_fixture(gr)
 
 
 def run(ctx, case, relu, names=None, guard=None, **over):
@@ -94,11 +90,6 @@ def test_both_kernels_agree_nhwc_relu(ctx, case):
         assert guard["ok"] and np.array_equal(guard["phys"], abi.Ctx.to_phys(want, c.ob, gc.ZP_OUT))
 
 
-class _Entry(C.Structure):
-    _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double), ("total_ops", C.c_double),
-                ("total_bytes", C.c_double)]
-
-
 @contextlib.contextmanager
 def kernels(ctx, names):
     """`names` receives the kernels launched inside"""
@@ -107,7 +98,7 @@ def kernels(ctx, names):
     try:
         yield
     finally:
-        ents, cnt = (_Entry * 64)(), C.c_int(0)
+        ents, cnt = (abi.ProfEntry * 64)(), C.c_int(0)
         abi.ck(lib.i8ie_profile_stop(ctx.h, ents, 64, C.byref(cnt)))
         names.extend(ents[i].name.decode().split("|")[0] for i in range(cnt.value))
 

@@ -13,33 +13,20 @@ import abi
 import grouped_ref as gr
 import groupnorm_ref as gn
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
-import layernorm_ref as lr
 import orc
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-QP = (f32(0.025), f32(0.02), 128, f32(1e-5))   # s_in, s_out, zp_out, eps
+QP = support.NORM_QP   # s_in, s_out, zp_out, eps
 # (C, G): cg = 1 (InstanceNorm), 2, 4, 10, 16, 32, G = 1, and two channel counts that are no multiple of 16 (direct)
 GROUPS = [(32, 32), (64, 32), (16, 4), (160, 16), (64, 4), (64, 2), (48, 1), (320, 32), (20, 5), (35, 7)]
 MAPS = [(1, 1), (3, 5), (8, 8), (7, 9)]
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    gn.bind(abi.lib())
-    yield c
-    c.close()
-
-
-def _params(ctx, Cn, seed, qp=QP):
-    rng = np.random.default_rng(seed)
-    gamma = rng.normal(1.0, 0.6, Cn).astype(f32)
-    beta = rng.normal(0.0, 0.6, Cn).astype(f32)
-    gamma[0] = 0.0
-    g, b = lr.affine(gamma, beta, qp[1], qp[2])
-    return gamma, beta, ctx.put(g), ctx.put(b)
+ctx = support.ctx_fixture(gn)
 
 
 def _images(rng, n, Cn, h, w):
@@ -98,7 +85,7 @@ def _run(ctx, q, G, dg, db, qp=QP, relu=False, fallback=False, bi=0, bo=0, in_s8
 def test_group_shapes_image_form_and_forced_fallback(ctx, Cn, G):
     """n = 3 images of distinct content (a mix-up of images or groups changes bytes), every map, relu on / off, in place"""
     rng = np.random.default_rng(500 + Cn + G)
-    gamma, beta, dg, db = _params(ctx, Cn, Cn)
+    gamma, beta, dg, db = support.norm_params(ctx, Cn, Cn)
     spread = set()
     for h, w in MAPS:
         assert gn.form(Cn, h, w) == ("direct" if Cn % 16 else "image")
@@ -126,7 +113,7 @@ def test_lds_budget_edge_and_split_form(ctx, Cn, G, h, w, n):
     assert edge or (h * w) % max(1, gn.CHUNK_BYTES // Cn) != 0
     assert not edge or h * w * Cn == gn.IMAGE_BYTES
     rng = np.random.default_rng(Cn + h)
-    gamma, beta, dg, db = _params(ctx, Cn, Cn + 1)
+    gamma, beta, dg, db = support.norm_params(ctx, Cn, Cn + 1)
     q = _images(rng, n, Cn, h, w)
     for relu in (False, True):
         want = gn.group_norm_u8(q, G, QP[0], QP[3], gamma, beta, QP[1], QP[2], relu)
@@ -143,7 +130,7 @@ def test_statistics_extremes_on_the_device(ctx, Cn, G):
     assert gn.form(Cn, 64, 64) == ("image" if Cn == 16 else "split")
     for name, q in gn.extreme_images(Cn, G):
         for qp in (QP, (f32(0.1), f32(0.05), 100, f32(1e-6))):
-            gamma, beta, dg, db = _params(ctx, Cn, 7 + Cn, qp)
+            gamma, beta, dg, db = support.norm_params(ctx, Cn, 7 + Cn, qp)
             want = gn.group_norm_u8(q, G, qp[0], qp[3], gamma, beta, qp[1], qp[2])
             for fallback in (False, True):
                 got = _run(ctx, q, G, dg, db, qp=qp, fallback=fallback)
@@ -156,7 +143,7 @@ def test_statistics_extremes_on_the_device(ctx, Cn, G):
 def test_layout_matrix_borders_rebias_relu_in_place_and_guards(ctx, Cn, G, h, w, n, fallback):
     rng = np.random.default_rng(40 + Cn)
     s_in, s_out, zp_out, eps = QP
-    gamma, beta, dg, db = _params(ctx, Cn, Cn)
+    gamma, beta, dg, db = support.norm_params(ctx, Cn, Cn)
     q = _images(rng, n, Cn, h, w)
     want = {relu: gn.group_norm_u8(q, G, s_in, eps, gamma, beta, s_out, zp_out, bool(relu)) for relu in (0, 1)}
     for bi, bo, in_s8, out_s8, relu in itertools.product((0, 1, 2), (0, 1, 3), (0, 1), (0, 1), (0, 1)):
@@ -204,28 +191,6 @@ def test_f32_against_float64(ctx, Cn, G, h, w):
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
-def _conv_ref(L, q, s_in, zp_in, pad=0, stride=1):
-    s_out, zp_out = L.output_qparams()
-    return gr.conv2d_grouped(q, L.layer.q_weight(), L.layer.q_bias(), 1, stride, pad, f32(s_in), zp_in, L.weight_scale(), f32(s_out), zp_out)[0]
-
-
 def _gn(i8ie, groups, c, seed, qp, eps=1e-5):
     rng = np.random.default_rng(seed)
     L = i8ie.GroupNorm(groups, c, eps)
@@ -235,25 +200,6 @@ def _gn(i8ie, groups, c, seed, qp, eps=1e-5):
     L.set_output_qparams(*qp)
     L.convert()
     return L, w, b
-
-
-def _counted(make):
-    """{kernel name: launches} of make() after one warm-up call (tests/test_gpu_layernorm.py)"""
-    import _CXX_i8ie as cx
-
-    for t in make():
-        t.numpy()
-    cx.synchronize()
-    cx.profile_start()
-    try:
-        for t in make():
-            t.data.layout()
-    finally:
-        prof = cx.profile_stop()
-    launches = {}
-    for k, v in prof.items():
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
-    return launches
 
 
 def test_surface_shapes_and_errors(i8ie):
@@ -302,26 +248,26 @@ def test_launch_counts_borders_and_bytes(i8ie, h, w, form):
     rng = np.random.default_rng(90)
     n, c = 2, 16
     assert gn.form(c, h, w) == form
-    stem0 = _conv(i8ie, 3, c, 3, 1, 9, (0.05, 128))
-    stem1 = _conv(i8ie, c, c, 3, 1, 11, (0.05, 128))
-    stem = _conv(i8ie, c, c, 3, 1, 1, (0.05, 120))
+    stem0 = support.conv(i8ie, 3, c, 3, 1, 9, (0.05, 128))
+    stem1 = support.conv(i8ie, c, c, 3, 1, 11, (0.05, 128))
+    stem = support.conv(i8ie, c, c, 3, 1, 1, (0.05, 120))
     g, gam, bet = _gn(i8ie, 4, c, 2, (0.02, 125))
-    tail = _conv(i8ie, c, 16, 3, 1, 5, (0.07, 100))
+    tail = support.conv(i8ie, c, 16, 3, 1, 5, (0.07, 100))
     q = i8ie.quantize(i8ie.tensor(rng.uniform(-3, 3, (n, 3, h, w)).astype(f32)), 0.025, 127)
     x = i8ie.relu(stem1(i8ie.relu(stem0(q))))
 
-    launches = _counted(lambda: [tail(i8ie.relu(g(stem(x))))])
+    launches = support.counted(lambda: [tail(i8ie.relu(g(stem(x))))])
     print(launches)
     mine = {k: v for k, v in launches.items() if k.startswith("groupnorm")}
     assert mine == gn.kernels(c, h, w) and sum(launches.values()) == (3 if form == "image" else 4), launches
     for k in launches:
         assert not k.startswith(("relu_u8", "rebias", "fill_border", "reborder", "layout_")), launches
     xv = x.numpy()
-    yv = _conv_ref(stem, xv, 0.05, 128, pad=1)
+    yv = support.conv_ref(stem, xv, 0.05, 128, pad=1)
     lv = gn.group_norm_u8(yv, 4, f32(0.05), f32(1e-5), gam, bet, f32(0.02), 125)
     assert len(np.unique(lv)) > 40
     assert np.array_equal(g(stem(x)).numpy(), lv)
-    assert np.array_equal(tail(i8ie.relu(g(stem(x)))).numpy(), _conv_ref(tail, np.maximum(lv, 125), 0.02, 125, pad=1))
+    assert np.array_equal(tail(i8ie.relu(g(stem(x)))).numpy(), support.conv_ref(tail, np.maximum(lv, 125), 0.02, 125, pad=1))
     # an NCHW input (user-made) goes through one layout conversion
     qn = i8ie.quantize(i8ie.tensor(rng.uniform(-3, 3, (n, c, h, w)).astype(f32)), 0.025, 127)
     assert np.array_equal(g(qn).numpy(), gn.group_norm_u8(qn.numpy(), 4, f32(0.025), f32(1e-5), gam, bet, f32(0.02), 125))
@@ -585,10 +531,6 @@ def _net(i8ie, per_channel):
     return _NET[per_channel]
 
 
-def _same(got, want):
-    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-
-
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [1, 5])
 def test_gn_net_bit_exact(i8ie, batch, per_channel, tmp_path):
@@ -605,10 +547,10 @@ def test_gn_net_bit_exact(i8ie, batch, per_channel, tmp_path):
     assert want.shape == (batch, 10) and len(np.unique(want)) > 1
     for k in ("a_gn1", "a_gn2", "d_gn", "b_gn1", "b_gn2", "s_gn"):   # the expected bytes discriminate
         assert len(np.unique(trace[k])) >= 32 and ((trace[k] == 0) | (trace[k] == 255)).mean() < 0.05, k
-    assert _same(net(i8ie.tensor(x)).numpy(), want), "eager"
+    assert support.same_bits(net(i8ie.tensor(x)).numpy(), want), "eager"
     net.trace = {}
     try:
-        assert _same(net(i8ie.tensor(x)).numpy(), want), "traced"
+        assert support.same_bits(net(i8ie.tensor(x)).numpy(), want), "traced"
         mine = net.trace
     finally:
         net.trace = None
@@ -620,16 +562,16 @@ def test_gn_net_bit_exact(i8ie, batch, per_channel, tmp_path):
         fb = net(i8ie.tensor(x)).numpy()
     finally:
         cx.force_fallback(False)
-    assert _same(fb, want), "force_fallback"
+    assert support.same_bits(fb, want), "force_fallback"
     g = GraphedForward(net, i8ie.tensor(x).prefetch())
     for _ in range(2):
-        assert _same(g().numpy(), want), "graph replay"
+        assert support.same_bits(g().numpy(), want), "graph replay"
     path = str(tmp_path / "gn_net.npz")
     net.save_quantized(path)
     fresh = _make_net(i8ie)
     fresh.load_quantized_file(path)
     assert {a: getattr(fresh, a).output_qparams() for a in qp} == qp and fresh.s_attn.score_qparams() == sq
-    assert _same(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
+    assert support.same_bits(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
 
 
 def test_gn_net_kernels_and_launches(i8ie):

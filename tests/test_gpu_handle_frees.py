@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import abi
+import support
 
 pytestmark = pytest.mark.gpu
 
@@ -24,11 +25,7 @@ LAYERS = {
 M = 2
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    yield c
-    c.close()
+ctx = support.ctx_fixture()
 
 
 def live(ctx):

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import abi
+import support
 
 pytestmark = pytest.mark.gpu
 
@@ -387,17 +388,10 @@ def expected_phys(cs, ref, zp_out=ZP_OUT):
 RECORDED_FIELDS = ("first", "warm", "queries", "error", "violations")
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    c = abi.Ctx(0)
-    yield c
-    c.close()
+gpu = support.ctx_fixture()
 
 
-@pytest.fixture(scope="module")
-def recorded():
-    with open(GOLDEN) as f:
-        return json.load(f)
+recorded = support.json_fixture(GOLDEN)
 
 
 @pytest.mark.parametrize("cid", list(CASES))

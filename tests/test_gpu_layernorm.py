@@ -12,11 +12,12 @@ import pytest
 import abi
 import attention_ref as ar
 import f64_ref
-import grouped_ref as gr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import layernorm_ref as lr
 import orc
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -24,30 +25,16 @@ f32 = np.float32
 # (lr.GROUP_WIDTHS) and where rows pass to layernorm_u8_block (lr.GROUP_MAX_C)
 WIDTHS = sorted(set([1, 2, 15, 16, 17, 48, 63, 64, 65, 96, 255, 256, 257, 1024, 1025, 4099, 16384]
                     + [w + d for w in lr.GROUP_WIDTHS + [lr.GROUP_MAX_C] for d in (-1, 0, 1)]))
-QP = (f32(0.025), f32(0.02), 128, f32(1e-5))   # s_in, s_out, zp_out, eps
+QP = support.NORM_QP   # s_in, s_out, zp_out, eps
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    lr.bind(abi.lib())
-    yield c
-    c.close()
+ctx = support.ctx_fixture(lr)
 
 
 def _kernel(Cn, fallback, offset):
     if fallback or offset % 16:
         return "layernorm_u8_direct"
     return "layernorm_u8_group" if Cn <= lr.GROUP_MAX_C else "layernorm_u8_block"
-
-
-def _params(ctx, Cn, seed, qp=QP):
-    rng = np.random.default_rng(seed)
-    gamma = rng.normal(1.0, 0.6, Cn).astype(f32)
-    beta = rng.normal(0.0, 0.6, Cn).astype(f32)
-    gamma[0] = 0.0
-    g, b = lr.affine(gamma, beta, qp[1], qp[2])
-    return gamma, beta, ctx.put(g), ctx.put(b)
 
 
 def _flat(ctx, a, dg, db, qp=QP, relu=False, fallback=False, offset=0, in_place=False):
@@ -77,7 +64,7 @@ def _flat(ctx, a, dg, db, qp=QP, relu=False, fallback=False, offset=0, in_place=
 @pytest.mark.parametrize("Cn", WIDTHS)
 def test_flat_rows_every_width_all_kernels(ctx, Cn):
     rng = np.random.default_rng(500 + Cn)
-    gamma, beta, dg, db = _params(ctx, Cn, Cn)
+    gamma, beta, dg, db = support.norm_params(ctx, Cn, Cn)
     spread = set()
     for rows in (1, 3, 67):
         a = rng.integers(0, 256, (rows, Cn), dtype=np.uint8)
@@ -98,7 +85,7 @@ def test_flat_rows_every_width_all_kernels(ctx, Cn):
 def test_statistics_extremes_on_the_device(ctx, name, a):
     Cn = a.shape[1]
     for qp in (QP, (f32(0.1), f32(0.05), 100, f32(1e-6))):
-        gamma, beta, dg, db = _params(ctx, Cn, 7 + Cn, qp)
+        gamma, beta, dg, db = support.norm_params(ctx, Cn, 7 + Cn, qp)
         want = lr.layer_norm_u8(a, qp[0], qp[3], gamma, beta, qp[1], qp[2])
         for fallback in (False, True):
             got = _flat(ctx, a, dg, db, qp=qp, fallback=fallback)
@@ -111,7 +98,7 @@ def test_direct_kernel_grid_strides(ctx):
     group and block kernels launch one group / block per row and do not stride.)"""
     rows, Cn = lr.DIRECT_ROWS_PER_PASS + 1, 2
     a = np.random.default_rng(1).integers(0, 256, (rows, Cn), dtype=np.uint8)
-    gamma, beta, dg, db = _params(ctx, Cn, 3)
+    gamma, beta, dg, db = support.norm_params(ctx, Cn, 3)
     gamma[:] = (1.5, -0.75)
     g, b = lr.affine(gamma, beta, QP[1], QP[2])
     dg.free(); db.free()
@@ -127,7 +114,7 @@ def test_nhwc_borders_rebias_relu_and_guards(ctx, Cn):
     rng = np.random.default_rng(40 + Cn)
     n, h, w = 2, 3, 5
     s_in, s_out, zp_out, eps = QP
-    gamma, beta, dg, db = _params(ctx, Cn, Cn)
+    gamma, beta, dg, db = support.norm_params(ctx, Cn, Cn)
     q = rng.integers(0, 256, (n, Cn, h, w), dtype=np.uint8)
     for i, (bi, bo, in_s8, out_s8, relu) in enumerate(itertools.product((0, 1, 2), (0, 1, 2), (0, 1), (0, 1), (0, 1))):
         fallback = bool(i % 3 == 2)
@@ -193,28 +180,6 @@ def test_f32_against_float64(ctx, Cn):
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
-def _conv_ref(L, q, s_in, zp_in, pad=0, stride=1):
-    s_out, zp_out = L.output_qparams()
-    return gr.conv2d_grouped(q, L.layer.q_weight(), L.layer.q_bias(), 1, stride, pad, f32(s_in), zp_in, L.weight_scale(), f32(s_out), zp_out)[0]
-
-
 def _ln(i8ie, c, seed, qp, eps=1e-5):
     rng = np.random.default_rng(seed)
     L = i8ie.LayerNorm(c, eps)
@@ -224,25 +189,6 @@ def _ln(i8ie, c, seed, qp, eps=1e-5):
     L.set_output_qparams(*qp)
     L.convert()
     return L, w, b
-
-
-def _counted(make):
-    """{kernel name: launches} of make() after one warm-up call (tests/test_gpu_attention.py)"""
-    import _CXX_i8ie as cx
-
-    for t in make():
-        t.numpy()
-    cx.synchronize()
-    cx.profile_start()
-    try:
-        for t in make():
-            t.data.layout()
-    finally:
-        prof = cx.profile_stop()
-    launches = {}
-    for k, v in prof.items():
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
-    return launches
 
 
 def test_surface_shapes_and_errors(i8ie):
@@ -289,34 +235,34 @@ def test_launch_counts_borders_and_bytes(i8ie):
     border in between"""
     rng = np.random.default_rng(90)
     n, c, h, w = 3, 16, 6, 5   # (16 channels: the convs keep the engine's NHWC layout, as in tests/test_gpu_attention.py)
-    stem0 = _conv(i8ie, 3, c, 3, 1, 9, (0.05, 128))
-    stem1 = _conv(i8ie, c, c, 3, 1, 11, (0.05, 128))
-    stem = _conv(i8ie, c, c, 3, 1, 1, (0.05, 120))
+    stem0 = support.conv(i8ie, 3, c, 3, 1, 9, (0.05, 128))
+    stem1 = support.conv(i8ie, c, c, 3, 1, 11, (0.05, 128))
+    stem = support.conv(i8ie, c, c, 3, 1, 1, (0.05, 120))
     ln, gam, bet = _ln(i8ie, c, 2, (0.02, 125))
-    tail = _conv(i8ie, c, 16, 3, 1, 5, (0.07, 100))
-    proj = [_conv(i8ie, c, 16, 1, 0, sd, (0.06, 120 + sd)) for sd in (3, 4, 6)]
+    tail = support.conv(i8ie, c, 16, 3, 1, 5, (0.07, 100))
+    proj = [support.conv(i8ie, c, 16, 1, 0, sd, (0.06, 120 + sd)) for sd in (3, 4, 6)]
     q = i8ie.quantize(i8ie.tensor(rng.uniform(-3, 3, (n, 3, h, w)).astype(f32)), 0.025, 127)
     # (two convs in front: the second one's result is an activation in the engine's layout, as in tests/test_gpu_mul.py)
     x = i8ie.relu(stem1(i8ie.relu(stem0(q))))
 
-    launches = _counted(lambda: [tail(i8ie.relu(ln(stem(x))))])
+    launches = support.counted(lambda: [tail(i8ie.relu(ln(stem(x))))])
     print(launches)
     assert launches.get("layernorm_u8_group") == 1 and sum(launches.values()) == 3, launches
     y = stem(x)
-    launches3 = _counted(lambda: (lambda t: [p(t) for p in proj])(ln(y)))
+    launches3 = support.counted(lambda: (lambda t: [p(t) for p in proj])(ln(y)))
     print(launches3)
     assert launches3.get("layernorm_u8_group") == 1 and sum(launches3.values()) == 4, launches3
     for k in list(launches) + list(launches3):
         assert not k.startswith(("relu_u8", "rebias", "fill_border", "reborder", "layout_")), (launches, launches3)
     xv = x.numpy()
-    yv = _conv_ref(stem, xv, 0.05, 128, pad=1)
+    yv = support.conv_ref(stem, xv, 0.05, 128, pad=1)
     lv = lr.layer_norm_u8_nchw(yv, f32(0.05), f32(1e-5), gam, bet, f32(0.02), 125)
     assert len(np.unique(lv)) > 40
     assert np.array_equal(ln(stem(x)).numpy(), lv)
-    assert np.array_equal(tail(i8ie.relu(ln(stem(x)))).numpy(), _conv_ref(tail, np.maximum(lv, 125), 0.02, 125, pad=1))
+    assert np.array_equal(tail(i8ie.relu(ln(stem(x)))).numpy(), support.conv_ref(tail, np.maximum(lv, 125), 0.02, 125, pad=1))
     t = ln(y)
     for p in proj:
-        assert np.array_equal(p(t).numpy(), _conv_ref(p, lv, 0.02, 125))
+        assert np.array_equal(p(t).numpy(), support.conv_ref(p, lv, 0.02, 125))
     # an NCHW input (user-made) goes through one layout conversion
     qn = i8ie.quantize(i8ie.tensor(rng.uniform(-3, 3, (n, c, h, w)).astype(f32)), 0.025, 127)
     qv = qn.numpy()

@@ -3,8 +3,6 @@ make_golden_layers.py; test_ref_layers_golden.py holds the oracle to the same fi
 (tests/abi.py) and the i8ie Python surface; reads committed fixtures only.  Bit exact except the FP32 forwards,
 which are compared within the rounding bound of tests/f64_ref.py."""
 import ctypes as C
-import json
-import os
 import struct
 
 import numpy as np
@@ -12,40 +10,15 @@ import pytest
 
 import abi
 import layer_cases as lc
-from conftest import GOLDEN, load_cases
+import support
+from conftest import load_cases
 from test_gpu_variants import NAMED
 from test_ref_layers_golden import N_CASES, N_KERNEL_CASES, _bits, _net_qparams, kernel_case
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    c = abi.Ctx(0)
-    yield c
-    c.close()
-
-
-class _Entry(C.Structure):
-    _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double),
-                ("total_ops", C.c_double), ("total_bytes", C.c_double)]
-
-
-def _kernels_run(gpu, fn):
-    lib = abi.lib()
-    abi.ck(lib.i8ie_profile_start(gpu.h, 0))
-    try:
-        res = fn()
-    finally:
-        ents = (_Entry * 64)()
-        n = C.c_int(0)
-        abi.ck(lib.i8ie_profile_stop(gpu.h, ents, 64, C.byref(n)))
-    return res, [ents[i].name.decode().split("|")[0] for i in range(n.value)]
-
-
-def _json(name):
-    with open(os.path.join(GOLDEN, name)) as f:
-        return json.load(f)
+gpu = support.ctx_fixture()
 
 
 def _case(name, i, kind):
@@ -148,7 +121,7 @@ def test_linear_layer_handle_relu_fallback_and_variants(gpu, i):
 def test_kernel_sized_cases_by_digest(gpu, orc, i):
     """One geometry each that a named kernel takes automatically (variant 0): the profile hooks show that it ran,
     and `out` and `acc` hash to what the reference's layer code produced (ref_kernel_digests.json)."""
-    k = _json("ref_kernel_digests.json")["cases"][i]
+    k = support.golden_json("ref_kernel_digests.json")["cases"][i]
     cs = kernel_case(orc, k)  # operands redrawn and checked; weights quantised by the (golden-pinned) oracle
     assert lc.sha(cs["q_w"]) == k["sha256"]["q_w"] and lc.sha(cs["q_b"]) == k["sha256"]["q_b"]
     geom = k["geom"]
@@ -156,7 +129,7 @@ def test_kernel_sized_cases_by_digest(gpu, orc, i):
         def run():
             return gpu.layer_forward_fused("linear", cs["q_in"], cs["q_w"], cs["q_b"], cs["s_in"], cs["zp_in"], cs["s_w"],
                                            cs["s_out"], cs["zp_out"])[:2]
-        (out, acc), names = _kernels_run(gpu, run)
+        (out, acc), names = gpu.kernels_run(run)
     elif k["kernel"].startswith("stem"):
         names = []
         out, acc = gpu.layer_forward_pool(cs["q_in"], cs["q_w"], cs["q_b"], cs["s_in"], cs["zp_in"], cs["s_w"], cs["s_out"],
@@ -167,7 +140,7 @@ def test_kernel_sized_cases_by_digest(gpu, orc, i):
             return gpu.layer_forward_fused("conv", cs["q_in"], cs["q_w"], cs["q_b"], cs["s_in"], cs["zp_in"], cs["s_w"],
                                            cs["s_out"], cs["zp_out"], stride=geom[6], pad=geom[7], in_nhwc=True,
                                            out_nhwc=True, in_border=geom[7])[:2]
-        (out, acc), names = _kernels_run(gpu, run)
+        (out, acc), names = gpu.kernels_run(run)
     assert any(nm.startswith(k["kernel"]) for nm in names), names
     assert lc.sha(acc) == k["sha256"]["acc"]
     assert lc.sha(out) == k["sha256"]["out"]
@@ -235,7 +208,7 @@ def test_alexnet_batch4_logits_are_the_references():
     import i8ie
     from int8inferenceengine_amd import workloads as wl
 
-    ref = _json("ref_alexnet_digests.json")
+    ref = support.golden_json("ref_alexnet_digests.json")
     net = wl.build("alexnet")
     net.load(wl.synthetic_state_dict("alexnet", seed=ref["weights_seed"]))
     for a, v in ref["qparams"].items():

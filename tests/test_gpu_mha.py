@@ -12,18 +12,15 @@ import abi
 import attention_ref as ar
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import mha_ref as mr
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 FILL = 0xC3
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    mr.bind(abi.lib())
-    yield c
-    c.close()
+ctx = support.ctx_fixture(mr)
 
 
 def qp_for(d, zp=(120, 131, 125, 140, 128), s_s=0.03):
@@ -31,11 +28,6 @@ def qp_for(d, zp=(120, 131, 125, 140, 128), s_s=0.03):
     ~40 score steps) and keep the softmax input scale where many table entries matter"""
     s = f32(np.sqrt(s_s * 40.0 / (5476.0 * np.sqrt(d))))
     return dict(s_q=s, zp_q=zp[0], s_k=s, zp_k=zp[1], s_v=f32(0.04), zp_v=zp[2], s_s=f32(s_s), zp_s=zp[3], s_o=f32(0.01), zp_o=zp[4])
-
-
-def rand_qkv(rng, b, tq, tk, c):
-    return (rng.integers(0, 256, (b, tq, c), dtype=np.uint8), rng.integers(0, 256, (b, tk, c), dtype=np.uint8),
-            rng.integers(0, 256, (b, tk, c), dtype=np.uint8))
 
 
 def run(ctx, q, k, v, heads, qp, relu=False, s8=(False, False, False), o_s8=False, fallback=False, offsets=(0, 0, 0), packed=False,
@@ -123,7 +115,7 @@ def test_grid_mfma_and_forced_direct(ctx, d):
     spread = 0
     for i in range(6):
         b, heads, tq, tk = (1, 3)[i % 2], (1, 2, 3)[i % 3], TQS[i], TKS[(i + d // 16) % 6]
-        q, k, v = rand_qkv(rng, b, tq, tk, heads * d)
+        q, k, v = support.rand_qkv(rng, b, tq, tk, heads * d)
         kw = dict(relu=bool(i & 1), s8=(bool(i & 1), bool(i & 2), bool(i & 4)), o_s8=bool(i & 2))
         want = check(ctx, q, k, v, heads, qp_for(d), "attn_mfma", **kw)
         check(ctx, q, k, v, heads, qp_for(d), "attn_direct", want=want, fallback=True, **kw)
@@ -136,7 +128,7 @@ def test_every_tq_meets_every_tk(ctx):
     """the full Tq x Tk product at d = 16, H = 2, b = 1 (the tail rules do not depend on d)"""
     rng = np.random.default_rng(77)
     for tq, tk in itertools.product(TQS, TKS):
-        q, k, v = rand_qkv(rng, 1, tq, tk, 32)
+        q, k, v = support.rand_qkv(rng, 1, tq, tk, 32)
         check(ctx, q, k, v, 2, qp_for(16), "attn_mfma")
 
 
@@ -144,7 +136,7 @@ def test_every_tq_meets_every_tk(ctx):
 @pytest.mark.parametrize("tk,kernel", [(1024, "attn_mfma"), (1025, "attn_direct")])
 def test_lds_limit(ctx, tk, kernel):
     rng = np.random.default_rng(tk)
-    q, k, v = rand_qkv(rng, 1, 65, tk, 64)
+    q, k, v = support.rand_qkv(rng, 1, 65, tk, 64)
     check(ctx, q, k, v, 1, qp_for(64), kernel, relu=True)
 
 
@@ -153,17 +145,17 @@ def test_lds_limit(ctx, tk, kernel):
 def test_direct_head_widths(ctx, d):
     rng = np.random.default_rng(300 + d)
     for b, heads, tq, tk in ((1, 1, 1, 1), (3, 2, 17, 33), (2, 3, 65, 70)):
-        q, k, v = rand_qkv(rng, b, tq, tk, heads * d)
+        q, k, v = support.rand_qkv(rng, b, tq, tk, heads * d)
         check(ctx, q, k, v, heads, qp_for(d), "attn_direct", s8=(True, False, True), relu=bool(d & 1))
 
 
 def test_direct_unaligned_pointers_and_long_rows(ctx):
     rng = np.random.default_rng(310)
-    q, k, v = rand_qkv(rng, 2, 17, 40, 32)
+    q, k, v = support.rand_qkv(rng, 2, 17, 40, 32)
     want = check(ctx, q, k, v, 2, qp_for(16), "attn_mfma")
     for offsets in ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1)):
         check(ctx, q, k, v, 2, qp_for(16), "attn_direct", want=want, offsets=offsets)
-    q, k, v = rand_qkv(rng, 1, 5, 3000, 32)
+    q, k, v = support.rand_qkv(rng, 1, 5, 3000, 32)
     check(ctx, q, k, v, 2, qp_for(16), "attn_direct", o_s8=True)
 
 
@@ -173,7 +165,7 @@ def test_zero_points_and_byte_extremes(ctx, fallback):
     kernel = "attn_direct" if fallback else "attn_mfma"
     rng = np.random.default_rng(40)
     b, heads, d, tq, tk = 2, 2, 16, 20, 200
-    q, k, v = rand_qkv(rng, b, tq, tk, heads * d)
+    q, k, v = support.rand_qkv(rng, b, tq, tk, heads * d)
     # every value on each of zp_q, zp_k, zp_v, zp_s, zp_o with the others central, then all at one extreme and mixed
     cases = [(128,) * 5] + [tuple(z if j == i else 128 for j in range(5)) for i in range(5) for z in (0, 255)]
     cases += [(0,) * 5, (255,) * 5, (0, 255, 0, 255, 0), (255, 0, 255, 0, 255), (0, 0, 255, 128, 255)]
@@ -195,7 +187,7 @@ def test_zero_points_and_byte_extremes(ctx, fallback):
     want = check(ctx, qd, kd, vd, 1, qp, kernel, fallback=fallback)
     assert (want[1][0, 0, :, 7] == 255).all() and (np.delete(want[1][0, 0], 7, axis=1) == 0).all()
     # Tk = 1: every probability is 255
-    q1, k1, v1 = rand_qkv(rng, 2, 33, 1, 32)
+    q1, k1, v1 = support.rand_qkv(rng, 2, 33, 1, 32)
     want = check(ctx, q1, k1, v1, 2, qp_for(16), kernel, fallback=fallback, relu=True)
     assert (want[1] == 255).all()
     # scales that saturate the scores at both ends
@@ -211,7 +203,7 @@ def test_operand_and_result_layouts(ctx, fallback):
     rng = np.random.default_rng(50)
     b, heads, d, h, w = 2, 2, 16, 5, 7
     t, c = h * w, heads * d
-    q, k, v = rand_qkv(rng, b, t, t, c)
+    q, k, v = support.rand_qkv(rng, b, t, t, c)
     qp = qp_for(d)
     want = mr.attention_u8(q, k, v, heads, **qp)
     for s8 in itertools.product([False, True], repeat=3):
@@ -264,42 +256,6 @@ def test_f32_entry_is_the_composition_bit_for_bit(ctx):
 
 
 # ---- 7: the Python surface --------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
-def _counted(make):
-    """{kernel name: launches} of make() after one warm-up call (tests/test_gpu_attention.py)"""
-    import _CXX_i8ie as cx
-
-    for t in make():
-        t.numpy()
-    cx.synchronize()
-    cx.profile_start()
-    try:
-        for t in make():
-            t.data.layout()
-    finally:
-        prof = cx.profile_stop()
-    launches = {}
-    for k, v in prof.items():
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
-    return launches
-
-
 def _quant(i8ie, a, s, zp):
     return i8ie.quantize(i8ie.tensor(a), s, zp)
 
@@ -361,21 +317,21 @@ def test_launch_counts_in_the_deferred_machinery(i8ie):
     re-bias come from the attention kernel); an unbordered producer is read with no conversion launch"""
     rng = np.random.default_rng(71)
     n, c, heads, h, w = 3, 32, 2, 6, 5
-    stem0, stem = _conv(i8ie, 3, c, 3, 1, 9, (0.05, 128)), _conv(i8ie, c, c, 3, 1, 1, (0.05, 120))
-    qkv = _conv(i8ie, c, 3 * c, 1, 0, 2, (0.02, 127))
-    proj = _conv(i8ie, c, c, 1, 0, 3, (0.05, 125))
-    tail = _conv(i8ie, c, 16, 3, 1, 5, (0.07, 100))
+    stem0, stem = support.conv(i8ie, 3, c, 3, 1, 9, (0.05, 128)), support.conv(i8ie, c, c, 3, 1, 1, (0.05, 120))
+    qkv = support.conv(i8ie, c, 3 * c, 1, 0, 2, (0.02, 127))
+    proj = support.conv(i8ie, c, c, 1, 0, 3, (0.05, 125))
+    tail = support.conv(i8ie, c, 16, 3, 1, 5, (0.07, 100))
     at = i8ie.Attention(heads)
     at.set_score_qparams(0.04, 140)
     at.set_output_qparams(0.012, 126)
     at.convert()
     x = i8ie.relu(stem(i8ie.relu(stem0(_quant(i8ie, rng.uniform(-3, 3, (n, 3, h, w)).astype(f32), 0.025, 127)))))
-    launches = _counted(lambda: [proj(at(qkv(x)))])
+    launches = support.counted(lambda: [proj(at(qkv(x)))])
     print(launches)
     assert launches.get("attn_mfma") == 1 and sum(launches.values()) == 3, launches
     p = qkv(x)
     p.data.layout()                                   # the producer has launched, unbordered
-    launches = _counted(lambda: [tail(i8ie.relu(at(p)))])
+    launches = support.counted(lambda: [tail(i8ie.relu(at(p)))])
     print(launches)
     assert launches.get("attn_mfma") == 1 and sum(launches.values()) == 2, launches
     for k in launches:
@@ -452,8 +408,8 @@ def test_operand_that_a_bordered_conv_consumed_first(i8ie):
 
     rng = np.random.default_rng(73)
     n, c, heads, h, w = 2, 16, 2, 5, 4
-    stem = _conv(i8ie, 3, 3 * c, 3, 1, 11, (0.03, 120))
-    tail = _conv(i8ie, 3 * c, 3 * c, 3, 1, 12, (0.05, 110))
+    stem = support.conv(i8ie, 3, 3 * c, 3, 1, 11, (0.03, 120))
+    tail = support.conv(i8ie, 3 * c, 3 * c, 3, 1, 12, (0.05, 110))
     x = _quant(i8ie, rng.uniform(-3, 3, (n, 3, h, w)).astype(f32), 0.025, 127)
     plain = stem(x).numpy()
     p = stem(x)
@@ -530,10 +486,6 @@ def _net(i8ie, per_channel):
     return _NET[per_channel]
 
 
-def _same(got, want):
-    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
-
-
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [1, 5])
 def test_mha_net_bit_exact(i8ie, batch, per_channel, tmp_path):
@@ -550,10 +502,10 @@ def test_mha_net_bit_exact(i8ie, batch, per_channel, tmp_path):
     assert want.shape == (batch, 10) and len(np.unique(want)) > 1
     for a in mr.NET_ATTENTIONS:   # the expected bytes discriminate: spread scores, probabilities and results
         assert len(np.unique(trace[a + ".S"])) > 30 and len(np.unique(trace[a + ".P"])) >= 16 and len(np.unique(trace[a])) >= 16
-    assert _same(net(i8ie.tensor(x)).numpy(), want), "eager"
+    assert support.same_bits(net(i8ie.tensor(x)).numpy(), want), "eager"
     net.trace = {}
     try:
-        assert _same(net(i8ie.tensor(x)).numpy(), want), "traced"
+        assert support.same_bits(net(i8ie.tensor(x)).numpy(), want), "traced"
         mine = net.trace
     finally:
         net.trace = None
@@ -565,17 +517,17 @@ def test_mha_net_bit_exact(i8ie, batch, per_channel, tmp_path):
         fb = net(i8ie.tensor(x)).numpy()
     finally:
         cx.force_fallback(False)
-    assert _same(fb, want), "force_fallback"
+    assert support.same_bits(fb, want), "force_fallback"
     g = GraphedForward(net, i8ie.tensor(x).prefetch())
     for _ in range(2):
-        assert _same(g().numpy(), want), "graph replay"
+        assert support.same_bits(g().numpy(), want), "graph replay"
     path = str(tmp_path / "mha_net.npz")
     net.save_quantized(path)
     fresh = _make_net(i8ie)
     fresh.load_quantized_file(path)
     assert {a: getattr(fresh, a).output_qparams() for a in qp} == qp
     assert {a: getattr(fresh, a).score_qparams() for a in sq} == sq
-    assert _same(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
+    assert support.same_bits(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
 
 
 def test_mha_net_kernels_and_launches(i8ie):

@@ -17,29 +17,15 @@ import mul_ref as mr
 import net_cases as nc
 import pointwise_util as pu
 import spec_ref as sr
+import support
+from support import i8ie, pairs  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 QP = dict(mr.QP)
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    mr.bind(abi.lib())
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def pairs(ctx):
-    """all 65 536 (a, b) byte pairs as flat tensors, resident on the device, and one output buffer"""
-    v = np.arange(256, dtype=np.uint8)
-    a, b = np.repeat(v, 256), np.tile(v, 256)
-    da, db, do = ctx.put(a), ctx.put(b), ctx.empty(a.shape, np.uint8)
-    yield a, b, da, db, do
-    for d in (da, db, do):
-        d.free()
+ctx = support.ctx_fixture(mr)
 
 
 def _mul_flat(ctx, pa, pb, po, n, qp, relu):
@@ -130,15 +116,11 @@ def test_exhaustive_byte_pairs_through_the_gate_kernel(ctx, c, gate_form):
         for name, relu in itertools.product(GATE_EXHAUSTIVE_SETS, (False, True)):
             qp = QP[name]
             got = _run_nhwc(ctx, a, g, True, borders, flags, qp, relu, keep)
-            want = _nchw_to_nhwc(_want(_nchw(a), g, qp, relu))
+            want = support.nhwc(_want(_nchw(a), g, qp, relu))
             bad = np.argwhere(got != want)
             assert bad.size == 0, (name, relu, bad[:4], [(a[tuple(i)], g[i[0], i[3]], got[tuple(i)], want[tuple(i)]) for i in bad[:4]])
     finally:
         _free(keep)
-
-
-def _nchw_to_nhwc(x):
-    return np.ascontiguousarray(x.transpose(0, 2, 3, 1))
 
 
 @pytest.mark.parametrize("form", ["equal", "gate"])
@@ -154,7 +136,7 @@ def test_bordered_nhwc(ctx, c, borders, form):
     for i, flags in enumerate(itertools.product((0, 1), repeat=3)):
         relu = (i + c) % 2
         got = _run_nhwc(ctx, a, b, gate, borders, flags, qp, bool(relu))
-        want = _nchw_to_nhwc(_want(_nchw(a), b if gate else _nchw(b), qp, bool(relu)))
+        want = support.nhwc(_want(_nchw(a), b if gate else _nchw(b), qp, bool(relu)))
         assert np.array_equal(got, want), (flags, relu)
 
 
@@ -210,7 +192,7 @@ def test_gate_kernel_tiling_edges(ctx, shape):
     qp = QP["gate_zp160"]
     borders, flags = ((1, 0, 1), (1, 0, 1)) if (h * w) % 2 else ((0, 1, 2), (0, 1, 0))
     got = _run_nhwc(ctx, a, g, True, borders, flags, qp, False)
-    assert np.array_equal(got, _nchw_to_nhwc(_want(_nchw(a), g, qp, False)))
+    assert np.array_equal(got, support.nhwc(_want(_nchw(a), g, qp, False)))
 
 
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 1025])
@@ -243,23 +225,6 @@ def test_fp32_bit_patterns(ctx, n):
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
 def _linear(i8ie, fin, fout, seed, qp):
     rng = np.random.default_rng(seed)
     L = i8ie.Linear(fin, fout)
@@ -273,7 +238,7 @@ def _linear(i8ie, fin, fout, seed, qp):
 def test_surface_shapes_mixed_layouts_and_errors(i8ie):
     rng = np.random.default_rng(11)
     x = rng.uniform(-2, 2, (2, 16, 8, 8)).astype(f32)
-    conv = _conv(i8ie, 16, 16, 3, 1, 5, (0.05, 120))
+    conv = support.conv(i8ie, 16, 16, 3, 1, 5, (0.05, 120))
     q = i8ie.quantize(i8ie.tensor(x), 0.025, 127)          # NCHW bytes
     qv = q.numpy()
     yv = conv(q).numpy()                                   # (observed on a tensor of its own: the operands below stay as they lie)
@@ -344,32 +309,13 @@ def test_surface_shapes_mixed_layouts_and_errors(i8ie):
     assert np.array_equal(m(conv(q), gq).numpy(), mr.mul_u8(yv, 120, f32(0.05), gv, 0, s_g, f32(0.04), 110))
 
 
-def _counted(make):
-    """{kernel name: launches} of make() -- a function that returns the tensors to launch -- after one warm-up call"""
-    import _CXX_i8ie as cx
-
-    for t in make():
-        t.numpy()
-    cx.synchronize()
-    cx.profile_start()
-    try:
-        for t in make():
-            t.data.layout()  # launches what is pending; the bytes are observed outside the counted region
-    finally:
-        prof = cx.profile_stop()
-    launches = {}
-    for k, v in prof.items():  # (a kernel name may come with several shapes behind the bar)
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
-    return launches
-
-
 def test_squeeze_excite_block_launch_counts(i8ie):
     """conv_c(relu(mul(x, g))) with x = conv0(..) and g = hardsigmoid(fc2(relu(fc1(gap(x))))) is exactly the launches of its
     producers -- x and g observed on their own, conv_c on an activation of the same shape -- plus ONE mul launch: conv0 feeds
     the pool and the mul from one launch, the relu folds into the mul, and the padded conv_c gets its border (and re-biased
     bytes, where it reads them) from the mul kernel; nothing converts, re-biases or fills."""
-    conv0 = _conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110))
-    conv_c = _conv(i8ie, 16, 16, 3, 1, 6, (0.08, 90))
+    conv0 = support.conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110))
+    conv_c = support.conv(i8ie, 16, 16, 3, 1, 6, (0.08, 90))
     fc1, fc2 = _linear(i8ie, 16, 8, 2, (0.02, 100)), _linear(i8ie, 8, 16, 3, (0.03, 128))
     hs = i8ie.Activation("hardsigmoid")
     hs.set_output_qparams(1 / 255, 0)
@@ -380,7 +326,7 @@ def test_squeeze_excite_block_launch_counts(i8ie):
     xin = np.random.default_rng(4).uniform(-2, 2, (2, 3, 8, 8)).astype(f32)
     # an activation in the engine's layout that stays recorded (as in tests/test_gpu_add.py): the warm-up forward launches it
     # once, with the border its consumer asks for, and the counted forward finds that result
-    q = i8ie.relu(_conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(_conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
+    q = i8ie.relu(support.conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(support.conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
         i8ie.quantize(i8ie.tensor(xin), 0.025, 127)))))
 
     def gate(x):
@@ -394,9 +340,9 @@ def test_squeeze_excite_block_launch_counts(i8ie):
         x = conv0(q)
         return [conv_c(i8ie.relu(mul(x, gate(x))))]
 
-    made = _counted(producers)      # conv0 once, the pool, the two Linears (with whatever their routes launch), the hardsigmoid
-    behind = _counted(lambda: [conv_c(q)])
-    whole = _counted(forward)
+    made = support.counted(producers)      # conv0 once, the pool, the two Linears (with whatever their routes launch), the hardsigmoid
+    behind = support.counted(lambda: [conv_c(q)])
+    whole = support.counted(forward)
     print(made, behind, whole)
     assert sum(behind.values()) == 1 and sum(v for k, v in made.items() if k.startswith(("avgpool", "lut_u8"))) == 2
     want_launches = dict(made)

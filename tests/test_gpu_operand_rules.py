@@ -12,6 +12,8 @@ import avgpool_ref as apr
 import concat_ref as cr
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import mul_ref as mr
+import support
+from support import i8ie  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -47,23 +49,6 @@ LAYOUTS = {
 COUNTED = ("pending", "consumed", "same", "reads")
 
 
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
 class _World:
     """the layers and inputs every case shares; `base` is an activation in the engine's layout that stays recorded (the first
     forward launches it once, bordered for the 3x3 pad-1 convs that read it, and every later one finds that result)"""
@@ -75,11 +60,11 @@ class _World:
         self.g_odd = rng.uniform(-2, 2, (2, 3, 1, 1)).astype(f32)
         self.x_rows = rng.uniform(-2, 2, (2, 16 * 8 * 8)).astype(f32)
         self.qp_a, self.qp_o, self.qp_f = (0.05, 120), (0.06, 130), (0.045, 115)
-        self.conv_a = _conv(i8ie, 16, 16, 3, 1, 2, self.qp_a)  # makes the operand under test
-        self.conv_o = _conv(i8ie, 16, 16, 3, 1, 3, self.qp_o)  # makes the other operand
-        self.conv_f = _conv(i8ie, 16, 16, 3, 1, 4, self.qp_f)  # f of "reads"
-        self.conv_c = _conv(i8ie, 16, 16, 3, 1, 5, (0.055, 122))  # the consumer of "consumed"
-        self.base = i8ie.relu(_conv(i8ie, 16, 16, 3, 1, 1, (0.05, 125))(i8ie.quantize(i8ie.tensor(self.x), 0.025, 127)))
+        self.conv_a = support.conv(i8ie, 16, 16, 3, 1, 2, self.qp_a)  # makes the operand under test
+        self.conv_o = support.conv(i8ie, 16, 16, 3, 1, 3, self.qp_o)  # makes the other operand
+        self.conv_f = support.conv(i8ie, 16, 16, 3, 1, 4, self.qp_f)  # f of "reads"
+        self.conv_c = support.conv(i8ie, 16, 16, 3, 1, 5, (0.055, 122))  # the consumer of "consumed"
+        self.base = i8ie.relu(support.conv(i8ie, 16, 16, 3, 1, 1, (0.05, 125))(i8ie.quantize(i8ie.tensor(self.x), 0.025, 127)))
 
 
 @pytest.fixture(scope="module")

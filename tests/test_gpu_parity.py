@@ -6,17 +6,14 @@ import pytest
 
 import abi
 import requant_ref
+import support
 import synth
 from conftest import load_cases
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    c = abi.Ctx(0)
-    yield c
-    c.close()
+gpu = support.ctx_fixture()
 
 
 # ---------------------------------------------------------------- elementwise --

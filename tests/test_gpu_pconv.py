@@ -8,12 +8,11 @@ tile counts that leave blocks with 0 / 1 / several tiles; bordered and plain out
 fused ReLU; patches that fit LDS twice (ring of whole patches) and C = 384 ones that do not (ring of channel
 slices, K slice-major, with and without K padding inside a slice).  The profile hooks confirm that the kernel
 under test is the one that ran."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import abi
+import support
 import synth
 
 pytestmark = pytest.mark.gpu
@@ -21,28 +20,7 @@ pytestmark = pytest.mark.gpu
 VARIANTS = {50: "pconv", 54: "pconv", 70: "tconv"}
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    c = abi.Ctx(0)
-    yield c
-    c.close()
-
-
-class _Entry(C.Structure):
-    _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double),
-                ("total_ops", C.c_double), ("total_bytes", C.c_double)]
-
-
-def _kernels_run(gpu, fn):
-    lib = abi.lib()
-    abi.ck(lib.i8ie_profile_start(gpu.h, 0))
-    try:
-        res = fn()
-    finally:
-        ents = (_Entry * 64)()
-        n = C.c_int(0)
-        abi.ck(lib.i8ie_profile_stop(gpu.h, ents, 64, C.byref(n)))
-    return res, [ents[i].name.decode().split("|")[0] for i in range(n.value)]
+gpu = support.ctx_fixture()
 
 
 GEOMS = [
@@ -81,7 +59,7 @@ def test_pconv_bit_exact(gpu, orc, geom, relu, ob, VARIANT):
         finally:
             abi.ck(lib.i8ie_ctx_set_option(gpu.h, 2, 0))
 
-    (out, acc, _), names = _kernels_run(gpu, run)  # (the harness also checks that border bytes stay zp_out)
+    (out, acc, _), names = gpu.kernels_run(run)  # (the harness also checks that border bytes stay zp_out)
     if not (VARIANT == 70 and k * k * c < 512):  # (the team kernel leaves K < 4 K tiles to the others)
         assert any(nm.startswith(VARIANTS[VARIANT]) for nm in names), names
     want = orc.relu(cs["out"], cs["zp_out"]) if relu else cs["out"]

@@ -10,16 +10,13 @@ import numpy as np
 import pytest
 
 import abi
+import support
 import synth
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    c = abi.Ctx(0)
-    yield c
-    c.close()
+gpu = support.ctx_fixture()
 
 
 def _cases(n_cases, seed):

@@ -16,16 +16,13 @@ import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path
 import orc
 import pc_pipeline as pcp
 from requant_ref import row_scales, s_out_for  # (shared with the requantiser's dense sweeps)
+import support
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    yield c
-    c.close()
+ctx = support.ctx_fixture()
 
 
 CONVS = [  # (name, m, c, h, kc, k, stride, pad)

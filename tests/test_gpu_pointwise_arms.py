@@ -19,6 +19,7 @@ import act_ref
 import add_ref
 import mul_ref
 import pointwise_util as pu
+import support
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -31,13 +32,7 @@ ADD_QP = (f32(0.043), 119, f32(0.027), 131, f32(0.061), 97)
 OPS = ["add", "mul", "gate"]
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    for m in (add_ref, mul_ref, act_ref):
-        m.bind(abi.lib())
-    yield c
-    c.close()
+ctx = support.ctx_fixture(add_ref, mul_ref, act_ref)
 
 
 def _at(dev, skew):
@@ -48,15 +43,11 @@ def _nchw(x):
     return np.ascontiguousarray(x.transpose(0, 3, 1, 2))
 
 
-def _nhwc(x):
-    return np.ascontiguousarray(x.transpose(0, 2, 3, 1))
-
-
 def _want(op, a, b, qp, relu):
     s_a, zp_a, s_b, zp_b, s_out, zp_out = qp
     if op == "add":
         return add_ref.add_u8(a, zp_a, s_a, b, zp_b, s_b, s_out, zp_out, relu)
-    return _nhwc(mul_ref.mul_u8(_nchw(a), zp_a, s_a, b if op == "gate" else _nchw(b), zp_b, s_b, s_out, zp_out, relu))
+    return support.nhwc(mul_ref.mul_u8(_nchw(a), zp_a, s_a, b if op == "gate" else _nchw(b), zp_b, s_b, s_out, zp_out, relu))
 
 
 def _run(ctx, op, a, b, borders, flags, skews, qp, relu):

@@ -19,6 +19,7 @@ import attention_ref as ar
 import mha_ref as mr
 import requant_cases as rc
 import requant_ref as rq
+import support
 import test_gpu_attention as tga
 import test_gpu_layer_routes as lr
 import test_gpu_mha as tgm
@@ -28,12 +29,7 @@ f32 = np.float32
 SEEN = {}   # case id -> launch map, for test_every_kernel_of_the_table_ran
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    c = abi.Ctx(0)
-    mr.bind(abi.lib())
-    yield c
-    c.close()
+gpu = support.ctx_fixture(mr)
 
 
 # ---- the layer sites ---------------------------------------------------------------------------------------------------------

@@ -16,6 +16,8 @@ import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path
 import net_cases as nc
 import pointwise_util as pu
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 import upsample_ref as ur
 
 pytestmark = pytest.mark.gpu
@@ -25,22 +27,10 @@ MODE_NAME = {ur.NEAREST: "nearest", ur.BILINEAR: "bilinear"}
 KERNEL = {ur.NEAREST: "upsample_nearest_u8_nhwc", ur.BILINEAR: "upsample_bilinear_u8_nhwc"}
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = abi.Ctx()
-    ur.bind(abi.lib())
-    yield c
-    c.close()
+ctx = support.ctx_fixture(ur)
 
 
-@pytest.fixture(scope="module")
-def i8ie():
-    import i8ie as mod
-
-    return mod
-
-
-def _same(got, want, tag):
+def _assert_same(got, want, tag):
     """bit equality, with the first few places that differ in the message"""
     assert got.shape == want.shape, (tag, got.shape, want.shape)
     bad = np.argwhere(got != want)
@@ -129,10 +119,10 @@ def test_every_rounding_case(ctx, fh, fw):
     assert (D // 2 in reached) == (D // 2 in reachable)
     for mode in MODES:
         want = ur.upsample_u8(q, fh, fw, mode)
-        assert _same(_nchw(ctx, q, fh, fw, mode), want, (fh, fw, mode, "nchw"))
-        assert _same(_nhwc(ctx, q, fh, fw, mode), want, (fh, fw, mode, "nhwc"))
+        assert _assert_same(_nchw(ctx, q, fh, fw, mode), want, (fh, fw, mode, "nchw"))
+        assert _assert_same(_nhwc(ctx, q, fh, fw, mode), want, (fh, fw, mode, "nhwc"))
         for zp in (0, 128, 255):
-            assert _same(_nhwc(ctx, q, fh, fw, mode, True, zp), ur.upsample_u8(q, fh, fw, mode, True, zp), (fh, fw, mode, zp))
+            assert _assert_same(_nhwc(ctx, q, fh, fw, mode, True, zp), ur.upsample_u8(q, fh, fw, mode, True, zp), (fh, fw, mode, zp))
 
 
 # ---- 2. edges ----------------------------------------------------------------------------------------------------------
@@ -144,8 +134,8 @@ def test_edges(ctx, c):
         q = rng.integers(0, 256, (n, c, h, w), dtype=np.uint8)
         for (fh, fw), mode in itertools.product([(2, 2), (3, 4), (8, 1)], MODES):
             want = ur.upsample_u8(q, fh, fw, mode)
-            assert _same(_nhwc(ctx, q, fh, fw, mode, ib=1, ob=1), want, (n, c, h, w, fh, fw, mode, "nhwc"))
-            assert _same(_nchw(ctx, q, fh, fw, mode), want, (n, c, h, w, fh, fw, mode, "nchw"))
+            assert _assert_same(_nhwc(ctx, q, fh, fw, mode, ib=1, ob=1), want, (n, c, h, w, fh, fw, mode, "nhwc"))
+            assert _assert_same(_nchw(ctx, q, fh, fw, mode), want, (n, c, h, w, fh, fw, mode, "nchw"))
 
 
 # ---- 3. the layout matrix ----------------------------------------------------------------------------------------------
@@ -160,7 +150,7 @@ def test_layout_matrix(ctx, c):
                 want = ur.upsample_u8(q, fh, fw, mode, relu, zp)
                 for ib, ob, in_s8, out_s8 in itertools.product((0, 1, 2), (0, 1, 2), (0, 1), (0, 1)):
                     got = _nhwc(ctx, q, fh, fw, mode, relu, zp, ib, ob, in_s8, out_s8)
-                    assert _same(got, want, (c, fh, fw, mode, relu, zp, ib, ob, in_s8, out_s8))
+                    assert _assert_same(got, want, (c, fh, fw, mode, relu, zp, ib, ob, in_s8, out_s8))
 
 
 # ---- 4. a grid that wraps ----------------------------------------------------------------------------------------------
@@ -173,8 +163,8 @@ def test_many_blocks(ctx, shape):
         assert shape[0] * shape[2] * shape[3] * (shape[1] // 4) > 2048 * 256
     for mode in MODES:
         want = ur.upsample_u8(q, 2, 2, mode, True, 100)
-        assert _same(_nhwc(ctx, q, 2, 2, mode, True, 100, ib=1, ob=1, out_s8=1), want, (mode, "nhwc"))
-        assert _same(_nchw(ctx, q, 2, 2, mode), ur.upsample_u8(q, 2, 2, mode), (mode, "nchw"))
+        assert _assert_same(_nhwc(ctx, q, 2, 2, mode, True, 100, ib=1, ob=1, out_s8=1), want, (mode, "nhwc"))
+        assert _assert_same(_nchw(ctx, q, 2, 2, mode), ur.upsample_u8(q, 2, 2, mode), (mode, "nchw"))
 
 
 # ---- 5. FP32 -----------------------------------------------------------------------------------------------------------
@@ -232,41 +222,6 @@ def test_c_entry_argument_errors(ctx):
 
 
 # ---- 7. the Python surface -----------------------------------------------------------------------------------------------
-def _conv(i8ie, cin, cout, k, pad, seed, qp, stride=1):
-    rng = np.random.default_rng(seed)
-    L = i8ie.Conv2d(cin, cout, k, stride=stride, padding=pad)
-    L.load_weight((rng.uniform(-1, 1, (cout, cin, k, k)) * np.sqrt(6.0 / (cin * k * k))).astype(f32))
-    L.load_bias(rng.uniform(-0.1, 0.1, cout).astype(f32))
-    L.set_output_qparams(*qp)
-    L.convert()
-    return L
-
-
-def _activation(i8ie, hw=8):
-    """an activation as it is inside a network: in the engine's layout, still recorded (test_gpu_add.py's construction)"""
-    xin = np.random.default_rng(4).uniform(-2, 2, (2, 3, hw, hw)).astype(f32)
-    return i8ie.relu(_conv(i8ie, 16, 16, 3, 1, 8, (0.05, 125))(i8ie.relu(_conv(i8ie, 3, 16, 3, 1, 9, (0.05, 128))(
-        i8ie.quantize(i8ie.tensor(xin), 0.025, 127)))))
-
-
-def _counted(forward):
-    import _CXX_i8ie as cx
-
-    first = forward().numpy()  # (packs weights, fills cached borders)
-    cx.synchronize()
-    cx.profile_start()
-    try:
-        y = forward()
-        y.data.layout()  # launches what is pending; the bytes are observed outside the counted region
-    finally:
-        prof = cx.profile_stop()
-    print(prof)
-    launches = {}
-    for k, v in prof.items():  # (a kernel name comes once per problem size: the sizes are summed)
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
-    return first, y.numpy(), launches
-
-
 FOREIGN = ("relu_u8", "rebias", "fill_border", "reborder", "layout_", "upsample_u8_nchw")
 
 
@@ -274,9 +229,9 @@ FOREIGN = ("relu_u8", "rebias", "fill_border", "reborder", "layout_", "upsample_
 def test_conv_upsample_relu_conv_is_three_launches(i8ie, mode):
     """conv -> upsample -> relu -> conv(3x3 pad 1): one launch each; the relu folds into the upsample, whose kernel writes the
     border and the bytes the second conv asks for"""
-    q = _activation(i8ie)
-    conv0, conv_c = _conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110)), _conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
-    first, got, launches = _counted(lambda: conv_c(i8ie.relu(i8ie.upsample(conv0(q), 2, mode))))
+    q = support.activation(i8ie)
+    conv0, conv_c = support.conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110)), support.conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120))
+    first, got, launches = support.counted_forward(lambda: conv_c(i8ie.relu(i8ie.upsample(conv0(q), 2, mode))))
     mid = i8ie.relu(i8ie.upsample(conv0(q), 2, mode))
     assert mid.shape == (2, 16, 16, 16) and mid.scale == pytest.approx(0.04) and mid.zero_point == 110
     assert np.array_equal(mid.numpy(), ur.upsample_u8(conv0(q).numpy(), 2, 2, mode, True, 110))
@@ -292,8 +247,8 @@ def test_upsample_into_add_with_bordered_skip(i8ie):
     as it lies; upsample and add are one launch each; nothing converts, re-biases or fills"""
     import add_ref as ar
 
-    q = _activation(i8ie, 16)
-    conv0, conv_d = _conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110)), _conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120), stride=2)
+    q = support.activation(i8ie, 16)
+    conv0, conv_d = support.conv(i8ie, 16, 16, 3, 1, 1, (0.04, 110)), support.conv(i8ie, 16, 16, 3, 1, 2, (0.05, 120), stride=2)
     add = i8ie.Add()
     add.set_output_qparams(0.07, 100)
     add.convert()
@@ -302,7 +257,7 @@ def test_upsample_into_add_with_bordered_skip(i8ie):
         x = i8ie.relu(conv0(q))
         return i8ie.relu(add(i8ie.upsample(i8ie.relu(conv_d(x)), 2, "nearest"), x))
 
-    first, got, launches = _counted(forward)
+    first, got, launches = support.counted_forward(forward)
     xv = i8ie.relu(conv0(q)).numpy()
     dv = i8ie.relu(conv_d(i8ie.relu(conv0(q)))).numpy()
     want = ar.add_u8(ur.upsample_u8(dv, 2, 2, "nearest"), 120, f32(0.05), xv, 110, f32(0.04), f32(0.07), 100, True)
@@ -368,11 +323,6 @@ def test_networks_bit_exact(i8ie, name, batch, per_channel):
     nc.check_bit_exact(i8ie, net, name, x, want, graph=name == "upsample_tiny")
 
 
-def _bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def test_fp32_upsample_tiny_layer_by_layer(i8ie):
     """Before convert(): walk the spec by hand with the FP32 ops, every op fed the product's own previous output -- convs
     inside f64_ref.dot_bound of the float64 result, the upsamples as test_fp32 has them, relu / pool / add / concat
@@ -399,21 +349,21 @@ def test_fp32_upsample_tiny_layer_by_layer(i8ie):
                 assert got.dtype == f32 and got.shape == want.shape and np.all(err <= bound), (op, float(np.nanmax(err / bound)))
             elif op[0] == "relu":
                 t = i8ie.relu(t)
-                assert _bits_equal(t.numpy(), f64_ref.relu(prev)), op
+                assert support.bits_equal(t.numpy(), f64_ref.relu(prev)), op
             elif op[0] == "pool":
                 t = i8ie.max_pool2d(t, op[1], op[2])
-                assert _bits_equal(t.numpy(), f64_ref.max_pool2d(prev.astype(np.float64), op[1], op[2])), op
+                assert support.bits_equal(t.numpy(), f64_ref.max_pool2d(prev.astype(np.float64), op[1], op[2])), op
             elif op[0] == "upsample":
                 fh, fw = ur.factors(op[1])
                 t = i8ie.upsample(t, op[1], op[2])
                 got = t.numpy()
                 seen.append(op)
                 if op[2] == "nearest":
-                    assert _bits_equal(got, ur.nearest(prev, fh, fw)), op
+                    assert support.bits_equal(got, ur.nearest(prev, fh, fw)), op
                 else:
                     val, mag = ur.bilinear_f64(prev, fh, fw)
                     assert got.shape == val.shape and np.all(np.abs(got.astype(np.float64) - val) <= 16 * 2.0 ** -24 * mag), op
-                    assert _bits_equal(got, ur.upsample_f32(prev, fh, fw, "bilinear")), op
+                    assert support.bits_equal(got, ur.upsample_f32(prev, fh, fw, "bilinear")), op
             elif op[0] == "save":
                 saved[op[1]] = t
             elif op[0] == "branch":
@@ -421,15 +371,15 @@ def test_fp32_upsample_tiny_layer_by_layer(i8ie):
             elif op[0] == "add":
                 other = saved[op[2]].numpy()
                 t = getattr(net, op[1])(t, saved[op[2]])
-                assert _bits_equal(t.numpy(), (prev + other).astype(f32)), op
+                assert support.bits_equal(t.numpy(), (prev + other).astype(f32)), op
             elif op[0] == "concat":
                 others = [saved[tag].numpy() for tag in op[2]]
                 t = getattr(net, op[1])([t] + [saved[tag] for tag in op[2]])
-                assert _bits_equal(t.numpy(), np.concatenate([prev] + others, axis=1)), op
+                assert support.bits_equal(t.numpy(), np.concatenate([prev] + others, axis=1)), op
             else:
                 raise AssertionError(op)
         return t
 
     walked = walk(spec, i8ie.tensor(x), {}).numpy()
     assert walked.shape == (3, 10, 32, 48) and len(seen) == 5
-    assert _bits_equal(net(i8ie.tensor(x)).numpy(), walked)
+    assert support.bits_equal(net(i8ie.tensor(x)).numpy(), walked)

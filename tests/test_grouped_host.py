@@ -8,6 +8,7 @@ import pytest
 
 import abi
 import grouped_ref as gr
+from support import i8ie  # noqa: F401
 
 
 @pytest.mark.parametrize("case", [(6, 9, 3, 3, 1, 1, 7, 9), (8, 16, 8, 3, 2, 0, 9, 9), (5, 7, 1, 3, 1, 1, 6, 5)],
@@ -26,14 +27,6 @@ def test_helper_equals_block_diagonal_dense_oracle(orc, case):
     # the offset vector: the reference's sequential fp32 sums over the [kc, Cg*kh*kw] matrix as it stands
     assert np.array_equal(orc.conv_offsets(qw.reshape(kc, -1), qb, s_in, zp_in),
                           orc.conv_offsets(gr.block_diagonal(qw, g).reshape(kc, -1), qb, s_in, zp_in))
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def test_conv2d_groups_surface(i8ie):

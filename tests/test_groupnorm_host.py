@@ -10,6 +10,8 @@ import pytest
 import abi
 import groupnorm_ref as gn
 import layernorm_ref as lr
+import support
+from support import i8ie  # noqa: F401
 
 f32 = np.float32
 ENTRIES = ["i8ie_groupnorm_u8_nhwc", "i8ie_groupnorm_workspace_bytes", "i8ie_groupnorm_f32"]
@@ -20,17 +22,7 @@ CASES = [(32, 32, 3, 5), (64, 32, 8, 8), (16, 4, 7, 9), (160, 16, 3, 5), (64, 4,
          (35, 7, 3, 5), (320, 32, 2, 3), (8, 8, 1, 1), (16, 16, 64, 64), (16, 1, 64, 64)]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return gn.bind(abi.lib())
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
+lib = support.lib_fixture(gn)
 
 
 def _params(Cn, seed):

@@ -9,6 +9,8 @@ import pytest
 
 import abi
 import layernorm_ref as lr
+import support
+from support import i8ie  # noqa: F401
 
 f32 = np.float32
 ENTRIES = ["i8ie_layernorm_affine", "i8ie_layernorm_u8", "i8ie_layernorm_u8_nhwc", "i8ie_layernorm_f32"]
@@ -16,17 +18,7 @@ ENTRIES = ["i8ie_layernorm_affine", "i8ie_layernorm_u8", "i8ie_layernorm_u8_nhwc
 QSETS = [(0.025, 127, 0.02, 128, 1e-5), (0.1, 0, 0.05, 100, 1e-6), (0.004, 255, 0.011, 0, 1e-3), (1.7, 13, 0.03, 255, 1e-5)]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return lr.bind(abi.lib())
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
+lib = support.lib_fixture(lr)
 
 
 def test_abi_symbols_declared_and_exported(lib):

@@ -9,14 +9,14 @@ import pytest
 import abi
 import attention_ref as ar
 import mha_ref as mr
+import support
+from support import i8ie  # noqa: F401
 
 f32 = np.float32
 QP = dict(s_q=f32(0.05), zp_q=120, s_k=f32(0.04), zp_k=131, s_v=f32(0.03), zp_v=7, s_s=f32(0.35), zp_s=140, s_o=f32(0.02), zp_o=9)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return mr.bind(abi.lib())
+lib = support.lib_fixture(mr)
 
 
 def test_header_declares_and_library_exports_the_entries(lib):
@@ -74,14 +74,6 @@ def test_argument_errors_need_no_gpu(lib):
     assert lib.i8ie_attention_f32(fake_ctx, C.byref(h)) == -1
 
 
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
-
-
 def test_surface_names(i8ie):
     import _CXX_i8ie as cx
 
@@ -126,14 +118,9 @@ def test_shape_and_type_errors_come_before_any_device_call(i8ie):
             bad()
 
 
-def _operands(rng, b, tq, tk, c):
-    return (rng.integers(0, 256, (b, tq, c), dtype=np.uint8), rng.integers(0, 256, (b, tk, c), dtype=np.uint8),
-            rng.integers(0, 256, (b, tk, c), dtype=np.uint8))
-
-
 def test_ref_with_one_head_is_the_three_attention_ref_calls(orc):
     rng = np.random.default_rng(11)
-    q, k, v = _operands(rng, 2, 7, 9, 12)
+    q, k, v = support.rand_qkv(rng, 2, 7, 9, 12)
     for relu in (False, True):
         S, P, acc, O = mr.attention_u8(q, k, v, 1, relu=relu, **QP)
         s = ar.matmul_u8(q, QP["zp_q"], QP["s_q"], k, QP["zp_k"], QP["s_k"], QP["s_s"], QP["zp_s"], transpose_b=True)
@@ -146,7 +133,7 @@ def test_ref_with_one_head_is_the_three_attention_ref_calls(orc):
 
 def test_ref_heads_are_column_slices_and_packed_equals_unpacked():
     rng = np.random.default_rng(12)
-    q, k, v = _operands(rng, 2, 5, 5, 12)
+    q, k, v = support.rand_qkv(rng, 2, 5, 5, 12)
     S, P, acc, O = mr.attention_u8(q, k, v, 3, **QP)
     for h in range(3):
         cs = slice(4 * h, 4 * h + 4)

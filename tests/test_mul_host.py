@@ -11,13 +11,10 @@ import abi
 import mul_ref as mr
 import pinned_networks as pn
 import spec_ref as sr
+import support
+from support import i8ie  # noqa: F401
 
 f32 = np.float32
-
-
-def _pairs():
-    v = np.arange(256, dtype=np.uint8)
-    return np.repeat(v, 256), np.tile(v, 256)
 
 
 # powers of two: fa, fb, their product and the quotient by s_out are exact in fp32 (|da * db| < 2^16), and so is the sum with
@@ -29,7 +26,7 @@ def _pairs():
 def test_restatement_equals_integer_arithmetic_for_power_of_two_scales(scales, zps, relu):
     """q = clamp(trunc((a - zp_a)(b - zp_b) k + zp_out)), k = s_a s_b / s_out = 2^-m, in integers: a negative value clamps to
     0 and a non-negative one truncates by the floor of the shift."""
-    a, b = _pairs()
+    a, b = support.byte_pairs()
     s_a, s_b, s_out = scales
     zp_a, zp_b, zp_out = zps
     k = s_a * s_b / s_out
@@ -45,7 +42,7 @@ def test_restatement_equals_integer_arithmetic_for_power_of_two_scales(scales, z
 
 @pytest.mark.parametrize("name,qp", mr.QP, ids=[q[0] for q in mr.QP])
 def test_restatement_commutes_with_swapped_parameters(name, qp):
-    a, b = _pairs()
+    a, b = support.byte_pairs()
     s_a, zp_a, s_b, zp_b, s_out, zp_out = qp
     for relu in (False, True):
         assert np.array_equal(mr.mul_u8(a, zp_a, s_a, b, zp_b, s_b, s_out, zp_out, relu), mr.mul_u8(b, zp_b, s_b, a, zp_a, s_a, s_out, zp_out, relu))
@@ -75,7 +72,7 @@ def test_saturation_relu_floor_and_gate_broadcast():
 
 
 def test_parameter_sets_cannot_pass_on_clamps_alone():
-    a, b = _pairs()
+    a, b = support.byte_pairs()
     assert len(mr.QP) >= 30 and len({n for n, _ in mr.QP}) == len(mr.QP) and len(mr.GATE_SETS) >= 5
     names = {n for n, _ in mr.QP}
     assert {"zero_s_a", "denormal_s_a", "denormal_products", "overflowing_products", "equal_saturating"} <= names
@@ -91,9 +88,7 @@ def test_parameter_sets_cannot_pass_on_clamps_alone():
     assert mostly_inside * 2 >= len(mr.QP), mostly_inside
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return mr.bind(abi.lib())
+lib = support.lib_fixture(mr)
 
 
 def test_new_symbols_are_declared_and_exported(lib):
@@ -146,14 +141,6 @@ def test_entry_points_check_arguments_before_any_device_call(lib):
     rc, msg = fp(b=odd, n=8, run=4)           # a gate is read element by element, but as floats
     assert rc == -1 and b"aligned" in msg
     assert flat(n=0)[0] == 0 and fp(n=0)[0] == 0 and fp(n=0, run=4)[0] == 0  # nothing to do: no device call either
-
-
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
 
 
 def test_surface_names_and_argument_rules(i8ie):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import abi
+from support import i8ie  # noqa: F401
 import upsample_ref as ur
 
 f32 = np.float32
@@ -123,14 +124,6 @@ def test_spec_op_is_walked():
 
 
 # ---- the surface --------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def i8ie():
-    import int8inferenceengine_amd  # noqa: F401
-    import i8ie as mod
-
-    return mod
-
-
 def test_surface_exports_upsample(i8ie):
     import _CXX_i8ie as cx
 
