@@ -18,7 +18,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def run(network, description):
+def run(network, description, report=None):
+    """report: called with the converted model behind the INT8 run, for what an example prints beyond the common lines"""
     ap = argparse.ArgumentParser(description=description)
     ap.add_argument("--batch", type=int, default=100)
     ap.add_argument("--batches", type=int, default=10)
@@ -78,6 +79,8 @@ def run(network, description):
     else:
         print("no labels: INT8 argmax agrees with FP32 argmax on %.2f %% of %d synthetic images"
               % (100.0 * (p_fp32 == p_int8).mean(), len(p_int8)))
+    if report is not None:
+        report(model)
     if args.save_quantized:
         model.save_quantized(args.save_quantized)
         again = wl.build(network)

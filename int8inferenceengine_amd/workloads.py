@@ -14,7 +14,8 @@ import numpy as np
 # name -> (layers, spec, input_shape CHW)
 #   layers: {attr: ("conv", in_c, out_c, k, stride, pad[, groups[, dilation]]) | ("fc", in_f, out_f)
 #                  | ("deconv", in_c, out_c, k, stride, pad, output_pad)   i8ie.ConvTranspose2d, weight [in_c, out_c, k, k]
-#                  | ("ln", channels)     i8ie.LayerNorm: float32 gamma / beta, no INT8 weights, no MACs}
+#                  | ("ln", channels)     i8ie.LayerNorm: float32 gamma / beta, no INT8 weights, no MACs
+#                  | ("gn", groups, channels)   i8ie.GroupNorm: every rule of "ln"}
 #   spec  : [("layer", attr) | ("relu",) | ("pool", k, s) | ("flatten", features)
 #            | ("save", tag)              remember the current tensor under `tag`
 #            | ("add", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Add (not in `layers`)
@@ -29,6 +30,9 @@ import numpy as np
 #            | ("matmul", attr, tag, transpose_a, transpose_b)   x = getattr(net, attr)(x, saved[tag]); attr names an
 #                                         i8ie.MatMul(transpose_a, transpose_b)
 #            | ("softmax",)               x = i8ie.softmax(x): scale 1/256, zero point 0, nothing to calibrate
+#            | ("attention", attr, heads)                x = getattr(net, attr)(x), x packed [n, 3c, h, w]; attr names an
+#                                         i8ie.Attention(heads)
+#            | ("attention", attr, heads, tag_k, tag_v)  x = getattr(net, attr)(x, saved[tag_k], saved[tag_v])
 #            | ("load", tag)              x = saved[tag] (what a branch computed becomes the current tensor)]
 NETWORKS = {
     # sample/notebooks/AlexNet_cifar10_resize224.ipynb:47-71
@@ -452,7 +456,8 @@ NETWORKS["aspp_tiny"] = _aspp_tiny()
 NETWORKS["deeplabv3_cifar"] = _deeplabv3_cifar()
 
 
-# {network: {attr: factor}}: what synthetic_state_dict folds into a layer's weight and bias (1.0 where nothing is named)
+# {network: {attr: factor}}: what synthetic_state_dict folds into a layer's weight and bias (1.0 where nothing is named); one
+# factor for the layer, or a float64 vector [out] of one per filter
 FOLDS = {}
 LAYER_SCALE = 0.5  # the layer-scale factor of a ConvNeXt block, folded into its second 1x1 conv
 
@@ -565,8 +570,126 @@ def _convnext_cifar(folds):
     return layers, spec, (3, 32, 32)
 
 
+def _mha(layers, spec, folds, qkv, attn, c, heads):
+    """Fused multi-head self-attention of the current [n, c, h, w] tensor: one packed 1x1 conv c -> 3c (query, key and value
+    filters in that order, the 1/sqrt(d) of the scores folded into the query filters) and one i8ie.Attention(heads)."""
+    layers[qkv] = ("conv", c, 3 * c, 1, 1, 0)
+    folds[qkv] = np.where(np.arange(3 * c) < c, 1.0 / np.sqrt(c // heads), 1.0)
+    spec += [("layer", qkv), ("attention", attn, heads)]
+
+
+def _silu(spec, p):
+    """x * sigmoid(x) of the current tensor x, with x the first operand of the Mul"""
+    spec += [("save", p + "g"), ("act", p + "sig", "sigmoid"), ("save", p + "sig"), ("load", p + "g"), ("mul", p + "mul", p + "sig")]
+
+
+def _mha_tiny(folds):
+    """3x32x32: conv 3->16 3x3 s2 p1, relu, max-pool 2/2 (8x8, t = 64), [LayerNorm, packed 1x1 conv 16 -> 48, Attention(2) at
+    d = 8 (attn_direct), 1x1 conv] + skip, relu, conv 16->32 3x3 s2 p1 (a bordered consumer; 4x4, t = 16), [three 1x1 convs,
+    Attention(2) of three tensors at d = 16 (attn_mfma), 1x1 conv] + skip, relu, global average pool, fc 32->10.  What the
+    Attention exists for."""
+    layers = {"c1": ("conv", 3, 16, 3, 2, 1), "ln1": ("ln", 16)}
+    spec = [("layer", "c1"), ("relu",), ("pool", 2, 2), ("save", "x1"), ("layer", "ln1")]
+    _mha(layers, spec, folds, "qkv1", "attn1", 16, 2)
+    layers.update({"proj1": ("conv", 16, 16, 1, 1, 0), "c2": ("conv", 16, 32, 3, 2, 1)})
+    for r in ("q2", "k2", "v2", "proj2"):
+        layers[r] = ("conv", 32, 32, 1, 1, 0)
+    layers["fc"] = ("fc", 32, 10)
+    folds["q2"] = 1.0 / np.sqrt(32 // 2)
+    spec += [("layer", "proj1"), ("add", "add1", "x1"), ("relu",), ("layer", "c2"),
+             ("save", "x2"), ("save", "k2"), ("save", "v2"), ("layer", "q2"), ("branch", "k2", [("layer", "k2")]),
+             ("branch", "v2", [("layer", "v2")]), ("attention", "attn2", 2, "k2", "v2"), ("layer", "proj2"), ("add", "add2", "x2"),
+             ("relu",), ("gap",), ("flatten", 32), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+def _botnet_cifar(folds):
+    """A ResNet-style network for 32x32 input whose last stage replaces the 3x3 convs of its bottleneck blocks with 4-head
+    self-attention (BoTNet, Srinivas et al. 2021, without the relative-position term): stem 3->32, a basic block at 32 (32x32),
+    one at 64 with a projection shortcut (16x16), conv 64->256 3x3 s2 (8x8, t = 64), two bottleneck blocks 256 -> 128 ->
+    attention at d = 32 -> 256, global average pool, fc 256->10"""
+    layers = {"stem": ("conv", 3, 32, 3, 1, 1), "s1a": ("conv", 32, 32, 3, 1, 1), "s1b": ("conv", 32, 32, 3, 1, 1),
+              "s2a": ("conv", 32, 64, 3, 2, 1), "s2b": ("conv", 64, 64, 3, 1, 1), "s2s": ("conv", 32, 64, 1, 2, 0),
+              "s3in": ("conv", 64, 256, 3, 2, 1)}
+    spec = [("layer", "stem"), ("relu",),
+            ("save", "x1"), ("layer", "s1a"), ("relu",), ("layer", "s1b"), ("add", "add1", "x1"), ("relu",),
+            ("save", "x2"), ("layer", "s2a"), ("relu",), ("layer", "s2b"), ("branch", "x2", [("layer", "s2s")]),
+            ("add", "add2", "x2"), ("relu",), ("layer", "s3in"), ("relu",)]
+    for p in ("b1", "b2"):
+        layers[p + "r"] = ("conv", 256, 128, 1, 1, 0)
+        spec += [("save", p), ("layer", p + "r"), ("relu",)]
+        _mha(layers, spec, folds, p + "qkv", p + "attn", 128, 4)
+        layers[p + "e"] = ("conv", 128, 256, 1, 1, 0)
+        spec += [("relu",), ("layer", p + "e"), ("add", "add_" + p, p), ("relu",)]
+    layers["fc"] = ("fc", 256, 10)
+    spec += [("gap",), ("flatten", 256), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+def _gn_block(layers, spec, p, in_c, c, groups, stride=1, shortcut="", relu=True):
+    """A basic residual block with a GroupNorm behind each conv: x = [relu](add(gn2(c2(relu(gn1(c1(x))))), skip)), skip = x or,
+    where `shortcut` names one, its 1x1 conv at the block's stride with `shortcut` + "gn" behind it.  groups: of gn1 and gn2"""
+    layers[p + "c1"], layers[p + "gn1"] = ("conv", in_c, c, 3, stride, 1), ("gn", groups[0], c)
+    layers[p + "c2"], layers[p + "gn2"] = ("conv", c, c, 3, 1, 1), ("gn", groups[1], c)
+    spec += [("save", p + "x"), ("layer", p + "c1"), ("layer", p + "gn1"), ("relu",), ("layer", p + "c2"), ("layer", p + "gn2")]
+    if shortcut:
+        layers[p + shortcut], layers[p + shortcut + "gn"] = ("conv", in_c, c, 1, stride, 0), ("gn", groups[1], c)
+        spec.append(("branch", p + "x", [("layer", p + shortcut), ("layer", p + shortcut + "gn")]))
+    spec += [("add", p + "add", p + "x")] + ([("relu",)] if relu else [])
+
+
+def _groupnorm_tiny(folds):
+    """3x32x32: conv 3->16 3x3 s2 p1, relu, max-pool 2/2 (8x8), a residual block at 16 channels with GN(4) and GN(16) (an
+    InstanceNorm; its first GN feeds a bordered consumer), conv 16->20 3x3 s2 p1 (4x4), GN(5), relu, a residual block at 20
+    channels with GN(1) and GN(10) and no relu behind its Add, the SiLU block [GN(4), x * sigmoid(x) (two consumers of one
+    pending GN), conv 3x3 p1, packed 1x1 conv 20 -> 60, Attention(2) at d = 10, 1x1 conv] + skip, relu, global average pool,
+    fc 20->10.  20 channels are no multiple of 16: those GroupNorms take the direct form, the 16-channel ones the image form.
+    What the GroupNorm exists for."""
+    layers = {"c1": ("conv", 3, 16, 3, 2, 1)}
+    spec = [("layer", "c1"), ("relu",), ("pool", 2, 2)]
+    _gn_block(layers, spec, "a_", 16, 16, (4, 16))
+    layers["down"], layers["d_gn"] = ("conv", 16, 20, 3, 2, 1), ("gn", 5, 20)
+    spec += [("layer", "down"), ("layer", "d_gn"), ("relu",)]
+    _gn_block(layers, spec, "b_", 20, 20, (1, 10), relu=False)
+    layers["s_gn"], layers["s_c"] = ("gn", 4, 20), ("conv", 20, 20, 3, 1, 1)
+    spec += [("save", "s_x"), ("layer", "s_gn")]
+    _silu(spec, "s_")
+    spec.append(("layer", "s_c"))
+    _mha(layers, spec, folds, "s_qkv", "s_attn", 20, 2)
+    layers["s_proj"], layers["fc"] = ("conv", 20, 20, 1, 1, 0), ("fc", 20, 10)
+    spec += [("layer", "s_proj"), ("add", "s_add", "s_x"), ("relu",), ("gap",), ("flatten", 20), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
+def _groupnorm_resnet_cifar(folds):
+    """A GroupNorm ResNet-18 for 32x32 input (Wu & He 2018: resnet18_cifar's topology with GroupNorm(32, c) behind every conv,
+    the shortcuts' included) with one diffusion-style block behind the 8x8 stage: GroupNorm, SiLU written as x * sigmoid(x),
+    3x3 conv, skip; then GroupNorm, 4-head self-attention at d = 64, 1x1 conv, skip, relu"""
+    layers = {"stem": ("conv", 3, 64, 3, 1, 1), "stem_gn": ("gn", 32, 64)}
+    spec = [("layer", "stem"), ("layer", "stem_gn"), ("relu",)]
+    in_c = 64
+    for s, (c, stride) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2))):
+        for b in range(2):
+            st = stride if b == 0 else 1
+            _gn_block(layers, spec, "s%db%d_" % (s, b), in_c, c, (32, 32), st, "sc" if st != 1 or in_c != c else "")
+            in_c = c
+        if c == 256:
+            layers["m_gn"], layers["m_c"], layers["m_gn2"] = ("gn", 32, c), ("conv", c, c, 3, 1, 1), ("gn", 32, c)
+            spec += [("save", "m_x"), ("layer", "m_gn")]
+            _silu(spec, "m_")
+            spec += [("layer", "m_c"), ("add", "m_add1", "m_x"), ("save", "m_x2"), ("layer", "m_gn2")]
+            _mha(layers, spec, folds, "m_qkv", "m_attn", c, 4)
+            layers["m_proj"] = ("conv", c, c, 1, 1, 0)
+            spec += [("layer", "m_proj"), ("add", "m_add2", "m_x2"), ("relu",)]
+    layers["fc"] = ("fc", 512, 10)
+    spec += [("gap",), ("flatten", 512), ("layer", "fc")]
+    return layers, spec, (3, 32, 32)
+
+
 for _name, _make in (("nonlocal_tiny", _nonlocal_tiny), ("nonlocal_resnet_cifar", _nonlocal_resnet_cifar),
-                     ("convnext_tiny", _convnext_tiny), ("convnext_cifar", _convnext_cifar)):
+                     ("convnext_tiny", _convnext_tiny), ("convnext_cifar", _convnext_cifar), ("mha_tiny", _mha_tiny),
+                     ("botnet_cifar", _botnet_cifar), ("groupnorm_tiny", _groupnorm_tiny),
+                     ("groupnorm_resnet_cifar", _groupnorm_resnet_cifar)):
     NETWORKS[_name] = _make(FOLDS.setdefault(_name, {}))
 
 
@@ -588,7 +711,7 @@ def _walk(spec):
 
 # the op names a spec may hold: build() refuses any other
 OPS = frozenset(("layer", "relu", "pool", "avgpool", "gap", "save", "branch", "add", "mul", "concat", "act", "upsample", "flatten",
-                 "matmul", "softmax", "load"))
+                 "matmul", "softmax", "load", "attention"))
 
 
 def conv_groups(L):
@@ -622,7 +745,8 @@ MAIN_PATH_MACS = frozenset((
 def _macs(layers, ops, hw, saved, branch_convs, in_branch=False):
     """MACs of the weighted layers of `ops` from an (h, w) map on, those of its branches included, with true taps (a dilated
     kernel's zeros are no work); without branch_convs a branch counts its Linears only.  Weighted layers only: a LayerNorm
-    has none, and the products of a ("matmul", ...) of two activations are not counted (no channel count is tracked here).
+    has none, and the products of a ("matmul", ...) or an ("attention", ...) of activations are not counted (no channel count is
+    tracked here).
     Returns (macs, (h, w) behind the ops)."""
     total = 0
     convs = branch_convs or not in_branch
@@ -641,7 +765,7 @@ def _macs(layers, ops, hw, saved, branch_convs, in_branch=False):
                 h, w = (h - 1) * s - 2 * p + k + op_, (w - 1) * s - 2 * p + k + op_
             elif L[0] == "fc":
                 total += L[1] * L[2]
-            # ("ln", c): no MACs, the same map
+            # ("ln", c), ("gn", groups, c): no MACs, the same map
         elif op[0] in ("pool", "avgpool"):
             h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
         elif op[0] == "gap":
@@ -657,7 +781,8 @@ def _macs(layers, ops, hw, saved, branch_convs, in_branch=False):
             t, saved[op[1]] = _macs(layers, op[2], saved[op[1]], saved, branch_convs, True)
             total += t
         # ("act", ...), like relu, flatten, add, mul and concat, has no MACs and keeps the shape; matmul and softmax leave
-        # (h, w) alone too: the map behind them is read only by 1x1 convs or replaced by a load
+        # (h, w) alone too: the map behind them is read only by 1x1 convs or replaced by a load.  So does attention, whose
+        # result has its query's map
     return total, (h, w)
 
 
@@ -669,25 +794,27 @@ def macs_per_image(name):
 
 
 def synthetic_state_dict(name, seed=42):
-    """He-uniform weights, U(-1/sqrt(fan_in), 1/sqrt(fan_in)) biases, both times the layer's factor in FOLDS; a LayerNorm gets
-    gamma from U(0.5, 1.5) and beta from U(-0.3, 0.3); keys '<attr>.weight'/'<attr>.bias'."""
+    """He-uniform weights, U(-1/sqrt(fan_in), 1/sqrt(fan_in)) biases, both times the layer's factor (or each filter's) in FOLDS;
+    a LayerNorm or GroupNorm gets gamma from U(0.5, 1.5) and beta from U(-0.3, 0.3); keys '<attr>.weight'/'<attr>.bias'."""
     rng = np.random.default_rng(seed)
     layers = network(name)[0]
     folds = FOLDS.get(name, {})
     sd = {}
     for attr, L in layers.items():
-        if L[0] == "ln":
-            sd[attr + ".weight"] = rng.uniform(0.5, 1.5, L[1]).astype(np.float32)
-            sd[attr + ".bias"] = rng.uniform(-0.3, 0.3, L[1]).astype(np.float32)
+        if L[0] in ("ln", "gn"):
+            sd[attr + ".weight"] = rng.uniform(0.5, 1.5, L[-1]).astype(np.float32)
+            sd[attr + ".bias"] = rng.uniform(-0.3, 0.3, L[-1]).astype(np.float32)
             continue
-        fold = folds.get(attr, 1.0)
+        fold = np.asarray(folds.get(attr, 1.0), np.float64)
         if L[0] == "deconv":  # [in, out, k, k]; an output pixel sums in * ceil(k / stride)^2 products
             shape, n_out = (L[1], L[2], L[3], L[3]), L[2]
             fan_in = L[1] * (-(-L[3] // L[4])) ** 2
         else:
             shape = (L[2], L[1] // conv_groups(L), L[3], L[3]) if L[0] == "conv" else (L[2], L[1])
             fan_in, n_out = int(np.prod(shape[1:])), shape[0]
-        sd[attr + ".weight"] = (rng.uniform(-1, 1, shape) * np.sqrt(6.0 / fan_in) * fold).astype(np.float32)
+        filter_axis = 1 if L[0] == "deconv" else 0
+        per_filter = fold.reshape([-1 if axis == filter_axis else 1 for axis in range(len(shape))])
+        sd[attr + ".weight"] = (rng.uniform(-1, 1, shape) * np.sqrt(6.0 / fan_in) * per_filter).astype(np.float32)
         sd[attr + ".bias"] = (rng.uniform(-1, 1, n_out) / np.sqrt(fan_in) * fold).astype(np.float32)
     return sd
 
@@ -727,6 +854,8 @@ def build(name):
                     setattr(self, op[1], i8ie.Activation(op[2], op[3] if len(op) > 3 else None))
                 elif op[0] == "matmul":
                     setattr(self, op[1], i8ie.MatMul(transpose_a=op[3], transpose_b=op[4]))
+                elif op[0] == "attention":
+                    setattr(self, op[1], i8ie.Attention(op[2]))
             for attr, L in layers.items():
                 if L[0] == "deconv":
                     setattr(self, attr, i8ie.ConvTranspose2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5], output_padding=L[6]))
@@ -735,6 +864,8 @@ def build(name):
                                                     dilation=conv_dilation(L)))
                 elif L[0] == "ln":
                     setattr(self, attr, i8ie.LayerNorm(L[1]))
+                elif L[0] == "gn":
+                    setattr(self, attr, i8ie.GroupNorm(L[1], L[2]))
                 else:
                     setattr(self, attr, i8ie.Linear(L[1], L[2]))
 
@@ -760,6 +891,8 @@ def build(name):
                     x = getattr(self, op[1])(x, saved[op[2]])
                 elif op[0] == "softmax":
                     x = i8ie.softmax(x)
+                elif op[0] == "attention":
+                    x = getattr(self, op[1])(x, *[saved[t] for t in op[3:]])
                 elif op[0] == "concat":
                     x = getattr(self, op[1])([x] + [saved[t] for t in op[2]])
                 elif op[0] == "act":
@@ -799,7 +932,7 @@ def op_names(name, *kinds):
 
 
 def layer_names(name):
-    """the layers of the `layers` dict (Conv2d / ConvTranspose2d / Linear / LayerNorm)"""
+    """the layers of the `layers` dict (Conv2d / ConvTranspose2d / Linear / LayerNorm / GroupNorm)"""
     return op_names(name, "layer")
 
 
@@ -819,7 +952,12 @@ def activation_names(name):
     return op_names(name, "act")
 
 
+def attention_names(name):
+    """the Attentions: the joins that have score_qparams() too"""
+    return op_names(name, "attention")
+
+
 def join_names(name):
-    """every op that is a module without weights (Add, Mul, Concat, Activation, MatMul): those with output_qparams() beside
-    the layers"""
-    return op_names(name, "add", "mul", "concat", "act", "matmul")
+    """every op that is a module without weights (Add, Mul, Concat, Activation, MatMul, Attention): those with
+    output_qparams() beside the layers"""
+    return op_names(name, "add", "mul", "concat", "act", "matmul", "attention")

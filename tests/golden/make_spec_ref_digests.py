@@ -9,8 +9,9 @@ fire networks), act_ref.forward and fp32_qparams (the MobileNetV2s, act_tiny), m
 mobilenetv3_small_cifar), deconv_ref.forward and fp32_qparams (the U-Nets), upsample_ref.forward (upsample_tiny,
 unet_bilinear_cifar) and dilated_ref.forward (aspp_tiny, deeplabv3_cifar); later, the same way, attention_ref.nonlocal_forward
 and nonlocal_fp32_qparams (the non-local networks) and the ConvNeXt walk of tests/test_gpu_layernorm.py with a float64 stand-in
-written beside it (the ConvNeXts).  Those are gone, so this script now records what
-spec_ref gives.  Run it on a tree whose expected bytes are the ones to keep, never to make a failing replay pass:
+written beside it (the ConvNeXts), and mha_ref.net_forward and the GroupNorm walk of tests/test_gpu_groupnorm.py (mha_tiny,
+groupnorm_tiny; botnet_cifar and groupnorm_resnet_cifar had no walk before spec_ref's, so their entries pin the interpreter
+and prove nothing more).  Those are gone, so this script now records what spec_ref gives.  Run it on a tree whose expected bytes are the ones to keep, never to make a failing replay pass:
 
     python tests/golden/make_spec_ref_digests.py
 """

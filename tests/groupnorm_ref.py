@@ -125,6 +125,15 @@ def group_norm_f32_bound(x, G, gamma, beta, eps):
     return lr.layer_norm_f32_bound(rows_of(x, G), per_element(gamma, G, hw), per_element(beta, G, hw), eps).reshape(x.shape)
 
 
+def tracer(layers, into):
+    """a trace callback for spec_ref.forward: into[attr] = the output bytes of every ("gn", groups, channels) layer"""
+    def trace(op, out, operands):
+        if op[0] == "layer" and layers[op[1]][0] == "gn":
+            into[op[1]] = out[0]
+
+    return trace
+
+
 # ---- ctypes ------------------------------------------------------------------------------------------------------------------
 def bind(lib):
     vp, i = C.c_void_p, C.c_int

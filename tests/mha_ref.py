@@ -68,6 +68,31 @@ def pixels(t, h, w):
     return np.ascontiguousarray(t.transpose(0, 2, 1).reshape(n, c, h, w))
 
 
+# ---- the ("attention", attr, heads[, tag_k, tag_v]) op of a workloads spec --------------------------------------------------
+SCORES = ".scores"   # attr + SCORES: the key of an Attention's score (scale, zero_point) in a table of join parameters
+
+
+def attend_u8(operands, heads, score_qp, s_o, zp_o):
+    """attention_u8 on spec_ref operands, each (bytes [n, c, h, w], scale, zp): one packed tensor, or q, k, v"""
+    t = [tokens(a[0]) for a in operands]
+    q, k, v = operands * 3 if len(operands) == 1 else operands
+    return attention_u8(t[0], *(t[1:] or (None, None)), heads, q[1], q[2], k[1], k[2], v[1], v[2],
+                        np.float32(score_qp[0]), int(score_qp[1]), s_o, zp_o)
+
+
+def tracer(into, join_qparams):
+    """a trace callback for spec_ref.forward: into[attr] = the output bytes of every Attention, and into[attr + ".S"] /
+    into[attr + ".P"] = its scores and probabilities [n, heads, tq, tk], from the operands (where the caller has them) and
+    join_qparams[attr + SCORES]"""
+    def trace(op, out, operands):
+        if op[0] == "attention":
+            into[op[1]] = out[0]
+            if operands is not None:
+                into[op[1] + ".S"], into[op[1] + ".P"] = attend_u8(operands, op[2], join_qparams[op[1] + SCORES], out[1], out[2])[:2]
+
+    return trace
+
+
 # ---- ctypes ----------------------------------------------------------------------------------------------------------
 class AttnMat(C.Structure):
     """i8ie_attn_mat"""
@@ -95,167 +120,3 @@ def bind(lib):
 def mat(ptr, tokens_, channels, s8=False, offset=0):
     """a dense [b, tokens, channels] array at ptr + offset"""
     return AttnMat(ptr + offset, tokens_ * channels, channels, 1 if s8 else 0)
-
-
-# ---- the test network of tests/test_gpu_mha.py and its numpy walk ----------------------------------------------------------
-# 3x32x32 -> conv 3x3 s2, relu, max-pool 2/2 (8x8, t = 64) -> [LayerNorm, packed 1x1 conv 16 -> 48, Attention(2) at d = 8,
-# 1x1 conv] + skip -> relu, conv 3x3 s2 with padding (4x4, t = 16) -> [three 1x1 convs, Attention(2) at d = 16, 1x1 conv] + skip
-# -> relu, global average pool, fc.  Layers in workloads' notation: ("conv", in, out, k, stride, pad), ("ln", c), ("fc", in, out).
-NET_INPUT = (3, 32, 32)
-NET_HEADS = 2
-NET_LAYERS = {
-    "c1": ("conv", 3, 16, 3, 2, 1), "ln1": ("ln", 16), "qkv1": ("conv", 16, 48, 1, 1, 0), "proj1": ("conv", 16, 16, 1, 1, 0),
-    "c2": ("conv", 16, 32, 3, 2, 1), "q2": ("conv", 32, 32, 1, 1, 0), "k2": ("conv", 32, 32, 1, 1, 0), "v2": ("conv", 32, 32, 1, 1, 0),
-    "proj2": ("conv", 32, 32, 1, 1, 0), "fc": ("fc", 32, 10)}
-NET_JOINS = ("attn1", "add1", "attn2", "add2")          # the modules without weights: output_qparams() beside the layers
-NET_ATTENTIONS = ("attn1", "attn2")                     # ... of which these have score_qparams() too
-NET_TRACED = ("pool", "ln1", "qkv1", "attn1", "add1", "c2", "attn2", "add2", "gap")
-WEIGHT_SEED, CALIB_SEED, INPUT_SEED = 42, 99, 5
-INPUT_SCALE, INPUT_ZP = np.float32(0.025), 127
-
-
-def net_state_dict(seed=WEIGHT_SEED):
-    """He-uniform weights and U(-1, 1) / sqrt(fan_in) biases, gamma from U(0.5, 1.5), beta from U(-0.3, 0.3).  The 1 / sqrt(d)
-    of scaled-dot-product attention is folded into the query projections: the first 16 filters of qkv1, and q2."""
-    rng = np.random.default_rng(seed)
-    sd = {}
-    for attr, L in NET_LAYERS.items():
-        if L[0] == "ln":
-            sd[attr + ".weight"] = rng.uniform(0.5, 1.5, L[1]).astype(np.float32)
-            sd[attr + ".bias"] = rng.uniform(-0.3, 0.3, L[1]).astype(np.float32)
-            continue
-        shape = (L[2], L[1], L[3], L[3]) if L[0] == "conv" else (L[2], L[1])
-        fan_in = int(np.prod(shape[1:]))
-        fold = np.ones(shape[0], np.float64)
-        if attr == "qkv1":
-            fold[:16] = 1.0 / np.sqrt(16 // NET_HEADS)
-        elif attr == "q2":
-            fold[:] = 1.0 / np.sqrt(32 // NET_HEADS)
-        w = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / fan_in)
-        sd[attr + ".weight"] = (w * fold.reshape((-1,) + (1,) * (len(shape) - 1))).astype(np.float32)
-        sd[attr + ".bias"] = (rng.uniform(-1, 1, shape[0]) / np.sqrt(fan_in) * fold).astype(np.float32)
-    return sd
-
-
-def net_input(batch, seed=INPUT_SEED):
-    """normalised-image-like input, inside quantize()'s no-wrap window for INPUT_SCALE / INPUT_ZP"""
-    rng = np.random.default_rng(seed)
-    u = rng.uniform(0, 1, (batch,) + NET_INPUT).astype(np.float32)
-    a = rng.uniform(0.2, 1.0, (batch, NET_INPUT[0], 1, 1)).astype(np.float32)
-    return ((u * a - np.float32(0.45)) / np.float32(0.226)).astype(np.float32)
-
-
-def net_quantize_layers(state_dict, per_channel=False):
-    """convert()'s weight rules; a LayerNorm keeps its float32 (gamma, beta)"""
-    import pc_pipeline as pcp
-
-    rule = pcp.quantize_weight_pc if per_channel else orc.quantize_weight
-    out = {}
-    for attr, L in NET_LAYERS.items():
-        w, b = state_dict[attr + ".weight"], state_dict[attr + ".bias"]
-        out[attr] = (w, b) if L[0] == "ln" else tuple(rule(w, b))
-    return out
-
-
-def net_forward(x, qlayers, qp, score_qp, per_channel=False, trace=None):
-    """float32 logits of the test network.  qlayers: net_quantize_layers(); qp: {attr: (scale, zp)} of NET_LAYERS and NET_JOINS;
-    score_qp: the same of the scores of NET_ATTENTIONS.  trace: a dict that receives the bytes of NET_TRACED, and of each
-    attention its scores and probabilities as attr + ".S" and attr + ".P"."""
-    import add_ref
-    import avgpool_ref as apr
-    import grouped_ref as gr
-    import layernorm_ref as lnr
-    import pc_pipeline as pcp
-
-    def out_of(table, attr):
-        s, zp = table[attr]
-        return np.float32(s), int(zp)
-
-    def layer(attr, cur):
-        (q, s, zp), L, (s_o, zp_o) = cur, NET_LAYERS[attr], out_of(qp, attr)
-        if L[0] == "ln":
-            return (lnr.layer_norm_any(q, s, np.float32(1e-5), qlayers[attr][0], qlayers[attr][1], s_o, zp_o), s_o, zp_o)
-        qw, qb, s_w = qlayers[attr]
-        if L[0] == "conv":
-            f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
-            return (f(q, qw, qb, 1, L[4], L[5], s, zp, s_w, s_o, zp_o)[0], s_o, zp_o)
-        f = pcp.linear_pc if per_channel else orc.linear
-        return (f(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_o, zp_o)[0], s_o, zp_o)
-
-    def attend(attr, q, k, v):
-        """q, k, v: (bytes [n, c, h, w], scale, zp), or k = v = None for the packed form"""
-        (s_s, zp_s), (s_o, zp_o) = out_of(score_qp, attr), out_of(qp, attr)
-        k, v = (q, q) if k is None else (k, v)
-        packed = k is q
-        S, P, _, O = attention_u8(tokens(q[0]), None if packed else tokens(k[0]), None if packed else tokens(v[0]), NET_HEADS,
-                                  q[1], q[2], k[1], k[2], v[1], v[2], s_s, zp_s, s_o, zp_o)
-        keep(attr + ".S", S)
-        keep(attr + ".P", P)
-        return (pixels(O, q[0].shape[2], q[0].shape[3]), s_o, zp_o)
-
-    def add(attr, a, b):
-        s_o, zp_o = out_of(qp, attr)
-        return (add_ref.add_u8(a[0], a[2], a[1], b[0], b[2], b[1], s_o, zp_o, relu=False), s_o, zp_o)
-
-    def relu(cur):
-        return (orc.relu(cur[0], cur[2]), cur[1], cur[2])
-
-    def keep(name, q):
-        if trace is not None:
-            trace[name] = q
-
-    def kept(name, cur):
-        keep(name, cur[0])
-        return cur
-
-    cur = (orc.quantize(x, INPUT_SCALE, INPUT_ZP), INPUT_SCALE, INPUT_ZP)
-    cur = relu(layer("c1", cur))
-    cur = kept("pool", (orc.max_pool2d(cur[0], 2, 2), cur[1], cur[2]))
-    y = kept("qkv1", layer("qkv1", kept("ln1", layer("ln1", cur))))
-    y = kept("attn1", attend("attn1", y, None, None))
-    cur = kept("add1", add("add1", layer("proj1", y), cur))
-    cur = kept("c2", layer("c2", relu(cur)))
-    y = kept("attn2", attend("attn2", layer("q2", cur), layer("k2", cur), layer("v2", cur)))
-    cur = kept("add2", add("add2", layer("proj2", y), cur))
-    cur = relu(cur)
-    cur = kept("gap", (apr.global_avg_pool2d_u8(cur[0]), cur[1], cur[2]))
-    return orc.dequantize(*layer("fc", cur))
-
-
-def net_fp32_qparams(state_dict, x):
-    """Stand-in for calibration without a GPU (spec_ref.fp32_qparams' method): a float64 forward over the FP32 weights; the
-    range of every layer, join and score tensor gives its (scale, zero_point).  Returns (qp, score_qp)."""
-    import f64_ref
-    import grouped_ref as gr
-    import layernorm_ref as lnr
-    import spec_ref as sr
-
-    qp, sq = {}, {}
-
-    def note(table, attr, v):
-        table[attr] = sr.range_qparams(v.min(), v.max())
-        return v
-
-    def layer(attr, v):
-        L = NET_LAYERS[attr]
-        w, b = state_dict[attr + ".weight"].astype(np.float64), state_dict[attr + ".bias"].astype(np.float64)
-        if L[0] == "ln":
-            return note(qp, attr, np.ascontiguousarray(np.moveaxis(lnr.layer_norm_f64(np.moveaxis(v, 1, -1), w, b, 1e-5), -1, 1)))
-        if L[0] == "conv":
-            return note(qp, attr, gr.conv2d_f64(v, w, b, 1, L[4], L[5]))
-        return note(qp, attr, f64_ref.linear(v.reshape(v.shape[0], -1), w, b))
-
-    def attend(attr, q, k, v):
-        s, o = attention(tokens(q), None if k is None else tokens(k), None if v is None else tokens(v), NET_HEADS)
-        note(sq, attr, s)
-        return note(qp, attr, pixels(o, q.shape[2], q.shape[3]))
-
-    v = np.maximum(layer("c1", np.asarray(x, np.float64)), 0.0)
-    v = f64_ref.max_pool2d(v, 2, 2)
-    y = attend("attn1", layer("qkv1", layer("ln1", v)), None, None)
-    v = note(qp, "add1", layer("proj1", y) + v)
-    v = layer("c2", np.maximum(v, 0.0))
-    y = attend("attn2", layer("q2", v), layer("k2", v), layer("v2", v))
-    v = note(qp, "add2", layer("proj2", y) + v)
-    layer("fc", np.maximum(v, 0.0).mean(axis=(2, 3)))
-    return qp, sq

@@ -6,5 +6,6 @@ MACS = {
     "squeezenet_cifar": 5224448, "mobilenetv2_tiny": 4375168, "act_tiny": 2092192, "mobilenetv2_cifar": 87976448,
     "se_tiny": 2093608, "mobilenetv3_small_cifar": 17507328, "unet_tiny": 6913024, "unet_cifar": 574947328,
     "nonlocal_tiny": 237768, "nonlocal_resnet_cifar": 563811328, "convnext_tiny": 358920, "convnext_cifar": 76612608,
+    "mha_tiny": 315712, "botnet_cifar": 58558976, "groupnorm_tiny": 650184, "groupnorm_resnet_cifar": 609948672,
 }
 NAMES = list(MACS)[:17] + ["upsample_tiny", "unet_bilinear_cifar", "aspp_tiny", "deeplabv3_cifar"] + list(MACS)[17:]

@@ -3,15 +3,16 @@
 
 Nothing is defined arithmetically here.  Every op is the function of its own module -- the reference's ops in oracle/orc.py,
 per-channel requantisation in pc_pipeline, and grouped_ref, add_ref, avgpool_ref, concat_ref, act_ref, mul_ref, deconv_ref,
-upsample_ref, dilated_ref, attention_ref, layernorm_ref for what the reference does not have -- and this module only walks
-the spec with (bytes, scale, zero_point) in hand.  A new op adds one branch to forward(), one to fp32_qparams() if it is calibrated, its name to OPS, and
-its arithmetic in a module of its own.
+upsample_ref, dilated_ref, attention_ref, layernorm_ref, mha_ref, groupnorm_ref for what the reference does not have -- and
+this module only walks the spec with (bytes, scale, zero_point) in hand.  A new op adds one branch to forward(), one to
+fp32_qparams() if it is calibrated, its name to OPS, and its arithmetic in a module of its own.
 
   OPS                                the op names a spec may hold; anything else raises ValueError
   forward(...)                       float32 logits of a network
   fp32_qparams(...)                  stand-in for calibration without a GPU: a float64 forward over the FP32 weights
   quantize_layers(...)               convert()'s weight rules
   outputs_of(name, into)             a trace callback that keeps the output bytes of the ops called `name`
+  keeps(keys, into)                  a trace callback that keeps the output bytes of the ops with the given attributes / names
   traces(*callbacks)                 several trace callbacks as one"""
 import numpy as np
 
@@ -24,7 +25,9 @@ import deconv_ref as dr
 import dilated_ref as dl
 import f64_ref
 import grouped_ref as gr
+import groupnorm_ref as gnr
 import layernorm_ref as lnr
+import mha_ref as mhr
 import mul_ref as mr
 import orc
 import pc_pipeline as pcp
@@ -34,7 +37,7 @@ from layer_cases import range_qparams  # (the calibrator's rule on a real-valued
 
 f32 = np.float32
 OPS = frozenset(["layer", "relu", "pool", "avgpool", "gap", "save", "branch", "add", "mul", "concat", "act", "upsample", "flatten",
-                 "matmul", "softmax", "load"])
+                 "matmul", "softmax", "load", "attention"])
 
 # synthetic weights, calibration batch and input of the network tests, GPU and host: with them the traced tensors keep the
 # limits of act_ref.nontrivial and mul_ref.nontrivial.  (CALIB_IMAGES is the batch of fp32_qparams in the host tests; the GPU
@@ -45,10 +48,12 @@ WEIGHT_SEED, CALIB_SEED, CALIB_IMAGES, INPUT_SEED = 42, 99, 4, 5
 def _layer(L, cur, qlayer, s_out, zp_out, per_channel):
     """the output bytes of a weighted layer.  Conv: the reference convolution per group, a dilated kernel inflated by zeros
     (the kernel extent is the weight's); deconv: the reference convolution of the equivalent problem; fc: the reference linear;
-    ln: layernorm_ref's LayerNorm at eps 1e-5, qlayer its float32 (gamma, beta)"""
+    ln, gn: layernorm_ref's LayerNorm and groupnorm_ref's GroupNorm at eps 1e-5, qlayer their float32 (gamma, beta)"""
     q, s, zp = cur
     if L[0] == "ln":
         return lnr.layer_norm_any(q, s, f32(1e-5), qlayer[0], qlayer[1], s_out, zp_out)
+    if L[0] == "gn":
+        return gnr.group_norm_u8(q, L[1], s, f32(1e-5), qlayer[0], qlayer[1], s_out, zp_out)
     qw, qb, s_w = qlayer
     if L[0] == "conv":
         d = dl.layer_dilation(L)
@@ -65,8 +70,8 @@ def _layer(L, cur, qlayer, s_out, zp_out, per_channel):
 
 def forward(networks_entry, x, qlayers, out_qparams, join_qparams=None, per_channel=False, trace=None):
     """x: float32 NCHW.  qlayers: {attr: (qw, qb, s_w)} as quantize_layers gives them (s_w a scalar or, per_channel, float32
-    [out]).  out_qparams: {attr: (scale, zp)} of the layers, join_qparams: the same of the Adds, Muls, Concats, Activations
-    and MatMuls.
+    [out]).  out_qparams: {attr: (scale, zp)} of the layers, join_qparams: the same of the Adds, Muls, Concats, Activations,
+    MatMuls and Attentions, and under attr + mha_ref.SCORES the score parameters of each Attention.
     trace: called as trace(op, (bytes, scale, zp), operands) behind every op that produces bytes, operands the list of
     (bytes, scale, zp) it read, the current tensor first.  Returns float32 logits."""
     layers, spec, _ = networks_entry
@@ -84,7 +89,7 @@ def forward(networks_entry, x, qlayers, out_qparams, join_qparams=None, per_chan
                 cur = saved[op[1]]
                 continue
             operands = [cur]
-            if name in ("layer", "add", "mul", "concat", "act", "matmul"):  # the ops with output parameters of their own
+            if name in ("layer", "add", "mul", "concat", "act", "matmul", "attention"):  # the ops with output parameters of their own
                 s_out, zp_out = (out_qparams if name == "layer" else join_qparams or {})[op[1]]
                 s_out, zp_out = f32(s_out), int(zp_out)
             if name == "layer":
@@ -110,6 +115,10 @@ def forward(networks_entry, x, qlayers, out_qparams, join_qparams=None, per_chan
                 cur = (out.reshape(atr.result_shape(q.shape, q2.shape, op[3], op[4])), s_out, zp_out)
             elif name == "softmax":
                 cur = (atr.softmax_u8(q, s), f32(1.0 / 256), 0)
+            elif name == "attention":  # [cur], packed, or [q, k, v]
+                operands += [saved[t] for t in op[3:]]
+                out = mhr.attend_u8(operands, op[2], join_qparams[op[1] + mhr.SCORES], s_out, zp_out)[3]
+                cur = (mhr.pixels(out, q.shape[2], q.shape[3]), s_out, zp_out)
             elif name == "concat":
                 operands += [saved[t] for t in op[2]]
                 cur = (cr.cat_u8(operands, s_out, zp_out), s_out, zp_out)
@@ -138,6 +147,17 @@ def outputs_of(name, into):
     return trace
 
 
+def keeps(keys, into):
+    """a trace callback for forward(): into[key] = the output bytes of every op whose key is in `keys`, the key of an op being
+    its attribute name where it has one (layer, add, mul, concat, act, matmul, attention) and its own name otherwise (pool, gap)"""
+    def trace(op, out, operands):
+        key = op[1] if len(op) > 1 and isinstance(op[1], str) else op[0]
+        if key in keys:
+            into[key] = out[0]
+
+    return trace
+
+
 def traces(*callbacks):
     """one trace callback that calls every one of `callbacks`"""
     def trace(op, out, operands):
@@ -149,8 +169,9 @@ def traces(*callbacks):
 
 def fp32_qparams(networks_entry, state_dict, x):
     """Stand-in for calibration without a GPU: a numpy forward in float64 over the FP32 weights; the output range of every
-    layer, Add, Mul, Concat, Activation and MatMul gives its (scale, zero_point) by the calibrator's rule.  No registry network needs
-    avgpool or upsample here; they raise like any other op.  Returns (layer qparams, join qparams)."""
+    layer, Add, Mul, Concat, Activation, MatMul and Attention gives its (scale, zero_point) by the calibrator's rule, and so does
+    the score range of an Attention, kept beside the joins under attr + mha_ref.SCORES.  No registry network needs avgpool or
+    upsample here; they raise like any other op.  Returns (layer qparams, join qparams)."""
     layers, spec, _ = networks_entry
     qp, jqp = {}, {}
 
@@ -163,6 +184,8 @@ def fp32_qparams(networks_entry, state_dict, x):
                 if L[0] == "ln":  # over the channel axis: axis 1 of [n, c, h, w], the last of [n, f]
                     rows = np.ascontiguousarray(np.moveaxis(v, 1, -1))
                     v = np.ascontiguousarray(np.moveaxis(lnr.layer_norm_f64(rows, w, b, 1e-5), -1, 1))
+                elif L[0] == "gn":
+                    v = gnr.group_norm_f64(v, L[1], w, b, 1e-5)
                 elif L[0] == "conv":
                     v = gr.conv2d_f64(v, dl.inflate(w, dl.layer_dilation(L)), b, gr.layer_groups(L), L[4], L[5])
                 elif L[0] == "deconv":
@@ -191,6 +214,11 @@ def fp32_qparams(networks_entry, state_dict, x):
                 v = atr.matmul(v, v2, op[3], op[4])[0].reshape(atr.result_shape(v.shape, v2.shape, op[3], op[4]))
             elif name == "softmax":
                 v = atr.softmax(v)
+            elif name == "attention":
+                toks = [mhr.tokens(a) for a in [v] + [saved[tag] for tag in op[3:]]]
+                scores, out = mhr.attention(toks[0], *(toks[1:] or (None, None)), op[2])
+                jqp[op[1] + mhr.SCORES] = range_qparams(scores.min(), scores.max())
+                v = mhr.pixels(out, v.shape[2], v.shape[3])
             elif name == "concat":
                 v = np.concatenate([v] + [saved[t] for t in op[2]], axis=1)
             elif name == "gap":
@@ -199,7 +227,7 @@ def fp32_qparams(networks_entry, state_dict, x):
                 v = v.reshape(-1, op[1])
             else:
                 raise ValueError("spec_ref.fp32_qparams: op %r" % (op,))
-            if name in ("layer", "act", "add", "mul", "concat", "matmul"):
+            if name in ("layer", "act", "add", "mul", "concat", "matmul", "attention"):
                 (qp if name == "layer" else jqp)[op[1]] = range_qparams(v.min(), v.max())
         return v
 
@@ -211,10 +239,10 @@ def quantize_layers(networks_entry, state_dict, per_channel=False):
     """{attr: (qw, qb, s_w)} by convert()'s rules on the weight tensors as they stand ([kc, c / groups, kh, kw] of a grouped
     conv, the compact kernel of a dilated one), a "deconv" layer as its equivalent kernel W~ [out, in, k, k]: per tensor the
     oracle's joint min / max over the whole weight and the bias, per channel the same per row of the [kc, K] matrix.  An "ln"
-    layer has no INT8 weights: its float32 (weight, bias) as they stand."""
+    or "gn" layer has no INT8 weights: its float32 (weight, bias) as they stand."""
     rule = pcp.quantize_weight_pc if per_channel else orc.quantize_weight
     out = {}
     for attr, L in networks_entry[0].items():
         w, b = state_dict[attr + ".weight"], state_dict[attr + ".bias"]
-        out[attr] = (w, b) if L[0] == "ln" else tuple(rule(dr.equivalent_weight(w) if L[0] == "deconv" else w, b))
+        out[attr] = (w, b) if L[0] in ("ln", "gn") else tuple(rule(dr.equivalent_weight(w) if L[0] == "deconv" else w, b))
     return out

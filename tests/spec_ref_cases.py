@@ -11,7 +11,9 @@ import numpy as np
 
 import attention_ref as atr
 import deconv_ref as dr
+import groupnorm_ref as gnr
 import layernorm_ref as lnr
+import mha_ref as mhr
 import mul_ref as mr
 import spec_ref as sr
 import upsample_ref as ur
@@ -28,9 +30,10 @@ FAMILY = {
     "upsample_tiny": "upsample", "unet_bilinear_cifar": "upsample", "aspp_tiny": "upsample", "deeplabv3_cifar": "upsample",
     "nonlocal_tiny": "attention", "nonlocal_resnet_cifar": "attention",
     "convnext_tiny": "layernorm", "convnext_cifar": "layernorm",
+    "mha_tiny": "mha", "botnet_cifar": "mha", "groupnorm_tiny": "groupnorm", "groupnorm_resnet_cifar": "groupnorm",
 }
 # the families whose host tests take their parameters from fp32_qparams
-CALIBRATED = ("act", "mul", "deconv", "attention", "layernorm")
+CALIBRATED = ("act", "mul", "deconv", "attention", "layernorm", "mha", "groupnorm")
 
 
 def synthetic_qparams(attrs):
@@ -55,7 +58,8 @@ def run(family, entry, x, qlayers, qp, jqp, per_channel):
     trace = [] if family == "upsample" else {}
     tracer = {"plain": None, "concat": sr.outputs_of("concat", trace), "act": sr.outputs_of("act", trace),
               "mul": mr.tracer(spec, trace), "deconv": dr.tracer(layers, trace), "upsample": ur.tracer(trace),
-              "attention": atr.tracer(trace), "layernorm": sr.traces(lnr.tracer(layers, trace), atr.tracer(trace))}[family]
+              "attention": atr.tracer(trace), "layernorm": sr.traces(lnr.tracer(layers, trace), atr.tracer(trace)),
+              "mha": mhr.tracer(trace, jqp), "groupnorm": gnr.tracer(layers, trace)}[family]
     return sr.forward(entry, x, qlayers, qp, jqp, per_channel, tracer), trace
 
 

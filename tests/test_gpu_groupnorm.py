@@ -10,7 +10,6 @@ import numpy as np
 import pytest
 
 import abi
-import grouped_ref as gr
 import groupnorm_ref as gn
 import int8inferenceengine_amd  # noqa: F401  (puts the i8ie package on the path)
 import orc
@@ -353,225 +352,42 @@ def test_calibration_on_the_device(i8ie):
     assert sh != 1.0 and sd != 1.0 and 0.5 < sd / sh < 2.0 and abs(int(zd) - int(zh)) <= 64, got
 
 
-# ---- the test network ----------------------------------------------------------------------------------------------------
-# 3x32x32 -> conv 3x3 s2, relu, max-pool 2/2 (16 channels, 8x8) -> GN residual block at 16 channels [conv, GN(4), relu, conv (a
-# bordered consumer of the GN), GN(16) = InstanceNorm] + skip, relu -> conv 3x3 s2 to 20 channels (4x4), GN(5), relu -> GN
-# residual block at 20 channels [conv, GN(1), relu, conv, GN(10)] + skip -> the SiLU block [GN(4), x * sigmoid(x) (two consumers
-# of one pending GN), conv 3x3 with padding, packed 1x1 conv 20 -> 60, Attention(2) at d = 10, 1x1 conv] + skip -> relu, global
-# average pool, fc.  20 channels are no multiple of 16, so those GroupNorms take the direct form; the 16-channel ones the image form.
-NET_INPUT = (3, 32, 32)
-NET_HEADS = 2
-NET_LAYERS = {
-    "c1": ("conv", 3, 16, 3, 2, 1),
-    "a_c1": ("conv", 16, 16, 3, 1, 1), "a_gn1": ("gn", 4, 16), "a_c2": ("conv", 16, 16, 3, 1, 1), "a_gn2": ("gn", 16, 16),
-    "down": ("conv", 16, 20, 3, 2, 1), "d_gn": ("gn", 5, 20),
-    "b_c1": ("conv", 20, 20, 3, 1, 1), "b_gn1": ("gn", 1, 20), "b_c2": ("conv", 20, 20, 3, 1, 1), "b_gn2": ("gn", 10, 20),
-    "s_gn": ("gn", 4, 20), "s_c": ("conv", 20, 20, 3, 1, 1), "s_qkv": ("conv", 20, 60, 1, 1, 0), "s_proj": ("conv", 20, 20, 1, 1, 0),
-    "fc": ("fc", 20, 10)}
-NET_JOINS = ("a_add", "b_add", "s_sig", "s_mul", "s_attn", "s_add")
-NET_TRACED = ("pool", "a_gn1", "a_gn2", "a_add", "d_gn", "b_gn1", "b_gn2", "b_add", "s_gn", "s_sig", "s_mul", "s_c", "s_attn", "s_add", "gap")
-WEIGHT_SEED, CALIB_SEED, INPUT_SEED = 42, 99, 5
-_NET = {}
+# ---- groupnorm_tiny (workloads.py), its expected bytes from tests/spec_ref.py ---------------------------------------------
+NAME = "groupnorm_tiny"
+GROUPNORMS = ("a_gn1", "a_gn2", "d_gn", "b_gn1", "b_gn2", "s_gn")
+TRACED = ("pool",) + GROUPNORMS + ("a_add", "b_add", "s_sig", "s_mul", "s_c", "s_attn", "s_add", "gap", "fc")
 
 
-def _net_state_dict():
-    """He-uniform weights and U(-1, 1) / sqrt(fan_in) biases, gamma from U(0.5, 1.5), beta from U(-0.3, 0.3); the 1 / sqrt(d) of
-    the attention is folded into the query third of s_qkv"""
-    rng = np.random.default_rng(WEIGHT_SEED)
-    sd = {}
-    for attr, L in NET_LAYERS.items():
-        if L[0] == "gn":
-            sd[attr + ".weight"] = rng.uniform(0.5, 1.5, L[2]).astype(f32)
-            sd[attr + ".bias"] = rng.uniform(-0.3, 0.3, L[2]).astype(f32)
-            continue
-        shape = (L[2], L[1], L[3], L[3]) if L[0] == "conv" else (L[2], L[1])
-        fan_in = int(np.prod(shape[1:]))
-        fold = np.ones(shape[0], np.float64)
-        if attr == "s_qkv":
-            fold[:20] = 1.0 / np.sqrt(20 // NET_HEADS)
-        w = rng.uniform(-1, 1, shape) * np.sqrt(6.0 / fan_in)
-        sd[attr + ".weight"] = (w * fold.reshape((-1,) + (1,) * (len(shape) - 1))).astype(f32)
-        sd[attr + ".bias"] = (rng.uniform(-1, 1, shape[0]) / np.sqrt(fan_in) * fold).astype(f32)
-    return sd
+def _net(per_channel):
+    """nc.calibrated on the device sampler, as tests/test_gpu_mha.py's network"""
+    import net_cases as nc
 
-
-def _net_input(batch, seed=INPUT_SEED):
-    import mha_ref as mr
-
-    return mr.net_input(batch, seed)   # (the same 3x32x32 normalised-image-like input)
-
-
-def _net_quantize_layers(sd, per_channel):
-    import pc_pipeline as pcp
-
-    rule = pcp.quantize_weight_pc if per_channel else orc.quantize_weight
-    return {a: (sd[a + ".weight"], sd[a + ".bias"]) if L[0] == "gn" else tuple(rule(sd[a + ".weight"], sd[a + ".bias"]))
-            for a, L in NET_LAYERS.items()}
-
-
-def _net_forward(x, qlayers, qp, score_qp, per_channel, trace):
-    """the numpy walk: float32 logits; trace receives the bytes of NET_TRACED"""
-    import act_ref
-    import add_ref
-    import avgpool_ref as apr
-    import mha_ref as mr
-    import mul_ref
-    import pc_pipeline as pcp
-
-    def out_of(attr):
-        return f32(qp[attr][0]), int(qp[attr][1])
-
-    def layer(attr, cur):
-        (q, s, zp), L, (s_o, zp_o) = cur, NET_LAYERS[attr], out_of(attr)
-        if L[0] == "gn":
-            return (gn.group_norm_u8(q, L[1], s, f32(1e-5), qlayers[attr][0], qlayers[attr][1], s_o, zp_o), s_o, zp_o)
-        qw, qb, s_w = qlayers[attr]
-        if L[0] == "conv":
-            f = gr.conv2d_grouped_pc if per_channel else gr.conv2d_grouped
-            return (f(q, qw, qb, 1, L[4], L[5], s, zp, s_w, s_o, zp_o)[0], s_o, zp_o)
-        f = pcp.linear_pc if per_channel else orc.linear
-        return (f(q.reshape(q.shape[0], -1), qw, qb, s, zp, s_w, s_o, zp_o)[0], s_o, zp_o)
-
-    def add(attr, a, b):
-        s_o, zp_o = out_of(attr)
-        return (add_ref.add_u8(a[0], a[2], a[1], b[0], b[2], b[1], s_o, zp_o, relu=False), s_o, zp_o)
-
-    def relu(cur):
-        return (orc.relu(cur[0], cur[2]), cur[1], cur[2])
-
-    def kept(name, cur):
-        trace[name] = cur[0]
-        return cur
-
-    cur = (orc.quantize(x, sr.pipeline.INPUT_SCALE, sr.pipeline.INPUT_ZP), f32(sr.pipeline.INPUT_SCALE), sr.pipeline.INPUT_ZP)
-    cur = relu(layer("c1", cur))
-    cur = kept("pool", (orc.max_pool2d(cur[0], 2, 2), cur[1], cur[2]))
-    y = relu(kept("a_gn1", layer("a_gn1", layer("a_c1", cur))))
-    y = kept("a_gn2", layer("a_gn2", layer("a_c2", y)))
-    cur = relu(kept("a_add", add("a_add", y, cur)))
-    cur = relu(kept("d_gn", layer("d_gn", layer("down", cur))))
-    y = relu(kept("b_gn1", layer("b_gn1", layer("b_c1", cur))))
-    y = kept("b_gn2", layer("b_gn2", layer("b_c2", y)))
-    cur = kept("b_add", add("b_add", y, cur))
-    g = kept("s_gn", layer("s_gn", cur))
-    s_o, zp_o = out_of("s_sig")
-    sig = kept("s_sig", (act_ref.act_u8(g[0], "sigmoid", f32(0.0), g[1], g[2], s_o, zp_o), s_o, zp_o))
-    s_o, zp_o = out_of("s_mul")
-    y = kept("s_mul", (mul_ref.mul_u8(g[0], g[2], g[1], sig[0], sig[2], sig[1], s_o, zp_o), s_o, zp_o))
-    y = kept("s_c", layer("s_c", y))
-    qkv = layer("s_qkv", y)
-    (s_s, zp_s), (s_o, zp_o) = (f32(score_qp[0]), int(score_qp[1])), out_of("s_attn")
-    O = mr.attention_u8(mr.tokens(qkv[0]), None, None, NET_HEADS, qkv[1], qkv[2], qkv[1], qkv[2], qkv[1], qkv[2], s_s, zp_s, s_o, zp_o)[3]
-    y = kept("s_attn", (mr.pixels(O, 4, 4), s_o, zp_o))
-    cur = relu(kept("s_add", add("s_add", layer("s_proj", y), cur)))
-    cur = kept("gap", (apr.global_avg_pool2d_u8(cur[0]), cur[1], cur[2]))
-    return orc.dequantize(*layer("fc", cur))
-
-
-def _make_net(i8ie):
-    class GnNet(i8ie.Module):
-        def __init__(self):
-            super().__init__()
-            for attr, L in NET_LAYERS.items():
-                if L[0] == "conv":
-                    setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5]))
-                elif L[0] == "gn":
-                    setattr(self, attr, i8ie.GroupNorm(L[1], L[2]))
-                else:
-                    setattr(self, attr, i8ie.Linear(L[1], L[2]))
-            self.a_add, self.b_add, self.s_add = i8ie.Add(), i8ie.Add(), i8ie.Add()
-            self.s_sig, self.s_mul, self.s_attn = i8ie.Activation("sigmoid"), i8ie.Mul(), i8ie.Attention(NET_HEADS)
-            self.trace = None
-
-        def keep(self, name, t):
-            if self.trace is not None:
-                self.trace[name] = t.numpy()
-            return t
-
-        def forward(self, x):
-            x = self.keep("pool", i8ie.max_pool2d(i8ie.relu(self.c1(x)), 2, 2))
-            y = i8ie.relu(self.keep("a_gn1", self.a_gn1(self.a_c1(x))))
-            y = self.keep("a_gn2", self.a_gn2(self.a_c2(y)))
-            x = i8ie.relu(self.keep("a_add", self.a_add(y, x)))
-            x = i8ie.relu(self.keep("d_gn", self.d_gn(self.down(x))))
-            y = i8ie.relu(self.keep("b_gn1", self.b_gn1(self.b_c1(x))))
-            y = self.keep("b_gn2", self.b_gn2(self.b_c2(y)))
-            x = self.keep("b_add", self.b_add(y, x))
-            g = self.keep("s_gn", self.s_gn(x))
-            y = self.keep("s_mul", self.s_mul(g, self.keep("s_sig", self.s_sig(g))))   # SiLU: x * sigmoid(x)
-            y = self.keep("s_c", self.s_c(y))
-            y = self.keep("s_attn", self.s_attn(self.s_qkv(y)))
-            x = i8ie.relu(self.keep("s_add", self.s_add(self.s_proj(y), x)))
-            x = self.keep("gap", i8ie.global_avg_pool2d(x))
-            return self.fc(x.reshape(-1, 20))
-
-    return GnNet()
-
-
-def _net(i8ie, per_channel):
-    """(net, qlayers, qp, score_qp): calibrated on the device once per weight mode; every quantisation parameter is read from
-    the product"""
-    import _CXX_i8ie as cx
-
-    if per_channel not in _NET:
-        sd = _net_state_dict()
-        net = _make_net(i8ie)
-        net.load(sd)
-        cx.set_calibration_mode("device")
-        cx.set_calibration_seed(7)
-        try:
-            net.prepare()
-            net(i8ie.tensor(_net_input(8, CALIB_SEED)))
-            net.convert(per_channel)
-        finally:
-            cx.set_calibration_mode("auto")
-            cx.set_calibration_seed(-1)
-        qp = {a: getattr(net, a).output_qparams() for a in list(NET_LAYERS) + list(NET_JOINS)}
-        _NET[per_channel] = (net, _net_quantize_layers(sd, per_channel), qp, net.s_attn.score_qparams())
-    return _NET[per_channel]
+    return nc.calibrated(NAME, per_channel, calib_images=8, mode="device")
 
 
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [1, 5])
 def test_gn_net_bit_exact(i8ie, batch, per_channel, tmp_path):
-    """logits and every traced tensor against the numpy walk: eager, under force-fallback, replayed as one HIP graph, and from a
-    fresh net that loaded what save_quantized() wrote"""
-    import _CXX_i8ie as cx
-    from int8inferenceengine_amd.graph import GraphedForward
+    """logits and every traced tensor against spec_ref.forward: eager, tensor by tensor, under force-fallback, replayed as one
+    HIP graph, and from a fresh net that loaded what save_quantized() wrote"""
+    import net_cases as nc
+    from int8inferenceengine_amd import workloads as wl
 
-    net, qlayers, qp, sq = _net(i8ie, per_channel)
-    assert all(s > 0 and s != 1.0 for s, _ in list(qp.values()) + [sq]), (qp, sq)   # everything was calibrated
-    x = _net_input(batch)
+    net, qlayers, qp, jqp = _net(per_channel)
+    both = dict(qp, **jqp)
+    assert "s_attn" + sr.mhr.SCORES in jqp and all(s > 0 and s != 1.0 for s, _ in both.values()), both   # everything was calibrated
+    x = wl.synthetic_input(NAME, batch, seed=sr.INPUT_SEED)
     trace = {}
-    want = _net_forward(x, qlayers, qp, sq, per_channel, trace)
+    want = sr.forward(wl.network(NAME), x, qlayers, qp, jqp, per_channel, sr.keeps(TRACED, trace))
     assert want.shape == (batch, 10) and len(np.unique(want)) > 1
-    for k in ("a_gn1", "a_gn2", "d_gn", "b_gn1", "b_gn2", "s_gn"):   # the expected bytes discriminate
+    for k in GROUPNORMS:   # the expected bytes discriminate
         assert len(np.unique(trace[k])) >= 32 and ((trace[k] == 0) | (trace[k] == 255)).mean() < 0.05, k
-    assert support.same_bits(net(i8ie.tensor(x)).numpy(), want), "eager"
-    net.trace = {}
-    try:
-        assert support.same_bits(net(i8ie.tensor(x)).numpy(), want), "traced"
-        mine = net.trace
-    finally:
-        net.trace = None
-    assert sorted(mine) == sorted(NET_TRACED) == sorted(trace)
-    for k in NET_TRACED:
+    nc.check_bit_exact(i8ie, net, NAME, x, want, fallback=True, graph=True, reload_dir=tmp_path, expect_jqp=both)
+    mine = {}
+    nc.traced(i8ie, net, NAME, x, sr.keeps(TRACED, mine))
+    assert sorted(mine) == sorted(TRACED) == sorted(trace)
+    for k in TRACED:   # ("fc": the logits of the walk tensor by tensor)
         assert mine[k].shape == trace[k].shape and np.array_equal(mine[k], trace[k]), k
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert support.same_bits(fb, want), "force_fallback"
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert support.same_bits(g().numpy(), want), "graph replay"
-    path = str(tmp_path / "gn_net.npz")
-    net.save_quantized(path)
-    fresh = _make_net(i8ie)
-    fresh.load_quantized_file(path)
-    assert {a: getattr(fresh, a).output_qparams() for a in qp} == qp and fresh.s_attn.score_qparams() == sq
-    assert support.same_bits(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
 
 
 def test_gn_net_kernels_and_launches(i8ie):
@@ -579,9 +395,10 @@ def test_gn_net_kernels_and_launches(i8ie):
     each, with the relus behind them folded in (the one relu launch left is c1's NCHW route).  The launches between the
     20-channel layers belong to the existing operand machinery, which tests/test_gpu_operand_rules.py pins."""
     import _CXX_i8ie as cx
+    from int8inferenceengine_amd import workloads as wl
 
-    net = _net(i8ie, False)[0]
-    x = _net_input(5)
+    net = _net(False)[0]
+    x = wl.synthetic_input(NAME, 5, seed=sr.INPUT_SEED)
     net(i8ie.tensor(x)).numpy()
     cx.synchronize()
     cx.profile_start()
@@ -589,9 +406,7 @@ def test_gn_net_kernels_and_launches(i8ie):
         net(i8ie.tensor(x)).numpy()
     finally:
         prof = cx.profile_stop()
-    launches = {}
-    for k, v in prof.items():
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
+    launches = support.launch_counts(prof)
     print(launches)
     assert launches.get("groupnorm_u8_image") == 2 and launches.get("groupnorm_u8_direct") == 4, launches
     assert launches.get("relu_u8", 0) <= 1, launches

@@ -424,119 +424,55 @@ def test_operand_that_a_bordered_conv_consumed_first(i8ie):
     assert np.array_equal(p.numpy(), plain)
 
 
-# ---- 8: the test network (its layer table and numpy walk: tests/mha_ref.py) ------------------------------------------------
-_NET = {}
+# ---- 8: mha_tiny (workloads.py), its expected bytes from tests/spec_ref.py ------------------------------------------------
+NAME = "mha_tiny"
+ATTENTIONS = ("attn1", "attn2")
+TRACED = ("pool", "ln1", "qkv1", "attn1", "add1", "c2", "attn2", "add2", "gap", "fc")
 
 
-def _make_net(i8ie):
-    class MhaNet(i8ie.Module):
-        def __init__(self):
-            super().__init__()
-            for attr, L in mr.NET_LAYERS.items():
-                if L[0] == "conv":
-                    setattr(self, attr, i8ie.Conv2d(L[1], L[2], kernel_size=L[3], stride=L[4], padding=L[5]))
-                elif L[0] == "ln":
-                    setattr(self, attr, i8ie.LayerNorm(L[1]))
-                else:
-                    setattr(self, attr, i8ie.Linear(L[1], L[2]))
-            self.attn1, self.attn2 = i8ie.Attention(mr.NET_HEADS), i8ie.Attention(mr.NET_HEADS)
-            self.add1, self.add2 = i8ie.Add(), i8ie.Add()
-            self.trace = None
+def _net(per_channel):
+    """nc.calibrated on the device sampler: that calibrator on score tensors too"""
+    import net_cases as nc
 
-        def keep(self, name, t):
-            if self.trace is not None:
-                self.trace[name] = t.numpy()
-            return t
-
-        def forward(self, x):
-            x = self.keep("pool", i8ie.max_pool2d(i8ie.relu(self.c1(x)), 2, 2))
-            y = self.keep("qkv1", self.qkv1(self.keep("ln1", self.ln1(x))))
-            y = self.keep("attn1", self.attn1(y))                                # packed, d = 8: attn_direct
-            x = self.keep("add1", self.add1(self.proj1(y), x))
-            x = self.keep("c2", self.c2(i8ie.relu(x)))                           # a bordered consumer
-            y = self.keep("attn2", self.attn2(self.q2(x), self.k2(x), self.v2(x)))   # d = 16: attn_mfma
-            x = self.keep("add2", self.add2(self.proj2(y), x))
-            x = self.keep("gap", i8ie.global_avg_pool2d(i8ie.relu(x)))
-            return self.fc(x.reshape(-1, 32))
-
-    return MhaNet()
-
-
-def _net(i8ie, per_channel):
-    """(net, qlayers, qp, score_qp): the test network calibrated on the device, once per weight mode; every quantisation
-    parameter is read from the product"""
-    import _CXX_i8ie as cx
-
-    if per_channel not in _NET:
-        sd = mr.net_state_dict()
-        net = _make_net(i8ie)
-        net.load(sd)
-        cx.set_calibration_mode("device")
-        cx.set_calibration_seed(7)
-        try:
-            net.prepare()
-            net(i8ie.tensor(mr.net_input(8, mr.CALIB_SEED)))
-            net.convert(per_channel)
-        finally:
-            cx.set_calibration_mode("auto")
-            cx.set_calibration_seed(-1)
-        qp = {a: getattr(net, a).output_qparams() for a in list(mr.NET_LAYERS) + list(mr.NET_JOINS)}
-        sq = {a: getattr(net, a).score_qparams() for a in mr.NET_ATTENTIONS}
-        _NET[per_channel] = (net, mr.net_quantize_layers(sd, per_channel), qp, sq)
-    return _NET[per_channel]
+    return nc.calibrated(NAME, per_channel, calib_images=8, mode="device")
 
 
 @pytest.mark.parametrize("per_channel", [False, True], ids=["per_tensor", "per_channel"])
 @pytest.mark.parametrize("batch", [1, 5])
 def test_mha_net_bit_exact(i8ie, batch, per_channel, tmp_path):
-    """logits and every traced tensor against mha_ref.net_forward: eager, under force-fallback, replayed as one HIP graph, and
-    from a fresh net that loaded what save_quantized() wrote"""
-    import _CXX_i8ie as cx
-    from int8inferenceengine_amd.graph import GraphedForward
+    """logits and every traced tensor against spec_ref.forward: eager, tensor by tensor, under force-fallback, replayed as one
+    HIP graph, and from a fresh net that loaded what save_quantized() wrote"""
+    import net_cases as nc
+    import spec_ref as sr
+    from int8inferenceengine_amd import workloads as wl
 
-    net, qlayers, qp, sq = _net(i8ie, per_channel)
-    assert all(s > 0 and s != 1.0 for s, _ in list(qp.values()) + list(sq.values())), (qp, sq)   # everything was calibrated
-    x = mr.net_input(batch)
+    net, qlayers, qp, jqp = _net(per_channel)
+    both = dict(qp, **jqp)
+    assert sorted(k for k in jqp if k.endswith(mr.SCORES)) == [a + mr.SCORES for a in ATTENTIONS]
+    assert all(s > 0 and s != 1.0 for s, _ in both.values()), both   # everything was calibrated, the scores included
+    x = wl.synthetic_input(NAME, batch, seed=sr.INPUT_SEED)
     trace = {}
-    want = mr.net_forward(x, qlayers, qp, sq, per_channel, trace)
+    want = sr.forward(wl.network(NAME), x, qlayers, qp, jqp, per_channel, sr.traces(mr.tracer(trace, jqp), sr.keeps(TRACED, trace)))
     assert want.shape == (batch, 10) and len(np.unique(want)) > 1
-    for a in mr.NET_ATTENTIONS:   # the expected bytes discriminate: spread scores, probabilities and results
+    for a in ATTENTIONS:   # the expected bytes discriminate: spread scores, probabilities and results
         assert len(np.unique(trace[a + ".S"])) > 30 and len(np.unique(trace[a + ".P"])) >= 16 and len(np.unique(trace[a])) >= 16
-    assert support.same_bits(net(i8ie.tensor(x)).numpy(), want), "eager"
-    net.trace = {}
-    try:
-        assert support.same_bits(net(i8ie.tensor(x)).numpy(), want), "traced"
-        mine = net.trace
-    finally:
-        net.trace = None
-    assert sorted(mine) == sorted(mr.NET_TRACED)
-    for k in mr.NET_TRACED:
+    nc.check_bit_exact(i8ie, net, NAME, x, want, fallback=True, graph=True, reload_dir=tmp_path, expect_jqp=both)
+    mine = {}
+    nc.traced(i8ie, net, NAME, x, sr.keeps(TRACED, mine))
+    assert sorted(mine) == sorted(TRACED) and sorted(trace) == sorted(TRACED + tuple(a + s for a in ATTENTIONS for s in (".S", ".P")))
+    for k in TRACED:   # ("fc": the logits of the walk tensor by tensor)
         assert mine[k].shape == trace[k].shape and np.array_equal(mine[k], trace[k]), k
-    cx.force_fallback(True)
-    try:
-        fb = net(i8ie.tensor(x)).numpy()
-    finally:
-        cx.force_fallback(False)
-    assert support.same_bits(fb, want), "force_fallback"
-    g = GraphedForward(net, i8ie.tensor(x).prefetch())
-    for _ in range(2):
-        assert support.same_bits(g().numpy(), want), "graph replay"
-    path = str(tmp_path / "mha_net.npz")
-    net.save_quantized(path)
-    fresh = _make_net(i8ie)
-    fresh.load_quantized_file(path)
-    assert {a: getattr(fresh, a).output_qparams() for a in qp} == qp
-    assert {a: getattr(fresh, a).score_qparams() for a in sq} == sq
-    assert support.same_bits(fresh(i8ie.tensor(x)).numpy(), want), "reloaded"
 
 
 def test_mha_net_kernels_and_launches(i8ie):
     """block 1 (packed, d = 8) runs in attn_direct, block 2 (d = 16) in attn_mfma; one launch per layer, attention and Add, the
     relus, borders and re-biases folded: c1 + pool, ln1, qkv1, attn1, proj1, add1, c2, q2, k2, v2, attn2, proj2, add2, gap, fc"""
     import _CXX_i8ie as cx
+    import spec_ref as sr
+    from int8inferenceengine_amd import workloads as wl
 
-    net = _net(i8ie, False)[0]
-    x = mr.net_input(5)
+    net = _net(False)[0]
+    x = wl.synthetic_input(NAME, 5, seed=sr.INPUT_SEED)
     net(i8ie.tensor(x)).numpy()
     cx.synchronize()
     cx.profile_start()
@@ -544,9 +480,7 @@ def test_mha_net_kernels_and_launches(i8ie):
         net(i8ie.tensor(x)).numpy()
     finally:
         prof = cx.profile_stop()
-    launches = {}
-    for k, v in prof.items():
-        launches[k.split("|")[0]] = launches.get(k.split("|")[0], 0) + v[0]
+    launches = support.launch_counts(prof)
     print(launches)
     assert launches.get("attn_direct") == 1 and launches.get("attn_mfma") == 1, launches
     for k in launches:

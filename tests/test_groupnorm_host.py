@@ -288,3 +288,64 @@ def test_private_binding_entries_are_the_recorded_ones():
     names = sorted(n for n in dir(c) if not n.startswith("_") or n in ("__init__", "__call__"))
     assert names == sorted(want["_GroupNorm"]) and {n: getattr(c, n).__doc__ for n in names} == want["_GroupNorm"]
     assert cx._group_norm.__doc__ == want["_group_norm"]
+
+
+NAME = "groupnorm_tiny"
+GROUPNORMS = ("a_gn1", "a_gn2", "d_gn", "b_gn1", "b_gn2", "s_gn")
+TRACED = ("pool",) + GROUPNORMS + ("a_add", "b_add", "s_sig", "s_mul", "s_c", "s_attn", "s_add", "gap")
+
+
+def test_network_walk_discriminates_and_agrees_with_float64():
+    """spec_ref's walk of groupnorm_tiny (the network of tests/test_gpu_groupnorm.py), on quantisation parameters from a float64
+    forward: every GroupNorm output and the attention's scores, probabilities and result are spread, and the per-channel walk
+    differs from the per-tensor one (the expected bytes tell the two modes apart)"""
+    import mha_ref as mr
+    import spec_ref as sr
+    from int8inferenceengine_amd import workloads as wl
+
+    entry = wl.network(NAME)
+    sd = wl.synthetic_state_dict(NAME, sr.WEIGHT_SEED)
+    x = wl.synthetic_input(NAME, 4, seed=sr.CALIB_SEED)
+    qp, jqp = sr.fp32_qparams(entry, sd, x)
+    assert sorted(qp) == sorted(entry[0]) == sorted(wl.layer_names(NAME))
+    assert sorted(jqp) == sorted(["a_add", "b_add", "s_sig", "s_mul", "s_attn", "s_add", "s_attn" + mr.SCORES])
+    outs = {}
+    for pc in (False, True):
+        trace = {}
+        outs[pc] = sr.forward(entry, x, sr.quantize_layers(entry, sd, pc), qp, jqp, pc, sr.traces(mr.tracer(trace, jqp), sr.keeps(TRACED, trace)))
+        assert outs[pc].shape == (4, 10) and sorted(trace) == sorted(TRACED + ("s_attn.S", "s_attn.P"))
+        for k in GROUPNORMS:
+            assert len(np.unique(trace[k])) >= 32 and ((trace[k] == 0) | (trace[k] == 255)).mean() < 0.05, k
+        S, P = trace["s_attn.S"], trace["s_attn.P"]
+        assert len(np.unique(S)) > 30 and ((S == 0) | (S == 255)).mean() < 0.05 and len(np.unique(P)) >= 16 and len(np.unique(trace["s_attn"])) >= 16
+        assert trace["a_gn2"].shape == (4, 16, 8, 8) and trace["s_attn"].shape == (4, 20, 4, 4)
+    assert not np.array_equal(outs[False], outs[True])
+    assert (outs[False].argmax(1) == outs[True].argmax(1)).all()
+
+
+def test_registry_networks_and_their_macs():
+    from int8inferenceengine_amd import workloads as wl
+
+    L, spec, shape = wl.network(NAME)
+    assert shape == (3, 32, 32) and list(L) == ["c1", "a_c1", "a_gn1", "a_c2", "a_gn2", "down", "d_gn", "b_c1", "b_gn1", "b_c2", "b_gn2",
+                                                "s_gn", "s_c", "s_qkv", "s_proj", "fc"]
+    assert {a: v[1:] for a, v in L.items() if v[0] == "gn"} == {"a_gn1": (4, 16), "a_gn2": (16, 16), "d_gn": (5, 20), "b_gn1": (1, 20),
+                                                                 "b_gn2": (10, 20), "s_gn": (4, 20)}
+    assert wl.join_names(NAME) == ["a_add", "b_add", "s_sig", "s_mul", "s_attn", "s_add"] and wl.attention_names(NAME) == ["s_attn"]
+    # SiLU: the GroupNorm's result is the Mul's first operand, its sigmoid the second
+    i = spec.index(("layer", "s_gn"))
+    assert spec[i + 1:i + 6] == [("save", "s_g"), ("act", "s_sig", "sigmoid"), ("save", "s_sig"), ("load", "s_g"), ("mul", "s_mul", "s_sig")]
+    sd = wl.synthetic_state_dict(NAME, 3)
+    assert sorted(sd) == sorted(k + s for k in L for s in (".weight", ".bias"))
+    assert sd["b_gn2.weight"].shape == (20,) and 0.5 <= sd["b_gn2.weight"].min() and np.abs(sd["b_gn2.bias"]).max() <= 0.3
+    # by hand: c1 16x16 x 16 x 27; two 3x3 convs 16 -> 16 at 8x8; down 4x4 x 20 x 144; at 4x4 three 3x3 convs 20 -> 20, the packed
+    # 1x1 20 -> 60 and the 1x1 20 -> 20; fc 200.  GroupNorms, the SiLU and the products inside the Attention count nothing.
+    assert wl.macs_per_image(NAME) == 256 * 16 * 27 + 2 * 64 * 16 * 144 + 16 * 20 * 144 + 16 * 20 * (3 * 180 + 60 + 20) + 200 == 650184
+    R, rspec, _ = wl.network("groupnorm_resnet_cifar")
+    B = wl.network("resnet18_cifar")[0]
+    assert all(v[:2] == ("gn", 32) for v in R.values() if v[0] == "gn") and sum(v[0] == "gn" for v in R.values()) == 22
+    assert [v for a, v in R.items() if v[0] == "conv" and not a.startswith("m_")] == [v for v in B.values() if v[0] == "conv"]
+    assert R["m_qkv"] == ("conv", 256, 768, 1, 1, 0) and ("attention", "m_attn", 4) in rspec and R["fc"] == ("fc", 512, 10)
+    # by hand: every weighted layer of resnet18_cifar (its pinned figure leaves the three 1x1 projections out: 3 x 2097152) and
+    # the middle block at 8x8: 3x3 256 -> 256, 1x1 256 -> 768, 1x1 256 -> 256
+    assert wl.macs_per_image("groupnorm_resnet_cifar") == 549131264 + 3 * 2097152 + 64 * 256 * (2304 + 768 + 256) == 609948672

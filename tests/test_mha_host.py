@@ -175,22 +175,64 @@ def test_module_saves_and_restores_both_parameter_sets(i8ie):
     assert sorted(other.quantized_state_dict()) == sorted(sd)
 
 
+NAME = "mha_tiny"
+ATTENTIONS = ("attn1", "attn2")
+TRACED = ("pool", "ln1", "qkv1", "attn1", "add1", "c2", "attn2", "add2", "gap")
+
+
 def test_network_walk_discriminates_and_agrees_with_float64():
-    """the numpy walk of the test network of tests/test_gpu_mha.py, on quantisation parameters from a float64 forward: every
-    traced tensor is spread (few saturated scores, many distinct probabilities), the logits follow the float64 ones, and the
-    per-channel walk differs from the per-tensor one (the expected bytes tell the two modes apart)"""
-    sd = mr.net_state_dict()
-    qp, sq = mr.net_fp32_qparams(sd, mr.net_input(4, mr.CALIB_SEED))
-    assert sorted(qp) == sorted(list(mr.NET_LAYERS) + list(mr.NET_JOINS)) and sorted(sq) == sorted(mr.NET_ATTENTIONS)
-    x = mr.net_input(4, mr.CALIB_SEED)
+    """spec_ref's walk of mha_tiny (the network of tests/test_gpu_mha.py), on quantisation parameters from a float64 forward:
+    every traced tensor is spread (few saturated scores, many distinct probabilities), the logits follow the float64 ones, and
+    the per-channel walk differs from the per-tensor one (the expected bytes tell the two modes apart)"""
+    import spec_ref as sr
+    from int8inferenceengine_amd import workloads as wl
+
+    entry = wl.network(NAME)
+    sd = wl.synthetic_state_dict(NAME, sr.WEIGHT_SEED)
+    x = wl.synthetic_input(NAME, 4, seed=sr.CALIB_SEED)
+    qp, jqp = sr.fp32_qparams(entry, sd, x)
+    assert sorted(qp) == sorted(entry[0]) == sorted(wl.layer_names(NAME))
+    assert sorted(jqp) == sorted(["attn1", "add1", "attn2", "add2"] + [a + mr.SCORES for a in ATTENTIONS])
     outs = {}
     for pc in (False, True):
         trace = {}
-        outs[pc] = mr.net_forward(x, mr.net_quantize_layers(sd, pc), qp, sq, pc, trace)
-        assert outs[pc].shape == (4, 10) and sorted(trace) == sorted(list(mr.NET_TRACED) + [a + s for a in mr.NET_ATTENTIONS for s in (".S", ".P")])
-        for a in mr.NET_ATTENTIONS:
+        outs[pc] = sr.forward(entry, x, sr.quantize_layers(entry, sd, pc), qp, jqp, pc, sr.traces(mr.tracer(trace, jqp), sr.keeps(TRACED, trace)))
+        assert outs[pc].shape == (4, 10) and sorted(trace) == sorted(list(TRACED) + [a + s for a in ATTENTIONS for s in (".S", ".P")])
+        for a in ATTENTIONS:
             S, P = trace[a + ".S"], trace[a + ".P"]
             assert len(np.unique(S)) > 30 and ((S == 0) | (S == 255)).mean() < 0.05 and len(np.unique(P)) >= 16 and len(np.unique(trace[a])) >= 16
         assert trace["attn1"].shape == (4, 16, 8, 8) and trace["attn2"].shape == (4, 32, 4, 4)
     assert not np.array_equal(outs[False], outs[True])
     assert (outs[False].argmax(1) == outs[True].argmax(1)).all()
+
+
+def test_registry_networks_and_their_macs():
+    from int8inferenceengine_amd import workloads as wl
+
+    L, spec, shape = wl.network(NAME)
+    assert shape == (3, 32, 32) and list(L) == ["c1", "ln1", "qkv1", "proj1", "c2", "q2", "k2", "v2", "proj2", "fc"]
+    assert L["qkv1"] == ("conv", 16, 48, 1, 1, 0) and L["c2"] == ("conv", 16, 32, 3, 2, 1) and L["ln1"] == ("ln", 16)
+    assert ("attention", "attn1", 2) in spec and ("attention", "attn2", 2, "k2", "v2") in spec and "attention" in wl.OPS
+    assert wl.attention_names(NAME) == list(ATTENTIONS) and wl.join_names(NAME) == ["attn1", "add1", "attn2", "add2"]
+    # the 1 / sqrt(d) of the scores: on the query filters of the packed projection (d = 8), on all of q2 (d = 16)
+    fold = wl.FOLDS[NAME]
+    assert sorted(fold) == ["q2", "qkv1"] and fold["q2"] == 0.25
+    assert np.array_equal(fold["qkv1"], np.where(np.arange(48) < 16, 1.0 / np.sqrt(8.0), 1.0)) and fold["qkv1"].dtype == np.float64
+    sd = wl.synthetic_state_dict(NAME, 3)
+    rng = np.random.default_rng(3)   # the draws up to qkv1's bias, without the fold
+    w = [rng.uniform(-1, 1, (16, 3, 3, 3)), rng.uniform(-1, 1, 16), rng.uniform(0.5, 1.5, 16), rng.uniform(-0.3, 0.3, 16),
+         rng.uniform(-1, 1, (48, 16, 1, 1)) * np.sqrt(6.0 / 16), rng.uniform(-1, 1, 48) / 4.0]
+    assert np.array_equal(sd["qkv1.weight"], (w[4] * fold["qkv1"].reshape(48, 1, 1, 1)).astype(f32))
+    assert np.array_equal(sd["qkv1.bias"], (w[5] * fold["qkv1"]).astype(f32))
+    # by hand: c1 16x16 x 16 x 27; at 8x8 qkv1 16 -> 48 and proj1 16 -> 16; c2 4x4 x 32 x 144; at 4x4 four 1x1 convs 32 <-> 32;
+    # fc 320.  The LayerNorm and the products inside an Attention count nothing.
+    assert wl.macs_per_image(NAME) == 256 * 16 * 27 + 64 * 16 * (48 + 16) + 16 * 32 * 144 + 4 * 16 * 32 * 32 + 320 == 315712
+    B, bspec, _ = wl.network("botnet_cifar")
+    assert list(B) == ["stem", "s1a", "s1b", "s2a", "s2b", "s2s", "s3in", "b1r", "b1qkv", "b1e", "b2r", "b2qkv", "b2e", "fc"]
+    assert B["b2qkv"] == ("conv", 128, 384, 1, 1, 0) and wl.attention_names("botnet_cifar") == ["b1attn", "b2attn"]
+    assert wl.add_names("botnet_cifar") == ["add1", "add2", "add_b1", "add_b2"] and ("attention", "b1attn", 4) in bspec
+    assert np.array_equal(wl.FOLDS["botnet_cifar"]["b1qkv"], np.where(np.arange(384) < 128, 1.0 / np.sqrt(32.0), 1.0))
+    # by hand: stem 32x32 x 32 x 27; two 3x3 convs 32 -> 32 at 32x32; at 16x16 3x3 32 -> 64, 3x3 64 -> 64 and the 1x1 shortcut;
+    # s3in 8x8 x 256 x 576; per bottleneck at 8x8: 256 -> 128, 128 -> 384, 128 -> 256; fc 2560
+    assert wl.macs_per_image("botnet_cifar") == 1024 * 32 * 27 + 2 * 1024 * 32 * 288 + 256 * 64 * (288 + 576 + 32) + 64 * 256 * 576 \
+        + 2 * 64 * (256 * 128 + 128 * 384 + 128 * 256) + 2560 == 58558976

@@ -35,7 +35,7 @@ def test_the_table_covers_both_registries_and_every_op():
     assert seen == sr.OPS == wl.OPS  # every op of the registry is known to both interpreters, and the replay below runs every known op
     assert seen - {"branch"} == {op[0] for n in names for op in wl._walk(wl.network(n)[1])}
     kinds = {wl.network(n)[0][a][0] for n in names for a in wl.layer_names(n)}
-    assert kinds == {"conv", "deconv", "fc", "ln"} and {"matmul", "softmax", "load"} <= seen and len(seen) == 16
+    assert kinds == {"conv", "deconv", "fc", "ln", "gn"} and {"matmul", "softmax", "load", "attention"} <= seen and len(seen) == 17
     assert any(wl.conv_dilation(L) > 1 for L in wl.network("aspp_tiny")[0].values())
 
 

@@ -8,8 +8,9 @@ import pinned_networks as pn
 def test_registry_macs_and_unknown_ops(monkeypatch):
     from int8inferenceengine_amd import workloads as wl
 
-    assert list(wl.NETWORKS) == pn.NAMES and len(pn.NAMES) == 25
-    assert pn.NAMES[21:] == ["nonlocal_tiny", "nonlocal_resnet_cifar", "convnext_tiny", "convnext_cifar"]
+    assert list(wl.NETWORKS) == pn.NAMES and len(pn.NAMES) == 29
+    assert pn.NAMES[21:25] == ["nonlocal_tiny", "nonlocal_resnet_cifar", "convnext_tiny", "convnext_cifar"]
+    assert pn.NAMES[25:] == ["mha_tiny", "botnet_cifar", "groupnorm_tiny", "groupnorm_resnet_cifar"]
     assert not hasattr(wl, "EXTRA_NETWORKS")
     assert {n: wl.macs_per_image(n) for n in pn.MACS} == pn.MACS
     assert wl.MAIN_PATH_MACS == set(pn.NAMES[:19])

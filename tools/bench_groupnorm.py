@@ -14,8 +14,9 @@ one the median over rounds.  Aims, from the bytes moved, with the project's spre
 LayerNorm (gn / ln <= 1.03), the split form at most 1.5 times it (three passes over the bytes against two; <= 1.545).  The bytes of
 the first two images are asserted against the definition (tests/groupnorm_ref.py).  This part goes through the C-ABI by ctypes.
 
-Then the step time of examples/groupnorm_resnet_cifar10.py at the same two batch sizes through the Python surface, with the
-share of the profiled kernel time its GroupNorm launches take (`--net-steps 0` skips it)."""
+Then the step time of workloads' groupnorm_resnet_cifar (the network of examples/groupnorm_resnet_cifar10.py) at the same two
+batch sizes through the Python surface, with the share of the profiled kernel time its GroupNorm launches take (`--net-steps 0`
+skips it)."""
 import argparse
 import ctypes as C
 import json
@@ -143,16 +144,15 @@ def kernels(args):
 
 def network(args):
     sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "examples"))
     import int8inferenceengine_amd  # noqa: F401
     import _CXX_i8ie as cx
     import i8ie
-    import groupnorm_resnet_cifar10 as ex
+    from int8inferenceengine_amd import workloads as wl
 
-    net = ex.calibrated()
+    net = wl.calibrated("groupnorm_resnet_cifar", calib_batch=wl.synthetic_input("groupnorm_resnet_cifar", 16, seed=99))
     rows = []
     for m in BATCHES:
-        x = i8ie.tensor(ex.synthetic_input(m)).prefetch()
+        x = i8ie.tensor(wl.synthetic_input("groupnorm_resnet_cifar", m)).prefetch()
         for _ in range(args.warmup):
             net(x).numpy()
         cx.synchronize()

@@ -9,8 +9,8 @@ is the library's own per-launch HIP-event bracket (i8ie_profile_start / _stop): 
 of `iters` profiled calls; a round's figure is its mean per call and the reported one the median over rounds.  Run-to-run spread
 of these figures is about +-3 %.  The aim is fused <= composition (ratio <= 1); every row records the ratio and met or MISSED.
 Before the timing the fused result of the first images is asserted against tests/mha_ref.py (the numpy definition) and the whole
-fused result against the composition's.  Then examples/botnet_cifar10.py's step through the Python surface with the share its
-attention launches take of the kernel time."""
+fused result against the composition's.  Then the step of workloads' botnet_cifar (the network of examples/botnet_cifar10.py)
+through the Python surface with the share its attention launches take of the kernel time."""
 import argparse
 import ctypes as C
 import json
@@ -22,7 +22,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "examples")):
+for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 BATCHES = [1000, 125]
@@ -145,12 +145,12 @@ def network(args):
     import int8inferenceengine_amd  # noqa: F401
     import _CXX_i8ie as cx
     import i8ie
-    import botnet_cifar10 as bot
+    from int8inferenceengine_amd import workloads as wl
 
-    net = bot.calibrated()
+    net = wl.calibrated("botnet_cifar", calib_batch=wl.synthetic_input("botnet_cifar", 16, seed=99))
     rows = []
     for m in BATCHES:
-        x = i8ie.tensor(bot.synthetic_input(m)).prefetch()
+        x = i8ie.tensor(wl.synthetic_input("botnet_cifar", m)).prefetch()
         for _ in range(args.warmup):
             net(x).numpy()
         walls = []
