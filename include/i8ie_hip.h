@@ -947,6 +947,54 @@ int64_t i8ie_groupnorm_workspace_bytes(int n, int C, int G, int h, int w);
 int i8ie_groupnorm_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int C, int G, int64_t hw,
                        const float* gamma_dev, const float* beta_dev, float eps);
 
+/* ---- max and average pooling with padding and ceil_mode (torch's geometry arguments; no counterpart in the reference) ----
+ * One square window k = kernel_size, one stride s, one padding p on every side, 0 <= p <= k / 2 (torch's rule), and
+ * k <= h + 2p, k <= w + 2p.  Per axis of length `in` the output size is, in integer division,
+ *     o = (in + 2p - k + (ceil_mode ? s - 1 : 0)) / s + 1;     if ceil_mode and (o - 1) * s >= in + p:  o -= 1
+ * (a window must start inside the image or its leading padding: (k, s, p, in) = (2, 2, 1, 3) gives 2, not 3).  Output
+ * (y, x) sees rows [y*s - p, min(y*s - p + k, h + p)) cut to [0, h), and columns likewise; every window has at least one
+ * valid tap (by p <= k / 2 and the drop rule).  The result carries the input's (scale, zero_point).
+ * max:  the maximum of the valid taps only -- padding never takes part; relu != 0: q = max(q, zero_point).
+ * avg:  with n_valid the number of valid taps and S their exact byte sum,
+ *     count_include_pad != 0 (torch's default):  D = (ye - ys) * (xe - xs), ys = y*s - p, ye = min(ys + k, h + p) and
+ *         likewise in x: the padding counts, a ceil-mode overhang beyond it does not; S' = S + (D - n_valid) * zero_point,
+ *         a padded zero being the byte zero_point
+ *     count_include_pad == 0:                    D = n_valid, S' = S
+ *     q = (S' + D / 2) / D        integer floor division: round to nearest, ties up (the rule of i8ie_avgpool2d_u8)
+ *     q = relu ? max(q, zero_point) : q
+ *   k * k <= 65536.
+ * FP32 (before convert(), and while calibrating), NCHW: max is i8ie_maxpool2d_f32's running maximum (start -FLT_MAX,
+ * mx >= v ? mx : v) over the valid taps in window order; avg sums the valid taps in fp32 in window order (rows outer,
+ * columns inner) and divides once by (float)D.
+ * With padding = 0 and ceil_mode = 0 every entry computes what its unpadded counterpart does.  Null pointers, non-positive
+ * sizes, negative padding or borders, p > k / 2, a window larger than the padded input and k * k > 65536 are I8IE_ERR_ARG,
+ * raised before any device call.  Stateless, no scratch, capturable in a graph (csrc/i8ie_padpool.hip, DESIGN.md
+ * section 8o).
+ * i8ie_pool_output_size: the output size above (host only); I8IE_ERR_ARG (negative) for arguments the entries refuse. */
+int i8ie_pool_output_size(int in, int kernel_size, int stride, int padding, int ceil_mode);
+/* NCHW in and out, any shape: one lane per output, off the timed path. */
+int i8ie_maxpool2d_u8_pad(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int n, int c, int h, int w,
+                          int kernel_size, int stride, int padding, int ceil_mode);
+int i8ie_avgpool2d_u8_pad(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int n, int c, int h, int w,
+                          int kernel_size, int stride, int padding, int ceil_mode, int count_include_pad,
+                          uint8_t zero_point);
+/* The same on NHWC buffers [n, h+2b, w+2b, c] -> [n, oh+2b', ow+2b', c], each with its own border and each plain
+ * (x_s8 = 0) or re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80).  The input's border bytes are not padding:
+ * neither kernel ever reads a byte outside the interior.  Only the interior of `out` is written: its border bytes are the
+ * caller's (i8ie_fill_border_u8).  Any c: 16 / 4 / 1 channels per lane by c % 16, c % 4 and the pointers' alignment.
+ * `out` must not overlap `in`.  h, w: logical input dims. */
+int i8ie_maxpool2d_u8_nhwc_pad(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev,
+                               int out_border, int out_s8, int n, int c, int h, int w, int kernel_size, int stride,
+                               int padding, int ceil_mode, int relu, uint8_t zero_point);
+int i8ie_avgpool2d_u8_nhwc_pad(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev,
+                               int out_border, int out_s8, int n, int c, int h, int w, int kernel_size, int stride,
+                               int padding, int ceil_mode, int count_include_pad, int relu, uint8_t zero_point);
+/* FP32, NCHW (above). */
+int i8ie_maxpool2d_f32_pad(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w,
+                           int kernel_size, int stride, int padding, int ceil_mode);
+int i8ie_avgpool2d_f32_pad(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w,
+                           int kernel_size, int stride, int padding, int ceil_mode, int count_include_pad);
+
 #ifdef __cplusplus
 }
 #endif

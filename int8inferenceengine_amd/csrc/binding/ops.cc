@@ -150,6 +150,69 @@ Tensor<u8_t> avg_pool_u8(Tensor<u8_t>& in, ssize_t k, ssize_t s, bool global) {
         return st;
       });
 }
+// ---- the pools with torch's padding and ceil_mode (no counterpart in the reference; geometry and arithmetic:
+// include/i8ie_hip.h, i8ie_pool_output_size).  The i8ie package sends a call here only where the geometry differs from the
+// unpadded floor pool's; that one keeps the entries above, and with them the conv + max-pool fusion.
+struct PadPool {
+  int k, s, p, ceil_mode, include_pad;
+  bool avg;
+  std::vector<ssize_t> oshp;
+};
+// the checked arguments of one call, and the result's shape
+template <typename T>
+PadPool pad_pool_args(const Tensor<T>& in, ssize_t k, ssize_t s, ssize_t p, bool ceil_mode, bool include_pad, bool avg) {
+  const std::string what = avg ? "i8ie: avg_pool2d" : "i8ie: max_pool2d";
+  if (in.shape.size() != 4) throw std::runtime_error(what + " expects an NCHW tensor");
+  if (k <= 0 || s <= 0) throw std::runtime_error(what + ": kernel_size and stride must be positive");
+  if (p < 0 || p > k / 2) throw std::runtime_error(what + ": padding must be at least 0 and at most half the kernel_size");
+  if (k > in.shape[2] + 2 * p || k > in.shape[3] + 2 * p) throw std::runtime_error(what + ": window larger than the padded input");
+  if (k * k > 65536) throw std::runtime_error(what + ": window of more than 65536 elements");
+  for (ssize_t d : in.shape)
+    if (d <= 0 || d > 0x7FFFFFFF) throw std::runtime_error(what + ": empty tensor");
+  const int oh = i8ie_pool_output_size((int)in.shape[2], (int)k, (int)s, (int)p, ceil_mode ? 1 : 0);
+  const int ow = i8ie_pool_output_size((int)in.shape[3], (int)k, (int)s, (int)p, ceil_mode ? 1 : 0);
+  if (oh < 0 || ow < 0) throw std::runtime_error(std::string("i8ie: ") + i8ie_last_error());
+  return PadPool{(int)k, (int)s, (int)p, ceil_mode ? 1 : 0, include_pad ? 1 : 0, avg, {in.shape[0], in.shape[1], oh, ow}};
+}
+Tensor<float> pad_pool_f32(Tensor<float>& in, const PadPool& g) {
+  Tensor<float> out(g.oshp);
+  const int n = (int)in.shape[0], c = (int)in.shape[1], h = (int)in.shape[2], w = (int)in.shape[3];
+  if (g.avg) check(i8ie_avgpool2d_f32_pad(ctx(), in.dptr(), out.dptr(), n, c, h, w, g.k, g.s, g.p, g.ceil_mode, g.include_pad));
+  else check(i8ie_maxpool2d_f32_pad(ctx(), in.dptr(), out.dptr(), n, c, h, w, g.k, g.s, g.p, g.ceil_mode));
+  return out;
+}
+Tensor<u8_t> pad_pool_u8(Tensor<u8_t>& in, const PadPool& g) {
+  const std::vector<ssize_t> ishp = in.shape, oshp = g.oshp;
+  need_contents(in);
+  const u8_t zp = in.zero_point;
+  // deferred like avg_pool2d's result: relu(pool(..)) is one launch, and a consuming conv gets its zero-point border and,
+  // where it reads them, re-biased bytes straight from the pool kernel
+  return deferred_one_input(  // (as the unpadded pools: the input's qparams)
+      in, oshp, in.scale, zp, [ishp, zp, g](std::shared_ptr<Storage> si, bool relu, int border, bool s8) {
+        const std::vector<ssize_t>& oshp = g.oshp;
+        const int n = (int)ishp[0], c = (int)ishp[1], h = (int)ishp[2], w = (int)ishp[3];
+        // (a view whose storage is NHWC under other logical dims goes back to the reference's order: the view is defined on it)
+        if (si->layout == I8IE_LAYOUT_NHWC && (si->dn != ishp[0] || si->dc != ishp[1] || si->dh != ishp[2] || si->dw != ishp[3])) si->to_nchw();
+        std::shared_ptr<Storage> st;
+        if (si->layout == I8IE_LAYOUT_NHWC) {
+          st = nhwc_storage(oshp, border, zp, s8);
+          const uint8_t* ip = (const uint8_t*)si->device_ptr();
+          if (g.avg)
+            check(i8ie_avgpool2d_u8_nhwc_pad(ctx(), ip, si->border, si->s8 ? 1 : 0, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, n, c, h, w,
+                                             g.k, g.s, g.p, g.ceil_mode, g.include_pad, relu ? 1 : 0, zp));
+          else
+            check(i8ie_maxpool2d_u8_nhwc_pad(ctx(), ip, si->border, si->s8 ? 1 : 0, (uint8_t*)st->dev, st->border, st->s8 ? 1 : 0, n, c, h, w,
+                                             g.k, g.s, g.p, g.ceil_mode, relu ? 1 : 0, zp));
+        } else {  // an NCHW operand (a user-made tensor)
+          st = device_storage((size_t)oshp[0] * oshp[1] * oshp[2] * oshp[3]);
+          const uint8_t* ip = (const uint8_t*)si->device_ptr();
+          if (g.avg) check(i8ie_avgpool2d_u8_pad(ctx(), ip, (uint8_t*)st->dev, n, c, h, w, g.k, g.s, g.p, g.ceil_mode, g.include_pad, zp));
+          else check(i8ie_maxpool2d_u8_pad(ctx(), ip, (uint8_t*)st->dev, n, c, h, w, g.k, g.s, g.p, g.ceil_mode));
+          if (relu) check(i8ie_relu_u8(ctx(), (const uint8_t*)st->dev, (uint8_t*)st->dev, (int64_t)st->bytes, zp));
+        }
+        return st;
+      });
+}
 // ---- upsample (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_upsample2d_u8) -----------------------
 template <typename T>
 std::vector<ssize_t> upsample_shape(const Tensor<T>& in, ssize_t fh, ssize_t fw, int mode) {
@@ -352,6 +415,21 @@ void bind_ops(py::module_& m) {
         py::arg("kernel_size"), py::arg("stride"));
   m.def("global_avg_pool2d", [](Tensor<float>& x) { return avg_pool_f32(x, 0, 1, true); }, py::arg("x"));
   m.def("global_avg_pool2d", [](Tensor<u8_t>& x) { return avg_pool_u8(x, 0, 1, true); }, py::arg("x"));
+  // additive: the pools with torch's padding and ceil_mode (include/i8ie_hip.h, i8ie_pool_output_size).  Private like
+  // _group_norm (tests/golden/binding_surface.json stays as it is): i8ie.max_pool2d / i8ie.avg_pool2d come here where the
+  // geometry is not the unpadded floor pool's.  No s8 overload: s8 tensors keep the unpadded pool only
+  m.def("_max_pool2d_pad", [](Tensor<float>& x, ssize_t k, ssize_t s, ssize_t p, bool ceil_mode) {
+    return pad_pool_f32(x, pad_pool_args(x, k, s, p, ceil_mode, false, false));
+  }, py::arg("x"), py::arg("kernel_size"), py::arg("stride"), py::arg("padding"), py::arg("ceil_mode"));
+  m.def("_max_pool2d_pad", [](Tensor<u8_t>& x, ssize_t k, ssize_t s, ssize_t p, bool ceil_mode) {
+    return pad_pool_u8(x, pad_pool_args(x, k, s, p, ceil_mode, false, false));
+  }, py::arg("x"), py::arg("kernel_size"), py::arg("stride"), py::arg("padding"), py::arg("ceil_mode"));
+  m.def("_avg_pool2d_pad", [](Tensor<float>& x, ssize_t k, ssize_t s, ssize_t p, bool ceil_mode, bool count_include_pad) {
+    return pad_pool_f32(x, pad_pool_args(x, k, s, p, ceil_mode, count_include_pad, true));
+  }, py::arg("x"), py::arg("kernel_size"), py::arg("stride"), py::arg("padding"), py::arg("ceil_mode"), py::arg("count_include_pad"));
+  m.def("_avg_pool2d_pad", [](Tensor<u8_t>& x, ssize_t k, ssize_t s, ssize_t p, bool ceil_mode, bool count_include_pad) {
+    return pad_pool_u8(x, pad_pool_args(x, k, s, p, ceil_mode, count_include_pad, true));
+  }, py::arg("x"), py::arg("kernel_size"), py::arg("stride"), py::arg("padding"), py::arg("ceil_mode"), py::arg("count_include_pad"));
   // additive (the reference has no resize op): nearest / bilinear upsampling by integer factors (mode: I8IE_UPSAMPLE_*), exact
   // integers on u8 tensors, the fp32 sequence of include/i8ie_hip.h on FP32 ones
   m.def("upsample", &upsample_f32, py::arg("x"), py::arg("factor_h"), py::arg("factor_w"), py::arg("mode"));

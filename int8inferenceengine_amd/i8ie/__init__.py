@@ -38,8 +38,23 @@ def relu(x):
     return Tensor(_C.relu(x.data))
 
 
-def max_pool2d(x, kernel_size, stride):
-    return Tensor(_C.max_pool2d(x.data, kernel_size, stride))
+def _same_as_floor_pool(x, k, s, padding, ceil_mode):
+    """Is this pool geometry the unpadded floor pool's: no padding, and ceil_mode off or changing no output size?  (The ceil
+    size is the floor size exactly where (in - k) % s == 0, and the dropped-window rule never applies without padding.)"""
+    shape = x.shape
+    return padding == 0 and (not ceil_mode or (len(shape) == 4 and 0 < k <= min(shape[2:]) and s > 0
+                                              and all((d - k) % s == 0 for d in shape[2:])))
+
+
+def max_pool2d(x, kernel_size, stride, padding=0, ceil_mode=False):
+    """Max pooling over kernel_size x kernel_size windows (NCHW), with torch's `padding` (0 <= padding <= kernel_size // 2,
+    never part of a maximum) and `ceil_mode` (include/i8ie_hip.h, i8ie_pool_output_size).  The result carries the input's
+    scale and zero point.  A call whose geometry is the unpadded floor pool's (padding 0, and ceil_mode off or changing no
+    output size) is the reference's max_pool2d, on every tensor type; int8 (s8) tensors take that form only."""
+    k, s, p = int(kernel_size), int(stride), int(padding)
+    if _same_as_floor_pool(x, k, s, p, ceil_mode):
+        return Tensor(_C.max_pool2d(x.data, kernel_size, stride))
+    return Tensor(_C._max_pool2d_pad(x.data, k, s, p, bool(ceil_mode)))
 
 
 def quantize(x, scale, zero_point):
@@ -209,12 +224,17 @@ def lut(x, table, scale, zero_point):
     return Tensor(_C.lut(x.data, np.ascontiguousarray(t), float(scale), int(zero_point)))
 
 
-def avg_pool2d(x, kernel_size, stride=None):
-    """Average pooling over kernel_size x kernel_size windows (NCHW, floor output size, no padding, as max_pool2d);
-    `stride` defaults to `kernel_size`.  uint8 tensors: the integer mean rounded to nearest, ties up,
-    (sum + n // 2) // n (include/i8ie_hip.h, i8ie_avgpool2d_u8); the result carries the input's scale and zero point.
-    FP32 tensors: the fp32 sum of the window divided by n."""
-    return Tensor(_C.avg_pool2d(x.data, int(kernel_size), int(kernel_size if stride is None else stride)))
+def avg_pool2d(x, kernel_size, stride=None, padding=0, ceil_mode=False, count_include_pad=True):
+    """Average pooling over kernel_size x kernel_size windows (NCHW, as max_pool2d); `stride` defaults to `kernel_size`.
+    uint8 tensors: the integer mean rounded to nearest, ties up, (sum + n // 2) // n (include/i8ie_hip.h,
+    i8ie_avgpool2d_u8); the result carries the input's scale and zero point.  FP32 tensors: the fp32 sum of the window
+    divided by n.  `padding` (0 <= padding <= kernel_size // 2), `ceil_mode` and `count_include_pad` are torch's
+    (include/i8ie_hip.h, i8ie_pool_output_size): a padded tap is the value zero (the byte zero_point) and counts in n
+    unless count_include_pad is False; a ceil-mode overhang beyond the padding never counts."""
+    k, s, p = int(kernel_size), int(kernel_size if stride is None else stride), int(padding)
+    if _same_as_floor_pool(x, k, s, p, ceil_mode):
+        return Tensor(_C.avg_pool2d(x.data, k, s))
+    return Tensor(_C._avg_pool2d_pad(x.data, k, s, p, bool(ceil_mode), bool(count_include_pad)))
 
 
 def global_avg_pool2d(x):
