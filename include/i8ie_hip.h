@@ -725,9 +725,19 @@ int i8ie_activation_f32(i8ie_ctx* ctx, int kind, float param, const float* in_de
  * caller's, as for i8ie_add_u8_nhwc.  out_pix_axis = 0 is the plain strided form.  `out` must not overlap an operand (a
  * and b may be the same buffer).  As in the other stateless entries, extents are the caller's responsibility: neither the
  * overlap nor whether the strides describe disjoint elements inside the caller's allocations is checked.
+ * The stride contract (tests/test_gpu_attention.py pins it): any non-negative strides with row_stride == 1 or col_stride == 1
+ * are accepted.  A matrix may lie inside a larger allocation -- a row pitch above the row's length, a batch pitch above the
+ * matrix' size -- and the bytes between rows and between batch items are never read (operands) or written (result).
+ * batch_stride == 0 on an operand is a broadcast: every batch item reads the same matrix, on a, on b or on both.
+ * batch_stride == 0 on the result with b > 1 is I8IE_ERR_ARG (the batch items would share their bytes).  No stride needs
+ * any alignment for correctness: bmm_mfma stages a K-contiguous operand (unit stride along k) in 16-byte loads where its
+ * pointer and every stride other than the unit one (batch_stride included) are multiples of 16, in 4-byte loads where
+ * they are multiples of 4, else in bytes; a K-strided operand (unit stride along its rows) in 4-byte loads where they are
+ * multiples of 4, else in bytes, never wider; four result columns are one dword store where that address is 4-byte
+ * aligned, else bytes.
  * acc_dbg_dev is NULL or int32 [b, m, n] and receives C.  Stateless and capturable in a graph: one launch, no device
  * allocation.  Every argument error (null pointers, non-positive sizes, k > 32768, both strides != 1, negative strides,
- * bad scales, a pixel axis that does not match) is I8IE_ERR_ARG before any device call.
+ * a result batch_stride of 0 with b > 1, bad scales, a pixel axis that does not match) is I8IE_ERR_ARG before any device call.
  * Two kernels with identical bytes (csrc/i8ie_matmul.hip): bmm_mfma, and bmm_direct for k < 16,
  * for a, b or out not 16-byte aligned, for strides beyond 2^31 and for everything under I8IE_OPT_FORCE_FALLBACK. */
 typedef struct i8ie_bmm_mat {
@@ -750,7 +760,7 @@ typedef struct i8ie_bmm_args {
   int32_t* acc_dbg_dev;   /* NULL or [b, m, n] */
 } i8ie_bmm_args;
 int i8ie_bmm_u8(i8ie_ctx* ctx, const i8ie_bmm_args* args);
-/* FP32 (before convert(), and while calibrating): the same descriptor with float elements (s8, the pixel axis, the
+/* FP32 (before convert(), and while calibrating): the same descriptor and stride contract with float elements (s8, the pixel axis, the
  * scales, relu and acc_dbg_dev are ignored and must be 0 / NULL); out[i,j] = sum over k in ascending order of
  * a[i,k] * b[k,j], fp32 products added in fp32 to a sum that starts at 0, one rounding per operation, no contraction. */
 int i8ie_bmm_f32(i8ie_ctx* ctx, const i8ie_bmm_args* args);

@@ -201,6 +201,7 @@ int i8ie_bmm_u8(i8ie_ctx* ctx, const i8ie_bmm_args* g) {
   I8IE_REQUIRE(g->b > 0 && g->m > 0 && g->n > 0 && g->k > 0, "non-positive size");
   I8IE_REQUIRE(g->k <= kMaxK, "k > 32768: the int32 sum could overflow");
   I8IE_REQUIRE(mat_ok(g->a) && mat_ok(g->bm) && mat_ok(g->out), "null pointer, negative stride, or neither stride of a matrix is 1");
+  I8IE_REQUIRE(g->b == 1 || g->out.batch_stride > 0, "the result's batch_stride is 0: its batch items would share their bytes");
   I8IE_REQUIRE(scales_ok(g->s_a, g->s_b, g->s_out), "scales must be finite and s_out > 0");
   I8IE_REQUIRE(g->out_pix_axis >= 0 && g->out_pix_axis <= 2, "out_pix_axis must be 0, 1 or 2");
   I8IE_REQUIRE((int64_t)g->b * g->m * g->n <= 0x7FFFFFFFFFFFll / 4, "too many outputs");
@@ -264,6 +265,7 @@ int i8ie_bmm_f32(i8ie_ctx* ctx, const i8ie_bmm_args* g) {
   I8IE_REQUIRE(ctx && g, "null argument");
   I8IE_REQUIRE(g->b > 0 && g->m > 0 && g->n > 0 && g->k > 0, "non-positive size");
   I8IE_REQUIRE(mat_ok(g->a) && mat_ok(g->bm) && mat_ok(g->out), "null pointer, negative stride, or neither stride of a matrix is 1");
+  I8IE_REQUIRE(g->b == 1 || g->out.batch_stride > 0, "the result's batch_stride is 0: its batch items would share their bytes");
   I8IE_REQUIRE(g->out_pix_axis == 0 && g->acc_dbg_dev == nullptr && !g->a.s8 && !g->bm.s8 && !g->out.s8, "an INT8-only field is set");
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   BmmF32Params p;

@@ -16,11 +16,12 @@ import numpy as np
 #                  | ("deconv", in_c, out_c, k, stride, pad, output_pad)   i8ie.ConvTranspose2d, weight [in_c, out_c, k, k]
 #                  | ("ln", channels)     i8ie.LayerNorm: float32 gamma / beta, no INT8 weights, no MACs
 #                  | ("gn", groups, channels)   i8ie.GroupNorm: every rule of "ln"}
-#   spec  : [("layer", attr) | ("relu",) | ("pool", k, s) | ("flatten", features)
+#   spec  : [("layer", attr) | ("relu",) | ("flatten", features)
+#            | ("pool", k, s[, pad[, ceil_mode]])   i8ie.max_pool2d(x, k, s, pad, ceil_mode)
 #            | ("save", tag)              remember the current tensor under `tag`
 #            | ("add", attr, tag)         x = getattr(net, attr)(x, saved[tag]); attr names an i8ie.Add (not in `layers`)
 #            | ("branch", tag, [ops...])  run ops on saved[tag] and store the result back under `tag` (projection shortcut)
-#            | ("avgpool", k, s)          i8ie.avg_pool2d(x, k, s)
+#            | ("avgpool", k, s[, pad[, ceil_mode[, count_include_pad]]])   i8ie.avg_pool2d(x, k, s, pad, ceil_mode, count_include_pad)
 #            | ("gap",)                   i8ie.global_avg_pool2d(x)
 #            | ("concat", attr, [tags])   x = getattr(net, attr)([x] + [saved[t] for t in tags]); attr names an i8ie.Concat
 #            | ("act", attr, kind[, param])  x = getattr(net, attr)(x); attr names an i8ie.Activation(kind, param)
@@ -724,6 +725,13 @@ def conv_dilation(L):
     return L[7] if len(L) > 7 else 1
 
 
+def pool_out_size(size, k, s, pad=0, ceil_mode=False):
+    """output size of one axis of a ("pool", ...) / ("avgpool", ...) op: the rule of i8ie_pool_output_size (a ceil-mode window
+    that would start beyond the input and its padding is dropped)"""
+    o = (size + 2 * pad - k + (s - 1 if ceil_mode else 0)) // s + 1
+    return o - 1 if ceil_mode and (o - 1) * s >= size + pad else o
+
+
 def upsample_factors(factor):
     """(fh, fw) of an ("upsample", factor, mode) op: factor is an int or a pair"""
     return tuple(factor) if isinstance(factor, (tuple, list)) else (factor, factor)
@@ -767,7 +775,7 @@ def _macs(layers, ops, hw, saved, branch_convs, in_branch=False):
                 total += L[1] * L[2]
             # ("ln", c), ("gn", groups, c): no MACs, the same map
         elif op[0] in ("pool", "avgpool"):
-            h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
+            h, w = pool_out_size(h, *op[1:5]), pool_out_size(w, *op[1:5])
         elif op[0] == "gap":
             h, w = 1, 1
         elif op[0] == "upsample":
@@ -876,9 +884,9 @@ def build(name):
                 elif op[0] == "relu":
                     x = i8ie.relu(x)
                 elif op[0] == "pool":
-                    x = i8ie.max_pool2d(x, op[1], op[2])
+                    x = i8ie.max_pool2d(x, *op[1:])
                 elif op[0] == "avgpool":
-                    x = i8ie.avg_pool2d(x, op[1], op[2])
+                    x = i8ie.avg_pool2d(x, *op[1:])
                 elif op[0] == "gap":
                     x = i8ie.global_avg_pool2d(x)
                 elif op[0] == "save":

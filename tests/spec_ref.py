@@ -3,7 +3,8 @@
 
 Nothing is defined arithmetically here.  Every op is the function of its own module -- the reference's ops in oracle/orc.py,
 per-channel requantisation in pc_pipeline, and grouped_ref, add_ref, avgpool_ref, concat_ref, act_ref, mul_ref, deconv_ref,
-upsample_ref, dilated_ref, attention_ref, layernorm_ref, mha_ref, groupnorm_ref for what the reference does not have -- and
+upsample_ref, dilated_ref, attention_ref, layernorm_ref, mha_ref, groupnorm_ref, padpool_ref for what the reference does not
+have -- and
 this module only walks the spec with (bytes, scale, zero_point) in hand.  A new op adds one branch to forward(), one to
 fp32_qparams() if it is calibrated, its name to OPS, and its arithmetic in a module of its own.
 
@@ -30,6 +31,7 @@ import layernorm_ref as lnr
 import mha_ref as mhr
 import mul_ref as mr
 import orc
+import padpool_ref as ppr
 import pc_pipeline as pcp
 import pipeline
 import upsample_ref as ur
@@ -96,10 +98,10 @@ def forward(networks_entry, x, qlayers, out_qparams, join_qparams=None, per_chan
                 cur = (_layer(layers[op[1]], cur, qlayers[op[1]], s_out, zp_out, per_channel), s_out, zp_out)
             elif name == "relu":
                 cur = (orc.relu(q, zp), s, zp)
-            elif name == "pool":
-                cur = (orc.max_pool2d(q, op[1], op[2]), s, zp)
-            elif name == "avgpool":
-                cur = (apr.avg_pool2d_u8(q, op[1], op[1], op[2]), s, zp)
+            elif name == "pool":  # (a tail -- pad, ceil_mode -- takes padpool_ref's definition; without one, the reference's)
+                cur = (ppr.max_pool2d_u8(q, *op[1:]) if len(op) > 3 else orc.max_pool2d(q, op[1], op[2]), s, zp)
+            elif name == "avgpool":  # (a padded tap is the byte zp)
+                cur = (ppr.avg_pool2d_u8(q, *op[1:], zp=zp) if len(op) > 3 else apr.avg_pool2d_u8(q, op[1], op[1], op[2]), s, zp)
             elif name == "gap":
                 cur = (apr.global_avg_pool2d_u8(q), s, zp)
             elif name == "upsample":
@@ -170,8 +172,8 @@ def traces(*callbacks):
 def fp32_qparams(networks_entry, state_dict, x):
     """Stand-in for calibration without a GPU: a numpy forward in float64 over the FP32 weights; the output range of every
     layer, Add, Mul, Concat, Activation, MatMul and Attention gives its (scale, zero_point) by the calibrator's rule, and so does
-    the score range of an Attention, kept beside the joins under attr + mha_ref.SCORES.  No registry network needs avgpool or
-    upsample here; they raise like any other op.  Returns (layer qparams, join qparams)."""
+    the score range of an Attention, kept beside the joins under attr + mha_ref.SCORES.  Pools and upsamples are the float64
+    functions of f64_ref, avgpool_ref, padpool_ref and upsample_ref.  Returns (layer qparams, join qparams)."""
     layers, spec, _ = networks_entry
     qp, jqp = {}, {}
 
@@ -198,7 +200,12 @@ def fp32_qparams(networks_entry, state_dict, x):
             elif name == "relu":
                 v = np.maximum(v, 0.0)
             elif name == "pool":
-                v = f64_ref.max_pool2d(v, op[1], op[2])
+                v = ppr.max_pool2d_f64(v, *op[1:]) if len(op) > 3 else f64_ref.max_pool2d(v, op[1], op[2])
+            elif name == "avgpool":
+                v = (ppr.avg_pool2d_f64(v, *op[1:]) if len(op) > 3 else apr.avg_pool2d_f64(v, op[1], op[1], op[2]))[0]
+            elif name == "upsample":
+                fh, fw = ur.factors(op[1])
+                v = ur.bilinear_f64(v, fh, fw)[0] if op[2] == "bilinear" else ur.nearest(v, fh, fw)
             elif name == "save":
                 saved[op[1]] = v
             elif name == "branch":

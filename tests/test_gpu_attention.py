@@ -25,11 +25,37 @@ QP = (f32(0.02), f32(0.03), f32(0.21), 117)   # s_a, s_b, s_out, zp_out: spreads
 ctx = support.ctx_fixture(ar)
 
 
+SENTINEL = 0xA5   # the bytes between the rows and the batch items of a pitched matrix
+
+
+def _pitched(phys, pitch=None):
+    """phys [b, R, C] (C the contiguous axis) inside a larger allocation.  pitch: (row pitch, batch pitch), None for the
+    compact value of either; batch pitch 0 keeps one matrix, which every batch item reads (phys must repeat it).
+    Returns (flat bytes with SENTINEL in every gap, the index of phys[i, r, c] in it, row pitch, batch pitch)."""
+    b, R, C = phys.shape
+    rp, bp = pitch or (None, None)
+    rp = C if rp is None else rp
+    bp = R * rp if bp is None else bp
+    assert rp >= C and (bp == 0 or bp >= (R - 1) * rp + C)
+    nb = b if bp else 1
+    assert bp or (phys == phys[:1]).all()
+    idx = np.arange(nb)[:, None, None] * bp + np.arange(R)[None, :, None] * rp + np.arange(C)[None, None, :]
+    flat = np.full((nb - 1) * bp + (R - 1) * rp + C, SENTINEL, np.uint8)
+    flat[idx] = phys[:nb]
+    return flat, idx, rp, bp
+
+
+def _mat(ptr, rp, bp, transposed, s8, offset=0):
+    """the descriptor of a pitched matrix: the logical rows are the physical ones, or with `transposed` the physical columns"""
+    return ar.BmmMat(ptr + offset, bp, 1 if transposed else rp, rp if transposed else 1, 1 if s8 else 0)
+
+
 def _bmm(ctx, A, zp_a, B, zp_b, ta=False, tb=False, relu=False, a_s8=False, b_s8=False, o_s8=False, qp=QP, fallback=False,
-         offsets=(0, 0, 0), out_t=False):
+         offsets=(0, 0, 0), out_t=False, pitch_a=None, pitch_b=None, pitch_o=None):
     """A [b, m, k], B [b, k, n] logical.  The operands are laid out as asked (transposed, re-biased, at a byte offset inside
-    their allocation), the result and the accumulators land in guarded regions.  Returns (out [b, m, n] plain bytes,
-    acc [b, m, n], kernel names)."""
+    their allocation, with a row pitch and a batch pitch -- _pitched), the result and the accumulators land in guarded
+    regions; the gaps of a pitched result are asserted untouched.  Returns (out [b, m, n] plain bytes, acc [b, m, n], kernel
+    names)."""
     bb, m, k = A.shape
     n = B.shape[2]
     s_a, s_b, s_out, zp_out = qp
@@ -38,12 +64,17 @@ def _bmm(ctx, A, zp_a, B, zp_b, ta=False, tb=False, relu=False, a_s8=False, b_s8
     pa = pa ^ np.uint8(0x80) if a_s8 else pa
     pb = pb ^ np.uint8(0x80) if b_s8 else pb
     oa, ob, oo = offsets
-    da = ctx.put(np.concatenate([np.zeros(oa, np.uint8), pa.ravel()]))
-    db = ctx.put(np.concatenate([np.zeros(ob, np.uint8), pb.ravel()]))
-    do = abi.GuardedU8(ctx, (bb * m * n + oo,))
+    (fa, _, rpa, bpa), (fb, _, rpb, bpb) = _pitched(pa, pitch_a), _pitched(pb, pitch_b)
+    fo, io, rpo, bpo = _pitched(np.zeros((bb, n, m) if out_t else (bb, m, n), np.uint8), pitch_o)
+    fo[:] = SENTINEL
+    da = ctx.put(np.concatenate([np.zeros(oa, np.uint8), fa]))
+    db = ctx.put(np.concatenate([np.zeros(ob, np.uint8), fb]))
+    do = abi.GuardedU8(ctx, (fo.size + oo,))
+    before = np.concatenate([np.full(oo, SENTINEL, np.uint8), fo])
+    abi.ck(abi.lib().i8ie_memcpy_h2d(ctx.h, do.ptr, before.ctypes.data_as(C.c_void_p), C.c_size_t(before.nbytes)))
     dacc = abi.GuardedU8(ctx, (bb, m, n), np.int32)
-    g = ar.BmmArgs(b=bb, m=m, n=n, k=k, a=ar.mat(da.ptr.value, m, k, ta, a_s8, oa), bm=ar.mat(db.ptr.value, k, n, tb, b_s8, ob),
-                   out=ar.mat(do.ptr.value, m, n, out_t, o_s8, oo), s_a=s_a, s_b=s_b, s_out=s_out, zp_a=zp_a, zp_b=zp_b,
+    g = ar.BmmArgs(b=bb, m=m, n=n, k=k, a=_mat(da.ptr.value, rpa, bpa, ta, a_s8, oa), bm=_mat(db.ptr.value, rpb, bpb, tb, b_s8, ob),
+                   out=_mat(do.ptr.value, rpo, bpo, out_t, o_s8, oo), s_a=s_a, s_b=s_b, s_out=s_out, zp_a=zp_a, zp_b=zp_b,
                    zp_out=zp_out, relu=1 if relu else 0, acc_dbg_dev=dacc.ptr.value)
     ctx.set_force_fallback(fallback)
     try:
@@ -51,8 +82,11 @@ def _bmm(ctx, A, zp_a, B, zp_b, ta=False, tb=False, relu=False, a_s8=False, b_s8
             abi.ck(abi.lib().i8ie_bmm_u8(ctx.h, C.byref(g)))
     finally:
         ctx.set_force_fallback(False)
-    raw = do.get()[oo:]
-    out = raw.reshape(bb, n, m).transpose(0, 2, 1) if out_t else raw.reshape(bb, m, n)
+    raw = do.get().ravel()
+    written = np.zeros(raw.size, bool)
+    written[io.ravel() + oo] = True
+    assert (raw[~written] == SENTINEL).all(), "a byte between the result's rows or batch items was written"
+    out = raw[io + oo].transpose(0, 2, 1) if out_t else raw[io + oo]
     out = out ^ np.uint8(0x80) if o_s8 else out
     acc = dacc.get()
     assert do.guards_ok() and dacc.guards_ok()
@@ -124,6 +158,62 @@ def test_matmul_unaligned_pointers_take_the_direct_kernel(ctx):
     _check(ctx, A, 3, B, 200, kernel="bmm_mfma")
     for offsets in ((1, 0, 0), (0, 4, 0), (0, 0, 8), (3, 5, 7)):
         _check(ctx, A, 3, B, 200, kernel="bmm_direct", offsets=offsets, relu=True)
+
+
+def _up16(v):
+    return (v + 15) // 16 * 16
+
+
+def _pitches(R, Cn):
+    """the pitch cases of a physical [R, Cn] operand: a) row pitch = extent + 16, batch pitch a multiple of 16; A) the same
+    with the extent rounded up to 16 first, so that both pitches are multiples of 16 at every extent (the 16-byte loads of a
+    K-contiguous operand under a real pitch); b) both multiples of 16 but for 4 more bytes per batch item (op_vec must drop
+    to the 4-byte loads); c) row pitch = extent + 4; C) a multiple of 4 above it (4-byte loads at every extent, the K-strided
+    operand's widest); d) row pitch = extent + 1 (byte loads)"""
+    up4 = (Cn + 3) // 4 * 4
+    return {"a": (Cn + 16, _up16(R * (Cn + 16)) + 16), "A": (_up16(Cn) + 16, _up16(R * (_up16(Cn) + 16)) + 16),
+            "b": (_up16(Cn) + 16, _up16(R * (_up16(Cn) + 16)) + 4), "c": (Cn + 4, None), "C": (up4 + 4, R * (up4 + 4) + 4),
+            "d": (Cn + 1, None)}
+
+
+@pytest.mark.parametrize("ta,tb", FORMS, ids=["nn", "tn", "nt", "tt"])
+def test_matmul_strided_and_broadcast_operands(ctx, ta, tb):
+    """each operand, K-contiguous or K-strided by the transpose form, inside a larger allocation under the six pitch cases of
+    _pitches, as a broadcast (batch_stride == 0 on A, on B, on both), and the result under a row pitch of n + 4 and n + 3
+    (dword and byte stores): accumulators, bytes and the untouched gaps, in bmm_mfma and again in bmm_direct.  k = 20, 36
+    and 68 are multiples of 4 and not of 16: the 4-byte arm of stage_tile with a K tail."""
+    rng = np.random.default_rng(21 + 2 * ta + tb)
+    bb = 3
+    for i, (m, n, k) in enumerate(itertools.product([17, 65], [17, 65], [20, 36, 64, 68, 130])):
+        A = rng.integers(0, 256, (bb, m, k), dtype=np.uint8)
+        B = rng.integers(0, 256, (bb, k, n), dtype=np.uint8)
+        A1, B1 = np.repeat(A[:1], bb, axis=0), np.repeat(B[:1], bb, axis=0)
+        pa, pb = _pitches(*((k, m) if ta else (m, k))), _pitches(*((n, k) if tb else (k, n)))
+        runs = [(A, B, {"pitch_a": pa[c]}) for c in "aAbcCd"] + [(A, B, {"pitch_b": pb[c]}) for c in "aAbcCd"]
+        runs += [(A, B, {"pitch_a": pa["c"], "pitch_b": pb["a"], "pitch_o": (n + 4, None)}), (A, B, {"pitch_o": (n + 3, None)}),
+                 (A, B, {"pitch_o": (m + 4, _up16(n * (m + 4)) + 4), "out_t": True})]
+        runs += [(A1, B, {"pitch_a": (None, 0)}), (A, B1, {"pitch_b": (None, 0)}), (A1, B1, {"pitch_a": (None, 0), "pitch_b": (None, 0)}),
+                 (A1, B, {"pitch_a": (pa["d"][0], 0), "pitch_b": pb["b"]})]
+        for j, (a, b_, kw) in enumerate(runs):
+            flags = dict(a_s8=bool((i + j) & 1), b_s8=bool((i + j) & 2), o_s8=bool((i + j) & 4), relu=bool((i + j) & 8))
+            for fallback in (False, True):
+                _check(ctx, a, (120, 128, 131, 3, 250)[j % 5], b_, (131, 117, 128, 250)[i % 4], kernel="bmm_direct" if fallback else "bmm_mfma", ta=ta,
+                       tb=tb, fallback=fallback, **flags, **kw)
+
+
+def test_matmul_refuses_a_broadcast_result(ctx):
+    """batch_stride == 0 on the result with b > 1: the batch items would share their bytes (include/i8ie_hip.h)"""
+    buf = ctx.put(np.zeros(4096, np.uint8))
+    p = buf.ptr.value
+    g = ar.BmmArgs(b=2, m=4, n=4, k=16, a=ar.mat(p, 4, 16), bm=ar.mat(p, 16, 4), out=ar.BmmMat(p + 2048, 0, 4, 1, 0), s_a=1.0,
+                   s_b=1.0, s_out=1.0)
+    with ctx.launch_map() as names:
+        assert abi.lib().i8ie_bmm_u8(ctx.h, C.byref(g)) == -1
+        assert abi.lib().i8ie_bmm_f32(ctx.h, C.byref(g)) == -1
+        g.b = 1
+        abi.ck(abi.lib().i8ie_bmm_u8(ctx.h, C.byref(g)))
+    assert names == {"bmm_mfma": 1}
+    buf.free()
 
 
 @pytest.mark.parametrize("fallback", [False, True], ids=["mfma", "forced_direct"])
@@ -267,6 +357,36 @@ def test_bmm_f32_against_float64(ctx, ta, tb):
         assert (err <= bound).all(), (bb, m, n, k, float((err / np.maximum(bound, 1e-300)).max()))
         for d in (da, db, do):
             d.free()
+
+
+@pytest.mark.parametrize("case", ["pitched", "broadcast"])
+def test_bmm_f32_pitched_and_broadcast_against_float64(ctx, case):
+    """i8ie_bmm_f32 under the stride contract of the u8 entry: every matrix under a row and a batch pitch (A given [b, k, m]),
+    or A as one matrix against the batch; the gaps of the result stay as they were"""
+    rng = np.random.default_rng(61)
+    bb, m, n, k = 3, 17, 33, 65
+    A = rng.normal(0, 1.5, (1 if case == "broadcast" else bb, m, k)).astype(f32)
+    B = rng.normal(0.2, 1.0, (bb, k, n)).astype(f32)
+    (rpa, bpa), (rpb, bpb), (rpo, bpo) = ((m + 3, k * (m + 3) + 5), (n + 1, k * (n + 1) + 2), (n + 2, m * (n + 2) + 7)) \
+        if case == "pitched" else ((k, 0), (n, k * n), (n, m * n))
+    pa = np.ascontiguousarray(A.transpose(0, 2, 1)) if case == "pitched" else A
+    ia = np.arange(pa.shape[0])[:, None, None] * bpa + np.arange(pa.shape[1])[None, :, None] * rpa + np.arange(pa.shape[2])
+    fa, fb = np.full(int(ia.max()) + 1, np.nan, f32), np.full(bb * bpb, np.nan, f32)
+    ib = np.arange(bb)[:, None, None] * bpb + np.arange(k)[None, :, None] * rpb + np.arange(n)
+    io = np.arange(bb)[:, None, None] * bpo + np.arange(m)[None, :, None] * rpo + np.arange(n)
+    fa[ia], fb[ib] = pa, B
+    da, db, do = ctx.put(fa), ctx.put(fb), ctx.guarded((bb * bpo,))
+    a_mat = ar.BmmMat(da.ptr.value, bpa, 1, rpa, 0) if case == "pitched" else ar.BmmMat(da.ptr.value, 0, rpa, 1, 0)
+    g = ar.BmmArgs(b=bb, m=m, n=n, k=k, a=a_mat, bm=ar.BmmMat(db.ptr.value, bpb, rpb, 1, 0), out=ar.BmmMat(do.ptr.value, bpo, rpo, 1, 0))
+    abi.ck(abi.lib().i8ie_bmm_f32(ctx.h, C.byref(g)))
+    raw, ok = do.read()
+    got = raw[io]
+    want, mag = ar.matmul(np.repeat(A, bb // A.shape[0], axis=0), B)
+    assert ok and abi.GuardedOut.unwritten(got) == 0 and abi.GuardedOut.unwritten(raw) == raw.size - got.size
+    err, bound = np.abs(got.astype(np.float64) - want), f64_ref.dot_bound(mag, k)
+    assert (err <= bound).all(), (case, float((err / np.maximum(bound, 1e-300)).max()))
+    for d in (da, db, do):
+        d.free()
 
 
 @pytest.mark.parametrize("L", [1, 2, 17, 64, 257, 1027])
