@@ -245,6 +245,12 @@ int i8ie_conv2d_f32_grouped(i8ie_ctx* ctx, const float* in_dev, int n, int c, in
 int i8ie_conv2d_f32_dilated(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int w,
                             const float* w_dev, const float* b_dev, int kc, int kh, int kw, int stride,
                             int pad, int groups, int dilation, float* out_dev);
+/* i8ie_conv2d_f32_dilated with the geometry per axis (see i8ie_conv2d_create_rect): the same FP32 implicit-GEMM kernel, the
+ * per-axis geometry only in its gather table and window origin.  With equal pairs it is i8ie_conv2d_f32_dilated bit for bit.
+ * A bad geometry is I8IE_ERR_ARG before any device call. */
+struct i8ie_conv_geom;
+int i8ie_conv2d_f32_rect(i8ie_ctx* ctx, const float* in_dev, int n, int c, int h, int w, const float* w_dev,
+                         const float* b_dev, int kc, int groups, const struct i8ie_conv_geom* geom, float* out_dev);
 /* ConvTranspose2d in FP32 (not in the reference; the definition of torch.nn.ConvTranspose2d with groups = 1,
  * dilation = 1, a square kernel): out[n, oc, iy*s - p + ky, ix*s - p + kx] += in[n, ic, iy, ix] * w[ic, oc, ky, kx], + b[oc].
  * w_dev is [c, kc, k, k], out_dev [n, kc, oh, ow] with oh = (h - 1)*stride - 2*pad + k + output_pad.  stride >= 1,
@@ -323,6 +329,14 @@ int i8ie_conv2d_u8s8_dilated(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c,
                              uint8_t zp_in, const int32_t* oc_dev, float s_in, float s_w, float s_out,
                              uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
 
+/* i8ie_conv2d_u8s8_dilated with the geometry per axis (see i8ie_conv2d_create_rect; not in the reference): qw
+ * [kc, (c/groups)*kh*kw] and oc [kc] are those of the compact kernel.  out NCHW [n, kc, oh, ow], acc_dbg_dev NULL or int32
+ * [n, oh*ow, kc].  A bad geometry is I8IE_ERR_ARG before any device call.  Equal pairs are i8ie_conv2d_u8s8_dilated itself;
+ * otherwise it reads the weights back and packs them for this one call. */
+int i8ie_conv2d_u8s8_rect(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w, const int8_t* qw_dev, int kc,
+                          int groups, const i8ie_conv_geom* geom, uint8_t zp_in, const int32_t* oc_dev, float s_in,
+                          float s_w, float s_out, uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
+
 /* ConvTranspose2d in INT8: Conv2d::forward_prop(Tensor<u8>&&), src/conv2d.cc:100-142, of the equivalent problem (see
  * i8ie_conv_transpose2d_create below); the layer itself: not in the reference.  qw_dev is the equivalent matrix
  * [kc, c*k*k], oc_dev [kc] from i8ie_conv_offsets on that matrix (K = c*k*k, src/conv2d.cc:117-124).  out_dev is NCHW
@@ -391,8 +405,42 @@ int i8ie_conv2d_create_dilated(i8ie_ctx* ctx, const int8_t* qw_host, const int8_
 int i8ie_conv2d_create_dilated_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc,
                                            int c, int kh, int kw, int stride, int pad, int groups, int dilation,
                                            const float* s_w_host, i8ie_layer** out);
-/* *dilation = the number the layer was created with: 1 for Linear, for ConvTranspose2d and for every other create entry */
+/* *dilation = the number the layer was created with: 1 for Linear, for ConvTranspose2d and for every other create entry.
+ * A handle made by i8ie_conv2d_create_rect with dilation_h != dilation_w has no one number: I8IE_ERR_ARG, and the error text
+ * names i8ie_layer_geometry. */
 int i8ie_layer_dilation(const i8ie_layer* layer, int* dilation);
+/* Rectangular / anisotropic Conv2d: torch.nn.Conv2d with pairs for kernel_size, stride, padding and dilation; not in the
+ * reference.  The geometry is eight integers: tap (ky, kx) of output pixel (oy, ox) reads input pixel
+ *   (oy*stride_h - pad_h + ky*dilation_h, ox*stride_w - pad_w + kx*dilation_w),
+ * a tap outside the image is zp_in, oh = (h + 2*pad_h - dilation_h*(kh-1) - 1)/stride_h + 1 and ow likewise on the w axis.
+ * Nothing new is defined arithmetically.  As for the dilated layer, the layer IS src/conv2d.cc:100-142 (per group) of a
+ * zero-embedded kernel: on the input padded explicitly with zp_in by (pad_h, pad_w), with the kernel W~ of side
+ * S = max(dilation_h*(kh-1), dilation_w*(kw-1)) + 1, W~[.., ky*dilation_h, kx*dilation_w] = W[.., ky, kx] (the dilated kernel
+ * embedded top-left in a square of zeros), at stride 1 and padding 0, then rows subsampled by stride_h and columns by
+ * stride_w.  (Where S exceeds the kernel's extent on an axis, the explicit padding continues by the difference below / to the
+ * right: positions that only the zeros of W~ meet.)  Zeros added to a kernel change neither the max-abs (per tensor or per output feature), nor the weight sums, nor
+ * the sequential fp32 offset sum (adding fl(zp_in * 0) = 0 to a float leaves it as it is), nor the bias join: so qw_host is
+ * the compact [kc][(c/groups)*kh*kw] matrix that convert() quantises, and the offset vector is src/conv2d.cc:117-124 on it.
+ * Rules per axis, those of the square entries on their one number: stride > 0, pad >= 0, dilation >= 1 at create time; the
+ * dilated kernel no larger than the padded input at forward time.  Each is I8IE_ERR_ARG before any device call.
+ * A geometry with all four pairs equal creates exactly what i8ie_conv2d_create_dilated(_per_channel) creates (same route, same
+ * kernels, same bytes).  Any other runs in lconv_mfma (csrc/i8ie_lconv.hip: whole lines of pixels resident in LDS) when it is
+ * dense, stride (1, 1), dilation (1, 1), 1 x k or k x 1 with k >= 2, c % 16 == 0, the buffers 16-byte aligned, the line's
+ * LDS plan inside the kernel's budget and I8IE_OPT_FORCE_FALLBACK off; and otherwise in the grouped kernels of
+ * csrc/i8ie_gconv.hip with the pairs in the tap offsets (gconv_mfma when (c/groups)*kh*kw >= 32, the buffers are aligned
+ * and the option is off, gconv_direct otherwise).  Such a handle answers the layout queries as a dilated handle does:
+ * i8ie_layer_padding 0, i8ie_layer_fuses_pool 0, i8ie_layer_accepts_f32_input 0, i8ie_layer_rebiased_io 0 / 0,
+ * i8ie_layer_preferred_layout as a grouped handle. */
+typedef struct i8ie_conv_geom {
+  int kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w;
+} i8ie_conv_geom;
+int i8ie_conv2d_create_rect(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int groups,
+                            const i8ie_conv_geom* geom, float s_w, i8ie_layer** out);
+int i8ie_conv2d_create_rect_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c,
+                                        int groups, const i8ie_conv_geom* geom, const float* s_w_host, i8ie_layer** out);
+/* the geometry of a conv handle (Conv2d of every create entry, ConvTranspose2d): square handles answer with equal pairs, the
+ * dilation pair being the number the layer was created with.  A Linear handle: I8IE_ERR_ARG. */
+int i8ie_layer_geometry(const i8ie_layer* layer, i8ie_conv_geom* geom);
 /* ConvTranspose2d (torch.nn.ConvTranspose2d with a square kernel, groups = 1, dilation = 1; not in the reference).
  * Nothing new is defined arithmetically: the layer IS src/conv2d.cc:100-142 (stride 1, padding 0) applied to
  *   x~  the input with stride - 1 positions inserted between neighbouring pixels, padded by k - 1 - pad on top / left and

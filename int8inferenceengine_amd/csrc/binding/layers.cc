@@ -51,15 +51,24 @@ class Linear : public BaseLayer {
 
 class Conv2d : public BaseLayer {
  public:
+  using Pair = std::pair<ssize_t, ssize_t>;
   // groups: not in the reference (src/conv2d.cc:100-142 per group); the weight is [out, in / groups, k, k]
   // dilation: not in the reference either (torch.nn.Conv2d's dilation=, one integer)
   Conv2d(ssize_t in_channel, ssize_t out_channel, ssize_t kernel_size, ssize_t stride, ssize_t padding, ssize_t groups = 1,
          ssize_t dilation = 1)
       : BaseLayer({out_channel, checked_cg(in_channel, out_channel, groups), kernel_size, kernel_size}, out_channel),
-        stride_(stride), padding_(padding), groups_(groups), dilation_(dilation), in_channels_(in_channel) {
-    if (dilation < 1) throw std::runtime_error("i8ie: Conv2d: dilation must be >= 1");
-    if (stride == 0) throw std::runtime_error("i8ie: Conv2d: stride must not be 0");  // include/conv2d.h:12-14
-    if (stride < 0 || padding < 0) throw std::runtime_error("i8ie: Conv2d: negative stride/padding");
+        stride_(stride), padding_(padding), groups_(groups), dilation_(dilation), in_channels_(in_channel),
+        stride_w_(stride), padding_w_(padding), dilation_w_(dilation) {
+    check_axis(stride, padding, dilation);
+  }
+  // pairs (h, w) for the four geometry arguments (_Conv2dRect): the weight is [out, in / groups, kh, kw]
+  Conv2d(ssize_t in_channel, ssize_t out_channel, Pair kernel_size, Pair stride, Pair padding, ssize_t groups, Pair dilation)
+      : BaseLayer({out_channel, checked_cg(in_channel, out_channel, groups), kernel_size.first, kernel_size.second}, out_channel),
+        stride_(stride.first), padding_(padding.first), groups_(groups), dilation_(dilation.first), in_channels_(in_channel),
+        stride_w_(stride.second), padding_w_(padding.second), dilation_w_(dilation.second) {
+    if (kernel_size.first < 1 || kernel_size.second < 1) throw std::runtime_error("i8ie: Conv2d: kernel_size must be >= 1");
+    check_axis(stride_, padding_, dilation_);
+    check_axis(stride_w_, padding_w_, dilation_w_);
   }
   // include/conv2d.h:16-17 leaves stride_/padding_ uninitialised for these two
   // constructors; they are 1 / 0 here.
@@ -68,20 +77,26 @@ class Conv2d : public BaseLayer {
   std::vector<ssize_t> out_shape(const std::vector<ssize_t>& s) const {
     if (s.size() != 4) throw std::runtime_error("i8ie: Conv2d expects an NCHW tensor");
     if (s[1] != in_channels()) throw std::runtime_error("i8ie: Conv2d: input channels do not match the weight");
-    const ssize_t kh = dilation_ * (wshape_[2] - 1) + 1, kw = dilation_ * (wshape_[3] - 1) + 1;  // the kernel's extent
-    if (s[2] - kh + 2 * padding_ < 0 || s[3] - kw + 2 * padding_ < 0)
-      throw std::runtime_error(dilation_ > 1 ? "i8ie: Conv2d: dilated kernel larger than the padded input"
-                                             : "i8ie: Conv2d: kernel larger than the padded input");
-    return {s[0], wshape_[0], (s[2] - kh + 2 * padding_) / stride_ + 1, (s[3] - kw + 2 * padding_) / stride_ + 1};
+    const ssize_t kh = dilation_ * (wshape_[2] - 1) + 1, kw = dilation_w_ * (wshape_[3] - 1) + 1;  // the kernel's extent
+    if (s[2] - kh + 2 * padding_ < 0 || s[3] - kw + 2 * padding_w_ < 0)
+      throw std::runtime_error((dilation_ > 1 || dilation_w_ > 1) ? "i8ie: Conv2d: dilated kernel larger than the padded input"
+                                                                  : "i8ie: Conv2d: kernel larger than the padded input");
+    return {s[0], wshape_[0], (s[2] - kh + 2 * padding_) / stride_ + 1, (s[3] - kw + 2 * padding_w_) / stride_w_ + 1};
   }
   Tensor<float> forward_f32(Tensor<float>& in) {  // src/conv2d.cc:63-98
     need_fp32();
     check_shapes();
     Tensor<float> out(out_shape(in.shape));
     upload_fp32();
-    check(i8ie_conv2d_f32_dilated(ctx(), in.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3],
-                                  w_dev_, b_dev_, (int)wshape_[0], (int)wshape_[2], (int)wshape_[3], (int)stride_,
-                                  (int)padding_, (int)groups_, (int)dilation_, out.dptr()));
+    if (square())
+      check(i8ie_conv2d_f32_dilated(ctx(), in.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3],
+                                    w_dev_, b_dev_, (int)wshape_[0], (int)wshape_[2], (int)wshape_[3], (int)stride_,
+                                    (int)padding_, (int)groups_, (int)dilation_, out.dptr()));
+    else {
+      const i8ie_conv_geom g = geom();
+      check(i8ie_conv2d_f32_rect(ctx(), in.dptr(), (int)in.shape[0], (int)in.shape[1], (int)in.shape[2], (int)in.shape[3], w_dev_,
+                                 b_dev_, (int)wshape_[0], (int)groups_, &g, out.dptr()));
+    }
     maybe_sample(out);
     return out;
   }
@@ -102,6 +117,17 @@ class Conv2d : public BaseLayer {
   }
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
+    if (!square()) {  // (equal pairs take the entries below: constructed exactly as a layer of ints is)
+      const i8ie_conv_geom g = geom();
+      if (per_channel_)
+        check(i8ie_conv2d_create_rect_per_channel(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
+                                                  reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)in_channels(),
+                                                  (int)groups_, &g, w_scales_.data(), &l));
+      else
+        check(i8ie_conv2d_create_rect(ctx(), reinterpret_cast<const int8_t*>(qw_.data()), reinterpret_cast<const int8_t*>(qb_.data()),
+                                      (int)n, (int)in_channels(), (int)groups_, &g, w_scale_, &l));
+      return l;
+    }
     if (per_channel_)
       check(i8ie_conv2d_create_dilated_per_channel(ctx(), reinterpret_cast<const int8_t*>(qw_.data()),
                                                    reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)in_channels(),
@@ -118,8 +144,29 @@ class Conv2d : public BaseLayer {
  public:
   ssize_t groups() const { return groups_; }
   ssize_t dilation() const { return dilation_; }
+  Pair dilation_pair() const { return {dilation_, dilation_w_}; }
+  py::dict geometry() const {
+    py::dict d;
+    d["kernel_size"] = py::make_tuple(wshape_[2], wshape_[3]);
+    d["stride"] = py::make_tuple(stride_, stride_w_);
+    d["padding"] = py::make_tuple(padding_, padding_w_);
+    d["dilation"] = py::make_tuple(dilation_, dilation_w_);
+    return d;
+  }
 
  private:
+  static void check_axis(ssize_t stride, ssize_t padding, ssize_t dilation) {
+    if (dilation < 1) throw std::runtime_error("i8ie: Conv2d: dilation must be >= 1");
+    if (stride == 0) throw std::runtime_error("i8ie: Conv2d: stride must not be 0");  // include/conv2d.h:12-14
+    if (stride < 0 || padding < 0) throw std::runtime_error("i8ie: Conv2d: negative stride/padding");
+  }
+  bool square() const {
+    return wshape_[2] == wshape_[3] && stride_ == stride_w_ && padding_ == padding_w_ && dilation_ == dilation_w_;
+  }
+  i8ie_conv_geom geom() const {
+    return i8ie_conv_geom{(int)wshape_[2], (int)wshape_[3], (int)stride_, (int)stride_w_, (int)padding_, (int)padding_w_,
+                          (int)dilation_, (int)dilation_w_};
+  }
   static ssize_t checked_cg(ssize_t in_channel, ssize_t out_channel, ssize_t groups) {
     if (groups < 1) throw std::runtime_error("i8ie: Conv2d: groups must be >= 1");
     if (in_channel % groups != 0 || out_channel % groups != 0)
@@ -132,6 +179,14 @@ class Conv2d : public BaseLayer {
   ssize_t groups_ = 1;
   ssize_t dilation_ = 1;
   ssize_t in_channels_ = 0;  // as constructed from sizes (0: constructed from arrays)
+  ssize_t stride_w_ = 1, padding_w_ = 0, dilation_w_ = 1;  // the w axis (stride_ / padding_ / dilation_: the h axis)
+};
+
+// Conv2d constructed from pairs (i8ie.Conv2d with a pair whose values differ): a class of its own, private to the package, so
+// that the extension's Conv2d keeps its recorded surface
+class Conv2dRect : public Conv2d {
+ public:
+  using Conv2d::Conv2d;
 };
 
 // ConvTranspose2d (additive, not in the reference): torch.nn.ConvTranspose2d with a square kernel, groups = 1, dilation = 1.
@@ -280,10 +335,25 @@ void bind_layers(py::module_& m) {
              py::arg("out_channels"), py::arg("kernel_size"), py::arg("stride") = 1, py::arg("padding") = 0,
              py::arg("groups") = 1, py::arg("dilation") = 1)
         .def("groups", &Conv2d::groups)
-        .def("dilation", &Conv2d::dilation);
+        .def("dilation", &Conv2d::dilation)
+        .def("_geometry", &Conv2d::geometry);  // (private: the class keeps its recorded public surface; i8ie.Layer.geometry() asks it)
     bind_layer_common(c);
   }
 
+  {
+    using Pair = Conv2d::Pair;
+    py::class_<Conv2dRect> c(m, "_Conv2dRect");
+    c.def(py::init<ssize_t, ssize_t, Pair, Pair, Pair, ssize_t, Pair>(), py::arg("in_channels"), py::arg("out_channels"),
+          py::arg("kernel_size"), py::arg("stride") = Pair(1, 1), py::arg("padding") = Pair(0, 0), py::arg("groups") = 1,
+          py::arg("dilation") = Pair(1, 1))
+        .def("groups", &Conv2dRect::groups)
+        .def("dilation", [](const Conv2dRect& l) -> py::object {
+          const Pair d = l.dilation_pair();
+          return d.first == d.second ? py::object(py::int_(d.first)) : py::object(py::make_tuple(d.first, d.second));
+        })
+        .def("geometry", &Conv2dRect::geometry);
+    bind_layer_common(c);
+  }
   {
     py::class_<ConvTranspose2d> c(m, "ConvTranspose2d");
     c.def(py::init<ssize_t, ssize_t, ssize_t, ssize_t, ssize_t, ssize_t>(), py::arg("in_channels"), py::arg("out_channels"),

@@ -37,15 +37,16 @@ struct F32Args {
   float* out;
   const int2* ktab;  // [K]: {input offset of K position k relative to the window origin, (kernel row << 16) | kernel column}
   int M, N, K;
-  int c, h, wd, oh, ow, stride, pad, P;  // P = oh * ow output pixels per image (1 for Linear)
+  int c, h, wd, oh, ow, stride, pad, P;  // P = oh * ow output pixels per image (1 for Linear); stride / pad: the h axis'
+  int stride_w, pad_w;                   // ... and the w axis' (equal unless i8ie_conv2d_f32_rect says otherwise)
   // grouped Conv2d (blockIdx.z = group): N, K, c above are one group's; these the whole tensors' channel counts
   int ctot, Ntot;
 };
 
-// dil: the dilation of a Conv2d (1 otherwise): kernel row l / column m read the window's pixel (l * dil, m * dil)
-__global__ __launch_bounds__(256) void k_table_kernel(int2* tab, int K, int h, int w, int kh, int kw, int dil) {
+// dil_h, dil_w: the dilation of a Conv2d (1 otherwise): kernel row l / column m read the window's pixel (l * dil_h, m * dil_w)
+__global__ __launch_bounds__(256) void k_table_kernel(int2* tab, int K, int h, int w, int kh, int kw, int dil_h, int dil_w) {
   for (int k = blockIdx.x * 256 + threadIdx.x; k < K; k += gridDim.x * 256) {
-    const int ch = k / (kh * kw), rem = k - ch * (kh * kw), l = rem / kw * dil, m = (rem % kw) * dil;
+    const int ch = k / (kh * kw), rem = k - ch * (kh * kw), l = rem / kw * dil_h, m = (rem % kw) * dil_w;
     tab[k] = make_int2((ch * h + l) * w + m, (l << 16) | m);
   }
 }
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(F32Args p) {
   const bool xrow_ok = xr < p.M;
   const int ximg = xr / p.P, xpix = xr - ximg * p.P;
   const int xoy = xpix / p.ow, xox = xpix - xoy * p.ow;
-  const int y0 = xoy * p.stride - p.pad, x0 = xox * p.stride - p.pad;
+  const int y0 = xoy * p.stride - p.pad, x0 = xox * p.stride_w - p.pad_w;
   const float* xbase = p.in + (((size_t)ximg * p.ctot + (size_t)grp * p.c) * p.h + y0) * (size_t)p.wd + x0;  // (may point before the image: only used with valid taps)
   // ---- this thread's weight elements: K position tid % 16, features tid / 16 + 16 e
   const int wk = tid & 15, wj0 = tid >> 4;
@@ -160,11 +161,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(F32Args p) {
 }
 
 template <bool CONV>
-int launch_gemm_f32(i8ie_ctx* ctx, F32Args a, int kh, int kw, const char* name, int groups = 1, int dil = 1) {
+int launch_gemm_f32(i8ie_ctx* ctx, F32Args a, int kh, int kw, const char* name, int groups = 1, int dil_h = 1, int dil_w = 1) {
   I8IE_REQUIRE((size_t)a.M * a.K < ((size_t)1 << 62) && a.K < (1 << 30), "f32 gemm: dimensions");
   I8IE_TRY(i8ie_ws_reserve(ctx, (size_t)a.K * sizeof(int2) + 256));
   int2* tab = reinterpret_cast<int2*>(ctx->ws);
-  k_table_kernel<<<(a.K + 255) / 256 < 64 ? (a.K + 255) / 256 : 64, 256, 0, ctx->stream>>>(tab, a.K, a.h, a.wd, kh, kw, dil);
+  k_table_kernel<<<(a.K + 255) / 256 < 64 ? (a.K + 255) / 256 : 64, 256, 0, ctx->stream>>>(tab, a.K, a.h, a.wd, kh, kw, dil_h, dil_w);
   I8IE_LAUNCH_CHECK();
   a.ktab = tab;
   const dim3 grid((unsigned)((a.N + FB - 1) / FB), (unsigned)((a.M + FB - 1) / FB), (unsigned)groups);
@@ -210,6 +211,19 @@ inline int cap_grid(int64_t items) {
   return (int)(b > 256 * 32 ? 256 * 32 : b);
 }
 
+// the launch of a checked Conv2d: what i8ie_conv2d_f32_dilated and i8ie_conv2d_f32_rect share behind their argument rules
+int conv2d_f32_run(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, const float* wt, const float* b, int kc, int groups,
+                   const i8ie_conv_geom& g, int oh, int ow, float* out) {
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  F32Args a{};
+  a.in = in; a.w = wt; a.b = b; a.out = out;
+  a.M = n * oh * ow; a.N = kc / groups; a.K = (c / groups) * g.kh * g.kw;
+  a.c = c / groups; a.h = h; a.wd = w; a.oh = oh; a.ow = ow; a.P = oh * ow;
+  a.stride = g.stride_h; a.stride_w = g.stride_w; a.pad = g.pad_h; a.pad_w = g.pad_w;
+  a.ctot = c; a.Ntot = kc;
+  return launch_gemm_f32<true>(ctx, a, g.kh, g.kw, "conv2d_f32_mfma", groups, g.dilation_h, g.dilation_w);
+}
+
 }  // namespace
 
 extern "C" {
@@ -222,7 +236,7 @@ int i8ie_linear_f32(i8ie_ctx* ctx, const float* in, int m, int k, const float* w
   F32Args a{};
   a.in = in; a.w = w; a.b = b; a.out = out;
   a.M = m; a.N = n; a.K = k;
-  a.c = k; a.h = 1; a.wd = 1; a.oh = 1; a.ow = 1; a.stride = 1; a.pad = 0; a.P = 1;
+  a.c = k; a.h = 1; a.wd = 1; a.oh = 1; a.ow = 1; a.stride = a.stride_w = 1; a.pad = a.pad_w = 0; a.P = 1;
   a.ctot = k; a.Ntot = n;
   return launch_gemm_f32<false>(ctx, a, 1, 1, "linear_f32_mfma");
 }
@@ -241,6 +255,7 @@ int i8ie_conv2d_f32_grouped(i8ie_ctx* ctx, const float* in, int n, int c, int h,
 // ... and with a dilation (not in the reference): the gather table carries it, the kernel is the same
 int i8ie_conv2d_f32_dilated(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, const float* wt, const float* b, int kc,
                             int kh, int kw, int stride, int pad, int groups, int dilation, float* out) {
+  // (this entry's own rules, in its order and under its name: the texts are what its callers have always seen)
   I8IE_REQUIRE(dilation >= 1, "dilation must be >= 1");
   I8IE_REQUIRE(groups >= 1 && groups <= 65535, "groups must be in [1, 65535]");
   I8IE_REQUIRE(c > 0 && kc > 0 && c % groups == 0 && kc % groups == 0, "groups must divide the input and the output channels");
@@ -252,13 +267,27 @@ int i8ie_conv2d_f32_dilated(i8ie_ctx* ctx, const float* in, int n, int c, int h,
   const int oh = (int)((h - eh + 2 * pad) / stride) + 1, ow = (int)((w - ew + 2 * pad) / stride) + 1;
   I8IE_REQUIRE((int64_t)n * oh * ow < ((int64_t)1 << 31) && eh < 65536 && ew < 65536, "conv2d_f32: too many output pixels");
   I8IE_REQUIRE(ctx && in && wt && b && out, "null argument");  // (behind the argument rules: they need no device)
-  I8IE_HIP_TRY(hipSetDevice(ctx->device));
-  F32Args a{};
-  a.in = in; a.w = wt; a.b = b; a.out = out;
-  a.M = n * oh * ow; a.N = kc / groups; a.K = (c / groups) * kh * kw;
-  a.c = c / groups; a.h = h; a.wd = w; a.oh = oh; a.ow = ow; a.stride = stride; a.pad = pad; a.P = oh * ow;
-  a.ctot = c; a.Ntot = kc;
-  return launch_gemm_f32<true>(ctx, a, kh, kw, "conv2d_f32_mfma", groups, dilation);
+  return conv2d_f32_run(ctx, in, n, c, h, w, wt, b, kc, groups, i8ie_conv_geom{kh, kw, stride, stride, pad, pad, dilation, dilation}, oh, ow, out);
+}
+
+// ... and with every geometry number per axis: still the gather table and the window origin alone
+int i8ie_conv2d_f32_rect(i8ie_ctx* ctx, const float* in, int n, int c, int h, int w, const float* wt, const float* b, int kc,
+                         int groups, const i8ie_conv_geom* geom, float* out) {
+  I8IE_REQUIRE(geom != nullptr, "null geometry");
+  const int kh = geom->kh, kw = geom->kw, dilation_h = geom->dilation_h, dilation_w = geom->dilation_w;
+  I8IE_REQUIRE(dilation_h >= 1 && dilation_w >= 1, "dilation must be >= 1");
+  I8IE_REQUIRE(groups >= 1 && groups <= 65535, "groups must be in [1, 65535]");
+  I8IE_REQUIRE(c > 0 && kc > 0 && c % groups == 0 && kc % groups == 0, "groups must divide the input and the output channels");
+  I8IE_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0 && kc > 0 && kh > 0 && kw > 0, "non-positive dimension");
+  I8IE_REQUIRE(geom->stride_h > 0 && geom->stride_w > 0 && geom->pad_h >= 0 && geom->pad_w >= 0, "bad stride/padding");
+  const int64_t eh = (int64_t)dilation_h * (kh - 1) + 1, ew = (int64_t)dilation_w * (kw - 1) + 1;  // the kernel's extent
+  I8IE_REQUIRE(h - eh + 2 * (int64_t)geom->pad_h >= 0 && w - ew + 2 * (int64_t)geom->pad_w >= 0,
+               (dilation_h > 1 || dilation_w > 1) ? "dilated kernel larger than padded input" : "kernel larger than padded input");
+  const int oh = (int)((h - eh + 2 * (int64_t)geom->pad_h) / geom->stride_h) + 1;
+  const int ow = (int)((w - ew + 2 * (int64_t)geom->pad_w) / geom->stride_w) + 1;
+  I8IE_REQUIRE((int64_t)n * oh * ow < ((int64_t)1 << 31) && eh < 65536 && ew < 65536, "conv2d_f32: too many output pixels");
+  I8IE_REQUIRE(ctx && in && wt && b && out, "null argument");  // (behind the argument rules: they need no device)
+  return conv2d_f32_run(ctx, in, n, c, h, w, wt, b, kc, groups, *geom, oh, ow, out);
 }
 
 // ConvTranspose2d in FP32 (not in the reference; torch.nn.functional.conv_transpose2d's definition): wt is [c][kc][k][k]

@@ -14,8 +14,10 @@ struct i8ie_ctx;
 struct I8ieGconvCall {
   const uint8_t* A;  // NHWC [m][H + 2 ib][W + 2 ib][C], border bytes = zp_in; taps beyond the border read as zp_in
   int m, H, W, C, ib;
-  int OH, OW, stride, pad, KH, KW;
-  int dil;            // dilation >= 1: tap (kh, kw) reads input pixel (oy * stride - pad + kh * dil, ox * stride - pad + kw * dil)
+  int OH, OW, KH, KW;
+  // per axis (DESIGN.md sections 8j, 8p): tap (ky, kx) reads input pixel (oy * stride_h - pad_h + ky * dil_h, ox * stride_w -
+  // pad_w + kx * dil_w); dil >= 1.  A square layer passes equal pairs.
+  int stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
   int groups, Cg, Ng, Ngp, Kgp;  // Ngp = Ng rounded up to 16, Kgp = Cg * KH * KW rounded up to 64
   const int8_t* Bp;   // [groups][Ngp][Kgp], K ordered (kh, kw, cg), zero padded
   const int* ktab;    // device, from i8ie_gconv_ktab

@@ -8,8 +8,9 @@
 //   gconv_mfma    a block owns (group, 128 output pixels, up to 64 features of the group); each wave multiplies 32 pixels by
 //                 the block's features on v_mfma_i32_16x16x64_i8, both operands read as fragments straight from global
 //                 memory (the weights of a group are a few hundred KiB at most: they stay in L2 / the vector cache)
-//   (both)        a dilation `dil` (Conv2d dilation=) multiplies a tap's pixel offset and nothing else: the
-//                 weights, the tap table and the K order are those of the undilated layer
+//   (both)        a dilation (Conv2d dilation=) multiplies a tap's pixel offset and nothing else: the
+//                 weights, the tap table and the K order are those of the undilated layer.  Stride, padding and dilation are
+//                 per axis (section 8p): a rectangular or anisotropic layer is the same walk with unequal pairs
 //   gconv_direct  no matrix instruction: a lane owns up to 4 features of one (pixel, group) and walks the taps
 //                 (v_dot4_i32_i8 where Cg % 4 == 0); depthwise, channel multipliers, tiny groups, and every grouped layer
 //                 while I8IE_OPT_FORCE_FALLBACK is on
@@ -25,7 +26,9 @@ namespace {
 struct GconvArgs {
   const uint8_t* A;  // [m][H + 2 ib][W + 2 ib][C]
   int H, W, C, ib;
-  int OH, OW, stride, pad, KH, KW, dil;  // dil: tap (kh, kw) reads the pixel (kh * dil, kw * dil) of the window
+  int OH, OW, KH, KW;
+  int sh, sw, ph, pw, dh, dw;  // stride, padding, dilation per axis: tap (kh, kw) reads the pixel (kh * dh, kw * dw) of the
+                               // window (DESIGN.md sections 8j, 8p)
   int Cg, Ng, Ngp, Kg, Kgp, kc;
   long long M;          // m * OH * OW output pixels
   const int8_t* Bp;     // [groups][Ngp][Kgp]
@@ -47,8 +50,8 @@ __device__ __forceinline__ Pixel locate(const GconvArgs& p, long long px, int g)
   const long long img = px / P;
   const int rem = (int)(px - img * P), oy = rem / p.OW, ox = rem - oy * p.OW;
   Pixel q;
-  q.y0 = oy * p.stride - p.pad;
-  q.x0 = ox * p.stride - p.pad;
+  q.y0 = oy * p.sh - p.ph;
+  q.x0 = ox * p.sw - p.pw;
   const int Hp = p.H + 2 * p.ib, Wp = p.W + 2 * p.ib;
   q.in_base = ((img * Hp + (q.y0 + p.ib)) * Wp + (q.x0 + p.ib)) * p.C + (long long)g * p.Cg;
   q.out_pix = (img * (p.OH + 2 * p.ob) + oy + p.ob) * (p.OW + 2 * p.ob) + ox + p.ob;
@@ -82,7 +85,7 @@ __device__ __forceinline__ v4i gather16(const GconvArgs& p, const Pixel& q, int 
   uint32_t d[4];
   if constexpr (G == 16) {
     const int2 t = p.ktab[kpos >> 4];
-    const int dy = (t.x >> 16) * p.dil, dx = (t.x & 0xffff) * p.dil;
+    const int dy = (t.x >> 16) * p.dh, dx = (t.x & 0xffff) * p.dw;
     v4i v = {(int)zp4, (int)zp4, (int)zp4, (int)zp4};
     if (tap_inside(p, q, dy, dx)) v = *reinterpret_cast<const v4i*>(p.A + q.in_base + (long long)(dy * Wp + dx) * p.C + t.y);
     return v;
@@ -90,7 +93,7 @@ __device__ __forceinline__ v4i gather16(const GconvArgs& p, const Pixel& q, int 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int2 t = p.ktab[(kpos >> 2) + i];
-      const int dy = (t.x >> 16) * p.dil, dx = (t.x & 0xffff) * p.dil;
+      const int dy = (t.x >> 16) * p.dh, dx = (t.x & 0xffff) * p.dw;
       d[i] = zp4;
       if (tap_inside(p, q, dy, dx)) d[i] = *reinterpret_cast<const uint32_t*>(p.A + q.in_base + (long long)(dy * Wp + dx) * p.C + t.y);
     }
@@ -101,7 +104,7 @@ __device__ __forceinline__ v4i gather16(const GconvArgs& p, const Pixel& q, int 
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
         const int2 t = p.ktab[kpos + 4 * i + b];
-        const int dy = (t.x >> 16) * p.dil, dx = (t.x & 0xffff) * p.dil;
+        const int dy = (t.x >> 16) * p.dh, dx = (t.x & 0xffff) * p.dw;
         uint32_t v = (uint32_t)p.zp_in;
         if (tap_inside(p, q, dy, dx)) v = p.A[q.in_base + (long long)(dy * Wp + dx) * p.C + t.y];
         d[i] |= v << (8 * b);
@@ -179,8 +182,8 @@ __global__ __launch_bounds__(256) void gconv_direct_kernel(GconvArgs p, int grou
     int c[4] = {0, 0, 0, 0};
     for (int dy = 0; dy < p.KH; ++dy)
       for (int dx = 0; dx < p.KW; ++dx) {
-        const bool in = tap_inside(p, q, dy * p.dil, dx * p.dil);
-        const uint8_t* a = p.A + q.in_base + (long long)(dy * Wp + dx) * p.dil * p.C;
+        const bool in = tap_inside(p, q, dy * p.dh, dx * p.dw);
+        const uint8_t* a = p.A + q.in_base + (long long)(dy * p.dh * Wp + dx * p.dw) * p.C;
         const int8_t* wt = w + (dy * p.KW + dx) * p.Cg;
         if constexpr (DOT4) {
           for (int cg = 0; cg < p.Cg; cg += 4) {
@@ -229,10 +232,12 @@ bool i8ie_gconv_mfma_takes(const i8ie_ctx* ctx, const I8ieGconvCall& c) {
 int i8ie_gconv_launch(i8ie_ctx* ctx, const I8ieGconvCall& c) {
   I8IE_REQUIRE(c.groups >= 1 && c.groups <= 65535, "grouped conv: at most 65535 groups");
   I8IE_REQUIRE(c.KH < 65536 && c.KW < 65536, "grouped conv: kernel size");
-  I8IE_REQUIRE(c.dil >= 1 && (long long)c.dil * (c.KH > c.KW ? c.KH : c.KW) < 65536, "grouped conv: dilation");
+  I8IE_REQUIRE(c.dil_h >= 1 && c.dil_w >= 1 && (long long)c.dil_h * c.KH < 65536 && (long long)c.dil_w * c.KW < 65536,
+               "grouped conv: dilation");
   GconvArgs a{};
   a.A = c.A; a.H = c.H; a.W = c.W; a.C = c.C; a.ib = c.ib;
-  a.OH = c.OH; a.OW = c.OW; a.stride = c.stride; a.pad = c.pad; a.KH = c.KH; a.KW = c.KW; a.dil = c.dil;
+  a.OH = c.OH; a.OW = c.OW; a.KH = c.KH; a.KW = c.KW;
+  a.sh = c.stride_h; a.sw = c.stride_w; a.ph = c.pad_h; a.pw = c.pad_w; a.dh = c.dil_h; a.dw = c.dil_w;
   a.Cg = c.Cg; a.Ng = c.Ng; a.Ngp = c.Ngp; a.Kg = c.Cg * c.KH * c.KW; a.Kgp = c.Kgp; a.kc = c.groups * c.Ng;
   a.M = (long long)c.m * c.OH * c.OW;
   a.Bp = c.Bp; a.ktab = reinterpret_cast<const int2*>(c.ktab);

@@ -12,31 +12,53 @@ inline bool force_fallback(const i8ie_ctx* ctx) { return (ctx->options & 1) != 0
 
 enum { PATH_F = 0, PATH_A = 1, PATH_B = 2, PATH_G = 3, PATH_T = 4 };  // PATH_G: grouped (i8ie_gconv.hip), PATH_T: transposed (i8ie_deconv.hip)
 
+// stride / pad: the h axis' numbers, which a square layer (every route but G) has on both axes; stride_w / pad_w / dil_h / dil_w:
+// the rest of the per-axis geometry, read by route G alone
 struct ConvGeom {
   int c, h, w, kc, kh, kw, stride, pad, oh, ow, K, Kpad;
+  int stride_w, pad_w, dil_h, dil_w;
 };
 
-// dil: the dilation: the kernel spans dil (k - 1) + 1 pixels; 1 = the reference's geometry
-inline int conv_geom(int c, int h, int w, int kc, int kh, int kw, int stride, int pad, ConvGeom* g, int dil = 1) {
+// The geometry of one forward from the eight integers of i8ie_conv_geom (`e`: the EFFECTIVE dilations, what the kernels walk;
+// DESIGN.md sections 8j, 8p): per axis the kernel spans dil (k - 1) + 1 pixels; 1 = the reference's geometry
+inline int conv_geom(int c, int h, int w, int kc, const i8ie_conv_geom& e, ConvGeom* g) {
+  // (the h axis' numbers under the names the square entries' error texts quote)
+  const int kh = e.kh, kw = e.kw, stride = e.stride_h, pad = e.pad_h, dil = e.dilation_h;
+  const int stride_w = e.stride_w, pad_w = e.pad_w, dil_w = e.dilation_w;
   I8IE_REQUIRE(c > 0 && h > 0 && w > 0 && kc > 0 && kh > 0 && kw > 0, "non-positive dimension");
   I8IE_REQUIRE(stride > 0, "stride must be positive");  // include/conv2d.h:12-14
+  I8IE_REQUIRE(stride_w > 0, "stride must be positive");
   I8IE_REQUIRE(pad >= 0, "negative padding");
+  I8IE_REQUIRE(pad_w >= 0, "negative padding");
   I8IE_REQUIRE(dil >= 1, "dilation must be >= 1");
-  const long long eh = (long long)dil * (kh - 1) + 1, ew = (long long)dil * (kw - 1) + 1;  // the kernel's extent
-  I8IE_REQUIRE(h - eh + 2 * pad >= 0 && w - ew + 2 * pad >= 0,
-               dil > 1 ? "dilated kernel larger than padded input" : "kernel larger than padded input");
+  I8IE_REQUIRE(dil_w >= 1, "dilation must be >= 1");
+  const long long eh = (long long)dil * (kh - 1) + 1, ew = (long long)dil_w * (kw - 1) + 1;  // the kernel's extent
+  const char* larger = (dil > 1 || dil_w > 1) ? "dilated kernel larger than padded input" : "kernel larger than padded input";
+  // I8IE_REQUIRE quotes its condition in the error text, and the text of a square layer is pinned (tests/golden/
+  // create_arg_rules.json) with the one `pad` on both axes: equal paddings answer with that wording, unequal ones with their own
+  if (pad == pad_w) {
+    I8IE_REQUIRE(h - eh + 2 * pad >= 0 && w - ew + 2 * pad >= 0, larger);
+  } else {
+    I8IE_REQUIRE(h - eh + 2 * pad >= 0 && w - ew + 2 * pad_w >= 0, larger);
+  }
   g->c = c; g->h = h; g->w = w; g->kc = kc; g->kh = kh; g->kw = kw; g->stride = stride; g->pad = pad;
+  g->stride_w = stride_w; g->pad_w = pad_w; g->dil_h = dil; g->dil_w = dil_w;
   g->oh = (int)((h - eh + 2 * pad) / stride) + 1;  // src/conv2d.cc:108-109
-  g->ow = (int)((w - ew + 2 * pad) / stride) + 1;
+  g->ow = (int)((w - ew + 2 * pad_w) / stride_w) + 1;
   g->K = c * kh * kw;
   g->Kpad = round_up(g->K, 128);
   return I8IE_OK;
+}
+// ... and from the one number per argument of the square entries
+inline int conv_geom(int c, int h, int w, int kc, int kh, int kw, int stride, int pad, ConvGeom* g, int dil = 1) {
+  return conv_geom(c, h, w, kc, i8ie_conv_geom{kh, kw, stride, stride, pad, pad, dil, dil}, g);
 }
 
 // ConvTranspose2d: kh = kw = k, OH = (H - 1) s - 2 p + k + output_padding (torch.nn.ConvTranspose2d)
 inline int deconv_geom(int c, int h, int w, int kc, int k, int stride, int pad, int opad, ConvGeom* g) {
   I8IE_REQUIRE(c > 0 && h > 0 && w > 0 && kc > 0 && k > 0, "non-positive dimension");
-  g->c = c; g->h = h; g->w = w; g->kc = kc; g->kh = k; g->kw = k; g->stride = stride; g->pad = pad;
+  g->c = c; g->h = h; g->w = w; g->kc = kc; g->kh = k; g->kw = k; g->stride = g->stride_w = stride; g->pad = g->pad_w = pad;
+  g->dil_h = g->dil_w = 1;
   const long long oh = (long long)(h - 1) * stride - 2 * pad + k + opad, ow = (long long)(w - 1) * stride - 2 * pad + k + opad;
   I8IE_REQUIRE(oh > 0 && ow > 0 && oh < (1 << 30) && ow < (1 << 30), "transposed conv: empty or oversized output");
   g->oh = (int)oh;
@@ -66,6 +88,10 @@ struct i8ie_layer {
   int path = PATH_F;        // conv: PATH_A / PATH_B / PATH_F / PATH_G / PATH_T
   int dil = 1, dil_arg = 1; // conv: the effective dilation (1 when the kernel is 1 x 1) and the number the layer was created with;
                             // dil > 1 is PATH_G as well, with groups >= 1
+  // a layer of i8ie_conv2d_create_rect with an unequal pair: PATH_G with any groups >= 1.  stride / pad /
+  // dil / dil_arg above are then the h axis' numbers and these the w axis'; a square layer holds equal values
+  bool rect = false;
+  int stride_w = 1, pad_w = 0, dil_w = 1, dil_arg_w = 1;
   int groups = 1;           // conv, groups > 1 (PATH_G): K above is the reduction length INSIDE a group, (c / groups) * kh * kw,
   int Ngp = 0, Kgp = 0;     // and the weights are [groups][Ngp][Kgp], K ordered (kh, kw, cg) (i8ie_gconv.h)
   int8_t* Bg = nullptr;
@@ -99,6 +125,11 @@ struct i8ie_layer {
   bool ms_fast = false;        // every column allows the guarded estimate (i8ie_requant_pc_fast)
   float ms_s_in = 0.0f, ms_s_out = 0.0f;
 };
+
+// the geometry the kernels walk: the handle's numbers with the effective dilations
+inline i8ie_conv_geom layer_geom(const i8ie_layer* L) {
+  return i8ie_conv_geom{L->kh, L->kw, L->stride, L->stride_w, L->pad, L->pad_w, L->dil, L->dil_w};
+}
 
 // one device buffer of the handle: `bytes` allocated into *dev and onto L->owned, filled from `host` when that is given
 int i8ie_layer_buffer(i8ie_layer* L, void** dev, size_t bytes, const void* host = nullptr);

@@ -12,6 +12,9 @@
 //      NHWC activations; and every layer with a dilation > 1 (not in the reference), dense ones as groups = 1
 //   D  inside G: a dense dilated layer at stride 1 with channels % 16 == 0 runs in dconv_mfma (i8ie_dconv.hip), its input
 //      patches phase-subsampled into LDS; what that kernel declines stays in the grouped kernels
+//   L  inside G: a dense 1 x k / k x 1 layer at stride 1, dilation 1 with channels % 16 == 0 (i8ie_conv2d_create_rect) runs in
+//      lconv_mfma (i8ie_lconv.hip), whole lines of pixels resident in LDS; what that kernel declines, and every other rectangular
+//      or anisotropic layer, stays in the grouped kernels with the per-axis geometry in their tap offsets
 //   T  ConvTranspose2d (not in the reference): the reference convolution of the equivalent zero-inserted problem, computed
 //      phase by phase in the kernels of i8ie_deconv.hip over NHWC activations
 // Activations cross the ABI as NCHW (the reference's layout) or, on request, as
@@ -26,6 +29,7 @@
 #include "i8ie_gconv.h"
 #include "i8ie_deconv.h"
 #include "i8ie_dconv.h"
+#include "i8ie_lconv.h"
 
 // ---- v1 (fallback) runners ------------------------------------------------------------------
 int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, const int8_t* Bpack, const int32_t* oc,
@@ -299,14 +303,15 @@ static int forward_grouped(i8ie_layer* L, const ConvGeom& cg, const ConvRequest&
   I8IE_TRY(stage_io(L->ctx, cg, q, &s));
   I8ieGconvCall g{};
   g.A = s.in; g.m = q.m; g.H = cg.h; g.W = cg.w; g.C = cg.c; g.ib = s.ib;
-  g.OH = cg.oh; g.OW = cg.ow; g.stride = cg.stride; g.pad = cg.pad; g.KH = cg.kh; g.KW = cg.kw; g.dil = L->dil;
+  g.OH = cg.oh; g.OW = cg.ow; g.KH = cg.kh; g.KW = cg.kw;
+  g.stride_h = cg.stride; g.stride_w = cg.stride_w; g.pad_h = cg.pad; g.pad_w = cg.pad_w; g.dil_h = cg.dil_h; g.dil_w = cg.dil_w;
   g.groups = L->groups; g.Cg = cg.c / L->groups; g.Ng = L->n / L->groups; g.Ngp = L->Ngp; g.Kgp = L->Kgp;
   g.Bp = L->Bg; g.ktab = L->gtab; g.ep = layer_epilogue(L, q); g.zp_in = q.zp_in;
   g.out = s.out; g.ob = s.ob;
   // route D: a dense dilated layer at stride 1 goes to the kernel of i8ie_dconv.hip (input patches resident in LDS) when that
   // takes it -- C % 16 == 0, K >= 32, aligned buffers, an LDS plan that fits, the force-fallback option off; it reads route G's
   // panel (groups = 1: [Ngp][Kgp], K ordered (kh, kw, c)) as it is.  Everything it declines stays in the grouped kernels.
-  if (L->dil > 1 && L->groups == 1 && cg.stride == 1 && cg.kh == cg.kw) {
+  if (!L->rect && L->dil > 1 && L->groups == 1 && cg.stride == 1 && cg.kh == cg.kw) {
     I8ieDconvCall d{};
     d.A = s.in; d.m = q.m; d.H = cg.h; d.W = cg.w; d.C = cg.c; d.ib = s.ib;
     d.OH = cg.oh; d.OW = cg.ow; d.pad = cg.pad; d.k = cg.kh; d.dil = L->dil;
@@ -314,6 +319,19 @@ static int forward_grouped(i8ie_layer* L, const ConvGeom& cg, const ConvRequest&
     d.out = s.out; d.ob = s.ob;
     if (i8ie_dconv_takes(L->ctx, d)) {
       I8IE_TRY(i8ie_dconv_launch(L->ctx, d));
+      return unstage(L->ctx, s, q, cg.kc, cg.oh, cg.ow);
+    }
+  }
+  // route L: a dense 1 x k / k x 1 layer at stride (1, 1), dilation (1, 1) goes to the kernel of i8ie_lconv.hip (whole lines
+  // resident in LDS) when that takes it; it reads the same panel.  Everything it declines stays in the grouped kernels.
+  if (L->rect && L->groups == 1 && cg.stride == 1 && cg.stride_w == 1 && cg.dil_h == 1 && cg.dil_w == 1 && (cg.kh == 1 || cg.kw == 1)) {
+    I8ieLconvCall d{};
+    d.A = s.in; d.m = q.m; d.H = cg.h; d.W = cg.w; d.C = cg.c; d.ib = s.ib;
+    d.OH = cg.oh; d.OW = cg.ow; d.KH = cg.kh; d.KW = cg.kw; d.pad_h = cg.pad; d.pad_w = cg.pad_w;
+    d.N = L->n; d.Ngp = L->Ngp; d.Kgp = L->Kgp; d.Bp = L->Bg; d.ep = g.ep; d.zp_in = q.zp_in;
+    d.out = s.out; d.ob = s.ob;
+    if (i8ie_lconv_takes(L->ctx, d)) {
+      I8IE_TRY(i8ie_lconv_launch(L->ctx, d));
       return unstage(L->ctx, s, q, cg.kc, cg.oh, cg.ow);
     }
   }
@@ -618,7 +636,7 @@ static int layer_forward(i8ie_layer* L, const ConvRequest& q) {
   if (L->path == PATH_T)
     I8IE_TRY(deconv_geom(L->c, q.h, q.w, L->n, L->kh, L->stride, L->pad, L->opad, &cg));
   else
-    I8IE_TRY(conv_geom(L->c, q.h, q.w, L->n, L->kh, L->kw, L->stride, L->pad, &cg, L->dil));
+    I8IE_TRY(conv_geom(L->c, q.h, q.w, L->n, layer_geom(L), &cg));
   if (q.pool()) I8IE_REQUIRE(q.pool_k <= cg.oh && q.pool_k <= cg.ow, "max-pool window larger than the convolution's output");
   return forward_conv(L, cg, q);
 }
@@ -657,7 +675,7 @@ int i8ie_layer_forward_dequant(i8ie_layer* L, const uint8_t* in, int in_layout, 
 // (NHWC in with the layer's padding as its border, NHWC out without one, no buffers yet: null pointers count as aligned)
 static bool query_plan(const i8ie_layer* L, int m, int h, int w, int pool_k, int pool_s, int in_layout, int out_layout, ConvPlan* p,
                        ConvGeom* cg) {
-  if (conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, cg, L->dil) != I8IE_OK) return false;
+  if (conv_geom(L->c, h, w, L->n, layer_geom(L), cg) != I8IE_OK) return false;
   ConvRequest q = make_request(nullptr, in_layout, cg->pad, m, h, w, 0.0f, 0, 0, nullptr, out_layout, 0, nullptr);
   q.pool_k = pool_k; q.pool_s = pool_s;
   if (q.pool() && (pool_s < 1 || pool_k > cg->oh || pool_k > cg->ow)) return false;
@@ -718,7 +736,7 @@ int i8ie_layer_forward_f32_input_pool(i8ie_layer* L, const float* in, int m, int
   I8IE_TRY(ensure_offsets(L, q_scale, q_zp));
   I8IE_TRY(ensure_multipliers(L, q_scale));
   ConvGeom cg;
-  I8IE_TRY(conv_geom(L->c, h, w, L->n, L->kh, L->kw, L->stride, L->pad, &cg, L->dil));
+  I8IE_TRY(conv_geom(L->c, h, w, L->n, layer_geom(L), &cg));
   ConvRequest q = make_request(nullptr, I8IE_LAYOUT_NCHW, 0, m, h, w, q_scale, q_zp, relu, out, out_layout, out_border, acc);
   q.x = in; q.pool_k = pool_k; q.pool_s = pool_s;
   if (q.pool()) I8IE_REQUIRE(pool_s > 0 && pool_k <= cg.oh && pool_k <= cg.ow, "max-pool window larger than the convolution's output");

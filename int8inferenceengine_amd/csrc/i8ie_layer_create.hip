@@ -23,13 +23,29 @@ enum { KIND_LINEAR, KIND_CONV, KIND_DECONV };
 struct LayerSpec {
   int kind = KIND_CONV;
   int n = 0, c = 0, kh = 1, kw = 1, stride = 1, pad = 0, groups = 1, dilation = 1, output_pad = 0;
+  // the w axis of a Conv2d: stride / pad / dilation above are the h axis' numbers.  Only
+  // i8ie_conv2d_create_rect gives unequal pairs; `rect`: it did (or kh != kw came with it), and the layer is route G's
+  int stride_w = 1, pad_w = 0, dilation_w = 1;
+  bool rect = false;
   float s_w = 1.0f;
   const float* s_w_pc = nullptr;  // [n] per-channel scales; null: per tensor (s_w)
   int K() const { return (c / groups) * kh * kw; }  // the reduction length of one output feature (after the checks: groups >= 1)
 };
 LayerSpec conv_spec(int kc, int c, int kh, int kw, int stride, int pad) {
   LayerSpec s;
-  s.n = kc; s.c = c; s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad;
+  s.n = kc; s.c = c; s.kh = kh; s.kw = kw; s.stride = s.stride_w = stride; s.pad = s.pad_w = pad;
+  return s;
+}
+LayerSpec dilated_spec(int kc, int c, int kh, int kw, int stride, int pad, int groups, int dilation) {
+  LayerSpec s = conv_spec(kc, c, kh, kw, stride, pad);
+  s.groups = groups; s.dilation = s.dilation_w = dilation;
+  return s;
+}
+// the eight integers of i8ie_conv2d_create_rect; all four pairs equal: the spec of i8ie_conv2d_create_dilated
+LayerSpec rect_spec(int kc, int c, int groups, const i8ie_conv_geom& g) {
+  LayerSpec s = dilated_spec(kc, c, g.kh, g.kw, g.stride_h, g.pad_h, groups, g.dilation_h);
+  s.stride_w = g.stride_w; s.pad_w = g.pad_w; s.dilation_w = g.dilation_w;
+  s.rect = g.kh != g.kw || g.stride_h != g.stride_w || g.pad_h != g.pad_w || g.dilation_h != g.dilation_w;
   return s;
 }
 LayerSpec deconv_spec(int kc, int c, int k, int stride, int pad, int output_pad) {
@@ -79,6 +95,14 @@ int check_dilation(int dilation) {
   I8IE_REQUIRE(dilation >= 1, "dilation must be >= 1");
   return I8IE_OK;
 }
+// the w axis of a rect geometry: the rules check_groups and check_dilation apply to the h axis' numbers
+int check_rect(const LayerSpec& s) {
+  const int stride_w = s.stride_w, pad_w = s.pad_w, dilation_w = s.dilation_w;
+  REQUIRE_AS("i8ie_conv2d_create_rect", stride_w > 0, "stride must be positive");
+  REQUIRE_AS("i8ie_conv2d_create_rect", pad_w >= 0, "negative padding");
+  REQUIRE_AS("i8ie_conv2d_create_rect", dilation_w >= 1, "dilation must be >= 1");
+  return I8IE_OK;
+}
 // ConvTranspose2d (not in the reference): i8ie_deconv_check_args is the rule
 int check_deconv(const LayerSpec& s) { return i8ie_deconv_check_args(s.n, s.c, s.kh, s.stride, s.pad, s.output_pad); }
 // scales from the caller: finite and >= 0 (pooling the INT32 accumulators before the requantiser needs a monotone
@@ -106,17 +130,24 @@ struct Route {
   int path;   // PATH_*
   int dil;    // the effective dilation: what the kernels walk (the handle's dil_arg remembers the number of the spec)
   bool stem;  // route B: the first-stage kernel's packing is made as well
+  int dil_w;  // a rect layer's effective dilation on the w axis (every other layer: dil)
 };
+// the geometry a forward of the spec walks (conv_geom of i8ie_layer.h)
+i8ie_conv_geom geom_of(const LayerSpec& s, const Route& r) {
+  return i8ie_conv_geom{s.kh, s.kw, s.stride, s.stride_w, s.pad, s.pad_w, r.dil, r.dil_w};
+}
 Route route_of(const LayerSpec& s) {
-  if (s.kind == KIND_LINEAR) return {PATH_F, 1, false};  // (a Linear handle has no route: PATH_F is the field's rest value)
-  if (s.kind == KIND_DECONV) return {PATH_T, 1, false};
+  if (s.kind == KIND_LINEAR) return {PATH_F, 1, false, 1};  // (a Linear handle has no route: PATH_F is the field's rest value)
+  if (s.kind == KIND_DECONV) return {PATH_T, 1, false, 1};
+  // an unequal pair: the grouped route with any groups >= 1, the pairs in the gather; one tap on an axis has no dilation there
+  if (s.rect) return {PATH_G, s.kh == 1 ? 1 : s.dilation, false, s.kw == 1 ? 1 : s.dilation_w};
   // dilation 1 or a 1 x 1 kernel is exactly the undilated layer: same route, same kernels
   const int dil = (s.dilation == 1 || (s.kh == 1 && s.kw == 1)) ? 1 : s.dilation;
-  if (s.groups > 1 || dil > 1) return {PATH_G, dil, false};  // (a dilated layer with any groups >= 1: the dilation is in the gather)
-  if (s.c % 16 == 0) return {PATH_A, 1, false};
+  if (s.groups > 1 || dil > 1) return {PATH_G, dil, false, dil};  // (a dilated layer with any groups >= 1: the dilation is in the gather)
+  if (s.c % 16 == 0) return {PATH_A, 1, false, 1};
   if (s.c <= 4 && s.stride % 4 == 0)
-    return {PATH_B, 1, s.c <= 3 && s.n % 32 == 0 && s.n <= 96 && (s.kh + 3) / 4 * ((s.kw + 3) / 4) * 48 <= 14 * 32};
-  return {PATH_F, 1, false};
+    return {PATH_B, 1, s.c <= 3 && s.n % 32 == 0 && s.n <= 96 && (s.kh + 3) / 4 * ((s.kw + 3) / 4) * 48 <= 14 * 32, 1};
+  return {PATH_F, 1, false, 1};
 }
 
 // ---- pack: the weights in the K orders of the kernels, built on the host once -----------------------------------------------------
@@ -244,8 +275,9 @@ int layer_build(i8ie_ctx* ctx, const LayerSpec& s, const int8_t* qw_host, const 
   if (L->conv) {
     L->c = s.c; L->kh = s.kh; L->kw = s.kw; L->stride = s.stride; L->pad = s.pad;
     L->groups = s.groups; L->opad = s.output_pad;
+    L->rect = s.rect; L->stride_w = s.stride_w; L->pad_w = s.pad_w;
   }
-  L->path = r.path; L->dil = r.dil; L->dil_arg = s.dilation;
+  L->path = r.path; L->dil = r.dil; L->dil_arg = s.dilation; L->dil_w = r.dil_w; L->dil_arg_w = s.dilation_w;
   L->s_w = s.s_w_pc ? 1.0f : s.s_w;  // (unused by a per-channel layer)
   L->Kpad = round_up(L->K, 128);
   L->Npad = round_up(L->n, 128);
@@ -283,7 +315,7 @@ int check_once(const char* who, const i8ie_ctx* ctx, const OnceCall& q) {
 int check_once_geometry(const LayerSpec& s, const OnceCall& q) {
   ConvGeom cg;
   if (s.kind == KIND_DECONV) return deconv_geom(s.c, q.h, q.w, s.n, s.kh, s.stride, s.pad, s.output_pad, &cg);
-  return conv_geom(s.c, q.h, q.w, s.n, s.kh, s.kw, s.stride, s.pad, &cg, route_of(s).dil);
+  return conv_geom(s.c, q.h, q.w, s.n, geom_of(s, route_of(s)), &cg);
 }
 // The weights are packed for this one call: read back from the device, built into a temporary handle (zero bias: the caller's
 // oc[] carries the bias term) that runs one NCHW forward with that oc[] instead of its own, and is destroyed.
@@ -372,8 +404,8 @@ int i8ie_conv2d_create_grouped_per_channel(i8ie_ctx* ctx, const int8_t* qw_host,
 
 int i8ie_conv2d_create_dilated(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh, int kw,
                                int stride, int pad, int groups, int dilation, float s_w, i8ie_layer** out) {
-  LayerSpec s = conv_spec(kc, c, kh, kw, stride, pad);
-  s.groups = groups; s.dilation = dilation; s.s_w = s_w;
+  LayerSpec s = dilated_spec(kc, c, kh, kw, stride, pad, groups, dilation);
+  s.s_w = s_w;
   I8IE_TRY(check_groups(s));
   I8IE_TRY(check_dilation(dilation));
   return layer_build(ctx, s, qw_host, qb_host, out);
@@ -382,10 +414,35 @@ int i8ie_conv2d_create_dilated(i8ie_ctx* ctx, const int8_t* qw_host, const int8_
 int i8ie_conv2d_create_dilated_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh,
                                            int kw, int stride, int pad, int groups, int dilation, const float* s_w_host,
                                            i8ie_layer** out) {
-  LayerSpec s = conv_spec(kc, c, kh, kw, stride, pad);
-  s.groups = groups; s.dilation = dilation; s.s_w_pc = s_w_host;
+  LayerSpec s = dilated_spec(kc, c, kh, kw, stride, pad, groups, dilation);
+  s.s_w_pc = s_w_host;
   I8IE_TRY(check_groups(s));
   I8IE_TRY(check_dilation(dilation));
+  I8IE_REQUIRE(out != nullptr, "bad argument");
+  I8IE_TRY(check_scales(s_w_host, kc));
+  return layer_build(ctx, s, qw_host, qb_host, out);
+}
+
+// a geometry of eight integers; all four pairs equal: what the two entries above make
+int i8ie_conv2d_create_rect(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int groups,
+                            const i8ie_conv_geom* geom, float s_w, i8ie_layer** out) {
+  I8IE_REQUIRE(geom != nullptr, "null geometry");
+  LayerSpec s = rect_spec(kc, c, groups, *geom);
+  s.s_w = s_w;
+  I8IE_TRY(check_groups(s));
+  I8IE_TRY(check_dilation(s.dilation));
+  I8IE_TRY(check_rect(s));
+  return layer_build(ctx, s, qw_host, qb_host, out);
+}
+
+int i8ie_conv2d_create_rect_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int groups,
+                                        const i8ie_conv_geom* geom, const float* s_w_host, i8ie_layer** out) {
+  I8IE_REQUIRE(geom != nullptr, "null geometry");
+  LayerSpec s = rect_spec(kc, c, groups, *geom);
+  s.s_w_pc = s_w_host;
+  I8IE_TRY(check_groups(s));
+  I8IE_TRY(check_dilation(s.dilation));
+  I8IE_TRY(check_rect(s));
   I8IE_REQUIRE(out != nullptr, "bad argument");
   I8IE_TRY(check_scales(s_w_host, kc));
   return layer_build(ctx, s, qw_host, qb_host, out);
@@ -426,7 +483,15 @@ int i8ie_layer_groups(const i8ie_layer* L, int* groups) {
 
 int i8ie_layer_dilation(const i8ie_layer* L, int* dilation) {
   I8IE_REQUIRE(L && dilation, "null argument");
+  I8IE_REQUIRE(L->dil_arg == L->dil_arg_w, "the layer's dilations differ per axis: ask i8ie_layer_geometry");
   *dilation = L->dil_arg;
+  return I8IE_OK;
+}
+
+int i8ie_layer_geometry(const i8ie_layer* L, i8ie_conv_geom* geom) {
+  I8IE_REQUIRE(L && geom, "null argument");
+  I8IE_REQUIRE(L->conv, "a Linear layer has no geometry");
+  *geom = i8ie_conv_geom{L->kh, L->kw, L->stride, L->stride_w, L->pad, L->pad_w, L->dil_arg, L->dil_arg_w};
   return I8IE_OK;
 }
 
@@ -456,7 +521,8 @@ int i8ie_layer_padding(const i8ie_layer* L, int* pad) {
   I8IE_REQUIRE(L && pad, "null argument");
   // (a transposed layer reads no border; a dilated one needs none and accepts any: its taps are bounds-checked, and a
   // border of `pad` pixels around a small map would multiply its bytes)
-  *pad = (L->conv && L->path != PATH_T && L->dil == 1) ? L->pad : 0;
+  // (a rect layer, like a dilated one, needs no border and accepts any)
+  *pad = (L->conv && L->path != PATH_T && L->dil == 1 && !L->rect) ? L->pad : 0;
   return I8IE_OK;
 }
 
@@ -546,13 +612,31 @@ int i8ie_conv2d_u8s8_grouped(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int
 int i8ie_conv2d_u8s8_dilated(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int kh,
                              int kw, int stride, int pad, int groups, int dilation, uint8_t zp_in, const int32_t* oc, float s_in,
                              float s_w, float s_out, uint8_t zp_out, uint8_t* out, int32_t* acc) {
-  LayerSpec s = conv_spec(kc, c, kh, kw, stride, pad);
-  s.groups = groups; s.dilation = dilation; s.s_w = s_w;
+  LayerSpec s = dilated_spec(kc, c, kh, kw, stride, pad, groups, dilation);
+  s.s_w = s_w;
   I8IE_TRY(check_groups(s));
   I8IE_TRY(check_dilation(dilation));
   if (route_of(s).dil == 1)
     return i8ie_conv2d_u8s8_grouped(ctx, in, n, c, h, w, qw, kc, kh, kw, stride, pad, groups, zp_in, oc, s_in, s_w, s_out, zp_out,
                                     out, acc);
+  const OnceCall q{in, n, h, w, qw, zp_in, oc, s_in, s_out, zp_out, out, acc};
+  I8IE_TRY(check_once_geometry(s, q));
+  I8IE_TRY(check_once(__func__, ctx, q));
+  return run_once(ctx, s, q);
+}
+
+int i8ie_conv2d_u8s8_rect(i8ie_ctx* ctx, const uint8_t* in, int n, int c, int h, int w, const int8_t* qw, int kc, int groups,
+                          const i8ie_conv_geom* geom, uint8_t zp_in, const int32_t* oc, float s_in, float s_w, float s_out,
+                          uint8_t zp_out, uint8_t* out, int32_t* acc) {
+  I8IE_REQUIRE(geom != nullptr, "null geometry");
+  LayerSpec s = rect_spec(kc, c, groups, *geom);
+  s.s_w = s_w;
+  I8IE_TRY(check_groups(s));
+  I8IE_TRY(check_dilation(s.dilation));
+  I8IE_TRY(check_rect(s));
+  if (!s.rect)
+    return i8ie_conv2d_u8s8_dilated(ctx, in, n, c, h, w, qw, kc, s.kh, s.kw, s.stride, s.pad, groups, s.dilation, zp_in, oc, s_in,
+                                    s_w, s_out, zp_out, out, acc);
   const OnceCall q{in, n, h, w, qw, zp_in, oc, s_in, s_out, zp_out, out, acc};
   I8IE_TRY(check_once_geometry(s, q));
   I8IE_TRY(check_once(__func__, ctx, q));

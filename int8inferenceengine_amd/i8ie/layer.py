@@ -1,4 +1,6 @@
 """Layer wrappers (reference i8ie/layer.py:5-35)."""
+import numbers
+
 import _CXX_i8ie as _C
 
 from .tensor import Tensor
@@ -54,13 +56,31 @@ class Layer:
         return self.layer.groups() if hasattr(self.layer, "groups") else 1
 
     def dilation(self):
-        """Dilation of a Conv2d as it was constructed (1 for every other layer)."""
+        """Dilation of a Conv2d as it was constructed: the int where both axes agree, the pair (h, w) otherwise (1 for every
+        other layer)."""
         return self.layer.dilation() if hasattr(self.layer, "dilation") else 1
+
+    def geometry(self):
+        """The four geometry pairs of a Conv2d, {"kernel_size", "stride", "padding", "dilation"}: each (h, w), equal values for
+        a layer constructed from ints.  None for every other layer."""
+        ask = getattr(self.layer, "geometry", None) or getattr(self.layer, "_geometry", None)  # (the extension's Conv2d binds it privately)
+        return None if ask is None else dict(ask())
 
     def forward_debug(self, x):
         """INT8 forward that also returns the INT32 pre-requant accumulators (numpy)."""
         out, acc = self.layer.forward_debug(x.data)
         return Tensor(out), acc
+
+
+def _pair(value, name):
+    """(h, w) of a geometry argument given as an int or as a pair of ints; anything else is a TypeError"""
+    def is_int(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if is_int(value):
+        return (int(value), int(value))
+    if isinstance(value, (tuple, list)) and len(value) == 2 and all(is_int(v) for v in value):
+        return (int(value[0]), int(value[1]))
+    raise TypeError("Conv2d: %s must be an int or a pair of ints (h, w), got %r" % (name, value))
 
 
 class Linear(Layer):
@@ -74,8 +94,16 @@ class Conv2d(Layer):
         [g*in/groups, (g+1)*in/groups); the weight is [out, in/groups, k, k].  groups == in_channels is depthwise.
         dilation (additive as well; one integer >= 1, torch.nn.Conv2d's): tap (ky, kx) reads the input dilation * ky rows and
         dilation * kx columns from the window's origin, so the output is (h + 2 * padding - dilation * (k - 1) - 1) // stride
-        + 1 high.  The weight keeps its shape; save / load are unchanged (dilation is a constructor argument like stride)."""
-        self.layer = _C.Conv2d(in_channels, out_channels, kernel_size, stride, padding, groups, dilation)
+        + 1 high.  The weight keeps its shape; save / load are unchanged (dilation is a constructor argument like stride).
+        kernel_size, stride, padding and dilation each take an int or a pair (h, w) (additive; torch.nn.Conv2d's; anything
+        else is a TypeError): tap (ky, kx) of output pixel (oy, ox) reads input pixel (oy * stride_h - padding_h + ky *
+        dilation_h, ox * stride_w - padding_w + kx * dilation_w), and the weight is [out, in/groups, kh, kw].  Ints and pairs of
+        equal values construct exactly the layer the ints always did; geometry() gives the four pairs either way."""
+        pairs = [_pair(v, n) for v, n in ((kernel_size, "kernel_size"), (stride, "stride"), (padding, "padding"), (dilation, "dilation"))]
+        if all(h == w for h, w in pairs):
+            self.layer = _C.Conv2d(in_channels, out_channels, pairs[0][0], pairs[1][0], pairs[2][0], groups, pairs[3][0])
+        else:
+            self.layer = _C._Conv2dRect(in_channels, out_channels, pairs[0], pairs[1], pairs[2], groups, pairs[3])
 
 
 class ConvTranspose2d(Layer):
