@@ -676,6 +676,45 @@ int i8ie_upsample2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border,
 int i8ie_upsample2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int fh, int fw,
                         int mode);
 
+/* ---- channel narrow, channel shuffle, pixel shuffle and unshuffle (no counterpart in the reference) ---------------
+ * Byte rearrangements of an NCHW logical shape [n, c, h, w]; nothing is requantised: the result carries the input's
+ * (scale, zero_point).  `kind` with its parameters p0, p1 (p1 is read by narrow alone):
+ *   I8IE_REARRANGE_NARROW           p0 = start, p1 = length, 0 <= start, 1 <= length, start + length <= c:
+ *       out[n, k, y, x] = in[n, start + k, y, x]                                    -> [n, length, h, w]
+ *   I8IE_REARRANGE_CHANNEL_SHUFFLE  p0 = groups >= 1, c % groups == 0 (torch.nn.ChannelShuffle):
+ *       out[n, j*groups + i, y, x] = in[n, i*(c/groups) + j, y, x]                  -> [n, c, h, w]
+ *   I8IE_REARRANGE_PIXEL_SHUFFLE    p0 = r in 1..8, c % (r*r) == 0 (torch's pixel_shuffle):
+ *       out[n, co, y*r + i, x*r + j] = in[n, co*r*r + i*r + j, y, x]                -> [n, c/(r*r), h*r, w*r]
+ *   I8IE_REARRANGE_PIXEL_UNSHUFFLE  p0 = r in 1..8, h % r == 0, w % r == 0 (torch's pixel_unshuffle, the inverse):
+ *       out[n, ci*r*r + i*r + j, y, x] = in[n, ci, y*r + i, x*r + j]                -> [n, c*r*r, h/r, w/r]
+ *   out = relu ? max(out, zero_point) : out        relu<u8>, src/functional.cc:15-26, on the NHWC entry
+ * The three permuting kinds take at most 65535 channels on either side.  Null pointers, non-positive sizes, negative
+ * borders, an unknown kind and parameters outside these rules are I8IE_ERR_ARG, raised before any device call; the
+ * message begins with the op's name (narrow, channel_shuffle, pixel_shuffle, pixel_unshuffle).  Stateless and capturable
+ * in a graph; `out` must not overlap `in` (csrc/i8ie_rearrange.hip).
+ * i8ie_rearrange_output_shape (host only): the result's four dims into out_dims, or I8IE_ERR_ARG. */
+#define I8IE_REARRANGE_NARROW 0
+#define I8IE_REARRANGE_CHANNEL_SHUFFLE 1
+#define I8IE_REARRANGE_PIXEL_SHUFFLE 2
+#define I8IE_REARRANGE_PIXEL_UNSHUFFLE 3
+int i8ie_rearrange_output_shape(int kind, int p0, int p1, int n, int c, int h, int w, int* out_dims);
+/* On NHWC buffers [n, h+2b, w+2b, c] -> [n, oh+2b', ow+2b', oc], each with its own border and each plain (x_s8 = 0) or
+ * re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80).  The input's border bytes are never read.  Only the interior
+ * of `out` is written: its border bytes are the caller's (i8ie_fill_border_u8).  Any c, any alignment: narrow moves
+ * 16 / 8 / 4 / 2 / 1 bytes per lane by start, length, c and the pointers' alignment; the permuting kinds take the
+ * 16-byte transposing kernel where c % 16 == 0, oc % 16 == 0 and both pointers are 16-byte aligned, one lane per byte
+ * otherwise (and under I8IE_OPT_FORCE_FALLBACK); the bytes are the same.  h, w: logical input dims. */
+int i8ie_rearrange_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev,
+                           int out_border, int out_s8, int n, int c, int h, int w, int kind, int p0, int p1, int relu,
+                           uint8_t zero_point);
+/* Plain NCHW in and out, any shape (no relu: a caller applies i8ie_relu_u8).  The rank-2 narrow of [m, f] rows is
+ * n = m, c = f, h = w = 1. */
+int i8ie_rearrange_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int n, int c, int h, int w, int kind,
+                      int p0, int p1);
+/* FP32, NCHW: the same index maps, bits copied (before convert(), and while calibrating). */
+int i8ie_rearrange_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int kind, int p0,
+                       int p1);
+
 /* ---- quantized channel concatenation (no counterpart in the reference: it has no op that joins two tensors) ----
  * cat(x_0 .. x_{k-1}) along axis 1, 1 <= k <= I8IE_CONCAT_MAX_INPUTS; the same buffer may appear more than once.  The
  * result carries its own (s_out, zp_out).  A byte a of input i, with that tensor's (s_i, zp_i), becomes

@@ -183,5 +183,6 @@ Tensor<u8_t> group_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, 
 Tensor<float> activation_f32(Tensor<float>& in, int kind, float param);
 Tensor<u8_t> activation_u8(Tensor<u8_t>& in, int kind, float param, float scale, int zp);
 void bind_ops(py::module_& m);
+void bind_rearrange(py::module_& m);  // ops_rearrange.cc: _narrow, _channel_shuffle, _pixel_shuffle, _pixel_unshuffle
 
 }  // namespace i8ie_py

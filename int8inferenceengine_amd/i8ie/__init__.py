@@ -20,6 +20,7 @@ __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
     "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "GroupNorm", "group_norm", "Attention", "attention",
+    "narrow", "split", "chunk", "channel_shuffle", "pixel_shuffle", "pixel_unshuffle",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
 
@@ -259,6 +260,76 @@ def upsample(x, scale_factor, mode="nearest"):
     if mode not in _UPSAMPLE_MODES:
         raise RuntimeError("upsample: mode must be 'nearest' or 'bilinear'")
     return Tensor(_C.upsample(x.data, int(fh), int(fw), _UPSAMPLE_MODES[mode]))
+
+
+def _integer(op, what, v):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+        raise TypeError("%s: %s must be an integer" % (op, what))
+    return int(v)
+
+
+def narrow(x, start, length):
+    """Channels start .. start + length - 1 of axis 1 of an [n, c, h, w] or [m, f] tensor (torch.narrow(x, 1, start, length)).
+    uint8 tensors: the bytes are copied and the result carries the input's scale and zero point (include/i8ie_hip.h,
+    i8ie_rearrange_u8_nhwc); FP32 tensors: bits copied; int8 (s8) tensors raise RuntimeError.  The result is recorded, not
+    launched: it launches when something consumes it."""
+    return Tensor(_C._narrow(x.data, _integer("narrow", "start", start), _integer("narrow", "length", length)))
+
+
+def split(x, split_size_or_sections):
+    """torch.split along axis 1: an int gives parts of that many channels (the last one may be smaller), a list gives parts
+    of exactly those sizes and must sum to the channel count.  A list of tensors, each a `narrow` of x: a part nobody
+    consumes launches nothing."""
+    shape = x.shape
+    if len(shape) not in (2, 4):
+        raise RuntimeError("split expects [n, c, h, w] or [m, f]")
+    c = int(shape[1])
+    if isinstance(split_size_or_sections, (tuple, list)):
+        sizes = [_integer("split", "every size", s) for s in split_size_or_sections]
+        if not sizes or any(s <= 0 for s in sizes) or sum(sizes) != c:
+            raise RuntimeError("split: the sizes must be positive and sum to the %d channels" % c)
+    else:
+        size = _integer("split", "the size", split_size_or_sections)
+        if size <= 0:
+            raise RuntimeError("split: the size must be positive")
+        sizes = [min(size, c - at) for at in range(0, c, size)]
+    parts, at = [], 0
+    for s in sizes:
+        parts.append(narrow(x, at, s))
+        at += s
+    return parts
+
+
+def chunk(x, chunks):
+    """torch.chunk along axis 1: parts of ceil(c / chunks) channels, the last one may be smaller (and there may be fewer
+    than `chunks` parts).  A list of tensors, as `split` returns it."""
+    chunks = _integer("chunk", "chunks", chunks)
+    if chunks <= 0:
+        raise RuntimeError("chunk: chunks must be positive")
+    shape = x.shape
+    if len(shape) not in (2, 4):
+        raise RuntimeError("chunk expects [n, c, h, w] or [m, f]")
+    return split(x, -(-int(shape[1]) // chunks))
+
+
+def channel_shuffle(x, groups):
+    """torch.nn.ChannelShuffle on an [n, c, h, w] tensor, c % groups == 0: x.view(n, g, c / g, h, w).transpose(1, 2), i.e.
+    out[:, j * g + i] = in[:, i * (c / g) + j].  uint8 tensors: bytes moved, the input's scale and zero point; FP32 tensors:
+    bits moved; int8 (s8) tensors raise RuntimeError (include/i8ie_hip.h, i8ie_rearrange_u8_nhwc)."""
+    return Tensor(_C._channel_shuffle(x.data, _integer("channel_shuffle", "groups", groups)))
+
+
+def pixel_shuffle(x, upscale_factor):
+    """torch's pixel_shuffle: [n, c r r, h, w] -> [n, c, h r, w r], out[n, co, h r + i, w r + j] = in[n, co r r + i r + j, h, w],
+    r an integer in 1..8.  uint8 tensors: bytes moved, the input's scale and zero point; FP32 tensors: bits moved; int8 (s8)
+    tensors raise RuntimeError (include/i8ie_hip.h, i8ie_rearrange_u8_nhwc)."""
+    return Tensor(_C._pixel_shuffle(x.data, _integer("pixel_shuffle", "upscale_factor", upscale_factor)))
+
+
+def pixel_unshuffle(x, downscale_factor):
+    """torch's pixel_unshuffle, the inverse of pixel_shuffle: [n, c, h, w] -> [n, c r r, h / r, w / r], r an integer in 1..8
+    that divides h and w.  Tensor types as pixel_shuffle."""
+    return Tensor(_C._pixel_unshuffle(x.data, _integer("pixel_unshuffle", "downscale_factor", downscale_factor)))
 
 
 def synchronize():
