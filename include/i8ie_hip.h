@@ -1092,6 +1092,58 @@ int i8ie_maxpool2d_f32_pad(i8ie_ctx* ctx, const float* in_dev, float* out_dev, i
 int i8ie_avgpool2d_f32_pad(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w,
                            int kernel_size, int stride, int padding, int ceil_mode, int count_include_pad);
 
+/* ---- quantized inference BatchNorm (torch.nn.BatchNorm2d in eval mode; no counterpart in the reference) -------------------
+ * Inference only: the statistics are the stored running ones; there is no momentum, no training mode and no
+ * track_running_stats.  The input is [n, C, h, w] bytes with (s_in, zp_in), 1 <= C <= 16384; gamma, beta, mean, var are fp32
+ * [C] with var[c] >= 0; eps is finite and > 0; the result carries (s_out, zp_out):
+ *     k[c] = (double)gamma[c] / sqrt((double)var[c] + (double)eps)                          host, double
+ *     g[c] = (float)(k[c] / (double)s_out)                                                  } i8ie_batchnorm_affine, once per
+ *     b[c] = (float)(((double)beta[c] - (double)mean[c] * k[c]) / (double)s_out + zp_out)   } layer: one rounding to float each
+ *     x = (float)((int)a - (int)zp_in) * s_in          dequantize, src/quantize_utils.cc:38-42
+ *     t = x * g[c];  v = t + b[c]                      fp32, one rounding per operation, no contraction
+ *     q = v >= 255 ? 255 : (v < 0 ? 0 : (u8)v)         down_scale's clamp + truncation, src/quantize_utils.cc:27-36
+ *     q = relu ? max(q, zp_out) : q                    relu<u8>, src/functional.cc:15-26
+ * (every double operation of k, g, b is IEEE, one rounding each, in the order written, no contraction.)  Every g[c] and b[c]
+ * must be finite, else I8IE_ERR_ARG from the host entry; s_in and 255 * s_in must be finite.  No NaN can then arise: x is
+ * finite, t may overflow to an infinity, which clamps.  g and b do not depend on the input's quantisation: they are made once
+ * per layer, and s_in, zp_in are arguments of the launch.  Per (channel, byte) the op is a fixed function; a kernel may
+ * evaluate it any way that gives these bytes.
+ * The bound against the real numbers.  With T = (a - zp_in) s_in k / s_out, Bt = (beta - mean k) / s_out + zp_out and
+ * y* = T + Bt, all as real numbers of the fp32 inputs:
+ *     |v - y*| <= B = 1.01 * 2^-24 * (4 |T| + |Bt| + |y*|)
+ * (x, g and t round once each on the T path, b once, v once: 3 |T| + |Bt| + |y*|; 4 and the factor 1.01 absorb the double
+ * roundings and every second-order term.)  Where y* lies further than B from an integer, q = clamp(trunc(y*)).
+ * i8ie_batchnorm_affine: host only (no ctx, like i8ie_layernorm_affine).  Null pointers, C outside 1..16384, eps or s_out not
+ * finite and positive, a gamma, beta, mean or var that is not finite, var[c] < 0 and a g[c] or b[c] that is not finite are
+ * I8IE_ERR_ARG; argument errors are reported before anything is written. */
+int i8ie_batchnorm_affine(const float* gamma, const float* beta, const float* mean, const float* var, int C, float eps,
+                          float s_out, uint8_t zp_out, float* g_host, float* b_host);
+/* NHWC buffers [n, h+2b, w+2b, C] -> [n, h+2b', w+2b', C], each with its own border and plain (x_s8 = 0) or re-biased
+ * (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80), the rules of i8ie_layernorm_u8_nhwc: the input's border bytes are never
+ * read; only the interior of `out` is written; out may be in itself when both geometries agree.  g_dev, b_dev: fp32 [C] on
+ * the device (4-byte aligned), as i8ie_batchnorm_affine made them.  Stateless: one launch, no device allocation, no host
+ * synchronisation, capturable in a graph.  Null pointers, C outside 1..16384, non-positive sizes, negative borders, more than
+ * 2^30 pixels per image and an s_in for which 255 * s_in is not finite are I8IE_ERR_ARG with a message, before any device
+ * call.  Two kernels with identical bytes (csrc/i8ie_batchnorm.hip): batchnorm_u8_nhwc (16 / 4 / 1
+ * channels per lane by C % 16 and C % 4, g and b in registers over a run of I8IE_BATCHNORM_WALK pixels) and
+ * batchnorm_u8_direct (one lane per byte, the definition verbatim) for in, out, g or b not 16-byte aligned and for
+ * everything under I8IE_OPT_FORCE_FALLBACK. */
+#define I8IE_BATCHNORM_WALK 8
+int i8ie_batchnorm_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev, int out_border,
+                           int out_s8, int n, int C, int h, int w, const float* g_dev, const float* b_dev, float s_in,
+                           uint8_t zp_in, int relu, uint8_t zp_out);
+/* The flat form for reference-order tensors, any alignment of in and out; out may alias in (no other overlap).  Element c of
+ * row r lies at ((r / inner) * C + c) * inner + r % inner, the convention of i8ie_layernorm_f32: inner = 1 is rows [m, C],
+ * inner = h * w an NCHW tensor in one launch (rows = n * h * w).  inner must divide rows; 1 <= rows <= 2^31 - 1.  Always
+ * batchnorm_u8_direct. */
+int i8ie_batchnorm_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int64_t rows, int C, int64_t inner,
+                      const float* g_dev, const float* b_dev, float s_in, uint8_t zp_in, int relu, uint8_t zp_out);
+/* FP32 (before convert(), and while calibrating), the same element order: out = (x - mean[c]) / sqrtf(var[c] + eps) *
+ * gamma[c] + beta[c], every step fp32 with one rounding per operation, no contraction (torch's eval-mode formula).  out may
+ * alias in.  Not tuned. */
+int i8ie_batchnorm_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int64_t rows, int C, int64_t inner,
+                       const float* gamma_dev, const float* beta_dev, const float* mean_dev, const float* var_dev, float eps);
+
 #ifdef __cplusplus
 }
 #endif

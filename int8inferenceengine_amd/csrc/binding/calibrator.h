@@ -97,6 +97,7 @@ class QuantState {
   }
   std::tuple<float, int> output_qparams() const { return std::make_tuple(scale_, (int)zero_point_); }
   bool is_quantized() const { return is_quantized_; }
+  bool is_preparing() const { return is_preparing_; }
 
  protected:
   ~QuantState() = default;

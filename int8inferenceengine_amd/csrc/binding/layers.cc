@@ -243,6 +243,14 @@ class ConvTranspose2d : public BaseLayer {
     return a;
   }
 
+  py::array_t<float> fp32_weight() override {  // torch's [in, out, k, k]
+    need_fp32_params();
+    const std::vector<float>& t = fp32_kernel_weight();
+    py::array_t<float> a(std::vector<ssize_t>{wshape_[1], wshape_[0], wshape_[2], wshape_[3]});
+    std::memcpy(a.mutable_data(), t.data(), t.size() * sizeof(float));
+    return a;
+  }
+
   std::vector<ssize_t> out_shape(const std::vector<ssize_t>& s) const {
     if (s.size() != 4) throw std::runtime_error("i8ie: ConvTranspose2d expects an NCHW tensor");
     if (s[1] != wshape_[1]) throw std::runtime_error("i8ie: ConvTranspose2d: input channels do not match the weight");
@@ -315,7 +323,11 @@ void bind_layer_common(py::class_<L>& c) {
       .def("q_bias", &L::q_bias)
       .def("weight_scale", &L::weight_scale)
       .def("weight_scales", &L::weight_scales)
-      .def("is_per_channel", &L::is_per_channel);
+      .def("is_per_channel", &L::is_per_channel)
+      // (private: the classes keep their recorded public surface; i8ie.fold_batchnorm reads the FP32 parameters through these)
+      .def("_weight", [](L& l) { return l.fp32_weight(); })
+      .def("_bias", [](L& l) { return l.fp32_bias(); })
+      .def("_is_preparing", [](const L& l) { return l.is_preparing(); });
   bind_quant_state(c);
 }
 

@@ -115,6 +115,17 @@ class BaseLayer : public QuantState {
     return a;
   }
   bool is_per_channel() const { return is_quantized_ && per_channel_; }
+  // the FP32 parameters as loaded (what i8ie.fold_batchnorm reads); gone once convert() has released them
+  virtual py::array_t<float> fp32_weight() {
+    need_fp32_params();
+    py::array_t<float> a(wshape_);
+    std::memcpy(a.mutable_data(), w_.data(), w_.size() * sizeof(float));
+    return a;
+  }
+  py::array_t<float> fp32_bias() {
+    need_fp32_params();
+    return py::array_t<float>((ssize_t)b_.size(), b_.data());
+  }
 
  protected:
   void output_qparams_changed() override {
@@ -265,6 +276,9 @@ class BaseLayer : public QuantState {
     if (!has_fp32_)
       throw std::runtime_error("i8ie: FP32 input given to a converted layer (its FP32 weights were released)");
   }
+  void need_fp32_params() const {
+    if (!has_fp32_) throw std::runtime_error("i8ie: the layer is converted: its FP32 weight and bias were released");
+  }
   virtual const std::vector<float>& fp32_kernel_weight() { return w_; }  // the host weight the FP32 kernel reads
   void upload_fp32() {
     if (w_dev_) return;
@@ -295,6 +309,6 @@ class BaseLayer : public QuantState {
 };
 
 void bind_layers(py::module_& m);             // layers.cc: Linear, Conv2d, ConvTranspose2d, then the weightless ones
-void bind_weightless_layers(py::module_& m);  // layers_weightless.cc: Add ... Activation, LayerNorm, GroupNorm
+void bind_weightless_layers(py::module_& m);  // layers_weightless.cc: Add ... Activation, LayerNorm, GroupNorm, BatchNorm2d
 
 }  // namespace i8ie_py

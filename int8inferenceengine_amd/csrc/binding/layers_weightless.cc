@@ -1,4 +1,4 @@
-// layers_weightless.cc -- the layers without INT8 weights (Add ... Activation, LayerNorm, GroupNorm) and their bindings.
+// layers_weightless.cc -- the layers without INT8 weights (Add ... Activation, LayerNorm, GroupNorm, BatchNorm2d) and their bindings.
 #include "layers.h"
 
 namespace i8ie_py {
@@ -290,6 +290,82 @@ class GroupNorm : public QuantState {
   std::shared_ptr<Storage> gamma_dev_, beta_dev_;  // FP32 path
   std::shared_ptr<Storage> g_dev_, b_dev_;         // after convert()
 };
+// Inference BatchNorm of [n, c, h, w] or [n, c] (torch.nn.BatchNorm2d / BatchNorm1d in eval mode): fp32 weight (gamma), bias
+// (beta), running_mean and running_var of num_features values each and the layers' prepare / convert state machine around its
+// output (scale, zero_point).  convert() computes g and b (i8ie_batchnorm_affine) and uploads them once; they do not depend on
+// the input's quantisation, which is an argument of every launch.
+class BatchNorm2d : public QuantState {
+ public:
+  BatchNorm2d(ssize_t channels, float eps) : channels_(channels), eps_(eps) {
+    if (channels < 1 || channels > 16384) throw std::runtime_error("i8ie: BatchNorm2d: num_features must be in 1..16384");
+    if (!(eps > 0) || !std::isfinite(eps)) throw std::runtime_error("i8ie: BatchNorm2d: eps must be positive and finite");
+    gamma_.assign((size_t)channels, 1.0f);
+    beta_.assign((size_t)channels, 0.0f);
+    mean_.assign((size_t)channels, 0.0f);
+    var_.assign((size_t)channels, 1.0f);
+  }
+  void load_weight(const py::object& a) { gamma_ = layer_norm_param(a, channels_, 1.0f, "weight"); params_changed(); }
+  void load_bias(const py::object& a) { beta_ = layer_norm_param(a, channels_, 0.0f, "bias"); params_changed(); }
+  void load_running_mean(const py::object& a) { mean_ = layer_norm_param(a, channels_, 0.0f, "running_mean"); params_changed(); }
+  void load_running_var(const py::object& a) { var_ = layer_norm_param(a, channels_, 1.0f, "running_var"); params_changed(); }
+  void convert(bool /*per_channel: there are no INT8 weights*/ = false) {
+    if (!convert_qparams()) return;
+    install();
+  }
+  void load_quantized(const py::object& w, const py::object& b, const py::object& mean, const py::object& var, float s_out,
+                      int zp_out) {  // what convert() would have left behind
+    check_zero_point(zp_out);
+    gamma_ = layer_norm_param(w, channels_, 1.0f, "weight");
+    beta_ = layer_norm_param(b, channels_, 0.0f, "bias");
+    mean_ = layer_norm_param(mean, channels_, 0.0f, "running_mean");
+    var_ = layer_norm_param(var, channels_, 1.0f, "running_var");
+    dev_ = BatchNormF32();
+    scale_ = s_out;
+    zero_point_ = (u8_t)zp_out;
+    qparams_overridden_ = true;
+    install();
+  }
+  Tensor<float> forward_f32(Tensor<float>& x) {
+    batch_norm_pixels(x, channels_);
+    if (!dev_.gamma) dev_ = BatchNormF32{upload_f32(gamma_), upload_f32(beta_), upload_f32(mean_), upload_f32(var_)};
+    Tensor<float> out = batch_norm_f32(x, dev_, channels_, eps_);
+    maybe_sample(out);
+    return out;
+  }
+  Tensor<u8_t> forward_u8(Tensor<u8_t>& x) {
+    batch_norm_pixels(x, channels_);
+    if (!is_quantized_) throw std::runtime_error("i8ie: BatchNorm2d is not converted (call convert() first)");
+    return batch_norm_u8(x, g_dev_, b_dev_, channels_, scale_, zero_point_);
+  }
+  static py::array_t<float> array_of(const std::vector<float>& v) { return py::array_t<float>((ssize_t)v.size(), v.data()); }
+  py::array_t<float> weight() const { return array_of(gamma_); }
+  py::array_t<float> bias() const { return array_of(beta_); }
+  py::array_t<float> running_mean() const { return array_of(mean_); }
+  py::array_t<float> running_var() const { return array_of(var_); }
+  ssize_t num_features() const { return channels_; }
+  float eps() const { return eps_; }
+
+ protected:
+  void output_qparams_changed() override {
+    if (is_quantized_) install();
+  }
+
+ private:
+  void params_changed() {
+    dev_ = BatchNormF32();
+    if (is_quantized_) install();
+  }
+  void install() {
+    if (!(scale_ > 0) || !std::isfinite(scale_)) throw std::runtime_error("i8ie: BatchNorm2d: the output scale must be positive and finite");
+    std::tie(g_dev_, b_dev_) = batch_norm_affine(gamma_, beta_, mean_, var_, eps_, scale_, zero_point_);
+    set_quantized();
+  }
+  ssize_t channels_;
+  float eps_;
+  std::vector<float> gamma_, beta_, mean_, var_;
+  BatchNormF32 dev_;                        // FP32 path
+  std::shared_ptr<Storage> g_dev_, b_dev_;  // after convert()
+};
 template <typename L>
 void bind_weightless_state(py::class_<L>& c) {
   bind_quant_state(c);
@@ -373,6 +449,26 @@ void bind_weightless_layers(py::module_& m) {
         .def("num_groups", &GroupNorm::num_groups)
         .def("channels", &GroupNorm::channels)
         .def("eps", &GroupNorm::eps);
+  }
+  {
+    py::class_<BatchNorm2d> c(m, "_BatchNorm2d");  // (private to the i8ie package: see _batch_norm in ops.cc)
+    bind_quant_state(c);
+    c.def(py::init<ssize_t, float>(), py::arg("num_features"), py::arg("eps") = 1e-5f)
+        .def("load_weight", &BatchNorm2d::load_weight)
+        .def("load_bias", &BatchNorm2d::load_bias)
+        .def("load_running_mean", &BatchNorm2d::load_running_mean)
+        .def("load_running_var", &BatchNorm2d::load_running_var)
+        .def("__call__", &BatchNorm2d::forward_f32)
+        .def("__call__", &BatchNorm2d::forward_u8)
+        .def("load_quantized", &BatchNorm2d::load_quantized, py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+             py::arg("running_var"), py::arg("out_scale"), py::arg("out_zero_point"))
+        .def("weight", &BatchNorm2d::weight)
+        .def("bias", &BatchNorm2d::bias)
+        .def("running_mean", &BatchNorm2d::running_mean)
+        .def("running_var", &BatchNorm2d::running_var)
+        .def("num_features", &BatchNorm2d::num_features)
+        .def("eps", &BatchNorm2d::eps)
+        .def("_is_preparing", &BatchNorm2d::is_preparing);
   }
 }
 

@@ -390,6 +390,28 @@ void bind_ops(py::module_& m) {
     auto gb = layer_norm_affine(layer_norm_param(w, c, 1.0f, "weight"), layer_norm_param(b, c, 0.0f, "bias"), scale, zp);
     return group_norm_u8(x, gb.first, gb.second, groups, c, eps, scale, zp);
   }, py::arg("x"), py::arg("num_groups"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("scale"), py::arg("zero_point"));
+  // additive: inference BatchNorm of [n, c, h, w] or [n, c] with the stored running statistics (include/i8ie_hip.h,
+  // i8ie_batchnorm_u8_nhwc); weight / bias: float32 [c] or None (ones / zeros); the affine is computed and uploaded per call.
+  // Private like _group_norm (tests/golden/binding_surface.json stays as it is): the i8ie package exposes it as i8ie.batch_norm
+  m.def("_batch_norm", [](Tensor<float>& x, const py::object& mean, const py::object& var, const py::object& w, const py::object& b, float eps) {
+    if (x.shape.size() != 2 && x.shape.size() != 4) throw std::runtime_error("i8ie: batch_norm expects [n, c, h, w] or [n, c]");
+    const ssize_t c = x.shape[1];
+    batch_norm_pixels(x, c);
+    return batch_norm_f32(x, BatchNormF32{upload_f32(layer_norm_param(w, c, 1.0f, "weight")), upload_f32(layer_norm_param(b, c, 0.0f, "bias")),
+                                          upload_f32(layer_norm_param(mean, c, 0.0f, "running_mean")),
+                                          upload_f32(layer_norm_param(var, c, 1.0f, "running_var"))}, c, eps);
+  }, py::arg("x"), py::arg("running_mean"), py::arg("running_var"), py::arg("weight"), py::arg("bias"), py::arg("eps"));
+  m.def("_batch_norm", [](Tensor<u8_t>& x, const py::object& mean, const py::object& var, const py::object& w, const py::object& b, float eps,
+                          float scale, int zp) {
+    check_out_qparams("batch_norm", scale, zp);
+    if (x.shape.size() != 2 && x.shape.size() != 4) throw std::runtime_error("i8ie: batch_norm expects [n, c, h, w] or [n, c]");
+    const ssize_t c = x.shape[1];
+    batch_norm_pixels(x, c);
+    auto gb = batch_norm_affine(layer_norm_param(w, c, 1.0f, "weight"), layer_norm_param(b, c, 0.0f, "bias"),
+                                layer_norm_param(mean, c, 0.0f, "running_mean"), layer_norm_param(var, c, 1.0f, "running_var"), eps, scale, zp);
+    return batch_norm_u8(x, gb.first, gb.second, c, scale, zp);
+  }, py::arg("x"), py::arg("running_mean"), py::arg("running_var"), py::arg("weight"), py::arg("bias"), py::arg("eps"), py::arg("scale"),
+     py::arg("zero_point"));
   // additive: cat along axis 1 of up to 8 tensors, a copy in FP32; the quantized concat of include/i8ie_hip.h on u8 tensors
   m.def("cat", [](const py::list& tensors) { return cat_f32(cat_list<float>(tensors)); }, py::arg("tensors"));
   m.def("cat", [](const py::list& tensors, float scale, int zp) { return cat_u8(cat_list<u8_t>(tensors), scale, zp); },

@@ -126,6 +126,18 @@ int64_t group_norm_pixels(const Tensor<T>& x, ssize_t groups, ssize_t channels) 
     throw std::runtime_error("i8ie: group_norm: a group of one image has more than 65536 values");
   return hw;
 }
+// ---- batch_norm (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_batchnorm_u8_nhwc) ----------------
+// [n, c, h, w] or [n, c], normalised per channel with the stored statistics: the pixels per image, or a RuntimeError (before
+// any device call)
+template <typename T>
+int64_t batch_norm_pixels(const Tensor<T>& x, ssize_t channels) {
+  const size_t r = x.shape.size();
+  if (x.size <= 0 || (r != 2 && r != 4)) throw std::runtime_error("i8ie: batch_norm expects [n, c, h, w] or [n, c]");
+  if (channels < 1 || channels > 16384) throw std::runtime_error("i8ie: batch_norm: channels must be in 1..16384");
+  if (x.shape[1] != channels)
+    throw std::runtime_error("i8ie: batch_norm: the tensor has " + std::to_string(x.shape[1]) + " channels, the layer " + std::to_string(channels));
+  return r == 4 ? (int64_t)(x.shape[2] * x.shape[3]) : 1;
+}
 // ---- cat (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_concat_u8) --------------------------
 // axis 1 of k rank-4 [n, c_i, h, w] or k rank-2 [m, f_i] tensors: the result's shape, or a RuntimeError (before any device call)
 template <typename T>
@@ -180,6 +192,16 @@ Tensor<float> group_norm_f32(Tensor<float>& x, const std::shared_ptr<Storage>& g
                              ssize_t channels, float eps);
 Tensor<u8_t> group_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, const std::shared_ptr<Storage>& b, ssize_t groups,
                            ssize_t channels, float eps, float scale, int zp);
+// the four device arrays gamma, beta, mean, var of the FP32 form
+struct BatchNormF32 {
+  std::shared_ptr<Storage> gamma, beta, mean, var;
+};
+Tensor<float> batch_norm_f32(Tensor<float>& x, const BatchNormF32& p, ssize_t channels, float eps);
+Tensor<u8_t> batch_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, const std::shared_ptr<Storage>& b, ssize_t channels, float scale,
+                           int zp);
+std::pair<std::shared_ptr<Storage>, std::shared_ptr<Storage>> batch_norm_affine(const std::vector<float>& gamma, const std::vector<float>& beta,
+                                                                                 const std::vector<float>& mean, const std::vector<float>& var,
+                                                                                 float eps, float scale, int zp);
 Tensor<float> activation_f32(Tensor<float>& in, int kind, float param);
 Tensor<u8_t> activation_u8(Tensor<u8_t>& in, int kind, float param, float scale, int zp);
 void bind_ops(py::module_& m);

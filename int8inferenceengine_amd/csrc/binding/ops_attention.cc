@@ -314,6 +314,60 @@ Tensor<u8_t> group_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, 
         return st;
       });
 }
+Tensor<float> batch_norm_f32(Tensor<float>& x, const BatchNormF32& p, ssize_t channels, float eps) {
+  const int64_t hw = batch_norm_pixels(x, channels);
+  if (!(eps > 0) || !std::isfinite(eps)) throw std::runtime_error("i8ie: batch_norm: eps must be positive and finite");
+  Tensor<float> out(x.shape);
+  check(i8ie_batchnorm_f32(ctx(), x.dptr(), out.dptr(), (int64_t)x.shape[0] * hw, (int)channels, hw, (const float*)p.gamma->dev,
+                           (const float*)p.beta->dev, (const float*)p.mean->dev, (const float*)p.var->dev, eps));
+  return out;
+}
+// g, b: the device arrays of i8ie_batchnorm_affine for (scale, zp), kept alive by the recorded launch
+Tensor<u8_t> batch_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, const std::shared_ptr<Storage>& b, ssize_t channels, float scale,
+                           int zp) {
+  check_out_qparams("batch_norm", scale, zp);
+  need_contents(in);
+  const int64_t hw = batch_norm_pixels(in, channels);
+  if (!std::isfinite(in.scale) || !std::isfinite(255.0f * in.scale)) throw std::runtime_error("i8ie: batch_norm: the input scale must be finite");
+  const std::vector<ssize_t> shp = in.shape;
+  const float s_in = in.scale;
+  const u8_t zp_i = in.zero_point, zp_o = (u8_t)zp;
+  const int C = (int)channels;
+  // deferred like layer_norm's result: relu(bn(..)) is one launch, a consuming conv gets its zero-point border and, where it
+  // reads them, re-biased bytes straight from the kernel, and several consumers share one launch (PendNode)
+  return deferred_one_input(
+      in, shp, scale, zp_o, [g, b, shp, hw, s_in, zp_i, zp_o, C](std::shared_ptr<Storage> si, bool relu, int border, bool s8) {
+        const int64_t n = (int64_t)shp[0];
+        std::shared_ptr<Storage> st;
+        if (shp.size() == 4) {
+          // (a view whose storage is NHWC under other logical dims goes back to the reference's order: the view is defined on it)
+          if (si->layout == I8IE_LAYOUT_NHWC && (si->dn != shp[0] || si->dc != shp[1] || si->dh != shp[2] || si->dw != shp[3])) si->to_nchw();
+          if (si->layout == I8IE_LAYOUT_NHWC) {
+            st = nhwc_storage(shp, border, zp_o, s8);
+            check(i8ie_batchnorm_u8_nhwc(ctx(), (const uint8_t*)si->device_ptr(), si->border, si->s8 ? 1 : 0, (uint8_t*)st->dev, st->border,
+                                         st->s8 ? 1 : 0, (int)n, C, (int)shp[2], (int)shp[3], (const float*)g->dev, (const float*)b->dev, s_in,
+                                         zp_i, relu ? 1 : 0, zp_o));
+            return st;
+          }
+        } else {  // [n, c] rows (a flattened NHWC activation of one pixel per image is in that order already)
+          if (si->layout == I8IE_LAYOUT_NHWC && si->dh * si->dw == 1 && si->border == 0) si->unbias();
+          else si->to_nchw();
+        }
+        // reference order (a user-made tensor, an im2col-route conv's result, rows): the flat entry, no layout conversion
+        st = device_storage((size_t)(n * C * hw));
+        check(i8ie_batchnorm_u8(ctx(), (const uint8_t*)si->device_ptr(), (uint8_t*)st->dev, n * hw, C, hw, (const float*)g->dev,
+                                (const float*)b->dev, s_in, zp_i, relu ? 1 : 0, zp_o));
+        return st;
+      });
+}
+// (g, b) of i8ie_batchnorm_affine on the device
+std::pair<std::shared_ptr<Storage>, std::shared_ptr<Storage>> batch_norm_affine(const std::vector<float>& gamma, const std::vector<float>& beta,
+                                                                                 const std::vector<float>& mean, const std::vector<float>& var,
+                                                                                 float eps, float scale, int zp) {
+  std::vector<float> g(gamma.size()), b(gamma.size());
+  check(i8ie_batchnorm_affine(gamma.data(), beta.data(), mean.data(), var.data(), (int)gamma.size(), eps, scale, (uint8_t)zp, g.data(), b.data()));
+  return {upload_f32(g), upload_f32(b)};
+}
 std::vector<float> layer_norm_param(const py::object& a, ssize_t channels, float fill, const char* what) {
   if (a.is_none()) return std::vector<float>((size_t)channels, fill);
   F32Array v = F32Array::ensure(a);

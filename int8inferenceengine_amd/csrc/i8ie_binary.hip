@@ -183,16 +183,8 @@ __global__ __launch_bounds__(kThreads) void bin_f32_kernel(const float* a, const
 }
 
 // ---- Mul's gate form: a and out as above, the gate [n][1 + 2b][1 + 2b][c] (plain rows [n][c] at b = 0)
-struct MulGate {
+struct MulGate : PixelWalk {  // (the walk: i8ie_pointwise.h)
   int64_t g_img, g_org;    // the gate: bytes per image, offset of its one pixel
-  int64_t units;           // n * chunks * tiles
-  int cpv;                 // items per pixel: c / VEC
-  int lanes_c, rows;       // a block's shape: lanes_c = min(cpv, 256) items by rows = 256 / lanes_c pixels
-  int chunks, tiles;       // channel chunks of lanes_c items per pixel; tiles of rows * kWalk pixels per image
-  int hw, w, c;
-  int step_x;              // rows % w: how far a lane's column moves per step (its row moves by rows / w, +1 where the column wraps)
-  int64_t a_step, a_wrap;  // ... and its byte offset in a: rows / w physical rows + step_x pixels; the extra 2 * border pixels of a wrap
-  int64_t o_step, o_wrap;
 };
 
 // four elements against four gate values: h4 = fl(fb * r) of the four channels (estimate), g4 their plain bytes (replay)
@@ -315,22 +307,8 @@ void launch_gate(i8ie_ctx* ctx, const uint8_t* a, const NhwcGeom& ga, const uint
   const NhwcGeom gg = buf_geom(c, 1, 1, g_border);
   t.g_img = gg.img;
   t.g_org = gg.org;
-  t.cpv = c / VEC;
-  t.lanes_c = t.cpv < kThreads ? t.cpv : kThreads;
-  t.rows = kThreads / t.lanes_c;
-  t.chunks = (t.cpv + t.lanes_c - 1) / t.lanes_c;
-  t.hw = h * w;
-  t.w = w;
-  t.c = c;
-  t.tiles = (t.hw + t.rows * kWalk - 1) / (t.rows * kWalk);
-  t.units = (int64_t)n * t.chunks * t.tiles;
-  const int step_y = t.rows / w;
-  t.step_x = t.rows % w;
-  t.a_step = step_y * ga.row + (int64_t)t.step_x * c;
-  t.a_wrap = ga.row - (int64_t)w * c;
-  t.o_step = step_y * go.row + (int64_t)t.step_x * c;
-  t.o_wrap = go.row - (int64_t)w * c;
-  const int blocks = (int)(t.units > kMaxBlocks ? kMaxBlocks : t.units);
+  pixel_walk_init(t, VEC, kWalk, n, c, h, w, ga, go);
+  const int blocks = pixel_walk_blocks(t);
   mul_u8_gate_kernel<VEC><<<blocks, kThreads, 0, ctx->stream>>>(a, ga, g, out, go, t, p);
 }
 

@@ -1,5 +1,5 @@
 // i8ie_pointwise.h -- helpers the pointwise units share (i8ie_elementwise, i8ie_binary, i8ie_concat, i8ie_lut, i8ie_avgpool).
-// Host: the launch constants and grid rule, the alignment test and the item width it allows, i8ie_requant.h's "ordinary scale"
+// Host: the launch constants and grid rule, the alignment test and the item width it allows, the pixel walk of the kernels that keep per-channel values in registers, i8ie_requant.h's "ordinary scale"
 // rule, the three-scale argument check of the two-operand ops and the geometry of a bordered NHWC buffer.  Device: the walk of
 // a bordered NHWC buffer by row items.  Everything here has internal linkage (an unnamed namespace per including unit): no
 // call crosses a translation unit through this header.  i8ie_gconv.hip and i8ie_deconv.hip include it for aligned_to alone.
@@ -54,6 +54,40 @@ inline NhwcGeom buf_geom(int c, int h, int w, int border) {
   g.org = (int64_t)border * g.row + (int64_t)border * c;
   return g;
 }
+
+// The pixel walk of the kernels that keep per-channel values in registers (Mul's gate form, i8ie_binary.hip; the BatchNorm,
+// i8ie_batchnorm.hip).  An item is VEC bytes of one pixel's channels.  A block holds `rows` whole pixels of `lanes_c` items each
+// (rows * lanes_c <= kThreads; consecutive lanes take consecutive channel items of one pixel, then the next pixel, so a wave's
+// accesses are contiguous), and every lane walks `walk` pixels of one image, `rows` pixels apart: its channel item never changes.
+// Blocks stride over (image, channel chunk, pixel tile) units up to kMaxBlocks.  a: the buffer read, o: the buffer written.
+struct PixelWalk {
+  int64_t units;           // n * chunks * tiles
+  int cpv;                 // items per pixel: c / VEC
+  int lanes_c, rows;       // a block's shape: lanes_c = min(cpv, 256) items by rows = 256 / lanes_c pixels
+  int chunks, tiles;       // channel chunks of lanes_c items per pixel; tiles of rows * walk pixels per image
+  int hw, w, c;
+  int step_x;              // rows % w: how far a lane's column moves per step (its row moves by rows / w, +1 where the column wraps)
+  int64_t a_step, a_wrap;  // ... and its byte offset in a: rows / w physical rows + step_x pixels; the extra 2 * border pixels of a wrap
+  int64_t o_step, o_wrap;
+};
+inline void pixel_walk_init(PixelWalk& t, int vec, int walk, int n, int c, int h, int w, const NhwcGeom& ga, const NhwcGeom& go) {
+  t.cpv = c / vec;
+  t.lanes_c = t.cpv < kThreads ? t.cpv : kThreads;
+  t.rows = kThreads / t.lanes_c;
+  t.chunks = (t.cpv + t.lanes_c - 1) / t.lanes_c;
+  t.hw = h * w;
+  t.w = w;
+  t.c = c;
+  t.tiles = (t.hw + t.rows * walk - 1) / (t.rows * walk);
+  t.units = (int64_t)n * t.chunks * t.tiles;
+  const int step_y = t.rows / w;
+  t.step_x = t.rows % w;
+  t.a_step = step_y * ga.row + (int64_t)t.step_x * c;
+  t.a_wrap = ga.row - (int64_t)w * c;
+  t.o_step = step_y * go.row + (int64_t)t.step_x * c;
+  t.o_wrap = go.row - (int64_t)w * c;
+}
+inline int pixel_walk_blocks(const PixelWalk& t) { return (int)(t.units > kMaxBlocks ? kMaxBlocks : t.units); }
 
 #if defined(__HIPCC__)
 // The interior of a bordered NHWC buffer walked by row items.  The w * c interior bytes of an image row are the contiguous

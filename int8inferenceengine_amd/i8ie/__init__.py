@@ -9,7 +9,7 @@ import numbers
 
 import _CXX_i8ie as _C
 
-from .layer import Activation, Add, Attention, Concat, Conv2d, ConvTranspose2d, GroupNorm, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind
+from .layer import Activation, Add, Attention, BatchNorm2d, Concat, Conv2d, ConvTranspose2d, GroupNorm, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind, fold_batchnorm
 from .module import Module
 from .tensor import Tensor
 
@@ -19,7 +19,7 @@ FullyConnected = Linear  # BASELINE.json's name for the same class (no such symb
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
-    "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "GroupNorm", "group_norm", "Attention", "attention",
+    "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "GroupNorm", "group_norm", "BatchNorm2d", "batch_norm", "fold_batchnorm", "Attention", "attention",
     "narrow", "split", "chunk", "channel_shuffle", "pixel_shuffle", "pixel_unshuffle",
     "synchronize", "set_device", "pinned_empty", "from_torch",
 ]
@@ -178,6 +178,23 @@ def group_norm(x, num_groups, weight=None, bias=None, eps=1e-5, scale=None, zero
     if scale is not None or zero_point is not None:
         raise TypeError("group_norm of an FP32 tensor takes no scale / zero_point")
     return Tensor(_C._group_norm(x.data, int(num_groups), weight, bias, float(eps)))
+
+
+def batch_norm(x, running_mean, running_var, weight=None, bias=None, eps=1e-5, scale=None, zero_point=None):
+    """Inference BatchNorm of [n, c, h, w] or [n, c] per channel with the given statistics (torch.nn.functional.batch_norm with
+    training=False; anything else raises RuntimeError).  `running_mean` / `running_var` / `weight` / `bias`: float32 arrays of
+    c values; None is zeros / ones / ones / zeros.  FP32 tensors: the fp32 sequence of include/i8ie_hip.h (i8ie_batchnorm_f32),
+    `scale` / `zero_point` must not be given.  uint8 tensors: the quantized BatchNorm (i8ie_batchnorm_u8_nhwc); the result's
+    `scale` and `zero_point` are required, and the per-channel affine (i8ie_batchnorm_affine) is computed and uploaded at every
+    call.  `i8ie.BatchNorm2d` is the calibrated form for use inside a Module (it uploads the affine once, at convert())."""
+    quantized = type(x.data).__name__ == "6TensorIhE"
+    if quantized:
+        if scale is None or zero_point is None:
+            raise TypeError("batch_norm of a uint8 tensor needs the result's scale and zero_point")
+        return Tensor(_C._batch_norm(x.data, running_mean, running_var, weight, bias, float(eps), float(scale), int(zero_point)))
+    if scale is not None or zero_point is not None:
+        raise TypeError("batch_norm of an FP32 tensor takes no scale / zero_point")
+    return Tensor(_C._batch_norm(x.data, running_mean, running_var, weight, bias, float(eps)))
 
 
 def cat(tensors, scale=None, zero_point=None):

@@ -167,6 +167,108 @@ class GroupNorm(Norm):
         self.layer = _C._GroupNorm(self.num_groups, self.num_channels, self.eps)
 
 
+class BatchNorm2d(Norm):
+    """Inference BatchNorm `y = self.bn1(x)` (additive, not in the reference): torch.nn.BatchNorm2d in eval mode, a layer with
+    fp32 `weight` (gamma, default ones), `bias` (beta, default zeros), `running_mean` (default zeros) and `running_var`
+    (default ones) of `num_features` values each, and no INT8 weights.  There is no momentum, no training mode and no
+    track_running_stats: the statistics are the stored ones.
+
+    [n, c, h, w] (c == num_features) is normalised per channel; [n, c] as well (torch's BatchNorm1d on rows); any other shape
+    raises RuntimeError.  1 <= num_features <= 16384.  FP32 tensors go through the fp32 sequence of include/i8ie_hip.h
+    (i8ie_batchnorm_f32; sampled by the calibrator while preparing); uint8 tensors, after convert(), through
+    i8ie_batchnorm_u8_nhwc with this layer's output (scale, zero_point).  Module.load() takes `<attr>.weight`, `.bias`,
+    `.running_mean` and `.running_var`; quantized_state_dict() keeps the four as float32 beside `<attr>.qparams`.
+
+    `i8ie.fold_batchnorm(layer, bn)` folds it into the Conv2d, Linear or ConvTranspose2d in front of it.  A folded BatchNorm is
+    the identity: `bn(x)` returns `x` itself (no launch, nothing sampled), prepare() and convert() do nothing,
+    quantized_state_dict() writes no key for it, and loading a parameter into it raises RuntimeError (so a Module.load() of a
+    state dict that holds its keys is refused after the fold: load first, then fold)."""
+
+    def __init__(self, num_features, eps=1e-5):
+        self.num_features, self.eps = int(num_features), float(eps)
+        self.layer = _C._BatchNorm2d(self.num_features, self.eps)
+        self._folded = False
+
+    def __call__(self, x):
+        if self._folded:
+            return x
+        return Tensor(self.layer(x.data))
+
+    def is_folded(self):
+        return self._folded
+
+    def _not_folded(self, what):
+        if self._folded:
+            raise RuntimeError("i8ie: BatchNorm2d: %s after the fold (the parameters are inside the neighbouring layer's weights)" % what)
+
+    def load_weight(self, weight):
+        self._not_folded("load_weight")
+        self.layer.load_weight(weight)
+
+    def load_bias(self, bias):
+        self._not_folded("load_bias")
+        self.layer.load_bias(bias)
+
+    def load_running_mean(self, mean):
+        self._not_folded("load_running_mean")
+        self.layer.load_running_mean(mean)
+
+    def load_running_var(self, var):
+        self._not_folded("load_running_var")
+        self.layer.load_running_var(var)
+
+    def running_mean(self):
+        return self.layer.running_mean()
+
+    def running_var(self):
+        return self.layer.running_var()
+
+    def prepare(self):
+        if not self._folded:
+            self.layer.prepare()
+
+    def convert(self, per_channel=False):
+        """per_channel is accepted and ignored: there are no INT8 weights.  A folded BatchNorm stays as it is."""
+        if not self._folded:
+            self.layer.convert()
+
+
+def fold_batchnorm(layer, bn):
+    """Fold the BatchNorm2d `bn` into the Conv2d (any groups, dilation or rectangular geometry), Linear or ConvTranspose2d
+    `layer` whose output it normalises, in FP32 and before prepare().  With k[o] = gamma[o] / sqrt(var[o] + eps) in double:
+        W'[o, ...] = (float)((double)W[o, ...] * k[o])
+        b'[o]      = (float)(((double)b[o] - (double)mean[o]) * k[o] + (double)beta[o])
+    (for ConvTranspose2d the output feature is axis 1 of torch's [in, out, k, k]).  W' and b' are loaded into `layer`, and `bn`
+    becomes the identity (BatchNorm2d.is_folded()).  RuntimeError if either object is preparing, is converted or `bn` is already
+    folded, and if the layer's output feature count is not bn.num_features; TypeError for any other layer class.  The fold is
+    one-way: load_weight / load_bias on `layer` afterwards replace the folded parameters like any others."""
+    import numpy as np
+
+    if not isinstance(bn, BatchNorm2d):
+        raise TypeError("fold_batchnorm: the second argument must be a BatchNorm2d, got %s" % type(bn).__name__)
+    if not isinstance(layer, (Conv2d, Linear, ConvTranspose2d)):
+        raise TypeError("fold_batchnorm: the first argument must be a Conv2d, a Linear or a ConvTranspose2d, got %s" % type(layer).__name__)
+    if bn.is_folded():
+        raise RuntimeError("fold_batchnorm: the BatchNorm2d is already folded")
+    for what, obj in (("layer", layer), ("BatchNorm2d", bn)):
+        if obj.layer.is_quantized():
+            raise RuntimeError("fold_batchnorm: the %s is already converted" % what)
+        if obj.layer._is_preparing():
+            raise RuntimeError("fold_batchnorm: the %s is preparing (fold before prepare())" % what)
+    w, b = np.asarray(layer.layer._weight(), np.float32), np.asarray(layer.layer._bias(), np.float32)
+    axis = 1 if isinstance(layer, ConvTranspose2d) else 0
+    if w.shape[axis] != bn.num_features or b.shape != (bn.num_features,):
+        raise RuntimeError("fold_batchnorm: the layer has %d output features, the BatchNorm2d %d" % (w.shape[axis], bn.num_features))
+    f64 = np.float64
+    k = np.asarray(bn.layer.weight(), np.float32).astype(f64) / np.sqrt(np.asarray(bn.running_var(), np.float32).astype(f64) + f64(np.float32(bn.eps)))
+    shape = [1] * w.ndim
+    shape[axis] = -1
+    layer.load_weight((w.astype(f64) * k.reshape(shape)).astype(np.float32))
+    layer.load_bias(((b.astype(f64) - np.asarray(bn.running_mean(), np.float32).astype(f64)) * k
+                     + np.asarray(bn.layer.bias(), np.float32).astype(f64)).astype(np.float32))
+    bn._folded = True
+
+
 class Weightless(Layer):
     """Common behaviour of the layers without weights (Add, Mul, Concat, Activation): `self.layer` has only the prepare / convert state
     machine around an output (scale, zero_point).  Takes part in Module.prepare() / convert() / quantized_state_dict()
