@@ -211,6 +211,61 @@ int i8ie_maxpool2d_s8(i8ie_ctx* ctx, const int8_t* in_dev, int8_t* out_dev, int 
  * (golden-pinned, tests/golden/ref_calibrator*.npz) stays in _CXX_i8ie for seeded runs. */
 int i8ie_calib_sample_f32(i8ie_ctx* ctx, const float* data_dev, int64_t n, int64_t seen_before, uint64_t seed,
                           float* samples_dev, int* scratch_dev);
+
+/* ---- Histogram calibration (additive, not in the reference) ----------------
+ * A second observer beside the 1000-slot reservoir above: it sees EVERY value of a layer's FP32 output.  Over all finite
+ * values observed so far it keeps the exact `min` and `max`, a count of the non-finite values (NaN, +-Inf: counted, otherwise
+ * ignored), B = 2048 counters of 64 bits and one integer exponent e.  A value with |x| < 2^-126 (a denormal, +-0) counts as
+ * +0, for the minimum and maximum too, whatever the device's flush mode.
+ *   bins      bin i covers [(i - 1024) * 2^e, (i - 1023) * 2^e); a finite x falls in bin floor(x * 2^-e) + 1024, the floor of
+ *             the exact product (it does not depend on rounding mode, FMA contraction or summation order).
+ *   exponent  e is the smallest integer >= -100 with absmax < 1024 * 2^e, strictly, over everything seen so far.  When a
+ *             later tensor raises absmax, e grows by d and the histogram is folded d times: old bin i goes to
+ *             512 + floor(i / 2), counts add.  The state is therefore a function of the multiset of values alone: not of the
+ *             chunking, the order of the chunks or the order of the atomics.
+ * The state is one caller-owned device buffer of i8ie_calib_hist_state_bytes() bytes, 16-byte aligned: this header, then
+ * uint64_t hist[2048].  At rest (between calls) `scratch` is zero; a state that was never observed has min = +Inf,
+ * max = -Inf, exponent = -100 and zero counters (i8ie_calib_hist_reset). */
+#define I8IE_CALIB_HIST_BINS 2048
+typedef struct i8ie_calib_hist_header {
+  float min, max;      /* of the finite values seen; +Inf / -Inf while there were none */
+  int32_t exponent;    /* e */
+  uint32_t scratch[3]; /* of an observe in flight (the chunk's minimum and maximum as ordered keys, a block ticket); 0 at rest */
+  uint64_t nonfinite;  /* NaN and +-Inf seen */
+} i8ie_calib_hist_header;
+size_t i8ie_calib_hist_state_bytes(void);
+int i8ie_calib_hist_reset(i8ie_ctx* ctx, void* state_dev);
+/* Observe n floats (n >= 0; data_dev aligned to 4 bytes, any offset from a 16-byte boundary).  Asynchronous on the ctx stream,
+ * never synchronises with the host: the exponent lives on the device.  Two launches (three above 2^30 values, one more per
+ * 2^30): "calib_hist_stats" takes min / max / absmax / the non-finite count, and its last block computes the new e and folds the
+ * counters in place when e grew; "calib_hist_count" reads e from the state and counts in LDS (32-bit LDS atomics, one table
+ * per wave), then adds the non-zero counters to the 64-bit global ones.  n == 0 launches nothing. */
+int i8ie_calib_hist_observe_f32(i8ie_ctx* ctx, const float* data_dev, int64_t n, void* state_dev);
+/* The state, read back once (synchronises the ctx stream): the header and the 2048 counters. */
+int i8ie_calib_hist_read(i8ie_ctx* ctx, const void* state_dev, i8ie_calib_hist_header* header, uint64_t* hist_host);
+/* Host only.  The last step of Calibrator::get_range (src/calibrator.cc:31-36), from `out_min = fmin(...)` on: the range is
+ * widened to include 0, zero_point = (u8)(255 * (0 - min) / (max - min + 1e-09)) in double, scale = (max - min) / 255 when
+ * zero_point == 0 and (0 - min) / zero_point otherwise in float, and a scale of 0 becomes 1.  Shared by the reservoir and by
+ * every method below. */
+void i8ie_calib_range_qparams(float out_min, float out_max, float* scale, uint8_t* zero_point);
+/* Host only, no ctx.  (lo, hi) of a state read back; (scale, zero_point) is i8ie_calib_range_qparams(lo, hi).  With T the
+ * total count:
+ *   I8IE_CALIB_MINMAX      lo = min, hi = max.
+ *   I8IE_CALIB_PERCENTILE  param = p, 50 < p <= 100 (I8IE_ERR_ARG otherwise); k = floor((1 - p / 100) * T) in double.  lo is the
+ *                          lower edge of the first bin at which the ascending cumulative count exceeds k, but not below min;
+ *                          hi the upper edge of the first bin at which the descending cumulative count exceeds k, but not
+ *                          above max.  p = 100 is MINMAX exactly.
+ *   I8IE_CALIB_MSE         (lo0, hi0) = (fmin(min, 0), fmax(max, 0)).  Candidate j = 16..64 is (float(lo0 * j / 64),
+ *                          float(hi0 * j / 64)) (the product and quotient in double) with its (s_j, z_j); its error is
+ *                          E_j = sum_i h_i * (c_i - d_j(c_i))^2 over the bins in ascending i, accumulated sequentially in double
+ *                          without contraction, c_i = (i - 1023.5) * 2^e, d_j(c) = (q - z_j) * s_j, q = min(255, max(0,
+ *                          trunc(c / s_j + z_j))): down_scale's clamp and truncation in double.  The smallest E_j wins, ties
+ *                          go to the larger j.
+ * A state that saw no finite value gives (0, 0), hence (scale, zero_point) = (1, 0), as an empty reservoir does. */
+enum { I8IE_CALIB_MINMAX = 0, I8IE_CALIB_PERCENTILE = 1, I8IE_CALIB_MSE = 2 };
+int i8ie_calib_hist_range(const i8ie_calib_hist_header* header, const uint64_t* hist, int method, double param, float* lo,
+                          float* hi);
+
 /* down_scale  src/quantize_utils.cc:27-36 (standalone requantiser; the layers fuse it) */
 int i8ie_down_scale(i8ie_ctx* ctx, const int32_t* acc_dev, uint8_t* out_dev, int64_t n, float sa,
                     float sb, float sc, uint8_t zp_c);

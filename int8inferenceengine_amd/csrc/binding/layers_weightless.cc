@@ -67,7 +67,7 @@ class Attention : public Weightless {
     if (heads < 1) throw std::runtime_error("i8ie: Attention: heads must be >= 1");
   }
   void prepare() {
-    if (!is_quantized_) score_cal_ = std::make_unique<Calibrator>();
+    if (!is_quantized_) score_cal_ = std::make_unique<Calibrator>(rt().calib_histogram);
     QuantState::prepare();
   }
   void convert(bool /*per_channel: there are no weights*/ = false) {
@@ -89,6 +89,8 @@ class Attention : public Weightless {
     score_zp_ = (u8_t)zp;
     score_overridden_ = true;
   }
+  py::dict score_calib_histogram() { return histogram_dict(score_cal_.get(), is_preparing_); }
+  py::tuple score_calib_range(const std::string& method, double param) { return histogram_range_tuple(score_cal_.get(), is_preparing_, method, param); }
   std::tuple<float, int> score_qparams() const { return std::make_tuple(score_scale_, (int)score_zp_); }
   void load_quantized(float s_out, int zp_out, float s_score, int zp_score) {  // what convert() would have left behind
     set_score_qparams(s_score, zp_score);
@@ -401,6 +403,8 @@ void bind_weightless_layers(py::module_& m) {
     c.def(py::init<ssize_t>(), py::arg("heads"))
         .def("set_score_qparams", &Attention::set_score_qparams, py::arg("scale"), py::arg("zero_point"))
         .def("score_qparams", &Attention::score_qparams)
+        .def("_score_calib_histogram", &Attention::score_calib_histogram)
+        .def("_score_calib_range", &Attention::score_calib_range, py::arg("method"), py::arg("param") = 99.99)
         .def("load_quantized", &Attention::load_quantized, py::arg("out_scale"), py::arg("out_zero_point"), py::arg("score_scale"),
              py::arg("score_zero_point"))
         .def("heads", &Attention::heads)

@@ -35,6 +35,11 @@ struct Runtime {
   long calib_seed = -1;  // < 0: std::random_device, as the reference (src/calibrator.cc:9-10)
   int calib_mode = 0;    // 0 auto: seeded -> the reference's mt19937 stream replayed on the host (golden-pinned),
                          // unseeded -> sampled on the device (no D2H of the layer outputs); 1 host; 2 device
+  // the observer a prepare() gives its calibrator, and how a histogram becomes a range at convert() (include/i8ie_hip.h,
+  // "Histogram calibration"); calib_mode above belongs to the reservoir alone
+  bool calib_histogram = false;           // false: the reference's 1000-slot reservoir
+  int calib_method = I8IE_CALIB_MINMAX;   // I8IE_CALIB_*, read at convert()
+  double calib_param = 99.99;             // the percentile of I8IE_CALIB_PERCENTILE
 };
 Runtime& rt();  // one instance, intentionally leaked: outlives every tensor at exit
 inline void check(int rc) {

@@ -9,7 +9,8 @@ import numbers
 
 import _CXX_i8ie as _C
 
-from .layer import Activation, Add, Attention, BatchNorm2d, Concat, Conv2d, ConvTranspose2d, GroupNorm, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind, fold_batchnorm
+from .layer import CALIBRATION_METHODS, Activation, Add, Attention, BatchNorm2d, Concat, Conv2d, ConvTranspose2d, GroupNorm, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind, fold_batchnorm
+from .layer import calibration_percentile as _percentile
 from .module import Module
 from .tensor import Tensor
 
@@ -21,8 +22,14 @@ __all__ = [
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
     "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "GroupNorm", "group_norm", "BatchNorm2d", "batch_norm", "fold_batchnorm", "Attention", "attention",
     "narrow", "split", "chunk", "channel_shuffle", "pixel_shuffle", "pixel_unshuffle",
-    "synchronize", "set_device", "pinned_empty", "from_torch",
+    "synchronize", "set_device", "pinned_empty", "from_torch", "set_calibration", "calibration",
 ]
+
+
+def _calibration_args(method, percentile):
+    if method != "reservoir" and method not in CALIBRATION_METHODS:
+        raise ValueError("calibration method %r (one of reservoir, %s)" % (method, ", ".join(CALIBRATION_METHODS)))
+    return method, _percentile(percentile)
 
 
 def tensor(ndarray):
@@ -347,6 +354,27 @@ def pixel_unshuffle(x, downscale_factor):
     """torch's pixel_unshuffle, the inverse of pixel_shuffle: [n, c, h, w] -> [n, c r r, h / r, w / r], r an integer in 1..8
     that divides h and w.  Tensor types as pixel_shuffle."""
     return Tensor(_C._pixel_unshuffle(x.data, _integer("pixel_unshuffle", "downscale_factor", downscale_factor)))
+
+
+def set_calibration(method="reservoir", percentile=99.99):
+    """Choose the observer that `prepare()` gives every layer from now on, and how `convert()` turns it into an output (scale,
+    zero_point).  "reservoir" (the default) is the reference's calibrator: 1000 slots, random overwrites, the smallest and
+    largest slot.  The other three observe every value of a layer's FP32 output on the device in a 2048-bin histogram
+    (include/i8ie_hip.h, "Histogram calibration") and read it as
+        "minmax"      the exact minimum and maximum (also of an output of fewer than 1000 values),
+        "percentile"  the range that leaves floor((1 - percentile / 100) * count) values outside on either side,
+        "mse"         the fraction j / 64, j = 16..64, of the minmax range with the smallest quantisation error.
+    The observer is fixed at prepare(); the method and percentile are those in force at convert(), so one calibration pass may
+    be converted under any of the three.  set_output_qparams still overrides every observer.  ValueError for an unknown method
+    and for a percentile outside (50, 100]."""
+    method, percentile = _calibration_args(method, percentile)
+    _C._set_calibration(method, percentile)
+
+
+def calibration():
+    """The setting of set_calibration as {"method", "percentile"}."""
+    method, percentile = _C._calibration()
+    return {"method": method, "percentile": percentile}
 
 
 def synchronize():

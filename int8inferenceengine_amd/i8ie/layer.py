@@ -6,6 +6,28 @@ import _CXX_i8ie as _C
 from .tensor import Tensor
 
 
+CALIBRATION_METHODS = ("minmax", "percentile", "mse")  # the range methods of a histogram observer (i8ie.set_calibration)
+
+
+def calibration_percentile(percentile):
+    """`percentile` as a float; ValueError unless it lies in (50, 100]"""
+    p = float(percentile)
+    if not 50.0 < p <= 100.0:
+        raise ValueError("calibration: the percentile must lie in (50, 100], got %r" % (percentile,))
+    return p
+
+
+def _range_args(method, percentile):
+    if method not in CALIBRATION_METHODS:
+        raise ValueError("calibration_range: method %r (one of %s)" % (method, ", ".join(CALIBRATION_METHODS)))
+    return method, calibration_percentile(percentile)
+
+
+def _histogram(d):
+    return {"exponent": int(d["exponent"]), "counts": d["counts"], "min": float(d["min"]), "max": float(d["max"]),
+            "nonfinite": int(d["nonfinite"])}
+
+
 class Layer:
     """Common behaviour of Linear and Conv2d; `self.layer` is the extension object."""
 
@@ -39,6 +61,17 @@ class Layer:
 
     def output_qparams(self):
         return self.layer.output_qparams()
+
+    def calibration_histogram(self):
+        """The histogram this layer's observer holds right now: {"exponent": e, "counts": np.uint64[2048], "min", "max",
+        "nonfinite"} (include/i8ie_hip.h, "Histogram calibration"; min / max are +inf / -inf before the first finite value).
+        RuntimeError unless the layer is preparing and prepared under a histogram method of i8ie.set_calibration."""
+        return _histogram(self.layer._calib_histogram())
+
+    def calibration_range(self, method, percentile=99.99):
+        """(scale, zero_point, lo, hi) that `method` ("minmax", "percentile" or "mse") reads from the live histogram, without
+        converting: one calibration pass can compare the methods.  Errors as calibration_histogram and i8ie.set_calibration."""
+        return tuple(self.layer._calib_range(*_range_args(method, percentile)))
 
     def weight_scale(self):
         """The per-tensor weight scale (raises for a per-channel layer)."""
@@ -365,6 +398,14 @@ class Attention(Weightless):
 
     def set_score_qparams(self, scale, zero_point):
         self.layer.set_score_qparams(float(scale), int(zero_point))
+
+    def score_calibration_histogram(self):
+        """calibration_histogram() of the observer of the FP32 scores."""
+        return _histogram(self.layer._score_calib_histogram())
+
+    def score_calibration_range(self, method, percentile=99.99):
+        """calibration_range() of the observer of the FP32 scores."""
+        return tuple(self.layer._score_calib_range(*_range_args(method, percentile)))
 
 
 class Concat(Weightless):

@@ -918,19 +918,29 @@ def build(name):
     return SpecNet()
 
 
-def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, per_channel=False):
+def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, per_channel=False, calibration=None):
     """The reference workflow (notebook cells 'prepare -> one FP32 batch -> convert'); per_channel=True converts
-    with one weight scale per output feature (Module.convert)."""
+    with one weight scale per output feature (Module.convert).  calibration: None for the setting in force (the reservoir
+    unless i8ie.set_calibration chose otherwise), or "minmax", ("percentile", p) or "mse": that histogram method around this
+    call alone, the earlier setting put back afterwards, also on an exception."""
     import _CXX_i8ie as cx
     import i8ie
 
     net = build(name)
     net.load(state_dict if state_dict is not None else synthetic_state_dict(name, seed))
     cx.set_calibration_seed(calib_seed)  # the reference's calibrator is unseeded (std::random_device)
-    net.prepare()
-    x = calib_batch if calib_batch is not None else synthetic_input(name, 100 if not name.startswith("alexnet") else 32, seed=99)
-    net(i8ie.tensor(x))
-    net.convert(per_channel)
+    before = i8ie.calibration()
+    if calibration is not None:
+        method, p = calibration if isinstance(calibration, (tuple, list)) else (calibration, before["percentile"])
+        i8ie.set_calibration(method, p)
+    try:
+        net.prepare()
+        x = calib_batch if calib_batch is not None else synthetic_input(name, 100 if not name.startswith("alexnet") else 32, seed=99)
+        net(i8ie.tensor(x))
+        net.convert(per_channel)
+    finally:
+        if calibration is not None:
+            i8ie.set_calibration(before["method"], before["percentile"])
     return net
 
 
