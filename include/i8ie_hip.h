@@ -731,6 +731,67 @@ int i8ie_upsample2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border,
 int i8ie_upsample2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int fh, int fw,
                         int mode);
 
+/* ---- resize to any size, and adaptive average pooling (no counterpart in the reference) --------------------------
+ * NCHW logical shape [n, c, h, w] -> [n, c, oh, ow], any oh, ow >= 1, up or down; the result carries the input's
+ * (scale, zero_point), as i8ie_upsample2d_u8's and the pools' results do; nothing is requantised.
+ * Resize.  Per axis with input length L and output length O, output index o gets (i0, i1, w0, w1) over `den`:
+ *     I8IE_RESIZE_BILINEAR          torch's align_corners=False, src = (o + 0.5) L / O - 0.5, negative clamped to 0:
+ *                                   den = 2*O,            num = max((2*o + 1)*L - O, 0)
+ *     I8IE_RESIZE_BILINEAR_ALIGNED  torch's align_corners=True, src = o (L - 1) / (O - 1):
+ *                                   den = max(O - 1, 1),  num = o*(L - 1), and 0 when O == 1
+ *     both:  i0 = num / den (floor),  w1 = num % den,  w0 = den - w1,  i1 = min(i0 + 1, L - 1)
+ *     I8IE_RESIZE_NEAREST           i0 = i1 = (o*L) / O (floor), w0 = den = 1, w1 = 0: a byte copy.  (torch's float
+ *                                   `scale` lands one index lower at a few places where o*L is a multiple of O; the
+ *                                   integer rule is the definition.)
+ * Bilinear on uint8, with (y0, y1, wy0, wy1) and (x0, x1, wx0, wx1) from that rule and D = den_y * den_x:
+ *     S = wx0 * (wy0 * q[y0,x0] + wy1 * q[y1,x0]) + wx1 * (wy0 * q[y0,x1] + wy1 * q[y1,x1])
+ *     out = (S + D / 2) / D       integer floor division: round to nearest, ties up, the rule of i8ie_upsample2d_u8 and
+ *                                 i8ie_avgpool2d_u8 (for odd D no tie exists and the floored half gives the same byte)
+ *     out = relu ? max(out, zero_point) : out                relu<u8>, src/functional.cc:15-26, on the result
+ * S / D is the interpolated value exactly; nothing leaves the integers.  D <= 2^22 (for I8IE_RESIZE_BILINEAR:
+ * oh * ow <= 2^20), so that S + D / 2 < 2^31; beyond it the call is I8IE_ERR_ARG.  At O = f*L, f in 1..8, the
+ * I8IE_RESIZE_BILINEAR rule is i8ie_upsample2d_u8's: num / den = (2*f*i + t) / (2*f), and S, D and D / 2 all scale by
+ * L_h * L_w, so the bytes (and the FP32 bits) are the same.
+ * Bilinear on FP32: l = (float)w1 / (float)den per axis, the two row blends a * (1 - lx) + b * lx first, then the
+ * column blend of their results with ly; one fp32 rounding per operation, no contraction (the sequence of
+ * i8ie_upsample2d_f32).  Nearest copies bits.  NaN and inf propagate as IEEE gives them.
+ * Adaptive average pool.  Output i of an axis covers [floor(i*L / O), ceil((i + 1)*L / O)) (torch's windows: they
+ * overlap when O does not divide L and are never empty).  uint8: q = (S + n / 2) / n with S the exact window sum and n
+ * the window's own element count (i8ie_avgpool2d_u8's rule), then the relu floor as above.  FP32: the fp32 sum of the
+ * window, rows outer, columns inner, divided by (float)n.  A window holds at most 65536 elements.  Where O divides L on
+ * both axes the result is i8ie_avgpool2d_u8's with kernel_h = L_h / O_h, kernel_w = L_w / O_w and stride = kernel (a
+ * square window where that entry takes one stride); (1, 1) is the global pool.
+ * Null pointers, non-positive sizes, an unknown mode, negative borders, D > 2^22 and a window of more than 65536
+ * elements are I8IE_ERR_ARG, raised before any device call.  Stateless, no allocation, capturable in a graph; `out`
+ * must not overlap `in` (csrc/i8ie_resize.hip).
+ * i8ie_resize_axis: host only, the rule of one axis: (i0, i1, w0, w1, den) of output index out_index; out_len <= 2^30. */
+#define I8IE_RESIZE_NEAREST 0
+#define I8IE_RESIZE_BILINEAR 1
+#define I8IE_RESIZE_BILINEAR_ALIGNED 2
+int i8ie_resize_axis(int in_len, int out_len, int mode, int out_index, int* i0, int* i1, int* w0, int* w1, int* den);
+/* NCHW in and out, any shape. */
+int i8ie_resize2d_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int n, int c, int h, int w, int oh, int ow,
+                     int mode);
+/* The same on NHWC buffers [n, h+2b, w+2b, c] -> [n, oh+2b', ow+2b', c], each with its own border and each plain
+ * (x_s8 = 0) or re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80).  Taps are read at the clamped indices of the
+ * rule: the input's border bytes are never read.  Only the interior of `out` is written: its border bytes are the
+ * caller's (i8ie_fill_border_u8).  Any c: 16 / 4 / 1 channels per lane by c % 16, c % 4; a buffer off that alignment
+ * takes the one-lane-per-byte kernel (same bytes).  h, w: logical input dims. */
+int i8ie_resize2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev,
+                          int out_border, int out_s8, int n, int c, int h, int w, int oh, int ow, int mode, int relu,
+                          uint8_t zero_point);
+/* FP32, NCHW (the definition above). */
+int i8ie_resize2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int oh, int ow,
+                      int mode);
+/* The adaptive average pool: NCHW; NHWC as i8ie_resize2d_u8_nhwc; FP32 NCHW. */
+int i8ie_adaptive_avgpool2d_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int n, int c, int h, int w, int oh,
+                               int ow);
+int i8ie_adaptive_avgpool2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev,
+                                    int out_border, int out_s8, int n, int c, int h, int w, int oh, int ow, int relu,
+                                    uint8_t zero_point);
+int i8ie_adaptive_avgpool2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int oh,
+                                int ow);
+
 /* ---- channel narrow, channel shuffle, pixel shuffle and unshuffle (no counterpart in the reference) ---------------
  * Byte rearrangements of an NCHW logical shape [n, c, h, w]; nothing is requantised: the result carries the input's
  * (scale, zero_point).  `kind` with its parameters p0, p1 (p1 is read by narrow alone):

@@ -206,5 +206,6 @@ Tensor<float> activation_f32(Tensor<float>& in, int kind, float param);
 Tensor<u8_t> activation_u8(Tensor<u8_t>& in, int kind, float param, float scale, int zp);
 void bind_ops(py::module_& m);
 void bind_rearrange(py::module_& m);  // ops_rearrange.cc: _narrow, _channel_shuffle, _pixel_shuffle, _pixel_unshuffle
+void bind_resize(py::module_& m);     // ops_resize.cc: _interpolate, _adaptive_avg_pool2d
 
 }  // namespace i8ie_py

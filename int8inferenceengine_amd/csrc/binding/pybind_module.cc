@@ -28,6 +28,7 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
   bind_tensors(m);
   bind_ops(m);
   bind_rearrange(m);
+  bind_resize(m);
   bind_layers(m);
   bind_calibration(m);
 

@@ -21,7 +21,7 @@ __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
     "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "GroupNorm", "group_norm", "BatchNorm2d", "batch_norm", "fold_batchnorm", "Attention", "attention",
-    "narrow", "split", "chunk", "channel_shuffle", "pixel_shuffle", "pixel_unshuffle",
+    "narrow", "split", "chunk", "channel_shuffle", "pixel_shuffle", "pixel_unshuffle", "interpolate", "adaptive_avg_pool2d",
     "synchronize", "set_device", "pinned_empty", "from_torch", "set_calibration", "calibration",
 ]
 
@@ -290,6 +290,80 @@ def _integer(op, what, v):
     if isinstance(v, bool) or not isinstance(v, numbers.Integral):
         raise TypeError("%s: %s must be an integer" % (op, what))
     return int(v)
+
+
+def _int_pair(op, what, v, none_ok=False):
+    """(a, b) of an int or a pair of ints (None allowed in a pair with none_ok); TypeError for anything else"""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise TypeError("%s: %s is an int or a pair" % (op, what))
+        pair = tuple(v)
+    else:
+        pair = (v, v)
+    return tuple(None if (none_ok and p is None) else _integer(op, what, p) for p in pair)
+
+
+def _nchw_dims(op, x):
+    """(h, w) of a uint8 or FP32 [n, c, h, w] tensor; RuntimeError for int8 (s8) tensors and any other rank"""
+    if type(x.data).__name__ not in ("6TensorIhE", "6TensorIfE"):
+        raise RuntimeError("%s: int8 (s8) tensors are not supported (uint8 and FP32 tensors are)" % op)
+    shape = x.shape
+    if len(shape) != 4:
+        raise RuntimeError("%s expects an NCHW tensor" % op)
+    return int(shape[2]), int(shape[3])
+
+
+def interpolate(x, size=None, scale_factor=None, mode="nearest", align_corners=None):
+    """torch.nn.functional.interpolate of an [n, c, h, w] tensor to any size, up or down.  Exactly one of `size` (an int or
+    (oh, ow)) and `scale_factor` (an int or a pair of ints, meaning size = (h f, w f); pass `size` for anything fractional).
+    `mode` is "nearest" or "bilinear"; `align_corners` (None / False / True) belongs to "bilinear" alone.  uint8 tensors: exact
+    integers -- per axis the taps and weights of include/i8ie_hip.h (i8ie_resize2d_u8), the blend rounded to nearest, ties up;
+    the result carries the input's scale and zero point.  Nearest takes in[(o * L) // O] per axis, which differs from torch's
+    float rule at a few indices where o * L is a multiple of O.  FP32 tensors: a copy (nearest) or the fp32 blend, rows first.
+    An output that is an integer multiple 1..8 of the input on both axes, align_corners not True, is `upsample` (same bytes by
+    definition, and the same launch)."""
+    if (size is None) == (scale_factor is None):
+        raise ValueError("interpolate: exactly one of size and scale_factor")
+    if mode not in _UPSAMPLE_MODES:
+        raise RuntimeError("interpolate: mode must be 'nearest' or 'bilinear'")
+    if align_corners is not None and not isinstance(align_corners, bool):
+        raise TypeError("interpolate: align_corners is None, False or True")
+    if align_corners is not None and mode == "nearest":
+        raise ValueError("interpolate: align_corners goes with mode 'bilinear' only")
+    if size is not None:
+        oh, ow = _int_pair("interpolate", "size", size)
+    else:
+        try:
+            fh, fw = _int_pair("interpolate", "scale_factor", scale_factor)
+        except TypeError:
+            raise TypeError("interpolate: scale_factor must be an int or a pair of ints; pass size= for any other ratio") from None
+    h, w = _nchw_dims("interpolate", x)
+    if size is None:
+        oh, ow = h * fh, w * fw
+    if h > 0 and w > 0 and oh % h == 0 and ow % w == 0 and 1 <= oh // h <= 8 and 1 <= ow // w <= 8 and not align_corners:
+        return Tensor(_C.upsample(x.data, oh // h, ow // w, _UPSAMPLE_MODES[mode]))
+    code = 0 if mode == "nearest" else (2 if align_corners else 1)  # I8IE_RESIZE_* of include/i8ie_hip.h
+    return Tensor(_C._interpolate(x.data, oh, ow, code))
+
+
+def adaptive_avg_pool2d(x, output_size):
+    """torch's adaptive_avg_pool2d of an [n, c, h, w] tensor: `output_size` is an int or (oh, ow), None in a pair keeps that
+    dim; output i of an axis averages inputs floor(i L / O) .. ceil((i + 1) L / O) - 1.  uint8 tensors: the integer mean of
+    each window rounded to nearest, ties up, (sum + n // 2) // n with the window's own n (include/i8ie_hip.h,
+    i8ie_adaptive_avgpool2d_u8); the result carries the input's scale and zero point.  FP32 tensors: the fp32 sum of the window
+    divided by n.  (1, 1) is `global_avg_pool2d`, and where the windows are uniform squares it is `avg_pool2d` (same bytes by
+    definition, and the same launch)."""
+    oh, ow = _int_pair("adaptive_avg_pool2d", "output_size", output_size, none_ok=True)
+    h, w = _nchw_dims("adaptive_avg_pool2d", x)
+    oh, ow = h if oh is None else oh, w if ow is None else ow
+    if oh < 1 or ow < 1:
+        raise RuntimeError("adaptive_avg_pool2d: the output size must be at least 1 x 1")
+    if h > 0 and w > 0:
+        if oh == 1 and ow == 1:
+            return Tensor(_C.global_avg_pool2d(x.data))
+        if h % oh == 0 and w % ow == 0 and h // oh == w // ow:
+            return Tensor(_C.avg_pool2d(x.data, h // oh, h // oh))
+    return Tensor(_C._adaptive_avg_pool2d(x.data, oh, ow))
 
 
 def narrow(x, start, length):
