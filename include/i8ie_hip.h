@@ -831,6 +831,46 @@ int i8ie_rearrange_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, in
 int i8ie_rearrange_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int kind, int p0,
                        int p1);
 
+/* ---- Spatial padding: constant, reflect, replicate, circular, and cropping (no counterpart in the reference) ------
+ * torch.nn.functional.pad on the last two axes of an NCHW logical shape [n, c, h, w] -> [n, c, h + top + bottom,
+ * w + left + right]; nothing is requantised: the result carries the input's (scale, zero_point).  Per axis of input
+ * length L with amounts (before, after): the output length is O = L + before + after >= 1, output index o reads input
+ * index i = o - before, and for i outside [0, L)
+ *     I8IE_PAD_CONSTANT   the fill value.  Amounts may be negative: they cut pixels off (a crop to the window
+ *                         [top', top' + O_h) x [left', left' + O_w) is the amounts (-left', left' + O_w - w, -top',
+ *                         top' + O_h - h)); mixed signs are allowed
+ *     I8IE_PAD_REFLECT    i < 0: -i;  i >= L: 2*(L - 1) - i     (the edge pixel is not repeated)   0 <= amount <= L - 1
+ *     I8IE_PAD_REPLICATE  i < 0: 0;   i >= L: L - 1                                                0 <= amount
+ *     I8IE_PAD_CIRCULAR   i < 0: i + L;  i >= L: i - L                                             0 <= amount <= L
+ *     out = relu ? max(out, zero_point) : out       relu<u8>, src/functional.cc:15-26, on the NHWC entry; fill bytes too
+ * These are torch's rules and limits.  |amount| <= 65535.  `fill` is the plain byte (not re-biased; the kernel
+ * re-biases it with the rest when out_s8) or the float; the three other modes do not read it.  Null pointers,
+ * non-positive sizes, negative borders, an unknown mode, an amount beyond its mode's limit, a negative amount outside
+ * the constant mode, O < 1 and an `out` that overlaps `in` are I8IE_ERR_ARG, raised before any device call;
+ * i8ie_last_error names what is wrong (the shape rules begin with "pad:").  Stateless, nothing is allocated or copied,
+ * the geometry travels in the kernel arguments: capturable in a graph (csrc/i8ie_pad.hip).
+ * i8ie_pad_output_shape (host only): the result's four dims into out_dims, or I8IE_ERR_ARG. */
+#define I8IE_PAD_CONSTANT 0
+#define I8IE_PAD_REFLECT 1
+#define I8IE_PAD_REPLICATE 2
+#define I8IE_PAD_CIRCULAR 3
+int i8ie_pad_output_shape(int mode, int left, int right, int top, int bottom, int n, int c, int h, int w, int* out_dims);
+/* On NHWC buffers [n, h+2b, w+2b, c] -> [n, oh+2b', ow+2b', c], each with its own border and each plain (x_s8 = 0) or
+ * re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80).  The input's border bytes are never read: they hold the
+ * zero point, which is not what reflect, replicate or circular put there.  Only the interior of `out` is written: its
+ * border bytes are the caller's (i8ie_fill_border_u8).  Any c: 16 / 4 / 1 bytes per lane by c % 16, c % 4 and the
+ * pointers' alignment; one lane per byte under I8IE_OPT_FORCE_FALLBACK; the bytes are the same.  h, w: logical input
+ * dims. */
+int i8ie_pad2d_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev, int out_border,
+                       int out_s8, int n, int c, int h, int w, int mode, int left, int right, int top, int bottom,
+                       uint8_t fill, int relu, uint8_t zero_point);
+/* Plain NCHW in and out, any shape (no relu: a caller applies i8ie_relu_u8). */
+int i8ie_pad2d_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, int n, int c, int h, int w, int mode, int left,
+                  int right, int top, int bottom, uint8_t fill);
+/* FP32, NCHW: the same index rule, bits copied (NaN payloads and -0.0 included, in the data and in `fill`). */
+int i8ie_pad2d_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int mode, int left,
+                   int right, int top, int bottom, float fill);
+
 /* ---- quantized channel concatenation (no counterpart in the reference: it has no op that joins two tensors) ----
  * cat(x_0 .. x_{k-1}) along axis 1, 1 <= k <= I8IE_CONCAT_MAX_INPUTS; the same buffer may appear more than once.  The
  * result carries its own (s_out, zp_out).  A byte a of input i, with that tensor's (s_i, zp_i), becomes

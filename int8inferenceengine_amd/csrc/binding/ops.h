@@ -207,5 +207,6 @@ Tensor<u8_t> activation_u8(Tensor<u8_t>& in, int kind, float param, float scale,
 void bind_ops(py::module_& m);
 void bind_rearrange(py::module_& m);  // ops_rearrange.cc: _narrow, _channel_shuffle, _pixel_shuffle, _pixel_unshuffle
 void bind_resize(py::module_& m);     // ops_resize.cc: _interpolate, _adaptive_avg_pool2d
+void bind_pad(py::module_& m);        // ops_pad.cc: _pad
 
 }  // namespace i8ie_py

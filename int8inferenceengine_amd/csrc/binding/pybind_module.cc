@@ -29,6 +29,7 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
   bind_ops(m);
   bind_rearrange(m);
   bind_resize(m);
+  bind_pad(m);
   bind_layers(m);
   bind_calibration(m);
 

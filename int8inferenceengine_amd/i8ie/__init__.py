@@ -15,13 +15,14 @@ from .module import Module
 from .tensor import Tensor
 
 _UPSAMPLE_MODES = {"nearest": 0, "bilinear": 1}  # I8IE_UPSAMPLE_* of include/i8ie_hip.h
+_PAD_MODES = {"constant": 0, "reflect": 1, "replicate": 2, "circular": 3}  # I8IE_PAD_* of include/i8ie_hip.h
 FullyConnected = Linear  # BASELINE.json's name for the same class (no such symbol in the reference)
 
 __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
     "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "GroupNorm", "group_norm", "BatchNorm2d", "batch_norm", "fold_batchnorm", "Attention", "attention",
-    "narrow", "split", "chunk", "channel_shuffle", "pixel_shuffle", "pixel_unshuffle", "interpolate", "adaptive_avg_pool2d",
+    "narrow", "split", "chunk", "channel_shuffle", "pixel_shuffle", "pixel_unshuffle", "interpolate", "adaptive_avg_pool2d", "pad", "crop",
     "synchronize", "set_device", "pinned_empty", "from_torch", "set_calibration", "calibration",
 ]
 
@@ -428,6 +429,45 @@ def pixel_unshuffle(x, downscale_factor):
     """torch's pixel_unshuffle, the inverse of pixel_shuffle: [n, c, h, w] -> [n, c r r, h / r, w / r], r an integer in 1..8
     that divides h and w.  Tensor types as pixel_shuffle."""
     return Tensor(_C._pixel_unshuffle(x.data, _integer("pixel_unshuffle", "downscale_factor", downscale_factor)))
+
+
+def pad(x, pad, mode="constant", value=0.0):
+    """torch.nn.functional.pad on the last two axes of an [n, c, h, w] tensor: `pad` is (left, right, top, bottom), or
+    (left, right) for the width alone, Python integers with |amount| <= 65535; `mode` is "constant", "reflect", "replicate"
+    or "circular".  Per axis of length L, output index o reads input index i = o - before, and outside [0, L): the fill value;
+    -i or 2 (L - 1) - i (amounts <= L - 1); the edge pixel; i mod L (amounts <= L) -- torch's rules and limits
+    (include/i8ie_hip.h, "Spatial padding").  Negative amounts cut pixels off, in "constant" mode only.  `value` belongs to
+    "constant" alone: FP32 tensors take the float itself, uint8 tensors the byte `quantize` gives it at the input's
+    (scale, zero_point), so 0 is the byte zero_point.  uint8 tensors: bytes copied, the result carries the input's scale and
+    zero point and is recorded, not launched (it launches when something consumes it); FP32 tensors: bits copied; int8 (s8)
+    tensors and any other rank raise RuntimeError, and so does every violation of the rules above, before any device call.
+    All-zero amounts return `x` itself."""
+    if not isinstance(pad, (tuple, list)) or len(pad) not in (2, 4):
+        raise TypeError("pad: pad is (left, right) or (left, right, top, bottom)")
+    amounts = [_integer("pad", "every amount", a) for a in pad] + [0] * (4 - len(pad))
+    if mode not in _PAD_MODES:
+        raise RuntimeError("pad: mode must be 'constant', 'reflect', 'replicate' or 'circular'")
+    if isinstance(value, bool) or not isinstance(value, numbers.Real):
+        raise TypeError("pad: value must be a number")
+    if mode != "constant" and value != 0:
+        raise TypeError("pad: value goes with mode 'constant' only")
+    _nchw_dims("pad", x)
+    if not any(amounts):
+        return x
+    return Tensor(_C._pad(x.data, *amounts, _PAD_MODES[mode], float(value)))
+
+
+def crop(x, top, left, height, width):
+    """The window x[:, :, top:top + height, left:left + width] of an [n, c, h, w] tensor, integers, inside the map and at
+    least 1 x 1 (anything else raises RuntimeError).  It is `pad` in "constant" mode with the negative amounts the window
+    implies: the same bytes and the same launch."""
+    top, left = _integer("crop", "top", top), _integer("crop", "left", left)
+    height, width = _integer("crop", "height", height), _integer("crop", "width", width)
+    h, w = _nchw_dims("crop", x)
+    if top < 0 or left < 0 or height < 1 or width < 1 or top + height > h or left + width > w:
+        raise RuntimeError("crop: the window %d x %d at (%d, %d) must be at least 1 x 1 and lie inside the %d x %d map"
+                           % (height, width, top, left, h, w))
+    return pad(x, (-left, left + width - w, -top, top + height - h))
 
 
 def set_calibration(method="reservoir", percentile=99.99):
