@@ -1300,6 +1300,56 @@ int i8ie_batchnorm_u8(i8ie_ctx* ctx, const uint8_t* in_dev, uint8_t* out_dev, in
 int i8ie_batchnorm_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int64_t rows, int C, int64_t inner,
                        const float* gamma_dev, const float* beta_dev, const float* mean_dev, const float* var_dev, float eps);
 
+/* ---- position embedding with an optional class token (no counterpart in the reference) ----------------------------------
+ * The input is [n, c, h, w] bytes with (s_in, zp_in), counted as n sequences of T = h * w tokens of c channels: token j is
+ * pixel (j / w, j % w), the order in which i8ie_attention_u8 and i8ie_layernorm_u8_nhwc count a rank-4 tensor.  E is an
+ * fp32 table [T', c] shared by every image of the batch; the result carries (s_out, zp_out).
+ *     class_token == 0: T' = T, the result is [n, c, h, w], and output token j is input token j.
+ *     class_token != 0: T' = T + 1, the result is [n, c, 1, T + 1] (physically [n, T + 1, c]); output token 0 has no input
+ *                       byte (its dequantised value is +0) and output token 1 + j is input token j.  This is torchvision's
+ *                       cat([class_token.expand(n, -1, -1), tokens], 1) + pos_embedding in the engine's NHWC storage.
+ * E = P (the learned table, torch's pos_embedding[0]), except row 0 of the class form: E[0][ch] = cls[ch] + P[0][ch], one
+ * fp32 add on the host (i8ie_posembed_table).  Per output element, the composition of the reference's dequantize
+ * (src/quantize_utils.cc:38-42) and down_scale's clamp and truncation (:27-36), IEEE fp32, one rounding per operation, no
+ * contraction, as for i8ie_add_u8:
+ *     fa = (float)((int)a - (int)zp_in) * s_in          (the class column: fa = +0)
+ *     t  = (fa + E[tok][ch]) / s_out + (float)zp_out
+ *     q  = t >= 255 ? 255 : (t < 0 ? 0 : (u8)t);   q = relu ? max(q, zp_out) : q        (relu<u8>, src/functional.cc:15-26)
+ * Every E entry, s_in, 255 * s_in and s_out must be finite and s_out > 0.  No NaN can then arise: fa and E are finite, their
+ * sum may overflow to an infinity, which clamps.
+ * The bound against the real numbers.  With Fa = (a - zp_in) s_in / s_out, X = ((a - zp_in) s_in + E*) / s_out and
+ * y* = X + zp_out as real numbers of the fp32 inputs, E* = P (row 0 of the class form: cls + P[0], the real sum), u = 2^-24:
+ *     |t - y*| <= B = 1.01 * u * (|Fa| + 3 |X| + |y*|)
+ * (fa rounds once: u |Fa|; E[0] of the class form, the sum fa + E and the quotient once each: 3 u |X|; t once: u |y*|; the
+ * factor 1.01 absorbs every second-order term, and a quotient below 2^-126 adds at most 2^-149.)  Where y* lies further than
+ * B from an integer, q = clamp(trunc(y*)).
+ * i8ie_posembed_table: host only (no ctx, like i8ie_layernorm_affine): E_host[tokens][c] from P[tokens][c] and, where cls is
+ * not null, the class token cls[c] added into row 0.  Null P or E_host, c outside 1..16384, tokens < 1 or > 2^30 and a P, cls
+ * or E entry that is not finite are I8IE_ERR_ARG; an error is reported before anything is written.  E_host may be P. */
+int i8ie_posembed_table(const float* P, const float* cls, int tokens, int c, float* E_host);
+/* NHWC buffers [n, h+2b, w+2b, c] -> [n, h+2b', w+2b', c] (class_token: [n, 1+2b', T+1+2b', c]), each with its own border
+ * and plain (x_s8 = 0) or re-biased (x_s8 != 0: I8IE_LAYOUT_NHWC_S8, bytes ^ 0x80), the rules of i8ie_layernorm_u8_nhwc: the
+ * input's border bytes are never read; only the interior of `out` is written, its border bytes are the caller's
+ * (i8ie_fill_border_u8).  out may be in itself in the plain form when both geometries agree; otherwise the buffers must not
+ * overlap.  e_dev: fp32 [T'][c] on the device (4-byte aligned), as i8ie_posembed_table made it.  Stateless: one launch, no
+ * device allocation, no host synchronisation, capturable in a graph.  Null pointers, c outside 1..16384, non-positive
+ * sizes, negative borders, more than 2^30 tokens per image, a scale that is not finite (255 * s_in included) and s_out <= 0
+ * are I8IE_ERR_ARG with a message, before any device call; the table's entries are checked where it is made
+ * (i8ie_posembed_table).  Two kernels with identical bytes (csrc/i8ie_posembed.hip):
+ * posembed_u8_nhwc (16 / 4 / 1 channels of one token per lane by c % 16 and c % 4, the item's E values in registers over
+ * up to I8IE_POSEMBED_WALK images, fewer where the batch is too small to fill the grid with that; the guarded estimate of
+ * i8ie_add_u8 with its exact replay) and posembed_u8_direct (one lane per output byte, the definition verbatim) for in,
+ * out or e_dev not 16-byte aligned and for everything under I8IE_OPT_FORCE_FALLBACK. */
+#define I8IE_POSEMBED_WALK 8
+int i8ie_posembed_u8_nhwc(i8ie_ctx* ctx, const uint8_t* in_dev, int in_border, int in_s8, uint8_t* out_dev, int out_border,
+                          int out_s8, int n, int c, int h, int w, int class_token, const float* e_dev, float s_in,
+                          uint8_t zp_in, float s_out, uint8_t zp_out, int relu);
+/* FP32 (before convert(), and while calibrating) on NCHW floats: [n, c, h, w] -> [n, c, h, w] or, with class_token,
+ * [n, c, 1, T + 1]: out = x + E[tok][ch] in fp32, one rounding; the class column is E[0][ch] itself.  4-byte aligned
+ * buffers that do not overlap (the plain form may run in place).  Not tuned. */
+int i8ie_posembed_f32(i8ie_ctx* ctx, const float* in_dev, float* out_dev, int n, int c, int h, int w, int class_token,
+                      const float* e_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,5 +208,6 @@ void bind_ops(py::module_& m);
 void bind_rearrange(py::module_& m);  // ops_rearrange.cc: _narrow, _channel_shuffle, _pixel_shuffle, _pixel_unshuffle
 void bind_resize(py::module_& m);     // ops_resize.cc: _interpolate, _adaptive_avg_pool2d
 void bind_pad(py::module_& m);        // ops_pad.cc: _pad
+void bind_posembed(py::module_& m);   // ops_posembed.cc: _position_embedding, _PositionEmbedding
 
 }  // namespace i8ie_py

@@ -30,6 +30,7 @@ PYBIND11_MODULE(_CXX_i8ie, m) {
   bind_rearrange(m);
   bind_resize(m);
   bind_pad(m);
+  bind_posembed(m);
   bind_layers(m);
   bind_calibration(m);
 

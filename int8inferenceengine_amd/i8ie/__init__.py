@@ -9,7 +9,7 @@ import numbers
 
 import _CXX_i8ie as _C
 
-from .layer import CALIBRATION_METHODS, Activation, Add, Attention, BatchNorm2d, Concat, Conv2d, ConvTranspose2d, GroupNorm, Layer, LayerNorm, Linear, MatMul, Mul, activation_kind, fold_batchnorm
+from .layer import CALIBRATION_METHODS, Activation, Add, Attention, BatchNorm2d, Concat, Conv2d, ConvTranspose2d, GroupNorm, Layer, LayerNorm, Linear, MatMul, Mul, PositionEmbedding, activation_kind, fold_batchnorm
 from .layer import calibration_percentile as _percentile
 from .module import Module
 from .tensor import Tensor
@@ -22,7 +22,7 @@ __all__ = [
     "tensor", "argmax", "relu", "max_pool2d", "quantize", "dequantize",
     "Linear", "FullyConnected", "Conv2d", "ConvTranspose2d", "Tensor", "Module", "Add", "add", "Mul", "mul", "Concat", "cat", "Activation", "activation", "lut", "avg_pool2d", "global_avg_pool2d", "upsample",
     "MatMul", "matmul", "softmax", "LayerNorm", "layer_norm", "GroupNorm", "group_norm", "BatchNorm2d", "batch_norm", "fold_batchnorm", "Attention", "attention",
-    "narrow", "split", "chunk", "channel_shuffle", "pixel_shuffle", "pixel_unshuffle", "interpolate", "adaptive_avg_pool2d", "pad", "crop",
+    "narrow", "split", "chunk", "channel_shuffle", "pixel_shuffle", "pixel_unshuffle", "interpolate", "adaptive_avg_pool2d", "pad", "crop", "PositionEmbedding", "position_embedding",
     "synchronize", "set_device", "pinned_empty", "from_torch", "set_calibration", "calibration",
 ]
 
@@ -203,6 +203,24 @@ def batch_norm(x, running_mean, running_var, weight=None, bias=None, eps=1e-5, s
     if scale is not None or zero_point is not None:
         raise TypeError("batch_norm of an FP32 tensor takes no scale / zero_point")
     return Tensor(_C._batch_norm(x.data, running_mean, running_var, weight, bias, float(eps)))
+
+
+def position_embedding(x, weight, class_token=None, scale=None, zero_point=None):
+    """x + weight over the tokens of an [n, c, h, w] tensor, token j being pixel (j // w, j % w): `weight` is a float32 array
+    [T', c] shared by every image.  class_token=None: T' = h * w, the shape is unchanged.  `class_token`, a float32 array [c]:
+    T' = h * w + 1 and the result is [n, c, 1, h * w + 1], column 0 being class_token + weight[0] and column 1 + j token j plus
+    weight[1 + j] (torchvision's cat + pos_embedding).  FP32 tensors: one fp32 add, `scale` / `zero_point` must not be given.
+    uint8 tensors: the quantized op of include/i8ie_hip.h (i8ie_posembed_u8_nhwc); the result's `scale` and `zero_point` are
+    required, and the table is made and uploaded at every call.  `i8ie.PositionEmbedding` is the calibrated form for use inside
+    a Module (it uploads the table once)."""
+    quantized = type(x.data).__name__ == "6TensorIhE"
+    if quantized:
+        if scale is None or zero_point is None:
+            raise TypeError("position_embedding of a uint8 tensor needs the result's scale and zero_point")
+        return Tensor(_C._position_embedding(x.data, weight, class_token, float(scale), int(zero_point)))
+    if scale is not None or zero_point is not None:
+        raise TypeError("position_embedding of an FP32 tensor takes no scale / zero_point")
+    return Tensor(_C._position_embedding(x.data, weight, class_token))
 
 
 def cat(tensors, scale=None, zero_point=None):

@@ -266,6 +266,30 @@ class BatchNorm2d(Norm):
             self.layer.convert()
 
 
+class PositionEmbedding(Norm):
+    """Learned position embedding with an optional class token `y = self.pos(x)` (additive, not in the reference): a layer
+    with an fp32 `weight` [T', channels] (torch's pos_embedding[0], default zeros), in the class form an fp32 `bias` [channels]
+    (the class token, default zeros; load_bias raises RuntimeError without class_token), and no INT8 weights.
+
+    The input is [n, channels, height, width], counted as n sequences of T = height * width tokens: token j is pixel
+    (j // width, j % width), the order in which Attention and LayerNorm count a rank-4 tensor.  class_token=False: T' = T and
+    y[i, ch, j] = x[i, ch, j] + weight[j, ch], shape unchanged.  class_token=True: T' = T + 1 and the result is
+    [n, channels, 1, T + 1]: column 0 is bias[ch] + weight[0, ch], column 1 + j is x[i, ch, j] + weight[1 + j, ch] -- torchvision's
+    cat([class_token.expand(n, -1, -1), tokens], 1) + pos_embedding in the engine's NHWC storage.  Any other input shape raises
+    RuntimeError.  FP32 tensors add in FP32 (include/i8ie_hip.h, i8ie_posembed_f32; sampled by the calibrator while preparing);
+    uint8 tensors, after convert(), go through i8ie_posembed_u8_nhwc with this layer's output (scale, zero_point).
+    Module.load() takes `<attr>.weight` / `<attr>.bias`; quantized_state_dict() keeps them as float32 beside `<attr>.qparams`
+    (`<attr>.bias` in the class form only).  `i8ie.crop(y, 0, 0, 1, 1).reshape(-1, channels)` picks the class column for a
+    Linear head."""
+
+    def __init__(self, channels, height, width, class_token=False):
+        self.channels, self.height, self.width, self.class_token = int(channels), int(height), int(width), bool(class_token)
+        self.layer = _C._PositionEmbedding(self.channels, self.height, self.width, self.class_token)
+
+    def set_output_qparams(self, scale, zero_point):
+        self.layer._set_output_qparams(float(scale), int(zero_point))  # (bound under a private name: csrc/binding/ops_posembed.cc)
+
+
 def fold_batchnorm(layer, bn):
     """Fold the BatchNorm2d `bn` into the Conv2d (any groups, dilation or rectangular geometry), Linear or ConvTranspose2d
     `layer` whose output it normalises, in FP32 and before prepare().  With k[o] = gamma[o] / sqrt(var[o] + eps) in double:

@@ -1,7 +1,7 @@
 """Module base class (reference i8ie/module.py:6-35)."""
 import _CXX_i8ie as _C
 
-from .layer import Attention, BatchNorm2d, Layer, Norm, Weightless, fold_batchnorm
+from .layer import Attention, BatchNorm2d, Layer, Norm, PositionEmbedding, Weightless, fold_batchnorm
 from .tensor import Tensor
 
 # Hard-coded input quantisation of the reference (i8ie/module.py:20).
@@ -64,7 +64,8 @@ class Module:
         (weight_scale, out_scale, out_zero_point)} for every converted layer; a per-channel layer also has
         '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused).  An Add, a Mul, a Concat or an Activation contributes only
         '<attr>.qparams' = (0, out_scale, out_zero_point), an Attention that and '<attr>.score_qparams' float64[2] = (scale, zero_point);
-        a LayerNorm or a GroupNorm '<attr>.qparams' and '<attr>.weight', '<attr>.bias' as float32; a BatchNorm2d those and
+        a LayerNorm or a GroupNorm '<attr>.qparams' and '<attr>.weight', '<attr>.bias' as float32 (a PositionEmbedding the same,
+        '<attr>.bias' with class_token only); a BatchNorm2d those and
         '<attr>.running_mean', '<attr>.running_var', or no key at all once it is folded into its neighbour."""
         import numpy as np
 
@@ -85,7 +86,8 @@ class Module:
                 continue
             if isinstance(layer, Norm):
                 out[name + ".weight"] = np.asarray(L.weight(), np.float32)
-                out[name + ".bias"] = np.asarray(L.bias(), np.float32)
+                if not isinstance(layer, PositionEmbedding) or layer.class_token:  # (a plain PositionEmbedding has no bias)
+                    out[name + ".bias"] = np.asarray(L.bias(), np.float32)
                 if isinstance(layer, BatchNorm2d):
                     out[name + ".running_mean"] = np.asarray(L.running_mean(), np.float32)
                     out[name + ".running_var"] = np.asarray(L.running_var(), np.float32)
@@ -124,7 +126,8 @@ class Module:
                 layer.layer.load_quantized(float(np.float32(s_out)), int(zp_out))
                 continue
             if isinstance(layer, Norm):
-                layer.layer.load_quantized(np.asarray(state[name + ".weight"], np.float32), np.asarray(state[name + ".bias"], np.float32),
+                bias = state.get(name + ".bias") if isinstance(layer, PositionEmbedding) and not layer.class_token else state[name + ".bias"]
+                layer.layer.load_quantized(np.asarray(state[name + ".weight"], np.float32), None if bias is None else np.asarray(bias, np.float32),
                                            float(np.float32(s_out)), int(zp_out))
                 continue
             if name + ".w_scales" in state:  # per-channel layer
