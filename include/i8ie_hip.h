@@ -1089,6 +1089,43 @@ int i8ie_attention_u8(i8ie_ctx* ctx, const i8ie_attention_args* args);
  * the scores before the softmax (what the calibrator samples).  The calibration path: 3 * heads launches, not tuned. */
 int i8ie_attention_f32(i8ie_ctx* ctx, const i8ie_attention_args* args);
 
+/* ---- windowed (local) attention on a map ---------------------------------------------------------
+ * Attention inside the non-overlapping win_h x win_w windows of an [n, c, map_h, map_w] map, map_h % win_h == 0 and
+ * map_w % win_w == 0.  Nothing new is defined arithmetically.  Let part(x) be
+ *     [n, c, h, w] -> [n * (h / win_h) * (w / win_w), win_h * win_w, c]
+ * with the window index counted (image, wy, wx) in that order and token j of a window being pixel
+ * (wy * win_h + j / win_w, wx * win_w + j % win_w), and unpart its inverse.  Then
+ *     out = unpart(attention(part(q), part(k), part(v), heads))
+ * and per (window, head) the bytes are exactly those of i8ie_bmm_u8, i8ie_softmax_u8, i8ie_bmm_u8 as i8ie_attention_u8
+ * defines them.  There is no shift, no mask and no bias.  A window that is the whole map is the global form, with the same
+ * bytes by definition.
+ * The i8ie_attention_args are read as follows: b is the image count; tq == tk == win_h * win_w (<= 32768); q, k, v and out
+ * describe whole maps, each the interior of a channels-last buffer [b][map_h + 2B][map_w + 2B][.] with a border B of its
+ * own (q_border, k_border, v_border here, out_border in the args): ptr is the buffer's first byte (plus the column offset
+ * of a packed operand), token_stride the stride of one physical pixel (>= heads * d), batch_stride that of one image, s8
+ * the re-bias mark.  Every border is at most 65535 pixels.  An operand's border is never read, the result's never
+ * written.  out_h and out_w must equal map_h and map_w, and b * heads * map_h * map_w must fit 31 bits.  The debug outputs count a window as a batch item: scores_dbg_dev and probs_dbg_dev are [b * nW, heads, T, T],
+ * acc_dbg_dev is [b * nW, T, c], nW = (map_h / win_h) * (map_w / win_w), T = win_h * win_w.  Everything else (scales, zero
+ * points, relu, one launch, no allocation, capturable) is as for i8ie_attention_u8; every argument error is I8IE_ERR_ARG
+ * before any device call.  The same two kernels, instantiated with the window's row-to-pixel map
+ * (j / win_w) * row pitch + (j % win_w) * pixel stride in place of the single token stride: attn_mfma under the global
+ * entry's conditions (d % 16 == 0, 16-byte-aligned pointers and strides, T <= 1024; one window per 64-row tile), attn_direct
+ * for everything else and under I8IE_OPT_FORCE_FALLBACK, with identical bytes. */
+typedef struct i8ie_attention_window {
+  int map_h, map_w;                  /* the map every operand and the result cover */
+  int win_h, win_w;                  /* the window; must divide the map */
+  int q_border, k_border, v_border;  /* the physical border, in pixels, of each operand's buffer (>= 0) */
+} i8ie_attention_window;
+int i8ie_attention_window_u8(i8ie_ctx* ctx, const i8ie_attention_args* args, const i8ie_attention_window* win);
+/* FP32 (before convert(), and while calibrating): q, k, v and out are NCHW float maps without borders; element
+ * (image, column, y, x) lies at ptr[image * batch_stride + column * token_stride + y * map_w + x], so token_stride is here
+ * the channel stride (>= map_h * map_w; a packed [n, 3c, h, w] tensor gives q, k, v at offsets 0, c * h * w, 2c * h * w).
+ * Every border, s8, relu and u8 debug pointer must be 0 / NULL.  Two small kernels gather the windows of q, k and v into
+ * dense [b * nW, T, c] arrays in the ctx workspace and scatter the result back; between them runs i8ie_attention_f32, so
+ * the result is bit-identical to that entry on host-partitioned tensors.  scores_out_dev, when given, receives the windowed
+ * scores [b * nW, heads, T, T].  The calibration path, not tuned. */
+int i8ie_attention_window_f32(i8ie_ctx* ctx, const i8ie_attention_args* args, const i8ie_attention_window* win);
+
 /* ---- quantized LayerNorm over the last axis (no counterpart in the reference: every op of it is a contraction, a pointwise
  * map or a window reduction; none takes a statistic of a row at run time) ----------------------------------------------------
  * A row is C bytes a[0..C) with (s_in, zp_in), 1 <= C <= 16384; eps is finite and > 0; the result carries (s_out, zp_out);

@@ -101,9 +101,16 @@ class Attention : public Weightless {
   Tensor<u8_t> forward_u8(Tensor<u8_t>& q, Tensor<u8_t>& k, Tensor<u8_t>& v) { return run_u8(q, &k, &v); }
   Tensor<u8_t> forward_u8_packed(Tensor<u8_t>& qkv) { return run_u8(qkv, nullptr, nullptr); }
   ssize_t heads() const { return heads_; }
+  // attend inside win_h x win_w windows of rank-4 maps from now on (i8ie.Attention(heads, window=): a constructor argument, not state)
+  void set_window(ssize_t wh, ssize_t ww) {
+    if (wh < 1 || ww < 1) throw std::runtime_error("i8ie: Attention: the window must be at least 1 x 1");
+    wh_ = wh;
+    ww_ = ww;
+  }
 
  private:
   Tensor<float> run_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v) {
+    if (wh_ > 0) return run_window_f32(q, k, v);
     if (!is_preparing_ || !score_cal_) return attention_f32(q, k, v, heads_, nullptr);
     const AttnShape s = attention_shape(q, k, v, heads_);
     Tensor<float> scores(std::vector<ssize_t>{s.b, s.heads, s.tq, s.tk});
@@ -111,12 +118,26 @@ class Attention : public Weightless {
     calib_sample(*score_cal_, scores);
     return sampled(out);
   }
+  Tensor<float> run_window_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v) {
+    if (!is_preparing_ || !score_cal_) return attention_window_f32(q, k, v, heads_, wh_, ww_, nullptr);
+    const AttnWindowShape s = attention_window_shape(q, k, v, heads_, wh_, ww_);
+    Tensor<float> scores(std::vector<ssize_t>{s.b * s.windows, s.heads, s.tq, s.tk});
+    Tensor<float> out = attention_window_f32(q, k, v, heads_, wh_, ww_, &scores);
+    calib_sample(*score_cal_, scores);
+    return sampled(out);
+  }
   Tensor<u8_t> run_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v) {
+    if (wh_ > 0) {
+      attention_window_shape(q, k, v, heads_, wh_, ww_);
+      need_quantized("Attention");
+      return attention_window_u8(q, k, v, heads_, wh_, ww_, score_scale_, score_zp_, scale_, zero_point_);
+    }
     attention_shape(q, k, v, heads_);
     need_quantized("Attention");
     return attention_u8(q, k, v, heads_, score_scale_, score_zp_, scale_, zero_point_);
   }
   ssize_t heads_;
+  ssize_t wh_ = 0, ww_ = 0;   // 0: the global form
   std::unique_ptr<Calibrator> score_cal_;
   float score_scale_ = 1;
   u8_t score_zp_ = 0;
@@ -408,6 +429,7 @@ void bind_weightless_layers(py::module_& m) {
         .def("load_quantized", &Attention::load_quantized, py::arg("out_scale"), py::arg("out_zero_point"), py::arg("score_scale"),
              py::arg("score_zero_point"))
         .def("heads", &Attention::heads)
+        .def("_set_window", &Attention::set_window, py::arg("win_h"), py::arg("win_w"))
         .def("__call__", &Attention::forward_f32).def("__call__", &Attention::forward_f32_packed)
         .def("__call__", &Attention::forward_u8).def("__call__", &Attention::forward_u8_packed);
   }

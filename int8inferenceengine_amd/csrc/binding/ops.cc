@@ -361,6 +361,12 @@ void bind_ops(py::module_& m) {
         py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"));
   m.def("attention", &attention_u8, py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"),
         py::arg("score_scale"), py::arg("score_zero_point"), py::arg("scale"), py::arg("zero_point"));
+  // ... inside win_h x win_w windows of rank-4 maps (i8ie_attention_window_u8); private: i8ie.attention(window=) is the surface
+  m.def("_attention_window", [](Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads, ssize_t wh, ssize_t ww) {
+    return attention_window_f32(q, k, v, heads, wh, ww, nullptr);
+  }, py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"), py::arg("win_h"), py::arg("win_w"));
+  m.def("_attention_window", &attention_window_u8, py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"),
+        py::arg("win_h"), py::arg("win_w"), py::arg("score_scale"), py::arg("score_zero_point"), py::arg("scale"), py::arg("zero_point"));
   // additive: LayerNorm over the channel axis of [n, c, h, w] or the last axis of [m, f] / [b, t, f] (include/i8ie_hip.h,
   // i8ie_layernorm_u8); weight / bias: float32 [channels] or None (ones / zeros); uploaded per call
   m.def("layer_norm", [](Tensor<float>& x, const py::object& w, const py::object& b, float eps) {

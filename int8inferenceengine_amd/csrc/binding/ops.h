@@ -97,6 +97,49 @@ AttnShape attention_shape(const Tensor<T>& q, const Tensor<T>* k, const Tensor<T
   else s.out = {s.b, s.tq, s.c};
   return s;
 }
+// The windowed form (include/i8ie_hip.h, i8ie_attention_window_u8): every operand is a rank-4 map [n, c, h, w] of one h x w,
+// the window (wh, ww) divides it and holds at most 32768 pixels.  b is the image count, tq == tk == wh * ww, and `windows` the
+// windows per image.  Anything else is a RuntimeError (before any device call).
+struct AttnWindowShape : AttnShape {
+  ssize_t h = 0, w = 0, wh = 0, ww = 0, windows = 0;
+};
+template <typename T>
+AttnWindowShape attention_window_shape(const Tensor<T>& q, const Tensor<T>* k, const Tensor<T>* v, ssize_t heads, ssize_t wh, ssize_t ww) {
+  if ((k == nullptr) != (v == nullptr)) throw std::runtime_error("i8ie: attention takes q, k and v, or one packed qkv tensor");
+  if (heads < 1) throw std::runtime_error("i8ie: attention: heads must be >= 1");
+  if (wh < 1 || ww < 1) throw std::runtime_error("i8ie: attention: the window must be at least 1 x 1");
+  for (const Tensor<T>* t : {&q, k, v}) {
+    if (!t) continue;
+    if (t->shape.size() != 4) throw std::runtime_error("i8ie: attention: the windowed form takes [n, c, h, w] operands");
+    for (ssize_t d : t->shape)
+      if (d <= 0) throw std::runtime_error("i8ie: attention: empty tensor");
+  }
+  AttnWindowShape s;
+  s.heads = heads;
+  s.packed = k == nullptr;
+  s.b = q.shape[0];
+  s.h = q.shape[2]; s.w = q.shape[3]; s.wh = wh; s.ww = ww;
+  if (s.packed) {
+    if (q.shape[1] % (3 * heads) != 0) throw std::runtime_error("i8ie: attention: a packed qkv tensor needs 3 * heads * d channels");
+    s.c = q.shape[1] / 3;
+  } else {
+    for (const Tensor<T>* t : {k, v}) {
+      if (t->shape[0] != s.b) throw std::runtime_error("i8ie: attention: the operands' batch sizes differ (there is no broadcasting)");
+      if (t->shape[1] != q.shape[1]) throw std::runtime_error("i8ie: attention: q, k and v must have the same channel count");
+      if (t->shape[2] != s.h || t->shape[3] != s.w) throw std::runtime_error("i8ie: attention: the windowed form needs q, k and v maps of one size");
+    }
+    if (q.shape[1] % heads != 0) throw std::runtime_error("i8ie: attention: the channel count is not heads * d");
+    s.c = q.shape[1];
+  }
+  s.d = s.c / heads;
+  if (s.h % wh != 0 || s.w % ww != 0)
+    throw std::runtime_error("i8ie: attention: the window does not divide the map (pad it first)");
+  if (wh * ww > 32768) throw std::runtime_error("i8ie: attention: more than 32768 pixels in a window");
+  s.tq = s.tk = wh * ww;
+  s.windows = (s.h / wh) * (s.w / ww);
+  s.out = {s.b, s.c, s.h, s.w};
+  return s;
+}
 // ---- layer_norm (no counterpart in the reference; arithmetic: include/i8ie_hip.h, i8ie_layernorm_u8) ---------------------
 // [n, c, h, w] is normalised over c per pixel, [m, f] and [b, t, f] over the last axis: (rows, inner) of the FP32 entry, or
 // a RuntimeError (before any device call)
@@ -182,6 +225,11 @@ Tensor<float> softmax_f32(Tensor<float>& x);
 Tensor<u8_t> softmax_u8(Tensor<u8_t>& x);
 Tensor<float> attention_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads, Tensor<float>* scores);
 Tensor<u8_t> attention_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, float s_s, int zp_s, float scale, int zp);
+// ... inside wh x ww windows of rank-4 maps; `scores` is then [n * windows, heads, wh * ww, wh * ww]
+Tensor<float> attention_window_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads, ssize_t wh, ssize_t ww,
+                                   Tensor<float>* scores);
+Tensor<u8_t> attention_window_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, ssize_t wh, ssize_t ww, float s_s, int zp_s,
+                                 float scale, int zp);
 Tensor<float> layer_norm_f32(Tensor<float>& x, const std::shared_ptr<Storage>& gamma, const std::shared_ptr<Storage>& beta, ssize_t channels, float eps);
 Tensor<u8_t> layer_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, const std::shared_ptr<Storage>& b, ssize_t channels, float eps,
                            float scale, int zp);

@@ -221,6 +221,79 @@ Tensor<u8_t> attention_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssi
   else out.pend = make_pend(run, {q.pend, k->pend, v->pend});
   return out;
 }
+// FP32, windowed: i8ie_attention_window_f32 on the NCHW tensors (part, i8ie_attention_f32, unpart)
+Tensor<float> attention_window_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads, ssize_t wh, ssize_t ww,
+                                   Tensor<float>* scores) {
+  const AttnWindowShape s = attention_window_shape(q, k, v, heads, wh, ww);
+  Tensor<float> out(s.out);
+  Tensor<float>* ts[3] = {&q, s.packed ? &q : k, s.packed ? &q : v};
+  const ssize_t C = s.packed ? 3 * s.c : s.c, hw = s.h * s.w;
+  i8ie_attention_args g{};
+  g.b = (int)s.b; g.heads = (int)s.heads; g.d = (int)s.d; g.tq = g.tk = (int)s.tq;
+  i8ie_attn_mat* ms[3] = {&g.q, &g.k, &g.v};
+  for (int i = 0; i < 3; ++i) *ms[i] = i8ie_attn_mat{ts[i]->dptr() + (s.packed ? i * s.c * hw : 0), (int64_t)C * hw, (int64_t)hw, 0};
+  g.out = i8ie_attn_mat{out.dptr(), (int64_t)s.c * hw, (int64_t)hw, 0};
+  g.out_h = (int)s.h; g.out_w = (int)s.w;
+  g.scores_out_dev = scores ? scores->dptr() : nullptr;
+  i8ie_attention_window win{(int)s.h, (int)s.w, (int)s.wh, (int)s.ww, 0, 0, 0};
+  check(i8ie_attention_window_f32(ctx(), &g, &win));
+  return out;
+}
+// A u8 map operand of the windowed form as it lies: NHWC under its own dims is read in place, border and re-bias included
+// (the kernel walks the interior); a view under other logical dims and an NCHW tensor take as_engine_nhwc's conversion.
+i8ie_attn_mat attn_window_operand(std::shared_ptr<Storage> s, const std::vector<ssize_t>& shp, ssize_t ch, ssize_t off, NhwcCopies& copies,
+                                  int* border) {
+  s = as_engine_nhwc(s, shp, copies);
+  *border = s->border;
+  i8ie_attn_mat m{};
+  m.ptr = (uint8_t*)s->device_ptr() + off;
+  m.batch_stride = (int64_t)ch * (shp[2] + 2 * s->border) * (shp[3] + 2 * s->border);
+  m.token_stride = (int64_t)ch;
+  m.s8 = s->s8 ? 1 : 0;
+  return m;
+}
+Tensor<u8_t> attention_window_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, ssize_t wh, ssize_t ww, float s_s, int zp_s,
+                                 float scale, int zp) {
+  const AttnWindowShape s = attention_window_shape(q, k, v, heads, wh, ww);
+  check_out_qparams("attention", scale, zp);
+  check_out_qparams("attention (scores)", s_s, zp_s);
+  std::vector<Tensor<u8_t>> ops{q};  // share the operands' storage / pending launches
+  if (!s.packed) {
+    ops.push_back(*k);
+    ops.push_back(*v);
+  }
+  for (const auto& t : ops) {
+    if (!std::isfinite(t.scale)) throw std::runtime_error("i8ie: attention: an operand's scale is not finite");
+    need_contents(t);
+  }
+  Tensor<u8_t> out = pending_u8(s.out, scale, (u8_t)zp);
+  const u8_t zp_o = (u8_t)zp, zs = (u8_t)zp_s;
+  // deferred like the global form's result (relu folds in, the consumer's border and re-bias come from the kernel); an operand
+  // that another consumer made bordered is read with its border: no conversion launch
+  auto run = [ops, s, s_s, zs, scale, zp_o](bool relu, int border, bool s8) mutable {
+    auto ss = resolve_operands(ops.data(), ops.size());
+    NhwcCopies copies;
+    i8ie_attention_args g{};
+    i8ie_attention_window win{(int)s.h, (int)s.w, (int)s.wh, (int)s.ww, 0, 0, 0};
+    g.b = (int)s.b; g.heads = (int)s.heads; g.d = (int)s.d; g.tq = g.tk = (int)s.tq;
+    const ssize_t C = s.packed ? 3 * s.c : s.c;
+    const Tensor<u8_t>&tq = ops[0], &tk = ops[s.packed ? 0 : 1], &tv = ops[s.packed ? 0 : 2];
+    g.q = attn_window_operand(ss[0], tq.shape, C, 0, copies, &win.q_border);
+    g.k = attn_window_operand(ss[s.packed ? 0 : 1], tk.shape, C, s.packed ? s.c : 0, copies, &win.k_border);
+    g.v = attn_window_operand(ss[s.packed ? 0 : 2], tv.shape, C, s.packed ? 2 * s.c : 0, copies, &win.v_border);
+    g.s_q = tq.scale; g.s_k = tk.scale; g.s_v = tv.scale; g.s_s = s_s; g.s_o = scale;
+    g.zp_q = tq.zero_point; g.zp_k = tk.zero_point; g.zp_v = tv.zero_point; g.zp_s = zs; g.zp_o = zp_o;
+    g.relu = relu ? 1 : 0;
+    std::shared_ptr<Storage> st = nhwc_storage(s.out, border, zp_o, s8);
+    g.out = i8ie_attn_mat{st->dev, (int64_t)s.c * (s.h + 2 * st->border) * (s.w + 2 * st->border), (int64_t)s.c, st->s8 ? 1 : 0};
+    g.out_h = (int)s.h; g.out_w = (int)s.w; g.out_border = st->border;
+    check(i8ie_attention_window_u8(ctx(), &g, &win));
+    return st;
+  };
+  if (s.packed) out.pend = make_pend(run, {q.pend});
+  else out.pend = make_pend(run, {q.pend, k->pend, v->pend});
+  return out;
+}
 Tensor<float> layer_norm_f32(Tensor<float>& x, const std::shared_ptr<Storage>& gamma, const std::shared_ptr<Storage>& beta, ssize_t channels,
                              float eps) {
   const auto ri = layer_norm_rows(x, channels);

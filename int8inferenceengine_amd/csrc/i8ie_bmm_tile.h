@@ -22,8 +22,16 @@ struct BmmOp {          // an operand as rows x k
   int zp;               // plain zero point
 };
 
+// The byte offset of index i along the strided axis (a row of a K-contiguous operand, a k of a K-strided one).  LinearRows is
+// the operand as BmmOp describes it; attn_mfma's windowed form passes a map of its own (WindowRows, i8ie_attention.hip).
+struct LinearRows {
+  __device__ __forceinline__ int64_t operator()(int i, int64_t stride) const { return (int64_t)i * stride; }
+};
+
 // one 64 x 64 tile of `op` (rows row0.., k k0..) into lds[64][LROW], re-biased, zero-filled outside the operand
-__device__ __forceinline__ void stage_tile(const BmmOp& op, const uint8_t* base, int rows, int K, int row0, int k0, uint8_t* lds) {
+template <class RowMap = LinearRows>
+__device__ __forceinline__ void stage_tile(const BmmOp& op, const uint8_t* base, int rows, int K, int row0, int k0, uint8_t* lds,
+                                           const RowMap& at = RowMap()) {
   const int t = threadIdx.x;
   const uint32_t x8 = op.x & 0xFFu;
   if (op.ks == 1) {  // K-contiguous: a lane moves 16 consecutive k of one row
@@ -31,7 +39,7 @@ __device__ __forceinline__ void stage_tile(const BmmOp& op, const uint8_t* base,
     const int gr = row0 + r, gk = k0 + kc;
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     if (gr < rows && gk < K) {
-      const uint8_t* src = base + (int64_t)gr * op.rs + gk;
+      const uint8_t* src = base + at(gr, op.rs) + gk;
       if (gk + 16 <= K && op.vec == 16) {
         const uint4 v = *reinterpret_cast<const uint4*>(src);
         w[0] = v.x ^ op.x; w[1] = v.y ^ op.x; w[2] = v.z ^ op.x; w[3] = v.w ^ op.x;
@@ -54,7 +62,7 @@ __device__ __forceinline__ void stage_tile(const BmmOp& op, const uint8_t* base,
       const int gk = k0 + kb + i;
       w[i] = 0u;
       if (gk < K && gr < rows) {
-        const uint8_t* src = base + (int64_t)gk * op.ks + gr;
+        const uint8_t* src = base + at(gk, op.ks) + gr;
         if (gr + 4 <= rows && op.vec >= 4) {
           w[i] = *reinterpret_cast<const uint32_t*>(src) ^ op.x;
         } else {

@@ -9,6 +9,7 @@ import numbers
 
 import _CXX_i8ie as _C
 
+from .layer import window_pair as _window_pair
 from .layer import CALIBRATION_METHODS, Activation, Add, Attention, BatchNorm2d, Concat, Conv2d, ConvTranspose2d, GroupNorm, Layer, LayerNorm, Linear, MatMul, Mul, PositionEmbedding, activation_kind, fold_batchnorm
 from .layer import calibration_percentile as _percentile
 from .module import Module
@@ -130,7 +131,7 @@ def softmax(x):
     return Tensor(_C.softmax(x.data))
 
 
-def attention(q, k=None, v=None, heads=1, score_scale=None, score_zero_point=None, scale=None, zero_point=None):
+def attention(q, k=None, v=None, heads=1, score_scale=None, score_zero_point=None, scale=None, zero_point=None, window=None):
     """Multi-head scaled-dot-product attention as one op.  Operands are rank 3 [b, t, c], or rank 4 [n, c, h, w] counted as
     [n, h * w, c] (the engine's NHWC storage as it lies); `q` is [b, tq, c], `k` and `v` are [b, tk, c] (tq != tk is allowed),
     c = heads * d, head h is channels h * d .. h * d + d - 1.  `k = v = None`: `q` is a packed qkv tensor with 3 * heads * d
@@ -139,17 +140,27 @@ def attention(q, k=None, v=None, heads=1, score_scale=None, score_zero_point=Non
     projection that makes q.  FP32 tensors: matmul, softmax, matmul per head in FP32; no quantisation parameter may be given.
     uint8 tensors: per head exactly matmul (-> `score_scale`, `score_zero_point`), softmax, matmul (-> `scale`, `zero_point`)
     of include/i8ie_hip.h, in one launch (i8ie_attention_u8); all four parameters are required.  `i8ie.Attention` is the
-    calibrated form for use inside a Module."""
+    calibrated form for use inside a Module.
+    `window`: None, or an int / a pair (wh, ww): attend inside the non-overlapping wh x ww windows of the map (Twins' locally
+    grouped attention; no shift, mask or bias).  Every operand is then rank 4 with one h x w, the window divides the map and
+    holds at most 32768 pixels (RuntimeError otherwise; TypeError for a window that is no int or pair of ints), and the result
+    is attention on the windows moved into the batch axis, moved back: still one launch (i8ie_attention_window_u8)."""
     if (k is None) != (v is None):
         raise TypeError("attention takes q, k and v, or one packed qkv tensor")
+    win = _window_pair(window)
     kd, vd = (None, None) if k is None else (k.data, v.data)
     params = (score_scale, score_zero_point, scale, zero_point)
     if type(q.data).__name__ == "6TensorIhE":
         if any(p is None for p in params):
             raise TypeError("attention of uint8 tensors needs score_scale, score_zero_point, scale and zero_point")
-        return Tensor(_C.attention(q.data, kd, vd, int(heads), float(score_scale), int(score_zero_point), float(scale), int(zero_point)))
+        qp = (float(score_scale), int(score_zero_point), float(scale), int(zero_point))
+        if win is not None:
+            return Tensor(_C._attention_window(q.data, kd, vd, int(heads), win[0], win[1], *qp))
+        return Tensor(_C.attention(q.data, kd, vd, int(heads), *qp))
     if any(p is not None for p in params):
         raise TypeError("attention of FP32 tensors takes no quantisation parameters")
+    if win is not None:
+        return Tensor(_C._attention_window(q.data, kd, vd, int(heads), win[0], win[1]))
     return Tensor(_C.attention(q.data, kd, vd, int(heads)))
 
 

@@ -393,6 +393,18 @@ class MatMul(Weightless):
         return Tensor(self.layer(a.data, b.data))
 
 
+def window_pair(window):
+    """None, or (wh, ww) of an attention window given as an int or a pair of ints; anything else is a TypeError"""
+    if window is None:
+        return None
+    is_int = lambda a: isinstance(a, numbers.Integral) and not isinstance(a, bool)  # noqa: E731
+    if is_int(window):
+        return int(window), int(window)
+    if isinstance(window, (tuple, list)) and len(window) == 2 and all(is_int(a) for a in window):
+        return int(window[0]), int(window[1])
+    raise TypeError("window must be None, an int or a pair of ints (wh, ww)")
+
+
 class Attention(Weightless):
     """Quantized multi-head attention `y = self.attn(q, k, v)` or, packed, `y = self.attn(qkv)` (additive, not in the
     reference): a layer without weights and with two calibrated parameter sets, the scores' and the output's.
@@ -404,11 +416,18 @@ class Attention(Weightless):
     that makes q.  FP32 tensors go through matmul, softmax, matmul per head in FP32; while preparing, the calibrator samples
     the FP32 scores and the FP32 result, and convert() fixes score_qparams() and output_qparams().  uint8 tensors, after
     convert(), take one launch (include/i8ie_hip.h, i8ie_attention_u8): per head exactly i8ie_bmm_u8, i8ie_softmax_u8,
-    i8ie_bmm_u8.  quantized_state_dict() writes `<attr>.qparams` and `<attr>.score_qparams` = (scale, zero_point)."""
+    i8ie_bmm_u8.  quantized_state_dict() writes `<attr>.qparams` and `<attr>.score_qparams` = (scale, zero_point).
 
-    def __init__(self, heads):
+    `window`: None, or an int / a pair (wh, ww): attention inside the non-overlapping wh x ww windows of rank-4 maps (see
+    `i8ie.attention`), one launch as well (i8ie_attention_window_u8).  While preparing, the calibrator samples the windowed
+    scores [n * windows, heads, wh * ww, wh * ww].  The window is a constructor argument and not part of the saved state."""
+
+    def __init__(self, heads, window=None):
         self.heads = int(heads)
+        self.window = window_pair(window)
         self.layer = _C.Attention(self.heads)
+        if self.window is not None:
+            self.layer._set_window(*self.window)
 
     def __call__(self, q, k=None, v=None):
         if (k is None) != (v is None):
