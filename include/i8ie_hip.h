@@ -1126,6 +1126,52 @@ int i8ie_attention_window_u8(i8ie_ctx* ctx, const i8ie_attention_args* args, con
  * scores [b * nW, heads, T, T].  The calibration path, not tuned. */
 int i8ie_attention_window_f32(i8ie_ctx* ctx, const i8ie_attention_args* args, const i8ie_attention_window* win);
 
+/* ---- shifted-window attention with a relative position bias (Swin) -------------------------------
+ * The windowed form above with a cyclic shift (sh, sw), 0 <= sh < win_h and 0 <= sw < win_w, Swin's region mask, and an
+ * additive fp32 term in the scores.  Map h x w, window wh x ww dividing it, T = wh * ww.
+ * Addressing.  Windows are counted (image, wy, wx) as above.  Token j of window (wy, wx) has the local coordinate
+ * (ly, lx) = (j / ww, j % ww) and the shifted coordinate (ys, xs) = (wy * wh + ly, wx * ww + lx); it is the map pixel
+ * ((ys + sh) mod h, (xs + sw) mod w), and the result token is written to that same pixel.  This is Swin's
+ * roll(-s) -> partition -> attention -> un-partition -> roll(+s) without the two rolls.
+ * Mask.  Swin's region class of a shifted coordinate is, per axis, 0 for ys < h - wh, 1 for ys < h - sh, else 2 (with
+ * sh == 0: 0 everywhere; likewise for x).  Query i may attend key j of its window iff both classes agree.  Because sh < wh,
+ * only the last window row holds classes 1 and 2, and they split exactly where the address wraps; so, equivalently,
+ *     i may attend j  iff  (ly_i >= ylim) == (ly_j >= ylim) and (lx_i >= xlim) == (lx_j >= xlim)
+ * with ylim = wh - sh in the last window row and wh elsewhere, xlim = ww - sw in the last window column and ww elsewhere.
+ * The two forms are equal (tests/test_swin_host.py pins that against Swin's published construction).
+ * Scores with a bias.  B is fp32 [heads][T][T].  With C the exact int32 accumulator of i8ie_bmm_u8 the score is down_scale's
+ * sequence with one more fp32 add,
+ *     deq = ((float)C * s_q) * s_k;   v = (deq + B[h][i][j]) / s_s + (float)zp_s;   then the same clamp and truncation,
+ * every operation IEEE fp32 with no contraction (the order i8ie_posembed uses for its float operand).  Without a bias the
+ * scores are exactly the windowed entry's.
+ * Masked softmax.  For row i with the allowed set A(i), the probabilities are i8ie_softmax_u8 applied to the allowed scores
+ * in ascending j; every other P[i][j] is 0.  A(i) contains i, so it is never empty.  The second product is unchanged and
+ * runs over all T columns: the zeros are ordinary probabilities.
+ * `args` and `win` are read exactly as i8ie_attention_window_u8 reads them; the debug outputs keep the windowed layouts
+ * (scores_dbg_dev holds the biased scores of every (i, j), masked or not).  bias_dev is NULL or float
+ * [heads][T][roundup(T, 4)], the row padding zero (every row 16-byte aligned; a pointer that is not takes attn_direct).
+ * Every argument error, a negative shift and a shift >= the window included, is I8IE_ERR_ARG before any device call.  One
+ * launch, no allocation, capturable.  shift == (0, 0) with bias_dev == NULL gives the windowed entry's bytes (it launches the
+ * windowed instance).  The same two kernels in further instances (attn_mfma_swin with and without the bias epilogue,
+ * attn_direct_swin), chosen as the windowed entry chooses, identical bytes. */
+typedef struct i8ie_attention_swin {
+  int shift_h, shift_w;    /* 0 <= shift_h < win_h, 0 <= shift_w < win_w */
+  const float* bias_dev;   /* NULL or [heads][T][roundup(T, 4)] */
+} i8ie_attention_swin;
+int i8ie_attention_swin_u8(i8ie_ctx* ctx, const i8ie_attention_args* args, const i8ie_attention_window* win,
+                           const i8ie_attention_swin* swin);
+/* FP32 (before convert(), and while calibrating): operands as for i8ie_attention_window_f32.  Per head: i8ie_bmm_f32, a
+ * small kernel, i8ie_softmax_f32, i8ie_bmm_f32 on the shifted windows gathered into the ctx workspace.  The score is
+ * bmm_f32 + B[h][i][j] (one fp32 add); masked entries are left out of the max and the sum and give probability 0 (the small
+ * kernel writes -INFINITY there; expf(-inf) == 0 exactly).  scores_out_dev, when given, receives the biased scores before
+ * masking [b * nW, heads, T, T], all finite.  The calibration path, not tuned. */
+int i8ie_attention_swin_f32(i8ie_ctx* ctx, const i8ie_attention_args* args, const i8ie_attention_window* win,
+                            const i8ie_attention_swin* swin);
+/* Host only: Swin's relative position bias table [(2 wh - 1)(2 ww - 1)][heads] expanded into the dense padded layout
+ * out_host [heads][T][roundup(T, 4)] that bias_dev takes: out[h][i][j] = table[index(i, j)][h] with
+ * index(i, j) = (ly_i - ly_j + wh - 1) * (2 ww - 1) + (lx_i - lx_j + ww - 1); the padding is 0. */
+int i8ie_relative_position_bias(const float* table_host, int wh, int ww, int heads, float* out_host);
+
 /* ---- quantized LayerNorm over the last axis (no counterpart in the reference: every op of it is a contraction, a pointwise
  * map or a window reduction; none takes a statistic of a row at run time) ----------------------------------------------------
  * A row is C bytes a[0..C) with (s_in, zp_in), 1 <= C <= 16384; eps is finite and > 0; the result carries (s_out, zp_out);

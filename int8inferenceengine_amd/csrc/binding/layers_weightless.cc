@@ -107,6 +107,20 @@ class Attention : public Weightless {
     wh_ = wh;
     ww_ = ww;
   }
+  // shift the windows by (sh, sw) with Swin's mask from now on (i8ie.Attention(heads, window=, shift=)); needs a window
+  void set_shift(ssize_t sh, ssize_t sw) {
+    if (wh_ < 1) throw std::runtime_error("i8ie: Attention: a shift needs a window");
+    if (sh < 0 || sw < 0 || sh >= wh_ || sw >= ww_) throw std::runtime_error("i8ie: Attention: the shift must be >= 0 and below the window");
+    swin_.sh = sh;
+    swin_.sw = sw;
+    shifted_ = true;
+  }
+  // Swin's relative position bias table [(2 wh - 1)(2 ww - 1), heads]: expanded and uploaded once, added to the scores from now on
+  void set_score_bias(F32Array table) {
+    if (wh_ < 1) throw std::runtime_error("i8ie: Attention: a relative position bias needs a window");
+    swin_.bias = upload_relative_position_bias(table, wh_, ww_, heads_);
+    shifted_ = true;
+  }
 
  private:
   Tensor<float> run_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v) {
@@ -119,10 +133,11 @@ class Attention : public Weightless {
     return sampled(out);
   }
   Tensor<float> run_window_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v) {
-    if (!is_preparing_ || !score_cal_) return attention_window_f32(q, k, v, heads_, wh_, ww_, nullptr);
+    const SwinArgs* swin = shifted_ ? &swin_ : nullptr;
+    if (!is_preparing_ || !score_cal_) return attention_window_f32(q, k, v, heads_, wh_, ww_, nullptr, swin);
     const AttnWindowShape s = attention_window_shape(q, k, v, heads_, wh_, ww_);
     Tensor<float> scores(std::vector<ssize_t>{s.b * s.windows, s.heads, s.tq, s.tk});
-    Tensor<float> out = attention_window_f32(q, k, v, heads_, wh_, ww_, &scores);
+    Tensor<float> out = attention_window_f32(q, k, v, heads_, wh_, ww_, &scores, swin);
     calib_sample(*score_cal_, scores);
     return sampled(out);
   }
@@ -130,7 +145,7 @@ class Attention : public Weightless {
     if (wh_ > 0) {
       attention_window_shape(q, k, v, heads_, wh_, ww_);
       need_quantized("Attention");
-      return attention_window_u8(q, k, v, heads_, wh_, ww_, score_scale_, score_zp_, scale_, zero_point_);
+      return attention_swin_u8(q, k, v, heads_, wh_, ww_, shifted_ ? &swin_ : nullptr, score_scale_, score_zp_, scale_, zero_point_);
     }
     attention_shape(q, k, v, heads_);
     need_quantized("Attention");
@@ -138,6 +153,8 @@ class Attention : public Weightless {
   }
   ssize_t heads_;
   ssize_t wh_ = 0, ww_ = 0;   // 0: the global form
+  SwinArgs swin_;             // the shift and the uploaded bias of the shifted-window form
+  bool shifted_ = false;      // a shift or a bias was set: i8ie_attention_swin_* in place of i8ie_attention_window_*
   std::unique_ptr<Calibrator> score_cal_;
   float score_scale_ = 1;
   u8_t score_zp_ = 0;
@@ -430,6 +447,8 @@ void bind_weightless_layers(py::module_& m) {
              py::arg("score_zero_point"))
         .def("heads", &Attention::heads)
         .def("_set_window", &Attention::set_window, py::arg("win_h"), py::arg("win_w"))
+        .def("_set_shift", &Attention::set_shift, py::arg("shift_h"), py::arg("shift_w"))
+        .def("_set_score_bias", &Attention::set_score_bias, py::arg("table"))
         .def("__call__", &Attention::forward_f32).def("__call__", &Attention::forward_f32_packed)
         .def("__call__", &Attention::forward_u8).def("__call__", &Attention::forward_u8_packed);
   }

@@ -367,6 +367,31 @@ void bind_ops(py::module_& m) {
   }, py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"), py::arg("win_h"), py::arg("win_w"));
   m.def("_attention_window", &attention_window_u8, py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"),
         py::arg("win_h"), py::arg("win_w"), py::arg("score_scale"), py::arg("score_zero_point"), py::arg("scale"), py::arg("zero_point"));
+  // ... shifted, with Swin's mask and an optional dense bias float32 [heads, T, T] or None, uploaded per call
+  // (i8ie_attention_swin_u8); private: i8ie.attention(window=, shift=, bias=) is the surface
+  auto swin_args = [](ssize_t heads, ssize_t wh, ssize_t ww, ssize_t sh, ssize_t sw, const py::object& bias) {
+    SwinArgs a;
+    a.sh = sh;
+    a.sw = sw;
+    if (!bias.is_none()) {
+      F32Array b = F32Array::ensure(bias);
+      if (!b) throw std::runtime_error("i8ie: attention: bias must be a float32 array");
+      a.bias = upload_score_bias(b, heads, wh * ww);
+    }
+    return a;
+  };
+  m.def("_attention_swin", [swin_args](Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads, ssize_t wh, ssize_t ww, ssize_t sh,
+                                       ssize_t sw, const py::object& bias) {
+    const SwinArgs a = swin_args(heads, wh, ww, sh, sw, bias);
+    return attention_window_f32(q, k, v, heads, wh, ww, nullptr, &a);
+  }, py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"), py::arg("win_h"), py::arg("win_w"), py::arg("shift_h"),
+        py::arg("shift_w"), py::arg("bias"));
+  m.def("_attention_swin", [swin_args](Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, ssize_t wh, ssize_t ww, ssize_t sh,
+                                       ssize_t sw, const py::object& bias, float s_s, int zp_s, float scale, int zp) {
+    const SwinArgs a = swin_args(heads, wh, ww, sh, sw, bias);
+    return attention_swin_u8(q, k, v, heads, wh, ww, &a, s_s, zp_s, scale, zp);
+  }, py::arg("q"), py::arg("k").none(true), py::arg("v").none(true), py::arg("heads"), py::arg("win_h"), py::arg("win_w"), py::arg("shift_h"),
+        py::arg("shift_w"), py::arg("bias"), py::arg("score_scale"), py::arg("score_zero_point"), py::arg("scale"), py::arg("zero_point"));
   // additive: LayerNorm over the channel axis of [n, c, h, w] or the last axis of [m, f] / [b, t, f] (include/i8ie_hip.h,
   // i8ie_layernorm_u8); weight / bias: float32 [channels] or None (ones / zeros); uploaded per call
   m.def("layer_norm", [](Tensor<float>& x, const py::object& w, const py::object& b, float eps) {

@@ -103,6 +103,11 @@ AttnShape attention_shape(const Tensor<T>& q, const Tensor<T>* k, const Tensor<T
 struct AttnWindowShape : AttnShape {
   ssize_t h = 0, w = 0, wh = 0, ww = 0, windows = 0;
 };
+// what the shifted-window form adds: the shift and the device copy of the padded bias [heads][T][roundup(T, 4)] (or none)
+struct SwinArgs {
+  ssize_t sh = 0, sw = 0;
+  std::shared_ptr<Storage> bias;
+};
 template <typename T>
 AttnWindowShape attention_window_shape(const Tensor<T>& q, const Tensor<T>* k, const Tensor<T>* v, ssize_t heads, ssize_t wh, ssize_t ww) {
   if ((k == nullptr) != (v == nullptr)) throw std::runtime_error("i8ie: attention takes q, k and v, or one packed qkv tensor");
@@ -227,9 +232,15 @@ Tensor<float> attention_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v
 Tensor<u8_t> attention_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, float s_s, int zp_s, float scale, int zp);
 // ... inside wh x ww windows of rank-4 maps; `scores` is then [n * windows, heads, wh * ww, wh * ww]
 Tensor<float> attention_window_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads, ssize_t wh, ssize_t ww,
-                                   Tensor<float>* scores);
+                                   Tensor<float>* scores, const SwinArgs* swin = nullptr);
 Tensor<u8_t> attention_window_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, ssize_t wh, ssize_t ww, float s_s, int zp_s,
                                  float scale, int zp);
+// ... shifted by (sh, sw) with Swin's mask and an optional bias (include/i8ie_hip.h, i8ie_attention_swin_u8); swin == nullptr:
+// the windowed form
+Tensor<u8_t> attention_swin_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, ssize_t wh, ssize_t ww, const SwinArgs* swin,
+                               float s_s, int zp_s, float scale, int zp);
+std::shared_ptr<Storage> upload_score_bias(const F32Array& bias, ssize_t heads, ssize_t T);
+std::shared_ptr<Storage> upload_relative_position_bias(const F32Array& table, ssize_t wh, ssize_t ww, ssize_t heads);
 Tensor<float> layer_norm_f32(Tensor<float>& x, const std::shared_ptr<Storage>& gamma, const std::shared_ptr<Storage>& beta, ssize_t channels, float eps);
 Tensor<u8_t> layer_norm_u8(Tensor<u8_t>& in, const std::shared_ptr<Storage>& g, const std::shared_ptr<Storage>& b, ssize_t channels, float eps,
                            float scale, int zp);

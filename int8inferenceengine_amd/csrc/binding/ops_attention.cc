@@ -221,10 +221,34 @@ Tensor<u8_t> attention_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssi
   else out.pend = make_pend(run, {q.pend, k->pend, v->pend});
   return out;
 }
-// FP32, windowed: i8ie_attention_window_f32 on the NCHW tensors (part, i8ie_attention_f32, unpart)
+// the shift of a shifted-window call against its window: a RuntimeError before any device call
+void check_shift(ssize_t wh, ssize_t ww, const SwinArgs& sw) {
+  if (sw.sh < 0 || sw.sw < 0 || sw.sh >= wh || sw.sw >= ww) throw std::runtime_error("i8ie: attention: the shift must be >= 0 and below the window");
+}
+// a dense bias [heads, T, T] in i8ie_attention_swin's padded layout, on the device
+std::shared_ptr<Storage> upload_score_bias(const F32Array& bias, ssize_t heads, ssize_t T) {
+  if (bias.ndim() != 3 || bias.shape(0) != heads || bias.shape(1) != T || bias.shape(2) != T)
+    throw std::runtime_error("i8ie: attention: bias must be float32 [heads, wh * ww, wh * ww]");
+  const ssize_t T4 = (T + 3) / 4 * 4;
+  std::vector<float> padded((size_t)(heads * T * T4), 0.0f);
+  for (ssize_t r = 0; r < heads * T; ++r) std::copy(bias.data() + r * T, bias.data() + (r + 1) * T, padded.begin() + r * T4);
+  return upload_f32(padded);
+}
+// Swin's table [(2 wh - 1)(2 ww - 1), heads] expanded by i8ie_relative_position_bias, on the device
+std::shared_ptr<Storage> upload_relative_position_bias(const F32Array& table, ssize_t wh, ssize_t ww, ssize_t heads) {
+  if (table.ndim() != 2 || table.shape(0) != (2 * wh - 1) * (2 * ww - 1) || table.shape(1) != heads)
+    throw std::runtime_error("i8ie: Attention: the relative position bias table must be float32 [(2 wh - 1)(2 ww - 1), heads]");
+  const ssize_t T = wh * ww, T4 = (T + 3) / 4 * 4;
+  std::vector<float> dense((size_t)(heads * T * T4));
+  check(i8ie_relative_position_bias(table.data(), (int)wh, (int)ww, (int)heads, dense.data()));
+  return upload_f32(dense);
+}
+// FP32, windowed: i8ie_attention_window_f32 on the NCHW tensors (part, i8ie_attention_f32, unpart); with `swin` the shifted
+// form, i8ie_attention_swin_f32
 Tensor<float> attention_window_f32(Tensor<float>& q, Tensor<float>* k, Tensor<float>* v, ssize_t heads, ssize_t wh, ssize_t ww,
-                                   Tensor<float>* scores) {
+                                   Tensor<float>* scores, const SwinArgs* swin) {
   const AttnWindowShape s = attention_window_shape(q, k, v, heads, wh, ww);
+  if (swin) check_shift(wh, ww, *swin);
   Tensor<float> out(s.out);
   Tensor<float>* ts[3] = {&q, s.packed ? &q : k, s.packed ? &q : v};
   const ssize_t C = s.packed ? 3 * s.c : s.c, hw = s.h * s.w;
@@ -236,7 +260,12 @@ Tensor<float> attention_window_f32(Tensor<float>& q, Tensor<float>* k, Tensor<fl
   g.out_h = (int)s.h; g.out_w = (int)s.w;
   g.scores_out_dev = scores ? scores->dptr() : nullptr;
   i8ie_attention_window win{(int)s.h, (int)s.w, (int)s.wh, (int)s.ww, 0, 0, 0};
-  check(i8ie_attention_window_f32(ctx(), &g, &win));
+  if (swin) {
+    const i8ie_attention_swin sw{(int)swin->sh, (int)swin->sw, swin->bias ? (const float*)swin->bias->dev : nullptr};
+    check(i8ie_attention_swin_f32(ctx(), &g, &win, &sw));
+  } else {
+    check(i8ie_attention_window_f32(ctx(), &g, &win));
+  }
   return out;
 }
 // A u8 map operand of the windowed form as it lies: NHWC under its own dims is read in place, border and re-bias included
@@ -254,7 +283,15 @@ i8ie_attn_mat attn_window_operand(std::shared_ptr<Storage> s, const std::vector<
 }
 Tensor<u8_t> attention_window_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, ssize_t wh, ssize_t ww, float s_s, int zp_s,
                                  float scale, int zp) {
+  return attention_swin_u8(q, k, v, heads, wh, ww, nullptr, s_s, zp_s, scale, zp);
+}
+// ... and with `swin` the shifted form (i8ie_attention_swin_u8): the same deferred result, the bias kept alive by the launch
+Tensor<u8_t> attention_swin_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>* v, ssize_t heads, ssize_t wh, ssize_t ww, const SwinArgs* swin,
+                               float s_s, int zp_s, float scale, int zp) {
   const AttnWindowShape s = attention_window_shape(q, k, v, heads, wh, ww);
+  if (swin) check_shift(wh, ww, *swin);
+  const bool shifted = swin != nullptr;
+  const SwinArgs sa = swin ? *swin : SwinArgs{};
   check_out_qparams("attention", scale, zp);
   check_out_qparams("attention (scores)", s_s, zp_s);
   std::vector<Tensor<u8_t>> ops{q};  // share the operands' storage / pending launches
@@ -270,7 +307,7 @@ Tensor<u8_t> attention_window_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>*
   const u8_t zp_o = (u8_t)zp, zs = (u8_t)zp_s;
   // deferred like the global form's result (relu folds in, the consumer's border and re-bias come from the kernel); an operand
   // that another consumer made bordered is read with its border: no conversion launch
-  auto run = [ops, s, s_s, zs, scale, zp_o](bool relu, int border, bool s8) mutable {
+  auto run = [ops, s, s_s, zs, scale, zp_o, shifted, sa](bool relu, int border, bool s8) mutable {
     auto ss = resolve_operands(ops.data(), ops.size());
     NhwcCopies copies;
     i8ie_attention_args g{};
@@ -287,7 +324,12 @@ Tensor<u8_t> attention_window_u8(Tensor<u8_t>& q, Tensor<u8_t>* k, Tensor<u8_t>*
     std::shared_ptr<Storage> st = nhwc_storage(s.out, border, zp_o, s8);
     g.out = i8ie_attn_mat{st->dev, (int64_t)s.c * (s.h + 2 * st->border) * (s.w + 2 * st->border), (int64_t)s.c, st->s8 ? 1 : 0};
     g.out_h = (int)s.h; g.out_w = (int)s.w; g.out_border = st->border;
-    check(i8ie_attention_window_u8(ctx(), &g, &win));
+    if (shifted) {
+      const i8ie_attention_swin sw{(int)sa.sh, (int)sa.sw, sa.bias ? (const float*)sa.bias->dev : nullptr};
+      check(i8ie_attention_swin_u8(ctx(), &g, &win, &sw));
+    } else {
+      check(i8ie_attention_window_u8(ctx(), &g, &win));
+    }
     return st;
   };
   if (s.packed) out.pend = make_pend(run, {q.pend});

@@ -40,6 +40,16 @@
 // count (image, window) as the batch) is the same code; without WIN the kernels compile to what they were.
 //   FP32         part / unpart: gather the windows of NCHW floats into [n * nW, T, c] in the ctx workspace, i8ie_attention_f32
 //                on them, scatter the result back.  The calibration path.
+//
+// The shifted-window form (i8ie_attention_swin_u8 / _f32): Swin's cyclic shift, region mask and relative
+// position bias inside the same launch, a third instance <WIN, SWIN> of both kernels.  The shift is a change of the row map
+// (ShiftedWindowRows: the window origin moves by the shift and a token past the map's edge subtracts one map height / width);
+// the mask is the same predicate as the wrap (wrap_flags: a query attends the keys whose flags equal its own), applied in
+// phase 2 from one register of column flags per lane, block-uniformly skipped where the window does not touch the map's last
+// row or column; the bias is one fp32 add in the score epilogue (biased_score), read as one float4 per pack.  Without SWIN
+// every added line is compiled out.
+//   FP32         part / unpart with the shift, and per head i8ie_bmm_f32, a small kernel (bias, scores_out_dev, -inf into masked
+//                entries), i8ie_softmax_f32, i8ie_bmm_f32.
 #include <algorithm>
 #include <cmath>
 
@@ -73,6 +83,10 @@ struct AttnParams {
   uint32_t w_mult;      // ceil(2^30 / ww): j / ww == umulhi(j << 2, w_mult) for j, ww <= 32768
   int wh, ww, nwx, nw;  // the window; windows per map row and per image
   int64_t q_pitch, k_pitch, v_pitch, o_pitch;  // bytes between two physical map rows of each operand and of the result
+  // the shifted-window form alone (SWIN kernels)
+  int sh, sw, map_h, map_w;  // the shift, 0 <= sh < wh and 0 <= sw < ww; the map
+  const float* bias;         // NULL or [H][T][T4] fp32, T4 = roundup(T, 4), the row padding zero
+  int T4;
 };
 
 // token j of a window -> the byte offset of its pixel from the window's first pixel; `stride` is one physical pixel
@@ -85,28 +99,49 @@ struct WindowRows {
     return (int64_t)y * pitch + (int64_t)(j - y * ww) * stride;
   }
 };
-template <bool WIN> struct RowsOf;
-template <> struct RowsOf<false> {
-  using type = LinearRows;
-  static __device__ __forceinline__ type make(const AttnParams&, int64_t) { return LinearRows(); }
+// The shifted window (SWIN): the window's origin is (wy * wh + sh, wx * ww + sw), always inside the map,
+// and a token whose local row is at or beyond ylim (column: xlim) lies past the map's edge and wraps: it subtracts one whole
+// map height (width) of bytes.  Only the last window row has ylim = wh - sh < wh, only the last window column xlim < ww; the
+// same two comparisons are the region mask (wrap_flags below).
+struct ShiftedWindowRows {
+  uint32_t mult;
+  int ww, ylim, xlim;
+  int64_t pitch, ywrap, xwrap;   // ywrap = map_h * pitch, xwrap = map_w * stride
+  __device__ __forceinline__ int64_t operator()(int j, int64_t stride) const {
+    const int y = (int)__umulhi((uint32_t)j << 2, mult);
+    const int x = j - y * ww;
+    int64_t off = (int64_t)y * pitch + (int64_t)x * stride;
+    if (y >= ylim) off -= ywrap;
+    if (x >= xlim) off -= xwrap;
+    return off;
+  }
 };
-template <> struct RowsOf<true> {
-  using type = WindowRows;
-  static __device__ __forceinline__ type make(const AttnParams& p, int64_t pitch) { return WindowRows{p.w_mult, p.ww, pitch}; }
-};
+// bit 0: token j's row wraps, bit 1: its column does.  Query i may attend key j iff their flags are equal: Swin's region
+// classes 1 | 2 on an axis exist in the last window row (column) alone and split it where the address wraps.
+__device__ __forceinline__ uint32_t wrap_flags(int j, uint32_t mult, int ww, int ylim, int xlim) {
+  const int y = (int)__umulhi((uint32_t)j << 2, mult);
+  return (y >= ylim ? 1u : 0u) | (j - y * ww >= xlim ? 2u : 0u);
+}
 
 // A block's sequence `seq` is a batch item, or with WIN one (image, window): the image, and the byte offsets of the window's
-// first pixel inside the image for q, k, v and the result.
-template <bool WIN>
+// first pixel inside the image for q, k, v and the result; with SWIN the origin is shifted and the block has its two limits.
+template <bool WIN, bool SWIN>
 struct AttnSeq {
   int batch;
   int64_t q0 = 0, k0 = 0, v0 = 0, o0 = 0;
+  int ylim = 0, xlim = 0;
   __device__ __forceinline__ AttnSeq(const AttnParams& p, int seq) : batch(seq) {
     if (WIN) {
       batch = seq / p.nw;
       const int wi = seq - batch * p.nw;
       const int wy = wi / p.nwx, wx = wi - wy * p.nwx;
-      const int64_t y0 = (int64_t)wy * p.wh, x0 = (int64_t)wx * p.ww;
+      int64_t y0 = (int64_t)wy * p.wh, x0 = (int64_t)wx * p.ww;
+      if (SWIN) {
+        y0 += p.sh;
+        x0 += p.sw;
+        ylim = wy == p.nw / p.nwx - 1 ? p.wh - p.sh : p.wh;
+        xlim = wx == p.nwx - 1 ? p.ww - p.sw : p.ww;
+      }
       q0 = y0 * p.q_pitch + x0 * p.Q.rs;
       k0 = y0 * p.k_pitch + x0 * p.K.rs;
       v0 = y0 * p.v_pitch + x0 * p.V.ks;
@@ -115,19 +150,105 @@ struct AttnSeq {
   }
 };
 
+template <bool WIN, bool SWIN> struct RowsOf;
+template <> struct RowsOf<false, false> {
+  using type = LinearRows;
+  static __device__ __forceinline__ type make(const AttnParams&, const AttnSeq<false, false>&, int64_t, int64_t) { return LinearRows(); }
+};
+template <> struct RowsOf<true, false> {
+  using type = WindowRows;
+  static __device__ __forceinline__ type make(const AttnParams& p, const AttnSeq<true, false>&, int64_t pitch, int64_t) {
+    return WindowRows{p.w_mult, p.ww, pitch};
+  }
+};
+template <> struct RowsOf<true, true> {
+  using type = ShiftedWindowRows;
+  static __device__ __forceinline__ type make(const AttnParams& p, const AttnSeq<true, true>& sq, int64_t pitch, int64_t stride) {
+    return ShiftedWindowRows{p.w_mult, p.ww, sq.ylim, sq.xlim, pitch, (int64_t)p.map_h * pitch, (int64_t)p.map_w * stride};
+  }
+};
+
 __device__ __forceinline__ int64_t out_token_index(const AttnParams& p, int i) {
   return p.pix_pad ? (int64_t)i + (int64_t)(i / p.pix_w) * p.pix_pad : (int64_t)i;
 }
 // the byte offset of result token i from the sequence's first result byte
-template <bool WIN>
-__device__ __forceinline__ int64_t out_token_offset(const AttnParams& p, int i) {
-  if (WIN) return WindowRows{p.w_mult, p.ww, p.o_pitch}(i, p.o_tok);
+template <bool WIN, bool SWIN>
+__device__ __forceinline__ int64_t out_token_offset(const AttnParams& p, const AttnSeq<WIN, SWIN>& sq, int i) {
+  if (WIN) return RowsOf<WIN, SWIN>::make(p, sq, p.o_pitch, p.o_tok)(i, p.o_tok);
   return out_token_index(p, i) * p.o_tok;
+}
+
+// The biased score (include/i8ie_hip.h, "scores with a bias"): down_scale's sequence with one more fp32 add, every operation
+// IEEE fp32 and uncontracted.  There is no estimate: deq and the bias may cancel, so no bound on the estimate's error holds.
+__device__ __forceinline__ uint32_t biased_score(int c, float bias, const I8ieRequant& q) {
+  const float deq = ((float)c * q.sa) * q.sb;
+  const float v = (deq + bias) / q.sc + q.zpf;
+  return (v >= 255.0f) ? 255u : ((v < 0.0f) ? 0u : (uint32_t)(int)v);
+}
+
+// Phase 2 of attn_mfma for the strip rows of one wave in a SWIN block whose window touches the map's last row or column: a
+// column takes part in the max, in S and in the row's sum iff its wrap flags (two bits per column of the lane's 16, packed in
+// `cflags`) equal the row's; every other probability is 0.  (Every other block runs the kernel's own phase 2, as it was.)
+__device__ __forceinline__ void softmax_masked_strip_rows(const AttnParams& p, uint8_t* strip, const uint32_t* E, uint32_t* psum, int wave, int lane,
+                                                   int m0, int64_t dbg_head, uint32_t cflags, int ylim, int xlim) {
+  for (int lr = wave * 16; lr < wave * 16 + 16; ++lr) {
+    uint8_t* row = strip + lr * p.SP;
+    const int m = m0 + lr;
+    // (a row >= tq is never stored: it takes token 0's flags, whose set is not empty)
+    const uint32_t rflags = wrap_flags(m < p.Tq ? m : 0, p.w_mult, p.ww, ylim, xlim) * 0x55555555u;
+    const uint32_t differ = cflags ^ rflags;   // column i is masked iff bits 2i, 2i + 1 are not both 0
+    uint32_t v[16];
+    uint32_t mx = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int j = 4 * (lane + 64 * i);
+      uint32_t w = 0;
+      if (j < p.Tk) w = *reinterpret_cast<const uint32_t*>(row + j);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const bool in = j + b < p.Tk && ((differ >> (2 * (4 * i + b))) & 3u) == 0u;
+        v[4 * i + b] = in ? (w >> (8 * b)) & 0xFFu : 0u;   // (a masked 0 never raises the max)
+        mx = v[4 * i + b] > mx ? v[4 * i + b] : mx;
+      }
+    }
+    mx = wave_max(mx);
+    uint32_t sum = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int j = 4 * (lane + 64 * (i >> 2)) + (i & 3);
+      v[i] = E[mx - v[i]];
+      sum += j < p.Tk && ((differ >> (2 * i)) & 3u) == 0u ? v[i] : 0u;
+    }
+    const uint32_t S = wave_sum(sum);
+    const float rinv = 1.0f / (float)S;
+    const uint32_t half = S >> 1;
+    uint32_t ps = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int j = 4 * (lane + 64 * i);
+      if (j >= p.Tk64) continue;
+      uint32_t w = 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        if (j + b < p.Tk) {
+          uint32_t pr = 0;
+          if (((differ >> (2 * (4 * i + b))) & 3u) == 0u) pr = div_by(v[4 * i + b] * 256u + half, S, rinv);
+          ps += pr;
+          w |= (pr ^ 0x80u) << (8 * b);
+          if (p.pdbg && m < p.Tq) p.pdbg[(dbg_head + m) * p.Tk + j + b] = (uint8_t)pr;
+        }
+      }
+      *reinterpret_cast<uint32_t*>(row + j) = w;
+    }
+    ps = wave_sum(ps);
+    if (lane == 0) psum[lr] = ps;
+  }
 }
 
 extern __shared__ __attribute__((aligned(16))) uint8_t attn_smem[];
 
-template <bool WIN>
+// BIAS (SWIN alone): the score epilogue adds B; a shifted launch without a bias does not carry that epilogue's registers
+template <bool WIN, bool SWIN, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnParams p, SoftmaxTable tab) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[2 * TM * LROW];
   __shared__ uint32_t E[256];
@@ -139,14 +260,15 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnParams p, SoftmaxTab
   E[tid] = tab.e[tid];
   const int tile = blockIdx.x % p.tiles_q, bh = blockIdx.x / p.tiles_q;
   const int h = bh % p.H, seq = bh / p.H;
-  const AttnSeq<WIN> sq(p, seq);
+  const AttnSeq<WIN, SWIN> sq(p, seq);
   const int batch = sq.batch;
   const int m0 = tile * TM;
   const uint8_t* Qb = p.Q.p + (int64_t)batch * p.Q.batch + sq.q0 + (int64_t)h * p.D;
   const uint8_t* Kb = p.K.p + (int64_t)batch * p.K.batch + sq.k0 + (int64_t)h * p.D;
   const uint8_t* Vb = p.V.p + (int64_t)batch * p.V.batch + sq.v0 + (int64_t)h * p.D;
-  const typename RowsOf<WIN>::type q_at = RowsOf<WIN>::make(p, p.q_pitch), k_at = RowsOf<WIN>::make(p, p.k_pitch),
-                                   v_at = RowsOf<WIN>::make(p, p.v_pitch);
+  const typename RowsOf<WIN, SWIN>::type q_at = RowsOf<WIN, SWIN>::make(p, sq, p.q_pitch, p.Q.rs),
+                                         k_at = RowsOf<WIN, SWIN>::make(p, sq, p.k_pitch, p.K.rs),
+                                         v_at = RowsOf<WIN, SWIN>::make(p, sq, p.v_pitch, p.V.ks);
   const int q = lane >> 4, r = lane & 15;
   const int wm = wave >> 1, wn = wave & 1;
   const v4i ones = v4i{0x01010101, 0x01010101, 0x01010101, 0x01010101};
@@ -197,7 +319,15 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnParams p, SoftmaxTab
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             c[e] = (int)((uint32_t)acc[mi][ni][e] - za * (uint32_t)csum[ni][e] - zb * (uint32_t)rsum[mi][e] + kzz);
-          const uint32_t packed = i8ie_requant_pack4(c, p.rq_s, 0, 0.0f);
+          uint32_t packed;
+          if (BIAS) {   // one float4 of B per pack; rows >= T and columns >= T are not read
+            float4 bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (m < p.Tq && nb < p.Tk) bv = *reinterpret_cast<const float4*>(p.bias + ((int64_t)h * p.Tq + m) * p.T4 + nb);
+            packed = biased_score(c[0], bv.x, p.rq_s) | biased_score(c[1], bv.y, p.rq_s) << 8 | biased_score(c[2], bv.z, p.rq_s) << 16 |
+                     biased_score(c[3], bv.w, p.rq_s) << 24;
+          } else {
+            packed = i8ie_requant_pack4(c, p.rq_s, 0, 0.0f);
+          }
           *reinterpret_cast<uint32_t*>(strip + lr * p.SP + nb) = packed;
           if (p.sdbg && m < p.Tq) {
             uint8_t* sp = p.sdbg + (dbg_head + m) * p.Tk + nb;
@@ -212,6 +342,13 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnParams p, SoftmaxTab
   __syncthreads();  // (also: E is complete)
 
   // ---- phase 2: softmax of each strip row over its first tk columns, in place, written back re-biased ----
+  if (SWIN && (sq.ylim < p.wh || sq.xlim < p.ww)) {   // (block-uniform) a window on the map's last row or column: masked
+    uint32_t cflags = 0;   // the wrap flags of the lane's 16 columns, the same for every row
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      cflags |= wrap_flags(4 * (lane + 64 * (i >> 2)) + (i & 3), p.w_mult, p.ww, sq.ylim, sq.xlim) << (2 * i);
+    softmax_masked_strip_rows(p, strip, E, psum, wave, lane, m0, dbg_head, cflags, sq.ylim, sq.xlim);
+  } else
   for (int lr = wave * 16; lr < wave * 16 + 16; ++lr) {
     uint8_t* row = strip + lr * p.SP;
     uint32_t v[16];
@@ -298,7 +435,7 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnParams p, SoftmaxTab
         const int m = m0 + lr;
         if (m >= p.Tq) continue;
         const uint32_t rs = psum[lr] - 128u * (uint32_t)p.Tk;   // the row sum of P' = P - 128 over the true tk
-        uint8_t* orow = p.out + (int64_t)batch * p.o_batch + sq.o0 + out_token_offset<WIN>(p, m) + (int64_t)h * p.D;
+        uint8_t* orow = p.out + (int64_t)batch * p.o_batch + sq.o0 + out_token_offset<WIN, SWIN>(p, sq, m) + (int64_t)h * p.D;
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
           const int nb = n0 + wn * 32 + ni * 16 + 4 * q;
@@ -326,7 +463,9 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnParams p, SoftmaxTab
 }
 
 // one block per (batch item, head, query row); attn_smem holds the row's tk scores, then its probabilities
-template <bool WIN>
+// with SWIN the definition verbatim as well: the biased score for every key, the max, S and the probabilities over the keys
+// whose wrap flags equal the query's, probability 0 for the others
+template <bool WIN, bool SWIN>
 __global__ __launch_bounds__(kThreads) void attn_direct_kernel(AttnParams p, SoftmaxTable tab) {
   __shared__ uint32_t E[256];
   __shared__ uint32_t red[kThreads / 64];
@@ -335,10 +474,14 @@ __global__ __launch_bounds__(kThreads) void attn_direct_kernel(AttnParams p, Sof
   E[tid] = tab.e[tid];
   const int i = blockIdx.x % p.Tq, bh = blockIdx.x / p.Tq;
   const int h = bh % p.H, seq = bh / p.H;
-  const AttnSeq<WIN> sq(p, seq);
+  const AttnSeq<WIN, SWIN> sq(p, seq);
   const int batch = sq.batch;
-  const typename RowsOf<WIN>::type q_at = RowsOf<WIN>::make(p, p.q_pitch), k_at = RowsOf<WIN>::make(p, p.k_pitch),
-                                   v_at = RowsOf<WIN>::make(p, p.v_pitch);
+  const typename RowsOf<WIN, SWIN>::type q_at = RowsOf<WIN, SWIN>::make(p, sq, p.q_pitch, p.Q.rs),
+                                         k_at = RowsOf<WIN, SWIN>::make(p, sq, p.k_pitch, p.K.rs),
+                                         v_at = RowsOf<WIN, SWIN>::make(p, sq, p.v_pitch, p.V.ks);
+  const uint32_t iflags = SWIN ? wrap_flags(i, p.w_mult, p.ww, sq.ylim, sq.xlim) : 0u;
+  auto allowed = [&](int j) { return !SWIN || wrap_flags(j, p.w_mult, p.ww, sq.ylim, sq.xlim) == iflags; };
+  const float* brow = SWIN && p.bias ? p.bias + ((int64_t)h * p.Tq + i) * p.T4 : nullptr;
   const uint32_t xq = (p.Q.x & 0xFFu) ^ 0x80u, xk = (p.K.x & 0xFFu) ^ 0x80u, xv = (p.V.x & 0xFFu) ^ 0x80u;  // to plain bytes
   const uint8_t* qr = p.Q.p + (int64_t)batch * p.Q.batch + sq.q0 + q_at(i, p.Q.rs) + (int64_t)h * p.D;
   const uint8_t* kb = p.K.p + (int64_t)batch * p.K.batch + sq.k0 + (int64_t)h * p.D;
@@ -353,10 +496,10 @@ __global__ __launch_bounds__(kThreads) void attn_direct_kernel(AttnParams p, Sof
       const int bv = (int)((uint32_t)kr[c] ^ xk) - p.K.zp;
       sum += (uint32_t)(av * bv);
     }
-    const uint32_t s = (uint32_t)i8ie_requant_exact((float)(int)sum, p.rq_s, 0);
+    const uint32_t s = SWIN && brow ? biased_score((int)sum, brow[j], p.rq_s) : (uint32_t)i8ie_requant_exact((float)(int)sum, p.rq_s, 0);
     sc[j] = (uint8_t)s;
     if (p.sdbg) p.sdbg[dbg_row + j] = (uint8_t)s;
-    mx = s > mx ? s : mx;
+    if (allowed(j)) mx = s > mx ? s : mx;
   }
   mx = wave_max(mx);
   if (lane == 0) red[wave] = mx;
@@ -366,7 +509,8 @@ __global__ __launch_bounds__(kThreads) void attn_direct_kernel(AttnParams p, Sof
   for (int w = 1; w < kThreads / 64; ++w) mx = red[w] > mx ? red[w] : mx;
   __syncthreads();
   uint32_t sum = 0;
-  for (int j = tid; j < p.Tk; j += kThreads) sum += E[mx - (uint32_t)sc[j]];
+  for (int j = tid; j < p.Tk; j += kThreads)
+    if (allowed(j)) sum += E[mx - (uint32_t)sc[j]];
   sum = wave_sum(sum);
   if (lane == 0) red[wave] = sum;
   __syncthreads();
@@ -376,7 +520,7 @@ __global__ __launch_bounds__(kThreads) void attn_direct_kernel(AttnParams p, Sof
   const float rinv = 1.0f / (float)S;
   const uint32_t half = S >> 1;
   for (int j = tid; j < p.Tk; j += kThreads) {   // (a lane rewrites only the bytes it read itself)
-    const uint32_t pr = div_by(E[mx - (uint32_t)sc[j]] * 256u + half, S, rinv);
+    const uint32_t pr = allowed(j) ? div_by(E[mx - (uint32_t)sc[j]] * 256u + half, S, rinv) : 0u;
     sc[j] = (uint8_t)pr;
     if (p.pdbg) p.pdbg[dbg_row + j] = (uint8_t)pr;
   }
@@ -390,7 +534,7 @@ __global__ __launch_bounds__(kThreads) void attn_direct_kernel(AttnParams p, Sof
     const int64_t col = (int64_t)h * p.D + c;
     if (p.acc) p.acc[((int64_t)seq * p.Tq + i) * ((int64_t)p.H * p.D) + col] = (int)acc;
     const int qv = i8ie_requant_exact((float)(int)acc, p.rq_o, p.lo);
-    p.out[(int64_t)batch * p.o_batch + sq.o0 + out_token_offset<WIN>(p, i) + col] = (uint8_t)((uint32_t)qv ^ (p.xout & 0xFFu));
+    p.out[(int64_t)batch * p.o_batch + sq.o0 + out_token_offset<WIN, SWIN>(p, sq, i) + col] = (uint8_t)((uint32_t)qv ^ (p.xout & 0xFFu));
   }
 }
 
@@ -401,23 +545,53 @@ struct PartParams {
   int64_t batch, chan;      // floats between two images / two channels of the map
 };
 // item e = (seq, j, col) of the dense [n * nW, T, c] side; the map element it mirrors
-__device__ __forceinline__ int64_t part_map_index(const PartParams& p, int64_t e, int wh) {
+// (sh, sw): the shift of the shifted-window form, (0, 0) otherwise; H is then the map's height
+__device__ __forceinline__ int64_t part_map_index(const PartParams& p, int64_t e, int wh, int sh = 0, int sw = 0, int H = 0) {
   const int col = (int)(e % p.c);
   const int64_t t = e / p.c;
   const int j = (int)(t % p.T);
   const int64_t seq = t / p.T;
   const int wi = (int)(seq % p.nw);
   const int64_t img = seq / p.nw;
-  const int y = (wi / p.nwx) * wh + j / p.ww, x = (wi % p.nwx) * p.ww + j % p.ww;
+  int y = (wi / p.nwx) * wh + j / p.ww + sh, x = (wi % p.nwx) * p.ww + j % p.ww + sw;
+  if (sh && y >= H) y -= H;
+  if (sw && x >= p.W) x -= p.W;
   return img * p.batch + (int64_t)col * p.chan + (int64_t)y * p.W + x;
 }
-__global__ __launch_bounds__(kThreads) void attn_part_f32_kernel(const float* __restrict__ map, float* __restrict__ win, PartParams p, int wh) {
+__global__ __launch_bounds__(kThreads) void attn_part_f32_kernel(const float* __restrict__ map, float* __restrict__ win, PartParams p, int wh,
+                                                                 int sh, int sw, int H) {
   for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < p.total; e += (int64_t)gridDim.x * kThreads)
-    win[e] = map[part_map_index(p, e, wh)];
+    win[e] = map[part_map_index(p, e, wh, sh, sw, H)];
 }
-__global__ __launch_bounds__(kThreads) void attn_unpart_f32_kernel(const float* __restrict__ win, float* __restrict__ map, PartParams p, int wh) {
+__global__ __launch_bounds__(kThreads) void attn_unpart_f32_kernel(const float* __restrict__ win, float* __restrict__ map, PartParams p, int wh,
+                                                                   int sh, int sw, int H) {
   for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < p.total; e += (int64_t)gridDim.x * kThreads)
-    map[part_map_index(p, e, wh)] = win[e];
+    map[part_map_index(p, e, wh, sh, sw, H)] = win[e];
+}
+
+// The FP32 shifted-window form between its two products: scores [seqs][T][T] of one head += B[T][T4]; the biased scores go to
+// `keep` (NULL, or the head's slice of scores_out_dev, `keep_seq` floats between two windows) before the mask; a masked entry
+// then becomes -inf, which i8ie_softmax_f32 leaves out of the max and turns into expf(-inf) == 0 exactly.
+struct SwinF32Params {
+  int64_t total;   // seqs * T * T
+  int T, T4, ww, wh, nwx, nw, sh, sw;
+  int64_t keep_seq;
+};
+__global__ __launch_bounds__(kThreads) void attn_swin_bias_mask_f32_kernel(float* __restrict__ s, const float* __restrict__ bias,
+                                                                           float* __restrict__ keep, SwinF32Params p) {
+  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < p.total; e += (int64_t)gridDim.x * kThreads) {
+    const int j = (int)(e % p.T);
+    const int64_t t = e / p.T;
+    const int i = (int)(t % p.T);
+    const int64_t seq = t / p.T;
+    const int wi = (int)(seq % p.nw);
+    const int ylim = wi / p.nwx == p.nw / p.nwx - 1 ? p.wh - p.sh : p.wh, xlim = wi % p.nwx == p.nwx - 1 ? p.ww - p.sw : p.ww;
+    float v = s[e];
+    if (bias) v = v + bias[(int64_t)i * p.T4 + j];
+    if (keep) keep[seq * p.keep_seq + (int64_t)i * p.T + j] = v;
+    const bool same = (i / p.ww >= ylim) == (j / p.ww >= ylim) && (i % p.ww >= xlim) == (j % p.ww >= xlim);
+    s[e] = same ? v : -INFINITY;
+  }
 }
 
 bool mat_ok(const i8ie_attn_mat& m, int64_t c) { return m.ptr != nullptr && m.batch_stride >= 0 && m.token_stride >= c; }
@@ -459,13 +633,31 @@ int check_window(const i8ie_attention_args* g, const i8ie_attention_window* w, b
   return I8IE_OK;
 }
 
+// the scales of a u8 entry (the shifted-window entry; the two older entries spell the same rule out)
+int check_u8_scales(const i8ie_attention_args* g) {
+  I8IE_REQUIRE(std::isfinite(g->s_q) && std::isfinite(g->s_k) && std::isfinite(g->s_v) && std::isfinite(g->s_s) && std::isfinite(g->s_o) &&
+                   g->s_s > 0.0f && g->s_o > 0.0f,
+               "scales must be finite, s_s > 0 and s_o > 0");
+  return I8IE_OK;
+}
+
+// what the two shifted-window entries add to check_window
+int check_swin(const i8ie_attention_window* w, const i8ie_attention_swin* s) {
+  I8IE_REQUIRE(s->shift_h >= 0 && s->shift_w >= 0 && s->shift_h < w->win_h && s->shift_w < w->win_w, "a shift is negative or not below the window");
+  return I8IE_OK;
+}
+
 // the first byte of interior pixel (0, 0) of a bordered [.][h + 2B][w + 2B][.] buffer, and the bytes of one of its rows
 int64_t padded(int w, int border) { return (int64_t)w + 2 * (int64_t)border; }
 int64_t interior_origin(int w, int border, int64_t pixel_stride) { return ((int64_t)border * padded(w, border) + border) * pixel_stride; }
 
 // What both u8 entries do once their arguments are checked.  win == nullptr: the global form, the result's pixel rule in
 // pix_w / pix_pad and `origin`, the first result byte's offset.
-int launch_u8(i8ie_ctx* ctx, const i8ie_attention_args* g, const i8ie_attention_window* win, int pix_w, int pix_pad, int64_t origin) {
+// swin != nullptr (with win): the shifted-window kernels.
+int launch_u8(i8ie_ctx* ctx, const i8ie_attention_args* g, const i8ie_attention_window* win, int pix_w, int pix_pad, int64_t origin,
+              const i8ie_attention_swin* swin = nullptr) {
+  // (no shift and no bias is the windowed form by definition: it takes the windowed instance)
+  if (swin && swin->shift_h == 0 && swin->shift_w == 0 && swin->bias_dev == nullptr) swin = nullptr;
   AttnParams p{};
   const uint32_t plain = 0x80808080u;
   const uint8_t *qp = (const uint8_t*)g->q.ptr, *kp = (const uint8_t*)g->k.ptr, *vp = (const uint8_t*)g->v.ptr;
@@ -483,6 +675,12 @@ int launch_u8(i8ie_ctx* ctx, const i8ie_attention_args* g, const i8ie_attention_
     p.v_pitch = padded(win->map_w, win->v_border) * g->v.token_stride;
     p.o_pitch = padded(win->map_w, g->out_border) * g->out.token_stride;
     seqs *= p.nw;
+  }
+  if (swin) {
+    p.sh = swin->shift_h; p.sw = swin->shift_w;
+    p.map_h = win->map_h; p.map_w = win->map_w;
+    p.bias = swin->bias_dev;
+    p.T4 = (g->tq + 3) / 4 * 4;
   }
   p.Q = BmmOp{qp, g->q.batch_stride, g->q.token_stride, 1, g->q.s8 ? 0u : plain, 16, (int)g->zp_q};
   p.K = BmmOp{kp, g->k.batch_stride, g->k.token_stride, 1, g->k.s8 ? 0u : plain, 16, (int)g->zp_k};
@@ -508,30 +706,39 @@ int launch_u8(i8ie_ctx* ctx, const i8ie_attention_args* g, const i8ie_attention_
   const int64_t blocks = seqs * g->heads * p.tiles_q;
   const bool mfma = (ctx->options & 1) == 0 && g->d % 16 == 0 && g->tk <= kStripMaxTk && aligned16(g->q) && aligned16(g->k) &&
                     aligned16(g->v) && fits31(g->q) && fits31(g->k) && fits31(g->v) &&
-                    (g->acc_dbg_dev == nullptr || aligned_to(g->acc_dbg_dev, 4));
+                    (g->acc_dbg_dev == nullptr || aligned_to(g->acc_dbg_dev, 4)) && (!swin || aligned_to(swin->bias_dev, 16));
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   const double pairs = (double)seqs * g->heads * g->tq * g->tk;
-  I8ieProfScope prof(ctx, mfma ? (win ? "attn_mfma_win" : "attn_mfma") : (win ? "attn_direct_win" : "attn_direct"), 4.0 * pairs * g->d,
+  I8ieProfScope prof(ctx, mfma ? (swin ? "attn_mfma_swin" : win ? "attn_mfma_win" : "attn_mfma")
+                                 : (swin ? "attn_direct_swin" : win ? "attn_direct_win" : "attn_direct"),
+                     4.0 * pairs * g->d,
                      (double)seqs * g->heads * g->d * (2.0 * g->tq + 2.0 * g->tk));
   if (mfma) {
     const size_t lds = (size_t)TM * p.SP;
     // The flag is read and written without a lock, and devices 64 apart share one: either can only repeat the attribute call,
     // which is idempotent (the same kernel, the same limit).  A forward is run eagerly before it is captured into a graph
     // (GraphedForward warms up), so the call is made outside any capture; launch_pc_t (i8ie_pconv.hip) does the same.
-    static bool raised[2][64] = {};
-    const int dev = ctx->device & 63;
-    if (!raised[win ? 1 : 0][dev]) {
-      const void* fn = win ? reinterpret_cast<const void*>(&attn_mfma_kernel<true>) : reinterpret_cast<const void*>(&attn_mfma_kernel<false>);
+    static bool raised[4][64] = {};
+    const bool biased = swin && swin->bias_dev;
+    const int dev = ctx->device & 63, form = biased ? 3 : swin ? 2 : win ? 1 : 0;
+    if (!raised[form][dev]) {
+      const void* fn = biased ? reinterpret_cast<const void*>(&attn_mfma_kernel<true, true, true>)
+                       : swin ? reinterpret_cast<const void*>(&attn_mfma_kernel<true, true>)
+                       : win  ? reinterpret_cast<const void*>(&attn_mfma_kernel<true, false>)
+                              : reinterpret_cast<const void*>(&attn_mfma_kernel<false, false>);
       I8IE_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, TM * (kStripMaxTk + kStripPad)));
-      raised[win ? 1 : 0][dev] = true;
+      raised[form][dev] = true;
     }
-    if (win) attn_mfma_kernel<true><<<(unsigned)blocks, 256, lds, ctx->stream>>>(p, tab);
-    else attn_mfma_kernel<false><<<(unsigned)blocks, 256, lds, ctx->stream>>>(p, tab);
+    if (biased) attn_mfma_kernel<true, true, true><<<(unsigned)blocks, 256, lds, ctx->stream>>>(p, tab);
+    else if (swin) attn_mfma_kernel<true, true><<<(unsigned)blocks, 256, lds, ctx->stream>>>(p, tab);
+    else if (win) attn_mfma_kernel<true, false><<<(unsigned)blocks, 256, lds, ctx->stream>>>(p, tab);
+    else attn_mfma_kernel<false, false><<<(unsigned)blocks, 256, lds, ctx->stream>>>(p, tab);
   } else {
     const size_t lds = i8ie_align_up((size_t)g->tk, 16);
     const unsigned rows = (unsigned)(seqs * g->heads * g->tq);
-    if (win) attn_direct_kernel<true><<<rows, kThreads, lds, ctx->stream>>>(p, tab);
-    else attn_direct_kernel<false><<<rows, kThreads, lds, ctx->stream>>>(p, tab);
+    if (swin) attn_direct_kernel<true, true><<<rows, kThreads, lds, ctx->stream>>>(p, tab);
+    else if (win) attn_direct_kernel<true, false><<<rows, kThreads, lds, ctx->stream>>>(p, tab);
+    else attn_direct_kernel<false, false><<<rows, kThreads, lds, ctx->stream>>>(p, tab);
   }
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
@@ -627,7 +834,7 @@ int i8ie_attention_window_f32(i8ie_ctx* ctx, const i8ie_attention_args* g, const
   for (int i = 0; i < 3; ++i) {
     pp.batch = ops[i]->batch_stride;
     pp.chan = ops[i]->token_stride;
-    attn_part_f32_kernel<<<blocks, kThreads, 0, ctx->stream>>>((const float*)ops[i]->ptr, part + i * dense, pp, w->win_h);
+    attn_part_f32_kernel<<<blocks, kThreads, 0, ctx->stream>>>((const float*)ops[i]->ptr, part + i * dense, pp, w->win_h, 0, 0, 0);
     I8IE_LAUNCH_CHECK();
   }
   i8ie_attention_args a{};
@@ -638,8 +845,90 @@ int i8ie_attention_window_f32(i8ie_ctx* ctx, const i8ie_attention_args* g, const
   I8IE_TRY(i8ie_attention_f32(ctx, &a));
   pp.batch = g->out.batch_stride;
   pp.chan = g->out.token_stride;
-  attn_unpart_f32_kernel<<<blocks, kThreads, 0, ctx->stream>>>(part + 3 * dense, (float*)g->out.ptr, pp, w->win_h);
+  attn_unpart_f32_kernel<<<blocks, kThreads, 0, ctx->stream>>>(part + 3 * dense, (float*)g->out.ptr, pp, w->win_h, 0, 0, 0);
   I8IE_LAUNCH_CHECK();
+  return I8IE_OK;
+}
+
+// ---- shifted-window attention with a relative position bias ----
+int i8ie_attention_swin_u8(i8ie_ctx* ctx, const i8ie_attention_args* g, const i8ie_attention_window* w, const i8ie_attention_swin* sw) {
+  I8IE_REQUIRE(ctx && g && w && sw, "null argument");
+  I8IE_TRY(check_window(g, w, false));
+  I8IE_TRY(check_swin(w, sw));
+  I8IE_REQUIRE(g->scores_out_dev == nullptr, "scores_out_dev belongs to the FP32 entry");
+  I8IE_TRY(check_u8_scales(g));
+  return launch_u8(ctx, g, w, 1, 0, interior_origin(g->out_w, g->out_border, g->out.token_stride), sw);
+}
+
+int i8ie_attention_swin_f32(i8ie_ctx* ctx, const i8ie_attention_args* g, const i8ie_attention_window* w, const i8ie_attention_swin* sw) {
+  I8IE_REQUIRE(ctx && g && w && sw, "null argument");
+  I8IE_TRY(check_window(g, w, true));
+  I8IE_TRY(check_swin(w, sw));
+  I8IE_REQUIRE(w->q_border == 0 && w->k_border == 0 && w->v_border == 0 && g->out_border == 0 && !g->q.s8 && !g->k.s8 && !g->v.s8 &&
+                   !g->out.s8 && !g->relu && g->scores_dbg_dev == nullptr && g->probs_dbg_dev == nullptr && g->acc_dbg_dev == nullptr,
+               "an INT8-only field is set");
+  const int T = g->tq, c = g->heads * g->d, T4 = (T + 3) / 4 * 4;
+  const int nwx = w->map_w / w->win_w, nw = nwx * (w->map_h / w->win_h);
+  const int64_t seqs = (int64_t)g->b * nw;
+  I8IE_REQUIRE(seqs <= 0x7FFFFFFF, "too many windows");
+  // the workspace: one head's scores [seqs, T, T], then the windows of q, k, v and of the result
+  const int64_t per_head = (int64_t)T * T, dense = seqs * T * c;
+  const size_t scores = i8ie_align_up((size_t)seqs * per_head * sizeof(float), 256);
+  I8IE_TRY(i8ie_ws_reserve(ctx, scores + 4 * (size_t)dense * sizeof(float)));
+  float* ws = (float*)ctx->ws;
+  float* part = (float*)((char*)ctx->ws + scores);
+  PartParams pp{dense, c, T, w->win_w, nwx, nw, w->map_w, 0, 0};
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  const unsigned blocks = (unsigned)std::min<int64_t>((dense + kThreads - 1) / kThreads, 65535);
+  const i8ie_attn_mat* ops[3] = {&g->q, &g->k, &g->v};
+  for (int i = 0; i < 3; ++i) {
+    pp.batch = ops[i]->batch_stride;
+    pp.chan = ops[i]->token_stride;
+    attn_part_f32_kernel<<<blocks, kThreads, 0, ctx->stream>>>((const float*)ops[i]->ptr, part + i * dense, pp, w->win_h, sw->shift_h,
+                                                               sw->shift_w, w->map_h);
+    I8IE_LAUNCH_CHECK();
+  }
+  const int64_t tc = (int64_t)T * c;
+  SwinF32Params sp{seqs * per_head, T, T4, w->win_w, w->win_h, nwx, nw, sw->shift_h, sw->shift_w, (int64_t)g->heads * per_head};
+  const unsigned sblocks = (unsigned)std::min<int64_t>((sp.total + kThreads - 1) / kThreads, 65535);
+  for (int h = 0; h < g->heads; ++h) {
+    const int64_t off = (int64_t)h * g->d;
+    i8ie_bmm_args s{};   // S = Q_h K_h^T
+    s.b = (int)seqs; s.m = T; s.n = T; s.k = g->d;
+    s.a = i8ie_bmm_mat{part + off, tc, (int64_t)c, 1, 0};
+    s.bm = i8ie_bmm_mat{part + dense + off, tc, 1, (int64_t)c, 0};
+    s.out = i8ie_bmm_mat{ws, per_head, (int64_t)T, 1, 0};
+    I8IE_TRY(i8ie_bmm_f32(ctx, &s));
+    attn_swin_bias_mask_f32_kernel<<<sblocks, kThreads, 0, ctx->stream>>>(
+        ws, sw->bias_dev ? sw->bias_dev + (int64_t)h * T * T4 : nullptr, g->scores_out_dev ? g->scores_out_dev + (int64_t)h * per_head : nullptr, sp);
+    I8IE_LAUNCH_CHECK();
+    I8IE_TRY(i8ie_softmax_f32(ctx, ws, ws, seqs * T, T));
+    i8ie_bmm_args o{};   // O_h = P V_h
+    o.b = (int)seqs; o.m = T; o.n = g->d; o.k = T;
+    o.a = i8ie_bmm_mat{ws, per_head, (int64_t)T, 1, 0};
+    o.bm = i8ie_bmm_mat{part + 2 * dense + off, tc, (int64_t)c, 1, 0};
+    o.out = i8ie_bmm_mat{part + 3 * dense + off, tc, (int64_t)c, 1, 0};
+    I8IE_TRY(i8ie_bmm_f32(ctx, &o));
+  }
+  pp.batch = g->out.batch_stride;
+  pp.chan = g->out.token_stride;
+  attn_unpart_f32_kernel<<<blocks, kThreads, 0, ctx->stream>>>(part + 3 * dense, (float*)g->out.ptr, pp, w->win_h, sw->shift_h, sw->shift_w,
+                                                               w->map_h);
+  I8IE_LAUNCH_CHECK();
+  return I8IE_OK;
+}
+
+int i8ie_relative_position_bias(const float* table_host, int wh, int ww, int heads, float* out_host) {
+  I8IE_REQUIRE(table_host && out_host && wh > 0 && ww > 0 && heads > 0 && (int64_t)wh * ww <= kMaxTk, "null pointer or bad size");
+  const int T = wh * ww, T4 = (T + 3) / 4 * 4;
+  for (int h = 0; h < heads; ++h)
+    for (int i = 0; i < T; ++i) {
+      float* row = out_host + ((int64_t)h * T + i) * T4;
+      for (int j = 0; j < T4; ++j) {
+        const int idx = (i / ww - j / ww + wh - 1) * (2 * ww - 1) + (i % ww - j % ww + ww - 1);
+        row[j] = j < T ? table_host[(int64_t)idx * heads + h] : 0.0f;
+      }
+    }
   return I8IE_OK;
 }
 

@@ -405,6 +405,17 @@ def window_pair(window):
     raise TypeError("window must be None, an int or a pair of ints (wh, ww)")
 
 
+def shift_pair(shift):
+    """(sh, sw) of a window shift given as an int or a pair of ints; anything else is a TypeError"""
+    try:
+        pair = window_pair(shift)
+    except TypeError:
+        pair = None
+    if pair is None:
+        raise TypeError("shift must be an int or a pair of ints (sh, sw)")
+    return pair
+
+
 class Attention(Weightless):
     """Quantized multi-head attention `y = self.attn(q, k, v)` or, packed, `y = self.attn(qkv)` (additive, not in the
     reference): a layer without weights and with two calibrated parameter sets, the scores' and the output's.
@@ -420,14 +431,48 @@ class Attention(Weightless):
 
     `window`: None, or an int / a pair (wh, ww): attention inside the non-overlapping wh x ww windows of rank-4 maps (see
     `i8ie.attention`), one launch as well (i8ie_attention_window_u8).  While preparing, the calibrator samples the windowed
-    scores [n * windows, heads, wh * ww, wh * ww].  The window is a constructor argument and not part of the saved state."""
+    scores [n * windows, heads, wh * ww, wh * ww].  The window is a constructor argument and not part of the saved state.
 
-    def __init__(self, heads, window=None):
+    `shift`: an int or a pair (sh, sw), 0 <= sh < wh and 0 <= sw < ww: the windows are cut from the map rolled by (-sh, -sw),
+    with Swin's region mask, and the result is rolled back (include/i8ie_hip.h, i8ie_attention_swin_u8): still one launch,
+    and no roll.  `relative_position_bias=True`: the layer owns Swin's fp32 table [(2 wh - 1)(2 ww - 1), heads], zero until
+    `load_relative_position_bias(table)` (Module.load routes `<attr>.relative_position_bias_table` to it); its expansion
+    B[h][i][j] is added to the scores before the softmax, in FP32 and in INT8.  quantized_state_dict() keeps the table as
+    float32 `<attr>.relative_position_bias_table`.  A non-zero shift or a bias without a window is a RuntimeError; a shift
+    that is no int or pair of ints a TypeError.  shift and relative_position_bias are constructor arguments like window."""
+
+    def __init__(self, heads, window=None, shift=0, relative_position_bias=False):
         self.heads = int(heads)
         self.window = window_pair(window)
+        self.shift = shift_pair(shift)
+        self.has_relative_position_bias = bool(relative_position_bias)
+        if self.window is None and (self.shift != (0, 0) or self.has_relative_position_bias):
+            raise RuntimeError("i8ie: Attention: a shift or a relative position bias needs a window")
         self.layer = _C.Attention(self.heads)
         if self.window is not None:
             self.layer._set_window(*self.window)
+        if self.shift != (0, 0):
+            self.layer._set_shift(*self.shift)
+        self._table = None
+        if self.has_relative_position_bias:
+            import numpy as np
+
+            wh, ww = self.window
+            self.load_relative_position_bias(np.zeros(((2 * wh - 1) * (2 * ww - 1), self.heads), np.float32))
+
+    def load_relative_position_bias(self, table):
+        """Swin's table, float32 [(2 wh - 1)(2 ww - 1), heads]: expanded to B[heads][T][T] and uploaded once."""
+        if not self.has_relative_position_bias:
+            raise RuntimeError("i8ie: Attention: built without relative_position_bias=True")
+        import numpy as np
+
+        table = np.ascontiguousarray(table, np.float32)
+        self.layer._set_score_bias(table)
+        self._table = table.copy()
+
+    def relative_position_bias(self):
+        """the table as loaded (zeros until then); None without relative_position_bias=True"""
+        return None if self._table is None else self._table.copy()
 
     def __call__(self, q, k=None, v=None):
         if (k is None) != (v is None):

@@ -20,7 +20,7 @@ class Module:
 
     def load(self, state_dict):
         """Load a torch-style state dict with keys '<attr>.weight' / '<attr>.bias' (reference :10-16); a BatchNorm2d also takes
-        '<attr>.running_mean' / '<attr>.running_var' (additive).  Every other key ('<attr>.num_batches_tracked') is ignored."""
+        '<attr>.running_mean' / '<attr>.running_var', an Attention with a bias '<attr>.relative_position_bias_table' (additive).  Every other key ('<attr>.num_batches_tracked') is ignored."""
         for key in state_dict:
             name, attr = key.split(".")
             if attr == "weight":
@@ -31,6 +31,8 @@ class Module:
                 self.__dict__[name].load_running_mean(state_dict[key])
             elif attr == "running_var":
                 self.__dict__[name].load_running_var(state_dict[key])
+            elif attr == "relative_position_bias_table":
+                self.__dict__[name].load_relative_position_bias(state_dict[key])
 
     def fold_batchnorm(self, pairs):
         """i8ie.fold_batchnorm(layer, bn) for every (layer attribute, BatchNorm2d attribute) pair of names, in FP32 and before
@@ -63,7 +65,8 @@ class Module:
         """{'<attr>.q_weight' int8, '<attr>.q_bias' int8, '<attr>.qparams' float64[3] =
         (weight_scale, out_scale, out_zero_point)} for every converted layer; a per-channel layer also has
         '<attr>.w_scales' float32[out] (its weight_scale entry is then 0 and unused).  An Add, a Mul, a Concat or an Activation contributes only
-        '<attr>.qparams' = (0, out_scale, out_zero_point), an Attention that and '<attr>.score_qparams' float64[2] = (scale, zero_point);
+        '<attr>.qparams' = (0, out_scale, out_zero_point), an Attention that and '<attr>.score_qparams' float64[2] = (scale, zero_point)
+        (and its float32 '<attr>.relative_position_bias_table' where it has one);
         a LayerNorm or a GroupNorm '<attr>.qparams' and '<attr>.weight', '<attr>.bias' as float32 (a PositionEmbedding the same,
         '<attr>.bias' with class_token only); a BatchNorm2d those and
         '<attr>.running_mean', '<attr>.running_var', or no key at all once it is folded into its neighbour."""
@@ -80,6 +83,8 @@ class Module:
             if isinstance(layer, Attention):
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
                 out[name + ".score_qparams"] = np.array(L.score_qparams(), np.float64)
+                if layer.has_relative_position_bias:
+                    out[name + ".relative_position_bias_table"] = layer.relative_position_bias()
                 continue
             if isinstance(layer, Weightless):
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
@@ -121,6 +126,8 @@ class Module:
             if isinstance(layer, Attention):
                 s_s, zp_s = (float(v) for v in state[name + ".score_qparams"])
                 layer.layer.load_quantized(float(np.float32(s_out)), int(zp_out), float(np.float32(s_s)), int(zp_s))
+                if layer.has_relative_position_bias:
+                    layer.load_relative_position_bias(state[name + ".relative_position_bias_table"])
                 continue
             if isinstance(layer, Weightless):
                 layer.layer.load_quantized(float(np.float32(s_out)), int(zp_out))
