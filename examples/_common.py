@@ -18,8 +18,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def run(network, description, report=None):
-    """report: called with the converted model behind the INT8 run, for what an example prints beyond the common lines"""
+def run(network, description, report=None, convert=None):
+    """report: called with the converted model behind the INT8 run, for what an example prints beyond the common lines;
+    convert: keyword arguments of Module.convert (default: the reference's per-tensor INT8)"""
     ap = argparse.ArgumentParser(description=description)
     ap.add_argument("--batch", type=int, default=100)
     ap.add_argument("--batches", type=int, default=10)
@@ -70,7 +71,7 @@ def run(network, description, report=None):
     t0 = time.perf_counter()
     model.prepare()
     model(tens[0])
-    model.convert()
+    model.convert(**(convert or {}))
     print("%-18s %8.1f ms" % ("prepare+convert", (time.perf_counter() - t0) * 1e3))
     evaluate("INT8 (warm-up)")
     p_int8 = evaluate("INT8")

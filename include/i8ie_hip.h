@@ -522,6 +522,39 @@ int i8ie_layer_groups(const i8ie_layer* layer, int* groups);
 /* the weight scales: out float [n] (n = out features); a per-tensor layer gives n copies of its scale and
  * *per_channel = 0, a per-channel layer its s_w[j] and *per_channel = 1 */
 int i8ie_layer_weight_scales(const i8ie_layer* layer, float* out, int n, int* per_channel);
+
+/* ---- 4-bit weights for Linear (W4A8; not in the reference) ------------------------------------------
+ * A 4-bit layer is a per-channel INT8 layer whose weight integers lie in [-8, 7]: the exact INT32 accumulator, the offset
+ * vector, Linear's float bias step and down_scale per column are unchanged; only the storage and the kernels differ.
+ * Quantiser (host, IEEE fp32, per output feature j of w [rows, row_len]; b_host may be NULL: zero bias):
+ *   a_j = max(max_k |w[j,k]|, |b[j]| * 7 / 127);  s_w[j] = a_j / 7  (a_j == 0: 1)
+ *   q_w[j,k] = clamp(rint(w[j,k] / s_w[j]), -7, 7);  q_b[j] = (s8) clamp(rint(b[j] / s_w[j]), -127, 127)   (rint: half to even)
+ * The bias term inside a_j keeps q_b within s8 (|b| / s_w <= 127) without letting a large bias eat the weights' sixteen
+ * levels, as taking |b[j]| itself would.  Weights are always per output feature: there is no per-tensor 4-bit mode.
+ * qw_host receives one s8 per weight; i8ie_pack_w4 makes the stored form. */
+int i8ie_quantize_weight_w4(const float* w_host, int rows, int64_t row_len, const float* b_host, int8_t* qw_host,
+                            int8_t* qb_host, float* scales_host);
+/* The packed format: row j is ceil(k / 2) bytes; element 2i sits in the low nibble of byte i and element 2i + 1 in the high
+ * nibble, both two's complement; the high nibble of an odd row's last byte is 0.  i8ie_pack_w4 refuses a value outside
+ * [-8, 7] (I8IE_ERR_ARG); i8ie_unpack_w4 is its inverse on the whole range. */
+int i8ie_pack_w4(const int8_t* qw_host, int rows, int k, uint8_t* packed_host);
+int i8ie_unpack_w4(const uint8_t* packed_host, int rows, int k, int8_t* qw_host);
+/* A Linear [n, k] from packed rows (any nibble in [-8, 7]), s8 biases and one finite scale >= 0 per output feature, all host
+ * pointers; k <= 65536.  The handle keeps the nibbles in the fragment order of csrc/i8ie_w4lin.hip plus the per-feature
+ * vectors: no unpacked copy of the weights exists on the device.  Every forward entry point gives the bytes (and acc_dbg the
+ * sums) of i8ie_linear_u8s8 with down_scale per column on the unpacked integers.  Kernels: w4lin_mfma when k % 32 == 0, the
+ * input is 16-byte aligned and I8IE_OPT_FORCE_FALLBACK is off (any m, any n, one launch; nibbles become bytes only in
+ * registers); w4lin_direct otherwise.  i8ie_layer_forward_dequant needs out_u8 and runs the dequantize kernel behind it. */
+int i8ie_linear_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int n,
+                          int k, i8ie_layer** out);
+/* *bits = 4 for a layer of i8ie_linear_create_w4, 8 for every other layer */
+int i8ie_layer_weight_bits(const i8ie_layer* layer, int* bits);
+/* Stateless form (for tests): in_dev [m, k] u8 -> out_dev [m, n] u8 through a temporary handle made from the host weights;
+ * the offset vector is computed inside (src/fully_connected.cc:30-38).  acc_dbg_dev: NULL, or int32 [m, n] receiving C BEFORE
+ * the float bias step, as i8ie_linear_u8s8 gives it. */
+int i8ie_linear_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const uint8_t* packed_host, const int8_t* qb_host,
+                     const float* s_w_host, int n, float s_in, uint8_t zp_in, float s_out, uint8_t zp_out,
+                     uint8_t* out_dev, int32_t* acc_dbg_dev);
 /* the layer's output (scale_, zero_point_): src/layer.cc:44, include/layer.h:46-47 (default 1, 0) */
 int i8ie_layer_set_output_qparams(i8ie_layer* layer, float s_out, uint8_t zp_out);
 int i8ie_layer_get_output_qparams(const i8ie_layer* layer, float* s_out, uint8_t* zp_out);

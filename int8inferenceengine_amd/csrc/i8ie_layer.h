@@ -124,6 +124,11 @@ struct i8ie_layer {
   bool ms_valid = false;
   bool ms_fast = false;        // every column allows the guarded estimate (i8ie_requant_pc_fast)
   float ms_s_in = 0.0f, ms_s_out = 0.0f;
+  // a Linear of i8ie_linear_create_w4: wbits = 4, always pc.  It holds the nibble panel of i8ie_w4lin.h and
+  // the per-feature vectors ([Npad] = [round_up(n, 128)]); qw, Bpack and Bperm stay null -- no unpacked copy of the weights exists on the
+  // device.  The panel re-packed for rows in (h, w, c) order lives in `wc`, one buffer per (c, h * w).
+  int wbits = 8;
+  uint8_t* w4 = nullptr;
 };
 
 // the geometry the kernels walk: the handle's numbers with the effective dilations

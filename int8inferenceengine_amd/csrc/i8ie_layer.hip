@@ -30,6 +30,7 @@
 #include "i8ie_deconv.h"
 #include "i8ie_dconv.h"
 #include "i8ie_lconv.h"
+#include "i8ie_w4lin.h"
 
 // ---- v1 (fallback) runners ------------------------------------------------------------------
 int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, const int8_t* Bpack, const int32_t* oc,
@@ -96,8 +97,12 @@ int ensure_offsets(i8ie_layer* L, float s_in, uint8_t zp_in) {
   // the reference recomputes this on every call (src/conv2d.cc:117-124); it only depends on
   // (s_in, zp_in), which are fixed once the network is converted
   i8ie_ctx* ctx = L->ctx;
-  I8IE_TRY(i8ie_launch_offsets(ctx, L->conv, L->qw, L->qb, L->n, L->K, s_in, zp_in, L->oc, nullptr));
-  I8IE_TRY(i8ie_launch_finish_offsets(ctx, L->oc, L->wsum, L->qb, s_in, L->n, L->ocp, L->conv ? nullptr : L->biasf));
+  if (L->wbits == 4) {  // the same vectors from the nibbles, in one launch
+    I8IE_TRY(i8ie_w4_launch_offsets(ctx, L->w4, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
+  } else {
+    I8IE_TRY(i8ie_launch_offsets(ctx, L->conv, L->qw, L->qb, L->n, L->K, s_in, zp_in, L->oc, nullptr));
+    I8IE_TRY(i8ie_launch_finish_offsets(ctx, L->oc, L->wsum, L->qb, s_in, L->n, L->ocp, L->conv ? nullptr : L->biasf));
+  }
   L->oc_valid = true;
   L->oc_s_in = s_in;
   L->oc_zp_in = zp_in;
@@ -527,11 +532,49 @@ static int forward_conv(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q)
   return L->path == PATH_A ? forward_implicit(L, cg, q, plan.pconv) : forward_small_c(L, cg, q, plan.stem);
 }
 
+// ---- Linear with 4-bit weights (i8ie_linear_create_w4): the two kernels of i8ie_w4lin.hip and nothing else ------------------------
+static int forward_linear_w4(i8ie_layer* L, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  const int m = q.m;
+  I8IE_REQUIRE(q.out != nullptr, "i8ie_layer_forward_dequant: this layer needs the u8 output buffer as well");
+  if (q.out_f32 != nullptr) {  // the ordinary forward, then the dequantize kernel
+    ConvRequest r = q;
+    r.out_f32 = nullptr;
+    I8IE_TRY(forward_linear_w4(L, r));
+    return i8ie_dequantize_u8_f32(ctx, q.out, q.out_f32, (int64_t)m * L->n, L->s_out, L->zp_out);
+  }
+  const int hw = (q.in_layout == I8IE_LAYOUT_NHWC && q.h > 0 && q.w > 0) ? q.h * q.w : 1;
+  if (hw > 1) I8IE_REQUIRE(L->K % hw == 0, "Linear: in_features is not c * h * w for the given h, w");
+  I8ieW4Call c{};
+  c.A = q.in; c.M = m; c.N = L->n; c.K = L->K; c.B = L->w4; c.hw = hw; c.out = q.out;
+  c.ep = layer_epilogue(L, q, L->biasf);
+  if (force_fallback(ctx) || !i8ie_w4lin_mfma_takes(c)) {
+    c.ep.ocp = L->oc;  // (the definition reads the activations as they are)
+    return i8ie_w4lin_direct_launch(ctx, c);
+  }
+  if (hw > 1) {  // rows in (h, w, c) order: the panel re-packed from the nibbles once per (c, h * w), never overwritten
+    const unsigned long long key = ((unsigned long long)(L->K / hw) << 32) | (unsigned)hw;
+    void* perm = L->wc.find(key);
+    if (perm == nullptr) {
+      I8IE_TRY(i8ie_malloc(ctx, i8ie_w4_panel_bytes(L->n, L->K), &perm));
+      const int rc = i8ie_w4_launch_permute(ctx, L->w4, (uint8_t*)perm, L->n, L->K, L->K / hw, hw);
+      if (rc != I8IE_OK) {  // (no entry for a panel that was never filled)
+        i8ie_free(ctx, perm);
+        return rc;
+      }
+      L->wc.ents.push_back({key, perm});
+    }
+    c.B = (const uint8_t*)perm;
+  }
+  return i8ie_w4lin_mfma_launch(ctx, c);
+}
+
 // ---- Linear: row-major in / out ------------------------------------------------------------------------------------------------
 static int forward_linear(i8ie_layer* L, const ConvRequest& q) {
   i8ie_ctx* ctx = L->ctx;
   const int m = q.m;
   I8IE_REQUIRE(q.in_border == 0 && q.out_border == 0, "Linear tensors carry no border");
+  if (L->wbits == 4) return forward_linear_w4(L, q);
   // Rows that are a flattened NHWC activation [m][h][w][c] (the engine's layout between layers) instead of
   // the reference's flattened NCHW: same contraction with K walked in (h, w, c) order, so the weight panel
   // is permuted once per (c, h*w) and the input is used as it lies -- no transpose back to NCHW.  oc[] and

@@ -13,6 +13,7 @@
 #include "i8ie_requant.h"
 #include "i8ie_gconv.h"
 #include "i8ie_deconv.h"
+#include "i8ie_w4lin.h"
 
 namespace {
 
@@ -363,6 +364,45 @@ int i8ie_linear_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const i
   return layer_build(ctx, s, qw_host, qb_host, out);
 }
 
+// A Linear with 4-bit weights: the packed rows go into the nibble panel of i8ie_w4lin.h on the host, and the
+// handle holds that panel and the per-feature vectors -- not layer_build's qw / Bpack, so no unpacked copy reaches the device.
+// wsum / oc / oc' / the float bias come from the panel per (s_in, zp_in), in one launch of the first forward (ensure_offsets).
+int i8ie_linear_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int n, int k,
+                          i8ie_layer** out) {
+  I8IE_REQUIRE(ctx && packed_host && qb_host && out, "null argument");
+  I8IE_REQUIRE(n > 0 && k > 0, "non-positive dimension");
+  I8IE_REQUIRE(k <= 65536, "4-bit Linear: at most 65536 input features (16 C must stay inside int32)");
+  I8IE_TRY(check_scales(s_w_host, n));
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  i8ie_layer* L = new (std::nothrow) i8ie_layer();
+  if (!L) return I8IE_ERR_OOM;
+  L->ctx = ctx; L->n = n; L->K = k; L->wbits = 4;
+  L->Kpad = round_up(k, 128);
+  L->Npad = round_up(n, 128);
+  std::vector<uint8_t> panel(i8ie_w4_panel_bytes(n, k), 0);
+  i8ie_w4_pack_panel(packed_host, n, k, panel.data());
+  const std::vector<int32_t> zeros((size_t)L->Npad, 0);  // (padding: the quads' vector loads read it)
+  int rc = upload(L, &L->w4, panel);
+  if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->qb, (size_t)n, qb_host);
+  if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->wsum, (size_t)n * 4);
+  if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->oc, (size_t)L->Npad * 4, zeros.data());
+  if (rc == I8IE_OK) rc = upload(L, &L->ocp, zeros);
+  if (rc == I8IE_OK) rc = upload(L, &L->biasf, zeros);
+  if (rc == I8IE_OK) rc = upload_scales(L, s_w_host);
+  if (rc != I8IE_OK) {
+    i8ie_layer_destroy(L);
+    return rc;
+  }
+  *out = L;
+  return I8IE_OK;
+}
+
+int i8ie_layer_weight_bits(const i8ie_layer* L, int* bits) {
+  I8IE_REQUIRE(L && bits, "null argument");
+  *bits = L->wbits;
+  return I8IE_OK;
+}
+
 int i8ie_conv2d_create(i8ie_ctx* ctx, const int8_t* qw_host, const int8_t* qb_host, int kc, int c, int kh, int kw,
                        int stride, int pad, float s_w, i8ie_layer** out) {
   LayerSpec s = conv_spec(kc, c, kh, kw, stride, pad);
@@ -699,6 +739,74 @@ int i8ie_quantize_weight_per_channel(const float* w, int rows, int64_t row_len, 
     scales[j] = s;
   }
   return I8IE_OK;
+}
+
+// 4-bit weights per output feature: sixteen levels for the weights, the bias still s8 at its row's scale.
+// The bias enters a_j scaled by 7 / 127: that keeps q_b inside s8 without a large bias eating the weights' levels.
+int i8ie_quantize_weight_w4(const float* w, int rows, int64_t row_len, const float* b, int8_t* qw, int8_t* qb, float* scales) {
+  I8IE_REQUIRE(w && qw && qb && scales, "null argument");
+  I8IE_REQUIRE(rows > 0 && row_len > 0, "empty tensor");
+  auto q = [](float x, float s, float lim) {
+    float r = std::nearbyint(x / s);  // (the default rounding mode: to nearest, ties to even)
+    r = r > lim ? lim : (r < -lim ? -lim : r);
+    return (int8_t)(int32_t)r;
+  };
+  for (int j = 0; j < rows; ++j) {
+    const float* row = w + (size_t)j * row_len;
+    const float bj = b ? b[j] : 0.0f;
+    float a = std::fabs(bj) * 7.0f / 127.0f;
+    for (int64_t k = 0; k < row_len; ++k) a = std::fabs(row[k]) > a ? std::fabs(row[k]) : a;
+    const float s = a == 0.0f ? 1.0f : a / 7.0f;
+    for (int64_t k = 0; k < row_len; ++k) qw[(size_t)j * row_len + k] = q(row[k], s, 7.0f);
+    qb[j] = q(bj, s, 127.0f);
+    scales[j] = s;
+  }
+  return I8IE_OK;
+}
+
+// the packed format: row j is ceil(k / 2) bytes, element 2 i in the low nibble of byte i, 2 i + 1 in the high one, two's complement
+int i8ie_pack_w4(const int8_t* qw, int rows, int k, uint8_t* packed) {
+  I8IE_REQUIRE(qw && packed, "null argument");
+  I8IE_REQUIRE(rows > 0 && k > 0, "empty tensor");
+  const size_t pitch = ((size_t)k + 1) / 2;
+  for (size_t e = 0; e < (size_t)rows * k; ++e)
+    if (qw[e] < -8 || qw[e] > 7) {
+      i8ie_set_error("i8ie_pack_w4: weight %zu is %d, outside [-8, 7]", e, (int)qw[e]);
+      return I8IE_ERR_ARG;
+    }
+  for (int j = 0; j < rows; ++j)
+    for (size_t i = 0; i < pitch; ++i) {
+      const int8_t* row = qw + (size_t)j * k;
+      const unsigned lo = (unsigned)row[2 * i] & 15u, hi = 2 * i + 1 < (size_t)k ? (unsigned)row[2 * i + 1] & 15u : 0u;
+      packed[j * pitch + i] = (uint8_t)(lo | (hi << 4));
+    }
+  return I8IE_OK;
+}
+
+int i8ie_unpack_w4(const uint8_t* packed, int rows, int k, int8_t* qw) {
+  I8IE_REQUIRE(qw && packed, "null argument");
+  I8IE_REQUIRE(rows > 0 && k > 0, "empty tensor");
+  const size_t pitch = ((size_t)k + 1) / 2;
+  for (int j = 0; j < rows; ++j)
+    for (int i = 0; i < k; ++i)
+      qw[(size_t)j * k + i] = (int8_t)((int)(((packed[j * pitch + i / 2] >> (4 * (i & 1))) & 15u) ^ 8u) - 8);
+  return I8IE_OK;
+}
+
+// the stateless form, for tests: a temporary handle made from host weights runs one forward and is destroyed (it waits for
+// nothing: the handle's buffers go back to the stream-ordered pool)
+int i8ie_linear_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const uint8_t* packed_host, const int8_t* qb_host,
+                     const float* s_w_host, int n, float s_in, uint8_t zp_in, float s_out, uint8_t zp_out, uint8_t* out_dev,
+                     int32_t* acc_dbg_dev) {
+  I8IE_REQUIRE(ctx && in_dev && out_dev, "null argument");
+  I8IE_REQUIRE(m > 0, "non-positive dimension");
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_linear_create_w4(ctx, packed_host, qb_host, s_w_host, n, k, &L));
+  L->s_out = s_out;
+  L->zp_out = zp_out;
+  const int rc = i8ie_layer_forward(L, in_dev, m, 0, 0, s_in, zp_in, out_dev, acc_dbg_dev);
+  i8ie_layer_destroy(L);
+  return rc;
 }
 
 }  // extern "C"

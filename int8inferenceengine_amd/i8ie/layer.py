@@ -47,12 +47,24 @@ class Layer:
         """Start collecting output samples for calibration (reference src/layer.cc:28-35)."""
         self.layer.prepare()
 
-    def convert(self, per_channel=False):
+    def convert(self, per_channel=False, weight_bits=8):
         """Quantise weights, fix the output (scale, zero_point) (reference src/layer.cc:36-54).
 
         per_channel=True (additive, not the reference's rule): one symmetric max-abs weight scale per output
-        feature, rounded to nearest even (include/i8ie_hip.h, i8ie_quantize_weight_per_channel)."""
-        self.layer.convert(bool(per_channel))
+        feature, rounded to nearest even (include/i8ie_hip.h, i8ie_quantize_weight_per_channel).
+        weight_bits=4 (additive; i8ie.Linear only, ValueError for every other layer class; any value but 4 or 8 is a
+        ValueError): 4-bit weights with one scale per output feature, whatever per_channel says (include/i8ie_hip.h,
+        i8ie_quantize_weight_w4).  The layer is then per-channel in every respect: is_per_channel() is True,
+        weight_scales() works and weight_scale() raises."""
+        if check_weight_bits(self, weight_bits) == 4:
+            self.layer._convert_w4()
+        else:
+            self.layer.convert(bool(per_channel))
+
+    def weight_bits(self):
+        """4 for a Linear converted or loaded with 4-bit weights, 8 for every other layer."""
+        ask = getattr(self.layer, "_weight_bits", None)
+        return 8 if ask is None else int(ask())
 
     # ---- additive (the reference cannot inject or read these) ----------------
     def set_output_qparams(self, scale, zero_point):
@@ -105,6 +117,15 @@ class Layer:
         return Tensor(out), acc
 
 
+def check_weight_bits(layer, weight_bits):
+    """weight_bits as convert() takes it: 8, or 4 on a Linear; ValueError otherwise"""
+    if weight_bits not in (4, 8) or isinstance(weight_bits, bool):
+        raise ValueError("convert: weight_bits must be 4 or 8, got %r" % (weight_bits,))
+    if weight_bits == 4 and not isinstance(layer, Linear):
+        raise ValueError("convert: weight_bits=4 is for i8ie.Linear only, not %s" % type(layer).__name__)
+    return weight_bits
+
+
 def _pair(value, name):
     """(h, w) of a geometry argument given as an int or as a pair of ints; anything else is a TypeError"""
     def is_int(v):
@@ -154,8 +175,9 @@ class Norm(Layer):
     zero_point) and no INT8 weights.  Module.load() takes `<attr>.weight` / `<attr>.bias`; quantized_state_dict() keeps both as
     float32 beside `<attr>.qparams`.  weight_scale, weight_scales, q_weight, q_bias and forward_debug raise RuntimeError."""
 
-    def convert(self, per_channel=False):
+    def convert(self, per_channel=False, weight_bits=8):
         """per_channel is accepted and ignored: there are no INT8 weights."""
+        check_weight_bits(self, weight_bits)
         self.layer.convert()
 
     def is_per_channel(self):
@@ -260,8 +282,9 @@ class BatchNorm2d(Norm):
         if not self._folded:
             self.layer.prepare()
 
-    def convert(self, per_channel=False):
+    def convert(self, per_channel=False, weight_bits=8):
         """per_channel is accepted and ignored: there are no INT8 weights.  A folded BatchNorm stays as it is."""
+        check_weight_bits(self, weight_bits)
         if not self._folded:
             self.layer.convert()
 
@@ -332,8 +355,9 @@ class Weightless(Layer):
     (`<attr>.qparams` only); Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values);
     load_weight, load_bias, weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
 
-    def convert(self, per_channel=False):
+    def convert(self, per_channel=False, weight_bits=8):
         """per_channel is accepted and ignored."""
+        check_weight_bits(self, weight_bits)
         self.layer.convert()
 
     def is_per_channel(self):

@@ -1,7 +1,7 @@
 """Module base class (reference i8ie/module.py:6-35)."""
 import _CXX_i8ie as _C
 
-from .layer import Attention, BatchNorm2d, Layer, Norm, PositionEmbedding, Weightless, fold_batchnorm
+from .layer import Attention, BatchNorm2d, Layer, Linear, Norm, PositionEmbedding, Weightless, fold_batchnorm
 from .tensor import Tensor
 
 # Hard-coded input quantisation of the reference (i8ie/module.py:20).
@@ -52,10 +52,14 @@ class Module:
         for _, layer in self._layers():
             layer.prepare()
 
-    def convert(self, per_channel=False):
-        """per_channel=True: every layer with one weight scale per output feature (Layer.convert)."""
+    def convert(self, per_channel=False, weight_bits=8):
+        """per_channel=True: every layer with one weight scale per output feature (Layer.convert).  weight_bits=4: every
+        Linear converts to 4-bit weights, every other layer as with 8 under the given per_channel; any value but 4 or 8 is a
+        ValueError."""
+        if weight_bits not in (4, 8) or isinstance(weight_bits, bool):
+            raise ValueError("convert: weight_bits must be 4 or 8, got %r" % (weight_bits,))
         for _, layer in self._layers():
-            layer.convert(per_channel)
+            layer.convert(per_channel, weight_bits if isinstance(layer, Linear) else 8)
         self.is_quant = True
 
     # ---- additive: save / restore the converted (INT8) model ------------------
@@ -98,7 +102,10 @@ class Module:
                     out[name + ".running_var"] = np.asarray(L.running_var(), np.float32)
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
                 continue
-            out[name + ".q_weight"] = L.q_weight()
+            if layer.weight_bits() == 4:  # uint8 [out, ceil(in / 2)]: element 2i in the low nibble of byte i (i8ie_pack_w4)
+                out[name + ".q_weight4"] = L._q_weight4()
+            else:
+                out[name + ".q_weight"] = L.q_weight()
             out[name + ".q_bias"] = L.q_bias()
             if L.is_per_channel():
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
@@ -136,6 +143,13 @@ class Module:
                 bias = state.get(name + ".bias") if isinstance(layer, PositionEmbedding) and not layer.class_token else state[name + ".bias"]
                 layer.layer.load_quantized(np.asarray(state[name + ".weight"], np.float32), None if bias is None else np.asarray(bias, np.float32),
                                            float(np.float32(s_out)), int(zp_out))
+                continue
+            if name + ".q_weight4" in state:  # 4-bit Linear
+                if not isinstance(layer, Linear):
+                    raise RuntimeError("i8ie: load_quantized: %r carries 4-bit weights (.q_weight4), which only a Linear takes; "
+                                       "the layer is a %s" % (name, type(layer).__name__))
+                layer.layer._load_quantized_w4(np.asarray(state[name + ".q_weight4"], np.uint8), np.asarray(state[name + ".q_bias"], np.int8),
+                                               np.ascontiguousarray(state[name + ".w_scales"], np.float32), float(np.float32(s_out)), int(zp_out))
                 continue
             if name + ".w_scales" in state:  # per-channel layer
                 w_scale = np.ascontiguousarray(state[name + ".w_scales"], np.float32)
