@@ -555,6 +555,44 @@ int i8ie_layer_weight_bits(const i8ie_layer* layer, int* bits);
 int i8ie_linear_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const uint8_t* packed_host, const int8_t* qb_host,
                      const float* s_w_host, int n, float s_in, uint8_t zp_in, float s_out, uint8_t zp_out,
                      uint8_t* out_dev, int32_t* acc_dbg_dev);
+
+/* ---- 2:4 structured-sparse weights for Linear (not in the reference) ----------------------------------
+ * A 2:4 layer is an ordinary INT8 Linear, per tensor or per output feature, whose weight integers have at most two non-zeros
+ * in every aligned group k = 4 g .. 4 g + 3 of in_features (the weight's own axis; a final partial group counts as padded
+ * with zeros): the exact INT32 accumulator, the offset vector, Linear's float bias step and the requantiser are unchanged, so
+ * an INT8 Linear holding the same dense integers gives the same bytes; only the storage and the kernels differ.
+ * Pruning rule (host, after the ordinary quantiser): in each group keep the two entries of largest |q|, ties to the lower k,
+ * and zero the rest.  Weights that are 2:4 already are unchanged, and so are the scales: a row's maximum always survives.
+ * pruned_host may be qw_host. */
+int i8ie_prune_2_4(const int8_t* qw_host, int rows, int k, int8_t* pruned_host);
+/* The compressed form, with K4 = 4 ceil(k / 4): values_host s8 [rows, K4 / 2], the two kept entries of every group in k order;
+ * index_host u8 [rows, ceil(K4 / 8)], one nibble per group, group 2 i in the low nibble of byte i (an odd group count leaves the
+ * last high nibble 0); bits 1:0 of a nibble are the position (0 .. 3) of the group's first kept entry, bits 3:2 that of the
+ * second, first < second.  Canonical: the kept positions are the non-zero positions; with fewer than two, the lowest positions
+ * not yet chosen fill up, holding the value 0 -- so i8ie_pack_2_4 of i8ie_unpack_2_4 of a canonical form is that form.
+ * i8ie_pack_2_4 refuses a group with more than two non-zeros, i8ie_unpack_2_4 a nibble with first >= second (I8IE_ERR_ARG). */
+int i8ie_pack_2_4(const int8_t* qw_host, int rows, int k, int8_t* values_host, uint8_t* index_host);
+int i8ie_unpack_2_4(const int8_t* values_host, const uint8_t* index_host, int rows, int k, int8_t* qw_host);
+/* A Linear [n, k] from the compressed form (any nibble with first < second), s8 biases and the weight scale(s), all host
+ * pointers; k <= 65536.  The handle keeps the compressed rows in the fragment order of csrc/i8ie_sp24lin.hip (0.625 of the
+ * dense bytes) plus the per-feature vectors: no dense copy of the weights exists on the device.  Every forward entry point
+ * gives the bytes (and acc_dbg the sums) of i8ie_linear_u8s8 on the unpacked integers.  Kernels: sp24lin_mfma
+ * (v_smfmac_i32_16x16x128_i8; one launch, any m, any n) when k % 32 == 0, the rows are in the reference's K order, the input is
+ * 16-byte aligned and I8IE_OPT_FORCE_FALLBACK is off; sp24lin_direct otherwise -- also for rows that are a flattened NHWC map
+ * with h * w > 1, because a K-permuted panel cannot keep the groups of four contiguous (a layout conversion ahead of the MFMA
+ * kernel is a follow-up).  i8ie_layer_forward_dequant needs out_u8 and runs the dequantize kernel behind it. */
+int i8ie_linear_create_sp24(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* index_host, const int8_t* qb_host, int n,
+                            int k, float s_w, i8ie_layer** out);
+int i8ie_linear_create_sp24_per_channel(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* index_host,
+                                        const int8_t* qb_host, int n, int k, const float* s_w_host, i8ie_layer** out);
+/* *kept_of_four = 2 for a layer of i8ie_linear_create_sp24 (2:4), 0 for every other layer (dense) */
+int i8ie_layer_sparsity(const i8ie_layer* layer, int* kept_of_four);
+/* Stateless form (for tests): in_dev [m, k] u8 -> out_dev [m, n] u8 through a temporary handle made from the host weights;
+ * per_channel != 0: s_w_host holds n scales, else one.  acc_dbg_dev: NULL, or int32 [m, n] receiving C BEFORE the float bias
+ * step, as i8ie_linear_u8s8 gives it. */
+int i8ie_linear_u8s8_sp24(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const int8_t* values_host,
+                          const uint8_t* index_host, const int8_t* qb_host, const float* s_w_host, int per_channel, int n,
+                          float s_in, uint8_t zp_in, float s_out, uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
 /* the layer's output (scale_, zero_point_): src/layer.cc:44, include/layer.h:46-47 (default 1, 0) */
 int i8ie_layer_set_output_qparams(i8ie_layer* layer, float s_out, uint8_t zp_out);
 int i8ie_layer_get_output_qparams(const i8ie_layer* layer, float* s_out, uint8_t* zp_out);

@@ -129,6 +129,9 @@ struct i8ie_layer {
   // device.  The panel re-packed for rows in (h, w, c) order lives in `wc`, one buffer per (c, h * w).
   int wbits = 8;
   uint8_t* w4 = nullptr;
+  // a Linear of i8ie_linear_create_sp24: the compressed 2:4 panel of i8ie_sp24lin.h, per-tensor or pc, and
+  // the per-feature vectors ([Npad]); qw, Bpack and Bperm stay null -- no dense copy of the weights exists on the device
+  uint8_t* sp24 = nullptr;
 };
 
 // the geometry the kernels walk: the handle's numbers with the effective dilations

@@ -31,6 +31,7 @@
 #include "i8ie_dconv.h"
 #include "i8ie_lconv.h"
 #include "i8ie_w4lin.h"
+#include "i8ie_sp24lin.h"
 
 // ---- v1 (fallback) runners ------------------------------------------------------------------
 int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, const int8_t* Bpack, const int32_t* oc,
@@ -99,6 +100,8 @@ int ensure_offsets(i8ie_layer* L, float s_in, uint8_t zp_in) {
   i8ie_ctx* ctx = L->ctx;
   if (L->wbits == 4) {  // the same vectors from the nibbles, in one launch
     I8IE_TRY(i8ie_w4_launch_offsets(ctx, L->w4, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
+  } else if (L->sp24 != nullptr) {  // ... and from the compressed 2:4 panel
+    I8IE_TRY(i8ie_sp24_launch_offsets(ctx, L->sp24, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
   } else {
     I8IE_TRY(i8ie_launch_offsets(ctx, L->conv, L->qw, L->qb, L->n, L->K, s_in, zp_in, L->oc, nullptr));
     I8IE_TRY(i8ie_launch_finish_offsets(ctx, L->oc, L->wsum, L->qb, s_in, L->n, L->ocp, L->conv ? nullptr : L->biasf));
@@ -569,12 +572,38 @@ static int forward_linear_w4(i8ie_layer* L, const ConvRequest& q) {
   return i8ie_w4lin_mfma_launch(ctx, c);
 }
 
+// ---- Linear with 2:4 structured-sparse weights (i8ie_linear_create_sp24): the two kernels of i8ie_sp24lin.hip and nothing else.
+// Rows that are a flattened NHWC activation go to the definition kernel: a K-permuted panel cannot keep the groups of four
+// contiguous (a layout conversion ahead of the MFMA kernel is a follow-up).
+static int forward_linear_sp24(i8ie_layer* L, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  const int m = q.m;
+  I8IE_REQUIRE(q.out != nullptr, "i8ie_layer_forward_dequant: this layer needs the u8 output buffer as well");
+  if (q.out_f32 != nullptr) {  // the ordinary forward, then the dequantize kernel
+    ConvRequest r = q;
+    r.out_f32 = nullptr;
+    I8IE_TRY(forward_linear_sp24(L, r));
+    return i8ie_dequantize_u8_f32(ctx, q.out, q.out_f32, (int64_t)m * L->n, L->s_out, L->zp_out);
+  }
+  const int hw = (q.in_layout == I8IE_LAYOUT_NHWC && q.h > 0 && q.w > 0) ? q.h * q.w : 1;
+  if (hw > 1) I8IE_REQUIRE(L->K % hw == 0, "Linear: in_features is not c * h * w for the given h, w");
+  I8ieSp24Call c{};
+  c.A = q.in; c.M = m; c.N = L->n; c.K = L->K; c.B = L->sp24; c.hw = hw; c.out = q.out;
+  c.ep = layer_epilogue(L, q, L->biasf);
+  if (force_fallback(ctx) || !i8ie_sp24lin_mfma_takes(c)) {
+    c.ep.ocp = L->oc;  // (the definition reads the activations as they are)
+    return i8ie_sp24lin_direct_launch(ctx, c);
+  }
+  return i8ie_sp24lin_mfma_launch(ctx, c);
+}
+
 // ---- Linear: row-major in / out ------------------------------------------------------------------------------------------------
 static int forward_linear(i8ie_layer* L, const ConvRequest& q) {
   i8ie_ctx* ctx = L->ctx;
   const int m = q.m;
   I8IE_REQUIRE(q.in_border == 0 && q.out_border == 0, "Linear tensors carry no border");
   if (L->wbits == 4) return forward_linear_w4(L, q);
+  if (L->sp24 != nullptr) return forward_linear_sp24(L, q);
   // Rows that are a flattened NHWC activation [m][h][w][c] (the engine's layout between layers) instead of
   // the reference's flattened NCHW: same contraction with K walked in (h, w, c) order, so the weight panel
   // is permuted once per (c, h*w) and the input is used as it lies -- no transpose back to NCHW.  oc[] and

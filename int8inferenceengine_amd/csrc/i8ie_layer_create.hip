@@ -14,6 +14,7 @@
 #include "i8ie_gconv.h"
 #include "i8ie_deconv.h"
 #include "i8ie_w4lin.h"
+#include "i8ie_sp24lin.h"
 
 namespace {
 
@@ -400,6 +401,65 @@ int i8ie_linear_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_
 int i8ie_layer_weight_bits(const i8ie_layer* L, int* bits) {
   I8IE_REQUIRE(L && bits, "null argument");
   *bits = L->wbits;
+  return I8IE_OK;
+}
+
+// A Linear with 2:4 structured-sparse weights: the compressed rows go into the panel of i8ie_sp24lin.h on
+// the host, and the handle holds that panel and the per-feature vectors -- not layer_build's qw / Bpack, so no dense copy reaches
+// the device.  wsum / oc / oc' / the float bias come from the panel per (s_in, zp_in), in one launch of the first forward.
+static int sp24_create(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* index_host, const int8_t* qb_host, int n, int k,
+                       float s_w, const float* s_w_pc, i8ie_layer** out) {
+  I8IE_REQUIRE(ctx && values_host && index_host && qb_host && out, "null argument");
+  I8IE_REQUIRE(n > 0 && k > 0, "non-positive dimension");
+  I8IE_REQUIRE(k <= 65536, "2:4 Linear: at most 65536 input features");
+  const size_t groups = ((size_t)k + 3) / 4, ipitch = (groups + 1) / 2;
+  for (int j = 0; j < n; ++j)
+    for (size_t g = 0; g < groups; ++g) {
+      const unsigned nib = (index_host[j * ipitch + g / 2] >> (4 * (g & 1))) & 15u;
+      if ((nib & 3u) >= (nib >> 2)) {
+        i8ie_set_error("i8ie_linear_create_sp24: row %d group %zu: first position %u is not below the second %u", j, g, nib & 3u, nib >> 2);
+        return I8IE_ERR_ARG;
+      }
+    }
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  i8ie_layer* L = new (std::nothrow) i8ie_layer();
+  if (!L) return I8IE_ERR_OOM;
+  L->ctx = ctx; L->n = n; L->K = k; L->s_w = s_w_pc ? 1.0f : s_w;
+  L->Kpad = round_up(k, 128);
+  L->Npad = round_up(n, 128);
+  std::vector<uint8_t> panel(i8ie_sp24_panel_bytes(n, k), 0);
+  i8ie_sp24_pack_panel(values_host, index_host, n, k, panel.data());
+  const std::vector<int32_t> zeros((size_t)L->Npad, 0);  // (padding: the quads' vector loads read it)
+  int rc = upload(L, &L->sp24, panel);
+  if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->qb, (size_t)n, qb_host);
+  if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->wsum, (size_t)n * 4);
+  if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->oc, (size_t)L->Npad * 4, zeros.data());
+  if (rc == I8IE_OK) rc = upload(L, &L->ocp, zeros);
+  if (rc == I8IE_OK) rc = upload(L, &L->biasf, zeros);
+  if (rc == I8IE_OK && s_w_pc) rc = upload_scales(L, s_w_pc);
+  if (rc != I8IE_OK) {
+    i8ie_layer_destroy(L);
+    return rc;
+  }
+  *out = L;
+  return I8IE_OK;
+}
+
+int i8ie_linear_create_sp24(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* index_host, const int8_t* qb_host, int n,
+                            int k, float s_w, i8ie_layer** out) {
+  return sp24_create(ctx, values_host, index_host, qb_host, n, k, s_w, nullptr, out);
+}
+
+int i8ie_linear_create_sp24_per_channel(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* index_host, const int8_t* qb_host,
+                                        int n, int k, const float* s_w_host, i8ie_layer** out) {
+  I8IE_REQUIRE(n > 0, "non-positive dimension");
+  I8IE_TRY(check_scales(s_w_host, n));
+  return sp24_create(ctx, values_host, index_host, qb_host, n, k, 1.0f, s_w_host, out);
+}
+
+int i8ie_layer_sparsity(const i8ie_layer* L, int* kept_of_four) {
+  I8IE_REQUIRE(L && kept_of_four, "null argument");
+  *kept_of_four = L->sp24 != nullptr ? 2 : 0;
   return I8IE_OK;
 }
 
@@ -802,6 +862,94 @@ int i8ie_linear_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const u
   I8IE_REQUIRE(m > 0, "non-positive dimension");
   i8ie_layer* L = nullptr;
   I8IE_TRY(i8ie_linear_create_w4(ctx, packed_host, qb_host, s_w_host, n, k, &L));
+  L->s_out = s_out;
+  L->zp_out = zp_out;
+  const int rc = i8ie_layer_forward(L, in_dev, m, 0, 0, s_in, zp_in, out_dev, acc_dbg_dev);
+  i8ie_layer_destroy(L);
+  return rc;
+}
+
+// ---- 2:4 structured sparsity, the host side ------------------------------------------------------------------
+// the pruning rule: in every aligned group of four along k keep the two entries of largest |q|, ties to the lower k
+int i8ie_prune_2_4(const int8_t* qw, int rows, int k, int8_t* pruned) {
+  I8IE_REQUIRE(qw && pruned, "null argument");
+  I8IE_REQUIRE(rows > 0 && k > 0, "empty tensor");
+  for (int j = 0; j < rows; ++j)
+    for (int g0 = 0; g0 < k; g0 += 4) {
+      const int8_t* src = qw + (size_t)j * k + g0;
+      int8_t* dst = pruned + (size_t)j * k + g0;
+      const int len = k - g0 < 4 ? k - g0 : 4;
+      int v[4] = {0, 0, 0, 0}, keep[2];
+      for (int i = 0; i < len; ++i) v[i] = src[i];
+      for (int e = 0; e < 2; ++e) {  // the largest |q| not yet chosen, the lowest position among equals
+        int best = -1;
+        for (int i = 0; i < 4; ++i)
+          if (!(e == 1 && i == keep[0]) && (best < 0 || std::abs(v[i]) > std::abs(v[best]))) best = i;
+        keep[e] = best;
+      }
+      for (int i = 0; i < len; ++i) dst[i] = (i == keep[0] || i == keep[1]) ? (int8_t)v[i] : (int8_t)0;
+    }
+  return I8IE_OK;
+}
+
+// the compressed form, canonical: the kept positions are the non-zero ones, filled up with the lowest positions not yet chosen
+// (holding 0); values [rows][K4 / 2], positions one nibble per group ([rows][K4 / 8], group 2 i in the low nibble of byte i)
+int i8ie_pack_2_4(const int8_t* qw, int rows, int k, int8_t* values, uint8_t* index) {
+  I8IE_REQUIRE(qw && values && index, "null argument");
+  I8IE_REQUIRE(rows > 0 && k > 0, "empty tensor");
+  const size_t groups = ((size_t)k + 3) / 4, ipitch = (groups + 1) / 2;
+  for (int j = 0; j < rows; ++j) {
+    for (size_t i = 0; i < ipitch; ++i) index[j * ipitch + i] = 0;
+    for (size_t g = 0; g < groups; ++g) {
+      int pos[4], cnt = 0;
+      int8_t v[4] = {0, 0, 0, 0};
+      for (int i = 0; i < 4 && 4 * g + i < (size_t)k; ++i) v[i] = qw[(size_t)j * k + 4 * g + i];
+      for (int i = 0; i < 4; ++i)
+        if (v[i] != 0) pos[cnt++] = i;
+      if (cnt > 2) {
+        i8ie_set_error("i8ie_pack_2_4: row %d has %d non-zeros in k = %zu .. %zu: not 2:4", j, cnt, 4 * g, 4 * g + 3);
+        return I8IE_ERR_ARG;
+      }
+      for (int i = 0; cnt < 2; ++i)
+        if (v[i] == 0 && !(cnt == 1 && pos[0] == i)) pos[cnt++] = i;
+      if (pos[0] > pos[1]) { const int t = pos[0]; pos[0] = pos[1]; pos[1] = t; }
+      values[(j * groups + g) * 2] = v[pos[0]];
+      values[(j * groups + g) * 2 + 1] = v[pos[1]];
+      index[j * ipitch + g / 2] |= (uint8_t)((pos[0] | (pos[1] << 2)) << (4 * (g & 1)));
+    }
+  }
+  return I8IE_OK;
+}
+
+int i8ie_unpack_2_4(const int8_t* values, const uint8_t* index, int rows, int k, int8_t* qw) {
+  I8IE_REQUIRE(qw && values && index, "null argument");
+  I8IE_REQUIRE(rows > 0 && k > 0, "empty tensor");
+  const size_t groups = ((size_t)k + 3) / 4, ipitch = (groups + 1) / 2;
+  for (int j = 0; j < rows; ++j)
+    for (size_t g = 0; g < groups; ++g) {
+      const unsigned nib = (index[j * ipitch + g / 2] >> (4 * (g & 1))) & 15u;
+      const unsigned p0 = nib & 3u, p1 = nib >> 2;
+      if (p0 >= p1) {
+        i8ie_set_error("i8ie_unpack_2_4: row %d group %zu: first position %u is not below the second %u", j, g, p0, p1);
+        return I8IE_ERR_ARG;
+      }
+      for (unsigned i = 0; i < 4 && 4 * g + i < (size_t)k; ++i)
+        qw[(size_t)j * k + 4 * g + i] = i == p0 ? values[(j * groups + g) * 2] : (i == p1 ? values[(j * groups + g) * 2 + 1] : (int8_t)0);
+    }
+  return I8IE_OK;
+}
+
+// the stateless form, for tests (as i8ie_linear_u8s4): per_channel != 0 reads n scales at s_w_host, else one
+int i8ie_linear_u8s8_sp24(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const int8_t* values_host, const uint8_t* index_host,
+                          const int8_t* qb_host, const float* s_w_host, int per_channel, int n, float s_in, uint8_t zp_in, float s_out,
+                          uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev) {
+  I8IE_REQUIRE(ctx && in_dev && out_dev && s_w_host, "null argument");
+  I8IE_REQUIRE(m > 0, "non-positive dimension");
+  i8ie_layer* L = nullptr;
+  if (per_channel)
+    I8IE_TRY(i8ie_linear_create_sp24_per_channel(ctx, values_host, index_host, qb_host, n, k, s_w_host, &L));
+  else
+    I8IE_TRY(i8ie_linear_create_sp24(ctx, values_host, index_host, qb_host, n, k, s_w_host[0], &L));
   L->s_out = s_out;
   L->zp_out = zp_out;
   const int rc = i8ie_layer_forward(L, in_dev, m, 0, 0, s_in, zp_in, out_dev, acc_dbg_dev);

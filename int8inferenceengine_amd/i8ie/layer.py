@@ -47,7 +47,7 @@ class Layer:
         """Start collecting output samples for calibration (reference src/layer.cc:28-35)."""
         self.layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
         """Quantise weights, fix the output (scale, zero_point) (reference src/layer.cc:36-54).
 
         per_channel=True (additive, not the reference's rule): one symmetric max-abs weight scale per output
@@ -55,11 +55,32 @@ class Layer:
         weight_bits=4 (additive; i8ie.Linear only, ValueError for every other layer class; any value but 4 or 8 is a
         ValueError): 4-bit weights with one scale per output feature, whatever per_channel says (include/i8ie_hip.h,
         i8ie_quantize_weight_w4).  The layer is then per-channel in every respect: is_per_channel() is True,
-        weight_scales() works and weight_scale() raises."""
+        weight_scales() works and weight_scale() raises.
+        sparsity="2:4" (additive; i8ie.Linear with weight_bits=8 only, ValueError for every other layer class, with
+        weight_bits=4, and for any value but None or "2:4"): quantise as per_channel says, then keep in every aligned group
+        of four along in_features the two integers of largest magnitude, ties to the lower index, and zero the rest
+        (include/i8ie_hip.h, i8ie_prune_2_4).  The scales are those of the dense layer."""
+        sparse = check_sparsity(self, sparsity, weight_bits)
         if check_weight_bits(self, weight_bits) == 4:
             self.layer._convert_w4()
+        elif sparse:
+            self.layer._convert_sp24(bool(per_channel))
         else:
             self.layer.convert(bool(per_channel))
+
+    def sparsity(self):
+        """"2:4" for a Linear converted or loaded with 2:4 structured-sparse weights, None for every other layer."""
+        ask = getattr(self.layer, "_sparse24", None)
+        return "2:4" if ask is not None and ask() else None
+
+    def load_quantized(self, q_weight, q_bias, weight_scale, out_scale, out_zero_point, sparsity=None):
+        """Restore a converted layer from dense INT8 weights (what convert() would have left behind); weight_scale is a number
+        or one scale per output feature.  sparsity="2:4" (i8ie.Linear only) installs them as a 2:4 layer and raises
+        ValueError unless every aligned group of four along in_features holds at most two non-zeros: nothing is pruned here."""
+        if check_sparsity(self, sparsity, 8):
+            self.layer._load_quantized_sp24(q_weight, q_bias, weight_scale, out_scale, out_zero_point)
+        else:
+            self.layer.load_quantized(q_weight, q_bias, weight_scale, out_scale, out_zero_point)
 
     def weight_bits(self):
         """4 for a Linear converted or loaded with 4-bit weights, 8 for every other layer."""
@@ -126,6 +147,19 @@ def check_weight_bits(layer, weight_bits):
     return weight_bits
 
 
+def check_sparsity(layer, sparsity, weight_bits=8):
+    """sparsity as convert() takes it: None, or "2:4" on a Linear with 8-bit weights; ValueError otherwise.  True for "2:4"."""
+    if sparsity is None:
+        return False
+    if not isinstance(sparsity, str) or sparsity != "2:4":
+        raise ValueError("convert: sparsity must be None or \"2:4\", got %r" % (sparsity,))
+    if not isinstance(layer, Linear):
+        raise ValueError("convert: sparsity=\"2:4\" is for i8ie.Linear only, not %s" % type(layer).__name__)
+    if weight_bits == 4:
+        raise ValueError("convert: sparsity=\"2:4\" keeps 8-bit weights; it does not combine with weight_bits=4")
+    return True
+
+
 def _pair(value, name):
     """(h, w) of a geometry argument given as an int or as a pair of ints; anything else is a TypeError"""
     def is_int(v):
@@ -175,9 +209,10 @@ class Norm(Layer):
     zero_point) and no INT8 weights.  Module.load() takes `<attr>.weight` / `<attr>.bias`; quantized_state_dict() keeps both as
     float32 beside `<attr>.qparams`.  weight_scale, weight_scales, q_weight, q_bias and forward_debug raise RuntimeError."""
 
-    def convert(self, per_channel=False, weight_bits=8):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
         """per_channel is accepted and ignored: there are no INT8 weights."""
         check_weight_bits(self, weight_bits)
+        check_sparsity(self, sparsity, weight_bits)
         self.layer.convert()
 
     def is_per_channel(self):
@@ -282,9 +317,10 @@ class BatchNorm2d(Norm):
         if not self._folded:
             self.layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
         """per_channel is accepted and ignored: there are no INT8 weights.  A folded BatchNorm stays as it is."""
         check_weight_bits(self, weight_bits)
+        check_sparsity(self, sparsity, weight_bits)
         if not self._folded:
             self.layer.convert()
 
@@ -355,9 +391,10 @@ class Weightless(Layer):
     (`<attr>.qparams` only); Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values);
     load_weight, load_bias, weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
 
-    def convert(self, per_channel=False, weight_bits=8):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
         """per_channel is accepted and ignored."""
         check_weight_bits(self, weight_bits)
+        check_sparsity(self, sparsity, weight_bits)
         self.layer.convert()
 
     def is_per_channel(self):

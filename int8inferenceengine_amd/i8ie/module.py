@@ -52,14 +52,18 @@ class Module:
         for _, layer in self._layers():
             layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
         """per_channel=True: every layer with one weight scale per output feature (Layer.convert).  weight_bits=4: every
         Linear converts to 4-bit weights, every other layer as with 8 under the given per_channel; any value but 4 or 8 is a
-        ValueError."""
+        ValueError.  sparsity="2:4": every Linear converts to 2:4 structured-sparse 8-bit weights, every other layer as
+        before; any value but None or "2:4", or weight_bits=4 with it, is a ValueError."""
         if weight_bits not in (4, 8) or isinstance(weight_bits, bool):
             raise ValueError("convert: weight_bits must be 4 or 8, got %r" % (weight_bits,))
+        if sparsity is not None and (not isinstance(sparsity, str) or sparsity != "2:4" or weight_bits == 4):
+            raise ValueError("convert: sparsity must be None or \"2:4\" (with weight_bits=8), got %r" % (sparsity,))
         for _, layer in self._layers():
-            layer.convert(per_channel, weight_bits if isinstance(layer, Linear) else 8)
+            linear = isinstance(layer, Linear)
+            layer.convert(per_channel, weight_bits if linear else 8, sparsity if linear else None)
         self.is_quant = True
 
     # ---- additive: save / restore the converted (INT8) model ------------------
@@ -104,6 +108,8 @@ class Module:
                 continue
             if layer.weight_bits() == 4:  # uint8 [out, ceil(in / 2)]: element 2i in the low nibble of byte i (i8ie_pack_w4)
                 out[name + ".q_weight4"] = L._q_weight4()
+            elif layer.sparsity() == "2:4":  # int8 [out, K4 / 2] and uint8 [out, K4 / 8], one nibble per group (i8ie_pack_2_4)
+                out[name + ".q_weight24"], out[name + ".q_index24"] = L._q_weight24()
             else:
                 out[name + ".q_weight"] = L.q_weight()
             out[name + ".q_bias"] = L.q_bias()
@@ -155,6 +161,13 @@ class Module:
                 w_scale = np.ascontiguousarray(state[name + ".w_scales"], np.float32)
             else:
                 w_scale = float(np.float32(w_scale))
+            if name + ".q_weight24" in state:  # 2:4 Linear
+                if not isinstance(layer, Linear):
+                    raise RuntimeError("i8ie: load_quantized: %r carries 2:4 weights (.q_weight24), which only a Linear takes; "
+                                       "the layer is a %s" % (name, type(layer).__name__))
+                layer.layer._load_compressed_sp24(np.asarray(state[name + ".q_weight24"], np.int8), np.asarray(state[name + ".q_index24"], np.uint8),
+                                                  np.asarray(state[name + ".q_bias"], np.int8), w_scale, float(np.float32(s_out)), int(zp_out))
+                continue
             layer.layer.load_quantized(np.asarray(state[name + ".q_weight"], np.int8),
                                        np.asarray(state[name + ".q_bias"], np.int8),
                                        w_scale, float(np.float32(s_out)), int(zp_out))
