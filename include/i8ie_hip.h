@@ -593,6 +593,42 @@ int i8ie_layer_sparsity(const i8ie_layer* layer, int* kept_of_four);
 int i8ie_linear_u8s8_sp24(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const int8_t* values_host,
                           const uint8_t* index_host, const int8_t* qb_host, const float* s_w_host, int per_channel, int n,
                           float s_in, uint8_t zp_in, float s_out, uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
+
+/* ---- 4-bit weights for Linear with group-wise scales along K (W4A8, integer group scales; not in the reference; DESIGN.md
+ * section 8za) ----------------------------------------------------------------------------------------------------------------
+ * group_size gs is 64, 128 or 256; G = ceil(k / gs); group g covers k = g gs .. min(K, (g + 1) gs) - 1 of the weight's own
+ * in_features axis.  A grouped layer holds per output feature j nibbles q[j,k] in [-8, 7], multipliers m[j,g] in [1, 32] (u8),
+ * an s8 bias q_b[j] and one fp32 scale s_w[j].  It IS the per-channel Linear of i8ie_linear_u8s8 on the integers
+ *   W_eff[j,k] = m[j, k / gs] * q[j,k]   (|W_eff| <= 256)     and the bias integer 32 q_b[j]:
+ *   t_j = the sequential fp32 sum over ascending k of zp_in * W_eff[j,k];  oc[j] = (int)(-t_j)
+ *   C = X W_eff^T + oc  in exact int32;  acc_dbg receives this C
+ *   C = (int)((float)C + (float)(32 q_b[j]) / s_in);  out = down_scale(C, s_in, s_w[j], s_out, zp_out), then the optional relu
+ * k <= 32768 (enforced at create), so |C| <= 255 * 256 * 32768 < 2^31.  Because the group scale is an integer multiple of the
+ * row's scale the sum is exact whatever its order, and every result is bit for bit that of the definition.
+ * Quantiser (host, IEEE fp32, one rounding per operation, rint half to even; b_host may be NULL: zero bias):
+ *   a_j = max(max_k |w[j,k]|, |b[j]| * 7 / 127);  S_j = a_j / 7  (a_j == 0: 1)       -- the 4-bit scale of i8ie_quantize_weight_w4
+ *   s_w[j] = S_j / 32
+ *   m[j,g] = clamp(ceil((32 * max_{k in g} |w[j,k]|) / a_j), 1, 32)                   (a_j == 0: 1)
+ *   q[j,k] = clamp(rint(w[j,k] / ((S_j * (float)m[j,g]) / 32)), -7, 7);  q_b[j] = clamp(rint(b[j] / S_j), -127, 127)
+ * qw_host receives one s8 per weight (i8ie_pack_w4 makes the stored form), m_host u8 [rows, G]. */
+int i8ie_quantize_weight_w4g(const float* w_host, int rows, int64_t row_len, const float* b_host, int group_size,
+                             int8_t* qw_host, uint8_t* m_host, int8_t* qb_host, float* scales_host);
+/* A grouped Linear [n, k] from rows packed as i8ie_pack_w4 packs them (any nibble in [-8, 7]), multipliers u8 [n, G], s8 biases
+ * and one finite scale >= 0 per output feature, all host pointers.  A multiplier outside [1, 32], a group_size other than 64,
+ * 128, 256 or k > 32768 is I8IE_ERR_ARG: nothing is clamped.  These values are checked before the context is used.  The handle
+ * holds the nibble panel of csrc/i8ie_w4lin.hip, the multipliers as [feature tile of 16][group][16] bytes and the per-feature
+ * vectors: no unpacked copy of the weights exists on the device.  Kernels: w4glin_mfma when k % 32 == 0, the input is 16-byte
+ * aligned, its rows are in the reference's K order and I8IE_OPT_FORCE_FALLBACK is off (any m, any n, one launch); w4glin_direct
+ * otherwise, also for rows that are a flattened NHWC map with h * w > 1.  i8ie_layer_forward, i8ie_layer_forward_fused (relu
+ * folded) and i8ie_layer_forward_dequant (needs out_u8; runs the dequantize kernel behind the forward) all take the handle. */
+int i8ie_linear_create_w4g(i8ie_ctx* ctx, const uint8_t* packed_host, const uint8_t* m_host, const int8_t* qb_host,
+                           const float* s_w_host, int n, int k, int group_size, i8ie_layer** out);
+/* *group_size = 64, 128 or 256 for a layer of i8ie_linear_create_w4g, 0 for every other layer (i8ie_layer_weight_bits gives 4) */
+int i8ie_layer_group_size(const i8ie_layer* layer, int* group_size);
+/* Stateless form (for tests), as i8ie_linear_u8s4: acc_dbg_dev: NULL, or int32 [m, n] receiving C BEFORE the float bias step. */
+int i8ie_linear_u8s4g(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const uint8_t* packed_host, const uint8_t* m_host,
+                      const int8_t* qb_host, const float* s_w_host, int n, int group_size, float s_in, uint8_t zp_in,
+                      float s_out, uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
 /* the layer's output (scale_, zero_point_): src/layer.cc:44, include/layer.h:46-47 (default 1, 0) */
 int i8ie_layer_set_output_qparams(i8ie_layer* layer, float s_out, uint8_t zp_out);
 int i8ie_layer_get_output_qparams(const i8ie_layer* layer, float* s_out, uint8_t* zp_out);

@@ -7,6 +7,7 @@ class Linear : public BaseLayer {
  public:
   Linear(ssize_t in_channel, ssize_t out_channel) : BaseLayer({out_channel, in_channel}, out_channel) {}
   using BaseLayer::BaseLayer;
+  using U8Array = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
 
   Tensor<float> forward_f32(Tensor<float>& in) {  // src/fully_connected.cc:5-21
     need_fp32();
@@ -44,6 +45,7 @@ class Linear : public BaseLayer {
                                   reinterpret_cast<int8_t*>(qb_.data()), w_scales_.data()));
     qw4_.assign((size_t)(n * ((k + 1) / 2)), 0);
     check(i8ie_pack_w4(reinterpret_cast<const int8_t*>(q.data()), (int)n, (int)k, qw4_.data()));
+    drop_groups();
     install_w4();
   }
   void load_quantized_w4(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> packed, S8Array qb, F32Array scales,
@@ -61,7 +63,66 @@ class Linear : public BaseLayer {
     scale_ = s_out;
     zero_point_ = (u8_t)zp_out;
     qparams_overridden_ = true;
+    drop_groups();
     install_w4();
+  }
+
+  // ---- ... with group-wise scales along K (include/i8ie_hip.h, "4-bit weights for Linear with group-wise scales"): beside the
+  //      packed rows the layer keeps the multipliers qm_ [out, ceil(in / group_size)] on the host; w_scales_ holds s_w[j] = S_j / 32
+  void convert_w4g(int group_size) {
+    if (wshape_.size() == 2 && wshape_[1] > 32768)
+      throw py::value_error("i8ie: convert: group_size needs in_features <= 32768 (the INT32 accumulator's bound)");
+    if (!convert_qparams()) return;
+    check_shapes();
+    const ssize_t n = wshape_[0], k = wshape_[1], groups = (k + group_size - 1) / group_size;
+    std::vector<s8_t> q(w_.size());
+    std::vector<uint8_t> qm((size_t)(n * groups));
+    qb_.resize(b_.size());
+    w_scales_.assign((size_t)n, 0.0f);
+    check(i8ie_quantize_weight_w4g(w_.data(), (int)n, (int64_t)k, b_.data(), group_size, reinterpret_cast<int8_t*>(q.data()), qm.data(),
+                                   reinterpret_cast<int8_t*>(qb_.data()), w_scales_.data()));
+    qw4_.assign((size_t)(n * ((k + 1) / 2)), 0);
+    check(i8ie_pack_w4(reinterpret_cast<const int8_t*>(q.data()), (int)n, (int)k, qw4_.data()));
+    qm_.swap(qm);
+    gsize_ = group_size;
+    install_w4();
+  }
+  // nothing is clamped at load: a group size other than 64 / 128 / 256 or a multiplier outside [1, 32] is a ValueError, raised
+  // before the layer changes or any device call
+  void load_quantized_w4g(U8Array packed, U8Array qm, int group_size, S8Array qb, F32Array scales, float s_out, int zp_out) {
+    check_zero_point(zp_out);
+    const ssize_t n = wshape_[0], k = wshape_[1];
+    if (group_size != 64 && group_size != 128 && group_size != 256)
+      throw py::value_error("i8ie: load_quantized: group_size must be 64, 128 or 256, got " + std::to_string(group_size));
+    if (k > 32768) throw py::value_error("i8ie: load_quantized: a grouped 4-bit Linear takes at most 32768 input features");
+    const ssize_t groups = (k + group_size - 1) / group_size;
+    if (packed.ndim() != 2 || packed.shape(0) != n || packed.shape(1) != (k + 1) / 2)
+      throw std::runtime_error("i8ie: Linear: load_quantized: q_weight4 must be uint8 [out_features, ceil(in_features / 2)]");
+    if (qm.ndim() != 2 || qm.shape(0) != n || qm.shape(1) != groups)
+      throw py::value_error("i8ie: Linear: load_quantized: q_group_scales must be uint8 [out_features, ceil(in_features / group_size)]");
+    for (ssize_t e = 0; e < qm.size(); ++e)
+      if (qm.data()[e] < 1 || qm.data()[e] > 32)
+        throw py::value_error("i8ie: load_quantized: group multiplier " + std::to_string((int)qm.data()[e]) + " is outside [1, 32]");
+    if (qb.size() != n) throw std::runtime_error("i8ie: load_quantized: bias size mismatch");
+    if (scales.ndim() != 1 || scales.size() != n)
+      throw std::runtime_error("i8ie: load_quantized: weight_scale array must hold one scale per output feature");
+    qw4_.assign(packed.data(), packed.data() + packed.size());
+    qm_.assign(qm.data(), qm.data() + qm.size());
+    gsize_ = group_size;
+    qb_.assign(qb.data(), qb.data() + qb.size());
+    w_scales_.assign(scales.data(), scales.data() + scales.size());
+    scale_ = s_out;
+    zero_point_ = (u8_t)zp_out;
+    qparams_overridden_ = true;
+    install_w4();
+  }
+  int group_size() const { return qw4_.empty() ? 0 : gsize_; }
+  py::array_t<uint8_t> group_scales() const {
+    need_quantized();
+    if (group_size() == 0) throw std::runtime_error("i8ie: group_scales: the layer has no group-wise scales");
+    py::array_t<uint8_t> a(std::vector<ssize_t>{wshape_[0], (wshape_[1] + gsize_ - 1) / gsize_});
+    std::memcpy(a.mutable_data(), qm_.data(), qm_.size());
+    return a;
   }
   int weight_bits() const { return qw4_.empty() ? 8 : 4; }
   py::array_t<uint8_t> q_weight4() const {
@@ -177,6 +238,11 @@ class Linear : public BaseLayer {
       throw;
     }
     if (qw_.empty()) qw4_.swap(keep4);
+    if (qw4_.empty()) drop_groups();
+  }
+  void drop_groups() {
+    gsize_ = 0;
+    std::vector<uint8_t>().swap(qm_);
   }
   void install_w4() {
     std::vector<s8_t>().swap(qw_);
@@ -188,7 +254,8 @@ class Linear : public BaseLayer {
     if (wshape_.size() != 2) throw std::runtime_error("i8ie: Linear weight must be [out_features, in_features]");
     if (has_fp32_ && (ssize_t)b_.size() != wshape_[0]) throw std::runtime_error("i8ie: Linear bias size mismatch");
   }
-  std::vector<uint8_t> qw4_;
+  std::vector<uint8_t> qw4_, qm_;  // qm_, gsize_: the group multipliers and size of a grouped 4-bit layer (gsize_ 0: one scale per row)
+  int gsize_ = 0;
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
     made_ = true;
@@ -207,6 +274,11 @@ class Linear : public BaseLayer {
     }
     if (!qw4_.empty()) {
       sp24_ = false;
+      if (gsize_ != 0) {
+        check(i8ie_linear_create_w4g(ctx(), qw4_.data(), qm_.data(), reinterpret_cast<const int8_t*>(qb_.data()), w_scales_.data(), (int)n,
+                                     (int)wshape_[1], gsize_, &l));
+        return l;
+      }
       check(i8ie_linear_create_w4(ctx(), qw4_.data(), reinterpret_cast<const int8_t*>(qb_.data()), w_scales_.data(), (int)n,
                                   (int)wshape_[1], &l));
       return l;
@@ -518,6 +590,11 @@ void bind_layers(py::module_& m) {
              py::arg("out_scale"), py::arg("out_zero_point"))
         .def("_weight_bits", &Linear::weight_bits)
         .def("_q_weight4", &Linear::q_weight4)
+        .def("_convert_w4g", &Linear::convert_w4g, py::arg("group_size"))
+        .def("_load_quantized_w4g", &Linear::load_quantized_w4g, py::arg("q_weight4"), py::arg("q_group_scales"), py::arg("group_size"),
+             py::arg("q_bias"), py::arg("weight_scales"), py::arg("out_scale"), py::arg("out_zero_point"))
+        .def("_group_size", &Linear::group_size)
+        .def("_group_scales", &Linear::group_scales)
         .def("_convert_sp24", &Linear::convert_sp24, py::arg("per_channel"))
         .def("_load_quantized_sp24", &Linear::load_quantized_sp24, py::arg("q_weight"), py::arg("q_bias"), py::arg("weight_scale"),
              py::arg("out_scale"), py::arg("out_zero_point"))

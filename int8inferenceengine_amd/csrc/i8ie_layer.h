@@ -132,6 +132,10 @@ struct i8ie_layer {
   // a Linear of i8ie_linear_create_sp24: the compressed 2:4 panel of i8ie_sp24lin.h, per-tensor or pc, and
   // the per-feature vectors ([Npad]); qw, Bpack and Bperm stay null -- no dense copy of the weights exists on the device
   uint8_t* sp24 = nullptr;
+  // a Linear of i8ie_linear_create_w4g: wbits = 4, gsize = 64 / 128 / 256, always pc.  w4 is the nibble
+  // panel and w4m the group multipliers in the layout of i8ie_w4glin.h; swv holds s_w[j] = S_j / 32.  No unpacked copy, no `wc` entry.
+  int gsize = 0;
+  uint8_t* w4m = nullptr;
 };
 
 // the geometry the kernels walk: the handle's numbers with the effective dilations

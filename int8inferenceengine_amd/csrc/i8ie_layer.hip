@@ -32,6 +32,7 @@
 #include "i8ie_lconv.h"
 #include "i8ie_w4lin.h"
 #include "i8ie_sp24lin.h"
+#include "i8ie_w4glin.h"
 
 // ---- v1 (fallback) runners ------------------------------------------------------------------
 int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, const int8_t* Bpack, const int32_t* oc,
@@ -98,7 +99,9 @@ int ensure_offsets(i8ie_layer* L, float s_in, uint8_t zp_in) {
   // the reference recomputes this on every call (src/conv2d.cc:117-124); it only depends on
   // (s_in, zp_in), which are fixed once the network is converted
   i8ie_ctx* ctx = L->ctx;
-  if (L->wbits == 4) {  // the same vectors from the nibbles, in one launch
+  if (L->gsize != 0) {  // from the nibbles and the group multipliers, in one launch
+    I8IE_TRY(i8ie_w4g_launch_offsets(ctx, L->w4, L->w4m, L->qb, L->n, L->K, L->gsize, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
+  } else if (L->wbits == 4) {  // the same vectors from the nibbles, in one launch
     I8IE_TRY(i8ie_w4_launch_offsets(ctx, L->w4, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
   } else if (L->sp24 != nullptr) {  // ... and from the compressed 2:4 panel
     I8IE_TRY(i8ie_sp24_launch_offsets(ctx, L->sp24, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
@@ -597,11 +600,37 @@ static int forward_linear_sp24(i8ie_layer* L, const ConvRequest& q) {
   return i8ie_sp24lin_mfma_launch(ctx, c);
 }
 
+// ---- Linear with 4-bit weights and group scales (i8ie_linear_create_w4g): the two kernels of i8ie_w4glin.hip and nothing else.
+// Rows that are a flattened NHWC activation go to the definition kernel: a K-permuted panel cannot keep a group's K contiguous
+// (a layout conversion ahead of the MFMA kernel is a follow-up, as for the 2:4 layer).
+static int forward_linear_w4g(i8ie_layer* L, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  const int m = q.m;
+  I8IE_REQUIRE(q.out != nullptr, "i8ie_layer_forward_dequant: this layer needs the u8 output buffer as well");
+  if (q.out_f32 != nullptr) {  // the ordinary forward, then the dequantize kernel
+    ConvRequest r = q;
+    r.out_f32 = nullptr;
+    I8IE_TRY(forward_linear_w4g(L, r));
+    return i8ie_dequantize_u8_f32(ctx, q.out, q.out_f32, (int64_t)m * L->n, L->s_out, L->zp_out);
+  }
+  const int hw = (q.in_layout == I8IE_LAYOUT_NHWC && q.h > 0 && q.w > 0) ? q.h * q.w : 1;
+  if (hw > 1) I8IE_REQUIRE(L->K % hw == 0, "Linear: in_features is not c * h * w for the given h, w");
+  I8ieW4gCall c{};
+  c.A = q.in; c.M = m; c.N = L->n; c.K = L->K; c.gs = L->gsize; c.B = L->w4; c.Mg = L->w4m; c.hw = hw; c.out = q.out;
+  c.ep = layer_epilogue(L, q, L->biasf);
+  if (force_fallback(ctx) || !i8ie_w4glin_mfma_takes(c)) {
+    c.ep.ocp = L->oc;  // (the definition reads the activations as they are)
+    return i8ie_w4glin_direct_launch(ctx, c);
+  }
+  return i8ie_w4glin_mfma_launch(ctx, c);
+}
+
 // ---- Linear: row-major in / out ------------------------------------------------------------------------------------------------
 static int forward_linear(i8ie_layer* L, const ConvRequest& q) {
   i8ie_ctx* ctx = L->ctx;
   const int m = q.m;
   I8IE_REQUIRE(q.in_border == 0 && q.out_border == 0, "Linear tensors carry no border");
+  if (L->gsize != 0) return forward_linear_w4g(L, q);
   if (L->wbits == 4) return forward_linear_w4(L, q);
   if (L->sp24 != nullptr) return forward_linear_sp24(L, q);
   // Rows that are a flattened NHWC activation [m][h][w][c] (the engine's layout between layers) instead of

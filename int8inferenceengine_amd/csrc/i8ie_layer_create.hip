@@ -14,6 +14,7 @@
 #include "i8ie_gconv.h"
 #include "i8ie_deconv.h"
 #include "i8ie_w4lin.h"
+#include "i8ie_w4glin.h"
 #include "i8ie_sp24lin.h"
 
 namespace {
@@ -401,6 +402,55 @@ int i8ie_linear_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_
 int i8ie_layer_weight_bits(const i8ie_layer* L, int* bits) {
   I8IE_REQUIRE(L && bits, "null argument");
   *bits = L->wbits;
+  return I8IE_OK;
+}
+
+// A Linear with 4-bit weights and integer group scales along K: the nibble panel of i8ie_w4lin.h, the
+// multipliers in the layout of i8ie_w4glin.h and the per-feature vectors; no unpacked copy reaches the device.  The values are
+// checked before the context is touched, so a refused argument needs no device.
+int i8ie_linear_create_w4g(i8ie_ctx* ctx, const uint8_t* packed_host, const uint8_t* m_host, const int8_t* qb_host,
+                           const float* s_w_host, int n, int k, int group_size, i8ie_layer** out) {
+  I8IE_REQUIRE(packed_host && m_host && qb_host && out, "null argument");
+  I8IE_REQUIRE(n > 0 && k > 0, "non-positive dimension");
+  I8IE_REQUIRE(i8ie_w4g_size_ok(group_size), "grouped 4-bit Linear: group_size must be 64, 128 or 256");
+  I8IE_REQUIRE(k <= 32768, "grouped 4-bit Linear: at most 32768 input features (255 * 256 * K must stay inside int32)");
+  I8IE_TRY(check_scales(s_w_host, n));
+  const int G = i8ie_w4g_groups(k, group_size);
+  for (size_t e = 0; e < (size_t)n * G; ++e)
+    if (m_host[e] < 1 || m_host[e] > 32) {
+      i8ie_set_error("i8ie_linear_create_w4g: multiplier %u of feature %zu, group %zu is outside [1, 32]", (unsigned)m_host[e], e / G, e % G);
+      return I8IE_ERR_ARG;
+    }
+  I8IE_REQUIRE(ctx != nullptr, "null context");
+  I8IE_HIP_TRY(hipSetDevice(ctx->device));
+  i8ie_layer* L = new (std::nothrow) i8ie_layer();
+  if (!L) return I8IE_ERR_OOM;
+  L->ctx = ctx; L->n = n; L->K = k; L->wbits = 4; L->gsize = group_size;
+  L->Kpad = round_up(k, 128);
+  L->Npad = round_up(n, 128);
+  std::vector<uint8_t> panel(i8ie_w4_panel_bytes(n, k), 0), mult(i8ie_w4g_mult_bytes(n, k, group_size));
+  i8ie_w4_pack_panel(packed_host, n, k, panel.data());
+  i8ie_w4g_pack_mult(m_host, n, k, group_size, mult.data());
+  const std::vector<int32_t> zeros((size_t)L->Npad, 0);  // (padding: the quads' vector loads read it)
+  int rc = upload(L, &L->w4, panel);
+  if (rc == I8IE_OK) rc = upload(L, &L->w4m, mult);
+  if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->qb, (size_t)n, qb_host);
+  if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->wsum, (size_t)n * 4);
+  if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->oc, (size_t)L->Npad * 4, zeros.data());
+  if (rc == I8IE_OK) rc = upload(L, &L->ocp, zeros);
+  if (rc == I8IE_OK) rc = upload(L, &L->biasf, zeros);
+  if (rc == I8IE_OK) rc = upload_scales(L, s_w_host);
+  if (rc != I8IE_OK) {
+    i8ie_layer_destroy(L);
+    return rc;
+  }
+  *out = L;
+  return I8IE_OK;
+}
+
+int i8ie_layer_group_size(const i8ie_layer* L, int* group_size) {
+  I8IE_REQUIRE(L && group_size, "null argument");
+  *group_size = L->gsize;
   return I8IE_OK;
 }
 
@@ -824,6 +874,42 @@ int i8ie_quantize_weight_w4(const float* w, int rows, int64_t row_len, const flo
   return I8IE_OK;
 }
 
+// 4-bit weights with integer group scales along K.  S_j is the 4-bit scale above; group g of row j is
+// quantised at S_j * m / 32 with the smallest integer m in [1, 32] that still covers the group's largest weight, so a group of
+// small weights gets up to 32 times finer levels while W_eff = m * q stays an integer at the row's one scale s_w[j] = S_j / 32.
+int i8ie_quantize_weight_w4g(const float* w, int rows, int64_t row_len, const float* b, int group_size, int8_t* qw, uint8_t* m_u8,
+                             int8_t* qb, float* scales) {
+  I8IE_REQUIRE(w && qw && m_u8 && qb && scales, "null argument");
+  I8IE_REQUIRE(rows > 0 && row_len > 0, "empty tensor");
+  I8IE_REQUIRE(i8ie_w4g_size_ok(group_size), "i8ie_quantize_weight_w4g: group_size must be 64, 128 or 256");
+  auto q = [](float x, float s, float lim) {
+    float r = std::nearbyint(x / s);  // (the default rounding mode: to nearest, ties to even)
+    r = r > lim ? lim : (r < -lim ? -lim : r);
+    return (int8_t)(int32_t)r;
+  };
+  const int64_t G = (row_len + group_size - 1) / group_size;
+  for (int j = 0; j < rows; ++j) {
+    const float* row = w + (size_t)j * row_len;
+    const float bj = b ? b[j] : 0.0f;
+    float a = std::fabs(bj) * 7.0f / 127.0f;
+    for (int64_t k = 0; k < row_len; ++k) a = std::fabs(row[k]) > a ? std::fabs(row[k]) : a;
+    const float S = a == 0.0f ? 1.0f : a / 7.0f;
+    for (int64_t g = 0; g < G; ++g) {
+      const int64_t k0 = g * group_size, k1 = k0 + group_size < row_len ? k0 + group_size : row_len;
+      float top = 0.0f;
+      for (int64_t k = k0; k < k1; ++k) top = std::fabs(row[k]) > top ? std::fabs(row[k]) : top;
+      float mf = a == 0.0f ? 1.0f : std::ceil((32.0f * top) / a);
+      mf = mf < 1.0f ? 1.0f : (mf > 32.0f ? 32.0f : mf);
+      m_u8[(size_t)j * G + g] = (uint8_t)mf;
+      const float step = (S * mf) / 32.0f;
+      for (int64_t k = k0; k < k1; ++k) qw[(size_t)j * row_len + k] = q(row[k], step, 7.0f);
+    }
+    qb[j] = q(bj, S, 127.0f);
+    scales[j] = S / 32.0f;
+  }
+  return I8IE_OK;
+}
+
 // the packed format: row j is ceil(k / 2) bytes, element 2 i in the low nibble of byte i, 2 i + 1 in the high one, two's complement
 int i8ie_pack_w4(const int8_t* qw, int rows, int k, uint8_t* packed) {
   I8IE_REQUIRE(qw && packed, "null argument");
@@ -862,6 +948,21 @@ int i8ie_linear_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const u
   I8IE_REQUIRE(m > 0, "non-positive dimension");
   i8ie_layer* L = nullptr;
   I8IE_TRY(i8ie_linear_create_w4(ctx, packed_host, qb_host, s_w_host, n, k, &L));
+  L->s_out = s_out;
+  L->zp_out = zp_out;
+  const int rc = i8ie_layer_forward(L, in_dev, m, 0, 0, s_in, zp_in, out_dev, acc_dbg_dev);
+  i8ie_layer_destroy(L);
+  return rc;
+}
+
+// ... and with group scales
+int i8ie_linear_u8s4g(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const uint8_t* packed_host, const uint8_t* m_host,
+                      const int8_t* qb_host, const float* s_w_host, int n, int group_size, float s_in, uint8_t zp_in, float s_out,
+                      uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev) {
+  I8IE_REQUIRE(ctx && in_dev && out_dev, "null argument");
+  I8IE_REQUIRE(m > 0, "non-positive dimension");
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_linear_create_w4g(ctx, packed_host, m_host, qb_host, s_w_host, n, k, group_size, &L));
   L->s_out = s_out;
   L->zp_out = zp_out;
   const int rc = i8ie_layer_forward(L, in_dev, m, 0, 0, s_in, zp_in, out_dev, acc_dbg_dev);

@@ -47,7 +47,7 @@ class Layer:
         """Start collecting output samples for calibration (reference src/layer.cc:28-35)."""
         self.layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
         """Quantise weights, fix the output (scale, zero_point) (reference src/layer.cc:36-54).
 
         per_channel=True (additive, not the reference's rule): one symmetric max-abs weight scale per output
@@ -59,10 +59,18 @@ class Layer:
         sparsity="2:4" (additive; i8ie.Linear with weight_bits=8 only, ValueError for every other layer class, with
         weight_bits=4, and for any value but None or "2:4"): quantise as per_channel says, then keep in every aligned group
         of four along in_features the two integers of largest magnitude, ties to the lower index, and zero the rest
-        (include/i8ie_hip.h, i8ie_prune_2_4).  The scales are those of the dense layer."""
+        (include/i8ie_hip.h, i8ie_prune_2_4).  The scales are those of the dense layer.
+        group_size=64, 128 or 256 (additive; i8ie.Linear with weight_bits=4 only, ValueError for every other layer class, for
+        weight_bits=8, with sparsity, and for any other value): every group of that many weights along in_features gets an
+        integer multiplier in [1, 32] of the row's scale / 32, so a group of small weights keeps its sixteen levels
+        (include/i8ie_hip.h, i8ie_quantize_weight_w4g).  weight_scales() then gives the row's scale / 32."""
         sparse = check_sparsity(self, sparsity, weight_bits)
+        grouped = check_group_size(self, group_size, weight_bits, sparsity)
         if check_weight_bits(self, weight_bits) == 4:
-            self.layer._convert_w4()
+            if grouped:
+                self.layer._convert_w4g(grouped)
+            else:
+                self.layer._convert_w4()
         elif sparse:
             self.layer._convert_sp24(bool(per_channel))
         else:
@@ -86,6 +94,18 @@ class Layer:
         """4 for a Linear converted or loaded with 4-bit weights, 8 for every other layer."""
         ask = getattr(self.layer, "_weight_bits", None)
         return 8 if ask is None else int(ask())
+
+    def group_size(self):
+        """64, 128 or 256 for a Linear converted or loaded with group-wise 4-bit scales, None for every other layer."""
+        ask = getattr(self.layer, "_group_size", None)
+        return (int(ask()) or None) if ask is not None else None
+
+    def group_scales(self):
+        """np.uint8[out, ceil(in / group_size)]: the integer multiplier m[j, g] of every group (RuntimeError for a layer
+        without group-wise scales).  Weight (j, k) stands for m[j, k // group_size] * q_weight()[j, k] * weight_scales()[j]."""
+        if self.group_size() is None:
+            raise RuntimeError("i8ie: group_scales: the layer has no group-wise scales")
+        return self.layer._group_scales()
 
     # ---- additive (the reference cannot inject or read these) ----------------
     def set_output_qparams(self, scale, zero_point):
@@ -160,6 +180,20 @@ def check_sparsity(layer, sparsity, weight_bits=8):
     return True
 
 
+def check_group_size(layer, group_size, weight_bits=8, sparsity=None):
+    """group_size as convert() takes it: None, or 64 / 128 / 256 on a Linear with weight_bits=4 and no sparsity; ValueError
+    otherwise.  The int, or 0 for None."""
+    if group_size is None:
+        return 0
+    if isinstance(group_size, bool) or group_size not in (64, 128, 256):
+        raise ValueError("convert: group_size must be None, 64, 128 or 256, got %r" % (group_size,))
+    if not isinstance(layer, Linear):
+        raise ValueError("convert: group_size is for i8ie.Linear only, not %s" % type(layer).__name__)
+    if weight_bits != 4 or sparsity is not None:
+        raise ValueError("convert: group_size needs weight_bits=4 and no sparsity")
+    return int(group_size)
+
+
 def _pair(value, name):
     """(h, w) of a geometry argument given as an int or as a pair of ints; anything else is a TypeError"""
     def is_int(v):
@@ -209,10 +243,11 @@ class Norm(Layer):
     zero_point) and no INT8 weights.  Module.load() takes `<attr>.weight` / `<attr>.bias`; quantized_state_dict() keeps both as
     float32 beside `<attr>.qparams`.  weight_scale, weight_scales, q_weight, q_bias and forward_debug raise RuntimeError."""
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
         """per_channel is accepted and ignored: there are no INT8 weights."""
         check_weight_bits(self, weight_bits)
         check_sparsity(self, sparsity, weight_bits)
+        check_group_size(self, group_size, weight_bits, sparsity)
         self.layer.convert()
 
     def is_per_channel(self):
@@ -317,10 +352,11 @@ class BatchNorm2d(Norm):
         if not self._folded:
             self.layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
         """per_channel is accepted and ignored: there are no INT8 weights.  A folded BatchNorm stays as it is."""
         check_weight_bits(self, weight_bits)
         check_sparsity(self, sparsity, weight_bits)
+        check_group_size(self, group_size, weight_bits, sparsity)
         if not self._folded:
             self.layer.convert()
 
@@ -391,10 +427,11 @@ class Weightless(Layer):
     (`<attr>.qparams` only); Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values);
     load_weight, load_bias, weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
         """per_channel is accepted and ignored."""
         check_weight_bits(self, weight_bits)
         check_sparsity(self, sparsity, weight_bits)
+        check_group_size(self, group_size, weight_bits, sparsity)
         self.layer.convert()
 
     def is_per_channel(self):

@@ -52,18 +52,22 @@ class Module:
         for _, layer in self._layers():
             layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
         """per_channel=True: every layer with one weight scale per output feature (Layer.convert).  weight_bits=4: every
         Linear converts to 4-bit weights, every other layer as with 8 under the given per_channel; any value but 4 or 8 is a
         ValueError.  sparsity="2:4": every Linear converts to 2:4 structured-sparse 8-bit weights, every other layer as
-        before; any value but None or "2:4", or weight_bits=4 with it, is a ValueError."""
+        before; any value but None or "2:4", or weight_bits=4 with it, is a ValueError.  group_size=64, 128 or 256 (with
+        weight_bits=4 and no sparsity; anything else is a ValueError): every Linear gets group-wise 4-bit scales along
+        in_features (Layer.convert), every other layer converts as before."""
         if weight_bits not in (4, 8) or isinstance(weight_bits, bool):
             raise ValueError("convert: weight_bits must be 4 or 8, got %r" % (weight_bits,))
         if sparsity is not None and (not isinstance(sparsity, str) or sparsity != "2:4" or weight_bits == 4):
             raise ValueError("convert: sparsity must be None or \"2:4\" (with weight_bits=8), got %r" % (sparsity,))
+        if group_size is not None and (isinstance(group_size, bool) or group_size not in (64, 128, 256) or weight_bits != 4):
+            raise ValueError("convert: group_size must be None or 64, 128, 256 (with weight_bits=4), got %r" % (group_size,))
         for _, layer in self._layers():
             linear = isinstance(layer, Linear)
-            layer.convert(per_channel, weight_bits if linear else 8, sparsity if linear else None)
+            layer.convert(per_channel, weight_bits if linear else 8, sparsity if linear else None, group_size if linear else None)
         self.is_quant = True
 
     # ---- additive: save / restore the converted (INT8) model ------------------
@@ -108,6 +112,9 @@ class Module:
                 continue
             if layer.weight_bits() == 4:  # uint8 [out, ceil(in / 2)]: element 2i in the low nibble of byte i (i8ie_pack_w4)
                 out[name + ".q_weight4"] = L._q_weight4()
+                if layer.group_size() is not None:  # uint8 [out, ceil(in / group_size)] multipliers and int32 [1] (i8ie_linear_create_w4g)
+                    out[name + ".q_group_scales"] = L._group_scales()
+                    out[name + ".group_size"] = np.array([layer.group_size()], np.int32)
             elif layer.sparsity() == "2:4":  # int8 [out, K4 / 2] and uint8 [out, K4 / 8], one nibble per group (i8ie_pack_2_4)
                 out[name + ".q_weight24"], out[name + ".q_index24"] = L._q_weight24()
             else:
@@ -154,8 +161,15 @@ class Module:
                 if not isinstance(layer, Linear):
                     raise RuntimeError("i8ie: load_quantized: %r carries 4-bit weights (.q_weight4), which only a Linear takes; "
                                        "the layer is a %s" % (name, type(layer).__name__))
-                layer.layer._load_quantized_w4(np.asarray(state[name + ".q_weight4"], np.uint8), np.asarray(state[name + ".q_bias"], np.int8),
-                                               np.ascontiguousarray(state[name + ".w_scales"], np.float32), float(np.float32(s_out)), int(zp_out))
+                rest = (np.asarray(state[name + ".q_bias"], np.int8), np.ascontiguousarray(state[name + ".w_scales"], np.float32),
+                        float(np.float32(s_out)), int(zp_out))
+                if (name + ".q_group_scales" in state) != (name + ".group_size" in state):
+                    raise ValueError("i8ie: load_quantized: %r needs both .q_group_scales and .group_size, or neither" % name)
+                if name + ".group_size" in state:  # ... with group-wise scales
+                    layer.layer._load_quantized_w4g(np.asarray(state[name + ".q_weight4"], np.uint8), np.asarray(state[name + ".q_group_scales"], np.uint8),
+                                                    int(np.asarray(state[name + ".group_size"]).reshape(-1)[0]), *rest)
+                else:
+                    layer.layer._load_quantized_w4(np.asarray(state[name + ".q_weight4"], np.uint8), *rest)
                 continue
             if name + ".w_scales" in state:  # per-channel layer
                 w_scale = np.ascontiguousarray(state[name + ".w_scales"], np.float32)
