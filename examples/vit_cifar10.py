@@ -93,6 +93,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--batches", type=int, nargs="+", default=[1000, 125])
     ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--weight-bits", type=int, choices=(4, 8), default=8,
+                    help="4: qkv, proj and both MLP layers (pointwise convs) and the head as packed 4-bit weights")
     args = ap.parse_args()
 
     import torch  # noqa: F401  (one HIP runtime per process: torch first)
@@ -120,8 +122,11 @@ def main():
     fp32 = evaluate("FP32")
     model.prepare()
     model(xs[min(xs)])
-    model.convert()
-    int8 = evaluate("INT8")
+    if args.weight_bits == 4:
+        model.convert(weight_bits=4, pointwise=True)
+    else:
+        model.convert()
+    int8 = evaluate("W4A8" if args.weight_bits == 4 else "INT8")
     for m, x in xs.items():
         cx.profile_start()
         for _ in range(args.steps):

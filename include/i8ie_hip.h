@@ -547,7 +547,7 @@ int i8ie_unpack_w4(const uint8_t* packed_host, int rows, int k, int8_t* qw_host)
  * registers); w4lin_direct otherwise.  i8ie_layer_forward_dequant needs out_u8 and runs the dequantize kernel behind it. */
 int i8ie_linear_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int n,
                           int k, i8ie_layer** out);
-/* *bits = 4 for a layer of i8ie_linear_create_w4, 8 for every other layer */
+/* *bits = 4 for a layer of i8ie_linear_create_w4 (or _w4g, or i8ie_conv2d_create_w4), 8 for every other layer */
 int i8ie_layer_weight_bits(const i8ie_layer* layer, int* bits);
 /* Stateless form (for tests): in_dev [m, k] u8 -> out_dev [m, n] u8 through a temporary handle made from the host weights;
  * the offset vector is computed inside (src/fully_connected.cc:30-38).  acc_dbg_dev: NULL, or int32 [m, n] receiving C BEFORE
@@ -629,6 +629,28 @@ int i8ie_layer_group_size(const i8ie_layer* layer, int* group_size);
 int i8ie_linear_u8s4g(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const uint8_t* packed_host, const uint8_t* m_host,
                       const int8_t* qb_host, const float* s_w_host, int n, int group_size, float s_in, uint8_t zp_in,
                       float s_out, uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
+
+/* ---- 4-bit weights for pointwise Conv2d (W4A8; not in the reference) ----------------------------------
+ * A 4-bit pointwise conv is the per-channel INT8 Conv2d of i8ie_conv2d_create_per_channel with kh = kw = 1, stride 1, pad 0
+ * whose weight integers lie in [-8, 7]: the exact INT32 sum, the offset vector with the bias folded in (src/conv2d.cc:117-124)
+ * and down_scale per column are unchanged.  The quantiser is i8ie_quantize_weight_w4 on the [kc, c] view of the [kc, c, 1, 1]
+ * weight and the stored form i8ie_pack_w4's rows.
+ * A Conv2d [kc, c, 1, 1] from packed rows (any nibble in [-8, 7]), s8 biases and one finite scale >= 0 per output feature, all
+ * host pointers; c <= 65536.  The handle keeps the nibble panel of csrc/i8ie_w4lin.hip plus the per-feature vectors: no
+ * unpacked copy of the weights exists on the device.  i8ie_layer_weight_bits answers 4.  i8ie_layer_forward,
+ * i8ie_layer_forward_fused and i8ie_layer_forward_pool (the pool as a launch of its own) take the handle like any Conv2d's, in
+ * NCHW, NHWC with any border and the re-biased NHWC form at either end; i8ie_layer_padding answers 0 and
+ * i8ie_layer_rebiased_io 1 / 1.  Kernels: w4pw_mfma when c % 32 == 0, both ends are NHWC, the input is 16-byte aligned and
+ * I8IE_OPT_FORCE_FALLBACK is off (any pixel count, any kc, one launch, relu, border and re-bias folded); w4pw_direct
+ * otherwise.  Both give the bytes (and acc_dbg the sums) of i8ie_conv2d_u8s8 with down_scale per column on the unpacked
+ * integers. */
+int i8ie_conv2d_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int kc, int c,
+                          i8ie_layer** out);
+/* Stateless form (for tests): in_dev NCHW [n, c, h, w] u8 -> out_dev NCHW [n, kc, h, w] u8 through a temporary handle made from
+ * the host weights; the offset vector is computed inside.  acc_dbg_dev: NULL, or int32 [n, h*w, kc] as i8ie_conv2d_u8s8 gives it. */
+int i8ie_conv2d_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w, const uint8_t* packed_host,
+                     const int8_t* qb_host, const float* s_w_host, int kc, float s_in, uint8_t zp_in, float s_out,
+                     uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
 /* the layer's output (scale_, zero_point_): src/layer.cc:44, include/layer.h:46-47 (default 1, 0) */
 int i8ie_layer_set_output_qparams(i8ie_layer* layer, float s_out, uint8_t zp_out);
 int i8ie_layer_get_output_qparams(const i8ie_layer* layer, float* s_out, uint8_t* zp_out);

@@ -32,37 +32,16 @@ class Linear : public BaseLayer {
     return forward_acc(in, {m, n}, {m, n}, (int)m, 0, 0);
   }
 
-  // ---- 4-bit weights (include/i8ie_hip.h, "4-bit weights for Linear"): the layer keeps the packed rows qw4_ [out, ceil(in / 2)]
-  //      on the host (qw_ stays empty) and is per-channel in every other respect
+  // ---- 4-bit weights (include/i8ie_hip.h, "4-bit weights for Linear"; the shared steps: BaseLayer)
   void convert_w4() {
     if (!convert_qparams()) return;
     check_shapes();
-    const ssize_t n = wshape_[0], k = wshape_[1];
-    std::vector<s8_t> q(w_.size());
-    qb_.resize(b_.size());
-    w_scales_.assign((size_t)n, 0.0f);
-    check(i8ie_quantize_weight_w4(w_.data(), (int)n, (int64_t)k, b_.data(), reinterpret_cast<int8_t*>(q.data()),
-                                  reinterpret_cast<int8_t*>(qb_.data()), w_scales_.data()));
-    qw4_.assign((size_t)(n * ((k + 1) / 2)), 0);
-    check(i8ie_pack_w4(reinterpret_cast<const int8_t*>(q.data()), (int)n, (int)k, qw4_.data()));
+    quantize_pack_w4();
     drop_groups();
     install_w4();
   }
-  void load_quantized_w4(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> packed, S8Array qb, F32Array scales,
-                         float s_out, int zp_out) {
-    check_zero_point(zp_out);
-    const ssize_t n = wshape_[0], k = wshape_[1];
-    if (packed.ndim() != 2 || packed.shape(0) != n || packed.shape(1) != (k + 1) / 2)
-      throw std::runtime_error("i8ie: Linear: load_quantized: q_weight4 must be uint8 [out_features, ceil(in_features / 2)]");
-    if (qb.size() != n) throw std::runtime_error("i8ie: load_quantized: bias size mismatch");
-    if (scales.ndim() != 1 || scales.size() != n)
-      throw std::runtime_error("i8ie: load_quantized: weight_scale array must hold one scale per output feature");
-    qw4_.assign(packed.data(), packed.data() + packed.size());
-    qb_.assign(qb.data(), qb.data() + qb.size());
-    w_scales_.assign(scales.data(), scales.data() + scales.size());
-    scale_ = s_out;
-    zero_point_ = (u8_t)zp_out;
-    qparams_overridden_ = true;
+  void load_quantized_w4(U8Array packed, S8Array qb, F32Array scales, float s_out, int zp_out) {
+    take_w4("Linear", packed, qb, scales, s_out, zp_out);
     drop_groups();
     install_w4();
   }
@@ -122,21 +101,6 @@ class Linear : public BaseLayer {
     if (group_size() == 0) throw std::runtime_error("i8ie: group_scales: the layer has no group-wise scales");
     py::array_t<uint8_t> a(std::vector<ssize_t>{wshape_[0], (wshape_[1] + gsize_ - 1) / gsize_});
     std::memcpy(a.mutable_data(), qm_.data(), qm_.size());
-    return a;
-  }
-  int weight_bits() const { return qw4_.empty() ? 8 : 4; }
-  py::array_t<uint8_t> q_weight4() const {
-    need_quantized();
-    if (qw4_.empty()) throw std::runtime_error("i8ie: q_weight4: the layer holds 8-bit weights (use q_weight())");
-    py::array_t<uint8_t> a(std::vector<ssize_t>{wshape_[0], (wshape_[1] + 1) / 2});
-    std::memcpy(a.mutable_data(), qw4_.data(), qw4_.size());
-    return a;
-  }
-  py::array_t<s8_t> q_weight() const {  // (a 4-bit layer unpacks on the host)
-    if (qw4_.empty()) return BaseLayer::q_weight();
-    need_quantized();
-    py::array_t<s8_t> a(wshape_);
-    check(i8ie_unpack_w4(qw4_.data(), (int)wshape_[0], (int)wshape_[1], reinterpret_cast<int8_t*>(a.mutable_data())));
     return a;
   }
   void load_quantized(S8Array qw, S8Array qb, py::object w_scale, float s_out, int zp_out) {
@@ -217,44 +181,16 @@ class Linear : public BaseLayer {
       throw py::value_error(std::string("i8ie: ") + i8ie_last_error());
   }
   bool sp24_ = false, prune_ = false, made_ = false;
-  // An 8-bit convert / load on a layer that may hold 4-bit weights: make_handle must not see qw4_ while the base call runs, and
-  // the packed rows go only once that call has installed 8-bit weights.  A call that leaves the layer as it was -- convert() on a
-  // converted layer returns early, a refused argument throws -- keeps the 4-bit state that the live handle still computes with.
-  template <class F>
-  void replacing_w4(F&& base_call) {
-    std::vector<uint8_t> keep4;
-    keep4.swap(qw4_);
-    const std::vector<ssize_t> shape = wshape_;
-    const std::vector<s8_t> qb = qb_;
-    const std::vector<float> scales = w_scales_;
-    try {
-      base_call();
-    } catch (...) {
-      if (!keep4.empty()) {
-        qw4_.swap(keep4);
-        wshape_ = shape; qb_ = qb; w_scales_ = scales; per_channel_ = true; w_scale_ = 1;
-        std::vector<s8_t>().swap(qw_);
-      }
-      throw;
-    }
-    if (qw_.empty()) qw4_.swap(keep4);
-    if (qw4_.empty()) drop_groups();
-  }
+  void w4_dropped() override { drop_groups(); }
   void drop_groups() {
     gsize_ = 0;
     std::vector<uint8_t>().swap(qm_);
-  }
-  void install_w4() {
-    std::vector<s8_t>().swap(qw_);
-    per_channel_ = true;
-    w_scale_ = 1;
-    install_handle();
   }
   void check_shapes() const override {
     if (wshape_.size() != 2) throw std::runtime_error("i8ie: Linear weight must be [out_features, in_features]");
     if (has_fp32_ && (ssize_t)b_.size() != wshape_[0]) throw std::runtime_error("i8ie: Linear bias size mismatch");
   }
-  std::vector<uint8_t> qw4_, qm_;  // qm_, gsize_: the group multipliers and size of a grouped 4-bit layer (gsize_ 0: one scale per row)
+  std::vector<uint8_t> qm_;  // qm_, gsize_: the group multipliers and size of a grouped 4-bit layer (gsize_ 0: one scale per row)
   int gsize_ = 0;
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
@@ -350,7 +286,34 @@ class Conv2d : public BaseLayer {
     return forward_spatial_u8(in, out_shape(in.shape), want_acc);
   }
 
+  // ---- 4-bit weights of a pointwise layer (include/i8ie_hip.h, "4-bit weights for pointwise Conv2d"; the shared steps: BaseLayer):
+  //      i8ie.Layer.convert and Module.load_quantized check that the layer is pointwise before they call these
+  void convert_w4() {
+    need_pointwise();
+    if (!convert_qparams()) return;
+    check_shapes();
+    quantize_pack_w4();
+    install_w4();
+  }
+  void load_quantized_w4(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> packed, S8Array qb, F32Array scales,
+                         float s_out, int zp_out) {
+    need_pointwise();
+    take_w4("Conv2d", packed, qb, scales, s_out, zp_out);
+    install_w4();
+  }
+  void load_quantized(S8Array qw, S8Array qb, py::object w_scale, float s_out, int zp_out) {
+    replacing_w4([&] { BaseLayer::load_quantized(qw, qb, w_scale, s_out, zp_out); });
+  }
+  void convert(bool per_channel = false) {
+    replacing_w4([&] { BaseLayer::convert(per_channel); });
+  }
+
  protected:
+  void need_pointwise() const {
+    if (wshape_.size() != 4 || wshape_[2] != 1 || wshape_[3] != 1 || stride_ != 1 || stride_w_ != 1 || padding_ != 0 || padding_w_ != 0 ||
+        groups_ != 1)
+      throw py::value_error("i8ie: Conv2d: 4-bit weights need a pointwise layer (kernel 1 x 1, stride 1, padding 0, groups 1)");
+  }
   void check_shapes() const override {
     if (wshape_.size() != 4) throw std::runtime_error("i8ie: Conv2d weight must be [out, in, kh, kw]");
     if (has_fp32_ && (ssize_t)b_.size() != wshape_[0]) throw std::runtime_error("i8ie: Conv2d bias size mismatch");
@@ -362,6 +325,11 @@ class Conv2d : public BaseLayer {
   }
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
+    if (!qw4_.empty()) {  // (pointwise: any dilation is the undilated layer)
+      check(i8ie_conv2d_create_w4(ctx(), qw4_.data(), reinterpret_cast<const int8_t*>(qb_.data()), w_scales_.data(), (int)n,
+                                  (int)in_channels(), &l));
+      return l;
+    }
     if (!square()) {  // (equal pairs take the entries below: constructed exactly as a layer of ints is)
       const i8ie_conv_geom g = geom();
       if (per_channel_)
@@ -555,6 +523,17 @@ class ConvTranspose2d : public BaseLayer {
   std::vector<float> wt_;  // the FP32 weight as loaded (torch's layout), for the FP32 kernel
 };
 
+// (private: the classes keep their recorded public surface; i8ie.Layer.convert(weight_bits=4), weight_bits() and the Module's save /
+// load reach the 4-bit form through these)
+template <typename L>
+void bind_w4(py::class_<L>& c) {
+  c.def("_convert_w4", &L::convert_w4)
+      .def("_load_quantized_w4", &L::load_quantized_w4, py::arg("q_weight4"), py::arg("q_bias"), py::arg("weight_scales"),
+           py::arg("out_scale"), py::arg("out_zero_point"))
+      .def("_weight_bits", &L::weight_bits)
+      .def("_q_weight4", &L::q_weight4);
+}
+
 template <typename L>
 void bind_layer_common(py::class_<L>& c) {
   c.def("load_weight", &L::load_weight)
@@ -583,14 +562,8 @@ void bind_layers(py::module_& m) {
         .def(py::init([](Tensor<float>& w, Tensor<float>& b) { return new Linear(w.numpy(), b.numpy()); }))
         .def(py::init<ssize_t, ssize_t>());
     bind_layer_common(c);
-    // (private: the class keeps its recorded public surface; i8ie.Layer.convert(weight_bits=4), weight_bits() and the Module's save /
-    // load reach the 4-bit form through these)
-    c.def("_convert_w4", &Linear::convert_w4)
-        .def("_load_quantized_w4", &Linear::load_quantized_w4, py::arg("q_weight4"), py::arg("q_bias"), py::arg("weight_scales"),
-             py::arg("out_scale"), py::arg("out_zero_point"))
-        .def("_weight_bits", &Linear::weight_bits)
-        .def("_q_weight4", &Linear::q_weight4)
-        .def("_convert_w4g", &Linear::convert_w4g, py::arg("group_size"))
+    bind_w4(c);
+    c.def("_convert_w4g", &Linear::convert_w4g, py::arg("group_size"))
         .def("_load_quantized_w4g", &Linear::load_quantized_w4g, py::arg("q_weight4"), py::arg("q_group_scales"), py::arg("group_size"),
              py::arg("q_bias"), py::arg("weight_scales"), py::arg("out_scale"), py::arg("out_zero_point"))
         .def("_group_size", &Linear::group_size)
@@ -614,6 +587,7 @@ void bind_layers(py::module_& m) {
         .def("dilation", &Conv2d::dilation)
         .def("_geometry", &Conv2d::geometry);  // (private: the class keeps its recorded public surface; i8ie.Layer.geometry() asks it)
     bind_layer_common(c);
+    bind_w4(c);
   }
 
   {
@@ -629,6 +603,7 @@ void bind_layers(py::module_& m) {
         })
         .def("geometry", &Conv2dRect::geometry);
     bind_layer_common(c);
+    bind_w4(c);
   }
   {
     py::class_<ConvTranspose2d> c(m, "ConvTranspose2d");

@@ -90,10 +90,23 @@ class BaseLayer : public QuantState {
     qparams_overridden_ = true;
     install_handle();
   }
-  py::array_t<s8_t> q_weight() const {
+  py::array_t<s8_t> q_weight() const {  // (a 4-bit layer unpacks on the host)
     need_quantized();
     py::array_t<s8_t> a(wshape_);
-    std::memcpy(a.mutable_data(), qw_.data(), qw_.size());
+    if (qw4_.empty())
+      std::memcpy(a.mutable_data(), qw_.data(), qw_.size());
+    else
+      check(i8ie_unpack_w4(qw4_.data(), (int)wshape_[0], (int)row_len(), reinterpret_cast<int8_t*>(a.mutable_data())));
+    return a;
+  }
+  // ---- 4-bit weights (Linear, and a pointwise Conv2d): the layer keeps the packed rows qw4_ [out, ceil(in / 2)] on the host (qw_
+  //      stays empty) and is per-channel in every other respect
+  int weight_bits() const { return qw4_.empty() ? 8 : 4; }
+  py::array_t<uint8_t> q_weight4() const {
+    need_quantized();
+    if (qw4_.empty()) throw std::runtime_error("i8ie: q_weight4: the layer holds 8-bit weights (use q_weight())");
+    py::array_t<uint8_t> a(std::vector<ssize_t>{wshape_[0], (row_len() + 1) / 2});
+    std::memcpy(a.mutable_data(), qw4_.data(), qw4_.size());
     return a;
   }
   py::array_t<s8_t> q_bias() const {
@@ -143,6 +156,65 @@ class BaseLayer : public QuantState {
     has_fp32_ = false;
     release_fp32_dev();
   }
+  ssize_t row_len() const { return (ssize_t)wshape_.size() < 2 ? 1 : wshape_[1] * (wshape_.size() > 2 ? wshape_[2] * wshape_[3] : 1); }
+  // i8ie_quantize_weight_w4 + i8ie_pack_w4 of the FP32 weights [out, row_len] into qw4_ / qb_ / w_scales_
+  void quantize_pack_w4() {
+    const ssize_t n = wshape_[0], k = row_len();
+    std::vector<s8_t> q(w_.size());
+    qb_.resize(b_.size());
+    w_scales_.assign((size_t)n, 0.0f);
+    check(i8ie_quantize_weight_w4(w_.data(), (int)n, (int64_t)k, b_.data(), reinterpret_cast<int8_t*>(q.data()),
+                                  reinterpret_cast<int8_t*>(qb_.data()), w_scales_.data()));
+    qw4_.assign((size_t)(n * ((k + 1) / 2)), 0);
+    check(i8ie_pack_w4(reinterpret_cast<const int8_t*>(q.data()), (int)n, (int)k, qw4_.data()));
+  }
+  // saved packed rows, biases and scales into the layer (`who`: the class, for the error text)
+  void take_w4(const char* who, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> packed, S8Array qb, F32Array scales,
+               float s_out, int zp_out) {
+    check_zero_point(zp_out);
+    const ssize_t n = wshape_[0], k = row_len();
+    if (packed.ndim() != 2 || packed.shape(0) != n || packed.shape(1) != (k + 1) / 2)
+      throw std::runtime_error(std::string("i8ie: ") + who + ": load_quantized: q_weight4 must be uint8 [out_features, ceil(in_features / 2)]");
+    if (qb.size() != n) throw std::runtime_error("i8ie: load_quantized: bias size mismatch");
+    if (scales.ndim() != 1 || scales.size() != n)
+      throw std::runtime_error("i8ie: load_quantized: weight_scale array must hold one scale per output feature");
+    qw4_.assign(packed.data(), packed.data() + packed.size());
+    qb_.assign(qb.data(), qb.data() + qb.size());
+    w_scales_.assign(scales.data(), scales.data() + scales.size());
+    scale_ = s_out;
+    zero_point_ = (u8_t)zp_out;
+    qparams_overridden_ = true;
+  }
+  void install_w4() {
+    std::vector<s8_t>().swap(qw_);
+    per_channel_ = true;
+    w_scale_ = 1;
+    install_handle();
+  }
+  // An 8-bit convert / load on a layer that may hold 4-bit weights: make_handle must not see qw4_ while the base call runs, and
+  // the packed rows go only once that call has installed 8-bit weights.  A call that leaves the layer as it was -- convert() on a
+  // converted layer returns early, a refused argument throws -- keeps the 4-bit state that the live handle still computes with.
+  template <class F>
+  void replacing_w4(F&& base_call) {
+    std::vector<uint8_t> keep4;
+    keep4.swap(qw4_);
+    const std::vector<ssize_t> shape = wshape_;
+    const std::vector<s8_t> qb = qb_;
+    const std::vector<float> scales = w_scales_;
+    try {
+      base_call();
+    } catch (...) {
+      if (!keep4.empty()) {
+        qw4_.swap(keep4);
+        wshape_ = shape; qb_ = qb; w_scales_ = scales; per_channel_ = true; w_scale_ = 1;
+        std::vector<s8_t>().swap(qw_);
+      }
+      throw;
+    }
+    if (qw_.empty()) qw4_.swap(keep4);
+    if (qw4_.empty()) w4_dropped();
+  }
+  virtual void w4_dropped() {}  // (what a class keeps beside the packed rows goes with them)
   virtual void check_shapes() const = 0;
   // a layer that was given its channel counts refuses a weight of another shape (Conv2d with groups: [out, in/groups, k, k])
   virtual void check_weight_shape(const std::vector<ssize_t>&, const char*) const {}
@@ -302,6 +374,7 @@ class BaseLayer : public QuantState {
   float* w_dev_ = nullptr;
   float* b_dev_ = nullptr;
   std::vector<s8_t> qw_, qb_;
+  std::vector<uint8_t> qw4_;  // the packed rows of a 4-bit layer
   float w_scale_ = 1;
   bool per_channel_ = false;
   std::vector<float> w_scales_;  // per-channel layers: s_w[j]

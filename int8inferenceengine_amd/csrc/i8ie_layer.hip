@@ -33,6 +33,7 @@
 #include "i8ie_w4lin.h"
 #include "i8ie_sp24lin.h"
 #include "i8ie_w4glin.h"
+#include "i8ie_w4pw.h"
 
 // ---- v1 (fallback) runners ------------------------------------------------------------------
 int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, const int8_t* Bpack, const int32_t* oc,
@@ -102,7 +103,7 @@ int ensure_offsets(i8ie_layer* L, float s_in, uint8_t zp_in) {
   if (L->gsize != 0) {  // from the nibbles and the group multipliers, in one launch
     I8IE_TRY(i8ie_w4g_launch_offsets(ctx, L->w4, L->w4m, L->qb, L->n, L->K, L->gsize, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
   } else if (L->wbits == 4) {  // the same vectors from the nibbles, in one launch
-    I8IE_TRY(i8ie_w4_launch_offsets(ctx, L->w4, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
+    I8IE_TRY(i8ie_w4_launch_offsets(ctx, L->w4, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf, L->conv));
   } else if (L->sp24 != nullptr) {  // ... and from the compressed 2:4 panel
     I8IE_TRY(i8ie_sp24_launch_offsets(ctx, L->sp24, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
   } else {
@@ -254,6 +255,7 @@ struct ConvPlan { bool stem = false, pconv = false; };
 static ConvPlan conv_plan(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
   ConvPlan p;
   i8ie_ctx* ctx = L->ctx;
+  if (L->wbits == 4) return p;  // (a 4-bit pointwise conv has its own route, which folds the re-biased layouts itself)
   if (!L->conv || force_fallback(ctx) || !(q.acc == nullptr || aligned16(q.acc))) return p;
   if (L->path == PATH_B)
     p.stem = L->Bstem != nullptr && !ctx->pick.no_stem &&
@@ -527,7 +529,28 @@ static int peel_pool(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
   return rc;
 }
 
+// ---- a pointwise Conv2d with 4-bit weights (i8ie_conv2d_create_w4): the two kernels of i8ie_w4pw.hip and
+// nothing else.  Both read and write NCHW, NHWC with any border and the re-biased form, so nothing is staged, peeled or converted.
+static int forward_pointwise_w4(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  I8IE_REQUIRE(q.x == nullptr, "a 4-bit pointwise conv takes u8 input");
+  I8ieW4pwCall c{};
+  c.A = q.in; c.m = q.m; c.H = cg.h; c.W = cg.w; c.C = cg.c; c.ib = q.in_border;
+  c.in_nchw = q.in_nchw() ? 1 : 0; c.in_s8 = q.in_s8() ? 1 : 0;
+  c.N = L->n; c.B = L->w4; c.ep = layer_epilogue(L, q);
+  c.out = q.out; c.ob = q.out_border; c.out_nchw = q.out_nchw() ? 1 : 0; c.out_s8 = q.out_s8() ? 1 : 0;
+  if (force_fallback(ctx) || !i8ie_w4pw_mfma_takes(c)) {
+    c.ep.ocp = L->oc;  // (the definition reads the activations as they are)
+    return i8ie_w4pw_direct_launch(ctx, c);
+  }
+  return i8ie_w4pw_mfma_launch(ctx, c);
+}
+
 static int forward_conv(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  if (L->wbits == 4) {  // (a pool, and a re-biased store behind a pool, run as launches of their own)
+    if (!q.pool()) return forward_pointwise_w4(L, cg, q);
+    return q.out_s8() ? peel_rebiased_output(L, cg, q) : peel_pool(L, cg, q);
+  }
   const ConvPlan plan = conv_plan(L, cg, q);
   if (q.in_s8() && !plan.pconv) return peel_rebiased_input(L, cg, q);
   if (q.out_s8() && !plan.pconv && !plan.stem) return peel_rebiased_output(L, cg, q);
@@ -811,6 +834,11 @@ int i8ie_layer_rebiased_io(const i8ie_layer* L, int m, int h, int w, int pool_k,
   ConvPlan in, out;
   ConvGeom cg;
   if (!L->conv || L->path == PATH_T || m < 1) return I8IE_OK;
+  if (L->wbits == 4) {  // (both kernels of i8ie_w4pw.hip read and store re-biased bytes; a pool runs behind a plain result)
+    *reads = 1;
+    *stores = i8ie_is_pool(pool_k, pool_s) ? 0 : 1;
+    return I8IE_OK;
+  }
   if (!query_plan(L, m, h, w, pool_k, pool_s, I8IE_LAYOUT_NHWC_S8, I8IE_LAYOUT_NHWC, &in, &cg) ||
       !query_plan(L, m, h, w, pool_k, pool_s, I8IE_LAYOUT_NHWC, I8IE_LAYOUT_NHWC_S8, &out, &cg))
     return I8IE_OK;

@@ -369,16 +369,21 @@ int i8ie_linear_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const i
 // A Linear with 4-bit weights: the packed rows go into the nibble panel of i8ie_w4lin.h on the host, and the
 // handle holds that panel and the per-feature vectors -- not layer_build's qw / Bpack, so no unpacked copy reaches the device.
 // wsum / oc / oc' / the float bias come from the panel per (s_in, zp_in), in one launch of the first forward (ensure_offsets).
-int i8ie_linear_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int n, int k,
-                          i8ie_layer** out) {
-  I8IE_REQUIRE(ctx && packed_host && qb_host && out, "null argument");
-  I8IE_REQUIRE(n > 0 && k > 0, "non-positive dimension");
-  I8IE_REQUIRE(k <= 65536, "4-bit Linear: at most 65536 input features (16 C must stay inside int32)");
+// (conv: the pointwise Conv2d [n, k, 1, 1] of DESIGN.md section 8zb -- the same handle with the conv geometry of a 1 x 1 layer)
+static int w4_create(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int n, int k, bool conv,
+                     i8ie_layer** out) {
+  const char* who = conv ? "i8ie_conv2d_create_w4" : "i8ie_linear_create_w4";
+  REQUIRE_AS(who, ctx && packed_host && qb_host && out, "null argument");
+  REQUIRE_AS(who, n > 0 && k > 0, "non-positive dimension");
+  REQUIRE_AS(who, k <= 65536, "4-bit Linear: at most 65536 input features (16 C must stay inside int32)");
   I8IE_TRY(check_scales(s_w_host, n));
   I8IE_HIP_TRY(hipSetDevice(ctx->device));
   i8ie_layer* L = new (std::nothrow) i8ie_layer();
   if (!L) return I8IE_ERR_OOM;
   L->ctx = ctx; L->n = n; L->K = k; L->wbits = 4;
+  if (conv) {
+    L->conv = true; L->c = k; L->kh = L->kw = 1; L->path = PATH_A;
+  }
   L->Kpad = round_up(k, 128);
   L->Npad = round_up(n, 128);
   std::vector<uint8_t> panel(i8ie_w4_panel_bytes(n, k), 0);
@@ -397,6 +402,16 @@ int i8ie_linear_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_
   }
   *out = L;
   return I8IE_OK;
+}
+
+int i8ie_linear_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int n, int k,
+                          i8ie_layer** out) {
+  return w4_create(ctx, packed_host, qb_host, s_w_host, n, k, false, out);
+}
+
+int i8ie_conv2d_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int kc, int c,
+                          i8ie_layer** out) {
+  return w4_create(ctx, packed_host, qb_host, s_w_host, kc, c, true, out);
 }
 
 int i8ie_layer_weight_bits(const i8ie_layer* L, int* bits) {
@@ -956,6 +971,20 @@ int i8ie_linear_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const u
 }
 
 // ... and with group scales
+int i8ie_conv2d_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w, const uint8_t* packed_host,
+                     const int8_t* qb_host, const float* s_w_host, int kc, float s_in, uint8_t zp_in, float s_out, uint8_t zp_out,
+                     uint8_t* out_dev, int32_t* acc_dbg_dev) {
+  I8IE_REQUIRE(ctx && in_dev && out_dev, "null argument");
+  I8IE_REQUIRE(n > 0, "non-positive batch");
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_conv2d_create_w4(ctx, packed_host, qb_host, s_w_host, kc, c, &L));
+  L->s_out = s_out;
+  L->zp_out = zp_out;
+  const int rc = i8ie_layer_forward(L, in_dev, n, h, w, s_in, zp_in, out_dev, acc_dbg_dev);
+  i8ie_layer_destroy(L);
+  return rc;
+}
+
 int i8ie_linear_u8s4g(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, const uint8_t* packed_host, const uint8_t* m_host,
                       const int8_t* qb_host, const float* s_w_host, int n, int group_size, float s_in, uint8_t zp_in, float s_out,
                       uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev) {

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void w4lin_direct_kernel(W4DirectArgs p) {
 __global__ __launch_bounds__(64) void w4_offsets_kernel(const uint8_t* __restrict__ B, const int8_t* __restrict__ qb, int n, int K,
                                                         int nch, float s_in, int zp_in, int32_t* __restrict__ oc,
                                                         int32_t* __restrict__ wsum, int32_t* __restrict__ ocp,
-                                                        float* __restrict__ biasf) {
+                                                        float* __restrict__ biasf, int conv) {
   const int j = blockIdx.x * 64 + threadIdx.x;
   if (j >= n) return;
   float t = 0.0f;
@@ -204,10 +204,10 @@ __global__ __launch_bounds__(64) void w4_offsets_kernel(const uint8_t* __restric
     t = t + (float)(zp_in * q);
     s += q;
   }
-  oc[j] = (int)(-t);
+  oc[j] = conv ? (int)((float)qb[j] / s_in - t) : (int)(-t);  // src/conv2d.cc:123 / src/fully_connected.cc:37
   wsum[j] = s;
   ocp[j] = oc[j] + 128 * s;
-  biasf[j] = (float)qb[j] / s_in;
+  biasf[j] = conv ? 0.0f : (float)qb[j] / s_in;
 }
 
 // the panel with K reordered (h, w, c): weight k = ch * hw + pix goes where k' = pix * c + ch lies.  One thread per byte of
@@ -300,9 +300,10 @@ int i8ie_w4lin_direct_launch(i8ie_ctx* ctx, const I8ieW4Call& c) {
 }
 
 int i8ie_w4_launch_offsets(i8ie_ctx* ctx, const uint8_t* panel, const int8_t* qb, int n, int K, float s_in, int zp_in,
-                           int32_t* oc, int32_t* wsum, int32_t* ocp, float* biasf) {
+                           int32_t* oc, int32_t* wsum, int32_t* ocp, float* biasf, bool conv) {
   I8ieProfScope prof(ctx, "w4_offsets", 0.0, 0.5 * n * K);
-  w4_offsets_kernel<<<(n + 63) / 64, 64, 0, ctx->stream>>>(panel, qb, n, K, i8ie_w4_chunks(K), s_in, zp_in, oc, wsum, ocp, biasf);
+  w4_offsets_kernel<<<(n + 63) / 64, 64, 0, ctx->stream>>>(panel, qb, n, K, i8ie_w4_chunks(K), s_in, zp_in, oc, wsum, ocp, biasf,
+                                                           conv ? 1 : 0);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }

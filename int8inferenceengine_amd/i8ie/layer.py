@@ -52,9 +52,10 @@ class Layer:
 
         per_channel=True (additive, not the reference's rule): one symmetric max-abs weight scale per output
         feature, rounded to nearest even (include/i8ie_hip.h, i8ie_quantize_weight_per_channel).
-        weight_bits=4 (additive; i8ie.Linear only, ValueError for every other layer class; any value but 4 or 8 is a
-        ValueError): 4-bit weights with one scale per output feature, whatever per_channel says (include/i8ie_hip.h,
-        i8ie_quantize_weight_w4).  The layer is then per-channel in every respect: is_per_channel() is True,
+        weight_bits=4 (additive; i8ie.Linear and a pointwise i8ie.Conv2d -- kernel 1 x 1, stride 1, padding 0, groups 1, any
+        dilation -- only, ValueError for every other layer; any value but 4 or 8 is a ValueError): 4-bit weights with one
+        scale per output feature, whatever per_channel says (include/i8ie_hip.h, i8ie_quantize_weight_w4, on the [out, in]
+        view of a conv's weight).  The layer is then per-channel in every respect: is_per_channel() is True,
         weight_scales() works and weight_scale() raises.
         sparsity="2:4" (additive; i8ie.Linear with weight_bits=8 only, ValueError for every other layer class, with
         weight_bits=4, and for any value but None or "2:4"): quantise as per_channel says, then keep in every aligned group
@@ -91,7 +92,7 @@ class Layer:
             self.layer.load_quantized(q_weight, q_bias, weight_scale, out_scale, out_zero_point)
 
     def weight_bits(self):
-        """4 for a Linear converted or loaded with 4-bit weights, 8 for every other layer."""
+        """4 for a Linear or a pointwise Conv2d converted or loaded with 4-bit weights, 8 for every other layer."""
         ask = getattr(self.layer, "_weight_bits", None)
         return 8 if ask is None else int(ask())
 
@@ -158,12 +159,21 @@ class Layer:
         return Tensor(out), acc
 
 
+def is_pointwise(layer):
+    """an i8ie.Conv2d with kernel 1 x 1, stride 1, padding 0 and groups 1 (any dilation: at k = 1 it is the undilated layer)"""
+    if not isinstance(layer, Conv2d):
+        return False
+    g = layer.geometry()
+    return tuple(g["kernel_size"]) == (1, 1) and tuple(g["stride"]) == (1, 1) and tuple(g["padding"]) == (0, 0) and layer.groups() == 1
+
+
 def check_weight_bits(layer, weight_bits):
-    """weight_bits as convert() takes it: 8, or 4 on a Linear; ValueError otherwise"""
+    """weight_bits as convert() takes it: 8, or 4 on a Linear or a pointwise Conv2d; ValueError otherwise"""
     if weight_bits not in (4, 8) or isinstance(weight_bits, bool):
         raise ValueError("convert: weight_bits must be 4 or 8, got %r" % (weight_bits,))
-    if weight_bits == 4 and not isinstance(layer, Linear):
-        raise ValueError("convert: weight_bits=4 is for i8ie.Linear only, not %s" % type(layer).__name__)
+    if weight_bits == 4 and not (isinstance(layer, Linear) or is_pointwise(layer)):
+        raise ValueError("convert: weight_bits=4 is for i8ie.Linear and a pointwise i8ie.Conv2d (kernel 1 x 1, stride 1, padding 0, "
+                         "groups 1) only, not this %s" % type(layer).__name__)
     return weight_bits
 
 

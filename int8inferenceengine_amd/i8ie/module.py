@@ -1,7 +1,7 @@
 """Module base class (reference i8ie/module.py:6-35)."""
 import _CXX_i8ie as _C
 
-from .layer import Attention, BatchNorm2d, Layer, Linear, Norm, PositionEmbedding, Weightless, fold_batchnorm
+from .layer import Attention, BatchNorm2d, Layer, Linear, Norm, PositionEmbedding, Weightless, fold_batchnorm, is_pointwise
 from .tensor import Tensor
 
 # Hard-coded input quantisation of the reference (i8ie/module.py:20).
@@ -52,10 +52,11 @@ class Module:
         for _, layer in self._layers():
             layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, pointwise=False):
         """per_channel=True: every layer with one weight scale per output feature (Layer.convert).  weight_bits=4: every
         Linear converts to 4-bit weights, every other layer as with 8 under the given per_channel; any value but 4 or 8 is a
-        ValueError.  sparsity="2:4": every Linear converts to 2:4 structured-sparse 8-bit weights, every other layer as
+        ValueError.  pointwise=True (with weight_bits=4 and neither sparsity nor group_size; anything else is a ValueError):
+        every pointwise Conv2d -- kernel 1 x 1, stride 1, padding 0, groups 1 -- converts to 4-bit weights as well.  sparsity="2:4": every Linear converts to 2:4 structured-sparse 8-bit weights, every other layer as
         before; any value but None or "2:4", or weight_bits=4 with it, is a ValueError.  group_size=64, 128 or 256 (with
         weight_bits=4 and no sparsity; anything else is a ValueError): every Linear gets group-wise 4-bit scales along
         in_features (Layer.convert), every other layer converts as before."""
@@ -65,9 +66,12 @@ class Module:
             raise ValueError("convert: sparsity must be None or \"2:4\" (with weight_bits=8), got %r" % (sparsity,))
         if group_size is not None and (isinstance(group_size, bool) or group_size not in (64, 128, 256) or weight_bits != 4):
             raise ValueError("convert: group_size must be None or 64, 128, 256 (with weight_bits=4), got %r" % (group_size,))
+        if pointwise and (weight_bits != 4 or sparsity is not None or group_size is not None):
+            raise ValueError("convert: pointwise=True needs weight_bits=4 and neither sparsity nor group_size")
         for _, layer in self._layers():
             linear = isinstance(layer, Linear)
-            layer.convert(per_channel, weight_bits if linear else 8, sparsity if linear else None, group_size if linear else None)
+            four = linear or (pointwise and is_pointwise(layer))
+            layer.convert(per_channel, weight_bits if four else 8, sparsity if linear else None, group_size if linear else None)
         self.is_quant = True
 
     # ---- additive: save / restore the converted (INT8) model ------------------
@@ -110,7 +114,7 @@ class Module:
                     out[name + ".running_var"] = np.asarray(L.running_var(), np.float32)
                 out[name + ".qparams"] = np.array([0.0, s_out, zp_out], np.float64)
                 continue
-            if layer.weight_bits() == 4:  # uint8 [out, ceil(in / 2)]: element 2i in the low nibble of byte i (i8ie_pack_w4)
+            if layer.weight_bits() == 4:  # uint8 [out, ceil(in / 2)]: element 2i in the low nibble of byte i (i8ie_pack_w4); a conv's too
                 out[name + ".q_weight4"] = L._q_weight4()
                 if layer.group_size() is not None:  # uint8 [out, ceil(in / group_size)] multipliers and int32 [1] (i8ie_linear_create_w4g)
                     out[name + ".q_group_scales"] = L._group_scales()
@@ -157,14 +161,16 @@ class Module:
                 layer.layer.load_quantized(np.asarray(state[name + ".weight"], np.float32), None if bias is None else np.asarray(bias, np.float32),
                                            float(np.float32(s_out)), int(zp_out))
                 continue
-            if name + ".q_weight4" in state:  # 4-bit Linear
-                if not isinstance(layer, Linear):
-                    raise RuntimeError("i8ie: load_quantized: %r carries 4-bit weights (.q_weight4), which only a Linear takes; "
-                                       "the layer is a %s" % (name, type(layer).__name__))
+            if name + ".q_weight4" in state:  # 4-bit Linear or pointwise Conv2d
+                if not (isinstance(layer, Linear) or is_pointwise(layer)):
+                    raise RuntimeError("i8ie: load_quantized: %r carries 4-bit weights (.q_weight4), which only a Linear or a pointwise "
+                                       "Conv2d takes; the layer is a %s" % (name, type(layer).__name__))
                 rest = (np.asarray(state[name + ".q_bias"], np.int8), np.ascontiguousarray(state[name + ".w_scales"], np.float32),
                         float(np.float32(s_out)), int(zp_out))
                 if (name + ".q_group_scales" in state) != (name + ".group_size" in state):
                     raise ValueError("i8ie: load_quantized: %r needs both .q_group_scales and .group_size, or neither" % name)
+                if name + ".group_size" in state and not isinstance(layer, Linear):
+                    raise ValueError("i8ie: load_quantized: %r carries group-wise scales, which only a Linear takes" % name)
                 if name + ".group_size" in state:  # ... with group-wise scales
                     layer.layer._load_quantized_w4g(np.asarray(state[name + ".q_weight4"], np.uint8), np.asarray(state[name + ".q_group_scales"], np.uint8),
                                                     int(np.asarray(state[name + ".group_size"]).reshape(-1)[0]), *rest)
