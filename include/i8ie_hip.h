@@ -651,6 +651,29 @@ int i8ie_conv2d_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_
 int i8ie_conv2d_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w, const uint8_t* packed_host,
                      const int8_t* qb_host, const float* s_w_host, int kc, float s_in, uint8_t zp_in, float s_out,
                      uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
+
+/* ---- 4-bit weights for k x k Conv2d (W4A8; not in the reference) ---------------------------------------
+ * A 4-bit k x k conv is the per-channel INT8 Conv2d of i8ie_conv2d_create_dilated_per_channel with groups 1 and kh = kw = k
+ * whose weight integers lie in [-8, 7]: the exact INT32 sum, the offset vector with the bias folded in (src/conv2d.cc:117-124)
+ * and down_scale per column are unchanged.  The quantiser is i8ie_quantize_weight_w4 on the [kc, c*k*k] view of the weight in
+ * the reference's K order (c, ky, kx), and the stored form i8ie_pack_w4's rows of that view.
+ * packed_host: [kc][ceil(c*k*k / 2)]; c*k*k <= 65536.  The argument rules are i8ie_conv2d_create_dilated's, checked before any
+ * device call.  The handle keeps the nibble panel in the kernel's K order (tap major, channels minor, each tap's channels padded
+ * to 64; repacked on the host) plus the per-feature vectors: no unpacked copy of the weights exists on the device.
+ * k == 1, stride == 1, pad == 0 creates exactly the handle of i8ie_conv2d_create_w4.  i8ie_layer_weight_bits answers 4,
+ * i8ie_layer_padding `pad` (at any dilation), i8ie_layer_rebiased_io 1 / 1 (1 / 0 with a pool), i8ie_layer_fuses_pool and
+ * i8ie_layer_accepts_f32_input 0, i8ie_layer_geometry the numbers given, i8ie_layer_preferred_layout NHWC.  Kernels:
+ * w4conv_mfma when c % 32 == 0, both ends are NHWC, the input is 16-byte aligned and I8IE_OPT_FORCE_FALLBACK is off -- an input
+ * border smaller than `pad` costs one reborder launch into the workspace, a larger one is read in place; w4conv_direct
+ * otherwise.  Both give the bytes (and acc_dbg the sums) of i8ie_conv2d_u8s8 with down_scale per column on the unpacked
+ * integers. */
+int i8ie_conv2d_create_w4_geom(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int kc,
+                               int c, int k, int stride, int pad, int dilation, i8ie_layer** out);
+/* Stateless form (for tests): in_dev NCHW [n, c, h, w] u8 -> out_dev NCHW [n, kc, oh, ow] u8 through a temporary handle made
+ * from the host weights.  acc_dbg_dev: NULL, or int32 [n, oh*ow, kc] as i8ie_conv2d_u8s8 gives it. */
+int i8ie_conv2d_u8s4_geom(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w, const uint8_t* packed_host,
+                          const int8_t* qb_host, const float* s_w_host, int kc, int k, int stride, int pad, int dilation,
+                          float s_in, uint8_t zp_in, float s_out, uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
 /* the layer's output (scale_, zero_point_): src/layer.cc:44, include/layer.h:46-47 (default 1, 0) */
 int i8ie_layer_set_output_qparams(i8ie_layer* layer, float s_out, uint8_t zp_out);
 int i8ie_layer_get_output_qparams(const i8ie_layer* layer, float* s_out, uint8_t* zp_out);

@@ -301,6 +301,22 @@ class Conv2d : public BaseLayer {
     take_w4("Conv2d", packed, qb, scales, s_out, zp_out);
     install_w4();
   }
+  // ... and of a k x k layer (include/i8ie_hip.h, "4-bit weights for k x k Conv2d"): groups 1 and one number per geometry
+  //     argument; the rows are those of the [out, in * k * k] view of the weight.  i8ie.Layer.convert(spatial=True) and
+  //     Module.load_quantized (a '.q_weight4_kernel' key) call these
+  void convert_w4_spatial() {
+    need_spatial();
+    if (!convert_qparams()) return;
+    check_shapes();
+    quantize_pack_w4();
+    install_w4();
+  }
+  void load_quantized_w4_spatial(py::array_t<uint8_t, py::array::c_style | py::array::forcecast> packed, S8Array qb, F32Array scales,
+                                 float s_out, int zp_out) {
+    need_spatial();
+    take_w4("Conv2d", packed, qb, scales, s_out, zp_out);
+    install_w4();
+  }
   void load_quantized(S8Array qw, S8Array qb, py::object w_scale, float s_out, int zp_out) {
     replacing_w4([&] { BaseLayer::load_quantized(qw, qb, w_scale, s_out, zp_out); });
   }
@@ -309,6 +325,12 @@ class Conv2d : public BaseLayer {
   }
 
  protected:
+  void need_spatial() const {
+    if (wshape_.size() != 4 || !square() || groups_ != 1)
+      throw py::value_error("i8ie: Conv2d: 4-bit weights need groups 1 and one number each for kernel, stride, padding and dilation");
+    if (wshape_[1] * wshape_[2] * wshape_[3] > 65536)
+      throw py::value_error("i8ie: Conv2d: 4-bit weights take at most 65536 weights per output feature");
+  }
   void need_pointwise() const {
     if (wshape_.size() != 4 || wshape_[2] != 1 || wshape_[3] != 1 || stride_ != 1 || stride_w_ != 1 || padding_ != 0 || padding_w_ != 0 ||
         groups_ != 1)
@@ -325,9 +347,10 @@ class Conv2d : public BaseLayer {
   }
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
-    if (!qw4_.empty()) {  // (pointwise: any dilation is the undilated layer)
-      check(i8ie_conv2d_create_w4(ctx(), qw4_.data(), reinterpret_cast<const int8_t*>(qb_.data()), w_scales_.data(), (int)n,
-                                  (int)in_channels(), &l));
+    if (!qw4_.empty()) {  // (pointwise: any dilation is the undilated layer; the entry makes i8ie_conv2d_create_w4's handle then)
+      check(i8ie_conv2d_create_w4_geom(ctx(), qw4_.data(), reinterpret_cast<const int8_t*>(qb_.data()), w_scales_.data(), (int)n,
+                                       (int)in_channels(), (int)wshape_[2], (int)stride_, (int)padding_,
+                                       wshape_[2] == 1 ? 1 : (int)dilation_, &l));
       return l;
     }
     if (!square()) {  // (equal pairs take the entries below: constructed exactly as a layer of ints is)
@@ -533,6 +556,13 @@ void bind_w4(py::class_<L>& c) {
       .def("_weight_bits", &L::weight_bits)
       .def("_q_weight4", &L::q_weight4);
 }
+// ... and the k x k steps of Conv2d (a _Conv2dRect is never square)
+template <typename L>
+void bind_w4_spatial(py::class_<L>& c) {
+  c.def("_convert_w4_spatial", &L::convert_w4_spatial)
+      .def("_load_quantized_w4_spatial", &L::load_quantized_w4_spatial, py::arg("q_weight4"), py::arg("q_bias"),
+           py::arg("weight_scales"), py::arg("out_scale"), py::arg("out_zero_point"));
+}
 
 template <typename L>
 void bind_layer_common(py::class_<L>& c) {
@@ -588,6 +618,7 @@ void bind_layers(py::module_& m) {
         .def("_geometry", &Conv2d::geometry);  // (private: the class keeps its recorded public surface; i8ie.Layer.geometry() asks it)
     bind_layer_common(c);
     bind_w4(c);
+    bind_w4_spatial(c);
   }
 
   {

@@ -128,6 +128,7 @@ struct i8ie_layer {
   // the per-feature vectors ([Npad] = [round_up(n, 128)]); qw, Bpack and Bperm stay null -- no unpacked copy of the weights exists on the
   // device.  The panel re-packed for rows in (h, w, c) order lives in `wc`, one buffer per (c, h * w).
   // A pointwise Conv2d of i8ie_conv2d_create_w4 (section 8zb) holds the same and no more: conv = true, kh = kw = 1, PATH_A.
+  // A k x k Conv2d of i8ie_conv2d_create_w4_geom (section 8zc) likewise, with its geometry and the panel in the K order of i8ie_w4conv.h.
   int wbits = 8;
   uint8_t* w4 = nullptr;
   // a Linear of i8ie_linear_create_sp24: the compressed 2:4 panel of i8ie_sp24lin.h, per-tensor or pc, and

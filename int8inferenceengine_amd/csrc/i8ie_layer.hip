@@ -34,6 +34,10 @@
 #include "i8ie_sp24lin.h"
 #include "i8ie_w4glin.h"
 #include "i8ie_w4pw.h"
+#include "i8ie_w4conv.h"
+
+// a 4-bit conv handle of i8ie_conv2d_create_w4 (its kernels: i8ie_w4pw.hip), as against one of i8ie_conv2d_create_w4_geom
+static bool w4_pointwise(const i8ie_layer* L) { return L->kh == 1 && L->kw == 1 && L->stride == 1 && L->pad == 0; }
 
 // ---- v1 (fallback) runners ------------------------------------------------------------------
 int conv_run_v1(i8ie_ctx* ctx, const uint8_t* in, int n, const ConvGeom& cg, const int8_t* Bpack, const int32_t* oc,
@@ -103,7 +107,9 @@ int ensure_offsets(i8ie_layer* L, float s_in, uint8_t zp_in) {
   if (L->gsize != 0) {  // from the nibbles and the group multipliers, in one launch
     I8IE_TRY(i8ie_w4g_launch_offsets(ctx, L->w4, L->w4m, L->qb, L->n, L->K, L->gsize, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
   } else if (L->wbits == 4) {  // the same vectors from the nibbles, in one launch
-    I8IE_TRY(i8ie_w4_launch_offsets(ctx, L->w4, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf, L->conv));
+    const bool geom = L->conv && !w4_pointwise(L);  // (a k x k conv's panel lies in the K order of i8ie_w4conv.h)
+    I8IE_TRY(i8ie_w4_launch_offsets(ctx, L->w4, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf, L->conv,
+                                    geom ? L->kh * L->kw : 1, geom ? i8ie_w4conv_cpad(L->c) : 0));
   } else if (L->sp24 != nullptr) {  // ... and from the compressed 2:4 panel
     I8IE_TRY(i8ie_sp24_launch_offsets(ctx, L->sp24, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
   } else {
@@ -546,9 +552,48 @@ static int forward_pointwise_w4(i8ie_layer* L, const ConvGeom& cg, const ConvReq
   return i8ie_w4pw_mfma_launch(ctx, c);
 }
 
+// ---- a k x k Conv2d with 4-bit weights (i8ie_conv2d_create_w4_geom): the two kernels of i8ie_w4conv.hip.
+// w4conv_mfma reads its taps from the input's border: an NHWC input whose border is smaller than the layer's padding is laid
+// into the workspace with that border first (one more launch, as forward_implicit does), a larger one is read in place.  An NCHW
+// result, an NCHW input in front of one, and everything else the MFMA kernel declines, is the direct kernel's, which reads and
+// writes what the caller has.
+static int forward_w4conv(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  I8IE_REQUIRE(q.x == nullptr, "a 4-bit conv takes u8 input");
+  I8ieW4convCall c{};
+  c.A = q.in; c.m = q.m; c.H = cg.h; c.W = cg.w; c.C = cg.c; c.ib = q.in_border;
+  c.in_nchw = q.in_nchw() ? 1 : 0; c.in_s8 = q.in_s8() ? 1 : 0;
+  c.k = cg.kh; c.stride = cg.stride; c.pad = cg.pad; c.dil = cg.dil_h; c.OH = cg.oh; c.OW = cg.ow; c.zp_in = q.zp_in;
+  c.N = L->n; c.B = L->w4; c.ep = layer_epilogue(L, q);
+  c.out = q.out; c.ob = q.out_border; c.out_nchw = q.out_nchw() ? 1 : 0; c.out_s8 = q.out_s8() ? 1 : 0;
+  // an NCHW input in front of an NHWC result (a network's first 4-bit layer behind the input quantiser) is laid out likewise
+  const bool relayout = q.in_nchw() && !q.out_nchw();
+  if (!force_fallback(ctx) && aligned16(q.in) && (relayout || (!q.in_nchw() && q.in_border < cg.pad))) {
+    I8ieW4convCall r = c;  // would the kernel take it with the layer's border?
+    r.A = nullptr; r.ib = cg.pad; r.in_nchw = 0;  // (the workspace is 256-byte aligned)
+    if (i8ie_w4conv_mfma_takes(r)) {
+      I8IE_TRY(i8ie_ws_reserve(ctx, (size_t)q.m * (cg.h + 2 * cg.pad) * (cg.w + 2 * cg.pad) * cg.c + 256));
+      uint8_t* ws = (uint8_t*)ctx->ws;
+      r.A = ws;
+      if (relayout) {  // (the border by a kernel, not a memset: c % 32 == 0 and the workspace is aligned)
+        I8IE_TRY(i8ie_launch_fill_border(ctx, ws, q.m, cg.c, cg.h, cg.w, cg.pad, q.zp_in));
+        I8IE_TRY(i8ie_launch_nchw_to_nhwc(ctx, q.in, ws, q.m, cg.c, cg.h, cg.w, cg.pad));
+      } else {
+        I8IE_TRY(i8ie_launch_reborder(ctx, q.in, ws, q.m, cg.c, cg.h, cg.w, q.in_border, cg.pad, q.in_s8() ? (q.zp_in ^ 0x80) : q.zp_in));
+      }
+      return i8ie_w4conv_mfma_launch(ctx, r);
+    }
+  }
+  if (force_fallback(ctx) || !i8ie_w4conv_mfma_takes(c)) {
+    c.ep.ocp = L->oc;  // (the definition reads the activations as they are)
+    return i8ie_w4conv_direct_launch(ctx, c);
+  }
+  return i8ie_w4conv_mfma_launch(ctx, c);
+}
+
 static int forward_conv(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
   if (L->wbits == 4) {  // (a pool, and a re-biased store behind a pool, run as launches of their own)
-    if (!q.pool()) return forward_pointwise_w4(L, cg, q);
+    if (!q.pool()) return w4_pointwise(L) ? forward_pointwise_w4(L, cg, q) : forward_w4conv(L, cg, q);
     return q.out_s8() ? peel_rebiased_output(L, cg, q) : peel_pool(L, cg, q);
   }
   const ConvPlan plan = conv_plan(L, cg, q);
@@ -834,7 +879,7 @@ int i8ie_layer_rebiased_io(const i8ie_layer* L, int m, int h, int w, int pool_k,
   ConvPlan in, out;
   ConvGeom cg;
   if (!L->conv || L->path == PATH_T || m < 1) return I8IE_OK;
-  if (L->wbits == 4) {  // (both kernels of i8ie_w4pw.hip read and store re-biased bytes; a pool runs behind a plain result)
+  if (L->wbits == 4) {  // (the kernels of i8ie_w4pw.hip and i8ie_w4conv.hip read and store re-biased bytes; a pool runs behind a plain result)
     *reads = 1;
     *stores = i8ie_is_pool(pool_k, pool_s) ? 0 : 1;
     return I8IE_OK;

@@ -16,6 +16,7 @@
 #include "i8ie_w4lin.h"
 #include "i8ie_w4glin.h"
 #include "i8ie_sp24lin.h"
+#include "i8ie_w4conv.h"
 
 namespace {
 
@@ -370,9 +371,10 @@ int i8ie_linear_create_per_channel(i8ie_ctx* ctx, const int8_t* qw_host, const i
 // handle holds that panel and the per-feature vectors -- not layer_build's qw / Bpack, so no unpacked copy reaches the device.
 // wsum / oc / oc' / the float bias come from the panel per (s_in, zp_in), in one launch of the first forward (ensure_offsets).
 // (conv: the pointwise Conv2d [n, k, 1, 1] of DESIGN.md section 8zb -- the same handle with the conv geometry of a 1 x 1 layer)
+// (geom: the k x k Conv2d of section 8zc -- k = c * ksz * ksz in reference order, the panel in the K order of i8ie_w4conv.h)
 static int w4_create(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int n, int k, bool conv,
-                     i8ie_layer** out) {
-  const char* who = conv ? "i8ie_conv2d_create_w4" : "i8ie_linear_create_w4";
+                     i8ie_layer** out, const LayerSpec* geom = nullptr) {
+  const char* who = geom ? "i8ie_conv2d_create_w4_geom" : conv ? "i8ie_conv2d_create_w4" : "i8ie_linear_create_w4";
   REQUIRE_AS(who, ctx && packed_host && qb_host && out, "null argument");
   REQUIRE_AS(who, n > 0 && k > 0, "non-positive dimension");
   REQUIRE_AS(who, k <= 65536, "4-bit Linear: at most 65536 input features (16 C must stay inside int32)");
@@ -384,10 +386,17 @@ static int w4_create(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb
   if (conv) {
     L->conv = true; L->c = k; L->kh = L->kw = 1; L->path = PATH_A;
   }
+  if (geom) {
+    L->c = geom->c; L->kh = L->kw = geom->kh; L->stride = L->stride_w = geom->stride; L->pad = L->pad_w = geom->pad;
+    L->dil = L->dil_w = geom->kh == 1 ? 1 : geom->dilation; L->dil_arg = L->dil_arg_w = geom->dilation;
+  }
   L->Kpad = round_up(k, 128);
   L->Npad = round_up(n, 128);
-  std::vector<uint8_t> panel(i8ie_w4_panel_bytes(n, k), 0);
-  i8ie_w4_pack_panel(packed_host, n, k, panel.data());
+  std::vector<uint8_t> panel(i8ie_w4_panel_bytes(n, geom ? i8ie_w4conv_kpanel(geom->c, geom->kh) : k), 0);
+  if (geom)
+    i8ie_w4conv_pack_panel(packed_host, n, geom->c, geom->kh, panel.data());
+  else
+    i8ie_w4_pack_panel(packed_host, n, k, panel.data());
   const std::vector<int32_t> zeros((size_t)L->Npad, 0);  // (padding: the quads' vector loads read it)
   int rc = upload(L, &L->w4, panel);
   if (rc == I8IE_OK) rc = i8ie_layer_buffer(L, (void**)&L->qb, (size_t)n, qb_host);
@@ -412,6 +421,18 @@ int i8ie_linear_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_
 int i8ie_conv2d_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int kc, int c,
                           i8ie_layer** out) {
   return w4_create(ctx, packed_host, qb_host, s_w_host, kc, c, true, out);
+}
+
+// A k x k Conv2d with 4-bit weights: i8ie_conv2d_create_dilated's argument rules, then the handle of
+// w4_create with the panel repacked on the host into the kernel's K order.  k = 1, stride 1, pad 0 is the pointwise layer.
+int i8ie_conv2d_create_w4_geom(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_t* qb_host, const float* s_w_host, int kc, int c,
+                               int k, int stride, int pad, int dilation, i8ie_layer** out) {
+  const LayerSpec s = dilated_spec(kc, c, k, k, stride, pad, 1, dilation);
+  I8IE_TRY(check_groups(s));
+  I8IE_TRY(check_dilation(dilation));
+  if (k == 1 && stride == 1 && pad == 0) return w4_create(ctx, packed_host, qb_host, s_w_host, kc, c, true, out);
+  I8IE_REQUIRE((long long)c * k * k <= 65536, "4-bit Conv2d: at most 65536 weights per output feature (16 C must stay inside int32)");
+  return w4_create(ctx, packed_host, qb_host, s_w_host, kc, c * k * k, true, out, &s);
 }
 
 int i8ie_layer_weight_bits(const i8ie_layer* L, int* bits) {
@@ -687,7 +708,8 @@ int i8ie_layer_padding(const i8ie_layer* L, int* pad) {
   // (a transposed layer reads no border; a dilated one needs none and accepts any: its taps are bounds-checked, and a
   // border of `pad` pixels around a small map would multiply its bytes)
   // (a rect layer, like a dilated one, needs no border and accepts any)
-  *pad = (L->conv && L->path != PATH_T && L->dil == 1 && !L->rect) ? L->pad : 0;
+  // (a 4-bit k x k layer reads its taps from a border of `pad` pixels at any dilation: w4conv_mfma has no bounds checks)
+  *pad = (L->conv && L->path != PATH_T && (L->dil == 1 || L->wbits == 4) && !L->rect) ? L->pad : 0;
   return I8IE_OK;
 }
 
@@ -978,6 +1000,21 @@ int i8ie_conv2d_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, 
   I8IE_REQUIRE(n > 0, "non-positive batch");
   i8ie_layer* L = nullptr;
   I8IE_TRY(i8ie_conv2d_create_w4(ctx, packed_host, qb_host, s_w_host, kc, c, &L));
+  L->s_out = s_out;
+  L->zp_out = zp_out;
+  const int rc = i8ie_layer_forward(L, in_dev, n, h, w, s_in, zp_in, out_dev, acc_dbg_dev);
+  i8ie_layer_destroy(L);
+  return rc;
+}
+
+// ... of a k x k conv
+int i8ie_conv2d_u8s4_geom(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w, const uint8_t* packed_host,
+                          const int8_t* qb_host, const float* s_w_host, int kc, int k, int stride, int pad, int dilation, float s_in,
+                          uint8_t zp_in, float s_out, uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev) {
+  I8IE_REQUIRE(ctx && in_dev && out_dev, "null argument");
+  I8IE_REQUIRE(n > 0, "non-positive batch");
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_conv2d_create_w4_geom(ctx, packed_host, qb_host, s_w_host, kc, c, k, stride, pad, dilation, &L));
   L->s_out = s_out;
   L->zp_out = zp_out;
   const int rc = i8ie_layer_forward(L, in_dev, n, h, w, s_in, zp_in, out_dev, acc_dbg_dev);

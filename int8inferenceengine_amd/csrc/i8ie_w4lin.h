@@ -44,7 +44,9 @@ int i8ie_w4lin_mfma_launch(i8ie_ctx* ctx, const I8ieW4Call& c);
 int i8ie_w4lin_direct_launch(i8ie_ctx* ctx, const I8ieW4Call& c);
 
 // one-off kernels of a handle: oc / wsum / oc' / the float bias for (s_in, zp_in) in the reference's accumulation order, and the
-// panel re-packed for rows in (h, w, c) order.  conv: the bias goes into oc as src/conv2d.cc:123 folds it, and biasf stays zero
+// panel re-packed for rows in (h, w, c) order.  conv: the bias goes into oc as src/conv2d.cc:123 folds it, and biasf stays zero.
+// cpad > 0: the panel of a k x k conv in the K order of i8ie_w4conv.h (taps = k * k, cpad channels per tap), walked in the
+// reference's order (c, ky, kx) -- the fp32 sum is order-free only while 255 * 8 * K < 2^24
 int i8ie_w4_launch_offsets(i8ie_ctx* ctx, const uint8_t* panel, const int8_t* qb, int n, int K, float s_in, int zp_in, int32_t* oc,
-                           int32_t* wsum, int32_t* ocp, float* biasf, bool conv = false);
+                           int32_t* wsum, int32_t* ocp, float* biasf, bool conv = false, int taps = 1, int cpad = 0);
 int i8ie_w4_launch_permute(i8ie_ctx* ctx, const uint8_t* panel, uint8_t* out, int n, int K, int c, int hw);

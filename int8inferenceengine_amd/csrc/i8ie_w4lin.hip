@@ -190,19 +190,24 @@ __global__ __launch_bounds__(256) void w4lin_direct_kernel(W4DirectArgs p) {
 
 // ---- one-off kernels of a handle --------------------------------------------------------------------------------------------
 // src/fully_connected.cc:30-38 from the nibbles: one thread per feature replays the reference's sequential fp32 accumulation
-// (k ascending), as offsets_kernel of i8ie_gemm.hip does from bytes; also the exact row sum, oc' and the float bias
+// (k ascending), as offsets_kernel of i8ie_gemm.hip does from bytes; also the exact row sum, oc' and the float bias.  cpad > 0:
+// the panel of a k x k conv (i8ie_w4conv.h) -- reference weight k = (c, tap) lies at position tap * cpad + c
 __global__ __launch_bounds__(64) void w4_offsets_kernel(const uint8_t* __restrict__ B, const int8_t* __restrict__ qb, int n, int K,
                                                         int nch, float s_in, int zp_in, int32_t* __restrict__ oc,
                                                         int32_t* __restrict__ wsum, int32_t* __restrict__ ocp,
-                                                        float* __restrict__ biasf, int conv) {
+                                                        float* __restrict__ biasf, int conv, int taps, int cpad) {
   const int j = blockIdx.x * 64 + threadIdx.x;
   if (j >= n) return;
   float t = 0.0f;
   int s = 0;
-  for (int k = 0; k < K; ++k) {
-    const int q = i8ie_w4_get(B, j, k, nch);
+  for (int k = 0, c = 0, tap = 0; k < K; ++k) {
+    const int q = i8ie_w4_get(B, j, cpad > 0 ? tap * cpad + c : k, nch);
     t = t + (float)(zp_in * q);
     s += q;
+    if (++tap == taps) {
+      tap = 0;
+      ++c;
+    }
   }
   oc[j] = conv ? (int)((float)qb[j] / s_in - t) : (int)(-t);  // src/conv2d.cc:123 / src/fully_connected.cc:37
   wsum[j] = s;
@@ -300,10 +305,10 @@ int i8ie_w4lin_direct_launch(i8ie_ctx* ctx, const I8ieW4Call& c) {
 }
 
 int i8ie_w4_launch_offsets(i8ie_ctx* ctx, const uint8_t* panel, const int8_t* qb, int n, int K, float s_in, int zp_in,
-                           int32_t* oc, int32_t* wsum, int32_t* ocp, float* biasf, bool conv) {
+                           int32_t* oc, int32_t* wsum, int32_t* ocp, float* biasf, bool conv, int taps, int cpad) {
   I8ieProfScope prof(ctx, "w4_offsets", 0.0, 0.5 * n * K);
-  w4_offsets_kernel<<<(n + 63) / 64, 64, 0, ctx->stream>>>(panel, qb, n, K, i8ie_w4_chunks(K), s_in, zp_in, oc, wsum, ocp, biasf,
-                                                           conv ? 1 : 0);
+  w4_offsets_kernel<<<(n + 63) / 64, 64, 0, ctx->stream>>>(panel, qb, n, K, i8ie_w4_chunks(cpad > 0 ? taps * cpad : K), s_in, zp_in,
+                                                           oc, wsum, ocp, biasf, conv ? 1 : 0, taps, cpad);
   I8IE_LAUNCH_CHECK();
   return I8IE_OK;
 }

@@ -47,7 +47,7 @@ class Layer:
         """Start collecting output samples for calibration (reference src/layer.cc:28-35)."""
         self.layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False):
         """Quantise weights, fix the output (scale, zero_point) (reference src/layer.cc:36-54).
 
         per_channel=True (additive, not the reference's rule): one symmetric max-abs weight scale per output
@@ -64,7 +64,13 @@ class Layer:
         group_size=64, 128 or 256 (additive; i8ie.Linear with weight_bits=4 only, ValueError for every other layer class, for
         weight_bits=8, with sparsity, and for any other value): every group of that many weights along in_features gets an
         integer multiplier in [1, 32] of the row's scale / 32, so a group of small weights keeps its sixteen levels
-        (include/i8ie_hip.h, i8ie_quantize_weight_w4g).  weight_scales() then gives the row's scale / 32."""
+        (include/i8ie_hip.h, i8ie_quantize_weight_w4g).  weight_scales() then gives the row's scale / 32.
+        spatial=True (additive; with weight_bits=4 on an i8ie.Conv2d with groups 1 whose kernel, stride, padding and dilation
+        are each an int or a pair of equal values; ValueError for every other layer, with weight_bits=8, sparsity or
+        group_size): 4-bit weights for a k x k layer, quantised on the [out, in * k * k] view of the weight.  On a pointwise
+        layer it does what the call without the keyword does."""
+        if check_spatial(self, spatial, weight_bits, sparsity, group_size):
+            return self.layer._convert_w4() if is_pointwise(self) else self.layer._convert_w4_spatial()
         sparse = check_sparsity(self, sparsity, weight_bits)
         grouped = check_group_size(self, group_size, weight_bits, sparsity)
         if check_weight_bits(self, weight_bits) == 4:
@@ -92,7 +98,7 @@ class Layer:
             self.layer.load_quantized(q_weight, q_bias, weight_scale, out_scale, out_zero_point)
 
     def weight_bits(self):
-        """4 for a Linear or a pointwise Conv2d converted or loaded with 4-bit weights, 8 for every other layer."""
+        """4 for a Linear or a Conv2d converted or loaded with 4-bit weights, 8 for every other layer."""
         ask = getattr(self.layer, "_weight_bits", None)
         return 8 if ask is None else int(ask())
 
@@ -167,6 +173,26 @@ def is_pointwise(layer):
     return tuple(g["kernel_size"]) == (1, 1) and tuple(g["stride"]) == (1, 1) and tuple(g["padding"]) == (0, 0) and layer.groups() == 1
 
 
+def is_spatial(layer):
+    """an i8ie.Conv2d that takes 4-bit weights at any kernel size: groups 1, every geometry pair of equal values"""
+    if not isinstance(layer, Conv2d):
+        return False
+    g = layer.geometry()
+    return layer.groups() == 1 and all(g[k][0] == g[k][1] for k in ("kernel_size", "stride", "padding", "dilation"))
+
+
+def check_spatial(layer, spatial, weight_bits=8, sparsity=None, group_size=None):
+    """spatial as convert() takes it: False, or True with weight_bits=4 alone on a layer of is_spatial; ValueError otherwise"""
+    if not spatial:
+        return False
+    if weight_bits != 4 or isinstance(weight_bits, bool) or sparsity is not None or group_size is not None:
+        raise ValueError("convert: spatial=True needs weight_bits=4 and neither sparsity nor group_size")
+    if not is_spatial(layer):
+        raise ValueError("convert: spatial=True is for an i8ie.Conv2d with groups 1 and equal kernel, stride, padding and dilation "
+                         "on both axes, not this %s" % type(layer).__name__)
+    return True
+
+
 def check_weight_bits(layer, weight_bits):
     """weight_bits as convert() takes it: 8, or 4 on a Linear or a pointwise Conv2d; ValueError otherwise"""
     if weight_bits not in (4, 8) or isinstance(weight_bits, bool):
@@ -232,6 +258,7 @@ class Conv2d(Layer):
         dilation_h, ox * stride_w - padding_w + kx * dilation_w), and the weight is [out, in/groups, kh, kw].  Ints and pairs of
         equal values construct exactly the layer the ints always did; geometry() gives the four pairs either way."""
         pairs = [_pair(v, n) for v, n in ((kernel_size, "kernel_size"), (stride, "stride"), (padding, "padding"), (dilation, "dilation"))]
+        self._in_channels = int(in_channels)  # (Module.convert(spatial=True) asks: the MFMA kernel wants a multiple of 32)
         if all(h == w for h, w in pairs):
             self.layer = _C.Conv2d(in_channels, out_channels, pairs[0][0], pairs[1][0], pairs[2][0], groups, pairs[3][0])
         else:
@@ -253,8 +280,9 @@ class Norm(Layer):
     zero_point) and no INT8 weights.  Module.load() takes `<attr>.weight` / `<attr>.bias`; quantized_state_dict() keeps both as
     float32 beside `<attr>.qparams`.  weight_scale, weight_scales, q_weight, q_bias and forward_debug raise RuntimeError."""
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False):
         """per_channel is accepted and ignored: there are no INT8 weights."""
+        check_spatial(self, spatial, weight_bits, sparsity, group_size)
         check_weight_bits(self, weight_bits)
         check_sparsity(self, sparsity, weight_bits)
         check_group_size(self, group_size, weight_bits, sparsity)
@@ -362,8 +390,9 @@ class BatchNorm2d(Norm):
         if not self._folded:
             self.layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False):
         """per_channel is accepted and ignored: there are no INT8 weights.  A folded BatchNorm stays as it is."""
+        check_spatial(self, spatial, weight_bits, sparsity, group_size)
         check_weight_bits(self, weight_bits)
         check_sparsity(self, sparsity, weight_bits)
         check_group_size(self, group_size, weight_bits, sparsity)
@@ -437,8 +466,9 @@ class Weightless(Layer):
     (`<attr>.qparams` only); Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values);
     load_weight, load_bias, weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False):
         """per_channel is accepted and ignored."""
+        check_spatial(self, spatial, weight_bits, sparsity, group_size)
         check_weight_bits(self, weight_bits)
         check_sparsity(self, sparsity, weight_bits)
         check_group_size(self, group_size, weight_bits, sparsity)

@@ -1,7 +1,7 @@
 """Module base class (reference i8ie/module.py:6-35)."""
 import _CXX_i8ie as _C
 
-from .layer import Attention, BatchNorm2d, Layer, Linear, Norm, PositionEmbedding, Weightless, fold_batchnorm, is_pointwise
+from .layer import Attention, BatchNorm2d, Layer, Linear, Norm, PositionEmbedding, Weightless, fold_batchnorm, is_pointwise, is_spatial
 from .tensor import Tensor
 
 # Hard-coded input quantisation of the reference (i8ie/module.py:20).
@@ -52,14 +52,17 @@ class Module:
         for _, layer in self._layers():
             layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, pointwise=False):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, pointwise=False, spatial=False):
         """per_channel=True: every layer with one weight scale per output feature (Layer.convert).  weight_bits=4: every
         Linear converts to 4-bit weights, every other layer as with 8 under the given per_channel; any value but 4 or 8 is a
         ValueError.  pointwise=True (with weight_bits=4 and neither sparsity nor group_size; anything else is a ValueError):
         every pointwise Conv2d -- kernel 1 x 1, stride 1, padding 0, groups 1 -- converts to 4-bit weights as well.  sparsity="2:4": every Linear converts to 2:4 structured-sparse 8-bit weights, every other layer as
         before; any value but None or "2:4", or weight_bits=4 with it, is a ValueError.  group_size=64, 128 or 256 (with
         weight_bits=4 and no sparsity; anything else is a ValueError): every Linear gets group-wise 4-bit scales along
-        in_features (Layer.convert), every other layer converts as before."""
+        in_features (Layer.convert), every other layer converts as before.  spatial=True (with weight_bits=4 and neither
+        sparsity nor group_size; anything else is a ValueError): every pointwise Conv2d and every Conv2d with groups 1, equal
+        geometry pairs and in_channels % 32 == 0 converts to 4-bit weights as well (Layer.convert(spatial=True)); the stem,
+        grouped, rectangular and transposed layers convert as with 8 bits."""
         if weight_bits not in (4, 8) or isinstance(weight_bits, bool):
             raise ValueError("convert: weight_bits must be 4 or 8, got %r" % (weight_bits,))
         if sparsity is not None and (not isinstance(sparsity, str) or sparsity != "2:4" or weight_bits == 4):
@@ -68,8 +71,13 @@ class Module:
             raise ValueError("convert: group_size must be None or 64, 128, 256 (with weight_bits=4), got %r" % (group_size,))
         if pointwise and (weight_bits != 4 or sparsity is not None or group_size is not None):
             raise ValueError("convert: pointwise=True needs weight_bits=4 and neither sparsity nor group_size")
+        if spatial and (weight_bits != 4 or sparsity is not None or group_size is not None):
+            raise ValueError("convert: spatial=True needs weight_bits=4 and neither sparsity nor group_size")
         for _, layer in self._layers():
             linear = isinstance(layer, Linear)
+            if spatial and not linear and (is_pointwise(layer) or (is_spatial(layer) and layer._in_channels % 32 == 0)):
+                layer.convert(per_channel, 4, spatial=True)
+                continue
             four = linear or (pointwise and is_pointwise(layer))
             layer.convert(per_channel, weight_bits if four else 8, sparsity if linear else None, group_size if linear else None)
         self.is_quant = True
@@ -116,6 +124,8 @@ class Module:
                 continue
             if layer.weight_bits() == 4:  # uint8 [out, ceil(in / 2)]: element 2i in the low nibble of byte i (i8ie_pack_w4); a conv's too
                 out[name + ".q_weight4"] = L._q_weight4()
+                if not isinstance(layer, Linear) and not is_pointwise(layer):  # a k x k conv: int32 [2], the kernel the rows were packed for
+                    out[name + ".q_weight4_kernel"] = np.array(layer.geometry()["kernel_size"], np.int32)
                 if layer.group_size() is not None:  # uint8 [out, ceil(in / group_size)] multipliers and int32 [1] (i8ie_linear_create_w4g)
                     out[name + ".q_group_scales"] = L._group_scales()
                     out[name + ".group_size"] = np.array([layer.group_size()], np.int32)
@@ -160,6 +170,15 @@ class Module:
                 bias = state.get(name + ".bias") if isinstance(layer, PositionEmbedding) and not layer.class_token else state[name + ".bias"]
                 layer.layer.load_quantized(np.asarray(state[name + ".weight"], np.float32), None if bias is None else np.asarray(bias, np.float32),
                                            float(np.float32(s_out)), int(zp_out))
+                continue
+            if name + ".q_weight4_kernel" in state:  # 4-bit k x k Conv2d
+                kernel = tuple(int(v) for v in np.asarray(state[name + ".q_weight4_kernel"]).reshape(-1))
+                if not is_spatial(layer) or kernel != tuple(layer.geometry()["kernel_size"]):
+                    raise ValueError("i8ie: load_quantized: %r carries 4-bit weights packed for kernel %r (.q_weight4_kernel), which "
+                                     "disagrees with the layer" % (name, kernel))
+                load = layer.layer._load_quantized_w4 if is_pointwise(layer) else layer.layer._load_quantized_w4_spatial
+                load(np.asarray(state[name + ".q_weight4"], np.uint8), np.asarray(state[name + ".q_bias"], np.int8),
+                     np.ascontiguousarray(state[name + ".w_scales"], np.float32), float(np.float32(s_out)), int(zp_out))
                 continue
             if name + ".q_weight4" in state:  # 4-bit Linear or pointwise Conv2d
                 if not (isinstance(layer, Linear) or is_pointwise(layer)):
