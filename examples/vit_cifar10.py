@@ -95,7 +95,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--weight-bits", type=int, choices=(4, 8), default=8,
                     help="4: qkv, proj and both MLP layers (pointwise convs) and the head as packed 4-bit weights")
+    ap.add_argument("--sparsity", choices=("2:4",), default=None,
+                    help="2:4: qkv, proj and both MLP layers (pointwise convs) and the head as 2:4 structured-sparse 8-bit weights")
     args = ap.parse_args()
+    if args.sparsity and args.weight_bits == 4:
+        ap.error("--sparsity 2:4 keeps 8-bit weights: it does not combine with --weight-bits 4")
 
     import torch  # noqa: F401  (one HIP runtime per process: torch first)
     import int8inferenceengine_amd  # noqa: F401
@@ -124,9 +128,11 @@ def main():
     model(xs[min(xs)])
     if args.weight_bits == 4:
         model.convert(weight_bits=4, pointwise=True)
+    elif args.sparsity:
+        model.convert(sparsity=args.sparsity, conv_sparsity=args.sparsity)
     else:
         model.convert()
-    int8 = evaluate("W4A8" if args.weight_bits == 4 else "INT8")
+    int8 = evaluate("W4A8" if args.weight_bits == 4 else "SP24" if args.sparsity else "INT8")
     for m, x in xs.items():
         cx.profile_start()
         for _ in range(args.steps):

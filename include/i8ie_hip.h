@@ -585,7 +585,7 @@ int i8ie_linear_create_sp24(i8ie_ctx* ctx, const int8_t* values_host, const uint
                             int k, float s_w, i8ie_layer** out);
 int i8ie_linear_create_sp24_per_channel(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* index_host,
                                         const int8_t* qb_host, int n, int k, const float* s_w_host, i8ie_layer** out);
-/* *kept_of_four = 2 for a layer of i8ie_linear_create_sp24 (2:4), 0 for every other layer (dense) */
+/* *kept_of_four = 2 for a layer of i8ie_linear_create_sp24 or i8ie_conv2d_create_sp24 (2:4), 0 for every other layer (dense) */
 int i8ie_layer_sparsity(const i8ie_layer* layer, int* kept_of_four);
 /* Stateless form (for tests): in_dev [m, k] u8 -> out_dev [m, n] u8 through a temporary handle made from the host weights;
  * per_channel != 0: s_w_host holds n scales, else one.  acc_dbg_dev: NULL, or int32 [m, n] receiving C BEFORE the float bias
@@ -651,6 +651,27 @@ int i8ie_conv2d_create_w4(i8ie_ctx* ctx, const uint8_t* packed_host, const int8_
 int i8ie_conv2d_u8s4(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w, const uint8_t* packed_host,
                      const int8_t* qb_host, const float* s_w_host, int kc, float s_in, uint8_t zp_in, float s_out,
                      uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
+
+/* ---- 2:4 structured-sparse weights for pointwise Conv2d (not in the reference) ----------------------------
+ * A 2:4 pointwise conv is the INT8 Conv2d of i8ie_conv2d_create(_per_channel) with kh = kw = 1, stride 1, padding 0 and groups 1
+ * whose weight integers, seen as [kc, c], have at most two non-zeros in every aligned group of four along c: the exact INT32
+ * sum, the offset vector with the bias folded in (src/conv2d.cc:117-124) and the requantiser are unchanged.
+ * A Conv2d [kc, c, 1, 1] from the compressed rows of i8ie_pack_2_4 on the [kc, c] view (any nibble with first < second), s8
+ * biases and the weight scale(s) -- per_channel != 0: s_w_host holds kc scales, else one -- all host pointers; c <= 65536.  The
+ * handle keeps the compressed panel of csrc/i8ie_sp24lin.hip (0.625 of the dense bytes) plus the per-feature vectors: no dense
+ * copy of the weights exists on the device.  i8ie_layer_sparsity answers 2, i8ie_layer_padding 0 and i8ie_layer_rebiased_io 1 / 1
+ * (1 / 0 with a pool, which runs as a launch of its own).  Every conv forward entry point takes the handle, in NCHW, NHWC with
+ * any border and the re-biased NHWC form at either end.  Kernels: sp24pw_mfma (v_smfmac_i32_16x16x128_i8) when c % 32 == 0,
+ * both ends are NHWC, the input is 16-byte aligned and I8IE_OPT_FORCE_FALLBACK is off (any pixel count, any kc, one launch, relu,
+ * border and re-bias folded); sp24pw_direct otherwise.  Both give the bytes (and acc_dbg the sums) of i8ie_conv2d_u8s8 on the
+ * unpacked integers. */
+int i8ie_conv2d_create_sp24(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* index_host, const int8_t* qb_host, int kc,
+                            int c, const float* s_w_host, int per_channel, i8ie_layer** out);
+/* Stateless form (for tests): in_dev NCHW [n, c, h, w] u8 -> out_dev NCHW [n, kc, h, w] u8 through a temporary handle made from
+ * the host weights; the offset vector is computed inside.  acc_dbg_dev: NULL, or int32 [n, h*w, kc] as i8ie_conv2d_u8s8 gives it. */
+int i8ie_conv2d_u8s8_sp24(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w, const int8_t* values_host,
+                          const uint8_t* index_host, const int8_t* qb_host, const float* s_w_host, int per_channel, int kc,
+                          float s_in, uint8_t zp_in, float s_out, uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev);
 
 /* ---- 4-bit weights for k x k Conv2d (W4A8; not in the reference) ---------------------------------------
  * A 4-bit k x k conv is the per-channel INT8 Conv2d of i8ie_conv2d_create_dilated_per_channel with groups 1 and kh = kw = k

@@ -109,78 +109,11 @@ class Linear : public BaseLayer {
   void convert(bool per_channel = false) {
     installing(false, [&] { BaseLayer::convert(per_channel); });
   }
-
-  // ---- 2:4 structured-sparse weights (include/i8ie_hip.h, "2:4 structured-sparse weights for Linear"): an 8-bit layer, per tensor
-  //      or per channel, whose qw_ holds the pruned dense integers on the host; the handle gets only their compressed form
-  void convert_sp24(bool per_channel) {
-    prune_ = true;  // (make_handle prunes what the quantiser left, between BaseLayer::convert's two steps)
-    try {
-      installing(true, [&] { BaseLayer::convert(per_channel); });
-    } catch (...) {
-      prune_ = false;
-      throw;
-    }
-    prune_ = false;
-  }
-  // dense integers that must be 2:4 already: nothing is pruned at load
-  void load_quantized_sp24(S8Array qw, S8Array qb, py::object w_scale, float s_out, int zp_out) {
-    if (qw.ndim() != 2 || qw.shape(0) < 1 || qw.shape(1) < 1) throw std::runtime_error("i8ie: load_quantized: weight rank mismatch");
-    std::vector<int8_t> values, index;
-    compress(reinterpret_cast<const int8_t*>(qw.data()), qw.shape(0), qw.shape(1), values, index);  // (py::value_error if not 2:4)
-    installing(true, [&] { BaseLayer::load_quantized(qw, qb, w_scale, s_out, zp_out); });
-  }
-  // the compressed form of quantized_state_dict(): q_weight24 s8 [out, K4 / 2], q_index24 u8 [out, ceil(K4 / 8)]
-  void load_compressed_sp24(S8Array values, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> index, S8Array qb,
-                            py::object w_scale, float s_out, int zp_out) {
-    const ssize_t n = wshape_[0], k = wshape_[1], groups = (k + 3) / 4;
-    if (values.ndim() != 2 || values.shape(0) != n || values.shape(1) != 2 * groups || index.ndim() != 2 || index.shape(0) != n ||
-        index.shape(1) != (groups + 1) / 2)
-      throw std::runtime_error("i8ie: Linear: load_quantized: q_weight24 must be int8 [out_features, K4 / 2] and q_index24 uint8 "
-                               "[out_features, ceil(K4 / 8)] with K4 = 4 ceil(in_features / 4)");
-    S8Array qw(std::vector<ssize_t>{n, k});
-    check(i8ie_unpack_2_4(reinterpret_cast<const int8_t*>(values.data()), index.data(), (int)n, (int)k,
-                          reinterpret_cast<int8_t*>(qw.mutable_data())));
-    installing(true, [&] { BaseLayer::load_quantized(qw, qb, w_scale, s_out, zp_out); });
-  }
-  bool sparse24() const { return sp24_; }
-  py::tuple q_weight24() const {
-    need_quantized();
-    if (!sp24_) throw std::runtime_error("i8ie: q_weight24: the layer holds dense weights (use q_weight())");
-    std::vector<int8_t> values, index;
-    compress(reinterpret_cast<const int8_t*>(qw_.data()), wshape_[0], wshape_[1], values, index);
-    const ssize_t groups = (wshape_[1] + 3) / 4;
-    py::array_t<s8_t> v(std::vector<ssize_t>{wshape_[0], 2 * groups});
-    py::array_t<uint8_t> i(std::vector<ssize_t>{wshape_[0], (groups + 1) / 2});
-    std::memcpy(v.mutable_data(), values.data(), values.size());
-    std::memcpy(i.mutable_data(), index.data(), index.size());
-    return py::make_tuple(v, i);
+  void load_compressed_sp24(S8Array values, U8Array index, S8Array qb, py::object w_scale, float s_out, int zp_out) {
+    BaseLayer::load_compressed_sp24("Linear", values, index, qb, w_scale, s_out, zp_out);
   }
 
  protected:
-  // A convert / load that installs 8-bit weights, dense or (sparse) 2:4: the layer says "2:4" only once make_handle has built that
-  // handle.  A call that leaves the layer as it was (see replacing_w4) keeps what the live handle computes with.
-  template <class F>
-  void installing(bool sparse, F&& base_call) {
-    const bool was = sp24_;
-    sp24_ = sparse;
-    made_ = false;
-    try {
-      replacing_w4(base_call);
-    } catch (...) {
-      sp24_ = was;
-      throw;
-    }
-    if (!made_) sp24_ = was;
-  }
-  // i8ie_pack_2_4 of dense rows; integers that are not 2:4 are a ValueError
-  static void compress(const int8_t* qw, ssize_t n, ssize_t k, std::vector<int8_t>& values, std::vector<int8_t>& index) {
-    const ssize_t groups = (k + 3) / 4;
-    values.assign((size_t)(n * 2 * groups), 0);
-    index.assign((size_t)(n * ((groups + 1) / 2)), 0);
-    if (i8ie_pack_2_4(qw, (int)n, (int)k, values.data(), reinterpret_cast<uint8_t*>(index.data())) != I8IE_OK)
-      throw py::value_error(std::string("i8ie: ") + i8ie_last_error());
-  }
-  bool sp24_ = false, prune_ = false, made_ = false;
   void w4_dropped() override { drop_groups(); }
   void drop_groups() {
     gsize_ = 0;
@@ -196,10 +129,8 @@ class Linear : public BaseLayer {
     i8ie_layer* l = nullptr;
     made_ = true;
     if (qw4_.empty() && sp24_) {
-      int8_t* qw = reinterpret_cast<int8_t*>(qw_.data());
-      if (prune_) check(i8ie_prune_2_4(qw, (int)n, (int)wshape_[1], qw));
       std::vector<int8_t> values, index;
-      compress(qw, n, wshape_[1], values, index);
+      compress_own(n, values, index);
       const int8_t* qb = reinterpret_cast<const int8_t*>(qb_.data());
       const uint8_t* ix = reinterpret_cast<const uint8_t*>(index.data());
       if (per_channel_)
@@ -318,10 +249,26 @@ class Conv2d : public BaseLayer {
     install_w4();
   }
   void load_quantized(S8Array qw, S8Array qb, py::object w_scale, float s_out, int zp_out) {
-    replacing_w4([&] { BaseLayer::load_quantized(qw, qb, w_scale, s_out, zp_out); });
+    installing(false, [&] { BaseLayer::load_quantized(qw, qb, w_scale, s_out, zp_out); });
   }
   void convert(bool per_channel = false) {
-    replacing_w4([&] { BaseLayer::convert(per_channel); });
+    installing(false, [&] { BaseLayer::convert(per_channel); });
+  }
+  // ---- 2:4 structured-sparse weights of a pointwise layer (include/i8ie_hip.h, "2:4 structured-sparse weights for pointwise
+  //      Conv2d"; the shared steps: BaseLayer): i8ie.Layer.convert(conv_sparsity="2:4") and Module.load_quantized check that the
+  //      layer is pointwise before they call these
+  void convert_sp24(bool per_channel) {
+    need_pointwise("2:4 weights");
+    BaseLayer::convert_sp24(per_channel);
+  }
+  void load_quantized_sp24(S8Array qw, S8Array qb, py::object w_scale, float s_out, int zp_out) {
+    need_pointwise("2:4 weights");
+    BaseLayer::load_quantized_sp24(qw, qb, w_scale, s_out, zp_out);
+  }
+  void load_compressed_sp24(S8Array values, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> index, S8Array qb,
+                            py::object w_scale, float s_out, int zp_out) {
+    need_pointwise("2:4 weights");
+    BaseLayer::load_compressed_sp24("Conv2d", values, index, qb, w_scale, s_out, zp_out);
   }
 
  protected:
@@ -331,10 +278,10 @@ class Conv2d : public BaseLayer {
     if (wshape_[1] * wshape_[2] * wshape_[3] > 65536)
       throw py::value_error("i8ie: Conv2d: 4-bit weights take at most 65536 weights per output feature");
   }
-  void need_pointwise() const {
+  void need_pointwise(const char* what = "4-bit weights") const {
     if (wshape_.size() != 4 || wshape_[2] != 1 || wshape_[3] != 1 || stride_ != 1 || stride_w_ != 1 || padding_ != 0 || padding_w_ != 0 ||
         groups_ != 1)
-      throw py::value_error("i8ie: Conv2d: 4-bit weights need a pointwise layer (kernel 1 x 1, stride 1, padding 0, groups 1)");
+      throw py::value_error(std::string("i8ie: Conv2d: ") + what + " need a pointwise layer (kernel 1 x 1, stride 1, padding 0, groups 1)");
   }
   void check_shapes() const override {
     if (wshape_.size() != 4) throw std::runtime_error("i8ie: Conv2d weight must be [out, in, kh, kw]");
@@ -347,6 +294,16 @@ class Conv2d : public BaseLayer {
   }
   i8ie_layer* make_handle(ssize_t n) override {
     i8ie_layer* l = nullptr;
+    made_ = true;
+    if (qw4_.empty() && sp24_) {  // (a pointwise layer: convert_sp24 and the two loads have checked)
+      std::vector<int8_t> values, index;
+      compress_own(n, values, index);
+      check(i8ie_conv2d_create_sp24(ctx(), values.data(), reinterpret_cast<const uint8_t*>(index.data()),
+                                    reinterpret_cast<const int8_t*>(qb_.data()), (int)n, (int)in_channels(),
+                                    per_channel_ ? w_scales_.data() : &w_scale_, per_channel_ ? 1 : 0, &l));
+      return l;
+    }
+    sp24_ = false;
     if (!qw4_.empty()) {  // (pointwise: any dilation is the undilated layer; the entry makes i8ie_conv2d_create_w4's handle then)
       check(i8ie_conv2d_create_w4_geom(ctx(), qw4_.data(), reinterpret_cast<const int8_t*>(qb_.data()), w_scales_.data(), (int)n,
                                        (int)in_channels(), (int)wshape_[2], (int)stride_, (int)padding_,
@@ -564,6 +521,18 @@ void bind_w4_spatial(py::class_<L>& c) {
            py::arg("weight_scales"), py::arg("out_scale"), py::arg("out_zero_point"));
 }
 
+// ... and the 2:4 steps of Linear and Conv2d (i8ie.Layer.convert(sparsity= / conv_sparsity=), sparsity() and the Module's save / load)
+template <typename L>
+void bind_sp24(py::class_<L>& c) {
+  c.def("_convert_sp24", &L::convert_sp24, py::arg("per_channel"))
+      .def("_load_quantized_sp24", &L::load_quantized_sp24, py::arg("q_weight"), py::arg("q_bias"), py::arg("weight_scale"),
+           py::arg("out_scale"), py::arg("out_zero_point"))
+      .def("_load_compressed_sp24", &L::load_compressed_sp24, py::arg("q_weight24"), py::arg("q_index24"), py::arg("q_bias"),
+           py::arg("weight_scale"), py::arg("out_scale"), py::arg("out_zero_point"))
+      .def("_sparse24", &L::sparse24)
+      .def("_q_weight24", &L::q_weight24);
+}
+
 template <typename L>
 void bind_layer_common(py::class_<L>& c) {
   c.def("load_weight", &L::load_weight)
@@ -597,14 +566,8 @@ void bind_layers(py::module_& m) {
         .def("_load_quantized_w4g", &Linear::load_quantized_w4g, py::arg("q_weight4"), py::arg("q_group_scales"), py::arg("group_size"),
              py::arg("q_bias"), py::arg("weight_scales"), py::arg("out_scale"), py::arg("out_zero_point"))
         .def("_group_size", &Linear::group_size)
-        .def("_group_scales", &Linear::group_scales)
-        .def("_convert_sp24", &Linear::convert_sp24, py::arg("per_channel"))
-        .def("_load_quantized_sp24", &Linear::load_quantized_sp24, py::arg("q_weight"), py::arg("q_bias"), py::arg("weight_scale"),
-             py::arg("out_scale"), py::arg("out_zero_point"))
-        .def("_load_compressed_sp24", &Linear::load_compressed_sp24, py::arg("q_weight24"), py::arg("q_index24"), py::arg("q_bias"),
-             py::arg("weight_scale"), py::arg("out_scale"), py::arg("out_zero_point"))
-        .def("_sparse24", &Linear::sparse24)
-        .def("_q_weight24", &Linear::q_weight24);
+        .def("_group_scales", &Linear::group_scales);
+    bind_sp24(c);
   }
   {
     py::class_<Conv2d> c(m, "Conv2d");  // src/conv2d.cc:144-165
@@ -619,6 +582,7 @@ void bind_layers(py::module_& m) {
     bind_layer_common(c);
     bind_w4(c);
     bind_w4_spatial(c);
+    bind_sp24(c);
   }
 
   {

@@ -109,6 +109,52 @@ class BaseLayer : public QuantState {
     std::memcpy(a.mutable_data(), qw4_.data(), qw4_.size());
     return a;
   }
+  // ---- 2:4 structured-sparse weights (include/i8ie_hip.h, "2:4 structured-sparse weights for Linear" / "... for pointwise
+  //      Conv2d"): an 8-bit layer, per tensor or per channel, whose qw_ holds the pruned dense integers [out, row_len] on the host;
+  //      the handle gets only their compressed form.  Linear and Conv2d bind these (a Conv2d checks that it is pointwise first).
+  void convert_sp24(bool per_channel) {
+    prune_ = true;  // (make_handle prunes what the quantiser left, between BaseLayer::convert's two steps)
+    try {
+      installing(true, [&] { BaseLayer::convert(per_channel); });
+    } catch (...) {
+      prune_ = false;
+      throw;
+    }
+    prune_ = false;
+  }
+  // dense integers that must be 2:4 already: nothing is pruned at load
+  void load_quantized_sp24(S8Array qw, S8Array qb, py::object w_scale, float s_out, int zp_out) {
+    if (qw.ndim() != (ssize_t)wshape_.size() || qw.size() < 1) throw std::runtime_error("i8ie: load_quantized: weight rank mismatch");
+    std::vector<int8_t> values, index;
+    compress(reinterpret_cast<const int8_t*>(qw.data()), qw.shape(0), qw.size() / qw.shape(0), values, index);  // (py::value_error if not 2:4)
+    installing(true, [&] { BaseLayer::load_quantized(qw, qb, w_scale, s_out, zp_out); });
+  }
+  // the compressed form of quantized_state_dict(): q_weight24 s8 [out, K4 / 2], q_index24 u8 [out, ceil(K4 / 8)] (`who`: the class)
+  void load_compressed_sp24(const char* who, S8Array values, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> index,
+                            S8Array qb, py::object w_scale, float s_out, int zp_out) {
+    const ssize_t n = wshape_[0], k = row_len(), groups = (k + 3) / 4;
+    if (values.ndim() != 2 || values.shape(0) != n || values.shape(1) != 2 * groups || index.ndim() != 2 || index.shape(0) != n ||
+        index.shape(1) != (groups + 1) / 2)
+      throw std::runtime_error(std::string("i8ie: ") + who + ": load_quantized: q_weight24 must be int8 [out_features, K4 / 2] and q_index24 "
+                               "uint8 [out_features, ceil(K4 / 8)] with K4 = 4 ceil(in_features / 4)");
+    S8Array qw(wshape_);
+    check(i8ie_unpack_2_4(reinterpret_cast<const int8_t*>(values.data()), index.data(), (int)n, (int)k,
+                          reinterpret_cast<int8_t*>(qw.mutable_data())));
+    installing(true, [&] { BaseLayer::load_quantized(qw, qb, w_scale, s_out, zp_out); });
+  }
+  bool sparse24() const { return sp24_; }
+  py::tuple q_weight24() const {
+    need_quantized();
+    if (!sp24_) throw std::runtime_error("i8ie: q_weight24: the layer holds dense weights (use q_weight())");
+    std::vector<int8_t> values, index;
+    compress(reinterpret_cast<const int8_t*>(qw_.data()), wshape_[0], row_len(), values, index);
+    const ssize_t groups = (row_len() + 3) / 4;
+    py::array_t<s8_t> v(std::vector<ssize_t>{wshape_[0], 2 * groups});
+    py::array_t<uint8_t> i(std::vector<ssize_t>{wshape_[0], (groups + 1) / 2});
+    std::memcpy(v.mutable_data(), values.data(), values.size());
+    std::memcpy(i.mutable_data(), index.data(), index.size());
+    return py::make_tuple(v, i);
+  }
   py::array_t<s8_t> q_bias() const {
     need_quantized();
     py::array_t<s8_t> a((ssize_t)qb_.size());
@@ -215,6 +261,36 @@ class BaseLayer : public QuantState {
     if (qw4_.empty()) w4_dropped();
   }
   virtual void w4_dropped() {}  // (what a class keeps beside the packed rows goes with them)
+  // A convert / load that installs 8-bit weights, dense or (sparse) 2:4: the layer says "2:4" only once make_handle has built that
+  // handle.  A call that leaves the layer as it was (see replacing_w4) keeps what the live handle computes with.
+  template <class F>
+  void installing(bool sparse, F&& base_call) {
+    const bool was = sp24_;
+    sp24_ = sparse;
+    made_ = false;
+    try {
+      replacing_w4(base_call);
+    } catch (...) {
+      sp24_ = was;
+      throw;
+    }
+    if (!made_) sp24_ = was;
+  }
+  // i8ie_pack_2_4 of dense rows; integers that are not 2:4 are a ValueError
+  static void compress(const int8_t* qw, ssize_t n, ssize_t k, std::vector<int8_t>& values, std::vector<int8_t>& index) {
+    const ssize_t groups = (k + 3) / 4;
+    values.assign((size_t)(n * 2 * groups), 0);
+    index.assign((size_t)(n * ((groups + 1) / 2)), 0);
+    if (i8ie_pack_2_4(qw, (int)n, (int)k, values.data(), reinterpret_cast<uint8_t*>(index.data())) != I8IE_OK)
+      throw py::value_error(std::string("i8ie: ") + i8ie_last_error());
+  }
+  // make_handle's 2:4 step: qw_ (pruned first inside convert_sp24) into its compressed rows
+  void compress_own(ssize_t n, std::vector<int8_t>& values, std::vector<int8_t>& index) {
+    int8_t* qw = reinterpret_cast<int8_t*>(qw_.data());
+    if (prune_) check(i8ie_prune_2_4(qw, (int)n, (int)row_len(), qw));
+    compress(qw, n, row_len(), values, index);
+  }
+  bool sp24_ = false, prune_ = false, made_ = false;
   virtual void check_shapes() const = 0;
   // a layer that was given its channel counts refuses a weight of another shape (Conv2d with groups: [out, in/groups, k, k])
   virtual void check_weight_shape(const std::vector<ssize_t>&, const char*) const {}

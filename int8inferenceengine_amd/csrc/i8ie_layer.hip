@@ -35,6 +35,7 @@
 #include "i8ie_w4glin.h"
 #include "i8ie_w4pw.h"
 #include "i8ie_w4conv.h"
+#include "i8ie_sp24pw.h"
 
 // a 4-bit conv handle of i8ie_conv2d_create_w4 (its kernels: i8ie_w4pw.hip), as against one of i8ie_conv2d_create_w4_geom
 static bool w4_pointwise(const i8ie_layer* L) { return L->kh == 1 && L->kw == 1 && L->stride == 1 && L->pad == 0; }
@@ -110,7 +111,9 @@ int ensure_offsets(i8ie_layer* L, float s_in, uint8_t zp_in) {
     const bool geom = L->conv && !w4_pointwise(L);  // (a k x k conv's panel lies in the K order of i8ie_w4conv.h)
     I8IE_TRY(i8ie_w4_launch_offsets(ctx, L->w4, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf, L->conv,
                                     geom ? L->kh * L->kw : 1, geom ? i8ie_w4conv_cpad(L->c) : 0));
-  } else if (L->sp24 != nullptr) {  // ... and from the compressed 2:4 panel
+  } else if (L->sp24 != nullptr && L->conv) {  // ... from the compressed 2:4 panel, the bias folded in
+    I8IE_TRY(i8ie_sp24pw_launch_offsets(ctx, L->sp24, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp));
+  } else if (L->sp24 != nullptr) {  // ... and a Linear's
     I8IE_TRY(i8ie_sp24_launch_offsets(ctx, L->sp24, L->qb, L->n, L->K, s_in, zp_in, L->oc, L->wsum, L->ocp, L->biasf));
   } else {
     I8IE_TRY(i8ie_launch_offsets(ctx, L->conv, L->qw, L->qb, L->n, L->K, s_in, zp_in, L->oc, nullptr));
@@ -261,7 +264,7 @@ struct ConvPlan { bool stem = false, pconv = false; };
 static ConvPlan conv_plan(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
   ConvPlan p;
   i8ie_ctx* ctx = L->ctx;
-  if (L->wbits == 4) return p;  // (a 4-bit pointwise conv has its own route, which folds the re-biased layouts itself)
+  if (L->wbits == 4 || L->sp24 != nullptr) return p;  // (a 4-bit or 2:4 conv has its own route, which folds the re-biased layouts itself)
   if (!L->conv || force_fallback(ctx) || !(q.acc == nullptr || aligned16(q.acc))) return p;
   if (L->path == PATH_B)
     p.stem = L->Bstem != nullptr && !ctx->pick.no_stem &&
@@ -552,6 +555,24 @@ static int forward_pointwise_w4(i8ie_layer* L, const ConvGeom& cg, const ConvReq
   return i8ie_w4pw_mfma_launch(ctx, c);
 }
 
+// ---- a pointwise Conv2d with 2:4 structured-sparse weights (i8ie_conv2d_create_sp24): the two kernels of
+// i8ie_sp24pw.hip and nothing else.  Both read and write NCHW, NHWC with any border and the re-biased form, so nothing is staged,
+// peeled or converted.
+static int forward_pointwise_sp24(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
+  i8ie_ctx* ctx = L->ctx;
+  I8IE_REQUIRE(q.x == nullptr, "a 2:4 pointwise conv takes u8 input");
+  I8ieSp24pwCall c{};
+  c.A = q.in; c.m = q.m; c.H = cg.h; c.W = cg.w; c.C = cg.c; c.ib = q.in_border;
+  c.in_nchw = q.in_nchw() ? 1 : 0; c.in_s8 = q.in_s8() ? 1 : 0;
+  c.N = L->n; c.B = L->sp24; c.ep = layer_epilogue(L, q);
+  c.out = q.out; c.ob = q.out_border; c.out_nchw = q.out_nchw() ? 1 : 0; c.out_s8 = q.out_s8() ? 1 : 0;
+  if (force_fallback(ctx) || !i8ie_sp24pw_mfma_takes(c)) {
+    c.ep.ocp = L->oc;  // (the definition reads the activations as they are)
+    return i8ie_sp24pw_direct_launch(ctx, c);
+  }
+  return i8ie_sp24pw_mfma_launch(ctx, c);
+}
+
 // ---- a k x k Conv2d with 4-bit weights (i8ie_conv2d_create_w4_geom): the two kernels of i8ie_w4conv.hip.
 // w4conv_mfma reads its taps from the input's border: an NHWC input whose border is smaller than the layer's padding is laid
 // into the workspace with that border first (one more launch, as forward_implicit does), a larger one is read in place.  An NCHW
@@ -594,6 +615,10 @@ static int forward_w4conv(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& 
 static int forward_conv(i8ie_layer* L, const ConvGeom& cg, const ConvRequest& q) {
   if (L->wbits == 4) {  // (a pool, and a re-biased store behind a pool, run as launches of their own)
     if (!q.pool()) return w4_pointwise(L) ? forward_pointwise_w4(L, cg, q) : forward_w4conv(L, cg, q);
+    return q.out_s8() ? peel_rebiased_output(L, cg, q) : peel_pool(L, cg, q);
+  }
+  if (L->sp24 != nullptr) {  // (likewise)
+    if (!q.pool()) return forward_pointwise_sp24(L, cg, q);
     return q.out_s8() ? peel_rebiased_output(L, cg, q) : peel_pool(L, cg, q);
   }
   const ConvPlan plan = conv_plan(L, cg, q);
@@ -879,7 +904,7 @@ int i8ie_layer_rebiased_io(const i8ie_layer* L, int m, int h, int w, int pool_k,
   ConvPlan in, out;
   ConvGeom cg;
   if (!L->conv || L->path == PATH_T || m < 1) return I8IE_OK;
-  if (L->wbits == 4) {  // (the kernels of i8ie_w4pw.hip and i8ie_w4conv.hip read and store re-biased bytes; a pool runs behind a plain result)
+  if (L->wbits == 4 || L->sp24 != nullptr) {  // (the kernels of i8ie_w4pw.hip, i8ie_w4conv.hip and i8ie_sp24pw.hip read and store re-biased bytes; a pool runs behind a plain result)
     *reads = 1;
     *stores = i8ie_is_pool(pool_k, pool_s) ? 0 : 1;
     return I8IE_OK;

@@ -494,7 +494,7 @@ int i8ie_layer_group_size(const i8ie_layer* L, int* group_size) {
 // the host, and the handle holds that panel and the per-feature vectors -- not layer_build's qw / Bpack, so no dense copy reaches
 // the device.  wsum / oc / oc' / the float bias come from the panel per (s_in, zp_in), in one launch of the first forward.
 static int sp24_create(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* index_host, const int8_t* qb_host, int n, int k,
-                       float s_w, const float* s_w_pc, i8ie_layer** out) {
+                       float s_w, const float* s_w_pc, i8ie_layer** out, bool conv = false) {
   I8IE_REQUIRE(ctx && values_host && index_host && qb_host && out, "null argument");
   I8IE_REQUIRE(n > 0 && k > 0, "non-positive dimension");
   I8IE_REQUIRE(k <= 65536, "2:4 Linear: at most 65536 input features");
@@ -511,6 +511,9 @@ static int sp24_create(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* 
   i8ie_layer* L = new (std::nothrow) i8ie_layer();
   if (!L) return I8IE_ERR_OOM;
   L->ctx = ctx; L->n = n; L->K = k; L->s_w = s_w_pc ? 1.0f : s_w;
+  if (conv) {  // (the pointwise Conv2d [n, k, 1, 1] of DESIGN.md section 8zd: the same handle with the geometry of a 1 x 1 layer)
+    L->conv = true; L->c = k; L->kh = L->kw = 1; L->path = PATH_A;
+  }
   L->Kpad = round_up(k, 128);
   L->Npad = round_up(n, 128);
   std::vector<uint8_t> panel(i8ie_sp24_panel_bytes(n, k), 0);
@@ -541,6 +544,16 @@ int i8ie_linear_create_sp24_per_channel(i8ie_ctx* ctx, const int8_t* values_host
   I8IE_REQUIRE(n > 0, "non-positive dimension");
   I8IE_TRY(check_scales(s_w_host, n));
   return sp24_create(ctx, values_host, index_host, qb_host, n, k, 1.0f, s_w_host, out);
+}
+
+// A pointwise Conv2d with 2:4 structured-sparse weights: sp24_create's handle on the [kc, c] view
+int i8ie_conv2d_create_sp24(i8ie_ctx* ctx, const int8_t* values_host, const uint8_t* index_host, const int8_t* qb_host, int kc, int c,
+                            const float* s_w_host, int per_channel, i8ie_layer** out) {
+  I8IE_REQUIRE(s_w_host != nullptr, "null argument");
+  I8IE_REQUIRE(kc > 0, "non-positive dimension");
+  if (!per_channel) return sp24_create(ctx, values_host, index_host, qb_host, kc, c, s_w_host[0], nullptr, out, true);
+  I8IE_TRY(check_scales(s_w_host, kc));
+  return sp24_create(ctx, values_host, index_host, qb_host, kc, c, 1.0f, s_w_host, out, true);
 }
 
 int i8ie_layer_sparsity(const i8ie_layer* L, int* kept_of_four) {
@@ -1120,6 +1133,21 @@ int i8ie_linear_u8s8_sp24(i8ie_ctx* ctx, const uint8_t* in_dev, int m, int k, co
   L->s_out = s_out;
   L->zp_out = zp_out;
   const int rc = i8ie_layer_forward(L, in_dev, m, 0, 0, s_in, zp_in, out_dev, acc_dbg_dev);
+  i8ie_layer_destroy(L);
+  return rc;
+}
+
+// ... of a pointwise conv (as i8ie_conv2d_u8s4): NCHW in, NCHW out
+int i8ie_conv2d_u8s8_sp24(i8ie_ctx* ctx, const uint8_t* in_dev, int n, int c, int h, int w, const int8_t* values_host,
+                          const uint8_t* index_host, const int8_t* qb_host, const float* s_w_host, int per_channel, int kc, float s_in,
+                          uint8_t zp_in, float s_out, uint8_t zp_out, uint8_t* out_dev, int32_t* acc_dbg_dev) {
+  I8IE_REQUIRE(ctx && in_dev && out_dev, "null argument");
+  I8IE_REQUIRE(n > 0, "non-positive batch");
+  i8ie_layer* L = nullptr;
+  I8IE_TRY(i8ie_conv2d_create_sp24(ctx, values_host, index_host, qb_host, kc, c, s_w_host, per_channel, &L));
+  L->s_out = s_out;
+  L->zp_out = zp_out;
+  const int rc = i8ie_layer_forward(L, in_dev, n, h, w, s_in, zp_in, out_dev, acc_dbg_dev);
   i8ie_layer_destroy(L);
   return rc;
 }

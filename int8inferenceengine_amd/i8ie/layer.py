@@ -47,7 +47,7 @@ class Layer:
         """Start collecting output samples for calibration (reference src/layer.cc:28-35)."""
         self.layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False, conv_sparsity=None):
         """Quantise weights, fix the output (scale, zero_point) (reference src/layer.cc:36-54).
 
         per_channel=True (additive, not the reference's rule): one symmetric max-abs weight scale per output
@@ -68,7 +68,12 @@ class Layer:
         spatial=True (additive; with weight_bits=4 on an i8ie.Conv2d with groups 1 whose kernel, stride, padding and dilation
         are each an int or a pair of equal values; ValueError for every other layer, with weight_bits=8, sparsity or
         group_size): 4-bit weights for a k x k layer, quantised on the [out, in * k * k] view of the weight.  On a pointwise
-        layer it does what the call without the keyword does."""
+        layer it does what the call without the keyword does.
+        conv_sparsity="2:4" (additive; a pointwise i8ie.Conv2d with weight_bits=8, sparsity=None, group_size=None and
+        spatial=False only, under either per_channel; ValueError for every other layer, value or combination): quantise as
+        per_channel says, then prune the [out, in] view of the weight by sparsity="2:4"'s rule along in_channels."""
+        if check_conv_sparsity(self, conv_sparsity, weight_bits, sparsity, group_size, spatial):
+            return self.layer._convert_sp24(bool(per_channel))
         if check_spatial(self, spatial, weight_bits, sparsity, group_size):
             return self.layer._convert_w4() if is_pointwise(self) else self.layer._convert_w4_spatial()
         sparse = check_sparsity(self, sparsity, weight_bits)
@@ -84,15 +89,16 @@ class Layer:
             self.layer.convert(bool(per_channel))
 
     def sparsity(self):
-        """"2:4" for a Linear converted or loaded with 2:4 structured-sparse weights, None for every other layer."""
+        """"2:4" for a Linear or a pointwise Conv2d converted or loaded with 2:4 structured-sparse weights, None for every other layer."""
         ask = getattr(self.layer, "_sparse24", None)
         return "2:4" if ask is not None and ask() else None
 
-    def load_quantized(self, q_weight, q_bias, weight_scale, out_scale, out_zero_point, sparsity=None):
+    def load_quantized(self, q_weight, q_bias, weight_scale, out_scale, out_zero_point, sparsity=None, conv_sparsity=None):
         """Restore a converted layer from dense INT8 weights (what convert() would have left behind); weight_scale is a number
         or one scale per output feature.  sparsity="2:4" (i8ie.Linear only) installs them as a 2:4 layer and raises
-        ValueError unless every aligned group of four along in_features holds at most two non-zeros: nothing is pruned here."""
-        if check_sparsity(self, sparsity, 8):
+        ValueError unless every aligned group of four along in_features holds at most two non-zeros: nothing is pruned here.
+        conv_sparsity="2:4" (a pointwise i8ie.Conv2d only, and without sparsity) does the same along in_channels."""
+        if check_conv_sparsity(self, conv_sparsity, 8, sparsity) or check_sparsity(self, sparsity, 8):
             self.layer._load_quantized_sp24(q_weight, q_bias, weight_scale, out_scale, out_zero_point)
         else:
             self.layer.load_quantized(q_weight, q_bias, weight_scale, out_scale, out_zero_point)
@@ -203,6 +209,21 @@ def check_weight_bits(layer, weight_bits):
     return weight_bits
 
 
+def check_conv_sparsity(layer, conv_sparsity, weight_bits=8, sparsity=None, group_size=None, spatial=False):
+    """conv_sparsity as convert() takes it: None, or "2:4" alone on a pointwise Conv2d with 8-bit weights; ValueError otherwise.
+    True for "2:4"."""
+    if conv_sparsity is None:
+        return False
+    if not isinstance(conv_sparsity, str) or conv_sparsity != "2:4":
+        raise ValueError("convert: conv_sparsity must be None or \"2:4\", got %r" % (conv_sparsity,))
+    if not is_pointwise(layer):
+        raise ValueError("convert: conv_sparsity=\"2:4\" is for a pointwise i8ie.Conv2d (kernel 1 x 1, stride 1, padding 0, groups 1) "
+                         "only, not this %s" % type(layer).__name__)
+    if weight_bits != 8 or isinstance(weight_bits, bool) or sparsity is not None or group_size is not None or spatial:
+        raise ValueError("convert: conv_sparsity=\"2:4\" needs weight_bits=8 and none of sparsity, group_size and spatial")
+    return True
+
+
 def check_sparsity(layer, sparsity, weight_bits=8):
     """sparsity as convert() takes it: None, or "2:4" on a Linear with 8-bit weights; ValueError otherwise.  True for "2:4"."""
     if sparsity is None:
@@ -280,8 +301,9 @@ class Norm(Layer):
     zero_point) and no INT8 weights.  Module.load() takes `<attr>.weight` / `<attr>.bias`; quantized_state_dict() keeps both as
     float32 beside `<attr>.qparams`.  weight_scale, weight_scales, q_weight, q_bias and forward_debug raise RuntimeError."""
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False, conv_sparsity=None):
         """per_channel is accepted and ignored: there are no INT8 weights."""
+        check_conv_sparsity(self, conv_sparsity, weight_bits, sparsity, group_size, spatial)
         check_spatial(self, spatial, weight_bits, sparsity, group_size)
         check_weight_bits(self, weight_bits)
         check_sparsity(self, sparsity, weight_bits)
@@ -390,8 +412,9 @@ class BatchNorm2d(Norm):
         if not self._folded:
             self.layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False, conv_sparsity=None):
         """per_channel is accepted and ignored: there are no INT8 weights.  A folded BatchNorm stays as it is."""
+        check_conv_sparsity(self, conv_sparsity, weight_bits, sparsity, group_size, spatial)
         check_spatial(self, spatial, weight_bits, sparsity, group_size)
         check_weight_bits(self, weight_bits)
         check_sparsity(self, sparsity, weight_bits)
@@ -466,8 +489,9 @@ class Weightless(Layer):
     (`<attr>.qparams` only); Module.load() ignores it.  groups() is 1 and is_per_channel() False (the neutral values);
     load_weight, load_bias, weight_scale, weight_scales and forward_debug raise RuntimeError: there are no weights."""
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, spatial=False, conv_sparsity=None):
         """per_channel is accepted and ignored."""
+        check_conv_sparsity(self, conv_sparsity, weight_bits, sparsity, group_size, spatial)
         check_spatial(self, spatial, weight_bits, sparsity, group_size)
         check_weight_bits(self, weight_bits)
         check_sparsity(self, sparsity, weight_bits)

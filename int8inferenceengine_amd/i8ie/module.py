@@ -52,7 +52,7 @@ class Module:
         for _, layer in self._layers():
             layer.prepare()
 
-    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, pointwise=False, spatial=False):
+    def convert(self, per_channel=False, weight_bits=8, sparsity=None, group_size=None, pointwise=False, spatial=False, conv_sparsity=None):
         """per_channel=True: every layer with one weight scale per output feature (Layer.convert).  weight_bits=4: every
         Linear converts to 4-bit weights, every other layer as with 8 under the given per_channel; any value but 4 or 8 is a
         ValueError.  pointwise=True (with weight_bits=4 and neither sparsity nor group_size; anything else is a ValueError):
@@ -62,7 +62,10 @@ class Module:
         in_features (Layer.convert), every other layer converts as before.  spatial=True (with weight_bits=4 and neither
         sparsity nor group_size; anything else is a ValueError): every pointwise Conv2d and every Conv2d with groups 1, equal
         geometry pairs and in_channels % 32 == 0 converts to 4-bit weights as well (Layer.convert(spatial=True)); the stem,
-        grouped, rectangular and transposed layers convert as with 8 bits."""
+        grouped, rectangular and transposed layers convert as with 8 bits.  conv_sparsity="2:4" (any other value but None, or
+        pointwise=True or spatial=True with it, is a ValueError: both claim the same layers): every pointwise Conv2d with
+        in_channels % 32 == 0 converts to 2:4 structured-sparse 8-bit weights (Layer.convert(conv_sparsity="2:4")), every other
+        layer exactly as the remaining arguments say -- sparsity="2:4", conv_sparsity="2:4" sparsifies a whole transformer."""
         if weight_bits not in (4, 8) or isinstance(weight_bits, bool):
             raise ValueError("convert: weight_bits must be 4 or 8, got %r" % (weight_bits,))
         if sparsity is not None and (not isinstance(sparsity, str) or sparsity != "2:4" or weight_bits == 4):
@@ -73,8 +76,13 @@ class Module:
             raise ValueError("convert: pointwise=True needs weight_bits=4 and neither sparsity nor group_size")
         if spatial and (weight_bits != 4 or sparsity is not None or group_size is not None):
             raise ValueError("convert: spatial=True needs weight_bits=4 and neither sparsity nor group_size")
+        if conv_sparsity is not None and (not isinstance(conv_sparsity, str) or conv_sparsity != "2:4" or pointwise or spatial):
+            raise ValueError("convert: conv_sparsity must be None or \"2:4\" (without pointwise and spatial), got %r" % (conv_sparsity,))
         for _, layer in self._layers():
             linear = isinstance(layer, Linear)
+            if conv_sparsity and is_pointwise(layer) and layer._in_channels % 32 == 0:
+                layer.convert(per_channel, conv_sparsity=conv_sparsity)
+                continue
             if spatial and not linear and (is_pointwise(layer) or (is_spatial(layer) and layer._in_channels % 32 == 0)):
                 layer.convert(per_channel, 4, spatial=True)
                 continue
@@ -200,10 +208,10 @@ class Module:
                 w_scale = np.ascontiguousarray(state[name + ".w_scales"], np.float32)
             else:
                 w_scale = float(np.float32(w_scale))
-            if name + ".q_weight24" in state:  # 2:4 Linear
-                if not isinstance(layer, Linear):
-                    raise RuntimeError("i8ie: load_quantized: %r carries 2:4 weights (.q_weight24), which only a Linear takes; "
-                                       "the layer is a %s" % (name, type(layer).__name__))
+            if name + ".q_weight24" in state:  # 2:4 Linear or pointwise Conv2d
+                if not (isinstance(layer, Linear) or is_pointwise(layer)):
+                    raise RuntimeError("i8ie: load_quantized: %r carries 2:4 weights (.q_weight24), which only a Linear or a pointwise "
+                                       "Conv2d takes; the layer is a %s" % (name, type(layer).__name__))
                 layer.layer._load_compressed_sp24(np.asarray(state[name + ".q_weight24"], np.int8), np.asarray(state[name + ".q_index24"], np.uint8),
                                                   np.asarray(state[name + ".q_bias"], np.int8), w_scale, float(np.float32(s_out)), int(zp_out))
                 continue

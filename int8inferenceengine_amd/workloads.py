@@ -918,9 +918,9 @@ def build(name):
     return SpecNet()
 
 
-def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, per_channel=False, weight_bits=8, sparsity=None, group_size=None, pointwise=False, spatial=False, calibration=None):
+def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, per_channel=False, weight_bits=8, sparsity=None, group_size=None, pointwise=False, spatial=False, conv_sparsity=None, calibration=None):
     """The reference workflow (notebook cells 'prepare -> one FP32 batch -> convert'); per_channel=True converts
-    with one weight scale per output feature, weight_bits=4 every Linear to 4-bit weights, sparsity="2:4" every Linear to 2:4 structured-sparse weights, group_size= (with weight_bits=4) every Linear to group-wise 4-bit scales, pointwise=True (with weight_bits=4) every pointwise Conv2d to 4-bit weights as well, spatial=True (with weight_bits=4) every Conv2d with groups 1, equal geometry pairs and in_channels % 32 == 0 too (Module.convert).  calibration: None for the setting in force (the reservoir
+    with one weight scale per output feature, weight_bits=4 every Linear to 4-bit weights, sparsity="2:4" every Linear to 2:4 structured-sparse weights, group_size= (with weight_bits=4) every Linear to group-wise 4-bit scales, pointwise=True (with weight_bits=4) every pointwise Conv2d to 4-bit weights as well, spatial=True (with weight_bits=4) every Conv2d with groups 1, equal geometry pairs and in_channels % 32 == 0 too, conv_sparsity="2:4" every pointwise Conv2d with in_channels % 32 == 0 to 2:4 structured-sparse weights (Module.convert).  calibration: None for the setting in force (the reservoir
     unless i8ie.set_calibration chose otherwise), or "minmax", ("percentile", p) or "mse": that histogram method around this
     call alone, the earlier setting put back afterwards, also on an exception."""
     import _CXX_i8ie as cx
@@ -937,7 +937,7 @@ def calibrated(name, state_dict=None, calib_batch=None, seed=42, calib_seed=7, p
         net.prepare()
         x = calib_batch if calib_batch is not None else synthetic_input(name, 100 if not name.startswith("alexnet") else 32, seed=99)
         net(i8ie.tensor(x))
-        net.convert(per_channel, weight_bits, sparsity, group_size, pointwise, spatial)
+        net.convert(per_channel, weight_bits, sparsity, group_size, pointwise, spatial, conv_sparsity)
     finally:
         if calibration is not None:
             i8ie.set_calibration(before["method"], before["percentile"])
